@@ -2,10 +2,23 @@
 """bench.py -- queries/sec of the VAQ ADC search path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|c2|c3|c4|c5]
+                    [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (project -> LUT build -> code scan with
 top-k -> merge [-> RCCL all-gather + merge across GPUs]) over one batch of nq
 synthetic queries that are already resident in HBM, results left in HBM.
+
+A plain run sets up, warms up, times --steps steps and prints the result line
+(`value`, `ms_per_step`, the configuration).  --dump-outputs DIR also writes what
+the last timed step returned: DIR/labels.npy (float64) and DIR/distances.npy
+(float32), nq x k; above 64 MB a fixed, seeded sample of the queries is kept and
+their indices are written to DIR/query_index.npy.  The inputs (base, training,
+queries) are the same from run to run for the same arguments.
+
+--full adds everything else the benchmark measures and checks, in the same
+process after the timed steps: per-kernel device times (`headline_kernel`), the
+`roofline` object, recall, the CPU baseline with its parity checks, and at N = 1
+on the default workload the 1B-row leg described below.
 
 Workloads (BASELINE.json configs):
   c2  SIFT-1M-shaped, d=128, 8 subspaces x 256 centroids, 10k queries, k=100
@@ -15,8 +28,8 @@ Workloads (BASELINE.json configs):
   c5  1B x 128, 16 x 256, 10k queries (the N > 1 default; --rows scales it)
 
 N = 1 (default invocation): `value` is the c2 rate.  c2's code array (8 MB) lives in
-cache and most of it is pruned unread, so its scan kernel has no HBM roofline; the
-`roofline` object is therefore measured, in the same process, on the one launch of this
+cache and most of it is pruned unread, so its scan kernel has no HBM roofline; with
+--full the `roofline` object is therefore measured, in the same process, on the one launch of this
 path that IS an HBM stream: a single pass over 1B x 16 B of encoded codes with every
 bucket visited (`roofline.workload` names it; --no-c5-leg skips it and leaves
 `roofline` to the counter-based description of the c2 kernel alone).  The same leg
@@ -35,6 +48,7 @@ Prints ONE JSON line on rank 0.
 from __future__ import annotations
 
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -56,6 +70,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline figure "
+                         "(per-kernel times, roofline, recall, CPU baseline and parity, the N = 1 1B-row leg)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the labels and distances of the last timed step to DIR/*.npy")
     ap.add_argument("--workload", default="auto", choices=["auto", "c2", "c3", "c4", "c5"])
     ap.add_argument("--rows", type=int, default=0, help="override database rows (total)")
     ap.add_argument("--nq", type=int, default=0, help="override queries per step")
@@ -81,13 +100,13 @@ def parse():
     ap.add_argument("--no-skip", action="store_true", help="visit every bucket (streaming-rate measurement)")
     ap.add_argument("--bucket-bits", type=int, default=0, help="bits of the first code that key the row buckets (0 = auto)")
     ap.add_argument("--random-codes", action="store_true", help="uniform-random codes instead of encoded vectors")
-    ap.add_argument("--no-recall", action="store_true")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
+    ap.add_argument("--no-recall", action="store_true", help="--full: skip the recall figures")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--parity-queries", type=int, default=256,
-                    help="queries of the timed result checked against the CPU oracle (N = 1, c2/c3)")
+                    help="--full: queries of the timed result checked against the CPU oracle (N = 1, c2/c3)")
     ap.add_argument("--no-c5-leg", action="store_true",
-                    help="N = 1 default run: skip the in-process 1B x 16 B roofline / scale_base leg")
+                    help="N = 1 default run with --full: skip the in-process 1B x 16 B roofline / scale_base leg")
     ap.add_argument("--c5-rows", type=int, default=1_000_000_000, help="rows of that leg (rehearsals)")
     ap.add_argument("--c5-launches", type=int, default=12)
     ap.add_argument("--c5-parity-queries", type=int, default=16,
@@ -106,11 +125,49 @@ def parse():
                          "already leave every shard close to its final thresholds -- against one more collective per step")
     ap.add_argument("--one-device", action="store_true",
                     help="rehearsal: every rank uses cuda:0 (needs --backend gloo; RCCL refuses duplicate GPUs)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+@contextlib.contextmanager
+def deterministic():
+    """Training (PCA, k-means) with torch's deterministic kernels: the k-means update sums rows into
+    their centroids with index_add_, whose default GPU kernel adds in whatever order the atomics land,
+    so centroids -- and with them codes, tables and results -- would differ in their last bits from
+    run to run.  Only the harness's training runs under it, never the timed path."""
+    prev = (torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled())
+    torch.use_deterministic_algorithms(True, warn_only=True)
+    try:
+        yield
+    finally:
+        torch.use_deterministic_algorithms(prev[0], warn_only=prev[1])
+
+
+DUMP_BYTES = 64_000_000 - 4096  # --dump-outputs: all files together, .npy headers included
+
+
+def dump_outputs(d, labels, dists):
+    """--dump-outputs: the labels (as float64, exact for int32) and distances (float32) the timed path
+    returned in its last step; past DUMP_BYTES a fixed, seeded sample of the queries, listed in
+    query_index.npy."""
+    lab = labels.cpu().numpy()
+    dis = dists.cpu().numpy()
+    nq, k = lab.shape
+    os.makedirs(d, exist_ok=True)
+    if nq * k * 12 > DUMP_BYTES:
+        keep = DUMP_BYTES // (k * 12 + 8)
+        rows = np.sort(np.random.default_rng(12345).choice(nq, keep, replace=False))
+        lab, dis = lab[rows], dis[rows]
+        np.save(os.path.join(d, "query_index.npy"), rows.astype(np.float64))
+    np.save(os.path.join(d, "labels.npy"), lab.astype(np.float64))
+    np.save(os.path.join(d, "distances.npy"), dis.astype(np.float32))
+    log(f"[dump] {lab.shape[0]} of {nq} queries x {k} written to {d}")
 
 
 def base_chunk(c, N, dev):
@@ -133,11 +190,12 @@ def build_index(bits, N, lo, hi, dev, device_index, world, rank, iters, random_c
     M = len(bits)
     n_local = hi - lo
     train = base_chunk(0, N, dev)[: min(N, 262144)]
-    eig = harness.pca_eigenvectors(train).to(dev)
-    if world > 1:
-        dist.broadcast(eig, 0)
-    tp = train @ eig
-    cents = harness.train_codebooks(tp, bits, iters=iters)
+    with deterministic():
+        eig = harness.pca_eigenvectors(train).to(dev)
+        if world > 1:
+            dist.broadcast(eig, 0)
+        tp = train @ eig
+        cents = harness.train_codebooks(tp, bits, iters=iters)
     if world > 1:
         for s in range(M):
             t = torch.from_numpy(cents[s]).to(dev)
@@ -195,7 +253,8 @@ def build_index(bits, N, lo, hi, dev, device_index, world, rank, iters, random_c
         pick = torch.randperm(n_local, generator=g)[: min(n_local, 256 * ti_T)].to(dev)
         samp = codes[pick].to(torch.int64) & 0xffff
         dec = torch.cat([torch.from_numpy(cents[s]).to(dev)[samp[:, s]] for s in range(ti_seg)], dim=1)
-        cl = harness.kmeans(dec, ti_T, iters=25, seed=harness.SEED)
+        with deterministic():
+            cl = harness.kmeans(dec, ti_T, iters=25, seed=harness.SEED)
         if world > 1:
             dist.broadcast(cl, 0)
         v.mTIClusters = cl.cpu().numpy()
@@ -422,6 +481,52 @@ def c5_leg(args, dev, device_index, k):
     return roof, scale_base
 
 
+def kernel_figures(args, info, tm, n_local, nq_local, wl, name, world):
+    """--full: `headline_kernel` and (for a streaming run) `roofline` from the per-kernel times `tm`."""
+    # SURVEY 8(d): unit = one database row scanned in one pass; bytes = ceil(sum bits / 8).  That
+    # product is HBM traffic only when every row is read and nothing is shared through cache: a
+    # single pass over a database far beyond the 256 MB Infinity Cache with bucket skipping off.
+    # Whatever else this launch was, its kernel is described by `headline_kernel`; an HBM fraction
+    # is printed for it only in that streaming case.
+    kname = scan_kernel_name(info, tm, ti=bool(args.ti), no_skip=args.no_skip)
+    passes = tm["passes"]
+    eff = float(n_local) * info["algo_code_bytes"] * nq_local / (tm["scan_ms"] * 1e-3) / 1e9 if tm["scan_ms"] > 0 else 0.0
+    streaming = (args.no_skip and passes == 1 and tm["seed_slices"] == 0 and
+                 float(n_local) * info["algo_code_bytes"] > 1e9)
+    headline_kernel = {
+        "kernel": kname, "kernel_ms": round(tm["scan_ms"], 4), "launches_timed": tm["n_searches"],
+        "queries_per_pass": tm["queries_per_pass"], "passes": passes,
+        "other_kernels_ms": {"project": round(tm["project_ms"], 4), "lut_build": round(tm["lut_ms"], 4),
+                             "threshold_seed": round(tm["seed_ms"], 4), "merge": round(tm["merge_ms"], 4)},
+        "pre_pass_note": "threshold_seed = whatever runs between the table build and the scan: the threshold pre-pass "
+                         "of streamed databases, or the ranking of the queries by cost (query_cost_kernel + "
+                         "cost_sort_kernel) where one best-first workgroup serves each query",
+        "slices": tm["slices"], "workgroups": tm["workgroups"], "lds_bytes": tm["lds_bytes"],
+        "effective_per_query_GBps": round(eff, 1),
+        "effective_note": "rows x code bytes x queries / kernel time: counts rows pruned unread and rows "
+                          "served from L2 / Infinity Cache, so it is NOT an HBM rate and may exceed the peak",
+    }
+    roofline = None
+    if streaming:
+        algo = float(n_local) * info["algo_code_bytes"] * passes
+        ach = algo / (tm["scan_ms"] * 1e-3) / 1e9
+        roofline = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                    "frac": round(ach / HBM_PEAK_GBPS, 4), "traffic": None, "workload": name + " (this run)",
+                    "kernel": kname, "kernel_ms": round(tm["scan_ms"], 4), "launches_timed": tm["n_searches"],
+                    "algorithmic_bytes_per_launch": algo}
+        tr = load_profile_json(PROFILE_ROUND + "_traffic.json").get("c5_stream")
+        if tr and tr.get("rows") == n_local and tr.get("kernel") == kname:
+            roofline["traffic"] = tr["hbm_bytes_per_launch"]
+            roofline["traffic_source"] = tr["source"]
+    else:
+        # counter-based description of a cache-resident, pruned scan (separate rocprofv3 --pmc passes
+        # of this same command: tools/profile_gpu.sh; the summary is committed under profiles/)
+        pm = load_profile_json(PROFILE_ROUND + "_bound.json").get(wl)
+        if pm and world == 1 and not args.rows and not args.nq and not args.ti and pm.get("kernel") == kname:
+            headline_kernel["bound"] = pm
+    return headline_kernel, roofline
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -468,13 +573,13 @@ def main():
         parts = [int(x) for x in args.ti.split(",")]
         ti = (parts[0], parts[1] if len(parts) > 1 else 0, args.visit)
     small = wl in ("c2", "c3")
-    want_cpu = rank == 0 and not args.no_cpu and world == 1
+    want_cpu = args.full and rank == 0 and not args.no_cpu and world == 1
     real_codes = not args.random_codes
     # replicas: every rank draws its own query batch (disjoint generator streams)
     queries = harness.sift_like(nq, D, stream=7 + (100 * rank if replicas else 0), device=dev)
     # big bases: the exact ground truth of the first queries is accumulated while the base is generated
     RECALL_Q = min(nq, 100)
-    big_gt = (not args.no_recall and real_codes and N > 4_000_000 and not replicas and mode == "rows")
+    big_gt = (args.full and not args.no_recall and real_codes and N > 4_000_000 and not replicas and mode == "rows")
     v, host_codes, cents, (ti_T, ti_seg) = build_index(
         bits, N, lo, hi, dev, local_rank, world, rank, iters=15 if small else 8,
         random_codes=args.random_codes, ti=ti, bucket_bits=args.bucket_bits,
@@ -523,8 +628,9 @@ def main():
     gathered = torch.empty((world, 2, n_pack, k), dtype=torch.int32, device=dev) if collective else None
     out_final = (torch.empty((nq, k), dtype=torch.int32, device=dev),
                  torch.empty((nq, k), dtype=torch.float32, device=dev)) if collective else None
-    # device time of the exchange step, per step: events on the stream everything is enqueued on
-    ev = [[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)] if collective else None
+    # device time of the exchange step, per step (--full): events on the stream everything is enqueued on
+    ev = ([[torch.cuda.Event(enable_timing=True) for _ in range(3)] for _ in range(args.steps)]
+          if collective and args.full else None)
 
     # rows mode: every shard finds ITS k best -- one all-reduce(MIN) of the nq thresholds between the
     # first rounds and the rest lets each shard scan only what the GLOBAL k-th distance allows
@@ -567,25 +673,29 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
-        labels, dists_ = run_step(i)
+        labels, dists_ = run_step(i if ev else -1)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    # Per-kernel device times: a SEPARATE pass of the same steps with the library's event recording on
-    # (HIP events on the launch stream around each kernel).  Not inside the timed region: the six event
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, labels, dists_)
+    # Per-kernel device times (--full): a SEPARATE pass of the same steps with the library's event recording
+    # on (HIP events on the launch stream around each kernel).  Not inside the timed region: the six event
     # records per search cost 34 us of a 0.48 ms C2 step (measured: 0.514 ms with them, 0.480 without) --
     # the timed steps above are the plain product path, `kernel_ms` below describes the same kernels.
-    v.set_option("timing", 1)
-    v.last_timing()  # reset the event ring
-    for _ in range(min(args.steps, 20)):
-        run_step()
-    torch.cuda.synchronize()
-    tm = v.last_timing()
-    v.set_option("timing", 0)
+    tm = None
+    if args.full:
+        v.set_option("timing", 1)
+        v.last_timing()  # reset the event ring
+        for _ in range(min(args.steps, 20)):
+            run_step()
+        torch.cuda.synchronize()
+        tm = v.last_timing()
+        v.set_option("timing", 0)
     exchange = None
-    if collective:
+    if collective and args.full:
         coll = float(np.mean([e[0].elapsed_time(e[1]) for e in ev]))
         mrg = float(np.mean([e[1].elapsed_time(e[2]) for e in ev]))
         stats = torch.tensor([elapsed, coll, mrg, tm["scan_ms"], float(n_local)], dtype=torch.float64, device=dev)
@@ -612,51 +722,12 @@ def main():
     qps = nq_total * args.steps / elapsed
 
     # ------------------------------------------------------------- roofline --
-    # unit = one database row scanned in one pass; bytes = ceil(sum bits / 8).  That
-    # product is HBM traffic only when every row is read and nothing is shared through cache: a
-    # single pass over a database far beyond the 256 MB Infinity Cache with bucket skipping off.
-    # Whatever else this launch was, its kernel is described by `headline_kernel`; an HBM fraction
-    # is printed for it only in that streaming case.
-    kname = scan_kernel_name(info, tm, ti=bool(args.ti), no_skip=args.no_skip)
-    passes = tm["passes"]
-    eff = float(n_local) * info["algo_code_bytes"] * nq_local / (tm["scan_ms"] * 1e-3) / 1e9 if tm["scan_ms"] > 0 else 0.0
-    streaming = (args.no_skip and passes == 1 and tm["seed_slices"] == 0 and
-                 float(n_local) * info["algo_code_bytes"] > 1e9)
-    headline_kernel = {
-        "kernel": kname, "kernel_ms": round(tm["scan_ms"], 4), "launches_timed": tm["n_searches"],
-        "queries_per_pass": tm["queries_per_pass"], "passes": passes,
-        "other_kernels_ms": {"project": round(tm["project_ms"], 4), "lut_build": round(tm["lut_ms"], 4),
-                             "threshold_seed": round(tm["seed_ms"], 4), "merge": round(tm["merge_ms"], 4)},
-        "pre_pass_note": "threshold_seed = whatever runs between the table build and the scan: the threshold pre-pass "
-                         "of streamed databases, or the ranking of the queries by cost (query_cost_kernel + "
-                         "cost_sort_kernel) where one best-first workgroup serves each query",
-        "slices": tm["slices"], "workgroups": tm["workgroups"], "lds_bytes": tm["lds_bytes"],
-        "effective_per_query_GBps": round(eff, 1),
-        "effective_note": "rows x code bytes x queries / kernel time: counts rows pruned unread and rows "
-                          "served from L2 / Infinity Cache, so it is NOT an HBM rate and may exceed the peak",
-    }
-    roofline = None
-    if streaming:
-        algo = float(n_local) * info["algo_code_bytes"] * passes
-        ach = algo / (tm["scan_ms"] * 1e-3) / 1e9
-        roofline = {"bound": "hbm", "achieved": round(ach, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                    "frac": round(ach / HBM_PEAK_GBPS, 4), "traffic": None, "workload": name + " (this run)",
-                    "kernel": kname, "kernel_ms": round(tm["scan_ms"], 4), "launches_timed": tm["n_searches"],
-                    "algorithmic_bytes_per_launch": algo}
-        tr = load_profile_json(PROFILE_ROUND + "_traffic.json").get("c5_stream")
-        if tr and tr.get("rows") == n_local and tr.get("kernel") == kname:
-            roofline["traffic"] = tr["hbm_bytes_per_launch"]
-            roofline["traffic_source"] = tr["source"]
-    else:
-        # counter-based description of a cache-resident, pruned scan (separate rocprofv3 --pmc passes
-        # of this same command: tools/profile_gpu.sh; the summary is committed under profiles/)
-        pm = load_profile_json(PROFILE_ROUND + "_bound.json").get(wl)
-        if pm and world == 1 and not args.rows and not args.nq and not args.ti and pm.get("kernel") == kname:
-            headline_kernel["bound"] = pm
+    headline_kernel, roofline = (kernel_figures(args, info, tm, n_local, nq_local, wl, name, world)
+                                 if args.full else (None, None))
 
     # --------------------------------------------------------------- recall --
     recall = None
-    if not args.no_recall and real_codes and N <= 4_000_000 and rank == 0:
+    if args.full and not args.no_recall and real_codes and N <= 4_000_000 and rank == 0:
         nq_r = min(nq, 1000)
         Xq = queries[:nq_r]
         nchunks = (N + GEN - 1) // GEN
@@ -794,23 +865,23 @@ def main():
 
     # ----------------------------------------- N = 1 default: the HBM leg --
     scale_base = None
-    if world == 1 and args.workload == "auto" and not args.no_c5_leg and not args.ti:
+    if args.full and world == 1 and args.workload == "auto" and not args.no_c5_leg and not args.ti:
         roofline, scale_base = c5_leg(args, dev, local_rank, k)
-    if roofline is None and tm.get("bucket_major"):
+    if args.full and roofline is None and tm.get("bucket_major"):
         roofline = {"bound": "latency / memory side (bucket-major rounds: a bucket's rows are streamed once per group of four "
                              "queries and meet the other groups in the XCD's L2 or the Infinity Cache; no single-pass HBM "
                              "roofline applies -- at 1B rows the step moves 442 GB at the fabric's ~6.6 TB/s, on smaller "
                              "shards the kernel waits at 4 waves per SIMD; counters under profiles/)",
                     "achieved": None, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": None, "traffic": None,
-                    "kernel": kname, "kernel_ms": round(tm["scan_ms"], 4)}
+                    "kernel": headline_kernel["kernel"], "kernel_ms": round(tm["scan_ms"], 4)}
         pm = load_profile_json(PROFILE_ROUND + "_bound.json").get("c5_bm")
         if pm and pm.get("rows") == n_local and pm.get("queries") == nq_local:
             roofline["counters"] = pm
             roofline["traffic"] = pm.get("memory_side_bytes_per_step")
-    if roofline is None:
+    if args.full and roofline is None:
         roofline = {"bound": "lds+issue (cache-resident, bucket-pruned scan: no HBM roofline applies)",
                     "achieved": None, "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": None, "traffic": None,
-                    "kernel": kname, "kernel_ms": round(tm["scan_ms"], 4)}
+                    "kernel": headline_kernel["kernel"], "kernel_ms": round(tm["scan_ms"], 4)}
 
     if rank == 0:
         out = {
@@ -831,9 +902,10 @@ def main():
                            "results stay with their owner (no data-path collective)" if replicas else
                            "rows: contiguous shards, RCCL all-gather of per-shard top-k + merge" if mode == "rows"
                            else "queries: codes replicated (fit HBM), disjoint query slices, RCCL all-gather of results")},
-            "roofline": roofline, "headline_kernel": headline_kernel, "cpu_baseline": cpu, "recall": recall,
-            "parity": parity,
         }
+        if args.full:
+            out.update({"roofline": roofline, "headline_kernel": headline_kernel, "cpu_baseline": cpu, "recall": recall,
+                        "parity": parity})
         if exchange:
             out["exchange"] = exchange
         if scale_base:

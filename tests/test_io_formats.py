@@ -1,12 +1,13 @@
 """On-disk formats against the reference's own IO code
-compiled in oracle/_ref, and the C++ adapter headers compile with plain g++."""
+compiled in oracle/_ref (or its recorded answers), and the C++ adapter headers
+compile with plain g++."""
 import ctypes as C
 import os
 import subprocess
 
 import numpy as np
-import pytest
 
+from ref_tape import RefTape
 from vaq_amd import io
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,51 +28,70 @@ def test_roundtrip(tmp_path):
     assert io.read_fvecs(str(tmp_path / "v.fvecs"), 3).shape == (3, 5)
 
 
-def test_against_reference_io(oracle, tmp_path):
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built")
-    r = oracle.ref()
+def test_against_reference_io(oracle, tmp_path, request):
+    """Files the reference writes parse here, and files written here parse in the reference
+    (live where oracle/_ref is built, else its recorded answers: tests/ref_tape.py -- there the
+    files written here must be byte for byte the ones the reference parsed when recorded)."""
+    tape = RefTape(oracle, request.node.name)
     rng = np.random.default_rng(1)
     codes = rng.integers(0, 4096, size=(321, 8)).astype(np.uint16)
+
     # reference writes, we read
-    p = str(tmp_path / "ref_cb.bin").encode()
-    r.ref_save_codebook(codes.ctypes.data_as(C.c_void_p), C.c_size_t(321), C.c_size_t(8), p)
-    assert np.array_equal(io.load_codebook(p.decode()), codes)
+    def ref_save_codebook():
+        p = str(tmp_path / "ref_cb.bin").encode()
+        oracle.ref().ref_save_codebook(codes.ctypes.data_as(C.c_void_p), C.c_size_t(321), C.c_size_t(8), p)
+        return np.fromfile(p.decode(), dtype=np.uint8)
+    p = str(tmp_path / "ref_cb.bin")
+    tape.call(ref_save_codebook, codes).tofile(p)
+    assert np.array_equal(io.load_codebook(p), codes)
+
     # we write, reference reads
     p2 = str(tmp_path / "our_cb.bin")
     io.save_codebook(codes, p2)
-    out = np.zeros_like(codes)
-    rows, cols = C.c_size_t(), C.c_size_t()
-    assert r.ref_load_codebook(p2.encode(), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.size),
-                               C.byref(rows), C.byref(cols)) == 0
-    assert (rows.value, cols.value) == (321, 8) and np.array_equal(out, codes)
+
+    def ref_load_codebook():
+        out = np.zeros_like(codes)
+        rows, cols = C.c_size_t(), C.c_size_t()
+        rc = oracle.ref().ref_load_codebook(p2.encode(), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.size),
+                                            C.byref(rows), C.byref(cols))
+        return np.array([rc, rows.value, cols.value], np.int64), out
+    meta, out = tape.call(ref_load_codebook, np.fromfile(p2, dtype=np.uint8))
+    assert meta.tolist() == [0, 321, 8] and np.array_equal(out, codes)
+
     # centroids both ways
     cents = [rng.normal(size=(1 << b, 16)).astype(np.float32) for b in (8, 10, 4, 6)]
-    arr = (C.POINTER(C.c_float) * 4)(*[c.ctypes.data_as(C.POINTER(C.c_float)) for c in cents])
-    rws = (C.c_size_t * 4)(*[c.shape[0] for c in cents])
-    cls = (C.c_size_t * 4)(*[c.shape[1] for c in cents])
+
+    def ref_save_centroids():
+        arr = (C.POINTER(C.c_float) * 4)(*[c.ctypes.data_as(C.POINTER(C.c_float)) for c in cents])
+        rws = (C.c_size_t * 4)(*[c.shape[0] for c in cents])
+        cls = (C.c_size_t * 4)(*[c.shape[1] for c in cents])
+        p3 = str(tmp_path / "ref_c.bin")
+        oracle.ref().ref_save_centroids(arr, rws, cls, C.c_size_t(4), p3.encode())
+        return np.fromfile(p3, dtype=np.uint8)
     p3 = str(tmp_path / "ref_c.bin")
-    r.ref_save_centroids(arr, rws, cls, C.c_size_t(4), p3.encode())
+    tape.call(ref_save_centroids, *cents).tofile(p3)
     back = io.load_centroids(p3)
     assert all(np.array_equal(a, b) for a, b in zip(cents, back))
     p4 = str(tmp_path / "our_c.bin")
     io.save_centroids(cents, p4)
-    flat = np.zeros(sum(c.size for c in cents), np.float32)
-    orow, ocol, nsub = (C.c_size_t * 8)(), (C.c_size_t * 8)(), C.c_size_t()
-    assert r.ref_load_centroids(p4.encode(), flat.ctypes.data_as(C.c_void_p), C.c_size_t(flat.size),
-                                orow, ocol, C.c_size_t(8), C.byref(nsub)) == 0
-    assert nsub.value == 4 and np.array_equal(flat, np.concatenate([c.ravel() for c in cents]))
+
+    def ref_load_centroids():
+        flat = np.zeros(sum(c.size for c in cents), np.float32)
+        orow, ocol, nsub = (C.c_size_t * 8)(), (C.c_size_t * 8)(), C.c_size_t()
+        rc = oracle.ref().ref_load_centroids(p4.encode(), flat.ctypes.data_as(C.c_void_p), C.c_size_t(flat.size),
+                                             orow, ocol, C.c_size_t(8), C.byref(nsub))
+        return np.array([rc, nsub.value], np.int64), flat
+    meta, flat = tape.call(ref_load_centroids, np.fromfile(p4, dtype=np.uint8))
+    assert meta.tolist() == [0, 4] and np.array_equal(flat, np.concatenate([c.ravel() for c in cents]))
 
 
 def test_reference_siftsmall_shape():
     """The query / ground-truth files the reference ships parse to the shapes
-    its demo expects (scripts/run_demos.sh: 100 queries, d=128, k=100).  Read
-    from /root/reference only when present (never on the GPU box)."""
-    q = "/root/reference/data/siftsmall/siftsmall_query.fvecs"
-    if not os.path.exists(q):
-        pytest.skip("reference data not present")
-    a = io.read_fvecs(q)
-    g = io.read_ivecs("/root/reference/data/siftsmall/siftsmall_groundtruth.ivecs")
+    its demo expects (scripts/run_demos.sh: 100 queries, d=128, k=100).  Copies
+    of the two files are kept under tests/golden/siftsmall/."""
+    d = os.path.join(ROOT, "tests", "golden", "siftsmall")
+    a = io.read_fvecs(os.path.join(d, "siftsmall_query.fvecs"))
+    g = io.read_ivecs(os.path.join(d, "siftsmall_groundtruth.ivecs"))
     assert a.shape == (100, 128) and g.shape == (100, 100)
 
 

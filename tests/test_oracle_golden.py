@@ -1,6 +1,6 @@
 """CPU tests: the oracle (oracle/vaq_oracle.c) against the committed golden
-vectors and, where oracle/_ref was built from /root/reference, against the
-reference's own code."""
+vectors and against the reference's own code (live where oracle/_ref is built,
+its recorded answers under tests/golden/ref_tape/ elsewhere: tests/ref_tape.py)."""
 import glob
 import json
 import os
@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from helpers import assert_topk_matches, make_case
+from ref_tape import RefTape
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CASES = sorted(json.load(open(os.path.join(GOLD, "manifest.json"))).keys())
@@ -45,40 +46,38 @@ def test_golden_has_boundary_ties():
     assert sum(v["boundary_tie_queries"] for v in man.values()) > 0
 
 
-def test_heap_against_reference_heap(oracle):
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built (no /root/reference here)")
+def test_heap_against_reference_heap(oracle, request):
+    tape = RefTape(oracle, request.node.name)
     rng = np.random.default_rng(7)
     for trial in range(200):
         n = int(rng.integers(1, 4000))
         k = int(rng.integers(1, 200))
         d = rng.integers(0, 12, n).astype(np.float32) if trial % 2 else rng.random(n).astype(np.float32)
         a = oracle.topk_from_dists(d, k)
-        b = oracle.ref_topk_from_dists(d, k)
+        b = tape.call(lambda: oracle.ref_topk_from_dists(d, k), d, k)
         assert np.array_equal(a[0], b[0]) and np.array_equal(a[1].view(np.uint32), b[1].view(np.uint32))
     ids = rng.permutation(5000).astype(np.int32)
     d = rng.integers(0, 30, 5000).astype(np.float32)
     a = oracle.topk_from_dists(d, 64, ids)
-    b = oracle.ref_topk_from_dists(d, 64, ids)
+    b = tape.call(lambda: oracle.ref_topk_from_dists(d, 64, ids), d, 64, ids)
     assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
 
 
-def test_lut_against_reference_primitives(oracle):
-    if not oracle.have_ref():
-        pytest.skip("oracle/_ref not built")
+def test_lut_against_reference_primitives(oracle, request):
+    tape = RefTape(oracle, request.node.name)
     rng = np.random.default_rng(11)
     for K, L in [(256, 16), (4096, 16), (16, 8), (8, 4), (64, 1), (512, 32)]:
         cent = (rng.normal(size=(K, L)) * 30).astype(np.float32)
         q = (rng.normal(size=L) * 30).astype(np.float32)
         lut = oracle.create_lut(np.tile(q, 4), [cent] * 4, int(np.log2(K)))
-        r = oracle.ref_lut_column_fma(q, cent)
+        r = tape.call(lambda: oracle.ref_lut_column_fma(q, cent), q, cent)
         assert np.array_equal(lut[2, :K].view(np.uint32), r.view(np.uint32))
     for L in [1, 2, 4, 8, 12, 16, 3, 5]:
         for K in [2, 4]:
             cent = (rng.normal(size=(K, L)) * 30).astype(np.float32)
             q = (rng.normal(size=L) * 30).astype(np.float32)
             lut = oracle.create_lut(np.tile(q, 4), [cent] * 4, 3)
-            r = oracle.ref_l2sqr_ny(q, cent)
+            r = tape.call(lambda: oracle.ref_l2sqr_ny(q, cent), q, cent)
             assert np.array_equal(lut[1, :K].view(np.uint32), r.view(np.uint32))
 
 
@@ -116,7 +115,7 @@ def test_m_not_multiple_of_4_rejected(oracle):
         oracle.search(c["X"], c["cents"], c["codes"], 5, eig=c["eig"])
 
 
-def test_recall_against_reference(oracle):
+def test_recall_against_reference(oracle, request):
     rng = np.random.default_rng(3)
     labels = rng.integers(0, 500, size=(20, 10)).astype(np.int32)
     gt = rng.integers(0, 500, size=(20, 100)).astype(np.int32)
@@ -129,14 +128,13 @@ def test_recall_against_reference(oracle):
     lab_u = np.stack([rng.permutation(500)[:10] for _ in range(20)]).astype(np.int32)
     gt_u = np.stack([rng.permutation(500)[:100] for _ in range(20)]).astype(np.int32)
     assert abs(harness.avg_recall(lab_u, gt_u) - oracle.avg_recall(lab_u, gt_u)) < 1e-12
-    if oracle.have_ref():
-        import ctypes as C
-        r = oracle.ref()
-        ra = r.ref_avg_recall(labels.ctypes.data_as(C.POINTER(C.c_int)), 20, 10,
-                              gt.ctypes.data_as(C.POINTER(C.c_int)), 100)
-        rb = r.ref_recall_at_r(labels.ctypes.data_as(C.POINTER(C.c_int)), 20, 10,
-                               gt.ctypes.data_as(C.POINTER(C.c_int)), 100)
-        assert ra == a and rb == b
+    import ctypes as C
+    tape = RefTape(oracle, request.node.name)
+    ra = tape.call(lambda: oracle.ref().ref_avg_recall(labels.ctypes.data_as(C.POINTER(C.c_int)), 20, 10,
+                                                       gt.ctypes.data_as(C.POINTER(C.c_int)), 100), labels, gt)
+    rb = tape.call(lambda: oracle.ref().ref_recall_at_r(labels.ctypes.data_as(C.POINTER(C.c_int)), 20, 10,
+                                                        gt.ctypes.data_as(C.POINTER(C.c_int)), 100), labels, gt)
+    assert ra == a and rb == b
 
 
 def test_refine_restatement(oracle):
@@ -157,13 +155,12 @@ ENC_PIN_CASES = [(128, [8] * 8), (128, [8] * 16), (128, [8] * 32), (128, [12, 10
 
 
 @pytest.mark.parametrize("D,bits", ENC_PIN_CASES, ids=[f"d{d}m{len(b)}" for d, b in ENC_PIN_CASES])
-def test_encode_against_reference_expression(oracle, D, bits):
+def test_encode_against_reference_expression(oracle, D, bits, request):
     """VAQ::encodeImpl leaves the summation order of (x - c).squaredNorm() to Eigen (VAQ.cpp:738).
     oracle/_ref compiles that very expression on the reference's matrix types with its vendored
     Eigen: the restatement's codes (sequential dist += t*t, strict <) must equal it code for code,
     including on rows planted half way between two centroids."""
-    if not oracle.have_ref():
-        pytest.skip("reference checkout not present")
+    tape = RefTape(oracle, request.node.name)
     rng = np.random.default_rng(D + len(bits))
     M = len(bits)
     L = D // M
@@ -174,22 +171,22 @@ def test_encode_against_reference_expression(oracle, D, bits):
         a, b = rng.integers(0, cents[s].shape[0], 2)
         X[i, s * L:(s + 1) * L] = (cents[s][a] + cents[s][b]) * np.float32(0.5)
         X[i + 1, s * L:(s + 1) * L] = cents[s][a]
-    assert np.array_equal(oracle.encode(X, cents, nthreads=4), oracle.ref_encode(X, cents))
+    ref_codes = tape.call(lambda: oracle.ref_encode(X, cents), X, *cents)
+    assert np.array_equal(oracle.encode(X, cents, nthreads=4), ref_codes)
 
 
-def test_project_against_reference_gemm(oracle):
+def test_project_against_reference_gemm(oracle, request):
     """VAQ::ProjectOnEigenVectors is an Eigen GEMM (VAQ.hpp:198-201): its summation order is the
     library's, not the source's.  The restatement (and the GPU kernel, which equals it bit for
     bit) uses one fmaf chain per output; against Eigen's own product of the same matrices it must
     stay within the path's float tolerance (north_star: 1e-4 relative)."""
-    if not oracle.have_ref():
-        pytest.skip("reference checkout not present")
+    tape = RefTape(oracle, request.node.name)
     rng = np.random.default_rng(11)
     q, _ = np.linalg.qr(rng.normal(size=(128, 128)))
     E = q.astype(np.float32)
     X = rng.integers(0, 256, size=(500, 128)).astype(np.float32)
     ours = oracle.project(X, E)
-    eig = oracle.ref_project(X, E)
+    eig = tape.call(lambda: oracle.ref_project(X, E), X, E)
     scale = np.abs(eig).max()
     assert np.max(np.abs(ours - eig)) <= 1e-4 * scale
     # and it is not vacuous: the two orders do differ in the last bits somewhere

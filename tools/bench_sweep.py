@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Run bench.py once per argument set and print one summary line each.
+"""Run bench.py --full once per argument set and print one summary line each.
 
     python tools/bench_sweep.py "--workload c3 --bucket-bits 8" "--workload c3 --bucket-bits 10" ...
 """
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for spec in sys.argv[1:]:
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + spec.split(), capture_output=True, text=True)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + spec.split(), capture_output=True, text=True)
     try:
         d = json.loads(r.stdout.strip().splitlines()[-1])
     except Exception:

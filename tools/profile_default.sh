@@ -1,6 +1,6 @@
 #!/bin/bash
 # tools/profile_default.sh <tag> [pmc] -- on the GPU box (via gpurun): the DEFAULT bench command
-# (`python3 bench.py --steps 20 --warmup 5`, what the driver runs) under rocprofv3:
+# (`python3 bench.py --steps 20 --warmup 5`, with --full: every leg of the benchmark) under rocprofv3:
 #   1. --kernel-trace --stats  -> gpurun_out/prof_<tag>/kernel_stats.csv + the bench line
 #   2. with `pmc`: counters of the scan kernels in their own runs (never combined with trace
 #      domains; FETCH_SIZE and WRITE_SIZE need separate passes: TCC slots)
@@ -14,7 +14,7 @@ python3 -m vaq_amd.build > /dev/null && make -s -C oracle all || exit 1
 export VAQ_NO_BUILD=1
 out=gpurun_out/prof_$tag
 mkdir -p $out
-BARGS="--steps 20 --warmup 5 ${BENCH_ARGS:-}"
+BARGS="--steps 20 --warmup 5 --full ${BENCH_ARGS:-}"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -- python3 bench.py $BARGS > $out/kt_bench.json 2> $out/kt.err || { tail -5 $out/kt.err; exit 1; }
 cp $(find $out/kt -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv
 rm -rf $out/kt  # (the raw trace of a 1B-row build is large; gpurun returns at most 64 MiB)

@@ -10,7 +10,7 @@ python3 -m vaq_amd.build > /dev/null && make -s -C oracle all || exit 1   # (no 
 export VAQ_NO_BUILD=1
 out=gpurun_out/prof_$tag
 mkdir -p $out
-BARGS="--steps 5 --warmup 2 --no-cpu --no-recall $*"
+BARGS="--steps 5 --warmup 2 --full --no-cpu --no-recall $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -- python3 bench.py $BARGS > $out/kt_bench.json 2> $out/kt.err || exit 1
 cp $(find $out/kt -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv
 rm -rf $out/kt
