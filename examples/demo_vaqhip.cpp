@@ -16,6 +16,8 @@
 //                                           search R >= k candidates, then VAQ::refine re-ranks them against the
 //                                           raw vectors; results go to <result>_R<R> when several R are given)
 //               [--devices 0,1,2,3]        (shard the rows over these GPUs: RCCL all-gather + merge)
+//               with a ...,FAST method (codes of at most 4 bits): --dataset base.fvecs [--dataset-size N]
+//               [--learn-ratio 0.05]       (demo_vaq.cpp:42, :120-124: VAQ::learnQuantization on the raw dataset)
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -37,7 +39,7 @@ int main(int argc, char **argv) {
   for (const char *req : {"centroids", "codebook", "queries"})
     if (!a.count(req)) { std::cerr << "missing --" << req << "\n"; return 2; }
   try {
-    VaqHip vaq;
+    VaqHipFast vaq;  // VaqHip plus the FAST method
     vaq.parseMethodString(a["method"]);
     vaq.mCentroidsPerSubs = loadCentroids(a["centroids"]);
     vaq.mCodebook = loadCodebook(a["codebook"]);
@@ -97,6 +99,15 @@ int main(int argc, char **argv) {
     }
     RowMatrix<int> gt;
     if (a.count("groundtruth")) gt = readIVecs(a["groundtruth"], k);
+    if (vaq.searchMethod() & VaqHip::NNMethod::Fast) {  // demo_vaq.cpp:120-124
+      if (!a.count("dataset")) throw Error(VAQHIP_EINVAL, "a FAST method learns its quantisation from --dataset <.fvecs>");
+      RowMatrixF dataset = readFVecs(a["dataset"], N, a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1, D - N);
+      const float ratio = (float)std::atof(a.count("learn-ratio") ? a["learn-ratio"].c_str() : "0.05");
+      auto t0 = std::chrono::steady_clock::now();
+      vaq.learnQuantization(dataset, ratio);
+      std::cout << "== Learn Quantization time: "
+                << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << std::endl;
+    }
     vaq.sync();
     for (const int refine : refines) {
       auto t0 = std::chrono::steady_clock::now();

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 104
+#define VAQHIP_VERSION 105
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -57,6 +57,9 @@ extern "C" {
 #define VAQHIP_METHOD_EA   0x02u
 #define VAQHIP_METHOD_TI   0x04u
 #define VAQHIP_METHOD_HEAP 0x80u
+/* VAQ::searchFast (VAQ.cpp:1778-1834): uint8 tables over codes of at most 4 bits, integer row sums,
+ * KNNFromDists' top-k; see vaqhip_index_set_lut_quantization */
+#define VAQHIP_METHOD_FAST 0x08u
 
 /* limits of this build */
 #define VAQHIP_MAX_SUBSPACES 128
@@ -147,8 +150,42 @@ int vaqhip_index_set_ti_clusters(vaqhip_index *ix, const float *clusters_rowmajo
  *     (VAQ.cpp:1583);
  *   - TI without EA returns the first k rows of the visiting order, as the
  *     reference does (its bsfKSquared stays 0, VAQ.cpp:1617-1686).
- * HEAP / EA without TI: the exhaustive scan; `visit` is ignored. */
+ * HEAP / EA without TI: the exhaustive scan; `visit` is ignored.
+ * FAST (max bits <= 4, else VAQHIP_EUNSUPPORTED; not on VAQHIP_SUM_SEQUENTIAL indexes) runs only when
+ * none of TI, EA, HEAP is set: the reference's precedence is TI > EA > HEAP > FAST (VAQ.cpp:799-834).
+ * SORT, FAST2, FAST3 are refused (VAQHIP_EUNSUPPORTED). */
 int vaqhip_index_set_method(vaqhip_index *ix, unsigned methods, float visit);
+
+/* FAST: mOffsets[M] and mScale[M] (VAQ.hpp), the affine map smallQuantize applies to every table:
+ *   q[s][c] = (uint8) min(floor(max(lut[s][c] - offsets[s], 0) * scale[s]), 255)   (Math.hpp:215-224)
+ * Non-finite values or scale <= 0: VAQHIP_EINVAL.  Setting or appending codes keeps them.
+ * With FAST in force, vaqhip_search* then answer as VAQ::searchFast does, slot for slot:
+ *   distances  float(sum_s q[s][code[s]]) -- integers, no sqrt;
+ *   labels     the k smallest rows by (dist, seq), seq = the row's position in KNNFromDists' std::sort
+ *              of rows 0..k-1 (utils/Experiment.hpp:40-56), the row itself for rows >= k; id_base + row;
+ *   N < k      unfilled slots -1 / FLT_MAX (the reference reads past its array there).
+ * Without a quantisation: VAQHIP_ESTATE.  exact_ties has no effect (FAST is slot-exact by itself);
+ * staged search and vaqhip_multi_* are VAQHIP_EUNSUPPORTED with FAST.
+ * Memory: while FAST is the method in force the index keeps a second copy of its codes in original row order
+ * (16 * ceil(M / 32) bytes per row, built at the first FAST search) and up to 1 GiB of per-search workspace;
+ * both are released when another method is set.  Indexes that never run FAST carry neither. */
+int vaqhip_index_set_lut_quantization(vaqhip_index *ix, const float *offsets, const float *scale);
+
+/* VAQ::learnQuantization(XTrain, ratio) (VAQ.cpp:1118-1187): sampleSize = int(ratio * float(n)) rows
+ * (< 1: VAQHIP_EINVAL) in randomPermutation order (utils/Random.hpp:18-28, mt19937(13517106)), their
+ * zero-padded tables, and per alpha in {.001, .002, .005, .01, .02, .05, .1} offsets = percentile(alpha),
+ * scale = 255 / percentile(1 - alpha) of the offset tables; the alpha of least quantisation loss wins
+ * (a later one on ties; the loss is summed in double, DESIGN.md "FAST").  X is n x D row-major,
+ * projected != 0: already in PCA space.  The result is set on the index and, where the pointers are
+ * not NULL, written to offsets_out[M] / scale_out[M]. */
+int vaqhip_learn_quantization(vaqhip_index *ix, const float *X_rowmajor, int64_t n, int projected,
+                              float sample_ratio, float *offsets_out, float *scale_out);
+
+/* Test hook for FAST's smallQuantize(CreateLUT(query)): out[q*M*16 + s*16 + c], uint8; entries
+ * c >= 1 << max(bits) (the reference's table has no such rows) are 0.  Needs max bits <= 4 and a
+ * quantisation (VAQHIP_EUNSUPPORTED / VAQHIP_ESTATE). */
+int vaqhip_build_small_lut(vaqhip_index *ix, const float *queries_rowmajor, int nq, int projected,
+                           uint8_t *out);
 
 /* VAQ::search (VAQ.hpp:102, VAQ.cpp:776-847), HEAP / EA semantics:
  *   queries   nq x D row-major, unprojected (projected by eigvec on the GPU)

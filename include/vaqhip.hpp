@@ -108,6 +108,7 @@ public:
 
   // VAQ::parseMethodString, VAQ.cpp:1189-1267.  HEAP, EA and TI<T>[m<seg>] are this
   // path; other search tokens throw (the reference would run a different algorithm).
+  // FAST is taken by VaqHipFast below, which has the quantisation members it needs.
   void parseMethodString(const std::string &methodString) {
     std::stringstream ss(methodString);
     std::string token;
@@ -144,7 +145,7 @@ public:
           else if (t.find("FAST2") != std::string::npos) m |= NNMethod::Fast2;
           else if (t.find("FAST") != std::string::npos) m |= NNMethod::Fast;
         }
-        if (m & ~(uint32_t)(NNMethod::Heap | NNMethod::EA | NNMethod::TI))
+        if (m & ~methodsAllowed_)
           throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: method '" + token + "' is outside the HEAP/EA/TI path");
         mMethods = m;
       }
@@ -262,7 +263,7 @@ public:
   // VAQ::search, VAQ.hpp:102 / VAQ.cpp:776-847
   template <class Mat> LabelDistVecF search(const Mat &XTest, const int k, bool verbose = false) {
     (void)verbose;
-    if (!(mMethods & (NNMethod::Heap | NNMethod::EA | NNMethod::TI)))
+    if (!(mMethods & methodsAllowed_))
       throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: only HEAP / EA / TI are implemented on this path");
     sync();
     LabelDistVecF ret;
@@ -360,6 +361,10 @@ public:
   vaqhip_index *handle() { return h_; }
   vaqhip_multi *multiHandle() { return mh_; }
 
+protected:
+  // NNMethod bits parseMethodString accepts and search() runs
+  uint32_t methodsAllowed_ = NNMethod::Heap | NNMethod::EA | NNMethod::TI;
+
 private:
   static void checkMulti(int rc) {
     if (rc < 0) throw Error(rc, std::string("vaqhip: ") + vaqhip_multi_last_error());
@@ -368,6 +373,73 @@ private:
   vaqhip_multi *mh_ = nullptr;
   bool codes_set_ = false;
   bool ti_set_ = false;
+};
+
+// ---------------------------------------------------------------------------
+// VAQ with the FAST search method (VAQ::searchFast, VAQ.cpp:1778-1834; vaqhip.h,
+// vaqhip_index_set_lut_quantization): uint8 tables over codes of at most 4 bits,
+// labels and distances as the reference returns them, slot for slot.  The extra
+// members are the reference's: mOffsets, mScale (set by learnQuantization, or by
+// hand) and mCodebookCMajor (filled by encode).  Method precedence is the
+// reference's, TI > EA > HEAP > FAST.  Single device only.
+// ---------------------------------------------------------------------------
+class VaqHipFast : public VaqHip {
+public:
+  std::vector<float> mOffsets, mScale;  // [M] each (VAQ.hpp: RowVector<float>, ColVector<float>)
+  // mCodebook as FAST reads it (VAQ.cpp:666-670, 718): uint8, column-major, rows padded to 32 with code 0;
+  // entry (row i, subspace s) at mCodebookCMajor[s * mCodebookCMajorRows + i]
+  std::vector<uint8_t> mCodebookCMajor;
+  size_t mCodebookCMajorRows = 0;
+
+  VaqHipFast() { methodsAllowed_ |= NNMethod::Fast; }
+
+  // VAQ::parseMethodString with FAST, and the reference's check after it (VAQ.cpp:1263-1266)
+  void parseMethodString(const std::string &methodString) {
+    VaqHip::parseMethodString(methodString);
+    if ((mMethods & NNMethod::Fast) && mMaxBitsPerSubs > 4)
+      throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: max bit per subs couldn't be > 4 when using FAST query method");
+  }
+
+  // VAQ::encode, plus the column-major copy
+  template <class Mat> void encode(const Mat &XTrain, bool projected = true) {
+    VaqHip::encode(XTrain, projected);
+    const size_t N = mCodebook.rows(), M = mCodebook.cols();
+    mCodebookCMajorRows = (N + 31) / 32 * 32;
+    mCodebookCMajor.assign(mCodebookCMajorRows * M, 0);
+    for (size_t i = 0; i < N; i++)
+      for (size_t s = 0; s < M; s++) mCodebookCMajor[s * mCodebookCMajorRows + i] = (uint8_t)mCodebook(i, s);
+  }
+
+  // VAQ::learnQuantization(XTrain, sampleRatio), VAQ.cpp:1118-1187: XTrain unprojected, as the reference
+  // takes it (demo_vaq.cpp:120-124 passes the dataset).  Call it after the codes are set (or encode).
+  template <class Mat> void learnQuantization(const Mat &XTrain, float sampleRatio) {
+    if ((int)XTrain.cols() != mTotalDim()) throw Error(VAQHIP_EINVAL, "vaqhip: XTrain has the wrong width");
+    sync();
+    mOffsets.assign((size_t)mHighestSubs(), 0.0f);
+    mScale.assign((size_t)mHighestSubs(), 0.0f);
+    check(vaqhip_learn_quantization(handle(), XTrain.data(), (int64_t)XTrain.rows(), 0, sampleRatio, mOffsets.data(),
+                                    mScale.data()));
+    pushedFor_ = handle();
+    pushedOffsets_ = mOffsets;
+    pushedScale_ = mScale;
+  }
+
+  // VAQ::search: pushes mOffsets / mScale when they changed, then runs the method in force
+  template <class Mat> LabelDistVecF search(const Mat &XTest, const int k, bool verbose = false) {
+    sync();
+    if (mOffsets.size() == (size_t)mHighestSubs() && mScale.size() == mOffsets.size() &&
+        (pushedFor_ != handle() || pushedOffsets_ != mOffsets || pushedScale_ != mScale)) {
+      check(vaqhip_index_set_lut_quantization(handle(), mOffsets.data(), mScale.data()));
+      pushedFor_ = handle();
+      pushedOffsets_ = mOffsets;
+      pushedScale_ = mScale;
+    }
+    return VaqHip::search(XTest, k, verbose);
+  }
+
+private:
+  const vaqhip_index *pushedFor_ = nullptr;
+  std::vector<float> pushedOffsets_, pushedScale_;
 };
 
 // ---------------------------------------------------------------------------

@@ -4,10 +4,11 @@ Product surface:
   include/vaqhip.h            C ABI (the drop-in boundary)
   include/vaqhip.hpp          C++ adapter with the reference's names (class VaqHip)
   vaq_amd.VaqHip              Python mirror of the same interface, over the C ABI
+  vaq_amd.VaqHipFast          the same with the FAST search method (uint8 tables, 4-bit codes)
 There is no CPU path: importing works anywhere, but every compute call needs
 the HIP library and a GPU and raises otherwise.
 """
 from ._lib import VaqHipError, lib_path, load  # noqa: F401
-from .index import LabelDistVec, NNMethod, VaqHip  # noqa: F401
+from .index import LabelDistVec, NNMethod, VaqHip, VaqHipFast  # noqa: F401
 
-__all__ = ["VaqHip", "NNMethod", "LabelDistVec", "VaqHipError", "load", "lib_path"]
+__all__ = ["VaqHip", "VaqHipFast", "NNMethod", "LabelDistVec", "VaqHipError", "load", "lib_path"]

@@ -16,6 +16,7 @@ SYMBOLS = [
     "vaqhip_index_create", "vaqhip_index_create_ex", "vaqhip_index_destroy", "vaqhip_index_set_codes_u16",
     "vaqhip_index_set_codes_u16_device", "vaqhip_index_add_codes_u16", "vaqhip_index_add_codes_u16_device",
     "vaqhip_index_set_ti_clusters", "vaqhip_index_set_method",
+    "vaqhip_index_set_lut_quantization", "vaqhip_learn_quantization", "vaqhip_build_small_lut",
     "vaqhip_search", "vaqhip_search_projected",
     "vaqhip_search_device", "vaqhip_search_staged_supported", "vaqhip_search_begin_device",
     "vaqhip_search_finish_device", "vaqhip_build_lut", "vaqhip_project", "vaqhip_merge_topk_device",
@@ -105,6 +106,9 @@ def load():
     L.vaqhip_index_add_codes_u16_device.argtypes = [vp, vp, i64, vp]
     L.vaqhip_index_set_ti_clusters.argtypes = [vp, vp, i32, i32]
     L.vaqhip_index_set_method.argtypes = [vp, C.c_uint, C.c_float]
+    L.vaqhip_index_set_lut_quantization.argtypes = [vp, vp, vp]
+    L.vaqhip_learn_quantization.argtypes = [vp, vp, i64, i32, C.c_float, vp, vp]
+    L.vaqhip_build_small_lut.argtypes = [vp, vp, i32, i32, vp]
     L.vaqhip_search.argtypes = [vp, vp, i32, i32, vp, vp]
     L.vaqhip_search_projected.argtypes = [vp, vp, i32, i32, vp, vp]
     L.vaqhip_search_device.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]

@@ -1,0 +1,171 @@
+// vaq_fast.h -- the FAST search method (VAQ::searchFast, VAQ.cpp:1778-1834): uint8 lookup tables
+// over codes of at most 4 bits, integer row sums, top-k by KNNFromDists (utils/Experiment.hpp:40-56).
+// DESIGN.md section "FAST" has the specification and the (dist, seq) argument.
+#ifndef VAQ_FAST_H_
+#define VAQ_FAST_H_
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace vaq {
+
+// rows of the FAST code image are padded to this (the reference pads mCodebookCMajor to 32, VAQ.cpp:666-670)
+constexpr int FAST_ROW_PAD = 32;
+// dwords per (row, lane group) of the FAST code image: code s = 4t + h sits in group h, nibble t
+__host__ __device__ inline int fast_code_words(int M) { return (M / 4 + 7) / 8; }
+
+// FAST code image: row r, group h (s % 4), dword w holds the codes of subspaces 4(8w + i) + h in nibble i.
+// Rows [row_begin, row_end) of `out` are written from codes_u16 (CodebookType rows, first = row_begin).
+hipError_t launch_fast_pack_codes(const uint16_t *codes_u16, int64_t row_begin, int64_t row_end, int M,
+                                  uint32_t *out, hipStream_t st);
+// smallQuantize (utils/Math.hpp:215-224) of the reference LUTType lut_ref[q][s][ksub] (rows >= 1 << bits[s]
+// zero, as CreateLUT leaves them): small[q][s][c] = min(floor(max(lut - off[s], 0) * scale[s]), 255) for
+// c < ksub, 0 for ksub <= c < 16
+hipError_t launch_fast_quantize(const float *lut_ref, int nq, int M, int ksub, const float *offsets,
+                                const float *scale, uint8_t *small, hipStream_t st);
+// dist[q][r] = sum_s small[q][s][code(r, s)] for rows [0, n_pad) (n_pad a multiple of FAST_ROW_PAD) as an
+// int8 GEMM on the matrix cores: A = one-hot rows, B = small - 128
+hipError_t launch_fast_scan(const uint32_t *codes, int64_t n_pad, int M, const uint8_t *small, int nq,
+                            uint16_t *dist, int n_cu, hipStream_t st);
+// KNNFromDists' std::sort of the first kk = min(k, n) rows by distance only (libstdc++ introsort, one
+// thread per query): order[q][p] = row at position p, for p < kk
+hipError_t launch_fast_head_sort(const uint16_t *dist, int64_t n_pad, int nq, int kk, uint32_t *scratch,
+                                 uint16_t *order, hipStream_t st);
+// the k smallest rows by (dist, seq) per query: seq = position in `order` for rows < kk, the row itself after.
+// Slots >= min(k, n) are -1 / FLT_MAX.
+hipError_t launch_fast_select(const uint16_t *dist, int64_t n_pad, int64_t n, int nq, int k, int M,
+                              const uint16_t *order, int64_t id_base, int32_t *labels, float *out_dist,
+                              hipStream_t st);
+
+// ---------------------------------------------------------------------------------------------------
+// libstdc++'s std::sort (bits/stl_algo.h, bits/stl_heap.h) restated over uint32 items compared by the
+// top 16 bits (the distance; the low 16 bits are the row and ride along).  The permutation std::sort
+// makes of equal keys is a function of the key sequence alone, so this reproduces it item for item.
+namespace stdsort {
+__host__ __device__ inline bool lt(uint32_t a, uint32_t b) { return (a >> 16) < (b >> 16); }
+__host__ __device__ inline void swp(uint32_t *a, uint32_t *b) { uint32_t t = *a; *a = *b; *b = t; }
+
+__host__ __device__ inline void push_heap(uint32_t *f, int hole, int top, uint32_t v) {
+  int parent = (hole - 1) / 2;
+  while (hole > top && lt(f[parent], v)) {
+    f[hole] = f[parent];
+    hole = parent;
+    parent = (hole - 1) / 2;
+  }
+  f[hole] = v;
+}
+__host__ __device__ inline void adjust_heap(uint32_t *f, int hole, int len, uint32_t v) {
+  const int top = hole;
+  int second = hole;
+  while (second < (len - 1) / 2) {
+    second = 2 * (second + 1);
+    if (lt(f[second], f[second - 1])) second--;
+    f[hole] = f[second];
+    hole = second;
+  }
+  if ((len & 1) == 0 && second == (len - 2) / 2) {
+    second = 2 * (second + 1);
+    f[hole] = f[second - 1];
+    hole = second - 1;
+  }
+  push_heap(f, hole, top, v);
+}
+// __partial_sort(first, last, last): __make_heap then __sort_heap
+__host__ __device__ inline void heap_sort(uint32_t *f, int len) {
+  if (len >= 2) {
+    for (int parent = (len - 2) / 2;; parent--) {
+      adjust_heap(f, parent, len, f[parent]);
+      if (parent == 0) break;
+    }
+  }
+  for (int last = len - 1; last > 0; last--) {
+    const uint32_t v = f[last];
+    f[last] = f[0];
+    adjust_heap(f, 0, last, v);
+  }
+}
+__host__ __device__ inline void move_median_to_first(uint32_t *r, uint32_t *a, uint32_t *b, uint32_t *c) {
+  if (lt(*a, *b)) {
+    if (lt(*b, *c)) swp(r, b);
+    else if (lt(*a, *c)) swp(r, c);
+    else swp(r, a);
+  } else if (lt(*a, *c)) swp(r, a);
+  else if (lt(*b, *c)) swp(r, c);
+  else swp(r, b);
+}
+__host__ __device__ inline int unguarded_partition_pivot(uint32_t *f, int lo, int hi) {
+  const int mid = lo + (hi - lo) / 2;
+  move_median_to_first(f + lo, f + lo + 1, f + mid, f + hi - 1);
+  int first = lo + 1, last = hi;
+  const uint32_t *pivot = f + lo;
+  while (true) {
+    while (lt(f[first], *pivot)) ++first;
+    --last;
+    while (lt(*pivot, f[last])) --last;
+    if (!(first < last)) return first;
+    swp(f + first, f + last);
+    ++first;
+  }
+}
+__host__ __device__ inline void unguarded_linear_insert(uint32_t *f, int last) {
+  const uint32_t v = f[last];
+  int next = last - 1;
+  while (lt(v, f[next])) {
+    f[last] = f[next];
+    last = next;
+    --next;
+  }
+  f[last] = v;
+}
+__host__ __device__ inline void insertion_sort(uint32_t *f, int lo, int hi) {
+  if (lo == hi) return;
+  for (int i = lo + 1; i != hi; ++i) {
+    if (lt(f[i], f[lo])) {
+      const uint32_t v = f[i];
+      for (int j = i; j > lo; --j) f[j] = f[j - 1];
+      f[lo] = v;
+    } else {
+      unguarded_linear_insert(f, i);
+    }
+  }
+}
+constexpr int THRESHOLD = 16;
+// std::__introsort_loop with its tail recursion (on the right part) made an explicit stack: the
+// depth limit bounds the stack at 2 * log2(n) frames
+__host__ __device__ inline void sort(uint32_t *f, int n) {
+  if (n <= 1) return;
+  int lg = 0;
+  while ((2 << lg) <= n) lg++;  // std::__lg(n)
+  struct Frame { int lo, hi, depth; };
+  Frame stack[2 * 11 + 2];  // n <= 1024 (VAQHIP_MAX_K): depth <= 2 * 10 frames below the root
+  int sp = 0;
+  stack[sp++] = {0, n, 2 * lg};
+  while (sp > 0) {
+    Frame fr = stack[--sp];
+    int lo = fr.lo, hi = fr.hi, depth = fr.depth;
+    // the loop body of __introsort_loop(lo, hi, depth): recurse right, continue left
+    while (hi - lo > THRESHOLD) {
+      if (depth == 0) {
+        heap_sort(f + lo, hi - lo);
+        break;
+      }
+      --depth;
+      const int cut = unguarded_partition_pivot(f, lo, hi);
+      // __introsort_loop(cut, hi, depth) runs to completion before the left part is continued;
+      // the two parts are disjoint, so finishing the left part first gives the same result
+      stack[sp++] = {cut, hi, depth};
+      hi = cut;
+    }
+  }
+  // __final_insertion_sort
+  if (n > THRESHOLD) {
+    insertion_sort(f, 0, THRESHOLD);
+    for (int i = THRESHOLD; i < n; ++i) unguarded_linear_insert(f, i);
+  } else {
+    insertion_sort(f, 0, n);
+  }
+}
+}  // namespace stdsort
+
+}  // namespace vaq
+#endif  // VAQ_FAST_H_

@@ -421,6 +421,8 @@ int vaqhip_multi_set_ti_clusters(vaqhip_multi *mx, const float *clusters, int T,
 
 int vaqhip_multi_set_method(vaqhip_multi *mx, unsigned methods, float visit) {
   if (!mx) return mfail(VAQHIP_EINVAL, "multi index is null");
+  if ((methods & VAQHIP_METHOD_FAST) && !(methods & (VAQHIP_METHOD_TI | VAQHIP_METHOD_EA | VAQHIP_METHOD_HEAP)))
+    return mfail(VAQHIP_EUNSUPPORTED, "method FAST is single-index only");
   std::lock_guard<std::mutex> lk(mx->mu);
   for (auto &s : mx->sh) {
     const int rc = vaqhip_index_set_method(s.ix, methods, visit);

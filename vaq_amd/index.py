@@ -71,7 +71,16 @@ class VaqHip:
         vaq.mEigenVectors = E                  # D x D (real part), or None
         vaq.mCodebook = codes                  # N x M uint16 (CodebookType)
         ans = vaq.search(XTest, 100)           # LabelDistVec
+
+    The FAST method (uint8 tables over codes of at most 4 bits) lives in the
+    subclass VaqHipFast: it needs members this class does not have (mOffsets,
+    mScale, learnQuantization), and VaqHip keeps refusing FAST in
+    parseMethodString so that a drop-in caller asking for it without them
+    gets an error instead of a search with no quantisation.
     """
+
+    # NNMethod bits parseMethodString accepts and search runs
+    _METHODS = NNMethod.Heap | NNMethod.EA | NNMethod.TI
 
     def __init__(self, device: int = 0, sequential_sum: bool = False):
         """sequential_sum=True: BitVecEngine::queryLUT's arithmetic (one scalar
@@ -108,7 +117,7 @@ class VaqHip:
     def parseMethodString(self, methodString: str) -> None:
         """VAQ::parseMethodString (VAQ.cpp:1189-1267).  HEAP, EA and TI<T>[m<seg>]
         select the scans on this path; the other tokens the reference accepts
-        (SORT, FAST*) are outside it and raise."""
+        (SORT, FAST*) are outside it and raise (FAST: see VaqHipFast)."""
         for token in methodString.split(","):
             if token.startswith("VAQ"):
                 m = re.match(r"VAQ(\d+)m(\d+)min(\d+)max(\d+)var([0-9.]+)", token)
@@ -149,7 +158,7 @@ class VaqHip:
                         methods |= NNMethod.Fast2
                     elif "FAST" in t:
                         methods |= NNMethod.Fast
-                unsupported = methods & ~(NNMethod.Heap | NNMethod.EA | NNMethod.TI)
+                unsupported = methods & ~self._METHODS
                 if unsupported:
                     raise _lib.VaqHipError(-2, f"search method bits 0x{unsupported:02x} in "
                                                f"'{token}' are outside the HEAP/EA/TI path")
@@ -316,7 +325,7 @@ class VaqHip:
                projected: bool = False) -> LabelDistVec:
         """VAQ::search (VAQ.cpp:776-847): flat labels / distances, ascending per
         query; squared for HEAP / EA, square roots with TI (VAQ.cpp:1583)."""
-        if not (self.mMethods & (NNMethod.Heap | NNMethod.EA | NNMethod.TI)):
+        if not (self.mMethods & self._METHODS):
             raise _lib.VaqHipError(-2, "only HEAP / EA / TI are implemented on this path")
         self._ensure_codes()
         X = np.ascontiguousarray(XTest, dtype=np.float32)
@@ -611,3 +620,115 @@ class VaqHipMulti:
             self.close()
         except Exception:
             pass
+
+
+class VaqHipFast(VaqHip):
+    """VAQ with the FAST search method (VAQ::searchFast, VAQ.cpp:1778-1834): every
+    table is quantised to uint8 by mOffsets / mScale (smallQuantize), rows are
+    summed as integers and the k best are KNNFromDists' choice, slot for slot
+    (include/vaqhip.h, vaqhip_index_set_lut_quantization).  Codes of at most 4
+    bits (mMaxBitsPerSubs <= 4).  Method precedence is the reference's:
+    TI > EA > HEAP > FAST.
+
+    Typical use (mirrors demo_vaq.cpp:120-124)::
+
+        vaq = VaqHipFast()
+        vaq.parseMethodString("VAQ256m64min4max4var1,FAST")
+        ...                                    # mBitsAlloc, mCentroidsPerSubs, mEigenVectors
+        vaq.encode(XTrainPCA)                  # mCodebook and mCodebookCMajor
+        vaq.learnQuantization(XTrain, 0.1)     # mOffsets, mScale
+        ans = vaq.search(XTest, 100)
+    """
+
+    _METHODS = VaqHip._METHODS | NNMethod.Fast
+
+    def __init__(self, device: int = 0):
+        super().__init__(device=device)
+        self.mOffsets: Optional[np.ndarray] = None  # [M] float32 (VAQ.hpp: RowVector<float>)
+        self.mScale: Optional[np.ndarray] = None    # [M] float32 (VAQ.hpp: ColVector<float>)
+        self.mCodebookCMajor: Optional[np.ndarray] = None
+        self._q_sig = None
+
+    def parseMethodString(self, methodString: str) -> None:
+        """VAQ::parseMethodString with FAST accepted, and the reference's check
+        after it (VAQ.cpp:1263-1266): FAST with mMaxBitsPerSubs > 4 is refused
+        (the reference exits; here VaqHipError EUNSUPPORTED)."""
+        super().parseMethodString(methodString)
+        if (self.mMethods & NNMethod.Fast) and self.mMaxBitsPerSubs > 4:
+            raise _lib.VaqHipError(-2, "max bit per subs couldn't be > 4 when using FAST query method "
+                                       f"(max {self.mMaxBitsPerSubs})")
+
+    # ----------------------------------------------------------- quantisation --
+    def setLUTQuantization(self, offsets, scale) -> None:
+        """mOffsets / mScale, checked as vaqhip_index_set_lut_quantization checks
+        them: M finite values each, every scale > 0."""
+        off = np.ascontiguousarray(offsets, dtype=np.float32).reshape(-1)
+        sc = np.ascontiguousarray(scale, dtype=np.float32).reshape(-1)
+        M = len(self.mBitsAlloc)
+        if M and (off.shape[0] != M or sc.shape[0] != M):
+            raise _lib.VaqHipError(-1, f"offsets {off.shape} / scale {sc.shape}: need {M} values each")
+        if off.shape != sc.shape:
+            raise _lib.VaqHipError(-1, f"offsets {off.shape} and scale {sc.shape} differ in length")
+        if not (np.all(np.isfinite(off)) and np.all(np.isfinite(sc)) and np.all(sc > 0)):
+            raise _lib.VaqHipError(-1, "offsets and scale must be finite and every scale > 0")
+        self.mOffsets = off
+        self.mScale = sc
+
+    def learnQuantization(self, XTrain: np.ndarray, sampleRatio: float, projected: bool = False) -> None:
+        """VAQ::learnQuantization (VAQ.cpp:1118-1187) on the GPU tables:
+        sets mOffsets / mScale.  XTrain is unprojected unless projected=True."""
+        X = np.ascontiguousarray(XTrain, dtype=np.float32)
+        if X.ndim != 2:
+            raise _lib.VaqHipError(-1, f"XTrain {X.shape} is not n x D")
+        if int(np.float32(sampleRatio) * np.float32(X.shape[0])) < 1:
+            raise _lib.VaqHipError(-1, f"sampleSize = int({sampleRatio} * {X.shape[0]}) < 1")
+        self._ensure_index()
+        if X.shape[1] != self.mTotalDim:
+            raise _lib.VaqHipError(-1, f"XTrain {X.shape} is not n x {self.mTotalDim}")
+        M = len(self.mBitsAlloc)
+        off = np.empty(M, np.float32)
+        sc = np.empty(M, np.float32)
+        _lib.check(_lib.load().vaqhip_learn_quantization(self._h, _ptr(X), X.shape[0], 1 if projected else 0,
+                                                         C.c_float(sampleRatio), _ptr(off), _ptr(sc)))
+        self.mOffsets, self.mScale = off, sc
+        self._q_sig = (self._h.value, _wref(off), _wref(sc))
+
+    def _ensure_quant(self):
+        if self.mOffsets is None or self.mScale is None:
+            return  # a FAST search then reports the missing quantisation (ESTATE)
+        if (self._q_sig is not None and self._q_sig[0] == self._h.value
+                and _same(self._q_sig[1], self.mOffsets) and _same(self._q_sig[2], self.mScale)):
+            return
+        self.setLUTQuantization(self.mOffsets, self.mScale)
+        _lib.check(_lib.load().vaqhip_index_set_lut_quantization(self._h, _ptr(self.mOffsets), _ptr(self.mScale)))
+        self._q_sig = (self._h.value, _wref(self.mOffsets), _wref(self.mScale))
+
+    def _ensure_codes(self):
+        super()._ensure_codes()
+        self._ensure_quant()
+
+    def close(self) -> None:
+        super().close()
+        self._q_sig = None  # a new index starts without a quantisation
+
+    # -------------------------------------------------------------- codes --
+    def encode(self, XTrain: np.ndarray, projected: bool = True) -> None:
+        """VAQ::encode; FAST also keeps the codes as mCodebookCMajor (uint8,
+        column-major, rows padded to 32 with code 0, VAQ.cpp:666-670, 718)."""
+        super().encode(XTrain, projected=projected)
+        N, M = self.mCodebook.shape
+        n_pad = (N + 31) // 32 * 32
+        cm = np.zeros((n_pad, M), np.uint8, order="F")
+        cm[:N] = self.mCodebook
+        self.mCodebookCMajor = cm
+
+    def buildSmallLUT(self, XTest: np.ndarray, projected: bool = False) -> np.ndarray:
+        """smallQuantize(CreateLUT(query)) for every query: (nq, M, 16) uint8
+        (vaqhip_build_small_lut; entries past 1 << max(bits) are 0)."""
+        self._ensure_index()
+        self._ensure_quant()
+        X = np.ascontiguousarray(XTest, dtype=np.float32)
+        out = np.empty((X.shape[0], len(self.mBitsAlloc), 16), np.uint8)
+        _lib.check(_lib.load().vaqhip_build_small_lut(self._h, _ptr(X), X.shape[0], 1 if projected else 0,
+                                                      _ptr(out)))
+        return out
