@@ -285,7 +285,25 @@ int vaqhip_merge_topk_strided_device(int device_id, const float *d_dist_lists,
  *                on that GPU (RCCL refuses duplicate devices, so the gather is then done with
  *                device-to-device copies; same buffers, same merge) -- how a one-GPU box tests
  *                the sharded path.
- * Options ("exchange": 0 auto, 1 RCCL, 2 copies; anything else is forwarded to every shard).
+ * Options ("exchange": 0 auto, 1 RCCL, 2 copies; "exact_batch" below; anything else is forwarded to
+ * every shard).
+ *   "exact_ties" = 1 holds ACROSS the shards: labels and distances are VAQ::search's over all rows,
+ *                slot for slot.  Shards are contiguous label ranges in label order (appends extend the
+ *                last one), so the reference's heap after the rows of shards 0..g is shard g's replay
+ *                started from the heap shards 0..g-1 left.  Shape of the cost: every shard scans with
+ *                k + 1 by the smallest-label rule, the exchange and merge give the global k + 1 list,
+ *                queries without equal neighbours in it are done; the tied ones take a second pass, a
+ *                chain of replays shard after shard with ONE hand-over of k * 8 bytes per tied query
+ *                per shard boundary (peer copies ordered by events, in batches of the list so that
+ *                distinct GPUs work on different batches at the same time; a shard that inherits an
+ *                already tight heap top skips most of its rows).  Calls of more than 16384 queries are
+ *                served in sets of that size.  last_merge_ms then includes the second pass.
+ *                No effect -- the result is then what each shard's own option gives, merged by
+ *                (distance, label), as on a single index where the option has no effect either --
+ *                with TI, with VAQHIP_SUM_SEQUENTIAL, with FAST (refused for a multi index anyway)
+ *                and for k == VAQHIP_MAX_K.  One shard: that shard's own replay.
+ *   "exact_batch" list entries per batch of that second pass; 0 (default) = max(64, a 16th of the
+ *                set's queries); never fewer than a 256th of them.  Results do not depend on it.
  * ------------------------------------------------------------------------- */
 #define VAQHIP_MAX_DEVICES 16
 typedef struct vaqhip_multi vaqhip_multi;
@@ -408,7 +426,10 @@ int vaqhip_index_info(const vaqhip_index *ix, vaqhip_info *out);
  *                       order (one workgroup per such query: 1M rows x 10 k queries, nine in ten of
  *                       them with ties: 0.65 -> 43 ms; about a second per tied query at 1B rows).
  *                       HEAP / EA without TI, k < 1024; labels and distances are then identical to
- *                       VAQ::search's, slot for slot.
+ *                       VAQ::search's, slot for slot.  Set on a vaqhip_multi it holds across the shards
+ *                       (the replay runs as a chain from shard to shard, see "multi-device" above); the
+ *                       staged search of one-process-per-GPU sharding (vaqhip_search_begin_device)
+ *                       stays VAQHIP_EUNSUPPORTED with the option set.
  *   "bucket_major"      1 (default): on a streamed database (> 128 MB of byte codes) with at least 8
  *                       queries in the call, the best-first pass is cut after each query's nearest
  *                       buckets and what is left in reach is scanned bucket by bucket: a bucket's

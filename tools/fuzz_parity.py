@@ -4,6 +4,8 @@ k, and scan options, each checked against the CPU oracle under the tie contract.
 
     python tools/fuzz_parity.py [seconds] [seed]
 
+Every fifth index is also searched as a multi-device index over logical shards, half
+of those with exact_ties over 2..8 shards (slot for slot against the oracle).
 Every third index is also regrouped by random triangle-inequality clusters and
 searched with TI|EA / TI at random visit fractions.  A progress line is printed
 every ~20 s (a silent GPU job is taken for hung).
@@ -22,7 +24,7 @@ only_bm = len(sys.argv) > 3 and sys.argv[3] == "bm"  # every index a byte-coded 
 rng = np.random.default_rng(seed)
 po.build(ref=False)
 t0 = time.time(); n_cases = 0; n_searches = 0; ties = 0; n_ti = 0; n_bf = 0; n_append = 0; n_multi = 0; t_print = t0
-n_bm = 0; n_exact = 0
+n_bm = 0; n_exact = 0; n_multi_exact = 0
 
 
 def visited_dists(c, ti, T, seg, visit, k, Xp):
@@ -166,6 +168,18 @@ while time.time() - t0 < budget:
             a = m.search(c["X"], k)
             ties += assert_topk_matches(a.labels.reshape(nq, k), a.distances.reshape(nq, k), o_lab, o_dis, ad,
                                         what=f"multi g={g} M={M} L={L} bits={bits} N={N} nq={nq} k={k}")
+            if k < 1024 and g >= 2 and rng.integers(0, 2) == 0:
+                # exact_ties across the logical shards (the replay as a chain): the oracle's answer slot for slot
+                m.set_option("exact_ties", 1)
+                m.set_option("exact_batch", int(rng.choice([0, 1, 2, 5])))
+                x = m.search(c["X"], k)
+                if not (np.array_equal(x.labels.reshape(nq, k), o_lab) and
+                        np.array_equal(x.distances.reshape(nq, k).view(np.uint32), o_dis.view(np.uint32))):
+                    print("MISMATCH (multi exact_ties)", g, M, L, bits, N, nq, k)
+                    bad = np.nonzero((x.labels.reshape(nq, k) != o_lab).any(axis=1))[0]
+                    print("queries", bad[:5], x.labels.reshape(nq, k)[bad[0]] if bad.size else "", o_lab[bad[0]] if bad.size else "")
+                    sys.exit(1)
+                n_searches += 1; n_multi_exact += 1
             m.close()
             n_searches += 1; n_multi += 1
         except vaq_amd.VaqHipError as e:
@@ -211,5 +225,6 @@ while time.time() - t0 < budget:
 print("unsupported (EUNSUPPORTED) cases:", globals().get("n_unsupported", 0))
 print(f"fuzz ok: {n_cases} indexes ({n_append} built by appends), {n_searches} searches ({n_bf} in the best-first form, {n_bm} with "
       f"bucket-major rounds, {n_exact} with exact_ties, "
-      f"{n_multi} on the multi-device index), {ties} boundary-tie queries, "
+      f"{n_multi} on the multi-device index, {n_multi_exact} of them also with exact_ties over 2..8 shards), "
+      f"{ties} boundary-tie queries, "
       f"{time.time()-t0:.0f}s, seed {seed}")

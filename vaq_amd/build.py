@@ -21,13 +21,14 @@ API_HEADER = os.path.join(ROOT, "include", "vaqhip.h")
 SCAN_HEADER = os.path.join(CSRC, "vaq_scan.h")
 SCAN_BF_HEADER = os.path.join(CSRC, "vaq_scan_bf.h")
 FAST_HEADER = os.path.join(CSRC, "vaq_fast.h")
+INTERNAL_HEADER = os.path.join(CSRC, "vaqhip_internal.h")
 
 
 def _deps(src: str):
     # only the host file sees the public C header; the scan bodies live in vaq_scan.h
     deps = [os.path.join(CSRC, src), KERNEL_HEADER]
     if src.endswith(".cpp"):
-        deps.append(API_HEADER)
+        deps += [API_HEADER, INTERNAL_HEADER]
     if src in ("vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip"):
         deps.append(SCAN_HEADER)
     if src in ("vaq_kernels.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip"):

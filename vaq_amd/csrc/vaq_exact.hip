@@ -20,6 +20,13 @@
 //                        own statements: if (top > dist) { heap_pop; heap_push }.  The top the evaluating
 //                        waves abandon against is always one the heap had BEFORE the rows they look at,
 //                        so nothing the reference would admit is ever dropped.  At the end heap_reorder.
+// Across the shards of a multi-device index (vaqhip_multi.cpp) the replay is a CHAIN: shards are
+// contiguous label ranges in label order, so the reference's heap after the rows of shards 0..g is shard
+// g's replay started from the heap (values and ids, raw layout) shards 0..g-1 left behind.  A chain link
+// (ExactParams::chain) takes that state instead of heap_heapify's neutral one, pushes GLOBAL row numbers
+// (the state travels), and writes the raw heap out again; exact_finish_kernel runs heap_reorder on the
+// state the last shard left.  The bucket-bound skip and the early abandon test against a top that is
+// never below the reference's at that row -- the inherited top IS the reference's top there.
 // The heap functions below are the reference's (utils/Heap.hpp), statement for statement, as restated
 // in oracle/vaq_oracle.c -- which is pinned against the compiled reference heap (tests/test_oracle_golden.py).
 #include "vaq_scan.h"
@@ -93,7 +100,29 @@ struct ExactParams {
   int *list;                 // [nq] queries to replay
   unsigned *count;
   int nq;
+  // one link of a chain over shards (0: the single-index replay).  Entry e of the list keeps its heap at
+  // state[e * 2 * k]: k values, then k ids (global row numbers, -1 = neutral).
+  int chain;
+  int e0;                    // the launch covers list entries e0 .. e0 + grid - 1
+  const int32_t *state_in;   // nullptr: the neutral state (first shard)
+  int32_t *state_out;
 };
+
+// heap_reorder (utils/Heap.hpp:322-349) by ONE thread: pop the maxima into the tail -> ascending; entries
+// of id -1 are dropped.  Returns the number kept: they sit in [k - kept, k).  (The memmove of the kept
+// entries to the front and the neutral tail are done by the copy that follows.)
+__device__ __forceinline__ int ex_heap_reorder(const int k, float *hval, int *hid) {
+  int ii = 0;
+  for (int i = 0; i < k; i++) {
+    const float v = hval[0];
+    const int id = hid[0];
+    ex_heap_pop(k - i, hval, hid);
+    hval[k - ii - 1] = v;
+    hid[k - ii - 1] = id;
+    if (id != -1) ii++;
+  }
+  return ii;
+}
 
 __global__ __launch_bounds__(256) void exact_flag_kernel(ExactParams p) {
   const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -151,7 +180,7 @@ __device__ __forceinline__ float ex_row_dist(const ExactParams &p, const float *
 template <bool BYTES>
 __global__ __launch_bounds__(EX_THREADS) void exact_replay_kernel(ExactParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char ex_smem[];
-  const int e = blockIdx.x;
+  const int e = p.e0 + blockIdx.x;
   if ((unsigned)e >= *p.count) return;
   const int q = p.list[e];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -164,20 +193,23 @@ __global__ __launch_bounds__(EX_THREADS) void exact_replay_kernel(ExactParams p)
   float *lds_lut = lbound + (p.row_bucket ? p.n_buckets : 0);
   const float *glut = p.lut + (size_t)q * p.lut_floats;
   const float *lut = glut;
-  if (p.lut_in_lds) {
+  if (p.lut_in_lds && p.n_rows > 0) {  // (an empty shard has built no tables)
     for (int i = tid; i < p.lut_floats; i += EX_THREADS) lds_lut[i] = glut[i];
     lut = lds_lut;
   }
-  // heap_heapify (utils/Heap.hpp:211-235): neutral FLT_MAX, ids -1
+  // heap_heapify (utils/Heap.hpp:211-235): neutral FLT_MAX, ids -1 -- or the heap the earlier shards left
+  const int32_t *sin = p.chain && p.state_in ? p.state_in + (size_t)e * 2 * k : nullptr;
   for (int i = tid; i < k; i += EX_THREADS) {
-    hval[i] = FLT_MAX;
-    hid[i] = -1;
+    hval[i] = sin ? bits_to_float((unsigned)sin[i]) : FLT_MAX;
+    hid[i] = sin ? sin[k + i] : -1;
   }
+  // ids pushed: rows of this index (id_base is added on the way out), or global row numbers in a chain
+  const int64_t push_base = p.chain ? p.id_base : 0;
   // the heap top after the last COMPLETE pop + push, for the evaluating waves (the root itself passes
   // through values below the new top while a pop is under way)
   __shared__ float s_top;
   __shared__ unsigned s_gmin[1 << GMIN_MAX_BITS];
-  if (tid == 0) s_top = FLT_MAX;
+  if (tid == 0) s_top = sin ? bits_to_float((unsigned)sin[0]) : FLT_MAX;
   if (p.row_bucket) {
     // Per bucket the smallest sum its rows can have -- the first table term, plus the smallest second
     // term of the bucket's group of second codes, or the minimum over a coarse bucket's first codes:
@@ -255,7 +287,7 @@ __global__ __launch_bounds__(EX_THREADS) void exact_replay_kernel(ExactParams p)
           if (top > dv) {  // if (heap_dis[0] > dist)
             if (lane == 0) {
               ex_heap_pop(k, hval, hid);
-              ex_heap_push(k, hval, hid, dv, (int)(base + j0 + src));
+              ex_heap_push(k, hval, hid, dv, (int)(push_base + base + j0 + src));
               __hip_atomic_store(&s_top, hval[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             }
             wave_lds_sync();
@@ -267,21 +299,17 @@ __global__ __launch_bounds__(EX_THREADS) void exact_replay_kernel(ExactParams p)
     }
     __syncthreads();
   }
-  // heap_reorder (utils/Heap.hpp:322-349): pop the maxima into the tail -> ascending; entries of id -1
-  // are dropped, the tail refilled with FLT_MAX / -1
-  if (tid == 0) {
-    int ii = 0;
-    for (int i = 0; i < k; i++) {
-      const float v = hval[0];
-      const int id = hid[0];
-      ex_heap_pop(k - i, hval, hid);
-      hval[k - ii - 1] = v;
-      hid[k - ii - 1] = id;
-      if (id != -1) ii++;
+  if (p.chain) {
+    // a link hands the raw heap on (the loop above ended with a barrier)
+    int32_t *sout = p.state_out + (size_t)e * 2 * k;
+    for (int i = tid; i < k; i += EX_THREADS) {
+      sout[i] = (int32_t)float_to_bits(hval[i]);
+      sout[k + i] = hid[i];
     }
-    // (memmove of the ii kept entries to the front, then the neutral tail -- done by the copy below)
-    reinterpret_cast<int *>(buf)[0] = ii;
+    return;
   }
+  // heap_reorder; the tail is refilled with FLT_MAX / -1
+  if (tid == 0) reinterpret_cast<int *>(buf)[0] = ex_heap_reorder(k, hval, hid);
   __syncthreads();
   const int nel = reinterpret_cast<int *>(buf)[0];
   for (int i = tid; i < k; i += EX_THREADS) {
@@ -289,6 +317,34 @@ __global__ __launch_bounds__(EX_THREADS) void exact_replay_kernel(ExactParams p)
     const int id = ok ? hid[k - nel + i] : -1;
     p.labels[(size_t)q * k + i] = ok ? (int32_t)(id + p.id_base) : -1;
     p.dist[(size_t)q * k + i] = ok ? hval[k - nel + i] : FLT_MAX;
+  }
+}
+
+// End of a chain: heap_reorder on the state the last shard left, into the caller's slots of the listed
+// queries.  One wave per list entry; the ids are global already.
+__global__ __launch_bounds__(64) void exact_finish_kernel(const int32_t *__restrict__ state, const int *__restrict__ list,
+                                                          const unsigned *__restrict__ count, int k,
+                                                          int32_t *__restrict__ labels, float *__restrict__ dist) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ex_smem[];
+  const int e = blockIdx.x, lane = threadIdx.x;
+  if ((unsigned)e >= *count) return;
+  const int q = list[e];
+  float *hval = reinterpret_cast<float *>(ex_smem);
+  int *hid = reinterpret_cast<int *>(hval + k);
+  const int32_t *sin = state + (size_t)e * 2 * k;
+  for (int i = lane; i < k; i += 64) {
+    hval[i] = bits_to_float((unsigned)sin[i]);
+    hid[i] = sin[k + i];
+  }
+  __shared__ int s_nel;
+  __syncthreads();
+  if (lane == 0) s_nel = ex_heap_reorder(k, hval, hid);
+  __syncthreads();
+  const int nel = s_nel;
+  for (int i = lane; i < k; i += 64) {
+    const bool ok = i < nel;
+    labels[(size_t)q * k + i] = ok ? hid[k - nel + i] : -1;
+    dist[(size_t)q * k + i] = ok ? hval[k - nel + i] : FLT_MAX;
   }
 }
 
@@ -316,6 +372,24 @@ hipError_t launch_inverse_perm(const uint32_t *perm, int64_t n, uint32_t *inv, c
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(inverse_perm_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, perm, n, inv, bucket_start,
                      n_buckets, row_bucket);
+  return hipGetLastError();
+}
+
+static hipError_t launch_replay(ExactParams &p, int grid, hipStream_t st) {
+  const int k = p.k;
+  size_t lds = (size_t)k * 8 + (size_t)2 * EX_CHUNK * 4 + (p.row_bucket ? (size_t)p.n_buckets * 4 : 0);
+  p.lut_in_lds = (size_t)p.lut_floats * 4 + lds <= 96 * 1024 ? 1 : 0;
+  if (p.lut_in_lds) lds += (size_t)p.lut_floats * 4;
+  hipError_t e;
+  if (p.layout == LAYOUT_BYTES) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(exact_replay_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(exact_replay_kernel<true>, dim3(grid), dim3(EX_THREADS), lds, st, p);
+  } else {
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(exact_replay_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(exact_replay_kernel<false>, dim3(grid), dim3(EX_THREADS), lds, st, p);
+  }
   return hipGetLastError();
 }
 
@@ -350,22 +424,70 @@ hipError_t launch_exact_ties(const uint32_t *codes, int layout, int M, int W, co
   p.list = list;
   p.count = count;
   p.nq = nq;
+  p.chain = 0;
+  p.e0 = 0;
+  p.state_in = nullptr;
+  p.state_out = nullptr;
   hipError_t e = hipMemsetAsync(count, 0, sizeof(unsigned), st);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(exact_flag_kernel, dim3((nq + 3) / 4), dim3(256), 0, st, p);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  size_t lds = (size_t)k * 8 + (size_t)2 * EX_CHUNK * 4 + (row_bucket ? (size_t)n_buckets * 4 : 0);
-  p.lut_in_lds = (size_t)lut_floats * 4 + lds <= 96 * 1024 ? 1 : 0;
-  if (p.lut_in_lds) lds += (size_t)lut_floats * 4;
-  if (layout == LAYOUT_BYTES) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(exact_replay_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(exact_replay_kernel<true>, dim3(nq), dim3(EX_THREADS), lds, st, p);
-  } else {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(exact_replay_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(exact_replay_kernel<false>, dim3(nq), dim3(EX_THREADS), lds, st, p);
-  }
+  return launch_replay(p, nq, st);
+}
+
+hipError_t launch_exact_flag(int nq, int k, const int32_t *in_labels, const float *in_dist, int32_t *labels, float *dist,
+                             int *list, unsigned *count, hipStream_t st) {
+  if (nq <= 0) return hipSuccess;
+  ExactParams p = {};
+  p.k = k;
+  p.in_labels = in_labels;
+  p.in_dist = in_dist;
+  p.labels = labels;
+  p.dist = dist;
+  p.list = list;
+  p.count = count;
+  p.nq = nq;
+  hipError_t e = hipMemsetAsync(count, 0, sizeof(unsigned), st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(exact_flag_kernel, dim3((nq + 3) / 4), dim3(256), 0, st, p);
+  return hipGetLastError();
+}
+
+hipError_t launch_exact_link(const uint32_t *codes, int layout, int M, int W, const SubDesc *sub, const uint32_t *inv,
+                             const unsigned short *row_bucket, int n_buckets, int bucket_shift, int bucket_t,
+                             int64_t n_rows, const float *lut, int lut_floats, int k, int64_t id_base, const int *list,
+                             const unsigned *count, int e0, int n_entries, const int32_t *state_in, int32_t *state_out,
+                             hipStream_t st) {
+  if (n_entries <= 0) return hipSuccess;
+  ExactParams p = {};
+  p.codes = codes;
+  p.layout = layout;
+  p.M = M;
+  p.W = W;
+  p.sub = sub;
+  p.inv = inv;
+  p.row_bucket = row_bucket;
+  p.n_buckets = n_buckets;
+  p.bucket_shift = bucket_shift;
+  p.bucket_t = bucket_t;
+  p.n_rows = n_rows;
+  p.lut = lut;
+  p.lut_floats = lut_floats;
+  p.k = k;
+  p.id_base = id_base;
+  p.list = const_cast<int *>(list);
+  p.count = const_cast<unsigned *>(count);
+  p.chain = 1;
+  p.e0 = e0;
+  p.state_in = state_in;
+  p.state_out = state_out;
+  return launch_replay(p, n_entries, st);
+}
+
+hipError_t launch_exact_finish(const int32_t *state, const int *list, const unsigned *count, int n_entries, int k,
+                               int32_t *labels, float *dist, hipStream_t st) {
+  if (n_entries <= 0) return hipSuccess;
+  hipLaunchKernelGGL(exact_finish_kernel, dim3(n_entries), dim3(64), (size_t)k * 8, st, state, list, count, k, labels, dist);
   return hipGetLastError();
 }
 

@@ -298,6 +298,22 @@ hipError_t launch_exact_ties(const uint32_t *codes, int layout, int M, int W, co
                              int64_t n_rows, const float *lut, int lut_floats, int nq, int k, int64_t id_base,
                              const int32_t *in_labels, const float *in_dist, int32_t *labels, float *dist, int *list,
                              unsigned *count, hipStream_t st);
+// The same across the shards of a multi-device index (vaqhip_multi.cpp): the flag step alone, on the MERGED
+// k + 1 list (untied queries copied to labels / dist, the others listed; count is zeroed first) ...
+hipError_t launch_exact_flag(int nq, int k, const int32_t *in_labels, const float *in_dist, int32_t *labels, float *dist,
+                             int *list, unsigned *count, hipStream_t st);
+// ... one link of the chain: list entries [e0, e0 + n_entries) (those beyond *count exit at once) are
+// replayed over this index's rows, starting from state_in (nullptr: the neutral heap) and leaving the
+// raw heap in state_out.  Entry e's state: 2 * k words at [e * 2 * k], k distance bits then k ids; ids
+// are id_base + row.  lut: [.][lut_floats] indexed by the listed query ...
+hipError_t launch_exact_link(const uint32_t *codes, int layout, int M, int W, const SubDesc *sub, const uint32_t *inv,
+                             const unsigned short *row_bucket, int n_buckets, int bucket_shift, int bucket_t,
+                             int64_t n_rows, const float *lut, int lut_floats, int k, int64_t id_base, const int *list,
+                             const unsigned *count, int e0, int n_entries, const int32_t *state_in, int32_t *state_out,
+                             hipStream_t st);
+// ... and its end: heap_reorder on the last state into the listed queries' slots of labels / dist [.][k]
+hipError_t launch_exact_finish(const int32_t *state, const int *list, const unsigned *count, int n_entries, int k,
+                               int32_t *labels, float *dist, hipStream_t st);
 
 // ---- triangle-inequality cluster pruning (vaq_ti.hip) ----------------------
 // packed index rows -> uint16 N x M in original row order (inverse of launch_pack_codes)

@@ -21,6 +21,7 @@
 
 #include "vaq_fast.h"
 #include "vaq_kernels.h"
+#include "vaqhip_internal.h"
 
 namespace {
 
@@ -1632,6 +1633,73 @@ int vaqhip_search_finish_device(vaqhip_index *ix, const int32_t *d_thresholds_in
   DeviceGuard g(ix->device);
   if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
   return search_finish_locked(ix, d_thresholds_in, static_cast<hipStream_t>(stream));
+}
+
+// ---- "exact_ties" across the shards of a multi-device index (vaqhip_internal.h) ----
+int vaqhip_internal_query_chunk(void) { return QUERY_CHUNK; }
+
+int vaqhip_internal_exact_applies(vaqhip_index *ix, int k) {
+  if (!ix) return 0;
+  std::lock_guard<std::mutex> lk(ix->mu);
+  return ix->opt_exact && !fast_only(ix) && ix->ti_T == 0 && !ix->seq && k > 0 && k < VAQHIP_MAX_K ? 1 : 0;
+}
+
+int vaqhip_internal_search_plain_device(vaqhip_index *ix, const float *d_queries, int nq, int k, int projected,
+                                        int32_t *d_labels, float *d_dist, void *stream) {
+  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
+  if (nq > QUERY_CHUNK) return fail(VAQHIP_EINVAL, "nq=%d > %d", nq, QUERY_CHUNK);
+  std::lock_guard<std::mutex> lk(ix->mu);
+  DeviceGuard g(ix->device);
+  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  if (fast_only(ix)) return fail(VAQHIP_EUNSUPPORTED, "method FAST has no chained form");
+  return search_core(ix, d_queries, nq, k, projected, d_labels, d_dist, static_cast<hipStream_t>(stream));
+}
+
+int vaqhip_internal_exact_flag_device(int device, int nq, int k, const int32_t *d_in_labels, const float *d_in_dist,
+                                      int32_t *d_labels, float *d_dist, int *d_list, unsigned *d_count, void *stream) {
+  if (nq <= 0 || k <= 0 || !d_in_labels || !d_in_dist || !d_labels || !d_dist || !d_list || !d_count)
+    return fail(VAQHIP_EINVAL, "bad arguments");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", device);
+  HIP_TRY(vaq::launch_exact_flag(nq, k, d_in_labels, d_in_dist, d_labels, d_dist, d_list, d_count,
+                                 static_cast<hipStream_t>(stream)));
+  return VAQHIP_OK;
+}
+
+int vaqhip_internal_exact_link_device(vaqhip_index *ix, int k, const int *d_list, const unsigned *d_count, int e0,
+                                      int n_entries, const int32_t *d_state_in, int32_t *d_state_out, void *stream) {
+  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
+  if (k <= 0 || k >= VAQHIP_MAX_K || e0 < 0 || n_entries < 0 || !d_list || !d_count || !d_state_out)
+    return fail(VAQHIP_EINVAL, "bad arguments");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  DeviceGuard g(ix->device);
+  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  if (ix->N < 0) return fail(VAQHIP_ESTATE, "search before codes were set");
+  if (ix->ti_T > 0 || ix->seq || fast_only(ix)) return fail(VAQHIP_EUNSUPPORTED, "no replay for this method");
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (int rc = ws_acquire(ix, st)) return rc;
+  if (ix->N > 0 && !ix->inv_valid) {
+    HIP_TRY(ix->d_inv.ensure((size_t)ix->N * sizeof(uint32_t)));
+    HIP_TRY(ix->d_rowbucket.ensure((size_t)ix->N * sizeof(unsigned short)));
+    HIP_TRY(vaq::launch_inverse_perm(ix->d_perm.as<uint32_t>(), ix->N, ix->d_inv.as<uint32_t>(), ix->d_bstart.as<int>(),
+                                     ix->n_buckets, ix->d_rowbucket.as<unsigned short>(), st));
+    ix->inv_valid = true;
+  }
+  HIP_TRY(vaq::launch_exact_link(ix->d_codes.as<uint32_t>(), ix->layout, ix->M, ix->W, ix->d_sub.as<vaq::SubDesc>(),
+                                 ix->d_inv.as<uint32_t>(), ix->N > 0 ? ix->d_rowbucket.as<unsigned short>() : nullptr,
+                                 ix->n_buckets, ix->bucket_shift, ix->bucket_t, ix->N, ix->w_lut.as<float>(), ix->lut_floats,
+                                 k, ix->id_base, d_list, d_count, e0, n_entries, d_state_in, d_state_out, st));
+  return ws_release(ix, st);
+}
+
+int vaqhip_internal_exact_finish_device(int device, const int32_t *d_state, const int *d_list, const unsigned *d_count,
+                                        int n_entries, int k, int32_t *d_labels, float *d_dist, void *stream) {
+  if (n_entries < 0 || k <= 0 || k >= VAQHIP_MAX_K || !d_state || !d_list || !d_count || !d_labels || !d_dist)
+    return fail(VAQHIP_EINVAL, "bad arguments");
+  DeviceGuard g(device);
+  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", device);
+  HIP_TRY(vaq::launch_exact_finish(d_state, d_list, d_count, n_entries, k, d_labels, d_dist, static_cast<hipStream_t>(stream)));
+  return VAQHIP_OK;
 }
 
 int vaqhip_search_device(vaqhip_index *ix, const float *d_queries, int nq, int k, int projected,

@@ -16,7 +16,17 @@
 // When the device list names one GPU several times (logical shards: how the exchange and merge
 // are tested on a one-GPU box) RCCL cannot be used -- it refuses duplicate devices -- and the
 // gather is done with device-to-device copies instead; same buffers, same merge.
+//
+// Option "exact_ties" with more than one shard ("exact_ties across shards"): the reference's
+// heap after the rows of shards 0..g is shard g's replay started from the heap shards 0..g-1 left, so
+// per set of queries (A) every shard scans with k + 1 by the smallest-label rule, the exchange and merge
+// above give the global k + 1 list on shard 0, the flag kernel copies the untied queries out and lists
+// the tied ones; the list goes to every shard; (B) batch by batch of the list, shard g waits for shard
+// g-1's event, takes the heap state by peer copy, runs its link (vaq_exact.hip) and records its own event;
+// shard 0 reorders the state the last shard left into the caller's slots.  Every wait is a stream wait on
+// an event; no kernel waits for another.
 #include "vaqhip.h"
+#include "vaqhip_internal.h"
 
 #include <dlfcn.h>
 #include <hip/hip_runtime.h>
@@ -98,6 +108,12 @@ struct Shard {
   int32_t *d_gathered = nullptr;  // [G][2][nq][k] (every device under RCCL; shard 0 with copies)
   size_t cap_q = 0, cap_p = 0, cap_g = 0;
   ncclComm_t comm = nullptr;
+  // "exact_ties" across shards: the replay list (word 0 = count, entries from byte 16), the heap states
+  // this shard's links start from and leave ([entry][2][k] words; shard 0's d_state_in receives the LAST
+  // shard's), one event per batch of the list
+  int32_t *d_list = nullptr, *d_state_in = nullptr, *d_state_out = nullptr;
+  size_t cap_list = 0, cap_si = 0, cap_so = 0;
+  std::vector<hipEvent_t> link_done;
   std::string err;  // what the shard's last phase failed with
 };
 
@@ -125,6 +141,13 @@ struct vaqhip_multi {
   float *d_out_dist = nullptr;
   size_t cap_out = 0;
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // shard 0: start, searched, gathered, merged
+  // "exact_ties" across shards
+  int opt_exact = 0, opt_exact_batch = 0;
+  bool chain = false;             // the current search runs the chain (then k above is the caller's k + 1)
+  int n_batches = 0, batch = 0;   //   of the current set of queries
+  hipEvent_t flagged = nullptr;   // shard 0: the replay list of the current set is complete
+  int32_t *d_final = nullptr;     // shard 0: [2][nq][k] the current set's answer (labels, distances)
+  size_t cap_final = 0;
   vaqhip_multi_info last = {};
 };
 
@@ -182,7 +205,20 @@ int run_shard(vaqhip_multi *mx, int g) {
     }
     mx->d_out_dist = reinterpret_cast<float *>(mx->d_out_labels + plane);
   }
-  // (the previous search's exchange has read this shard's packed result: never recorded = no wait)
+  if (mx->chain) {
+    const size_t state = (size_t)nq * 2 * (k - 1) * 4;
+    if (int rc = grow(s, reinterpret_cast<void **>(&s.d_list), &s.cap_list, 16 + (size_t)nq * 4)) return rc;
+    if (int rc = grow(s, reinterpret_cast<void **>(&s.d_state_in), &s.cap_si, state)) return rc;
+    if (int rc = grow(s, reinterpret_cast<void **>(&s.d_state_out), &s.cap_so, state)) return rc;
+    if (g == 0)
+      if (int rc = grow(s, reinterpret_cast<void **>(&mx->d_final), &mx->cap_final, (size_t)nq * 2 * (k - 1) * 4)) return rc;
+    while ((int)s.link_done.size() < mx->n_batches) {
+      hipEvent_t e = nullptr;
+      MHIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+      s.link_done.push_back(e);
+    }
+  }
+  // (the previous search's exchange -- and chain -- has read this shard's buffers: never recorded = no wait)
   MHIP(hipStreamWaitEvent(s.stream, mx->consumed, 0));
   if (g == 0) MHIP(hipEventRecord(mx->ev[0], s.stream));
   if (mx->d_queries0) {
@@ -194,7 +230,8 @@ int run_shard(vaqhip_multi *mx, int g) {
   }
   int32_t *labels = G == 1 ? mx->d_out_labels : s.d_packed;
   float *dist = G == 1 ? mx->d_out_dist : reinterpret_cast<float *>(s.d_packed + plane);
-  const int rc = vaqhip_search_device(s.ix, s.d_queries, nq, k, mx->projected, labels, dist, s.stream);
+  const int rc = mx->chain ? vaqhip_internal_search_plain_device(s.ix, s.d_queries, nq, k, mx->projected, labels, dist, s.stream)
+                           : vaqhip_search_device(s.ix, s.d_queries, nq, k, mx->projected, labels, dist, s.stream);
   if (rc) {
     s.err = vaqhip_last_error();
     return rc;
@@ -226,8 +263,8 @@ int exchange_rccl(vaqhip_multi *mx) {
 }
 
 // after every shard has enqueued its part: gather by copies when RCCL is not in play, merge on
-// shard 0's device, bring the result to the host
-int finish_on_shard0(vaqhip_multi *mx, int32_t *labels, float *distances, hipStream_t user) {
+// shard 0's device
+int gather_and_merge(vaqhip_multi *mx) {
   Shard &s = mx->sh[0];
   const int G = mx->G, nq = mx->nq, k = mx->k;
   const size_t plane = (size_t)nq * k;
@@ -251,19 +288,88 @@ int finish_on_shard0(vaqhip_multi *mx, int32_t *labels, float *distances, hipStr
   } else {
     MHIP(hipEventRecord(mx->ev[2], s.stream));
   }
+  return 0;
+}
+
+// "exact_ties" across shards, after the merge of the k + 1 lists (mx->k): flag on shard 0, the list to
+// every shard, the chain of links batch by batch, heap_reorder on shard 0 -> mx->d_final [2][nq][k].
+// Issued by the calling thread; everything is enqueued, nothing waited for.  A failure part-way leaves
+// streams that wait only for events already recorded (or never recorded: no wait).
+#define MIX(expr)                                 \
+  do {                                            \
+    const int rc_ = (expr);                       \
+    if (rc_) {                                    \
+      s.err = vaqhip_last_error();                \
+      return rc_;                                 \
+    }                                             \
+  } while (0)
+int chain_on_shard0(vaqhip_multi *mx) {
+  Shard &s = mx->sh[0];
+  const int G = mx->G, nq = mx->nq, k = mx->k - 1;
+  const size_t plane = (size_t)nq * k, entry = (size_t)2 * k;
+  int32_t *fl = mx->d_final;
+  float *fd = reinterpret_cast<float *>(mx->d_final + plane);
+  const size_t list_bytes = 16 + (size_t)nq * 4;
+  MIX(vaqhip_internal_exact_flag_device(s.device, nq, k, mx->d_out_labels, mx->d_out_dist, fl, fd,
+                                        reinterpret_cast<int *>(s.d_list + 4), reinterpret_cast<unsigned *>(s.d_list),
+                                        s.stream));
+  MHIP(hipEventRecord(mx->flagged, s.stream));
+  for (int g = 1; g < G; g++) {
+    Shard &t = mx->sh[g];
+    MHIP(hipSetDevice(t.device));
+    MHIP(hipStreamWaitEvent(t.stream, mx->flagged, 0));
+    MHIP(hipMemcpyPeerAsync(t.d_list, t.device, s.d_list, s.device, list_bytes, t.stream));
+  }
+  // Batches are enqueued in order on every shard's stream: on distinct GPUs shard g works on batch b
+  // while shard g + 1 works on batch b - 1.  Entries beyond the device-side count exit at once.
+  for (int b = 0; b < mx->n_batches; b++) {
+    const int e0 = b * mx->batch, ne = std::min(mx->batch, nq - e0);
+    for (int g = 0; g < G; g++) {
+      Shard &t = mx->sh[g];
+      MHIP(hipSetDevice(t.device));
+      if (g > 0) {
+        const Shard &u = mx->sh[g - 1];
+        MHIP(hipStreamWaitEvent(t.stream, u.link_done[b], 0));
+        MHIP(hipMemcpyPeerAsync(t.d_state_in + e0 * entry, t.device, u.d_state_out + e0 * entry, u.device,
+                                ne * entry * 4, t.stream));
+      }
+      MIX(vaqhip_internal_exact_link_device(t.ix, k, reinterpret_cast<const int *>(t.d_list + 4),
+                                            reinterpret_cast<const unsigned *>(t.d_list), e0, ne,
+                                            g > 0 ? t.d_state_in : nullptr, t.d_state_out, t.stream));
+      MHIP(hipEventRecord(t.link_done[b], t.stream));
+    }
+  }
+  const Shard &last = mx->sh[G - 1];
+  MHIP(hipSetDevice(s.device));
+  MHIP(hipStreamWaitEvent(s.stream, last.link_done[mx->n_batches - 1], 0));
+  MHIP(hipMemcpyPeerAsync(s.d_state_in, s.device, last.d_state_out, last.device, nq * entry * 4, s.stream));
+  MIX(vaqhip_internal_exact_finish_device(s.device, s.d_state_in, reinterpret_cast<const int *>(s.d_list + 4),
+                                          reinterpret_cast<const unsigned *>(s.d_list), nq, k, fl, fd, s.stream));
+  return 0;
+}
+#undef MIX
+
+// the result (k per query, on shard 0's device) to the caller: device buffers behind the caller's
+// stream, or the host
+int deliver(vaqhip_multi *mx, const int32_t *src_labels, const float *src_dist, int k, int32_t *labels, float *distances,
+            hipStream_t user) {
+  Shard &s = mx->sh[0];
+  const int G = mx->G;
+  const size_t plane = (size_t)mx->nq * k;
+  MHIP(hipSetDevice(s.device));
   MHIP(hipEventRecord(mx->ev[3], s.stream));
   MHIP(hipEventRecord(mx->consumed, s.stream));
   if (mx->d_queries0) {
     // device entry: results into the caller's buffers on shard 0's device; the caller's stream waits
     // for them, the host does not
-    MHIP(hipMemcpyAsync(labels, mx->d_out_labels, plane * 4, hipMemcpyDeviceToDevice, s.stream));
-    MHIP(hipMemcpyAsync(distances, mx->d_out_dist, plane * 4, hipMemcpyDeviceToDevice, s.stream));
+    MHIP(hipMemcpyAsync(labels, src_labels, plane * 4, hipMemcpyDeviceToDevice, s.stream));
+    MHIP(hipMemcpyAsync(distances, src_dist, plane * 4, hipMemcpyDeviceToDevice, s.stream));
     MHIP(hipEventRecord(mx->finished, s.stream));
     MHIP(hipStreamWaitEvent(user, mx->finished, 0));
     return 0;
   }
-  MHIP(hipMemcpyAsync(labels, mx->d_out_labels, plane * 4, hipMemcpyDeviceToHost, s.stream));
-  MHIP(hipMemcpyAsync(distances, mx->d_out_dist, plane * 4, hipMemcpyDeviceToHost, s.stream));
+  MHIP(hipMemcpyAsync(labels, src_labels, plane * 4, hipMemcpyDeviceToHost, s.stream));
+  MHIP(hipMemcpyAsync(distances, src_dist, plane * 4, hipMemcpyDeviceToHost, s.stream));
   MHIP(hipStreamSynchronize(s.stream));
   for (int g = 1; g < G; g++) {  // (their collective / copies are complete before anyone reuses the buffers)
     MHIP(hipSetDevice(mx->sh[g].device));
@@ -276,6 +382,15 @@ int finish_on_shard0(vaqhip_multi *mx, int32_t *labels, float *distances, hipStr
   mx->last.last_exchange_ms = ms[1];
   mx->last.last_merge_ms = ms[2];
   return 0;
+}
+
+int finish_on_shard0(vaqhip_multi *mx, int32_t *labels, float *distances, hipStream_t user) {
+  if (int rc = gather_and_merge(mx)) return rc;
+  if (!mx->chain) return deliver(mx, mx->d_out_labels, mx->d_out_dist, mx->k, labels, distances, user);
+  if (int rc = chain_on_shard0(mx)) return rc;
+  const int k = mx->k - 1;
+  return deliver(mx, mx->d_final, reinterpret_cast<const float *>(mx->d_final + (size_t)mx->nq * k), k, labels, distances,
+                 user);
 }
 
 int ensure_comms(vaqhip_multi *mx) {
@@ -328,7 +443,8 @@ int vaqhip_multi_create(vaqhip_multi **out, int D, int M, const int *bits, const
       for (auto &e : mx->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
       ok = ok && hipEventCreateWithFlags(&mx->user_ready, hipEventDisableTiming) == hipSuccess &&
            hipEventCreateWithFlags(&mx->consumed, hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&mx->finished, hipEventDisableTiming) == hipSuccess;
+           hipEventCreateWithFlags(&mx->finished, hipEventDisableTiming) == hipSuccess &&
+           hipEventCreateWithFlags(&mx->flagged, hipEventDisableTiming) == hipSuccess;
     }
     if (!ok) {
       vaqhip_multi_destroy(mx);
@@ -350,15 +466,19 @@ void vaqhip_multi_destroy(vaqhip_multi *mx) {
     if (s.d_queries) (void)hipFree(s.d_queries);
     if (s.d_packed) (void)hipFree(s.d_packed);
     if (s.d_gathered) (void)hipFree(s.d_gathered);
+    for (void *p : {(void *)s.d_list, (void *)s.d_state_in, (void *)s.d_state_out})
+      if (p) (void)hipFree(p);
+    for (hipEvent_t e : s.link_done) (void)hipEventDestroy(e);
     if (s.done) (void)hipEventDestroy(s.done);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     if (s.ix) vaqhip_index_destroy(s.ix);
   }
   if (!mx->sh.empty()) (void)hipSetDevice(mx->sh[0].device);
   if (mx->d_out_labels) (void)hipFree(mx->d_out_labels);
+  if (mx->d_final) (void)hipFree(mx->d_final);
   for (auto &e : mx->ev)
     if (e) (void)hipEventDestroy(e);
-  for (hipEvent_t e : {mx->user_ready, mx->consumed, mx->finished})
+  for (hipEvent_t e : {mx->user_ready, mx->consumed, mx->finished, mx->flagged})
     if (e) (void)hipEventDestroy(e);
   delete mx;
 }
@@ -444,6 +564,11 @@ int vaqhip_multi_set_option(vaqhip_multi *mx, const char *key, int64_t value) {
     mx->exchange = (int)value;
     return VAQHIP_OK;
   }
+  if (std::strcmp(key, "exact_batch") == 0) {
+    if (value < 0 || value > (1 << 20)) return mfail(VAQHIP_EINVAL, "exact_batch must be 0 (auto) or a number of list entries");
+    mx->opt_exact_batch = (int)value;
+    return VAQHIP_OK;
+  }
   for (auto &s : mx->sh) {
     const int rc = vaqhip_set_option(s.ix, key, value);
     if (rc) {
@@ -451,34 +576,15 @@ int vaqhip_multi_set_option(vaqhip_multi *mx, const char *key, int64_t value) {
       return rc;
     }
   }
+  // (every shard holds the option too: one shard alone answers by its own replay, and the chain is only
+  //  taken where the option has an effect on every shard)
+  if (std::strcmp(key, "exact_ties") == 0) mx->opt_exact = value != 0;
   return VAQHIP_OK;
 }
 
-static int multi_search_common(vaqhip_multi *mx, const float *queries, const float *d_queries0, hipStream_t user, int nq, int k,
-                               int projected, int32_t *labels, float *distances) {
-  if (!mx) return mfail(VAQHIP_EINVAL, "multi index is null");
-  if (nq < 0 || k <= 0) return mfail(VAQHIP_EINVAL, "nq=%d k=%d", nq, k);
-  if (nq == 0) return VAQHIP_OK;
-  if ((!queries && !d_queries0) || !labels || !distances) return mfail(VAQHIP_EINVAL, "null pointer");
-  std::lock_guard<std::mutex> lk(mx->mu);
-  // RCCL when the GPUs are distinct and there is something to exchange (or when asked for by
-  // option, which also exercises it on one device); device-to-device copies otherwise
-  bool rccl = mx->exchange == EX_RCCL || (mx->exchange == EX_AUTO && mx->distinct && mx->G > 1);
-  if (rccl) {
-    const int rc = ensure_comms(mx);
-    if (rc) return rc;
-  }
-  // a one-shard index asked to use RCCL still goes through the collective (G == 1 skips packing)
-  mx->use_rccl = rccl && mx->G > 1;
-  mx->queries = queries;
-  mx->d_queries0 = d_queries0;
-  mx->nq = nq;
-  mx->k = k;
-  mx->projected = projected;
-  if (d_queries0) {
-    if (hipSetDevice(mx->sh[0].device) != hipSuccess || hipEventRecord(mx->user_ready, user) != hipSuccess)
-      return mfail(VAQHIP_EHIP, "recording the caller's stream");
-  }
+// one set of queries (mx->queries / d_queries0, nq, k): the shards' searches, the exchange, the merge
+// (and the chain) on shard 0, the result to the caller
+static int search_set(vaqhip_multi *mx, bool rccl, int32_t *labels, float *distances, hipStream_t user) {
   // phase 1: every shard uploads (or copies) the queries and enqueues its search
   const int rc1 = mx->pool.run([&](int g) -> int {
     mx->sh[g].err.clear();
@@ -500,7 +606,7 @@ static int multi_search_common(vaqhip_multi *mx, const float *queries, const flo
     // one rank: the collective degenerates to a copy; run it anyway so that a one-GPU box
     // proves the RCCL binding (communicator, stream, datatype) end to end
     Shard &s = mx->sh[0];
-    const size_t plane = (size_t)nq * k;
+    const size_t plane = (size_t)mx->nq * mx->k;
     if (hipSetDevice(s.device) != hipSuccess) return mfail(VAQHIP_EHIP, "hipSetDevice");
     if (grow(s, reinterpret_cast<void **>(&s.d_gathered), &s.cap_g, 2 * plane * 4))
       return mfail(VAQHIP_ENOMEM, "%s", s.err.c_str());
@@ -512,6 +618,52 @@ static int multi_search_common(vaqhip_multi *mx, const float *queries, const flo
   Shard &s0 = mx->sh[0];
   const int rc = finish_on_shard0(mx, labels, distances, user);
   if (rc) return mfail(rc, "exchange / merge on device %d: %s", s0.device, s0.err.c_str());
+  return VAQHIP_OK;
+}
+
+static int multi_search_common(vaqhip_multi *mx, const float *queries, const float *d_queries0, hipStream_t user, int nq, int k,
+                               int projected, int32_t *labels, float *distances) {
+  if (!mx) return mfail(VAQHIP_EINVAL, "multi index is null");
+  if (nq < 0 || k <= 0) return mfail(VAQHIP_EINVAL, "nq=%d k=%d", nq, k);
+  if (nq == 0) return VAQHIP_OK;
+  if ((!queries && !d_queries0) || !labels || !distances) return mfail(VAQHIP_EINVAL, "null pointer");
+  std::lock_guard<std::mutex> lk(mx->mu);
+  // RCCL when the GPUs are distinct and there is something to exchange (or when asked for by
+  // option, which also exercises it on one device); device-to-device copies otherwise
+  bool rccl = mx->exchange == EX_RCCL || (mx->exchange == EX_AUTO && mx->distinct && mx->G > 1);
+  if (rccl) {
+    const int rc = ensure_comms(mx);
+    if (rc) return rc;
+  }
+  // a one-shard index asked to use RCCL still goes through the collective (G == 1 skips packing)
+  mx->use_rccl = rccl && mx->G > 1;
+  mx->projected = projected;
+  if (d_queries0) {
+    if (hipSetDevice(mx->sh[0].device) != hipSuccess || hipEventRecord(mx->user_ready, user) != hipSuccess)
+      return mfail(VAQHIP_EHIP, "recording the caller's stream");
+  }
+  // "exact_ties" over several shards: the chain, where the option has an effect on a single index too
+  // (not TI, not the sequential sum, not FAST, k < VAQHIP_MAX_K); one set of queries at a time, because
+  // every link reads the lookup tables its shard built for the set
+  mx->chain = mx->opt_exact && mx->G > 1;
+  for (int g = 0; mx->chain && g < mx->G; g++) mx->chain = vaqhip_internal_exact_applies(mx->sh[g].ix, k) != 0;
+  const int set = mx->chain ? std::min(nq, vaqhip_internal_query_chunk()) : nq;
+  for (int q0 = 0; q0 < nq; q0 += set) {
+    const int n = std::min(set, nq - q0);
+    mx->queries = queries ? queries + (size_t)q0 * mx->D : nullptr;
+    mx->d_queries0 = d_queries0 ? d_queries0 + (size_t)q0 * mx->D : nullptr;
+    mx->nq = n;
+    mx->k = mx->chain ? k + 1 : k;
+    if (mx->chain) {
+      // batches of the replay list, chosen from the set's size (the count of tied queries lives on the device)
+      int b = mx->opt_exact_batch > 0 ? mx->opt_exact_batch : std::max(64, (n + 15) / 16);
+      b = std::max(b, (n + 255) / 256);
+      mx->batch = b;
+      mx->n_batches = (n + b - 1) / b;
+    }
+    const int rc = search_set(mx, rccl, labels + (size_t)q0 * k, distances + (size_t)q0 * k, user);
+    if (rc) return rc;
+  }
   mx->last.exchange = rccl ? EX_RCCL : (mx->G == 1 ? 0 : EX_COPIES);
   return VAQHIP_OK;
 }

@@ -560,6 +560,13 @@ class VaqHipMulti:
         _lib.check_multi(_lib.load().vaqhip_multi_add_codes_u16(self._h, _ptr(cb), cb.shape[0]))
 
     def set_option(self, key: str, value: int) -> None:
+        """vaqhip_multi_set_option: "exchange" (0 auto, 1 RCCL, 2 copies) and "exact_batch" belong to the
+        multi index, everything else is forwarded to every shard.  "exact_ties" = 1 holds across the
+        shards: labels and distances equal VAQ::search's over ALL rows slot for slot -- every shard scans
+        with k + 1, the merged list decides which queries have ties, and those are replayed through the
+        reference's heap as a chain from shard to shard (k * 8 bytes per tied query per shard boundary;
+        "exact_batch" = list entries per batch of that chain, 0 = automatic).  No effect with TI, the
+        sequential sum and k = 1024, as on a single index."""
         _lib.check_multi(_lib.load().vaqhip_multi_set_option(self._h, key.encode(), int(value)))
 
     def set_method(self, methods: int, visit: float = 1.0) -> None:
