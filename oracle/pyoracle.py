@@ -137,6 +137,18 @@ def ref_topk_from_dists(dist, k, ids=None):
     return out_ids, out_val
 
 
+def ref_knn_from_dists(dists, k):
+    """KNNFromDists<int16_t> (utils/Experiment.hpp:39-56) from the compiled reference: (idx int32 [k],
+    dist int16 [k]).  len >= k only: the reference reads dists[0..k) unconditionally."""
+    d = np.ascontiguousarray(dists, dtype=np.int16)
+    assert d.ndim == 1 and d.size >= k > 0
+    idx = np.empty(k, dtype=np.int32)
+    dist = np.empty(k, dtype=np.int16)
+    ref().ref_knn_from_dists(d.ctypes.data_as(C.POINTER(C.c_int16)), C.c_int(d.size), C.c_int(k), _ip(idx),
+                             dist.ctypes.data_as(C.POINTER(C.c_int16)))
+    return idx, dist
+
+
 # ------------------------------------------------------------------- LUT ---
 def project(X, E):
     X = np.ascontiguousarray(X, dtype=np.float32)

@@ -7,7 +7,7 @@
 //   bitvecengine/utils/Math.hpp              fvec_L2sqr_ny (LUT fallback, K_s < 8)
 //   bitvecengine/utils/AVXUtils.hpp          fma() used by CreateLUT
 //   bitvecengine/utils/IO.hpp                save/load Centroids + Codebook, fvecs/ivecs
-//   bitvecengine/utils/Experiment.hpp        getAvgRecall / getRecallAtR
+//   bitvecengine/utils/Experiment.hpp        getAvgRecall / getRecallAtR, KNNFromDists
 //   external/eigen + utils/Types.hpp         the matrix types and the Eigen expressions of
 //                                            VAQ::encodeImpl / ProjectOnEigenVectors (what Eigen's
 //                                            reductions and GEMM actually sum)
@@ -190,6 +190,16 @@ double ref_recall_at_r(const int *labels, int nq, int K, const int *topnn,
   for (int q = 0; q < nq; q++)
     gt[q].assign(topnn + size_t(q) * stride, topnn + size_t(q) * stride + stride);
   return getRecallAtR<0>(lab, gt, K);
+}
+
+// KNNFromDists<int16_t> (utils/Experiment.hpp:39-56), the top-k of VAQ::searchFast: std::sort of rows
+// < k by distance alone, then maybeInsertNeighbor for every later row.  len >= k (it reads dists[0..k)).
+void ref_knn_from_dists(const int16_t *dists, int len, int k, int *idx, int16_t *dist) {
+  std::vector<IdxDistPairBase<int16_t>> r = KNNFromDists<int16_t>(dists, len, k);
+  for (int i = 0; i < k; i++) {
+    idx[i] = r[(size_t)i].idx;
+    dist[i] = r[(size_t)i].dist;
+  }
 }
 
 } // extern "C"

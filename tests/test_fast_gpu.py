@@ -46,8 +46,11 @@ def check(v, c, k, lut, projected=False, what=""):
     return lab, dis
 
 
-# (128 x 4 bits = 512 code bits per row: more than vaqhip_index_create packs, so M stops at 64 here)
-@pytest.mark.parametrize("bits", [[4] * 8, [4] * 16, [4] * 32, [4] * 64, [4, 4, 3, 3, 2, 2, 1, 1]])
+# A row packs at most 256 code bits, so 4-bit codes stop at M = 64; FAST itself serves every M up to 128
+# (narrower codes: 80 x 3, 96 x 2, 128 x 2 bits and a 1/2-bit mix; searched in test_fast_shapes_gpu.py)
+@pytest.mark.parametrize("bits", [[4] * 8, [4] * 16, [4] * 32, [4] * 64, [4, 4, 3, 3, 2, 2, 1, 1],
+                                  [4] * 4, [4] * 12, [4] * 20, [4] * 36, [4] * 40, [3] * 80, [2] * 96, [2] * 128,
+                                  [2, 1] * 64])
 def test_small_lut_bytes(vaqlib, bits):
     M = len(bits)
     c = make_case(11, 2 * M if M > 8 else 16, bits, 100, 9)
