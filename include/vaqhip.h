@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 105
+#define VAQHIP_VERSION 106
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -165,7 +165,8 @@ int vaqhip_index_set_method(vaqhip_index *ix, unsigned methods, float visit);
  *              of rows 0..k-1 (utils/Experiment.hpp:40-56), the row itself for rows >= k; id_base + row;
  *   N < k      unfilled slots -1 / FLT_MAX (the reference reads past its array there).
  * Without a quantisation: VAQHIP_ESTATE.  exact_ties has no effect (FAST is slot-exact by itself);
- * staged search and vaqhip_multi_* are VAQHIP_EUNSUPPORTED with FAST.
+ * the staged search is VAQHIP_EUNSUPPORTED with FAST.  A vaqhip_multi answers FAST over its shards with the
+ * same slots (vaqhip_multi_set_lut_quantization below).
  * Memory: while FAST is the method in force the index keeps a second copy of its codes in original row order
  * (16 * ceil(M / 32) bytes per row, built at the first FAST search) and up to 1 GiB of per-search workspace;
  * both are released when another method is set.  Indexes that never run FAST carry neither. */
@@ -271,6 +272,24 @@ int vaqhip_merge_topk_strided_device(int device_id, const float *d_dist_lists,
                                      int64_t list_stride, int64_t query_stride, int nq, int k,
                                      int32_t *d_labels_out, float *d_dist_out, void *stream);
 
+/* FAST's exchange step.  A FAST answer is not ordered by (distance, label): it is the first k of a stable sort
+ * by distance of "the head -- the first n_head = min(k, N) rows of the whole database -- in the order
+ * KNNFromDists' std::sort leaves them, then every other row in row order" ("FAST across
+ * shards").  So a shard contributes the distances of the head rows it holds, untruncated, and the top-k of its
+ * OTHER rows by (distance, row); this call sorts the gathered head as the single index does and merges:
+ *   d_head_dist   uint16 distance of head row p of query q at [q * head_stride + p], p < n_head <= k
+ *   lists         as for vaqhip_merge_topk_strided_device (candidate i of list l of query q at
+ *                 [l * list_stride + q * query_stride + i]), each ascending by distance, lists in row order,
+ *                 k slots each, empty slots label < 0; distances are integers below 65535 held as float
+ *   result        k per query; head rows get label head_label_base + p; ties go to the head, then to the
+ *                 earlier list, then to the earlier slot; slots past the number of entries are -1 / FLT_MAX
+ * At most 16 lists, k <= VAQHIP_MAX_K (VAQHIP_EUNSUPPORTED).  The outputs are used as scratch while the call
+ * runs on the device and must not overlap the inputs.  Enqueue only. */
+int vaqhip_merge_fast_device(int device_id, const uint16_t *d_head_dist, int64_t head_stride, int n_head,
+                             int64_t head_label_base, const float *d_dist_lists, const int32_t *d_label_lists,
+                             int n_lists, int64_t list_stride, int64_t query_stride, int nq, int k,
+                             int32_t *d_labels_out, float *d_dist_out, void *stream);
+
 /* ---------------------------------------------------------------------------
  * Multi-device index (north_star: "the code database shards
  * naturally across the 8 GPUs of one node with a final RCCL all-gather of per-shard top-k").
@@ -300,8 +319,8 @@ int vaqhip_merge_topk_strided_device(int device_id, const float *d_dist_lists,
  *                served in sets of that size.  last_merge_ms then includes the second pass.
  *                No effect -- the result is then what each shard's own option gives, merged by
  *                (distance, label), as on a single index where the option has no effect either --
- *                with TI, with VAQHIP_SUM_SEQUENTIAL, with FAST (refused for a multi index anyway)
- *                and for k == VAQHIP_MAX_K.  One shard: that shard's own replay.
+ *                with TI, with VAQHIP_SUM_SEQUENTIAL, with FAST (whose sharded answer is the single index's
+ *                slot for slot already) and for k == VAQHIP_MAX_K.  One shard: that shard's own replay.
  *   "exact_batch" list entries per batch of that second pass; 0 (default) = max(64, a 16th of the
  *                set's queries); never fewer than a 256th of them.  Results do not depend on it.
  * ------------------------------------------------------------------------- */
@@ -331,6 +350,20 @@ int vaqhip_multi_search_device(vaqhip_multi *mx, const float *d_queries, int nq,
 int vaqhip_multi_set_ti_clusters(vaqhip_multi *mx, const float *clusters_rowmajor, int T, int seg_num);
 int vaqhip_multi_set_method(vaqhip_multi *mx, unsigned methods, float visit);
 int vaqhip_multi_set_option(vaqhip_multi *mx, const char *key, int64_t value);
+/* Method FAST on a multi index: labels and distances are the single index's over all rows, slot for slot.
+ * Every shard sends the distances of the head rows it holds (the first min(k, N) rows of the database, which
+ * span several shards when N / n_devices < k) and the top-k of its other rows by (distance, row) in the ONE
+ * all-gather; shard 0 sorts the head and merges (vaqhip_merge_fast_device).  The rows being sharded, the
+ * [queries][rows] distance matrix of a chunk is a shard's, not the database's.  One shard: the single-index
+ * search itself.  set_lut_quantization gives every shard the same mOffsets / mScale; learn_quantization is
+ * vaqhip_learn_quantization once, on shard 0 (the rows play no part in it), replicated to the others -- the
+ * same values as on a single index, bit for bit.  Both leave the caller's current device as it was.
+ * Call order: the quantisation first.  vaqhip_multi_set_method with FAST alone stays VAQHIP_EUNSUPPORTED until one
+ * of these two calls has given every shard the same quantisation (a multi index without one cannot run FAST on
+ * any shard; it is refused where the method is chosen, not at the first search). */
+int vaqhip_multi_set_lut_quantization(vaqhip_multi *mx, const float *offsets, const float *scale);
+int vaqhip_multi_learn_quantization(vaqhip_multi *mx, const float *X_rowmajor, int64_t n, int projected,
+                                    float sample_ratio, float *offsets_out, float *scale_out);
 typedef struct {
   int n_devices;
   int exchange;              /* what the last search used: 0 none (one shard), 1 RCCL all-gather, 2 copies */

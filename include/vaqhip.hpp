@@ -205,6 +205,7 @@ public:
                                      mDevices.data(), 0u));
       codes_set_ = false;
       ti_set_ = false;
+      fastQuantPushed_ = false;
     }
     if ((mMethods & NNMethod::TI) && !ti_set_) {
       const int seg = mTISegmentNum == -1 ? M : mTISegmentNum;
@@ -216,7 +217,8 @@ public:
       checkMulti(vaqhip_multi_set_ti_clusters(mh_, nullptr, 0, 0));
       ti_set_ = false;
     }
-    checkMulti(vaqhip_multi_set_method(mh_, mMethods, mVisit));
+    // (FAST alone is only taken once the quantisation is on the shards: VaqHipFast pushes it and sets the method)
+    if (!fastOnly() || fastQuantPushed_) checkMulti(vaqhip_multi_set_method(mh_, mMethods, mVisit));
     if (!codes_set_) {
       if (mCodebook.cols() != (size_t)M && mCodebook.rows() != 0)
         throw Error(VAQHIP_EINVAL, "vaqhip: mCodebook is not N x M");
@@ -364,6 +366,8 @@ public:
 protected:
   // NNMethod bits parseMethodString accepts and search() runs
   uint32_t methodsAllowed_ = NNMethod::Heap | NNMethod::EA | NNMethod::TI;
+  bool fastOnly() const { return (mMethods & NNMethod::Fast) && !(mMethods & (NNMethod::TI | NNMethod::EA | NNMethod::Heap)); }
+  bool fastQuantPushed_ = false;  // the current multi-device index holds a FAST quantisation
 
 private:
   static void checkMulti(int rc) {
@@ -381,7 +385,8 @@ private:
 // labels and distances as the reference returns them, slot for slot.  The extra
 // members are the reference's: mOffsets, mScale (set by learnQuantization, or by
 // hand) and mCodebookCMajor (filled by encode).  Method precedence is the
-// reference's, TI > EA > HEAP > FAST.  Single device only.
+// reference's, TI > EA > HEAP > FAST.  With setDevices the quantisation goes to every shard and the sharded
+// search returns the same slots (vaqhip.h, vaqhip_multi_set_lut_quantization).
 // ---------------------------------------------------------------------------
 class VaqHipFast : public VaqHip {
 public:
@@ -417,9 +422,14 @@ public:
     sync();
     mOffsets.assign((size_t)mHighestSubs(), 0.0f);
     mScale.assign((size_t)mHighestSubs(), 0.0f);
-    check(vaqhip_learn_quantization(handle(), XTrain.data(), (int64_t)XTrain.rows(), 0, sampleRatio, mOffsets.data(),
-                                    mScale.data()));
-    pushedFor_ = handle();
+    if (multiHandle())
+      checkFast(vaqhip_multi_learn_quantization(multiHandle(), XTrain.data(), (int64_t)XTrain.rows(), 0, sampleRatio,
+                                                mOffsets.data(), mScale.data()), true),
+          fastQuantPushed_ = true;
+    else
+      check(vaqhip_learn_quantization(handle(), XTrain.data(), (int64_t)XTrain.rows(), 0, sampleRatio, mOffsets.data(),
+                                      mScale.data()));
+    pushedFor_ = current();
     pushedOffsets_ = mOffsets;
     pushedScale_ = mScale;
   }
@@ -428,17 +438,29 @@ public:
   template <class Mat> LabelDistVecF search(const Mat &XTest, const int k, bool verbose = false) {
     sync();
     if (mOffsets.size() == (size_t)mHighestSubs() && mScale.size() == mOffsets.size() &&
-        (pushedFor_ != handle() || pushedOffsets_ != mOffsets || pushedScale_ != mScale)) {
-      check(vaqhip_index_set_lut_quantization(handle(), mOffsets.data(), mScale.data()));
-      pushedFor_ = handle();
+        (pushedFor_ != current() || pushedOffsets_ != mOffsets || pushedScale_ != mScale ||
+         (multiHandle() && !fastQuantPushed_))) {
+      if (multiHandle())
+        checkFast(vaqhip_multi_set_lut_quantization(multiHandle(), mOffsets.data(), mScale.data()), true),
+            fastQuantPushed_ = true;
+      else
+        check(vaqhip_index_set_lut_quantization(handle(), mOffsets.data(), mScale.data()));
+      pushedFor_ = current();
       pushedOffsets_ = mOffsets;
       pushedScale_ = mScale;
     }
+    if (multiHandle() && fastOnly() && !fastQuantPushed_)
+      throw Error(VAQHIP_ESTATE, "vaqhip: method FAST needs mOffsets / mScale (learnQuantization) first");
     return VaqHip::search(XTest, k, verbose);
   }
 
 private:
-  const vaqhip_index *pushedFor_ = nullptr;
+  // the index the quantisation was last pushed to: the multi-device one when setDevices is in force
+  const void *current() { return multiHandle() ? (const void *)multiHandle() : (const void *)handle(); }
+  static void checkFast(int rc, bool multi) {
+    if (rc < 0) throw Error(rc, std::string("vaqhip: ") + (multi ? vaqhip_multi_last_error() : vaqhip_last_error()));
+  }
+  const void *pushedFor_ = nullptr;
   std::vector<float> pushedOffsets_, pushedScale_;
 };
 

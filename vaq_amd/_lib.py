@@ -20,12 +20,13 @@ SYMBOLS = [
     "vaqhip_search", "vaqhip_search_projected",
     "vaqhip_search_device", "vaqhip_search_staged_supported", "vaqhip_search_begin_device",
     "vaqhip_search_finish_device", "vaqhip_build_lut", "vaqhip_project", "vaqhip_merge_topk_device",
-    "vaqhip_merge_topk_strided_device",
+    "vaqhip_merge_topk_strided_device", "vaqhip_merge_fast_device",
     "vaqhip_encode", "vaqhip_encode_device", "vaqhip_refine", "vaqhip_refine_device",
     "vaqhip_index_info", "vaqhip_set_option", "vaqhip_last_timing", "vaqhip_last_error",
     "vaqhip_version", "vaqhip_device_count",
     "vaqhip_multi_create", "vaqhip_multi_destroy", "vaqhip_multi_set_codes_u16", "vaqhip_multi_add_codes_u16",
     "vaqhip_multi_search", "vaqhip_multi_search_device", "vaqhip_multi_set_ti_clusters", "vaqhip_multi_set_method", "vaqhip_multi_set_option",
+    "vaqhip_multi_set_lut_quantization", "vaqhip_multi_learn_quantization",
     "vaqhip_multi_get_info", "vaqhip_multi_shard", "vaqhip_multi_last_error",
 ]
 MAX_DEVICES = 16
@@ -123,6 +124,7 @@ def load():
     L.vaqhip_refine.argtypes = [i32, vp, i32, i32, vp, i64, vp, i32, i32, vp, vp]
     L.vaqhip_refine_device.argtypes = [i32, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp]
     L.vaqhip_merge_topk_strided_device.argtypes = [i32, vp, vp, i32, i64, i64, i32, i32, vp, vp, vp]
+    L.vaqhip_merge_fast_device.argtypes = [i32, vp, i64, i32, i64, vp, vp, i32, i64, i64, i32, i32, vp, vp, vp]
     L.vaqhip_index_info.argtypes = [vp, C.POINTER(Info)]
     L.vaqhip_set_option.argtypes = [vp, C.c_char_p, i64]
     L.vaqhip_last_timing.argtypes = [vp, C.POINTER(Timing)]
@@ -138,6 +140,8 @@ def load():
     L.vaqhip_multi_set_ti_clusters.argtypes = [vp, vp, i32, i32]
     L.vaqhip_multi_set_method.argtypes = [vp, C.c_uint, C.c_float]
     L.vaqhip_multi_set_option.argtypes = [vp, C.c_char_p, i64]
+    L.vaqhip_multi_set_lut_quantization.argtypes = [vp, vp, vp]
+    L.vaqhip_multi_learn_quantization.argtypes = [vp, vp, i64, i32, C.c_float, vp, vp]
     L.vaqhip_multi_get_info.argtypes = [vp, C.POINTER(MultiInfo)]
     L.vaqhip_multi_shard.argtypes = [vp, i32]
     L.vaqhip_multi_shard.restype = vp

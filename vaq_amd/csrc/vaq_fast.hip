@@ -136,13 +136,14 @@ fast_scan_kernel(const uint32_t *__restrict__ codes, int64_t n_pad, int M, const
 }
 
 __global__ void fast_head_sort_kernel(const uint16_t *__restrict__ dist, int64_t n_pad, int nq, int kk,
-                                      uint32_t *__restrict__ scratch, uint16_t *__restrict__ order) {
+                                      uint32_t *__restrict__ scratch, int64_t scratch_stride,
+                                      uint16_t *__restrict__ order, int64_t order_stride) {
   const int q = blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= nq) return;
-  uint32_t *f = scratch + (int64_t)q * kk;
+  uint32_t *f = scratch + (int64_t)q * scratch_stride;
   for (int i = 0; i < kk; i++) f[i] = ((uint32_t)dist[(int64_t)q * n_pad + i] << 16) | (uint32_t)i;
   stdsort::sort(f, kk);
-  for (int i = 0; i < kk; i++) order[(int64_t)q * kk + i] = (uint16_t)(f[i] & 0xffffu);
+  for (int i = 0; i < kk; i++) order[(int64_t)q * order_stride + i] = (uint16_t)(f[i] & 0xffffu);
 }
 
 constexpr int SEL_THREADS = 1024;
@@ -174,10 +175,13 @@ __device__ inline int block_scan(int v, int *wsum, int &total) {
 // kk-th smallest distance, and how many rows lie below it.  Only these rows can be among the kk best by
 // (dist, seq): every row below tau, the rows < kk at tau (seq < kk), and the first rows >= kk at tau in
 // row order (seq = row there).  They are sorted by (dist, seq) and the first kk written.
+// TAIL (one shard of a sharded index): rows < skip are left out of all three passes, there is no `order`,
+// every row's seq is the row, and kk = min(k, n - skip).
+template <bool TAIL>
 __global__ void __launch_bounds__(SEL_THREADS)
 fast_select_kernel(const uint16_t *__restrict__ dist, int64_t n_pad, int64_t n, int k, int nbins,
-                   const uint16_t *__restrict__ order, int kk, int64_t id_base, int32_t *__restrict__ labels,
-                   float *__restrict__ out_dist) {
+                   const uint16_t *__restrict__ order, int kk, int64_t skip, int64_t id_base,
+                   int32_t *__restrict__ labels, float *__restrict__ out_dist) {
   // the histogram and, once tau is known, the candidate keys (dist << 32 | seq) share the LDS
   extern __shared__ unsigned long long sel_smem[];
   unsigned *hist = reinterpret_cast<unsigned *>(sel_smem);
@@ -188,7 +192,8 @@ fast_select_kernel(const uint16_t *__restrict__ dist, int64_t n_pad, int64_t n, 
   const int q = blockIdx.x;
   const int tid = threadIdx.x;
   const uint16_t *d = dist + (int64_t)q * n_pad;
-  const uint16_t *ord = order + (int64_t)q * kk;
+  const uint16_t *ord = TAIL ? nullptr : order + (int64_t)q * kk;
+  const int hk = TAIL ? 0 : kk;  // rows whose seq comes from `order`
   int32_t *lab_out = labels + (int64_t)q * k;
   float *dist_out = out_dist + (int64_t)q * k;
   for (int i = kk + tid; i < k; i += SEL_THREADS) {
@@ -197,7 +202,8 @@ fast_select_kernel(const uint16_t *__restrict__ dist, int64_t n_pad, int64_t n, 
   }
   if (kk == 0) return;
   for (int i = tid; i < nbins; i += SEL_THREADS) hist[i] = 0;
-  for (int i = tid; i < kk; i += SEL_THREADS) inv[ord[i]] = (uint16_t)i;
+  if (!TAIL)
+    for (int i = tid; i < kk; i += SEL_THREADS) inv[ord[i]] = (uint16_t)i;
   if (tid == 0) s_count = 0;
   __syncthreads();
   // 8 distances per 16-byte load (rows are padded to FAST_ROW_PAD, the row start is 64-byte aligned)
@@ -218,7 +224,7 @@ fast_select_kernel(const uint16_t *__restrict__ dist, int64_t n_pad, int64_t n, 
       const uint32_t ws[4] = {w[u].x, w[u].y, w[u].z, w[u].w};
 #pragma unroll
       for (int j = 0; j < 8; j++)
-        if (v * 8 + j < n) atomicAdd(&hist[min((int)((ws[j >> 1] >> (16 * (j & 1))) & 0xffffu), nbins - 1)], 1u);
+        if (v * 8 + j < n && (!TAIL || v * 8 + j >= skip)) atomicAdd(&hist[min((int)((ws[j >> 1] >> (16 * (j & 1))) & 0xffffu), nbins - 1)], 1u);
     }
   }
   __syncthreads();
@@ -253,8 +259,8 @@ fast_select_kernel(const uint16_t *__restrict__ dist, int64_t n_pad, int64_t n, 
       const int64_t i = (v0 + (int64_t)(j >> 3) * SEL_THREADS) * 8 + (j & 7);
       const uint32_t ws[4] = {w[j >> 3].x, w[j >> 3].y, w[j >> 3].z, w[j >> 3].w};
       const int di = (int)((ws[(j & 7) >> 1] >> (16 * (j & 1))) & 0xffffu);
-      if (i < n && (di < tau || (di == tau && i < kk))) {
-        const unsigned seq = i < kk ? (unsigned)inv[i] : (unsigned)i;
+      if (i < n && (!TAIL || i >= skip) && (di < tau || (di == tau && i < hk))) {
+        const unsigned seq = i < hk ? (unsigned)inv[i] : (unsigned)i;
         const int slot = atomicAdd(&s_count, 1);
         if (slot < 2 * kk) cand[slot] = ((unsigned long long)di << 32) | seq;
       }
@@ -264,7 +270,7 @@ fast_select_kernel(const uint16_t *__restrict__ dist, int64_t n_pad, int64_t n, 
   int count = min(s_count, 2 * kk);  // < kk rows below tau + <= kk rows < kk at tau
   // the first `need` rows >= kk at tau, in row order
   int taken = 0;
-  for (int64_t base = kk; base < n && taken < need; base += SEL_THREADS) {
+  for (int64_t base = TAIL ? skip : (int64_t)kk; base < n && taken < need; base += SEL_THREADS) {
     const int64_t i = base + tid;
     const int flag = (i < n && d[i] == tau) ? 1 : 0;
     int tot;
@@ -297,9 +303,97 @@ fast_select_kernel(const uint16_t *__restrict__ dist, int64_t n_pad, int64_t n, 
   for (int i = tid; i < kk; i += SEL_THREADS) {
     const unsigned long long key = cand[i];
     const unsigned seq = (unsigned)key;
-    const int64_t row = seq < (unsigned)kk ? (int64_t)ord[seq] : (int64_t)seq;
+    const int64_t row = seq < (unsigned)hk ? (int64_t)ord[seq] : (int64_t)seq;
     lab_out[i] = (int32_t)(id_base + row);
     dist_out[i] = (float)(unsigned)(key >> 32);
+  }
+}
+
+__global__ void fast_head_copy_kernel(const uint16_t *__restrict__ dist, int64_t n_pad, int nq, int h,
+                                      uint16_t *__restrict__ out, int64_t out_stride) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)nq * h) return;
+  const int64_t q = i / h, p = i % h;
+  out[q * out_stride + p] = dist[q * n_pad + p];
+}
+
+__global__ void fast_head_gather_kernel(const uint16_t *__restrict__ planes, int64_t plane_stride, FastHeadParts parts,
+                                        int nq, int kk, uint16_t *__restrict__ head) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)nq * kk) return;
+  const int p = (int)(i % kk);
+  int g = 0;
+  while (g + 1 < parts.n_parts && p >= parts.start[g + 1]) g++;  // (a part without head rows owns nothing)
+  head[i] = planes[(int64_t)g * plane_stride + i];
+}
+
+// One workgroup per query (a few KiB of LDS at k = 100: eight workgroups, 32 waves, per CU).  The lists'
+// distances sit in LDS as uint16, 0xffff = no entry, every list padded to k slots; the lists are ascending, so
+// the place of entry p of list l in the stable merge is p + the entries of earlier lists <= its distance + the
+// entries of later lists < it: one binary search per other list.  The places are a permutation, so every
+// output slot below the number of entries is written exactly once, and equal distances need no special case.
+constexpr int MERGE_THREADS = 256;
+__global__ void __launch_bounds__(MERGE_THREADS)
+fast_merge_kernel(const uint32_t *head_sorted, int64_t head_stride, int kk, int64_t head_label_base,
+                  const float *__restrict__ dist_lists, const int32_t *__restrict__ label_lists, int n_lists,
+                  int64_t list_stride, int64_t query_stride, int k, int32_t *labels, float *out_dist) {
+  extern __shared__ uint16_t mg_d[];  // [1 + n_lists][k] distances, then the head rows [kk]
+  __shared__ int s_total;
+  const int q = blockIdx.x, tid = threadIdx.x;
+  const int L = n_lists + 1;
+  uint16_t *hrow = mg_d + (size_t)L * k;
+  if (tid == 0) s_total = 0;
+  int mine = 0;
+  for (int i = tid; i < k; i += MERGE_THREADS) {
+    uint16_t d = 0xffffu;
+    if (i < kk) {
+      const uint32_t item = head_sorted[(int64_t)q * head_stride + i];
+      d = (uint16_t)(item >> 16);
+      hrow[i] = (uint16_t)(item & 0xffffu);
+      mine++;
+    }
+    mg_d[i] = d;
+  }
+  for (int e = tid; e < n_lists * k; e += MERGE_THREADS) {
+    const int l = e / k, i = e % k;
+    const int64_t at = (int64_t)l * list_stride + (int64_t)q * query_stride + i;
+    uint16_t d = 0xffffu;
+    if (label_lists[at] >= 0) {
+      d = (uint16_t)fminf(fmaxf(dist_lists[at], 0.0f), 65534.0f);
+      mine++;
+    }
+    mg_d[k + e] = d;
+  }
+  __syncthreads();  // head_sorted (which may be this query's row of `labels`) is not read after this point
+  if (mine) atomicAdd(&s_total, mine);
+  for (int e = tid; e < L * k; e += MERGE_THREADS) {
+    const int l = e / k, p = e % k;
+    const uint32_t d = mg_d[e];
+    if (d == 0xffffu) continue;
+    int place = p;
+    for (int l2 = 0; l2 < L && place < k; l2++) {
+      if (l2 == l) continue;
+      const uint16_t *a = mg_d + (size_t)l2 * k;
+      const uint32_t t = d + (l2 < l ? 1u : 0u);  // entries below t: <= d in an earlier list, < d in a later one
+      int lo = 0, hi = k;
+      while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] < t) lo = mid + 1;
+        else hi = mid;
+      }
+      place += lo;
+    }
+    if (place < k) {
+      labels[(int64_t)q * k + place] =
+          l == 0 ? (int32_t)(head_label_base + hrow[p])
+                 : label_lists[(int64_t)(l - 1) * list_stride + (int64_t)q * query_stride + p];
+      out_dist[(int64_t)q * k + place] = (float)d;
+    }
+  }
+  __syncthreads();
+  for (int i = min(s_total, k) + tid; i < k; i += MERGE_THREADS) {
+    labels[(int64_t)q * k + i] = -1;
+    out_dist[(int64_t)q * k + i] = FLT_MAX;
   }
 }
 
@@ -358,7 +452,15 @@ hipError_t launch_fast_head_sort(const uint16_t *dist, int64_t n_pad, int nq, in
                                  uint16_t *order, hipStream_t st) {
   if (nq <= 0 || kk <= 0) return hipSuccess;
   if (kk > 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(fast_head_sort_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, dist, n_pad, nq, kk, scratch, order);
+  return launch_fast_head_sort_strided(dist, n_pad, nq, kk, scratch, kk, order, kk, st);
+}
+
+hipError_t launch_fast_head_sort_strided(const uint16_t *dist, int64_t dist_stride, int nq, int kk, uint32_t *scratch,
+                                         int64_t scratch_stride, uint16_t *order, int64_t order_stride, hipStream_t st) {
+  if (nq <= 0 || kk <= 0) return hipSuccess;
+  if (kk > 1024 || scratch_stride < kk || order_stride < kk) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(fast_head_sort_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, dist, dist_stride, nq, kk, scratch,
+                     scratch_stride, order, order_stride);
   return hipGetLastError();
 }
 
@@ -370,11 +472,60 @@ hipError_t launch_fast_select(const uint16_t *dist, int64_t n_pad, int64_t n, in
   const int kk = (int)std::min<int64_t>(k, n);
   const int nbins = 255 * M + 1;
   const size_t lds = std::max<size_t>((size_t)nbins * 4, (size_t)SEL_CAND * 8);
-  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fast_select_kernel),
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fast_select_kernel<false>),
                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(fast_select_kernel, dim3(nq), dim3(SEL_THREADS), lds, st, dist, n_pad, n, k, nbins, order, kk,
-                     id_base, labels, out_dist);
+  hipLaunchKernelGGL(fast_select_kernel<false>, dim3(nq), dim3(SEL_THREADS), lds, st, dist, n_pad, n, k, nbins, order,
+                     kk, (int64_t)0, id_base, labels, out_dist);
+  return hipGetLastError();
+}
+
+hipError_t launch_fast_select_tail(const uint16_t *dist, int64_t n_pad, int64_t n, int64_t head_rows, int nq, int k,
+                                   int M, int64_t id_base, int32_t *labels, float *out_dist, hipStream_t st) {
+  if (nq <= 0) return hipSuccess;
+  if (k <= 0 || k > 1024 || 3 * k > SEL_CAND || head_rows < 0 || head_rows > n) return hipErrorInvalidValue;
+  const int kk = (int)std::min<int64_t>(k, n - head_rows);
+  const int nbins = 255 * M + 1;
+  const size_t lds = std::max<size_t>((size_t)nbins * 4, (size_t)SEL_CAND * 8);
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(fast_select_kernel<true>),
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(fast_select_kernel<true>, dim3(nq), dim3(SEL_THREADS), lds, st, dist, n_pad, n, k, nbins,
+                     (const uint16_t *)nullptr, kk, head_rows, id_base, labels, out_dist);
+  return hipGetLastError();
+}
+
+hipError_t launch_fast_head_copy(const uint16_t *dist, int64_t n_pad, int nq, int h, uint16_t *out,
+                                 int64_t out_stride, hipStream_t st) {
+  if (nq <= 0 || h <= 0) return hipSuccess;
+  if (h > n_pad || out_stride < h) return hipErrorInvalidValue;
+  const int64_t n = (int64_t)nq * h;
+  hipLaunchKernelGGL(fast_head_copy_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dist, n_pad, nq, h, out,
+                     out_stride);
+  return hipGetLastError();
+}
+
+hipError_t launch_fast_head_gather(const uint16_t *planes, int64_t plane_stride, FastHeadParts parts, int nq, int kk,
+                                   uint16_t *head, hipStream_t st) {
+  if (nq <= 0 || kk <= 0) return hipSuccess;
+  if (parts.n_parts < 1 || parts.n_parts > FAST_MAX_LISTS || parts.start[0] != 0 || parts.start[parts.n_parts] != kk)
+    return hipErrorInvalidValue;
+  for (int g = 0; g < parts.n_parts; g++)
+    if (parts.start[g] > parts.start[g + 1]) return hipErrorInvalidValue;
+  const int64_t n = (int64_t)nq * kk;
+  hipLaunchKernelGGL(fast_head_gather_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, planes, plane_stride,
+                     parts, nq, kk, head);
+  return hipGetLastError();
+}
+
+hipError_t launch_fast_merge(const uint32_t *head_sorted, int64_t head_stride, int kk, int64_t head_label_base,
+                             const float *dist_lists, const int32_t *label_lists, int n_lists, int64_t list_stride,
+                             int64_t query_stride, int nq, int k, int32_t *labels, float *out_dist, hipStream_t st) {
+  if (nq <= 0) return hipSuccess;
+  if (k <= 0 || k > 1024 || kk < 0 || kk > k || n_lists < 0 || n_lists > FAST_MAX_LISTS) return hipErrorInvalidValue;
+  const size_t lds = ((size_t)(n_lists + 1) * k + kk) * sizeof(uint16_t);  // <= 36 KiB
+  hipLaunchKernelGGL(fast_merge_kernel, dim3(nq), dim3(MERGE_THREADS), lds, st, head_sorted, head_stride, kk,
+                     head_label_base, dist_lists, label_lists, n_lists, list_stride, query_stride, k, labels, out_dist);
   return hipGetLastError();
 }
 

@@ -1061,10 +1061,18 @@ int fast_small_luts(vaqhip_index *ix, const float *qp, int n, hipStream_t st) {
   return VAQHIP_OK;
 }
 
+// One shard's part of a sharded FAST search (vaqhip_internal_search_fast_shard_device): the shard's first
+// head_rows rows belong to the head of the whole index (positions head_at.. of its kk_all); their distances go
+// to d_head [nq][kk_all], the other rows are ranked by (dist, row)
+struct FastShardPart {
+  int head_rows, head_at, kk_all;
+  uint16_t *d_head;
+};
+
 // VAQ::searchFast for nq queries (device pointers): per chunk of queries, tables -> uint8 tables -> every
 // row's distance (matrix cores) -> std::sort of rows < k -> the k best by (dist, seq)
 int search_fast(vaqhip_index *ix, const float *d_queries, int nq, int k, int projected, int32_t *d_labels,
-                float *d_dist, hipStream_t st) {
+                float *d_dist, hipStream_t st, const FastShardPart *part = nullptr) {
   if (ix->N < 0) return fail(VAQHIP_ESTATE, "search before codes were set");
   if (ix->staged.open)
     return fail(VAQHIP_ESTATE, "a staged search is open on this index: call vaqhip_search_finish_device first");
@@ -1087,8 +1095,10 @@ int search_fast(vaqhip_index *ix, const float *d_queries, int nq, int k, int pro
   HIP_TRY(ix->w_lutref.ensure((size_t)chunk * ix->M * (1 << ix->max_bits) * sizeof(float)));
   HIP_TRY(ix->w_fast_small.ensure((size_t)chunk * ix->M * 16));
   HIP_TRY(ix->w_fast_dist.ensure((size_t)chunk * n_pad * sizeof(uint16_t)));
-  HIP_TRY(ix->w_fast_order.ensure((size_t)chunk * std::max(kk, 1) * sizeof(uint16_t)));
-  HIP_TRY(ix->w_fast_scratch.ensure((size_t)chunk * std::max(kk, 1) * sizeof(uint32_t)));
+  if (!part) {
+    HIP_TRY(ix->w_fast_order.ensure((size_t)chunk * std::max(kk, 1) * sizeof(uint16_t)));
+    HIP_TRY(ix->w_fast_scratch.ensure((size_t)chunk * std::max(kk, 1) * sizeof(uint32_t)));
+  }
   for (int q0 = 0; q0 < nq; q0 += chunk) {
     const int n = std::min(chunk, nq - q0);
     const float *qp = d_queries + (size_t)q0 * ix->D;
@@ -1097,6 +1107,17 @@ int search_fast(vaqhip_index *ix, const float *d_queries, int nq, int k, int pro
       qp = ix->w_qproj.as<float>();
     }
     if (int rc = fast_small_luts(ix, qp, n, st)) return rc;
+    if (part) {
+      // the head is sorted where all of it is known (shard 0, after the exchange), not here
+      if (N > 0)
+        HIP_TRY(vaq::launch_fast_scan(ix->d_fast_codes.as<uint32_t>(), n_pad, ix->M, ix->w_fast_small.as<uint8_t>(), n,
+                                      ix->w_fast_dist.as<uint16_t>(), ix->n_cu, st));
+      HIP_TRY(vaq::launch_fast_head_copy(ix->w_fast_dist.as<uint16_t>(), n_pad, n, part->head_rows,
+                                         part->d_head + (size_t)q0 * part->kk_all + part->head_at, part->kk_all, st));
+      HIP_TRY(vaq::launch_fast_select_tail(ix->w_fast_dist.as<uint16_t>(), n_pad, N, part->head_rows, n, k, ix->M,
+                                           ix->id_base, d_labels + (size_t)q0 * k, d_dist + (size_t)q0 * k, st));
+      continue;
+    }
     if (N > 0) {
       HIP_TRY(vaq::launch_fast_scan(ix->d_fast_codes.as<uint32_t>(), n_pad, ix->M, ix->w_fast_small.as<uint8_t>(), n,
                                     ix->w_fast_dist.as<uint16_t>(), ix->n_cu, st));
@@ -1702,6 +1723,45 @@ int vaqhip_internal_exact_finish_device(int device, const int32_t *d_state, cons
   return VAQHIP_OK;
 }
 
+// ---- FAST across the shards of a multi-device index (vaqhip_internal.h) ----
+int vaqhip_internal_fast_in_force(vaqhip_index *ix) {
+  if (!ix) return 0;
+  std::lock_guard<std::mutex> lk(ix->mu);
+  return fast_only(ix) ? 1 : 0;
+}
+
+int vaqhip_internal_search_fast_shard_device(vaqhip_index *ix, const float *d_queries, int nq, int k, int projected,
+                                             int64_t row_offset, int kk, int32_t *d_labels, float *d_dist,
+                                             uint16_t *d_head, void *stream) {
+  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
+  if (row_offset < 0 || kk < 0 || kk > k || (kk > 0 && !d_head)) return fail(VAQHIP_EINVAL, "bad head description");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  DeviceGuard g(ix->device);
+  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  if (!fast_only(ix)) return fail(VAQHIP_ESTATE, "method FAST is not in force on this shard");
+  FastShardPart part;
+  part.kk_all = kk;
+  part.head_at = (int)std::min<int64_t>(row_offset, kk);
+  part.head_rows = (int)std::max<int64_t>(0, std::min<int64_t>(kk - part.head_at, std::max<int64_t>(ix->N, 0)));
+  part.d_head = d_head;
+  return search_fast(ix, d_queries, nq, k, projected, d_labels, d_dist, static_cast<hipStream_t>(stream), &part);
+}
+
+int vaqhip_internal_fast_head_gather_device(int device, const uint16_t *d_planes, int64_t plane_stride, int n_parts,
+                                            const int *start, int nq, int kk, uint16_t *d_head, void *stream) {
+  if (n_parts < 1 || n_parts > vaq::FAST_MAX_LISTS || !start || nq < 0 || kk < 0 || plane_stride < 0)
+    return fail(VAQHIP_EINVAL, "bad arguments");
+  if (nq == 0 || kk == 0) return VAQHIP_OK;
+  if (!d_planes || !d_head) return fail(VAQHIP_EINVAL, "null pointer");
+  vaq::FastHeadParts parts;
+  parts.n_parts = n_parts;
+  for (int g = 0; g <= vaq::FAST_MAX_LISTS; g++) parts.start[g] = start[std::min(g, n_parts)];
+  DeviceGuard g(device);
+  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", device);
+  HIP_TRY(vaq::launch_fast_head_gather(d_planes, plane_stride, parts, nq, kk, d_head, static_cast<hipStream_t>(stream)));
+  return VAQHIP_OK;
+}
+
 int vaqhip_search_device(vaqhip_index *ix, const float *d_queries, int nq, int k, int projected,
                          int32_t *d_labels, float *d_dist, void *stream) {
   if (!ix) return fail(VAQHIP_EINVAL, "index is null");
@@ -2022,6 +2082,33 @@ int vaqhip_merge_topk_strided_device(int device_id, const float *d_dist_lists,
   HIP_TRY(vaq::launch_merge(d_dist_lists, d_label_lists, nullptr, n_lists, list_stride, query_stride, nq, k, 0, 1,
                             d_labels_out, d_dist_out, nullptr, nullptr, nullptr,
                             static_cast<hipStream_t>(stream)));
+  return VAQHIP_OK;
+}
+
+int vaqhip_merge_fast_device(int device_id, const uint16_t *d_head_dist, int64_t head_stride, int n_head,
+                             int64_t head_label_base, const float *d_dist_lists, const int32_t *d_label_lists,
+                             int n_lists, int64_t list_stride, int64_t query_stride, int nq, int k,
+                             int32_t *d_labels_out, float *d_dist_out, void *stream) {
+  if (n_lists < 0 || nq < 0 || k <= 0 || n_head < 0) return fail(VAQHIP_EINVAL, "bad sizes");
+  if (k > VAQHIP_MAX_K) return fail(VAQHIP_EUNSUPPORTED, "k=%d > %d", k, VAQHIP_MAX_K);
+  if (n_lists > vaq::FAST_MAX_LISTS) return fail(VAQHIP_EUNSUPPORTED, "at most %d lists per merge", vaq::FAST_MAX_LISTS);
+  if (n_head > k) return fail(VAQHIP_EINVAL, "n_head=%d > k=%d: the head is the first min(k, N) rows", n_head, k);
+  if (list_stride < 0 || query_stride < 0 || head_stride < 0 || (n_head > 0 && head_stride < n_head))
+    return fail(VAQHIP_EINVAL, "bad stride");
+  if (head_label_base < 0 || head_label_base + n_head > 0x7fffffffLL) return fail(VAQHIP_ERANGE, "head labels past 2^31");
+  if ((n_lists > 0 && (!d_dist_lists || !d_label_lists)) || (n_head > 0 && !d_head_dist) || !d_labels_out || !d_dist_out)
+    return fail(VAQHIP_EINVAL, "null pointer");
+  if (nq == 0) return VAQHIP_OK;
+  DeviceGuard g(device_id);
+  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", device_id);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  // every query's output rows serve its head sort first: the items in the label row (n_head <= k words), the
+  // order in the distance row; the merge reads the items whole before it writes
+  uint32_t *items = reinterpret_cast<uint32_t *>(d_labels_out);
+  HIP_TRY(vaq::launch_fast_head_sort_strided(d_head_dist, head_stride, nq, n_head, items, k,
+                                             reinterpret_cast<uint16_t *>(d_dist_out), 2 * (int64_t)k, st));
+  HIP_TRY(vaq::launch_fast_merge(items, k, n_head, head_label_base, d_dist_lists, d_label_lists, n_lists, list_stride,
+                                 query_stride, nq, k, d_labels_out, d_dist_out, st));
   return VAQHIP_OK;
 }
 

@@ -1,5 +1,6 @@
 // vaqhip_internal.h -- entries of the single-device index that only the multi-device host
-// (vaqhip_multi.cpp) calls: the pieces of option "exact_ties" as a chain over shards (vaq_exact.hip).
+// (vaqhip_multi.cpp) calls: the pieces of option "exact_ties" as a chain over shards (vaq_exact.hip), and
+// one shard's part of a FAST search (vaq_fast.hip).
 // Not part of the public interface (include/vaqhip.h).
 #ifndef VAQHIP_INTERNAL_H
 #define VAQHIP_INTERNAL_H
@@ -31,6 +32,24 @@ int vaqhip_internal_exact_link_device(vaqhip_index *ix, int k, const int *d_list
 /* on `device`: the reference's heap_reorder on the last state, into the listed queries' k slots */
 int vaqhip_internal_exact_finish_device(int device, const int32_t *d_state, const int *d_list, const unsigned *d_count,
                                         int n_entries, int k, int32_t *d_labels, float *d_distances, void *stream);
+
+
+/* 1 when FAST is the method in force on this index (none of TI, EA, HEAP set) */
+int vaqhip_internal_fast_in_force(vaqhip_index *ix);
+/* One shard's part of a FAST search over a sharded index ("FAST across shards"), for all
+ * nq queries, chunked by this shard's own row count.  row_offset: the shard's first row within the whole index;
+ * kk = min(k, rows of the whole index), the head.  The shard's rows at index positions < kk are head rows: their
+ * distances are written to d_head[q * kk + position] (uint16; positions other shards own are left alone) and they
+ * are left out of the list.  d_labels / d_distances [nq][k]: the other rows' top min(k, their count) by
+ * (dist, row), labels id_base + row, the rest -1 / FLT_MAX.  VAQHIP_ESTATE while a staged search is open, without
+ * a quantisation, or when FAST is not in force. */
+int vaqhip_internal_search_fast_shard_device(vaqhip_index *ix, const float *d_queries, int nq, int k, int projected,
+                                             int64_t row_offset, int kk, int32_t *d_labels, float *d_distances,
+                                             uint16_t *d_head, void *stream);
+/* on `device`: d_head[q * kk + p] for p < kk from the gathered planes; part g (n_parts <= 16) owns positions
+ * [start[g], start[g + 1]) and holds them at d_planes[g * plane_stride + q * kk + p]; start[n_parts] = kk */
+int vaqhip_internal_fast_head_gather_device(int device, const uint16_t *d_planes, int64_t plane_stride, int n_parts,
+                                            const int *start, int nq, int kk, uint16_t *d_head, void *stream);
 
 #ifdef __cplusplus
 }

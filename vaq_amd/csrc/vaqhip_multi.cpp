@@ -25,6 +25,13 @@
 // g-1's event, takes the heap state by peer copy, runs its link (vaq_exact.hip) and records its own event;
 // shard 0 reorders the state the last shard left into the caller's slots.  Every wait is a stream wait on
 // an event; no kernel waits for another.
+//
+// Method FAST with more than one shard ("FAST across shards"): its answer is ordered by
+// (dist, seq), and seq depends on std::sort's permutation of the first kk = min(k, N) rows of the WHOLE index
+// (the head), so every shard hands over two things in its packed buffer -- the distances of the head rows it
+// holds (never truncated: at most k in all) and the top-k of its other rows by (dist, row) -- and shard 0, after
+// the one all-gather, sorts the gathered head as the single index does and takes the first k of the stable merge
+// by distance of "head, then the shards' lists in shard order".
 #include "vaqhip.h"
 #include "vaqhip_internal.h"
 
@@ -104,8 +111,8 @@ struct Shard {
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;  // this shard's packed result is complete
   float *d_queries = nullptr;
-  int32_t *d_packed = nullptr;    // [2][nq][k]: labels, distance bits
-  int32_t *d_gathered = nullptr;  // [G][2][nq][k] (every device under RCCL; shard 0 with copies)
+  int32_t *d_packed = nullptr;    // [2][nq][k]: labels, distance bits (FAST: + the head plane, [nq][kk] uint16)
+  int32_t *d_gathered = nullptr;  // [G][packed] (every device under RCCL; shard 0 with copies)
   size_t cap_q = 0, cap_p = 0, cap_g = 0;
   ncclComm_t comm = nullptr;
   // "exact_ties" across shards: the replay list (word 0 = count, entries from byte 16), the heap states
@@ -148,6 +155,13 @@ struct vaqhip_multi {
   hipEvent_t flagged = nullptr;   // shard 0: the replay list of the current set is complete
   int32_t *d_final = nullptr;     // shard 0: [2][nq][k] the current set's answer (labels, distances)
   size_t cap_final = 0;
+  // method FAST across shards
+  bool fast_q = false;            // a quantisation was given to every shard (vaqhip_multi_set_lut_quantization / learn)
+  bool fast = false;              // the current search is FAST's sharded form
+  int kk = 0;                     //   min(k, N): rows of the head
+  size_t pk = 0;                  // int32 words of one shard's packed buffer: 2 * nq * k (+ the head plane)
+  uint16_t *d_head = nullptr;     // shard 0: [nq][kk] the gathered head distances
+  size_t cap_head = 0;
   vaqhip_multi_info last = {};
 };
 
@@ -174,6 +188,17 @@ int mfail(int code, const char *fmt, ...) {
     }                                                                                      \
   } while (0)
 
+// the caller's current device, put back when the scope ends
+struct DeviceRestore {
+  int prev = -1;
+  explicit DeviceRestore(bool active = true) {
+    if (active && hipGetDevice(&prev) != hipSuccess) prev = -1;
+  }
+  ~DeviceRestore() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
 int grow(Shard &s, void **p, size_t *cap, size_t bytes) {
   if (bytes <= *cap) return 0;
   if (*p) MHIP(hipFree(*p));
@@ -191,10 +216,12 @@ int run_shard(vaqhip_multi *mx, int g) {
   const size_t plane = (size_t)nq * k;
   MHIP(hipSetDevice(s.device));
   if (int rc = grow(s, reinterpret_cast<void **>(&s.d_queries), &s.cap_q, (size_t)nq * mx->D * 4)) return rc;
-  if (int rc = grow(s, reinterpret_cast<void **>(&s.d_packed), &s.cap_p, 2 * plane * 4)) return rc;
+  if (int rc = grow(s, reinterpret_cast<void **>(&s.d_packed), &s.cap_p, mx->pk * 4)) return rc;
   const bool holds_all = mx->use_rccl || g == 0;
   if (G > 1 && holds_all)
-    if (int rc = grow(s, reinterpret_cast<void **>(&s.d_gathered), &s.cap_g, (size_t)G * 2 * plane * 4)) return rc;
+    if (int rc = grow(s, reinterpret_cast<void **>(&s.d_gathered), &s.cap_g, (size_t)G * mx->pk * 4)) return rc;
+  if (mx->fast && g == 0)
+    if (int rc = grow(s, reinterpret_cast<void **>(&mx->d_head), &mx->cap_head, (size_t)nq * std::max(mx->kk, 1) * 2)) return rc;
   if (g == 0) {
     if (mx->cap_out < 2 * plane * 4) {
       if (mx->d_out_labels) MHIP(hipFree(mx->d_out_labels));
@@ -230,8 +257,10 @@ int run_shard(vaqhip_multi *mx, int g) {
   }
   int32_t *labels = G == 1 ? mx->d_out_labels : s.d_packed;
   float *dist = G == 1 ? mx->d_out_dist : reinterpret_cast<float *>(s.d_packed + plane);
-  const int rc = mx->chain ? vaqhip_internal_search_plain_device(s.ix, s.d_queries, nq, k, mx->projected, labels, dist, s.stream)
-                           : vaqhip_search_device(s.ix, s.d_queries, nq, k, mx->projected, labels, dist, s.stream);
+  const int rc = mx->fast ? vaqhip_internal_search_fast_shard_device(s.ix, s.d_queries, nq, k, mx->projected, s.lo, mx->kk, labels, dist,
+                                                                     reinterpret_cast<uint16_t *>(s.d_packed + 2 * plane), s.stream)
+                 : mx->chain ? vaqhip_internal_search_plain_device(s.ix, s.d_queries, nq, k, mx->projected, labels, dist, s.stream)
+                             : vaqhip_search_device(s.ix, s.d_queries, nq, k, mx->projected, labels, dist, s.stream);
   if (rc) {
     s.err = vaqhip_last_error();
     return rc;
@@ -242,18 +271,17 @@ int run_shard(vaqhip_multi *mx, int g) {
 }
 
 // The exchange step, issued by the CALLING thread once every shard's search is enqueued without error:
-// one ncclAllGather per device inside a group (nq * k * 8 bytes per rank over xGMI).  A shard that
+// one ncclAllGather per device inside a group (nq * k * 8 bytes per rank over xGMI; FAST: + nq * kk * 2).  A shard that
 // failed has returned before this point and no collective was enqueued anywhere, so nothing can be
 // left waiting for a peer that never arrives.
 int exchange_rccl(vaqhip_multi *mx) {
-  const size_t plane = (size_t)mx->nq * mx->k;
   ncclResult_t nr = g_rccl.GroupStart();
   if (nr != 0) return mfail(VAQHIP_EHIP, "ncclGroupStart: %s", g_rccl.GetErrorString(nr));
   ncclResult_t first = 0;
   for (int g = 0; g < mx->G; g++) {
     Shard &s = mx->sh[g];
     if (hipSetDevice(s.device) != hipSuccess) { first = first ? first : -1; continue; }
-    nr = g_rccl.AllGather(s.d_packed, s.d_gathered, 2 * plane, NCCL_INT32, s.comm, s.stream);
+    nr = g_rccl.AllGather(s.d_packed, s.d_gathered, mx->pk, NCCL_INT32, s.comm, s.stream);
     if (nr != 0 && !first) first = nr;
   }
   nr = g_rccl.GroupEnd();
@@ -273,14 +301,28 @@ int gather_and_merge(vaqhip_multi *mx) {
     if (!mx->use_rccl) {
       for (int g = 0; g < G; g++) {
         MHIP(hipStreamWaitEvent(s.stream, mx->sh[g].done, 0));
-        MHIP(hipMemcpyPeerAsync(s.d_gathered + (size_t)g * 2 * plane, s.device, mx->sh[g].d_packed, mx->sh[g].device,
-                                2 * plane * 4, s.stream));
+        MHIP(hipMemcpyPeerAsync(s.d_gathered + (size_t)g * mx->pk, s.device, mx->sh[g].d_packed, mx->sh[g].device,
+                                mx->pk * 4, s.stream));
       }
     }
     MHIP(hipEventRecord(mx->ev[2], s.stream));
-    const int rc = vaqhip_merge_topk_strided_device(
-        s.device, reinterpret_cast<const float *>(s.d_gathered + plane), s.d_gathered, G, (int64_t)(2 * plane),
-        (int64_t)k, nq, k, mx->d_out_labels, mx->d_out_dist, s.stream);
+    int rc;
+    if (mx->fast) {
+      // the head rows' distances from the planes of the shards that hold them, then the head's std::sort and
+      // the stable merge "head, then the shards' lists in shard order"
+      int start[VAQHIP_MAX_DEVICES + 1];
+      for (int g = 0; g <= G; g++) start[g] = g < G ? (int)std::min<int64_t>(mx->sh[g].lo, mx->kk) : mx->kk;
+      rc = vaqhip_internal_fast_head_gather_device(s.device, reinterpret_cast<const uint16_t *>(s.d_gathered + 2 * plane),
+                                                   (int64_t)(2 * mx->pk), G, start, nq, mx->kk, mx->d_head, s.stream);
+      if (!rc)
+        rc = vaqhip_merge_fast_device(s.device, mx->d_head, mx->kk, mx->kk, mx->id_base,
+                                      reinterpret_cast<const float *>(s.d_gathered + plane), s.d_gathered, G,
+                                      (int64_t)mx->pk, (int64_t)k, nq, k, mx->d_out_labels, mx->d_out_dist, s.stream);
+    } else {
+      rc = vaqhip_merge_topk_strided_device(
+          s.device, reinterpret_cast<const float *>(s.d_gathered + plane), s.d_gathered, G, (int64_t)mx->pk,
+          (int64_t)k, nq, k, mx->d_out_labels, mx->d_out_dist, s.stream);
+    }
     if (rc) {
       s.err = vaqhip_last_error();
       return rc;
@@ -476,6 +518,7 @@ void vaqhip_multi_destroy(vaqhip_multi *mx) {
   if (!mx->sh.empty()) (void)hipSetDevice(mx->sh[0].device);
   if (mx->d_out_labels) (void)hipFree(mx->d_out_labels);
   if (mx->d_final) (void)hipFree(mx->d_final);
+  if (mx->d_head) (void)hipFree(mx->d_head);
   for (auto &e : mx->ev)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : {mx->user_ready, mx->consumed, mx->finished, mx->flagged})
@@ -541,9 +584,12 @@ int vaqhip_multi_set_ti_clusters(vaqhip_multi *mx, const float *clusters, int T,
 
 int vaqhip_multi_set_method(vaqhip_multi *mx, unsigned methods, float visit) {
   if (!mx) return mfail(VAQHIP_EINVAL, "multi index is null");
-  if ((methods & VAQHIP_METHOD_FAST) && !(methods & (VAQHIP_METHOD_TI | VAQHIP_METHOD_EA | VAQHIP_METHOD_HEAP)))
-    return mfail(VAQHIP_EUNSUPPORTED, "method FAST is single-index only");
   std::lock_guard<std::mutex> lk(mx->mu);
+  // FAST on its own is taken once every shard holds the SAME quantisation, i.e. after one of the two multi calls
+  // that replicate it; before that the index keeps refusing the method, as it always has
+  if ((methods & VAQHIP_METHOD_FAST) && !(methods & (VAQHIP_METHOD_TI | VAQHIP_METHOD_EA | VAQHIP_METHOD_HEAP)) && !mx->fast_q)
+    return mfail(VAQHIP_EUNSUPPORTED, "method FAST on a multi index needs vaqhip_multi_set_lut_quantization or "
+                                      "vaqhip_multi_learn_quantization first");
   for (auto &s : mx->sh) {
     const int rc = vaqhip_index_set_method(s.ix, methods, visit);
     if (rc) {
@@ -551,6 +597,42 @@ int vaqhip_multi_set_method(vaqhip_multi *mx, unsigned methods, float visit) {
       return rc;
     }
   }
+  return VAQHIP_OK;
+}
+
+int vaqhip_multi_set_lut_quantization(vaqhip_multi *mx, const float *offsets, const float *scale) {
+  if (!mx) return mfail(VAQHIP_EINVAL, "multi index is null");
+  if (!offsets || !scale) return mfail(VAQHIP_EINVAL, "null pointer");
+  std::lock_guard<std::mutex> lk(mx->mu);
+  DeviceRestore keep;
+  for (auto &s : mx->sh) {  // every shard quantises its tables by the same map
+    const int rc = vaqhip_index_set_lut_quantization(s.ix, offsets, scale);
+    if (rc) {
+      g_merr = vaqhip_last_error();
+      return rc;
+    }
+  }
+  mx->fast_q = true;
+  return VAQHIP_OK;
+}
+
+int vaqhip_multi_learn_quantization(vaqhip_multi *mx, const float *X, int64_t n, int projected, float sample_ratio,
+                                    float *offsets_out, float *scale_out) {
+  if (!mx) return mfail(VAQHIP_EINVAL, "multi index is null");
+  std::lock_guard<std::mutex> lk(mx->mu);
+  DeviceRestore keep;
+  // learnt once, on shard 0 (every shard holds the same codebooks and rotation, and the rows play no part),
+  // then replicated: the values are the single index's, bit for bit
+  std::vector<float> off((size_t)mx->M), sc((size_t)mx->M);
+  int rc = vaqhip_learn_quantization(mx->sh[0].ix, X, n, projected, sample_ratio, off.data(), sc.data());
+  for (int g = 1; !rc && g < mx->G; g++) rc = vaqhip_index_set_lut_quantization(mx->sh[g].ix, off.data(), sc.data());
+  if (rc) {
+    g_merr = vaqhip_last_error();
+    return rc;
+  }
+  mx->fast_q = true;
+  if (offsets_out) std::memcpy(offsets_out, off.data(), off.size() * sizeof(float));
+  if (scale_out) std::memcpy(scale_out, sc.data(), sc.size() * sizeof(float));
   return VAQHIP_OK;
 }
 
@@ -628,6 +710,11 @@ static int multi_search_common(vaqhip_multi *mx, const float *queries, const flo
   if (nq == 0) return VAQHIP_OK;
   if ((!queries && !d_queries0) || !labels || !distances) return mfail(VAQHIP_EINVAL, "null pointer");
   std::lock_guard<std::mutex> lk(mx->mu);
+  // FAST over several shards: the head-and-lists form (one shard alone answers as the single index does)
+  mx->fast = mx->G > 1;
+  for (int g = 0; mx->fast && g < mx->G; g++) mx->fast = vaqhip_internal_fast_in_force(mx->sh[g].ix) != 0;
+  if (mx->fast && k > VAQHIP_MAX_K) return mfail(VAQHIP_EUNSUPPORTED, "k=%d > %d", k, VAQHIP_MAX_K);
+  DeviceRestore keep(mx->fast);  // (the other methods leave shard 0's device current, as they always have)
   // RCCL when the GPUs are distinct and there is something to exchange (or when asked for by
   // option, which also exercises it on one device); device-to-device copies otherwise
   bool rccl = mx->exchange == EX_RCCL || (mx->exchange == EX_AUTO && mx->distinct && mx->G > 1);
@@ -654,6 +741,9 @@ static int multi_search_common(vaqhip_multi *mx, const float *queries, const flo
     mx->d_queries0 = d_queries0 ? d_queries0 + (size_t)q0 * mx->D : nullptr;
     mx->nq = n;
     mx->k = mx->chain ? k + 1 : k;
+    // appends may have grown N past k, or the head with it: both are taken from the rows as they are now
+    mx->kk = mx->fast ? (int)std::min<int64_t>(k, mx->N) : 0;
+    mx->pk = 2 * (size_t)n * mx->k + (mx->fast ? ((size_t)n * mx->kk + 1) / 2 : 0);
     if (mx->chain) {
       // batches of the replay list, chosen from the set's size (the count of tied queries lives on the device)
       int b = mx->opt_exact_batch > 0 ? mx->opt_exact_batch : std::max(64, (n + 15) / 16);

@@ -527,6 +527,33 @@ def merge_topk_packed_device(packed, world: int, nq: int, k: int, out=None):
     return out_l, out_d
 
 
+def merge_fast_device(head_dist, dist_lists, label_lists, k: int, head_label_base: int = 0, out=None):
+    """FAST's exchange step (vaqhip_merge_fast_device): head_dist uint16-valued int16 CUDA tensor [nq, n_head]
+    -- the distances of the first n_head = min(k, N) rows of the whole database -- and [n_lists, nq, k] lists of
+    the OTHER rows, each ascending by (distance, row), lists in row order, empty slots -1 / FLT_MAX.  Returns the
+    single index's FAST answer: the first k of the stable merge by distance of the head in std::sort's order,
+    then the lists."""
+    import torch
+    d = dist_lists.contiguous()
+    l = label_lists.contiguous()
+    h = head_dist.contiguous()
+    n_lists, nq, kk = d.shape
+    assert kk == k and l.shape == d.shape and l.dtype == torch.int32 and d.dtype == torch.float32
+    assert h.dim() == 2 and h.shape[0] == nq and h.element_size() == 2 and h.shape[1] <= k
+    if out is not None:
+        out_l, out_d = out
+    else:
+        out_l = torch.empty((nq, k), dtype=torch.int32, device=d.device)
+        out_d = torch.empty((nq, k), dtype=torch.float32, device=d.device)
+    st = torch.cuda.current_stream(d.device).cuda_stream
+    dev = d.device.index if d.device.index is not None else torch.cuda.current_device()
+    _lib.check(_lib.load().vaqhip_merge_fast_device(
+        dev, C.c_void_p(h.data_ptr()), h.shape[1], h.shape[1], int(head_label_base), C.c_void_p(d.data_ptr()),
+        C.c_void_p(l.data_ptr()), n_lists, nq * k, k, nq, k, C.c_void_p(out_l.data_ptr()),
+        C.c_void_p(out_d.data_ptr()), C.c_void_p(st)))
+    return out_l, out_d
+
+
 class VaqHipMulti:
     """One process, several GPUs (include/vaqhip.h "multi-device"): the rows are sharded
     contiguously over `devices`, every device answers all queries on its shard, one RCCL
@@ -571,6 +598,28 @@ class VaqHipMulti:
 
     def set_method(self, methods: int, visit: float = 1.0) -> None:
         _lib.check_multi(_lib.load().vaqhip_multi_set_method(self._h, methods, float(visit)))
+
+    def set_lut_quantization(self, offsets, scale) -> None:
+        """vaqhip_multi_set_lut_quantization: mOffsets / mScale of method FAST, the same on every shard.  Call it
+        (or learn_quantization) BEFORE set_method(NNMethod.Fast): without a quantisation the multi index refuses
+        the method (EUNSUPPORTED)."""
+        off = np.ascontiguousarray(offsets, dtype=np.float32).reshape(-1)
+        sc = np.ascontiguousarray(scale, dtype=np.float32).reshape(-1)
+        if off.shape[0] != self.M or sc.shape[0] != self.M:
+            raise _lib.VaqHipError(-1, f"offsets {off.shape} / scale {sc.shape}: need {self.M} values each")
+        _lib.check_multi(_lib.load().vaqhip_multi_set_lut_quantization(self._h, _ptr(off), _ptr(sc)))
+
+    def learn_quantization(self, XTrain: np.ndarray, sampleRatio: float, projected: bool = False):
+        """vaqhip_multi_learn_quantization: VAQ::learnQuantization once, on the first shard, replicated to the
+        others.  Returns (offsets, scale), bit-equal to VaqHipFast.learnQuantization on the same rows."""
+        X = np.ascontiguousarray(XTrain, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != self.D:
+            raise _lib.VaqHipError(-1, f"XTrain {X.shape} is not n x {self.D}")
+        off = np.empty(self.M, np.float32)
+        sc = np.empty(self.M, np.float32)
+        _lib.check_multi(_lib.load().vaqhip_multi_learn_quantization(
+            self._h, _ptr(X), X.shape[0], 1 if projected else 0, C.c_float(sampleRatio), _ptr(off), _ptr(sc)))
+        return off, sc
 
     def set_ti_clusters(self, clusters: Optional[np.ndarray], seg: int = 0) -> None:
         if clusters is None:
