@@ -13,7 +13,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vaq_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "vaq_amd", "lib")
 LIB = os.path.join(LIBDIR, "libvaqhip.so")
-SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_fast.hip", "vaqhip_api.cpp", "vaqhip_multi.cpp"]
+SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_fast.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp",
+           "vaqhip_multi.cpp"]
 KERNEL_HEADER = os.path.join(CSRC, "vaq_kernels.h")
 API_HEADER = os.path.join(ROOT, "include", "vaqhip.h")
 
@@ -22,18 +23,21 @@ SCAN_HEADER = os.path.join(CSRC, "vaq_scan.h")
 SCAN_BF_HEADER = os.path.join(CSRC, "vaq_scan_bf.h")
 FAST_HEADER = os.path.join(CSRC, "vaq_fast.h")
 INTERNAL_HEADER = os.path.join(CSRC, "vaqhip_internal.h")
+INDEX_HEADER = os.path.join(CSRC, "vaqhip_index.h")  # private to the single-index host files
 
 
 def _deps(src: str):
-    # only the host file sees the public C header; the scan bodies live in vaq_scan.h
+    # only the host files see the public C header; the scan bodies live in vaq_scan.h
     deps = [os.path.join(CSRC, src), KERNEL_HEADER]
     if src.endswith(".cpp"):
         deps += [API_HEADER, INTERNAL_HEADER]
+        if src != "vaqhip_multi.cpp":
+            deps.append(INDEX_HEADER)
     if src in ("vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip"):
         deps.append(SCAN_HEADER)
     if src in ("vaq_kernels.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip"):
         deps.append(SCAN_BF_HEADER)
-    if src in ("vaq_fast.hip", "vaqhip_api.cpp"):
+    if src in ("vaq_fast.hip", "vaqhip_fast.cpp"):
         deps.append(FAST_HEADER)
     return deps
 OBJDIR = os.path.join(LIBDIR, "obj")

@@ -1,5 +1,5 @@
 // vaq_kernels.h -- launch interface between the C-ABI host code
-// (vaqhip_api.cpp) and the gfx950 kernels (vaq_kernels.hip).
+// (vaqhip_*.cpp) and the gfx950 kernels (vaq_kernels.hip).
 #ifndef VAQ_KERNELS_H_
 #define VAQ_KERNELS_H_
 
