@@ -139,6 +139,43 @@ def test_multi_search_device_entry(vaqlib):
     m.close()
 
 
+@pytest.mark.parametrize("exact", [0, 1], ids=["plain", "exact_ties"])
+@pytest.mark.parametrize("entry", ["search", "search_device"])
+def test_multi_buffers_regrow(vaqlib, entry, exact):
+    """The sizes of a search change from call to call on a fresh multi index: (nq, k) = (5, 10), (33, 100),
+    (5, 10) again, so every buffer of the shards and of the multi index is allocated, grown, then used below
+    its capacity; with exact_ties the replay list, the heap states and the final answer join in.  Three logical
+    shards of device 0: the exchange runs by copies.  Every answer equals the single index's for the same call,
+    labels and distance bits."""
+    import torch
+    from vaq_amd.index import VaqHipMulti
+    c = make_case(4600, 64, [8] * 8, 20_000, 33, dup_frac=0.02)
+    ref = single(c)
+    m = VaqHipMulti([0, 0, 0], c["bits"], c["cents"], c["eig"])
+    m.set_codes(c["codes"])
+    ref.set_option("exact_ties", exact)
+    m.set_option("exact_ties", exact)
+    sizes = ((5, 10), (33, 100), (5, 10))
+    if entry == "search":
+        got = [m.search(c["X"][:n], k) for n, k in sizes]
+        want = [ref.search(c["X"][:n], k) for n, k in sizes]
+        got = [(a.labels, a.distances) for a in got]
+        want = [(r.labels, r.distances) for r in want]
+    else:
+        # back to back on one stream, then one synchronisation: the buffers grow behind work in flight
+        qs = [torch.from_numpy(c["X"][:n]).cuda() for n, _ in sizes]
+        got = [m.search_device(q, k) for q, (_, k) in zip(qs, sizes)]
+        want = [ref.search_device(q, k) for q, (_, k) in zip(qs, sizes)]
+        torch.cuda.synchronize()
+        got = [(l.cpu().numpy(), d.cpu().numpy()) for l, d in got]
+        want = [(l.cpu().numpy(), d.cpu().numpy()) for l, d in want]
+    for (n, k), (l, d), (rl, rd) in zip(sizes, got, want):
+        assert np.array_equal(l, rl), (n, k)
+        assert np.array_equal(d.view(np.uint32), rd.view(np.uint32)), (n, k)
+    m.close()
+    ref.close()
+
+
 @pytest.mark.parametrize("bits,N,nq", [([8] * 16, 1_200_000, 64), ([8] * 8, 900_000, 40)], ids=["m16", "m8"])
 def test_staged_search_with_threshold_exchange(vaqlib, oracle, bits, N, nq):
     """vaqhip_search_begin_device / _finish_device on three row shards (three indexes on the one GPU):

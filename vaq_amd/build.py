@@ -24,15 +24,18 @@ SCAN_BF_HEADER = os.path.join(CSRC, "vaq_scan_bf.h")
 FAST_HEADER = os.path.join(CSRC, "vaq_fast.h")
 INTERNAL_HEADER = os.path.join(CSRC, "vaqhip_internal.h")
 INDEX_HEADER = os.path.join(CSRC, "vaqhip_index.h")  # private to the single-index host files
+DEV_HEADER = os.path.join(CSRC, "vaqhip_dev.h")      # DevBuf, DeviceGuard: both hosts and the two scratch allocators
+JOB_POOL_HEADER = os.path.join(CSRC, "job_pool.h")
 
 
 def _deps(src: str):
     # only the host files see the public C header; the scan bodies live in vaq_scan.h
     deps = [os.path.join(CSRC, src), KERNEL_HEADER]
     if src.endswith(".cpp"):
-        deps += [API_HEADER, INTERNAL_HEADER]
-        if src != "vaqhip_multi.cpp":
-            deps.append(INDEX_HEADER)
+        deps += [API_HEADER, INTERNAL_HEADER, DEV_HEADER]
+        deps.append(JOB_POOL_HEADER if src == "vaqhip_multi.cpp" else INDEX_HEADER)
+    if src in ("vaq_kernels.hip", "vaq_ti.hip"):
+        deps.append(DEV_HEADER)
     if src in ("vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip"):
         deps.append(SCAN_HEADER)
     if src in ("vaq_kernels.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip"):

@@ -14,6 +14,7 @@
 //   merge_kernel        heap_reorder's sorted output         utils/Heap.hpp:322-349
 #include "vaq_scan.h"
 #include "vaq_scan_bf.h"
+#include "vaqhip_dev.h"
 
 #include <cstring>
 #include <rocprim/device/device_radix_sort.hpp>
@@ -449,18 +450,13 @@ hipError_t sort_by_first_code(const uint16_t *d_codes, int64_t n, int M, int bit
   hipError_t e = hipMemsetAsync(d_bucket_start, 0xff, (size_t)(K0 + 1) * sizeof(int), st);
   if (e == hipSuccess && fine > 0) e = hipMemsetAsync(d_sub_start, 0xff, ((size_t)(K0 << fine) + 1) * sizeof(int), st);
   if (e != hipSuccess || n == 0) return e;
-  uint16_t *keys_in = nullptr, *keys_out = nullptr;
-  uint32_t *idx_in = nullptr;
-  void *temp = nullptr;
+  vaqhost::DevBuf b_keys_in, b_keys_out, b_idx_in, b_temp;  // (freed on return, after the stream is synchronised)
   size_t temp_bytes = 0;
-  auto cleanup = [&]() {
-    (void)hipFree(keys_in); (void)hipFree(keys_out); (void)hipFree(idx_in); (void)hipFree(temp);
-  };
-  if ((e = hipMalloc(&keys_in, (size_t)n * 2)) != hipSuccess || (e = hipMalloc(&keys_out, (size_t)n * 2)) != hipSuccess ||
-      (e = hipMalloc(&idx_in, (size_t)n * 4)) != hipSuccess) {
-    cleanup();
+  if ((e = b_keys_in.ensure((size_t)n * 2)) != hipSuccess || (e = b_keys_out.ensure((size_t)n * 2)) != hipSuccess ||
+      (e = b_idx_in.ensure((size_t)n * 4)) != hipSuccess)
     return e;
-  }
+  uint16_t *keys_in = b_keys_in.as<uint16_t>(), *keys_out = b_keys_out.as<uint16_t>();
+  uint32_t *idx_in = b_idx_in.as<uint32_t>();
   const unsigned blocks = (unsigned)((n + 255) / 256);
   hipLaunchKernelGGL(first_code_keys_kernel, dim3(blocks), dim3(256), 0, st, d_codes, n, M,
                      (unsigned)((1 << bits0) - 1), shift, (unsigned)((1 << bits1) - 1), bits1 - (t + fine), t + fine, keys_in,
@@ -468,9 +464,9 @@ hipError_t sort_by_first_code(const uint16_t *d_codes, int64_t n, int M, int bit
   // stable LSD radix sort on the b0 key bits: equal codes keep ascending original rows
   e = rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, idx_in, d_perm, (size_t)n, 0u,
                                 (unsigned)kbits, st);
-  if (e == hipSuccess) e = hipMalloc(&temp, temp_bytes ? temp_bytes : 16);
+  if (e == hipSuccess) e = b_temp.ensure(temp_bytes ? temp_bytes : 16);
   if (e == hipSuccess)
-    e = rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, idx_in, d_perm, (size_t)n, 0u,
+    e = rocprim::radix_sort_pairs(b_temp.p, temp_bytes, keys_in, keys_out, idx_in, d_perm, (size_t)n, 0u,
                                   (unsigned)kbits, st);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(bucket_bounds_kernel, dim3(blocks), dim3(256), 0, st, keys_out, n, fine, d_bucket_start,
@@ -478,7 +474,6 @@ hipError_t sort_by_first_code(const uint16_t *d_codes, int64_t n, int M, int bit
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  cleanup();
   return e;
 }
 

@@ -8,6 +8,7 @@
 // are the reference's  res += tmp * tmp  (utils/Math.hpp:8-19), multiply and
 // add unfused, or its SSE orders for d in {1,2,4,8,12} (:38-128).
 #include "vaq_kernels.h"
+#include "vaqhip_dev.h"
 
 #include <algorithm>
 #include <cstring>
@@ -187,29 +188,24 @@ hipError_t ti_group_rows(const uint16_t *d_codes, int64_t n, int M, int L, int s
                          int *d_start, float *d_xcc_sorted, hipStream_t st) {
   hipError_t e = hipMemsetAsync(d_start, 0xff, (size_t)(T + 1) * sizeof(int), st);
   if (e != hipSuccess || n == 0) return e;
-  int *assign = nullptr;
-  float *xcc = nullptr, *scratch = nullptr;
-  uint64_t *keys_in = nullptr, *keys_out = nullptr;
-  uint32_t *idx_in = nullptr;
-  void *temp = nullptr;
+  // (freed on return, after the stream is synchronised)
+  vaqhost::DevBuf b_assign, b_xcc, b_scratch, b_keys_in, b_keys_out, b_idx_in, b_temp;
   size_t temp_bytes = 0;
-  auto cleanup = [&]() {
-    (void)hipFree(assign); (void)hipFree(xcc); (void)hipFree(scratch); (void)hipFree(keys_in); (void)hipFree(keys_out);
-    (void)hipFree(idx_in); (void)hipFree(temp);
-  };
-  if ((e = hipMalloc(&assign, (size_t)n * 4)) != hipSuccess || (e = hipMalloc(&xcc, (size_t)n * 4)) != hipSuccess ||
-      (e = hipMalloc(&keys_in, (size_t)n * 8)) != hipSuccess ||
-      (e = hipMalloc(&keys_out, (size_t)n * 8)) != hipSuccess ||
-      (e = hipMalloc(&idx_in, (size_t)n * 4)) != hipSuccess) {
-    cleanup();
+  if ((e = b_assign.ensure((size_t)n * 4)) != hipSuccess || (e = b_xcc.ensure((size_t)n * 4)) != hipSuccess ||
+      (e = b_keys_in.ensure((size_t)n * 8)) != hipSuccess ||
+      (e = b_keys_out.ensure((size_t)n * 8)) != hipSuccess ||
+      (e = b_idx_in.ensure((size_t)n * 4)) != hipSuccess)
     return e;
-  }
+  int *assign = b_assign.as<int>();
+  float *xcc = b_xcc.as<float>();
+  uint64_t *keys_in = b_keys_in.as<uint64_t>(), *keys_out = b_keys_out.as<uint64_t>();
+  uint32_t *idx_in = b_idx_in.as<uint32_t>();
   int R = 0;
   const size_t lds = ti_assign_lds(seg * L, &R);
   int64_t grid = (n + R - 1) / R;
   if (lds == 0) {
     grid = std::min<int64_t>(grid, 2048);
-    e = hipMalloc(&scratch, (size_t)grid * R * seg * L * sizeof(float));
+    e = b_scratch.ensure((size_t)grid * R * seg * L * sizeof(float));
   } else {
     grid = std::min<int64_t>(grid, (int64_t)1 << 30);
     e = hipFuncSetAttribute(reinterpret_cast<const void *>(ti_assign_kernel),
@@ -217,7 +213,7 @@ hipError_t ti_group_rows(const uint16_t *d_codes, int64_t n, int M, int L, int s
   }
   if (e == hipSuccess) {
     hipLaunchKernelGGL(ti_assign_kernel, dim3((unsigned)grid), dim3(R), lds, st, d_codes, n, M, L, seg, sub,
-                       cent, d_clusters, T, scratch, assign, xcc);
+                       cent, d_clusters, T, b_scratch.as<float>(), assign, xcc);
     e = hipGetLastError();
   }
   const unsigned blocks = (unsigned)((n + 255) / 256);
@@ -230,16 +226,15 @@ hipError_t ti_group_rows(const uint16_t *d_codes, int64_t n, int M, int L, int s
   if (e == hipSuccess)
     e = rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, idx_in, d_perm, (size_t)n, 0u,
                                   32u + cbits, st);
-  if (e == hipSuccess) e = hipMalloc(&temp, temp_bytes ? temp_bytes : 16);
+  if (e == hipSuccess) e = b_temp.ensure(temp_bytes ? temp_bytes : 16);
   if (e == hipSuccess)
-    e = rocprim::radix_sort_pairs(temp, temp_bytes, keys_in, keys_out, idx_in, d_perm, (size_t)n, 0u,
+    e = rocprim::radix_sort_pairs(b_temp.p, temp_bytes, keys_in, keys_out, idx_in, d_perm, (size_t)n, 0u,
                                   32u + cbits, st);
   if (e == hipSuccess) {
     hipLaunchKernelGGL(ti_bounds_kernel, dim3(blocks), dim3(256), 0, st, keys_out, n, d_start, d_xcc_sorted);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(st);
-  cleanup();
   return e;
 }
 

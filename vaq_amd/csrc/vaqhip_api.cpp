@@ -149,32 +149,21 @@ int vaqhip_index_create_ex(vaqhip_index **out, int D, int M, const int *bits,
 
 void vaqhip_index_destroy(vaqhip_index *ix) {
   if (!ix) return;
-  {
-    DeviceGuard g(ix->device);
-    if (ix->stream) {
-      (void)hipStreamSynchronize(ix->stream);
-      (void)hipStreamDestroy(ix->stream);
-    }
-    for (auto &e : ix->ev) (void)hipEventDestroy(e);
-    if (ix->ws_event) (void)hipEventDestroy(ix->ws_event);
-    for (DevBuf *b : {&ix->d_cent, &ix->d_cent_t, &ix->d_eig, &ix->d_sub, &ix->d_first_sub, &ix->d_codes, &ix->d_perm,
-                      &ix->d_bstart, &ix->w_q,
-                      &ix->w_qproj, &ix->w_lut, &ix->w_part_d, &ix->w_part_id, &ix->w_part_cnt, &ix->w_labels,
-                      &ix->w_dist, &ix->w_stage, &ix->w_lutref, &ix->w_thr, &ix->w_ms_d, &ix->w_ms_id, &ix->w_order, &ix->w_qorder,
-                      &ix->d_fast_codes, &ix->d_fast_off, &ix->d_fast_scale, &ix->w_fast_small, &ix->w_fast_dist,
-                      &ix->w_fast_order, &ix->w_fast_scratch})
-      b->release();
+  DeviceGuard g(ix->device);
+  if (ix->stream) {
+    (void)hipStreamSynchronize(ix->stream);
+    (void)hipStreamDestroy(ix->stream);
   }
-  delete ix;
+  for (auto &e : ix->ev) (void)hipEventDestroy(e);
+  if (ix->ws_event) (void)hipEventDestroy(ix->ws_event);
+  delete ix;  // every DevBuf goes here: the index's device is current, its stream idle and gone
 }
 
 int vaqhip_project(vaqhip_index *ix, const float *X, int64_t n, float *out) {
   if (!ix) return fail(VAQHIP_EINVAL, "index is null");
   if (n < 0 || (n > 0 && (!X || !out))) return fail(VAQHIP_EINVAL, "bad arguments");
   if (n == 0) return VAQHIP_OK;
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  ENTRY(ix);
   if (!ix->has_eig) {
     std::memcpy(out, X, (size_t)n * ix->D * sizeof(float));
     return VAQHIP_OK;
@@ -182,7 +171,7 @@ int vaqhip_project(vaqhip_index *ix, const float *X, int64_t n, float *out) {
   const int64_t chunk = std::min<int64_t>(n, 1 << 20);
   HIP_TRY(ix->w_q.ensure((size_t)chunk * ix->D * sizeof(float)));
   HIP_TRY(ix->w_qproj.ensure((size_t)chunk * ix->D * sizeof(float)));
-  if (int rc = ws_acquire(ix, ix->stream)) return rc;
+  WS_SCOPE(ws, ix, ix->stream);
   for (int64_t r = 0; r < n; r += chunk) {
     const int64_t m = std::min(chunk, n - r);
     const size_t bytes = (size_t)m * ix->D * sizeof(float);
@@ -192,16 +181,14 @@ int vaqhip_project(vaqhip_index *ix, const float *X, int64_t n, float *out) {
     HIP_TRY(hipMemcpyAsync(out + r * ix->D, ix->w_qproj.p, bytes, hipMemcpyDeviceToHost, ix->stream));
     HIP_TRY(hipStreamSynchronize(ix->stream));
   }
-  return VAQHIP_OK;
+  return ws.finish();
 }
 
 int vaqhip_build_lut(vaqhip_index *ix, const float *queries, int nq, int projected, float *lut_out) {
   if (!ix) return fail(VAQHIP_EINVAL, "index is null");
   if (nq < 0 || (nq > 0 && (!queries || !lut_out))) return fail(VAQHIP_EINVAL, "bad arguments");
   if (nq == 0) return VAQHIP_OK;
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  ENTRY(ix);
   const int ksub = 1 << ix->max_bits;
   const size_t per_q = (size_t)ix->M * ksub;
   const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)nq, ((size_t)256 << 20) / (per_q * 4)));
@@ -210,7 +197,7 @@ int vaqhip_build_lut(vaqhip_index *ix, const float *queries, int nq, int project
   HIP_TRY(ix->w_lut.ensure((size_t)chunk * ix->lut_floats * sizeof(float)));
   HIP_TRY(ix->w_lutref.ensure((size_t)chunk * per_q * sizeof(float)));
   hipStream_t st = ix->stream;
-  if (int rc = ws_acquire(ix, st)) return rc;
+  WS_SCOPE(ws, ix, st);
   for (int q0 = 0; q0 < nq; q0 += chunk) {
     const int n = std::min(chunk, nq - q0);
     HIP_TRY(hipMemcpyAsync(ix->w_q.p, queries + (size_t)q0 * ix->D, (size_t)n * ix->D * sizeof(float),
@@ -229,7 +216,7 @@ int vaqhip_build_lut(vaqhip_index *ix, const float *queries, int nq, int project
                            hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
-  return VAQHIP_OK;
+  return ws.finish();
 }
 
 int vaqhip_merge_topk_device(int device_id, const float *d_dist_lists, const int32_t *d_label_lists,
@@ -266,7 +253,7 @@ static int encode_device_locked(vaqhip_index *ix, const float *d_X, int64_t n, i
   const bool do_project = !projected && (ix->has_eig || ix->seq);
   const int64_t chunk = std::min<int64_t>(n, 1 << 20);
   if (do_project) HIP_TRY(ix->w_qproj.ensure((size_t)chunk * ix->D * sizeof(float)));
-  if (int rc = ws_acquire(ix, st)) return rc;
+  WS_SCOPE(ws, ix, st);
   for (int64_t r = 0; r < n; r += chunk) {
     const int64_t m = std::min(chunk, n - r);
     const float *xp = d_X + r * ix->D;
@@ -277,7 +264,7 @@ static int encode_device_locked(vaqhip_index *ix, const float *d_X, int64_t n, i
     HIP_TRY(vaq::launch_encode(xp, m, ix->D, ix->M, ix->L, ix->d_sub.as<vaq::SubDesc>(),
                                ix->d_cent.as<float>(), d_codes + r * ix->M, st));
   }
-  return ws_release(ix, st);
+  return ws.finish();
 }
 
 int vaqhip_encode_device(vaqhip_index *ix, const float *d_X, int64_t n, int projected,
@@ -285,9 +272,7 @@ int vaqhip_encode_device(vaqhip_index *ix, const float *d_X, int64_t n, int proj
   if (!ix) return fail(VAQHIP_EINVAL, "index is null");
   if (n < 0 || (n > 0 && (!d_X || !d_codes))) return fail(VAQHIP_EINVAL, "bad arguments");
   if (n == 0) return VAQHIP_OK;
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  ENTRY(ix);
   return encode_device_locked(ix, d_X, n, projected, d_codes, static_cast<hipStream_t>(stream));
 }
 
@@ -298,14 +283,12 @@ int vaqhip_encode(vaqhip_index *ix, const float *X, int64_t n, int projected, ui
   const int64_t chunk = std::min<int64_t>(n, 1 << 20);
   // the staging buffers (w_q, w_stage) are the index's: hold its lock across upload, encode and
   // download, as search_host does
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  ENTRY(ix);
   HIP_TRY(ix->w_q.ensure((size_t)chunk * ix->D * sizeof(float)));
   HIP_TRY(ix->w_stage.ensure((size_t)chunk * ix->M * sizeof(uint16_t)));
+  WS_SCOPE(ws, ix, ix->stream);  // (w_q may still be read by a search on another stream)
   for (int64_t r = 0; r < n; r += chunk) {
     const int64_t m = std::min(chunk, n - r);
-    if (int rc = ws_acquire(ix, ix->stream)) return rc;  // (w_q may still be read by a search on another stream)
     HIP_TRY(hipMemcpyAsync(ix->w_q.p, X + r * ix->D, (size_t)m * ix->D * sizeof(float), hipMemcpyHostToDevice,
                            ix->stream));
     if (int rc = encode_device_locked(ix, ix->w_q.as<float>(), m, projected, ix->w_stage.as<uint16_t>(), ix->stream)) return rc;
@@ -313,7 +296,7 @@ int vaqhip_encode(vaqhip_index *ix, const float *X, int64_t n, int projected, ui
                            hipMemcpyDeviceToHost, ix->stream));
     HIP_TRY(hipStreamSynchronize(ix->stream));
   }
-  return VAQHIP_OK;
+  return ws.finish();
 }
 
 int vaqhip_refine_device(int device_id, const float *d_queries, int nq, int D, const float *d_dataset,
@@ -386,10 +369,10 @@ int vaqhip_index_set_method(vaqhip_index *ix, unsigned methods, float visit) {
   ix->ti_visit = visit;
   if (!fast_only(ix) && (ix->fast_rows >= 0 || ix->w_fast_dist.p)) {
     DeviceGuard g(ix->device);
-    if (int rc = ws_acquire(ix, ix->stream)) return rc;  // (a FAST search may still read them)
+    WS_SCOPE(ws, ix, ix->stream);  // (a FAST search may still read them)
     HIP_TRY(hipStreamSynchronize(ix->stream));
     fast_release(ix);
-    return ws_release(ix, ix->stream);
+    return ws.finish();
   }
   return VAQHIP_OK;
 }

@@ -101,9 +101,7 @@ int set_codes_common(vaqhip_index *ix, const uint16_t *codes, bool on_device, in
   if (N > 0x7fffffffLL - 1 || id_base + N > 0x7fffffffLL)
     return fail(VAQHIP_ERANGE, "labels are 32-bit ints (utils/Types.hpp:100): id_base+N = %lld",
                 (long long)(id_base + N));
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  ENTRY(ix);
   // all rows must be resident to sort them: stage a host matrix on the device first
   DevBuf staged;
   const uint16_t *d_u16 = codes;
@@ -117,11 +115,11 @@ int set_codes_common(vaqhip_index *ix, const uint16_t *codes, bool on_device, in
     d_u16 = staged.as<uint16_t>();
   }
   // (a search enqueued on another stream may still be scanning the rows this call rewrites)
-  if (int rc = ws_acquire(ix, st)) return rc;
+  WS_SCOPE(ws, ix, st);
   if (int rc = fast_codes_update(ix, d_u16, 0, N, st)) return rc;
   if (int rc = build_rows(ix, d_u16, N, st)) return rc;  // synchronises: `staged` is freed on return
   ix->id_base = id_base;
-  return ws_release(ix, st);
+  return ws.finish();
 }
 
 // append to a bucketed (non-TI) index: sort and pack the NEW rows only, then merge them into the
@@ -201,7 +199,7 @@ int add_codes_common(vaqhip_index *ix, const uint16_t *codes, bool on_device, in
   DeviceGuard g(ix->device);
   if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
   if (n_new == 0 && ix->N >= 0) return VAQHIP_OK;
-  if (int rc = ws_acquire(ix, st)) return rc;  // (a search on another stream may still be reading the codes)
+  WS_SCOPE(ws, ix, st);  // (a search on another stream may still be reading the codes)
   if (ix->ti_T == 0 && n_old > 0 && n_new > 0 && N < 4 * std::max<int64_t>(ix->N_keyed, 4096)) {
     DevBuf staged;
     const uint16_t *d_new = codes;
@@ -211,7 +209,8 @@ int add_codes_common(vaqhip_index *ix, const uint16_t *codes, bool on_device, in
       d_new = staged.as<uint16_t>();
     }
     if (int rc = fast_codes_update(ix, d_new, n_old, N, st)) return rc;
-    return append_rows_bucketed(ix, d_new, n_new, st);  // synchronises
+    if (int rc = append_rows_bucketed(ix, d_new, n_new, st)) return rc;  // synchronises
+    return ws.finish();
   }
   DevBuf rows;
   HIP_TRY(rows.ensure(std::max<size_t>((size_t)N * ix->M * sizeof(uint16_t), 16)));
@@ -223,7 +222,8 @@ int add_codes_common(vaqhip_index *ix, const uint16_t *codes, bool on_device, in
     HIP_TRY(hipMemcpyAsync(rows.as<uint16_t>() + n_old * ix->M, codes, (size_t)n_new * ix->M * sizeof(uint16_t),
                            on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
   if (int rc = fast_codes_update(ix, rows.as<uint16_t>() + n_old * ix->M, n_old, N, st)) return rc;
-  return build_rows(ix, rows.as<uint16_t>(), N, st);  // synchronises
+  if (int rc = build_rows(ix, rows.as<uint16_t>(), N, st)) return rc;  // synchronises
+  return ws.finish();
 }
 } // namespace
 
@@ -260,13 +260,11 @@ int vaqhip_index_set_ti_clusters(vaqhip_index *ix, const float *clusters, int T,
   if (T > 0 && (int64_t)seg_num * ix->L > 1024)
     return fail(VAQHIP_EUNSUPPORTED, "TI centres of %d dims (> 1024)", seg_num * ix->L);
   if (T > 0 && ix->seq) return fail(VAQHIP_EINVAL, "TI is a VAQ::search method, not a queryLUT one");
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  ENTRY(ix);
   if (T == 0 && ix->ti_T == 0) return VAQHIP_OK;
   hipStream_t st = ix->stream;
   // (a search enqueued on another stream may still be scanning the rows this call regroups)
-  if (int rc = ws_acquire(ix, st)) return rc;
+  WS_SCOPE(ws, ix, st);
   // rows already handed over: recover them in original order, then regroup
   DevBuf rows;
   if (ix->N > 0) {
@@ -298,6 +296,6 @@ int vaqhip_index_set_ti_clusters(vaqhip_index *ix, const float *clusters, int T,
     if (int rc = build_rows(ix, rows.as<uint16_t>(), ix->N, st)) return rc;
   }
   HIP_TRY(hipStreamSynchronize(st));
-  return VAQHIP_OK;
+  return ws.finish();
 }
 } // extern "C"

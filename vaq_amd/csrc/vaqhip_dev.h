@@ -1,0 +1,62 @@
+// vaqhip_dev.h -- what every host of the library owns device state with: a grow-only device buffer and
+// the guard of the current device.  Shared by the single-index host files (through vaqhip_index.h), the
+// multi-device host (vaqhip_multi.cpp) and the two kernel files that allocate scratch (vaq_kernels.hip,
+// vaq_ti.hip).  It holds nothing of vaqhip_index.
+#ifndef VAQHIP_DEV_H
+#define VAQHIP_DEV_H
+#include <hip/hip_runtime.h>
+#include <cstddef>
+
+// (hidden: none of this joins the library's exported symbols)
+namespace vaqhost __attribute__((visibility("hidden"))) {
+
+// Freed by release() or the destructor, with the CALLER's current device: the owner makes the buffer's
+// device current (and its streams idle) first.
+struct DevBuf {
+  void *p = nullptr;
+  size_t cap = 0;
+  DevBuf() = default;
+  DevBuf(DevBuf &&o) noexcept : p(o.p), cap(o.cap) {  // one owner: moved into a container, never copied or assigned
+    o.p = nullptr;
+    o.cap = 0;
+  }
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(DevBuf &&) = delete;
+  ~DevBuf() { release(); }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+  // grow-only; the old contents are not kept
+  hipError_t ensure(size_t bytes) {
+    if (bytes <= cap) return hipSuccess;
+    release();
+    hipError_t e = hipMalloc(&p, bytes);
+    if (e == hipSuccess) cap = bytes;
+    else p = nullptr;
+    return e;
+  }
+  template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+
+// Makes `dev` current and puts the caller's device back when the scope ends; the restore-only form
+// leaves the current device alone and only puts it back (`active` false: not even that).
+struct DeviceGuard {
+  enum RestoreOnly { restore_only };
+  int prev = -1;
+  bool ok = false;
+  explicit DeviceGuard(int dev) {
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    ok = hipSetDevice(dev) == hipSuccess;
+  }
+  explicit DeviceGuard(RestoreOnly, bool active = true) : ok(true) {
+    if (active && hipGetDevice(&prev) != hipSuccess) prev = -1;
+  }
+  ~DeviceGuard() {
+    if (prev >= 0) (void)hipSetDevice(prev);
+  }
+};
+
+} // namespace vaqhost
+#endif

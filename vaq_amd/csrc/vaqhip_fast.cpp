@@ -88,14 +88,14 @@ int set_quantization_locked(vaqhip_index *ix, const float *off, const float *sca
       return fail(VAQHIP_EINVAL, "subspace %d: offset %g, scale %g (finite, scale > 0)", s, off[s], scale[s]);
   HIP_TRY(ix->d_fast_off.ensure((size_t)ix->M * sizeof(float)));
   HIP_TRY(ix->d_fast_scale.ensure((size_t)ix->M * sizeof(float)));
-  if (int rc = ws_acquire(ix, ix->stream)) return rc;  // (a search on another stream may still read them)
+  WS_SCOPE(ws, ix, ix->stream);  // (a search on another stream may still read them)
   HIP_TRY(hipMemcpyAsync(ix->d_fast_off.p, off, (size_t)ix->M * sizeof(float), hipMemcpyHostToDevice, ix->stream));
   HIP_TRY(hipMemcpyAsync(ix->d_fast_scale.p, scale, (size_t)ix->M * sizeof(float), hipMemcpyHostToDevice, ix->stream));
   HIP_TRY(hipStreamSynchronize(ix->stream));
   ix->fast_off.assign(off, off + ix->M);
   ix->fast_scale.assign(scale, scale + ix->M);
   ix->fast_q = true;
-  return ws_release(ix, ix->stream);
+  return ws.finish();
 }
 
 // utils/Math.hpp:190-213 on an ascending column: the value at rank percent * (rows - 1), as written
@@ -126,7 +126,7 @@ int vaqhost::search_fast(vaqhip_index *ix, const float *d_queries, int nq, int k
   else if (!ix->fast_q) method_err = "method FAST needs vaqhip_index_set_lut_quantization or vaqhip_learn_quantization first";
   if (int rc = check_search_args(ix, d_queries, nq, k, d_labels, d_dist, method_err)) return rc;
   if (nq == 0) return VAQHIP_OK;
-  if (int rc = ws_acquire(ix, st)) return rc;
+  WS_SCOPE(ws, ix, st);
   if (int rc = fast_codes_ensure(ix, st)) return rc;
   const int64_t N = ix->N;
   const int64_t n_pad = std::max<int64_t>(1, (N + vaq::FAST_ROW_PAD - 1) / vaq::FAST_ROW_PAD) * vaq::FAST_ROW_PAD;
@@ -168,7 +168,7 @@ int vaqhost::search_fast(vaqhip_index *ix, const float *d_queries, int nq, int k
     HIP_TRY(vaq::launch_fast_select(ix->w_fast_dist.as<uint16_t>(), n_pad, N, n, k, ix->M, ix->w_fast_order.as<uint16_t>(),
                                     ix->id_base, d_labels + (size_t)q0 * k, d_dist + (size_t)q0 * k, st));
   }
-  return ws_release(ix, st);
+  return ws.finish();
 }
 
 extern "C" {
@@ -176,9 +176,7 @@ int vaqhip_index_set_lut_quantization(vaqhip_index *ix, const float *offsets, co
   if (!ix) return fail(VAQHIP_EINVAL, "index is null");
   if (!offsets || !scale) return fail(VAQHIP_EINVAL, "null pointer");
   if (!ix->fast_ok) return fail(VAQHIP_EUNSUPPORTED, "FAST needs max bits per subspace <= 4 and the grouped row sum");
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  ENTRY(ix);
   return set_quantization_locked(ix, offsets, scale);
 }
 
@@ -190,9 +188,7 @@ int vaqhip_learn_quantization(vaqhip_index *ix, const float *X, int64_t n, int p
   if (n > 0x7fffffffLL) return fail(VAQHIP_ERANGE, "the reference's rows are int: n = %lld", (long long)n);
   const int sample = static_cast<int>(sample_ratio * (float)n);  // VAQ.cpp:1120
   if (!(sample >= 1)) return fail(VAQHIP_EINVAL, "sampleSize = int(%g * %lld) < 1", sample_ratio, (long long)n);
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  ENTRY(ix);
   // randomPermutation (utils/Random.hpp:18-28): i2 = i + mt() % (n - i)
   std::vector<int> perm((size_t)n);
   for (int64_t i = 0; i < n; i++) perm[i] = (int)i;
@@ -216,7 +212,7 @@ int vaqhip_learn_quantization(vaqhip_index *ix, const float *X, int64_t n, int p
     HIP_TRY(ix->w_lut.ensure((size_t)chunk * ix->lut_floats * sizeof(float)));
     HIP_TRY(ix->w_lutref.ensure((size_t)chunk * M * ksub * sizeof(float)));
     hipStream_t st = ix->stream;
-    if (int rc = ws_acquire(ix, st)) return rc;
+    WS_SCOPE(ws, ix, st);
     for (int i0 = 0; i0 < sample; i0 += chunk) {
       const int m = std::min(chunk, sample - i0);
       for (int i = 0; i < m; i++) std::memcpy(&xs[(size_t)i * D], X + (size_t)perm[i0 + i] * D, (size_t)D * sizeof(float));
@@ -234,7 +230,7 @@ int vaqhip_learn_quantization(vaqhip_index *ix, const float *X, int64_t n, int p
                              hipMemcpyDeviceToHost, st));
       HIP_TRY(hipStreamSynchronize(st));
     }
-    if (int rc = ws_release(ix, st)) return rc;
+    if (int rc = ws.finish()) return rc;
   }
   // per column s: its values sorted once; max(x - f, 0) is monotone, so the offset column's order
   // statistics are those of the sorted column shifted.  Loss per (alpha, column) in double.
@@ -307,7 +303,7 @@ int vaqhip_build_small_lut(vaqhip_index *ix, const float *queries, int nq, int p
   HIP_TRY(ix->w_lutref.ensure((size_t)chunk * ix->M * (1 << ix->max_bits) * sizeof(float)));
   HIP_TRY(ix->w_fast_small.ensure((size_t)chunk * ix->M * 16));
   hipStream_t st = ix->stream;
-  if (int rc = ws_acquire(ix, st)) return rc;
+  WS_SCOPE(ws, ix, st);
   for (int q0 = 0; q0 < nq; q0 += chunk) {
     const int n = std::min(chunk, nq - q0);
     HIP_TRY(hipMemcpyAsync(ix->w_q.p, queries + (size_t)q0 * ix->D, (size_t)n * ix->D * sizeof(float),
@@ -322,7 +318,7 @@ int vaqhip_build_small_lut(vaqhip_index *ix, const float *queries, int nq, int p
                            hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
   }
-  return ws_release(ix, st);
+  return ws.finish();
 }
 
 int vaqhip_merge_fast_device(int device_id, const uint16_t *d_head_dist, int64_t head_stride, int n_head,
@@ -364,9 +360,7 @@ int vaqhip_internal_search_fast_shard_device(vaqhip_index *ix, const float *d_qu
                                              uint16_t *d_head, void *stream) {
   if (!ix) return fail(VAQHIP_EINVAL, "index is null");
   if (row_offset < 0 || kk < 0 || kk > k || (kk > 0 && !d_head)) return fail(VAQHIP_EINVAL, "bad head description");
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  ENTRY(ix);
   if (!fast_only(ix)) return fail(VAQHIP_ESTATE, "method FAST is not in force on this shard");
   FastShardPart part;
   part.kk_all = kk;

@@ -1,5 +1,6 @@
 // vaqhip_index.h -- what the host files of the single-device index share: the index itself, its device
-// buffers, the launch plan and the few functions that cross files.  Private to vaqhip_api.cpp,
+// buffers (vaqhip_dev.h), the entry preamble, the workspace scope, the launch plan and the few functions
+// that cross files.  Private to vaqhip_api.cpp,
 // vaqhip_plan.cpp, vaqhip_search.cpp, vaqhip_codes.cpp and vaqhip_fast.cpp: the multi-device host
 // (vaqhip_multi.cpp) sees the index through include/vaqhip.h and vaqhip_internal.h only.
 #ifndef VAQHIP_INDEX_H
@@ -15,6 +16,7 @@
 #include <vector>
 
 #include "vaq_kernels.h"
+#include "vaqhip_dev.h"
 #include "vaqhip_internal.h"
 
 // (hidden: none of this joins the library's exported symbols)
@@ -30,27 +32,6 @@ int fail(int code, const char *fmt, ...);
       return fail(e_ == hipErrorOutOfMemory ? VAQHIP_ENOMEM : VAQHIP_EHIP, "%s: %s", #expr, \
                   hipGetErrorString(e_));                                                 \
   } while (0)
-
-struct DevBuf {
-  void *p = nullptr;
-  size_t cap = 0;
-  ~DevBuf() { release(); }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-  // grow-only
-  hipError_t ensure(size_t bytes) {
-    if (bytes <= cap) return hipSuccess;
-    release();
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) cap = bytes;
-    else p = nullptr;
-    return e;
-  }
-  template <typename T> T *as() const { return static_cast<T *>(p); }
-};
 
 constexpr int QUERY_CHUNK = 16384;             // queries per internal launch set
 // (launch_cost_order pays from about one residency of workgroups on: 7 per CU)
@@ -142,18 +123,6 @@ struct vaqhip_index {
 
 namespace vaqhost __attribute__((visibility("hidden"))) {
 
-struct DeviceGuard {
-  int prev = -1;
-  bool ok = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    ok = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
 struct Plan {
   int qb, ea, kp, ccap, qcap, nwaves, n_slices;
   int lds_subs, lut_lds_entries;  // LUT tables staged in LDS (a prefix of the subspaces)
@@ -189,18 +158,52 @@ int search_fast(vaqhip_index *ix, const float *d_queries, int nq, int k, int pro
 void fast_release(vaqhip_index *ix);
 int fast_codes_update(vaqhip_index *ix, const uint16_t *d_u16, int64_t row_begin, int64_t row_end, hipStream_t st);
 
-// before / after enqueueing work that touches the index's shared workspaces on stream `st`
-inline int ws_acquire(vaqhip_index *ix, hipStream_t st) {
-  if (!ix->ws_event) HIP_TRY(hipEventCreateWithFlags(&ix->ws_event, hipEventDisableTiming));
-  if (ix->ws_used && st != ix->ws_stream) HIP_TRY(hipStreamWaitEvent(st, ix->ws_event, 0));
-  return VAQHIP_OK;
-}
-inline int ws_release(vaqhip_index *ix, hipStream_t st) {
-  HIP_TRY(hipEventRecord(ix->ws_event, st));
-  ix->ws_stream = st;
-  ix->ws_used = true;
-  return VAQHIP_OK;
-}
+// The preamble of an entry point: the index's lock, then its device current (put back when the scope ends).
+// rc: VAQHIP_OK, or what the entry returns at once -- ENTRY(ix) declares it and does so, as HIP_TRY would.
+#define ENTRY(ix) Entry entry_(ix); if (entry_.rc) return entry_.rc
+struct Entry {
+  std::lock_guard<std::mutex> lk;
+  DeviceGuard g;
+  int rc;
+  explicit Entry(vaqhip_index *ix)
+      : lk(ix->mu), g(ix->device),
+        rc(g.ok ? VAQHIP_OK : fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device)) {}
+};
+
+// Around the enqueueing of work that touches the index's shared workspaces on stream `st`: construction makes
+// `st` wait for the last such work on another stream (rc: its code), finish() leaves the event for the next call
+// and is the success path.  A return before finish() is a failure with work possibly enqueued already: the
+// destructor leaves the event all the same, without touching the failure's code and text.
+// WS_SCOPE(ws, ix, st) declares the scope and returns its code at once when the construction failed.
+#define WS_SCOPE(name, ix, st) WsScope name(ix, st); if (name.rc) return name.rc
+struct WsScope {
+  vaqhip_index *ix;
+  hipStream_t st;
+  bool open = false;
+  int rc;
+  WsScope(vaqhip_index *ix, hipStream_t st) : ix(ix), st(st), rc(acquire()) { open = rc == VAQHIP_OK; }
+  WsScope(const WsScope &) = delete;
+  ~WsScope() {
+    if (open && hipEventRecord(ix->ws_event, st) == hipSuccess) mark();
+  }
+  int finish() {
+    open = false;
+    HIP_TRY(hipEventRecord(ix->ws_event, st));
+    mark();
+    return VAQHIP_OK;
+  }
+
+ private:
+  int acquire() {
+    if (!ix->ws_event) HIP_TRY(hipEventCreateWithFlags(&ix->ws_event, hipEventDisableTiming));
+    if (ix->ws_used && st != ix->ws_stream) HIP_TRY(hipStreamWaitEvent(st, ix->ws_event, 0));
+    return VAQHIP_OK;
+  }
+  void mark() {
+    ix->ws_stream = st;
+    ix->ws_used = true;
+  }
+};
 
 inline int ensure_events(vaqhip_index *ix) {
   if (!ix->ev.empty()) return VAQHIP_OK;

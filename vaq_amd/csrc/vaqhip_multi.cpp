@@ -49,8 +49,12 @@
 #include <vector>
 
 #include "job_pool.h"
+#include "vaqhip_dev.h"
 
 namespace {
+
+using vaqhost::DevBuf;
+using vaqhost::DeviceGuard;
 
 int mfail(int code, const char *fmt, ...);
 
@@ -110,16 +114,14 @@ struct Shard {
   int64_t lo = 0, n = 0;  // rows [lo, lo + n) of the database
   hipStream_t stream = nullptr;
   hipEvent_t done = nullptr;  // this shard's packed result is complete
-  float *d_queries = nullptr;
-  int32_t *d_packed = nullptr;    // [2][nq][k]: labels, distance bits (FAST: + the head plane, [nq][kk] uint16)
-  int32_t *d_gathered = nullptr;  // [G][packed] (every device under RCCL; shard 0 with copies)
-  size_t cap_q = 0, cap_p = 0, cap_g = 0;
+  DevBuf d_queries;   // float [nq][D]
+  DevBuf d_packed;    // int32 [2][nq][k]: labels, distance bits (FAST: + the head plane, [nq][kk] uint16)
+  DevBuf d_gathered;  // int32 [G][packed] (every device under RCCL; shard 0 with copies)
   ncclComm_t comm = nullptr;
   // "exact_ties" across shards: the replay list (word 0 = count, entries from byte 16), the heap states
   // this shard's links start from and leave ([entry][2][k] words; shard 0's d_state_in receives the LAST
-  // shard's), one event per batch of the list
-  int32_t *d_list = nullptr, *d_state_in = nullptr, *d_state_out = nullptr;
-  size_t cap_list = 0, cap_si = 0, cap_so = 0;
+  // shard's), one event per batch of the list; int32 words
+  DevBuf d_list, d_state_in, d_state_out;
   std::vector<hipEvent_t> link_done;
   std::string err;  // what the shard's last phase failed with
 };
@@ -127,6 +129,8 @@ struct Shard {
 } // namespace
 
 struct vaqhip_multi {
+  // (its members have destructors now: declared so that it can be hidden, the exported symbols stay as they were)
+  __attribute__((visibility("hidden"))) ~vaqhip_multi() = default;
   int D = 0, M = 0, G = 0;
   std::vector<Shard> sh;
   bool distinct = true;  // no device named twice
@@ -137,31 +141,29 @@ struct vaqhip_multi {
   // caller only goes on to the next phase -- the collective -- when every shard has succeeded
   mutable std::mutex mu;
   vaq::JobPool pool;
-  // the current search
-  const float *queries = nullptr;      // host pointer, or
-  const float *d_queries0 = nullptr;   // device pointer on shard 0's device (vaqhip_multi_search_device)
-  hipEvent_t user_ready = nullptr;     //   recorded on the caller's stream: the queries are there
+  // the search in flight: filled by multi_search_common per set of queries, read by every phase
+  struct Call {
+    const float *queries = nullptr;     // host pointer, or
+    const float *d_queries0 = nullptr;  // device pointer on shard 0's device (vaqhip_multi_search_device)
+    int nq = 0, k = 0, projected = 0, use_rccl = 0;
+    bool chain = false;            // "exact_ties" across shards: the chain runs (then k is the caller's k + 1)
+    int n_batches = 0, batch = 0;  //   of the set's replay list
+    bool fast = false;             // FAST's sharded form
+    int kk = 0;                    //   min(k, N): rows of the head
+    size_t pk = 0;                 // int32 words of one shard's packed buffer: 2 * nq * k (+ the head plane)
+  } call;
+  // what outlives a call: events and buffers on shard 0's device, options
+  hipEvent_t user_ready = nullptr;     // recorded on the caller's stream: the queries are there
   hipEvent_t consumed = nullptr;       // shard 0 has read every shard's packed result (copies) / merged
   hipEvent_t finished = nullptr;       // the result is in the caller's device buffers
-  int nq = 0, k = 0, projected = 0, use_rccl = 0;
-  int32_t *d_out_labels = nullptr;
-  float *d_out_dist = nullptr;
-  size_t cap_out = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // shard 0: start, searched, gathered, merged
-  // "exact_ties" across shards
+  hipEvent_t flagged = nullptr;        // "exact_ties": the replay list of the current set is complete
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};  // start, searched, gathered, merged
+  DevBuf d_out_labels;            // int32 [nq][k] labels, then
+  float *d_out_dist = nullptr;    //   float [nq][k] distances (inside d_out_labels)
+  DevBuf d_final;                 // "exact_ties": int32 [2][nq][k] the current set's answer (labels, distances)
+  DevBuf d_head;                  // FAST: uint16 [nq][kk] the gathered head distances
   int opt_exact = 0, opt_exact_batch = 0;
-  bool chain = false;             // the current search runs the chain (then k above is the caller's k + 1)
-  int n_batches = 0, batch = 0;   //   of the current set of queries
-  hipEvent_t flagged = nullptr;   // shard 0: the replay list of the current set is complete
-  int32_t *d_final = nullptr;     // shard 0: [2][nq][k] the current set's answer (labels, distances)
-  size_t cap_final = 0;
-  // method FAST across shards
   bool fast_q = false;            // a quantisation was given to every shard (vaqhip_multi_set_lut_quantization / learn)
-  bool fast = false;              // the current search is FAST's sharded form
-  int kk = 0;                     //   min(k, N): rows of the head
-  size_t pk = 0;                  // int32 words of one shard's packed buffer: 2 * nq * k (+ the head plane)
-  uint16_t *d_head = nullptr;     // shard 0: [nq][kk] the gathered head distances
-  size_t cap_head = 0;
   vaqhip_multi_info last = {};
 };
 
@@ -188,58 +190,35 @@ int mfail(int code, const char *fmt, ...) {
     }                                                                                      \
   } while (0)
 
-// the caller's current device, put back when the scope ends
-struct DeviceRestore {
-  int prev = -1;
-  explicit DeviceRestore(bool active = true) {
-    if (active && hipGetDevice(&prev) != hipSuccess) prev = -1;
-  }
-  ~DeviceRestore() {
-    if (prev >= 0) (void)hipSetDevice(prev);
-  }
-};
-
-int grow(Shard &s, void **p, size_t *cap, size_t bytes) {
-  if (bytes <= *cap) return 0;
-  if (*p) MHIP(hipFree(*p));
-  *p = nullptr;
-  *cap = 0;
-  MHIP(hipMalloc(p, bytes));
-  *cap = bytes;
+// DevBuf::ensure with the shard's error text, where MHIP's own return does not fit
+int ensure(Shard &s, DevBuf &b, size_t bytes) {
+  MHIP(b.ensure(bytes));
   return 0;
 }
 
 // one shard's part of a search; runs on that shard's worker thread with its device current
 int run_shard(vaqhip_multi *mx, int g) {
   Shard &s = mx->sh[g];
-  const int G = mx->G, nq = mx->nq, k = mx->k;
+  const vaqhip_multi::Call &c = mx->call;
+  const int G = mx->G, nq = c.nq, k = c.k;
   const size_t plane = (size_t)nq * k;
   MHIP(hipSetDevice(s.device));
-  if (int rc = grow(s, reinterpret_cast<void **>(&s.d_queries), &s.cap_q, (size_t)nq * mx->D * 4)) return rc;
-  if (int rc = grow(s, reinterpret_cast<void **>(&s.d_packed), &s.cap_p, mx->pk * 4)) return rc;
-  const bool holds_all = mx->use_rccl || g == 0;
-  if (G > 1 && holds_all)
-    if (int rc = grow(s, reinterpret_cast<void **>(&s.d_gathered), &s.cap_g, (size_t)G * mx->pk * 4)) return rc;
-  if (mx->fast && g == 0)
-    if (int rc = grow(s, reinterpret_cast<void **>(&mx->d_head), &mx->cap_head, (size_t)nq * std::max(mx->kk, 1) * 2)) return rc;
+  MHIP(s.d_queries.ensure((size_t)nq * mx->D * 4));
+  MHIP(s.d_packed.ensure(c.pk * 4));
+  const bool holds_all = c.use_rccl || g == 0;
+  if (G > 1 && holds_all) MHIP(s.d_gathered.ensure((size_t)G * c.pk * 4));
+  if (c.fast && g == 0) MHIP(mx->d_head.ensure((size_t)nq * std::max(c.kk, 1) * 2));
   if (g == 0) {
-    if (mx->cap_out < 2 * plane * 4) {
-      if (mx->d_out_labels) MHIP(hipFree(mx->d_out_labels));
-      mx->d_out_labels = nullptr;
-      mx->cap_out = 0;
-      MHIP(hipMalloc(reinterpret_cast<void **>(&mx->d_out_labels), 2 * plane * 4));
-      mx->cap_out = 2 * plane * 4;
-    }
-    mx->d_out_dist = reinterpret_cast<float *>(mx->d_out_labels + plane);
+    MHIP(mx->d_out_labels.ensure(2 * plane * 4));
+    mx->d_out_dist = reinterpret_cast<float *>(mx->d_out_labels.as<int32_t>() + plane);
   }
-  if (mx->chain) {
+  if (c.chain) {
     const size_t state = (size_t)nq * 2 * (k - 1) * 4;
-    if (int rc = grow(s, reinterpret_cast<void **>(&s.d_list), &s.cap_list, 16 + (size_t)nq * 4)) return rc;
-    if (int rc = grow(s, reinterpret_cast<void **>(&s.d_state_in), &s.cap_si, state)) return rc;
-    if (int rc = grow(s, reinterpret_cast<void **>(&s.d_state_out), &s.cap_so, state)) return rc;
-    if (g == 0)
-      if (int rc = grow(s, reinterpret_cast<void **>(&mx->d_final), &mx->cap_final, (size_t)nq * 2 * (k - 1) * 4)) return rc;
-    while ((int)s.link_done.size() < mx->n_batches) {
+    MHIP(s.d_list.ensure(16 + (size_t)nq * 4));
+    MHIP(s.d_state_in.ensure(state));
+    MHIP(s.d_state_out.ensure(state));
+    if (g == 0) MHIP(mx->d_final.ensure(state));
+    while ((int)s.link_done.size() < c.n_batches) {
       hipEvent_t e = nullptr;
       MHIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
       s.link_done.push_back(e);
@@ -248,19 +227,21 @@ int run_shard(vaqhip_multi *mx, int g) {
   // (the previous search's exchange -- and chain -- has read this shard's buffers: never recorded = no wait)
   MHIP(hipStreamWaitEvent(s.stream, mx->consumed, 0));
   if (g == 0) MHIP(hipEventRecord(mx->ev[0], s.stream));
-  if (mx->d_queries0) {
+  float *dq = s.d_queries.as<float>();
+  int32_t *packed = s.d_packed.as<int32_t>();
+  if (c.d_queries0) {
     // device entry: the queries sit on shard 0's device; every shard takes its copy over the fabric
     MHIP(hipStreamWaitEvent(s.stream, mx->user_ready, 0));
-    MHIP(hipMemcpyPeerAsync(s.d_queries, s.device, mx->d_queries0, mx->sh[0].device, (size_t)nq * mx->D * 4, s.stream));
+    MHIP(hipMemcpyPeerAsync(dq, s.device, c.d_queries0, mx->sh[0].device, (size_t)nq * mx->D * 4, s.stream));
   } else {
-    MHIP(hipMemcpyAsync(s.d_queries, mx->queries, (size_t)nq * mx->D * 4, hipMemcpyHostToDevice, s.stream));
+    MHIP(hipMemcpyAsync(dq, c.queries, (size_t)nq * mx->D * 4, hipMemcpyHostToDevice, s.stream));
   }
-  int32_t *labels = G == 1 ? mx->d_out_labels : s.d_packed;
-  float *dist = G == 1 ? mx->d_out_dist : reinterpret_cast<float *>(s.d_packed + plane);
-  const int rc = mx->fast ? vaqhip_internal_search_fast_shard_device(s.ix, s.d_queries, nq, k, mx->projected, s.lo, mx->kk, labels, dist,
-                                                                     reinterpret_cast<uint16_t *>(s.d_packed + 2 * plane), s.stream)
-                 : mx->chain ? vaqhip_internal_search_plain_device(s.ix, s.d_queries, nq, k, mx->projected, labels, dist, s.stream)
-                             : vaqhip_search_device(s.ix, s.d_queries, nq, k, mx->projected, labels, dist, s.stream);
+  int32_t *labels = G == 1 ? mx->d_out_labels.as<int32_t>() : packed;
+  float *dist = G == 1 ? mx->d_out_dist : reinterpret_cast<float *>(packed + plane);
+  const int rc = c.fast ? vaqhip_internal_search_fast_shard_device(s.ix, dq, nq, k, c.projected, s.lo, c.kk, labels, dist,
+                                                                   reinterpret_cast<uint16_t *>(packed + 2 * plane), s.stream)
+                 : c.chain ? vaqhip_internal_search_plain_device(s.ix, dq, nq, k, c.projected, labels, dist, s.stream)
+                           : vaqhip_search_device(s.ix, dq, nq, k, c.projected, labels, dist, s.stream);
   if (rc) {
     s.err = vaqhip_last_error();
     return rc;
@@ -281,7 +262,7 @@ int exchange_rccl(vaqhip_multi *mx) {
   for (int g = 0; g < mx->G; g++) {
     Shard &s = mx->sh[g];
     if (hipSetDevice(s.device) != hipSuccess) { first = first ? first : -1; continue; }
-    nr = g_rccl.AllGather(s.d_packed, s.d_gathered, mx->pk, NCCL_INT32, s.comm, s.stream);
+    nr = g_rccl.AllGather(s.d_packed.p, s.d_gathered.p, mx->call.pk, NCCL_INT32, s.comm, s.stream);
     if (nr != 0 && !first) first = nr;
   }
   nr = g_rccl.GroupEnd();
@@ -294,34 +275,37 @@ int exchange_rccl(vaqhip_multi *mx) {
 // shard 0's device
 int gather_and_merge(vaqhip_multi *mx) {
   Shard &s = mx->sh[0];
-  const int G = mx->G, nq = mx->nq, k = mx->k;
+  const vaqhip_multi::Call &c = mx->call;
+  const int G = mx->G, nq = c.nq, k = c.k;
   const size_t plane = (size_t)nq * k;
+  int32_t *gathered = s.d_gathered.as<int32_t>(), *out_labels = mx->d_out_labels.as<int32_t>();
   MHIP(hipSetDevice(s.device));
   if (G > 1) {
-    if (!mx->use_rccl) {
+    if (!c.use_rccl) {
       for (int g = 0; g < G; g++) {
         MHIP(hipStreamWaitEvent(s.stream, mx->sh[g].done, 0));
-        MHIP(hipMemcpyPeerAsync(s.d_gathered + (size_t)g * mx->pk, s.device, mx->sh[g].d_packed, mx->sh[g].device,
-                                mx->pk * 4, s.stream));
+        MHIP(hipMemcpyPeerAsync(gathered + (size_t)g * c.pk, s.device, mx->sh[g].d_packed.p, mx->sh[g].device,
+                                c.pk * 4, s.stream));
       }
     }
     MHIP(hipEventRecord(mx->ev[2], s.stream));
     int rc;
-    if (mx->fast) {
+    if (c.fast) {
       // the head rows' distances from the planes of the shards that hold them, then the head's std::sort and
       // the stable merge "head, then the shards' lists in shard order"
       int start[VAQHIP_MAX_DEVICES + 1];
-      for (int g = 0; g <= G; g++) start[g] = g < G ? (int)std::min<int64_t>(mx->sh[g].lo, mx->kk) : mx->kk;
-      rc = vaqhip_internal_fast_head_gather_device(s.device, reinterpret_cast<const uint16_t *>(s.d_gathered + 2 * plane),
-                                                   (int64_t)(2 * mx->pk), G, start, nq, mx->kk, mx->d_head, s.stream);
+      for (int g = 0; g <= G; g++) start[g] = g < G ? (int)std::min<int64_t>(mx->sh[g].lo, c.kk) : c.kk;
+      uint16_t *head = mx->d_head.as<uint16_t>();
+      rc = vaqhip_internal_fast_head_gather_device(s.device, reinterpret_cast<const uint16_t *>(gathered + 2 * plane),
+                                                   (int64_t)(2 * c.pk), G, start, nq, c.kk, head, s.stream);
       if (!rc)
-        rc = vaqhip_merge_fast_device(s.device, mx->d_head, mx->kk, mx->kk, mx->id_base,
-                                      reinterpret_cast<const float *>(s.d_gathered + plane), s.d_gathered, G,
-                                      (int64_t)mx->pk, (int64_t)k, nq, k, mx->d_out_labels, mx->d_out_dist, s.stream);
+        rc = vaqhip_merge_fast_device(s.device, head, c.kk, c.kk, mx->id_base,
+                                      reinterpret_cast<const float *>(gathered + plane), gathered, G,
+                                      (int64_t)c.pk, (int64_t)k, nq, k, out_labels, mx->d_out_dist, s.stream);
     } else {
       rc = vaqhip_merge_topk_strided_device(
-          s.device, reinterpret_cast<const float *>(s.d_gathered + plane), s.d_gathered, G, (int64_t)mx->pk,
-          (int64_t)k, nq, k, mx->d_out_labels, mx->d_out_dist, s.stream);
+          s.device, reinterpret_cast<const float *>(gathered + plane), gathered, G, (int64_t)c.pk,
+          (int64_t)k, nq, k, out_labels, mx->d_out_dist, s.stream);
     }
     if (rc) {
       s.err = vaqhip_last_error();
@@ -333,7 +317,7 @@ int gather_and_merge(vaqhip_multi *mx) {
   return 0;
 }
 
-// "exact_ties" across shards, after the merge of the k + 1 lists (mx->k): flag on shard 0, the list to
+// "exact_ties" across shards, after the merge of the k + 1 lists (mx->call.k): flag on shard 0, the list to
 // every shard, the chain of links batch by batch, heap_reorder on shard 0 -> mx->d_final [2][nq][k].
 // Issued by the calling thread; everything is enqueued, nothing waited for.  A failure part-way leaves
 // streams that wait only for events already recorded (or never recorded: no wait).
@@ -347,46 +331,49 @@ int gather_and_merge(vaqhip_multi *mx) {
   } while (0)
 int chain_on_shard0(vaqhip_multi *mx) {
   Shard &s = mx->sh[0];
-  const int G = mx->G, nq = mx->nq, k = mx->k - 1;
+  const vaqhip_multi::Call &c = mx->call;
+  const int G = mx->G, nq = c.nq, k = c.k - 1;
   const size_t plane = (size_t)nq * k, entry = (size_t)2 * k;
-  int32_t *fl = mx->d_final;
-  float *fd = reinterpret_cast<float *>(mx->d_final + plane);
+  int32_t *fl = mx->d_final.as<int32_t>();
+  float *fd = reinterpret_cast<float *>(fl + plane);
   const size_t list_bytes = 16 + (size_t)nq * 4;
-  MIX(vaqhip_internal_exact_flag_device(s.device, nq, k, mx->d_out_labels, mx->d_out_dist, fl, fd,
-                                        reinterpret_cast<int *>(s.d_list + 4), reinterpret_cast<unsigned *>(s.d_list),
-                                        s.stream));
+  // a shard's replay list: the count in word 0, the entries from byte 16
+  auto list_count = [](const Shard &t) { return t.d_list.as<unsigned>(); };
+  auto list_entries = [](const Shard &t) { return reinterpret_cast<int *>(t.d_list.as<int32_t>() + 4); };
+  MIX(vaqhip_internal_exact_flag_device(s.device, nq, k, mx->d_out_labels.as<int32_t>(), mx->d_out_dist, fl, fd,
+                                        list_entries(s), list_count(s), s.stream));
   MHIP(hipEventRecord(mx->flagged, s.stream));
   for (int g = 1; g < G; g++) {
     Shard &t = mx->sh[g];
     MHIP(hipSetDevice(t.device));
     MHIP(hipStreamWaitEvent(t.stream, mx->flagged, 0));
-    MHIP(hipMemcpyPeerAsync(t.d_list, t.device, s.d_list, s.device, list_bytes, t.stream));
+    MHIP(hipMemcpyPeerAsync(t.d_list.p, t.device, s.d_list.p, s.device, list_bytes, t.stream));
   }
   // Batches are enqueued in order on every shard's stream: on distinct GPUs shard g works on batch b
   // while shard g + 1 works on batch b - 1.  Entries beyond the device-side count exit at once.
-  for (int b = 0; b < mx->n_batches; b++) {
-    const int e0 = b * mx->batch, ne = std::min(mx->batch, nq - e0);
+  for (int b = 0; b < c.n_batches; b++) {
+    const int e0 = b * c.batch, ne = std::min(c.batch, nq - e0);
     for (int g = 0; g < G; g++) {
       Shard &t = mx->sh[g];
       MHIP(hipSetDevice(t.device));
       if (g > 0) {
         const Shard &u = mx->sh[g - 1];
         MHIP(hipStreamWaitEvent(t.stream, u.link_done[b], 0));
-        MHIP(hipMemcpyPeerAsync(t.d_state_in + e0 * entry, t.device, u.d_state_out + e0 * entry, u.device,
-                                ne * entry * 4, t.stream));
+        MHIP(hipMemcpyPeerAsync(t.d_state_in.as<int32_t>() + e0 * entry, t.device, u.d_state_out.as<int32_t>() + e0 * entry,
+                                u.device, ne * entry * 4, t.stream));
       }
-      MIX(vaqhip_internal_exact_link_device(t.ix, k, reinterpret_cast<const int *>(t.d_list + 4),
-                                            reinterpret_cast<const unsigned *>(t.d_list), e0, ne,
-                                            g > 0 ? t.d_state_in : nullptr, t.d_state_out, t.stream));
+      MIX(vaqhip_internal_exact_link_device(t.ix, k, list_entries(t), list_count(t), e0, ne,
+                                            g > 0 ? t.d_state_in.as<int32_t>() : nullptr, t.d_state_out.as<int32_t>(),
+                                            t.stream));
       MHIP(hipEventRecord(t.link_done[b], t.stream));
     }
   }
   const Shard &last = mx->sh[G - 1];
   MHIP(hipSetDevice(s.device));
-  MHIP(hipStreamWaitEvent(s.stream, last.link_done[mx->n_batches - 1], 0));
-  MHIP(hipMemcpyPeerAsync(s.d_state_in, s.device, last.d_state_out, last.device, nq * entry * 4, s.stream));
-  MIX(vaqhip_internal_exact_finish_device(s.device, s.d_state_in, reinterpret_cast<const int *>(s.d_list + 4),
-                                          reinterpret_cast<const unsigned *>(s.d_list), nq, k, fl, fd, s.stream));
+  MHIP(hipStreamWaitEvent(s.stream, last.link_done[c.n_batches - 1], 0));
+  MHIP(hipMemcpyPeerAsync(s.d_state_in.p, s.device, last.d_state_out.p, last.device, nq * entry * 4, s.stream));
+  MIX(vaqhip_internal_exact_finish_device(s.device, s.d_state_in.as<int32_t>(), list_entries(s), list_count(s), nq, k, fl,
+                                          fd, s.stream));
   return 0;
 }
 #undef MIX
@@ -397,11 +384,11 @@ int deliver(vaqhip_multi *mx, const int32_t *src_labels, const float *src_dist, 
             hipStream_t user) {
   Shard &s = mx->sh[0];
   const int G = mx->G;
-  const size_t plane = (size_t)mx->nq * k;
+  const size_t plane = (size_t)mx->call.nq * k;
   MHIP(hipSetDevice(s.device));
   MHIP(hipEventRecord(mx->ev[3], s.stream));
   MHIP(hipEventRecord(mx->consumed, s.stream));
-  if (mx->d_queries0) {
+  if (mx->call.d_queries0) {
     // device entry: results into the caller's buffers on shard 0's device; the caller's stream waits
     // for them, the host does not
     MHIP(hipMemcpyAsync(labels, src_labels, plane * 4, hipMemcpyDeviceToDevice, s.stream));
@@ -428,11 +415,12 @@ int deliver(vaqhip_multi *mx, const int32_t *src_labels, const float *src_dist, 
 
 int finish_on_shard0(vaqhip_multi *mx, int32_t *labels, float *distances, hipStream_t user) {
   if (int rc = gather_and_merge(mx)) return rc;
-  if (!mx->chain) return deliver(mx, mx->d_out_labels, mx->d_out_dist, mx->k, labels, distances, user);
+  const vaqhip_multi::Call &c = mx->call;
+  if (!c.chain) return deliver(mx, mx->d_out_labels.as<int32_t>(), mx->d_out_dist, c.k, labels, distances, user);
   if (int rc = chain_on_shard0(mx)) return rc;
-  const int k = mx->k - 1;
-  return deliver(mx, mx->d_final, reinterpret_cast<const float *>(mx->d_final + (size_t)mx->nq * k), k, labels, distances,
-                 user);
+  const int k = c.k - 1;
+  const int32_t *fl = mx->d_final.as<int32_t>();
+  return deliver(mx, fl, reinterpret_cast<const float *>(fl + (size_t)c.nq * k), k, labels, distances, user);
 }
 
 int ensure_comms(vaqhip_multi *mx) {
@@ -505,20 +493,14 @@ void vaqhip_multi_destroy(vaqhip_multi *mx) {
     (void)hipSetDevice(s.device);
     if (s.stream) (void)hipStreamSynchronize(s.stream);
     if (s.comm && g_rccl.CommDestroy) (void)g_rccl.CommDestroy(s.comm);
-    if (s.d_queries) (void)hipFree(s.d_queries);
-    if (s.d_packed) (void)hipFree(s.d_packed);
-    if (s.d_gathered) (void)hipFree(s.d_gathered);
-    for (void *p : {(void *)s.d_list, (void *)s.d_state_in, (void *)s.d_state_out})
-      if (p) (void)hipFree(p);
+    for (DevBuf *b : {&s.d_queries, &s.d_packed, &s.d_gathered, &s.d_list, &s.d_state_in, &s.d_state_out}) b->release();
     for (hipEvent_t e : s.link_done) (void)hipEventDestroy(e);
     if (s.done) (void)hipEventDestroy(s.done);
     if (s.stream) (void)hipStreamDestroy(s.stream);
     if (s.ix) vaqhip_index_destroy(s.ix);
   }
   if (!mx->sh.empty()) (void)hipSetDevice(mx->sh[0].device);
-  if (mx->d_out_labels) (void)hipFree(mx->d_out_labels);
-  if (mx->d_final) (void)hipFree(mx->d_final);
-  if (mx->d_head) (void)hipFree(mx->d_head);
+  for (DevBuf *b : {&mx->d_out_labels, &mx->d_final, &mx->d_head}) b->release();
   for (auto &e : mx->ev)
     if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : {mx->user_ready, mx->consumed, mx->finished, mx->flagged})
@@ -604,7 +586,7 @@ int vaqhip_multi_set_lut_quantization(vaqhip_multi *mx, const float *offsets, co
   if (!mx) return mfail(VAQHIP_EINVAL, "multi index is null");
   if (!offsets || !scale) return mfail(VAQHIP_EINVAL, "null pointer");
   std::lock_guard<std::mutex> lk(mx->mu);
-  DeviceRestore keep;
+  DeviceGuard keep(DeviceGuard::restore_only);
   for (auto &s : mx->sh) {  // every shard quantises its tables by the same map
     const int rc = vaqhip_index_set_lut_quantization(s.ix, offsets, scale);
     if (rc) {
@@ -620,7 +602,7 @@ int vaqhip_multi_learn_quantization(vaqhip_multi *mx, const float *X, int64_t n,
                                     float *offsets_out, float *scale_out) {
   if (!mx) return mfail(VAQHIP_EINVAL, "multi index is null");
   std::lock_guard<std::mutex> lk(mx->mu);
-  DeviceRestore keep;
+  DeviceGuard keep(DeviceGuard::restore_only);
   // learnt once, on shard 0 (every shard holds the same codebooks and rotation, and the rows play no part),
   // then replicated: the values are the single index's, bit for bit
   std::vector<float> off((size_t)mx->M), sc((size_t)mx->M);
@@ -664,7 +646,7 @@ int vaqhip_multi_set_option(vaqhip_multi *mx, const char *key, int64_t value) {
   return VAQHIP_OK;
 }
 
-// one set of queries (mx->queries / d_queries0, nq, k): the shards' searches, the exchange, the merge
+// one set of queries (mx->call): the shards' searches, the exchange, the merge
 // (and the chain) on shard 0, the result to the caller
 static int search_set(vaqhip_multi *mx, bool rccl, int32_t *labels, float *distances, hipStream_t user) {
   // phase 1: every shard uploads (or copies) the queries and enqueues its search
@@ -680,7 +662,7 @@ static int search_set(vaqhip_multi *mx, bool rccl, int32_t *labels, float *dista
         return mfail(mx->pool.rc(g), "shard %d (device %d): %s", g, mx->sh[g].device, mx->sh[g].err.c_str());
   }
   // phase 2: the exchange, only now that every shard is known to take part
-  if (mx->use_rccl) {
+  if (mx->call.use_rccl) {
     const int rc = exchange_rccl(mx);
     if (rc) return rc;
   }
@@ -688,13 +670,12 @@ static int search_set(vaqhip_multi *mx, bool rccl, int32_t *labels, float *dista
     // one rank: the collective degenerates to a copy; run it anyway so that a one-GPU box
     // proves the RCCL binding (communicator, stream, datatype) end to end
     Shard &s = mx->sh[0];
-    const size_t plane = (size_t)mx->nq * mx->k;
+    const size_t plane = (size_t)mx->call.nq * mx->call.k;
     if (hipSetDevice(s.device) != hipSuccess) return mfail(VAQHIP_EHIP, "hipSetDevice");
-    if (grow(s, reinterpret_cast<void **>(&s.d_gathered), &s.cap_g, 2 * plane * 4))
-      return mfail(VAQHIP_ENOMEM, "%s", s.err.c_str());
-    const ncclResult_t nr = g_rccl.AllGather(mx->d_out_labels, s.d_gathered, 2 * plane, NCCL_INT32, s.comm, s.stream);
+    if (ensure(s, s.d_gathered, 2 * plane * 4)) return mfail(VAQHIP_ENOMEM, "%s", s.err.c_str());
+    const ncclResult_t nr = g_rccl.AllGather(mx->d_out_labels.p, s.d_gathered.p, 2 * plane, NCCL_INT32, s.comm, s.stream);
     if (nr != 0) return mfail(VAQHIP_EHIP, "ncclAllGather: %s", g_rccl.GetErrorString(nr));
-    if (hipMemcpyAsync(mx->d_out_labels, s.d_gathered, 2 * plane * 4, hipMemcpyDeviceToDevice, s.stream) != hipSuccess)
+    if (hipMemcpyAsync(mx->d_out_labels.p, s.d_gathered.p, 2 * plane * 4, hipMemcpyDeviceToDevice, s.stream) != hipSuccess)
       return mfail(VAQHIP_EHIP, "copy back from the gathered buffer");
   }
   Shard &s0 = mx->sh[0];
@@ -710,11 +691,13 @@ static int multi_search_common(vaqhip_multi *mx, const float *queries, const flo
   if (nq == 0) return VAQHIP_OK;
   if ((!queries && !d_queries0) || !labels || !distances) return mfail(VAQHIP_EINVAL, "null pointer");
   std::lock_guard<std::mutex> lk(mx->mu);
+  vaqhip_multi::Call &c = mx->call;
   // FAST over several shards: the head-and-lists form (one shard alone answers as the single index does)
-  mx->fast = mx->G > 1;
-  for (int g = 0; mx->fast && g < mx->G; g++) mx->fast = vaqhip_internal_fast_in_force(mx->sh[g].ix) != 0;
-  if (mx->fast && k > VAQHIP_MAX_K) return mfail(VAQHIP_EUNSUPPORTED, "k=%d > %d", k, VAQHIP_MAX_K);
-  DeviceRestore keep(mx->fast);  // (the other methods leave shard 0's device current, as they always have)
+  c.fast = mx->G > 1;
+  for (int g = 0; c.fast && g < mx->G; g++) c.fast = vaqhip_internal_fast_in_force(mx->sh[g].ix) != 0;
+  if (c.fast && k > VAQHIP_MAX_K) return mfail(VAQHIP_EUNSUPPORTED, "k=%d > %d", k, VAQHIP_MAX_K);
+  // (the other methods leave shard 0's device current, as they always have)
+  DeviceGuard keep(DeviceGuard::restore_only, c.fast);
   // RCCL when the GPUs are distinct and there is something to exchange (or when asked for by
   // option, which also exercises it on one device); device-to-device copies otherwise
   bool rccl = mx->exchange == EX_RCCL || (mx->exchange == EX_AUTO && mx->distinct && mx->G > 1);
@@ -723,8 +706,8 @@ static int multi_search_common(vaqhip_multi *mx, const float *queries, const flo
     if (rc) return rc;
   }
   // a one-shard index asked to use RCCL still goes through the collective (G == 1 skips packing)
-  mx->use_rccl = rccl && mx->G > 1;
-  mx->projected = projected;
+  c.use_rccl = rccl && mx->G > 1;
+  c.projected = projected;
   if (d_queries0) {
     if (hipSetDevice(mx->sh[0].device) != hipSuccess || hipEventRecord(mx->user_ready, user) != hipSuccess)
       return mfail(VAQHIP_EHIP, "recording the caller's stream");
@@ -732,24 +715,24 @@ static int multi_search_common(vaqhip_multi *mx, const float *queries, const flo
   // "exact_ties" over several shards: the chain, where the option has an effect on a single index too
   // (not TI, not the sequential sum, not FAST, k < VAQHIP_MAX_K); one set of queries at a time, because
   // every link reads the lookup tables its shard built for the set
-  mx->chain = mx->opt_exact && mx->G > 1;
-  for (int g = 0; mx->chain && g < mx->G; g++) mx->chain = vaqhip_internal_exact_applies(mx->sh[g].ix, k) != 0;
-  const int set = mx->chain ? std::min(nq, vaqhip_internal_query_chunk()) : nq;
+  c.chain = mx->opt_exact && mx->G > 1;
+  for (int g = 0; c.chain && g < mx->G; g++) c.chain = vaqhip_internal_exact_applies(mx->sh[g].ix, k) != 0;
+  const int set = c.chain ? std::min(nq, vaqhip_internal_query_chunk()) : nq;
   for (int q0 = 0; q0 < nq; q0 += set) {
     const int n = std::min(set, nq - q0);
-    mx->queries = queries ? queries + (size_t)q0 * mx->D : nullptr;
-    mx->d_queries0 = d_queries0 ? d_queries0 + (size_t)q0 * mx->D : nullptr;
-    mx->nq = n;
-    mx->k = mx->chain ? k + 1 : k;
+    c.queries = queries ? queries + (size_t)q0 * mx->D : nullptr;
+    c.d_queries0 = d_queries0 ? d_queries0 + (size_t)q0 * mx->D : nullptr;
+    c.nq = n;
+    c.k = c.chain ? k + 1 : k;
     // appends may have grown N past k, or the head with it: both are taken from the rows as they are now
-    mx->kk = mx->fast ? (int)std::min<int64_t>(k, mx->N) : 0;
-    mx->pk = 2 * (size_t)n * mx->k + (mx->fast ? ((size_t)n * mx->kk + 1) / 2 : 0);
-    if (mx->chain) {
+    c.kk = c.fast ? (int)std::min<int64_t>(k, mx->N) : 0;
+    c.pk = 2 * (size_t)n * c.k + (c.fast ? ((size_t)n * c.kk + 1) / 2 : 0);
+    if (c.chain) {
       // batches of the replay list, chosen from the set's size (the count of tied queries lives on the device)
       int b = mx->opt_exact_batch > 0 ? mx->opt_exact_batch : std::max(64, (n + 15) / 16);
       b = std::max(b, (n + 255) / 256);
-      mx->batch = b;
-      mx->n_batches = (n + b - 1) / b;
+      c.batch = b;
+      c.n_batches = (n + b - 1) / b;
     }
     const int rc = search_set(mx, rccl, labels + (size_t)q0 * k, distances + (size_t)q0 * k, user);
     if (rc) return rc;

@@ -460,7 +460,7 @@ int search_core(vaqhip_index *ix, const float *d_queries, int nq, int k, int pro
                               : "method TI needs vaqhip_index_set_ti_clusters first";
   if (int rc = check_search_args(ix, d_queries, nq, k, d_labels, d_dist, method_err)) return rc;
   if (nq == 0) return VAQHIP_OK;
-  if (int rc = ws_acquire(ix, st)) return rc;
+  WS_SCOPE(ws, ix, st);
   bool timing = ix->opt_timing != 0;
   hipEvent_t *ev = nullptr;
   if (timing) {
@@ -540,7 +540,7 @@ int search_core(vaqhip_index *ix, const float *d_queries, int nq, int k, int pro
       if (int rc = run_bucket_major(ix, bp, sp, bi, pl.bm_boot, k, stage_thr_out, d_labels, d_dist, st)) return rc;
       if (stage_thr_out) {
         ix->last = tm;
-        return ws_release(ix, st);
+        return ws.finish();
       }
     }
     if (defer || bm)
@@ -564,7 +564,7 @@ int search_core(vaqhip_index *ix, const float *d_queries, int nq, int k, int pro
   tm.n_searches = 0;
   ix->last = tm;
   if (timing) ix->ev_used++;
-  return ws_release(ix, st);
+  return ws.finish();
 }
 
 // original row -> bucketed row and bucket, for the replay of option "exact_ties": made at the first such search
@@ -599,7 +599,7 @@ int search_device_locked(vaqhip_index *ix, const float *d_queries, int nq, int k
     if (int rc = search_core(ix, d_queries + (size_t)q0 * ix->D, n, k + 1, projected, ix->w_ex_labels.as<int32_t>(),
                              ix->w_ex_dist.as<float>(), st))
       return rc;
-    if (int rc = ws_acquire(ix, st)) return rc;
+    WS_SCOPE(ws, ix, st);
     HIP_TRY(vaq::launch_exact_ties(ix->d_codes.as<uint32_t>(), ix->layout, ix->M, ix->W, ix->d_sub.as<vaq::SubDesc>(),
                                    ix->d_inv.as<uint32_t>(), ix->N > 0 ? ix->d_rowbucket.as<unsigned short>() : nullptr,
                                    ix->n_buckets, ix->bucket_shift, ix->bucket_t, ix->N, ix->w_lut.as<float>(), ix->lut_floats, n,
@@ -607,7 +607,7 @@ int search_device_locked(vaqhip_index *ix, const float *d_queries, int nq, int k
                                    ix->w_ex_labels.as<int32_t>(), ix->w_ex_dist.as<float>(), d_labels + (size_t)q0 * k,
                                    d_dist + (size_t)q0 * k, reinterpret_cast<int *>(ix->w_ex_list.as<unsigned char>() + 16),
                                    ix->w_ex_list.as<unsigned>(), st));
-    if (int rc = ws_release(ix, st)) return rc;
+    if (int rc = ws.finish()) return rc;
   }
   return VAQHIP_OK;
 }
@@ -616,12 +616,12 @@ int search_device_locked(vaqhip_index *ix, const float *d_queries, int nq, int k
 int search_finish_locked(vaqhip_index *ix, const int32_t *d_thr_in, hipStream_t st) {
   StagedState &ss = ix->staged;
   if (!ss.open) return fail(VAQHIP_ESTATE, "no staged search is open on this index");
-  if (int rc = ws_acquire(ix, st)) return rc;
+  WS_SCOPE(ws, ix, st);
   ss.open = false;
   if (d_thr_in) HIP_TRY(vaq::launch_bm_thresholds(ss.bp, d_thr_in, nullptr, 0, st));
   if (int rc = bm_run_rounds(ix, ss.bp, ss.limits, ss.r_next, ss.nr, ss.nr, ss.bi, st)) return rc;
   if (int rc = bm_fallback(ix, ss.sp, ss.defer_cap, ss.k, ss.labels, ss.dist, st)) return rc;
-  return ws_release(ix, st);
+  return ws.finish();
 }
 
 int search_host(vaqhip_index *ix, const float *queries, int nq, int k, int projected, int32_t *labels,
@@ -630,15 +630,13 @@ int search_host(vaqhip_index *ix, const float *queries, int nq, int k, int proje
   if (nq < 0 || k <= 0) return fail(VAQHIP_EINVAL, "nq=%d k=%d", nq, k);
   if (nq == 0) return VAQHIP_OK;
   if (!queries || !labels || !distances) return fail(VAQHIP_EINVAL, "null pointer");
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  ENTRY(ix);
   const size_t qbytes = (size_t)nq * ix->D * sizeof(float);
   const size_t rbytes = (size_t)nq * k * sizeof(float);
   HIP_TRY(ix->w_q.ensure(qbytes));
   HIP_TRY(ix->w_labels.ensure(rbytes));
   HIP_TRY(ix->w_dist.ensure(rbytes));
-  if (int rc = ws_acquire(ix, ix->stream)) return rc;
+  WS_SCOPE(ws, ix, ix->stream);
   HIP_TRY(hipMemcpyAsync(ix->w_q.p, queries, qbytes, hipMemcpyHostToDevice, ix->stream));
   int rc = search_device_locked(ix, ix->w_q.as<float>(), nq, k, projected, ix->w_labels.as<int32_t>(),
                                 ix->w_dist.as<float>(), ix->stream);
@@ -646,7 +644,7 @@ int search_host(vaqhip_index *ix, const float *queries, int nq, int k, int proje
   HIP_TRY(hipMemcpyAsync(labels, ix->w_labels.p, rbytes, hipMemcpyDeviceToHost, ix->stream));
   HIP_TRY(hipMemcpyAsync(distances, ix->w_dist.p, rbytes, hipMemcpyDeviceToHost, ix->stream));
   HIP_TRY(hipStreamSynchronize(ix->stream));
-  return VAQHIP_OK;
+  return ws.finish();
 }
 
 } // namespace
@@ -655,9 +653,7 @@ extern "C" {
 int vaqhip_search_device(vaqhip_index *ix, const float *d_queries, int nq, int k, int projected,
                          int32_t *d_labels, float *d_dist, void *stream) {
   if (!ix) return fail(VAQHIP_EINVAL, "index is null");
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  ENTRY(ix);
   return search_device_locked(ix, d_queries, nq, k, projected, d_labels, d_dist,
                               static_cast<hipStream_t>(stream));
 }
@@ -685,9 +681,7 @@ int vaqhip_search_begin_device(vaqhip_index *ix, const float *d_queries, int nq,
                                int32_t *d_labels, float *d_distances, int32_t *d_thresholds_out, void *stream) {
   if (!ix) return fail(VAQHIP_EINVAL, "index is null");
   if (!d_thresholds_out) return fail(VAQHIP_EINVAL, "null pointer");
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  ENTRY(ix);
   if (ix->opt_exact) return fail(VAQHIP_EUNSUPPORTED, "exact_ties is a property of ONE index; shards merge by (distance, label)");
   if (fast_only(ix)) return fail(VAQHIP_EUNSUPPORTED, "method FAST has no staged form");
   return search_core(ix, d_queries, nq, k, projected, d_labels, d_distances, static_cast<hipStream_t>(stream),
@@ -696,9 +690,7 @@ int vaqhip_search_begin_device(vaqhip_index *ix, const float *d_queries, int nq,
 
 int vaqhip_search_finish_device(vaqhip_index *ix, const int32_t *d_thresholds_in, void *stream) {
   if (!ix) return fail(VAQHIP_EINVAL, "index is null");
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  ENTRY(ix);
   return search_finish_locked(ix, d_thresholds_in, static_cast<hipStream_t>(stream));
 }
 
@@ -715,9 +707,7 @@ int vaqhip_internal_search_plain_device(vaqhip_index *ix, const float *d_queries
                                         int32_t *d_labels, float *d_dist, void *stream) {
   if (!ix) return fail(VAQHIP_EINVAL, "index is null");
   if (nq > QUERY_CHUNK) return fail(VAQHIP_EINVAL, "nq=%d > %d", nq, QUERY_CHUNK);
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  ENTRY(ix);
   if (fast_only(ix)) return fail(VAQHIP_EUNSUPPORTED, "method FAST has no chained form");
   return search_core(ix, d_queries, nq, k, projected, d_labels, d_dist, static_cast<hipStream_t>(stream));
 }
@@ -738,19 +728,17 @@ int vaqhip_internal_exact_link_device(vaqhip_index *ix, int k, const int *d_list
   if (!ix) return fail(VAQHIP_EINVAL, "index is null");
   if (k <= 0 || k >= VAQHIP_MAX_K || e0 < 0 || n_entries < 0 || !d_list || !d_count || !d_state_out)
     return fail(VAQHIP_EINVAL, "bad arguments");
-  std::lock_guard<std::mutex> lk(ix->mu);
-  DeviceGuard g(ix->device);
-  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device);
+  ENTRY(ix);
   if (ix->N < 0) return fail(VAQHIP_ESTATE, "search before codes were set");
   if (ix->ti_T > 0 || ix->seq || fast_only(ix)) return fail(VAQHIP_EUNSUPPORTED, "no replay for this method");
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (int rc = ws_acquire(ix, st)) return rc;
+  WS_SCOPE(ws, ix, st);
   if (int rc = ensure_inverse_perm(ix, st)) return rc;
   HIP_TRY(vaq::launch_exact_link(ix->d_codes.as<uint32_t>(), ix->layout, ix->M, ix->W, ix->d_sub.as<vaq::SubDesc>(),
                                  ix->d_inv.as<uint32_t>(), ix->N > 0 ? ix->d_rowbucket.as<unsigned short>() : nullptr,
                                  ix->n_buckets, ix->bucket_shift, ix->bucket_t, ix->N, ix->w_lut.as<float>(), ix->lut_floats,
                                  k, ix->id_base, d_list, d_count, e0, n_entries, d_state_in, d_state_out, st));
-  return ws_release(ix, st);
+  return ws.finish();
 }
 
 int vaqhip_internal_exact_finish_device(int device, const int32_t *d_state, const int *d_list, const unsigned *d_count,
