@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 106
+#define VAQHIP_VERSION 107
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -130,8 +130,8 @@ int vaqhip_index_add_codes_u16_device(vaqhip_index *ix, const uint16_t *d_codes_
 /* VAQ::clusterTI (VAQ.hpp:106, VAQ.cpp:878-999) from the point where mTIClusters
  * exists: `clusters` is mTIClusters, T x (seg_num * D/M) row-major, i.e. T
  * centres over the first seg_num subspaces (mTIClusterNum, mTISegmentNum); how
- * they were made (the reference: k-means over decoded codes, VAQ.cpp:897-900) is
- * the caller's business, like the codebooks.  Every code row joins its nearest
+ * they were made is the caller's business, like the codebooks (the reference's own
+ * way, k-means over decoded codes, VAQ.cpp:897-900: vaqhip_index_cluster_ti_kmeans below).  Every code row joins its nearest
  * centre (VAQ.cpp:926-950), clusters are ordered farthest member first
  * (:972-979) and the packed codes are regrouped on the GPU (:984-996).  May be
  * called before or after the codes are set (the reference calls it after
@@ -140,6 +140,35 @@ int vaqhip_index_add_codes_u16_device(vaqhip_index *ix, const uint16_t *d_codes_
  * Labels stay ORIGINAL row indices + id_base, as mTIClustersMember holds them. */
 int vaqhip_index_set_ti_clusters(vaqhip_index *ix, const float *clusters_rowmajor, int T,
                                  int seg_num);
+
+/* VAQ::clusterTI(true) (VAQ.cpp:896-900): the centres themselves, made on the GPU as the reference makes
+ * them -- KMeans::staticFitCodebook (KMeans.hpp:618-652) -> staticFitSampling (:487-616) over the decoded
+ * first seg_num codes of the index's rows in original row order:
+ *   sample   N > 256 * T: rows randomPermutation(N)[0 .. 256 * T) (utils/Random.hpp:18-28, mt19937(13517106)),
+ *            in that order; else all rows
+ *   seeds    means[i] = row randomPermutation(rows)[i] of the sample
+ *   Lloyd    until no centre changes or max_iter (the reference passes 50): nearest centre by
+ *            sqrt(squaredNorm) with Eigen's summation order, strict `<`; sums in the order of the reference's
+ *            two OpenMP threads; new = (p0 + p1) / float(count)
+ * The result equals the reference's bit for bit where finite (compiled without -ffast-math and with
+ * -ffp-contract=off, as everything this library is compared with).  An empty cluster is 0 / 0: its centre
+ * becomes NaN, stays NaN, and the loop then runs to max_iter -- the reference's behaviour, reproduced, not
+ * repaired (equal decoded rows among the seeds are enough for it).
+ * Then exactly what vaqhip_index_set_ti_clusters(ix, means, T, seg_num) does.  clusters_out (T x seg_num * D/M),
+ * iters_out (iterations run) and nan_rows_out (centres holding a NaN) may be NULL.
+ * VAQHIP_ESTATE before the codes are set or while a staged search is open; VAQHIP_EINVAL for T < 1, T > N (the
+ * reference reads out of bounds), seg_num outside 1..M, max_iter < 1; the limits of set_ti_clusters apply.
+ * Calling it again, or after add_codes, clusters the codes then present.  Synchronises. */
+int vaqhip_index_cluster_ti_kmeans(vaqhip_index *ix, int T, int seg_num, int max_iter, float *clusters_out,
+                                   int *iters_out, int *nan_rows_out);
+typedef struct {
+  float total_ms;                             /* host time of the k-means: unpack, sample, decode, iterations */
+  float assign_ms, accumulate_ms, update_ms;  /* per phase over all iterations; only with option "timing" = 1
+                                                 (each phase then ends with a stream synchronisation), else 0 */
+  int iterations, rows, dims, clusters;       /* rows = the sample's */
+} vaqhip_kmeans_timing;
+/* figures of the last vaqhip_index_cluster_ti_kmeans on this index */
+int vaqhip_last_kmeans_timing(vaqhip_index *ix, vaqhip_kmeans_timing *out);
 
 /* mMethods (VAQ::parseMethodString, VAQ.cpp:1205-1262) and mVisit (VAQ.hpp:84,
  * demo_vaq --visit-cluster).  With TI:

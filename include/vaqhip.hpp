@@ -75,8 +75,8 @@ public:
   std::vector<int> mBitsAlloc;
   CodebookType mCodebook;                     // N x M uint16
   // VAQ.hpp:77-84: triangle-inequality clusters.  mTIClusters is T x (mTISegmentNum * mSubsLen);
-  // the reference fills it in clusterTI() with a k-means over decoded codes -- here the caller
-  // provides it (like the codebooks), or clusterTI(false) draws random decoded rows.
+  // the reference fills it in clusterTI() with a k-means over decoded codes: clusterTI(true) does the
+  // same on the GPU, clusterTI(false) draws random decoded rows, or the caller provides it.
   int mTIClusterNum = 0, mTISegmentNum = -1;
   float mTIVariance = 1.0f;
   float mVisit = 1.0f;
@@ -238,17 +238,34 @@ public:
 
   // VAQ::clusterTI, VAQ.hpp:106 / VAQ.cpp:878-999.  useKMeans = false is the reference's
   // other branch (:901-911): mTIClusterNum random code rows, decoded over the first
-  // mTISegmentNum subspaces.  The reference's k-means branch (:897-900) is training and
-  // is not provided: fill mTIClusters yourself for that.  The grouping itself happens
-  // on the GPU at the next search().
+  // mTISegmentNum subspaces; the grouping itself then happens on the GPU at the next search().
+  // useKMeans = true is the reference's k-means over decoded code rows (:897-900,
+  // KMeans::staticFitCodebook with max_iter = 50) on the GPU, centre for centre what the reference
+  // computes (vaqhip_index_cluster_ti_kmeans); it pushes mCodebook first and groups at once.
+  // Single-device only: with setDevices() fill mTIClusters yourself.
+  int mKMeansIterations = 0, mKMeansNanRows = 0;  // how the last k-means ended (not in the reference)
   void clusterTI(bool useKMeans = false, bool verbose = false) {
     (void)verbose;
     if (mTIVariance < 1.0f)
       throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: TI<T>var<v> needs train()'s variance profile; use TI<T>m<seg>");
     if (mTISegmentNum == -1) mTISegmentNum = mHighestSubs();
+    if (mTIClusters.rows() == 0 && useKMeans) {
+      if (!mDevices.empty())
+        throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: the k-means of clusterTI runs on a single-device index");
+      const uint32_t methods = mMethods;
+      mMethods = (methods & ~(uint32_t)NNMethod::TI) ? (methods & ~(uint32_t)NNMethod::TI) : (uint32_t)NNMethod::Heap;
+      try { sync(); } catch (...) { mMethods = methods; throw; }  // the codes, in the exhaustive order
+      mMethods = methods;
+      mTIClusters = RowMatrixF((size_t)(mTIClusterNum > 0 ? mTIClusterNum : 0), (size_t)mTISegmentNum * mSubsLen());
+      const int rc = vaqhip_index_cluster_ti_kmeans(h_, mTIClusterNum, mTISegmentNum, 50, mTIClusters.data(),
+                                                    &mKMeansIterations, &mKMeansNanRows);
+      if (rc) mTIClusters = RowMatrixF();
+      check(rc);
+      mMethods |= NNMethod::TI;
+      ti_set_ = true;  // the index holds these centres already
+      return;
+    }
     if (mTIClusters.rows() == 0) {
-      if (useKMeans)
-        throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: the k-means of clusterTI is training; set mTIClusters");
       if (mCodebook.rows() == 0) throw Error(VAQHIP_ESTATE, "vaqhip: clusterTI needs mCodebook");
       const int L = mSubsLen();
       mTIClusters = RowMatrixF((size_t)mTIClusterNum, (size_t)mTISegmentNum * L);

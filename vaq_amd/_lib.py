@@ -15,7 +15,8 @@ _LIB_PATH = os.environ.get("VAQHIP_LIB") or os.path.join(_HERE, "lib", "libvaqhi
 SYMBOLS = [
     "vaqhip_index_create", "vaqhip_index_create_ex", "vaqhip_index_destroy", "vaqhip_index_set_codes_u16",
     "vaqhip_index_set_codes_u16_device", "vaqhip_index_add_codes_u16", "vaqhip_index_add_codes_u16_device",
-    "vaqhip_index_set_ti_clusters", "vaqhip_index_set_method",
+    "vaqhip_index_set_ti_clusters", "vaqhip_index_cluster_ti_kmeans", "vaqhip_last_kmeans_timing",
+    "vaqhip_index_set_method",
     "vaqhip_index_set_lut_quantization", "vaqhip_learn_quantization", "vaqhip_build_small_lut",
     "vaqhip_search", "vaqhip_search_projected",
     "vaqhip_search_device", "vaqhip_search_staged_supported", "vaqhip_search_begin_device",
@@ -59,6 +60,12 @@ class Timing(C.Structure):
                 ("seed_slices", C.c_int), ("early_abandon", C.c_int),
                 ("best_first", C.c_int), ("deferred_queries", C.c_int),
                 ("bucket_major", C.c_int)]
+
+
+class KmeansTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("assign_ms", C.c_float), ("accumulate_ms", C.c_float),
+                ("update_ms", C.c_float), ("iterations", C.c_int), ("rows", C.c_int), ("dims", C.c_int),
+                ("clusters", C.c_int)]
 
 
 class MultiInfo(C.Structure):
@@ -106,6 +113,8 @@ def load():
     L.vaqhip_index_add_codes_u16.argtypes = [vp, vp, i64]
     L.vaqhip_index_add_codes_u16_device.argtypes = [vp, vp, i64, vp]
     L.vaqhip_index_set_ti_clusters.argtypes = [vp, vp, i32, i32]
+    L.vaqhip_index_cluster_ti_kmeans.argtypes = [vp, i32, i32, i32, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.vaqhip_last_kmeans_timing.argtypes = [vp, C.POINTER(KmeansTiming)]
     L.vaqhip_index_set_method.argtypes = [vp, C.c_uint, C.c_float]
     L.vaqhip_index_set_lut_quantization.argtypes = [vp, vp, vp]
     L.vaqhip_learn_quantization.argtypes = [vp, vp, i64, i32, C.c_float, vp, vp]

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vaq_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "vaq_amd", "lib")
 LIB = os.path.join(LIBDIR, "libvaqhip.so")
-SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_fast.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp",
+SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_fast.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp",
            "vaqhip_multi.cpp"]
 KERNEL_HEADER = os.path.join(CSRC, "vaq_kernels.h")
 API_HEADER = os.path.join(ROOT, "include", "vaqhip.h")
@@ -24,7 +24,7 @@ SCAN_BF_HEADER = os.path.join(CSRC, "vaq_scan_bf.h")
 FAST_HEADER = os.path.join(CSRC, "vaq_fast.h")
 INTERNAL_HEADER = os.path.join(CSRC, "vaqhip_internal.h")
 INDEX_HEADER = os.path.join(CSRC, "vaqhip_index.h")  # private to the single-index host files
-DEV_HEADER = os.path.join(CSRC, "vaqhip_dev.h")      # DevBuf, DeviceGuard: both hosts and the two scratch allocators
+DEV_HEADER = os.path.join(CSRC, "vaqhip_dev.h")      # DevBuf, DeviceGuard: both hosts and the scratch allocators
 JOB_POOL_HEADER = os.path.join(CSRC, "job_pool.h")
 
 
@@ -34,7 +34,7 @@ def _deps(src: str):
     if src.endswith(".cpp"):
         deps += [API_HEADER, INTERNAL_HEADER, DEV_HEADER]
         deps.append(JOB_POOL_HEADER if src == "vaqhip_multi.cpp" else INDEX_HEADER)
-    if src in ("vaq_kernels.hip", "vaq_ti.hip"):
+    if src in ("vaq_kernels.hip", "vaq_ti.hip", "vaq_kmeans.hip"):
         deps.append(DEV_HEADER)
     if src in ("vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip"):
         deps.append(SCAN_HEADER)

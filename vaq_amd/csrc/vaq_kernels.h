@@ -332,5 +332,22 @@ hipError_t launch_ti_plan(const float *qproj, int nq, int D, int d, const float 
 // extra LDS bytes of a TI scan workgroup staging `cap` entries of its visiting list
 size_t scan_ti_lds_bytes(int cap);
 
+// ---- the k-means of VAQ::clusterTI(true) (vaq_kmeans.hip) ------------------
+// d_scodes[rows][seg] = the first seg codes of row d_ids[r] (nullptr: row r) of the N x M matrix d_codes
+hipError_t launch_kmeans_gather(const uint16_t *d_codes, int M, const int *d_ids, int rows, int seg,
+                                uint16_t *d_scodes, hipStream_t st);
+// host time per phase over all iterations, each phase ended by a stream synchronisation
+struct KmeansPhases {
+  double assign_ms = 0, accumulate_ms = 0, update_ms = 0;
+};
+// KMeans::staticFitSampling on the rows whose first seg codes are d_scodes[rows][seg] (device, in the
+// reference's row order): d_means[T][seg * L] seeded from rows seed_rows[0..T) (host), then Lloyd iterations
+// until no centre changes or max_iter.  *no_centre_out != 0: some row had no centre at a distance below FLT_MAX
+// (the reference indexes row -1 there); the centres are then not to be used.  phases (optional) adds one stream
+// synchronisation per phase.  Synchronises the stream.
+hipError_t kmeans_fit(const uint16_t *d_scodes, int rows, int seg, int L, const SubDesc *sub, const float *cent,
+                      const int *seed_rows, int T, int max_iter, float *d_means, int *iters_out, int *no_centre_out,
+                      KmeansPhases *phases, hipStream_t st);
+
 } // namespace vaq
 #endif

@@ -1,6 +1,11 @@
 // vaqhip_codes.cpp -- the rows of the single-device index: upload, bucketed (or TI-grouped) order,
-// packing, append, TI clustering.
+// packing, append, TI clustering (the regrouping, and the k-means that makes the centres).
 #include "vaqhip_index.h"
+
+#include <chrono>
+#include <cmath>
+#include <random>
+#include <unordered_map>
 
 using namespace vaqhost;
 
@@ -225,34 +230,8 @@ int add_codes_common(vaqhip_index *ix, const uint16_t *codes, bool on_device, in
   if (int rc = build_rows(ix, rows.as<uint16_t>(), N, st)) return rc;  // synchronises
   return ws.finish();
 }
-} // namespace
-
-extern "C" {
-int vaqhip_index_add_codes_u16(vaqhip_index *ix, const uint16_t *codes, int64_t n_new) {
-  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
-  return add_codes_common(ix, codes, false, n_new, ix->stream);
-}
-
-int vaqhip_index_add_codes_u16_device(vaqhip_index *ix, const uint16_t *d_codes, int64_t n_new, void *stream) {
-  return add_codes_common(ix, d_codes, true, n_new, static_cast<hipStream_t>(stream));
-}
-
-int vaqhip_index_set_codes_u16(vaqhip_index *ix, const uint16_t *codes, int64_t N, int64_t id_base) {
-  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
-  if (int rc = set_codes_common(ix, codes, false, N, id_base, ix->stream)) return rc;
-  DeviceGuard g(ix->device);
-  HIP_TRY(hipStreamSynchronize(ix->stream));
-  return VAQHIP_OK;
-}
-
-int vaqhip_index_set_codes_u16_device(vaqhip_index *ix, const uint16_t *d_codes, int64_t N,
-                                      int64_t id_base, void *stream) {
-  return set_codes_common(ix, d_codes, true, N, id_base, static_cast<hipStream_t>(stream));
-}
-
-int vaqhip_index_set_ti_clusters(vaqhip_index *ix, const float *clusters, int T, int seg_num) {
-  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
-  if (T < 0 || (T > 0 && !clusters)) return fail(VAQHIP_EINVAL, "bad clusters/T");
+// what set_ti_clusters and cluster_ti_kmeans refuse alike (T > 0)
+int check_ti_shape(const vaqhip_index *ix, int T, int seg_num) {
   if (T > VAQHIP_MAX_TI_CLUSTERS)
     return fail(VAQHIP_EUNSUPPORTED, "T=%d > %d clusters", T, VAQHIP_MAX_TI_CLUSTERS);
   if (T > 0 && (seg_num < 1 || seg_num > ix->M))
@@ -260,7 +239,11 @@ int vaqhip_index_set_ti_clusters(vaqhip_index *ix, const float *clusters, int T,
   if (T > 0 && (int64_t)seg_num * ix->L > 1024)
     return fail(VAQHIP_EUNSUPPORTED, "TI centres of %d dims (> 1024)", seg_num * ix->L);
   if (T > 0 && ix->seq) return fail(VAQHIP_EINVAL, "TI is a VAQ::search method, not a queryLUT one");
-  ENTRY(ix);
+  return VAQHIP_OK;
+}
+
+// vaqhip_index_set_ti_clusters under the index's lock, arguments checked
+int set_ti_clusters_locked(vaqhip_index *ix, const float *clusters, int T, int seg_num) {
   if (T == 0 && ix->ti_T == 0) return VAQHIP_OK;
   hipStream_t st = ix->stream;
   // (a search enqueued on another stream may still be scanning the rows this call regroups)
@@ -297,5 +280,136 @@ int vaqhip_index_set_ti_clusters(vaqhip_index *ix, const float *clusters, int T,
   }
   HIP_TRY(hipStreamSynchronize(st));
   return ws.finish();
+}
+
+// The first r entries of randomPermutation(n) (utils/Random.hpp:18-28, mt19937(13517106), i2 = i + mt() % (n - i)):
+// entry i is final after step i, so r steps over a sparse map of the positions touched so far suffice.
+std::vector<int> permutation_head(int64_t n, int64_t r) {
+  r = std::min(r, n);
+  std::vector<int> out((size_t)r);
+  std::unordered_map<int, int> moved;
+  std::mt19937 mt(13517106u);
+  auto at = [&](int i) {
+    auto it = moved.find(i);
+    return it == moved.end() ? i : it->second;
+  };
+  for (int64_t i = 0; i < r; i++) {
+    if (i + 1 < n) {
+      const int i2 = (int)i + (int)(mt() % (unsigned)(int)(n - i));
+      const int vi = at((int)i);
+      out[i] = at(i2);
+      moved[i2] = vi;
+    } else {
+      out[i] = at((int)i);
+    }
+  }
+  return out;
+}
+
+// KMeans::staticFitCodebook's sample: more than 256 rows per centre are cut to the first 256 * T of a permutation
+constexpr int64_t KMEANS_ROWS_PER_CENTRE = 256;
+} // namespace
+
+extern "C" {
+int vaqhip_index_add_codes_u16(vaqhip_index *ix, const uint16_t *codes, int64_t n_new) {
+  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
+  return add_codes_common(ix, codes, false, n_new, ix->stream);
+}
+
+int vaqhip_index_add_codes_u16_device(vaqhip_index *ix, const uint16_t *d_codes, int64_t n_new, void *stream) {
+  return add_codes_common(ix, d_codes, true, n_new, static_cast<hipStream_t>(stream));
+}
+
+int vaqhip_index_set_codes_u16(vaqhip_index *ix, const uint16_t *codes, int64_t N, int64_t id_base) {
+  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
+  if (int rc = set_codes_common(ix, codes, false, N, id_base, ix->stream)) return rc;
+  DeviceGuard g(ix->device);
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  return VAQHIP_OK;
+}
+
+int vaqhip_index_set_codes_u16_device(vaqhip_index *ix, const uint16_t *d_codes, int64_t N,
+                                      int64_t id_base, void *stream) {
+  return set_codes_common(ix, d_codes, true, N, id_base, static_cast<hipStream_t>(stream));
+}
+
+int vaqhip_index_set_ti_clusters(vaqhip_index *ix, const float *clusters, int T, int seg_num) {
+  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
+  if (T < 0 || (T > 0 && !clusters)) return fail(VAQHIP_EINVAL, "bad clusters/T");
+  if (int rc = check_ti_shape(ix, T, seg_num)) return rc;
+  ENTRY(ix);
+  return set_ti_clusters_locked(ix, clusters, T, seg_num);
+}
+
+int vaqhip_index_cluster_ti_kmeans(vaqhip_index *ix, int T, int seg_num, int max_iter, float *clusters_out,
+                                   int *iters_out, int *nan_rows_out) {
+  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
+  if (T < 1 || max_iter < 1) return fail(VAQHIP_EINVAL, "T=%d max_iter=%d", T, max_iter);
+  if (int rc = check_ti_shape(ix, T, seg_num)) return rc;
+  ENTRY(ix);
+  if (ix->N < 0) return fail(VAQHIP_ESTATE, "the k-means of clusterTI runs over the codes: set them first");
+  if (ix->staged.open)
+    return fail(VAQHIP_ESTATE, "a staged search is open on this index: call vaqhip_search_finish_device first");
+  if (T > ix->N)  // (the sample is min(N, 256 * T) rows: never fewer than T unless N is)
+    return fail(VAQHIP_EINVAL, "T=%d centres from %lld rows (the reference reads out of bounds)", T, (long long)ix->N);
+  const int64_t N = ix->N;
+  const int rows = (int)std::min<int64_t>(N, KMEANS_ROWS_PER_CENTRE * T), dd = seg_num * ix->L;
+  std::vector<float> means((size_t)T * dd);
+  int iters = 0, no_centre = 0;
+  {
+    hipStream_t st = ix->stream;
+    WS_SCOPE(ws, ix, st);  // (a search enqueued on another stream may still be using the index)
+    const auto t0 = std::chrono::steady_clock::now();
+    // the codes in original row order, then the sample's first seg_num codes as [rows][seg_num]
+    DevBuf all, ids, scodes, d_means;
+    HIP_TRY(all.ensure((size_t)N * ix->M * sizeof(uint16_t)));
+    HIP_TRY(vaq::launch_unpack_codes(ix->d_codes.as<uint32_t>(), N, ix->M, ix->layout, ix->W,
+                                     ix->d_sub.as<vaq::SubDesc>(), ix->d_perm.as<uint32_t>(), all.as<uint16_t>(), st));
+    std::vector<int> sample;
+    if (N > rows) {
+      sample = permutation_head(N, rows);
+      HIP_TRY(ids.ensure((size_t)rows * sizeof(int)));
+      HIP_TRY(hipMemcpyAsync(ids.p, sample.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice, st));
+    }
+    HIP_TRY(scodes.ensure((size_t)rows * seg_num * sizeof(uint16_t)));
+    HIP_TRY(vaq::launch_kmeans_gather(all.as<uint16_t>(), ix->M, N > rows ? ids.as<int>() : nullptr, rows, seg_num,
+                                      scodes.as<uint16_t>(), st));
+    const std::vector<int> seeds = permutation_head(rows, T);
+    HIP_TRY(d_means.ensure(means.size() * sizeof(float)));
+    vaq::KmeansPhases ph;
+    HIP_TRY(vaq::kmeans_fit(scodes.as<uint16_t>(), rows, seg_num, ix->L, ix->d_sub.as<vaq::SubDesc>(),
+                            ix->d_cent.as<float>(), seeds.data(), T, max_iter, d_means.as<float>(), &iters, &no_centre,
+                            ix->opt_timing ? &ph : nullptr, st));  // synchronises
+    HIP_TRY(hipMemcpy(means.data(), d_means.p, means.size() * sizeof(float), hipMemcpyDeviceToHost));
+    ix->km_last = vaqhip_kmeans_timing{};
+    ix->km_last.total_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ix->km_last.assign_ms = (float)ph.assign_ms;
+    ix->km_last.accumulate_ms = (float)ph.accumulate_ms;
+    ix->km_last.update_ms = (float)ph.update_ms;
+    ix->km_last.iterations = iters;
+    ix->km_last.rows = rows;
+    ix->km_last.dims = dd;
+    ix->km_last.clusters = T;
+    if (int rc = ws.finish()) return rc;
+  }
+  if (no_centre)
+    return fail(VAQHIP_EINVAL, "a row is at a distance >= FLT_MAX (or NaN) from every centre: the reference indexes row -1");
+  int nan_rows = 0;
+  for (int c = 0; c < T; c++) {
+    bool nan = false;
+    for (int j = 0; j < dd; j++) nan |= std::isnan(means[(size_t)c * dd + j]);
+    nan_rows += nan;
+  }
+  if (clusters_out) std::memcpy(clusters_out, means.data(), means.size() * sizeof(float));
+  if (iters_out) *iters_out = iters;
+  if (nan_rows_out) *nan_rows_out = nan_rows;
+  return set_ti_clusters_locked(ix, means.data(), T, seg_num);
+}
+
+int vaqhip_last_kmeans_timing(vaqhip_index *ix, vaqhip_kmeans_timing *out) {
+  if (!ix || !out) return fail(VAQHIP_EINVAL, "null pointer");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  *out = ix->km_last;
+  return VAQHIP_OK;
 }
 } // extern "C"

@@ -118,6 +118,7 @@ struct vaqhip_index {
   std::vector<hipEvent_t> ev;   // EV_SETS * 6, created on first use
   int ev_used = 0;              // searches recorded since the last vaqhip_last_timing
   vaqhip_timing last = {};
+  vaqhip_kmeans_timing km_last = {};  // the last vaqhip_index_cluster_ti_kmeans
   std::mutex mu;
 };
 

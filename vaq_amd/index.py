@@ -232,29 +232,38 @@ class VaqHip:
     def clusterTI(self, useKMeans: bool = False, verbose: bool = False, seed: int = 13517106) -> None:
         """VAQ::clusterTI (VAQ.hpp:106, VAQ.cpp:878-999).  Makes mTIClusters when it
         is not set yet -- useKMeans=False: mTIClusterNum random code rows, decoded
-        (VAQ.cpp:901-911); True: k-means over decoded code rows (:897-900, at most
-        256 rows per centre as KMeans::staticFitCodebook samples) -- and leaves the
-        grouping itself (:913-996) to the GPU at the next search."""
+        (VAQ.cpp:901-911, drawn with `seed`); True: the reference's k-means over decoded
+        code rows (:897-900, KMeans::staticFitCodebook, 50 iterations at most) on the GPU,
+        centre for centre what the reference computes (vaqhip_index_cluster_ti_kmeans;
+        kmeansIterations / kmeansNanRows tell how it ended) -- and leaves the grouping
+        itself (:913-996) to the GPU: at once with the k-means, else at the next search."""
         if self.mTIVariance < 1:
             raise _lib.VaqHipError(-2, "TI<T>var<v> needs train()'s variance profile; use TI<T>m<seg>")
         seg = self.mTISegmentNum if self.mTISegmentNum != -1 else self.mHighestSubs  # :890-892
         self.mTISegmentNum = seg
-        if self.mTIClusters is None:
+        if self.mTIClusters is None and useKMeans:
+            # the codes go to the device first, in the exhaustive order (no centres yet)
+            methods = self.mMethods
+            self.mMethods = (methods & ~NNMethod.TI) or NNMethod.Heap
+            try:
+                self._ensure_codes()
+            finally:
+                self.mMethods = methods
+            T = self.mTIClusterNum
+            out = np.empty((max(T, 0), seg * self.mSubsLen), np.float32)
+            iters, nan_rows = C.c_int(0), C.c_int(0)
+            _lib.check(_lib.load().vaqhip_index_cluster_ti_kmeans(self._h, T, seg, 50, _ptr(out), C.byref(iters),
+                                                                  C.byref(nan_rows)))
+            self.mTIClusters = out
+            self.kmeansIterations, self.kmeansNanRows = iters.value, nan_rows.value
+            self._ti_sig = (_wref(out), seg)  # the index holds these centres already
+        elif self.mTIClusters is None:
             if self.mCodebook is None or hasattr(self.mCodebook, "data_ptr"):
                 raise _lib.VaqHipError(-7, "clusterTI needs a host mCodebook (or set mTIClusters)")
             T = self.mTIClusterNum
             N = self.mCodebook.shape[0]
             rng = np.random.default_rng(seed)
-            if not useKMeans:
-                self.mTIClusters = self.decodeFirstSegments(rng.integers(0, N, size=T), seg)
-            else:
-                import torch
-                from . import harness
-                n = min(N, 256 * T)
-                X = self.decodeFirstSegments(rng.permutation(N)[:n], seg)
-                dev = "cuda" if torch.cuda.is_available() else "cpu"
-                self.mTIClusters = harness.kmeans(torch.from_numpy(X).to(dev), T, iters=50,
-                                                  seed=seed).cpu().numpy()
+            self.mTIClusters = self.decodeFirstSegments(rng.integers(0, N, size=T), seg)
         self.mMethods |= NNMethod.TI
 
     def _ensure_ti(self):
