@@ -10,7 +10,8 @@
 //               --method VAQ64m8min8max8var1,HEAP --k 100 \
 //               [--groundtruth gt.ivecs] [--result out.csv] [--bits 8,8,...]
 //               [--visit-cluster 0.25]     (demo_vaq.cpp:43,57; with a ...,EA_TI<T>m<seg> method)
-//               [--ti-clusters c.f32]      (raw T x seg*L float32; default: random decoded rows)
+//               [--ti-clusters c.f32]      (raw T x seg*L float32; default: clusterTI(true), the reference's k-means
+//                                           on the GPU -- over the shards with --devices)
 //               [--refine 100,200 --dataset base.fvecs [--dataset-size N]]   (or --dataset-refine)
 //                                          (demo_vaq.cpp:40, :312-345 and scripts/run_demos.sh:9,22: per value R,
 //                                           search R >= k candidates, then VAQ::refine re-ranks them against the
@@ -58,20 +59,6 @@ int main(int argc, char **argv) {
       detail::File f(a["eigen"], "rb");
       f.read(vaq.mEigenVectors.data(), sizeof(float), (size_t)D * D);
     }
-    if (vaq.searchMethod() & VaqHip::NNMethod::TI) {  // demo_vaq.cpp:57, :263-267
-      if (a.count("visit-cluster")) vaq.mVisit = (float)std::atof(a["visit-cluster"].c_str());
-      if (vaq.mTISegmentNum == -1) vaq.mTISegmentNum = M;
-      if (a.count("ti-clusters")) {
-        vaq.mTIClusters = RowMatrixF((size_t)vaq.mTIClusterNum, (size_t)vaq.mTISegmentNum * vaq.mSubsLen());
-        detail::File f(a["ti-clusters"], "rb");
-        f.read(vaq.mTIClusters.data(), sizeof(float), vaq.mTIClusters.rows() * vaq.mTIClusters.cols());
-      }
-      vaq.clusterTI(false, true);
-    }
-    RowMatrixF queries = readFVecs(a["queries"], N, std::atoi(a["queries-size"].c_str()), D - N);
-    const int k = std::atoi(a["k"].c_str());
-    std::cout << "index: " << vaq.mCodebook.rows() << " rows x " << M << " subspaces, D=" << D
-              << ", queries " << queries.rows() << ", k=" << k << std::endl;
     if (a.count("devices")) {
       std::vector<int> devs;
       std::stringstream ss(a["devices"]);
@@ -80,6 +67,21 @@ int main(int argc, char **argv) {
       vaq.setDevices(devs);
       std::cout << "sharding the rows over " << devs.size() << " device entr" << (devs.size() == 1 ? "y" : "ies") << std::endl;
     }
+    if (vaq.searchMethod() & VaqHip::NNMethod::TI) {  // demo_vaq.cpp:57, :263-267
+      if (a.count("visit-cluster")) vaq.mVisit = (float)std::atof(a["visit-cluster"].c_str());
+      if (vaq.mTISegmentNum == -1) vaq.mTISegmentNum = M;
+      if (a.count("ti-clusters")) {
+        vaq.mTIClusters = RowMatrixF((size_t)vaq.mTIClusterNum, (size_t)vaq.mTISegmentNum * vaq.mSubsLen());
+        detail::File f(a["ti-clusters"], "rb");
+        f.read(vaq.mTIClusters.data(), sizeof(float), vaq.mTIClusters.rows() * vaq.mTIClusters.cols());
+      }
+      // without --ti-clusters: the reference's own k-means (demo_vaq.cpp:265), on one device or over the shards
+      vaq.clusterTI(!a.count("ti-clusters"), true);
+    }
+    RowMatrixF queries = readFVecs(a["queries"], N, std::atoi(a["queries-size"].c_str()), D - N);
+    const int k = std::atoi(a["k"].c_str());
+    std::cout << "index: " << vaq.mCodebook.rows() << " rows x " << M << " subspaces, D=" << D
+              << ", queries " << queries.rows() << ", k=" << k << std::endl;
     // --refine R1,R2,... (demo_vaq.cpp:312-323); without it one plain search (refine = 0)
     std::vector<int> refines;
     if (a.count("refine")) {

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 107
+#define VAQHIP_VERSION 108
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -162,7 +162,7 @@ int vaqhip_index_set_ti_clusters(vaqhip_index *ix, const float *clusters_rowmajo
 int vaqhip_index_cluster_ti_kmeans(vaqhip_index *ix, int T, int seg_num, int max_iter, float *clusters_out,
                                    int *iters_out, int *nan_rows_out);
 typedef struct {
-  float total_ms;                             /* host time of the k-means: unpack, sample, decode, iterations */
+  float total_ms;                             /* host time of the k-means: sample, gather, decode, iterations */
   float assign_ms, accumulate_ms, update_ms;  /* per phase over all iterations; only with option "timing" = 1
                                                  (each phase then ends with a stream synchronisation), else 0 */
   int iterations, rows, dims, clusters;       /* rows = the sample's */
@@ -378,6 +378,22 @@ int vaqhip_multi_search_device(vaqhip_multi *mx, const float *d_queries, int nq,
 /* forwarded to every shard (each shard regroups its own rows under the same TI centres) */
 int vaqhip_multi_set_ti_clusters(vaqhip_multi *mx, const float *clusters_rowmajor, int T, int seg_num);
 int vaqhip_multi_set_method(vaqhip_multi *mx, unsigned methods, float visit);
+/* vaqhip_index_cluster_ti_kmeans over ALL rows of the multi index, in global row order: the same sample
+ * (randomPermutation(N)[0 .. 256 * T) when N > 256 * T, else every row; id_base plays no part), the same seeds, and
+ * therefore the same centres, iteration count and NaN-centre count as a single index over the same rows, bit for
+ * bit, for any number of shards -- shards grown by add_codes and empty shards included.  Every shard reads its
+ * part of the sample from its packed rows on its own device; the assign step of every iteration is cut over the
+ * shards' devices (contiguous slices of ceil(rows / G) sample rows; keys, values and centres travel by peer copy),
+ * the sums and the update run on the first device, which alone decides the summation order.  Then what
+ * vaqhip_multi_set_ti_clusters does with the centres.  Refusals are the single index's (VAQHIP_EINVAL: T < 1,
+ * max_iter < 1, seg_num outside 1..M, T > N, a sequential-sum index; VAQHIP_ESTATE: no codes yet;
+ * VAQHIP_EUNSUPPORTED: T > 4096, centres of more than 1024 dims); a call that fails or is refused leaves every
+ * shard's grouping and method as they were.  The out-pointers may be NULL.  Synchronises. */
+int vaqhip_multi_cluster_ti_kmeans(vaqhip_multi *mx, int T, int seg_num, int max_iter, float *clusters_out,
+                                   int *iters_out, int *nan_rows_out);
+/* figures of the last vaqhip_multi_cluster_ti_kmeans: total_ms covers the gather on the shards, the fit and the
+ * copies; with option "timing" = 1 assign_ms is the wall time of the assign step over all shards, copies included */
+int vaqhip_multi_last_kmeans_timing(vaqhip_multi *mx, vaqhip_kmeans_timing *out);
 int vaqhip_multi_set_option(vaqhip_multi *mx, const char *key, int64_t value);
 /* Method FAST on a multi index: labels and distances are the single index's over all rows, slot for slot.
  * Every shard sends the distances of the head rows it holds (the first min(k, N) rows of the database, which

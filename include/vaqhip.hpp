@@ -242,7 +242,7 @@ public:
   // useKMeans = true is the reference's k-means over decoded code rows (:897-900,
   // KMeans::staticFitCodebook with max_iter = 50) on the GPU, centre for centre what the reference
   // computes (vaqhip_index_cluster_ti_kmeans); it pushes mCodebook first and groups at once.
-  // Single-device only: with setDevices() fill mTIClusters yourself.
+  // With setDevices() the same centres come from the shards (vaqhip_multi_cluster_ti_kmeans).
   int mKMeansIterations = 0, mKMeansNanRows = 0;  // how the last k-means ended (not in the reference)
   void clusterTI(bool useKMeans = false, bool verbose = false) {
     (void)verbose;
@@ -250,17 +250,18 @@ public:
       throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: TI<T>var<v> needs train()'s variance profile; use TI<T>m<seg>");
     if (mTISegmentNum == -1) mTISegmentNum = mHighestSubs();
     if (mTIClusters.rows() == 0 && useKMeans) {
-      if (!mDevices.empty())
-        throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: the k-means of clusterTI runs on a single-device index");
       const uint32_t methods = mMethods;
       mMethods = (methods & ~(uint32_t)NNMethod::TI) ? (methods & ~(uint32_t)NNMethod::TI) : (uint32_t)NNMethod::Heap;
       try { sync(); } catch (...) { mMethods = methods; throw; }  // the codes, in the exhaustive order
       mMethods = methods;
       mTIClusters = RowMatrixF((size_t)(mTIClusterNum > 0 ? mTIClusterNum : 0), (size_t)mTISegmentNum * mSubsLen());
-      const int rc = vaqhip_index_cluster_ti_kmeans(h_, mTIClusterNum, mTISegmentNum, 50, mTIClusters.data(),
-                                                    &mKMeansIterations, &mKMeansNanRows);
+      const int rc = mh_ ? vaqhip_multi_cluster_ti_kmeans(mh_, mTIClusterNum, mTISegmentNum, 50, mTIClusters.data(),
+                                                          &mKMeansIterations, &mKMeansNanRows)
+                         : vaqhip_index_cluster_ti_kmeans(h_, mTIClusterNum, mTISegmentNum, 50, mTIClusters.data(),
+                                                          &mKMeansIterations, &mKMeansNanRows);
       if (rc) mTIClusters = RowMatrixF();
-      check(rc);
+      if (mh_) checkMulti(rc);
+      else check(rc);
       mMethods |= NNMethod::TI;
       ti_set_ = true;  // the index holds these centres already
       return;

@@ -5,7 +5,9 @@ call, the iterations it ran, and -- from a second call with option "timing" = 1,
 stream synchronisation -- the time per iteration split into assign / accumulate (sort + ordered sums) / update.
 Codes are uniform random and the codebooks gaussian with a decaying scale, from a fixed seed.
 
-    python tools/bench_kmeans.py [--rows 1000000 --clusters 1000 --segs 2 4 --max-iter 50]
+    python tools/bench_kmeans.py [--rows 1000000 --clusters 1000 --segs 2 4 --max-iter 50 --runs 1]
+    python tools/bench_kmeans.py --devices 0,0,0,0   # the multi-device call (vaqhip_multi_cluster_ti_kmeans) on the
+        # same inputs, the rows sharded over these devices (a device named twice: logical shards on it)
     python tools/bench_kmeans.py --dump-inputs DIR   # also writes the inputs of every seg (int32 N, seg, L,
         # centroids, T, max_iter; codes N x seg uint16; seg codebooks) to time another implementation on them
 """
@@ -33,16 +35,23 @@ def make_inputs(rows):
 
 
 def run(v, T, seg, max_iter, timing):
+    """One call on a VaqHip or a VaqHipMulti: (wall ms, iterations, NaN centres, the library's timing)."""
     from vaq_amd import _lib
     L = _lib.load()
+    multi = not hasattr(v, "mCodebook")
     v.set_option("timing", 1 if timing else 0)
     iters = C.c_int(0)
     nan_rows = C.c_int(0)
-    t0 = time.perf_counter()
-    _lib.check(L.vaqhip_index_cluster_ti_kmeans(v._h, T, seg, max_iter, None, C.byref(iters), C.byref(nan_rows)))
-    wall = (time.perf_counter() - t0) * 1e3
     t = _lib.KmeansTiming()
-    _lib.check(L.vaqhip_last_kmeans_timing(v._h, C.byref(t)))
+    t0 = time.perf_counter()
+    if multi:
+        _lib.check_multi(L.vaqhip_multi_cluster_ti_kmeans(v._h, T, seg, max_iter, None, C.byref(iters), C.byref(nan_rows)))
+        wall = (time.perf_counter() - t0) * 1e3
+        _lib.check_multi(L.vaqhip_multi_last_kmeans_timing(v._h, C.byref(t)))
+    else:
+        _lib.check(L.vaqhip_index_cluster_ti_kmeans(v._h, T, seg, max_iter, None, C.byref(iters), C.byref(nan_rows)))
+        wall = (time.perf_counter() - t0) * 1e3
+        _lib.check(L.vaqhip_last_kmeans_timing(v._h, C.byref(t)))
     return wall, iters.value, nan_rows.value, t
 
 
@@ -53,6 +62,8 @@ def main():
     ap.add_argument("--segs", type=int, nargs="+", default=[2, 4])
     ap.add_argument("--max-iter", type=int, default=50)
     ap.add_argument("--dump-inputs", default=None)
+    ap.add_argument("--devices", default=None, help="comma-separated device list: time the multi-device call")
+    ap.add_argument("--runs", type=int, default=1, help="untimed-phase calls per seg; every total is reported")
     args = ap.parse_args()
     import vaq_amd
 
@@ -66,21 +77,32 @@ def main():
                 f.write(np.ascontiguousarray(codes[:, :seg]).tobytes())
                 for s in range(seg):
                     f.write(cents[s].tobytes())
-    v = vaq_amd.VaqHip(device=0)
-    v.mBitsAlloc = [BITS] * M
-    v.mCentroidsPerSubs = cents
-    v.mCodebook = codes
-    v._ensure_codes()
+    if args.devices:
+        devices = [int(d) for d in args.devices.split(",")]
+        v = vaq_amd.VaqHipMulti(devices, [BITS] * M, cents)
+        v.set_codes(codes)
+    else:
+        v = vaq_amd.VaqHip(device=0)
+        v.mBitsAlloc = [BITS] * M
+        v.mCentroidsPerSubs = cents
+        v.mCodebook = codes
+        v._ensure_codes()
     out = {"workload": f"k-means of clusterTI: T={T}, {args.rows} rows x {M} x {BITS}-bit, D={D}, max_iter={args.max_iter}"}
+    if args.devices:
+        out["devices"] = devices
     run(v, min(T, 16), args.segs[0], 2, False)  # warm-up: module load, allocations
     for seg in args.segs:
-        wall, iters, nan_rows, t = run(v, T, seg, args.max_iter, False)
+        totals = []
+        for _ in range(max(args.runs, 1)):
+            wall, iters, nan_rows, t = run(v, T, seg, args.max_iter, False)
+            totals.append(round(t.total_ms, 2))
         _, iters2, _, tp = run(v, T, seg, args.max_iter, True)
         assert iters2 == iters
         out[f"seg{seg}"] = {
             "dims": t.dims, "sampled_rows": t.rows, "iterations": iters, "nan_centres": nan_rows,
             "call_ms": round(wall, 2),                       # the whole call: k-means + regrouping the rows
-            "kmeans_ms": round(t.total_ms, 2),               # unpack, sample, decode, iterations
+            "kmeans_ms": round(t.total_ms, 2),               # sample, gather, decode, iterations (the last run's)
+            "kmeans_ms_runs": totals,
             "assign_ms_per_iter": round(tp.assign_ms / iters, 4),
             "accumulate_ms_per_iter": round(tp.accumulate_ms / iters, 4),
             "update_ms_per_iter": round(tp.update_ms / iters, 4),

@@ -28,6 +28,7 @@ SYMBOLS = [
     "vaqhip_multi_create", "vaqhip_multi_destroy", "vaqhip_multi_set_codes_u16", "vaqhip_multi_add_codes_u16",
     "vaqhip_multi_search", "vaqhip_multi_search_device", "vaqhip_multi_set_ti_clusters", "vaqhip_multi_set_method", "vaqhip_multi_set_option",
     "vaqhip_multi_set_lut_quantization", "vaqhip_multi_learn_quantization",
+    "vaqhip_multi_cluster_ti_kmeans", "vaqhip_multi_last_kmeans_timing",
     "vaqhip_multi_get_info", "vaqhip_multi_shard", "vaqhip_multi_last_error",
 ]
 MAX_DEVICES = 16
@@ -151,6 +152,8 @@ def load():
     L.vaqhip_multi_set_option.argtypes = [vp, C.c_char_p, i64]
     L.vaqhip_multi_set_lut_quantization.argtypes = [vp, vp, vp]
     L.vaqhip_multi_learn_quantization.argtypes = [vp, vp, i64, i32, C.c_float, vp, vp]
+    L.vaqhip_multi_cluster_ti_kmeans.argtypes = [vp, i32, i32, i32, vp, C.POINTER(i32), C.POINTER(i32)]
+    L.vaqhip_multi_last_kmeans_timing.argtypes = [vp, C.POINTER(KmeansTiming)]
     L.vaqhip_multi_get_info.argtypes = [vp, C.POINTER(MultiInfo)]
     L.vaqhip_multi_shard.argtypes = [vp, i32]
     L.vaqhip_multi_shard.restype = vp

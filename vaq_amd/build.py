@@ -26,6 +26,7 @@ INTERNAL_HEADER = os.path.join(CSRC, "vaqhip_internal.h")
 INDEX_HEADER = os.path.join(CSRC, "vaqhip_index.h")  # private to the single-index host files
 DEV_HEADER = os.path.join(CSRC, "vaqhip_dev.h")      # DevBuf, DeviceGuard: both hosts and the scratch allocators
 JOB_POOL_HEADER = os.path.join(CSRC, "job_pool.h")
+KMEANS_SAMPLE_HEADER = os.path.join(CSRC, "kmeans_sample.h")  # the k-means' sample and its split: both hosts
 
 
 def _deps(src: str):
@@ -36,6 +37,8 @@ def _deps(src: str):
         deps.append(JOB_POOL_HEADER if src == "vaqhip_multi.cpp" else INDEX_HEADER)
     if src in ("vaq_kernels.hip", "vaq_ti.hip", "vaq_kmeans.hip"):
         deps.append(DEV_HEADER)
+    if src in ("vaq_kmeans.hip", "vaqhip_codes.cpp", "vaqhip_multi.cpp"):
+        deps.append(KMEANS_SAMPLE_HEADER)
     if src in ("vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip"):
         deps.append(SCAN_HEADER)
     if src in ("vaq_kernels.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip"):

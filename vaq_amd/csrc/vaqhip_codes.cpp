@@ -2,10 +2,10 @@
 // packing, append, TI clustering (the regrouping, and the k-means that makes the centres).
 #include "vaqhip_index.h"
 
+#include "kmeans_sample.h"
+
 #include <chrono>
 #include <cmath>
-#include <random>
-#include <unordered_map>
 
 using namespace vaqhost;
 
@@ -282,32 +282,23 @@ int set_ti_clusters_locked(vaqhip_index *ix, const float *clusters, int T, int s
   return ws.finish();
 }
 
-// The first r entries of randomPermutation(n) (utils/Random.hpp:18-28, mt19937(13517106), i2 = i + mt() % (n - i)):
-// entry i is final after step i, so r steps over a sparse map of the positions touched so far suffice.
-std::vector<int> permutation_head(int64_t n, int64_t r) {
-  r = std::min(r, n);
-  std::vector<int> out((size_t)r);
-  std::unordered_map<int, int> moved;
-  std::mt19937 mt(13517106u);
-  auto at = [&](int i) {
-    auto it = moved.find(i);
-    return it == moved.end() ? i : it->second;
-  };
-  for (int64_t i = 0; i < r; i++) {
-    if (i + 1 < n) {
-      const int i2 = (int)i + (int)(mt() % (unsigned)(int)(n - i));
-      const int vi = at((int)i);
-      out[i] = at(i2);
-      moved[i2] = vi;
-    } else {
-      out[i] = at((int)i);
-    }
-  }
-  return out;
+// what vaqhip_index_cluster_ti_kmeans refuses beyond its plain arguments (T >= 1); under the index's lock
+int check_kmeans_state(const vaqhip_index *ix, int T, int seg_num) {
+  if (int rc = check_ti_shape(ix, T, seg_num)) return rc;
+  if (ix->N < 0) return fail(VAQHIP_ESTATE, "the k-means of clusterTI runs over the codes: set them first");
+  if (ix->staged.open)
+    return fail(VAQHIP_ESTATE, "a staged search is open on this index: call vaqhip_search_finish_device first");
+  return VAQHIP_OK;
 }
 
-// KMeans::staticFitCodebook's sample: more than 256 rows per centre are cut to the first 256 * T of a permutation
-constexpr int64_t KMEANS_ROWS_PER_CENTRE = 256;
+// the first seg_num codes of the sampled rows (vaq::kmeans_gather_packed), read from the packed rows as they lie
+int gather_sample(vaqhip_index *ix, const int *sample_rows, int n_sample, int seg_num, uint16_t *d_scodes,
+                  hipStream_t st) {
+  HIP_TRY(vaq::kmeans_gather_packed(ix->d_codes.as<uint32_t>(), ix->N, ix->M, ix->layout, ix->W,
+                                    ix->d_sub.as<vaq::SubDesc>(), ix->d_perm.as<uint32_t>(), sample_rows, n_sample,
+                                    seg_num, d_scodes, st));
+  return VAQHIP_OK;
+}
 } // namespace
 
 extern "C" {
@@ -345,41 +336,32 @@ int vaqhip_index_cluster_ti_kmeans(vaqhip_index *ix, int T, int seg_num, int max
                                    int *iters_out, int *nan_rows_out) {
   if (!ix) return fail(VAQHIP_EINVAL, "index is null");
   if (T < 1 || max_iter < 1) return fail(VAQHIP_EINVAL, "T=%d max_iter=%d", T, max_iter);
-  if (int rc = check_ti_shape(ix, T, seg_num)) return rc;
   ENTRY(ix);
-  if (ix->N < 0) return fail(VAQHIP_ESTATE, "the k-means of clusterTI runs over the codes: set them first");
-  if (ix->staged.open)
-    return fail(VAQHIP_ESTATE, "a staged search is open on this index: call vaqhip_search_finish_device first");
+  if (int rc = check_kmeans_state(ix, T, seg_num)) return rc;
   if (T > ix->N)  // (the sample is min(N, 256 * T) rows: never fewer than T unless N is)
     return fail(VAQHIP_EINVAL, "T=%d centres from %lld rows (the reference reads out of bounds)", T, (long long)ix->N);
   const int64_t N = ix->N;
-  const int rows = (int)std::min<int64_t>(N, KMEANS_ROWS_PER_CENTRE * T), dd = seg_num * ix->L;
+  const int rows = vaq::kmeans_sample_rows(N, T), dd = seg_num * ix->L;
   std::vector<float> means((size_t)T * dd);
   int iters = 0, no_centre = 0;
   {
     hipStream_t st = ix->stream;
     WS_SCOPE(ws, ix, st);  // (a search enqueued on another stream may still be using the index)
     const auto t0 = std::chrono::steady_clock::now();
-    // the codes in original row order, then the sample's first seg_num codes as [rows][seg_num]
-    DevBuf all, ids, scodes, d_means;
-    HIP_TRY(all.ensure((size_t)N * ix->M * sizeof(uint16_t)));
-    HIP_TRY(vaq::launch_unpack_codes(ix->d_codes.as<uint32_t>(), N, ix->M, ix->layout, ix->W,
-                                     ix->d_sub.as<vaq::SubDesc>(), ix->d_perm.as<uint32_t>(), all.as<uint16_t>(), st));
+    // the sample's first seg_num codes as [rows][seg_num], from the packed rows
+    DevBuf scodes, d_means;
     std::vector<int> sample;
-    if (N > rows) {
-      sample = permutation_head(N, rows);
-      HIP_TRY(ids.ensure((size_t)rows * sizeof(int)));
-      HIP_TRY(hipMemcpyAsync(ids.p, sample.data(), (size_t)rows * sizeof(int), hipMemcpyHostToDevice, st));
-    }
+    if (N > rows) sample = vaq::permutation_head(N, rows);
     HIP_TRY(scodes.ensure((size_t)rows * seg_num * sizeof(uint16_t)));
-    HIP_TRY(vaq::launch_kmeans_gather(all.as<uint16_t>(), ix->M, N > rows ? ids.as<int>() : nullptr, rows, seg_num,
-                                      scodes.as<uint16_t>(), st));
-    const std::vector<int> seeds = permutation_head(rows, T);
+    if (int rc = gather_sample(ix, N > rows ? sample.data() : nullptr, rows, seg_num, scodes.as<uint16_t>(), st))
+      return rc;
+    const std::vector<int> seeds = vaq::permutation_head(rows, T);
     HIP_TRY(d_means.ensure(means.size() * sizeof(float)));
     vaq::KmeansPhases ph;
-    HIP_TRY(vaq::kmeans_fit(scodes.as<uint16_t>(), rows, seg_num, ix->L, ix->d_sub.as<vaq::SubDesc>(),
-                            ix->d_cent.as<float>(), seeds.data(), T, max_iter, d_means.as<float>(), &iters, &no_centre,
-                            ix->opt_timing ? &ph : nullptr, st));  // synchronises
+    const vaq::KmeansDev dev = {ix->device, st, ix->d_sub.as<vaq::SubDesc>(), ix->d_cent.as<float>()};
+    HIP_TRY(vaq::kmeans_fit(&dev, 1, scodes.as<uint16_t>(), rows, seg_num, ix->L, seeds.data(), T, max_iter,
+                            d_means.as<float>(), &iters, &no_centre, ix->opt_timing ? &ph : nullptr,
+                            nullptr));  // synchronises
     HIP_TRY(hipMemcpy(means.data(), d_means.p, means.size() * sizeof(float), hipMemcpyDeviceToHost));
     ix->km_last = vaqhip_kmeans_timing{};
     ix->km_last.total_ms = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -404,6 +386,42 @@ int vaqhip_index_cluster_ti_kmeans(vaqhip_index *ix, int T, int seg_num, int max
   if (iters_out) *iters_out = iters;
   if (nan_rows_out) *nan_rows_out = nan_rows;
   return set_ti_clusters_locked(ix, means.data(), T, seg_num);
+}
+
+int vaqhip_internal_kmeans_check(vaqhip_index *ix, int T, int seg_num) {
+  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
+  std::lock_guard<std::mutex> lk(ix->mu);
+  return check_kmeans_state(ix, T, seg_num);
+}
+
+int vaqhip_internal_kmeans_gather(vaqhip_index *ix, const int *sample_rows, int n_sample, int seg_num,
+                                  uint16_t *scodes_out) {
+  if (!ix || !scodes_out || n_sample < 0) return fail(VAQHIP_EINVAL, "null pointer");
+  ENTRY(ix);
+  if (int rc = check_kmeans_state(ix, 1, seg_num)) return rc;
+  if (sample_rows ? n_sample > ix->N : n_sample != ix->N)
+    return fail(VAQHIP_EINVAL, "%d sampled rows of %lld", n_sample, (long long)ix->N);
+  for (int i = 0; sample_rows && i < n_sample; i++)
+    if (sample_rows[i] < 0 || sample_rows[i] >= ix->N)
+      return fail(VAQHIP_EINVAL, "sampled row %d outside the index's %lld rows", sample_rows[i], (long long)ix->N);
+  if (n_sample == 0) return VAQHIP_OK;
+  hipStream_t st = ix->stream;
+  WS_SCOPE(ws, ix, st);  // (a search enqueued on another stream may still be using the index)
+  DevBuf scodes;
+  const size_t bytes = (size_t)n_sample * seg_num * sizeof(uint16_t);
+  HIP_TRY(scodes.ensure(bytes));
+  if (int rc = gather_sample(ix, sample_rows, n_sample, seg_num, scodes.as<uint16_t>(), st)) return rc;
+  HIP_TRY(hipMemcpyAsync(scodes_out, scodes.p, bytes, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return ws.finish();
+}
+
+int vaqhip_internal_kmeans_tables(vaqhip_index *ix, const void **d_sub, const float **d_cent, int *L) {
+  if (!ix || !d_sub || !d_cent || !L) return fail(VAQHIP_EINVAL, "null pointer");
+  *d_sub = ix->d_sub.p;
+  *d_cent = ix->d_cent.as<float>();
+  *L = ix->L;
+  return VAQHIP_OK;
 }
 
 int vaqhip_last_kmeans_timing(vaqhip_index *ix, vaqhip_kmeans_timing *out) {

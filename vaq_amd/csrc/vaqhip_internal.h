@@ -1,6 +1,6 @@
 // vaqhip_internal.h -- entries of the single-device index that only the multi-device host
 // (vaqhip_multi.cpp) calls: the pieces of option "exact_ties" as a chain over shards (vaq_exact.hip), and
-// one shard's part of a FAST search (vaq_fast.hip).
+// one shard's part of a FAST search (vaq_fast.hip), and one shard's part of the k-means of clusterTI (vaq_kmeans.hip).
 // Not part of the public interface (include/vaqhip.h).
 #ifndef VAQHIP_INTERNAL_H
 #define VAQHIP_INTERNAL_H
@@ -50,6 +50,19 @@ int vaqhip_internal_search_fast_shard_device(vaqhip_index *ix, const float *d_qu
  * [start[g], start[g + 1]) and holds them at d_planes[g * plane_stride + q * kk + p]; start[n_parts] = kk */
 int vaqhip_internal_fast_head_gather_device(int device, const uint16_t *d_planes, int64_t plane_stride, int n_parts,
                                             const int *start, int nq, int kk, uint16_t *d_head, void *stream);
+
+
+/* The k-means of clusterTI over the shards of a multi index (vaq_kmeans.hip).
+ * What vaqhip_index_cluster_ti_kmeans refuses for reasons the index alone knows (T >= 1 assumed): the limits of
+ * set_ti_clusters, no codes yet, a staged search open. */
+int vaqhip_internal_kmeans_check(vaqhip_index *ix, int T, int seg_num);
+/* scodes_out (host) [n_sample][seg_num] = the first seg_num codes of this index's rows sample_rows[0 .. n_sample)
+ * (local rows, all different), read from the packed rows in place; sample_rows NULL (n_sample = the index's rows):
+ * every row in original order.  Synchronises. */
+int vaqhip_internal_kmeans_gather(vaqhip_index *ix, const int *sample_rows, int n_sample, int seg_num,
+                                  uint16_t *scodes_out);
+/* the index's subspace table (vaq::SubDesc [M]) and centroids on its device, and D / M */
+int vaqhip_internal_kmeans_tables(vaqhip_index *ix, const void **d_sub, const float **d_cent, int *L);
 
 #ifdef __cplusplus
 }

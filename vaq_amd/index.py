@@ -482,6 +482,12 @@ class VaqHip:
         _lib.check(_lib.load().vaqhip_last_timing(self._h, C.byref(t)))
         return {f: getattr(t, f) for f, _ in _lib.Timing._fields_}
 
+    def last_kmeans_timing(self) -> dict:
+        """Figures of the last clusterTI(True) on this index (vaqhip_last_kmeans_timing)."""
+        t = _lib.KmeansTiming()
+        _lib.check(_lib.load().vaqhip_last_kmeans_timing(self._h, C.byref(t)))
+        return {f: getattr(t, f) for f, _ in _lib.KmeansTiming._fields_}
+
     def close(self) -> None:
         if self._h:
             _lib.load().vaqhip_index_destroy(self._h)
@@ -636,6 +642,21 @@ class VaqHipMulti:
             return
         cl = np.ascontiguousarray(clusters, dtype=np.float32)
         _lib.check_multi(_lib.load().vaqhip_multi_set_ti_clusters(self._h, _ptr(cl), cl.shape[0], seg))
+
+    def cluster_ti_kmeans(self, T: int, seg: int, max_iter: int = 50):
+        """vaqhip_multi_cluster_ti_kmeans: the k-means of VAQ::clusterTI(true) over all rows of the shards -- the
+        centres a single VaqHip computes over the same rows, bit for bit, whatever the number of shards -- then
+        set_ti_clusters with them.  Returns (centres [T, seg * L], iterations, nan_rows)."""
+        out = np.empty((max(T, 0), max(seg, 0) * (self.D // self.M)), np.float32)
+        iters, nan_rows = C.c_int(0), C.c_int(0)
+        _lib.check_multi(_lib.load().vaqhip_multi_cluster_ti_kmeans(self._h, T, seg, max_iter, _ptr(out),
+                                                                    C.byref(iters), C.byref(nan_rows)))
+        return out, iters.value, nan_rows.value
+
+    def last_kmeans_timing(self) -> dict:
+        t = _lib.KmeansTiming()
+        _lib.check_multi(_lib.load().vaqhip_multi_last_kmeans_timing(self._h, C.byref(t)))
+        return {f: getattr(t, f) for f, _ in _lib.KmeansTiming._fields_}
 
     def search(self, XTest: np.ndarray, k: int, projected: bool = False) -> LabelDistVec:
         X = np.ascontiguousarray(XTest, dtype=np.float32)
