@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 108
+#define VAQHIP_VERSION 109
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -93,7 +93,8 @@ int vaqhip_index_create(vaqhip_index **out, int D, int M, const int *bits,
  * engine's centroidsMat (1 << bits[s] values).  Queries are projected WITH CHECKING, as queryLUT
  * does (:1226 -> :53-71): a PCA coordinate that comes out NaN or infinite becomes 0 (one non-finite
  * component makes every coordinate of z * V non-finite, so such a query is answered as the zero
- * vector); VAQ::search's projection (VAQ.hpp:198-201) does not check and is left as it is. */
+ * vector); VAQ::search's projection (VAQ.hpp:198-201) does not check and is left as it is.
+ * Option "exact_ties" reproduces queryLUT's own order among equal distances (below). */
 #define VAQHIP_SUM_SEQUENTIAL 0x1u
 int vaqhip_index_create_ex(vaqhip_index **out, int D, int M, const int *bits,
                            const float *const *centroids_rowmajor,
@@ -348,8 +349,11 @@ int vaqhip_merge_fast_device(int device_id, const uint16_t *d_head_dist, int64_t
  *                served in sets of that size.  last_merge_ms then includes the second pass.
  *                No effect -- the result is then what each shard's own option gives, merged by
  *                (distance, label), as on a single index where the option has no effect either --
- *                with TI, with VAQHIP_SUM_SEQUENTIAL, with FAST (whose sharded answer is the single index's
- *                slot for slot already) and for k == VAQHIP_MAX_K.  One shard: that shard's own replay.
+ *                with TI, with FAST (whose sharded answer is the single index's slot for slot already)
+ *                and for k == VAQHIP_MAX_K.  One shard: that shard's own replay.
+ *                On VAQHIP_SUM_SEQUENTIAL shards the answer is BitVecEngine::queryLUT's over all rows: the
+ *                state handed on is its raw std heap (k + 1 pairs), the heap's length and bsfK
+ *                ((k + 2) * 8 bytes), and `dataIndex >= k` counts from the shard's first global row.
  *   "exact_batch" list entries per batch of that second pass; 0 (default) = max(64, a 16th of the
  *                set's queries); never fewer than a 256th of them.  Results do not depend on it.
  * ------------------------------------------------------------------------- */
@@ -508,6 +512,20 @@ int vaqhip_index_info(const vaqhip_index *ix, vaqhip_info *out);
  *                       (the replay runs as a chain from shard to shard, see "multi-device" above); the
  *                       staged search of one-process-per-GPU sharding (vaqhip_search_begin_device)
  *                       stays VAQHIP_EUNSUPPORTED with the option set.
+ *                       On a VAQHIP_SUM_SEQUENTIAL index the choice reproduced is BitVecEngine::queryLUT's
+ *                       (BitVecEngine.hpp:1282-1317), which keeps its k best in a std::vector under
+ *                       libstdc++'s std::push_heap / std::pop_heap / std::sort_heap with the comparator
+ *                       a.dist < b.dist: rows in original order, bsfK = FLT_MAX; a row with
+ *                       dist < bsfK (strict; :1301) is appended and pushed (:1302-1303); from row k on
+ *                       (the row's POSITION in the database, :1304) the maximum of the k + 1 pairs is
+ *                       popped and bsfK becomes the new front's distance (:1305-1307); std::sort_heap at
+ *                       the end (:1316).  So the first k rows enter unconditionally, and N <= k never
+ *                       pops.  Same pipeline and limits as above (vaqhip_search, _projected, _device;
+ *                       k < 1024 -- no effect at k == VAQHIP_MAX_K; the staged search stays
+ *                       VAQHIP_EUNSUPPORTED); labels are id_base + row, unfilled slots -1 / FLT_MAX.
+ *                       Assumes finite lookup tables (the reference reads front() of an empty vector
+ *                       when a row sum is not finite); queryLUT's checked projection makes every query
+ *                       finite, so finite centroids suffice.
  *   "bucket_major"      1 (default): on a streamed database (> 128 MB of byte codes) with at least 8
  *                       queries in the call, the best-first pass is cut after each query's nearest
  *                       buckets and what is left in reach is scanned bucket by bucket: a bucket's

@@ -500,6 +500,8 @@ public:
   std::vector<int> solutionX;       // bits per dimension
   RowMatrixF eigenVectors;          // real part, D x D, D = nonZeroAllocCount (empty = identity)
   int mDevice = 0;
+  // option "exact_ties" (vaqhip.h): queryLUT's own order among equal distances, from its std heap
+  bool exactTies = false;
 
   BitVecEngineHip() = default;
   BitVecEngineHip(const BitVecEngineHip &) = delete;
@@ -524,12 +526,13 @@ public:
                                    eigenVectors.rows() ? eigenVectors.data() : nullptr, mDevice,
                                    VAQHIP_SUM_SEQUENTIAL));
     }
+    check(vaqhip_set_option(h_, "exact_ties", exactTies ? 1 : 0));
     check(vaqhip_index_set_codes_u16(h_, codebook.data(), (int64_t)codebook.rows(), 0));
     const int nq = (int)queries.rows();
     std::vector<int> lab((size_t)nq * k);
     std::vector<float> dis((size_t)nq * k);
     check(vaqhip_search(h_, queries.data(), nq, k, lab.data(), dis.data()));
-    std::vector<std::vector<IdxDistPairFloat>> answers(nq);
+    std::vector<std::vector<IdxDistPairFloat>> answers(nq);  // min(k, rows) pairs each, as the reference's
     for (int q = 0; q < nq; q++)
       for (int i = 0; i < k && lab[(size_t)q * k + i] >= 0; i++)
         answers[q].push_back({lab[(size_t)q * k + i], dis[(size_t)q * k + i]});

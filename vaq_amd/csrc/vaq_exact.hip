@@ -29,6 +29,18 @@
 // never below the reference's at that row -- the inherited top IS the reference's top there.
 // The heap functions below are the reference's (utils/Heap.hpp), statement for statement, as restated
 // in oracle/vaq_oracle.c -- which is pinned against the compiled reference heap (tests/test_oracle_golden.py).
+//
+// Sequential-sum indexes (BitVecEngine::queryLUT, BitVecEngine.hpp:1282-1317) keep their k best under
+// libstdc++'s heap functions instead: with pairs empty and bsfK = FLT_MAX, row i (ORIGINAL order, dist the
+// sequential column sum) is taken iff dist < bsfK: emplace_back + std::push_heap, and for i >= k also
+// std::pop_heap + pop_back + bsfK = front().dist; std::sort_heap at the end.  The first k rows enter
+// unconditionally, row k meets a full heap (k + 1 slots are needed), i is the row's position in the WHOLE
+// database.  The same pipeline replays it (template argument SEQ): the heap is k + 1 pairs under
+// stdheap:: (vaq_fast.h, pinned against the real functions by tests/cpp/stdheap_test.cpp), the state of a
+// chain link is the raw heap, its length and bsfK, and the links count i from ExactParams::row0.  The
+// loop's partial-sum abandon only drops rows the test dist < bsfK drops (table entries are >= 0), so the
+// evaluating waves abandon and skip buckets against bsfK exactly as they do against the heap top.
+#include "vaq_fast.h"
 #include "vaq_scan.h"
 
 namespace vaq {
@@ -101,12 +113,17 @@ struct ExactParams {
   unsigned *count;
   int nq;
   // one link of a chain over shards (0: the single-index replay).  Entry e of the list keeps its heap at
-  // state[e * 2 * k]: k values, then k ids (global row numbers, -1 = neutral).
+  // state[e * 2 * k]: k values, then k ids (global row numbers, -1 = neutral).  Sequential sum: at
+  // state[e * ex_state_words(k, 1)]: k + 1 values, k + 1 ids, the heap's length, bsfK.
   int chain;
+  int64_t row0;              // sequential sum: position in the whole database of this index's row 0
   int e0;                    // the launch covers list entries e0 .. e0 + grid - 1
   const int32_t *state_in;   // nullptr: the neutral state (first shard)
   int32_t *state_out;
 };
+
+// int32 words of one list entry's state in a chain
+__host__ __device__ inline int ex_state_words(int k, int seq) { return seq ? 2 * (k + 1) + 2 : 2 * k; }
 
 // heap_reorder (utils/Heap.hpp:322-349) by ONE thread: pop the maxima into the tail -> ascending; entries
 // of id -1 are dropped.  Returns the number kept: they sit in [k - kept, k).  (The memmove of the kept
@@ -177,18 +194,38 @@ __device__ __forceinline__ float ex_row_dist(const ExactParams &p, const float *
   return dist;
 }
 
-template <bool BYTES>
+// the sequential sum of sorted row r (BitVecEngine.hpp:1295-1300: dist += luts[code], column by column),
+// abandoned (-> +inf) once a partial sum is no longer below t, as the loop's own condition does
+__device__ __forceinline__ float ex_row_dist_seq(const ExactParams &p, const float *lut, const int64_t r, const float t) {
+  const int W = p.W;
+  const uint32_t *tp = p.codes + (r / TILE_ROWS) * (int64_t)(TILE_ROWS * W) + (r % TILE_ROWS);
+  float dist = 0.0f;
+  for (int s = 0; s < p.M; s++) {
+    const SubDesc d = p.sub[s];
+    const uint32_t lo = tp[(int64_t)d.word * TILE_ROWS];
+    const uint32_t hi = d.word + 1 < W ? tp[(int64_t)(d.word + 1) * TILE_ROWS] : 0u;
+    const uint32_t c = __builtin_amdgcn_alignbit(hi, lo, (unsigned)d.shift) & ((1u << d.bits) - 1u);
+    const float l = lut[d.lut_off + c];
+    dist = s == 0 ? l : dist + l;
+    if (!(dist < t)) return INFINITY;
+  }
+  return dist;
+}
+
+template <bool BYTES, bool SEQ>
 __global__ __launch_bounds__(EX_THREADS) void exact_replay_kernel(ExactParams p) {
+  static_assert(!(BYTES && SEQ), "sequential-sum rows are always bit-packed");
   extern __shared__ __attribute__((aligned(16))) unsigned char ex_smem[];
   const int e = p.e0 + blockIdx.x;
   if ((unsigned)e >= *p.count) return;
   const int q = p.list[e];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int k = p.k;
+  const int hs = SEQ ? k + 1 : k;  // heap slots
   // LDS: heap values, heap ids, two chunk buffers, [the query's lookup tables]
   float *hval = reinterpret_cast<float *>(ex_smem);
-  int *hid = reinterpret_cast<int *>(hval + k);
-  float *buf = reinterpret_cast<float *>(hid + k);  // [2][EX_CHUNK]
+  int *hid = reinterpret_cast<int *>(hval + hs);
+  float *buf = reinterpret_cast<float *>(hid + hs);  // [2][EX_CHUNK]
   float *lbound = buf + 2 * EX_CHUNK;              // [n_buckets] lower bound of the row sums of each bucket (row_bucket)
   float *lds_lut = lbound + (p.row_bucket ? p.n_buckets : 0);
   const float *glut = p.lut + (size_t)q * p.lut_floats;
@@ -198,18 +235,24 @@ __global__ __launch_bounds__(EX_THREADS) void exact_replay_kernel(ExactParams p)
     lut = lds_lut;
   }
   // heap_heapify (utils/Heap.hpp:211-235): neutral FLT_MAX, ids -1 -- or the heap the earlier shards left
-  const int32_t *sin = p.chain && p.state_in ? p.state_in + (size_t)e * 2 * k : nullptr;
-  for (int i = tid; i < k; i += EX_THREADS) {
+  // (sequential sum: `pairs` empty and bsfK = FLT_MAX, BitVecEngine.hpp:1287-1290 -- or what the earlier
+  //  shards left; slots past the length are never read)
+  const int32_t *sin = p.chain && p.state_in ? p.state_in + (size_t)e * ex_state_words(k, SEQ) : nullptr;
+  for (int i = tid; i < hs; i += EX_THREADS) {
     hval[i] = sin ? bits_to_float((unsigned)sin[i]) : FLT_MAX;
-    hid[i] = sin ? sin[k + i] : -1;
+    hid[i] = sin ? sin[hs + i] : -1;
   }
+  // (the clamp is defensive only: a length outside [0, k] can only come from a bug in an earlier link, and
+  //  it keeps such a bug from writing outside the heap's slots -- it does not make the answer right)
+  int len = SEQ && sin ? min(max(sin[2 * hs], 0), k) : 0;                      // pairs.size()
+  float bsf = SEQ && sin ? bits_to_float((unsigned)sin[2 * hs + 1]) : FLT_MAX;  // bsfK
   // ids pushed: rows of this index (id_base is added on the way out), or global row numbers in a chain
   const int64_t push_base = p.chain ? p.id_base : 0;
   // the heap top after the last COMPLETE pop + push, for the evaluating waves (the root itself passes
   // through values below the new top while a pop is under way)
   __shared__ float s_top;
   __shared__ unsigned s_gmin[1 << GMIN_MAX_BITS];
-  if (tid == 0) s_top = sin ? bits_to_float((unsigned)sin[0]) : FLT_MAX;
+  if (tid == 0) s_top = SEQ ? bsf : (sin ? bits_to_float((unsigned)sin[0]) : FLT_MAX);
   if (p.row_bucket) {
     // Per bucket the smallest sum its rows can have -- the first table term, plus the smallest second
     // term of the bucket's group of second codes, or the minimum over a coarse bucket's first codes:
@@ -269,42 +312,99 @@ __global__ __launch_bounds__(EX_THREADS) void exact_replay_kernel(ExactParams p)
 #pragma unroll
         for (int i = 0; i < RPT; i++) {
           const int j = tid - 64 + i * (EX_THREADS - 64);
-          if (j < EX_CHUNK) out[j] = live[i] ? ex_row_dist<BYTES>(p, lut, src[i], t) : INFINITY;
+          if (j < EX_CHUNK)
+            out[j] = !live[i] ? INFINITY : SEQ ? ex_row_dist_seq(p, lut, src[i], t) : ex_row_dist<BYTES>(p, lut, src[i], t);
         }
       }
     } else if (c > 0) {
       // wave 0: the previous chunk through the reference's loop (VAQ.cpp:1750-1753), 64 rows at a time
       const float *in = buf + ((c - 1) & 1) * EX_CHUNK;
       const int64_t base = (c - 1) * EX_CHUNK;
-      for (int j0 = 0; j0 < EX_CHUNK; j0 += 64) {
-        const float d = in[j0 + lane];
-        float top = hval[0];
-        unsigned long long m = __ballot(d < top);
-        while (m != 0ull) {
-          const int src = __builtin_ctzll(m);
-          m &= m - 1ull;
-          const float dv = bits_to_float((unsigned)__builtin_amdgcn_readlane((int)float_to_bits(d), src));
-          if (top > dv) {  // if (heap_dis[0] > dist)
-            if (lane == 0) {
-              ex_heap_pop(k, hval, hid);
-              ex_heap_push(k, hval, hid, dv, (int)(push_base + base + j0 + src));
-              __hip_atomic_store(&s_top, hval[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      if constexpr (SEQ) {
+        for (int j0 = 0; j0 < EX_CHUNK; j0 += 64) {
+          // BitVecEngine.hpp:1301-1311: rows past the end and abandoned rows are +inf, never below bsfK
+          const float d = in[j0 + lane];
+          unsigned long long m = __ballot(d < bsf);
+          while (m != 0ull) {
+            const int src = __builtin_ctzll(m);
+            m &= m - 1ull;
+            const float dv = bits_to_float((unsigned)__builtin_amdgcn_readlane((int)float_to_bits(d), src));
+            if (dv < bsf) {  // if (dist < bsfK)
+              const bool full = p.row0 + base + j0 + src >= k;  // if (dataIndex >= k)
+              if (lane == 0) {
+                hval[len] = dv;
+                hid[len] = (int)(push_base + base + j0 + src);
+                stdheap::push_heap(hval, hid, len + 1);
+                if (full) stdheap::pop_heap(hval, hid, len + 1);  // (pop_back: the length stays)
+              }
+              wave_lds_sync();
+              if (full) {
+                bsf = hval[0];
+                if (lane == 0) __hip_atomic_store(&s_top, bsf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                m &= __ballot(d < bsf);  // (rows the new bsfK already excludes)
+              } else {
+                len++;
+              }
             }
-            wave_lds_sync();
-            top = hval[0];
-            m &= __ballot(d < top);  // (rows the new top already excludes)
+          }
+        }
+      } else {
+        for (int j0 = 0; j0 < EX_CHUNK; j0 += 64) {
+          const float d = in[j0 + lane];
+          float top = hval[0];
+          unsigned long long m = __ballot(d < top);
+          while (m != 0ull) {
+            const int src = __builtin_ctzll(m);
+            m &= m - 1ull;
+            const float dv = bits_to_float((unsigned)__builtin_amdgcn_readlane((int)float_to_bits(d), src));
+            if (top > dv) {  // if (heap_dis[0] > dist)
+              if (lane == 0) {
+                ex_heap_pop(k, hval, hid);
+                ex_heap_push(k, hval, hid, dv, (int)(push_base + base + j0 + src));
+                __hip_atomic_store(&s_top, hval[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              }
+              wave_lds_sync();
+              top = hval[0];
+              m &= __ballot(d < top);  // (rows the new top already excludes)
+            }
           }
         }
       }
     }
     __syncthreads();
   }
+  if (SEQ) {
+    // the length and bsfK live in wave 0; the chunk buffers are free (the loop above ended with a barrier)
+    if (tid == 0) {
+      reinterpret_cast<int *>(buf)[0] = len;
+      buf[1] = bsf;
+    }
+    __syncthreads();
+    len = reinterpret_cast<int *>(buf)[0];
+    bsf = buf[1];
+    __syncthreads();
+  }
   if (p.chain) {
     // a link hands the raw heap on (the loop above ended with a barrier)
-    int32_t *sout = p.state_out + (size_t)e * 2 * k;
-    for (int i = tid; i < k; i += EX_THREADS) {
+    int32_t *sout = p.state_out + (size_t)e * ex_state_words(k, SEQ);
+    for (int i = tid; i < hs; i += EX_THREADS) {
       sout[i] = (int32_t)float_to_bits(hval[i]);
-      sout[k + i] = hid[i];
+      sout[hs + i] = hid[i];
+    }
+    if (SEQ && tid == 0) {
+      sout[2 * hs] = len;
+      sout[2 * hs + 1] = (int32_t)float_to_bits(bsf);
+    }
+    return;
+  }
+  if (SEQ) {
+    // std::sort_heap (BitVecEngine.hpp:1316): ascending from slot 0; at most k pairs are left
+    if (tid == 0) stdheap::sort_heap(hval, hid, len);
+    __syncthreads();
+    for (int i = tid; i < k; i += EX_THREADS) {
+      const bool ok = i < len;
+      p.labels[(size_t)q * k + i] = ok ? (int32_t)(hid[i] + p.id_base) : -1;
+      p.dist[(size_t)q * k + i] = ok ? hval[i] : FLT_MAX;
     }
     return;
   }
@@ -322,6 +422,7 @@ __global__ __launch_bounds__(EX_THREADS) void exact_replay_kernel(ExactParams p)
 
 // End of a chain: heap_reorder on the state the last shard left, into the caller's slots of the listed
 // queries.  One wave per list entry; the ids are global already.
+template <bool SEQ>
 __global__ __launch_bounds__(64) void exact_finish_kernel(const int32_t *__restrict__ state, const int *__restrict__ list,
                                                           const unsigned *__restrict__ count, int k,
                                                           int32_t *__restrict__ labels, float *__restrict__ dist) {
@@ -329,15 +430,29 @@ __global__ __launch_bounds__(64) void exact_finish_kernel(const int32_t *__restr
   const int e = blockIdx.x, lane = threadIdx.x;
   if ((unsigned)e >= *count) return;
   const int q = list[e];
+  const int hs = SEQ ? k + 1 : k;
   float *hval = reinterpret_cast<float *>(ex_smem);
-  int *hid = reinterpret_cast<int *>(hval + k);
-  const int32_t *sin = state + (size_t)e * 2 * k;
-  for (int i = lane; i < k; i += 64) {
+  int *hid = reinterpret_cast<int *>(hval + hs);
+  const int32_t *sin = state + (size_t)e * ex_state_words(k, SEQ);
+  for (int i = lane; i < hs; i += 64) {
     hval[i] = bits_to_float((unsigned)sin[i]);
-    hid[i] = sin[k + i];
+    hid[i] = sin[hs + i];
   }
   __shared__ int s_nel;
   __syncthreads();
+  if (SEQ) {
+    // std::sort_heap on the pairs the last shard left: ascending from slot 0 (the clamp is defensive only,
+    // as in the replay kernel: the links never leave a length outside [0, k])
+    const int len = min(max(sin[2 * hs], 0), k);
+    if (lane == 0) stdheap::sort_heap(hval, hid, len);
+    __syncthreads();
+    for (int i = lane; i < k; i += 64) {
+      const bool ok = i < len;
+      labels[(size_t)q * k + i] = ok ? hid[i] : -1;
+      dist[(size_t)q * k + i] = ok ? hval[i] : FLT_MAX;
+    }
+    return;
+  }
   if (lane == 0) s_nel = ex_heap_reorder(k, hval, hid);
   __syncthreads();
   const int nel = s_nel;
@@ -377,18 +492,23 @@ hipError_t launch_inverse_perm(const uint32_t *perm, int64_t n, uint32_t *inv, c
 
 static hipError_t launch_replay(ExactParams &p, int grid, hipStream_t st) {
   const int k = p.k;
-  size_t lds = (size_t)k * 8 + (size_t)2 * EX_CHUNK * 4 + (p.row_bucket ? (size_t)p.n_buckets * 4 : 0);
+  if (p.seq && p.layout == LAYOUT_BYTES) return hipErrorInvalidValue;  // (sequential-sum rows are always bit-packed)
+  size_t lds = (size_t)(p.seq ? k + 1 : k) * 8 + (size_t)2 * EX_CHUNK * 4 + (p.row_bucket ? (size_t)p.n_buckets * 4 : 0);
   p.lut_in_lds = (size_t)p.lut_floats * 4 + lds <= 96 * 1024 ? 1 : 0;
   if (p.lut_in_lds) lds += (size_t)p.lut_floats * 4;
   hipError_t e;
-  if (p.layout == LAYOUT_BYTES) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(exact_replay_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (p.seq) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(exact_replay_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(exact_replay_kernel<true>, dim3(grid), dim3(EX_THREADS), lds, st, p);
+    hipLaunchKernelGGL((exact_replay_kernel<false, true>), dim3(grid), dim3(EX_THREADS), lds, st, p);
+  } else if (p.layout == LAYOUT_BYTES) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(exact_replay_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((exact_replay_kernel<true, false>), dim3(grid), dim3(EX_THREADS), lds, st, p);
   } else {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(exact_replay_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(exact_replay_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(exact_replay_kernel<false>, dim3(grid), dim3(EX_THREADS), lds, st, p);
+    hipLaunchKernelGGL((exact_replay_kernel<false, false>), dim3(grid), dim3(EX_THREADS), lds, st, p);
   }
   return hipGetLastError();
 }
@@ -396,7 +516,7 @@ static hipError_t launch_replay(ExactParams &p, int grid, hipStream_t st) {
 // in_labels / in_dist: the scan's result for k + 1 per query; labels / dist: the caller's k per query
 hipError_t launch_exact_ties(const uint32_t *codes, int layout, int M, int W, const SubDesc *sub, const uint32_t *inv,
                              const unsigned short *row_bucket, int n_buckets, int bucket_shift, int bucket_t,
-                             int64_t n_rows, const float *lut, int lut_floats, int nq, int k, int64_t id_base,
+                             int64_t n_rows, const float *lut, int lut_floats, int seq, int nq, int k, int64_t id_base,
                              const int32_t *in_labels, const float *in_dist, int32_t *labels, float *dist, int *list,
                              unsigned *count, hipStream_t st) {
   if (nq <= 0) return hipSuccess;
@@ -414,7 +534,7 @@ hipError_t launch_exact_ties(const uint32_t *codes, int layout, int M, int W, co
   p.n_rows = n_rows;
   p.lut = lut;
   p.lut_floats = lut_floats;
-  p.seq = 0;
+  p.seq = seq;
   p.k = k;
   p.id_base = id_base;
   p.in_labels = in_labels;
@@ -425,6 +545,7 @@ hipError_t launch_exact_ties(const uint32_t *codes, int layout, int M, int W, co
   p.count = count;
   p.nq = nq;
   p.chain = 0;
+  p.row0 = 0;
   p.e0 = 0;
   p.state_in = nullptr;
   p.state_out = nullptr;
@@ -455,9 +576,9 @@ hipError_t launch_exact_flag(int nq, int k, const int32_t *in_labels, const floa
 
 hipError_t launch_exact_link(const uint32_t *codes, int layout, int M, int W, const SubDesc *sub, const uint32_t *inv,
                              const unsigned short *row_bucket, int n_buckets, int bucket_shift, int bucket_t,
-                             int64_t n_rows, const float *lut, int lut_floats, int k, int64_t id_base, const int *list,
-                             const unsigned *count, int e0, int n_entries, const int32_t *state_in, int32_t *state_out,
-                             hipStream_t st) {
+                             int64_t n_rows, const float *lut, int lut_floats, int seq, int64_t row0, int k,
+                             int64_t id_base, const int *list, const unsigned *count, int e0, int n_entries,
+                             const int32_t *state_in, int32_t *state_out, hipStream_t st) {
   if (n_entries <= 0) return hipSuccess;
   ExactParams p = {};
   p.codes = codes;
@@ -473,6 +594,8 @@ hipError_t launch_exact_link(const uint32_t *codes, int layout, int M, int W, co
   p.n_rows = n_rows;
   p.lut = lut;
   p.lut_floats = lut_floats;
+  p.seq = seq;
+  p.row0 = row0;
   p.k = k;
   p.id_base = id_base;
   p.list = const_cast<int *>(list);
@@ -484,11 +607,18 @@ hipError_t launch_exact_link(const uint32_t *codes, int layout, int M, int W, co
   return launch_replay(p, n_entries, st);
 }
 
-hipError_t launch_exact_finish(const int32_t *state, const int *list, const unsigned *count, int n_entries, int k,
+hipError_t launch_exact_finish(const int32_t *state, const int *list, const unsigned *count, int n_entries, int seq, int k,
                                int32_t *labels, float *dist, hipStream_t st) {
   if (n_entries <= 0) return hipSuccess;
-  hipLaunchKernelGGL(exact_finish_kernel, dim3(n_entries), dim3(64), (size_t)k * 8, st, state, list, count, k, labels, dist);
+  if (seq)
+    hipLaunchKernelGGL(exact_finish_kernel<true>, dim3(n_entries), dim3(64), (size_t)(k + 1) * 8, st, state, list, count, k,
+                       labels, dist);
+  else
+    hipLaunchKernelGGL(exact_finish_kernel<false>, dim3(n_entries), dim3(64), (size_t)k * 8, st, state, list, count, k,
+                       labels, dist);
   return hipGetLastError();
 }
+
+int exact_state_words(int k, int seq) { return ex_state_words(k, seq); }
 
 } // namespace vaq

@@ -197,5 +197,70 @@ __host__ __device__ inline void sort(uint32_t *f, int n) {
 }
 }  // namespace stdsort
 
+// ---------------------------------------------------------------------------------------------------
+// libstdc++'s std::push_heap / std::pop_heap / std::sort_heap (bits/stl_heap.h) restated over (dist, id)
+// pairs held as two arrays and compared by dist alone -- BitVecEngine::queryLUT's k best
+// (BitVecEngine.hpp:1283-1316: std::vector<IdxDistPairFloat> under a.dist < b.dist).  The same
+// __push_heap / __adjust_heap as stdsort's above, over another element; which of several equal
+// distances ends where is a function of the sequence of calls alone.  Used by option "exact_ties" on
+// sequential-sum indexes (vaq_exact.hip).
+namespace stdheap {
+// std::__push_heap(first, hole, top, value, comp)
+__host__ __device__ inline void sift_up(float *d, int *id, int hole, int top, float vd, int vi) {
+  int parent = (hole - 1) / 2;
+  while (hole > top && d[parent] < vd) {
+    d[hole] = d[parent];
+    id[hole] = id[parent];
+    hole = parent;
+    parent = (hole - 1) / 2;
+  }
+  d[hole] = vd;
+  id[hole] = vi;
+}
+// std::__adjust_heap(first, hole, len, value, comp)
+__host__ __device__ inline void adjust_heap(float *d, int *id, int hole, int len, float vd, int vi) {
+  const int top = hole;
+  int second = hole;
+  while (second < (len - 1) / 2) {
+    second = 2 * (second + 1);
+    if (d[second] < d[second - 1]) second--;
+    d[hole] = d[second];
+    id[hole] = id[second];
+    hole = second;
+  }
+  if ((len & 1) == 0 && second == (len - 2) / 2) {
+    second = 2 * (second + 1);
+    d[hole] = d[second - 1];
+    id[hole] = id[second - 1];
+    hole = second - 1;
+  }
+  sift_up(d, id, hole, top, vd, vi);
+}
+// std::push_heap(first, first + len): the new element is the last one
+__host__ __device__ inline void push_heap(float *d, int *id, int len) {
+  sift_up(d, id, len - 1, 0, d[len - 1], id[len - 1]);
+}
+// std::__pop_heap(first, last, result = last): the maximum goes to slot `last`, the element that was there
+// is sifted down from the root of the remaining `last` elements
+__host__ __device__ inline void pop_to(float *d, int *id, int last) {
+  const float vd = d[last];
+  const int vi = id[last];
+  d[last] = d[0];
+  id[last] = id[0];
+  adjust_heap(d, id, 0, last, vd, vi);
+}
+// std::pop_heap(first, first + len): the maximum goes to the last slot
+__host__ __device__ inline void pop_heap(float *d, int *id, int len) {
+  if (len > 1) pop_to(d, id, len - 1);
+}
+// std::sort_heap(first, first + len): ascending
+__host__ __device__ inline void sort_heap(float *d, int *id, int len) {
+  while (len > 1) {
+    --len;
+    pop_to(d, id, len);
+  }
+}
+}  // namespace stdheap
+
 }  // namespace vaq
 #endif  // VAQ_FAST_H_

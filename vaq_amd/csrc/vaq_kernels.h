@@ -293,9 +293,11 @@ hipError_t launch_inverse_perm(const uint32_t *perm, int64_t n, uint32_t *inv, c
 // in_labels / in_dist: the scan's result for k + 1 per query (labels carry id_base); labels / dist: the
 // caller's k per query.  Queries whose k + 1 smallest distances are distinct are copied; the others
 // are replayed through the reference's heap in original row order.  list: [nq] ints, count: one word.
+// seq: the index sums sequentially -- the heap is BitVecEngine::queryLUT's (std::push_heap / pop_heap /
+// sort_heap over k + 1 pairs) instead of VAQ::searchHeap's.
 hipError_t launch_exact_ties(const uint32_t *codes, int layout, int M, int W, const SubDesc *sub, const uint32_t *inv,
                              const unsigned short *row_bucket, int n_buckets, int bucket_shift, int bucket_t,
-                             int64_t n_rows, const float *lut, int lut_floats, int nq, int k, int64_t id_base,
+                             int64_t n_rows, const float *lut, int lut_floats, int seq, int nq, int k, int64_t id_base,
                              const int32_t *in_labels, const float *in_dist, int32_t *labels, float *dist, int *list,
                              unsigned *count, hipStream_t st);
 // The same across the shards of a multi-device index (vaqhip_multi.cpp): the flag step alone, on the MERGED
@@ -305,15 +307,20 @@ hipError_t launch_exact_flag(int nq, int k, const int32_t *in_labels, const floa
 // ... one link of the chain: list entries [e0, e0 + n_entries) (those beyond *count exit at once) are
 // replayed over this index's rows, starting from state_in (nullptr: the neutral heap) and leaving the
 // raw heap in state_out.  Entry e's state: 2 * k words at [e * 2 * k], k distance bits then k ids; ids
-// are id_base + row.  lut: [.][lut_floats] indexed by the listed query ...
+// are id_base + row.  lut: [.][lut_floats] indexed by the listed query.  seq: exact_state_words(k, 1) words
+// per entry instead -- k + 1 distance bits, k + 1 ids, the heap's length, bsfK -- and row0 is the position of
+// this index's first row in the whole database (queryLUT's `dataIndex >= k` counts from there) ...
 hipError_t launch_exact_link(const uint32_t *codes, int layout, int M, int W, const SubDesc *sub, const uint32_t *inv,
                              const unsigned short *row_bucket, int n_buckets, int bucket_shift, int bucket_t,
-                             int64_t n_rows, const float *lut, int lut_floats, int k, int64_t id_base, const int *list,
-                             const unsigned *count, int e0, int n_entries, const int32_t *state_in, int32_t *state_out,
-                             hipStream_t st);
-// ... and its end: heap_reorder on the last state into the listed queries' slots of labels / dist [.][k]
-hipError_t launch_exact_finish(const int32_t *state, const int *list, const unsigned *count, int n_entries, int k,
+                             int64_t n_rows, const float *lut, int lut_floats, int seq, int64_t row0, int k,
+                             int64_t id_base, const int *list, const unsigned *count, int e0, int n_entries,
+                             const int32_t *state_in, int32_t *state_out, hipStream_t st);
+// ... and its end: heap_reorder (seq: std::sort_heap) on the last state into the listed queries' slots of
+// labels / dist [.][k]
+hipError_t launch_exact_finish(const int32_t *state, const int *list, const unsigned *count, int n_entries, int seq, int k,
                                int32_t *labels, float *dist, hipStream_t st);
+// int32 words of one list entry's state
+int exact_state_words(int k, int seq);
 
 // ---- triangle-inequality cluster pruning (vaq_ti.hip) ----------------------
 // packed index rows -> uint16 N x M in original row order (inverse of launch_pack_codes)

@@ -12,9 +12,12 @@ extern "C" {
 
 /* queries per internal launch set: the lookup tables of at most this many queries are kept per search */
 int vaqhip_internal_query_chunk(void);
-/* 1 when "exact_ties" is set on this index and has an effect for this k (not TI, not the sequential
- * sum, not FAST, k < VAQHIP_MAX_K) */
+/* 1 when "exact_ties" is set on this index and has an effect for this k (not TI, not FAST,
+ * k < VAQHIP_MAX_K) */
 int vaqhip_internal_exact_applies(vaqhip_index *ix, int k);
+/* int32 words of one list entry's heap state in the chain: 2 * k (k distance bits, k ids), or on a
+ * sequential-sum index 2 * (k + 1) + 2 (queryLUT's k + 1 pairs, their number, bsfK) */
+int vaqhip_internal_exact_state_words(vaqhip_index *ix, int k);
 /* vaqhip_search_device by the smallest-label rule whatever "exact_ties" says; nq at most the query
  * chunk.  The index keeps the lookup tables of these queries until its next search. */
 int vaqhip_internal_search_plain_device(vaqhip_index *ix, const float *d_queries, int nq, int k, int projected,
@@ -25,13 +28,17 @@ int vaqhip_internal_exact_flag_device(int device, int nq, int k, const int32_t *
                                       int32_t *d_labels, float *d_distances, int *d_list, unsigned *d_count,
                                       void *stream);
 /* one link of the chain on this index: entries [e0, e0 + n_entries) of d_list (queries of the last
- * vaqhip_internal_search_plain_device) from d_state_in (NULL: neutral) to d_state_out; 2 * k words per
- * list entry */
-int vaqhip_internal_exact_link_device(vaqhip_index *ix, int k, const int *d_list, const unsigned *d_count, int e0,
-                                      int n_entries, const int32_t *d_state_in, int32_t *d_state_out, void *stream);
-/* on `device`: the reference's heap_reorder on the last state, into the listed queries' k slots */
+ * vaqhip_internal_search_plain_device) from d_state_in (NULL: neutral) to d_state_out;
+ * vaqhip_internal_exact_state_words words per list entry.  row0: the position of this index's first row in
+ * the whole database (a sequential-sum index admits unconditionally below position k) */
+int vaqhip_internal_exact_link_device(vaqhip_index *ix, int k, int64_t row0, const int *d_list, const unsigned *d_count,
+                                      int e0, int n_entries, const int32_t *d_state_in, int32_t *d_state_out,
+                                      void *stream);
+/* on `device`: the reference's heap_reorder (seq != 0: queryLUT's std::sort_heap) on the last state, into the
+ * listed queries' k slots */
 int vaqhip_internal_exact_finish_device(int device, const int32_t *d_state, const int *d_list, const unsigned *d_count,
-                                        int n_entries, int k, int32_t *d_labels, float *d_distances, void *stream);
+                                        int n_entries, int seq, int k, int32_t *d_labels, float *d_distances,
+                                        void *stream);
 
 
 /* 1 when FAST is the method in force on this index (none of TI, EA, HEAP set) */

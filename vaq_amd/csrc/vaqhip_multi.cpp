@@ -136,6 +136,7 @@ struct vaqhip_multi {
   // (its members have destructors now: declared so that it can be hidden, the exported symbols stay as they were)
   __attribute__((visibility("hidden"))) ~vaqhip_multi() = default;
   int D = 0, M = 0, G = 0;
+  bool seq = false;  // VAQHIP_SUM_SEQUENTIAL: every shard is a queryLUT index
   std::vector<Shard> sh;
   bool distinct = true;  // no device named twice
   int exchange = EX_AUTO;
@@ -152,6 +153,7 @@ struct vaqhip_multi {
     int nq = 0, k = 0, projected = 0, use_rccl = 0;
     bool chain = false;            // "exact_ties" across shards: the chain runs (then k is the caller's k + 1)
     int n_batches = 0, batch = 0;  //   of the set's replay list
+    int entry = 0;                 //   int32 words of one list entry's heap state
     bool fast = false;             // FAST's sharded form
     int kk = 0;                    //   min(k, N): rows of the head
     size_t pk = 0;                 // int32 words of one shard's packed buffer: 2 * nq * k (+ the head plane)
@@ -219,7 +221,7 @@ int run_shard(vaqhip_multi *mx, int g) {
     mx->d_out_dist = reinterpret_cast<float *>(mx->d_out_labels.as<int32_t>() + plane);
   }
   if (c.chain) {
-    const size_t state = (size_t)nq * 2 * (k - 1) * 4;
+    const size_t state = (size_t)nq * c.entry * 4;
     MHIP(s.d_list.ensure(16 + (size_t)nq * 4));
     MHIP(s.d_state_in.ensure(state));
     MHIP(s.d_state_out.ensure(state));
@@ -339,7 +341,7 @@ int chain_on_shard0(vaqhip_multi *mx) {
   Shard &s = mx->sh[0];
   const vaqhip_multi::Call &c = mx->call;
   const int G = mx->G, nq = c.nq, k = c.k - 1;
-  const size_t plane = (size_t)nq * k, entry = (size_t)2 * k;
+  const size_t plane = (size_t)nq * k, entry = (size_t)c.entry;
   int32_t *fl = mx->d_final.as<int32_t>();
   float *fd = reinterpret_cast<float *>(fl + plane);
   const size_t list_bytes = 16 + (size_t)nq * 4;
@@ -368,7 +370,7 @@ int chain_on_shard0(vaqhip_multi *mx) {
         MHIP(hipMemcpyPeerAsync(t.d_state_in.as<int32_t>() + e0 * entry, t.device, u.d_state_out.as<int32_t>() + e0 * entry,
                                 u.device, ne * entry * 4, t.stream));
       }
-      MIX(vaqhip_internal_exact_link_device(t.ix, k, list_entries(t), list_count(t), e0, ne,
+      MIX(vaqhip_internal_exact_link_device(t.ix, k, t.lo, list_entries(t), list_count(t), e0, ne,
                                             g > 0 ? t.d_state_in.as<int32_t>() : nullptr, t.d_state_out.as<int32_t>(),
                                             t.stream));
       MHIP(hipEventRecord(t.link_done[b], t.stream));
@@ -378,8 +380,8 @@ int chain_on_shard0(vaqhip_multi *mx) {
   MHIP(hipSetDevice(s.device));
   MHIP(hipStreamWaitEvent(s.stream, last.link_done[c.n_batches - 1], 0));
   MHIP(hipMemcpyPeerAsync(s.d_state_in.p, s.device, last.d_state_out.p, last.device, nq * entry * 4, s.stream));
-  MIX(vaqhip_internal_exact_finish_device(s.device, s.d_state_in.as<int32_t>(), list_entries(s), list_count(s), nq, k, fl,
-                                          fd, s.stream));
+  MIX(vaqhip_internal_exact_finish_device(s.device, s.d_state_in.as<int32_t>(), list_entries(s), list_count(s), nq,
+                                          mx->seq ? 1 : 0, k, fl, fd, s.stream));
   return 0;
 }
 #undef MIX
@@ -460,6 +462,7 @@ int vaqhip_multi_create(vaqhip_multi **out, int D, int M, const int *bits, const
   mx->D = D;
   mx->M = M;
   mx->G = n_devices;
+  mx->seq = (flags & VAQHIP_SUM_SEQUENTIAL) != 0;
   mx->sh.resize(n_devices);
   for (int g = 0; g < n_devices; g++)
     for (int h = 0; h < g; h++)
@@ -853,10 +856,11 @@ static int multi_search_common(vaqhip_multi *mx, const float *queries, const flo
       return mfail(VAQHIP_EHIP, "recording the caller's stream");
   }
   // "exact_ties" over several shards: the chain, where the option has an effect on a single index too
-  // (not TI, not the sequential sum, not FAST, k < VAQHIP_MAX_K); one set of queries at a time, because
-  // every link reads the lookup tables its shard built for the set
+  // (not TI, not FAST, k < VAQHIP_MAX_K); one set of queries at a time, because every link reads the lookup
+  // tables its shard built for the set
   c.chain = mx->opt_exact && mx->G > 1;
   for (int g = 0; c.chain && g < mx->G; g++) c.chain = vaqhip_internal_exact_applies(mx->sh[g].ix, k) != 0;
+  if (c.chain) c.entry = vaqhip_internal_exact_state_words(mx->sh[0].ix, k);
   const int set = c.chain ? std::min(nq, vaqhip_internal_query_chunk()) : nq;
   for (int q0 = 0; q0 < nq; q0 += set) {
     const int n = std::min(set, nq - q0);

@@ -586,7 +586,7 @@ int ensure_inverse_perm(vaqhip_index *ix, hipStream_t st) {
 int search_device_locked(vaqhip_index *ix, const float *d_queries, int nq, int k, int projected,
                          int32_t *d_labels, float *d_dist, hipStream_t st) {
   if (fast_only(ix)) return search_fast(ix, d_queries, nq, k, projected, d_labels, d_dist, st);
-  const bool exact =ix->opt_exact && ix->ti_T == 0 && !ix->seq && nq > 0 && k > 0 && k < VAQHIP_MAX_K && ix->N >= 0 &&
+  const bool exact =ix->opt_exact && ix->ti_T == 0 && nq > 0 && k > 0 && k < VAQHIP_MAX_K && ix->N >= 0 &&
                      d_queries && d_labels && d_dist;
   if (!exact) return search_core(ix, d_queries, nq, k, projected, d_labels, d_dist, st);
   const int chunk = std::min(nq, QUERY_CHUNK);
@@ -602,8 +602,8 @@ int search_device_locked(vaqhip_index *ix, const float *d_queries, int nq, int k
     WS_SCOPE(ws, ix, st);
     HIP_TRY(vaq::launch_exact_ties(ix->d_codes.as<uint32_t>(), ix->layout, ix->M, ix->W, ix->d_sub.as<vaq::SubDesc>(),
                                    ix->d_inv.as<uint32_t>(), ix->N > 0 ? ix->d_rowbucket.as<unsigned short>() : nullptr,
-                                   ix->n_buckets, ix->bucket_shift, ix->bucket_t, ix->N, ix->w_lut.as<float>(), ix->lut_floats, n,
-                                   k, ix->id_base,
+                                   ix->n_buckets, ix->bucket_shift, ix->bucket_t, ix->N, ix->w_lut.as<float>(), ix->lut_floats,
+                                   ix->seq, n, k, ix->id_base,
                                    ix->w_ex_labels.as<int32_t>(), ix->w_ex_dist.as<float>(), d_labels + (size_t)q0 * k,
                                    d_dist + (size_t)q0 * k, reinterpret_cast<int *>(ix->w_ex_list.as<unsigned char>() + 16),
                                    ix->w_ex_list.as<unsigned>(), st));
@@ -700,7 +700,13 @@ int vaqhip_internal_query_chunk(void) { return QUERY_CHUNK; }
 int vaqhip_internal_exact_applies(vaqhip_index *ix, int k) {
   if (!ix) return 0;
   std::lock_guard<std::mutex> lk(ix->mu);
-  return ix->opt_exact && !fast_only(ix) && ix->ti_T == 0 && !ix->seq && k > 0 && k < VAQHIP_MAX_K ? 1 : 0;
+  return ix->opt_exact && !fast_only(ix) && ix->ti_T == 0 && k > 0 && k < VAQHIP_MAX_K ? 1 : 0;
+}
+
+int vaqhip_internal_exact_state_words(vaqhip_index *ix, int k) {
+  if (!ix || k <= 0) return 0;
+  std::lock_guard<std::mutex> lk(ix->mu);
+  return vaq::exact_state_words(k, ix->seq);
 }
 
 int vaqhip_internal_search_plain_device(vaqhip_index *ix, const float *d_queries, int nq, int k, int projected,
@@ -723,31 +729,33 @@ int vaqhip_internal_exact_flag_device(int device, int nq, int k, const int32_t *
   return VAQHIP_OK;
 }
 
-int vaqhip_internal_exact_link_device(vaqhip_index *ix, int k, const int *d_list, const unsigned *d_count, int e0,
-                                      int n_entries, const int32_t *d_state_in, int32_t *d_state_out, void *stream) {
+int vaqhip_internal_exact_link_device(vaqhip_index *ix, int k, int64_t row0, const int *d_list, const unsigned *d_count,
+                                      int e0, int n_entries, const int32_t *d_state_in, int32_t *d_state_out,
+                                      void *stream) {
   if (!ix) return fail(VAQHIP_EINVAL, "index is null");
-  if (k <= 0 || k >= VAQHIP_MAX_K || e0 < 0 || n_entries < 0 || !d_list || !d_count || !d_state_out)
+  if (k <= 0 || k >= VAQHIP_MAX_K || row0 < 0 || e0 < 0 || n_entries < 0 || !d_list || !d_count || !d_state_out)
     return fail(VAQHIP_EINVAL, "bad arguments");
   ENTRY(ix);
   if (ix->N < 0) return fail(VAQHIP_ESTATE, "search before codes were set");
-  if (ix->ti_T > 0 || ix->seq || fast_only(ix)) return fail(VAQHIP_EUNSUPPORTED, "no replay for this method");
+  if (ix->ti_T > 0 || fast_only(ix)) return fail(VAQHIP_EUNSUPPORTED, "no replay for this method");
   hipStream_t st = static_cast<hipStream_t>(stream);
   WS_SCOPE(ws, ix, st);
   if (int rc = ensure_inverse_perm(ix, st)) return rc;
   HIP_TRY(vaq::launch_exact_link(ix->d_codes.as<uint32_t>(), ix->layout, ix->M, ix->W, ix->d_sub.as<vaq::SubDesc>(),
                                  ix->d_inv.as<uint32_t>(), ix->N > 0 ? ix->d_rowbucket.as<unsigned short>() : nullptr,
                                  ix->n_buckets, ix->bucket_shift, ix->bucket_t, ix->N, ix->w_lut.as<float>(), ix->lut_floats,
-                                 k, ix->id_base, d_list, d_count, e0, n_entries, d_state_in, d_state_out, st));
+                                 ix->seq, row0, k, ix->id_base, d_list, d_count, e0, n_entries, d_state_in, d_state_out, st));
   return ws.finish();
 }
 
 int vaqhip_internal_exact_finish_device(int device, const int32_t *d_state, const int *d_list, const unsigned *d_count,
-                                        int n_entries, int k, int32_t *d_labels, float *d_dist, void *stream) {
+                                        int n_entries, int seq, int k, int32_t *d_labels, float *d_dist, void *stream) {
   if (n_entries < 0 || k <= 0 || k >= VAQHIP_MAX_K || !d_state || !d_list || !d_count || !d_labels || !d_dist)
     return fail(VAQHIP_EINVAL, "bad arguments");
   DeviceGuard g(device);
   if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", device);
-  HIP_TRY(vaq::launch_exact_finish(d_state, d_list, d_count, n_entries, k, d_labels, d_dist, static_cast<hipStream_t>(stream)));
+  HIP_TRY(vaq::launch_exact_finish(d_state, d_list, d_count, n_entries, seq, k, d_labels, d_dist,
+                                   static_cast<hipStream_t>(stream)));
   return VAQHIP_OK;
 }
 } // extern "C"

@@ -607,8 +607,10 @@ class VaqHipMulti:
         shards: labels and distances equal VAQ::search's over ALL rows slot for slot -- every shard scans
         with k + 1, the merged list decides which queries have ties, and those are replayed through the
         reference's heap as a chain from shard to shard (k * 8 bytes per tied query per shard boundary;
-        "exact_batch" = list entries per batch of that chain, 0 = automatic).  No effect with TI, the
-        sequential sum and k = 1024, as on a single index."""
+        "exact_batch" = list entries per batch of that chain, 0 = automatic).  On sequential-sum shards
+        the answer is BitVecEngine::queryLUT's: the chain hands on its std heap of k + 1 pairs, the heap's
+        length and bsfK, (k + 2) * 8 bytes per tied query per shard boundary.  No effect with
+        TI and k = 1024, as on a single index."""
         _lib.check_multi(_lib.load().vaqhip_multi_set_option(self._h, key.encode(), int(value)))
 
     def set_method(self, methods: int, visit: float = 1.0) -> None:
