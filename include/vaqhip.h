@@ -350,6 +350,7 @@ int vaqhip_merge_fast_device(int device_id, const uint16_t *d_head_dist, int64_t
  *                No effect -- the result is then what each shard's own option gives, merged by
  *                (distance, label), as on a single index where the option has no effect either --
  *                with TI, with FAST (whose sharded answer is the single index's slot for slot already)
+ *                (a cluster's member order is one std::sort over rows of all shards: no chain reproduces it)
  *                and for k == VAQHIP_MAX_K.  One shard: that shard's own replay.
  *                On VAQHIP_SUM_SEQUENTIAL shards the answer is BitVecEngine::queryLUT's over all rows: the
  *                state handed on is its raw std heap (k + 1 pairs), the heap's length and bsfK
@@ -507,8 +508,28 @@ int vaqhip_index_info(const vaqhip_index *ix, vaqhip_info *out);
  *                       every other query is replayed through that heap over ALL rows in original
  *                       order (one workgroup per such query: 1M rows x 10 k queries, nine in ten of
  *                       them with ties: 0.65 -> 43 ms; about a second per tied query at 1B rows).
- *                       HEAP / EA without TI, k < 1024; labels and distances are then identical to
- *                       VAQ::search's, slot for slot.  Set on a vaqhip_multi it holds across the shards
+ *                       HEAP / EA: k < 1024; labels and distances are then identical to
+ *                       VAQ::search's, slot for slot.
+ *                       On a TI index (vaqhip_index_set_ti_clusters, vaqhip_index_cluster_ti_kmeans; methods
+ *                       TI and TI | EA; any visit; every k up to VAQHIP_MAX_K) the reference's answer is a
+ *                       function of its sequential walk, and EVERY query is answered by a replay of it: the
+ *                       members of a cluster in the order std::sort leaves them (VAQ.cpp:973-979: ascending
+ *                       rows under mCodeToCCDist[i] > mCodeToCCDist[j]; libstdc++'s introsort, not stable),
+ *                       the clusters in the order std::sort of 0..T-1 under qToCCDist[i] < qToCCDist[j]
+ *                       leaves (:815-820; NaN centres compare false, keep places in the order and count
+ *                       towards maxClusterVisit), then VAQ::searchTriangleInequality (:1540-1692) statement
+ *                       for statement: the first k rows enter unconditionally, break at
+ *                       bsfK <= qcc - xcc (no slack), admission on dist < bsfKSquared with
+ *                       bsfKSquared = bsfK * bsfK, heap_reorder; without EA the answer is the first k rows
+ *                       of the walk.  The member order is built at the first such search after the rows
+ *                       were (re)grouped (one thread per cluster sorts its members: one-time cost) and
+ *                       kept on the index; one workgroup per query walks its visited rows (1M rows x 8 B,
+ *                       1000 centres, 10 k queries, k = 100, TI | EA: visit 0.1 2.9 -> 25.5 ms, visit 1
+ *                       27.5 -> 110 ms; the member order 16 ms, once).  With option
+ *                       "timing" the plan is reported as seed_ms and the replay as scan_ms.  On a
+ *                       vaqhip_multi with TI the option has NO effect: a cluster's member list is one
+ *                       std::sort over rows of all shards and does not decompose into a chain.
+ *                       Set on a vaqhip_multi (HEAP / EA) it holds across the shards
  *                       (the replay runs as a chain from shard to shard, see "multi-device" above); the
  *                       staged search of one-process-per-GPU sharding (vaqhip_search_begin_device)
  *                       stays VAQHIP_EUNSUPPORTED with the option set.

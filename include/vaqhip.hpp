@@ -82,6 +82,13 @@ public:
   float mVisit = 1.0f;
   RowMatrixF mTIClusters;
   int64_t mIdBase = 0;                        // shard offset (not in the reference: single node)
+  // option "exact_ties" (vaqhip.h; not in the reference, which IS the order it asks for): labels and distances
+  // identical to VAQ::search's slot for slot -- HEAP / EA through the reference's heap, and after clusterTI()
+  // the whole walk of VAQ::searchTriangleInequality over the reference's cluster and member orders (single
+  // device; with setDevices() a TI search keeps the default tie contract).  Takes effect at the next search().
+  // The member is pushed when the index is made and whenever its value has changed since the last push; between
+  // such pushes an option set directly on handle() stays as it was set.
+  bool exactTies = false;
   int mDevice = 0;
   // Several GPUs of the node (not in the reference, which is one host thread on one CPU): with
   // setDevices({0, 1, ..}) the code rows are sharded contiguously over them and search() ends
@@ -171,6 +178,7 @@ public:
                                 mEigenVectors.rows() ? mEigenVectors.data() : nullptr, mDevice));
       codes_set_ = false;
       ti_set_ = false;
+      exact_pushed_ = 0;  // (a new index has the option off)
     }
     if ((mMethods & NNMethod::TI) && !ti_set_) {  // before the codes: they are then grouped once
       const int seg = mTISegmentNum == -1 ? M : mTISegmentNum;  // VAQ.cpp:890-892
@@ -183,6 +191,10 @@ public:
       ti_set_ = false;
     }
     check(vaqhip_index_set_method(h_, mMethods, mVisit));
+    if (exact_pushed_ != (exactTies ? 1 : 0)) {
+      check(vaqhip_set_option(h_, "exact_ties", exactTies ? 1 : 0));
+      exact_pushed_ = exactTies ? 1 : 0;
+    }
     if (!codes_set_) {
       if (mCodebook.cols() != (size_t)M && mCodebook.rows() != 0)
         throw Error(VAQHIP_EINVAL, "vaqhip: mCodebook is not N x M");
@@ -205,6 +217,7 @@ public:
                                      mDevices.data(), 0u));
       codes_set_ = false;
       ti_set_ = false;
+      exact_pushed_ = 0;  // (a new index has the option off)
       fastQuantPushed_ = false;
     }
     if ((mMethods & NNMethod::TI) && !ti_set_) {
@@ -219,6 +232,10 @@ public:
     }
     // (FAST alone is only taken once the quantisation is on the shards: VaqHipFast pushes it and sets the method)
     if (!fastOnly() || fastQuantPushed_) checkMulti(vaqhip_multi_set_method(mh_, mMethods, mVisit));
+    if (exact_pushed_ != (exactTies ? 1 : 0)) {
+      checkMulti(vaqhip_multi_set_option(mh_, "exact_ties", exactTies ? 1 : 0));
+      exact_pushed_ = exactTies ? 1 : 0;
+    }
     if (!codes_set_) {
       if (mCodebook.cols() != (size_t)M && mCodebook.rows() != 0)
         throw Error(VAQHIP_EINVAL, "vaqhip: mCodebook is not N x M");
@@ -395,6 +412,7 @@ private:
   vaqhip_multi *mh_ = nullptr;
   bool codes_set_ = false;
   bool ti_set_ = false;
+  int exact_pushed_ = 0;  // the value of exactTies the index holds from the last push
 };
 
 // ---------------------------------------------------------------------------

@@ -43,7 +43,7 @@ def _deps(src: str):
         deps.append(SCAN_HEADER)
     if src in ("vaq_kernels.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip"):
         deps.append(SCAN_BF_HEADER)
-    if src in ("vaq_fast.hip", "vaqhip_fast.cpp", "vaq_exact.hip"):
+    if src in ("vaq_fast.hip", "vaqhip_fast.cpp", "vaq_exact.hip", "vaq_ti.hip"):
         deps.append(FAST_HEADER)
     return deps
 OBJDIR = os.path.join(LIBDIR, "obj")

@@ -619,6 +619,284 @@ hipError_t launch_exact_finish(const int32_t *state, const int *list, const unsi
   return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------------
+// TI indexes: VAQ::searchTriangleInequality (VAQ.cpp:1540-1692) replayed, EVERY query (there is no "queries
+// that have ties" shortcut: the 1-ulp cases of the unslacked bound are part of what is reproduced).
+// The walk of a query: the clusters in the order of launch_ti_plan(exact = 1), the first nvisit of them
+// ((ccIdxIdx < maxClusterVisit) || (!retrievedEnough && ccIdxIdx < T), :1555), empty ones skipped, inside a
+// cluster the reference's member order (ti_build_walk).  Walk position w is row w of that concatenation when
+// nothing is pruned; a `break` (:1566-1569) makes the cursor jump to the first position of the next cluster.
+//   - heap_heapify; bsfK = 0, bsfKSquared = 0
+//   - positions < k (counter < k; no break can precede them) enter unconditionally: heap_pop, heap_push of
+//     sqrt(dist), if (dist > bsfK) { bsfK = dist; [EA: bsfKSquared = bsfK * bsfK] }  (:1591-1613)
+//   - from position k on: break at the first member with bsfK <= qToCCDist[c] - mCodeToCCDist[row] (plain
+//     fp32 subtraction); else admit iff dist < bsfKSquared on the un-rooted sum: heap_pop, heap_push(sqrt(dist)),
+//     bsfK = heap_dis[0], bsfKSquared = bsfK * bsfK (one rounded multiply)  (:1565-1590)
+//   - without EA bsfKSquared stays 0 (:1624-1658): nothing is admitted after position k - 1, so the walk ends
+//     there -- labels and distances are final
+//   - heap_reorder
+// The EA branch's partial-sum abandon (:1574) only drops rows dist < bsfKSquared drops (table entries >= 0).
+// Waves 1.. evaluate a chunk of consecutive walk positions into LDS -- the complete row sum, the bound
+// qcc - xcc, the row's label --, wave 0 replays the previous chunk: per 64 positions a ballot of the break
+// test and one of the admission test over the lanes at or after the cursor; the first set lane of either is
+// the next event (the break test comes first in the loop body, so it wins a shared lane), handled with the
+// reference's statements, after which both ballots are taken again.  After the first k positions bsfK and
+// bsfKSquared never rise as long as bsfK * bsfK is a normal number (sqrt(fl(x * x)) == x then), so the
+// evaluating waves may abandon against the published bsfKSquared and skip rows whose bound the published bsfK
+// already excludes: both are never below the reference's at that row, and an excluded row lies at or behind
+// its cluster's break.  Where bsfK * bsfK is subnormal or underflows (bsfK below about 1.1e-19) the identity
+// fails and an admission can RAISE heap_dis[0]: +inf is published there instead (tix_publish), i.e. nothing is
+// skipped or abandoned -- and a value published earlier, from the normal range, stays above all of these.  When the cursor jumps
+// past whole chunks they are not evaluated at all.
+constexpr int TIX_THREADS = 512;
+constexpr int TIX_CHUNK = 1024;  // walk positions per chunk (a multiple of 64)
+
+struct TiExactParams {
+  ExactParams x;  // codes, layout, M, W, sub, lut, lut_floats, lut_in_lds, k, id_base, labels, dist
+  const uint32_t *perm;  // index row -> original row
+  const uint32_t *walk;  // position in the reference's member order -> index row
+  const int *start;      // [T + 1] first index row of each cluster
+  const float *xcc;      // mCodeToCCDist by index row
+  int T;
+  const int *order;      // [nq][T]
+  const float *qcc;      // [nq][T], in `order`'s order
+  const int *nvisit;     // [nq]
+  int ea;
+};
+
+// what the evaluating waves may test against (above)
+__device__ __forceinline__ void tix_publish(float *s_bsfk, float *s_bsf2, const float bsfK, const float bsf2) {
+  const bool mono = bsf2 >= FLT_MIN;
+  __hip_atomic_store(s_bsfk, mono ? bsfK : INFINITY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __hip_atomic_store(s_bsf2, mono ? bsf2 : INFINITY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+template <bool BYTES>
+__global__ __launch_bounds__(TIX_THREADS) void ti_exact_replay_kernel(TiExactParams tp) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char ex_smem[];
+  const ExactParams &p = tp.x;
+  const int q = blockIdx.x;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int k = p.k, T = tp.T;
+  // LDS: heap values, heap ids, two chunk buffers of (row sum, bound, label), the walk position of every
+  // visited cluster's first member, [the query's lookup tables]
+  float *hval = reinterpret_cast<float *>(ex_smem);
+  int *hid = reinterpret_cast<int *>(hval + k);
+  float *bufd = reinterpret_cast<float *>(hid + k);      // [2][TIX_CHUNK]
+  float *bufb = bufd + 2 * TIX_CHUNK;                    // [2][TIX_CHUNK]
+  int *bufl = reinterpret_cast<int *>(bufb + 2 * TIX_CHUNK);  // [2][TIX_CHUNK]
+  int *cum = bufl + 2 * TIX_CHUNK;                       // [T + 1]
+  float *lds_lut = reinterpret_cast<float *>(cum + T + 1);
+  const float *glut = p.lut + (size_t)q * p.lut_floats;
+  const float *lut = glut;
+  if (p.lut_in_lds) {
+    for (int i = tid; i < p.lut_floats; i += TIX_THREADS) lds_lut[i] = glut[i];
+    lut = lds_lut;
+  }
+  const int *order = tp.order + (size_t)q * T;
+  const float *qcc = tp.qcc + (size_t)q * T;
+  const int nv = min(max(tp.nvisit[q], 0), T);
+  for (int i = tid; i < k; i += TIX_THREADS) {  // heap_heapify (utils/Heap.hpp:211-235)
+    hval[i] = FLT_MAX;
+    hid[i] = -1;
+  }
+  // cum[i] = members of the first i clusters of the order (wave 0: a segment per lane, then the lanes' totals)
+  if (wave == 0) {
+    const int seg = (nv + 63) / 64;
+    const int i0 = min(lane * seg, nv), i1 = min(i0 + seg, nv);
+    int sum = 0;
+    for (int i = i0; i < i1; i++) {
+      const int c = order[i];
+      sum += tp.start[c + 1] - tp.start[c];
+    }
+    int incl = sum;
+    for (int off = 1; off < 64; off <<= 1) {
+      const int o = __shfl_up(incl, off, 64);
+      if (lane >= off) incl += o;
+    }
+    int run = incl - sum;
+    for (int i = i0; i < i1; i++) {
+      const int c = order[i];
+      cum[i] = run;
+      run += tp.start[c + 1] - tp.start[c];
+    }
+    if (lane == 63) cum[nv] = incl;
+  }
+  // what the evaluating waves test against: +inf until k rows have entered (nothing is skipped before)
+  __shared__ float s_bsfk, s_bsf2;
+  __shared__ int s_cur[2];
+  if (tid == 0) {
+    s_bsfk = INFINITY;
+    s_bsf2 = INFINITY;
+  }
+  __syncthreads();
+  // without EA the walk ends with the k-th row that enters
+  const int wend = tp.ea ? cum[nv] : min(cum[nv], k);
+  const int nchunks = (wend + TIX_CHUNK - 1) / TIX_CHUNK;
+  float bsfK = 0.0f, bsf2 = 0.0f;
+  int cur = 0;  // wave 0: the walk position the reference's loops stand at
+  int ec = 0, pc = -1;  // chunk the waves evaluate in this round, chunk wave 0 replays
+  for (int it = 0;; it++) {
+    if (wave > 0) {
+      if (ec < nchunks) {
+        const float t2 = __hip_atomic_load(&s_bsf2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const float tk = __hip_atomic_load(&s_bsfk, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        const int scur = it > 0 ? s_cur[(it - 1) & 1] : 0;  // (the cursor after the round before: never ahead)
+        float *od = bufd + (it & 1) * TIX_CHUNK, *ob = bufb + (it & 1) * TIX_CHUNK;
+        int *ol = bufl + (it & 1) * TIX_CHUNK;
+        for (int j = tid - 64; j < TIX_CHUNK; j += TIX_THREADS - 64) {
+          const int w = ec * TIX_CHUNK + j;
+          float dv = INFINITY, bv = 0.0f;
+          int lab = -1;
+          if (w < wend && w >= scur) {
+            int lo = 0, hi = nv;  // largest i with cum[i] <= w: its cluster (w < cum[nv]; empty ones skipped)
+            while (hi - lo > 1) {
+              const int mid = (lo + hi) >> 1;
+              if (cum[mid] <= w) lo = mid;
+              else hi = mid;
+            }
+            const int c = order[lo];
+            const int64_t row = tp.walk[tp.start[c] + (w - cum[lo])];
+            bv = qcc[lo] - tp.xcc[row];
+            lab = (int)tp.perm[row];
+            const bool uncond = w < k;
+            if (uncond || !(tk <= bv)) dv = ex_row_dist<BYTES>(p, lut, row, uncond ? INFINITY : t2);
+          }
+          od[j] = dv;
+          ob[j] = bv;
+          ol[j] = lab;
+        }
+      }
+    } else if (pc >= 0) {
+      const float *id = bufd + ((it - 1) & 1) * TIX_CHUNK, *ib = bufb + ((it - 1) & 1) * TIX_CHUNK;
+      const int *il = bufl + ((it - 1) & 1) * TIX_CHUNK;
+      const int base = pc * TIX_CHUNK;
+      for (int j0 = 0; j0 < TIX_CHUNK; j0 += 64) {
+        const int g0 = base + j0, g1 = min(g0 + 64, wend);
+        if (g0 >= wend) break;
+        if (cur >= g1) continue;
+        const float d = id[j0 + lane], b = ib[j0 + lane];
+        const int lab = il[j0 + lane];
+        const int w = g0 + lane;
+        if (cur < k) {
+          // counter < k (:1591-1613 / :1659-1679): (cur >= g0 here: nothing jumps before k rows have entered)
+          const int e = min(k, g1);
+          for (int w1 = cur; w1 < e; w1++) {
+            const float dv = bits_to_float((unsigned)__builtin_amdgcn_readlane((int)float_to_bits(d), w1 - g0));
+            const int lb = __builtin_amdgcn_readlane(lab, w1 - g0);
+            const float r = sqrtf(dv);
+            if (lane == 0) {
+              ex_heap_pop(k, hval, hid);
+              ex_heap_push(k, hval, hid, r, lb);
+            }
+            if (r > bsfK) {
+              bsfK = r;
+              if (tp.ea) bsf2 = bsfK * bsfK;
+            }
+          }
+          wave_lds_sync();
+          cur = e;
+          if (cur >= k && lane == 0) tix_publish(&s_bsfk, &s_bsf2, bsfK, bsf2);
+        }
+        while (cur < g1) {
+          // counter >= k (:1565-1590): the next event among the positions at or after the cursor
+          const bool act = w >= cur && w < g1;
+          const unsigned long long brk = __ballot(act && bsfK <= b);
+          const unsigned long long adm = __ballot(act && d < bsf2);
+          const int fb = brk != 0ull ? __builtin_ctzll(brk) : 64, fa = adm != 0ull ? __builtin_ctzll(adm) : 64;
+          if (fb == 64 && fa == 64) {
+            cur = g1;
+          } else if (fb <= fa) {
+            // break: on to the first member of the next cluster
+            const int wb = g0 + fb;
+            int lo = 0, hi = nv;
+            while (hi - lo > 1) {
+              const int mid = (lo + hi) >> 1;
+              if (cum[mid] <= wb) lo = mid;
+              else hi = mid;
+            }
+            cur = cum[lo + 1];
+          } else {
+            const float dv = bits_to_float((unsigned)__builtin_amdgcn_readlane((int)float_to_bits(d), fa));
+            const int lb = __builtin_amdgcn_readlane(lab, fa);
+            if (lane == 0) {
+              ex_heap_pop(k, hval, hid);
+              ex_heap_push(k, hval, hid, sqrtf(dv), lb);
+            }
+            wave_lds_sync();
+            bsfK = hval[0];
+            bsf2 = bsfK * bsfK;
+            if (lane == 0) tix_publish(&s_bsfk, &s_bsf2, bsfK, bsf2);
+            cur = g0 + fa + 1;
+          }
+        }
+      }
+    }
+    // (two slots: a wave still reading this round's cursor is at most one barrier behind wave 0)
+    if (tid == 0) s_cur[it & 1] = cur;
+    __syncthreads();
+    const int cc = s_cur[it & 1];
+    if (ec >= nchunks || cc >= wend) break;  // the last chunk has been replayed / the walk is over
+    pc = ec;
+    ec = max(ec + 1, cc / TIX_CHUNK);
+  }
+  // heap_reorder; the tail is refilled with FLT_MAX / -1
+  __shared__ int s_nel;
+  if (tid == 0) s_nel = ex_heap_reorder(k, hval, hid);
+  __syncthreads();
+  const int nel = s_nel;
+  for (int i = tid; i < k; i += TIX_THREADS) {
+    const bool ok = i < nel;
+    const int id = ok ? hid[k - nel + i] : -1;
+    p.labels[(size_t)q * k + i] = ok ? (int32_t)(id + p.id_base) : -1;
+    p.dist[(size_t)q * k + i] = ok ? hval[k - nel + i] : FLT_MAX;
+  }
+}
+
+hipError_t launch_ti_exact_replay(const uint32_t *codes, int layout, int M, int W, const SubDesc *sub,
+                                  const uint32_t *perm, const uint32_t *walk, const int *start, const float *xcc_sorted,
+                                  int T, const int *order, const float *qcc, const int *nvisit, int ea,
+                                  const float *lut, int lut_floats, int nq, int k, int64_t id_base, int32_t *labels,
+                                  float *dist, hipStream_t st) {
+  if (nq <= 0) return hipSuccess;
+  TiExactParams tp = {};
+  tp.x.codes = codes;
+  tp.x.layout = layout;
+  tp.x.M = M;
+  tp.x.W = W;
+  tp.x.sub = sub;
+  tp.x.lut = lut;
+  tp.x.lut_floats = lut_floats;
+  tp.x.k = k;
+  tp.x.id_base = id_base;
+  tp.x.labels = labels;
+  tp.x.dist = dist;
+  tp.x.nq = nq;
+  tp.perm = perm;
+  tp.walk = walk;
+  tp.start = start;
+  tp.xcc = xcc_sorted;
+  tp.T = T;
+  tp.order = order;
+  tp.qcc = qcc;
+  tp.nvisit = nvisit;
+  tp.ea = ea;
+  size_t lds = (size_t)k * 8 + (size_t)6 * TIX_CHUNK * 4 + (size_t)(T + 1) * 4;
+  tp.x.lut_in_lds = (size_t)lut_floats * 4 + lds <= 96 * 1024 ? 1 : 0;
+  if (tp.x.lut_in_lds) lds += (size_t)lut_floats * 4;
+  hipError_t e;
+  if (layout == LAYOUT_BYTES) {
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(ti_exact_replay_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ti_exact_replay_kernel<true>), dim3(nq), dim3(TIX_THREADS), lds, st, tp);
+  } else {
+    e = hipFuncSetAttribute(reinterpret_cast<const void *>(ti_exact_replay_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL((ti_exact_replay_kernel<false>), dim3(nq), dim3(TIX_THREADS), lds, st, tp);
+  }
+  return hipGetLastError();
+}
+
 int exact_state_words(int k, int seq) { return ex_state_words(k, seq); }
 
 } // namespace vaq

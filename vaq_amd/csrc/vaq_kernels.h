@@ -335,7 +335,21 @@ hipError_t ti_group_rows(const uint16_t *d_codes, int64_t n, int M, int L, int s
 // (clusters_t: the centres dimension-major, T floats per dimension)
 hipError_t launch_ti_plan(const float *qproj, int nq, int D, int d, const float *clusters_t, int T,
                           const int *start, int max_visit, int k, int *order, float *qcc, int *nvisit,
-                          hipStream_t st);
+                          hipStream_t st, int exact = 0);
+// option "exact_ties" on a TI index (vaq_ti.hip, vaq_exact.hip).  exact = 1 above: the cluster order is the
+// reference's std::sort's, equal and NaN distances included.
+// d_walk[n]: position in the reference's member order (clusters in index order, VAQ::clusterTI's std::sort
+// inside each) -> index row.  d_start: the back-filled cluster starts [T + 1].  Synchronises the stream.
+hipError_t ti_build_walk(const uint32_t *d_perm, const int *d_start, const float *d_xcc_sorted, int64_t n, int T,
+                         uint32_t *d_walk, hipStream_t st);
+// VAQ::searchTriangleInequality (VAQ.cpp:1540-1692) replayed statement for statement, one workgroup per query,
+// over the walk above and the plan of launch_ti_plan(exact = 1).  ea: the method includes EA.  Labels are
+// id_base + original row, unfilled slots -1 / FLT_MAX.
+hipError_t launch_ti_exact_replay(const uint32_t *codes, int layout, int M, int W, const SubDesc *sub,
+                                  const uint32_t *perm, const uint32_t *walk, const int *start, const float *xcc_sorted,
+                                  int T, const int *order, const float *qcc, const int *nvisit, int ea,
+                                  const float *lut, int lut_floats, int nq, int k, int64_t id_base, int32_t *labels,
+                                  float *dist, hipStream_t st);
 // extra LDS bytes of a TI scan workgroup staging `cap` entries of its visiting list
 size_t scan_ti_lds_bytes(int cap);
 

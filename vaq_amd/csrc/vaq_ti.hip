@@ -7,6 +7,7 @@
 // Compiled with -ffp-contract=off like every file of the library: distances
 // are the reference's  res += tmp * tmp  (utils/Math.hpp:8-19), multiply and
 // add unfused, or its SSE orders for d in {1,2,4,8,12} (:38-128).
+#include "vaq_fast.h"
 #include "vaq_kernels.h"
 #include "vaqhip_dev.h"
 
@@ -248,9 +249,21 @@ hipError_t ti_group_rows(const uint16_t *d_codes, int64_t n, int M, int L, int s
 // that order.
 // Outputs, per query: order[T] (cluster ids), qcc[T] (their distances, same
 // order), nvisit.
+// EXACT (option "exact_ties"): the order is the reference's own, std::sort of
+// 0..T-1 under qToCCDist[i] < qToCCDist[j] (VAQ.cpp:815-820).  Where all
+// distances differ and none is NaN that IS the ascending order the bitonic
+// network leaves; otherwise (equal distances; NaN centres, the empty clusters
+// of clusterTI(true), whose comparisons are all false and whose places in the
+// order are whatever introsort leaves) one thread runs stdsort::sort_by.
 // ---------------------------------------------------------------------------
 constexpr int TI_PLAN_THREADS = 256;
 
+struct QccLess {  // qToCCDist[i] < qToCCDist[j]
+  const float *qcc;
+  __device__ __forceinline__ bool operator()(int i, int j) const { return qcc[i] < qcc[j]; }
+};
+
+template <bool EXACT>
 __global__ __launch_bounds__(TI_PLAN_THREADS) void ti_plan_kernel(
     const float *__restrict__ qproj, int D, int d, const float *__restrict__ clusters_t, int T, int Tp,
     const int *__restrict__ start, int max_visit, int k, int *__restrict__ order,
@@ -260,7 +273,11 @@ __global__ __launch_bounds__(TI_PLAN_THREADS) void ti_plan_kernel(
   // last) above the cluster index -- ascending keys = ascending (distance, cluster)
   unsigned long long *key = reinterpret_cast<unsigned long long *>(smem);  // [Tp]
   float *qs = reinterpret_cast<float *>(key + Tp);                         // [d]
+  float *qn = qs + d;                                                      // EXACT: [T] distances by cluster
+  int *idx = reinterpret_cast<int *>(qn + T);                              // EXACT: [T]
+  __shared__ int s_redo;
   const int q = blockIdx.x, tid = threadIdx.x;
+  if (EXACT && tid == 0) s_redo = 0;
   for (int j = tid; j < d; j += TI_PLAN_THREADS) qs[j] = qproj[(size_t)q * D + j];
   __syncthreads();
   for (int c = tid; c < Tp; c += TI_PLAN_THREADS) {
@@ -269,6 +286,7 @@ __global__ __launch_bounds__(TI_PLAN_THREADS) void ti_plan_kernel(
       // clusters_t is dimension-major (T floats per dimension): lanes read consecutive floats
       const float v = sqrtf(l2sqr_ref_order(qs, 1, clusters_t + c, d, T));
       k = ((unsigned long long)__builtin_bit_cast(unsigned, v) << 32) | (unsigned)c;
+      if (EXACT) qn[c] = v;
     }
     key[c] = k;
   }
@@ -286,6 +304,27 @@ __global__ __launch_bounds__(TI_PLAN_THREADS) void ti_plan_kernel(
       }
       __syncthreads();
     }
+  if (EXACT) {
+    bool redo = false;
+    for (int i = tid; i < T; i += TI_PLAN_THREADS) {
+      const unsigned hi = (unsigned)(key[i] >> 32);
+      const float v = __builtin_bit_cast(float, hi);
+      redo = redo || v != v || (i + 1 < T && (unsigned)(key[i + 1] >> 32) == hi);
+    }
+    if (redo) s_redo = 1;
+    __syncthreads();
+    if (s_redo) {
+      for (int i = tid; i < T; i += TI_PLAN_THREADS) idx[i] = i;
+      __syncthreads();
+      if (tid == 0) stdsort::sort_by<12, true>(idx, T, QccLess{qn});  // T <= VAQHIP_MAX_TI_CLUSTERS = 1 << 12
+      __syncthreads();
+      for (int i = tid; i < T; i += TI_PLAN_THREADS) {
+        const int c = idx[i];
+        key[i] = ((unsigned long long)__builtin_bit_cast(unsigned, qn[c]) << 32) | (unsigned)c;
+      }
+      __syncthreads();
+    }
+  }
   for (int i = tid; i < T; i += TI_PLAN_THREADS) {
     const unsigned long long k = key[i];
     order[(size_t)q * T + i] = (int)(unsigned)k;
@@ -305,14 +344,91 @@ __global__ __launch_bounds__(TI_PLAN_THREADS) void ti_plan_kernel(
 
 hipError_t launch_ti_plan(const float *qproj, int nq, int D, int d, const float *clusters_t, int T,
                           const int *start, int max_visit, int k, int *order, float *qcc, int *nvisit,
-                          hipStream_t st) {
+                          hipStream_t st, int exact) {
   if (nq == 0) return hipSuccess;
+  if (exact && T > (1 << 12)) return hipErrorInvalidValue;  // (the sort's stack; VAQHIP_MAX_TI_CLUSTERS)
   int Tp = 2;
   while (Tp < T) Tp <<= 1;
   const size_t lds = (size_t)Tp * 8 + (size_t)d * 4;  // keys + the query's first d dims
-  hipLaunchKernelGGL(ti_plan_kernel, dim3(nq), dim3(TI_PLAN_THREADS), lds, st, qproj, D, d, clusters_t, T, Tp,
-                     start, max_visit, k, order, qcc, nvisit);
+  if (exact)  // + the distances by cluster and the sequence std::sort works on
+    hipLaunchKernelGGL(ti_plan_kernel<true>, dim3(nq), dim3(TI_PLAN_THREADS), lds + (size_t)T * 8, st, qproj, D, d,
+                       clusters_t, T, Tp, start, max_visit, k, order, qcc, nvisit);
+  else
+    hipLaunchKernelGGL(ti_plan_kernel<false>, dim3(nq), dim3(TI_PLAN_THREADS), lds, st, qproj, D, d, clusters_t, T, Tp,
+                       start, max_visit, k, order, qcc, nvisit);
   return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// The reference's member order (option "exact_ties").  VAQ::clusterTI appends
+// the members of a cluster in ascending row order (VAQ.cpp:929-951) and then
+// runs std::sort under mCodeToCCDist[i] > mCodeToCCDist[j] (:973-979): where
+// members have EQUAL distances, their order is what libstdc++'s introsort
+// leaves -- a function of the whole cluster's key sequence.  The index keeps
+// such members in ascending row order instead (ti_keys_kernel); walk[] maps a
+// position of the reference's order to the index row that holds that member.
+// The two orders differ only inside runs of equal xcc.
+//   ti_walk_keys_kernel   key = cluster << 32 | original row, value = index row
+//   (radix sort)          -> per cluster its index rows by ascending ORIGINAL row
+//   ti_member_sort_kernel lane 0 of one wave per cluster: stdsort::sort_by over
+//                         that sequence, in global memory
+// ---------------------------------------------------------------------------
+__global__ void ti_walk_keys_kernel(const uint32_t *__restrict__ perm, const int *__restrict__ start, int T,
+                                    int64_t n, uint64_t *__restrict__ keys, uint32_t *__restrict__ rows) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n) return;
+  int lo = 0, hi = T;  // largest c with start[c] <= r (start[T] = n > r): its cluster, empty ones skipped
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((int64_t)start[mid] <= r) lo = mid;
+    else hi = mid;
+  }
+  keys[r] = ((uint64_t)(uint32_t)lo << 32) | perm[r];
+  rows[r] = (uint32_t)r;
+}
+
+struct XccGreater {  // mCodeToCCDist[i] > mCodeToCCDist[j], through the index rows that hold i and j
+  const float *xcc;
+  __device__ __forceinline__ bool operator()(uint32_t a, uint32_t b) const { return xcc[a] > xcc[b]; }
+};
+
+__global__ __launch_bounds__(64) void ti_member_sort_kernel(const int *__restrict__ start,
+                                                            const float *__restrict__ xcc_sorted,
+                                                            uint32_t *__restrict__ walk) {
+  if (threadIdx.x != 0) return;
+  const int c = blockIdx.x;
+  const int b = start[c], n = start[c + 1] - b;
+  // (xcc is never NaN -- a NaN distance never wins ti_assign_kernel's `<` --, so the guard never acts)
+  stdsort::sort_by<31, true>(walk + b, n, XccGreater{xcc_sorted});
+}
+
+hipError_t ti_build_walk(const uint32_t *d_perm, const int *d_start, const float *d_xcc_sorted, int64_t n, int T,
+                         uint32_t *d_walk, hipStream_t st) {
+  if (n <= 0 || T <= 0) return hipSuccess;
+  vaqhost::DevBuf b_keys_in, b_keys_out, b_rows_in, b_temp;  // (freed on return, after the stream is synchronised)
+  hipError_t e;
+  if ((e = b_keys_in.ensure((size_t)n * 8)) != hipSuccess || (e = b_keys_out.ensure((size_t)n * 8)) != hipSuccess ||
+      (e = b_rows_in.ensure((size_t)n * 4)) != hipSuccess)
+    return e;
+  uint64_t *keys_in = b_keys_in.as<uint64_t>(), *keys_out = b_keys_out.as<uint64_t>();
+  uint32_t *rows_in = b_rows_in.as<uint32_t>();
+  hipLaunchKernelGGL(ti_walk_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, d_perm, d_start, T, n,
+                     keys_in, rows_in);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  unsigned cbits = 1;
+  while ((1u << cbits) < (unsigned)T) cbits++;
+  size_t temp_bytes = 0;
+  e = rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, rows_in, d_walk, (size_t)n, 0u, 32u + cbits, st);
+  if (e == hipSuccess) e = b_temp.ensure(temp_bytes ? temp_bytes : 16);
+  if (e == hipSuccess)
+    e = rocprim::radix_sort_pairs(b_temp.p, temp_bytes, keys_in, keys_out, rows_in, d_walk, (size_t)n, 0u, 32u + cbits,
+                                  st);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(ti_member_sort_kernel, dim3(T), dim3(64), 0, st, d_start, d_xcc_sorted, d_walk);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  return e;
 }
 
 } // namespace vaq

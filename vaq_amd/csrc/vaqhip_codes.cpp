@@ -95,6 +95,7 @@ int build_rows(vaqhip_index *ix, const uint16_t *d_u16, int64_t N, hipStream_t s
   ix->n_buckets = K0;
   ix->sub_fine = N > 0 ? fine : 0;
   ix->inv_valid = false;
+  ix->ti_walk_valid = false;  // (set / add codes, set_ti_clusters and cluster_ti_kmeans all regroup here)
   return VAQHIP_OK;
 }
 

@@ -90,6 +90,11 @@ struct vaqhip_index {
   // option "exact_ties": original row -> bucketed row (built at the first such search after the codes change),
   // the scan's k + 1 results, the replay list
   DevBuf d_inv, d_rowbucket, w_ex_labels, w_ex_dist, w_ex_list;
+  // ... on a TI index: position in the reference's member order -> index row (vaq::ti_build_walk), built at the
+  // first such search after the rows were (re)grouped
+  DevBuf d_ti_walk;
+  bool ti_walk_valid = false;
+  bool sharded = false;  // one shard of several (vaqhip_internal_set_sharded): no TI replay, the shards merge by (distance, label)
   vaqhost::StagedState staged;  // vaqhip_search_begin_device .. vaqhip_search_finish_device
   // FAST (max bits <= 4): the codes again in ORIGINAL row order as nibbles (vaq_fast.h), rows padded to
   // FAST_ROW_PAD with code 0; mOffsets / mScale on the host and the device; per-call workspaces

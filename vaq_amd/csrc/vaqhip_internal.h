@@ -12,9 +12,13 @@ extern "C" {
 
 /* queries per internal launch set: the lookup tables of at most this many queries are kept per search */
 int vaqhip_internal_query_chunk(void);
-/* 1 when "exact_ties" is set on this index and has an effect for this k (not TI, not FAST,
- * k < VAQHIP_MAX_K) */
+/* 1 when "exact_ties" is set on this index and the chain over shards reproduces it for this k (not TI, not
+ * FAST, k < VAQHIP_MAX_K).  TI: on one index the option replays the reference's walk, but its member list of a
+ * cluster is ONE std::sort over rows of all shards, whose order among equal keys does not decompose into a
+ * chain -- so this answers 0 and a multi-device index with TI keeps the default tie contract. */
 int vaqhip_internal_exact_applies(vaqhip_index *ix, int k);
+/* marks the index as one shard of several: "exact_ties" then leaves its TI searches alone (above) */
+void vaqhip_internal_set_sharded(vaqhip_index *ix, int sharded);
 /* int32 words of one list entry's heap state in the chain: 2 * k (k distance bits, k ids), or on a
  * sequential-sum index 2 * (k + 1) + 2 (queryLUT's k + 1 pairs, their number, bsfK) */
 int vaqhip_internal_exact_state_words(vaqhip_index *ix, int k);

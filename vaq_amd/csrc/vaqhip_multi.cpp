@@ -476,6 +476,8 @@ int vaqhip_multi_create(vaqhip_multi **out, int D, int M, const int *bits, const
       vaqhip_multi_destroy(mx);
       return rc;
     }
+    // ("exact_ties" with TI is a property of ONE index: a shard among several keeps the default tie contract)
+    if (n_devices > 1) vaqhip_internal_set_sharded(s.ix, 1);
     bool ok = hipSetDevice(s.device) == hipSuccess && hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess &&
               hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
     if (g == 0) {

@@ -579,6 +579,82 @@ int ensure_inverse_perm(vaqhip_index *ix, hipStream_t st) {
   return VAQHIP_OK;
 }
 
+// the reference's member order of a TI index, for option "exact_ties": made at the first such search after the
+// rows were (re)grouped
+int ensure_ti_walk(vaqhip_index *ix, hipStream_t st) {
+  if (ix->N <= 0 || ix->ti_walk_valid) return VAQHIP_OK;
+  HIP_TRY(ix->d_ti_walk.ensure((size_t)ix->N * sizeof(uint32_t)));
+  HIP_TRY(vaq::ti_build_walk(ix->d_perm.as<uint32_t>(), ix->d_bstart.as<int>(), ix->d_ti_xcc.as<float>(), ix->N, ix->ti_T,
+                             ix->d_ti_walk.as<uint32_t>(), st));  // synchronises
+  ix->ti_walk_valid = true;
+  return VAQHIP_OK;
+}
+
+// Option "exact_ties" on a TI index: every query is answered by a replay of VAQ::searchTriangleInequality's walk
+// (vaq_exact.hip) over the reference's own cluster order and member order (vaq_ti.hip).  Timing: the plan is
+// reported as seed_ms, the replay as scan_ms; nothing is merged, so merge_ms is always 0 on this path (its two
+// events are recorded back to back), and the plan figures are one workgroup and one pass per query.
+int search_ti_exact(vaqhip_index *ix, const float *d_queries, int nq, int k, int projected, int32_t *d_labels,
+                    float *d_dist, hipStream_t st) {
+  if (int rc = check_search_args(ix, d_queries, nq, k, d_labels, d_dist, nullptr)) return rc;
+  if (nq == 0) return VAQHIP_OK;
+  WS_SCOPE(ws, ix, st);
+  bool timing = ix->opt_timing != 0;
+  hipEvent_t *ev = nullptr;
+  if (timing) {
+    if (int rc = ensure_events(ix)) return rc;
+    if (ix->ev_used >= vaqhip_index::EV_SETS) timing = false;  // ring full: stop recording
+    else ev = ix->ev.data() + (size_t)ix->ev_used * 6;
+  }
+  const int chunk = std::min(nq, QUERY_CHUNK);
+  if (timing && nq > chunk) return fail(VAQHIP_EUNSUPPORTED, "timing supports at most %d queries per call", QUERY_CHUNK);
+  const int T = ix->ti_T;
+  const bool do_project = !projected && ix->has_eig;
+  if (do_project) HIP_TRY(ix->w_qproj.ensure((size_t)chunk * ix->D * sizeof(float)));
+  HIP_TRY(ix->w_lut.ensure((size_t)chunk * ix->lut_floats * sizeof(float)));
+  HIP_TRY(ix->w_ti_order.ensure((size_t)chunk * T * sizeof(int)));
+  HIP_TRY(ix->w_ti_qcc.ensure((size_t)chunk * T * sizeof(float)));
+  HIP_TRY(ix->w_ti_nvisit.ensure((size_t)chunk * sizeof(int)));
+  if (int rc = ensure_ti_walk(ix, st)) return rc;
+  const int max_visit = ix->ti_visit < 1.0f ? (int)((float)T * ix->ti_visit) : T;  // VAQ.cpp:1548-1551
+  for (int q0 = 0; q0 < nq; q0 += chunk) {
+    const int n = std::min(chunk, nq - q0);
+    const float *qp = d_queries + (size_t)q0 * ix->D;
+    if (timing) HIP_TRY(hipEventRecord(ev[0], st));
+    if (do_project) {
+      HIP_TRY(vaq::launch_project(qp, n, ix->D, ix->d_eig.as<float>(), ix->w_qproj.as<float>(), st, 0));
+      qp = ix->w_qproj.as<float>();
+    }
+    if (timing) HIP_TRY(hipEventRecord(ev[1], st));
+    HIP_TRY(vaq::launch_lut_build(qp, n, ix->D, ix->M, ix->L, ix->d_sub.as<vaq::SubDesc>(), ix->d_cent_t.as<float>(),
+                                  ix->lut_floats, 1 << ix->max_bits, ix->w_lut.as<float>(), st, 1 << ix->min_bits));
+    if (timing) HIP_TRY(hipEventRecord(ev[2], st));
+    HIP_TRY(vaq::launch_ti_plan(qp, n, ix->D, ix->ti_seg * ix->L, ix->d_ti_clusters_t.as<float>(), T,
+                                ix->d_bstart.as<int>(), max_visit, k, ix->w_ti_order.as<int>(), ix->w_ti_qcc.as<float>(),
+                                ix->w_ti_nvisit.as<int>(), st, 1));
+    if (timing) HIP_TRY(hipEventRecord(ev[3], st));
+    HIP_TRY(vaq::launch_ti_exact_replay(ix->d_codes.as<uint32_t>(), ix->layout, ix->M, ix->W, ix->d_sub.as<vaq::SubDesc>(),
+                                        ix->d_perm.as<uint32_t>(), ix->d_ti_walk.as<uint32_t>(), ix->d_bstart.as<int>(),
+                                        ix->d_ti_xcc.as<float>(), T, ix->w_ti_order.as<int>(), ix->w_ti_qcc.as<float>(),
+                                        ix->w_ti_nvisit.as<int>(), (ix->methods & VAQHIP_METHOD_EA) ? 1 : 0,
+                                        ix->w_lut.as<float>(), ix->lut_floats, n, k, ix->id_base,
+                                        d_labels + (size_t)q0 * k, d_dist + (size_t)q0 * k, st));
+    if (timing) {
+      HIP_TRY(hipEventRecord(ev[4], st));
+      HIP_TRY(hipEventRecord(ev[5], st));
+    }
+  }
+  vaqhip_timing tm = {};
+  tm.deferred_queries = -1;
+  tm.queries_per_pass = 1;
+  tm.slices = 1;
+  tm.workgroups = std::min(nq, chunk);
+  tm.passes = std::min(nq, chunk);
+  ix->last = tm;
+  if (timing) ix->ev_used++;
+  return ws.finish();
+}
+
 // Option "exact_ties": the scan runs with k + 1; queries whose k + 1 smallest distances are distinct
 // have a unique answer and are copied out, the others are replayed through the reference's heap in
 // original row order (vaq_exact.hip).  One internal launch set (<= QUERY_CHUNK queries) at a time: the
@@ -586,6 +662,8 @@ int ensure_inverse_perm(vaqhip_index *ix, hipStream_t st) {
 int search_device_locked(vaqhip_index *ix, const float *d_queries, int nq, int k, int projected,
                          int32_t *d_labels, float *d_dist, hipStream_t st) {
   if (fast_only(ix)) return search_fast(ix, d_queries, nq, k, projected, d_labels, d_dist, st);
+  if (ix->opt_exact && !ix->sharded && ix->ti_T > 0 && (ix->methods & VAQHIP_METHOD_TI))
+    return search_ti_exact(ix, d_queries, nq, k, projected, d_labels, d_dist, st);
   const bool exact =ix->opt_exact && ix->ti_T == 0 && nq > 0 && k > 0 && k < VAQHIP_MAX_K && ix->N >= 0 &&
                      d_queries && d_labels && d_dist;
   if (!exact) return search_core(ix, d_queries, nq, k, projected, d_labels, d_dist, st);
@@ -701,6 +779,12 @@ int vaqhip_internal_exact_applies(vaqhip_index *ix, int k) {
   if (!ix) return 0;
   std::lock_guard<std::mutex> lk(ix->mu);
   return ix->opt_exact && !fast_only(ix) && ix->ti_T == 0 && k > 0 && k < VAQHIP_MAX_K ? 1 : 0;
+}
+
+void vaqhip_internal_set_sharded(vaqhip_index *ix, int sharded) {
+  if (!ix) return;
+  std::lock_guard<std::mutex> lk(ix->mu);
+  ix->sharded = sharded != 0;
 }
 
 int vaqhip_internal_exact_state_words(vaqhip_index *ix, int k) {

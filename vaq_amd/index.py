@@ -468,6 +468,11 @@ class VaqHip:
         self._method_sig = None
 
     def set_option(self, key: str, value: int) -> None:
+        """vaqhip_set_option (include/vaqhip.h lists the options).  "exact_ties" = 1: labels and distances
+        identical to VAQ::search's slot for slot -- HEAP / EA through the reference's heap (k < 1024), and on
+        a TI index (mTIClusters set, methods TI and TI | EA, any mVisit, k <= 1024) every query is a replay
+        of VAQ::searchTriangleInequality over the cluster order and the member order libstdc++'s std::sort
+        leaves, NaN centres included."""
         self._ensure_index()
         _lib.check(_lib.load().vaqhip_set_option(self._h, key.encode(), int(value)))
 
@@ -609,8 +614,10 @@ class VaqHipMulti:
         reference's heap as a chain from shard to shard (k * 8 bytes per tied query per shard boundary;
         "exact_batch" = list entries per batch of that chain, 0 = automatic).  On sequential-sum shards
         the answer is BitVecEngine::queryLUT's: the chain hands on its std heap of k + 1 pairs, the heap's
-        length and bsfK, (k + 2) * 8 bytes per tied query per shard boundary.  No effect with
-        TI and k = 1024, as on a single index."""
+        length and bsfK, (k + 2) * 8 bytes per tied query per shard boundary.  No effect at
+        k = 1024, and none with TI on several shards (on ONE index the option replays the reference's walk;
+        a cluster's member order is one std::sort over rows of all shards and does not decompose into a
+        chain)."""
         _lib.check_multi(_lib.load().vaqhip_multi_set_option(self._h, key.encode(), int(value)))
 
     def set_method(self, methods: int, visit: float = 1.0) -> None:
