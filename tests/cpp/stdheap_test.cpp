@@ -1,4 +1,4 @@
-// stdheap_test.cpp -- vaq::stdheap (vaq_amd/csrc/vaq_fast.h) against the real libstdc++ std::push_heap /
+// stdheap_test.cpp -- vaq::stdheap (vaq_amd/csrc/vaq_restated.h) against the real libstdc++ std::push_heap /
 // std::pop_heap / std::sort_heap on the host.  BitVecEngine::queryLUT (BitVecEngine.hpp:1282-1317) keeps its k
 // best in a std::vector<IdxDistPairFloat> under those functions with a distance-only comparator, so where equal
 // distances end up is part of its answer; the restatement works on two arrays (dist, idx) and must agree with the
@@ -19,7 +19,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "vaq_fast.h"
+#include "vaq_restated.h"
 
 struct IdxDistPairFloat {  // the element of queryLUT's vector
   int idx;

@@ -1,4 +1,4 @@
-// stdsort_generic_test.cpp -- vaq::stdsort::sort_by (vaq_amd/csrc/vaq_fast.h) under the two comparators of
+// stdsort_generic_test.cpp -- vaq::stdsort::sort_by (vaq_amd/csrc/vaq_restated.h) under the two comparators of
 // option "exact_ties" on TI indexes, against the real libstdc++ std::sort on the host, element for element:
 //   mode 0  VAQ::clusterTI's member sort (VAQ.cpp:973-979): row numbers 0..n-1, comparator key[i] > key[j]
 //   mode 1  the cluster order of VAQ::search's TI branch (VAQ.cpp:815-820): ints 0..n-1, comparator
@@ -22,7 +22,7 @@
 #include <cstdlib>
 #include <vector>
 
-#include "vaq_fast.h"
+#include "vaq_restated.h"
 
 static int32_t read_i32(FILE *f) {
   int32_t v;

@@ -4,7 +4,7 @@ outputs of the loop run over the real libstdc++ heap functions, and a digest of 
 
 The loop keeps its k best in a std::vector under std::push_heap / std::pop_heap / std::sort_heap with the
 comparator a.dist < b.dist: bits/stl_heap.h's __push_heap and __adjust_heap, restated below as they are in
-vaq_amd/csrc/vaq_fast.h (namespace stdheap)."""
+vaq_amd/csrc/vaq_restated.h (namespace stdheap)."""
 import hashlib
 import os
 

@@ -1,7 +1,8 @@
 """The CPU side of option "exact_ties" on sequential-sum (BitVecEngine::queryLUT) indexes: the restatements
-of libstdc++'s heap functions -- vaq::stdheap in vaq_amd/csrc/vaq_fast.h, which the replay kernel runs, and
+of libstdc++'s heap functions -- vaq::stdheap in vaq_amd/csrc/vaq_restated.h, which the replay kernel runs, and
 seq_exact_ref's Python one -- against the real functions, and against the fixtures under
-tests/golden/seq_exact/ (recorded from the loop of BitVecEngine.hpp:1282-1317 over the real functions)."""
+tests/golden/seq_exact/ (recorded from the loop of BitVecEngine.hpp:1282-1317 over the real functions).  Beside them the reference's own
+heap, vaq::refheap in the same header (byte-code and TI indexes), against the oracle's."""
 import functools
 import os
 import shutil
@@ -116,3 +117,35 @@ def test_stdheap_restatements_match_libstdcxx(tmp_path):
         assert np.array_equal(lab[:m], want) and np.all(lab[m:] == -1), (n, k)
         assert np.array_equal(dis[:m], keys[want]) and np.all(np.diff(dis[:m]) >= 0), (n, k)
     assert at == ids.size
+
+
+def test_refheap_restatement_matches_the_oracle_heap(tmp_path):
+    """vaq::refheap (built for the host) against vo_heap_* of oracle/vaq_oracle.c, slot for slot after every call of
+    heapify, VAQ::searchHeap's loop and reorder (tests/cpp/refheap_test.cpp): ties and n < k (neutral entries
+    dropped by reorder) included.  Run once more under AddressSanitizer + UBSan (host code only, its own main)."""
+    seqs = heap_sequences()
+    assert {n for n, _, _ in seqs} == {1, 2, 3, 16, 17, 101, 1024, 1025}
+    for n in (1, 2, 3, 16, 17, 101, 1024, 1025):
+        assert {1, max(1, n - 1), n, n + 1} <= {k for m, k, _ in seqs if m == n}
+    assert any(n < k and len(np.unique(keys)) < n for n, k, keys in seqs)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cxx, cc = shutil.which("g++"), shutil.which("gcc")
+    assert cxx and cc
+    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
+    with open(str(tmp_path / "in.bin"), "wb") as f:
+        np.array([len(seqs)], np.int32).tofile(f)
+        for n, k, keys in seqs:
+            np.array([n, k], np.int32).tofile(f)
+            keys.tofile(f)
+    for extra, name in ((["-O2"], "refheap_test"),
+                        (["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "refheap_asan")):
+        obj = str(tmp_path / (name + "_oracle.o"))
+        subprocess.check_call([cc, "-std=c11", "-g", "-ffp-contract=off"] + extra +
+                              ["-c", os.path.join(root, "oracle", "vaq_oracle.c"), "-o", obj])
+        exe = str(tmp_path / name)
+        subprocess.check_call([cxx, "-std=c++17", "-g", "-D__HIP_PLATFORM_AMD__", "-I" + os.path.join(rocm, "include"),
+                               "-I" + os.path.join(root, "vaq_amd", "csrc"), "-I" + os.path.join(root, "oracle")] + extra +
+                              [os.path.join(root, "tests", "cpp", "refheap_test.cpp"), obj, "-lm", "-o", exe])
+        r = subprocess.run([exe, str(tmp_path / "in.bin")], capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, (r.stdout + r.stderr)[-2000:]
+        assert f"refheap_test: ok ({len(seqs)} sequences)" in r.stdout

@@ -1,7 +1,7 @@
 """Option "exact_ties" on sequential-sum indexes (VaqHip(sequential_sum=True), the reference's
 BitVecEngine::queryLUT): labels and distances identical to queryLUT's slot for slot, also where rows tie --
 its choice among equal distances comes from libstdc++'s heap functions over k + 1 pairs
-(BitVecEngine.hpp:1282-1317), replayed on the GPU (vaq_amd/csrc/vaq_exact.hip, vaq_fast.h stdheap).
+(BitVecEngine.hpp:1282-1317), replayed on the GPU (vaq_amd/csrc/vaq_exact.hip, vaq_restated.h stdheap).
 
 Checked with plain array_equal on labels and bit equality on distances against the fixtures under
 tests/golden/seq_exact/ (recorded from the loop over the real std::push_heap / pop_heap / sort_heap) and

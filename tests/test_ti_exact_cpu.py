@@ -1,7 +1,7 @@
 """Option "exact_ties" on TI indexes, the parts that need no GPU: the fixtures under tests/golden/ti_exact/
 belong to the inputs tests/ti_exact_ref.py regenerates, the tie-heavy cases really separate the reference's
 visiting order from the stable one (what makes tests/test_ti_exact_gpu.py fail without the feature), and the
-generalised std::sort restatement (vaq::stdsort::sort_by, vaq_fast.h) equals libstdc++'s std::sort under the
+generalised std::sort restatement (vaq::stdsort::sort_by, vaq_restated.h) equals libstdc++'s std::sort under the
 two comparators the feature sorts by."""
 import os
 import shutil

@@ -22,6 +22,7 @@ API_HEADER = os.path.join(ROOT, "include", "vaqhip.h")
 SCAN_HEADER = os.path.join(CSRC, "vaq_scan.h")
 SCAN_BF_HEADER = os.path.join(CSRC, "vaq_scan_bf.h")
 FAST_HEADER = os.path.join(CSRC, "vaq_fast.h")
+RESTATED_HEADER = os.path.join(CSRC, "vaq_restated.h")  # stdsort, stdheap, refheap: FAST, TI planning, the replay
 INTERNAL_HEADER = os.path.join(CSRC, "vaqhip_internal.h")
 INDEX_HEADER = os.path.join(CSRC, "vaqhip_index.h")  # private to the single-index host files
 DEV_HEADER = os.path.join(CSRC, "vaqhip_dev.h")      # DevBuf, DeviceGuard: both hosts and the scratch allocators
@@ -43,8 +44,10 @@ def _deps(src: str):
         deps.append(SCAN_HEADER)
     if src in ("vaq_kernels.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip"):
         deps.append(SCAN_BF_HEADER)
-    if src in ("vaq_fast.hip", "vaqhip_fast.cpp", "vaq_exact.hip", "vaq_ti.hip"):
+    if src in ("vaq_fast.hip", "vaqhip_fast.cpp"):
         deps.append(FAST_HEADER)
+    if src in ("vaq_fast.hip", "vaqhip_fast.cpp", "vaq_exact.hip", "vaq_ti.hip"):
+        deps.append(RESTATED_HEADER)
     return deps
 OBJDIR = os.path.join(LIBDIR, "obj")
 # Experiment builds: VAQ_VARIANT=name compiles (with VAQ_EXTRA_FLAGS) into vaq_amd/lib/variants/name/

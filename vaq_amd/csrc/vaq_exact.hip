@@ -27,8 +27,9 @@
 // (the state travels), and writes the raw heap out again; exact_finish_kernel runs heap_reorder on the
 // state the last shard left.  The bucket-bound skip and the early abandon test against a top that is
 // never below the reference's at that row -- the inherited top IS the reference's top there.
-// The heap functions below are the reference's (utils/Heap.hpp), statement for statement, as restated
-// in oracle/vaq_oracle.c -- which is pinned against the compiled reference heap (tests/test_oracle_golden.py).
+// The heap functions are the reference's (utils/Heap.hpp), statement for statement: refheap:: in
+// vaq_restated.h, pinned on the CPU against oracle/vaq_oracle.c's (tests/cpp/refheap_test.cpp) -- which is
+// pinned against the compiled reference heap (tests/test_oracle_golden.py).
 //
 // Sequential-sum indexes (BitVecEngine::queryLUT, BitVecEngine.hpp:1282-1317) keep their k best under
 // libstdc++'s heap functions instead: with pairs empty and bsfK = FLT_MAX, row i (ORIGINAL order, dist the
@@ -36,11 +37,11 @@
 // std::pop_heap + pop_back + bsfK = front().dist; std::sort_heap at the end.  The first k rows enter
 // unconditionally, row k meets a full heap (k + 1 slots are needed), i is the row's position in the WHOLE
 // database.  The same pipeline replays it (template argument SEQ): the heap is k + 1 pairs under
-// stdheap:: (vaq_fast.h, pinned against the real functions by tests/cpp/stdheap_test.cpp), the state of a
+// stdheap:: (vaq_restated.h, pinned against the real functions by tests/cpp/stdheap_test.cpp), the state of a
 // chain link is the raw heap, its length and bsfK, and the links count i from ExactParams::row0.  The
 // loop's partial-sum abandon only drops rows the test dist < bsfK drops (table entries are >= 0), so the
 // evaluating waves abandon and skip buckets against bsfK exactly as they do against the heap top.
-#include "vaq_fast.h"
+#include "vaq_restated.h"
 #include "vaq_scan.h"
 
 namespace vaq {
@@ -48,118 +49,93 @@ namespace vaq {
 constexpr int EX_THREADS = 512;
 constexpr int EX_CHUNK = 2048;  // rows per chunk (a multiple of 64)
 
-// utils/Heap.hpp:115-144 (1-based sift-down of the last element from the root; on equal children the
-// comparison is false, so the RIGHT child is taken)
-__device__ __forceinline__ void ex_heap_pop(const int k, float *val0, int *ids0) {
-  float *val = val0 - 1;
-  int *ids = ids0 - 1;
-  const float v = val[k];
-  int i = 1;
-  for (;;) {
-    const int i1 = i << 1, i2 = i1 + 1;
-    if (i1 > k) break;
-    if (i2 == k + 1 || val[i1] > val[i2]) {
-      if (v > val[i1]) break;
-      val[i] = val[i1];
-      ids[i] = ids[i1];
-      i = i1;
-    } else {
-      if (v > val[i2]) break;
-      val[i] = val[i2];
-      ids[i] = ids[i2];
-      i = i2;
-    }
+// the block's threads write query q's k output slots: the kept entries hval / hid[first, first + kept) with
+// id_add added to the ids, then the -1 / FLT_MAX tail
+__device__ __forceinline__ void ex_write_out(int32_t *labels, float *dist, const int q, const int k, const float *hval,
+                                             const int *hid, const int first, const int kept, const int64_t id_add,
+                                             const int tid, const int nthreads) {
+  for (int i = tid; i < k; i += nthreads) {
+    const bool ok = i < kept;
+    labels[(size_t)q * k + i] = ok ? (int32_t)(hid[first + i] + id_add) : -1;
+    dist[(size_t)q * k + i] = ok ? hval[first + i] : FLT_MAX;
   }
-  val[i] = val[k];
-  ids[i] = ids[k];
 }
 
-// utils/Heap.hpp:151-169 (sift-up from slot k)
-__device__ __forceinline__ void ex_heap_push(const int k, float *val0, int *ids0, const float v, const int id) {
-  float *val = val0 - 1;
-  int *ids = ids0 - 1;
-  int i = k;
-  while (i > 1) {
-    const int f = i >> 1;
-    if (!(v > val[f])) break;
-    val[i] = val[f];
-    ids[i] = ids[f];
-    i = f;
-  }
-  val[i] = v;
-  ids[i] = id;
+// heap_reorder by thread 0, then the output slots (the tail is refilled with FLT_MAX / -1).  Ends with the
+// block's threads past a barrier on *s_kept.
+__device__ __forceinline__ void ex_reorder_out(int32_t *labels, float *dist, const int q, const int k, float *hval,
+                                               int *hid, const int64_t id_add, int *s_kept, const int tid,
+                                               const int nthreads) {
+  if (tid == 0) *s_kept = refheap::reorder(k, hval, hid);
+  __syncthreads();
+  const int kept = *s_kept;
+  ex_write_out(labels, dist, q, k, hval, hid, k - kept, kept, id_add, tid, nthreads);
 }
 
-struct ExactParams {
-  const uint32_t *codes;
-  int layout, M, W;
-  const SubDesc *sub;
-  const uint32_t *inv;  // original row -> row of the bucketed order (nullptr = identity)
-  const unsigned short *row_bucket;  // original row -> its bucket (nullptr: no bucket pruning)
-  int n_buckets, bucket_shift, bucket_t;
-  int64_t n_rows;
-  const float *lut;     // [nq][lut_floats]
-  int lut_floats;
-  int lut_in_lds;
-  int seq;
-  int k;
-  int64_t id_base;
-  // the scan's result for k + 1
-  const int32_t *in_labels;  // [nq][k + 1]
-  const float *in_dist;
-  int32_t *labels;           // [nq][k]
-  float *dist;
-  int *list;                 // [nq] queries to replay
-  unsigned *count;
-  int nq;
-  // one link of a chain over shards (0: the single-index replay).  Entry e of the list keeps its heap at
-  // state[e * 2 * k]: k values, then k ids (global row numbers, -1 = neutral).  Sequential sum: at
-  // state[e * ex_state_words(k, 1)]: k + 1 values, k + 1 ids, the heap's length, bsfK.
-  int chain;
-  int64_t row0;              // sequential sum: position in the whole database of this index's row 0
-  int e0;                    // the launch covers list entries e0 .. e0 + grid - 1
-  const int32_t *state_in;   // nullptr: the neutral state (first shard)
-  int32_t *state_out;
-};
-
-// int32 words of one list entry's state in a chain
-__host__ __device__ inline int ex_state_words(int k, int seq) { return seq ? 2 * (k + 1) + 2 : 2 * k; }
-
-// heap_reorder (utils/Heap.hpp:322-349) by ONE thread: pop the maxima into the tail -> ascending; entries
-// of id -1 are dropped.  Returns the number kept: they sit in [k - kept, k).  (The memmove of the kept
-// entries to the front and the neutral tail are done by the copy that follows.)
-__device__ __forceinline__ int ex_heap_reorder(const int k, float *hval, int *hid) {
-  int ii = 0;
-  for (int i = 0; i < k; i++) {
-    const float v = hval[0];
-    const int id = hid[0];
-    ex_heap_pop(k - i, hval, hid);
-    hval[k - ii - 1] = v;
-    hid[k - ii - 1] = id;
-    if (id != -1) ii++;
-  }
-  return ii;
+// std::sort_heap (BitVecEngine.hpp:1316) by thread 0: ascending from slot 0; at most k pairs are left
+__device__ __forceinline__ void ex_sort_out(int32_t *labels, float *dist, const int q, const int k, float *hval, int *hid,
+                                            const int len, const int64_t id_add, const int tid, const int nthreads) {
+  if (tid == 0) stdheap::sort_heap(hval, hid, len);
+  __syncthreads();
+  ex_write_out(labels, dist, q, k, hval, hid, 0, len, id_add, tid, nthreads);
 }
 
-__global__ __launch_bounds__(256) void exact_flag_kernel(ExactParams p) {
+// A list entry's state in a chain (ExactParams::chain) into the heap's slots, by the block's threads; sin ==
+// nullptr: heap_heapify's neutral state (utils/Heap.hpp:211-235: FLT_MAX, ids -1; sequential sum: `pairs` empty
+// and bsfK = FLT_MAX, BitVecEngine.hpp:1287-1290 -- slots past the length are never read).
+template <bool SEQ>
+__device__ __forceinline__ void ex_state_load(const int32_t *sin, const int k, float *hval, int *hid, const int tid,
+                                              const int nthreads, int *len, float *bsf) {
+  const int hs = SEQ ? k + 1 : k;
+  for (int i = tid; i < hs; i += nthreads) {
+    hval[i] = sin ? bits_to_float((unsigned)sin[i]) : FLT_MAX;
+    hid[i] = sin ? sin[hs + i] : -1;
+  }
+  // (the clamp is defensive only: a length outside [0, k] can only come from a bug in an earlier link, and
+  //  it keeps such a bug from writing outside the heap's slots -- it does not make the answer right)
+  *len = SEQ && sin ? min(max(sin[2 * hs], 0), k) : 0;                      // pairs.size()
+  *bsf = SEQ && sin ? bits_to_float((unsigned)sin[2 * hs + 1]) : FLT_MAX;  // bsfK
+}
+
+// ... and the raw heap back out
+template <bool SEQ>
+__device__ __forceinline__ void ex_state_store(int32_t *sout, const int k, const float *hval, const int *hid,
+                                               const int tid, const int nthreads, const int len, const float bsf) {
+  const int hs = SEQ ? k + 1 : k;
+  for (int i = tid; i < hs; i += nthreads) {
+    sout[i] = (int32_t)float_to_bits(hval[i]);
+    sout[hs + i] = hid[i];
+  }
+  if (SEQ && tid == 0) {
+    sout[2 * hs] = len;
+    sout[2 * hs + 1] = (int32_t)float_to_bits(bsf);
+  }
+}
+
+__global__ __launch_bounds__(256) void exact_flag_kernel(const int nq, const int k, const int32_t *__restrict__ in_labels,
+                                                          const float *__restrict__ in_dist, int32_t *__restrict__ labels,
+                                                          float *__restrict__ dist, int *__restrict__ list,
+                                                          unsigned *__restrict__ count) {
   const int q = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (q >= p.nq) return;
-  const int k = p.k, k1 = k + 1;
-  const int32_t *il = p.in_labels + (size_t)q * k1;
-  const float *id = p.in_dist + (size_t)q * k1;
+  if (q >= nq) return;
+  const int k1 = k + 1;
+  const int32_t *il = in_labels + (size_t)q * k1;
+  const float *id = in_dist + (size_t)q * k1;
   bool tie = false;
   for (int i = lane; i < k; i += 64) {
     const int32_t a = il[i], b = il[i + 1];
     tie = tie || (a >= 0 && b >= 0 && id[i] == id[i + 1]);
-    p.labels[(size_t)q * k + i] = a;
-    p.dist[(size_t)q * k + i] = id[i];
+    labels[(size_t)q * k + i] = a;
+    dist[(size_t)q * k + i] = id[i];
   }
-  if (__ballot(tie) != 0ull && lane == 0) p.list[atomicAdd(p.count, 1u)] = q;
+  if (__ballot(tie) != 0ull && lane == 0) list[atomicAdd(count, 1u)] = q;
 }
 
-// complete sum of sorted row r in the reference's order (groups of four, VAQ.cpp:1737-1748),
-// abandoned (-> +inf) once a partial sum is no longer below t
-template <bool BYTES>
+// complete sum of sorted row r, abandoned (-> +inf) once a partial sum is no longer below t: in the
+// reference's order (groups of four, each added to the sum and tested, VAQ.cpp:1737-1748), or with SEQ the
+// sequential sum (BitVecEngine.hpp:1295-1300: dist += luts[code], column by column, tested after each as the
+// loop's own condition does)
+template <bool BYTES, bool SEQ>
 __device__ __forceinline__ float ex_row_dist(const ExactParams &p, const float *lut, const int64_t r, const float t) {
   float dist = 0.0f;
   if (BYTES) {
@@ -185,29 +161,16 @@ __device__ __forceinline__ float ex_row_dist(const ExactParams &p, const float *
     const uint32_t hi = d.word + 1 < W ? tp[(int64_t)(d.word + 1) * TILE_ROWS] : 0u;
     const uint32_t c = __builtin_amdgcn_alignbit(hi, lo, (unsigned)d.shift) & ((1u << d.bits) - 1u);
     const float l = lut[d.lut_off + c];
-    dism = (s & 3) == 0 ? l : dism + l;
-    if ((s & 3) == 3) {
-      dist = s == 3 ? dism : dist + dism;
+    if (SEQ) {
+      dist = s == 0 ? l : dist + l;
       if (!(dist < t)) return INFINITY;
+    } else {
+      dism = (s & 3) == 0 ? l : dism + l;
+      if ((s & 3) == 3) {
+        dist = s == 3 ? dism : dist + dism;
+        if (!(dist < t)) return INFINITY;
+      }
     }
-  }
-  return dist;
-}
-
-// the sequential sum of sorted row r (BitVecEngine.hpp:1295-1300: dist += luts[code], column by column),
-// abandoned (-> +inf) once a partial sum is no longer below t, as the loop's own condition does
-__device__ __forceinline__ float ex_row_dist_seq(const ExactParams &p, const float *lut, const int64_t r, const float t) {
-  const int W = p.W;
-  const uint32_t *tp = p.codes + (r / TILE_ROWS) * (int64_t)(TILE_ROWS * W) + (r % TILE_ROWS);
-  float dist = 0.0f;
-  for (int s = 0; s < p.M; s++) {
-    const SubDesc d = p.sub[s];
-    const uint32_t lo = tp[(int64_t)d.word * TILE_ROWS];
-    const uint32_t hi = d.word + 1 < W ? tp[(int64_t)(d.word + 1) * TILE_ROWS] : 0u;
-    const uint32_t c = __builtin_amdgcn_alignbit(hi, lo, (unsigned)d.shift) & ((1u << d.bits) - 1u);
-    const float l = lut[d.lut_off + c];
-    dist = s == 0 ? l : dist + l;
-    if (!(dist < t)) return INFINITY;
   }
   return dist;
 }
@@ -234,18 +197,11 @@ __global__ __launch_bounds__(EX_THREADS) void exact_replay_kernel(ExactParams p)
     for (int i = tid; i < p.lut_floats; i += EX_THREADS) lds_lut[i] = glut[i];
     lut = lds_lut;
   }
-  // heap_heapify (utils/Heap.hpp:211-235): neutral FLT_MAX, ids -1 -- or the heap the earlier shards left
-  // (sequential sum: `pairs` empty and bsfK = FLT_MAX, BitVecEngine.hpp:1287-1290 -- or what the earlier
-  //  shards left; slots past the length are never read)
-  const int32_t *sin = p.chain && p.state_in ? p.state_in + (size_t)e * ex_state_words(k, SEQ) : nullptr;
-  for (int i = tid; i < hs; i += EX_THREADS) {
-    hval[i] = sin ? bits_to_float((unsigned)sin[i]) : FLT_MAX;
-    hid[i] = sin ? sin[hs + i] : -1;
-  }
-  // (the clamp is defensive only: a length outside [0, k] can only come from a bug in an earlier link, and
-  //  it keeps such a bug from writing outside the heap's slots -- it does not make the answer right)
-  int len = SEQ && sin ? min(max(sin[2 * hs], 0), k) : 0;                      // pairs.size()
-  float bsf = SEQ && sin ? bits_to_float((unsigned)sin[2 * hs + 1]) : FLT_MAX;  // bsfK
+  // the neutral heap -- or the one the earlier shards left
+  const int32_t *sin = p.chain && p.state_in ? p.state_in + (size_t)e * exact_state_words(k, SEQ) : nullptr;
+  int len;    // pairs.size()
+  float bsf;  // bsfK
+  ex_state_load<SEQ>(sin, k, hval, hid, tid, EX_THREADS, &len, &bsf);
   // ids pushed: rows of this index (id_base is added on the way out), or global row numbers in a chain
   const int64_t push_base = p.chain ? p.id_base : 0;
   // the heap top after the last COMPLETE pop + push, for the evaluating waves (the root itself passes
@@ -313,7 +269,7 @@ __global__ __launch_bounds__(EX_THREADS) void exact_replay_kernel(ExactParams p)
         for (int i = 0; i < RPT; i++) {
           const int j = tid - 64 + i * (EX_THREADS - 64);
           if (j < EX_CHUNK)
-            out[j] = !live[i] ? INFINITY : SEQ ? ex_row_dist_seq(p, lut, src[i], t) : ex_row_dist<BYTES>(p, lut, src[i], t);
+            out[j] = !live[i] ? INFINITY : ex_row_dist<BYTES, SEQ>(p, lut, src[i], t);
         }
       }
     } else if (c > 0) {
@@ -359,8 +315,8 @@ __global__ __launch_bounds__(EX_THREADS) void exact_replay_kernel(ExactParams p)
             const float dv = bits_to_float((unsigned)__builtin_amdgcn_readlane((int)float_to_bits(d), src));
             if (top > dv) {  // if (heap_dis[0] > dist)
               if (lane == 0) {
-                ex_heap_pop(k, hval, hid);
-                ex_heap_push(k, hval, hid, dv, (int)(push_base + base + j0 + src));
+                refheap::pop(k, hval, hid);
+                refheap::push(k, hval, hid, dv, (int)(push_base + base + j0 + src));
                 __hip_atomic_store(&s_top, hval[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
               }
               wave_lds_sync();
@@ -386,38 +342,11 @@ __global__ __launch_bounds__(EX_THREADS) void exact_replay_kernel(ExactParams p)
   }
   if (p.chain) {
     // a link hands the raw heap on (the loop above ended with a barrier)
-    int32_t *sout = p.state_out + (size_t)e * ex_state_words(k, SEQ);
-    for (int i = tid; i < hs; i += EX_THREADS) {
-      sout[i] = (int32_t)float_to_bits(hval[i]);
-      sout[hs + i] = hid[i];
-    }
-    if (SEQ && tid == 0) {
-      sout[2 * hs] = len;
-      sout[2 * hs + 1] = (int32_t)float_to_bits(bsf);
-    }
+    ex_state_store<SEQ>(p.state_out + (size_t)e * exact_state_words(k, SEQ), k, hval, hid, tid, EX_THREADS, len, bsf);
     return;
   }
-  if (SEQ) {
-    // std::sort_heap (BitVecEngine.hpp:1316): ascending from slot 0; at most k pairs are left
-    if (tid == 0) stdheap::sort_heap(hval, hid, len);
-    __syncthreads();
-    for (int i = tid; i < k; i += EX_THREADS) {
-      const bool ok = i < len;
-      p.labels[(size_t)q * k + i] = ok ? (int32_t)(hid[i] + p.id_base) : -1;
-      p.dist[(size_t)q * k + i] = ok ? hval[i] : FLT_MAX;
-    }
-    return;
-  }
-  // heap_reorder; the tail is refilled with FLT_MAX / -1
-  if (tid == 0) reinterpret_cast<int *>(buf)[0] = ex_heap_reorder(k, hval, hid);
-  __syncthreads();
-  const int nel = reinterpret_cast<int *>(buf)[0];
-  for (int i = tid; i < k; i += EX_THREADS) {
-    const bool ok = i < nel;
-    const int id = ok ? hid[k - nel + i] : -1;
-    p.labels[(size_t)q * k + i] = ok ? (int32_t)(id + p.id_base) : -1;
-    p.dist[(size_t)q * k + i] = ok ? hval[k - nel + i] : FLT_MAX;
-  }
+  if (SEQ) ex_sort_out(p.labels, p.dist, q, k, hval, hid, len, p.id_base, tid, EX_THREADS);
+  else ex_reorder_out(p.labels, p.dist, q, k, hval, hid, p.id_base, reinterpret_cast<int *>(buf), tid, EX_THREADS);
 }
 
 // End of a chain: heap_reorder on the state the last shard left, into the caller's slots of the listed
@@ -433,34 +362,13 @@ __global__ __launch_bounds__(64) void exact_finish_kernel(const int32_t *__restr
   const int hs = SEQ ? k + 1 : k;
   float *hval = reinterpret_cast<float *>(ex_smem);
   int *hid = reinterpret_cast<int *>(hval + hs);
-  const int32_t *sin = state + (size_t)e * ex_state_words(k, SEQ);
-  for (int i = lane; i < hs; i += 64) {
-    hval[i] = bits_to_float((unsigned)sin[i]);
-    hid[i] = sin[hs + i];
-  }
+  int len;
+  float bsf;
+  ex_state_load<SEQ>(state + (size_t)e * exact_state_words(k, SEQ), k, hval, hid, lane, 64, &len, &bsf);
   __shared__ int s_nel;
   __syncthreads();
-  if (SEQ) {
-    // std::sort_heap on the pairs the last shard left: ascending from slot 0 (the clamp is defensive only,
-    // as in the replay kernel: the links never leave a length outside [0, k])
-    const int len = min(max(sin[2 * hs], 0), k);
-    if (lane == 0) stdheap::sort_heap(hval, hid, len);
-    __syncthreads();
-    for (int i = lane; i < k; i += 64) {
-      const bool ok = i < len;
-      labels[(size_t)q * k + i] = ok ? hid[i] : -1;
-      dist[(size_t)q * k + i] = ok ? hval[i] : FLT_MAX;
-    }
-    return;
-  }
-  if (lane == 0) s_nel = ex_heap_reorder(k, hval, hid);
-  __syncthreads();
-  const int nel = s_nel;
-  for (int i = lane; i < k; i += 64) {
-    const bool ok = i < nel;
-    labels[(size_t)q * k + i] = ok ? hid[k - nel + i] : -1;
-    dist[(size_t)q * k + i] = ok ? hval[k - nel + i] : FLT_MAX;
-  }
+  if (SEQ) ex_sort_out(labels, dist, q, k, hval, hid, len, 0, lane, 64);
+  else ex_reorder_out(labels, dist, q, k, hval, hid, 0, &s_nel, lane, 64);
 }
 
 // inv[original row] = row of the bucketed order; row_bucket[original row] = its bucket (optional)
@@ -490,133 +398,50 @@ hipError_t launch_inverse_perm(const uint32_t *perm, int64_t n, uint32_t *inv, c
   return hipGetLastError();
 }
 
-static hipError_t launch_replay(ExactParams &p, int grid, hipStream_t st) {
-  const int k = p.k;
-  if (p.seq && p.layout == LAYOUT_BYTES) return hipErrorInvalidValue;  // (sequential-sum rows are always bit-packed)
-  size_t lds = (size_t)(p.seq ? k + 1 : k) * 8 + (size_t)2 * EX_CHUNK * 4 + (p.row_bucket ? (size_t)p.n_buckets * 4 : 0);
-  p.lut_in_lds = (size_t)p.lut_floats * 4 + lds <= 96 * 1024 ? 1 : 0;
-  if (p.lut_in_lds) lds += (size_t)p.lut_floats * 4;
-  hipError_t e;
-  if (p.seq) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(exact_replay_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((exact_replay_kernel<false, true>), dim3(grid), dim3(EX_THREADS), lds, st, p);
-  } else if (p.layout == LAYOUT_BYTES) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(exact_replay_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((exact_replay_kernel<true, false>), dim3(grid), dim3(EX_THREADS), lds, st, p);
-  } else {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(exact_replay_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((exact_replay_kernel<false, false>), dim3(grid), dim3(EX_THREADS), lds, st, p);
-  }
+// a launch with dynamic LDS beyond the default limit
+template <class... P, class... A>
+static hipError_t launch_lds(void (*kernel)(P...), int grid, int threads, size_t lds, hipStream_t st, const A &...args) {
+  const hipError_t e =
+      hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(threads), lds, st, args...);
   return hipGetLastError();
 }
 
-// in_labels / in_dist: the scan's result for k + 1 per query; labels / dist: the caller's k per query
-hipError_t launch_exact_ties(const uint32_t *codes, int layout, int M, int W, const SubDesc *sub, const uint32_t *inv,
-                             const unsigned short *row_bucket, int n_buckets, int bucket_shift, int bucket_t,
-                             int64_t n_rows, const float *lut, int lut_floats, int seq, int nq, int k, int64_t id_base,
-                             const int32_t *in_labels, const float *in_dist, int32_t *labels, float *dist, int *list,
-                             unsigned *count, hipStream_t st) {
-  if (nq <= 0) return hipSuccess;
-  ExactParams p;
-  p.codes = codes;
-  p.layout = layout;
-  p.M = M;
-  p.W = W;
-  p.sub = sub;
-  p.inv = inv;
-  p.row_bucket = row_bucket;
-  p.n_buckets = n_buckets;
-  p.bucket_shift = bucket_shift;
-  p.bucket_t = bucket_t;
-  p.n_rows = n_rows;
-  p.lut = lut;
-  p.lut_floats = lut_floats;
-  p.seq = seq;
-  p.k = k;
-  p.id_base = id_base;
-  p.in_labels = in_labels;
-  p.in_dist = in_dist;
-  p.labels = labels;
-  p.dist = dist;
-  p.list = list;
-  p.count = count;
-  p.nq = nq;
-  p.chain = 0;
-  p.row0 = 0;
-  p.e0 = 0;
-  p.state_in = nullptr;
-  p.state_out = nullptr;
-  hipError_t e = hipMemsetAsync(count, 0, sizeof(unsigned), st);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(exact_flag_kernel, dim3((nq + 3) / 4), dim3(256), 0, st, p);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
-  return launch_replay(p, nq, st);
+// `fixed` bytes of LDS, plus the query's lookup tables if both fit in 96 KiB (*lut_in_lds)
+static size_t lds_with_tables(size_t fixed, int lut_floats, int *lut_in_lds) {
+  const size_t tables = (size_t)lut_floats * 4;
+  *lut_in_lds = tables + fixed <= 96 * 1024 ? 1 : 0;
+  return *lut_in_lds ? fixed + tables : fixed;
 }
 
 hipError_t launch_exact_flag(int nq, int k, const int32_t *in_labels, const float *in_dist, int32_t *labels, float *dist,
                              int *list, unsigned *count, hipStream_t st) {
   if (nq <= 0) return hipSuccess;
-  ExactParams p = {};
-  p.k = k;
-  p.in_labels = in_labels;
-  p.in_dist = in_dist;
-  p.labels = labels;
-  p.dist = dist;
-  p.list = list;
-  p.count = count;
-  p.nq = nq;
   hipError_t e = hipMemsetAsync(count, 0, sizeof(unsigned), st);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(exact_flag_kernel, dim3((nq + 3) / 4), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(exact_flag_kernel, dim3((nq + 3) / 4), dim3(256), 0, st, nq, k, in_labels, in_dist, labels, dist, list,
+                     count);
   return hipGetLastError();
 }
 
-hipError_t launch_exact_link(const uint32_t *codes, int layout, int M, int W, const SubDesc *sub, const uint32_t *inv,
-                             const unsigned short *row_bucket, int n_buckets, int bucket_shift, int bucket_t,
-                             int64_t n_rows, const float *lut, int lut_floats, int seq, int64_t row0, int k,
-                             int64_t id_base, const int *list, const unsigned *count, int e0, int n_entries,
-                             const int32_t *state_in, int32_t *state_out, hipStream_t st) {
+hipError_t launch_exact_replay(const ExactParams &params, int n_entries, hipStream_t st) {
   if (n_entries <= 0) return hipSuccess;
-  ExactParams p = {};
-  p.codes = codes;
-  p.layout = layout;
-  p.M = M;
-  p.W = W;
-  p.sub = sub;
-  p.inv = inv;
-  p.row_bucket = row_bucket;
-  p.n_buckets = n_buckets;
-  p.bucket_shift = bucket_shift;
-  p.bucket_t = bucket_t;
-  p.n_rows = n_rows;
-  p.lut = lut;
-  p.lut_floats = lut_floats;
-  p.seq = seq;
-  p.row0 = row0;
-  p.k = k;
-  p.id_base = id_base;
-  p.list = const_cast<int *>(list);
-  p.count = const_cast<unsigned *>(count);
-  p.chain = 1;
-  p.e0 = e0;
-  p.state_in = state_in;
-  p.state_out = state_out;
-  return launch_replay(p, n_entries, st);
+  ExactParams p = params;
+  if (p.seq && p.layout == LAYOUT_BYTES) return hipErrorInvalidValue;  // (sequential-sum rows are always bit-packed)
+  const size_t lds = lds_with_tables((size_t)(p.seq ? p.k + 1 : p.k) * 8 + (size_t)2 * EX_CHUNK * 4 +
+                                         (p.row_bucket ? (size_t)p.n_buckets * 4 : 0),
+                                     p.lut_floats, &p.lut_in_lds);
+  if (p.seq) return launch_lds(exact_replay_kernel<false, true>, n_entries, EX_THREADS, lds, st, p);
+  if (p.layout == LAYOUT_BYTES) return launch_lds(exact_replay_kernel<true, false>, n_entries, EX_THREADS, lds, st, p);
+  return launch_lds(exact_replay_kernel<false, false>, n_entries, EX_THREADS, lds, st, p);
 }
 
 hipError_t launch_exact_finish(const int32_t *state, const int *list, const unsigned *count, int n_entries, int seq, int k,
                                int32_t *labels, float *dist, hipStream_t st) {
   if (n_entries <= 0) return hipSuccess;
-  if (seq)
-    hipLaunchKernelGGL(exact_finish_kernel<true>, dim3(n_entries), dim3(64), (size_t)(k + 1) * 8, st, state, list, count, k,
-                       labels, dist);
-  else
-    hipLaunchKernelGGL(exact_finish_kernel<false>, dim3(n_entries), dim3(64), (size_t)k * 8, st, state, list, count, k,
-                       labels, dist);
-  return hipGetLastError();
+  if (seq) return launch_lds(exact_finish_kernel<true>, n_entries, 64, (size_t)(k + 1) * 8, st, state, list, count, k, labels, dist);
+  return launch_lds(exact_finish_kernel<false>, n_entries, 64, (size_t)k * 8, st, state, list, count, k, labels, dist);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -650,19 +475,6 @@ hipError_t launch_exact_finish(const int32_t *state, const int *list, const unsi
 // past whole chunks they are not evaluated at all.
 constexpr int TIX_THREADS = 512;
 constexpr int TIX_CHUNK = 1024;  // walk positions per chunk (a multiple of 64)
-
-struct TiExactParams {
-  ExactParams x;  // codes, layout, M, W, sub, lut, lut_floats, lut_in_lds, k, id_base, labels, dist
-  const uint32_t *perm;  // index row -> original row
-  const uint32_t *walk;  // position in the reference's member order -> index row
-  const int *start;      // [T + 1] first index row of each cluster
-  const float *xcc;      // mCodeToCCDist by index row
-  int T;
-  const int *order;      // [nq][T]
-  const float *qcc;      // [nq][T], in `order`'s order
-  const int *nvisit;     // [nq]
-  int ea;
-};
 
 // what the evaluating waves may test against (above)
 __device__ __forceinline__ void tix_publish(float *s_bsfk, float *s_bsf2, const float bsfK, const float bsf2) {
@@ -760,7 +572,7 @@ __global__ __launch_bounds__(TIX_THREADS) void ti_exact_replay_kernel(TiExactPar
             bv = qcc[lo] - tp.xcc[row];
             lab = (int)tp.perm[row];
             const bool uncond = w < k;
-            if (uncond || !(tk <= bv)) dv = ex_row_dist<BYTES>(p, lut, row, uncond ? INFINITY : t2);
+            if (uncond || !(tk <= bv)) dv = ex_row_dist<BYTES, false>(p, lut, row, uncond ? INFINITY : t2);
           }
           od[j] = dv;
           ob[j] = bv;
@@ -786,8 +598,8 @@ __global__ __launch_bounds__(TIX_THREADS) void ti_exact_replay_kernel(TiExactPar
             const int lb = __builtin_amdgcn_readlane(lab, w1 - g0);
             const float r = sqrtf(dv);
             if (lane == 0) {
-              ex_heap_pop(k, hval, hid);
-              ex_heap_push(k, hval, hid, r, lb);
+              refheap::pop(k, hval, hid);
+              refheap::push(k, hval, hid, r, lb);
             }
             if (r > bsfK) {
               bsfK = r;
@@ -820,8 +632,8 @@ __global__ __launch_bounds__(TIX_THREADS) void ti_exact_replay_kernel(TiExactPar
             const float dv = bits_to_float((unsigned)__builtin_amdgcn_readlane((int)float_to_bits(d), fa));
             const int lb = __builtin_amdgcn_readlane(lab, fa);
             if (lane == 0) {
-              ex_heap_pop(k, hval, hid);
-              ex_heap_push(k, hval, hid, sqrtf(dv), lb);
+              refheap::pop(k, hval, hid);
+              refheap::push(k, hval, hid, sqrtf(dv), lb);
             }
             wave_lds_sync();
             bsfK = hval[0];
@@ -840,63 +652,17 @@ __global__ __launch_bounds__(TIX_THREADS) void ti_exact_replay_kernel(TiExactPar
     pc = ec;
     ec = max(ec + 1, cc / TIX_CHUNK);
   }
-  // heap_reorder; the tail is refilled with FLT_MAX / -1
   __shared__ int s_nel;
-  if (tid == 0) s_nel = ex_heap_reorder(k, hval, hid);
-  __syncthreads();
-  const int nel = s_nel;
-  for (int i = tid; i < k; i += TIX_THREADS) {
-    const bool ok = i < nel;
-    const int id = ok ? hid[k - nel + i] : -1;
-    p.labels[(size_t)q * k + i] = ok ? (int32_t)(id + p.id_base) : -1;
-    p.dist[(size_t)q * k + i] = ok ? hval[k - nel + i] : FLT_MAX;
-  }
+  ex_reorder_out(p.labels, p.dist, q, k, hval, hid, p.id_base, &s_nel, tid, TIX_THREADS);
 }
 
-hipError_t launch_ti_exact_replay(const uint32_t *codes, int layout, int M, int W, const SubDesc *sub,
-                                  const uint32_t *perm, const uint32_t *walk, const int *start, const float *xcc_sorted,
-                                  int T, const int *order, const float *qcc, const int *nvisit, int ea,
-                                  const float *lut, int lut_floats, int nq, int k, int64_t id_base, int32_t *labels,
-                                  float *dist, hipStream_t st) {
+hipError_t launch_ti_exact_replay(const TiExactParams &params, int nq, hipStream_t st) {
   if (nq <= 0) return hipSuccess;
-  TiExactParams tp = {};
-  tp.x.codes = codes;
-  tp.x.layout = layout;
-  tp.x.M = M;
-  tp.x.W = W;
-  tp.x.sub = sub;
-  tp.x.lut = lut;
-  tp.x.lut_floats = lut_floats;
-  tp.x.k = k;
-  tp.x.id_base = id_base;
-  tp.x.labels = labels;
-  tp.x.dist = dist;
-  tp.x.nq = nq;
-  tp.perm = perm;
-  tp.walk = walk;
-  tp.start = start;
-  tp.xcc = xcc_sorted;
-  tp.T = T;
-  tp.order = order;
-  tp.qcc = qcc;
-  tp.nvisit = nvisit;
-  tp.ea = ea;
-  size_t lds = (size_t)k * 8 + (size_t)6 * TIX_CHUNK * 4 + (size_t)(T + 1) * 4;
-  tp.x.lut_in_lds = (size_t)lut_floats * 4 + lds <= 96 * 1024 ? 1 : 0;
-  if (tp.x.lut_in_lds) lds += (size_t)lut_floats * 4;
-  hipError_t e;
-  if (layout == LAYOUT_BYTES) {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(ti_exact_replay_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((ti_exact_replay_kernel<true>), dim3(nq), dim3(TIX_THREADS), lds, st, tp);
-  } else {
-    e = hipFuncSetAttribute(reinterpret_cast<const void *>(ti_exact_replay_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((ti_exact_replay_kernel<false>), dim3(nq), dim3(TIX_THREADS), lds, st, tp);
-  }
-  return hipGetLastError();
+  TiExactParams tp = params;
+  const size_t lds = lds_with_tables((size_t)tp.x.k * 8 + (size_t)6 * TIX_CHUNK * 4 + (size_t)(tp.T + 1) * 4,
+                                     tp.x.lut_floats, &tp.x.lut_in_lds);
+  if (tp.x.layout == LAYOUT_BYTES) return launch_lds(ti_exact_replay_kernel<true>, nq, TIX_THREADS, lds, st, tp);
+  return launch_lds(ti_exact_replay_kernel<false>, nq, TIX_THREADS, lds, st, tp);
 }
-
-int exact_state_words(int k, int seq) { return ex_state_words(k, seq); }
 
 } // namespace vaq

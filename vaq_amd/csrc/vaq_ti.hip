@@ -7,8 +7,8 @@
 // Compiled with -ffp-contract=off like every file of the library: distances
 // are the reference's  res += tmp * tmp  (utils/Math.hpp:8-19), multiply and
 // add unfused, or its SSE orders for d in {1,2,4,8,12} (:38-128).
-#include "vaq_fast.h"
 #include "vaq_kernels.h"
+#include "vaq_restated.h"
 #include "vaqhip_dev.h"
 
 #include <algorithm>

@@ -178,6 +178,29 @@ vaq::ScanParams base_scan_params(const vaqhip_index *ix, const Plan &pl, int n, 
   return sp;
 }
 
+// the index as the replay of option "exact_ties" sees it (vaq_exact.hip) and the tables of the launch set in
+// flight; a caller adds its output, or its list and chain fields
+vaq::ExactParams exact_params(const vaqhip_index *ix, int k) {
+  vaq::ExactParams p = {};
+  p.codes = ix->d_codes.as<uint32_t>();
+  p.layout = ix->layout;
+  p.M = ix->M;
+  p.W = ix->W;
+  p.sub = ix->d_sub.as<vaq::SubDesc>();
+  p.inv = ix->d_inv.as<uint32_t>();
+  p.row_bucket = ix->N > 0 ? ix->d_rowbucket.as<unsigned short>() : nullptr;
+  p.n_buckets = ix->n_buckets;
+  p.bucket_shift = ix->bucket_shift;
+  p.bucket_t = ix->bucket_t;
+  p.n_rows = ix->N;
+  p.lut = ix->w_lut.as<float>();
+  p.lut_floats = ix->lut_floats;
+  p.seq = ix->seq;
+  p.k = k;
+  p.id_base = ix->id_base;
+  return p;
+}
+
 #if defined(VAQ_STATS) || defined(VAQ_PHASES)
 int attach_stats(vaq::ScanParams &sp, hipStream_t st) {
   static unsigned long long *d_stats = nullptr;
@@ -633,12 +656,20 @@ int search_ti_exact(vaqhip_index *ix, const float *d_queries, int nq, int k, int
                                 ix->d_bstart.as<int>(), max_visit, k, ix->w_ti_order.as<int>(), ix->w_ti_qcc.as<float>(),
                                 ix->w_ti_nvisit.as<int>(), st, 1));
     if (timing) HIP_TRY(hipEventRecord(ev[3], st));
-    HIP_TRY(vaq::launch_ti_exact_replay(ix->d_codes.as<uint32_t>(), ix->layout, ix->M, ix->W, ix->d_sub.as<vaq::SubDesc>(),
-                                        ix->d_perm.as<uint32_t>(), ix->d_ti_walk.as<uint32_t>(), ix->d_bstart.as<int>(),
-                                        ix->d_ti_xcc.as<float>(), T, ix->w_ti_order.as<int>(), ix->w_ti_qcc.as<float>(),
-                                        ix->w_ti_nvisit.as<int>(), (ix->methods & VAQHIP_METHOD_EA) ? 1 : 0,
-                                        ix->w_lut.as<float>(), ix->lut_floats, n, k, ix->id_base,
-                                        d_labels + (size_t)q0 * k, d_dist + (size_t)q0 * k, st));
+    vaq::TiExactParams tp = {};
+    tp.x = exact_params(ix, k);
+    tp.x.labels = d_labels + (size_t)q0 * k;
+    tp.x.dist = d_dist + (size_t)q0 * k;
+    tp.perm = ix->d_perm.as<uint32_t>();
+    tp.walk = ix->d_ti_walk.as<uint32_t>();
+    tp.start = ix->d_bstart.as<int>();
+    tp.xcc = ix->d_ti_xcc.as<float>();
+    tp.T = T;
+    tp.order = ix->w_ti_order.as<int>();
+    tp.qcc = ix->w_ti_qcc.as<float>();
+    tp.nvisit = ix->w_ti_nvisit.as<int>();
+    tp.ea = (ix->methods & VAQHIP_METHOD_EA) ? 1 : 0;
+    HIP_TRY(vaq::launch_ti_exact_replay(tp, n, st));
     if (timing) {
       HIP_TRY(hipEventRecord(ev[4], st));
       HIP_TRY(hipEventRecord(ev[5], st));
@@ -678,13 +709,16 @@ int search_device_locked(vaqhip_index *ix, const float *d_queries, int nq, int k
                              ix->w_ex_dist.as<float>(), st))
       return rc;
     WS_SCOPE(ws, ix, st);
-    HIP_TRY(vaq::launch_exact_ties(ix->d_codes.as<uint32_t>(), ix->layout, ix->M, ix->W, ix->d_sub.as<vaq::SubDesc>(),
-                                   ix->d_inv.as<uint32_t>(), ix->N > 0 ? ix->d_rowbucket.as<unsigned short>() : nullptr,
-                                   ix->n_buckets, ix->bucket_shift, ix->bucket_t, ix->N, ix->w_lut.as<float>(), ix->lut_floats,
-                                   ix->seq, n, k, ix->id_base,
-                                   ix->w_ex_labels.as<int32_t>(), ix->w_ex_dist.as<float>(), d_labels + (size_t)q0 * k,
-                                   d_dist + (size_t)q0 * k, reinterpret_cast<int *>(ix->w_ex_list.as<unsigned char>() + 16),
-                                   ix->w_ex_list.as<unsigned>(), st));
+    vaq::ExactParams p = exact_params(ix, k);
+    p.labels = d_labels + (size_t)q0 * k;
+    p.dist = d_dist + (size_t)q0 * k;
+    int *list = reinterpret_cast<int *>(ix->w_ex_list.as<unsigned char>() + 16);
+    unsigned *count = ix->w_ex_list.as<unsigned>();
+    p.list = list;
+    p.count = count;
+    HIP_TRY(vaq::launch_exact_flag(n, k, ix->w_ex_labels.as<int32_t>(), ix->w_ex_dist.as<float>(), p.labels, p.dist, list,
+                                   count, st));
+    HIP_TRY(vaq::launch_exact_replay(p, n, st));
     if (int rc = ws.finish()) return rc;
   }
   return VAQHIP_OK;
@@ -825,10 +859,15 @@ int vaqhip_internal_exact_link_device(vaqhip_index *ix, int k, int64_t row0, con
   hipStream_t st = static_cast<hipStream_t>(stream);
   WS_SCOPE(ws, ix, st);
   if (int rc = ensure_inverse_perm(ix, st)) return rc;
-  HIP_TRY(vaq::launch_exact_link(ix->d_codes.as<uint32_t>(), ix->layout, ix->M, ix->W, ix->d_sub.as<vaq::SubDesc>(),
-                                 ix->d_inv.as<uint32_t>(), ix->N > 0 ? ix->d_rowbucket.as<unsigned short>() : nullptr,
-                                 ix->n_buckets, ix->bucket_shift, ix->bucket_t, ix->N, ix->w_lut.as<float>(), ix->lut_floats,
-                                 ix->seq, row0, k, ix->id_base, d_list, d_count, e0, n_entries, d_state_in, d_state_out, st));
+  vaq::ExactParams p = exact_params(ix, k);
+  p.list = d_list;
+  p.count = d_count;
+  p.chain = 1;
+  p.row0 = row0;
+  p.e0 = e0;
+  p.state_in = d_state_in;
+  p.state_out = d_state_out;
+  HIP_TRY(vaq::launch_exact_replay(p, n_entries, st));
   return ws.finish();
 }
 
