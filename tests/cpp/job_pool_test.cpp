@@ -72,6 +72,25 @@ int main() {
     vaq::JobPool idle;
     idle.start(4);
   }
+  // start, run, stop, start, run: the second set of workers takes jobs like the first; a stopped (or never
+  // started) pool runs nothing and waits for nobody
+  {
+    vaq::JobPool pool;
+    std::atomic<int> ran{0};
+    const auto job = [&](int g) -> int {
+      ran++;
+      return g == 1 ? 5 : 0;
+    };
+    CHECK(pool.run(job) == 0 && ran == 0);
+    pool.start(3);
+    CHECK(pool.run(job) == 5 && ran == 3 && pool.rc(1) == 5);
+    pool.stop();
+    CHECK(pool.size() == 0 && pool.run(job) == 0 && ran == 3);
+    pool.start(2);
+    CHECK(pool.size() == 2);
+    CHECK(pool.run(job) == 5 && ran == 5 && pool.rc(0) == 0 && pool.rc(1) == 5);
+    CHECK(pool.run([](int) { return 0; }) == 0);
+  }
   std::puts("job_pool_test: ok");
   return 0;
 }

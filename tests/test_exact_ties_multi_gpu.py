@@ -1,7 +1,7 @@
 """Option "exact_ties" on the multi-device index: labels and distances identical to VAQ::search's over
 ALL rows, slot for slot, although the rows are cut into shards.  The reference's heap after the rows of
 shards 0..g is shard g's replay started from the heap shards 0..g-1 left behind, so the shards replay as
-a chain (vaq_amd/csrc/vaqhip_multi.cpp, vaq_exact.hip); logical shards on device 0 exercise every step
+a chain (vaq_amd/csrc/vaqhip_multi_search.cpp, vaq_exact.hip); logical shards on device 0 exercise every step
 of it.  Checked with plain array_equal against oracle.search (pinned against the reference's heap in
 tests/test_oracle_golden.py) and the golden label lists.
 

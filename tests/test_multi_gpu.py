@@ -95,7 +95,7 @@ def test_multi_append_ti_and_errors(vaqlib, oracle):
 def test_a_failing_shard_does_not_hang_the_others(vaqlib):
     """One shard of four refuses the search (its method is set to TI without clusters): the call
     returns that shard's error, NO exchange step was enqueued for anybody (the collective is only
-    issued after every shard succeeded: vaqhip_multi.cpp, multi_search_common), the index answers
+    issued after every shard succeeded: vaqhip_multi_search.cpp, search_set), the index answers
     again once the shard is repaired, and destroy returns."""
     import ctypes as C
     from vaq_amd import _lib

@@ -1,7 +1,7 @@
 """Option "exact_ties" on a multi-device index of sequential-sum shards (VaqHipMulti(sequential_sum=True)):
 BitVecEngine::queryLUT's answer over ALL rows slot for slot, identical to the single index's.  Shard g's
 replay starts from the raw heap (k + 1 pairs, its length, bsfK) shards 0..g-1 left, and `dataIndex >= k`
-counts from the shard's first global row (vaq_amd/csrc/vaqhip_multi.cpp, vaq_exact.hip); logical shards on
+counts from the shard's first global row (vaq_amd/csrc/vaqhip_multi_search.cpp, vaq_exact.hip); logical shards on
 device 0 exercise every step.  Plain array_equal against the fixtures under tests/golden/seq_exact/ and
 seq_exact_ref (tests/test_seq_exact_cpu.py pins both, and asserts that the tie-heavy fixtures differ from
 the (distance, label) order the shards' merge follows)."""

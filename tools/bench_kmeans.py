@@ -79,7 +79,8 @@ def main():
                     f.write(cents[s].tobytes())
     if args.devices:
         devices = [int(d) for d in args.devices.split(",")]
-        v = vaq_amd.VaqHipMulti(devices, [BITS] * M, cents)
+        from vaq_amd.index import VaqHipMulti
+        v = VaqHipMulti(devices, [BITS] * M, cents)
         v.set_codes(codes)
     else:
         v = vaq_amd.VaqHip(device=0)

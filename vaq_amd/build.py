@@ -14,7 +14,8 @@ CSRC = os.path.join(ROOT, "vaq_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "vaq_amd", "lib")
 LIB = os.path.join(LIBDIR, "libvaqhip.so")
 SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_fast.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp",
-           "vaqhip_multi.cpp"]
+           "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_rccl.cpp"]
+MULTI_SOURCES = ("vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp")
 KERNEL_HEADER = os.path.join(CSRC, "vaq_kernels.h")
 API_HEADER = os.path.join(ROOT, "include", "vaqhip.h")
 
@@ -26,19 +27,23 @@ RESTATED_HEADER = os.path.join(CSRC, "vaq_restated.h")  # stdsort, stdheap, refh
 INTERNAL_HEADER = os.path.join(CSRC, "vaqhip_internal.h")
 INDEX_HEADER = os.path.join(CSRC, "vaqhip_index.h")  # private to the single-index host files
 DEV_HEADER = os.path.join(CSRC, "vaqhip_dev.h")      # DevBuf, DeviceGuard: both hosts and the scratch allocators
+MULTI_HEADER = os.path.join(CSRC, "vaqhip_multi.h")  # private to the multi-device host files; brings the next two
 JOB_POOL_HEADER = os.path.join(CSRC, "job_pool.h")
+RCCL_HEADER = os.path.join(CSRC, "vaqhip_rccl.h")
 KMEANS_SAMPLE_HEADER = os.path.join(CSRC, "kmeans_sample.h")  # the k-means' sample and its split: both hosts
 
 
 def _deps(src: str):
     # only the host files see the public C header; the scan bodies live in vaq_scan.h
     deps = [os.path.join(CSRC, src), KERNEL_HEADER]
+    if src == "vaqhip_rccl.cpp":  # nothing of the index
+        return [os.path.join(CSRC, src), RCCL_HEADER]
     if src.endswith(".cpp"):
         deps += [API_HEADER, INTERNAL_HEADER, DEV_HEADER]
-        deps.append(JOB_POOL_HEADER if src == "vaqhip_multi.cpp" else INDEX_HEADER)
+        deps += [MULTI_HEADER, JOB_POOL_HEADER, RCCL_HEADER] if src in MULTI_SOURCES else [INDEX_HEADER]
     if src in ("vaq_kernels.hip", "vaq_ti.hip", "vaq_kmeans.hip"):
         deps.append(DEV_HEADER)
-    if src in ("vaq_kmeans.hip", "vaqhip_codes.cpp", "vaqhip_multi.cpp"):
+    if src in ("vaq_kmeans.hip", "vaqhip_codes.cpp", "vaqhip_multi_kmeans.cpp"):
         deps.append(KMEANS_SAMPLE_HEADER)
     if src in ("vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip"):
         deps.append(SCAN_HEADER)

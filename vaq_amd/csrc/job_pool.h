@@ -1,4 +1,4 @@
-// job_pool.h -- the host-side worker protocol of the multi-device index (vaqhip_multi.cpp): one
+// job_pool.h -- the host-side worker protocol of the multi-device index (on_shards in vaqhip_multi.h): one
 // persistent thread per shard; the caller hands every worker the same job (a callable taking the
 // shard number), waits until ALL of them have reported, and reads their return codes.  A job is one
 // PHASE: the caller decides between phases -- in particular a collective is only issued after every
@@ -25,9 +25,14 @@ public:
   JobPool &operator=(const JobPool &) = delete;
   ~JobPool() { stop(); }
 
-  // start n workers (idempotent for the same n)
+  // start n workers (idempotent for the same n; also after stop)
   void start(int n) {
     if (!threads_.empty()) return;
+    {
+      std::lock_guard<std::mutex> lk(mu_);
+      quit_ = false;
+      seq_ = 0;  // (a new worker has seen no job)
+    }
     rc_.assign((size_t)n, 0);
     for (int g = 0; g < n; g++) threads_.emplace_back([this, g] { loop(g); });
   }
@@ -47,8 +52,10 @@ public:
 
   // Run fn(g) on worker g for every g, wait for all of them; returns the first non-zero code (by
   // shard number) or 0.  rc(g) gives each worker's own code afterwards.  One run at a time (the
-  // caller serialises; vaqhip_multi holds its mutex).
+  // caller serialises; vaqhip_multi holds its mutex).  A pool without workers (never started, or stopped) has
+  // nobody to wait for: 0.
   int run(const std::function<int(int)> &fn) {
+    if (threads_.empty()) return 0;
     {
       std::lock_guard<std::mutex> lk(mu_);
       fn_ = &fn;

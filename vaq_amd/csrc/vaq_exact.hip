@@ -20,7 +20,7 @@
 //                        own statements: if (top > dist) { heap_pop; heap_push }.  The top the evaluating
 //                        waves abandon against is always one the heap had BEFORE the rows they look at,
 //                        so nothing the reference would admit is ever dropped.  At the end heap_reorder.
-// Across the shards of a multi-device index (vaqhip_multi.cpp) the replay is a CHAIN: shards are
+// Across the shards of a multi-device index (vaqhip_multi_search.cpp) the replay is a CHAIN: shards are
 // contiguous label ranges in label order, so the reference's heap after the rows of shards 0..g is shard
 // g's replay started from the heap (values and ids, raw layout) shards 0..g-1 left behind.  A chain link
 // (ExactParams::chain) takes that state instead of heap_heapify's neutral one, pushes GLOBAL row numbers

@@ -292,7 +292,7 @@ hipError_t launch_inverse_perm(const uint32_t *perm, int64_t n, uint32_t *inv, c
                                unsigned short *row_bucket, hipStream_t st);
 // int32 words of one list entry's state in a chain over shards (ExactParams::chain)
 __host__ __device__ inline int exact_state_words(int k, int seq) { return seq ? 2 * (k + 1) + 2 : 2 * k; }
-// The flag step, also on the MERGED k + 1 list of a multi-device index (vaqhip_multi.cpp).  in_labels / in_dist:
+// The flag step, also on the MERGED k + 1 list of a multi-device index (vaqhip_multi_search.cpp).  in_labels / in_dist:
 // the scan's result for k + 1 per query (labels carry id_base); labels / dist: the caller's k per query.  Queries
 // whose k + 1 smallest distances are distinct are copied; the others are listed for the replay.  list: [nq] ints,
 // count: one word, zeroed first.

@@ -2,7 +2,7 @@
 // buffers (vaqhip_dev.h), the entry preamble, the workspace scope, the launch plan and the few functions
 // that cross files.  Private to vaqhip_api.cpp,
 // vaqhip_plan.cpp, vaqhip_search.cpp, vaqhip_codes.cpp and vaqhip_fast.cpp: the multi-device host
-// (vaqhip_multi.cpp) sees the index through include/vaqhip.h and vaqhip_internal.h only.
+// (vaqhip_multi*.cpp) sees the index through include/vaqhip.h and vaqhip_internal.h only.
 #ifndef VAQHIP_INDEX_H
 #define VAQHIP_INDEX_H
 #include "vaqhip.h"

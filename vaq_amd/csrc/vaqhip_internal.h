@@ -1,5 +1,5 @@
 // vaqhip_internal.h -- entries of the single-device index that only the multi-device host
-// (vaqhip_multi.cpp) calls: the pieces of option "exact_ties" as a chain over shards (vaq_exact.hip), and
+// (vaqhip_multi*.cpp) calls: the pieces of option "exact_ties" as a chain over shards (vaq_exact.hip), and
 // one shard's part of a FAST search (vaq_fast.hip), and one shard's part of the k-means of clusterTI (vaq_kmeans.hip).
 // Not part of the public interface (include/vaqhip.h).
 #ifndef VAQHIP_INTERNAL_H
