@@ -19,6 +19,13 @@
 //               [--devices 0,1,2,3]        (shard the rows over these GPUs: RCCL all-gather + merge)
 //               with a ...,FAST method (codes of at most 4 bits): --dataset base.fvecs [--dataset-size N]
 //               [--learn-ratio 0.05]       (demo_vaq.cpp:42, :120-124: VAQ::learnQuantization on the raw dataset)
+//
+//   demo_vaqhip --lut-bits 8,6,5,...  --dataset base.fvecs [--dataset-size N] [--eigen e.f32] \
+//               --queries q.fvecs --timeseries-size 128 [--queries-size N] --k 100 [--exact-ties 1] \
+//               [--result out.csv] [--save-enc cb.bin] [--groundtruth gt.ivecs]
+//       builds a queryLUT index (BitVecEngine::binaryEncodingLUT from the bit allocation on: quantile
+//       codebooks and codes on the GPU; the PCA rotation and the bits per dimension are the caller's, as
+//       with the reference's hardcoded solutionX) over the first len(bits) PCA dimensions and queries it
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -30,12 +37,70 @@
 
 using namespace vaqhip;
 
+static std::vector<int> intList(const std::string &csv) {
+  std::vector<int> v;
+  std::stringstream ss(csv);
+  std::string t;
+  while (std::getline(ss, t, ',')) v.push_back(std::atoi(t.c_str()));
+  return v;
+}
+
+// --lut-bits: build and query BitVecEngine's LUT index
+static int lutMain(std::map<std::string, std::string> &a) {
+  for (const char *req : {"dataset", "queries"})
+    if (!a.count(req)) { std::cerr << "missing --" << req << "\n"; return 2; }
+  BitVecEngineHip engine;
+  engine.solutionX = intList(a["lut-bits"]);
+  engine.exactTies = a.count("exact-ties") && std::atoi(a["exact-ties"].c_str()) != 0;
+  const int D = (int)engine.solutionX.size();
+  const int N = std::atoi(a["timeseries-size"].c_str());
+  if (D != N) throw Error(VAQHIP_EINVAL, "--lut-bits needs one entry per dimension (--timeseries-size)");
+  if (a.count("eigen")) {
+    engine.eigenVectors = RowMatrixF(D, D);
+    detail::File f(a["eigen"], "rb");
+    f.read(engine.eigenVectors.data(), sizeof(float), (size_t)D * D);
+  }
+  RowMatrixF dataset = readFVecs(a["dataset"], N, a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1, 0);
+  RowMatrixF queries = readFVecs(a["queries"], N, std::atoi(a["queries-size"].c_str()), 0);
+  const int k = std::atoi(a["k"].c_str());
+  CodebookType codebook;
+  auto t0 = std::chrono::steady_clock::now();
+  engine.binaryEncodingLUT(dataset, codebook);
+  std::cout << "== Encoding time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+            << " s (" << codebook.rows() << " rows x " << D << " dimensions, quantile codebooks + codes)" << std::endl;
+  if (a.count("save-enc")) saveCodebook(codebook, a["save-enc"]);
+  t0 = std::chrono::steady_clock::now();
+  auto answers = engine.queryLUT(queries, k, codebook);
+  const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  std::cout << "== Querying time: " << sec << " s (" << queries.rows() / sec << " queries/s)" << std::endl;
+  LabelDistVecF flat;
+  for (auto &ans : answers)
+    for (int i = 0; i < k; i++) {
+      flat.labels.push_back(i < (int)ans.size() ? ans[i].idx : -1);
+      flat.distances.push_back(i < (int)ans.size() ? ans[i].dist : 0.0f);
+    }
+  if (a.count("result")) writeKNNResults(a["result"], flat, queries.rows());
+  if (a.count("groundtruth")) {
+    RowMatrix<int> gt = readIVecs(a["groundtruth"], k);
+    std::cout << "\tprecision(avg_recall): " << getAvgRecall(flat.labels, gt, k) << std::endl;
+  }
+  return 0;
+}
+
 int main(int argc, char **argv) {
   std::map<std::string, std::string> a = {{"k", "100"}, {"method", "VAQ64m8min8max8var1,HEAP"},
                                           {"timeseries-size", "128"}, {"queries-size", "-1"}};
   for (int i = 1; i + 1 < argc; i += 2) {
     if (std::strncmp(argv[i], "--", 2) != 0) { std::cerr << "bad argument " << argv[i] << "\n"; return 2; }
     a[argv[i] + 2] = argv[i + 1];
+  }
+  if (a.count("lut-bits")) {
+    try {
+      return lutMain(a);
+    } catch (const std::exception &e) {
+      std::cerr << "error: " << e.what() << std::endl;
+      return 1;
+    }
   }
   for (const char *req : {"centroids", "codebook", "queries"})
     if (!a.count(req)) { std::cerr << "missing --" << req << "\n"; return 2; }

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 109
+#define VAQHIP_VERSION 110
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -273,6 +273,63 @@ int vaqhip_encode(vaqhip_index *ix, const float *X_rowmajor, int64_t n, int proj
                   uint16_t *codes_out);
 int vaqhip_encode_device(vaqhip_index *ix, const float *d_X, int64_t n, int projected,
                          uint16_t *d_codes_out, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Building a queryLUT index: BitVecEngine::binaryEncodingLUT (BitVecEngine.hpp:594-935) from the bit allocation
+ * on.  The PCA (:596-617) and the glpk bit allocation (:622-809) stay the caller's: eigenvectors and bits per
+ * dimension come in, as the reference's own parseAndLoadHardcoded / hardcodedSolutionX (:127-149) takes the bits.
+ *
+ * vaqhip_lut_fit_quantiles = centroidsQuantile (:811-840) for every dimension d, N = 1 << bits[d], over the
+ * column sorted ascending (Z):
+ *   Q[0] = Z.front(), Q[N] = Z.back(), Q[i+1] = (1 - (poi - left)) * Z[left] + (poi - left) * Z[right] with
+ *   p = (float)(i+1)/N, poi = float((1 - p) * (-0.5) + p * ((float)n - 0.5)) -- the products and the sum in
+ *   double --, left = max(floor(poi), 0), right = min(ceil(poi), n - 1);
+ *   bucket i = the values from where bucket i-1 ended up to the first Z > Q[i+1]; its centre is the float sum of
+ *   its values, ONE ADD AFTER ANOTHER in ascending order from +0, divided by the count; an empty bucket gets
+ *   (Q[i] + Q[i+1]) / 2.
+ *   X              n x D row-major (the reference's matrix is column-major); in PCA space when eigvec is NULL,
+ *                  else out = X * eigvec is taken first WITHOUT checking, as :620 does
+ *   bits[D]        solutionX, 1..8 each
+ *   centroids_out  256 x D column-major, the layout of centroidsMat (column d at centroids_out + 256 * d, rows
+ *                  >= N zero)
+ *   quantiles_out  D x 257 (row d = Q[d][0 .. N], the rest zero)
+ * Refused with VAQHIP_EINVAL: bits outside 1..8, n < 1, n >= 2^31, a NaN or infinite (projected) training value
+ * (std::sort has no defined result on NaN) -- the outputs are then left untouched.  A column holding both -0 and
+ * +0 is sorted with -0 first where std::sort's order among them is unspecified: only the sign of a zero in Q can
+ * differ.  Workspace: two key buffers of n words (one column at a time), plus the projected rows when eigvec is
+ * given.  The result equals a build of the reference without -ffast-math and with -ffp-contract=off bit for bit
+ * by construction; it is not pinned against a compiled reference (BitVecEngine.hpp needs glpk.h).
+ * The _device form takes device pointers (bits stays a host array) and works on `stream`, which it
+ * synchronises before it returns (the refusal above is known only then). */
+int vaqhip_lut_fit_quantiles(int device_id, const float *X_rowmajor, int64_t n, int D, const int *bits,
+                             const float *eigvec_real_rowmajor, float *centroids_out, float *quantiles_out);
+int vaqhip_lut_fit_quantiles_device(int device_id, const float *d_X, int64_t n, int D, const int *bits,
+                                    const float *d_eigvec, float *d_centroids_out, float *d_quantiles_out,
+                                    void *stream);
+typedef struct {
+  float total_ms;                                    /* host time of the last fit on this thread, copies excluded */
+  float project_ms;                                  /* only with vaqhip_lut_fit_set_timing(1), else 0: */
+  float extract_ms, sort_ms, quantile_ms, means_ms;  /*   device time per phase, summed over the columns */
+  int64_t rows;
+  int dims;
+} vaqhip_lut_fit_timing;
+int vaqhip_lut_fit_set_timing(int on);                       /* per calling thread */
+int vaqhip_last_lut_fit_timing(vaqhip_lut_fit_timing *out);  /* the calling thread's last fit */
+
+/* Keeps Q (D x 257, as vaqhip_lut_fit_quantiles writes it) on a VAQHIP_SUM_SEQUENTIAL index, whose centroids are
+ * the matching centres; VAQHIP_EINVAL on any other index, for bits above 8 and for a NaN in Q. */
+int vaqhip_index_set_lut_quantiles(vaqhip_index *ix, const float *quantiles);
+
+/* encodeToLUTCode (:889-932): per row x and dimension j, the first q in 0..N with x <= Q[j][q]; none (x above
+ * the range, NaN): code N - 1; q == 0: 0; q == 1: |x - c[0]| <= |x - c[1]| ? 0 : 1; q == N: m = |x - c[N-1]|,
+ * l = |x - c[N-2]|, m <= l ? N - 1 : N - 2; else m = |x - c[q-1]|, l = |x - c[q-2]|, r = |x - c[q]|:
+ * m <= l && m <= r gives q - 1, else l <= m && l <= r gives q - 2, else q.  (With bits == 1, q == 1 is tested
+ * first.)  NOT vaqhip_encode's first global argmin under strict <: the two differ where distances tie and
+ * outside the training range.  codes_out is n x D uint16 row-major, what vaqhip_index_set_codes_u16* takes.
+ * projected == 0 applies eigvec first, unchecked (:620).  VAQHIP_ESTATE before the quantiles are set. */
+int vaqhip_encode_lut(vaqhip_index *ix, const float *X_rowmajor, int64_t n, int projected, uint16_t *codes_out);
+int vaqhip_encode_lut_device(vaqhip_index *ix, const float *d_X, int64_t n, int projected, uint16_t *d_codes_out,
+                             void *stream);
 
 /* VAQ::refine (VAQ.cpp:849-876): exact squared L2 in the ORIGINAL space between each
  * query and its R candidate rows of the raw dataset, k best by the same k-min rule.

@@ -531,19 +531,7 @@ public:
   // takes a column-major Eigen::MatrixXf: pass its transpose's storage or a RowMatrixF)
   template <class Mat, class Codebook>
   std::vector<std::vector<IdxDistPairFloat>> queryLUT(const Mat &queries, const int k, const Codebook &codebook) {
-    const int nd = (int)solutionX.size();
-    if (!h_) {
-      std::vector<std::vector<float>> cols(nd);
-      std::vector<const float *> cp(nd);
-      for (int d = 0; d < nd; d++) {
-        cols[d].assign(centroidsMat.begin() + (size_t)d * centroidRows,
-                       centroidsMat.begin() + (size_t)d * centroidRows + ((size_t)1 << solutionX[d]));
-        cp[d] = cols[d].data();
-      }
-      check(vaqhip_index_create_ex(&h_, nd, nd, solutionX.data(), cp.data(),
-                                   eigenVectors.rows() ? eigenVectors.data() : nullptr, mDevice,
-                                   VAQHIP_SUM_SEQUENTIAL));
-    }
+    ensureIndex();
     check(vaqhip_set_option(h_, "exact_ties", exactTies ? 1 : 0));
     check(vaqhip_index_set_codes_u16(h_, codebook.data(), (int64_t)codebook.rows(), 0));
     const int nq = (int)queries.rows();
@@ -557,7 +545,45 @@ public:
     return answers;
   }
 
+  // BitVecEngine::binaryEncodingLUT (BitVecEngine.hpp:594-935) from the bit allocation on, on the GPU.  The PCA
+  // (:596-617) and the glpk bit allocation (:622-809) stay the caller's: with solutionX (1..8 bits per dimension, as
+  // hardcodedSolutionX gives them) and eigenVectors set, this fills centroidsMat (256 x nonZeroAllocCount) and
+  // `quantiles` as centroidsQuantile does (:811-867), then codebookOut as encodeToLUTCode does (:889-934), bit for
+  // bit (vaqhip_lut_fit_quantiles, vaqhip_encode_lut).  XTrain: row-major, unprojected -- projected here without
+  // checking, as :620 does.  A NaN or infinite projected value is refused (VAQHIP_EINVAL).
+  std::vector<float> quantiles;  // nonZeroAllocCount x 257: row d = Q[d][0 .. 1 << solutionX[d]], the rest 0
+  template <class Mat>
+  void binaryEncodingLUT(const Mat &XTrain, CodebookType &codebookOut) {
+    const int nd = (int)solutionX.size();
+    if ((int)XTrain.cols() != nd) throw Error(VAQHIP_EINVAL, "vaqhip: XTrain must have one column per entry of solutionX");
+    centroidRows = 256;
+    std::vector<float> cent((size_t)centroidRows * nd), q((size_t)257 * nd);
+    check(vaqhip_lut_fit_quantiles(mDevice, XTrain.data(), (int64_t)XTrain.rows(), nd, solutionX.data(),
+                                   eigenVectors.rows() ? eigenVectors.data() : nullptr, cent.data(), q.data()));
+    centroidsMat.swap(cent);
+    quantiles.swap(q);
+    invalidate();
+    ensureIndex();
+    check(vaqhip_index_set_lut_quantiles(h_, quantiles.data()));
+    codebookOut = CodebookType((size_t)XTrain.rows(), (size_t)nd);
+    check(vaqhip_encode_lut(h_, XTrain.data(), (int64_t)XTrain.rows(), 0, codebookOut.data()));
+  }
+
 private:
+  void ensureIndex() {
+    if (h_) return;
+    const int nd = (int)solutionX.size();
+    std::vector<std::vector<float>> cols(nd);
+    std::vector<const float *> cp(nd);
+    for (int d = 0; d < nd; d++) {
+      cols[d].assign(centroidsMat.begin() + (size_t)d * centroidRows,
+                     centroidsMat.begin() + (size_t)d * centroidRows + ((size_t)1 << solutionX[d]));
+      cp[d] = cols[d].data();
+    }
+    check(vaqhip_index_create_ex(&h_, nd, nd, solutionX.data(), cp.data(),
+                                 eigenVectors.rows() ? eigenVectors.data() : nullptr, mDevice,
+                                 VAQHIP_SUM_SEQUENTIAL));
+  }
   vaqhip_index *h_ = nullptr;
 };
 

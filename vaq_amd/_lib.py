@@ -22,7 +22,10 @@ SYMBOLS = [
     "vaqhip_search_device", "vaqhip_search_staged_supported", "vaqhip_search_begin_device",
     "vaqhip_search_finish_device", "vaqhip_build_lut", "vaqhip_project", "vaqhip_merge_topk_device",
     "vaqhip_merge_topk_strided_device", "vaqhip_merge_fast_device",
-    "vaqhip_encode", "vaqhip_encode_device", "vaqhip_refine", "vaqhip_refine_device",
+    "vaqhip_encode", "vaqhip_encode_device",
+    "vaqhip_lut_fit_quantiles", "vaqhip_lut_fit_quantiles_device", "vaqhip_lut_fit_set_timing",
+    "vaqhip_last_lut_fit_timing", "vaqhip_index_set_lut_quantiles", "vaqhip_encode_lut", "vaqhip_encode_lut_device",
+    "vaqhip_refine", "vaqhip_refine_device",
     "vaqhip_index_info", "vaqhip_set_option", "vaqhip_last_timing", "vaqhip_last_error",
     "vaqhip_version", "vaqhip_device_count",
     "vaqhip_multi_create", "vaqhip_multi_destroy", "vaqhip_multi_set_codes_u16", "vaqhip_multi_add_codes_u16",
@@ -67,6 +70,12 @@ class KmeansTiming(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("assign_ms", C.c_float), ("accumulate_ms", C.c_float),
                 ("update_ms", C.c_float), ("iterations", C.c_int), ("rows", C.c_int), ("dims", C.c_int),
                 ("clusters", C.c_int)]
+
+
+class LutFitTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("project_ms", C.c_float), ("extract_ms", C.c_float),
+                ("sort_ms", C.c_float), ("quantile_ms", C.c_float), ("means_ms", C.c_float),
+                ("rows", C.c_int64), ("dims", C.c_int)]
 
 
 class MultiInfo(C.Structure):
@@ -131,6 +140,13 @@ def load():
     L.vaqhip_merge_topk_device.argtypes = [i32, vp, vp, i32, i32, i32, vp, vp, vp]
     L.vaqhip_encode.argtypes = [vp, vp, i64, i32, vp]
     L.vaqhip_encode_device.argtypes = [vp, vp, i64, i32, vp, vp]
+    L.vaqhip_lut_fit_quantiles.argtypes = [i32, vp, i64, i32, C.POINTER(i32), vp, vp, vp]
+    L.vaqhip_lut_fit_quantiles_device.argtypes = [i32, vp, i64, i32, C.POINTER(i32), vp, vp, vp, vp]
+    L.vaqhip_lut_fit_set_timing.argtypes = [i32]
+    L.vaqhip_last_lut_fit_timing.argtypes = [C.POINTER(LutFitTiming)]
+    L.vaqhip_index_set_lut_quantiles.argtypes = [vp, vp]
+    L.vaqhip_encode_lut.argtypes = [vp, vp, i64, i32, vp]
+    L.vaqhip_encode_lut_device.argtypes = [vp, vp, i64, i32, vp, vp]
     L.vaqhip_refine.argtypes = [i32, vp, i32, i32, vp, i64, vp, i32, i32, vp, vp]
     L.vaqhip_refine_device.argtypes = [i32, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp]
     L.vaqhip_merge_topk_strided_device.argtypes = [i32, vp, vp, i32, i64, i64, i32, i32, vp, vp, vp]

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vaq_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "vaq_amd", "lib")
 LIB = os.path.join(LIBDIR, "libvaqhip.so")
-SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_fast.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp",
+SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_fast.hip", "vaq_lutfit.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp", "vaqhip_lutfit.cpp",
            "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_rccl.cpp"]
 MULTI_SOURCES = ("vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp")
 KERNEL_HEADER = os.path.join(CSRC, "vaq_kernels.h")
@@ -31,6 +31,7 @@ MULTI_HEADER = os.path.join(CSRC, "vaqhip_multi.h")  # private to the multi-devi
 JOB_POOL_HEADER = os.path.join(CSRC, "job_pool.h")
 RCCL_HEADER = os.path.join(CSRC, "vaqhip_rccl.h")
 KMEANS_SAMPLE_HEADER = os.path.join(CSRC, "kmeans_sample.h")  # the k-means' sample and its split: both hosts
+LUTFIT_HEADER = os.path.join(CSRC, "vaq_lutfit.h")  # binaryEncodingLUT's two lambdas: kernels and host
 
 
 def _deps(src: str):
@@ -41,8 +42,10 @@ def _deps(src: str):
     if src.endswith(".cpp"):
         deps += [API_HEADER, INTERNAL_HEADER, DEV_HEADER]
         deps += [MULTI_HEADER, JOB_POOL_HEADER, RCCL_HEADER] if src in MULTI_SOURCES else [INDEX_HEADER]
-    if src in ("vaq_kernels.hip", "vaq_ti.hip", "vaq_kmeans.hip"):
+    if src in ("vaq_kernels.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_lutfit.hip"):
         deps.append(DEV_HEADER)
+    if src in ("vaq_lutfit.hip", "vaqhip_lutfit.cpp"):
+        deps.append(LUTFIT_HEADER)
     if src in ("vaq_kmeans.hip", "vaqhip_codes.cpp", "vaqhip_multi_kmeans.cpp"):
         deps.append(KMEANS_SAMPLE_HEADER)
     if src in ("vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip"):

@@ -136,6 +136,16 @@ hipError_t launch_lut_expand(const float *lut_packed, int nq, int M, const SubDe
 // VAQ::encodeImpl: Xp is n x D already in PCA space; codes is n x M uint16 row-major
 hipError_t launch_encode(const float *Xp, int64_t n, int D, int M, int L, const SubDesc *sub,
                          const float *cent, uint16_t *codes, hipStream_t st);
+// BitVecEngine::binaryEncodingLUT from the bit allocation on (vaq_lutfit.hip, arithmetic in vaq_lutfit.h).
+// lut_fit_columns: centroidsQuantile per column of the n x D rows in PCA space -- d_cent_out [D][256] (centroidsMat:
+// 256 x D column-major), d_q_out [D][257], *d_bad set when a value is not finite; synchronises `st`;
+// phase_ms (optional) [4]: device time of extract, sort, quantiles, means over all columns.
+hipError_t lut_fit_columns(const float *d_Xp, int64_t n, int D, const int *bits, float *d_cent_out, float *d_q_out,
+                           int *d_bad, float *phase_ms, hipStream_t st);
+// encodeToLUTCode: Xp n x D in PCA space (D == M, one centre column per dimension), codes n x D uint16 row-major;
+// d_pm: per dimension s the N + 1 prefix maxima of Q[s] at sub[s].cent_off + s (lutfit::first_boundary)
+hipError_t launch_lut_encode(const float *Xp, int64_t n, int D, const SubDesc *h_sub, const SubDesc *d_sub,
+                             const float *d_pm, const float *d_cent, uint16_t *codes, int n_cu, hipStream_t st);
 // VAQ::refine: exact re-rank of R (<= 2048) candidates per query
 hipError_t launch_refine(const float *Q, int nq, int D, const float *dataset, const float *rows,
                          const int32_t *labels_in, int R, int k, int32_t *labels, float *dist,

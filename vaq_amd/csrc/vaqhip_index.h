@@ -1,7 +1,7 @@
 // vaqhip_index.h -- what the host files of the single-device index share: the index itself, its device
 // buffers (vaqhip_dev.h), the entry preamble, the workspace scope, the launch plan and the few functions
 // that cross files.  Private to vaqhip_api.cpp,
-// vaqhip_plan.cpp, vaqhip_search.cpp, vaqhip_codes.cpp and vaqhip_fast.cpp: the multi-device host
+// vaqhip_plan.cpp, vaqhip_search.cpp, vaqhip_codes.cpp, vaqhip_fast.cpp and vaqhip_lutfit.cpp: the multi-device host
 // (vaqhip_multi*.cpp) sees the index through include/vaqhip.h and vaqhip_internal.h only.
 #ifndef VAQHIP_INDEX_H
 #define VAQHIP_INDEX_H
@@ -108,6 +108,10 @@ struct vaqhip_index {
   int64_t fast_cap = 0;    // rows its allocation holds (multiple of FAST_ROW_PAD)
   std::vector<float> fast_off, fast_scale;
   bool inv_valid = false;
+  // a sequential-sum index that can encode (vaqhip_index_set_lut_quantiles): Q[D][257] of
+  // BitVecEngine::binaryEncodingLUT on the host, its prefix maxima packed on the device (vaq_lutfit.h)
+  std::vector<float> lut_q;
+  DevBuf d_lut_pm;
   hipStream_t stream = nullptr;
   // The workspaces above are shared by every call on this index.  Host-side enqueues are
   // serialised by `mu`, but `_device` entry points run on the caller's stream: the last enqueue

@@ -424,6 +424,75 @@ class VaqHip:
                                                     C.c_void_p(st)))
         return codes
 
+    # ------------------------------------------- building a queryLUT index --
+    def _need_sequential(self, what: str) -> None:
+        if not self.sequential_sum:
+            raise _lib.VaqHipError(-1, f"{what} builds BitVecEngine::queryLUT's index: VaqHip(sequential_sum=True)")
+
+    def fitQuantiles(self, XTrain: np.ndarray, projected: bool = True) -> None:
+        """BitVecEngine::binaryEncodingLUT's codebooks (BitVecEngine.hpp:811-867) on the GPU: with mBitsAlloc
+        (solutionX, 1..8 per dimension) and, for projected=False, mEigenVectors set by the caller -- the PCA
+        and the bit allocation stay the caller's --, fills mCentroidsPerSubs (column d of centroidsMat),
+        centroidsMat (256 x D) and mQuantiles (D x 257), bit for bit what centroidsQuantile computes
+        (vaqhip_lut_fit_quantiles).  A NaN or infinite training value is refused (EINVAL)."""
+        self._need_sequential("fitQuantiles")
+        X = np.ascontiguousarray(XTrain, dtype=np.float32)
+        D = len(self.mBitsAlloc)
+        if X.ndim != 2 or X.shape[1] != D or D == 0:
+            raise _lib.VaqHipError(-1, f"XTrain {X.shape} is not n x {D} (one quantiser per dimension)")
+        eig = None
+        if not projected and self.mEigenVectors is not None:
+            eig = np.ascontiguousarray(np.real(self.mEigenVectors), dtype=np.float32)
+            if eig.shape != (D, D):
+                raise _lib.VaqHipError(-1, f"mEigenVectors {eig.shape} is not {D}x{D}")
+        cent = np.empty((D, 256), np.float32)
+        q = np.empty((D, 257), np.float32)
+        _lib.check(_lib.load().vaqhip_lut_fit_quantiles(self.device, _ptr(X), X.shape[0], D, (C.c_int * D)(*self.mBitsAlloc),
+                                                        _ptr(eig) if eig is not None else None, _ptr(cent), _ptr(q)))
+        self.centroidsMat = np.ascontiguousarray(cent.T)
+        self.mCentroidsPerSubs = [np.ascontiguousarray(cent[d, :1 << b].reshape(-1, 1)) for d, b in enumerate(self.mBitsAlloc)]
+        self.mQuantiles = q
+
+    def _ensure_quantiles(self) -> None:
+        self._need_sequential("encodeLUT")
+        q = getattr(self, "mQuantiles", None)
+        if q is None:
+            raise _lib.VaqHipError(-7, "encodeLUT needs mQuantiles: call fitQuantiles first")
+        self._ensure_index()
+        sig = getattr(self, "_lutq_sig", None)
+        if sig is not None and sig[0] == self._h.value and _same(sig[1], q):
+            return
+        qq = np.ascontiguousarray(q, dtype=np.float32)
+        if qq.shape != (len(self.mBitsAlloc), 257):
+            raise _lib.VaqHipError(-1, f"mQuantiles {qq.shape} is not {len(self.mBitsAlloc)} x 257")
+        _lib.check(_lib.load().vaqhip_index_set_lut_quantiles(self._h, _ptr(qq)))
+        self._lutq_sig = (self._h.value, _wref(q))
+
+    def encodeLUT(self, XTrain: np.ndarray, projected: bool = True) -> None:
+        """encodeToLUTCode (BitVecEngine.hpp:889-932): fills mCodebook (N x D uint16) with the engine's own
+        choice among the centres around a row's quantile bucket -- not encode()'s first argmin."""
+        self._ensure_quantiles()
+        X = np.ascontiguousarray(XTrain, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != len(self.mBitsAlloc):
+            raise _lib.VaqHipError(-1, f"XTrain {X.shape} is not n x {len(self.mBitsAlloc)}")
+        codes = np.empty((X.shape[0], len(self.mBitsAlloc)), np.uint16)
+        _lib.check(_lib.load().vaqhip_encode_lut(self._h, _ptr(X), X.shape[0], 1 if projected else 0, _ptr(codes)))
+        self.mCodebook = codes
+
+    def encodeLUT_device(self, d_X, projected: bool = True):
+        """torch CUDA tensor in, N x D int16 CUDA tensor (uint16 codes) out, on torch's current stream: the layout
+        mCodebook takes as a device tensor, so a build never leaves the device."""
+        import torch
+        self._ensure_quantiles()
+        x = d_X.contiguous()
+        assert x.is_cuda and x.dtype == torch.float32 and x.shape[1] == len(self.mBitsAlloc)
+        codes = torch.empty((x.shape[0], len(self.mBitsAlloc)), dtype=torch.int16, device=x.device)
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        _lib.check(_lib.load().vaqhip_encode_lut_device(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
+                                                        1 if projected else 0, C.c_void_p(codes.data_ptr()),
+                                                        C.c_void_p(st)))
+        return codes
+
     def refine(self, XTest: np.ndarray, answersIn: LabelDistVec, XTrain: np.ndarray, k: int) -> LabelDistVec:
         """VAQ::refine (VAQ.cpp:849-876): exact re-rank of the candidates in
         answersIn against the raw dataset XTrain."""
