@@ -16,6 +16,10 @@
 //                                          (demo_vaq.cpp:40, :312-345 and scripts/run_demos.sh:9,22: per value R,
 //                                           search R >= k candidates, then VAQ::refine re-ranks them against the
 //                                           raw vectors; results go to <result>_R<R> when several R are given)
+//               [--refine-resident]        (with --refine: the raw vectors are uploaded once and every R is ONE fused
+//                                           call, search + refine with the candidates kept on the device; distances in
+//                                           the reference's (Eigen's) summation order; needs --timeseries-size == D
+//                                           and a single device.  --exact-ties 1: also the reference heap's tie order)
 //               [--devices 0,1,2,3]        (shard the rows over these GPUs: RCCL all-gather + merge)
 //               with a ...,FAST method (codes of at most 4 bits): --dataset base.fvecs [--dataset-size N]
 //               [--learn-ratio 0.05]       (demo_vaq.cpp:42, :120-124: VAQ::learnQuantization on the raw dataset)
@@ -90,7 +94,13 @@ static int lutMain(std::map<std::string, std::string> &a) {
 int main(int argc, char **argv) {
   std::map<std::string, std::string> a = {{"k", "100"}, {"method", "VAQ64m8min8max8var1,HEAP"},
                                           {"timeseries-size", "128"}, {"queries-size", "-1"}};
-  for (int i = 1; i + 1 < argc; i += 2) {
+  for (int i = 1; i < argc; i += 2) {
+    if (std::strcmp(argv[i], "--refine-resident") == 0) {  // the one switch without a value
+      a["refine-resident"] = "1";
+      i--;
+      continue;
+    }
+    if (i + 1 >= argc) break;
     if (std::strncmp(argv[i], "--", 2) != 0) { std::cerr << "bad argument " << argv[i] << "\n"; return 2; }
     a[argv[i] + 2] = argv[i + 1];
   }
@@ -164,6 +174,15 @@ int main(int argc, char **argv) {
       if (raw.empty()) throw Error(VAQHIP_EINVAL, "--refine needs the raw vectors: --dataset <.fvecs> (or --dataset-refine)");
       datasetrefine = readFVecs(raw, N, a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1, 0);
     }
+    const bool resident = any_refine && a.count("refine-resident");
+    if (resident) {
+      if (N != D) throw Error(VAQHIP_EINVAL, "--refine-resident searches and refines with the same raw query: --timeseries-size must be D");
+      vaq.refineExactTies = a.count("exact-ties") && std::atoi(a["exact-ties"].c_str()) != 0;
+      auto t0 = std::chrono::steady_clock::now();
+      vaq.setRefineDataset(datasetrefine);
+      std::cout << "== Refine dataset upload: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+                << " s (" << datasetrefine.rows() << " rows resident)" << std::endl;
+    }
     RowMatrix<int> gt;
     if (a.count("groundtruth")) gt = readIVecs(a["groundtruth"], k);
     if (vaq.searchMethod() & VaqHip::NNMethod::Fast) {  // demo_vaq.cpp:120-124
@@ -179,8 +198,14 @@ int main(int argc, char **argv) {
     for (const int refine : refines) {
       auto t0 = std::chrono::steady_clock::now();
       const int searchK = refine >= k ? refine : k;  // demo_vaq.cpp:338
-      LabelDistVecF answers = vaq.search(queries, searchK, true);
-      if (refine >= k) {
+      LabelDistVecF answers;
+      if (resident && refine >= k) {
+        std::cout << "Refining the answer with Refine = " << refine << " (resident rows, fused with the search)" << std::endl;
+        answers = vaq.search(queries, k, refine);
+      } else {
+        answers = vaq.search(queries, searchK, true);
+      }
+      if (refine >= k && !resident) {
         std::cout << "Refining the answer with Refine = " << refine << std::endl;
         // the raw queries (first N dims), as the reference passes them (demo_vaq.cpp:342)
         RowMatrixF qraw((size_t)queries.rows(), (size_t)N);

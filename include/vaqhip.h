@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 110
+#define VAQHIP_VERSION 111
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -332,7 +332,9 @@ int vaqhip_encode_lut_device(vaqhip_index *ix, const float *d_X, int64_t n, int 
                              void *stream);
 
 /* VAQ::refine (VAQ.cpp:849-876): exact squared L2 in the ORIGINAL space between each
- * query and its R candidate rows of the raw dataset, k best by the same k-min rule.
+ * query and its R candidate rows of the raw dataset, k best by the same k-min rule.  The sum is
+ * sequential (dist += t * t), ties go to the smaller label: see the resident refiner below for the
+ * reference's own summation order and heap.
  * labels_in: nq x R (negative labels are skipped); R <= 2048.  The host form gathers
  * the candidate rows from `dataset_rowmajor` (N x D, raw, unprojected) itself. */
 int vaqhip_refine(int device_id, const float *queries_rowmajor, int nq, int D,
@@ -341,6 +343,49 @@ int vaqhip_refine(int device_id, const float *queries_rowmajor, int nq, int D,
 int vaqhip_refine_device(int device_id, const float *d_queries, int nq, int D,
                          const float *d_dataset, const int32_t *d_labels_in, int R, int k,
                          int32_t *d_labels_out, float *d_distances_out, void *stream);
+
+/* ---------------------------------------------------------------------------
+ * Resident refiner: VAQ::refine (VAQ.cpp:849-876) with the reference's own numbers, over raw rows that stay on
+ * the device -- what `demo_vaq --refine R1,R2` runs after every search (demo_vaq.cpp:336-345).
+ *   distances  (XTest.row(q) - XTrain.row(l)).squaredNorm() in Eigen's summation order (8-float packets, two
+ *              accumulators, predux, scalar tail; plain sequential below 8 columns): bit for bit the reference's on
+ *              any float data.  vaqhip_refine* above sum sequentially, which equals this only for D < 8 or where
+ *              every partial sum is exact (integer-valued data such as SIFT).
+ *   rows       N x D raw, unprojected float32, row-major; row i has label id_base + i (set_rows_device copies;
+ *              add_rows appends, labels continue at id_base + N).  VAQHIP_ERANGE where labels would pass int32.
+ *   labels_in  nq x R in the order the search returned them, 1 <= k <= R <= 2048.  A label that is negative or
+ *              outside [id_base, id_base + N) is SKIPPED and its row never read (the reference reads out of bounds),
+ *              also in the _device form: the kernel checks every label itself.  Duplicates are kept, as the
+ *              reference keeps them.
+ *   result     nq x k; admission is the reference's heap_top > dist from a heap of FLT_MAX: an infinite or NaN
+ *              distance never enters; unfilled slots -1 / FLT_MAX.
+ *   option "exact_ties"  0 (default): the k smallest by (distance, label).  1: which of several candidates tying at
+ *              the k-th distance survive, and the order equal distances come in, are the reference's -- its loop
+ *              (heap_heapify, heap_pop + heap_push when heap_top > dist, heap_reorder; utils/Heap.hpp) is replayed
+ *              over the R distances in candidate order: labels and distances equal VAQ::refine's slot for slot.
+ * vaqhip_search_refine = the index's search with k = R (its own method and options, "exact_ties" included) followed
+ * by the refine of that result in the order the search returned it; the candidates never leave the device.  Equals
+ * vaqhip_search followed by vaqhip_refiner_refine on the same inputs.  R <= VAQHIP_MAX_K.  VAQHIP_ESTATE when the
+ * refiner's N or id_base differ from the index's, VAQHIP_EINVAL when the two live on different devices or differ in D.
+ * The host forms are synchronous; the _device forms take device pointers on the refiner's GPU, enqueue on `stream`
+ * and never synchronise (the fused one grows its candidate buffer on first use).  Calls on one refiner are serialised
+ * on the host; set_rows / add_rows wait for the device to go idle before rows are moved or replaced.
+ * ------------------------------------------------------------------------- */
+typedef struct vaqhip_refiner vaqhip_refiner;
+int vaqhip_refiner_create(vaqhip_refiner **out, int device_id, int D);
+void vaqhip_refiner_destroy(vaqhip_refiner *r);
+int vaqhip_refiner_set_rows(vaqhip_refiner *r, const float *X_rowmajor, int64_t N, int64_t id_base);
+int vaqhip_refiner_set_rows_device(vaqhip_refiner *r, const float *d_X, int64_t N, int64_t id_base, void *stream);
+int vaqhip_refiner_add_rows(vaqhip_refiner *r, const float *X_rowmajor, int64_t n_new);
+int vaqhip_refiner_set_option(vaqhip_refiner *r, const char *key, int64_t value);
+int vaqhip_refiner_refine(vaqhip_refiner *r, const float *queries_rowmajor, int nq, const int32_t *labels_in, int R,
+                          int k, int32_t *labels_out, float *distances_out);
+int vaqhip_refiner_refine_device(vaqhip_refiner *r, const float *d_queries, int nq, const int32_t *d_labels_in, int R,
+                                 int k, int32_t *d_labels_out, float *d_distances_out, void *stream);
+int vaqhip_search_refine(vaqhip_index *ix, vaqhip_refiner *r, const float *queries_raw_rowmajor, int nq, int R, int k,
+                         int32_t *labels_out, float *distances_out);
+int vaqhip_search_refine_device(vaqhip_index *ix, vaqhip_refiner *r, const float *d_queries_raw, int nq, int R, int k,
+                                int32_t *d_labels_out, float *d_distances_out, void *stream);
 
 /* Multi-GPU exchange step: after an all-gather of per-shard
  * results laid out [n_lists][nq][k] (labels already global), keep per query

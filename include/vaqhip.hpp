@@ -104,6 +104,7 @@ public:
   VaqHip(const VaqHip &) = delete;
   VaqHip &operator=(const VaqHip &) = delete;
   ~VaqHip() {
+    vaqhip_refiner_destroy(rf_);
     vaqhip_index_destroy(h_);
     vaqhip_multi_destroy(mh_);
   }
@@ -341,6 +342,39 @@ public:
     return ret;
   }
 
+  // The refine loop of demo_vaq.cpp:336-345 without the round trips (vaqhip.h, "Resident refiner"; not in the
+  // reference, whose XTrain is in host memory anyway): setRefineDataset uploads the raw rows once -- row i has label
+  // mIdBase + i --, search(XTest, k, refineNum) is search(XTest, refineNum) followed by refine(.., k) with the
+  // candidates kept on the device, distances in Eigen's summation order.  refineExactTies: the k best are the
+  // reference heap's, slot for slot (option "exact_ties" of the refiner).  Single device only; XTest is the raw
+  // query, as wide as the index.
+  bool refineExactTies = false;
+  template <class MatT> void setRefineDataset(const MatT &XTrain) {
+    if (rf_ && rf_dim_ != (int)XTrain.cols()) {
+      vaqhip_refiner_destroy(rf_);
+      rf_ = nullptr;
+    }
+    if (!rf_) check(vaqhip_refiner_create(&rf_, mDevice, (int)XTrain.cols()));
+    rf_dim_ = (int)XTrain.cols();
+    check(vaqhip_refiner_set_rows(rf_, XTrain.data(), (int64_t)XTrain.rows(), mIdBase));
+  }
+  template <class Mat> LabelDistVecF search(const Mat &XTest, const int k, const int refineNum) {
+    if (!(mMethods & methodsAllowed_))
+      throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: only HEAP / EA / TI are implemented on this path");
+    if (!rf_) throw Error(VAQHIP_ESTATE, "vaqhip: search(XTest, k, refineNum) needs setRefineDataset() first");
+    sync();
+    if (mh_) throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: the resident refiner serves one device (no setDevices)");
+    if ((int)XTest.cols() != mTotalDim()) throw Error(VAQHIP_EINVAL, "vaqhip: XTest has the wrong width");
+    check(vaqhip_refiner_set_option(rf_, "exact_ties", refineExactTies ? 1 : 0));
+    LabelDistVecF ret;
+    const size_t nq = (size_t)XTest.rows();
+    ret.labels.resize(k * nq);
+    ret.distances.resize(k * nq);
+    check(vaqhip_search_refine(h_, rf_, XTest.data(), (int)nq, refineNum, k, ret.labels.data(), ret.distances.data()));
+    return ret;
+  }
+  vaqhip_refiner *refinerHandle() { return rf_; }
+
   // Copy the search state out of a reference `VAQ` object (duck-typed: the
   // members of VAQ.hpp:51-75, Eigen matrices).  Instantiate only in a
   // translation unit that includes the reference's VAQ.hpp.
@@ -410,6 +444,8 @@ private:
   }
   vaqhip_index *h_ = nullptr;
   vaqhip_multi *mh_ = nullptr;
+  vaqhip_refiner *rf_ = nullptr;
+  int rf_dim_ = 0;
   bool codes_set_ = false;
   bool ti_set_ = false;
   int exact_pushed_ = 0;  // the value of exactTies the index holds from the last push
@@ -472,6 +508,17 @@ public:
 
   // VAQ::search: pushes mOffsets / mScale when they changed, then runs the method in force
   template <class Mat> LabelDistVecF search(const Mat &XTest, const int k, bool verbose = false) {
+    pushQuantization();
+    return VaqHip::search(XTest, k, verbose);
+  }
+  // ... and the search fused with the resident refine (VaqHip::search(XTest, k, refineNum))
+  template <class Mat> LabelDistVecF search(const Mat &XTest, const int k, const int refineNum) {
+    pushQuantization();
+    return VaqHip::search(XTest, k, refineNum);
+  }
+
+private:
+  void pushQuantization() {
     sync();
     if (mOffsets.size() == (size_t)mHighestSubs() && mScale.size() == mOffsets.size() &&
         (pushedFor_ != current() || pushedOffsets_ != mOffsets || pushedScale_ != mScale ||
@@ -487,10 +534,7 @@ public:
     }
     if (multiHandle() && fastOnly() && !fastQuantPushed_)
       throw Error(VAQHIP_ESTATE, "vaqhip: method FAST needs mOffsets / mScale (learnQuantization) first");
-    return VaqHip::search(XTest, k, verbose);
   }
-
-private:
   // the index the quantisation was last pushed to: the multi-device one when setDevices is in force
   const void *current() { return multiHandle() ? (const void *)multiHandle() : (const void *)handle(); }
   static void checkFast(int rc, bool multi) {

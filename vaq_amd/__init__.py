@@ -5,10 +5,11 @@ Product surface:
   include/vaqhip.hpp          C++ adapter with the reference's names (class VaqHip)
   vaq_amd.VaqHip              Python mirror of the same interface, over the C ABI
   vaq_amd.VaqHipFast          the same with the FAST search method (uint8 tables, 4-bit codes)
+  vaq_amd.VaqRefiner          VAQ::refine over raw rows resident on the device, reference-exact
 There is no CPU path: importing works anywhere, but every compute call needs
 the HIP library and a GPU and raises otherwise.
 """
 from ._lib import VaqHipError, lib_path, load  # noqa: F401
-from .index import LabelDistVec, NNMethod, VaqHip, VaqHipFast  # noqa: F401
+from .index import LabelDistVec, NNMethod, VaqHip, VaqHipFast, VaqRefiner  # noqa: F401
 
-__all__ = ["VaqHip", "VaqHipFast", "NNMethod", "LabelDistVec", "VaqHipError", "load", "lib_path"]
+__all__ = ["VaqHip", "VaqHipFast", "VaqRefiner", "NNMethod", "LabelDistVec", "VaqHipError", "load", "lib_path"]

@@ -26,6 +26,9 @@ SYMBOLS = [
     "vaqhip_lut_fit_quantiles", "vaqhip_lut_fit_quantiles_device", "vaqhip_lut_fit_set_timing",
     "vaqhip_last_lut_fit_timing", "vaqhip_index_set_lut_quantiles", "vaqhip_encode_lut", "vaqhip_encode_lut_device",
     "vaqhip_refine", "vaqhip_refine_device",
+    "vaqhip_refiner_create", "vaqhip_refiner_destroy", "vaqhip_refiner_set_rows", "vaqhip_refiner_set_rows_device",
+    "vaqhip_refiner_add_rows", "vaqhip_refiner_set_option", "vaqhip_refiner_refine", "vaqhip_refiner_refine_device",
+    "vaqhip_search_refine", "vaqhip_search_refine_device",
     "vaqhip_index_info", "vaqhip_set_option", "vaqhip_last_timing", "vaqhip_last_error",
     "vaqhip_version", "vaqhip_device_count",
     "vaqhip_multi_create", "vaqhip_multi_destroy", "vaqhip_multi_set_codes_u16", "vaqhip_multi_add_codes_u16",
@@ -149,6 +152,17 @@ def load():
     L.vaqhip_encode_lut_device.argtypes = [vp, vp, i64, i32, vp, vp]
     L.vaqhip_refine.argtypes = [i32, vp, i32, i32, vp, i64, vp, i32, i32, vp, vp]
     L.vaqhip_refine_device.argtypes = [i32, vp, i32, i32, vp, vp, i32, i32, vp, vp, vp]
+    L.vaqhip_refiner_create.argtypes = [C.POINTER(vp), i32, i32]
+    L.vaqhip_refiner_destroy.argtypes = [vp]
+    L.vaqhip_refiner_destroy.restype = None
+    L.vaqhip_refiner_set_rows.argtypes = [vp, vp, i64, i64]
+    L.vaqhip_refiner_set_rows_device.argtypes = [vp, vp, i64, i64, vp]
+    L.vaqhip_refiner_add_rows.argtypes = [vp, vp, i64]
+    L.vaqhip_refiner_set_option.argtypes = [vp, C.c_char_p, i64]
+    L.vaqhip_refiner_refine.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
+    L.vaqhip_refiner_refine_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp]
+    L.vaqhip_search_refine.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
+    L.vaqhip_search_refine_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.vaqhip_merge_topk_strided_device.argtypes = [i32, vp, vp, i32, i64, i64, i32, i32, vp, vp, vp]
     L.vaqhip_merge_fast_device.argtypes = [i32, vp, i64, i32, i64, vp, vp, i32, i64, i64, i32, i32, vp, vp, vp]
     L.vaqhip_index_info.argtypes = [vp, C.POINTER(Info)]

@@ -150,6 +150,14 @@ hipError_t launch_lut_encode(const float *Xp, int64_t n, int D, const SubDesc *h
 hipError_t launch_refine(const float *Q, int nq, int D, const float *dataset, const float *rows,
                          const int32_t *labels_in, int R, int k, int32_t *labels, float *dist,
                          hipStream_t st);
+// VAQ::refine over resident raw rows (vaq_refine.hip): rows is N x D, row i carries label id_base + i; distances in
+// Eigen's summation order; a label outside [id_base, id_base + N) is skipped and its row never read.  exact != 0: the
+// k best are the reference heap's (VAQ.cpp:863-872), else the k smallest by (distance, label).  1 <= k <= R <= 2048,
+// D <= refine_rows_max_dim()
+size_t refine_rows_max_dim();
+hipError_t launch_refine_rows(const float *Q, int nq, int D, const float *rows, int64_t N, int64_t id_base,
+                              const int32_t *labels_in, int R, int k, int exact, int32_t *labels, float *dist,
+                              hipStream_t st);
 // dwords the packed layout needs for `rows` rows
 int64_t packed_words(int64_t rows, int M, int layout, int W);
 // Pack rows [row_begin, row_end) (codes_u16 points at row_begin; row_begin a

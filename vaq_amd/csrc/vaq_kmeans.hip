@@ -6,7 +6,7 @@
 //   assign      sqrt((x - mean).squaredNorm()) per (row, centre), centres ascending, strict `<` on the square
 //               roots (the first minimum wins, a NaN never does).  squaredNorm is Eigen's linear vectorised
 //               reduction (Eigen/src/Core/Redux.h, 8-float packets, two accumulators, unaligned start 0):
-//               sq_norm_eigen below
+//               sq_norm_eigen (vaq_restated.h)
 //   accumulate  the reference runs two OpenMP threads with a static schedule: rows [0, ceil(n/2)) and the rest.
 //               Per thread, centre and column a float sum from +0 in ascending row order -- here a stable sort
 //               of the rows by (half, centre) and one thread per (half, centre, column) walking its run
@@ -16,6 +16,7 @@
 // No float atomics, no MFMA, no reassociation.
 #include "kmeans_sample.h"
 #include "vaq_kernels.h"
+#include "vaq_restated.h"
 #include "vaqhip_dev.h"
 
 #include <algorithm>
@@ -91,47 +92,6 @@ __global__ void km_seed_kernel(const float *__restrict__ X, int d, const int *__
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= T * d) return;
   means[i] = X[(size_t)seed_rows[i / d] * d + i % d];
-}
-
-__device__ __forceinline__ float km_sq(float x, float m) {
-  const float t = x - m;
-  return t * t;
-}
-
-// (x - m).squaredNorm() as Eigen reduces it; x[j] is read at xs[j * xstride] (UNIT: at xs[j])
-template <bool UNIT>
-__device__ __forceinline__ float sq_norm_eigen(const float *xs, int xstride, const float *__restrict__ m, int d) {
-#define T_(j) km_sq(xs[UNIT ? (size_t)(j) : (size_t)(j) * xstride], m[j])
-  if (d < 8) {  // too small to vectorise: res = coeff(0); res += coeff(i)
-    float res = T_(0);
-    for (int j = 1; j < d; j++) res += T_(j);
-    return res;
-  }
-  const int end1 = (d / 8) * 8, end2 = (d / 16) * 16;
-  float a0[8], a1[8];
-#pragma unroll
-  for (int l = 0; l < 8; l++) a0[l] = T_(l);
-  if (end1 > 8) {
-#pragma unroll
-    for (int l = 0; l < 8; l++) a1[l] = T_(8 + l);
-    for (int i = 16; i < end2; i += 16) {
-#pragma unroll
-      for (int l = 0; l < 8; l++) a0[l] += T_(i + l);
-#pragma unroll
-      for (int l = 0; l < 8; l++) a1[l] += T_(i + 8 + l);
-    }
-#pragma unroll
-    for (int l = 0; l < 8; l++) a0[l] += a1[l];
-    if (end1 > end2) {
-#pragma unroll
-      for (int l = 0; l < 8; l++) a0[l] += T_(end2 + l);
-    }
-  }
-  // predux<Packet8f>: the halves added, then (b0 + b2) + (b1 + b3)
-  float res = ((a0[0] + a0[4]) + (a0[2] + a0[6])) + ((a0[1] + a0[5]) + (a0[3] + a0[7]));
-  for (int j = end1; j < d; j++) res += T_(j);
-  return res;
-#undef T_
 }
 
 // One row per thread.  X_LDS: the workgroup's decoded rows sit in LDS as [dim][row] (each thread reads its own

@@ -1,0 +1,157 @@
+// vaq_refine.hip -- VAQ::refine (VAQ.cpp:849-876) over raw rows resident on the device, with the reference's own
+// numbers: the distance is (XTest.row(q) - XTrain.row(l)).squaredNorm() in Eigen's summation order (sq_norm_eigen in
+// vaq_restated.h is the specification), the k best are kept by the reference's heap on request.
+//
+// One workgroup per query, the query row staged in LDS.  A candidate row is read by 16 adjacent lanes, 64 contiguous
+// bytes per step, four candidates per wave.  Lane j of the group IS Eigen's accumulator lane: a0[j] for j < 8,
+// a1[j - 8] otherwise, adding (q[i + j] - y[i + j])^2 for i = 0, 16, 32, ... in that order.  Then, inside the 16 lanes:
+// a0 += a1; the odd eighth packet (D mod 16 >= 8) is added to a0; predux = ((a0+a4)+(a2+a6)) + ((a1+a5)+(a3+a7)); the
+// scalar tail is added element by element.  The shuffles move operands between lanes, they do not regroup the sums:
+// every addition has the operands the specification gives it (fp add commutes, its grouping is what is fixed).
+// Compiled with -ffp-contract=off like the rest: no FMA, no MFMA, no float atomics; plain vector stores.
+//
+// A label that is negative or outside [id_base, id_base + N) is skipped HERE, before its row's address is formed
+// (the reference would read out of bounds): a device caller can hand over any list.
+#include "vaq_kernels.h"
+#include "vaq_restated.h"
+#include "vaq_scan.h"
+
+namespace vaq {
+
+constexpr int RF_THREADS = 256;
+constexpr int RF_CAP = 2048;    // candidates per query
+constexpr int RF_GROUP = 16;    // lanes per candidate row
+constexpr int RF_GROUPS = RF_THREADS / RF_GROUP;
+
+// the value lane `src` of this lane's group holds
+__device__ __forceinline__ float rf_from(float v, int gbase, int src) { return __shfl(v, gbase + src, 64); }
+
+// Squared distance of the group's row y to the staged query qs, complete in lane 0 of the group.  Every lane of the
+// wave runs every shuffle; `valid` (the same in all 16 lanes of a group) only masks the loads of a skipped candidate.
+__device__ __forceinline__ float rf_group_sq_norm(const float *qs, const float *__restrict__ y, int D, bool valid, int j,
+                                                  int gbase) {
+#define T_(idx, ok) ((valid && (ok)) ? km_sq(qs[idx], y[idx]) : 0.0f)
+  if (D < 8) {  // res = coeff(0); res += coeff(i)
+    const float t = T_(j, j < D);
+    float res = rf_from(t, gbase, 0);
+    for (int e = 1; e < D; e++) res += rf_from(t, gbase, e);
+    return res;
+  }
+  const int end1 = (D / 8) * 8, end2 = (D / 16) * 16;
+  float acc;
+  if (end2 >= 16) {  // a0 = packet 0, a1 = packet 1, then the loop over pairs of packets
+    acc = T_(j, true);
+#pragma unroll 4
+    for (int i = 16; i < end2; i += 16) acc += T_(i + j, true);
+  } else {  // 8 <= D < 16: only a0 exists
+    acc = T_(j, j < 8);
+  }
+  if (end1 > 8) {
+    acc += rf_from(acc, gbase, (j + 8) & 15);                // lanes 0..7: a0 += a1
+    if (end1 > end2) acc += T_(end2 + j, j < 8);             // the odd eighth packet
+  }
+  // predux<Packet8f> in lanes 0..7: the halves added, then (b0 + b2) + (b1 + b3)
+  acc += rf_from(acc, gbase, j ^ 4);
+  acc += rf_from(acc, gbase, j ^ 2);
+  acc += rf_from(acc, gbase, j ^ 1);
+  const float t = T_(end1 + j, end1 + j < D);  // the scalar tail, at most 7 elements
+  float res = acc;
+  for (int e = 0; e < D - end1; e++) res += rf_from(t, gbase, e);
+  return res;
+#undef T_
+}
+
+// EXACT: the k best are what the reference's loop leaves (VAQ.cpp:863-872: heap_heapify, pop + push when
+// heap_top > dist, heap_reorder), replayed by one thread over the R distances in candidate order.  Otherwise the k
+// smallest by (distance, label).  Either way a distance that is not below FLT_MAX never enters (the heap starts from
+// FLT_MAX: an infinite or NaN distance fails heap_top > dist), duplicates are kept, unfilled slots are -1 / FLT_MAX.
+template <bool EXACT>
+__global__ __launch_bounds__(RF_THREADS) void refine_rows_kernel(const float *__restrict__ Q, int D,
+                                                                 const float *__restrict__ rows, int64_t N,
+                                                                 int64_t id_base, const int32_t *__restrict__ labels_in,
+                                                                 int R, int k, int32_t *__restrict__ labels,
+                                                                 float *__restrict__ dist) {
+  __shared__ float sd[RF_CAP];
+  __shared__ int si[RF_CAP];
+  __shared__ float hv[EXACT ? RF_CAP : 1];
+  __shared__ int hi[EXACT ? RF_CAP : 1];
+  __shared__ int s_kept;
+  extern __shared__ float qs[];
+  const int q = blockIdx.x, tid = threadIdx.x;
+  for (int j = tid; j < D; j += RF_THREADS) qs[j] = Q[(size_t)q * D + j];
+  __syncthreads();
+  const int g = tid / RF_GROUP, j = tid % RF_GROUP, gbase = (tid & 63) & ~(RF_GROUP - 1);
+  for (int c0 = 0; c0 < R; c0 += RF_GROUPS) {  // (uniform trip count: the shuffles run in whole waves)
+    const int c = c0 + g;
+    const int lab = c < R ? labels_in[(size_t)q * R + c] : -1;
+    const int64_t row = (int64_t)lab - id_base;
+    const bool valid = lab >= 0 && row >= 0 && row < N;
+    const float *y = rows + (valid ? (size_t)row * D : (size_t)0);
+    const float res = rf_group_sq_norm(qs, y, D, valid, j, gbase);
+    if (j == 0 && c < R) {
+      if (EXACT) {
+        sd[c] = valid ? res : INFINITY;
+        si[c] = lab;
+      } else {
+        const bool in = valid && res < FLT_MAX;
+        sd[c] = in ? res : INFINITY;
+        si[c] = in ? lab : ID_SENTINEL;
+      }
+    }
+  }
+  const size_t o = (size_t)q * k;
+  if (EXACT) {
+    __syncthreads();
+    if (tid == 0) {
+      refheap::heapify(k, hv, hi);
+      for (int i = 0; i < R; i++) {
+        const float d = sd[i];
+        if (hv[0] > d) {
+          refheap::pop(k, hv, hi);
+          refheap::push(k, hv, hi, d, si[i]);
+        }
+      }
+      s_kept = refheap::reorder(k, hv, hi);
+    }
+    __syncthreads();
+    const int kept = s_kept;
+    for (int i = tid; i < k; i += RF_THREADS) {
+      labels[o + i] = i < kept ? hi[k - kept + i] : -1;
+      dist[o + i] = i < kept ? hv[k - kept + i] : FLT_MAX;
+    }
+  } else {
+    int P = 2;
+    while (P < R) P <<= 1;
+    for (int i = R + tid; i < P; i += RF_THREADS) {
+      sd[i] = INFINITY;
+      si[i] = ID_SENTINEL;
+    }
+    __syncthreads();
+    bitonic_sort<true>(sd, si, P, tid, RF_THREADS);
+    for (int i = tid; i < k; i += RF_THREADS) {
+      const bool ok = i < P && si[i] != ID_SENTINEL;
+      labels[o + i] = ok ? si[i] : -1;
+      dist[o + i] = ok ? sd[i] : FLT_MAX;
+    }
+  }
+}
+
+size_t refine_rows_max_dim() { return (size_t)(64 * 1024 - 4 * RF_CAP * sizeof(float) - 64) / sizeof(float); }
+
+hipError_t launch_refine_rows(const float *Q, int nq, int D, const float *rows, int64_t N, int64_t id_base,
+                              const int32_t *labels_in, int R, int k, int exact, int32_t *labels, float *dist,
+                              hipStream_t st) {
+  if (nq == 0) return hipSuccess;
+  if (R > RF_CAP || R < 1 || k < 1 || k > R || D < 1 || (size_t)D > refine_rows_max_dim() || N < 0)
+    return hipErrorInvalidValue;
+  const size_t lds = (size_t)D * sizeof(float);
+  if (exact)
+    hipLaunchKernelGGL(refine_rows_kernel<true>, dim3(nq), dim3(RF_THREADS), lds, st, Q, D, rows, N, id_base, labels_in,
+                       R, k, labels, dist);
+  else
+    hipLaunchKernelGGL(refine_rows_kernel<false>, dim3(nq), dim3(RF_THREADS), lds, st, Q, D, rows, N, id_base, labels_in,
+                       R, k, labels, dist);
+  return hipGetLastError();
+}
+
+}  // namespace vaq

@@ -1,13 +1,14 @@
 // vaq_restated.h -- library functions whose behaviour on EQUAL keys is part of the reference's answers,
 // restated so that host and device run the same statements: libstdc++'s std::sort (stdsort) and heap
-// functions (stdheap), and the reference's own heap, utils/Heap.hpp (refheap).  Each is pinned on the CPU
-// against the real thing: tests/cpp/stdsort_test.cpp, stdsort_generic_test.cpp, stdheap_test.cpp and
-// refheap_test.cpp.
+// functions (stdheap), the reference's own heap, utils/Heap.hpp (refheap), and the summation order of Eigen's
+// squaredNorm (sq_norm_eigen).  Each is pinned on the CPU against the real thing: tests/cpp/stdsort_test.cpp,
+// stdsort_generic_test.cpp, stdheap_test.cpp, refheap_test.cpp and refine_order_test.cpp.
 #ifndef VAQ_RESTATED_H_
 #define VAQ_RESTATED_H_
 
 #include <hip/hip_runtime.h>
 #include <float.h>
+#include <stddef.h>
 #include <stdint.h>
 
 namespace vaq {
@@ -300,6 +301,53 @@ __host__ __device__ inline int reorder(const int k, float *hval, int *hid) {
   return ii;
 }
 }  // namespace refheap
+
+// ---------------------------------------------------------------------------------------------------
+// Eigen's (x - m).squaredNorm() over float rows (Eigen/src/Core/Redux.h, redux_impl<.., LinearVectorizedTraversal,
+// NoUnrolling>: 8-float packets, two accumulators, predux, scalar tail; fewer than 8 columns: the plain sequential
+// sum), as the k-means of clusterTI (vaq_kmeans.hip) and VAQ::refine (VAQ.cpp:866; vaq_refine.hip spreads the same
+// additions over 16 lanes) evaluate it.  Pinned against the compiled reference by tests/golden/kmeans and
+// tests/golden/refine (tests/cpp/refine_order_test.cpp runs this very function on the host).
+__host__ __device__ __forceinline__ float km_sq(float x, float m) {
+  const float t = x - m;
+  return t * t;
+}
+
+// (x - m).squaredNorm() as Eigen reduces it; x[j] is read at xs[j * xstride] (UNIT: at xs[j])
+template <bool UNIT>
+__host__ __device__ __forceinline__ float sq_norm_eigen(const float *xs, int xstride, const float *__restrict__ m, int d) {
+#define T_(j) km_sq(xs[UNIT ? (size_t)(j) : (size_t)(j) * xstride], m[j])
+  if (d < 8) {  // too small to vectorise: res = coeff(0); res += coeff(i)
+    float res = T_(0);
+    for (int j = 1; j < d; j++) res += T_(j);
+    return res;
+  }
+  const int end1 = (d / 8) * 8, end2 = (d / 16) * 16;
+  float a0[8], a1[8];
+#pragma unroll
+  for (int l = 0; l < 8; l++) a0[l] = T_(l);
+  if (end1 > 8) {
+#pragma unroll
+    for (int l = 0; l < 8; l++) a1[l] = T_(8 + l);
+    for (int i = 16; i < end2; i += 16) {
+#pragma unroll
+      for (int l = 0; l < 8; l++) a0[l] += T_(i + l);
+#pragma unroll
+      for (int l = 0; l < 8; l++) a1[l] += T_(i + 8 + l);
+    }
+#pragma unroll
+    for (int l = 0; l < 8; l++) a0[l] += a1[l];
+    if (end1 > end2) {
+#pragma unroll
+      for (int l = 0; l < 8; l++) a0[l] += T_(end2 + l);
+    }
+  }
+  // predux<Packet8f>: the halves added, then (b0 + b2) + (b1 + b3)
+  float res = ((a0[0] + a0[4]) + (a0[2] + a0[6])) + ((a0[1] + a0[5]) + (a0[3] + a0[7]));
+  for (int j = end1; j < d; j++) res += T_(j);
+  return res;
+#undef T_
+}
 
 }  // namespace vaq
 #endif  // VAQ_RESTATED_H_

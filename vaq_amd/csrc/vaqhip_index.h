@@ -1,7 +1,8 @@
 // vaqhip_index.h -- what the host files of the single-device index share: the index itself, its device
 // buffers (vaqhip_dev.h), the entry preamble, the workspace scope, the launch plan and the few functions
 // that cross files.  Private to vaqhip_api.cpp,
-// vaqhip_plan.cpp, vaqhip_search.cpp, vaqhip_codes.cpp, vaqhip_fast.cpp and vaqhip_lutfit.cpp: the multi-device host
+// vaqhip_plan.cpp, vaqhip_search.cpp, vaqhip_codes.cpp, vaqhip_fast.cpp and vaqhip_lutfit.cpp (vaqhip_refiner.cpp takes
+// fail(), HIP_TRY and the device types from here and reaches the index through include/vaqhip.h): the multi-device host
 // (vaqhip_multi*.cpp) sees the index through include/vaqhip.h and vaqhip_internal.h only.
 #ifndef VAQHIP_INDEX_H
 #define VAQHIP_INDEX_H

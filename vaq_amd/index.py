@@ -507,6 +507,22 @@ class VaqHip:
                                              _ptr(lab), R, k, _ptr(ret.labels), _ptr(ret.distances)))
         return ret
 
+    def search_refine(self, XTest: np.ndarray, R: int, k: int, refiner: "VaqRefiner") -> LabelDistVec:
+        """search(XTest, R) followed by VAQ::refine to k against the refiner's resident rows, in one call
+        (vaqhip_search_refine): the R candidates per query never leave the device.  The search runs under this
+        index's own method and options; the result equals search() + refiner.refine() on the same inputs."""
+        if not (self.mMethods & self._METHODS):
+            raise _lib.VaqHipError(-2, "only HEAP / EA / TI are implemented on this path")
+        self._ensure_codes()
+        X = np.ascontiguousarray(XTest, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != self.mTotalDim:
+            raise _lib.VaqHipError(-1, f"XTest {X.shape} is not nq x {self.mTotalDim}")
+        nq = X.shape[0]
+        ret = LabelDistVec(np.empty(nq * k, np.int32), np.empty(nq * k, np.float32))
+        _lib.check(_lib.load().vaqhip_search_refine(self._h, refiner._h, _ptr(X), nq, int(R), int(k), _ptr(ret.labels),
+                                                    _ptr(ret.distances)))
+        return ret
+
     # -------------------------------------------------------- test hooks ---
     def build_lut(self, XTest: np.ndarray, projected: bool = False) -> np.ndarray:
         """CreateLUT for every query in the reference's LUTType layout:
@@ -568,6 +584,110 @@ class VaqHip:
             self._h = C.c_void_p()
             self._sig = None
             self._codes_sig = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class VaqRefiner:
+    """The raw rows VAQ::refine reads (VAQ.cpp:849-876), resident on the device, and the reference-exact re-rank
+    over them (vaqhip_refiner_*): distances in Eigen's summation order, bit for bit the reference's on any float
+    data; with exact_ties also its heap's choice and order among equal distances.
+
+        r = VaqRefiner(D, device=0)
+        r.set_rows(XTrain)                       # one upload; row i has label id_base + i
+        r.exact_ties = True
+        ans = r.refine(XTest, candidates, k)     # candidates: nq x R labels in the order the search returned them
+        ans = vaq.search_refine(XTest, R, k, r)  # or fused with the search: the candidates stay on the device
+    """
+
+    def __init__(self, D: int, device: int = 0):
+        self.D = int(D)
+        self.device = device
+        self._exact = False
+        self._h = C.c_void_p()
+        h = C.c_void_p()
+        _lib.check(_lib.load().vaqhip_refiner_create(C.byref(h), device, self.D))
+        self._h = h
+
+    def _rows(self, X) -> np.ndarray:
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != self.D:
+            raise _lib.VaqHipError(-1, f"rows {X.shape} are not n x {self.D}")
+        return X
+
+    def set_rows(self, XTrain, id_base: int = 0) -> None:
+        """Replace the rows: a host array, or a contiguous float32 torch tensor on the refiner's device (copied)."""
+        if hasattr(XTrain, "data_ptr"):
+            import torch
+            x = XTrain
+            if not (x.is_cuda and x.device.index == self.device and x.dtype == torch.float32 and x.is_contiguous()
+                    and x.dim() == 2 and x.shape[1] == self.D):
+                raise _lib.VaqHipError(-1, f"device rows must be a contiguous float32 n x {self.D} tensor on cuda:{self.device}")
+            st = torch.cuda.current_stream(x.device).cuda_stream
+            _lib.check(_lib.load().vaqhip_refiner_set_rows_device(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
+                                                                  int(id_base), C.c_void_p(st)))
+            return
+        X = self._rows(XTrain)
+        _lib.check(_lib.load().vaqhip_refiner_set_rows(self._h, _ptr(X), X.shape[0], int(id_base)))
+
+    def add_rows(self, X) -> None:
+        """Append rows; their labels continue behind the rows already held."""
+        X = self._rows(X)
+        _lib.check(_lib.load().vaqhip_refiner_add_rows(self._h, _ptr(X), X.shape[0]))
+
+    @property
+    def exact_ties(self) -> bool:
+        return self._exact
+
+    @exact_ties.setter
+    def exact_ties(self, on: bool) -> None:
+        _lib.check(_lib.load().vaqhip_refiner_set_option(self._h, b"exact_ties", 1 if on else 0))
+        self._exact = bool(on)
+
+    def refine(self, XTest, answersIn, k: int) -> LabelDistVec:
+        """answersIn: a LabelDistVec (as search() returns it) or an array of nq * R labels.  Labels that are negative
+        or name no resident row are skipped."""
+        Xq = self._rows(XTest)
+        nq = Xq.shape[0]
+        lab = np.ascontiguousarray(getattr(answersIn, "labels", answersIn), dtype=np.int32).reshape(-1)
+        R = lab.size // max(nq, 1)
+        if nq and lab.size != nq * R:
+            raise _lib.VaqHipError(-1, f"{lab.size} labels for {nq} queries")
+        ret = LabelDistVec(np.empty(nq * k, np.int32), np.empty(nq * k, np.float32))
+        if nq == 0:
+            return ret
+        _lib.check(_lib.load().vaqhip_refiner_refine(self._h, _ptr(Xq), nq, _ptr(lab), R, int(k), _ptr(ret.labels),
+                                                     _ptr(ret.distances)))
+        return ret
+
+    def refine_device(self, d_queries, d_labels_in, k: int, out=None):
+        """torch CUDA tensors in and out (queries nq x D float32, labels nq x R int32), enqueued on torch's current
+        stream, no synchronisation."""
+        import torch
+        q = d_queries.contiguous()
+        lin = d_labels_in.contiguous()
+        assert q.is_cuda and q.dtype == torch.float32 and q.shape[1] == self.D
+        assert lin.is_cuda and lin.dtype == torch.int32 and lin.shape[0] == q.shape[0]
+        nq, R = lin.shape
+        if out is not None:
+            labels, dists = out
+        else:
+            labels = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+            dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        st = torch.cuda.current_stream(q.device).cuda_stream
+        _lib.check(_lib.load().vaqhip_refiner_refine_device(
+            self._h, C.c_void_p(q.data_ptr()), nq, C.c_void_p(lin.data_ptr()), R, int(k),
+            C.c_void_p(labels.data_ptr()), C.c_void_p(dists.data_ptr()), C.c_void_p(st)))
+        return labels, dists
+
+    def close(self) -> None:
+        if self._h:
+            _lib.load().vaqhip_refiner_destroy(self._h)
+            self._h = C.c_void_p()
 
     def __del__(self):
         try:
