@@ -18,8 +18,9 @@
 //                                           raw vectors; results go to <result>_R<R> when several R are given)
 //               [--refine-resident]        (with --refine: the raw vectors are uploaded once and every R is ONE fused
 //                                           call, search + refine with the candidates kept on the device; distances in
-//                                           the reference's (Eigen's) summation order; needs --timeseries-size == D
-//                                           and a single device.  --exact-ties 1: also the reference heap's tie order)
+//                                           the reference's (Eigen's) summation order; needs --timeseries-size == D.
+//                                           --exact-ties 1: also the reference heap's tie order.  With --devices the
+//                                           raw vectors are cut over the same GPUs as the code rows: same answer)
 //               [--devices 0,1,2,3]        (shard the rows over these GPUs: RCCL all-gather + merge)
 //               with a ...,FAST method (codes of at most 4 bits): --dataset base.fvecs [--dataset-size N]
 //               [--learn-ratio 0.05]       (demo_vaq.cpp:42, :120-124: VAQ::learnQuantization on the raw dataset)
@@ -182,6 +183,13 @@ int main(int argc, char **argv) {
       vaq.setRefineDataset(datasetrefine);
       std::cout << "== Refine dataset upload: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
                 << " s (" << datasetrefine.rows() << " rows resident)" << std::endl;
+      if (vaq.multiRefinerHandle()) {
+        vaqhip_multi_refiner_info inf;
+        if (vaqhip_multi_refiner_get_info(vaq.multiRefinerHandle(), &inf) == 0)
+          for (int g = 0; g < inf.n_devices; g++)
+            std::cout << "   shard " << g << " (device " << inf.device_ids[g] << "): " << inf.shard_rows[g]
+                      << " rows resident" << std::endl;
+      }
     }
     RowMatrix<int> gt;
     if (a.count("groundtruth")) gt = readIVecs(a["groundtruth"], k);

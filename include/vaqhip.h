@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 111
+#define VAQHIP_VERSION 112
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -530,6 +530,70 @@ int vaqhip_multi_get_info(const vaqhip_multi *mx, vaqhip_multi_info *out);
 /* shard g's single-device index (options, timing, info); owned by the multi index */
 vaqhip_index *vaqhip_multi_shard(vaqhip_multi *mx, int g);
 const char *vaqhip_multi_last_error(void);
+
+/* ---------------------------------------------------------------------------
+ * Multi-device refiner: the resident refiner above with the raw rows cut over several GPUs -- at 1B x 128 floats
+ * the rows (512 GB) fit no single device, the 8 GPUs of a node hold them together.  The answer is the single
+ * refiner's slot for slot, with "exact_ties" on or off and for any number of shards: a candidate's distance depends
+ * on the query and its own row only, the selection on the R (distance, label) pairs in candidate order only.  So
+ * every shard computes the distances of the candidates it holds (the same reduction, Eigen's summation order), and
+ * ONE selection runs on device_ids[0] over the R gathered distances in the original candidate order.  No chain of
+ * replays is needed, unlike the search's "exact_ties".
+ *   cut         the multi index's: shard g holds rows [g * ceil(N/G), (g+1) * ceil(N/G)), row i has label
+ *               id_base + i; add_rows extends the LAST shard (set_rows with the whole matrix re-balances).  Every
+ *               shard's rows are uploaded by its own host thread.
+ *   device_ids  as for vaqhip_multi_create; a device named several times gives logical shards on that GPU.
+ *   a refine    per set of queries: (1) queries (nq * D * 4 bytes) and candidate labels (nq * R * 4) go from
+ *               device_ids[0] to every other shard that holds rows (hipMemcpyPeerAsync behind an event of the caller's
+ *               stream; the first shard reads them in place); (2) every shard runs the distance kernel on its own
+ *               stream; (3) their [nq][R] float planes (nq * R * 4 bytes per shard) are copied to device_ids[0];
+ *               (4) the select kernel runs there and writes the caller's buffers.  Copies only, no RCCL.  Calls of
+ *               more than VAQHIP_MULTI_REFINER_SET queries are served in sets of that size (the gathered planes take
+ *               G * set * R * 4 bytes); results do not depend on it.  One shard: the single refiner's kernel itself, on
+ *               the caller's stream.
+ *   limits      the single refiner's: 1 <= k <= R <= 2048 (VAQHIP_EUNSUPPORTED), sizes that are not positive
+ *               VAQHIP_EINVAL, labels that would pass int32 VAQHIP_ERANGE, D beyond the workgroup's LDS
+ *               VAQHIP_EUNSUPPORTED; labels outside [id_base, id_base + N) are skipped, never read.
+ *   options     "exact_ties" as above; "timing" = 1: device events around the four phases of every following call.
+ * vaqhip_multi_search_refine = vaqhip_multi_search_device with k = R (the multi index's own method and options as they
+ * are, "exact_ties" and its stated exceptions included) into a buffer on device_ids[0], followed by the refine of that
+ * buffer in the order the search returned it; the candidates never reach the host.  R <= VAQHIP_MAX_K.  VAQHIP_ESTATE
+ * when N or id_base differ between the index and the refiner, VAQHIP_EINVAL when D or the device lists differ.
+ * The host forms are synchronous; the _device forms take pointers on device_ids[0], enqueue only and never
+ * synchronise once their buffers have their size (`stream`, a stream of device_ids[0], is made to wait for the
+ * result).  Errors: vaqhip_multi_last_error().  Calls on one refiner are serialised on the host.
+ * ------------------------------------------------------------------------- */
+#define VAQHIP_MULTI_REFINER_SET 16384
+typedef struct vaqhip_multi_refiner vaqhip_multi_refiner;
+int vaqhip_multi_refiner_create(vaqhip_multi_refiner **out, int D, int n_devices, const int *device_ids);
+void vaqhip_multi_refiner_destroy(vaqhip_multi_refiner *r);
+int vaqhip_multi_refiner_set_rows(vaqhip_multi_refiner *r, const float *X_rowmajor, int64_t N, int64_t id_base);
+int vaqhip_multi_refiner_add_rows(vaqhip_multi_refiner *r, const float *X_rowmajor, int64_t n_new);
+int vaqhip_multi_refiner_set_option(vaqhip_multi_refiner *r, const char *key, int64_t value);
+int vaqhip_multi_refiner_refine(vaqhip_multi_refiner *r, const float *queries_rowmajor, int nq, const int32_t *labels_in,
+                                int R, int k, int32_t *labels_out, float *distances_out);
+int vaqhip_multi_refiner_refine_device(vaqhip_multi_refiner *r, const float *d_queries, int nq,
+                                       const int32_t *d_labels_in, int R, int k, int32_t *d_labels_out,
+                                       float *d_distances_out, void *stream);
+int vaqhip_multi_search_refine(vaqhip_multi *mx, vaqhip_multi_refiner *r, const float *queries_raw_rowmajor, int nq,
+                               int R, int k, int32_t *labels_out, float *distances_out);
+int vaqhip_multi_search_refine_device(vaqhip_multi *mx, vaqhip_multi_refiner *r, const float *d_queries_raw, int nq,
+                                      int R, int k, int32_t *d_labels_out, float *d_distances_out, void *stream);
+typedef struct {
+  int n_devices, D;
+  int64_t N, id_base;
+  int device_ids[VAQHIP_MAX_DEVICES];
+  int64_t shard_rows[VAQHIP_MAX_DEVICES];  /* rows resident per shard */
+  int exact_ties;
+  int set_queries;           /* VAQHIP_MULTI_REFINER_SET */
+  /* the last refine made under "timing" = 1, summed over its sets (get_info waits for it); 0 without the option */
+  int last_sets;
+  float last_broadcast_ms;   /* queries and labels to the shards: the slowest shard                         */
+  float last_distances_ms;   /* the distance kernel: the slowest shard (one shard: the whole refine kernel) */
+  float last_gather_ms;      /* the planes to device_ids[0]                                                 */
+  float last_select_ms;      /* the select kernel                                                           */
+} vaqhip_multi_refiner_info;
+int vaqhip_multi_refiner_get_info(vaqhip_multi_refiner *r, vaqhip_multi_refiner_info *out);
 
 /* ----- introspection / tuning -------------------------------------------- */
 typedef struct {

@@ -96,6 +96,7 @@ public:
   std::vector<int> mDevices;
   void setDevices(const std::vector<int> &devices) {
     invalidate();
+    if (devices != mDevices) dropRefiners();  // (they live on the devices named before: setRefineDataset() comes after)
     mDevices = devices;
     if (!devices.empty()) mDevice = devices[0];
   }
@@ -104,7 +105,7 @@ public:
   VaqHip(const VaqHip &) = delete;
   VaqHip &operator=(const VaqHip &) = delete;
   ~VaqHip() {
-    vaqhip_refiner_destroy(rf_);
+    dropRefiners();
     vaqhip_index_destroy(h_);
     vaqhip_multi_destroy(mh_);
   }
@@ -346,34 +347,44 @@ public:
   // reference, whose XTrain is in host memory anyway): setRefineDataset uploads the raw rows once -- row i has label
   // mIdBase + i --, search(XTest, k, refineNum) is search(XTest, refineNum) followed by refine(.., k) with the
   // candidates kept on the device, distances in Eigen's summation order.  refineExactTies: the k best are the
-  // reference heap's, slot for slot (option "exact_ties" of the refiner).  Single device only; XTest is the raw
-  // query, as wide as the index.
+  // reference heap's, slot for slot (option "exact_ties" of the refiner).  After setDevices() the rows are cut over
+  // the same devices as the code rows (vaqhip.h, "Multi-device refiner") and the answer is the same, slot for slot.
+  // XTest is the raw query, as wide as the index.
   bool refineExactTies = false;
   template <class MatT> void setRefineDataset(const MatT &XTrain) {
-    if (rf_ && rf_dim_ != (int)XTrain.cols()) {
-      vaqhip_refiner_destroy(rf_);
-      rf_ = nullptr;
-    }
-    if (!rf_) check(vaqhip_refiner_create(&rf_, mDevice, (int)XTrain.cols()));
+    if (rf_dim_ != (int)XTrain.cols()) dropRefiners();
     rf_dim_ = (int)XTrain.cols();
+    if (!mDevices.empty()) {
+      if (!mrf_) checkMulti(vaqhip_multi_refiner_create(&mrf_, rf_dim_, (int)mDevices.size(), mDevices.data()));
+      checkMulti(vaqhip_multi_refiner_set_rows(mrf_, XTrain.data(), (int64_t)XTrain.rows(), mIdBase));
+      return;
+    }
+    if (!rf_) check(vaqhip_refiner_create(&rf_, mDevice, rf_dim_));
     check(vaqhip_refiner_set_rows(rf_, XTrain.data(), (int64_t)XTrain.rows(), mIdBase));
   }
   template <class Mat> LabelDistVecF search(const Mat &XTest, const int k, const int refineNum) {
     if (!(mMethods & methodsAllowed_))
       throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: only HEAP / EA / TI are implemented on this path");
-    if (!rf_) throw Error(VAQHIP_ESTATE, "vaqhip: search(XTest, k, refineNum) needs setRefineDataset() first");
+    if (!(mDevices.empty() ? (bool)rf_ : (bool)mrf_))
+      throw Error(VAQHIP_ESTATE, "vaqhip: search(XTest, k, refineNum) needs setRefineDataset() first");
     sync();
-    if (mh_) throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: the resident refiner serves one device (no setDevices)");
     if ((int)XTest.cols() != mTotalDim()) throw Error(VAQHIP_EINVAL, "vaqhip: XTest has the wrong width");
-    check(vaqhip_refiner_set_option(rf_, "exact_ties", refineExactTies ? 1 : 0));
     LabelDistVecF ret;
     const size_t nq = (size_t)XTest.rows();
     ret.labels.resize(k * nq);
     ret.distances.resize(k * nq);
+    if (mh_) {
+      checkMulti(vaqhip_multi_refiner_set_option(mrf_, "exact_ties", refineExactTies ? 1 : 0));
+      checkMulti(vaqhip_multi_search_refine(mh_, mrf_, XTest.data(), (int)nq, refineNum, k, ret.labels.data(),
+                                            ret.distances.data()));
+      return ret;
+    }
+    check(vaqhip_refiner_set_option(rf_, "exact_ties", refineExactTies ? 1 : 0));
     check(vaqhip_search_refine(h_, rf_, XTest.data(), (int)nq, refineNum, k, ret.labels.data(), ret.distances.data()));
     return ret;
   }
   vaqhip_refiner *refinerHandle() { return rf_; }
+  vaqhip_multi_refiner *multiRefinerHandle() { return mrf_; }
 
   // Copy the search state out of a reference `VAQ` object (duck-typed: the
   // members of VAQ.hpp:51-75, Eigen matrices).  Instantiate only in a
@@ -444,7 +455,14 @@ private:
   }
   vaqhip_index *h_ = nullptr;
   vaqhip_multi *mh_ = nullptr;
+  void dropRefiners() {
+    vaqhip_refiner_destroy(rf_);
+    rf_ = nullptr;
+    vaqhip_multi_refiner_destroy(mrf_);
+    mrf_ = nullptr;
+  }
   vaqhip_refiner *rf_ = nullptr;
+  vaqhip_multi_refiner *mrf_ = nullptr;  // after setDevices(): the rows cut over mDevices
   int rf_dim_ = 0;
   bool codes_set_ = false;
   bool ti_set_ = false;

@@ -36,6 +36,10 @@ SYMBOLS = [
     "vaqhip_multi_set_lut_quantization", "vaqhip_multi_learn_quantization",
     "vaqhip_multi_cluster_ti_kmeans", "vaqhip_multi_last_kmeans_timing",
     "vaqhip_multi_get_info", "vaqhip_multi_shard", "vaqhip_multi_last_error",
+    "vaqhip_multi_refiner_create", "vaqhip_multi_refiner_destroy", "vaqhip_multi_refiner_set_rows",
+    "vaqhip_multi_refiner_add_rows", "vaqhip_multi_refiner_set_option", "vaqhip_multi_refiner_refine",
+    "vaqhip_multi_refiner_refine_device", "vaqhip_multi_search_refine", "vaqhip_multi_search_refine_device",
+    "vaqhip_multi_refiner_get_info",
 ]
 MAX_DEVICES = 16
 
@@ -85,6 +89,13 @@ class MultiInfo(C.Structure):
     _fields_ = [("n_devices", C.c_int), ("exchange", C.c_int), ("N", C.c_int64), ("id_base", C.c_int64),
                 ("device_ids", C.c_int * 16), ("shard_rows", C.c_int64 * 16), ("last_search_ms", C.c_float),
                 ("last_exchange_ms", C.c_float), ("last_merge_ms", C.c_float)]
+
+
+class MultiRefinerInfo(C.Structure):
+    _fields_ = [("n_devices", C.c_int), ("D", C.c_int), ("N", C.c_int64), ("id_base", C.c_int64),
+                ("device_ids", C.c_int * 16), ("shard_rows", C.c_int64 * 16), ("exact_ties", C.c_int),
+                ("set_queries", C.c_int), ("last_sets", C.c_int), ("last_broadcast_ms", C.c_float),
+                ("last_distances_ms", C.c_float), ("last_gather_ms", C.c_float), ("last_select_ms", C.c_float)]
 
 
 _lib = None
@@ -188,6 +199,17 @@ def load():
     L.vaqhip_multi_shard.argtypes = [vp, i32]
     L.vaqhip_multi_shard.restype = vp
     L.vaqhip_multi_last_error.restype = C.c_char_p
+    L.vaqhip_multi_refiner_create.argtypes = [C.POINTER(vp), i32, i32, C.POINTER(i32)]
+    L.vaqhip_multi_refiner_destroy.argtypes = [vp]
+    L.vaqhip_multi_refiner_destroy.restype = None
+    L.vaqhip_multi_refiner_set_rows.argtypes = [vp, vp, i64, i64]
+    L.vaqhip_multi_refiner_add_rows.argtypes = [vp, vp, i64]
+    L.vaqhip_multi_refiner_set_option.argtypes = [vp, C.c_char_p, i64]
+    L.vaqhip_multi_refiner_refine.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
+    L.vaqhip_multi_refiner_refine_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp]
+    L.vaqhip_multi_search_refine.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
+    L.vaqhip_multi_search_refine_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.vaqhip_multi_refiner_get_info.argtypes = [vp, C.POINTER(MultiRefinerInfo)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:

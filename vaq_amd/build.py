@@ -14,9 +14,10 @@ CSRC = os.path.join(ROOT, "vaq_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "vaq_amd", "lib")
 LIB = os.path.join(LIBDIR, "libvaqhip.so")
 SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_fast.hip", "vaq_lutfit.hip", "vaq_refine.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp", "vaqhip_lutfit.cpp", "vaqhip_refiner.cpp",
-           "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_rccl.cpp"]
-MULTI_SOURCES = ("vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp")
+           "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp", "vaqhip_rccl.cpp"]
+MULTI_SOURCES = ("vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp")
 KERNEL_HEADER = os.path.join(CSRC, "vaq_kernels.h")
+OWNER_HEADER = os.path.join(CSRC, "refine_owner.h")  # the refiner's cut and label -> shard: vaq_kernels.h brings it
 API_HEADER = os.path.join(ROOT, "include", "vaqhip.h")
 
 
@@ -36,7 +37,7 @@ LUTFIT_HEADER = os.path.join(CSRC, "vaq_lutfit.h")  # binaryEncodingLUT's two la
 
 def _deps(src: str):
     # only the host files see the public C header; the scan bodies live in vaq_scan.h
-    deps = [os.path.join(CSRC, src), KERNEL_HEADER]
+    deps = [os.path.join(CSRC, src), KERNEL_HEADER, OWNER_HEADER]
     if src == "vaqhip_rccl.cpp":  # nothing of the index
         return [os.path.join(CSRC, src), RCCL_HEADER]
     if src.endswith(".cpp"):

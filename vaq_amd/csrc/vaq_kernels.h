@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "refine_owner.h"
+
 namespace vaq {
 
 // Per-subspace descriptor, one table per index in device memory.
@@ -158,6 +160,15 @@ size_t refine_rows_max_dim();
 hipError_t launch_refine_rows(const float *Q, int nq, int D, const float *rows, int64_t N, int64_t id_base,
                               const int32_t *labels_in, int R, int k, int exact, int32_t *labels, float *dist,
                               hipStream_t st);
+// The same in two halves, for rows sharded over devices (refine_owner.h has the cut).  launch_refine_dist: one shard's
+// rows (n x D, row i carries label lo_label + i) -> plane[q * R + c] for the candidates it holds, other slots left
+// alone; n == 0 launches nothing.  launch_refine_select: slot c of query q is read from the plane of the shard that owns
+// its label (planes + owner * plane_stride), labels nobody owns are skipped, then launch_refine_rows' selection.
+hipError_t launch_refine_dist(const float *Q, int nq, int D, const float *rows, int64_t n, int64_t lo_label,
+                              const int32_t *labels_in, int R, float *plane, hipStream_t st);
+hipError_t launch_refine_select(const int32_t *labels_in, int nq, const float *planes, size_t plane_stride,
+                                const RefineBounds &bounds, int R, int k, int exact, int32_t *labels, float *dist,
+                                hipStream_t st);
 // dwords the packed layout needs for `rows` rows
 int64_t packed_words(int64_t rows, int M, int layout, int W);
 // Pack rows [row_begin, row_end) (codes_u16 points at row_begin; row_begin a

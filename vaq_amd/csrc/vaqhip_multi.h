@@ -1,7 +1,8 @@
 // vaqhip_multi.h -- what the host files of the multi-device index share: the shard, the index with the
 // geometry of the search in flight, the error hand-over and the two loops over shards.  Private to
-// vaqhip_multi.cpp (life cycle, codes, setters), vaqhip_multi_search.cpp (the search) and
-// vaqhip_multi_kmeans.cpp (the k-means of clusterTI); they see a shard's index through include/vaqhip.h
+// vaqhip_multi.cpp (life cycle, codes, setters), vaqhip_multi_search.cpp (the search),
+// vaqhip_multi_kmeans.cpp (the k-means of clusterTI) and vaqhip_multi_refiner.cpp (the refiner over sharded raw rows,
+// which takes the error hand-over and on_shards from here); they see a shard's index through include/vaqhip.h
 // and vaqhip_internal.h only.
 #ifndef VAQHIP_MULTI_H
 #define VAQHIP_MULTI_H
@@ -129,10 +130,10 @@ inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? VAQHIP_ENO
 
 // job(g, shard) on every shard's worker at once.  A job that fails and leaves the shard's text empty says that a
 // single-index call failed: the text is then that call's, taken on the worker's thread.  The first failing shard
-// is reported.
-template <class Job> int on_shards(vaqhip_multi *mx, Job &&job) {
+// is reported.  (Owner: vaqhip_multi, or the multi-device refiner -- G, pool and sh[] with device and err.)
+template <class Owner, class Job> int on_shards(Owner *mx, Job &&job) {
   const int rc = mx->pool.run([&](int g) -> int {
-    Shard &s = mx->sh[g];
+    auto &s = mx->sh[g];
     s.err.clear();
     const int r = job(g, s);
     if (r && s.err.empty()) s.err = vaqhip_last_error();

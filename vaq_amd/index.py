@@ -696,6 +696,112 @@ class VaqRefiner:
             pass
 
 
+class VaqMultiRefiner:
+    """VaqRefiner with the raw rows cut over several GPUs (vaqhip_multi_refiner_*): every shard computes the distances
+    of the candidates it holds, one selection on the first device finishes -- the single refiner's answer slot for
+    slot, with exact_ties on or off and for any number of shards.  `devices` as for VaqHipMulti (a device named
+    several times gives logical shards on that GPU).
+
+        r = VaqMultiRefiner([0, 1, 2, 3], D)
+        r.set_rows(XTrain)                          # cut like the multi index's code rows, one upload per shard
+        ans = r.refine(XTest, candidates, k)
+        ans = multi.search_refine(XTest, R, k, r)   # fused with VaqHipMulti.search
+    """
+
+    def __init__(self, devices: Sequence[int], D: int):
+        self.D = int(D)
+        self.devices = [int(d) for d in devices]
+        self._exact = False
+        self._h = C.c_void_p()
+        h = C.c_void_p()
+        devs = (C.c_int * len(self.devices))(*self.devices)
+        _lib.check_multi(_lib.load().vaqhip_multi_refiner_create(C.byref(h), self.D, len(self.devices), devs))
+        self._h = h
+
+    def _rows(self, X) -> np.ndarray:
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != self.D:
+            raise _lib.VaqHipError(-1, f"rows {X.shape} are not n x {self.D}")
+        return X
+
+    def set_rows(self, XTrain, id_base: int = 0) -> None:
+        """Replace the rows (a host array): shard g takes rows [g * ceil(N / G), (g + 1) * ceil(N / G))."""
+        X = self._rows(XTrain)
+        _lib.check_multi(_lib.load().vaqhip_multi_refiner_set_rows(self._h, _ptr(X), X.shape[0], int(id_base)))
+
+    def add_rows(self, X) -> None:
+        """Append rows; their labels continue behind the rows already held, so they extend the last shard."""
+        X = self._rows(X)
+        _lib.check_multi(_lib.load().vaqhip_multi_refiner_add_rows(self._h, _ptr(X), X.shape[0]))
+
+    def set_option(self, key: str, value: int) -> None:
+        _lib.check_multi(_lib.load().vaqhip_multi_refiner_set_option(self._h, key.encode(), int(value)))
+
+    @property
+    def exact_ties(self) -> bool:
+        return self._exact
+
+    @exact_ties.setter
+    def exact_ties(self, on: bool) -> None:
+        self.set_option("exact_ties", 1 if on else 0)
+        self._exact = bool(on)
+
+    def refine(self, XTest, answersIn, k: int) -> LabelDistVec:
+        """As VaqRefiner.refine: answersIn is a LabelDistVec or an array of nq * R labels."""
+        Xq = self._rows(XTest)
+        nq = Xq.shape[0]
+        lab = np.ascontiguousarray(getattr(answersIn, "labels", answersIn), dtype=np.int32).reshape(-1)
+        R = lab.size // max(nq, 1)
+        if nq and lab.size != nq * R:
+            raise _lib.VaqHipError(-1, f"{lab.size} labels for {nq} queries")
+        ret = LabelDistVec(np.empty(nq * k, np.int32), np.empty(nq * k, np.float32))
+        if nq == 0:
+            return ret
+        _lib.check_multi(_lib.load().vaqhip_multi_refiner_refine(self._h, _ptr(Xq), nq, _ptr(lab), R, int(k),
+                                                                 _ptr(ret.labels), _ptr(ret.distances)))
+        return ret
+
+    def refine_device(self, d_queries, d_labels_in, k: int, out=None):
+        """torch CUDA tensors on the FIRST device of the list in and out, enqueued behind torch's current stream of
+        that device; nothing is synchronised."""
+        import torch
+        q = d_queries.contiguous()
+        lin = d_labels_in.contiguous()
+        assert q.is_cuda and q.dtype == torch.float32 and q.shape[1] == self.D
+        assert lin.is_cuda and lin.dtype == torch.int32 and lin.shape[0] == q.shape[0]
+        nq, R = lin.shape
+        if out is not None:
+            labels, dists = out
+        else:
+            labels = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+            dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        st = torch.cuda.current_stream(q.device).cuda_stream
+        _lib.check_multi(_lib.load().vaqhip_multi_refiner_refine_device(
+            self._h, C.c_void_p(q.data_ptr()), nq, C.c_void_p(lin.data_ptr()), R, int(k),
+            C.c_void_p(labels.data_ptr()), C.c_void_p(dists.data_ptr()), C.c_void_p(st)))
+        return labels, dists
+
+    def info(self) -> dict:
+        """Shard rows, and the phase times of the last refine made under set_option("timing", 1) (waits for it)."""
+        inf = _lib.MultiRefinerInfo()
+        _lib.check_multi(_lib.load().vaqhip_multi_refiner_get_info(self._h, C.byref(inf)))
+        n = inf.n_devices
+        d = {f: getattr(inf, f) for f, _ in _lib.MultiRefinerInfo._fields_ if f not in ("device_ids", "shard_rows")}
+        d.update(device_ids=list(inf.device_ids)[:n], shard_rows=list(inf.shard_rows)[:n])
+        return d
+
+    def close(self) -> None:
+        if self._h:
+            _lib.load().vaqhip_multi_refiner_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def merge_topk_device(dist_lists, label_lists, k: int, out=None):
     """Multi-GPU exchange step: [n_lists, nq, k] CUDA tensors (labels global,
     empty slots -1 / FLT_MAX) -> per-query k smallest by (distance, label)."""
@@ -878,6 +984,35 @@ class VaqHipMulti:
         stream = torch.cuda.current_stream(q.device).cuda_stream
         _lib.check_multi(_lib.load().vaqhip_multi_search_device(
             self._h, C.c_void_p(q.data_ptr()), nq, k, 1 if projected else 0, C.c_void_p(labels.data_ptr()),
+            C.c_void_p(dists.data_ptr()), C.c_void_p(stream)))
+        return labels, dists
+
+    def search_refine(self, XTest: np.ndarray, R: int, k: int, refiner: "VaqMultiRefiner") -> LabelDistVec:
+        """search(XTest, R) followed by VAQ::refine to k against the multi refiner's sharded rows, in one call
+        (vaqhip_multi_search_refine): the candidates go from the merge on the first device straight into the refine.
+        Equals search() + refiner.refine() on the same inputs; this index's options apply to the search half."""
+        X = np.ascontiguousarray(XTest, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != self.D:
+            raise _lib.VaqHipError(-1, f"XTest {X.shape} is not nq x {self.D}")
+        nq = X.shape[0]
+        ret = LabelDistVec(np.empty(nq * k, np.int32), np.empty(nq * k, np.float32))
+        _lib.check_multi(_lib.load().vaqhip_multi_search_refine(self._h, refiner._h, _ptr(X), nq, int(R), int(k),
+                                                                _ptr(ret.labels), _ptr(ret.distances)))
+        return ret
+
+    def search_refine_device(self, d_queries, R: int, k: int, refiner: "VaqMultiRefiner", out=None):
+        """vaqhip_multi_search_refine_device: torch CUDA tensors on the first device, enqueue only."""
+        import torch
+        q = d_queries.contiguous()
+        assert q.is_cuda and q.dtype == torch.float32 and q.shape[1] == self.D
+        nq = q.shape[0]
+        if out is None:
+            out = (torch.empty((nq, k), dtype=torch.int32, device=q.device),
+                   torch.empty((nq, k), dtype=torch.float32, device=q.device))
+        labels, dists = out
+        stream = torch.cuda.current_stream(q.device).cuda_stream
+        _lib.check_multi(_lib.load().vaqhip_multi_search_refine_device(
+            self._h, refiner._h, C.c_void_p(q.data_ptr()), nq, int(R), int(k), C.c_void_p(labels.data_ptr()),
             C.c_void_p(dists.data_ptr()), C.c_void_p(stream)))
         return labels, dists
 
