@@ -21,6 +21,10 @@
 //                                           the reference's (Eigen's) summation order; needs --timeseries-size == D.
 //                                           --exact-ties 1: also the reference heap's tie order.  With --devices the
 //                                           raw vectors are cut over the same GPUs as the code rows: same answer)
+//               [--exact-groundtruth]      (without --groundtruth: the true k nearest rows of every query are computed
+//                                           on the device from the raw vectors -- --dataset, resident as with
+//                                           --refine-resident, single device -- and the recall lines are printed
+//                                           against them)
 //               [--devices 0,1,2,3]        (shard the rows over these GPUs: RCCL all-gather + merge)
 //               with a ...,FAST method (codes of at most 4 bits): --dataset base.fvecs [--dataset-size N]
 //               [--learn-ratio 0.05]       (demo_vaq.cpp:42, :120-124: VAQ::learnQuantization on the raw dataset)
@@ -96,8 +100,8 @@ int main(int argc, char **argv) {
   std::map<std::string, std::string> a = {{"k", "100"}, {"method", "VAQ64m8min8max8var1,HEAP"},
                                           {"timeseries-size", "128"}, {"queries-size", "-1"}};
   for (int i = 1; i < argc; i += 2) {
-    if (std::strcmp(argv[i], "--refine-resident") == 0) {  // the one switch without a value
-      a["refine-resident"] = "1";
+    if (std::strcmp(argv[i], "--refine-resident") == 0 || std::strcmp(argv[i], "--exact-groundtruth") == 0) {
+      a[argv[i] + 2] = "1";  // the switches without a value
       i--;
       continue;
     }
@@ -192,7 +196,27 @@ int main(int argc, char **argv) {
       }
     }
     RowMatrix<int> gt;
-    if (a.count("groundtruth")) gt = readIVecs(a["groundtruth"], k);
+    if (a.count("groundtruth")) {
+      gt = readIVecs(a["groundtruth"], k);
+    } else if (a.count("exact-groundtruth")) {
+      if (a.count("devices")) throw Error(VAQHIP_EUNSUPPORTED, "--exact-groundtruth runs on a single device");
+      if (N != D) throw Error(VAQHIP_EINVAL, "--exact-groundtruth compares raw vectors: --timeseries-size must be D");
+      if (!resident) {  // (with --refine-resident the rows are there already)
+        const std::string raw = a.count("dataset-refine") ? a["dataset-refine"] : (a.count("dataset") ? a["dataset"] : "");
+        if (raw.empty()) throw Error(VAQHIP_EINVAL, "--exact-groundtruth needs the raw vectors: --dataset <.fvecs>");
+        if (datasetrefine.rows() == 0)
+          datasetrefine = readFVecs(raw, N, a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1, 0);
+        vaq.setRefineDataset(datasetrefine);
+      }
+      auto t0 = std::chrono::steady_clock::now();
+      const LabelDistVecF exact = vaq.searchExhaustive(queries, k);
+      gt = RowMatrix<int>((size_t)queries.rows(), (size_t)k);
+      for (size_t i = 0; i < gt.rows(); i++)
+        for (size_t j = 0; j < gt.cols(); j++) gt(i, j) = exact.labels[i * k + j];
+      std::cout << "== Exact ground truth: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+                << " s (" << datasetrefine.rows() << " rows x " << queries.rows() << " queries, exhaustive)" << std::endl;
+      a["groundtruth"] = "(exact)";
+    }
     if (vaq.searchMethod() & VaqHip::NNMethod::Fast) {  // demo_vaq.cpp:120-124
       if (!a.count("dataset")) throw Error(VAQHIP_EINVAL, "a FAST method learns its quantisation from --dataset <.fvecs>");
       RowMatrixF dataset = readFVecs(a["dataset"], N, a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1, D - N);

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 112
+#define VAQHIP_VERSION 113
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -386,6 +386,44 @@ int vaqhip_search_refine(vaqhip_index *ix, vaqhip_refiner *r, const float *queri
                          int32_t *labels_out, float *distances_out);
 int vaqhip_search_refine_device(vaqhip_index *ix, vaqhip_refiner *r, const float *d_queries_raw, int nq, int R, int k,
                                 int32_t *d_labels_out, float *d_distances_out, void *stream);
+
+/* Exhaustive form of the resident refiner: the true k nearest rows of every query, i.e. what vaqhip_refiner_refine
+ * would return for the candidate list id_base, id_base + 1, ..., id_base + N - 1 in that order if R were allowed to be
+ * N -- VAQ::refine (VAQ.cpp:849-876) with answersIn naming every row once in row order; ground truth with the
+ * reference's own distances, no file needed.  Rows appended with add_rows are searched.
+ *   distances   the refiner's: Eigen's summation order, bit for bit, for every D the refiner accepts (rows of up to 128
+ *               columns are held in registers, one thread per row, and meet many queries; wider rows take a general
+ *               path with the same answers).
+ *   selection   "exact_ties" = 0: the k smallest by (distance, label) among rows with distance < FLT_MAX; unfilled
+ *               slots -1 / FLT_MAX (N < k, rows whose distance is inf or NaN).  "exact_ties" = 1: the reference heap's
+ *               labels and distances slot for slot (heap_heapify, then over rows 0..N-1 heap_pop + heap_push when
+ *               heap_top > dist, heap_reorder): queries whose k + 1 best hold two equal distances are replayed through
+ *               the heap on the device, one streamed pass over the rows each.  Both modes at every k <= VAQHIP_MAX_K.
+ *   options     "exhaustive_splits": the rows are cut into S splits searched side by side and merged; 0 = automatic,
+ *               1..64 forces S (any other value VAQHIP_EINVAL; a split may be empty).  The answer does not depend on it.
+ *               "timing" = 1: device events around the phases of every following search, which then synchronises
+ *               after each launch set; vaqhip_refiner_last_search_timing reads the last call's figures.
+ *   limits      1 <= k <= VAQHIP_MAX_K (larger: VAQHIP_EUNSUPPORTED); nq == 0 succeeds and writes nothing; null
+ *               pointers or k < 1 VAQHIP_EINVAL -- all checked before any device work; VAQHIP_ESTATE before rows are set.
+ * The host form is synchronous; the _device form takes pointers on the refiner's GPU, enqueues on `stream` and never
+ * synchronises (it grows its workspace on first use).  Serialised with the refiner's other calls. */
+int vaqhip_refiner_search(vaqhip_refiner *r, const float *queries_rowmajor, int nq, int k, int32_t *labels_out,
+                          float *distances_out);
+int vaqhip_refiner_search_device(vaqhip_refiner *r, const float *d_queries, int nq, int k, int32_t *d_labels_out,
+                                 float *d_distances_out, void *stream);
+typedef struct {
+  float select_ms;        /* distances + streaming selection, all splits */
+  float merge_ms;         /* the splits' lists merged */
+  float flag_ms;          /* "exact_ties": queries with equal distances listed, the others copied out */
+  float replay_ms;        /* "exact_ties": the listed queries through the reference's heap */
+  int listed_queries;     /* queries replayed */
+  int splits;             /* S */
+  int workgroups;         /* of one select launch: S x query groups */
+  int queries_per_group;  /* queries one workgroup's rows meet */
+  int register_form;      /* 1: one thread per row (D <= 128), 0: the general path */
+} vaqhip_refiner_search_timing;
+/* figures of the last vaqhip_refiner_search[_device] on this refiner (zero times unless "timing" was set) */
+int vaqhip_refiner_last_search_timing(vaqhip_refiner *r, vaqhip_refiner_search_timing *out);
 
 /* Multi-GPU exchange step: after an all-gather of per-shard
  * results laid out [n_lists][nq][k] (labels already global), keep per query

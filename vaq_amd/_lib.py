@@ -29,6 +29,7 @@ SYMBOLS = [
     "vaqhip_refiner_create", "vaqhip_refiner_destroy", "vaqhip_refiner_set_rows", "vaqhip_refiner_set_rows_device",
     "vaqhip_refiner_add_rows", "vaqhip_refiner_set_option", "vaqhip_refiner_refine", "vaqhip_refiner_refine_device",
     "vaqhip_search_refine", "vaqhip_search_refine_device",
+    "vaqhip_refiner_search", "vaqhip_refiner_search_device", "vaqhip_refiner_last_search_timing",
     "vaqhip_index_info", "vaqhip_set_option", "vaqhip_last_timing", "vaqhip_last_error",
     "vaqhip_version", "vaqhip_device_count",
     "vaqhip_multi_create", "vaqhip_multi_destroy", "vaqhip_multi_set_codes_u16", "vaqhip_multi_add_codes_u16",
@@ -83,6 +84,12 @@ class LutFitTiming(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("project_ms", C.c_float), ("extract_ms", C.c_float),
                 ("sort_ms", C.c_float), ("quantile_ms", C.c_float), ("means_ms", C.c_float),
                 ("rows", C.c_int64), ("dims", C.c_int)]
+
+
+class RefinerSearchTiming(C.Structure):
+    _fields_ = [("select_ms", C.c_float), ("merge_ms", C.c_float), ("flag_ms", C.c_float), ("replay_ms", C.c_float),
+                ("listed_queries", C.c_int), ("splits", C.c_int), ("workgroups", C.c_int),
+                ("queries_per_group", C.c_int), ("register_form", C.c_int)]
 
 
 class MultiInfo(C.Structure):
@@ -172,6 +179,9 @@ def load():
     L.vaqhip_refiner_set_option.argtypes = [vp, C.c_char_p, i64]
     L.vaqhip_refiner_refine.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
     L.vaqhip_refiner_refine_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp]
+    L.vaqhip_refiner_search.argtypes = [vp, vp, i32, i32, vp, vp]
+    L.vaqhip_refiner_search_device.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+    L.vaqhip_refiner_last_search_timing.argtypes = [vp, C.POINTER(RefinerSearchTiming)]
     L.vaqhip_search_refine.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     L.vaqhip_search_refine_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.vaqhip_merge_topk_strided_device.argtypes = [i32, vp, vp, i32, i64, i64, i32, i32, vp, vp, vp]

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vaq_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "vaq_amd", "lib")
 LIB = os.path.join(LIBDIR, "libvaqhip.so")
-SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_fast.hip", "vaq_lutfit.hip", "vaq_refine.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp", "vaqhip_lutfit.cpp", "vaqhip_refiner.cpp",
+SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_fast.hip", "vaq_lutfit.hip", "vaq_refine.hip", "vaq_exhaust.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp", "vaqhip_lutfit.cpp", "vaqhip_refiner.cpp",
            "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp", "vaqhip_rccl.cpp"]
 MULTI_SOURCES = ("vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp")
 KERNEL_HEADER = os.path.join(CSRC, "vaq_kernels.h")
@@ -24,6 +24,8 @@ API_HEADER = os.path.join(ROOT, "include", "vaqhip.h")
 SCAN_HEADER = os.path.join(CSRC, "vaq_scan.h")
 SCAN_BF_HEADER = os.path.join(CSRC, "vaq_scan_bf.h")
 FAST_HEADER = os.path.join(CSRC, "vaq_fast.h")
+REFINE_GROUP_HEADER = os.path.join(CSRC, "vaq_refine_group.h")  # Eigen's squaredNorm over 16 lanes: refine, exhaustive form
+EXHAUST_HEADER = os.path.join(CSRC, "vaq_exhaust.h")  # the same by one thread, host and device: exhaustive form
 RESTATED_HEADER = os.path.join(CSRC, "vaq_restated.h")  # stdsort, stdheap, refheap, sq_norm_eigen: FAST, TI planning, the replay, k-means, refine
 INTERNAL_HEADER = os.path.join(CSRC, "vaqhip_internal.h")
 INDEX_HEADER = os.path.join(CSRC, "vaqhip_index.h")  # private to the single-index host files
@@ -49,14 +51,18 @@ def _deps(src: str):
         deps.append(LUTFIT_HEADER)
     if src in ("vaq_kmeans.hip", "vaqhip_codes.cpp", "vaqhip_multi_kmeans.cpp"):
         deps.append(KMEANS_SAMPLE_HEADER)
-    if src in ("vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_refine.hip"):
+    if src in ("vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_refine.hip", "vaq_exhaust.hip"):
         deps.append(SCAN_HEADER)
     if src in ("vaq_kernels.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip"):
         deps.append(SCAN_BF_HEADER)
     if src in ("vaq_fast.hip", "vaqhip_fast.cpp"):
         deps.append(FAST_HEADER)
-    if src in ("vaq_fast.hip", "vaqhip_fast.cpp", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_refine.hip"):
+    if src in ("vaq_fast.hip", "vaqhip_fast.cpp", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_refine.hip", "vaq_exhaust.hip"):
         deps.append(RESTATED_HEADER)
+    if src in ("vaq_refine.hip", "vaq_exhaust.hip"):
+        deps.append(REFINE_GROUP_HEADER)
+    if src == "vaq_exhaust.hip":
+        deps.append(EXHAUST_HEADER)
     return deps
 OBJDIR = os.path.join(LIBDIR, "obj")
 # Experiment builds: VAQ_VARIANT=name compiles (with VAQ_EXTRA_FLAGS) into vaq_amd/lib/variants/name/

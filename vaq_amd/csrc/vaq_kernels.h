@@ -169,6 +169,35 @@ hipError_t launch_refine_dist(const float *Q, int nq, int D, const float *rows, 
 hipError_t launch_refine_select(const int32_t *labels_in, int nq, const float *planes, size_t plane_stride,
                                 const RefineBounds &bounds, int R, int k, int exact, int32_t *labels, float *dist,
                                 hipStream_t st);
+// ---- the exhaustive form of VAQ::refine (vaq_exhaust.hip): every resident row a candidate, in row order ----
+constexpr int XS_TILE = 256;      // rows a workgroup takes at a time
+constexpr int XS_MAX_QG = 1024;   // queries a workgroup owns (their thresholds and counts sit in LDS)
+constexpr int XS_MAX_K1 = 1025;   // entries per list: VAQHIP_MAX_K, and one more for the flag step of "exact_ties"
+// The plan of one launch: S splits of split_rows rows each (the last may be short or empty), G = ceil(nq / qg) groups
+// of qg queries; workgroup (s, g) streams split s against group g.  buf_*: [nq][S][cap] candidate lists,
+// cap = exhaust_list_cap(k); part_*: [S][nq][k] the splits' k best, labels with id_base, -1 / FLT_MAX in empty slots
+// (launch_merge's in_final format).  The answer does not depend on S, qg or the tile.
+struct XsParams {
+  int nq, D;
+  int64_t N, id_base;
+  int k, cap;
+  int S, G, qg;
+  int64_t split_rows;
+  float *buf_d;
+  int *buf_id;
+  float *part_d;
+  int *part_id;
+};
+int exhaust_list_cap(int k);
+size_t exhaust_register_max_dim();  // widest row of the register form
+int exhaust_blocks_per_cu(int D);     // resident workgroups per CU of the select kernel for this width
+// Q: nq x D, rows: N x D; D <= refine_rows_max_dim(); rows of up to XS_MAX_DIM columns (vaq_exhaust.h) take the
+// register form, wider ones the general path
+hipError_t launch_exhaust_select(const XsParams &p, const float *Q, const float *rows, hipStream_t st);
+// "exact_ties": block e replays query list[e] over all rows through the reference's heap and writes its k slots of
+// labels / dist; blocks at or beyond *count exit at once (launch nq of them)
+hipError_t launch_exhaust_replay(const float *Q, int nq, int D, const float *rows, int64_t N, int64_t id_base, int k,
+                                 const int *list, const unsigned *count, int32_t *labels, float *dist, hipStream_t st);
 // dwords the packed layout needs for `rows` rows
 int64_t packed_words(int64_t rows, int M, int layout, int W);
 // Pack rows [row_begin, row_end) (codes_u16 points at row_begin; row_begin a

@@ -18,6 +18,7 @@
 // A candidate's distance depends on its own row only and the selection on the R (distance, label) pairs in candidate
 // order only, so the answer is refine_rows_kernel's slot for slot.
 #include "refine_owner.h"
+#include "vaq_refine_group.h"
 #include "vaq_kernels.h"
 #include "vaq_restated.h"
 #include "vaq_scan.h"
@@ -26,46 +27,7 @@ namespace vaq {
 
 constexpr int RF_THREADS = 256;
 constexpr int RF_CAP = 2048;    // candidates per query
-constexpr int RF_GROUP = 16;    // lanes per candidate row
 constexpr int RF_GROUPS = RF_THREADS / RF_GROUP;
-
-// the value lane `src` of this lane's group holds
-__device__ __forceinline__ float rf_from(float v, int gbase, int src) { return __shfl(v, gbase + src, 64); }
-
-// Squared distance of the group's row y to the staged query qs, complete in lane 0 of the group.  Every lane of the
-// wave runs every shuffle; `valid` (the same in all 16 lanes of a group) only masks the loads of a skipped candidate.
-__device__ __forceinline__ float rf_group_sq_norm(const float *qs, const float *__restrict__ y, int D, bool valid, int j,
-                                                  int gbase) {
-#define T_(idx, ok) ((valid && (ok)) ? km_sq(qs[idx], y[idx]) : 0.0f)
-  if (D < 8) {  // res = coeff(0); res += coeff(i)
-    const float t = T_(j, j < D);
-    float res = rf_from(t, gbase, 0);
-    for (int e = 1; e < D; e++) res += rf_from(t, gbase, e);
-    return res;
-  }
-  const int end1 = (D / 8) * 8, end2 = (D / 16) * 16;
-  float acc;
-  if (end2 >= 16) {  // a0 = packet 0, a1 = packet 1, then the loop over pairs of packets
-    acc = T_(j, true);
-#pragma unroll 4
-    for (int i = 16; i < end2; i += 16) acc += T_(i + j, true);
-  } else {  // 8 <= D < 16: only a0 exists
-    acc = T_(j, j < 8);
-  }
-  if (end1 > 8) {
-    acc += rf_from(acc, gbase, (j + 8) & 15);                // lanes 0..7: a0 += a1
-    if (end1 > end2) acc += T_(end2 + j, j < 8);             // the odd eighth packet
-  }
-  // predux<Packet8f> in lanes 0..7: the halves added, then (b0 + b2) + (b1 + b3)
-  acc += rf_from(acc, gbase, j ^ 4);
-  acc += rf_from(acc, gbase, j ^ 2);
-  acc += rf_from(acc, gbase, j ^ 1);
-  const float t = T_(end1 + j, end1 + j < D);  // the scalar tail, at most 7 elements
-  float res = acc;
-  for (int e = 0; e < D - end1; e++) res += rf_from(t, gbase, e);
-  return res;
-#undef T_
-}
 
 // One candidate slot of the selection's input: what refine_rows_kernel and refine_select_kernel both leave in sd / si.
 template <bool EXACT>

@@ -1,7 +1,8 @@
 // vaqhip_refiner.cpp -- the resident refiner of include/vaqhip.h: the raw rows VAQ::refine reads (VAQ.cpp:849-876)
 // kept on the device, the reference-exact re-rank over them (vaq_refine.hip), and the search fused with it.  It sees
 // the index through the public ABI only (vaqhip_index_info, vaqhip_search_device): the candidates of a fused call go
-// from the search's output buffer straight into the refine kernel and never to the host.
+// from the search's output buffer straight into the refine kernel and never to the host.  The exhaustive form
+// (vaqhip_refiner_search: every resident row a candidate) plans the launches of vaq_exhaust.hip here.
 #include "vaqhip_index.h"
 
 #include <string>
@@ -13,9 +14,16 @@ struct vaqhip_refiner {
   int64_t N = 0, id_base = 0;
   int64_t cap_rows = 0;  // rows the allocation holds (appends grow it geometrically)
   int opt_exact = 0;
+  int opt_splits = 0;  // "exhaustive_splits": 0 = automatic
+  int opt_timing = 0;  // "timing": events around the phases of the exhaustive form
+  int n_cu = 0, blocks_per_cu = 0;
   DevBuf d_rows;
   // workspaces of the host forms and of the fused call (grow-only)
   DevBuf w_q, w_lin, w_lout, w_dout, w_cand_l, w_cand_d;
+  // the exhaustive form's: candidate lists, the splits' lists, the merge's scratch, the k + 1 lists and the replay list
+  DevBuf x_buf_d, x_buf_id, x_part_d, x_part_id, x_ms_d, x_ms_id, x_k1_l, x_k1_d, x_list;
+  hipEvent_t x_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  vaqhip_refiner_search_timing x_timing = {};
   hipStream_t stream = nullptr;
   // the candidate buffers of the fused _device call are shared by its callers' streams: as on the index, the last
   // enqueue leaves an event and a call on another stream waits for it first
@@ -106,6 +114,141 @@ int search_refine_locked(vaqhip_index *ix, vaqhip_refiner *r, const float *d_q, 
   return rc;
 }
 
+// ---- the exhaustive form ----
+constexpr size_t XS_LIST_BYTES = (size_t)256 << 20;  // candidate lists of one launch (the queries are cut to fit)
+
+struct XsPlan {
+  int S, qg, chunk;  // splits, queries per workgroup, queries per launch
+};
+
+XsPlan plan_search(const vaqhip_refiner *r, int nq, int k1) {
+  // ONE round of resident workgroups: with equal shares they end together, and no partly filled second round runs
+  const int target = std::max(r->n_cu, 1) * std::max(r->blocks_per_cu, 1);
+  const int64_t tiles = std::max<int64_t>(1, (r->N + vaq::XS_TILE - 1) / vaq::XS_TILE);
+  XsPlan pl;
+  if (r->opt_splits > 0) {
+    pl.S = r->opt_splits;
+  } else {  // few queries: many splits fill the device; many queries: few splits, the lists stay small
+    const int g0 = (nq + 63) / 64;
+    pl.S = (int)std::min<int64_t>(std::min<int64_t>(64, tiles), std::max(1, (target + g0 - 1) / g0));
+  }
+  const size_t per_query = (size_t)pl.S * vaq::exhaust_list_cap(k1) * (sizeof(float) + sizeof(int));
+  const int fit = (int)std::min<size_t>((size_t)nq, std::max<size_t>(1, XS_LIST_BYTES / per_query));
+  const int sets = (nq + fit - 1) / fit;
+  pl.chunk = (nq + sets - 1) / sets;  // equal sets: the last one fills the device like the others
+  const int g_want = std::max(1, target / pl.S);  // S * groups <= target
+  pl.qg = std::min(vaq::XS_MAX_QG, std::max((pl.chunk + g_want - 1) / g_want, std::min(pl.chunk, 8)));
+  return pl;
+}
+
+// one set of queries: select per split, merge, and with "exact_ties" flag + replay; caller holds r->mu
+int search_set(vaqhip_refiner *r, const XsPlan &pl, const float *d_q, int n, int k, int32_t *d_lout, float *d_dout,
+               hipStream_t st) {
+  const bool exact = r->opt_exact != 0, timing = r->opt_timing != 0;
+  const int k1 = exact ? k + 1 : k;
+  vaq::XsParams p;
+  p.nq = n;
+  p.D = r->D;
+  p.N = r->N;
+  p.id_base = r->id_base;
+  p.k = k1;
+  p.cap = vaq::exhaust_list_cap(k1);
+  p.S = pl.S;
+  p.qg = std::min(pl.qg, n);
+  p.G = (n + p.qg - 1) / p.qg;
+  p.split_rows = (r->N + pl.S - 1) / pl.S;
+  p.buf_d = r->x_buf_d.as<float>();
+  p.buf_id = r->x_buf_id.as<int>();
+  p.part_d = r->x_part_d.as<float>();
+  p.part_id = r->x_part_id.as<int>();
+  int32_t *m_l = exact ? r->x_k1_l.as<int32_t>() : d_lout;
+  float *m_d = exact ? r->x_k1_d.as<float>() : d_dout;
+  int *list = r->x_list.as<int>();
+  unsigned *count = reinterpret_cast<unsigned *>(list + n);
+  if (timing) HIP_TRY(hipEventRecord(r->x_ev[0], st));
+  HIP_TRY(vaq::launch_exhaust_select(p, d_q, r->d_rows.as<float>(), st));
+  if (timing) HIP_TRY(hipEventRecord(r->x_ev[1], st));
+  HIP_TRY(vaq::launch_merge(p.part_d, p.part_id, nullptr, p.S, (int64_t)n * k1, (int64_t)k1, n, k1, 0, 1, m_l, m_d, nullptr,
+                            r->x_ms_d.as<float>(), r->x_ms_id.as<int>(), st));
+  if (timing) HIP_TRY(hipEventRecord(r->x_ev[2], st));
+  if (exact) {
+    HIP_TRY(vaq::launch_exact_flag(n, k, m_l, m_d, d_lout, d_dout, list, count, st));
+    if (timing) HIP_TRY(hipEventRecord(r->x_ev[3], st));
+    HIP_TRY(vaq::launch_exhaust_replay(d_q, n, r->D, r->d_rows.as<float>(), r->N, r->id_base, k, list, count, d_lout,
+                                       d_dout, st));
+  } else if (timing) {
+    HIP_TRY(hipEventRecord(r->x_ev[3], st));
+  }
+  if (timing) {  // (the option is a measurement: it synchronises after every set)
+    HIP_TRY(hipEventRecord(r->x_ev[4], st));
+    HIP_TRY(hipEventSynchronize(r->x_ev[4]));
+    float ms[4] = {0, 0, 0, 0};
+    for (int i = 0; i < 4; i++) HIP_TRY(hipEventElapsedTime(&ms[i], r->x_ev[i], r->x_ev[i + 1]));
+    unsigned listed = 0;
+    if (exact) HIP_TRY(hipMemcpy(&listed, count, sizeof(unsigned), hipMemcpyDeviceToHost));
+    vaqhip_refiner_search_timing &t = r->x_timing;
+    t.select_ms += ms[0];
+    t.merge_ms += ms[1];
+    t.flag_ms += ms[2];
+    t.replay_ms += ms[3];
+    t.listed_queries += (int)listed;
+    t.workgroups = p.S * p.G;
+    t.queries_per_group = p.qg;
+  }
+  return VAQHIP_OK;
+}
+
+int check_search(const vaqhip_refiner *r, int nq, int k, const void *a, const void *b, const void *c) {
+  if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
+  if (nq < 0 || k < 1) return fail(VAQHIP_EINVAL, "bad sizes (nq=%d k=%d)", nq, k);
+  if (k > VAQHIP_MAX_K) return fail(VAQHIP_EUNSUPPORTED, "k=%d > %d", k, VAQHIP_MAX_K);
+  if (nq > 0 && (!a || !b || !c)) return fail(VAQHIP_EINVAL, "null pointer");
+  return VAQHIP_OK;
+}
+
+// all sets of one call, enqueued on st; caller holds r->mu, device current
+int search_locked(vaqhip_refiner *r, const float *d_q, int nq, int k, int32_t *d_lout, float *d_dout, hipStream_t st) {
+  if (r->cap_rows == 0 && r->N == 0) return fail(VAQHIP_ESTATE, "no rows were set");
+  if (!r->n_cu) {
+    HIP_TRY(hipDeviceGetAttribute(&r->n_cu, hipDeviceAttributeMultiprocessorCount, r->device));
+    if (r->n_cu < 1) r->n_cu = 1;
+    r->blocks_per_cu = vaq::exhaust_blocks_per_cu(r->D);
+  }
+  const bool exact = r->opt_exact != 0;
+  const int k1 = exact ? k + 1 : k;
+  const XsPlan pl = plan_search(r, nq, k1);
+  const size_t cap = (size_t)vaq::exhaust_list_cap(k1), c = (size_t)pl.chunk;
+  HIP_TRY(r->x_buf_d.ensure(c * pl.S * cap * sizeof(float)));
+  HIP_TRY(r->x_buf_id.ensure(c * pl.S * cap * sizeof(int)));
+  HIP_TRY(r->x_part_d.ensure(c * pl.S * k1 * sizeof(float)));
+  HIP_TRY(r->x_part_id.ensure(c * pl.S * k1 * sizeof(int)));
+  const size_t ms = vaq::merge_scratch_elems(pl.S, pl.chunk, k1);
+  HIP_TRY(r->x_ms_d.ensure(ms * sizeof(float)));
+  HIP_TRY(r->x_ms_id.ensure(ms * sizeof(int)));
+  if (exact) {
+    HIP_TRY(r->x_k1_l.ensure(c * k1 * sizeof(int32_t)));
+    HIP_TRY(r->x_k1_d.ensure(c * k1 * sizeof(float)));
+    HIP_TRY(r->x_list.ensure((c + 1) * sizeof(int)));
+  }
+  if (r->opt_timing)
+    for (hipEvent_t &e : r->x_ev)
+      if (!e) HIP_TRY(hipEventCreate(&e));
+  if (!r->ws_event) HIP_TRY(hipEventCreateWithFlags(&r->ws_event, hipEventDisableTiming));
+  if (r->ws_used && st != r->ws_stream) HIP_TRY(hipStreamWaitEvent(st, r->ws_event, 0));
+  r->x_timing = {};
+  r->x_timing.splits = pl.S;
+  r->x_timing.register_form = r->D <= (int)vaq::exhaust_register_max_dim();
+  int rc = VAQHIP_OK;
+  for (int q0 = 0; q0 < nq && !rc; q0 += pl.chunk)
+    rc = search_set(r, pl, d_q + (size_t)q0 * r->D, std::min(pl.chunk, nq - q0), k, d_lout + (size_t)q0 * k,
+                    d_dout + (size_t)q0 * k, st);
+  if (hipEventRecord(r->ws_event, st) == hipSuccess) {  // (also after a failure: work may be enqueued already)
+    r->ws_stream = st;
+    r->ws_used = true;
+  }
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -141,6 +284,8 @@ void vaqhip_refiner_destroy(vaqhip_refiner *r) {
   (void)hipDeviceSynchronize();  // (refines enqueued on the callers' streams read the rows)
   if (r->stream) (void)hipStreamDestroy(r->stream);
   if (r->ws_event) (void)hipEventDestroy(r->ws_event);
+  for (hipEvent_t e : r->x_ev)
+    if (e) (void)hipEventDestroy(e);
   delete r;  // every DevBuf goes here, with the refiner's device current
 }
 
@@ -188,9 +333,47 @@ int vaqhip_refiner_add_rows(vaqhip_refiner *r, const float *X, int64_t n_new) {
 
 int vaqhip_refiner_set_option(vaqhip_refiner *r, const char *key, int64_t value) {
   if (!r || !key) return fail(VAQHIP_EINVAL, "null pointer");
+  const std::string name(key);
+  if (name != "exact_ties" && name != "exhaustive_splits" && name != "timing")
+    return fail(VAQHIP_EINVAL, "unknown option '%s'", key);
+  if (name == "exhaustive_splits" && (value < 0 || value > 64))  // (refused before the refiner is touched)
+    return fail(VAQHIP_EINVAL, "exhaustive_splits=%lld: 0 (automatic) or 1..64", (long long)value);
   std::lock_guard<std::mutex> lk(r->mu);
-  if (std::string(key) == "exact_ties") r->opt_exact = value != 0;
-  else return fail(VAQHIP_EINVAL, "unknown option '%s'", key);
+  if (name == "exact_ties") r->opt_exact = value != 0;
+  else if (name == "exhaustive_splits") r->opt_splits = (int)value;
+  else r->opt_timing = value != 0;
+  return VAQHIP_OK;
+}
+
+int vaqhip_refiner_search_device(vaqhip_refiner *r, const float *d_queries, int nq, int k, int32_t *d_labels_out,
+                                 float *d_distances_out, void *stream) {
+  if (int rc = check_search(r, nq, k, d_queries, d_labels_out, d_distances_out)) return rc;
+  if (nq == 0) return VAQHIP_OK;
+  RENTRY(r);
+  return search_locked(r, d_queries, nq, k, d_labels_out, d_distances_out, static_cast<hipStream_t>(stream));
+}
+
+int vaqhip_refiner_search(vaqhip_refiner *r, const float *queries, int nq, int k, int32_t *labels_out,
+                          float *distances_out) {
+  if (int rc = check_search(r, nq, k, queries, labels_out, distances_out)) return rc;
+  if (nq == 0) return VAQHIP_OK;
+  RENTRY(r);
+  HIP_TRY(r->w_q.ensure((size_t)nq * r->D * sizeof(float)));
+  HIP_TRY(r->w_lout.ensure((size_t)nq * k * sizeof(int32_t)));
+  HIP_TRY(r->w_dout.ensure((size_t)nq * k * sizeof(float)));
+  hipStream_t st = r->stream;
+  HIP_TRY(hipMemcpyAsync(r->w_q.p, queries, (size_t)nq * r->D * sizeof(float), hipMemcpyHostToDevice, st));
+  if (int rc = search_locked(r, r->w_q.as<float>(), nq, k, r->w_lout.as<int32_t>(), r->w_dout.as<float>(), st)) return rc;
+  HIP_TRY(hipMemcpyAsync(labels_out, r->w_lout.p, (size_t)nq * k * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(distances_out, r->w_dout.p, (size_t)nq * k * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return VAQHIP_OK;
+}
+
+int vaqhip_refiner_last_search_timing(vaqhip_refiner *r, vaqhip_refiner_search_timing *out) {
+  if (!r || !out) return fail(VAQHIP_EINVAL, "null pointer");
+  std::lock_guard<std::mutex> lk(r->mu);
+  *out = r->x_timing;
   return VAQHIP_OK;
 }
 

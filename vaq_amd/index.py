@@ -684,6 +684,44 @@ class VaqRefiner:
             C.c_void_p(labels.data_ptr()), C.c_void_p(dists.data_ptr()), C.c_void_p(st)))
         return labels, dists
 
+    def set_option(self, key: str, value: int) -> None:
+        """"exact_ties", "exhaustive_splits" (0 = automatic, 1..64), "timing"."""
+        _lib.check(_lib.load().vaqhip_refiner_set_option(self._h, key.encode(), int(value)))
+        if key == "exact_ties":
+            self._exact = bool(value)
+
+    def search(self, XTest, k: int) -> LabelDistVec:
+        """The exhaustive form of refine(): the candidates are ALL resident rows in row order -- the true k nearest rows
+        of every query with the reference's own distances (and, with exact_ties, its heap's choice among equal ones)."""
+        Xq = self._rows(XTest)
+        nq = Xq.shape[0]
+        ret = LabelDistVec(np.empty(nq * k, np.int32), np.empty(nq * k, np.float32))
+        _lib.check(_lib.load().vaqhip_refiner_search(self._h, _ptr(Xq), nq, int(k), _ptr(ret.labels), _ptr(ret.distances)))
+        return ret
+
+    def search_device(self, d_queries, k: int, out=None):
+        """search() on torch CUDA tensors (queries nq x D float32), enqueued on torch's current stream, no
+        synchronisation; returns (labels nq x k int32, distances nq x k float32)."""
+        import torch
+        q = d_queries.contiguous()
+        assert q.is_cuda and q.dtype == torch.float32 and q.dim() == 2 and q.shape[1] == self.D
+        nq = q.shape[0]
+        if out is not None:
+            labels, dists = out
+        else:
+            labels = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+            dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        st = torch.cuda.current_stream(q.device).cuda_stream
+        _lib.check(_lib.load().vaqhip_refiner_search_device(
+            self._h, C.c_void_p(q.data_ptr()), nq, int(k), C.c_void_p(labels.data_ptr()), C.c_void_p(dists.data_ptr()),
+            C.c_void_p(st)))
+        return labels, dists
+
+    def last_search_timing(self) -> dict:
+        t = _lib.RefinerSearchTiming()
+        _lib.check(_lib.load().vaqhip_refiner_last_search_timing(self._h, C.byref(t)))
+        return {n: getattr(t, n) for n, _ in t._fields_}
+
     def close(self) -> None:
         if self._h:
             _lib.load().vaqhip_refiner_destroy(self._h)
