@@ -23,8 +23,8 @@
 //                                           raw vectors are cut over the same GPUs as the code rows: same answer)
 //               [--exact-groundtruth]      (without --groundtruth: the true k nearest rows of every query are computed
 //                                           on the device from the raw vectors -- --dataset, resident as with
-//                                           --refine-resident, single device -- and the recall lines are printed
-//                                           against them)
+//                                           --refine-resident; with --devices cut over the same GPUs, same answer --
+//                                           and the recall lines are printed against them)
 //               [--devices 0,1,2,3]        (shard the rows over these GPUs: RCCL all-gather + merge)
 //               with a ...,FAST method (codes of at most 4 bits): --dataset base.fvecs [--dataset-size N]
 //               [--learn-ratio 0.05]       (demo_vaq.cpp:42, :120-124: VAQ::learnQuantization on the raw dataset)
@@ -199,7 +199,6 @@ int main(int argc, char **argv) {
     if (a.count("groundtruth")) {
       gt = readIVecs(a["groundtruth"], k);
     } else if (a.count("exact-groundtruth")) {
-      if (a.count("devices")) throw Error(VAQHIP_EUNSUPPORTED, "--exact-groundtruth runs on a single device");
       if (N != D) throw Error(VAQHIP_EINVAL, "--exact-groundtruth compares raw vectors: --timeseries-size must be D");
       if (!resident) {  // (with --refine-resident the rows are there already)
         const std::string raw = a.count("dataset-refine") ? a["dataset-refine"] : (a.count("dataset") ? a["dataset"] : "");

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 113
+#define VAQHIP_VERSION 114
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -592,7 +592,8 @@ const char *vaqhip_multi_last_error(void);
  *   limits      the single refiner's: 1 <= k <= R <= 2048 (VAQHIP_EUNSUPPORTED), sizes that are not positive
  *               VAQHIP_EINVAL, labels that would pass int32 VAQHIP_ERANGE, D beyond the workgroup's LDS
  *               VAQHIP_EUNSUPPORTED; labels outside [id_base, id_base + N) are skipped, never read.
- *   options     "exact_ties" as above; "timing" = 1: device events around the four phases of every following call.
+ *   options     "exact_ties" as above; "timing" = 1: device events around the four phases of every following call;
+ *               "exhaustive_splits" (0 = automatic, 1..64 per shard, any other value VAQHIP_EINVAL): the search below.
  * vaqhip_multi_search_refine = vaqhip_multi_search_device with k = R (the multi index's own method and options as they
  * are, "exact_ties" and its stated exceptions included) into a buffer on device_ids[0], followed by the refine of that
  * buffer in the order the search returned it; the candidates never reach the host.  R <= VAQHIP_MAX_K.  VAQHIP_ESTATE
@@ -632,6 +633,52 @@ typedef struct {
   float last_select_ms;      /* the select kernel                                                           */
 } vaqhip_multi_refiner_info;
 int vaqhip_multi_refiner_get_info(vaqhip_multi_refiner *r, vaqhip_multi_refiner_info *out);
+
+/* Exhaustive form across the shards: what vaqhip_refiner_search[_device] returns for the same rows, queries, k and
+ * options -- labels and distance bit patterns slot for slot -- for any number of shards, logical and empty ones and
+ * rows that arrived by add_rows included.  Per set of queries:
+ *   select      every shard that holds rows runs the single form's select over its own rows (labels from the shard's
+ *               first label, "exhaustive_splits" splits per shard, merged on the shard) into a [nq][k1] list, k1 = k,
+ *               or k + 1 under "exact_ties"; the queries reach shards 1.. by peer copy behind the caller's stream's event.
+ *   gather      the lists are copied next to the first device's (nq * k1 * 8 bytes per shard) and merged there by
+ *               (distance, label).  Labels are global and distinct, so the k smallest keys of the union are among the
+ *               shards' k smallest: without "exact_ties" this is the answer.
+ *   exact_ties  the flag step runs on the MERGED k + 1 list (a run of equal distances may span a cut).  The listed
+ *               queries are replayed as a chain: shard g walks its rows in row order through the reference's heap,
+ *               starting from the raw heap arrays shard g - 1 left (k * 8 bytes per query of the set and hop, by peer
+ *               copy behind events); only the last shard that holds rows applies heap_reorder.  The heap's statements
+ *               meet rows 0..N-1 in order with nothing in between: the reference's answer by construction.
+ * Calls are cut into equal sets of queries such that the gathered lists stay within 256 MB on the first device and
+ * every shard's candidate lists within the single form's 256 MB (never more than VAQHIP_MULTI_REFINER_SET queries);
+ * the answer does not depend on the set size.  Copies only, no RCCL.  One shard: the single form's launches on the
+ * caller's stream.  Limits and refusals are the single form's, all checked before any device work: 1 <= k <=
+ * VAQHIP_MAX_K (VAQHIP_EUNSUPPORTED), nq == 0 succeeds, null pointers or k < 1 VAQHIP_EINVAL, VAQHIP_ESTATE before
+ * rows are set.  The host form is synchronous; the _device form takes pointers on device_ids[0], enqueues only and
+ * never synchronises once its buffers have their size.  "timing" = 1 synchronises after every set. */
+int vaqhip_multi_refiner_search(vaqhip_multi_refiner *r, const float *queries_rowmajor, int nq, int k,
+                                int32_t *labels_out, float *distances_out);
+int vaqhip_multi_refiner_search_device(vaqhip_multi_refiner *r, const float *d_queries, int nq, int k,
+                                       int32_t *d_labels_out, float *d_distances_out, void *stream);
+typedef struct {
+  /* the fields of vaqhip_refiner_search_timing: times of the SLOWEST shard, geometry of the first shard with rows */
+  float select_ms;        /* distances + streaming selection on a shard */
+  float merge_ms;         /* a shard's splits merged */
+  float flag_ms;          /* "exact_ties": the flag step on the merged lists (first device) */
+  float replay_ms;        /* "exact_ties": one shard's link of the chain (one shard: the whole replay) */
+  int listed_queries;
+  int splits;
+  int workgroups;
+  int queries_per_group;
+  int register_form;
+  /* across the shards, summed over the sets (0 with one shard) */
+  float gather_ms;        /* the shards' lists to the first device, incl. waiting for the slowest shard's copy */
+  float cross_merge_ms;   /* the merge of the gathered lists */
+  float chain_ms;         /* "exact_ties": from the flag step's end to the last slot placed on the first device */
+  int chain_shards;       /* shards that hold rows: links of the chain, lists of the cross-shard merge */
+  int sets;               /* sets of queries the call was cut into */
+} vaqhip_multi_refiner_search_timing;
+/* figures of the last vaqhip_multi_refiner_search[_device] (zero times unless "timing" was set) */
+int vaqhip_multi_refiner_last_search_timing(vaqhip_multi_refiner *r, vaqhip_multi_refiner_search_timing *out);
 
 /* ----- introspection / tuning -------------------------------------------- */
 typedef struct {

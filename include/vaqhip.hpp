@@ -386,14 +386,21 @@ public:
   // The exhaustive form of refine(): refine(XTest, <every row of the refine dataset in row order>, XTrain, k) without
   // the candidate list -- the true k nearest rows of every query with the reference's own distances, and with
   // refineExactTies its heap's choice among equal ones (vaqhip.h, "Exhaustive form of the resident refiner").  Ground
-  // truth for recall when no file exists.  Needs setRefineDataset() on a single device; XTest is the raw query.
+  // truth for recall when no file exists.  Needs setRefineDataset(); after setDevices() the rows are cut over the
+  // devices and the answer is the single device's, slot for slot (vaqhip.h, "Exhaustive form across the shards").
+  // XTest is the raw query.
   template <class Mat> LabelDistVecF searchExhaustive(const Mat &XTest, const int k) {
-    if (!rf_) throw Error(VAQHIP_ESTATE, "vaqhip: searchExhaustive needs setRefineDataset() on a single device first");
+    if (!rf_ && !mrf_) throw Error(VAQHIP_ESTATE, "vaqhip: searchExhaustive needs setRefineDataset() first");
     if ((int)XTest.cols() != rf_dim_) throw Error(VAQHIP_EINVAL, "vaqhip: XTest has the wrong width");
     LabelDistVecF ret;
     const size_t nq = (size_t)XTest.rows();
     ret.labels.resize((size_t)(k > 0 ? k : 0) * nq);
     ret.distances.resize((size_t)(k > 0 ? k : 0) * nq);
+    if (mrf_) {
+      checkMulti(vaqhip_multi_refiner_set_option(mrf_, "exact_ties", refineExactTies ? 1 : 0));
+      checkMulti(vaqhip_multi_refiner_search(mrf_, XTest.data(), (int)nq, k, ret.labels.data(), ret.distances.data()));
+      return ret;
+    }
     check(vaqhip_refiner_set_option(rf_, "exact_ties", refineExactTies ? 1 : 0));
     check(vaqhip_refiner_search(rf_, XTest.data(), (int)nq, k, ret.labels.data(), ret.distances.data()));
     return ret;

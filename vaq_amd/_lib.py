@@ -41,6 +41,7 @@ SYMBOLS = [
     "vaqhip_multi_refiner_add_rows", "vaqhip_multi_refiner_set_option", "vaqhip_multi_refiner_refine",
     "vaqhip_multi_refiner_refine_device", "vaqhip_multi_search_refine", "vaqhip_multi_search_refine_device",
     "vaqhip_multi_refiner_get_info",
+    "vaqhip_multi_refiner_search", "vaqhip_multi_refiner_search_device", "vaqhip_multi_refiner_last_search_timing",
 ]
 MAX_DEVICES = 16
 
@@ -90,6 +91,11 @@ class RefinerSearchTiming(C.Structure):
     _fields_ = [("select_ms", C.c_float), ("merge_ms", C.c_float), ("flag_ms", C.c_float), ("replay_ms", C.c_float),
                 ("listed_queries", C.c_int), ("splits", C.c_int), ("workgroups", C.c_int),
                 ("queries_per_group", C.c_int), ("register_form", C.c_int)]
+
+
+class MultiRefinerSearchTiming(C.Structure):
+    _fields_ = RefinerSearchTiming._fields_ + [("gather_ms", C.c_float), ("cross_merge_ms", C.c_float),
+                                               ("chain_ms", C.c_float), ("chain_shards", C.c_int), ("sets", C.c_int)]
 
 
 class MultiInfo(C.Structure):
@@ -220,6 +226,9 @@ def load():
     L.vaqhip_multi_search_refine.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp]
     L.vaqhip_multi_search_refine_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.vaqhip_multi_refiner_get_info.argtypes = [vp, C.POINTER(MultiRefinerInfo)]
+    L.vaqhip_multi_refiner_search.argtypes = [vp, vp, i32, i32, vp, vp]
+    L.vaqhip_multi_refiner_search_device.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+    L.vaqhip_multi_refiner_last_search_timing.argtypes = [vp, C.POINTER(MultiRefinerSearchTiming)]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:

@@ -26,6 +26,7 @@ SCAN_BF_HEADER = os.path.join(CSRC, "vaq_scan_bf.h")
 FAST_HEADER = os.path.join(CSRC, "vaq_fast.h")
 REFINE_GROUP_HEADER = os.path.join(CSRC, "vaq_refine_group.h")  # Eigen's squaredNorm over 16 lanes: refine, exhaustive form
 EXHAUST_HEADER = os.path.join(CSRC, "vaq_exhaust.h")  # the same by one thread, host and device: exhaustive form
+EXHAUST_PLAN_HEADER = os.path.join(CSRC, "vaqhip_exhaust_plan.h")  # the exhaustive form's plan and launches: both refiners
 RESTATED_HEADER = os.path.join(CSRC, "vaq_restated.h")  # stdsort, stdheap, refheap, sq_norm_eigen: FAST, TI planning, the replay, k-means, refine
 INTERNAL_HEADER = os.path.join(CSRC, "vaqhip_internal.h")
 INDEX_HEADER = os.path.join(CSRC, "vaqhip_index.h")  # private to the single-index host files
@@ -63,6 +64,8 @@ def _deps(src: str):
         deps.append(REFINE_GROUP_HEADER)
     if src == "vaq_exhaust.hip":
         deps.append(EXHAUST_HEADER)
+    if src in ("vaqhip_refiner.cpp", "vaqhip_multi_refiner.cpp"):
+        deps.append(EXHAUST_PLAN_HEADER)
     return deps
 OBJDIR = os.path.join(LIBDIR, "obj")
 # Experiment builds: VAQ_VARIANT=name compiles (with VAQ_EXTRA_FLAGS) into vaq_amd/lib/variants/name/

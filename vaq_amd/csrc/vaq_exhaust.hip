@@ -18,7 +18,9 @@
 // xs_replay_kernel     "exact_ties": one workgroup per LISTED query (launch_exact_flag lists the queries whose merged
 //                      k + 1 list holds two equal distances) walks rows 0..N-1 in order: 1024 distances into LDS, then
 //                      wave 0 tests 64 rows at a time against the heap top by ballot and lane 0 applies the
-//                      reference's statements to the admitted rows in row order; heap_reorder at the end.
+//                      reference's statements to the admitted rows in row order; heap_reorder at the end.  It is one
+//                      link of a chain: across the shards of a multi-device refiner the raw heap arrays go from
+//                      shard to shard and only the last link reorders (xs_scatter_kernel places its slots).
 // Compiled with -ffp-contract=off like the rest: no FMA, no MFMA, no float atomics; plain vector stores.
 #include "vaq_exhaust.h"
 #include "vaq_kernels.h"
@@ -180,12 +182,21 @@ __global__ __launch_bounds__(XS_THREADS) void xs_wide_kernel(const XsParams p, c
   xs_emit(p, sh, w, tid);
 }
 
-// VAQ.cpp:863-872 over ALL rows in row order, for the listed queries.  A block beyond the device-side count exits
-// at once: no host round trip decides anything.
+// VAQ.cpp:863-872 over rows [0, N) of `rows` in row order, for the listed queries.  A block beyond the device-side
+// count exits at once: no host round trip decides anything.  One LINK of a chain over shards (the single refiner's
+// call is the chain of one link): entry e starts from the raw heap arrays hin_v / hin_i [e][k] as the link before
+// left them (nullptr: heap_heapify of nothing), and
+//   finish == 0   leaves its raw arrays in hout_v / hout_i [e][k] for the next link;
+//   finish != 0   applies heap_reorder and writes the k slots: to labels / dist [query][k], or, when labels is
+//                 nullptr, to hout_v / hout_i [e][k] (xs_scatter_kernel places them on the first device).
+// The heap's statements see the rows of all links in order with nothing in between.
 __global__ __launch_bounds__(XS_THREADS) void xs_replay_kernel(const float *__restrict__ Q, int D,
                                                                const float *__restrict__ rows, int64_t N, int64_t id_base,
                                                                int k, const int *__restrict__ list,
                                                                const unsigned *__restrict__ count,
+                                                               const float *__restrict__ hin_v,
+                                                               const int *__restrict__ hin_i, float *__restrict__ hout_v,
+                                                               int *__restrict__ hout_i, int finish,
                                                                int32_t *__restrict__ labels, float *__restrict__ dist) {
   __shared__ float hv[XS_MAX_K1];
   __shared__ int hi[XS_MAX_K1];
@@ -195,9 +206,10 @@ __global__ __launch_bounds__(XS_THREADS) void xs_replay_kernel(const float *__re
   if (blockIdx.x >= *count) return;
   const int q = list[blockIdx.x], tid = threadIdx.x, lane = tid & 63;
   for (int e = tid; e < D; e += XS_THREADS) qs[e] = Q[(size_t)q * D + e];
-  for (int i = tid; i < k; i += XS_THREADS) {  // heap_heapify of nothing
-    hv[i] = FLT_MAX;
-    hi[i] = -1;
+  const size_t eo = (size_t)blockIdx.x * k;  // this entry's slots of the chain's state
+  for (int i = tid; i < k; i += XS_THREADS) {  // heap_heapify of nothing, or the heap as the link before left it
+    hv[i] = hin_v ? hin_v[eo + i] : FLT_MAX;
+    hi[i] = hin_i ? hin_i[eo + i] : -1;
   }
   __syncthreads();
   const int g = tid / RF_GROUP, j = tid % RF_GROUP, gbase = lane & ~(RF_GROUP - 1);
@@ -232,12 +244,35 @@ __global__ __launch_bounds__(XS_THREADS) void xs_replay_kernel(const float *__re
     }
     __syncthreads();
   }
+  if (!finish) {  // (the chunk loop ended past a barrier: hv / hi are lane 0's last)
+    for (int i = tid; i < k; i += XS_THREADS) {
+      hout_v[eo + i] = hv[i];
+      hout_i[eo + i] = hi[i];
+    }
+    return;
+  }
   if (tid == 0) s_kept = refheap::reorder(k, hv, hi);
   __syncthreads();
   const int kept = s_kept;
+  int32_t *ol = labels ? labels + (size_t)q * k : hout_i + eo;
+  float *od = labels ? dist + (size_t)q * k : hout_v + eo;
   for (int i = tid; i < k; i += XS_THREADS) {
-    labels[(size_t)q * k + i] = i < kept ? hi[k - kept + i] : -1;
-    dist[(size_t)q * k + i] = i < kept ? hv[k - kept + i] : FLT_MAX;
+    ol[i] = i < kept ? hi[k - kept + i] : -1;
+    od[i] = i < kept ? hv[k - kept + i] : FLT_MAX;
+  }
+}
+
+// the k slots the chain's last link wrote per ENTRY, brought to the first device: entry e is query list[e]
+__global__ __launch_bounds__(XS_THREADS) void xs_scatter_kernel(int k, const int *__restrict__ list,
+                                                                const unsigned *__restrict__ count,
+                                                                const float *__restrict__ src_v,
+                                                                const int *__restrict__ src_i,
+                                                                int32_t *__restrict__ labels, float *__restrict__ dist) {
+  if (blockIdx.x >= *count) return;
+  const size_t eo = (size_t)blockIdx.x * k, qo = (size_t)list[blockIdx.x] * k;
+  for (int i = threadIdx.x; i < k; i += XS_THREADS) {
+    labels[qo + i] = src_i[eo + i];
+    dist[qo + i] = src_v[eo + i];
   }
 }
 
@@ -308,14 +343,34 @@ hipError_t launch_exhaust_select(const XsParams &p, const float *Q, const float 
   return hipGetLastError();
 }
 
-hipError_t launch_exhaust_replay(const float *Q, int nq, int D, const float *rows, int64_t N, int64_t id_base, int k,
-                                 const int *list, const unsigned *count, int32_t *labels, float *dist, hipStream_t st) {
+hipError_t launch_exhaust_replay_link(const float *Q, int nq, int D, const float *rows, int64_t N, int64_t id_base, int k,
+                                      const int *list, const unsigned *count, const float *hin_v, const int *hin_i,
+                                      float *hout_v, int *hout_i, int finish, int32_t *labels, float *dist,
+                                      hipStream_t st) {
   if (nq == 0) return hipSuccess;
   if (nq < 0 || D < 1 || (size_t)D > refine_rows_max_dim() || N < 0 || k < 1 || k > XS_MAX_K1 || id_base < 0 ||
-      id_base + N > 0x7fffffffLL)
+      id_base + N > 0x7fffffffLL || !list || !count || (hin_v == nullptr) != (hin_i == nullptr) ||
+      (hout_v == nullptr) != (hout_i == nullptr) || (labels == nullptr) != (dist == nullptr) ||
+      (finish ? !labels && !hout_v : !hout_v))
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(xs_replay_kernel, dim3(nq), dim3(XS_THREADS), (size_t)D * sizeof(float), st, Q, D, rows, N, id_base,
-                     k, list, count, labels, dist);
+                     k, list, count, hin_v, hin_i, hout_v, hout_i, finish, labels, dist);
+  return hipGetLastError();
+}
+
+hipError_t launch_exhaust_replay(const float *Q, int nq, int D, const float *rows, int64_t N, int64_t id_base, int k,
+                                 const int *list, const unsigned *count, int32_t *labels, float *dist, hipStream_t st) {
+  if (!labels || !dist) return nq == 0 ? hipSuccess : hipErrorInvalidValue;
+  return launch_exhaust_replay_link(Q, nq, D, rows, N, id_base, k, list, count, nullptr, nullptr, nullptr, nullptr, 1, labels,
+                                    dist, st);
+}
+
+hipError_t launch_exhaust_scatter(int nq, int k, const int *list, const unsigned *count, const float *src_v,
+                                  const int *src_i, int32_t *labels, float *dist, hipStream_t st) {
+  if (nq == 0) return hipSuccess;
+  if (nq < 0 || k < 1 || k > XS_MAX_K1 || !list || !count || !src_v || !src_i || !labels || !dist)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(xs_scatter_kernel, dim3(nq), dim3(XS_THREADS), 0, st, k, list, count, src_v, src_i, labels, dist);
   return hipGetLastError();
 }
 

@@ -198,6 +198,17 @@ hipError_t launch_exhaust_select(const XsParams &p, const float *Q, const float 
 // labels / dist; blocks at or beyond *count exit at once (launch nq of them)
 hipError_t launch_exhaust_replay(const float *Q, int nq, int D, const float *rows, int64_t N, int64_t id_base, int k,
                                  const int *list, const unsigned *count, int32_t *labels, float *dist, hipStream_t st);
+// The same as one link of a chain over shards: `rows` are the shard's n rows, id_base its first label.  Entry e of
+// the list starts from the raw heap arrays hin_v / hin_i [e][k] the link before left (nullptr: the empty heap).
+// finish == 0: its raw arrays go to hout_v / hout_i [e][k].  finish != 0: heap_reorder, the k slots go to labels / dist
+// [query][k], or with labels == nullptr to hout_v / hout_i [e][k], which launch_exhaust_scatter -- on the device of
+// the caller's buffers, after a copy -- places at query list[e].  launch_exhaust_replay is the chain of one link.
+hipError_t launch_exhaust_replay_link(const float *Q, int nq, int D, const float *rows, int64_t N, int64_t id_base, int k,
+                                      const int *list, const unsigned *count, const float *hin_v, const int *hin_i,
+                                      float *hout_v, int *hout_i, int finish, int32_t *labels, float *dist,
+                                      hipStream_t st);
+hipError_t launch_exhaust_scatter(int nq, int k, const int *list, const unsigned *count, const float *src_v,
+                                  const int *src_i, int32_t *labels, float *dist, hipStream_t st);
 // dwords the packed layout needs for `rows` rows
 int64_t packed_words(int64_t rows, int M, int layout, int W);
 // Pack rows [row_begin, row_end) (codes_u16 points at row_begin; row_begin a

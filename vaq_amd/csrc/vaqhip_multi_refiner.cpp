@@ -17,11 +17,22 @@
 //   3 gather     shard 0's stream waits for every shard's event and copies the planes of shards 1.. next to its own
 //   4 select     refine_select_kernel there, straight into the caller's buffers; the caller's stream waits for it
 // Every wait is a stream wait on an event.  With one shard the call is launch_refine_rows on the caller's stream.
+//
+// The exhaustive form (vaqhip_multi_refiner_search: every resident row a candidate, in row order) is the second half
+// of this file.  Its selection DOES depend on other shards' rows under "exact_ties", so it ends in a chain of replays:
+//   A select     every shard with rows: the single form's select + merge over its own rows (vaqhip_exhaust_plan.h), a
+//                [nq][k1] list per shard; on the shards' workers
+//   B gather     the lists next to shard 0's, one merge by (distance, label) there: the answer without "exact_ties"
+//   C flag       on the MERGED k + 1 lists: queries without equal distances are copied out, the others listed
+//   D chain      the listed queries through the reference's heap, shard after shard in row order; the raw heap
+//                arrays travel by peer copy, the last shard with rows reorders, shard 0 places the slots
+// B to D are enqueued by the calling thread in chain order, so an event is always recorded before its wait is enqueued.
 #include "vaqhip_multi.h"
 
 #include <cstring>
 
 #include "vaq_kernels.h"
+#include "vaqhip_exhaust_plan.h"
 
 using namespace vaqhost;
 
@@ -37,6 +48,16 @@ struct RShard {
   DevBuf d_q, d_lin;          // shards 1..: the set's queries and candidate labels
   DevBuf d_plane;             // shards 1..: float [nq][R]; shard 0 writes into the gathered planes
   std::vector<hipEvent_t> t;  // option "timing": 3 events per set (start, broadcast done, distances done)
+  // the exhaustive form: this device's workspace and its plan for the call in flight; shards 1..: the shard's
+  // [set][k1] lists (shard 0 writes into the gathered lists) and the replay list with its count; the chain's state,
+  // [set][k] raw heap arrays in and out (shard 0's x_hin receives the last link's finished slots)
+  XsWork xs;
+  XsPlan xpl = {1, 1, 1};
+  int x_wgs = 0, x_qg = 0;
+  DevBuf x_l, x_d, x_list;
+  DevBuf x_hin_v, x_hin_i, x_hout_v, x_hout_i;
+  hipEvent_t link = nullptr;  // this shard's link of the chain is complete
+  hipEvent_t xt[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // "timing": start, selected, merged; link start, end
   std::string err;
 };
 
@@ -49,6 +70,7 @@ struct vaqhip_multi_refiner {
   int64_t N = 0, id_base = 0;
   vaq::RefineBounds bounds = {};
   int opt_exact = 0, opt_timing = 0;
+  int opt_splits = 0;  // "exhaustive_splits": per shard, 0 = automatic
   std::mutex mu;  // one call at a time
   vaq::JobPool pool;
   // on the first device
@@ -61,6 +83,16 @@ struct vaqhip_multi_refiner {
   std::vector<hipEvent_t> t;              // option "timing": 3 events per set (gather start, gathered, selected)
   int last_sets = 0;                      // sets of the last call that carry timing events
   bool last_single = false;               //   it was the one-shard form (t[0], t[1] around the kernel)
+  // the exhaustive form, on the first device: the gathered [lists][set][k1] labels and distances, the cross-shard
+  // merge's scratch, the merged k + 1 lists and the replay list with its count
+  DevBuf x_gl, x_gd, x_ms_d, x_ms_id, x_k1_l, x_k1_d, x_list;
+  hipEvent_t flagged = nullptr;  // the replay list of the current set is complete
+  hipEvent_t xt[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // "timing": gather start, gathered, merged, flagged, placed
+  vaqhip_multi_refiner_search_timing x_timing = {};
+  int x_k = 0, x_k1 = 0, x_lists = 0;     // of the search in flight: k, entries per list, lists gathered
+  int x_slot[VAQHIP_MAX_DEVICES] = {};    //   where shard g's list sits among them
+  int x_last = 0;                         //   the last shard that holds rows (0 when none does)
+  bool x_chain = false;                   //   "exact_ties" and some shard holds rows: k1 = k + 1, flag step, chain
   // the set in flight
   const float *d_q0 = nullptr;
   const int32_t *d_lin0 = nullptr;
@@ -307,6 +339,322 @@ int search_refine_locked(vaqhip_multi *mx, vaqhip_multi_refiner *r, const float 
   return refine_device_locked(r, d_q, nq, r->w_cand_l.as<int32_t>(), R, k, d_lout, d_dout, st);
 }
 
+
+// ---- the exhaustive form across shards ----
+// the gathered lists of one set, in bytes on the first device (the set is cut to fit; every shard's own candidate
+// lists are bounded by XS_LIST_BYTES as in the single form)
+constexpr size_t XS_GATHER_BYTES = (size_t)256 << 20;
+
+int check_search(const vaqhip_multi_refiner *r, int nq, int k, const void *a, const void *b, const void *c) {
+  if (!r) return mfail(VAQHIP_EINVAL, "multi refiner is null");
+  if (nq < 0 || k < 1) return mfail(VAQHIP_EINVAL, "bad sizes (nq=%d k=%d)", nq, k);
+  if (k > VAQHIP_MAX_K) return mfail(VAQHIP_EUNSUPPORTED, "k=%d > %d", k, VAQHIP_MAX_K);
+  if (nq > 0 && (!a || !b || !c)) return mfail(VAQHIP_EINVAL, "null pointer");
+  return VAQHIP_OK;
+}
+
+bool xs_takes_part(int g, const RShard &s) { return g == 0 || s.n > 0; }  // (shard 0 hosts the merge even without rows)
+
+// Phase A of a set, on the shard's worker: buffers, the queries, select + merge over the shard's own rows
+int xs_enqueue_shard(vaqhip_multi_refiner *r, int g, RShard &s) {
+  if (!xs_takes_part(g, s)) return 0;  // (owns no label: no list, no link)
+  const int n = r->nq, D = r->D, k = r->x_k, k1 = r->x_k1;
+  const bool exact = r->x_chain, timing = r->opt_timing != 0;
+  MHIP(hipSetDevice(s.device));
+  // Growing frees a buffer the last set's gather, merge and chain may still read: `finished` follows all of them.
+  const size_t lists = (size_t)n * k1 * 4, state = (size_t)n * k * 4, list = ((size_t)n + 1) * 4;
+  struct Fit { DevBuf *b; size_t bytes; } fit[16];
+  int nf = 0;
+  if (g == 0) {
+    const size_t ms = vaq::merge_scratch_elems(r->x_lists, n, k1) * 4;
+    for (DevBuf *b : {&r->x_gl, &r->x_gd}) fit[nf++] = Fit{b, (size_t)r->x_lists * lists};
+    for (DevBuf *b : {&r->x_ms_d, &r->x_ms_id}) fit[nf++] = Fit{b, ms};
+    if (exact) {
+      for (DevBuf *b : {&r->x_k1_l, &r->x_k1_d}) fit[nf++] = Fit{b, lists};
+      fit[nf++] = Fit{&r->x_list, list};
+    }
+  } else {
+    fit[nf++] = Fit{&s.d_q, (size_t)n * D * sizeof(float)};
+    for (DevBuf *b : {&s.x_l, &s.x_d}) fit[nf++] = Fit{b, lists};
+    if (exact) fit[nf++] = Fit{&s.x_list, list};
+  }
+  if (exact)
+    for (DevBuf *b : {&s.x_hin_v, &s.x_hin_i, &s.x_hout_v, &s.x_hout_i}) fit[nf++] = Fit{b, state};
+  bool grows = !s.xs.fits(s.xpl, k1, false);
+  for (int i = 0; i < nf; i++) grows |= fit[i].bytes > fit[i].b->cap;
+  if (grows) MHIP(hipEventSynchronize(r->finished));
+  for (int i = 0; i < nf; i++) MHIP(fit[i].b->ensure(fit[i].bytes));
+  MHIP(s.xs.fit(s.xpl, k1, false, false));
+  if (timing)
+    for (hipEvent_t &e : s.xt)
+      if (!e) MHIP(hipEventCreate(&e));
+  // the previous set has been read (never recorded: no wait); the caller's inputs are there
+  MHIP(hipStreamWaitEvent(s.stream, r->finished, 0));
+  MHIP(hipStreamWaitEvent(s.stream, r->user_ready, 0));
+  if (timing) MHIP(hipEventRecord(s.xt[0], s.stream));
+  const float *dq = r->d_q0;
+  int32_t *out_l = r->x_gl.as<int32_t>();  // shard 0: list 0 of the gathered lists
+  float *out_d = r->x_gd.as<float>();
+  if (g > 0) {
+    MHIP(hipMemcpyPeerAsync(s.d_q.p, s.device, r->d_q0, r->sh[0].device, (size_t)n * D * sizeof(float), s.stream));
+    dq = s.d_q.as<float>();
+    out_l = s.x_l.as<int32_t>();
+    out_d = s.x_d.as<float>();
+  }
+  const XsRows rows = {s.d_rows.as<float>(), s.n, r->id_base + s.lo, D};
+  MHIP(xs_select_merge(s.xs, s.xpl, rows, dq, n, k1, out_l, out_d, s.stream, timing ? s.xt[1] : nullptr, &s.x_wgs, &s.x_qg));
+  if (timing) MHIP(hipEventRecord(s.xt[2], s.stream));
+  MHIP(hipEventRecord(s.done, s.stream));
+  return 0;
+}
+
+// Phases B and C, by the calling thread on the first device, once every shard's part is enqueued
+int xs_gather_merge_flag(vaqhip_multi_refiner *r, int32_t *d_lout, float *d_dout) {
+  RShard &s = r->sh[0];
+  const int n = r->nq, k = r->x_k, k1 = r->x_k1;
+  const bool exact = r->x_chain, timing = r->opt_timing != 0;
+  const size_t plane = (size_t)n * k1;
+  MHIP(hipSetDevice(s.device));
+  if (timing)
+    for (hipEvent_t &e : r->xt)
+      if (!e) MHIP(hipEventCreate(&e));
+  for (int g = 1; g < r->G; g++)
+    if (r->sh[g].n > 0) MHIP(hipStreamWaitEvent(s.stream, r->sh[g].done, 0));
+  if (timing) MHIP(hipEventRecord(r->xt[0], s.stream));
+  for (int g = 1; g < r->G; g++) {
+    const RShard &u = r->sh[g];
+    if (u.n == 0) continue;
+    const size_t at = (size_t)r->x_slot[g] * plane;
+    MHIP(hipMemcpyPeerAsync(r->x_gl.as<int32_t>() + at, s.device, u.x_l.p, u.device, plane * 4, s.stream));
+    MHIP(hipMemcpyPeerAsync(r->x_gd.as<float>() + at, s.device, u.x_d.p, u.device, plane * 4, s.stream));
+  }
+  if (timing) MHIP(hipEventRecord(r->xt[1], s.stream));
+  int32_t *m_l = exact ? r->x_k1_l.as<int32_t>() : d_lout;
+  float *m_d = exact ? r->x_k1_d.as<float>() : d_dout;
+  MHIP(vaq::launch_merge(r->x_gd.as<float>(), r->x_gl.as<int>(), nullptr, r->x_lists, (int64_t)plane, (int64_t)k1, n, k1, 0, 1,
+                         m_l, m_d, nullptr, r->x_ms_d.as<float>(), r->x_ms_id.as<int>(), s.stream));
+  if (timing) MHIP(hipEventRecord(r->xt[2], s.stream));
+  if (exact) {
+    int *list = r->x_list.as<int>();
+    MHIP(vaq::launch_exact_flag(n, k, m_l, m_d, d_lout, d_dout, list, reinterpret_cast<unsigned *>(list + n), s.stream));
+    MHIP(hipEventRecord(r->flagged, s.stream));
+  }
+  if (timing) MHIP(hipEventRecord(r->xt[3], s.stream));
+  return 0;
+}
+
+// One link of phase D on shard g, by the calling thread: the list, the heap arrays of the link before (prev < 0: none),
+// the replay over the shard's rows.  Enqueued in chain order: `flagged` and the previous link's event are recorded.
+int xs_link(vaqhip_multi_refiner *r, int g, int prev, int32_t *d_lout, float *d_dout) {
+  RShard &s = r->sh[g];
+  const int n = r->nq, k = r->x_k, dev0 = r->sh[0].device;
+  const bool timing = r->opt_timing != 0, last = g == r->x_last;
+  const size_t state = (size_t)n * k * 4;
+  MHIP(hipSetDevice(s.device));
+  const float *dq = r->d_q0;
+  const int *list = r->x_list.as<int>();
+  if (g > 0) {  // (shard 0's stream holds the flag step itself)
+    MHIP(hipStreamWaitEvent(s.stream, r->flagged, 0));
+    MHIP(hipMemcpyPeerAsync(s.x_list.p, s.device, r->x_list.p, dev0, ((size_t)n + 1) * 4, s.stream));
+    dq = s.d_q.as<float>();  // (there since phase A)
+    list = s.x_list.as<int>();
+  }
+  if (prev >= 0) {
+    const RShard &u = r->sh[prev];
+    MHIP(hipStreamWaitEvent(s.stream, u.link, 0));
+    MHIP(hipMemcpyPeerAsync(s.x_hin_v.p, s.device, u.x_hout_v.p, u.device, state, s.stream));
+    MHIP(hipMemcpyPeerAsync(s.x_hin_i.p, s.device, u.x_hout_i.p, u.device, state, s.stream));
+  }
+  if (timing) MHIP(hipEventRecord(s.xt[3], s.stream));
+  const bool direct = last && g == 0;  // (all rows on the first shard: its link writes the caller's buffers)
+  MHIP(vaq::launch_exhaust_replay_link(dq, n, r->D, s.d_rows.as<float>(), s.n, r->id_base + s.lo, k, list,
+                                       reinterpret_cast<const unsigned *>(list + n), prev >= 0 ? s.x_hin_v.as<float>() : nullptr,
+                                       prev >= 0 ? s.x_hin_i.as<int>() : nullptr, direct ? nullptr : s.x_hout_v.as<float>(),
+                                       direct ? nullptr : s.x_hout_i.as<int>(), last ? 1 : 0, direct ? d_lout : nullptr,
+                                       direct ? d_dout : nullptr, s.stream));
+  if (timing) MHIP(hipEventRecord(s.xt[4], s.stream));
+  MHIP(hipEventRecord(s.link, s.stream));
+  return 0;
+}
+
+// the end of a set on the first device: with a chain, the last link's slots placed at their queries
+int xs_finish(vaqhip_multi_refiner *r, bool chain, int32_t *d_lout, float *d_dout, hipStream_t user) {
+  RShard &s = r->sh[0];
+  const int n = r->nq, k = r->x_k;
+  MHIP(hipSetDevice(s.device));
+  if (chain && r->x_last > 0) {
+    const RShard &u = r->sh[r->x_last];
+    const size_t state = (size_t)n * k * 4;
+    const int *list = r->x_list.as<int>();
+    MHIP(hipStreamWaitEvent(s.stream, u.link, 0));
+    MHIP(hipMemcpyPeerAsync(s.x_hin_v.p, s.device, u.x_hout_v.p, u.device, state, s.stream));
+    MHIP(hipMemcpyPeerAsync(s.x_hin_i.p, s.device, u.x_hout_i.p, u.device, state, s.stream));
+    MHIP(vaq::launch_exhaust_scatter(n, k, list, reinterpret_cast<const unsigned *>(list + n), s.x_hin_v.as<float>(),
+                                     s.x_hin_i.as<int>(), d_lout, d_dout, s.stream));
+  }
+  if (r->opt_timing) MHIP(hipEventRecord(r->xt[4], s.stream));
+  MHIP(hipEventRecord(r->finished, s.stream));
+  MHIP(hipStreamWaitEvent(user, r->finished, 0));
+  return 0;
+}
+
+// option "timing": waits for the set and adds its figures (the slowest shard's select, merge and link)
+int xs_read_timing(vaqhip_multi_refiner *r, bool chain) {
+  RShard &s = r->sh[0];
+  vaqhip_multi_refiner_search_timing &t = r->x_timing;
+  auto span = [](hipEvent_t a, hipEvent_t b, float *ms) { return hipEventElapsedTime(ms, a, b); };
+  MHIP(hipSetDevice(s.device));
+  MHIP(hipEventSynchronize(r->finished));
+  float sel = 0, mer = 0, rep = 0, ms = 0;
+  for (int g = 0; g < r->G; g++) {
+    RShard &u = r->sh[g];
+    if (!xs_takes_part(g, u)) continue;
+    MHIP(hipSetDevice(u.device));
+    MHIP(span(u.xt[0], u.xt[1], &ms));
+    sel = std::max(sel, ms);
+    MHIP(span(u.xt[1], u.xt[2], &ms));
+    mer = std::max(mer, ms);
+    if (chain && u.n > 0) {
+      MHIP(span(u.xt[3], u.xt[4], &ms));
+      rep = std::max(rep, ms);
+    }
+  }
+  MHIP(hipSetDevice(s.device));
+  t.select_ms += sel;
+  t.merge_ms += mer;
+  t.replay_ms += rep;
+  MHIP(span(r->xt[0], r->xt[1], &ms));
+  t.gather_ms += ms;
+  MHIP(span(r->xt[1], r->xt[2], &ms));
+  t.cross_merge_ms += ms;
+  MHIP(span(r->xt[2], r->xt[3], &ms));
+  t.flag_ms += ms;
+  MHIP(span(r->xt[3], r->xt[4], &ms));
+  if (chain) t.chain_ms += ms;
+  if (chain) {
+    unsigned listed = 0;
+    MHIP(hipMemcpy(&listed, r->x_list.as<int>() + r->nq, sizeof(unsigned), hipMemcpyDeviceToHost));
+    t.listed_queries += (int)listed;
+  }
+  return 0;
+}
+
+// Device pointers on the first device, enqueue only; r->mu held.  As refine_device_locked.
+int search_device_locked(vaqhip_multi_refiner *r, const float *d_q, int nq, int k, int32_t *d_lout, float *d_dout,
+                         hipStream_t user) {
+  RShard &s = r->sh[0];
+  bool any_cap = false;
+  for (const RShard &u : r->sh) any_cap |= u.cap_rows > 0;
+  if (r->N == 0 && !any_cap) return mfail(VAQHIP_ESTATE, "no rows were set");
+  if (hipSetDevice(s.device) != hipSuccess) return mfail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", s.device);
+  const bool exact = r->opt_exact != 0, timing = r->opt_timing != 0;
+  s.err.clear();
+  r->x_timing = {};
+  r->x_timing.register_form = r->D <= (int)vaq::exhaust_register_max_dim();
+  if (r->G == 1) {  // the single refiner's launches, at their cost, on the caller's stream
+    auto body = [&]() -> int {
+      MHIP(s.xs.size_for(s.device, r->D));
+      const int k1 = exact ? k + 1 : k;
+      const XsPlan pl = xs_plan(s.xs, r->N, r->opt_splits, nq, k1);
+      MHIP(s.xs.fit(pl, k1, exact, timing));
+      MHIP(hipStreamWaitEvent(user, r->finished, 0));  // (the workspace is shared by the callers' streams)
+      const XsRows rows = {s.d_rows.as<float>(), r->N, r->id_base, r->D};
+      vaqhip_refiner_search_timing t1 = {};
+      hipError_t e = hipSuccess;
+      int sets = 0;
+      for (int q0 = 0; q0 < nq && e == hipSuccess; q0 += pl.chunk, sets++)
+        e = xs_search_set(s.xs, pl, rows, d_q + (size_t)q0 * r->D, std::min(pl.chunk, nq - q0), k, exact,
+                          d_lout + (size_t)q0 * k, d_dout + (size_t)q0 * k, user, timing ? &t1 : nullptr);
+      (void)hipEventRecord(r->finished, user);  // (also after a failure: work may be enqueued already)
+      MHIP(e);
+      vaqhip_multi_refiner_search_timing &t = r->x_timing;
+      t.select_ms = t1.select_ms;
+      t.merge_ms = t1.merge_ms;
+      t.flag_ms = t1.flag_ms;
+      t.replay_ms = t1.replay_ms;
+      t.listed_queries = t1.listed_queries;
+      t.splits = pl.S;
+      t.workgroups = t1.workgroups;
+      t.queries_per_group = t1.queries_per_group;
+      t.chain_shards = r->N > 0 ? 1 : 0;
+      t.sets = sets;
+      return 0;
+    };
+    const int rc = body();
+    return rc ? mfail(rc, "device %d: %s", s.device, s.err.c_str()) : VAQHIP_OK;
+  }
+  if (r->dirty) drain(r);
+  // the call's plan: the lists gathered, the chain's ends, one set size for every shard
+  int first = -1;
+  r->x_lists = 0;
+  r->x_last = 0;
+  for (int g = 0; g < r->G; g++) {
+    const RShard &u = r->sh[g];
+    if (!xs_takes_part(g, u)) continue;
+    r->x_slot[g] = r->x_lists++;
+    if (u.n > 0) {
+      if (first < 0) first = g;
+      r->x_last = g;
+    }
+  }
+  const bool chain = exact && first >= 0;  // (no rows at all: every slot is -1 / FLT_MAX under either rule)
+  const int k1 = chain ? k + 1 : k;
+  r->x_chain = chain;
+  r->x_k = k;
+  r->x_k1 = k1;
+  int set = std::min(nq, SET_QUERIES);
+  set = (int)std::min<size_t>((size_t)set, std::max<size_t>(1, XS_GATHER_BYTES / ((size_t)r->x_lists * k1 * 8)));
+  auto plan = [&](int max_chunk) -> int {
+    for (int g = 0; g < r->G; g++) {
+      RShard &u = r->sh[g];
+      if (!xs_takes_part(g, u)) continue;
+      if (hipSetDevice(u.device) != hipSuccess) return mfail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", u.device);
+      const hipError_t e = u.xs.size_for(u.device, r->D);
+      if (e != hipSuccess) return mfail(hip_code(e), "device %d: %s", u.device, hipGetErrorString(e));
+      u.xpl = xs_plan(u.xs, u.n, r->opt_splits, nq, k1, max_chunk);
+      set = std::min(set, u.xpl.chunk);
+    }
+    return VAQHIP_OK;
+  };
+  if (const int rc = plan(set)) return rc;  // every shard's own bound ...
+  if (const int rc = plan(set)) return rc;  // ... and the smallest of them for all: equal sets of one size
+  set = r->sh[0].xpl.chunk;
+  r->x_timing.splits = r->sh[std::max(first, 0)].xpl.S;
+  r->x_timing.chain_shards = first < 0 ? 0 : r->x_lists - (r->sh[0].n > 0 ? 0 : 1);
+  if (hipSetDevice(s.device) != hipSuccess) return mfail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", s.device);
+  if (hipEventRecord(r->user_ready, user) != hipSuccess) return mfail(VAQHIP_EHIP, "recording the caller's stream");
+  for (int q0 = 0; q0 < nq; q0 += set) {
+    r->nq = std::min(set, nq - q0);
+    r->d_q0 = d_q + (size_t)q0 * r->D;
+    int32_t *lo = d_lout + (size_t)q0 * k;
+    float *d_o = d_dout + (size_t)q0 * k;
+    int rc = on_shards(r, [&](int g, RShard &u) { return xs_enqueue_shard(r, g, u); });
+    auto step = [&](int g, int step_rc) {  // a step of the calling thread failed on shard g
+      return step_rc ? mfail(step_rc, "shard %d (device %d): %s", g, r->sh[g].device, r->sh[g].err.c_str()) : 0;
+    };
+    if (!rc) {
+      s.err.clear();
+      rc = step(0, xs_gather_merge_flag(r, lo, d_o));
+    }
+    for (int g = 0, prev = -1; !rc && chain && g < r->G; g++) {
+      if (r->sh[g].n == 0) continue;  // (a shard without rows is no link)
+      r->sh[g].err.clear();
+      rc = step(g, xs_link(r, g, prev, lo, d_o));
+      prev = g;
+    }
+    if (!rc) rc = step(0, xs_finish(r, chain, lo, d_o, user));
+    if (!rc && timing) rc = step(0, xs_read_timing(r, chain));
+    if (rc) {
+      r->dirty = true;  // (`finished` may not follow what was enqueued: the next call drains first)
+      return rc;
+    }
+    r->x_timing.sets++;
+    r->x_timing.workgroups = r->sh[std::max(first, 0)].x_wgs;
+    r->x_timing.queries_per_group = r->sh[std::max(first, 0)].x_qg;
+  }
+  return VAQHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -336,10 +684,12 @@ int vaqhip_multi_refiner_create(vaqhip_multi_refiner **out, int D, int n_devices
     RShard &s = r->sh[g];
     s.device = device_ids[g];
     bool ok = hipSetDevice(s.device) == hipSuccess && hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess &&
-              hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess;
+              hipEventCreateWithFlags(&s.done, hipEventDisableTiming) == hipSuccess &&
+              hipEventCreateWithFlags(&s.link, hipEventDisableTiming) == hipSuccess;
     if (g == 0)
       ok = ok && hipEventCreateWithFlags(&r->user_ready, hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&r->finished, hipEventDisableTiming) == hipSuccess;
+           hipEventCreateWithFlags(&r->finished, hipEventDisableTiming) == hipSuccess &&
+           hipEventCreateWithFlags(&r->flagged, hipEventDisableTiming) == hipSuccess;
     if (!ok) {
       vaqhip_multi_refiner_destroy(r);
       return mfail(VAQHIP_ENODEVICE, "stream / event creation on device %d failed", s.device);
@@ -357,15 +707,25 @@ void vaqhip_multi_refiner_destroy(vaqhip_multi_refiner *r) {
   for (RShard &s : r->sh) {
     (void)hipSetDevice(s.device);
     (void)hipDeviceSynchronize();  // (refines enqueued on the callers' streams read the rows)
-    for (DevBuf *b : {&s.d_rows, &s.d_q, &s.d_lin, &s.d_plane}) b->release();
+    for (DevBuf *b : {&s.d_rows, &s.d_q, &s.d_lin, &s.d_plane, &s.x_l, &s.x_d, &s.x_list, &s.x_hin_v, &s.x_hin_i, &s.x_hout_v,
+                      &s.x_hout_i})
+      b->release();
+    s.xs.release();
     for (hipEvent_t e : s.t) (void)hipEventDestroy(e);
-    if (s.done) (void)hipEventDestroy(s.done);
+    for (hipEvent_t e : s.xt)
+      if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : {s.done, s.link})
+      if (e) (void)hipEventDestroy(e);
     if (s.stream) (void)hipStreamDestroy(s.stream);
   }
   if (!r->sh.empty()) (void)hipSetDevice(r->sh[0].device);
-  for (DevBuf *b : {&r->d_planes, &r->w_q, &r->w_lin, &r->w_lout, &r->w_dout, &r->w_cand_l, &r->w_cand_d}) b->release();
+  for (DevBuf *b : {&r->d_planes, &r->w_q, &r->w_lin, &r->w_lout, &r->w_dout, &r->w_cand_l, &r->w_cand_d, &r->x_gl, &r->x_gd,
+                    &r->x_ms_d, &r->x_ms_id, &r->x_k1_l, &r->x_k1_d, &r->x_list})
+    b->release();
   for (hipEvent_t e : r->t) (void)hipEventDestroy(e);
-  for (hipEvent_t e : {r->user_ready, r->finished})
+  for (hipEvent_t e : r->xt)
+    if (e) (void)hipEventDestroy(e);
+  for (hipEvent_t e : {r->user_ready, r->finished, r->flagged})
     if (e) (void)hipEventDestroy(e);
   delete r;
 }
@@ -427,10 +787,15 @@ int vaqhip_multi_refiner_add_rows(vaqhip_multi_refiner *r, const float *X, int64
 
 int vaqhip_multi_refiner_set_option(vaqhip_multi_refiner *r, const char *key, int64_t value) {
   if (!r || !key) return mfail(VAQHIP_EINVAL, "null pointer");
+  const bool exact = std::strcmp(key, "exact_ties") == 0, timing = std::strcmp(key, "timing") == 0,
+             splits = std::strcmp(key, "exhaustive_splits") == 0;
+  if (!exact && !timing && !splits) return mfail(VAQHIP_EINVAL, "unknown option '%s'", key);
+  if (splits && (value < 0 || value > 64))  // (refused before the refiner is touched)
+    return mfail(VAQHIP_EINVAL, "exhaustive_splits=%lld: 0 (automatic) or 1..64", (long long)value);
   std::lock_guard<std::mutex> lk(r->mu);
-  if (std::strcmp(key, "exact_ties") == 0) r->opt_exact = value != 0;
-  else if (std::strcmp(key, "timing") == 0) r->opt_timing = value != 0;
-  else return mfail(VAQHIP_EINVAL, "unknown option '%s'", key);
+  if (exact) r->opt_exact = value != 0;
+  else if (timing) r->opt_timing = value != 0;
+  else r->opt_splits = (int)value;
   return VAQHIP_OK;
 }
 
@@ -480,6 +845,34 @@ int vaqhip_multi_search_refine(vaqhip_multi *mx, vaqhip_multi_refiner *r, const 
   return through_staging(r, queries_raw, nq, nullptr, R, k, labels_out, distances_out, [&](int n, hipStream_t st) {
     return search_refine_locked(mx, r, r->w_q.as<float>(), n, R, k, r->w_lout.as<int32_t>(), r->w_dout.as<float>(), st);
   });
+}
+
+int vaqhip_multi_refiner_search_device(vaqhip_multi_refiner *r, const float *d_queries, int nq, int k, int32_t *d_labels_out,
+                                       float *d_distances_out, void *stream) {
+  if (const int rc = check_search(r, nq, k, d_queries, d_labels_out, d_distances_out)) return rc;
+  if (nq == 0) return VAQHIP_OK;
+  std::lock_guard<std::mutex> lk(r->mu);
+  DeviceGuard keep(DeviceGuard::restore_only);
+  return search_device_locked(r, d_queries, nq, k, d_labels_out, d_distances_out, static_cast<hipStream_t>(stream));
+}
+
+int vaqhip_multi_refiner_search(vaqhip_multi_refiner *r, const float *queries, int nq, int k, int32_t *labels_out,
+                                float *distances_out) {
+  if (const int rc = check_search(r, nq, k, queries, labels_out, distances_out)) return rc;
+  if (nq == 0) return VAQHIP_OK;
+  std::lock_guard<std::mutex> lk(r->mu);
+  DeviceGuard keep(DeviceGuard::restore_only);
+  // (under "timing" the figures are the last staged set's: the bench and the tests stay within one)
+  return through_staging(r, queries, nq, nullptr, 0, k, labels_out, distances_out, [&](int n, hipStream_t st) {
+    return search_device_locked(r, r->w_q.as<float>(), n, k, r->w_lout.as<int32_t>(), r->w_dout.as<float>(), st);
+  });
+}
+
+int vaqhip_multi_refiner_last_search_timing(vaqhip_multi_refiner *r, vaqhip_multi_refiner_search_timing *out) {
+  if (!r || !out) return mfail(VAQHIP_EINVAL, "null pointer");
+  std::lock_guard<std::mutex> lk(r->mu);
+  *out = r->x_timing;
+  return VAQHIP_OK;
 }
 
 int vaqhip_multi_refiner_get_info(vaqhip_multi_refiner *r, vaqhip_multi_refiner_info *out) {

@@ -2,8 +2,11 @@
 // kept on the device, the reference-exact re-rank over them (vaq_refine.hip), and the search fused with it.  It sees
 // the index through the public ABI only (vaqhip_index_info, vaqhip_search_device): the candidates of a fused call go
 // from the search's output buffer straight into the refine kernel and never to the host.  The exhaustive form
-// (vaqhip_refiner_search: every resident row a candidate) plans the launches of vaq_exhaust.hip here.
+// (vaqhip_refiner_search: every resident row a candidate) runs the launches of vaq_exhaust.hip as
+// vaqhip_exhaust_plan.h plans them -- the plan and the set of launches it shares with the multi-device refiner.
 #include "vaqhip_index.h"
+
+#include "vaqhip_exhaust_plan.h"
 
 #include <string>
 
@@ -16,13 +19,10 @@ struct vaqhip_refiner {
   int opt_exact = 0;
   int opt_splits = 0;  // "exhaustive_splits": 0 = automatic
   int opt_timing = 0;  // "timing": events around the phases of the exhaustive form
-  int n_cu = 0, blocks_per_cu = 0;
   DevBuf d_rows;
   // workspaces of the host forms and of the fused call (grow-only)
   DevBuf w_q, w_lin, w_lout, w_dout, w_cand_l, w_cand_d;
-  // the exhaustive form's: candidate lists, the splits' lists, the merge's scratch, the k + 1 lists and the replay list
-  DevBuf x_buf_d, x_buf_id, x_part_d, x_part_id, x_ms_d, x_ms_id, x_k1_l, x_k1_d, x_list;
-  hipEvent_t x_ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  XsWork xs;  // the exhaustive form's
   vaqhip_refiner_search_timing x_timing = {};
   hipStream_t stream = nullptr;
   // the candidate buffers of the fused _device call are shared by its callers' streams: as on the index, the last
@@ -115,89 +115,6 @@ int search_refine_locked(vaqhip_index *ix, vaqhip_refiner *r, const float *d_q, 
 }
 
 // ---- the exhaustive form ----
-constexpr size_t XS_LIST_BYTES = (size_t)256 << 20;  // candidate lists of one launch (the queries are cut to fit)
-
-struct XsPlan {
-  int S, qg, chunk;  // splits, queries per workgroup, queries per launch
-};
-
-XsPlan plan_search(const vaqhip_refiner *r, int nq, int k1) {
-  // ONE round of resident workgroups: with equal shares they end together, and no partly filled second round runs
-  const int target = std::max(r->n_cu, 1) * std::max(r->blocks_per_cu, 1);
-  const int64_t tiles = std::max<int64_t>(1, (r->N + vaq::XS_TILE - 1) / vaq::XS_TILE);
-  XsPlan pl;
-  if (r->opt_splits > 0) {
-    pl.S = r->opt_splits;
-  } else {  // few queries: many splits fill the device; many queries: few splits, the lists stay small
-    const int g0 = (nq + 63) / 64;
-    pl.S = (int)std::min<int64_t>(std::min<int64_t>(64, tiles), std::max(1, (target + g0 - 1) / g0));
-  }
-  const size_t per_query = (size_t)pl.S * vaq::exhaust_list_cap(k1) * (sizeof(float) + sizeof(int));
-  const int fit = (int)std::min<size_t>((size_t)nq, std::max<size_t>(1, XS_LIST_BYTES / per_query));
-  const int sets = (nq + fit - 1) / fit;
-  pl.chunk = (nq + sets - 1) / sets;  // equal sets: the last one fills the device like the others
-  const int g_want = std::max(1, target / pl.S);  // S * groups <= target
-  pl.qg = std::min(vaq::XS_MAX_QG, std::max((pl.chunk + g_want - 1) / g_want, std::min(pl.chunk, 8)));
-  return pl;
-}
-
-// one set of queries: select per split, merge, and with "exact_ties" flag + replay; caller holds r->mu
-int search_set(vaqhip_refiner *r, const XsPlan &pl, const float *d_q, int n, int k, int32_t *d_lout, float *d_dout,
-               hipStream_t st) {
-  const bool exact = r->opt_exact != 0, timing = r->opt_timing != 0;
-  const int k1 = exact ? k + 1 : k;
-  vaq::XsParams p;
-  p.nq = n;
-  p.D = r->D;
-  p.N = r->N;
-  p.id_base = r->id_base;
-  p.k = k1;
-  p.cap = vaq::exhaust_list_cap(k1);
-  p.S = pl.S;
-  p.qg = std::min(pl.qg, n);
-  p.G = (n + p.qg - 1) / p.qg;
-  p.split_rows = (r->N + pl.S - 1) / pl.S;
-  p.buf_d = r->x_buf_d.as<float>();
-  p.buf_id = r->x_buf_id.as<int>();
-  p.part_d = r->x_part_d.as<float>();
-  p.part_id = r->x_part_id.as<int>();
-  int32_t *m_l = exact ? r->x_k1_l.as<int32_t>() : d_lout;
-  float *m_d = exact ? r->x_k1_d.as<float>() : d_dout;
-  int *list = r->x_list.as<int>();
-  unsigned *count = reinterpret_cast<unsigned *>(list + n);
-  if (timing) HIP_TRY(hipEventRecord(r->x_ev[0], st));
-  HIP_TRY(vaq::launch_exhaust_select(p, d_q, r->d_rows.as<float>(), st));
-  if (timing) HIP_TRY(hipEventRecord(r->x_ev[1], st));
-  HIP_TRY(vaq::launch_merge(p.part_d, p.part_id, nullptr, p.S, (int64_t)n * k1, (int64_t)k1, n, k1, 0, 1, m_l, m_d, nullptr,
-                            r->x_ms_d.as<float>(), r->x_ms_id.as<int>(), st));
-  if (timing) HIP_TRY(hipEventRecord(r->x_ev[2], st));
-  if (exact) {
-    HIP_TRY(vaq::launch_exact_flag(n, k, m_l, m_d, d_lout, d_dout, list, count, st));
-    if (timing) HIP_TRY(hipEventRecord(r->x_ev[3], st));
-    HIP_TRY(vaq::launch_exhaust_replay(d_q, n, r->D, r->d_rows.as<float>(), r->N, r->id_base, k, list, count, d_lout,
-                                       d_dout, st));
-  } else if (timing) {
-    HIP_TRY(hipEventRecord(r->x_ev[3], st));
-  }
-  if (timing) {  // (the option is a measurement: it synchronises after every set)
-    HIP_TRY(hipEventRecord(r->x_ev[4], st));
-    HIP_TRY(hipEventSynchronize(r->x_ev[4]));
-    float ms[4] = {0, 0, 0, 0};
-    for (int i = 0; i < 4; i++) HIP_TRY(hipEventElapsedTime(&ms[i], r->x_ev[i], r->x_ev[i + 1]));
-    unsigned listed = 0;
-    if (exact) HIP_TRY(hipMemcpy(&listed, count, sizeof(unsigned), hipMemcpyDeviceToHost));
-    vaqhip_refiner_search_timing &t = r->x_timing;
-    t.select_ms += ms[0];
-    t.merge_ms += ms[1];
-    t.flag_ms += ms[2];
-    t.replay_ms += ms[3];
-    t.listed_queries += (int)listed;
-    t.workgroups = p.S * p.G;
-    t.queries_per_group = p.qg;
-  }
-  return VAQHIP_OK;
-}
-
 int check_search(const vaqhip_refiner *r, int nq, int k, const void *a, const void *b, const void *c) {
   if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
   if (nq < 0 || k < 1) return fail(VAQHIP_EINVAL, "bad sizes (nq=%d k=%d)", nq, k);
@@ -209,39 +126,24 @@ int check_search(const vaqhip_refiner *r, int nq, int k, const void *a, const vo
 // all sets of one call, enqueued on st; caller holds r->mu, device current
 int search_locked(vaqhip_refiner *r, const float *d_q, int nq, int k, int32_t *d_lout, float *d_dout, hipStream_t st) {
   if (r->cap_rows == 0 && r->N == 0) return fail(VAQHIP_ESTATE, "no rows were set");
-  if (!r->n_cu) {
-    HIP_TRY(hipDeviceGetAttribute(&r->n_cu, hipDeviceAttributeMultiprocessorCount, r->device));
-    if (r->n_cu < 1) r->n_cu = 1;
-    r->blocks_per_cu = vaq::exhaust_blocks_per_cu(r->D);
-  }
+  HIP_TRY(r->xs.size_for(r->device, r->D));
   const bool exact = r->opt_exact != 0;
   const int k1 = exact ? k + 1 : k;
-  const XsPlan pl = plan_search(r, nq, k1);
-  const size_t cap = (size_t)vaq::exhaust_list_cap(k1), c = (size_t)pl.chunk;
-  HIP_TRY(r->x_buf_d.ensure(c * pl.S * cap * sizeof(float)));
-  HIP_TRY(r->x_buf_id.ensure(c * pl.S * cap * sizeof(int)));
-  HIP_TRY(r->x_part_d.ensure(c * pl.S * k1 * sizeof(float)));
-  HIP_TRY(r->x_part_id.ensure(c * pl.S * k1 * sizeof(int)));
-  const size_t ms = vaq::merge_scratch_elems(pl.S, pl.chunk, k1);
-  HIP_TRY(r->x_ms_d.ensure(ms * sizeof(float)));
-  HIP_TRY(r->x_ms_id.ensure(ms * sizeof(int)));
-  if (exact) {
-    HIP_TRY(r->x_k1_l.ensure(c * k1 * sizeof(int32_t)));
-    HIP_TRY(r->x_k1_d.ensure(c * k1 * sizeof(float)));
-    HIP_TRY(r->x_list.ensure((c + 1) * sizeof(int)));
-  }
-  if (r->opt_timing)
-    for (hipEvent_t &e : r->x_ev)
-      if (!e) HIP_TRY(hipEventCreate(&e));
+  const XsPlan pl = xs_plan(r->xs, r->N, r->opt_splits, nq, k1);
+  HIP_TRY(r->xs.fit(pl, k1, exact, r->opt_timing != 0));
   if (!r->ws_event) HIP_TRY(hipEventCreateWithFlags(&r->ws_event, hipEventDisableTiming));
   if (r->ws_used && st != r->ws_stream) HIP_TRY(hipStreamWaitEvent(st, r->ws_event, 0));
   r->x_timing = {};
   r->x_timing.splits = pl.S;
   r->x_timing.register_form = r->D <= (int)vaq::exhaust_register_max_dim();
-  int rc = VAQHIP_OK;
-  for (int q0 = 0; q0 < nq && !rc; q0 += pl.chunk)
-    rc = search_set(r, pl, d_q + (size_t)q0 * r->D, std::min(pl.chunk, nq - q0), k, d_lout + (size_t)q0 * k,
-                    d_dout + (size_t)q0 * k, st);
+  const XsRows rows = {r->d_rows.as<float>(), r->N, r->id_base, r->D};
+  hipError_t e = hipSuccess;
+  for (int q0 = 0; q0 < nq && e == hipSuccess; q0 += pl.chunk)
+    e = xs_search_set(r->xs, pl, rows, d_q + (size_t)q0 * r->D, std::min(pl.chunk, nq - q0), k, exact,
+                      d_lout + (size_t)q0 * k, d_dout + (size_t)q0 * k, st, r->opt_timing ? &r->x_timing : nullptr);
+  const int rc = e == hipSuccess ? VAQHIP_OK
+                                 : fail(e == hipErrorOutOfMemory ? VAQHIP_ENOMEM : VAQHIP_EHIP, "exhaustive search: %s",
+                                        hipGetErrorString(e));
   if (hipEventRecord(r->ws_event, st) == hipSuccess) {  // (also after a failure: work may be enqueued already)
     r->ws_stream = st;
     r->ws_used = true;
@@ -284,8 +186,7 @@ void vaqhip_refiner_destroy(vaqhip_refiner *r) {
   (void)hipDeviceSynchronize();  // (refines enqueued on the callers' streams read the rows)
   if (r->stream) (void)hipStreamDestroy(r->stream);
   if (r->ws_event) (void)hipEventDestroy(r->ws_event);
-  for (hipEvent_t e : r->x_ev)
-    if (e) (void)hipEventDestroy(e);
+  r->xs.release();
   delete r;  // every DevBuf goes here, with the refiner's device current
 }
 

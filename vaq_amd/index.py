@@ -744,6 +744,7 @@ class VaqMultiRefiner:
         r.set_rows(XTrain)                          # cut like the multi index's code rows, one upload per shard
         ans = r.refine(XTest, candidates, k)
         ans = multi.search_refine(XTest, R, k, r)   # fused with VaqHipMulti.search
+        truth = r.search(XTest, k)                  # exhaustive: the true k nearest rows over all shards
     """
 
     def __init__(self, devices: Sequence[int], D: int):
@@ -773,7 +774,10 @@ class VaqMultiRefiner:
         _lib.check_multi(_lib.load().vaqhip_multi_refiner_add_rows(self._h, _ptr(X), X.shape[0]))
 
     def set_option(self, key: str, value: int) -> None:
+        """"exact_ties", "timing", "exhaustive_splits" (per shard: 0 = automatic, 1..64)."""
         _lib.check_multi(_lib.load().vaqhip_multi_refiner_set_option(self._h, key.encode(), int(value)))
+        if key == "exact_ties":
+            self._exact = bool(value)
 
     @property
     def exact_ties(self) -> bool:
@@ -818,6 +822,42 @@ class VaqMultiRefiner:
             self._h, C.c_void_p(q.data_ptr()), nq, C.c_void_p(lin.data_ptr()), R, int(k),
             C.c_void_p(labels.data_ptr()), C.c_void_p(dists.data_ptr()), C.c_void_p(st)))
         return labels, dists
+
+    def search(self, XTest, k: int) -> LabelDistVec:
+        """VaqRefiner.search over the rows of all shards: the same labels and distances slot for slot, with exact_ties
+        on or off -- every shard selects over its own rows, the first device merges, and with exact_ties the queries
+        that hold equal distances are replayed through the reference's heap shard after shard in row order."""
+        Xq = self._rows(XTest)
+        nq = Xq.shape[0]
+        ret = LabelDistVec(np.empty(nq * k, np.int32), np.empty(nq * k, np.float32))
+        _lib.check_multi(_lib.load().vaqhip_multi_refiner_search(self._h, _ptr(Xq), nq, int(k), _ptr(ret.labels),
+                                                                 _ptr(ret.distances)))
+        return ret
+
+    def search_device(self, d_queries, k: int, out=None):
+        """search() on torch CUDA tensors on the FIRST device of the list (queries nq x D float32), enqueued behind
+        torch's current stream of that device; nothing is synchronised."""
+        import torch
+        q = d_queries.contiguous()
+        assert q.is_cuda and q.dtype == torch.float32 and q.dim() == 2 and q.shape[1] == self.D
+        nq = q.shape[0]
+        if out is not None:
+            labels, dists = out
+        else:
+            labels = torch.empty((nq, k), dtype=torch.int32, device=q.device)
+            dists = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        st = torch.cuda.current_stream(q.device).cuda_stream
+        _lib.check_multi(_lib.load().vaqhip_multi_refiner_search_device(
+            self._h, C.c_void_p(q.data_ptr()), nq, int(k), C.c_void_p(labels.data_ptr()), C.c_void_p(dists.data_ptr()),
+            C.c_void_p(st)))
+        return labels, dists
+
+    def last_search_timing(self) -> dict:
+        """Figures of the last search (times only under set_option("timing", 1)): the slowest shard's select, merge and
+        link, the gather, the cross-shard merge, the flag step and the chain on the first device."""
+        t = _lib.MultiRefinerSearchTiming()
+        _lib.check_multi(_lib.load().vaqhip_multi_refiner_last_search_timing(self._h, C.byref(t)))
+        return {n: getattr(t, n) for n, _ in t._fields_}
 
     def info(self) -> dict:
         """Shard rows, and the phase times of the last refine made under set_option("timing", 1) (waits for it)."""
