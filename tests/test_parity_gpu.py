@@ -481,6 +481,9 @@ def test_encode_matches_oracle(vaqlib, oracle, D, bits):
 
 
 def test_refine_matches_oracle(vaqlib, oracle):
+    """vaqhip_refine against the oracle on integer-valued rows.  On integers every summation order gives
+    the same bits, so this does not test the sequential-sum contract of include/vaqhip.h: continuous data,
+    the edges of R and k and the device form are in tests/test_primitives_edges_gpu.py."""
     import vaq_amd
     rng = np.random.default_rng(9)
     N, D, nq, R, k = 5000, 128, 12, 200, 100
