@@ -192,6 +192,47 @@ def test_search_device(vaqlib):
     r.close()
 
 
+def test_more_than_one_set(vaqlib):
+    """nq = 16384 + 40 on 3 shards: the _device call is cut into equal sets (pointer offsets per set, the buffers of a
+    set reused by the next), the host form into two staged calls.  The integer rows tiled: every query ties across the
+    cuts (test_exhaustive_multi_cpu.py), so under exact_ties every query of every set is listed and replayed.  The
+    expected answer is computed on the 6 distinct queries and tiled.
+
+    The answers are checked WITHOUT option "timing" first: the sets of a _device call are then only enqueued, with no
+    host synchronise between them, so the next set's reuse of the gathered lists, the merged lists, the replay list and
+    the heap arrays rests on the stream waits alone; sets and chain_shards are reported without the option too.
+
+    Under "timing" listed_queries is summed over the sets of one call like the times: after search_device it is the
+    call's nq; after the host form, whose staged calls each start the figures anew, it is the last staged call's share
+    of the queries, worked out from the set size info() reports."""
+    import torch
+    Xq, Xt = int_data()
+    r = multi(3, 32, Xt)
+    SET = r.info()["set_queries"]
+    nq = SET + 40
+    last = nq - (nq - 1) // SET * SET
+    pick = np.arange(nq) % len(Xq)
+    Xq_t = np.ascontiguousarray(Xq[pick])
+    dq = torch.from_numpy(Xq_t).cuda()
+    for timing in (0, 1):
+        r.set_option("timing", timing)
+        for exact in (False, True):
+            for k in (1, 10):
+                ref = want(Xq, Xt, k, exact)
+                ref = (ref[0][pick], ref[1][pick])
+                check(search(r, Xq_t, k, exact), ref, (timing, k, exact, "host form"))
+                t = r.last_search_timing()
+                assert t["chain_shards"] == 3 and t["sets"] == 1, t
+                assert t["listed_queries"] == (last if exact and timing else 0), t
+                l, d = r.search_device(dq, k)
+                torch.cuda.synchronize()
+                check((l.cpu().numpy(), d.cpu().numpy()), ref, (timing, k, exact, "device form"))
+                t = r.last_search_timing()
+                assert t["sets"] >= 2 and t["chain_shards"] == 3, t
+                assert t["listed_queries"] == (nq if exact and timing else 0), t
+    r.close()
+
+
 def test_one_shard_is_the_single_form(vaqlib):
     import vaq_amd
     Xq, Xt = int_data()

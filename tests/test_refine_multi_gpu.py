@@ -253,6 +253,53 @@ def test_equals_the_single_refiner(vaqlib, G):
     one.close()
 
 
+def test_more_than_one_set(vaqlib):
+    """nq = 2 * 16384 + 5 on 3 shards: a _device call of three sets (the third of 5 queries), the host form in three
+    staged calls; int_ties tiled, so every query still ties across the cuts (test_inputs_have_cross_shard_ties).  The
+    expected answer is computed on the 6 distinct queries and tiled.  Under "timing" the three sets are reported, the
+    answer is the same, and a small call afterwards reports one set again."""
+    import torch
+    import vaq_amd
+    Xq, Xt, cand, _ = case("int_ties")
+    r = multi_refiner([0, 0, 0], Xt)
+    SET = r.info()["set_queries"]
+    assert SET == 16384
+    nq = 2 * SET + 5
+    pick = np.arange(nq) % len(Xq)
+    Xq_t, cand_t = np.ascontiguousarray(Xq[pick]), np.ascontiguousarray(cand[pick])
+    dq, dc = torch.from_numpy(Xq_t).cuda(), torch.from_numpy(cand_t).cuda()
+    one = vaq_amd.VaqRefiner(Xt.shape[1])
+    one.set_rows(Xt)
+
+    def device_form(k):
+        dl, dd = r.refine_device(dq, dc, k)
+        torch.cuda.synchronize()
+        return dl.cpu().numpy(), dd.cpu().numpy()
+
+    for exact in (True, False):
+        for k in (1, 10):
+            want_l, want_d = rr.refine(Xq, Xt, cand, k, exact=exact)
+            want_l, want_d = want_l[pick], want_d[pick]
+            lab, dis = run(r, Xq_t, cand_t, k, exact)
+            assert np.array_equal(lab, want_l) and bits_equal(dis, want_d), (exact, k, "host form")
+            lab, dis = device_form(k)
+            assert np.array_equal(lab, want_l) and bits_equal(dis, want_d), (exact, k, "device form")
+            lab, dis = run(one, Xq_t, cand_t, k, exact)
+            assert np.array_equal(lab, want_l) and bits_equal(dis, want_d), (exact, k, "single refiner")
+    assert r.info()["last_sets"] == 0
+    r.set_option("timing", 1)
+    lab, dis = device_form(10)  # (exact_ties is off since the loop's last round)
+    inf = r.info()
+    assert inf["last_sets"] == 3 and inf["last_distances_ms"] > 0 and inf["last_select_ms"] > 0, inf
+    assert np.array_equal(lab, want_l) and bits_equal(dis, want_d)
+    dl, dd = r.refine_device(dq[:3], dc[:3], 10)
+    torch.cuda.synchronize()
+    assert r.info()["last_sets"] == 1
+    assert np.array_equal(dl.cpu().numpy(), want_l[:3]) and bits_equal(dd.cpu().numpy(), want_d[:3])
+    r.close()
+    one.close()
+
+
 def golden_multi(name, exact, devices):
     from vaq_amd.index import VaqHipMulti
     z = np.load(os.path.join(GOLD, name + ".npz"))

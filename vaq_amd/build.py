@@ -14,8 +14,9 @@ CSRC = os.path.join(ROOT, "vaq_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "vaq_amd", "lib")
 LIB = os.path.join(LIBDIR, "libvaqhip.so")
 SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_fast.hip", "vaq_lutfit.hip", "vaq_refine.hip", "vaq_exhaust.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp", "vaqhip_lutfit.cpp", "vaqhip_refiner.cpp",
-           "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp", "vaqhip_rccl.cpp"]
-MULTI_SOURCES = ("vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp")
+           "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp", "vaqhip_rccl.cpp"]
+MULTI_REFINER_SOURCES = ("vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp")
+MULTI_SOURCES = ("vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp") + MULTI_REFINER_SOURCES
 KERNEL_HEADER = os.path.join(CSRC, "vaq_kernels.h")
 OWNER_HEADER = os.path.join(CSRC, "refine_owner.h")  # the refiner's cut and label -> shard: vaq_kernels.h brings it
 API_HEADER = os.path.join(ROOT, "include", "vaqhip.h")
@@ -27,6 +28,8 @@ FAST_HEADER = os.path.join(CSRC, "vaq_fast.h")
 REFINE_GROUP_HEADER = os.path.join(CSRC, "vaq_refine_group.h")  # Eigen's squaredNorm over 16 lanes: refine, exhaustive form
 EXHAUST_HEADER = os.path.join(CSRC, "vaq_exhaust.h")  # the same by one thread, host and device: exhaustive form
 EXHAUST_PLAN_HEADER = os.path.join(CSRC, "vaqhip_exhaust_plan.h")  # the exhaustive form's plan and launches: both refiners
+REFINE_COMMON_HEADER = os.path.join(CSRC, "vaqhip_refine_common.h")  # checks, options, the row store: both refiners
+MULTI_REFINER_HEADER = os.path.join(CSRC, "vaqhip_multi_refiner.h")  # private to the multi refiner's two host files
 RESTATED_HEADER = os.path.join(CSRC, "vaq_restated.h")  # stdsort, stdheap, refheap, sq_norm_eigen: FAST, TI planning, the replay, k-means, refine
 INTERNAL_HEADER = os.path.join(CSRC, "vaqhip_internal.h")
 INDEX_HEADER = os.path.join(CSRC, "vaqhip_index.h")  # private to the single-index host files
@@ -64,8 +67,10 @@ def _deps(src: str):
         deps.append(REFINE_GROUP_HEADER)
     if src == "vaq_exhaust.hip":
         deps.append(EXHAUST_HEADER)
-    if src in ("vaqhip_refiner.cpp", "vaqhip_multi_refiner.cpp"):
-        deps.append(EXHAUST_PLAN_HEADER)
+    if src == "vaqhip_refiner.cpp" or src in MULTI_REFINER_SOURCES:
+        deps += [EXHAUST_PLAN_HEADER, REFINE_COMMON_HEADER]
+    if src in MULTI_REFINER_SOURCES:
+        deps.append(MULTI_REFINER_HEADER)
     return deps
 OBJDIR = os.path.join(LIBDIR, "obj")
 # Experiment builds: VAQ_VARIANT=name compiles (with VAQ_EXTRA_FLAGS) into vaq_amd/lib/variants/name/

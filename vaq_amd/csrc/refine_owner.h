@@ -1,5 +1,6 @@
 // refine_owner.h -- the cut of the multi-device refiner's rows and the way from a label to the shard that holds
-// its row.  Compiled by the host (vaqhip_multi_refiner.cpp), by the select kernel (vaq_refine.hip) and, with a plain
+// its row.  Compiled by the host (vaqhip_multi_refiner.cpp: the cut and the refine form's select; through
+// vaqhip_multi_refiner.h also vaqhip_multi_refiner_search.cpp), by the select kernel (vaq_refine.hip) and, with a plain
 // C++ compiler, by tests/cpp/refine_owner_test.cpp: one function, so that the host and the device cannot disagree
 // about who owns a label.  Nothing of HIP in here.
 #ifndef VAQ_REFINE_OWNER_H_

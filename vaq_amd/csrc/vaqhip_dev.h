@@ -1,11 +1,13 @@
-// vaqhip_dev.h -- what every host of the library owns device state with: a grow-only device buffer and
-// the guard of the current device.  Shared by the single-index host files (through vaqhip_index.h), the
-// multi-device host files (through vaqhip_multi.h) and the two kernel files that allocate scratch (vaq_kernels.hip,
-// vaq_ti.hip).  It holds nothing of vaqhip_index.
+// vaqhip_dev.h -- what every host of the library owns device state with: a grow-only device buffer, the
+// events of an option "timing" and the guard of the current device.  Shared by the single-index host files
+// (through vaqhip_index.h), the multi-device host files (through vaqhip_multi.h) and the two kernel files that
+// allocate scratch (vaq_kernels.hip, vaq_ti.hip).  It holds nothing of vaqhip_index.
 #ifndef VAQHIP_DEV_H
 #define VAQHIP_DEV_H
 #include <hip/hip_runtime.h>
 #include <cstddef>
+#include <initializer_list>
+#include <vector>
 
 // (hidden: none of this joins the library's exported symbols)
 namespace vaqhost __attribute__((visibility("hidden"))) {
@@ -39,6 +41,39 @@ struct DevBuf {
   }
   template <typename T> T *as() const { return static_cast<T *>(p); }
 };
+
+// Creates those of e[0..n) that are still null: the events of an option "timing", made when it is first used.
+inline hipError_t ensure_events(hipEvent_t *e, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (!e[i])
+      if (const hipError_t r = hipEventCreate(&e[i])) return r;
+  return hipSuccess;
+}
+
+inline void destroy_events(hipEvent_t *e, size_t n) {
+  for (size_t i = 0; i < n; i++) {
+    if (e[i]) (void)hipEventDestroy(e[i]);
+    e[i] = nullptr;
+  }
+}
+
+template <size_t N> hipError_t ensure_events(hipEvent_t (&e)[N]) { return ensure_events(e, N); }
+template <size_t N> void destroy_events(hipEvent_t (&e)[N]) { destroy_events(e, N); }
+
+// The events of an option "timing" where their number grows with the call: the first n exist after ensure(n).
+struct EventList {
+  std::vector<hipEvent_t> e;
+  hipError_t ensure(size_t n) {
+    while (e.size() < n) e.push_back(nullptr);
+    return ensure_events(e.data(), n);
+  }
+  hipEvent_t operator[](size_t i) const { return e[i]; }
+  void release() { destroy_events(e.data(), e.size()); }
+};
+
+inline void release_all(std::initializer_list<DevBuf *> bufs) {
+  for (DevBuf *b : bufs) b->release();
+}
 
 // Makes `dev` current and puts the caller's device back when the scope ends; the restore-only form
 // leaves the current device alone and only puts it back (`active` false: not even that).

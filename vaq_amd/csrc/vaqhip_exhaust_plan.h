@@ -1,7 +1,8 @@
 // vaqhip_exhaust_plan.h -- what the two hosts of the exhaustive form share (vaqhip_refiner.cpp: one device;
-// vaqhip_multi_refiner.cpp: the rows cut over shards): the split and group plan of a select launch, the workspace of
-// one device, and the launches of one set of queries over one device's rows.  A shard of the multi refiner runs
-// xs_select_merge over its own rows; the single refiner, and the multi refiner with one shard, run xs_search_set.
+// vaqhip_multi_refiner_search.cpp: the rows cut over shards): the split and group plan of a select launch, the
+// workspace of one device, and the launches of one set of queries over one device's rows.  A shard of the multi
+// refiner runs xs_select_merge over its own rows; the single refiner, and the multi refiner with one shard, run
+// xs_search_set.
 // Every function returns the first HIP error; the hosts put their own text around it.
 #ifndef VAQHIP_EXHAUST_PLAN_H
 #define VAQHIP_EXHAUST_PLAN_H
@@ -66,19 +67,11 @@ struct XsWork {
       XS_TRY(k1_d.ensure(c * k1 * sizeof(float)));
       XS_TRY(list.ensure((c + 1) * sizeof(int)));
     }
-    if (timing)
-      for (hipEvent_t &e : ev)
-        if (!e) XS_TRY(hipEventCreate(&e));
+    if (timing) XS_TRY(ensure_events(ev));
     return hipSuccess;
   }
   // with the workspace's device current and its streams idle
-  void release() {
-    for (DevBuf *b : {&buf_d, &buf_id, &part_d, &part_id, &ms_d, &ms_id, &k1_l, &k1_d, &list}) b->release();
-    for (hipEvent_t &e : ev) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-  }
+  void release() { release_all({&buf_d, &buf_id, &part_d, &part_id, &ms_d, &ms_id, &k1_l, &k1_d, &list}), destroy_events(ev); }
 };
 
 // N rows on the workspace's device against nq queries, lists of k1; opt_splits: "exhaustive_splits"; max_chunk: a

@@ -1,9 +1,9 @@
 // vaqhip_multi.h -- what the host files of the multi-device index share: the shard, the index with the
-// geometry of the search in flight, the error hand-over and the two loops over shards.  Private to
-// vaqhip_multi.cpp (life cycle, codes, setters), vaqhip_multi_search.cpp (the search),
-// vaqhip_multi_kmeans.cpp (the k-means of clusterTI) and vaqhip_multi_refiner.cpp (the refiner over sharded raw rows,
-// which takes the error hand-over and on_shards from here); they see a shard's index through include/vaqhip.h
-// and vaqhip_internal.h only.
+// geometry of the search in flight, the error hand-over, the grow path of a phase's buffers and the two loops over
+// shards.  Private to vaqhip_multi.cpp (life cycle, codes, setters), vaqhip_multi_search.cpp (the search),
+// vaqhip_multi_kmeans.cpp (the k-means of clusterTI) and, through vaqhip_multi_refiner.h, the refiner over sharded raw
+// rows (vaqhip_multi_refiner.cpp, vaqhip_multi_refiner_search.cpp), which takes the error hand-over, the grow path and
+// on_shards from here; they see a shard's index through include/vaqhip.h and vaqhip_internal.h only.
 #ifndef VAQHIP_MULTI_H
 #define VAQHIP_MULTI_H
 #include "vaqhip.h"
@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -126,6 +127,47 @@ inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? VAQHIP_ENO
       s.err = vaqhip_last_error();  \
       return rc_;                   \
     }                               \
+  } while (0)
+
+// The buffers a phase needs, fitted together.  Growing frees the old buffer, and hipFree waits for the work of the
+// buffer's own device only, while a stream of ANOTHER device may still read it.  So when any entry would grow (or
+// `also`: something else of the caller's will), fit() first waits for `read`, the event the owner records behind
+// every such reader, and then ensures all of them.  In steady state nothing grows and nothing waits.  It returns the
+// first HIP error; `failed` then names the buffer (null: the wait failed) and text() says both.
+struct FitList {
+  static constexpr int CAP = 16;  // (the longest list today: 11, phase A of the exhaustive form on the first device)
+  struct Entry { DevBuf *b; size_t bytes; const char *name; } e[CAP];
+  int n = 0;
+  const char *failed = nullptr;
+  void want(DevBuf &b, size_t bytes, const char *name) {
+    assert(n < CAP);
+    if (n < CAP) e[n++] = Entry{&b, bytes, name};
+  }
+  hipError_t fit(hipEvent_t read, bool also = false) {
+    bool grows = also;
+    for (int i = 0; i < n; i++) grows |= e[i].bytes > e[i].b->cap;
+    if (grows)
+      if (const hipError_t r = hipEventSynchronize(read)) return r;
+    for (int i = 0; i < n; i++) {
+      failed = e[i].name;
+      if (const hipError_t r = e[i].b->ensure(e[i].bytes)) return r;
+    }
+    failed = nullptr;
+    return hipSuccess;
+  }
+  std::string text(hipError_t r) const {
+    return std::string(failed ? failed : "the wait before a buffer grows") + (failed ? ".ensure: " : ": ") + hipGetErrorString(r);
+  }
+};
+
+// fits the list of shard `s`, as MHIP
+#define MFIT(list, ...)                             \
+  do {                                              \
+    const hipError_t e_ = (list).fit(__VA_ARGS__);  \
+    if (e_ != hipSuccess) {                         \
+      s.err = (list).text(e_);                      \
+      return vaqhost::hip_code(e_);                 \
+    }                                               \
   } while (0)
 
 // job(g, shard) on every shard's worker at once.  A job that fails and leaves the shard's text empty says that a

@@ -17,183 +17,67 @@
 //   3 gather     shard 0's stream waits for every shard's event and copies the planes of shards 1.. next to its own
 //   4 select     refine_select_kernel there, straight into the caller's buffers; the caller's stream waits for it
 // Every wait is a stream wait on an event.  With one shard the call is launch_refine_rows on the caller's stream.
-//
-// The exhaustive form (vaqhip_multi_refiner_search: every resident row a candidate, in row order) is the second half
-// of this file.  Its selection DOES depend on other shards' rows under "exact_ties", so it ends in a chain of replays:
-//   A select     every shard with rows: the single form's select + merge over its own rows (vaqhip_exhaust_plan.h), a
-//                [nq][k1] list per shard; on the shards' workers
-//   B gather     the lists next to shard 0's, one merge by (distance, label) there: the answer without "exact_ties"
-//   C flag       on the MERGED k + 1 lists: queries without equal distances are copied out, the others listed
-//   D chain      the listed queries through the reference's heap, shard after shard in row order; the raw heap
-//                arrays travel by peer copy, the last shard with rows reorders, shard 0 places the slots
-// B to D are enqueued by the calling thread in chain order, so an event is always recorded before its wait is enqueued.
-#include "vaqhip_multi.h"
+// The exhaustive form (every resident row a candidate) is vaqhip_multi_refiner_search.cpp.
+#include "vaqhip_multi_refiner.h"
 
 #include <cstring>
 
-#include "vaq_kernels.h"
-#include "vaqhip_exhaust_plan.h"
-
 using namespace vaqhost;
 
-namespace vaqhost __attribute__((visibility("hidden"))) {
-
-struct RShard {
-  int device = 0;
-  int64_t lo = 0, n = 0;  // rows [lo, lo + n) of the dataset
-  int64_t cap_rows = 0;   // rows the allocation holds (appends grow the last shard geometrically)
-  DevBuf d_rows;
-  hipStream_t stream = nullptr;
-  hipEvent_t done = nullptr;  // this shard's plane of the current set is complete
-  DevBuf d_q, d_lin;          // shards 1..: the set's queries and candidate labels
-  DevBuf d_plane;             // shards 1..: float [nq][R]; shard 0 writes into the gathered planes
-  std::vector<hipEvent_t> t;  // option "timing": 3 events per set (start, broadcast done, distances done)
-  // the exhaustive form: this device's workspace and its plan for the call in flight; shards 1..: the shard's
-  // [set][k1] lists (shard 0 writes into the gathered lists) and the replay list with its count; the chain's state,
-  // [set][k] raw heap arrays in and out (shard 0's x_hin receives the last link's finished slots)
-  XsWork xs;
-  XsPlan xpl = {1, 1, 1};
-  int x_wgs = 0, x_qg = 0;
-  DevBuf x_l, x_d, x_list;
-  DevBuf x_hin_v, x_hin_i, x_hout_v, x_hout_i;
-  hipEvent_t link = nullptr;  // this shard's link of the chain is complete
-  hipEvent_t xt[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // "timing": start, selected, merged; link start, end
-  std::string err;
-};
-
-}  // namespace vaqhost
-
-struct vaqhip_multi_refiner {
-  __attribute__((visibility("hidden"))) ~vaqhip_multi_refiner() = default;
-  int D = 0, G = 0;
-  std::vector<RShard> sh;
-  int64_t N = 0, id_base = 0;
-  vaq::RefineBounds bounds = {};
-  int opt_exact = 0, opt_timing = 0;
-  int opt_splits = 0;  // "exhaustive_splits": per shard, 0 = automatic
-  std::mutex mu;  // one call at a time
-  vaq::JobPool pool;
-  // on the first device
-  DevBuf d_planes;                        // float [G][set][R]
-  DevBuf w_q, w_lin, w_lout, w_dout;      // the host forms' staging
-  DevBuf w_cand_l, w_cand_d;              // the fused call's candidates
-  hipEvent_t user_ready = nullptr;        // recorded on the caller's stream: its inputs are there
-  hipEvent_t finished = nullptr;          // the last set's select is complete: every buffer of the set has been read
-  bool dirty = false;                     // a call failed part-way: `finished` does not cover what it enqueued
-  std::vector<hipEvent_t> t;              // option "timing": 3 events per set (gather start, gathered, selected)
-  int last_sets = 0;                      // sets of the last call that carry timing events
-  bool last_single = false;               //   it was the one-shard form (t[0], t[1] around the kernel)
-  // the exhaustive form, on the first device: the gathered [lists][set][k1] labels and distances, the cross-shard
-  // merge's scratch, the merged k + 1 lists and the replay list with its count
-  DevBuf x_gl, x_gd, x_ms_d, x_ms_id, x_k1_l, x_k1_d, x_list;
-  hipEvent_t flagged = nullptr;  // the replay list of the current set is complete
-  hipEvent_t xt[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // "timing": gather start, gathered, merged, flagged, placed
-  vaqhip_multi_refiner_search_timing x_timing = {};
-  int x_k = 0, x_k1 = 0, x_lists = 0;     // of the search in flight: k, entries per list, lists gathered
-  int x_slot[VAQHIP_MAX_DEVICES] = {};    //   where shard g's list sits among them
-  int x_last = 0;                         //   the last shard that holds rows (0 when none does)
-  bool x_chain = false;                   //   "exact_ties" and some shard holds rows: k1 = k + 1, flag step, chain
-  // the set in flight
-  const float *d_q0 = nullptr;
-  const int32_t *d_lin0 = nullptr;
-  int nq = 0, R = 0, set_no = 0;
-  size_t plane() const { return (size_t)nq * R; }
-};
-
-namespace {
-
-constexpr int REFINE_MAX_R = 2048;
-// Queries per set: the planes of one set take G * SET_QUERIES * R * 4 bytes on the first device (512 MB at
-// G = 8, R = 1024).  Results do not depend on it: a query's answer depends on its own candidates only.
-constexpr int SET_QUERIES = VAQHIP_MULTI_REFINER_SET;
-
-int check_sizes(const vaqhip_multi_refiner *r, int nq, int R, int k) {
-  if (!r) return mfail(VAQHIP_EINVAL, "multi refiner is null");
-  if (nq < 0 || R <= 0 || k <= 0) return mfail(VAQHIP_EINVAL, "bad sizes (nq=%d R=%d k=%d)", nq, R, k);
-  if (R > REFINE_MAX_R || k > R) return mfail(VAQHIP_EUNSUPPORTED, "need k <= R <= %d (R=%d k=%d)", REFINE_MAX_R, R, k);
-  return VAQHIP_OK;
-}
-
-int check_labels_fit(int64_t N, int64_t id_base) {
-  if (id_base < 0) return mfail(VAQHIP_EINVAL, "id_base < 0");
-  if (N > 0x7fffffffLL - 1 || id_base + N > 0x7fffffffLL)
-    return mfail(VAQHIP_ERANGE, "labels are 32-bit ints (utils/Types.hpp:100): id_base+N = %lld", (long long)(id_base + N));
-  return VAQHIP_OK;
-}
-
-// `n` timing events more where the vector is short
-int fit_events(std::vector<hipEvent_t> &v, size_t n) {
-  while (v.size() < n) {
-    hipEvent_t e = nullptr;
-    if (hipEventCreate(&e) != hipSuccess) return VAQHIP_EHIP;
-    v.push_back(e);
-  }
-  return 0;
-}
-
-// room for `rows` rows on the shard whose device is current; keep: the first s.n rows survive the move
-int reserve_rows(vaqhip_multi_refiner *r, RShard &s, int64_t rows, bool keep) {
-  if (rows <= s.cap_rows) return 0;
-  const int64_t want = keep ? std::max(rows, s.cap_rows + s.cap_rows / 2) : rows;
-  DevBuf nb;
-  MHIP(nb.ensure((size_t)want * r->D * sizeof(float)));
-  MHIP(hipDeviceSynchronize());  // (a refine enqueued on any stream may still read the old rows)
-  if (keep && s.n > 0) MHIP(hipMemcpy(nb.p, s.d_rows.p, (size_t)s.n * r->D * sizeof(float), hipMemcpyDeviceToDevice));
-  std::swap(nb.p, s.d_rows.p);
-  std::swap(nb.cap, s.d_rows.cap);
-  s.cap_rows = want;
-  return 0;
-}
-
-// every stream idle: after a call that failed part-way, before anything it may still read is freed or reused
-void drain(vaqhip_multi_refiner *r) {
+void vaqhost::drain(vaqhip_multi_refiner *r) {
   for (RShard &s : r->sh)
     if (hipSetDevice(s.device) == hipSuccess) (void)hipStreamSynchronize(s.stream);
   (void)hipSetDevice(r->sh[0].device);
   r->dirty = false;
 }
 
-// Phases 1 and 2 of a set, on the shard's worker: buffers, the broadcast, the distances.
-int enqueue_shard(vaqhip_multi_refiner *r, int g, RShard &s) {
-  const int nq = r->nq, R = r->R, D = r->D;
-  const bool timing = r->opt_timing != 0;
-  MHIP(hipSetDevice(s.device));
-  if (timing && fit_events(s.t, 3 * (size_t)(r->set_no + 1))) {
+namespace {
+
+// the three timing events of the set in flight among `rf`'s (null without option "timing"); `s` takes the text
+int set_events(const vaqhip_multi_refiner *r, EventList &ev, RShard &s, hipEvent_t *&t) {
+  t = nullptr;
+  if (!r->opt.timing) return 0;
+  if (ev.ensure(3 * (size_t)(r->set.set_no + 1)) != hipSuccess) {
     s.err = "hipEventCreate failed";
     return VAQHIP_EHIP;
   }
-  hipEvent_t *t = timing ? &s.t[3 * (size_t)r->set_no] : nullptr;
-  // Growing frees the old buffer, which the last set's gather and select (on shard 0's stream) may still read:
-  // `finished` follows all of them.  In steady state nothing grows and nothing here waits.
-  struct Fit { DevBuf *b; size_t bytes; } fit[3];
-  int n = 0;
-  if (g == 0) fit[n++] = Fit{&r->d_planes, (size_t)r->G * r->plane() * sizeof(float)};
+  t = &ev.e[3 * (size_t)r->set.set_no];
+  return 0;
+}
+
+// Phases 1 and 2 of a set, on the shard's worker: buffers, the broadcast, the distances.
+int enqueue_shard(vaqhip_multi_refiner *r, int g, RShard &s) {
+  const RefineSet &c = r->set;
+  const int D = r->D;
+  MHIP(hipSetDevice(s.device));
+  hipEvent_t *t;
+  if (const int rc = set_events(r, s.rf.t, s, t)) return rc;
+  // the last set's gather and select (on shard 0's stream) may still read the old buffers: `finished` follows them
+  FitList fit;
+  if (g == 0) fit.want(r->rf.planes, r->G * c.plane_bytes(), "planes");
   else if (s.n > 0) {
-    fit[n++] = Fit{&s.d_q, (size_t)nq * D * sizeof(float)};
-    fit[n++] = Fit{&s.d_lin, r->plane() * sizeof(int32_t)};
-    fit[n++] = Fit{&s.d_plane, r->plane() * sizeof(float)};
+    fit.want(s.d_q, c.query_bytes(D), "d_q");
+    fit.want(s.rf.lin, c.plane_bytes(), "lin");
+    fit.want(s.rf.plane, c.plane_bytes(), "plane");
   }
-  bool grows = false;
-  for (int i = 0; i < n; i++) grows |= fit[i].bytes > fit[i].b->cap;
-  if (grows) MHIP(hipEventSynchronize(r->finished));
-  for (int i = 0; i < n; i++) MHIP(fit[i].b->ensure(fit[i].bytes));
+  MFIT(fit, r->finished);
   // the previous set has been read (never recorded: no wait); the caller's inputs are there
   MHIP(hipStreamWaitEvent(s.stream, r->finished, 0));
   MHIP(hipStreamWaitEvent(s.stream, r->user_ready, 0));
   if (t) MHIP(hipEventRecord(t[0], s.stream));
-  const float *dq = r->d_q0;
-  const int32_t *dl = r->d_lin0;
-  float *plane = r->d_planes.as<float>();  // shard 0: plane 0 of the gathered buffer
+  const float *dq = c.d_q0;
+  const int32_t *dl = c.d_lin0;
+  float *plane = r->rf.planes.as<float>();  // shard 0: plane 0 of the gathered buffer
   if (g > 0 && s.n > 0) {
     const int dev0 = r->sh[0].device;
-    MHIP(hipMemcpyPeerAsync(s.d_q.p, s.device, r->d_q0, dev0, (size_t)nq * D * sizeof(float), s.stream));
-    MHIP(hipMemcpyPeerAsync(s.d_lin.p, s.device, r->d_lin0, dev0, r->plane() * sizeof(int32_t), s.stream));
+    MHIP(hipMemcpyPeerAsync(s.d_q.p, s.device, c.d_q0, dev0, c.query_bytes(D), s.stream));
+    MHIP(hipMemcpyPeerAsync(s.rf.lin.p, s.device, c.d_lin0, dev0, c.plane_bytes(), s.stream));
     dq = s.d_q.as<float>();
-    dl = s.d_lin.as<int32_t>();
-    plane = s.d_plane.as<float>();
+    dl = s.rf.lin.as<int32_t>();
+    plane = s.rf.plane.as<float>();
   }
   if (t) MHIP(hipEventRecord(t[1], s.stream));
-  MHIP(vaq::launch_refine_dist(dq, nq, D, s.d_rows.as<float>(), s.n, r->id_base + s.lo, dl, R, plane, s.stream));
+  MHIP(vaq::launch_refine_dist(dq, c.nq, D, s.rows.rows(), s.n, r->id_base + s.lo, dl, c.R, plane, s.stream));
   if (t) MHIP(hipEventRecord(t[2], s.stream));
   MHIP(hipEventRecord(s.done, s.stream));
   return 0;
@@ -202,25 +86,20 @@ int enqueue_shard(vaqhip_multi_refiner *r, int g, RShard &s) {
 // Phases 3 and 4, by the calling thread on the first device, once every shard's part is enqueued
 int gather_and_select(vaqhip_multi_refiner *r, int k, int32_t *d_lout, float *d_dout, hipStream_t user) {
   RShard &s = r->sh[0];
-  const bool timing = r->opt_timing != 0;
+  const RefineSet &c = r->set;
   MHIP(hipSetDevice(s.device));
-  if (timing && fit_events(r->t, 3 * (size_t)(r->set_no + 1))) {
-    s.err = "hipEventCreate failed";
-    return VAQHIP_EHIP;
-  }
-  hipEvent_t *t = timing ? &r->t[3 * (size_t)r->set_no] : nullptr;
+  hipEvent_t *t;
+  if (const int rc = set_events(r, r->rf.t, s, t)) return rc;
   for (int g = 1; g < r->G; g++) MHIP(hipStreamWaitEvent(s.stream, r->sh[g].done, 0));
   if (t) MHIP(hipEventRecord(t[0], s.stream));
-  float *planes = r->d_planes.as<float>();
+  float *planes = r->rf.planes.as<float>();
   for (int g = 1; g < r->G; g++) {
     const RShard &u = r->sh[g];
     if (u.n > 0)  // (an empty shard owns no label: its plane is never read)
-      MHIP(hipMemcpyPeerAsync(planes + (size_t)g * r->plane(), s.device, u.d_plane.p, u.device, r->plane() * sizeof(float),
-                              s.stream));
+      MHIP(hipMemcpyPeerAsync(planes + (size_t)g * c.plane(), s.device, u.rf.plane.p, u.device, c.plane_bytes(), s.stream));
   }
   if (t) MHIP(hipEventRecord(t[1], s.stream));
-  MHIP(vaq::launch_refine_select(r->d_lin0, r->nq, planes, r->plane(), r->bounds, r->R, k, r->opt_exact, d_lout, d_dout,
-                                 s.stream));
+  MHIP(vaq::launch_refine_select(c.d_lin0, c.nq, planes, c.plane(), r->bounds, c.R, k, r->opt.exact, d_lout, d_dout, s.stream));
   if (t) MHIP(hipEventRecord(t[2], s.stream));
   MHIP(hipEventRecord(r->finished, s.stream));
   MHIP(hipStreamWaitEvent(user, r->finished, 0));
@@ -233,17 +112,16 @@ int refine_device_locked(vaqhip_multi_refiner *r, const float *d_q, int nq, cons
                          int32_t *d_lout, float *d_dout, hipStream_t user) {
   RShard &s0 = r->sh[0];
   if (hipSetDevice(s0.device) != hipSuccess) return mfail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", s0.device);
-  const bool timing = r->opt_timing != 0;
+  const bool timing = r->opt.timing != 0;
   r->last_sets = 0;
   r->last_single = r->G == 1;
   if (r->G == 1) {  // the single refiner's call, at its cost
     hipError_t e = hipSuccess;
-    if (timing && fit_events(r->t, 3)) return mfail(VAQHIP_EHIP, "hipEventCreate failed");
-    if (timing) e = hipEventRecord(r->t[0], user);
+    if (timing && r->rf.t.ensure(3) != hipSuccess) return mfail(VAQHIP_EHIP, "hipEventCreate failed");
+    if (timing) e = hipEventRecord(r->rf.t[0], user);
     if (e == hipSuccess)
-      e = vaq::launch_refine_rows(d_q, nq, r->D, s0.d_rows.as<float>(), r->N, r->id_base, d_lin, R, k, r->opt_exact, d_lout,
-                                  d_dout, user);
-    if (e == hipSuccess && timing) e = hipEventRecord(r->t[1], user);
+      e = vaq::launch_refine_rows(d_q, nq, r->D, s0.rows.rows(), r->N, r->id_base, d_lin, R, k, r->opt.exact, d_lout, d_dout, user);
+    if (e == hipSuccess && timing) e = hipEventRecord(r->rf.t[1], user);
     if (e != hipSuccess) return mfail(hip_code(e), "refine on device %d: %s", s0.device, hipGetErrorString(e));
     r->last_sets = timing ? 1 : 0;
     return VAQHIP_OK;
@@ -251,11 +129,7 @@ int refine_device_locked(vaqhip_multi_refiner *r, const float *d_q, int nq, cons
   if (r->dirty) drain(r);
   if (hipEventRecord(r->user_ready, user) != hipSuccess) return mfail(VAQHIP_EHIP, "recording the caller's stream");
   for (int q0 = 0, set_no = 0; q0 < nq; q0 += SET_QUERIES, set_no++) {
-    r->nq = std::min(SET_QUERIES, nq - q0);
-    r->R = R;
-    r->set_no = set_no;
-    r->d_q0 = d_q + (size_t)q0 * r->D;
-    r->d_lin0 = d_lin + (size_t)q0 * R;
+    r->set = RefineSet{d_q + (size_t)q0 * r->D, d_lin + (size_t)q0 * R, std::min(SET_QUERIES, nq - q0), R, set_no};
     int rc = on_shards(r, [&](int g, RShard &s) { return enqueue_shard(r, g, s); });
     if (!rc) {
       s0.err.clear();
@@ -269,40 +143,6 @@ int refine_device_locked(vaqhip_multi_refiner *r, const float *d_q, int nq, cons
     if (timing) r->last_sets = set_no + 1;
   }
   return VAQHIP_OK;
-}
-
-// the host form of a device call: sets of SET_QUERIES through the staging buffers on the first device
-template <class Call> int through_staging(vaqhip_multi_refiner *r, const float *queries, int nq, const int32_t *labels_in,
-                                          int R, int k, int32_t *labels_out, float *distances_out, Call &&call) {
-  RShard &s = r->sh[0];
-  if (hipSetDevice(s.device) != hipSuccess) return mfail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", s.device);
-  const int chunk = std::min(nq, SET_QUERIES);
-  if (r->dirty) drain(r);
-  s.err.clear();
-  auto body = [&]() -> int {
-    MHIP(hipEventSynchronize(r->finished));  // (the staging may grow: nothing reads it any more)
-    MHIP(r->w_q.ensure((size_t)chunk * r->D * sizeof(float)));
-    if (labels_in) MHIP(r->w_lin.ensure((size_t)chunk * R * sizeof(int32_t)));
-    MHIP(r->w_lout.ensure((size_t)chunk * k * sizeof(int32_t)));
-    MHIP(r->w_dout.ensure((size_t)chunk * k * sizeof(float)));
-    hipStream_t st = s.stream;
-    for (int q0 = 0; q0 < nq; q0 += chunk) {
-      const int n = std::min(chunk, nq - q0);
-      MHIP(hipSetDevice(s.device));
-      MHIP(hipMemcpyAsync(r->w_q.p, queries + (size_t)q0 * r->D, (size_t)n * r->D * sizeof(float), hipMemcpyHostToDevice, st));
-      if (labels_in)
-        MHIP(hipMemcpyAsync(r->w_lin.p, labels_in + (size_t)q0 * R, (size_t)n * R * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      if (const int rc = call(n, st)) return rc;
-      MHIP(hipSetDevice(s.device));
-      MHIP(hipMemcpyAsync(labels_out + (size_t)q0 * k, r->w_lout.p, (size_t)n * k * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-      MHIP(hipMemcpyAsync(distances_out + (size_t)q0 * k, r->w_dout.p, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost, st));
-      MHIP(hipStreamSynchronize(st));
-    }
-    return 0;
-  };
-  const int rc = body();
-  if (rc && !s.err.empty()) return mfail(rc, "device %d: %s", s.device, s.err.c_str());
-  return rc;
 }
 
 // the index and the refiner of a fused call must describe the same rows on the same devices
@@ -328,331 +168,15 @@ int search_refine_locked(vaqhip_multi *mx, vaqhip_multi_refiner *r, const float 
   if (hipSetDevice(s.device) != hipSuccess) return mfail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", s.device);
   if (r->dirty) drain(r);
   const size_t bytes = (size_t)nq * R * 4;
-  if (bytes > r->w_cand_l.cap) {  // (the last fused call's shards and select read the old buffers)
+  if (bytes > r->w.cand_l.cap) {  // (the last fused call's shards and select read the old buffers)
     hipError_t e = hipEventSynchronize(r->finished);
-    if (e == hipSuccess) e = r->w_cand_l.ensure(bytes);
-    if (e == hipSuccess) e = r->w_cand_d.ensure(bytes);
+    if (e == hipSuccess) e = r->w.cand_l.ensure(bytes);
+    if (e == hipSuccess) e = r->w.cand_d.ensure(bytes);
     if (e != hipSuccess) return mfail(hip_code(e), "candidate buffers on device %d: %s", s.device, hipGetErrorString(e));
   }
-  if (const int rc = vaqhip_multi_search_device(mx, d_q, nq, R, 0, r->w_cand_l.as<int32_t>(), r->w_cand_d.as<float>(), st))
+  if (const int rc = vaqhip_multi_search_device(mx, d_q, nq, R, 0, r->w.cand_l.as<int32_t>(), r->w.cand_d.as<float>(), st))
     return rc;
-  return refine_device_locked(r, d_q, nq, r->w_cand_l.as<int32_t>(), R, k, d_lout, d_dout, st);
-}
-
-
-// ---- the exhaustive form across shards ----
-// the gathered lists of one set, in bytes on the first device (the set is cut to fit; every shard's own candidate
-// lists are bounded by XS_LIST_BYTES as in the single form)
-constexpr size_t XS_GATHER_BYTES = (size_t)256 << 20;
-
-int check_search(const vaqhip_multi_refiner *r, int nq, int k, const void *a, const void *b, const void *c) {
-  if (!r) return mfail(VAQHIP_EINVAL, "multi refiner is null");
-  if (nq < 0 || k < 1) return mfail(VAQHIP_EINVAL, "bad sizes (nq=%d k=%d)", nq, k);
-  if (k > VAQHIP_MAX_K) return mfail(VAQHIP_EUNSUPPORTED, "k=%d > %d", k, VAQHIP_MAX_K);
-  if (nq > 0 && (!a || !b || !c)) return mfail(VAQHIP_EINVAL, "null pointer");
-  return VAQHIP_OK;
-}
-
-bool xs_takes_part(int g, const RShard &s) { return g == 0 || s.n > 0; }  // (shard 0 hosts the merge even without rows)
-
-// Phase A of a set, on the shard's worker: buffers, the queries, select + merge over the shard's own rows
-int xs_enqueue_shard(vaqhip_multi_refiner *r, int g, RShard &s) {
-  if (!xs_takes_part(g, s)) return 0;  // (owns no label: no list, no link)
-  const int n = r->nq, D = r->D, k = r->x_k, k1 = r->x_k1;
-  const bool exact = r->x_chain, timing = r->opt_timing != 0;
-  MHIP(hipSetDevice(s.device));
-  // Growing frees a buffer the last set's gather, merge and chain may still read: `finished` follows all of them.
-  const size_t lists = (size_t)n * k1 * 4, state = (size_t)n * k * 4, list = ((size_t)n + 1) * 4;
-  struct Fit { DevBuf *b; size_t bytes; } fit[16];
-  int nf = 0;
-  if (g == 0) {
-    const size_t ms = vaq::merge_scratch_elems(r->x_lists, n, k1) * 4;
-    for (DevBuf *b : {&r->x_gl, &r->x_gd}) fit[nf++] = Fit{b, (size_t)r->x_lists * lists};
-    for (DevBuf *b : {&r->x_ms_d, &r->x_ms_id}) fit[nf++] = Fit{b, ms};
-    if (exact) {
-      for (DevBuf *b : {&r->x_k1_l, &r->x_k1_d}) fit[nf++] = Fit{b, lists};
-      fit[nf++] = Fit{&r->x_list, list};
-    }
-  } else {
-    fit[nf++] = Fit{&s.d_q, (size_t)n * D * sizeof(float)};
-    for (DevBuf *b : {&s.x_l, &s.x_d}) fit[nf++] = Fit{b, lists};
-    if (exact) fit[nf++] = Fit{&s.x_list, list};
-  }
-  if (exact)
-    for (DevBuf *b : {&s.x_hin_v, &s.x_hin_i, &s.x_hout_v, &s.x_hout_i}) fit[nf++] = Fit{b, state};
-  bool grows = !s.xs.fits(s.xpl, k1, false);
-  for (int i = 0; i < nf; i++) grows |= fit[i].bytes > fit[i].b->cap;
-  if (grows) MHIP(hipEventSynchronize(r->finished));
-  for (int i = 0; i < nf; i++) MHIP(fit[i].b->ensure(fit[i].bytes));
-  MHIP(s.xs.fit(s.xpl, k1, false, false));
-  if (timing)
-    for (hipEvent_t &e : s.xt)
-      if (!e) MHIP(hipEventCreate(&e));
-  // the previous set has been read (never recorded: no wait); the caller's inputs are there
-  MHIP(hipStreamWaitEvent(s.stream, r->finished, 0));
-  MHIP(hipStreamWaitEvent(s.stream, r->user_ready, 0));
-  if (timing) MHIP(hipEventRecord(s.xt[0], s.stream));
-  const float *dq = r->d_q0;
-  int32_t *out_l = r->x_gl.as<int32_t>();  // shard 0: list 0 of the gathered lists
-  float *out_d = r->x_gd.as<float>();
-  if (g > 0) {
-    MHIP(hipMemcpyPeerAsync(s.d_q.p, s.device, r->d_q0, r->sh[0].device, (size_t)n * D * sizeof(float), s.stream));
-    dq = s.d_q.as<float>();
-    out_l = s.x_l.as<int32_t>();
-    out_d = s.x_d.as<float>();
-  }
-  const XsRows rows = {s.d_rows.as<float>(), s.n, r->id_base + s.lo, D};
-  MHIP(xs_select_merge(s.xs, s.xpl, rows, dq, n, k1, out_l, out_d, s.stream, timing ? s.xt[1] : nullptr, &s.x_wgs, &s.x_qg));
-  if (timing) MHIP(hipEventRecord(s.xt[2], s.stream));
-  MHIP(hipEventRecord(s.done, s.stream));
-  return 0;
-}
-
-// Phases B and C, by the calling thread on the first device, once every shard's part is enqueued
-int xs_gather_merge_flag(vaqhip_multi_refiner *r, int32_t *d_lout, float *d_dout) {
-  RShard &s = r->sh[0];
-  const int n = r->nq, k = r->x_k, k1 = r->x_k1;
-  const bool exact = r->x_chain, timing = r->opt_timing != 0;
-  const size_t plane = (size_t)n * k1;
-  MHIP(hipSetDevice(s.device));
-  if (timing)
-    for (hipEvent_t &e : r->xt)
-      if (!e) MHIP(hipEventCreate(&e));
-  for (int g = 1; g < r->G; g++)
-    if (r->sh[g].n > 0) MHIP(hipStreamWaitEvent(s.stream, r->sh[g].done, 0));
-  if (timing) MHIP(hipEventRecord(r->xt[0], s.stream));
-  for (int g = 1; g < r->G; g++) {
-    const RShard &u = r->sh[g];
-    if (u.n == 0) continue;
-    const size_t at = (size_t)r->x_slot[g] * plane;
-    MHIP(hipMemcpyPeerAsync(r->x_gl.as<int32_t>() + at, s.device, u.x_l.p, u.device, plane * 4, s.stream));
-    MHIP(hipMemcpyPeerAsync(r->x_gd.as<float>() + at, s.device, u.x_d.p, u.device, plane * 4, s.stream));
-  }
-  if (timing) MHIP(hipEventRecord(r->xt[1], s.stream));
-  int32_t *m_l = exact ? r->x_k1_l.as<int32_t>() : d_lout;
-  float *m_d = exact ? r->x_k1_d.as<float>() : d_dout;
-  MHIP(vaq::launch_merge(r->x_gd.as<float>(), r->x_gl.as<int>(), nullptr, r->x_lists, (int64_t)plane, (int64_t)k1, n, k1, 0, 1,
-                         m_l, m_d, nullptr, r->x_ms_d.as<float>(), r->x_ms_id.as<int>(), s.stream));
-  if (timing) MHIP(hipEventRecord(r->xt[2], s.stream));
-  if (exact) {
-    int *list = r->x_list.as<int>();
-    MHIP(vaq::launch_exact_flag(n, k, m_l, m_d, d_lout, d_dout, list, reinterpret_cast<unsigned *>(list + n), s.stream));
-    MHIP(hipEventRecord(r->flagged, s.stream));
-  }
-  if (timing) MHIP(hipEventRecord(r->xt[3], s.stream));
-  return 0;
-}
-
-// One link of phase D on shard g, by the calling thread: the list, the heap arrays of the link before (prev < 0: none),
-// the replay over the shard's rows.  Enqueued in chain order: `flagged` and the previous link's event are recorded.
-int xs_link(vaqhip_multi_refiner *r, int g, int prev, int32_t *d_lout, float *d_dout) {
-  RShard &s = r->sh[g];
-  const int n = r->nq, k = r->x_k, dev0 = r->sh[0].device;
-  const bool timing = r->opt_timing != 0, last = g == r->x_last;
-  const size_t state = (size_t)n * k * 4;
-  MHIP(hipSetDevice(s.device));
-  const float *dq = r->d_q0;
-  const int *list = r->x_list.as<int>();
-  if (g > 0) {  // (shard 0's stream holds the flag step itself)
-    MHIP(hipStreamWaitEvent(s.stream, r->flagged, 0));
-    MHIP(hipMemcpyPeerAsync(s.x_list.p, s.device, r->x_list.p, dev0, ((size_t)n + 1) * 4, s.stream));
-    dq = s.d_q.as<float>();  // (there since phase A)
-    list = s.x_list.as<int>();
-  }
-  if (prev >= 0) {
-    const RShard &u = r->sh[prev];
-    MHIP(hipStreamWaitEvent(s.stream, u.link, 0));
-    MHIP(hipMemcpyPeerAsync(s.x_hin_v.p, s.device, u.x_hout_v.p, u.device, state, s.stream));
-    MHIP(hipMemcpyPeerAsync(s.x_hin_i.p, s.device, u.x_hout_i.p, u.device, state, s.stream));
-  }
-  if (timing) MHIP(hipEventRecord(s.xt[3], s.stream));
-  const bool direct = last && g == 0;  // (all rows on the first shard: its link writes the caller's buffers)
-  MHIP(vaq::launch_exhaust_replay_link(dq, n, r->D, s.d_rows.as<float>(), s.n, r->id_base + s.lo, k, list,
-                                       reinterpret_cast<const unsigned *>(list + n), prev >= 0 ? s.x_hin_v.as<float>() : nullptr,
-                                       prev >= 0 ? s.x_hin_i.as<int>() : nullptr, direct ? nullptr : s.x_hout_v.as<float>(),
-                                       direct ? nullptr : s.x_hout_i.as<int>(), last ? 1 : 0, direct ? d_lout : nullptr,
-                                       direct ? d_dout : nullptr, s.stream));
-  if (timing) MHIP(hipEventRecord(s.xt[4], s.stream));
-  MHIP(hipEventRecord(s.link, s.stream));
-  return 0;
-}
-
-// the end of a set on the first device: with a chain, the last link's slots placed at their queries
-int xs_finish(vaqhip_multi_refiner *r, bool chain, int32_t *d_lout, float *d_dout, hipStream_t user) {
-  RShard &s = r->sh[0];
-  const int n = r->nq, k = r->x_k;
-  MHIP(hipSetDevice(s.device));
-  if (chain && r->x_last > 0) {
-    const RShard &u = r->sh[r->x_last];
-    const size_t state = (size_t)n * k * 4;
-    const int *list = r->x_list.as<int>();
-    MHIP(hipStreamWaitEvent(s.stream, u.link, 0));
-    MHIP(hipMemcpyPeerAsync(s.x_hin_v.p, s.device, u.x_hout_v.p, u.device, state, s.stream));
-    MHIP(hipMemcpyPeerAsync(s.x_hin_i.p, s.device, u.x_hout_i.p, u.device, state, s.stream));
-    MHIP(vaq::launch_exhaust_scatter(n, k, list, reinterpret_cast<const unsigned *>(list + n), s.x_hin_v.as<float>(),
-                                     s.x_hin_i.as<int>(), d_lout, d_dout, s.stream));
-  }
-  if (r->opt_timing) MHIP(hipEventRecord(r->xt[4], s.stream));
-  MHIP(hipEventRecord(r->finished, s.stream));
-  MHIP(hipStreamWaitEvent(user, r->finished, 0));
-  return 0;
-}
-
-// option "timing": waits for the set and adds its figures (the slowest shard's select, merge and link)
-int xs_read_timing(vaqhip_multi_refiner *r, bool chain) {
-  RShard &s = r->sh[0];
-  vaqhip_multi_refiner_search_timing &t = r->x_timing;
-  auto span = [](hipEvent_t a, hipEvent_t b, float *ms) { return hipEventElapsedTime(ms, a, b); };
-  MHIP(hipSetDevice(s.device));
-  MHIP(hipEventSynchronize(r->finished));
-  float sel = 0, mer = 0, rep = 0, ms = 0;
-  for (int g = 0; g < r->G; g++) {
-    RShard &u = r->sh[g];
-    if (!xs_takes_part(g, u)) continue;
-    MHIP(hipSetDevice(u.device));
-    MHIP(span(u.xt[0], u.xt[1], &ms));
-    sel = std::max(sel, ms);
-    MHIP(span(u.xt[1], u.xt[2], &ms));
-    mer = std::max(mer, ms);
-    if (chain && u.n > 0) {
-      MHIP(span(u.xt[3], u.xt[4], &ms));
-      rep = std::max(rep, ms);
-    }
-  }
-  MHIP(hipSetDevice(s.device));
-  t.select_ms += sel;
-  t.merge_ms += mer;
-  t.replay_ms += rep;
-  MHIP(span(r->xt[0], r->xt[1], &ms));
-  t.gather_ms += ms;
-  MHIP(span(r->xt[1], r->xt[2], &ms));
-  t.cross_merge_ms += ms;
-  MHIP(span(r->xt[2], r->xt[3], &ms));
-  t.flag_ms += ms;
-  MHIP(span(r->xt[3], r->xt[4], &ms));
-  if (chain) t.chain_ms += ms;
-  if (chain) {
-    unsigned listed = 0;
-    MHIP(hipMemcpy(&listed, r->x_list.as<int>() + r->nq, sizeof(unsigned), hipMemcpyDeviceToHost));
-    t.listed_queries += (int)listed;
-  }
-  return 0;
-}
-
-// Device pointers on the first device, enqueue only; r->mu held.  As refine_device_locked.
-int search_device_locked(vaqhip_multi_refiner *r, const float *d_q, int nq, int k, int32_t *d_lout, float *d_dout,
-                         hipStream_t user) {
-  RShard &s = r->sh[0];
-  bool any_cap = false;
-  for (const RShard &u : r->sh) any_cap |= u.cap_rows > 0;
-  if (r->N == 0 && !any_cap) return mfail(VAQHIP_ESTATE, "no rows were set");
-  if (hipSetDevice(s.device) != hipSuccess) return mfail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", s.device);
-  const bool exact = r->opt_exact != 0, timing = r->opt_timing != 0;
-  s.err.clear();
-  r->x_timing = {};
-  r->x_timing.register_form = r->D <= (int)vaq::exhaust_register_max_dim();
-  if (r->G == 1) {  // the single refiner's launches, at their cost, on the caller's stream
-    auto body = [&]() -> int {
-      MHIP(s.xs.size_for(s.device, r->D));
-      const int k1 = exact ? k + 1 : k;
-      const XsPlan pl = xs_plan(s.xs, r->N, r->opt_splits, nq, k1);
-      MHIP(s.xs.fit(pl, k1, exact, timing));
-      MHIP(hipStreamWaitEvent(user, r->finished, 0));  // (the workspace is shared by the callers' streams)
-      const XsRows rows = {s.d_rows.as<float>(), r->N, r->id_base, r->D};
-      vaqhip_refiner_search_timing t1 = {};
-      hipError_t e = hipSuccess;
-      int sets = 0;
-      for (int q0 = 0; q0 < nq && e == hipSuccess; q0 += pl.chunk, sets++)
-        e = xs_search_set(s.xs, pl, rows, d_q + (size_t)q0 * r->D, std::min(pl.chunk, nq - q0), k, exact,
-                          d_lout + (size_t)q0 * k, d_dout + (size_t)q0 * k, user, timing ? &t1 : nullptr);
-      (void)hipEventRecord(r->finished, user);  // (also after a failure: work may be enqueued already)
-      MHIP(e);
-      vaqhip_multi_refiner_search_timing &t = r->x_timing;
-      t.select_ms = t1.select_ms;
-      t.merge_ms = t1.merge_ms;
-      t.flag_ms = t1.flag_ms;
-      t.replay_ms = t1.replay_ms;
-      t.listed_queries = t1.listed_queries;
-      t.splits = pl.S;
-      t.workgroups = t1.workgroups;
-      t.queries_per_group = t1.queries_per_group;
-      t.chain_shards = r->N > 0 ? 1 : 0;
-      t.sets = sets;
-      return 0;
-    };
-    const int rc = body();
-    return rc ? mfail(rc, "device %d: %s", s.device, s.err.c_str()) : VAQHIP_OK;
-  }
-  if (r->dirty) drain(r);
-  // the call's plan: the lists gathered, the chain's ends, one set size for every shard
-  int first = -1;
-  r->x_lists = 0;
-  r->x_last = 0;
-  for (int g = 0; g < r->G; g++) {
-    const RShard &u = r->sh[g];
-    if (!xs_takes_part(g, u)) continue;
-    r->x_slot[g] = r->x_lists++;
-    if (u.n > 0) {
-      if (first < 0) first = g;
-      r->x_last = g;
-    }
-  }
-  const bool chain = exact && first >= 0;  // (no rows at all: every slot is -1 / FLT_MAX under either rule)
-  const int k1 = chain ? k + 1 : k;
-  r->x_chain = chain;
-  r->x_k = k;
-  r->x_k1 = k1;
-  int set = std::min(nq, SET_QUERIES);
-  set = (int)std::min<size_t>((size_t)set, std::max<size_t>(1, XS_GATHER_BYTES / ((size_t)r->x_lists * k1 * 8)));
-  auto plan = [&](int max_chunk) -> int {
-    for (int g = 0; g < r->G; g++) {
-      RShard &u = r->sh[g];
-      if (!xs_takes_part(g, u)) continue;
-      if (hipSetDevice(u.device) != hipSuccess) return mfail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", u.device);
-      const hipError_t e = u.xs.size_for(u.device, r->D);
-      if (e != hipSuccess) return mfail(hip_code(e), "device %d: %s", u.device, hipGetErrorString(e));
-      u.xpl = xs_plan(u.xs, u.n, r->opt_splits, nq, k1, max_chunk);
-      set = std::min(set, u.xpl.chunk);
-    }
-    return VAQHIP_OK;
-  };
-  if (const int rc = plan(set)) return rc;  // every shard's own bound ...
-  if (const int rc = plan(set)) return rc;  // ... and the smallest of them for all: equal sets of one size
-  set = r->sh[0].xpl.chunk;
-  r->x_timing.splits = r->sh[std::max(first, 0)].xpl.S;
-  r->x_timing.chain_shards = first < 0 ? 0 : r->x_lists - (r->sh[0].n > 0 ? 0 : 1);
-  if (hipSetDevice(s.device) != hipSuccess) return mfail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", s.device);
-  if (hipEventRecord(r->user_ready, user) != hipSuccess) return mfail(VAQHIP_EHIP, "recording the caller's stream");
-  for (int q0 = 0; q0 < nq; q0 += set) {
-    r->nq = std::min(set, nq - q0);
-    r->d_q0 = d_q + (size_t)q0 * r->D;
-    int32_t *lo = d_lout + (size_t)q0 * k;
-    float *d_o = d_dout + (size_t)q0 * k;
-    int rc = on_shards(r, [&](int g, RShard &u) { return xs_enqueue_shard(r, g, u); });
-    auto step = [&](int g, int step_rc) {  // a step of the calling thread failed on shard g
-      return step_rc ? mfail(step_rc, "shard %d (device %d): %s", g, r->sh[g].device, r->sh[g].err.c_str()) : 0;
-    };
-    if (!rc) {
-      s.err.clear();
-      rc = step(0, xs_gather_merge_flag(r, lo, d_o));
-    }
-    for (int g = 0, prev = -1; !rc && chain && g < r->G; g++) {
-      if (r->sh[g].n == 0) continue;  // (a shard without rows is no link)
-      r->sh[g].err.clear();
-      rc = step(g, xs_link(r, g, prev, lo, d_o));
-      prev = g;
-    }
-    if (!rc) rc = step(0, xs_finish(r, chain, lo, d_o, user));
-    if (!rc && timing) rc = step(0, xs_read_timing(r, chain));
-    if (rc) {
-      r->dirty = true;  // (`finished` may not follow what was enqueued: the next call drains first)
-      return rc;
-    }
-    r->x_timing.sets++;
-    r->x_timing.workgroups = r->sh[std::max(first, 0)].x_wgs;
-    r->x_timing.queries_per_group = r->sh[std::max(first, 0)].x_qg;
-  }
-  return VAQHIP_OK;
+  return refine_device_locked(r, d_q, nq, r->w.cand_l.as<int32_t>(), R, k, d_lout, d_dout, st);
 }
 
 }  // namespace
@@ -707,24 +231,13 @@ void vaqhip_multi_refiner_destroy(vaqhip_multi_refiner *r) {
   for (RShard &s : r->sh) {
     (void)hipSetDevice(s.device);
     (void)hipDeviceSynchronize();  // (refines enqueued on the callers' streams read the rows)
-    for (DevBuf *b : {&s.d_rows, &s.d_q, &s.d_lin, &s.d_plane, &s.x_l, &s.x_d, &s.x_list, &s.x_hin_v, &s.x_hin_i, &s.x_hout_v,
-                      &s.x_hout_i})
-      b->release();
-    s.xs.release();
-    for (hipEvent_t e : s.t) (void)hipEventDestroy(e);
-    for (hipEvent_t e : s.xt)
-      if (e) (void)hipEventDestroy(e);
+    s.release();
     for (hipEvent_t e : {s.done, s.link})
       if (e) (void)hipEventDestroy(e);
     if (s.stream) (void)hipStreamDestroy(s.stream);
   }
   if (!r->sh.empty()) (void)hipSetDevice(r->sh[0].device);
-  for (DevBuf *b : {&r->d_planes, &r->w_q, &r->w_lin, &r->w_lout, &r->w_dout, &r->w_cand_l, &r->w_cand_d, &r->x_gl, &r->x_gd,
-                    &r->x_ms_d, &r->x_ms_id, &r->x_k1_l, &r->x_k1_d, &r->x_list})
-    b->release();
-  for (hipEvent_t e : r->t) (void)hipEventDestroy(e);
-  for (hipEvent_t e : r->xt)
-    if (e) (void)hipEventDestroy(e);
+  r->w.release(), r->rf.release(), r->x.release();
   for (hipEvent_t e : {r->user_ready, r->finished, r->flagged})
     if (e) (void)hipEventDestroy(e);
   delete r;
@@ -733,7 +246,7 @@ void vaqhip_multi_refiner_destroy(vaqhip_multi_refiner *r) {
 int vaqhip_multi_refiner_set_rows(vaqhip_multi_refiner *r, const float *X, int64_t N, int64_t id_base) {
   if (!r) return mfail(VAQHIP_EINVAL, "multi refiner is null");
   if (N < 0 || (N > 0 && !X)) return mfail(VAQHIP_EINVAL, "bad rows");
-  if (const int rc = check_labels_fit(N, id_base)) return rc;
+  if (const int rc = check_labels_fit(MULTI_REFINER, N, id_base)) return rc;
   std::lock_guard<std::mutex> lk(r->mu);
   DeviceGuard keep(DeviceGuard::restore_only);
   const vaq::RefineBounds cut = vaq::refine_cut(N, r->G, id_base);
@@ -742,9 +255,9 @@ int vaqhip_multi_refiner_set_rows(vaqhip_multi_refiner *r, const float *X, int64
         MHIP(hipSetDevice(s.device));
         const int64_t lo = cut.b[g] - id_base, n = cut.b[g + 1] - cut.b[g];
         s.n = 0;
-        if (const int rc = reserve_rows(r, s, n, false)) return rc;
+        MHIP(s.rows.reserve(n, RowStore::DROP, r->D));
         MHIP(hipDeviceSynchronize());
-        if (n > 0) MHIP(hipMemcpy(s.d_rows.p, X + (size_t)lo * r->D, (size_t)n * r->D * sizeof(float), hipMemcpyHostToDevice));
+        if (n > 0) MHIP(hipMemcpy(s.rows.buf.p, X + (size_t)lo * r->D, (size_t)n * r->D * sizeof(float), hipMemcpyHostToDevice));
         s.lo = lo;
         s.n = n;
         return 0;
@@ -766,16 +279,16 @@ int vaqhip_multi_refiner_add_rows(vaqhip_multi_refiner *r, const float *X, int64
   if (n_new < 0 || (n_new > 0 && !X)) return mfail(VAQHIP_EINVAL, "bad rows");
   if (n_new == 0) return VAQHIP_OK;
   std::lock_guard<std::mutex> lk(r->mu);
-  if (const int rc = check_labels_fit(r->N + n_new, r->id_base)) return rc;
+  if (const int rc = check_labels_fit(MULTI_REFINER, r->N + n_new, r->id_base)) return rc;
   // the new rows continue the numbering, so they extend the LAST shard, as vaqhip_multi_add_codes_u16 does
   RShard &s = r->sh[r->G - 1];
   DeviceGuard g(s.device);
   if (!g.ok) return mfail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", s.device);
   s.err.clear();
   auto body = [&]() -> int {
-    if (const int rc = reserve_rows(r, s, s.n + n_new, true)) return rc;
+    MHIP(s.rows.reserve(s.n + n_new, s.n, r->D));
     // (rows past s.n are read by no launch in flight: no wait is needed before they are written)
-    MHIP(hipMemcpy(s.d_rows.as<float>() + (size_t)s.n * r->D, X, (size_t)n_new * r->D * sizeof(float), hipMemcpyHostToDevice));
+    MHIP(hipMemcpy(s.rows.buf.as<float>() + (size_t)s.n * r->D, X, (size_t)n_new * r->D * sizeof(float), hipMemcpyHostToDevice));
     return 0;
   };
   if (const int rc = body()) return mfail(rc, "shard %d (device %d): %s", r->G - 1, s.device, s.err.c_str());
@@ -786,22 +299,12 @@ int vaqhip_multi_refiner_add_rows(vaqhip_multi_refiner *r, const float *X, int64
 }
 
 int vaqhip_multi_refiner_set_option(vaqhip_multi_refiner *r, const char *key, int64_t value) {
-  if (!r || !key) return mfail(VAQHIP_EINVAL, "null pointer");
-  const bool exact = std::strcmp(key, "exact_ties") == 0, timing = std::strcmp(key, "timing") == 0,
-             splits = std::strcmp(key, "exhaustive_splits") == 0;
-  if (!exact && !timing && !splits) return mfail(VAQHIP_EINVAL, "unknown option '%s'", key);
-  if (splits && (value < 0 || value > 64))  // (refused before the refiner is touched)
-    return mfail(VAQHIP_EINVAL, "exhaustive_splits=%lld: 0 (automatic) or 1..64", (long long)value);
-  std::lock_guard<std::mutex> lk(r->mu);
-  if (exact) r->opt_exact = value != 0;
-  else if (timing) r->opt_timing = value != 0;
-  else r->opt_splits = (int)value;
-  return VAQHIP_OK;
+  return set_option(MULTI_REFINER, r, key, value);
 }
 
 int vaqhip_multi_refiner_refine_device(vaqhip_multi_refiner *r, const float *d_queries, int nq, const int32_t *d_labels_in,
                                        int R, int k, int32_t *d_labels_out, float *d_distances_out, void *stream) {
-  if (const int rc = check_sizes(r, nq, R, k)) return rc;
+  if (const int rc = check_sizes(MULTI_REFINER, r, nq, R, k)) return rc;
   if (nq == 0) return VAQHIP_OK;
   if (!d_queries || !d_labels_in || !d_labels_out || !d_distances_out) return mfail(VAQHIP_EINVAL, "null pointer");
   std::lock_guard<std::mutex> lk(r->mu);
@@ -812,20 +315,20 @@ int vaqhip_multi_refiner_refine_device(vaqhip_multi_refiner *r, const float *d_q
 
 int vaqhip_multi_refiner_refine(vaqhip_multi_refiner *r, const float *queries, int nq, const int32_t *labels_in, int R,
                                 int k, int32_t *labels_out, float *distances_out) {
-  if (const int rc = check_sizes(r, nq, R, k)) return rc;
+  if (const int rc = check_sizes(MULTI_REFINER, r, nq, R, k)) return rc;
   if (nq == 0) return VAQHIP_OK;
   if (!queries || !labels_in || !labels_out || !distances_out) return mfail(VAQHIP_EINVAL, "null pointer");
   std::lock_guard<std::mutex> lk(r->mu);
   DeviceGuard keep(DeviceGuard::restore_only);
   return through_staging(r, queries, nq, labels_in, R, k, labels_out, distances_out, [&](int n, hipStream_t st) {
-    return refine_device_locked(r, r->w_q.as<float>(), n, r->w_lin.as<int32_t>(), R, k, r->w_lout.as<int32_t>(),
-                                r->w_dout.as<float>(), st);
+    return refine_device_locked(r, r->w.q.as<float>(), n, r->w.lin.as<int32_t>(), R, k, r->w.lout.as<int32_t>(),
+                                r->w.dout.as<float>(), st);
   });
 }
 
 int vaqhip_multi_search_refine_device(vaqhip_multi *mx, vaqhip_multi_refiner *r, const float *d_queries_raw, int nq, int R,
                                       int k, int32_t *d_labels_out, float *d_distances_out, void *stream) {
-  if (const int rc = check_sizes(r, nq, R, k)) return rc;
+  if (const int rc = check_sizes(MULTI_REFINER, r, nq, R, k)) return rc;
   std::lock_guard<std::mutex> lk(r->mu);
   if (const int rc = check_pair(mx, r, R)) return rc;
   if (nq == 0) return VAQHIP_OK;
@@ -836,43 +339,15 @@ int vaqhip_multi_search_refine_device(vaqhip_multi *mx, vaqhip_multi_refiner *r,
 
 int vaqhip_multi_search_refine(vaqhip_multi *mx, vaqhip_multi_refiner *r, const float *queries_raw, int nq, int R, int k,
                                int32_t *labels_out, float *distances_out) {
-  if (const int rc = check_sizes(r, nq, R, k)) return rc;
+  if (const int rc = check_sizes(MULTI_REFINER, r, nq, R, k)) return rc;
   std::lock_guard<std::mutex> lk(r->mu);
   if (const int rc = check_pair(mx, r, R)) return rc;
   if (nq == 0) return VAQHIP_OK;
   if (!queries_raw || !labels_out || !distances_out) return mfail(VAQHIP_EINVAL, "null pointer");
   DeviceGuard keep(DeviceGuard::restore_only);
   return through_staging(r, queries_raw, nq, nullptr, R, k, labels_out, distances_out, [&](int n, hipStream_t st) {
-    return search_refine_locked(mx, r, r->w_q.as<float>(), n, R, k, r->w_lout.as<int32_t>(), r->w_dout.as<float>(), st);
+    return search_refine_locked(mx, r, r->w.q.as<float>(), n, R, k, r->w.lout.as<int32_t>(), r->w.dout.as<float>(), st);
   });
-}
-
-int vaqhip_multi_refiner_search_device(vaqhip_multi_refiner *r, const float *d_queries, int nq, int k, int32_t *d_labels_out,
-                                       float *d_distances_out, void *stream) {
-  if (const int rc = check_search(r, nq, k, d_queries, d_labels_out, d_distances_out)) return rc;
-  if (nq == 0) return VAQHIP_OK;
-  std::lock_guard<std::mutex> lk(r->mu);
-  DeviceGuard keep(DeviceGuard::restore_only);
-  return search_device_locked(r, d_queries, nq, k, d_labels_out, d_distances_out, static_cast<hipStream_t>(stream));
-}
-
-int vaqhip_multi_refiner_search(vaqhip_multi_refiner *r, const float *queries, int nq, int k, int32_t *labels_out,
-                                float *distances_out) {
-  if (const int rc = check_search(r, nq, k, queries, labels_out, distances_out)) return rc;
-  if (nq == 0) return VAQHIP_OK;
-  std::lock_guard<std::mutex> lk(r->mu);
-  DeviceGuard keep(DeviceGuard::restore_only);
-  // (under "timing" the figures are the last staged set's: the bench and the tests stay within one)
-  return through_staging(r, queries, nq, nullptr, 0, k, labels_out, distances_out, [&](int n, hipStream_t st) {
-    return search_device_locked(r, r->w_q.as<float>(), n, k, r->w_lout.as<int32_t>(), r->w_dout.as<float>(), st);
-  });
-}
-
-int vaqhip_multi_refiner_last_search_timing(vaqhip_multi_refiner *r, vaqhip_multi_refiner_search_timing *out) {
-  if (!r || !out) return mfail(VAQHIP_EINVAL, "null pointer");
-  std::lock_guard<std::mutex> lk(r->mu);
-  *out = r->x_timing;
-  return VAQHIP_OK;
 }
 
 int vaqhip_multi_refiner_get_info(vaqhip_multi_refiner *r, vaqhip_multi_refiner_info *out) {
@@ -884,7 +359,7 @@ int vaqhip_multi_refiner_get_info(vaqhip_multi_refiner *r, vaqhip_multi_refiner_
   out->D = r->D;
   out->N = r->N;
   out->id_base = r->id_base;
-  out->exact_ties = r->opt_exact;
+  out->exact_ties = r->opt.exact;
   out->set_queries = SET_QUERIES;
   for (int g = 0; g < VAQHIP_MAX_DEVICES; g++) {
     out->device_ids[g] = g < r->G ? r->sh[g].device : -1;
@@ -899,23 +374,23 @@ int vaqhip_multi_refiner_get_info(vaqhip_multi_refiner *r, vaqhip_multi_refiner_
   bool ok = true;
   float ms = 0;
   if (r->last_single && r->last_sets) {
-    ok = hipSetDevice(r->sh[0].device) == hipSuccess && span(r->t[0], r->t[1], &ms);
+    ok = hipSetDevice(r->sh[0].device) == hipSuccess && span(r->rf.t[0], r->rf.t[1], &ms);
     out->last_distances_ms = ms;  // (one kernel: the distances and the selection together)
   } else {
     for (int i = 0; ok && i < r->last_sets; i++) {
       float bc = 0, di = 0;
       for (int g = 0; ok && g < r->G; g++) {
         const RShard &s = r->sh[g];
-        ok = hipSetDevice(s.device) == hipSuccess && span(s.t[3 * i], s.t[3 * i + 1], &ms);
+        ok = hipSetDevice(s.device) == hipSuccess && span(s.rf.t[3 * i], s.rf.t[3 * i + 1], &ms);
         bc = std::max(bc, ms);
-        ok = ok && span(s.t[3 * i + 1], s.t[3 * i + 2], &ms);
+        ok = ok && span(s.rf.t[3 * i + 1], s.rf.t[3 * i + 2], &ms);
         di = std::max(di, ms);
       }
       out->last_broadcast_ms += bc;
       out->last_distances_ms += di;
-      ok = ok && hipSetDevice(r->sh[0].device) == hipSuccess && span(r->t[3 * i], r->t[3 * i + 1], &ms);
+      ok = ok && hipSetDevice(r->sh[0].device) == hipSuccess && span(r->rf.t[3 * i], r->rf.t[3 * i + 1], &ms);
       out->last_gather_ms += ms;
-      ok = ok && span(r->t[3 * i + 1], r->t[3 * i + 2], &ms);
+      ok = ok && span(r->rf.t[3 * i + 1], r->rf.t[3 * i + 2], &ms);
       out->last_select_ms += ms;
     }
   }

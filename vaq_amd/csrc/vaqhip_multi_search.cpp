@@ -38,36 +38,24 @@ namespace {
 int fit_buffers(vaqhip_multi *mx, int g, Shard &s) {
   const Call &c = mx->call;
   const int G = mx->G;
-  struct Fit { DevBuf *b; size_t bytes; const char *what; } fit[9];
-  int n = 0;
-  auto want = [&](DevBuf &b, size_t bytes, const char *what) { fit[n++] = Fit{&b, bytes, what}; };
-  want(s.d_queries, c.query_bytes(mx->D), "d_queries");
-  want(s.d_packed, c.packed_bytes(), "d_packed");
-  if (G > 1 && (c.rccl || g == 0)) want(s.d_gathered, G * c.packed_bytes(), "d_gathered");  // who holds every shard's
-  if (c.fast && g == 0) want(mx->d_head, c.head_bytes(), "d_head");
-  if (g == 0) want(mx->d_out_labels, c.pair_bytes(), "d_out_labels");
+  FitList fit;
+  fit.want(s.d_queries, c.query_bytes(mx->D), "d_queries");
+  fit.want(s.d_packed, c.packed_bytes(), "d_packed");
+  if (G > 1 && (c.rccl || g == 0)) fit.want(s.d_gathered, G * c.packed_bytes(), "d_gathered");  // who holds every shard's
+  if (c.fast && g == 0) fit.want(mx->d_head, c.head_bytes(), "d_head");
+  if (g == 0) fit.want(mx->d_out_labels, c.pair_bytes(), "d_out_labels");
   if (c.chain) {
-    want(s.d_list, c.list_bytes(), "d_list");
-    want(s.d_state_in, c.state_bytes(), "d_state_in");
-    want(s.d_state_out, c.state_bytes(), "d_state_out");
-    if (g == 0) want(mx->d_final, c.state_bytes(), "d_final");
+    fit.want(s.d_list, c.list_bytes(), "d_list");
+    fit.want(s.d_state_in, c.state_bytes(), "d_state_in");
+    fit.want(s.d_state_out, c.state_bytes(), "d_state_out");
+    if (g == 0) fit.want(mx->d_final, c.state_bytes(), "d_final");
   }
   MHIP(hipSetDevice(s.device));
-  // Growing frees the old buffer, and hipFree waits for the work of the buffer's own device only -- but the last
-  // search's copies out of d_packed, d_state_out and d_list run on ANOTHER device's stream, and after the device
-  // entry nobody has waited for them.  `consumed` follows all of them (never recorded, or recorded before a host
-  // entry returned: no wait).  A search that failed on shard 0 after phase 1 may not have recorded it: search_set
-  // leaves every stream idle instead.
-  bool grows = false;
-  for (int i = 0; i < n; i++) grows |= fit[i].bytes > fit[i].b->cap;
-  if (grows) MHIP(hipEventSynchronize(mx->consumed));
-  for (int i = 0; i < n; i++) {
-    const hipError_t e = fit[i].b->ensure(fit[i].bytes);
-    if (e != hipSuccess) {
-      s.err = std::string(fit[i].what) + ".ensure: " + hipGetErrorString(e);
-      return hip_code(e);
-    }
-  }
+  // The last search's copies out of d_packed, d_state_out and d_list run on ANOTHER device's stream, and after the
+  // device entry nobody has waited for them.  `consumed` follows all of them (never recorded, or recorded before a
+  // host entry returned: no wait).  A search that failed on shard 0 after phase 1 may not have recorded it:
+  // search_set leaves every stream idle instead.
+  MFIT(fit, mx->consumed);
   if (g == 0) mx->d_out_dist = reinterpret_cast<float *>(mx->d_out_labels.as<int32_t>() + c.plane());
   while (c.chain && (int)s.link_done.size() < c.n_batches) {
     hipEvent_t e = nullptr;
