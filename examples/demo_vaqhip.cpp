@@ -26,6 +26,11 @@
 //                                           --refine-resident; with --devices cut over the same GPUs, same answer --
 //                                           and the recall lines are printed against them)
 //               [--devices 0,1,2,3]        (shard the rows over these GPUs: RCCL all-gather + merge)
+//               [--encode --dataset base.fvecs [--save-enc cb.bin]]
+//                                          (instead of --codebook: VAQ::encode of the raw vectors, mEigenVectors applied.
+//                                           With --devices every shard encodes the rows it will hold and keeps their
+//                                           codes; with --devices and --refine-resident the rows are uploaded once, cut
+//                                           over the GPUs, and encoded where they lie -- the same codes either way)
 //               with a ...,FAST method (codes of at most 4 bits): --dataset base.fvecs [--dataset-size N]
 //               [--learn-ratio 0.05]       (demo_vaq.cpp:42, :120-124: VAQ::learnQuantization on the raw dataset)
 //
@@ -100,7 +105,8 @@ int main(int argc, char **argv) {
   std::map<std::string, std::string> a = {{"k", "100"}, {"method", "VAQ64m8min8max8var1,HEAP"},
                                           {"timeseries-size", "128"}, {"queries-size", "-1"}};
   for (int i = 1; i < argc; i += 2) {
-    if (std::strcmp(argv[i], "--refine-resident") == 0 || std::strcmp(argv[i], "--exact-groundtruth") == 0) {
+    if (std::strcmp(argv[i], "--refine-resident") == 0 || std::strcmp(argv[i], "--exact-groundtruth") == 0 ||
+        std::strcmp(argv[i], "--encode") == 0) {
       a[argv[i] + 2] = "1";  // the switches without a value
       i--;
       continue;
@@ -117,13 +123,14 @@ int main(int argc, char **argv) {
       return 1;
     }
   }
-  for (const char *req : {"centroids", "codebook", "queries"})
+  const bool encode = a.count("encode") != 0;
+  for (const char *req : {"centroids", encode ? "dataset" : "codebook", "queries"})
     if (!a.count(req)) { std::cerr << "missing --" << req << "\n"; return 2; }
   try {
     VaqHipFast vaq;  // VaqHip plus the FAST method
     vaq.parseMethodString(a["method"]);
     vaq.mCentroidsPerSubs = loadCentroids(a["centroids"]);
-    vaq.mCodebook = loadCodebook(a["codebook"]);
+    if (!encode) vaq.mCodebook = loadCodebook(a["codebook"]);
     const int M = (int)vaq.mCentroidsPerSubs.size();
     if (a.count("bits")) {  // --hc-bitalloc style list (demo_vaq.cpp:94-97)
       std::stringstream ss(a["bits"]);
@@ -146,6 +153,41 @@ int main(int argc, char **argv) {
       while (std::getline(ss, t, ',')) devs.push_back(std::atoi(t.c_str()));
       vaq.setDevices(devs);
       std::cout << "sharding the rows over " << devs.size() << " device entr" << (devs.size() == 1 ? "y" : "ies") << std::endl;
+    }
+    RowMatrixF datasetrefine;
+    bool uploaded = false;  // the raw vectors are resident already (--encode with --refine-resident)
+    if (encode) {  // demo_vaq.cpp:126-135, from the raw vectors
+      const int dsize = a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1;
+      auto t0 = std::chrono::steady_clock::now();
+      // (the TI centres come from the codes: encode under the method without TI, as clusterTI(true) pushes the codes)
+      const uint32_t methods = vaq.mMethods, plain = methods & ~(uint32_t)VaqHip::NNMethod::TI;
+      vaq.mMethods = plain ? plain : (uint32_t)VaqHip::NNMethod::Heap;
+      if (a.count("devices") && a.count("refine-resident")) {
+        if (N != D) throw Error(VAQHIP_EINVAL, "--encode with --refine-resident encodes the resident raw rows: --timeseries-size must be D");
+        datasetrefine = readFVecs(a.count("dataset-refine") ? a["dataset-refine"] : a["dataset"], N, dsize, 0);
+        t0 = std::chrono::steady_clock::now();
+        vaq.setRefineDataset(datasetrefine);
+        uploaded = true;
+        std::cout << "== Refine dataset upload: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+                  << " s (" << datasetrefine.rows() << " rows resident)" << std::endl;
+        t0 = std::chrono::steady_clock::now();
+        vaq.encodeRefineDataset();
+      } else {
+        if (a.count("refine-resident"))
+          std::cout << "(--refine-resident without --devices: one device does not encode its resident rows in place, "
+                       "the rows are encoded from the host matrix)" << std::endl;
+        RowMatrixF dataset = readFVecs(a["dataset"], N, dsize, D - N);
+        t0 = std::chrono::steady_clock::now();
+        vaq.encode(dataset, false);
+      }
+      vaq.mMethods = methods;
+      std::cout << "== Encoding time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s ("
+                << vaq.mCodebook.rows() << " rows" << (uploaded ? ", from the resident rows" : "") << ")" << std::endl;
+      vaqhip_multi_encode_timing et;
+      if (vaq.multiHandle() && vaqhip_multi_last_encode_timing(vaq.multiHandle(), &et) == 0)
+        std::cout << "   across " << et.n_devices << " shards: total " << et.total_ms << " ms, encode " << et.encode_ms
+                  << " ms, set codes " << et.set_codes_ms << " ms (slowest shard)" << std::endl;
+      if (a.count("save-enc")) saveCodebook(vaq.mCodebook, a["save-enc"]);
     }
     if (vaq.searchMethod() & VaqHip::NNMethod::TI) {  // demo_vaq.cpp:57, :263-267
       if (a.count("visit-cluster")) vaq.mVisit = (float)std::atof(a["visit-cluster"].c_str());
@@ -170,17 +212,17 @@ int main(int argc, char **argv) {
       while (std::getline(ss, t, ',')) refines.push_back(std::atoi(t.c_str()));
     }
     if (refines.empty()) refines.push_back(0);
-    RowMatrixF datasetrefine;
     bool any_refine = false;
     for (const int r : refines) any_refine = any_refine || r >= k;
     if (any_refine) {
       // the reference re-reads --dataset for this (demo_vaq.cpp:320-333); --dataset-refine names another file
       const std::string raw = a.count("dataset-refine") ? a["dataset-refine"] : (a.count("dataset") ? a["dataset"] : "");
       if (raw.empty()) throw Error(VAQHIP_EINVAL, "--refine needs the raw vectors: --dataset <.fvecs> (or --dataset-refine)");
-      datasetrefine = readFVecs(raw, N, a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1, 0);
+      if (!uploaded) datasetrefine = readFVecs(raw, N, a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1, 0);
     }
-    const bool resident = any_refine && a.count("refine-resident");
-    if (resident) {
+    const bool resident = (any_refine && a.count("refine-resident")) || uploaded;
+    if (resident && uploaded) vaq.refineExactTies = a.count("exact-ties") && std::atoi(a["exact-ties"].c_str()) != 0;
+    if (resident && !uploaded) {
       if (N != D) throw Error(VAQHIP_EINVAL, "--refine-resident searches and refines with the same raw query: --timeseries-size must be D");
       vaq.refineExactTies = a.count("exact-ties") && std::atoi(a["exact-ties"].c_str()) != 0;
       auto t0 = std::chrono::steady_clock::now();

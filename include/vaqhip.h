@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 114
+#define VAQHIP_VERSION 115
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -474,8 +474,8 @@ int vaqhip_merge_fast_device(int device_id, const uint16_t *d_head_dist, int64_t
  *                on that GPU (RCCL refuses duplicate devices, so the gather is then done with
  *                device-to-device copies; same buffers, same merge) -- how a one-GPU box tests
  *                the sharded path.
- * Options ("exchange": 0 auto, 1 RCCL, 2 copies; "exact_batch" below; anything else is forwarded to
- * every shard).
+ * Options ("exchange": 0 auto, 1 RCCL, 2 copies; "exact_batch" below; "encode_chunk_rows": "Encode across the
+ * shards" below; anything else is forwarded to every shard).
  *   "exact_ties" = 1 holds ACROSS the shards: labels and distances are VAQ::search's over all rows,
  *                slot for slot.  Shards are contiguous label ranges in label order (appends extend the
  *                last one), so the reference's heap after the rows of shards 0..g is shard g's replay
@@ -500,6 +500,7 @@ int vaqhip_merge_fast_device(int device_id, const uint16_t *d_head_dist, int64_t
  * ------------------------------------------------------------------------- */
 #define VAQHIP_MAX_DEVICES 16
 typedef struct vaqhip_multi vaqhip_multi;
+typedef struct vaqhip_multi_refiner vaqhip_multi_refiner;  /* "Multi-device refiner" below */
 int vaqhip_multi_create(vaqhip_multi **out, int D, int M, const int *bits,
                         const float *const *centroids_rowmajor, const float *eigvec_real_rowmajor,
                         int n_devices, const int *device_ids, unsigned flags);
@@ -554,6 +555,47 @@ int vaqhip_multi_set_option(vaqhip_multi *mx, const char *key, int64_t value);
 int vaqhip_multi_set_lut_quantization(vaqhip_multi *mx, const float *offsets, const float *scale);
 int vaqhip_multi_learn_quantization(vaqhip_multi *mx, const float *X_rowmajor, int64_t n, int projected,
                                     float sample_ratio, float *offsets_out, float *scale_out);
+/* Encode across the shards: VAQ::encode (vaqhip_encode's rule: strict `<`, first minimum, the checked projection on
+ * VAQHIP_SUM_SEQUENTIAL shards) with every shard encoding the rows it will hold, on its own device.
+ *   contract    vaqhip_multi_encode_set_codes leaves the index in exactly the state of vaqhip_encode on one index with
+ *               the same codebooks over all N rows followed by vaqhip_multi_set_codes_u16(mx, codes, N, id_base): the
+ *               same cut, shard_rows, labels and packed order, hence the same answer bit for bit from every later call.
+ *               codes_out (N x M, may be NULL) is vaqhip_encode's matrix.  vaqhip_multi_encode_add_codes is the same
+ *               against vaqhip_encode + vaqhip_multi_add_codes_u16: the rows extend the last shard and are encoded on
+ *               its device.  A row's code depends on that row and the codebooks only, and every shard holds the
+ *               codebooks and the rotation: nothing is exchanged.
+ *   host form   every shard's host thread uploads ITS slice of X in chunks, encodes them into a device buffer of
+ *               rows_g x M uint16 and hands that buffer to its index on the device.  No code reaches the host unless
+ *               codes_out asks for it, no row reaches a device other than the one that will hold its code.  Per shard:
+ *               rows_g * M * 2 bytes of codes and one chunk of D * 4 bytes per row (twice with projected = 0).
+ *   refiner     vaqhip_multi_encode_from_refiner reads the RAW rows resident in a multi refiner in place (projected = 0):
+ *               N, id_base and the cut are the refiner's, shard g of the index receives the rows of shard g of the
+ *               refiner -- a last shard grown by add_rows and empty shards included -- so vaqhip_multi_search_refine
+ *               sees equal N and id_base afterwards.  Nothing is uploaded.
+ *   refusals    before any device is touched: VAQHIP_EINVAL for a null index, matrix or refiner, negative sizes, D or
+ *               device lists that differ between index and refiner; labels that would pass int32 and N == 0 as
+ *               vaqhip_multi_set_codes_u16 treats them; VAQHIP_ESTATE for a refiner without rows and for _add_codes on
+ *               an index that never received codes.
+ *   failure     phase one, every shard encodes into scratch: a failure leaves every shard as it was.  Phase two, the
+ *               shards take their codes: a failure there is vaqhip_multi_set_codes_u16's.
+ *   option      "encode_chunk_rows" (vaqhip_multi_set_option): rows per upload / project chunk, 0 = 1 << 20, negative
+ *               VAQHIP_EINVAL.  Results do not depend on it.
+ * Synchronous; the caller's current device is left as it was; serialised with the other calls on the index. */
+int vaqhip_multi_encode_set_codes(vaqhip_multi *mx, const float *X_rowmajor, int64_t N, int projected,
+                                  int64_t id_base, uint16_t *codes_out /* N x M, may be NULL */);
+int vaqhip_multi_encode_add_codes(vaqhip_multi *mx, const float *X_rowmajor, int64_t n_new, int projected,
+                                  uint16_t *codes_out /* n_new x M, may be NULL */);
+int vaqhip_multi_encode_from_refiner(vaqhip_multi *mx, vaqhip_multi_refiner *r,
+                                     uint16_t *codes_out /* N x M, may be NULL */);
+typedef struct {
+  float total_ms;      /* wall time of the call                                                   */
+  float encode_ms;     /* the slowest shard, device events: upload (host form), project, encode   */
+  float set_codes_ms;  /* the slowest shard, device events: sort and pack (append: merge)         */
+  int64_t rows;        /* rows encoded                                                            */
+  int n_devices;
+} vaqhip_multi_encode_timing;
+/* figures of the last of the three calls above that ran (zeros before the first) */
+int vaqhip_multi_last_encode_timing(vaqhip_multi *mx, vaqhip_multi_encode_timing *out);
 typedef struct {
   int n_devices;
   int exchange;              /* what the last search used: 0 none (one shard), 1 RCCL all-gather, 2 copies */
@@ -603,7 +645,6 @@ const char *vaqhip_multi_last_error(void);
  * result).  Errors: vaqhip_multi_last_error().  Calls on one refiner are serialised on the host.
  * ------------------------------------------------------------------------- */
 #define VAQHIP_MULTI_REFINER_SET 16384
-typedef struct vaqhip_multi_refiner vaqhip_multi_refiner;
 int vaqhip_multi_refiner_create(vaqhip_multi_refiner **out, int D, int n_devices, const int *device_ids);
 void vaqhip_multi_refiner_destroy(vaqhip_multi_refiner *r);
 int vaqhip_multi_refiner_set_rows(vaqhip_multi_refiner *r, const float *X_rowmajor, int64_t N, int64_t id_base);

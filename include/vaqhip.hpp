@@ -326,8 +326,32 @@ public:
     try { sync(); } catch (...) { codes_set_ = had; throw; }
     codes_set_ = false;
     mCodebook = CodebookType((size_t)XTrain.rows(), (size_t)mHighestSubs());
-    vaqhip_index *enc = mh_ ? vaqhip_multi_shard(mh_, 0) : h_;  // (every shard holds the codebooks)
-    check(vaqhip_encode(enc, XTrain.data(), (int64_t)XTrain.rows(), projected ? 1 : 0, mCodebook.data()));
+    if (mh_) {
+      // every shard encodes the rows it will hold and keeps their codes (vaqhip.h, "Encode across the shards");
+      // mCodebook is filled all the same (saveCodebook and callers read it), but search() need not upload it again
+      checkMulti(vaqhip_multi_encode_set_codes(mh_, XTrain.data(), (int64_t)XTrain.rows(), projected ? 1 : 0, mIdBase,
+                                               mCodebook.data()));
+      codes_set_ = true;
+      return;
+    }
+    check(vaqhip_encode(h_, XTrain.data(), (int64_t)XTrain.rows(), projected ? 1 : 0, mCodebook.data()));
+  }
+
+  // encode() from the rows setRefineDataset() left on the devices (after setDevices(); the RAW rows, so mEigenVectors
+  // are applied): nothing is uploaded, every shard encodes its resident rows in place, and mCodebook is filled as
+  // encode(XTrain, false) fills it.  On one device the rows of a refiner are not encoded in place: VAQHIP_EUNSUPPORTED.
+  void encodeRefineDataset() {
+    if (mDevices.empty()) throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: encodeRefineDataset needs setDevices()");
+    if (!mrf_) throw Error(VAQHIP_ESTATE, "vaqhip: encodeRefineDataset needs setRefineDataset() first");
+    const bool had = codes_set_;
+    codes_set_ = true;  // (as encode(): the codebook is not there yet)
+    try { sync(); } catch (...) { codes_set_ = had; throw; }
+    codes_set_ = false;
+    vaqhip_multi_refiner_info inf;
+    checkMulti(vaqhip_multi_refiner_get_info(mrf_, &inf));
+    mCodebook = CodebookType((size_t)inf.N, (size_t)mHighestSubs());
+    checkMulti(vaqhip_multi_encode_from_refiner(mh_, mrf_, mCodebook.data()));
+    codes_set_ = true;
   }
 
   // VAQ::refine, VAQ.hpp:104 / VAQ.cpp:849-876

@@ -37,6 +37,8 @@ SYMBOLS = [
     "vaqhip_multi_set_lut_quantization", "vaqhip_multi_learn_quantization",
     "vaqhip_multi_cluster_ti_kmeans", "vaqhip_multi_last_kmeans_timing",
     "vaqhip_multi_get_info", "vaqhip_multi_shard", "vaqhip_multi_last_error",
+    "vaqhip_multi_encode_set_codes", "vaqhip_multi_encode_add_codes", "vaqhip_multi_encode_from_refiner",
+    "vaqhip_multi_last_encode_timing",
     "vaqhip_multi_refiner_create", "vaqhip_multi_refiner_destroy", "vaqhip_multi_refiner_set_rows",
     "vaqhip_multi_refiner_add_rows", "vaqhip_multi_refiner_set_option", "vaqhip_multi_refiner_refine",
     "vaqhip_multi_refiner_refine_device", "vaqhip_multi_search_refine", "vaqhip_multi_search_refine_device",
@@ -96,6 +98,11 @@ class RefinerSearchTiming(C.Structure):
 class MultiRefinerSearchTiming(C.Structure):
     _fields_ = RefinerSearchTiming._fields_ + [("gather_ms", C.c_float), ("cross_merge_ms", C.c_float),
                                                ("chain_ms", C.c_float), ("chain_shards", C.c_int), ("sets", C.c_int)]
+
+
+class MultiEncodeTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("encode_ms", C.c_float), ("set_codes_ms", C.c_float), ("rows", C.c_int64),
+                ("n_devices", C.c_int)]
 
 
 class MultiInfo(C.Structure):
@@ -215,6 +222,10 @@ def load():
     L.vaqhip_multi_shard.argtypes = [vp, i32]
     L.vaqhip_multi_shard.restype = vp
     L.vaqhip_multi_last_error.restype = C.c_char_p
+    L.vaqhip_multi_encode_set_codes.argtypes = [vp, vp, i64, i32, i64, vp]
+    L.vaqhip_multi_encode_add_codes.argtypes = [vp, vp, i64, i32, vp]
+    L.vaqhip_multi_encode_from_refiner.argtypes = [vp, vp, vp]
+    L.vaqhip_multi_last_encode_timing.argtypes = [vp, C.POINTER(MultiEncodeTiming)]
     L.vaqhip_multi_refiner_create.argtypes = [C.POINTER(vp), i32, i32, C.POINTER(i32)]
     L.vaqhip_multi_refiner_destroy.argtypes = [vp]
     L.vaqhip_multi_refiner_destroy.restype = None

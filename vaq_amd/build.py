@@ -14,9 +14,10 @@ CSRC = os.path.join(ROOT, "vaq_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "vaq_amd", "lib")
 LIB = os.path.join(LIBDIR, "libvaqhip.so")
 SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_fast.hip", "vaq_lutfit.hip", "vaq_refine.hip", "vaq_exhaust.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp", "vaqhip_lutfit.cpp", "vaqhip_refiner.cpp",
-           "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp", "vaqhip_rccl.cpp"]
+           "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp", "vaqhip_multi_encode.cpp", "vaqhip_rccl.cpp"]
 MULTI_REFINER_SOURCES = ("vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp")
-MULTI_SOURCES = ("vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp") + MULTI_REFINER_SOURCES
+MULTI_ENCODE_SOURCE = "vaqhip_multi_encode.cpp"  # reads the multi refiner's resident rows: its headers too
+MULTI_SOURCES = ("vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", MULTI_ENCODE_SOURCE) + MULTI_REFINER_SOURCES
 KERNEL_HEADER = os.path.join(CSRC, "vaq_kernels.h")
 OWNER_HEADER = os.path.join(CSRC, "refine_owner.h")  # the refiner's cut and label -> shard: vaq_kernels.h brings it
 API_HEADER = os.path.join(ROOT, "include", "vaqhip.h")
@@ -67,9 +68,9 @@ def _deps(src: str):
         deps.append(REFINE_GROUP_HEADER)
     if src == "vaq_exhaust.hip":
         deps.append(EXHAUST_HEADER)
-    if src == "vaqhip_refiner.cpp" or src in MULTI_REFINER_SOURCES:
+    if src == "vaqhip_refiner.cpp" or src in MULTI_REFINER_SOURCES or src == MULTI_ENCODE_SOURCE:
         deps += [EXHAUST_PLAN_HEADER, REFINE_COMMON_HEADER]
-    if src in MULTI_REFINER_SOURCES:
+    if src in MULTI_REFINER_SOURCES or src == MULTI_ENCODE_SOURCE:
         deps.append(MULTI_REFINER_HEADER)
     return deps
 OBJDIR = os.path.join(LIBDIR, "obj")

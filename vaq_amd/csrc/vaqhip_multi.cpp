@@ -107,12 +107,7 @@ int vaqhip_multi_set_codes_u16(vaqhip_multi *mx, const uint16_t *codes, int64_t 
   if (!mx) return mfail(VAQHIP_EINVAL, "multi index is null");
   if (N < 0 || (N > 0 && !codes) || id_base < 0) return mfail(VAQHIP_EINVAL, "bad codes/N/id_base");
   std::lock_guard<std::mutex> lk(mx->mu);
-  const int64_t per = (N + mx->G - 1) / mx->G;  // contiguous shards of ceil(N / G) rows
-  for (int g = 0; g < mx->G; g++) {
-    Shard &s = mx->sh[g];
-    s.lo = std::min<int64_t>(N, (int64_t)g * per);
-    s.n = std::min<int64_t>(N, (int64_t)(g + 1) * per) - s.lo;
-  }
+  for (int g = 0; g < mx->G; g++) shard_cut(N, mx->G, g, &mx->sh[g].lo, &mx->sh[g].n);
   // every shard uploads, sorts and packs its rows on its own device, all of them at once
   if (const int rc = on_shards(mx, [&](int, Shard &s) {
         return vaqhip_index_set_codes_u16(s.ix, codes + s.lo * mx->M, s.n, id_base + s.lo);
@@ -120,6 +115,7 @@ int vaqhip_multi_set_codes_u16(vaqhip_multi *mx, const uint16_t *codes, int64_t 
     return rc;
   mx->N = N;
   mx->id_base = id_base;
+  mx->has_codes = true;
   return VAQHIP_OK;
 }
 
@@ -133,6 +129,7 @@ int vaqhip_multi_add_codes_u16(vaqhip_multi *mx, const uint16_t *codes, int64_t 
   if (const int rc = forward(vaqhip_index_add_codes_u16(s.ix, codes, n_new))) return rc;
   s.n += n_new;
   mx->N += n_new;
+  mx->has_codes = true;
   return VAQHIP_OK;
 }
 
@@ -184,6 +181,7 @@ int vaqhip_multi_learn_quantization(vaqhip_multi *mx, const float *X, int64_t n,
 
 int vaqhip_multi_set_option(vaqhip_multi *mx, const char *key, int64_t value) {
   if (!mx || !key) return mfail(VAQHIP_EINVAL, "null pointer");
+  if (std::strcmp(key, "encode_chunk_rows") == 0) return set_encode_chunk_rows(mx, value);
   std::lock_guard<std::mutex> lk(mx->mu);
   if (std::strcmp(key, "exchange") == 0) {
     if (value < 0 || value > 2) return mfail(VAQHIP_EINVAL, "exchange must be 0 (auto), 1 (RCCL) or 2 (copies)");

@@ -1,9 +1,10 @@
 // vaqhip_multi.h -- what the host files of the multi-device index share: the shard, the index with the
 // geometry of the search in flight, the error hand-over, the grow path of a phase's buffers and the two loops over
 // shards.  Private to vaqhip_multi.cpp (life cycle, codes, setters), vaqhip_multi_search.cpp (the search),
-// vaqhip_multi_kmeans.cpp (the k-means of clusterTI) and, through vaqhip_multi_refiner.h, the refiner over sharded raw
-// rows (vaqhip_multi_refiner.cpp, vaqhip_multi_refiner_search.cpp), which takes the error hand-over, the grow path and
-// on_shards from here; they see a shard's index through include/vaqhip.h and vaqhip_internal.h only.
+// vaqhip_multi_kmeans.cpp (the k-means of clusterTI), vaqhip_multi_encode.cpp (the encode across the shards) and,
+// through vaqhip_multi_refiner.h, the refiner over sharded raw rows (vaqhip_multi_refiner.cpp,
+// vaqhip_multi_refiner_search.cpp), which takes the error hand-over, the grow path and on_shards from here; they see a
+// shard's index through include/vaqhip.h and vaqhip_internal.h only.
 #ifndef VAQHIP_MULTI_H
 #define VAQHIP_MULTI_H
 #include "vaqhip.h"
@@ -99,6 +100,10 @@ struct vaqhip_multi {
   bool fast_q = false;            // a quantisation was given to every shard (vaqhip_multi_set_lut_quantization / learn)
   int opt_timing = 0;             // option "timing", as the shards hold it
   vaqhip_kmeans_timing km_last = {};  // the last vaqhip_multi_cluster_ti_kmeans
+  // the encode across the shards (vaqhip_multi_encode.cpp)
+  bool has_codes = false;             // a set or an add has given the shards rows (an empty matrix counts)
+  int64_t opt_encode_chunk = 0;       // option "encode_chunk_rows", 0 = the default
+  vaqhip_multi_encode_timing enc_last = {};
   vaqhip_multi_info last = {};
 };
 
@@ -198,6 +203,16 @@ template <class F> int each_shard(vaqhip_multi *mx, F &&call) {
 
 // vaqhip_multi_set_ti_clusters with mx->mu held (vaqhip_multi.cpp): the k-means ends with it
 int set_ti_clusters_on_shards(vaqhip_multi *mx, const float *clusters, int T, int seg_num);
+
+// the cut of N rows over G shards: shard g = rows [g * ceil(N / G), (g + 1) * ceil(N / G))
+inline void shard_cut(int64_t N, int G, int g, int64_t *lo, int64_t *n) {
+  const int64_t per = (N + G - 1) / G;
+  *lo = std::min<int64_t>(N, (int64_t)g * per);
+  *n = std::min<int64_t>(N, (int64_t)(g + 1) * per) - *lo;
+}
+
+// option "encode_chunk_rows" of vaqhip_multi_set_option (vaqhip_multi_encode.cpp): refuses before it locks
+int set_encode_chunk_rows(vaqhip_multi *mx, int64_t value);
 
 } // namespace vaqhost
 #endif

@@ -1,7 +1,7 @@
 // vaqhip_multi_refiner.h -- what the two host files of the multi-device refiner share: the shard, the handle, the set
 // of each form in flight (every buffer of a set is sized by it) and the two steps both forms take.  Buffers are
 // grouped by form and device.  Private to vaqhip_multi_refiner.cpp (life cycle, rows, options, the refine form, the
-// fused call) and vaqhip_multi_refiner_search.cpp (the exhaustive form).
+// fused call) and vaqhip_multi_refiner_search.cpp (the exhaustive form); vaqhip_multi_encode.cpp takes resident_rows().
 #ifndef VAQHIP_MULTI_REFINER_H
 #define VAQHIP_MULTI_REFINER_H
 #include "vaqhip_multi.h"
@@ -120,6 +120,15 @@ namespace vaqhost __attribute__((visibility("hidden"))) {
 
 // every stream idle: after a call that failed part-way, before anything it may still read is freed or reused
 void drain(vaqhip_multi_refiner *r);
+
+// Shard g's resident rows for the encode across the shards (vaqhip_multi_encode.cpp), which reads them in place on the
+// shard's device: n rows of D floats, the first with label first_label.  r->mu held; set_rows and add_rows copy
+// synchronously, so the rows are complete.
+struct ResidentRows { const float *rows; int64_t n, first_label; };
+inline ResidentRows resident_rows(const vaqhip_multi_refiner *r, int g) {
+  const RShard &s = r->sh[g];
+  return ResidentRows{s.rows.rows(), s.n, r->id_base + s.lo};
+}
 
 // The host form of a device call: sets of SET_QUERIES through the staging buffers on the first device (r->w); r->mu held
 template <class Call> int through_staging(vaqhip_multi_refiner *r, const float *queries, int nq, const int32_t *labels_in,

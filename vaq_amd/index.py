@@ -979,8 +979,50 @@ class VaqHipMulti:
         cb = np.ascontiguousarray(codes, dtype=np.uint16)
         _lib.check_multi(_lib.load().vaqhip_multi_add_codes_u16(self._h, _ptr(cb), cb.shape[0]))
 
+    def _train_rows(self, X) -> np.ndarray:
+        X = np.ascontiguousarray(X, dtype=np.float32)
+        if X.ndim != 2 or X.shape[1] != self.D:
+            raise _lib.VaqHipError(-1, f"rows {X.shape} are not n x {self.D}")
+        return X
+
+    def encode(self, X, projected: bool = True, id_base: int = 0, return_codes: bool = False):
+        """vaqhip_multi_encode_set_codes: VAQ::encode with every shard encoding the rows it will hold on its own
+        device -- the state VaqHip.encode on one index followed by set_codes(codes, id_base) leaves, bit for bit,
+        without the codes crossing to the host and back.  projected = False applies the eigenvectors first.
+        return_codes: the N x M uint16 matrix VaqHip.encode would have filled (else None)."""
+        X = self._train_rows(X)
+        codes = np.empty((X.shape[0], self.M), np.uint16) if return_codes else None
+        _lib.check_multi(_lib.load().vaqhip_multi_encode_set_codes(
+            self._h, _ptr(X), X.shape[0], 1 if projected else 0, int(id_base), _ptr(codes) if return_codes else None))
+        return codes
+
+    def encode_add(self, X, projected: bool = True, return_codes: bool = False):
+        """vaqhip_multi_encode_add_codes: encode + add_codes; the rows extend the last shard and are encoded on its
+        device.  ESTATE on an index that never received codes."""
+        X = self._train_rows(X)
+        codes = np.empty((X.shape[0], self.M), np.uint16) if return_codes else None
+        _lib.check_multi(_lib.load().vaqhip_multi_encode_add_codes(
+            self._h, _ptr(X), X.shape[0], 1 if projected else 0, _ptr(codes) if return_codes else None))
+        return codes
+
+    def encode_from_refiner(self, refiner: "VaqMultiRefiner", return_codes: bool = False):
+        """vaqhip_multi_encode_from_refiner: encode the RAW rows resident in a multi refiner on the same devices where
+        they lie (projected = False); N, id_base and the cut are the refiner's, so search_refine fits afterwards."""
+        codes = None
+        if return_codes:
+            codes = np.empty((refiner.info()["N"], self.M), np.uint16)
+        _lib.check_multi(_lib.load().vaqhip_multi_encode_from_refiner(self._h, refiner._h,
+                                                                      _ptr(codes) if return_codes else None))
+        return codes
+
+    def last_encode_timing(self) -> dict:
+        t = _lib.MultiEncodeTiming()
+        _lib.check_multi(_lib.load().vaqhip_multi_last_encode_timing(self._h, C.byref(t)))
+        return {f: getattr(t, f) for f, _ in _lib.MultiEncodeTiming._fields_}
+
     def set_option(self, key: str, value: int) -> None:
-        """vaqhip_multi_set_option: "exchange" (0 auto, 1 RCCL, 2 copies) and "exact_batch" belong to the
+        """vaqhip_multi_set_option: "exchange" (0 auto, 1 RCCL, 2 copies), "exact_batch" and "encode_chunk_rows" (rows
+        per upload chunk of encode(), 0 = 1 << 20) belong to the
         multi index, everything else is forwarded to every shard.  "exact_ties" = 1 holds across the
         shards: labels and distances equal VAQ::search's over ALL rows slot for slot -- every shard scans
         with k + 1, the merged list decides which queries have ties, and those are replayed through the
