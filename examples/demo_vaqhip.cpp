@@ -36,10 +36,13 @@
 //
 //   demo_vaqhip --lut-bits 8,6,5,...  --dataset base.fvecs [--dataset-size N] [--eigen e.f32] \
 //               --queries q.fvecs --timeseries-size 128 [--queries-size N] --k 100 [--exact-ties 1] \
-//               [--result out.csv] [--save-enc cb.bin] [--groundtruth gt.ivecs]
+//               [--result out.csv] [--save-enc cb.bin] [--groundtruth gt.ivecs] [--devices 0,1]
 //       builds a queryLUT index (BitVecEngine::binaryEncodingLUT from the bit allocation on: quantile
 //       codebooks and codes on the GPU; the PCA rotation and the bits per dimension are the caller's, as
-//       with the reference's hardcoded solutionX) over the first len(bits) PCA dimensions and queries it
+//       with the reference's hardcoded solutionX) over the first len(bits) PCA dimensions and queries it.
+//       With --devices the build is sharded: the fit runs over these GPUs (dimension d on device d % G, no GPU
+//       holds all rows), every shard encodes the rows it will hold, and the queries go to the multi index --
+//       the same codebook and answers
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -66,6 +69,7 @@ static int lutMain(std::map<std::string, std::string> &a) {
   BitVecEngineHip engine;
   engine.solutionX = intList(a["lut-bits"]);
   engine.exactTies = a.count("exact-ties") && std::atoi(a["exact-ties"].c_str()) != 0;
+  if (a.count("devices")) engine.setDevices(intList(a["devices"]));
   const int D = (int)engine.solutionX.size();
   const int N = std::atoi(a["timeseries-size"].c_str());
   if (D != N) throw Error(VAQHIP_EINVAL, "--lut-bits needs one entry per dimension (--timeseries-size)");
@@ -82,6 +86,14 @@ static int lutMain(std::map<std::string, std::string> &a) {
   engine.binaryEncodingLUT(dataset, codebook);
   std::cout << "== Encoding time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
             << " s (" << codebook.rows() << " rows x " << D << " dimensions, quantile codebooks + codes)" << std::endl;
+  if (engine.multiHandle()) {
+    vaqhip_multi_lut_fit_timing ft;
+    vaqhip_multi_encode_timing et;
+    if (vaqhip_multi_last_lut_fit_timing(&ft) == 0 && vaqhip_multi_last_encode_timing(engine.multiHandle(), &et) == 0)
+      std::cout << "   across " << ft.n_devices << " shards: fit " << ft.total_ms << " ms (columns " << ft.columns_ms
+                << ", copy " << ft.copy_ms << ", sort " << ft.sort_ms << ", quantiles " << ft.quantile_ms << ", means "
+                << ft.means_ms << "), encode + set " << et.total_ms << " ms" << std::endl;
+  }
   if (a.count("save-enc")) saveCodebook(codebook, a["save-enc"]);
   t0 = std::chrono::steady_clock::now();
   auto answers = engine.queryLUT(queries, k, codebook);

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 115
+#define VAQHIP_VERSION 116
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -594,8 +594,66 @@ typedef struct {
   int64_t rows;        /* rows encoded                                                            */
   int n_devices;
 } vaqhip_multi_encode_timing;
-/* figures of the last of the three calls above that ran (zeros before the first) */
+/* figures of the last of the three calls above, or of their _lut forms below, that ran (zeros before the first) */
 int vaqhip_multi_last_encode_timing(vaqhip_multi *mx, vaqhip_multi_encode_timing *out);
+/* Build a queryLUT index across the shards (BitVecEngine::binaryEncodingLUT on a VAQHIP_SUM_SEQUENTIAL multi index).
+ * Call order: the fit (below) -> vaqhip_multi_create with its centres -> vaqhip_multi_set_lut_quantiles -> one of the
+ * vaqhip_multi_encode_lut_* calls.
+ *   Q           vaqhip_multi_set_lut_quantiles is vaqhip_index_set_lut_quantiles on every shard.  It validates once on
+ *               the host with that call's checks (VAQHIP_EINVAL: shards that are not sequential-sum, D != M, bits > 8,
+ *               a NaN in Q) and then gives Q to shard after shard.  If a shard fails, the shards that already took Q
+ *               keep it and the error is returned: Q is idempotent state, a repeated call heals it.
+ *   encoders    the contract of "Encode across the shards" above with vaqhip_encode_lut (encodeToLUTCode: the boundary
+ *               scan, `<=` ties to the middle, then left; the unchecked projection) in the place of vaqhip_encode: the
+ *               index ends in exactly the state of vaqhip_encode_lut on one index over all rows followed by
+ *               vaqhip_multi_set_codes_u16 / _add_codes_u16, codes_out is that call's matrix; the same two phases, failure
+ *               semantics, option "encode_chunk_rows" and vaqhip_multi_last_encode_timing.  VAQHIP_ESTATE before
+ *               vaqhip_multi_set_lut_quantiles, and from _add_codes before any codes. */
+int vaqhip_multi_set_lut_quantiles(vaqhip_multi *mx, const float *quantiles /* [D][257] */);
+int vaqhip_multi_encode_lut_set_codes(vaqhip_multi *mx, const float *X_rowmajor, int64_t N, int projected,
+                                      int64_t id_base, uint16_t *codes_out /* N x M, may be NULL */);
+int vaqhip_multi_encode_lut_add_codes(vaqhip_multi *mx, const float *X_rowmajor, int64_t n_new, int projected,
+                                      uint16_t *codes_out /* n_new x M, may be NULL */);
+int vaqhip_multi_encode_lut_from_refiner(vaqhip_multi *mx, vaqhip_multi_refiner *r,
+                                         uint16_t *codes_out /* N x M, may be NULL */);
+/* The sharded quantile fit: vaqhip_lut_fit_quantiles's result, bit for bit, for ANY device list, with no device ever
+ * holding the n x D rows (nor a projected copy of its own slice).
+ *   scheme      dimension d is owned by device d % G.  In rounds of G consecutive dimensions every shard turns its
+ *               resident rows into the round's column slices of sortable keys (one kernel, the projection fused: one
+ *               fmaf chain per value, vaqhip_project's), sends slice j to owner j at the word offset of its first row
+ *               (peer copies; device-to-device where two shards name one GPU), and every owner runs the single fit's
+ *               column pipeline on its assembled n keys: radix sort, quantiles, ordered bucket sums.  A sorted column
+ *               does not depend on the order its values arrived in and everything behind the sort runs unchanged on
+ *               one device, so no chain and no tie question arises.  The last round may be partial; D < G leaves
+ *               owners idle.  The rows are re-read once per round, ceil(D / G) times in all.
+ *   host form   X is cut over the devices as vaqhip_multi_set_codes_u16 cuts rows; every shard uploads its slice once.
+ *   refiner     the RAW rows a multi refiner holds are read in place; n, D and the cut are the refiner's (a last shard
+ *               grown by add_rows and empty shards included); nothing is uploaded but eigvec.
+ *   workspace   per owner two key buffers of n words and rocprim's scratch; per shard G x n_g words and, in the host
+ *               form, its slice of n_g x D floats.
+ *   refusals    decided before any device is touched, with the single fit's codes: null pointers, n < 1, n >= 2^31,
+ *               D < 1 (VAQHIP_EINVAL), D > 4096 (VAQHIP_EUNSUPPORTED), bits outside 1..8; n_devices outside
+ *               1..VAQHIP_MAX_DEVICES, a null refiner (VAQHIP_EINVAL), a refiner without rows (VAQHIP_ESTATE).  A NaN or
+ *               infinite (projected) value on ANY shard: VAQHIP_EINVAL, both outputs untouched.
+ * Synchronous; a failing shard ends the call; the caller's current device is left as it was. */
+int vaqhip_multi_lut_fit_quantiles(int n_devices, const int *device_ids, const float *X_rowmajor, int64_t n, int D,
+                                   const int *bits, const float *eigvec_real_rowmajor /* D x D or NULL */,
+                                   float *centroids_out /* [D][256] */, float *quantiles_out /* [D][257] */);
+int vaqhip_multi_refiner_lut_fit_quantiles(vaqhip_multi_refiner *r, const int *bits,
+                                           const float *eigvec_real_rowmajor /* D x D or NULL */,
+                                           float *centroids_out /* [D][256] */, float *quantiles_out /* [D][257] */);
+typedef struct {
+  float total_ms;     /* wall time of the call                                                       */
+  float columns_ms;   /* per phase: the slowest device, device events, summed over the rounds --     */
+  float copy_ms;      /*   rows -> column keys; slices to their owners;                              */
+  float sort_ms;      /*   radix sort; quantiles and bucket ends; ordered bucket sums                */
+  float quantile_ms;
+  float means_ms;
+  int64_t rows;
+  int dims;
+  int n_devices;
+} vaqhip_multi_lut_fit_timing;
+int vaqhip_multi_last_lut_fit_timing(vaqhip_multi_lut_fit_timing *out);  /* the calling thread's last sharded fit */
 typedef struct {
   int n_devices;
   int exchange;              /* what the last search used: 0 none (one shard), 1 RCCL all-gather, 2 copies */

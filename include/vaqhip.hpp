@@ -632,20 +632,41 @@ public:
   BitVecEngineHip() = default;
   BitVecEngineHip(const BitVecEngineHip &) = delete;
   BitVecEngineHip &operator=(const BitVecEngineHip &) = delete;
-  ~BitVecEngineHip() { vaqhip_index_destroy(h_); }
-  void invalidate() { vaqhip_index_destroy(h_); h_ = nullptr; }
+  ~BitVecEngineHip() { invalidate(); }
+  void invalidate() {
+    vaqhip_index_destroy(h_);
+    h_ = nullptr;
+    vaqhip_multi_destroy(mh_);
+    mh_ = nullptr;
+  }
+  // Several devices (a device named several times: logical shards on that GPU): binaryEncodingLUT then fits over
+  // them (vaqhip_multi_lut_fit_quantiles), builds a VAQHIP_SUM_SEQUENTIAL multi index, gives it Q and encodes across
+  // the shards (vaqhip_multi_encode_lut_set_codes), and queryLUT answers from that multi index -- the same members
+  // and answers as on one device.  An empty list: back to mDevice.
+  void setDevices(const std::vector<int> &devices) {
+    invalidate();
+    mDevices = devices;
+  }
+  vaqhip_multi *multiHandle() const { return mh_; }
 
   // queries: any row-major float matrix with data()/rows()/cols() (the reference
   // takes a column-major Eigen::MatrixXf: pass its transpose's storage or a RowMatrixF)
   template <class Mat, class Codebook>
   std::vector<std::vector<IdxDistPairFloat>> queryLUT(const Mat &queries, const int k, const Codebook &codebook) {
     ensureIndex();
-    check(vaqhip_set_option(h_, "exact_ties", exactTies ? 1 : 0));
-    check(vaqhip_index_set_codes_u16(h_, codebook.data(), (int64_t)codebook.rows(), 0));
     const int nq = (int)queries.rows();
     std::vector<int> lab((size_t)nq * k);
     std::vector<float> dis((size_t)nq * k);
-    check(vaqhip_search(h_, queries.data(), nq, k, lab.data(), dis.data()));
+    if (mh_) {
+      checkMulti(vaqhip_multi_set_option(mh_, "exact_ties", exactTies ? 1 : 0));
+      // (as on one device: the codebook handed in is the one searched, whatever binaryEncodingLUT left on the shards)
+      checkMulti(vaqhip_multi_set_codes_u16(mh_, codebook.data(), (int64_t)codebook.rows(), 0));
+      checkMulti(vaqhip_multi_search(mh_, queries.data(), nq, k, 0, lab.data(), dis.data()));
+    } else {
+      check(vaqhip_set_option(h_, "exact_ties", exactTies ? 1 : 0));
+      check(vaqhip_index_set_codes_u16(h_, codebook.data(), (int64_t)codebook.rows(), 0));
+      check(vaqhip_search(h_, queries.data(), nq, k, lab.data(), dis.data()));
+    }
     std::vector<std::vector<IdxDistPairFloat>> answers(nq);  // min(k, rows) pairs each, as the reference's
     for (int q = 0; q < nq; q++)
       for (int i = 0; i < k && lab[(size_t)q * k + i] >= 0; i++)
@@ -666,20 +687,33 @@ public:
     if ((int)XTrain.cols() != nd) throw Error(VAQHIP_EINVAL, "vaqhip: XTrain must have one column per entry of solutionX");
     centroidRows = 256;
     std::vector<float> cent((size_t)centroidRows * nd), q((size_t)257 * nd);
-    check(vaqhip_lut_fit_quantiles(mDevice, XTrain.data(), (int64_t)XTrain.rows(), nd, solutionX.data(),
-                                   eigenVectors.rows() ? eigenVectors.data() : nullptr, cent.data(), q.data()));
+    const float *eig = eigenVectors.rows() ? eigenVectors.data() : nullptr;
+    if (mDevices.empty())
+      check(vaqhip_lut_fit_quantiles(mDevice, XTrain.data(), (int64_t)XTrain.rows(), nd, solutionX.data(), eig,
+                                     cent.data(), q.data()));
+    else
+      checkMulti(vaqhip_multi_lut_fit_quantiles((int)mDevices.size(), mDevices.data(), XTrain.data(),
+                                                (int64_t)XTrain.rows(), nd, solutionX.data(), eig, cent.data(), q.data()));
     centroidsMat.swap(cent);
     quantiles.swap(q);
     invalidate();
     ensureIndex();
-    check(vaqhip_index_set_lut_quantiles(h_, quantiles.data()));
     codebookOut = CodebookType((size_t)XTrain.rows(), (size_t)nd);
+    if (mh_) {
+      checkMulti(vaqhip_multi_set_lut_quantiles(mh_, quantiles.data()));
+      checkMulti(vaqhip_multi_encode_lut_set_codes(mh_, XTrain.data(), (int64_t)XTrain.rows(), 0, 0, codebookOut.data()));
+      return;
+    }
+    check(vaqhip_index_set_lut_quantiles(h_, quantiles.data()));
     check(vaqhip_encode_lut(h_, XTrain.data(), (int64_t)XTrain.rows(), 0, codebookOut.data()));
   }
 
 private:
+  static void checkMulti(int rc) {
+    if (rc < 0) throw Error(rc, std::string("vaqhip: ") + vaqhip_multi_last_error());
+  }
   void ensureIndex() {
-    if (h_) return;
+    if (h_ || mh_) return;
     const int nd = (int)solutionX.size();
     std::vector<std::vector<float>> cols(nd);
     std::vector<const float *> cp(nd);
@@ -688,11 +722,17 @@ private:
                      centroidsMat.begin() + (size_t)d * centroidRows + ((size_t)1 << solutionX[d]));
       cp[d] = cols[d].data();
     }
-    check(vaqhip_index_create_ex(&h_, nd, nd, solutionX.data(), cp.data(),
-                                 eigenVectors.rows() ? eigenVectors.data() : nullptr, mDevice,
-                                 VAQHIP_SUM_SEQUENTIAL));
+    const float *eig = eigenVectors.rows() ? eigenVectors.data() : nullptr;
+    if (!mDevices.empty()) {
+      checkMulti(vaqhip_multi_create(&mh_, nd, nd, solutionX.data(), cp.data(), eig, (int)mDevices.size(), mDevices.data(),
+                                     VAQHIP_SUM_SEQUENTIAL));
+      return;
+    }
+    check(vaqhip_index_create_ex(&h_, nd, nd, solutionX.data(), cp.data(), eig, mDevice, VAQHIP_SUM_SEQUENTIAL));
   }
   vaqhip_index *h_ = nullptr;
+  vaqhip_multi *mh_ = nullptr;
+  std::vector<int> mDevices;
 };
 
 } // namespace vaqhip

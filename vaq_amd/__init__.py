@@ -7,10 +7,13 @@ Product surface:
   vaq_amd.VaqHipFast          the same with the FAST search method (uint8 tables, 4-bit codes)
   vaq_amd.VaqRefiner          VAQ::refine over raw rows resident on the device, reference-exact
   vaq_amd.VaqMultiRefiner     the same over raw rows sharded across several GPUs
+  vaq_amd.lut_fit_quantiles_multi  binaryEncodingLUT's quantile codebooks with the rows cut over several GPUs
 There is no CPU path: importing works anywhere, but every compute call needs
 the HIP library and a GPU and raises otherwise.
 """
 from ._lib import VaqHipError, lib_path, load  # noqa: F401
 from .index import LabelDistVec, NNMethod, VaqHip, VaqHipFast, VaqHipMulti, VaqMultiRefiner, VaqRefiner  # noqa: F401
+from .index import last_lut_fit_multi_timing, lut_fit_quantiles_multi  # noqa: F401
 
-__all__ = ["VaqHip", "VaqHipFast", "VaqHipMulti", "VaqRefiner", "VaqMultiRefiner", "NNMethod", "LabelDistVec", "VaqHipError", "load", "lib_path"]
+__all__ = ["VaqHip", "VaqHipFast", "VaqHipMulti", "VaqRefiner", "VaqMultiRefiner", "NNMethod", "LabelDistVec", "VaqHipError", "load", "lib_path",
+           "lut_fit_quantiles_multi", "last_lut_fit_multi_timing"]

@@ -39,6 +39,9 @@ SYMBOLS = [
     "vaqhip_multi_get_info", "vaqhip_multi_shard", "vaqhip_multi_last_error",
     "vaqhip_multi_encode_set_codes", "vaqhip_multi_encode_add_codes", "vaqhip_multi_encode_from_refiner",
     "vaqhip_multi_last_encode_timing",
+    "vaqhip_multi_set_lut_quantiles", "vaqhip_multi_encode_lut_set_codes", "vaqhip_multi_encode_lut_add_codes",
+    "vaqhip_multi_encode_lut_from_refiner",
+    "vaqhip_multi_lut_fit_quantiles", "vaqhip_multi_refiner_lut_fit_quantiles", "vaqhip_multi_last_lut_fit_timing",
     "vaqhip_multi_refiner_create", "vaqhip_multi_refiner_destroy", "vaqhip_multi_refiner_set_rows",
     "vaqhip_multi_refiner_add_rows", "vaqhip_multi_refiner_set_option", "vaqhip_multi_refiner_refine",
     "vaqhip_multi_refiner_refine_device", "vaqhip_multi_search_refine", "vaqhip_multi_search_refine_device",
@@ -102,6 +105,12 @@ class MultiRefinerSearchTiming(C.Structure):
 
 class MultiEncodeTiming(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("encode_ms", C.c_float), ("set_codes_ms", C.c_float), ("rows", C.c_int64),
+                ("n_devices", C.c_int)]
+
+
+class MultiLutFitTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("columns_ms", C.c_float), ("copy_ms", C.c_float), ("sort_ms", C.c_float),
+                ("quantile_ms", C.c_float), ("means_ms", C.c_float), ("rows", C.c_int64), ("dims", C.c_int),
                 ("n_devices", C.c_int)]
 
 
@@ -226,6 +235,13 @@ def load():
     L.vaqhip_multi_encode_add_codes.argtypes = [vp, vp, i64, i32, vp]
     L.vaqhip_multi_encode_from_refiner.argtypes = [vp, vp, vp]
     L.vaqhip_multi_last_encode_timing.argtypes = [vp, C.POINTER(MultiEncodeTiming)]
+    L.vaqhip_multi_set_lut_quantiles.argtypes = [vp, vp]
+    L.vaqhip_multi_encode_lut_set_codes.argtypes = [vp, vp, i64, i32, i64, vp]
+    L.vaqhip_multi_encode_lut_add_codes.argtypes = [vp, vp, i64, i32, vp]
+    L.vaqhip_multi_encode_lut_from_refiner.argtypes = [vp, vp, vp]
+    L.vaqhip_multi_lut_fit_quantiles.argtypes = [i32, C.POINTER(i32), vp, i64, i32, C.POINTER(i32), vp, vp, vp]
+    L.vaqhip_multi_refiner_lut_fit_quantiles.argtypes = [vp, C.POINTER(i32), vp, vp, vp]
+    L.vaqhip_multi_last_lut_fit_timing.argtypes = [C.POINTER(MultiLutFitTiming)]
     L.vaqhip_multi_refiner_create.argtypes = [C.POINTER(vp), i32, i32, C.POINTER(i32)]
     L.vaqhip_multi_refiner_destroy.argtypes = [vp]
     L.vaqhip_multi_refiner_destroy.restype = None

@@ -4,6 +4,8 @@
 //
 // Fit, one column at a time (workspace: two key buffers of n words and rocprim's scratch):
 //   lutfit_extract_kernel     column d of the row-major rows -> sortable keys; flags non-finite values
+//   lutfit_project_columns_kernel  the sharded fit's form of it: up to 16 columns of a shard's RAW rows at once,
+//                             the projection fused (no projected copy of the rows exists there)
 //   rocprim::radix_sort_keys  the column ascending
 //   lutfit_quantiles_kernel   Q[0 .. N] and the bucket ends (one workgroup: <= 257 values)
 //   lutfit_means_kernel       one workgroup per bucket: the bucket's values are staged through LDS in
@@ -13,6 +15,7 @@
 // dimensions sit in LDS, packed (2N + 1 floats per dimension).
 #include "vaq_kernels.h"
 #include "vaq_lutfit.h"
+#include "vaq_lutfit_dev.h"
 #include "vaqhip_dev.h"
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -33,6 +36,67 @@ __global__ __launch_bounds__(256) void lutfit_extract_kernel(const float *__rest
     const float x = Xp[r * D + d];
     any_bad = any_bad || !is_finite(x);
     keys[r] = float_to_key(x);
+  }
+  if (any_bad) atomicOr(bad, 1);
+}
+
+// ---- rows -> column keys, projection fused (the sharded fit, vaqhip_multi_lutfit.cpp) ----
+// A workgroup takes PC_ROWS rows at a time, lane = row, so each of the W column stores of a wave is 64 consecutive
+// words.  The rows pass through LDS in tiles of PC_JT inner indices, loaded coalesced (32 consecutive floats of a
+// row per half-wave) and read back one row per lane; the row stride PC_STRIDE = 33 words is odd, so the 32 lanes of
+// a half-wave hit 32 different banks both ways (a stride of D = 128 would put them all on one).  A thread keeps W
+// accumulators; E[j][d0 + w] is the same for the whole wave and comes in as scalar loads.  Each y is ONE fmaf chain
+// over j ascending from acc = 0.0f: project_kernel's / project_tile_kernel's value bit for bit (vaq_kernels.hip).
+// 16 accumulators, the tile value and the addresses stay far below the 128 VGPRs at which a SIMD still holds four
+// waves; LDS (33 KB) allows four workgroups per CU.  Rows and offsets are 64-bit: a shard of 125M x 128 has 1.6e10
+// elements.
+constexpr int PC_ROWS = 256, PC_JT = 32, PC_STRIDE = PC_JT + 1, PC_MAX_W = 16;
+
+template <int W>
+__global__ __launch_bounds__(PC_ROWS) void lutfit_project_columns_kernel(const float *__restrict__ X, int64_t n, int D,
+                                                                         const float *__restrict__ E, int d0,
+                                                                         uint32_t *__restrict__ keys,
+                                                                         int *__restrict__ bad) {
+  __shared__ float tile[PC_ROWS * PC_STRIDE];
+  const int tid = threadIdx.x;
+  const int c = tid & (PC_JT - 1), r8 = tid / PC_JT;
+  bool any_bad = false;
+  for (int64_t row0 = (int64_t)blockIdx.x * PC_ROWS; row0 < n; row0 += (int64_t)gridDim.x * PC_ROWS) {
+    const int64_t row = row0 + tid;
+    float acc[W];
+#pragma unroll
+    for (int w = 0; w < W; w++) acc[w] = 0.0f;
+    if (!E) {  // a transposing extract: the row's own values
+      if (row < n) {
+#pragma unroll
+        for (int w = 0; w < W; w++) acc[w] = X[row * D + d0 + w];
+      }
+    } else {
+      for (int j0 = 0; j0 < D; j0 += PC_JT) {
+        __syncthreads();  // (the tile before has been read)
+#pragma unroll 8
+        for (int i = 0; i < PC_JT; i++) {  // (PC_ROWS x PC_JT values by PC_ROWS threads)
+          const int r = i * (PC_ROWS / PC_JT) + r8;
+          const int64_t src = row0 + r;
+          tile[r * PC_STRIDE + c] = (src < n && j0 + c < D) ? X[src * D + j0 + c] : 0.0f;
+        }
+        __syncthreads();
+        const int jn = D - j0 < PC_JT ? D - j0 : PC_JT;
+        const float *e = E + (size_t)j0 * D + d0;
+        for (int jj = 0; jj < jn; jj++, e += D) {
+          const float x = tile[tid * PC_STRIDE + jj];
+#pragma unroll
+          for (int w = 0; w < W; w++) acc[w] = __builtin_fmaf(x, e[w], acc[w]);
+        }
+      }
+    }
+    if (row < n) {
+#pragma unroll
+      for (int w = 0; w < W; w++) {
+        any_bad = any_bad || !is_finite(acc[w]);
+        keys[(int64_t)w * n + row] = float_to_key(acc[w]);
+      }
+    }
   }
   if (any_bad) atomicOr(bad, 1);
 }
@@ -162,20 +226,59 @@ hipError_t launch_lut_encode(const float *Xp, int64_t n, int D, const SubDesc *h
   return hipSuccess;
 }
 
+hipError_t launch_lutfit_project_columns(const float *X, int64_t n, int D, const float *E, int d0, int W, uint32_t *keys,
+                                         int *d_bad, hipStream_t st) {
+  if (n == 0 || W == 0) return hipSuccess;
+  if (W < 0 || W > PC_MAX_W || d0 < 0 || d0 + W > D) return hipErrorInvalidValue;
+  const dim3 grid((unsigned)std::min<int64_t>((n + PC_ROWS - 1) / PC_ROWS, 4096));
+  switch (W) {
+#define PC_CASE(w)                                                                                                   \
+  case w:                                                                                                            \
+    hipLaunchKernelGGL((lutfit_project_columns_kernel<w>), grid, dim3(PC_ROWS), 0, st, X, n, D, E, d0, keys, d_bad); \
+    break;
+    PC_CASE(1) PC_CASE(2) PC_CASE(3) PC_CASE(4) PC_CASE(5) PC_CASE(6) PC_CASE(7) PC_CASE(8)
+    PC_CASE(9) PC_CASE(10) PC_CASE(11) PC_CASE(12) PC_CASE(13) PC_CASE(14) PC_CASE(15) PC_CASE(16)
+#undef PC_CASE
+  }
+  return hipGetLastError();
+}
+
+hipError_t LutFitColumnWork::ensure(int64_t n, hipStream_t st) {
+  const size_t key_bytes = (size_t)n * sizeof(uint32_t);
+  LF_TRY(keys.ensure(key_bytes));
+  LF_TRY(sorted.ensure(key_bytes));
+  LF_TRY(ends.ensure((MAX_CENT + 1) * sizeof(int64_t)));
+  temp_bytes = 0;
+  LF_TRY(rocprim::radix_sort_keys(nullptr, temp_bytes, keys.as<uint32_t>(), sorted.as<uint32_t>(), (size_t)n, 0u, 32u,
+                                  st));
+  return temp.ensure(temp_bytes ? temp_bytes : 16);
+}
+
+hipError_t lut_fit_column_from_keys(LutFitColumnWork &w, int64_t n, int bits, float *d_q, float *d_cent, hipEvent_t *e,
+                                    hipStream_t st) {
+  const int N = 1 << bits;
+  if (e) LF_TRY(hipEventRecord(e[0], st));
+  LF_TRY(rocprim::radix_sort_keys(w.temp.p, w.temp_bytes, w.keys.as<uint32_t>(), w.sorted.as<uint32_t>(), (size_t)n, 0u,
+                                  32u, st));
+  if (e) LF_TRY(hipEventRecord(e[1], st));
+  hipLaunchKernelGGL(lutfit_quantiles_kernel, dim3(1), dim3(256), 0, st, w.sorted.as<uint32_t>(), n, N, d_q,
+                     w.ends.as<int64_t>());
+  LF_TRY(hipGetLastError());
+  if (e) LF_TRY(hipEventRecord(e[2], st));
+  hipLaunchKernelGGL(lutfit_means_kernel, dim3((unsigned)N), dim3(MEANS_THREADS), 0, st, w.sorted.as<uint32_t>(),
+                     w.ends.as<int64_t>(), d_q, d_cent);
+  LF_TRY(hipGetLastError());
+  if (e) LF_TRY(hipEventRecord(e[3], st));
+  return hipSuccess;
+}
+
 // d_cent_out [D][256] (= centroidsMat, 256 x D column-major), d_q_out [D][257], *d_bad: set when a value is not
 // finite (zeroed here).  Enqueues on `st`; the scratch is freed on return, so the stream is synchronised first.
 // phase_ms (optional) [4]: extract, sort, quantiles, means, summed over the columns (device events).
 hipError_t lut_fit_columns(const float *d_Xp, int64_t n, int D, const int *bits, float *d_cent_out, float *d_q_out,
                            int *d_bad, float *phase_ms, hipStream_t st) {
-  vaqhost::DevBuf b_keys, b_sorted, b_temp, b_ends;
-  const size_t key_bytes = (size_t)n * sizeof(uint32_t);
-  LF_TRY(b_keys.ensure(key_bytes));
-  LF_TRY(b_sorted.ensure(key_bytes));
-  LF_TRY(b_ends.ensure((MAX_CENT + 1) * sizeof(int64_t)));
-  size_t temp_bytes = 0;
-  LF_TRY(rocprim::radix_sort_keys(nullptr, temp_bytes, b_keys.as<uint32_t>(), b_sorted.as<uint32_t>(), (size_t)n, 0u,
-                                  32u, st));
-  LF_TRY(b_temp.ensure(temp_bytes ? temp_bytes : 16));
+  LutFitColumnWork w;
+  LF_TRY(w.ensure(n, st));
   LF_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), st));
   LF_TRY(hipMemsetAsync(d_cent_out, 0, (size_t)D * MAX_CENT * sizeof(float), st));
   std::vector<hipEvent_t> ev;
@@ -190,25 +293,14 @@ hipError_t lut_fit_columns(const float *d_Xp, int64_t n, int D, const int *bits,
   }
   const unsigned ex_grid = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
   for (int d = 0; d < D; d++) {
-    const int N = 1 << bits[d];
     hipEvent_t *e = phase_ms ? ev.data() + (size_t)d * 5 : nullptr;
     if (e) LF_TRY(hipEventRecord(e[0], st));
-    hipLaunchKernelGGL(lutfit_extract_kernel, dim3(ex_grid), dim3(256), 0, st, d_Xp, n, D, d, b_keys.as<uint32_t>(),
+    hipLaunchKernelGGL(lutfit_extract_kernel, dim3(ex_grid), dim3(256), 0, st, d_Xp, n, D, d, w.keys.as<uint32_t>(),
                        d_bad);
     LF_TRY(hipGetLastError());
-    if (e) LF_TRY(hipEventRecord(e[1], st));
-    LF_TRY(rocprim::radix_sort_keys(b_temp.p, temp_bytes, b_keys.as<uint32_t>(), b_sorted.as<uint32_t>(), (size_t)n,
-                                    0u, 32u, st));
-    if (e) LF_TRY(hipEventRecord(e[2], st));
-    float *q = d_q_out + (size_t)d * MAX_Q;
-    hipLaunchKernelGGL(lutfit_quantiles_kernel, dim3(1), dim3(256), 0, st, b_sorted.as<uint32_t>(), n, N, q,
-                       b_ends.as<int64_t>());
-    LF_TRY(hipGetLastError());
-    if (e) LF_TRY(hipEventRecord(e[3], st));
-    hipLaunchKernelGGL(lutfit_means_kernel, dim3((unsigned)N), dim3(MEANS_THREADS), 0, st, b_sorted.as<uint32_t>(),
-                       b_ends.as<int64_t>(), q, d_cent_out + (size_t)d * MAX_CENT);
-    LF_TRY(hipGetLastError());
-    if (e) LF_TRY(hipEventRecord(e[4], st));
+    // (e[1], the end of the extract, is the column fit's first event)
+    LF_TRY(lut_fit_column_from_keys(w, n, bits[d], d_q_out + (size_t)d * MAX_Q, d_cent_out + (size_t)d * MAX_CENT,
+                                    e ? e + 1 : nullptr, st));
   }
   LF_TRY(hipStreamSynchronize(st));
   if (phase_ms) {

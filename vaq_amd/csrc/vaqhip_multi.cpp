@@ -60,6 +60,7 @@ int vaqhip_multi_create(vaqhip_multi **out, int D, int M, const int *bits, const
       vaqhip_multi_destroy(mx);
       return rc;
     }
+    if (g == 0) mx->bits.assign(bits, bits + M);  // (the first shard's creation has checked bits and M)
     // ("exact_ties" with TI is a property of ONE index: a shard among several keeps the default tie contract)
     if (n_devices > 1) vaqhip_internal_set_sharded(s.ix, 1);
     bool ok = hipSetDevice(s.device) == hipSuccess && hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess &&
@@ -159,6 +160,26 @@ int vaqhip_multi_set_lut_quantization(vaqhip_multi *mx, const float *offsets, co
   if (const int rc = each_shard(mx, [&](vaqhip_index *ix) { return vaqhip_index_set_lut_quantization(ix, offsets, scale); }))
     return rc;
   mx->fast_q = true;
+  return VAQHIP_OK;
+}
+
+int vaqhip_multi_set_lut_quantiles(vaqhip_multi *mx, const float *quantiles) {
+  if (!mx || !quantiles) return mfail(VAQHIP_EINVAL, "null pointer");
+  std::lock_guard<std::mutex> lk(mx->mu);
+  // vaqhip_index_set_lut_quantiles's checks, once, on the host: every shard was created from the same arguments
+  constexpr int MAX_Q = 257;
+  if (!mx->seq) return mfail(VAQHIP_EINVAL, "quantiles belong to a VAQHIP_SUM_SEQUENTIAL index (BitVecEngine's scalar quantisers)");
+  if (mx->D != mx->M) return mfail(VAQHIP_EINVAL, "D=%d != M=%d: the engine has one quantiser per dimension", mx->D, mx->M);
+  for (int s = 0; s < mx->M; s++) {
+    if (mx->bits[(size_t)s] > 8) return mfail(VAQHIP_EINVAL, "bits[%d]=%d > 8: Q has at most 257 entries", s, mx->bits[(size_t)s]);
+    for (int j = 0; j <= (1 << mx->bits[(size_t)s]); j++)
+      if (quantiles[(size_t)s * MAX_Q + j] != quantiles[(size_t)s * MAX_Q + j])
+        return mfail(VAQHIP_EINVAL, "quantiles[%d][%d] is NaN", s, j);
+  }
+  DeviceGuard keep(DeviceGuard::restore_only);
+  // shard after shard: one that fails leaves those before it with Q (idempotent state: a repeated call heals it)
+  if (const int rc = each_shard(mx, [&](vaqhip_index *ix) { return vaqhip_index_set_lut_quantiles(ix, quantiles); })) return rc;
+  mx->lut_q = true;
   return VAQHIP_OK;
 }
 

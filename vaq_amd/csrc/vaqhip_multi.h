@@ -1,7 +1,8 @@
 // vaqhip_multi.h -- what the host files of the multi-device index share: the shard, the index with the
 // geometry of the search in flight, the error hand-over, the grow path of a phase's buffers and the two loops over
 // shards.  Private to vaqhip_multi.cpp (life cycle, codes, setters), vaqhip_multi_search.cpp (the search),
-// vaqhip_multi_kmeans.cpp (the k-means of clusterTI), vaqhip_multi_encode.cpp (the encode across the shards) and,
+// vaqhip_multi_kmeans.cpp (the k-means of clusterTI), vaqhip_multi_encode.cpp (the encode across the shards),
+// vaqhip_multi_lutfit.cpp (the sharded quantile fit: the error hand-over and on_shards over a call of its own) and,
 // through vaqhip_multi_refiner.h, the refiner over sharded raw rows (vaqhip_multi_refiner.cpp,
 // vaqhip_multi_refiner_search.cpp), which takes the error hand-over, the grow path and on_shards from here; they see a
 // shard's index through include/vaqhip.h and vaqhip_internal.h only.
@@ -52,6 +53,7 @@ struct vaqhip_multi {
   __attribute__((visibility("hidden"))) ~vaqhip_multi() = default;
   int D = 0, M = 0, G = 0;
   bool seq = false;  // VAQHIP_SUM_SEQUENTIAL: every shard is a queryLUT index
+  std::vector<int> bits;  // [M], as every shard was created with
   std::vector<vaqhost::Shard> sh;
   bool distinct = true;  // no device named twice
   int exchange = vaqhost::EX_AUTO;
@@ -104,6 +106,7 @@ struct vaqhip_multi {
   bool has_codes = false;             // a set or an add has given the shards rows (an empty matrix counts)
   int64_t opt_encode_chunk = 0;       // option "encode_chunk_rows", 0 = the default
   vaqhip_multi_encode_timing enc_last = {};
+  bool lut_q = false;                 // vaqhip_multi_set_lut_quantiles has given every shard Q (the _lut encoders need it)
   vaqhip_multi_info last = {};
 };
 

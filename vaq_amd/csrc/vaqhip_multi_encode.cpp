@@ -6,6 +6,8 @@
 // its index the same n_g x M matrix that call would have uploaded: the index ends in the same state, bit for bit,
 // without a chain, an exchange or a tie question.  No kernel of its own: the shard's vaqhip_encode_device (project,
 // encode) and vaqhip_index_set_codes_u16_device / _add_codes_u16_device (sort, pack, merge).
+// The vaqhip_multi_encode_lut_* calls are the same calls with the engine's rule (vaqhip_encode_lut_device,
+// encodeToLUTCode) in the place of VAQ::encode's: one flag on the call, everything else shared.
 //
 // Two phases, each on every shard's worker at once (on_shards):
 //   1 encode  the rows -- uploaded slice by slice in chunks (host form), or read where a multi refiner holds them
@@ -40,6 +42,7 @@ struct EncodePart {
 struct EncodeCall {
   const float *X = nullptr;  // host form: the call's matrix
   int projected = 0;
+  bool lut = false;          // the engine's encoder (vaqhip_encode_lut_device) in the place of vaqhip_encode_device
   int64_t id_base = 0;       // set: the label of the matrix's first row
   bool append = false;
   uint16_t *codes_out = nullptr;
@@ -69,7 +72,9 @@ int encode_part(vaqhip_multi *mx, const EncodeCall &c, EncodePart &p, Shard &s) 
     if (c.X)  // (one chunk buffer: the stream orders this copy behind the encode of the chunk before)
       MHIP(hipMemcpyAsync(p.chunk.p, c.X + (size_t)(p.lo + r) * D, (size_t)m * D * sizeof(float), hipMemcpyHostToDevice, s.stream));
     else d_x = p.d_rows + (size_t)r * D;
-    MIX(vaqhip_encode_device(s.ix, d_x, m, c.projected, p.codes.as<uint16_t>() + (size_t)r * M, s.stream));
+    uint16_t *d_codes = p.codes.as<uint16_t>() + (size_t)r * M;
+    if (c.lut) MIX(vaqhip_encode_lut_device(s.ix, d_x, m, c.projected, d_codes, s.stream));
+    else MIX(vaqhip_encode_device(s.ix, d_x, m, c.projected, d_codes, s.stream));
   }
   MHIP(hipEventRecord(p.t[1], s.stream));
   MHIP(hipStreamSynchronize(s.stream));
@@ -142,14 +147,22 @@ int vaqhost::set_encode_chunk_rows(vaqhip_multi *mx, int64_t value) {
   return VAQHIP_OK;
 }
 
-extern "C" {
+namespace {
 
-int vaqhip_multi_encode_set_codes(vaqhip_multi *mx, const float *X, int64_t N, int projected, int64_t id_base,
-                                  uint16_t *codes_out) {
+// the engine's encoder needs Q on every shard (mx->mu held)
+int check_lut(const vaqhip_multi *mx, bool lut) {
+  if (lut && !mx->lut_q) return mfail(VAQHIP_ESTATE, "vaqhip_multi_encode_lut_* needs vaqhip_multi_set_lut_quantiles first");
+  return VAQHIP_OK;
+}
+
+int encode_set_codes(vaqhip_multi *mx, const float *X, int64_t N, int projected, int64_t id_base, uint16_t *codes_out,
+                     bool lut) {
   if (!mx) return mfail(VAQHIP_EINVAL, "multi index is null");
   if (N < 0 || (N > 0 && !X) || id_base < 0) return mfail(VAQHIP_EINVAL, "bad rows/N/id_base");
   std::lock_guard<std::mutex> lk(mx->mu);
+  if (const int rc = check_lut(mx, lut)) return rc;
   EncodeCall c;
+  c.lut = lut;
   c.X = X;
   c.projected = projected;
   c.id_base = id_base;
@@ -165,15 +178,17 @@ int vaqhip_multi_encode_set_codes(vaqhip_multi *mx, const float *X, int64_t N, i
   return VAQHIP_OK;
 }
 
-int vaqhip_multi_encode_add_codes(vaqhip_multi *mx, const float *X, int64_t n_new, int projected, uint16_t *codes_out) {
+int encode_add_codes(vaqhip_multi *mx, const float *X, int64_t n_new, int projected, uint16_t *codes_out, bool lut) {
   if (!mx) return mfail(VAQHIP_EINVAL, "multi index is null");
   if (n_new < 0 || (n_new > 0 && !X)) return mfail(VAQHIP_EINVAL, "bad rows/N");
   std::lock_guard<std::mutex> lk(mx->mu);
+  if (const int rc = check_lut(mx, lut)) return rc;
   if (!mx->has_codes) return mfail(VAQHIP_ESTATE, "no codes yet: vaqhip_multi_encode_set_codes (or set_codes_u16) first");
   // the new rows continue the numbering: they extend the LAST shard (vaqhip_multi_add_codes_u16) and are encoded there
   Shard &last = mx->sh[mx->G - 1];
   if (const int rc = check_labels(last.n + n_new, mx->id_base + last.lo)) return rc;
   EncodeCall c;
+  c.lut = lut;
   c.X = X;
   c.projected = projected;
   c.append = true;
@@ -186,17 +201,19 @@ int vaqhip_multi_encode_add_codes(vaqhip_multi *mx, const float *X, int64_t n_ne
   return VAQHIP_OK;
 }
 
-int vaqhip_multi_encode_from_refiner(vaqhip_multi *mx, vaqhip_multi_refiner *r, uint16_t *codes_out) {
+int encode_from_refiner(vaqhip_multi *mx, vaqhip_multi_refiner *r, uint16_t *codes_out, bool lut) {
   if (!mx) return mfail(VAQHIP_EINVAL, "multi index is null");
   if (!r) return mfail(VAQHIP_EINVAL, "multi refiner is null");
   std::lock_guard<std::mutex> lr(r->mu);  // (the order of vaqhip_multi_search_refine: the refiner, then the index)
   std::lock_guard<std::mutex> lk(mx->mu);
+  if (const int rc = check_lut(mx, lut)) return rc;
   if (mx->D != r->D) return mfail(VAQHIP_EINVAL, "the index has D=%d, the refiner D=%d", mx->D, r->D);
   bool same = mx->G == r->G;
   for (int g = 0; same && g < r->G; g++) same = mx->sh[g].device == r->sh[g].device;
   if (!same) return mfail(VAQHIP_EINVAL, "the index and the refiner name different device lists");
   if (r->N == 0) return mfail(VAQHIP_ESTATE, "the refiner holds no rows: vaqhip_multi_refiner_set_rows first");
   EncodeCall c;
+  c.lut = lut;
   c.id_base = r->id_base;
   c.codes_out = codes_out;
   c.part.resize((size_t)mx->G);
@@ -211,6 +228,32 @@ int vaqhip_multi_encode_from_refiner(vaqhip_multi *mx, vaqhip_multi_refiner *r, 
   mx->N = r->N;
   mx->id_base = r->id_base;
   return VAQHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vaqhip_multi_encode_set_codes(vaqhip_multi *mx, const float *X, int64_t N, int projected, int64_t id_base,
+                                  uint16_t *codes_out) {
+  return encode_set_codes(mx, X, N, projected, id_base, codes_out, false);
+}
+int vaqhip_multi_encode_add_codes(vaqhip_multi *mx, const float *X, int64_t n_new, int projected, uint16_t *codes_out) {
+  return encode_add_codes(mx, X, n_new, projected, codes_out, false);
+}
+int vaqhip_multi_encode_from_refiner(vaqhip_multi *mx, vaqhip_multi_refiner *r, uint16_t *codes_out) {
+  return encode_from_refiner(mx, r, codes_out, false);
+}
+int vaqhip_multi_encode_lut_set_codes(vaqhip_multi *mx, const float *X, int64_t N, int projected, int64_t id_base,
+                                      uint16_t *codes_out) {
+  return encode_set_codes(mx, X, N, projected, id_base, codes_out, true);
+}
+int vaqhip_multi_encode_lut_add_codes(vaqhip_multi *mx, const float *X, int64_t n_new, int projected,
+                                      uint16_t *codes_out) {
+  return encode_add_codes(mx, X, n_new, projected, codes_out, true);
+}
+int vaqhip_multi_encode_lut_from_refiner(vaqhip_multi *mx, vaqhip_multi_refiner *r, uint16_t *codes_out) {
+  return encode_from_refiner(mx, r, codes_out, true);
 }
 
 int vaqhip_multi_last_encode_timing(vaqhip_multi *mx, vaqhip_multi_encode_timing *out) {

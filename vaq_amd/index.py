@@ -429,12 +429,14 @@ class VaqHip:
         if not self.sequential_sum:
             raise _lib.VaqHipError(-1, f"{what} builds BitVecEngine::queryLUT's index: VaqHip(sequential_sum=True)")
 
-    def fitQuantiles(self, XTrain: np.ndarray, projected: bool = True) -> None:
+    def fitQuantiles(self, XTrain: np.ndarray, projected: bool = True, devices: Optional[Sequence[int]] = None) -> None:
         """BitVecEngine::binaryEncodingLUT's codebooks (BitVecEngine.hpp:811-867) on the GPU: with mBitsAlloc
         (solutionX, 1..8 per dimension) and, for projected=False, mEigenVectors set by the caller -- the PCA
         and the bit allocation stay the caller's --, fills mCentroidsPerSubs (column d of centroidsMat),
         centroidsMat (256 x D) and mQuantiles (D x 257), bit for bit what centroidsQuantile computes
-        (vaqhip_lut_fit_quantiles).  A NaN or infinite training value is refused (EINVAL)."""
+        (vaqhip_lut_fit_quantiles).  A NaN or infinite training value is refused (EINVAL).  devices=[...]: the same
+        members from the sharded fit over those devices (lut_fit_quantiles_multi): the rows are cut over them and no
+        device holds them all."""
         self._need_sequential("fitQuantiles")
         X = np.ascontiguousarray(XTrain, dtype=np.float32)
         D = len(self.mBitsAlloc)
@@ -445,10 +447,13 @@ class VaqHip:
             eig = np.ascontiguousarray(np.real(self.mEigenVectors), dtype=np.float32)
             if eig.shape != (D, D):
                 raise _lib.VaqHipError(-1, f"mEigenVectors {eig.shape} is not {D}x{D}")
-        cent = np.empty((D, 256), np.float32)
-        q = np.empty((D, 257), np.float32)
-        _lib.check(_lib.load().vaqhip_lut_fit_quantiles(self.device, _ptr(X), X.shape[0], D, (C.c_int * D)(*self.mBitsAlloc),
-                                                        _ptr(eig) if eig is not None else None, _ptr(cent), _ptr(q)))
+        if devices is not None:
+            cent, q = lut_fit_quantiles_multi(devices, X, self.mBitsAlloc, eig)
+        else:
+            cent = np.empty((D, 256), np.float32)
+            q = np.empty((D, 257), np.float32)
+            _lib.check(_lib.load().vaqhip_lut_fit_quantiles(self.device, _ptr(X), X.shape[0], D, (C.c_int * D)(*self.mBitsAlloc),
+                                                            _ptr(eig) if eig is not None else None, _ptr(cent), _ptr(q)))
         self.centroidsMat = np.ascontiguousarray(cent.T)
         self.mCentroidsPerSubs = [np.ascontiguousarray(cent[d, :1 << b].reshape(-1, 1)) for d, b in enumerate(self.mBitsAlloc)]
         self.mQuantiles = q
@@ -852,6 +857,13 @@ class VaqMultiRefiner:
             C.c_void_p(st)))
         return labels, dists
 
+    def fit_quantiles(self, bits: Sequence[int], eigvec: Optional[np.ndarray] = None):
+        """vaqhip_multi_refiner_lut_fit_quantiles: binaryEncodingLUT's quantile codebooks over the RAW rows resident on
+        the shards, read in place (eigvec: D x D, applied first; None: the rows are their own image).  Returns
+        (cent[D, 256], q[D, 257]), bit for bit the single fit's over all rows."""
+        return _fit_quantiles_call(self.D, bits, eigvec, lambda L, b, e, c, q: L.vaqhip_multi_refiner_lut_fit_quantiles(
+            self._h, b, e, c, q))
+
     def last_search_timing(self) -> dict:
         """Figures of the last search (times only under set_option("timing", 1)): the slowest shard's select, merge and
         link, the gather, the cross-shard merge, the flag step and the chain on the first device."""
@@ -878,6 +890,42 @@ class VaqMultiRefiner:
             self.close()
         except Exception:
             pass
+
+
+def _fit_quantiles_call(D: int, bits, eigvec, call):
+    bits = [int(b) for b in bits]
+    if len(bits) != D:
+        raise _lib.VaqHipError(-1, f"{len(bits)} bits for D = {D}")
+    eig = None
+    if eigvec is not None:
+        eig = np.ascontiguousarray(np.real(eigvec), dtype=np.float32)
+        if eig.shape != (D, D):
+            raise _lib.VaqHipError(-1, f"eigvec {eig.shape} is not {D}x{D}")
+    cent = np.empty((D, 256), np.float32)
+    q = np.empty((D, 257), np.float32)
+    _lib.check_multi(call(_lib.load(), (C.c_int * max(D, 1))(*bits), _ptr(eig) if eig is not None else None, _ptr(cent),
+                          _ptr(q)))
+    return cent, q
+
+
+def lut_fit_quantiles_multi(devices: Sequence[int], X, bits: Sequence[int], eigvec: Optional[np.ndarray] = None):
+    """vaqhip_multi_lut_fit_quantiles: vaqhip_lut_fit_quantiles's (cent[D, 256], q[D, 257]) bit for bit, with the rows
+    of X cut over `devices` as VaqHipMulti.set_codes cuts code rows and dimension d fitted on device d % len(devices);
+    no device holds all rows.  A device named several times gives logical shards on that GPU."""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    if X.ndim != 2:
+        raise _lib.VaqHipError(-1, f"X {X.shape} is not n x D")
+    devs = [int(d) for d in devices]
+    arr = (C.c_int * max(len(devs), 1))(*devs)
+    return _fit_quantiles_call(X.shape[1], bits, eigvec, lambda L, b, e, c, q: L.vaqhip_multi_lut_fit_quantiles(
+        len(devs), arr, _ptr(X), X.shape[0], X.shape[1], b, e, c, q))
+
+
+def last_lut_fit_multi_timing() -> dict:
+    """Figures of the calling thread's last sharded fit (vaqhip_multi_last_lut_fit_timing)."""
+    t = _lib.MultiLutFitTiming()
+    _lib.check_multi(_lib.load().vaqhip_multi_last_lut_fit_timing(C.byref(t)))
+    return {f: getattr(t, f) for f, _ in _lib.MultiLutFitTiming._fields_}
 
 
 def merge_topk_device(dist_lists, label_lists, k: int, out=None):
@@ -1013,6 +1061,40 @@ class VaqHipMulti:
             codes = np.empty((refiner.info()["N"], self.M), np.uint16)
         _lib.check_multi(_lib.load().vaqhip_multi_encode_from_refiner(self._h, refiner._h,
                                                                       _ptr(codes) if return_codes else None))
+        return codes
+
+    def set_lut_quantiles(self, q) -> None:
+        """vaqhip_multi_set_lut_quantiles: Q (D x 257, as the fit writes it) on every shard of a sequential_sum index;
+        the encode_lut calls need it."""
+        qq = np.ascontiguousarray(q, dtype=np.float32)
+        if qq.shape != (self.M, 257):
+            raise _lib.VaqHipError(-1, f"quantiles {qq.shape} are not {self.M} x 257")
+        _lib.check_multi(_lib.load().vaqhip_multi_set_lut_quantiles(self._h, _ptr(qq)))
+
+    def encode_lut(self, X, projected: bool = True, id_base: int = 0, return_codes: bool = False):
+        """encode() with the engine's rule (encodeToLUTCode, VaqHip.encodeLUT) in the place of VAQ::encode's: the state
+        VaqHip.encodeLUT on one index followed by set_codes(codes, id_base) leaves, bit for bit."""
+        X = self._train_rows(X)
+        codes = np.empty((X.shape[0], self.M), np.uint16) if return_codes else None
+        _lib.check_multi(_lib.load().vaqhip_multi_encode_lut_set_codes(
+            self._h, _ptr(X), X.shape[0], 1 if projected else 0, int(id_base), _ptr(codes) if return_codes else None))
+        return codes
+
+    def encode_lut_add(self, X, projected: bool = True, return_codes: bool = False):
+        """encode_add() with the engine's rule: the rows extend the last shard and are encoded on its device."""
+        X = self._train_rows(X)
+        codes = np.empty((X.shape[0], self.M), np.uint16) if return_codes else None
+        _lib.check_multi(_lib.load().vaqhip_multi_encode_lut_add_codes(
+            self._h, _ptr(X), X.shape[0], 1 if projected else 0, _ptr(codes) if return_codes else None))
+        return codes
+
+    def encode_lut_from_refiner(self, refiner: "VaqMultiRefiner", return_codes: bool = False):
+        """encode_from_refiner() with the engine's rule over the RAW rows resident in a multi refiner."""
+        codes = None
+        if return_codes:
+            codes = np.empty((refiner.info()["N"], self.M), np.uint16)
+        _lib.check_multi(_lib.load().vaqhip_multi_encode_lut_from_refiner(self._h, refiner._h,
+                                                                          _ptr(codes) if return_codes else None))
         return codes
 
     def last_encode_timing(self) -> dict:
