@@ -25,6 +25,11 @@
 //                                           on the device from the raw vectors -- --dataset, resident as with
 //                                           --refine-resident; with --devices cut over the same GPUs, same answer --
 //                                           and the recall lines are printed against them)
+//               [--file-format-ori bvecs]  (demo_vaq.cpp:23: --dataset, --dataset-refine and --queries are bvecs files,
+//                                           SIFT1B / BIGANN.  With --refine-resident and / or --exact-groundtruth the
+//                                           raw vectors go to the device as the BYTES the file holds, a quarter of the
+//                                           memory, same answers; everything else reads them widened to float, as the
+//                                           reference does.  Default fvecs)
 //               [--devices 0,1,2,3]        (shard the rows over these GPUs: RCCL all-gather + merge)
 //               [--encode --dataset base.fvecs [--save-enc cb.bin]]
 //                                          (instead of --codebook: VAQ::encode of the raw vectors, mEigenVectors applied.
@@ -62,6 +67,12 @@ static std::vector<int> intList(const std::string &csv) {
   return v;
 }
 
+// --file-format-ori (demo_vaq.cpp:75-83): fvecs, or bvecs widened to float as readBVecsFromExternal widens them
+static bool g_bvecs = false;
+static RowMatrixF readOri(const std::string &path, int N, int maxRow, int pad) {
+  return g_bvecs ? readBVecs(path, N, maxRow, pad) : readFVecs(path, N, maxRow, pad);
+}
+
 // --lut-bits: build and query BitVecEngine's LUT index
 static int lutMain(std::map<std::string, std::string> &a) {
   for (const char *req : {"dataset", "queries"})
@@ -78,8 +89,8 @@ static int lutMain(std::map<std::string, std::string> &a) {
     detail::File f(a["eigen"], "rb");
     f.read(engine.eigenVectors.data(), sizeof(float), (size_t)D * D);
   }
-  RowMatrixF dataset = readFVecs(a["dataset"], N, a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1, 0);
-  RowMatrixF queries = readFVecs(a["queries"], N, std::atoi(a["queries-size"].c_str()), 0);
+  RowMatrixF dataset = readOri(a["dataset"], N, a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1, 0);
+  RowMatrixF queries = readOri(a["queries"], N, std::atoi(a["queries-size"].c_str()), 0);
   const int k = std::atoi(a["k"].c_str());
   CodebookType codebook;
   auto t0 = std::chrono::steady_clock::now();
@@ -127,6 +138,11 @@ int main(int argc, char **argv) {
     if (std::strncmp(argv[i], "--", 2) != 0) { std::cerr << "bad argument " << argv[i] << "\n"; return 2; }
     a[argv[i] + 2] = argv[i + 1];
   }
+  if (a.count("file-format-ori") && a["file-format-ori"] != "fvecs" && a["file-format-ori"] != "bvecs") {
+    std::cerr << "--file-format-ori " << a["file-format-ori"] << ": fvecs or bvecs\n";
+    return 2;
+  }
+  g_bvecs = a.count("file-format-ori") && a["file-format-ori"] == "bvecs";
   if (a.count("lut-bits")) {
     try {
       return lutMain(a);
@@ -167,6 +183,19 @@ int main(int argc, char **argv) {
       std::cout << "sharding the rows over " << devs.size() << " device entr" << (devs.size() == 1 ? "y" : "ies") << std::endl;
     }
     RowMatrixF datasetrefine;
+    RowMatrix<uint8_t> datasetrefine8;  // bvecs: the raw vectors of the resident paths, as bytes
+    // the raw vectors of a resident path: read as the file holds them and uploaded that way
+    auto uploadRefine = [&](const std::string &path, int maxRow) -> size_t {
+      if (g_bvecs) {
+        datasetrefine8 = readBVecsU8(path, N, maxRow);
+        vaq.setRefineDataset(datasetrefine8);
+        return datasetrefine8.rows();
+      }
+      if (datasetrefine.rows() == 0) datasetrefine = readFVecs(path, N, maxRow, 0);
+      vaq.setRefineDataset(datasetrefine);
+      return datasetrefine.rows();
+    };
+    size_t resident_rows = 0;
     bool uploaded = false;  // the raw vectors are resident already (--encode with --refine-resident)
     if (encode) {  // demo_vaq.cpp:126-135, from the raw vectors
       const int dsize = a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1;
@@ -176,19 +205,18 @@ int main(int argc, char **argv) {
       vaq.mMethods = plain ? plain : (uint32_t)VaqHip::NNMethod::Heap;
       if (a.count("devices") && a.count("refine-resident")) {
         if (N != D) throw Error(VAQHIP_EINVAL, "--encode with --refine-resident encodes the resident raw rows: --timeseries-size must be D");
-        datasetrefine = readFVecs(a.count("dataset-refine") ? a["dataset-refine"] : a["dataset"], N, dsize, 0);
         t0 = std::chrono::steady_clock::now();
-        vaq.setRefineDataset(datasetrefine);
+        resident_rows = uploadRefine(a.count("dataset-refine") ? a["dataset-refine"] : a["dataset"], dsize);
         uploaded = true;
-        std::cout << "== Refine dataset upload: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
-                  << " s (" << datasetrefine.rows() << " rows resident)" << std::endl;
+        std::cout << "== Refine dataset read + upload: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+                  << " s (" << resident_rows << " rows resident" << (g_bvecs ? ", as bytes" : "") << ")" << std::endl;
         t0 = std::chrono::steady_clock::now();
         vaq.encodeRefineDataset();
       } else {
         if (a.count("refine-resident"))
           std::cout << "(--refine-resident without --devices: one device does not encode its resident rows in place, "
                        "the rows are encoded from the host matrix)" << std::endl;
-        RowMatrixF dataset = readFVecs(a["dataset"], N, dsize, D - N);
+        RowMatrixF dataset = readOri(a["dataset"], N, dsize, D - N);
         t0 = std::chrono::steady_clock::now();
         vaq.encode(dataset, false);
       }
@@ -212,7 +240,7 @@ int main(int argc, char **argv) {
       // without --ti-clusters: the reference's own k-means (demo_vaq.cpp:265), on one device or over the shards
       vaq.clusterTI(!a.count("ti-clusters"), true);
     }
-    RowMatrixF queries = readFVecs(a["queries"], N, std::atoi(a["queries-size"].c_str()), D - N);
+    RowMatrixF queries = readOri(a["queries"], N, std::atoi(a["queries-size"].c_str()), D - N);
     const int k = std::atoi(a["k"].c_str());
     std::cout << "index: " << vaq.mCodebook.rows() << " rows x " << M << " subspaces, D=" << D
               << ", queries " << queries.rows() << ", k=" << k << std::endl;
@@ -226,21 +254,23 @@ int main(int argc, char **argv) {
     if (refines.empty()) refines.push_back(0);
     bool any_refine = false;
     for (const int r : refines) any_refine = any_refine || r >= k;
+    const bool resident = (any_refine && a.count("refine-resident")) || uploaded;
+    const int dsize_raw = a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1;
+    std::string raw_refine;
     if (any_refine) {
       // the reference re-reads --dataset for this (demo_vaq.cpp:320-333); --dataset-refine names another file
-      const std::string raw = a.count("dataset-refine") ? a["dataset-refine"] : (a.count("dataset") ? a["dataset"] : "");
-      if (raw.empty()) throw Error(VAQHIP_EINVAL, "--refine needs the raw vectors: --dataset <.fvecs> (or --dataset-refine)");
-      if (!uploaded) datasetrefine = readFVecs(raw, N, a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1, 0);
+      raw_refine = a.count("dataset-refine") ? a["dataset-refine"] : (a.count("dataset") ? a["dataset"] : "");
+      if (raw_refine.empty()) throw Error(VAQHIP_EINVAL, "--refine needs the raw vectors: --dataset <.fvecs> (or --dataset-refine)");
+      if (!resident) datasetrefine = readOri(raw_refine, N, dsize_raw, 0);  // (a resident path reads it where it uploads)
     }
-    const bool resident = (any_refine && a.count("refine-resident")) || uploaded;
     if (resident && uploaded) vaq.refineExactTies = a.count("exact-ties") && std::atoi(a["exact-ties"].c_str()) != 0;
     if (resident && !uploaded) {
       if (N != D) throw Error(VAQHIP_EINVAL, "--refine-resident searches and refines with the same raw query: --timeseries-size must be D");
       vaq.refineExactTies = a.count("exact-ties") && std::atoi(a["exact-ties"].c_str()) != 0;
       auto t0 = std::chrono::steady_clock::now();
-      vaq.setRefineDataset(datasetrefine);
-      std::cout << "== Refine dataset upload: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
-                << " s (" << datasetrefine.rows() << " rows resident)" << std::endl;
+      resident_rows = uploadRefine(raw_refine, dsize_raw);
+      std::cout << "== Refine dataset read + upload: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+                << " s (" << resident_rows << " rows resident" << (g_bvecs ? ", as bytes" : "") << ")" << std::endl;
       if (vaq.multiRefinerHandle()) {
         vaqhip_multi_refiner_info inf;
         if (vaqhip_multi_refiner_get_info(vaq.multiRefinerHandle(), &inf) == 0)
@@ -257,9 +287,7 @@ int main(int argc, char **argv) {
       if (!resident) {  // (with --refine-resident the rows are there already)
         const std::string raw = a.count("dataset-refine") ? a["dataset-refine"] : (a.count("dataset") ? a["dataset"] : "");
         if (raw.empty()) throw Error(VAQHIP_EINVAL, "--exact-groundtruth needs the raw vectors: --dataset <.fvecs>");
-        if (datasetrefine.rows() == 0)
-          datasetrefine = readFVecs(raw, N, a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1, 0);
-        vaq.setRefineDataset(datasetrefine);
+        resident_rows = uploadRefine(raw, dsize_raw);  // (float rows a --refine read are there already)
       }
       auto t0 = std::chrono::steady_clock::now();
       const LabelDistVecF exact = vaq.searchExhaustive(queries, k);
@@ -267,12 +295,12 @@ int main(int argc, char **argv) {
       for (size_t i = 0; i < gt.rows(); i++)
         for (size_t j = 0; j < gt.cols(); j++) gt(i, j) = exact.labels[i * k + j];
       std::cout << "== Exact ground truth: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
-                << " s (" << datasetrefine.rows() << " rows x " << queries.rows() << " queries, exhaustive)" << std::endl;
+                << " s (" << resident_rows << " rows x " << queries.rows() << " queries, exhaustive)" << std::endl;
       a["groundtruth"] = "(exact)";
     }
     if (vaq.searchMethod() & VaqHip::NNMethod::Fast) {  // demo_vaq.cpp:120-124
       if (!a.count("dataset")) throw Error(VAQHIP_EINVAL, "a FAST method learns its quantisation from --dataset <.fvecs>");
-      RowMatrixF dataset = readFVecs(a["dataset"], N, a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1, D - N);
+      RowMatrixF dataset = readOri(a["dataset"], N, a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1, D - N);
       const float ratio = (float)std::atof(a.count("learn-ratio") ? a["learn-ratio"].c_str() : "0.05");
       auto t0 = std::chrono::steady_clock::now();
       vaq.learnQuantization(dataset, ratio);

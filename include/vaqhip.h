@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 116
+#define VAQHIP_VERSION 117
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -370,6 +370,16 @@ int vaqhip_refine_device(int device_id, const float *d_queries, int nq, int D,
  * The host forms are synchronous; the _device forms take device pointers on the refiner's GPU, enqueue on `stream`
  * and never synchronise (the fused one grows its candidate buffer on first use).  Calls on one refiner are serialised
  * on the host; set_rows / add_rows wait for the device to go idle before rows are moved or replaced.
+ *   byte rows  the *_u8 calls keep the rows as uint8, N x D row-major, as a bvecs file (SIFT1B / BIGANN; the reference's
+ *              --file-format-ori bvecs) stores them: a quarter of the memory and of the bytes a refine fetches.  The
+ *              reference widens every byte to a float when it reads the file (utils/IO.hpp, readBVecsFromExternal);
+ *              here the kernels widen a byte where they load it.  (float)uint8 is exact, so every distance is the same
+ *              float operations on the same operands as over the widened rows: all of the above holds bit for bit,
+ *              for any float query, in every call that reads the rows (refine, the fused call, the exhaustive form).
+ *              The element type belongs to the rows: set_rows* of either type replaces the rows and their type;
+ *              add_rows on byte rows and add_rows_u8 on float rows are VAQHIP_ESTATE (nothing is converted), a refiner
+ *              with N == 0 takes either.  Null, range and id_base checks are those of the float calls.
+ *              vaqhip_refiner_elem_size: 4 (float32, also before any rows) or 1 (uint8); negative for a null handle.
  * ------------------------------------------------------------------------- */
 typedef struct vaqhip_refiner vaqhip_refiner;
 int vaqhip_refiner_create(vaqhip_refiner **out, int device_id, int D);
@@ -377,6 +387,10 @@ void vaqhip_refiner_destroy(vaqhip_refiner *r);
 int vaqhip_refiner_set_rows(vaqhip_refiner *r, const float *X_rowmajor, int64_t N, int64_t id_base);
 int vaqhip_refiner_set_rows_device(vaqhip_refiner *r, const float *d_X, int64_t N, int64_t id_base, void *stream);
 int vaqhip_refiner_add_rows(vaqhip_refiner *r, const float *X_rowmajor, int64_t n_new);
+int vaqhip_refiner_set_rows_u8(vaqhip_refiner *r, const uint8_t *X_rowmajor, int64_t N, int64_t id_base);
+int vaqhip_refiner_set_rows_u8_device(vaqhip_refiner *r, const uint8_t *d_X, int64_t N, int64_t id_base, void *stream);
+int vaqhip_refiner_add_rows_u8(vaqhip_refiner *r, const uint8_t *X_rowmajor, int64_t n_new);
+int vaqhip_refiner_elem_size(vaqhip_refiner *r);
 int vaqhip_refiner_set_option(vaqhip_refiner *r, const char *key, int64_t value);
 int vaqhip_refiner_refine(vaqhip_refiner *r, const float *queries_rowmajor, int nq, const int32_t *labels_in, int R,
                           int k, int32_t *labels_out, float *distances_out);
@@ -635,6 +649,8 @@ int vaqhip_multi_encode_lut_from_refiner(vaqhip_multi *mx, vaqhip_multi_refiner 
  *               D < 1 (VAQHIP_EINVAL), D > 4096 (VAQHIP_EUNSUPPORTED), bits outside 1..8; n_devices outside
  *               1..VAQHIP_MAX_DEVICES, a null refiner (VAQHIP_EINVAL), a refiner without rows (VAQHIP_ESTATE).  A NaN or
  *               infinite (projected) value on ANY shard: VAQHIP_EINVAL, both outputs untouched.
+ *   byte rows   a refiner that holds uint8 rows (vaqhip_multi_refiner_set_rows_u8) is refused for now,
+ *               VAQHIP_EUNSUPPORTED: the column kernel re-reads the rows every round and has no byte form yet.
  * Synchronous; a failing shard ends the call; the caller's current device is left as it was. */
 int vaqhip_multi_lut_fit_quantiles(int n_devices, const int *device_ids, const float *X_rowmajor, int64_t n, int D,
                                    const int *bits, const float *eigvec_real_rowmajor /* D x D or NULL */,
@@ -671,7 +687,8 @@ const char *vaqhip_multi_last_error(void);
 
 /* ---------------------------------------------------------------------------
  * Multi-device refiner: the resident refiner above with the raw rows cut over several GPUs -- at 1B x 128 floats
- * the rows (512 GB) fit no single device, the 8 GPUs of a node hold them together.  The answer is the single
+ * the rows (512 GB) fit no single device, the 8 GPUs of a node hold them together; kept as the bytes a bvecs file
+ * holds (the *_u8 calls below) they are 128 GB, within the 288 GB of one MI355X.  The answer is the single
  * refiner's slot for slot, with "exact_ties" on or off and for any number of shards: a candidate's distance depends
  * on the query and its own row only, the selection on the R (distance, label) pairs in candidate order only.  So
  * every shard computes the distances of the candidates it holds (the same reduction, Eigen's summation order), and
@@ -701,12 +718,20 @@ const char *vaqhip_multi_last_error(void);
  * The host forms are synchronous; the _device forms take pointers on device_ids[0], enqueue only and never
  * synchronise once their buffers have their size (`stream`, a stream of device_ids[0], is made to wait for the
  * result).  Errors: vaqhip_multi_last_error().  Calls on one refiner are serialised on the host.
+ *   byte rows   vaqhip_multi_refiner_set_rows_u8 / _add_rows_u8 / _elem_size: the single refiner's byte rows with its
+ *               rules (one element type for all shards; VAQHIP_ESTATE for an append of the other type), cut as set_rows
+ *               cuts, add_rows_u8 extending the last shard.  Refine, the fused call, the exhaustive form and
+ *               vaqhip_multi_encode[_lut]_from_refiner (chunks of "encode_chunk_rows" rows widened on the shard, codes
+ *               equal to those from the widened host matrix) read them; the sharded quantile fit does not yet.
  * ------------------------------------------------------------------------- */
 #define VAQHIP_MULTI_REFINER_SET 16384
 int vaqhip_multi_refiner_create(vaqhip_multi_refiner **out, int D, int n_devices, const int *device_ids);
 void vaqhip_multi_refiner_destroy(vaqhip_multi_refiner *r);
 int vaqhip_multi_refiner_set_rows(vaqhip_multi_refiner *r, const float *X_rowmajor, int64_t N, int64_t id_base);
 int vaqhip_multi_refiner_add_rows(vaqhip_multi_refiner *r, const float *X_rowmajor, int64_t n_new);
+int vaqhip_multi_refiner_set_rows_u8(vaqhip_multi_refiner *r, const uint8_t *X_rowmajor, int64_t N, int64_t id_base);
+int vaqhip_multi_refiner_add_rows_u8(vaqhip_multi_refiner *r, const uint8_t *X_rowmajor, int64_t n_new);
+int vaqhip_multi_refiner_elem_size(vaqhip_multi_refiner *r);
 int vaqhip_multi_refiner_set_option(vaqhip_multi_refiner *r, const char *key, int64_t value);
 int vaqhip_multi_refiner_refine(vaqhip_multi_refiner *r, const float *queries_rowmajor, int nq, const int32_t *labels_in,
                                 int R, int k, int32_t *labels_out, float *distances_out);

@@ -386,6 +386,20 @@ public:
     if (!rf_) check(vaqhip_refiner_create(&rf_, mDevice, rf_dim_));
     check(vaqhip_refiner_set_rows(rf_, XTrain.data(), (int64_t)XTrain.rows(), mIdBase));
   }
+  // The same with the rows kept as the BYTES a bvecs file holds (readBVecsU8; vaqhip.h, "byte rows"): a quarter of
+  // the device memory, and every answer -- search(XTest, k, refineNum), searchExhaustive, encodeRefineDataset -- as
+  // over the widened matrix, bit for bit.
+  void setRefineDataset(const RowMatrix<uint8_t> &XTrain) {
+    if (rf_dim_ != (int)XTrain.cols()) dropRefiners();
+    rf_dim_ = (int)XTrain.cols();
+    if (!mDevices.empty()) {
+      if (!mrf_) checkMulti(vaqhip_multi_refiner_create(&mrf_, rf_dim_, (int)mDevices.size(), mDevices.data()));
+      checkMulti(vaqhip_multi_refiner_set_rows_u8(mrf_, XTrain.data(), (int64_t)XTrain.rows(), mIdBase));
+      return;
+    }
+    if (!rf_) check(vaqhip_refiner_create(&rf_, mDevice, rf_dim_));
+    check(vaqhip_refiner_set_rows_u8(rf_, XTrain.data(), (int64_t)XTrain.rows(), mIdBase));
+  }
   template <class Mat> LabelDistVecF search(const Mat &XTest, const int k, const int refineNum) {
     if (!(mMethods & methodsAllowed_))
       throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: only HEAP / EA / TI are implemented on this path");

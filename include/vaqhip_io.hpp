@@ -115,6 +115,10 @@ inline RowMatrixF readFVecs(const std::string &p, int N, int maxRow = -1, int pa
 inline RowMatrixF readBVecs(const std::string &p, int N, int maxRow = -1, int pad = 0) {
   return readVecs<uint8_t, float>(p, N, maxRow, pad);
 }
+// the bytes as the file holds them, for VaqHip::setRefineDataset(RowMatrix<uint8_t>)
+inline RowMatrix<uint8_t> readBVecsU8(const std::string &p, int N, int maxRow = -1) {
+  return readVecs<uint8_t, uint8_t>(p, N, maxRow, 0);
+}
 inline RowMatrix<int> readIVecs(const std::string &p, int N) { return readVecs<int, int>(p, N); }
 
 

@@ -27,7 +27,8 @@ SYMBOLS = [
     "vaqhip_last_lut_fit_timing", "vaqhip_index_set_lut_quantiles", "vaqhip_encode_lut", "vaqhip_encode_lut_device",
     "vaqhip_refine", "vaqhip_refine_device",
     "vaqhip_refiner_create", "vaqhip_refiner_destroy", "vaqhip_refiner_set_rows", "vaqhip_refiner_set_rows_device",
-    "vaqhip_refiner_add_rows", "vaqhip_refiner_set_option", "vaqhip_refiner_refine", "vaqhip_refiner_refine_device",
+    "vaqhip_refiner_add_rows", "vaqhip_refiner_set_rows_u8", "vaqhip_refiner_set_rows_u8_device",
+    "vaqhip_refiner_add_rows_u8", "vaqhip_refiner_elem_size", "vaqhip_refiner_set_option", "vaqhip_refiner_refine", "vaqhip_refiner_refine_device",
     "vaqhip_search_refine", "vaqhip_search_refine_device",
     "vaqhip_refiner_search", "vaqhip_refiner_search_device", "vaqhip_refiner_last_search_timing",
     "vaqhip_index_info", "vaqhip_set_option", "vaqhip_last_timing", "vaqhip_last_error",
@@ -43,7 +44,8 @@ SYMBOLS = [
     "vaqhip_multi_encode_lut_from_refiner",
     "vaqhip_multi_lut_fit_quantiles", "vaqhip_multi_refiner_lut_fit_quantiles", "vaqhip_multi_last_lut_fit_timing",
     "vaqhip_multi_refiner_create", "vaqhip_multi_refiner_destroy", "vaqhip_multi_refiner_set_rows",
-    "vaqhip_multi_refiner_add_rows", "vaqhip_multi_refiner_set_option", "vaqhip_multi_refiner_refine",
+    "vaqhip_multi_refiner_add_rows", "vaqhip_multi_refiner_set_rows_u8", "vaqhip_multi_refiner_add_rows_u8",
+    "vaqhip_multi_refiner_elem_size", "vaqhip_multi_refiner_set_option", "vaqhip_multi_refiner_refine",
     "vaqhip_multi_refiner_refine_device", "vaqhip_multi_search_refine", "vaqhip_multi_search_refine_device",
     "vaqhip_multi_refiner_get_info",
     "vaqhip_multi_refiner_search", "vaqhip_multi_refiner_search_device", "vaqhip_multi_refiner_last_search_timing",
@@ -198,6 +200,10 @@ def load():
     L.vaqhip_refiner_set_rows.argtypes = [vp, vp, i64, i64]
     L.vaqhip_refiner_set_rows_device.argtypes = [vp, vp, i64, i64, vp]
     L.vaqhip_refiner_add_rows.argtypes = [vp, vp, i64]
+    L.vaqhip_refiner_set_rows_u8.argtypes = [vp, vp, i64, i64]
+    L.vaqhip_refiner_set_rows_u8_device.argtypes = [vp, vp, i64, i64, vp]
+    L.vaqhip_refiner_add_rows_u8.argtypes = [vp, vp, i64]
+    L.vaqhip_refiner_elem_size.argtypes = [vp]
     L.vaqhip_refiner_set_option.argtypes = [vp, C.c_char_p, i64]
     L.vaqhip_refiner_refine.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
     L.vaqhip_refiner_refine_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp]
@@ -247,6 +253,9 @@ def load():
     L.vaqhip_multi_refiner_destroy.restype = None
     L.vaqhip_multi_refiner_set_rows.argtypes = [vp, vp, i64, i64]
     L.vaqhip_multi_refiner_add_rows.argtypes = [vp, vp, i64]
+    L.vaqhip_multi_refiner_set_rows_u8.argtypes = [vp, vp, i64, i64]
+    L.vaqhip_multi_refiner_add_rows_u8.argtypes = [vp, vp, i64]
+    L.vaqhip_multi_refiner_elem_size.argtypes = [vp]
     L.vaqhip_multi_refiner_set_option.argtypes = [vp, C.c_char_p, i64]
     L.vaqhip_multi_refiner_refine.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp]
     L.vaqhip_multi_refiner_refine_device.argtypes = [vp, vp, i32, vp, i32, i32, vp, vp, vp]

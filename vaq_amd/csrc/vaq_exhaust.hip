@@ -21,6 +21,9 @@
 //                      reference's statements to the admitted rows in row order; heap_reorder at the end.  It is one
 //                      link of a chain: across the shards of a multi-device refiner the raw heap arrays go from
 //                      shard to shard and only the last link reorders (xs_scatter_kernel places its slots).
+// Rows are float or uint8 (RowsRef): the row type is a template argument of the three kernels that read rows.  A byte
+// is widened to the float it stands for where it is loaded -- in the register form once per tile, outside the query
+// loop -- and nothing after the load differs.
 // Compiled with -ffp-contract=off like the rest: no FMA, no MFMA, no float atomics; plain vector stores.
 #include "vaq_exhaust.h"
 #include "vaq_kernels.h"
@@ -122,9 +125,9 @@ __device__ __forceinline__ void xs_emit(const XsParams &p, XsShared &sh, const X
   }
 }
 
-template <int NP>
+template <int NP, typename T>
 __global__ __launch_bounds__(XS_THREADS) void xs_tile_kernel(const XsParams p, const float *__restrict__ Q,
-                                                             const float *__restrict__ rows) {
+                                                             const T *__restrict__ rows) {
   __shared__ XsShared sh;
   const int tid = threadIdx.x;
   const XsPart w = xs_part(p);
@@ -133,11 +136,15 @@ __global__ __launch_bounds__(XS_THREADS) void xs_tile_kernel(const XsParams p, c
   for (int64_t t0 = w.r0; t0 < w.r1; t0 += XS_TILE) {
     const int64_t row = t0 + tid;
     const bool valid = row < w.r1;
-    const float *yp = rows + (size_t)(valid ? row : w.r0) * D;
+    const T *yp = rows + (size_t)(valid ? row : w.r0) * D;
     constexpr bool REST = NP < XS_MAX_NP;  // (the widest form has no columns past its packets)
     float y[XsRow<NP, REST>::SLOTS];
+    if constexpr (sizeof(T) == 1) {
+      xs_widen_row<NP, REST>(y, yp, D);
+    } else {
 #pragma unroll
-    for (int e = 0; e < XsRow<NP, REST>::SLOTS; e++) y[e] = (e < NP * 16 || e < D) ? yp[e] : 0.0f;
+      for (int e = 0; e < XsRow<NP, REST>::SLOTS; e++) y[e] = (e < NP * 16 || e < D) ? yp[e] : 0.0f;
+    }
     const int label = (int)(p.id_base + row);
     for (int qb = 0; qb < w.nqg; qb += XS_QB) {
       const int nb = min(XS_QB, w.nqg - qb);
@@ -154,8 +161,9 @@ __global__ __launch_bounds__(XS_THREADS) void xs_tile_kernel(const XsParams p, c
   xs_emit(p, sh, w, tid);
 }
 
+template <typename T>
 __global__ __launch_bounds__(XS_THREADS) void xs_wide_kernel(const XsParams p, const float *__restrict__ Q,
-                                                             const float *__restrict__ rows) {
+                                                             const T *__restrict__ rows) {
   __shared__ XsShared sh;
   extern __shared__ float qs[];
   const int tid = threadIdx.x;
@@ -170,7 +178,7 @@ __global__ __launch_bounds__(XS_THREADS) void xs_wide_kernel(const XsParams p, c
       for (int c0 = 0; c0 < XS_TILE; c0 += XS_THREADS / RF_GROUP) {  // (uniform trip count: the shuffles run in whole waves)
         const int64_t row = t0 + c0 + g;
         const bool valid = row < w.r1;
-        const float *y = rows + (size_t)(valid ? row : w.r0) * D;
+        const T *y = rows + (size_t)(valid ? row : w.r0) * D;
         const float res = rf_group_sq_norm(qs, y, D, valid, j, gbase);
         if (j == 0 && valid) xs_offer(p, sh, w, ql, res, (int)(p.id_base + row));
       }
@@ -190,8 +198,9 @@ __global__ __launch_bounds__(XS_THREADS) void xs_wide_kernel(const XsParams p, c
 //   finish != 0   applies heap_reorder and writes the k slots: to labels / dist [query][k], or, when labels is
 //                 nullptr, to hout_v / hout_i [e][k] (xs_scatter_kernel places them on the first device).
 // The heap's statements see the rows of all links in order with nothing in between.
+template <typename T>
 __global__ __launch_bounds__(XS_THREADS) void xs_replay_kernel(const float *__restrict__ Q, int D,
-                                                               const float *__restrict__ rows, int64_t N, int64_t id_base,
+                                                               const T *__restrict__ rows, int64_t N, int64_t id_base,
                                                                int k, const int *__restrict__ list,
                                                                const unsigned *__restrict__ count,
                                                                const float *__restrict__ hin_v,
@@ -217,7 +226,7 @@ __global__ __launch_bounds__(XS_THREADS) void xs_replay_kernel(const float *__re
     for (int i0 = 0; i0 < XR_CHUNK; i0 += XS_THREADS / RF_GROUP) {  // (uniform trip count)
       const int64_t row = c0 + i0 + g;
       const bool valid = row < N;
-      const float *y = rows + (size_t)(valid ? row : 0) * D;
+      const T *y = rows + (size_t)(valid ? row : 0) * D;
       const float res = rf_group_sq_norm(qs, y, D, valid, j, gbase);
       if (j == 0) cd[i0 + g] = valid ? res : INFINITY;
     }
@@ -284,50 +293,50 @@ int exhaust_list_cap(int k) {
 
 size_t exhaust_register_max_dim() { return XS_MAX_DIM; }
 
-template <int NP>
+template <int NP, typename T>
 static int xs_tile_blocks_per_cu() {
   int n = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, xs_tile_kernel<NP>, XS_THREADS, 0) != hipSuccess) n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, xs_tile_kernel<NP, T>, XS_THREADS, 0) != hipSuccess) n = 0;
   return n;
+}
+
+template <typename T>
+static int xs_blocks_per_cu(int D) {
+  int n = 0;
+  if (D > XS_MAX_DIM) {
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, xs_wide_kernel<T>, XS_THREADS, (size_t)D * sizeof(float)) != hipSuccess) n = 0;
+    return n;
+  }
+  switch (D / 16) {
+    case 0: return xs_tile_blocks_per_cu<0, T>();
+    case 1: return xs_tile_blocks_per_cu<1, T>();
+    case 2: return xs_tile_blocks_per_cu<2, T>();
+    case 3: return xs_tile_blocks_per_cu<3, T>();
+    case 4: return xs_tile_blocks_per_cu<4, T>();
+    case 5: return xs_tile_blocks_per_cu<5, T>();
+    case 6: return xs_tile_blocks_per_cu<6, T>();
+    case 7: return xs_tile_blocks_per_cu<7, T>();
+    default: return xs_tile_blocks_per_cu<8, T>();
+  }
 }
 
 // workgroups of launch_exhaust_select's kernel for rows of D columns that one CU holds at a time (>= 1): the plan
 // sizes its grid to ONE round of them -- a second, partly filled round runs at a fraction of the issue rate
-int exhaust_blocks_per_cu(int D) {
-  int n = 0;
-  if (D > XS_MAX_DIM) {
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, xs_wide_kernel, XS_THREADS, (size_t)D * sizeof(float)) != hipSuccess) n = 0;
-  } else {
-    switch (D / 16) {
-      case 0: n = xs_tile_blocks_per_cu<0>(); break;
-      case 1: n = xs_tile_blocks_per_cu<1>(); break;
-      case 2: n = xs_tile_blocks_per_cu<2>(); break;
-      case 3: n = xs_tile_blocks_per_cu<3>(); break;
-      case 4: n = xs_tile_blocks_per_cu<4>(); break;
-      case 5: n = xs_tile_blocks_per_cu<5>(); break;
-      case 6: n = xs_tile_blocks_per_cu<6>(); break;
-      case 7: n = xs_tile_blocks_per_cu<7>(); break;
-      default: n = xs_tile_blocks_per_cu<8>(); break;
-    }
-  }
+int exhaust_blocks_per_cu(int D, int elem) {
+  const int n = elem == 1 ? xs_blocks_per_cu<uint8_t>(D) : xs_blocks_per_cu<float>(D);
   return n < 1 ? 1 : (n > 8 ? 8 : n);
 }
 
-template <int NP>
-static void xs_launch_tile(const XsParams &p, const float *Q, const float *rows, hipStream_t st) {
-  hipLaunchKernelGGL(xs_tile_kernel<NP>, dim3(p.S * p.G), dim3(XS_THREADS), 0, st, p, Q, rows);
+template <int NP, typename T>
+static void xs_launch_tile(const XsParams &p, const float *Q, const T *rows, hipStream_t st) {
+  hipLaunchKernelGGL((xs_tile_kernel<NP, T>), dim3(p.S * p.G), dim3(XS_THREADS), 0, st, p, Q, rows);
 }
 
-hipError_t launch_exhaust_select(const XsParams &p, const float *Q, const float *rows, hipStream_t st) {
-  if (p.nq == 0) return hipSuccess;
-  if (p.nq < 0 || p.D < 1 || (size_t)p.D > refine_rows_max_dim() || p.N < 0 || p.k < 1 || p.k > XS_MAX_K1 ||
-      p.cap != exhaust_list_cap(p.k) || p.cap > XS_SORT_CAP || p.S < 1 || p.qg < 1 || p.qg > XS_MAX_QG ||
-      p.G != (p.nq + p.qg - 1) / p.qg || p.split_rows < 0 || (p.N > 0 && (p.N + p.S - 1) / p.S > p.split_rows) ||
-      p.id_base < 0 || p.id_base + p.N > 0x7fffffffLL)
-    return hipErrorInvalidValue;
+template <typename T>
+static void xs_launch_select(const XsParams &p, const float *Q, const T *rows, hipStream_t st) {
   if (p.D > XS_MAX_DIM) {
-    hipLaunchKernelGGL(xs_wide_kernel, dim3(p.S * p.G), dim3(XS_THREADS), (size_t)p.D * sizeof(float), st, p, Q, rows);
-    return hipGetLastError();
+    hipLaunchKernelGGL(xs_wide_kernel<T>, dim3(p.S * p.G), dim3(XS_THREADS), (size_t)p.D * sizeof(float), st, p, Q, rows);
+    return;
   }
   switch (p.D / 16) {
     case 0: xs_launch_tile<0>(p, Q, rows, st); break;
@@ -340,10 +349,26 @@ hipError_t launch_exhaust_select(const XsParams &p, const float *Q, const float 
     case 7: xs_launch_tile<7>(p, Q, rows, st); break;
     default: xs_launch_tile<8>(p, Q, rows, st); break;
   }
+}
+
+hipError_t launch_exhaust_select(const XsParams &p, const float *Q, RowsRef rows, hipStream_t st) {
+  if (p.nq == 0) return hipSuccess;
+  if (p.nq < 0 || p.D < 1 || (size_t)p.D > refine_rows_max_dim() || p.N < 0 || p.k < 1 || p.k > XS_MAX_K1 ||
+      p.cap != exhaust_list_cap(p.k) || p.cap > XS_SORT_CAP || p.S < 1 || p.qg < 1 || p.qg > XS_MAX_QG ||
+      p.G != (p.nq + p.qg - 1) / p.qg || p.split_rows < 0 || (p.N > 0 && (p.N + p.S - 1) / p.S > p.split_rows) ||
+      p.id_base < 0 || p.id_base + p.N > 0x7fffffffLL || (rows.elem != 4 && rows.elem != 1))
+    return hipErrorInvalidValue;
+  if (rows.elem == 1) {
+    // (xs_widen_row's wide loads need the allocation's own alignment)
+    if (reinterpret_cast<uintptr_t>(rows.p) % 16 != 0) return hipErrorInvalidValue;
+    xs_launch_select(p, Q, static_cast<const uint8_t *>(rows.p), st);
+  } else {
+    xs_launch_select(p, Q, static_cast<const float *>(rows.p), st);
+  }
   return hipGetLastError();
 }
 
-hipError_t launch_exhaust_replay_link(const float *Q, int nq, int D, const float *rows, int64_t N, int64_t id_base, int k,
+hipError_t launch_exhaust_replay_link(const float *Q, int nq, int D, RowsRef rows, int64_t N, int64_t id_base, int k,
                                       const int *list, const unsigned *count, const float *hin_v, const int *hin_i,
                                       float *hout_v, int *hout_i, int finish, int32_t *labels, float *dist,
                                       hipStream_t st) {
@@ -351,14 +376,21 @@ hipError_t launch_exhaust_replay_link(const float *Q, int nq, int D, const float
   if (nq < 0 || D < 1 || (size_t)D > refine_rows_max_dim() || N < 0 || k < 1 || k > XS_MAX_K1 || id_base < 0 ||
       id_base + N > 0x7fffffffLL || !list || !count || (hin_v == nullptr) != (hin_i == nullptr) ||
       (hout_v == nullptr) != (hout_i == nullptr) || (labels == nullptr) != (dist == nullptr) ||
-      (finish ? !labels && !hout_v : !hout_v))
+      (finish ? !labels && !hout_v : !hout_v) || (rows.elem != 4 && rows.elem != 1))
     return hipErrorInvalidValue;
-  hipLaunchKernelGGL(xs_replay_kernel, dim3(nq), dim3(XS_THREADS), (size_t)D * sizeof(float), st, Q, D, rows, N, id_base,
-                     k, list, count, hin_v, hin_i, hout_v, hout_i, finish, labels, dist);
+  const size_t lds = (size_t)D * sizeof(float);
+  if (rows.elem == 1)
+    hipLaunchKernelGGL(xs_replay_kernel<uint8_t>, dim3(nq), dim3(XS_THREADS), lds, st, Q, D,
+                       static_cast<const uint8_t *>(rows.p), N, id_base, k, list, count, hin_v, hin_i, hout_v, hout_i, finish,
+                       labels, dist);
+  else
+    hipLaunchKernelGGL(xs_replay_kernel<float>, dim3(nq), dim3(XS_THREADS), lds, st, Q, D,
+                       static_cast<const float *>(rows.p), N, id_base, k, list, count, hin_v, hin_i, hout_v, hout_i, finish,
+                       labels, dist);
   return hipGetLastError();
 }
 
-hipError_t launch_exhaust_replay(const float *Q, int nq, int D, const float *rows, int64_t N, int64_t id_base, int k,
+hipError_t launch_exhaust_replay(const float *Q, int nq, int D, RowsRef rows, int64_t N, int64_t id_base, int k,
                                  const int *list, const unsigned *count, int32_t *labels, float *dist, hipStream_t st) {
   if (!labels || !dist) return nq == 0 ? hipSuccess : hipErrorInvalidValue;
   return launch_exhaust_replay_link(Q, nq, D, rows, N, id_base, k, list, count, nullptr, nullptr, nullptr, nullptr, 1, labels,

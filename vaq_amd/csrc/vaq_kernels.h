@@ -156,19 +156,29 @@ hipError_t launch_refine(const float *Q, int nq, int D, const float *dataset, co
 // Eigen's summation order; a label outside [id_base, id_base + N) is skipped and its row never read.  exact != 0: the
 // k best are the reference heap's (VAQ.cpp:863-872), else the k smallest by (distance, label).  1 <= k <= R <= 2048,
 // D <= refine_rows_max_dim()
+// Resident rows are held as float32 or as uint8 (a bvecs dataset as it is stored): elem is the element's size, 4 or 1.
+// (float)uint8 is exact, so a kernel over byte rows runs the float form's operations on the float form's operands;
+// only the load differs.  Queries are float either way.
+struct RowsRef {
+  const void *p;
+  int elem;
+};
 size_t refine_rows_max_dim();
-hipError_t launch_refine_rows(const float *Q, int nq, int D, const float *rows, int64_t N, int64_t id_base,
+hipError_t launch_refine_rows(const float *Q, int nq, int D, RowsRef rows, int64_t N, int64_t id_base,
                               const int32_t *labels_in, int R, int k, int exact, int32_t *labels, float *dist,
                               hipStream_t st);
 // The same in two halves, for rows sharded over devices (refine_owner.h has the cut).  launch_refine_dist: one shard's
 // rows (n x D, row i carries label lo_label + i) -> plane[q * R + c] for the candidates it holds, other slots left
 // alone; n == 0 launches nothing.  launch_refine_select: slot c of query q is read from the plane of the shard that owns
 // its label (planes + owner * plane_stride), labels nobody owns are skipped, then launch_refine_rows' selection.
-hipError_t launch_refine_dist(const float *Q, int nq, int D, const float *rows, int64_t n, int64_t lo_label,
+hipError_t launch_refine_dist(const float *Q, int nq, int D, RowsRef rows, int64_t n, int64_t lo_label,
                               const int32_t *labels_in, int R, float *plane, hipStream_t st);
 hipError_t launch_refine_select(const int32_t *labels_in, int nq, const float *planes, size_t plane_stride,
                                 const RefineBounds &bounds, int R, int k, int exact, int32_t *labels, float *dist,
                                 hipStream_t st);
+// n x D byte rows widened to float (dst[i] = (float)src[i]): the encoders read float rows, a byte refiner's chunk
+// goes through here first
+hipError_t launch_widen_rows_u8(const uint8_t *src, int64_t elems, float *dst, hipStream_t st);
 // ---- the exhaustive form of VAQ::refine (vaq_exhaust.hip): every resident row a candidate, in row order ----
 constexpr int XS_TILE = 256;      // rows a workgroup takes at a time
 constexpr int XS_MAX_QG = 1024;   // queries a workgroup owns (their thresholds and counts sit in LDS)
@@ -190,20 +200,20 @@ struct XsParams {
 };
 int exhaust_list_cap(int k);
 size_t exhaust_register_max_dim();  // widest row of the register form
-int exhaust_blocks_per_cu(int D);     // resident workgroups per CU of the select kernel for this width
+int exhaust_blocks_per_cu(int D, int elem);  // resident workgroups per CU of the select kernel for this width and row type
 // Q: nq x D, rows: N x D; D <= refine_rows_max_dim(); rows of up to XS_MAX_DIM columns (vaq_exhaust.h) take the
 // register form, wider ones the general path
-hipError_t launch_exhaust_select(const XsParams &p, const float *Q, const float *rows, hipStream_t st);
+hipError_t launch_exhaust_select(const XsParams &p, const float *Q, RowsRef rows, hipStream_t st);
 // "exact_ties": block e replays query list[e] over all rows through the reference's heap and writes its k slots of
 // labels / dist; blocks at or beyond *count exit at once (launch nq of them)
-hipError_t launch_exhaust_replay(const float *Q, int nq, int D, const float *rows, int64_t N, int64_t id_base, int k,
+hipError_t launch_exhaust_replay(const float *Q, int nq, int D, RowsRef rows, int64_t N, int64_t id_base, int k,
                                  const int *list, const unsigned *count, int32_t *labels, float *dist, hipStream_t st);
 // The same as one link of a chain over shards: `rows` are the shard's n rows, id_base its first label.  Entry e of
 // the list starts from the raw heap arrays hin_v / hin_i [e][k] the link before left (nullptr: the empty heap).
 // finish == 0: its raw arrays go to hout_v / hout_i [e][k].  finish != 0: heap_reorder, the k slots go to labels / dist
 // [query][k], or with labels == nullptr to hout_v / hout_i [e][k], which launch_exhaust_scatter -- on the device of
 // the caller's buffers, after a copy -- places at query list[e].  launch_exhaust_replay is the chain of one link.
-hipError_t launch_exhaust_replay_link(const float *Q, int nq, int D, const float *rows, int64_t N, int64_t id_base, int k,
+hipError_t launch_exhaust_replay_link(const float *Q, int nq, int D, RowsRef rows, int64_t N, int64_t id_base, int k,
                                       const int *list, const unsigned *count, const float *hin_v, const int *hin_i,
                                       float *hout_v, int *hout_i, int finish, int32_t *labels, float *dist,
                                       hipStream_t st);

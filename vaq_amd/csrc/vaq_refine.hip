@@ -10,6 +10,10 @@
 // every addition has the operands the specification gives it (fp add commutes, its grouping is what is fixed).
 // Compiled with -ffp-contract=off like the rest: no FMA, no MFMA, no float atomics; plain vector stores.
 //
+// Rows are float or uint8 (RowsRef; a bvecs dataset kept as its bytes): the row type is a template argument of the two
+// kernels that read rows, a byte is widened where it is loaded ((float)uint8 is exact) and nothing after the load
+// differs -- the same instruction count, a quarter of the bytes.
+//
 // A label that is negative or outside [id_base, id_base + N) is skipped HERE, before its row's address is formed
 // (the reference would read out of bounds): a device caller can hand over any list.
 //
@@ -87,9 +91,9 @@ __device__ __forceinline__ void rf_select(float *sd, int *si, float *hv, int *hi
   }
 }
 
-template <bool EXACT>
+template <bool EXACT, typename T>
 __global__ __launch_bounds__(RF_THREADS) void refine_rows_kernel(const float *__restrict__ Q, int D,
-                                                                 const float *__restrict__ rows, int64_t N,
+                                                                 const T *__restrict__ rows, int64_t N,
                                                                  int64_t id_base, const int32_t *__restrict__ labels_in,
                                                                  int R, int k, int32_t *__restrict__ labels,
                                                                  float *__restrict__ dist) {
@@ -108,7 +112,7 @@ __global__ __launch_bounds__(RF_THREADS) void refine_rows_kernel(const float *__
     const int lab = c < R ? labels_in[(size_t)q * R + c] : -1;
     const int64_t row = (int64_t)lab - id_base;
     const bool valid = lab >= 0 && row >= 0 && row < N;
-    const float *y = rows + (valid ? (size_t)row * D : (size_t)0);
+    const T *y = rows + (valid ? (size_t)row * D : (size_t)0);
     const float res = rf_group_sq_norm(qs, y, D, valid, j, gbase);
     if (j == 0 && c < R) rf_fill_slot<EXACT>(sd, si, c, valid, res, lab);
   }
@@ -118,8 +122,9 @@ __global__ __launch_bounds__(RF_THREADS) void refine_rows_kernel(const float *__
 // The multi-device refiner, one shard's part: the distances of the candidates whose rows this shard holds (labels
 // [lo_label, lo_label + n), row 0 of `rows` carrying lo_label), written to their own slots of the [nq][R] plane.  Every
 // other slot is left alone: the select kernel reads a slot only from the plane of the shard that owns its label.
+template <typename T>
 __global__ __launch_bounds__(RF_THREADS) void refine_dist_kernel(const float *__restrict__ Q, int D,
-                                                                 const float *__restrict__ rows, int64_t n,
+                                                                 const T *__restrict__ rows, int64_t n,
                                                                  int64_t lo_label, const int32_t *__restrict__ labels_in,
                                                                  int R, float *__restrict__ plane) {
   extern __shared__ float qs[];
@@ -132,7 +137,7 @@ __global__ __launch_bounds__(RF_THREADS) void refine_dist_kernel(const float *__
     const int lab = c < R ? labels_in[(size_t)q * R + c] : -1;
     const int64_t row = (int64_t)lab - lo_label;
     const bool valid = lab >= 0 && row >= 0 && row < n;
-    const float *y = rows + (valid ? (size_t)row * D : (size_t)0);
+    const T *y = rows + (valid ? (size_t)row * D : (size_t)0);
     const float res = rf_group_sq_norm(qs, y, D, valid, j, gbase);
     if (j == 0 && valid) plane[(size_t)q * R + c] = res;
   }
@@ -167,28 +172,60 @@ __global__ __launch_bounds__(RF_THREADS) void refine_select_kernel(const int32_t
 
 size_t refine_rows_max_dim() { return (size_t)(64 * 1024 - 4 * RF_CAP * sizeof(float) - 64) / sizeof(float); }
 
-hipError_t launch_refine_rows(const float *Q, int nq, int D, const float *rows, int64_t N, int64_t id_base,
+template <typename T>
+static void rf_launch_rows(const float *Q, int nq, int D, const T *rows, int64_t N, int64_t id_base, const int32_t *labels_in,
+                           int R, int k, int exact, int32_t *labels, float *dist, hipStream_t st) {
+  const size_t lds = (size_t)D * sizeof(float);
+  if (exact)
+    hipLaunchKernelGGL((refine_rows_kernel<true, T>), dim3(nq), dim3(RF_THREADS), lds, st, Q, D, rows, N, id_base,
+                       labels_in, R, k, labels, dist);
+  else
+    hipLaunchKernelGGL((refine_rows_kernel<false, T>), dim3(nq), dim3(RF_THREADS), lds, st, Q, D, rows, N, id_base,
+                       labels_in, R, k, labels, dist);
+}
+
+hipError_t launch_refine_rows(const float *Q, int nq, int D, RowsRef rows, int64_t N, int64_t id_base,
                               const int32_t *labels_in, int R, int k, int exact, int32_t *labels, float *dist,
                               hipStream_t st) {
   if (nq == 0) return hipSuccess;
-  if (R > RF_CAP || R < 1 || k < 1 || k > R || D < 1 || (size_t)D > refine_rows_max_dim() || N < 0)
+  if (R > RF_CAP || R < 1 || k < 1 || k > R || D < 1 || (size_t)D > refine_rows_max_dim() || N < 0 ||
+      (rows.elem != 4 && rows.elem != 1))
     return hipErrorInvalidValue;
-  const size_t lds = (size_t)D * sizeof(float);
-  if (exact)
-    hipLaunchKernelGGL(refine_rows_kernel<true>, dim3(nq), dim3(RF_THREADS), lds, st, Q, D, rows, N, id_base, labels_in,
-                       R, k, labels, dist);
+  if (rows.elem == 1)
+    rf_launch_rows(Q, nq, D, static_cast<const uint8_t *>(rows.p), N, id_base, labels_in, R, k, exact, labels, dist, st);
   else
-    hipLaunchKernelGGL(refine_rows_kernel<false>, dim3(nq), dim3(RF_THREADS), lds, st, Q, D, rows, N, id_base, labels_in,
-                       R, k, labels, dist);
+    rf_launch_rows(Q, nq, D, static_cast<const float *>(rows.p), N, id_base, labels_in, R, k, exact, labels, dist, st);
   return hipGetLastError();
 }
 
-hipError_t launch_refine_dist(const float *Q, int nq, int D, const float *rows, int64_t n, int64_t lo_label,
+hipError_t launch_refine_dist(const float *Q, int nq, int D, RowsRef rows, int64_t n, int64_t lo_label,
                               const int32_t *labels_in, int R, float *plane, hipStream_t st) {
   if (nq == 0 || n == 0) return hipSuccess;  // (a shard without rows owns no label)
-  if (R > RF_CAP || R < 1 || D < 1 || (size_t)D > refine_rows_max_dim() || n < 0 || lo_label < 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(refine_dist_kernel, dim3(nq), dim3(RF_THREADS), (size_t)D * sizeof(float), st, Q, D, rows, n, lo_label,
-                     labels_in, R, plane);
+  if (R > RF_CAP || R < 1 || D < 1 || (size_t)D > refine_rows_max_dim() || n < 0 || lo_label < 0 ||
+      (rows.elem != 4 && rows.elem != 1))
+    return hipErrorInvalidValue;
+  const size_t lds = (size_t)D * sizeof(float);
+  if (rows.elem == 1)
+    hipLaunchKernelGGL(refine_dist_kernel<uint8_t>, dim3(nq), dim3(RF_THREADS), lds, st, Q, D,
+                       static_cast<const uint8_t *>(rows.p), n, lo_label, labels_in, R, plane);
+  else
+    hipLaunchKernelGGL(refine_dist_kernel<float>, dim3(nq), dim3(RF_THREADS), lds, st, Q, D,
+                       static_cast<const float *>(rows.p), n, lo_label, labels_in, R, plane);
+  return hipGetLastError();
+}
+
+// dst[i] = (float)src[i]: a chunk of byte rows as the encoders read it (vaqhip_multi_encode.cpp)
+__global__ __launch_bounds__(RF_THREADS) void widen_rows_u8_kernel(const uint8_t *__restrict__ src, int64_t elems,
+                                                                   float *__restrict__ dst) {
+  const int64_t stride = (int64_t)gridDim.x * RF_THREADS;
+  for (int64_t i = (int64_t)blockIdx.x * RF_THREADS + threadIdx.x; i < elems; i += stride) dst[i] = (float)src[i];
+}
+
+hipError_t launch_widen_rows_u8(const uint8_t *src, int64_t elems, float *dst, hipStream_t st) {
+  if (elems == 0) return hipSuccess;
+  if (elems < 0 || !src || !dst) return hipErrorInvalidValue;
+  const int64_t blocks = std::min<int64_t>((elems + RF_THREADS - 1) / RF_THREADS, 256 * 16);
+  hipLaunchKernelGGL(widen_rows_u8_kernel, dim3((unsigned)blocks), dim3(RF_THREADS), 0, st, src, elems, dst);
   return hipGetLastError();
 }
 

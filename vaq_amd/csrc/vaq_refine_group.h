@@ -1,5 +1,7 @@
 // vaq_refine_group.h -- Eigen's (q - y).squaredNorm() spread over 16 adjacent lanes of a wave: the distance of
 // vaq_refine.hip's kernels and of the exhaustive form's general path and replay (vaq_exhaust.hip).  Device only.
+// The row's element type T is float or uint8_t: a byte is widened where it is loaded ((float)uint8 is exact) and
+// every subtraction, product and sum after it is the float form's; a byte row moves a quarter of the bytes.
 #ifndef VAQ_REFINE_GROUP_H_
 #define VAQ_REFINE_GROUP_H_
 
@@ -14,9 +16,10 @@ __device__ __forceinline__ float rf_from(float v, int gbase, int src) { return _
 
 // Squared distance of the group's row y to the staged query qs, complete in lane 0 of the group.  Every lane of the
 // wave runs every shuffle; `valid` (the same in all 16 lanes of a group) only masks the loads of a skipped candidate.
-__device__ __forceinline__ float rf_group_sq_norm(const float *qs, const float *__restrict__ y, int D, bool valid, int j,
+template <typename T>
+__device__ __forceinline__ float rf_group_sq_norm(const float *qs, const T *__restrict__ y, int D, bool valid, int j,
                                                   int gbase) {
-#define T_(idx, ok) ((valid && (ok)) ? km_sq(qs[idx], y[idx]) : 0.0f)
+#define T_(idx, ok) ((valid && (ok)) ? km_sq(qs[idx], (float)y[idx]) : 0.0f)
   if (D < 8) {  // res = coeff(0); res += coeff(i)
     const float t = T_(j, j < D);
     float res = rf_from(t, gbase, 0);

@@ -33,16 +33,17 @@ struct XsPlan {
 // One device's workspace (grow-only): candidate lists, the splits' lists, the merge's scratch, and with "exact_ties"
 // the k + 1 lists and the replay list (count behind the entries).  ev: option "timing".
 struct XsWork {
-  int n_cu = 0, blocks_per_cu = 0;
+  int n_cu = 0, blocks_per_cu = 0, sized_elem = 0;
   DevBuf buf_d, buf_id, part_d, part_id, ms_d, ms_id, k1_l, k1_d, list;
   hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
 
-  // the sizing of the plan: once per device and row width
-  hipError_t size_for(int device, int D) {
-    if (n_cu) return hipSuccess;
+  // the sizing of the plan: once per device, row width and row type (the byte-row kernels are other kernels)
+  hipError_t size_for(int device, int D, int elem) {
+    if (n_cu && sized_elem == elem) return hipSuccess;
     XS_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, device));
     if (n_cu < 1) n_cu = 1;
-    blocks_per_cu = vaq::exhaust_blocks_per_cu(D);
+    blocks_per_cu = vaq::exhaust_blocks_per_cu(D, elem);
+    sized_elem = elem;
     return hipSuccess;
   }
   // bytes every buffer needs under `pl`; `own_k1`: the k + 1 lists and the replay list are this workspace's
@@ -96,9 +97,9 @@ inline XsPlan xs_plan(const XsWork &w, int64_t N, int opt_splits, int nq, int k1
   return pl;
 }
 
-// the rows one call searches: N x D floats on the current device, row i carries label id_base + i
+// the rows one call searches: N x D floats or bytes on the current device, row i carries label id_base + i
 struct XsRows {
-  const float *rows;
+  vaq::RowsRef rows;
   int64_t N, id_base;
   int D;
 };

@@ -11,7 +11,8 @@
 //
 // Two phases, each on every shard's worker at once (on_shards):
 //   1 encode  the rows -- uploaded slice by slice in chunks (host form), or read where a multi refiner holds them
-//             (refiner form) -- into a scratch buffer of n_g x M uint16 on the shard's device; the stream is
+//             (refiner form; byte rows are widened chunk by chunk into the host form's chunk buffer:
+//             launch_widen_rows_u8, (float)uint8 is exact) -- into a scratch buffer of n_g x M uint16 on the shard's device; the stream is
 //             synchronised, so whatever fails has failed before any shard's rows change
 //   2 set     the index takes the buffer (set: every shard, an empty one is emptied; append: the last shard), the
 //             codes go to the host only when the caller asked for them
@@ -33,8 +34,8 @@ constexpr int64_t ENCODE_CHUNK_ROWS = (int64_t)1 << 20;  // rows per upload / pr
 // one shard's part of the call in flight
 struct EncodePart {
   int64_t lo = 0, n = 0;           // rows [lo, lo + n) of the call's matrix
-  const float *d_rows = nullptr;   // refiner form: the shard's resident rows
-  DevBuf chunk, codes;             // float [chunk rows][D] (host form), uint16 [n][M]
+  vaq::RowsRef d_rows = {nullptr, 4};  // refiner form: the shard's resident rows, float or byte
+  DevBuf chunk, codes;             // float [chunk rows][D] (host form, byte rows widened), uint16 [n][M]
   hipEvent_t t[4] = {nullptr, nullptr, nullptr, nullptr};  // phase 1: start, encoded; phase 2: start, set
   float encode_ms = 0, set_ms = 0;
 };
@@ -64,14 +65,17 @@ int encode_part(vaqhip_multi *mx, const EncodeCall &c, EncodePart &p, Shard &s) 
   MHIP(hipSetDevice(s.device));
   MHIP(ensure_events(p.t));
   MHIP(p.codes.ensure((size_t)p.n * M * sizeof(uint16_t)));
-  if (c.X) MHIP(p.chunk.ensure((size_t)std::min(c.chunk, p.n) * D * sizeof(float)));
+  const bool widen = !c.X && p.d_rows.elem == 1;
+  if (c.X || widen) MHIP(p.chunk.ensure((size_t)std::min(c.chunk, p.n) * D * sizeof(float)));
   MHIP(hipEventRecord(p.t[0], s.stream));
   for (int64_t r = 0; r < p.n; r += c.chunk) {
     const int64_t m = std::min(c.chunk, p.n - r);
     const float *d_x = p.chunk.as<float>();
     if (c.X)  // (one chunk buffer: the stream orders this copy behind the encode of the chunk before)
       MHIP(hipMemcpyAsync(p.chunk.p, c.X + (size_t)(p.lo + r) * D, (size_t)m * D * sizeof(float), hipMemcpyHostToDevice, s.stream));
-    else d_x = p.d_rows + (size_t)r * D;
+    else if (widen)  // (the same one buffer, the same order)
+      MHIP(vaq::launch_widen_rows_u8(static_cast<const uint8_t *>(p.d_rows.p) + (size_t)r * D, m * (int64_t)D, p.chunk.as<float>(), s.stream));
+    else d_x = static_cast<const float *>(p.d_rows.p) + (size_t)r * D;
     uint16_t *d_codes = p.codes.as<uint16_t>() + (size_t)r * M;
     if (c.lut) MIX(vaqhip_encode_lut_device(s.ix, d_x, m, c.projected, d_codes, s.stream));
     else MIX(vaqhip_encode_device(s.ix, d_x, m, c.projected, d_codes, s.stream));

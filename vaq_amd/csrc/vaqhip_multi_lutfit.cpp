@@ -250,6 +250,8 @@ int vaqhip_multi_refiner_lut_fit_quantiles(vaqhip_multi_refiner *r, const int *b
   if (!bits || !centroids_out || !quantiles_out) return mfail(VAQHIP_EINVAL, "null pointer");
   std::lock_guard<std::mutex> lk(r->mu);
   if (r->N == 0) return mfail(VAQHIP_ESTATE, "the refiner holds no rows: vaqhip_multi_refiner_set_rows first");
+  if (rows_elem(r) != 4)  // (the column kernel re-reads the rows every round: its byte form is not written yet)
+    return mfail(VAQHIP_EUNSUPPORTED, "the refiner holds uint8 rows: the sharded quantile fit reads float32 rows only");
   if (const int rc = check_fit_args(r->N, r->D, bits, centroids_out, quantiles_out)) return rc;
   DeviceGuard keep(DeviceGuard::restore_only);  // (declared first: it puts the device back after f has released)
   FitRun f;
@@ -259,7 +261,7 @@ int vaqhip_multi_refiner_lut_fit_quantiles(vaqhip_multi_refiner *r, const int *b
   for (int g = 0; g < r->G; g++) {
     const ResidentRows rows = resident_rows(r, g);
     f.sh[(size_t)g].device = r->sh[g].device;
-    f.sh[(size_t)g].d_rows = rows.rows;
+    f.sh[(size_t)g].d_rows = static_cast<const float *>(rows.rows.p);
     cnt[g] = rows.n;
   }
   if (!lp::plan_from_counts(r->G, r->D, cnt, &f.plan)) return mfail(VAQHIP_EINVAL, "bad shard counts");

@@ -179,6 +179,74 @@ int search_refine_locked(vaqhip_multi *mx, vaqhip_multi_refiner *r, const float 
   return refine_device_locked(r, d_q, nq, r->w.cand_l.as<int32_t>(), R, k, d_lout, d_dout, st);
 }
 
+// The row calls, for either element type (elem: 4 or 1).  A set replaces the rows and their type on every shard; an
+// append keeps the type of the rows there are, and a refiner without rows takes either.
+int set_rows_any(vaqhip_multi_refiner *r, const void *X, int elem, int64_t N, int64_t id_base) {
+  if (!r) return mfail(VAQHIP_EINVAL, "multi refiner is null");
+  if (N < 0 || (N > 0 && !X)) return mfail(VAQHIP_EINVAL, "bad rows");
+  if (const int rc = check_labels_fit(MULTI_REFINER, N, id_base)) return rc;
+  std::lock_guard<std::mutex> lk(r->mu);
+  DeviceGuard keep(DeviceGuard::restore_only);
+  const vaq::RefineBounds cut = vaq::refine_cut(N, r->G, id_base);
+  if (rows_elem(r) != elem) {  // (the rows there are go either way: a failure below leaves none, not rows misread)
+    for (RShard &s : r->sh) s.lo = s.n = 0, s.rows.retype(elem, r->D);
+    r->N = 0;
+    r->bounds = vaq::refine_cut(0, r->G, r->id_base);
+  }
+  // every shard uploads its own rows, all of them at once
+  if (const int rc = on_shards(r, [&](int g, RShard &s) {
+        MHIP(hipSetDevice(s.device));
+        const int64_t lo = cut.b[g] - id_base, n = cut.b[g + 1] - cut.b[g];
+        const size_t rb = s.rows.row_bytes(r->D);
+        s.n = 0;
+        MHIP(s.rows.reserve(n, RowStore::DROP, r->D));
+        MHIP(hipDeviceSynchronize());
+        if (n > 0) MHIP(hipMemcpy(s.rows.buf.p, static_cast<const char *>(X) + (size_t)lo * rb, (size_t)n * rb, hipMemcpyHostToDevice));
+        s.lo = lo;
+        s.n = n;
+        return 0;
+      })) {
+    // (shards that did upload hold rows of a dataset the others do not: nothing is resident)
+    for (RShard &s : r->sh) s.lo = s.n = 0;
+    r->N = 0;
+    r->bounds = vaq::refine_cut(0, r->G, r->id_base);
+    return rc;
+  }
+  r->N = N;
+  r->id_base = id_base;
+  r->bounds = cut;
+  return VAQHIP_OK;
+}
+
+int add_rows_any(vaqhip_multi_refiner *r, const void *X, int elem, int64_t n_new) {
+  if (!r) return mfail(VAQHIP_EINVAL, "multi refiner is null");
+  if (n_new < 0 || (n_new > 0 && !X)) return mfail(VAQHIP_EINVAL, "bad rows");
+  if (n_new == 0) return VAQHIP_OK;
+  std::lock_guard<std::mutex> lk(r->mu);
+  if (r->N > 0 && rows_elem(r) != elem)
+    return mfail(VAQHIP_ESTATE, "the multi refiner holds %s rows: append rows of that type (nothing is converted)",
+                 rows_elem(r) == 1 ? "uint8" : "float32");
+  if (const int rc = check_labels_fit(MULTI_REFINER, r->N + n_new, r->id_base)) return rc;
+  for (RShard &u : r->sh) u.rows.retype(elem, r->D);  // (only without rows does this change anything)
+  // the new rows continue the numbering, so they extend the LAST shard, as vaqhip_multi_add_codes_u16 does
+  RShard &s = r->sh[r->G - 1];
+  DeviceGuard g(s.device);
+  if (!g.ok) return mfail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", s.device);
+  s.err.clear();
+  auto body = [&]() -> int {
+    const size_t rb = s.rows.row_bytes(r->D);
+    MHIP(s.rows.reserve(s.n + n_new, s.n, r->D));
+    // (rows past s.n are read by no launch in flight: no wait is needed before they are written)
+    MHIP(hipMemcpy(s.rows.buf.as<char>() + (size_t)s.n * rb, X, (size_t)n_new * rb, hipMemcpyHostToDevice));
+    return 0;
+  };
+  if (const int rc = body()) return mfail(rc, "shard %d (device %d): %s", r->G - 1, s.device, s.err.c_str());
+  s.n += n_new;
+  r->N += n_new;
+  vaq::refine_grow_last(r->bounds, n_new);
+  return VAQHIP_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -244,58 +312,20 @@ void vaqhip_multi_refiner_destroy(vaqhip_multi_refiner *r) {
 }
 
 int vaqhip_multi_refiner_set_rows(vaqhip_multi_refiner *r, const float *X, int64_t N, int64_t id_base) {
-  if (!r) return mfail(VAQHIP_EINVAL, "multi refiner is null");
-  if (N < 0 || (N > 0 && !X)) return mfail(VAQHIP_EINVAL, "bad rows");
-  if (const int rc = check_labels_fit(MULTI_REFINER, N, id_base)) return rc;
-  std::lock_guard<std::mutex> lk(r->mu);
-  DeviceGuard keep(DeviceGuard::restore_only);
-  const vaq::RefineBounds cut = vaq::refine_cut(N, r->G, id_base);
-  // every shard uploads its own rows, all of them at once
-  if (const int rc = on_shards(r, [&](int g, RShard &s) {
-        MHIP(hipSetDevice(s.device));
-        const int64_t lo = cut.b[g] - id_base, n = cut.b[g + 1] - cut.b[g];
-        s.n = 0;
-        MHIP(s.rows.reserve(n, RowStore::DROP, r->D));
-        MHIP(hipDeviceSynchronize());
-        if (n > 0) MHIP(hipMemcpy(s.rows.buf.p, X + (size_t)lo * r->D, (size_t)n * r->D * sizeof(float), hipMemcpyHostToDevice));
-        s.lo = lo;
-        s.n = n;
-        return 0;
-      })) {
-    // (shards that did upload hold rows of a dataset the others do not: nothing is resident)
-    for (RShard &s : r->sh) s.lo = s.n = 0;
-    r->N = 0;
-    r->bounds = vaq::refine_cut(0, r->G, r->id_base);
-    return rc;
-  }
-  r->N = N;
-  r->id_base = id_base;
-  r->bounds = cut;
-  return VAQHIP_OK;
+  return set_rows_any(r, X, 4, N, id_base);
+}
+int vaqhip_multi_refiner_add_rows(vaqhip_multi_refiner *r, const float *X, int64_t n_new) { return add_rows_any(r, X, 4, n_new); }
+int vaqhip_multi_refiner_set_rows_u8(vaqhip_multi_refiner *r, const uint8_t *X, int64_t N, int64_t id_base) {
+  return set_rows_any(r, X, 1, N, id_base);
+}
+int vaqhip_multi_refiner_add_rows_u8(vaqhip_multi_refiner *r, const uint8_t *X, int64_t n_new) {
+  return add_rows_any(r, X, 1, n_new);
 }
 
-int vaqhip_multi_refiner_add_rows(vaqhip_multi_refiner *r, const float *X, int64_t n_new) {
+int vaqhip_multi_refiner_elem_size(vaqhip_multi_refiner *r) {
   if (!r) return mfail(VAQHIP_EINVAL, "multi refiner is null");
-  if (n_new < 0 || (n_new > 0 && !X)) return mfail(VAQHIP_EINVAL, "bad rows");
-  if (n_new == 0) return VAQHIP_OK;
   std::lock_guard<std::mutex> lk(r->mu);
-  if (const int rc = check_labels_fit(MULTI_REFINER, r->N + n_new, r->id_base)) return rc;
-  // the new rows continue the numbering, so they extend the LAST shard, as vaqhip_multi_add_codes_u16 does
-  RShard &s = r->sh[r->G - 1];
-  DeviceGuard g(s.device);
-  if (!g.ok) return mfail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", s.device);
-  s.err.clear();
-  auto body = [&]() -> int {
-    MHIP(s.rows.reserve(s.n + n_new, s.n, r->D));
-    // (rows past s.n are read by no launch in flight: no wait is needed before they are written)
-    MHIP(hipMemcpy(s.rows.buf.as<float>() + (size_t)s.n * r->D, X, (size_t)n_new * r->D * sizeof(float), hipMemcpyHostToDevice));
-    return 0;
-  };
-  if (const int rc = body()) return mfail(rc, "shard %d (device %d): %s", r->G - 1, s.device, s.err.c_str());
-  s.n += n_new;
-  r->N += n_new;
-  vaq::refine_grow_last(r->bounds, n_new);
-  return VAQHIP_OK;
+  return rows_elem(r);
 }
 
 int vaqhip_multi_refiner_set_option(vaqhip_multi_refiner *r, const char *key, int64_t value) {

@@ -118,13 +118,16 @@ struct vaqhip_multi_refiner {
 
 namespace vaqhost __attribute__((visibility("hidden"))) {
 
+// the element size of the rows the refiner holds (4 or 1): every shard's store carries it, set together (r->mu held)
+inline int rows_elem(const vaqhip_multi_refiner *r) { return r->sh[0].rows.elem; }
+
 // every stream idle: after a call that failed part-way, before anything it may still read is freed or reused
 void drain(vaqhip_multi_refiner *r);
 
 // Shard g's resident rows for the encode across the shards (vaqhip_multi_encode.cpp), which reads them in place on the
-// shard's device: n rows of D floats, the first with label first_label.  r->mu held; set_rows and add_rows copy
-// synchronously, so the rows are complete.
-struct ResidentRows { const float *rows; int64_t n, first_label; };
+// shard's device: n rows of D floats or bytes (rows.elem), the first with label first_label.  r->mu held; set_rows and
+// add_rows copy synchronously, so the rows are complete.
+struct ResidentRows { vaq::RowsRef rows; int64_t n, first_label; };
 inline ResidentRows resident_rows(const vaqhip_multi_refiner *r, int g) {
   const RShard &s = r->sh[g];
   return ResidentRows{s.rows.rows(), s.n, r->id_base + s.lo};

@@ -222,7 +222,7 @@ int search_device_locked(vaqhip_multi_refiner *r, const float *d_q, int nq, int 
   r->x_timing.register_form = r->D <= (int)vaq::exhaust_register_max_dim();
   if (r->G == 1) {  // the single refiner's launches, at their cost, on the caller's stream
     auto body = [&]() -> int {
-      MHIP(s.xs.work.size_for(s.device, r->D));
+      MHIP(s.xs.work.size_for(s.device, r->D, s.rows.elem));
       const int k1 = exact ? k + 1 : k;
       const XsPlan pl = xs_plan(s.xs.work, r->N, r->opt.splits, nq, k1);
       MHIP(s.xs.work.fit(pl, k1, exact, timing));
@@ -278,7 +278,7 @@ int search_device_locked(vaqhip_multi_refiner *r, const float *d_q, int nq, int 
       RShard &u = r->sh[g];
       if (!xs_takes_part(g, u)) continue;
       if (hipSetDevice(u.device) != hipSuccess) return mfail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", u.device);
-      const hipError_t e = u.xs.work.size_for(u.device, r->D);
+      const hipError_t e = u.xs.work.size_for(u.device, r->D, u.rows.elem);
       if (e != hipSuccess) return mfail(hip_code(e), "device %d: %s", u.device, hipGetErrorString(e));
       u.xs.plan = xs_plan(u.xs.work, u.n, r->opt.splits, nq, k1, max_chunk);
       set = std::min(set, u.xs.plan.chunk);

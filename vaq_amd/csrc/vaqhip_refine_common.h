@@ -56,19 +56,30 @@ template <class Refiner> int set_option(const RefineHost &h, Refiner *r, const c
 }
 
 // One device's raw rows: grow-only, appends grow it geometrically.  Used with its device current.
+// The rows are of one element type, float32 or uint8 (elem: the element's size, 4 or 1); retype() changes it when no
+// row is kept.
 struct RowStore {
   DevBuf buf;
   int64_t cap_rows = 0;  // rows the allocation holds
+  int elem = 4;
   static constexpr int64_t DROP = -1;
-  const float *rows() const { return buf.as<float>(); }
-  // room for `rows` rows of D floats; keep_n >= 0: an append, the first keep_n survive, growth by half at least; DROP: none
+  vaq::RowsRef rows() const { return vaq::RowsRef{buf.p, elem}; }
+  size_t row_bytes(int D) const { return (size_t)D * elem; }
+  // the rows to come are of `elem_size` bytes an element: the allocation stays and holds more or fewer of them.  The
+  // caller keeps no row across the change (a set, or an append to none); no device work.
+  void retype(int elem_size, int D) {
+    if (elem_size == elem) return;
+    elem = elem_size;
+    cap_rows = (int64_t)(buf.cap / row_bytes(D));
+  }
+  // room for `rows` rows of D elements; keep_n >= 0: an append, the first keep_n survive, growth by half at least; DROP: none
   hipError_t reserve(int64_t rows, int64_t keep_n, int D) {
     if (rows <= cap_rows) return hipSuccess;
     const int64_t want = keep_n >= 0 ? std::max(rows, cap_rows + cap_rows / 2) : rows;
     DevBuf nb;
-    XS_TRY(nb.ensure((size_t)want * D * sizeof(float)));
+    XS_TRY(nb.ensure((size_t)want * row_bytes(D)));
     XS_TRY(hipDeviceSynchronize());  // (a refine enqueued on any stream may still read the old rows)
-    if (keep_n > 0) XS_TRY(hipMemcpy(nb.p, buf.p, (size_t)keep_n * D * sizeof(float), hipMemcpyDeviceToDevice));
+    if (keep_n > 0) XS_TRY(hipMemcpy(nb.p, buf.p, (size_t)keep_n * row_bytes(D), hipMemcpyDeviceToDevice));
     std::swap(nb.p, buf.p);
     std::swap(nb.cap, buf.cap);
     cap_rows = want;

@@ -82,7 +82,7 @@ int search_refine_locked(vaqhip_index *ix, vaqhip_refiner *r, const float *d_q, 
 // all sets of one call, enqueued on st; caller holds r->mu, device current
 int search_locked(vaqhip_refiner *r, const float *d_q, int nq, int k, int32_t *d_lout, float *d_dout, hipStream_t st) {
   if (r->rows.cap_rows == 0 && r->N == 0) return fail(VAQHIP_ESTATE, "no rows were set");
-  HIP_TRY(r->xs.size_for(r->device, r->D));
+  HIP_TRY(r->xs.size_for(r->device, r->D, r->rows.elem));
   const bool exact = r->opt.exact != 0;
   const int k1 = exact ? k + 1 : k;
   const XsPlan pl = xs_plan(r->xs, r->N, r->opt.splits, nq, k1);
@@ -113,6 +113,47 @@ template <class Call> int through_staging(vaqhip_refiner *r, int chunk, const fl
   int rc = 0;
   HIP_TRY(through_staging(r->w, r->stream, r->D, chunk, queries, nq, labels_in, R, k, labels_out, distances_out, rc, call));
   return rc;
+}
+
+// The three row calls, for either element type (elem: 4 or 1).  A set replaces the rows and their type; an append
+// keeps the type of the rows there are, and an empty refiner takes either.
+int set_rows_any(vaqhip_refiner *r, const void *X, int elem, bool on_device, int64_t N, int64_t id_base, void *stream) {
+  if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
+  if (N < 0 || (N > 0 && !X)) return fail(VAQHIP_EINVAL, "bad rows");
+  if (int rc = check_labels_fit(REFINER, N, id_base)) return rc;
+  RENTRY(r);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (r->rows.elem != elem) {  // (the rows there are go either way: a failure below leaves none, not rows misread)
+    r->N = 0;
+    r->rows.retype(elem, r->D);
+  }
+  HIP_TRY(r->rows.reserve(N, RowStore::DROP, r->D));
+  HIP_TRY(hipDeviceSynchronize());
+  const size_t bytes = (size_t)N * r->rows.row_bytes(r->D);
+  if (N > 0 && on_device) HIP_TRY(hipMemcpyAsync(r->rows.buf.p, X, bytes, hipMemcpyDeviceToDevice, st));
+  if (on_device) HIP_TRY(hipStreamSynchronize(st));
+  if (N > 0 && !on_device) HIP_TRY(hipMemcpy(r->rows.buf.p, X, bytes, hipMemcpyHostToDevice));
+  r->N = N;
+  r->id_base = id_base;
+  return VAQHIP_OK;
+}
+
+int add_rows_any(vaqhip_refiner *r, const void *X, int elem, int64_t n_new) {
+  if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
+  if (n_new < 0 || (n_new > 0 && !X)) return fail(VAQHIP_EINVAL, "bad rows");
+  if (n_new == 0) return VAQHIP_OK;
+  RENTRY(r);
+  if (r->N > 0 && r->rows.elem != elem)
+    return fail(VAQHIP_ESTATE, "the refiner holds %s rows: append rows of that type (nothing is converted)",
+                r->rows.elem == 1 ? "uint8" : "float32");
+  if (int rc = check_labels_fit(REFINER, r->N + n_new, r->id_base)) return rc;
+  r->rows.retype(elem, r->D);
+  HIP_TRY(r->rows.reserve(r->N + n_new, r->N, r->D));
+  // (rows past N are read by no launch in flight: no wait is needed before they are written)
+  const size_t rb = r->rows.row_bytes(r->D);
+  HIP_TRY(hipMemcpy(r->rows.buf.as<char>() + (size_t)r->N * rb, X, (size_t)n_new * rb, hipMemcpyHostToDevice));
+  r->N += n_new;
+  return VAQHIP_OK;
 }
 
 }  // namespace
@@ -155,45 +196,25 @@ void vaqhip_refiner_destroy(vaqhip_refiner *r) {
 }
 
 int vaqhip_refiner_set_rows_device(vaqhip_refiner *r, const float *d_X, int64_t N, int64_t id_base, void *stream) {
-  if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
-  if (N < 0 || (N > 0 && !d_X)) return fail(VAQHIP_EINVAL, "bad rows");
-  if (int rc = check_labels_fit(REFINER, N, id_base)) return rc;
-  RENTRY(r);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  HIP_TRY(r->rows.reserve(N, RowStore::DROP, r->D));
-  HIP_TRY(hipDeviceSynchronize());
-  if (N > 0) HIP_TRY(hipMemcpyAsync(r->rows.buf.p, d_X, (size_t)N * r->D * sizeof(float), hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  r->N = N;
-  r->id_base = id_base;
-  return VAQHIP_OK;
+  return set_rows_any(r, d_X, 4, true, N, id_base, stream);
 }
-
 int vaqhip_refiner_set_rows(vaqhip_refiner *r, const float *X, int64_t N, int64_t id_base) {
-  if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
-  if (N < 0 || (N > 0 && !X)) return fail(VAQHIP_EINVAL, "bad rows");
-  if (int rc = check_labels_fit(REFINER, N, id_base)) return rc;
-  RENTRY(r);
-  HIP_TRY(r->rows.reserve(N, RowStore::DROP, r->D));
-  HIP_TRY(hipDeviceSynchronize());
-  if (N > 0) HIP_TRY(hipMemcpy(r->rows.buf.p, X, (size_t)N * r->D * sizeof(float), hipMemcpyHostToDevice));
-  r->N = N;
-  r->id_base = id_base;
-  return VAQHIP_OK;
+  return set_rows_any(r, X, 4, false, N, id_base, nullptr);
 }
+int vaqhip_refiner_add_rows(vaqhip_refiner *r, const float *X, int64_t n_new) { return add_rows_any(r, X, 4, n_new); }
 
-int vaqhip_refiner_add_rows(vaqhip_refiner *r, const float *X, int64_t n_new) {
+int vaqhip_refiner_set_rows_u8_device(vaqhip_refiner *r, const uint8_t *d_X, int64_t N, int64_t id_base, void *stream) {
+  return set_rows_any(r, d_X, 1, true, N, id_base, stream);
+}
+int vaqhip_refiner_set_rows_u8(vaqhip_refiner *r, const uint8_t *X, int64_t N, int64_t id_base) {
+  return set_rows_any(r, X, 1, false, N, id_base, nullptr);
+}
+int vaqhip_refiner_add_rows_u8(vaqhip_refiner *r, const uint8_t *X, int64_t n_new) { return add_rows_any(r, X, 1, n_new); }
+
+int vaqhip_refiner_elem_size(vaqhip_refiner *r) {
   if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
-  if (n_new < 0 || (n_new > 0 && !X)) return fail(VAQHIP_EINVAL, "bad rows");
-  if (n_new == 0) return VAQHIP_OK;
-  RENTRY(r);
-  if (int rc = check_labels_fit(REFINER, r->N + n_new, r->id_base)) return rc;
-  HIP_TRY(r->rows.reserve(r->N + n_new, r->N, r->D));
-  // (rows past N are read by no launch in flight: no wait is needed before they are written)
-  HIP_TRY(hipMemcpy(r->rows.buf.as<float>() + (size_t)r->N * r->D, X, (size_t)n_new * r->D * sizeof(float),
-                    hipMemcpyHostToDevice));
-  r->N += n_new;
-  return VAQHIP_OK;
+  std::lock_guard<std::mutex> lk(r->mu);
+  return r->rows.elem;
 }
 
 int vaqhip_refiner_set_option(vaqhip_refiner *r, const char *key, int64_t value) {

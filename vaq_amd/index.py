@@ -607,6 +607,7 @@ class VaqRefiner:
         r.exact_ties = True
         ans = r.refine(XTest, candidates, k)     # candidates: nq x R labels in the order the search returned them
         ans = vaq.search_refine(XTest, R, k, r)  # or fused with the search: the candidates stay on the device
+        r.set_rows_u8(io.read_bvecs_u8(path))    # a bvecs dataset kept as bytes: a quarter of the memory, same answers
     """
 
     def __init__(self, D: int, device: int = 0):
@@ -643,6 +644,39 @@ class VaqRefiner:
         """Append rows; their labels continue behind the rows already held."""
         X = self._rows(X)
         _lib.check(_lib.load().vaqhip_refiner_add_rows(self._h, _ptr(X), X.shape[0]))
+
+    def _rows_u8(self, X) -> np.ndarray:
+        X = np.asarray(X)
+        if X.dtype != np.uint8 or X.ndim != 2 or X.shape[1] != self.D or not X.flags.c_contiguous:
+            raise _lib.VaqHipError(-1, f"byte rows must be a contiguous uint8 n x {self.D} array (nothing is converted)")
+        return X
+
+    def set_rows_u8(self, XTrain, id_base: int = 0) -> None:
+        """Replace the rows by BYTE rows, kept as uint8 on the device (a bvecs dataset as stored): a contiguous np.uint8
+        n x D array, or a contiguous torch.uint8 tensor on the refiner's device (copied).  Every call that reads the rows
+        answers as over XTrain.astype(float32), bit for bit.  set_rows(uint8 array) still widens to float."""
+        if hasattr(XTrain, "data_ptr"):
+            import torch
+            x = XTrain
+            if not (x.is_cuda and x.device.index == self.device and x.dtype == torch.uint8 and x.is_contiguous()
+                    and x.dim() == 2 and x.shape[1] == self.D):
+                raise _lib.VaqHipError(-1, f"device rows must be a contiguous uint8 n x {self.D} tensor on cuda:{self.device}")
+            st = torch.cuda.current_stream(x.device).cuda_stream
+            _lib.check(_lib.load().vaqhip_refiner_set_rows_u8_device(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
+                                                                     int(id_base), C.c_void_p(st)))
+            return
+        X = self._rows_u8(XTrain)
+        _lib.check(_lib.load().vaqhip_refiner_set_rows_u8(self._h, _ptr(X), X.shape[0], int(id_base)))
+
+    def add_rows_u8(self, X) -> None:
+        """Append byte rows to byte rows (or to none); ESTATE (-7) on float rows, as add_rows on byte rows."""
+        X = self._rows_u8(X)
+        _lib.check(_lib.load().vaqhip_refiner_add_rows_u8(self._h, _ptr(X), X.shape[0]))
+
+    @property
+    def elem_size(self) -> int:
+        """Bytes per element of the rows held: 4 (float32) or 1 (uint8)."""
+        return _lib.check(_lib.load().vaqhip_refiner_elem_size(self._h))
 
     @property
     def exact_ties(self) -> bool:
@@ -777,6 +811,27 @@ class VaqMultiRefiner:
         """Append rows; their labels continue behind the rows already held, so they extend the last shard."""
         X = self._rows(X)
         _lib.check_multi(_lib.load().vaqhip_multi_refiner_add_rows(self._h, _ptr(X), X.shape[0]))
+
+    def _rows_u8(self, X) -> np.ndarray:
+        X = np.asarray(X)
+        if X.dtype != np.uint8 or X.ndim != 2 or X.shape[1] != self.D or not X.flags.c_contiguous:
+            raise _lib.VaqHipError(-1, f"byte rows must be a contiguous uint8 n x {self.D} array (nothing is converted)")
+        return X
+
+    def set_rows_u8(self, XTrain, id_base: int = 0) -> None:
+        """set_rows with the rows kept as uint8 on the shards (VaqRefiner.set_rows_u8), cut as set_rows cuts."""
+        X = self._rows_u8(XTrain)
+        _lib.check_multi(_lib.load().vaqhip_multi_refiner_set_rows_u8(self._h, _ptr(X), X.shape[0], int(id_base)))
+
+    def add_rows_u8(self, X) -> None:
+        """Append byte rows to byte rows (or to none): they extend the last shard.  ESTATE (-7) on float rows."""
+        X = self._rows_u8(X)
+        _lib.check_multi(_lib.load().vaqhip_multi_refiner_add_rows_u8(self._h, _ptr(X), X.shape[0]))
+
+    @property
+    def elem_size(self) -> int:
+        """Bytes per element of the rows held: 4 (float32) or 1 (uint8)."""
+        return _lib.check_multi(_lib.load().vaqhip_multi_refiner_elem_size(self._h))
 
     def set_option(self, key: str, value: int) -> None:
         """"exact_ties", "timing", "exhaustive_splits" (per shard: 0 = automatic, 1..64)."""

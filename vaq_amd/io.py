@@ -75,6 +75,11 @@ def read_bvecs(path, max_rows=-1):
     return _read_vecs(path, np.uint8, max_rows).astype(np.float32)
 
 
+def read_bvecs_u8(path, max_rows=-1):
+    """The bytes as the file holds them (np.uint8, n x dim): VaqRefiner.set_rows_u8 keeps them that way."""
+    return _read_vecs(path, np.uint8, max_rows)
+
+
 def write_vecs(path: str, a: np.ndarray) -> None:
     a = np.ascontiguousarray(a)
     n, d = a.shape
