@@ -89,14 +89,20 @@ static int lutMain(std::map<std::string, std::string> &a) {
     detail::File f(a["eigen"], "rb");
     f.read(engine.eigenVectors.data(), sizeof(float), (size_t)D * D);
   }
-  RowMatrixF dataset = readOri(a["dataset"], N, a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1, 0);
+  const int dsize = a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1;
+  RowMatrixF dataset;
+  RowMatrix<uint8_t> dataset8;  // bvecs: the dataset as the file holds it, fitted and encoded from the bytes
+  if (g_bvecs) dataset8 = readBVecsU8(a["dataset"], N, dsize);
+  else dataset = readOri(a["dataset"], N, dsize, 0);
   RowMatrixF queries = readOri(a["queries"], N, std::atoi(a["queries-size"].c_str()), 0);
   const int k = std::atoi(a["k"].c_str());
   CodebookType codebook;
   auto t0 = std::chrono::steady_clock::now();
-  engine.binaryEncodingLUT(dataset, codebook);
+  if (g_bvecs) engine.binaryEncodingLUT(dataset8, codebook);
+  else engine.binaryEncodingLUT(dataset, codebook);
   std::cout << "== Encoding time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
-            << " s (" << codebook.rows() << " rows x " << D << " dimensions, quantile codebooks + codes)" << std::endl;
+            << " s (" << codebook.rows() << " rows x " << D << " dimensions, quantile codebooks + codes"
+            << (g_bvecs ? ", from byte rows" : "") << ")" << std::endl;
   if (engine.multiHandle()) {
     vaqhip_multi_lut_fit_timing ft;
     vaqhip_multi_encode_timing et;
@@ -216,9 +222,16 @@ int main(int argc, char **argv) {
         if (a.count("refine-resident"))
           std::cout << "(--refine-resident without --devices: one device does not encode its resident rows in place, "
                        "the rows are encoded from the host matrix)" << std::endl;
-        RowMatrixF dataset = readOri(a["dataset"], N, dsize, D - N);
-        t0 = std::chrono::steady_clock::now();
-        vaq.encode(dataset, false);
+        if (g_bvecs && N == D) {  // the bytes the file holds: a quarter of the host memory and of the upload
+          RowMatrix<uint8_t> dataset8 = readBVecsU8(a["dataset"], N, dsize);
+          t0 = std::chrono::steady_clock::now();
+          vaq.encode(dataset8, false);
+          std::cout << "(encoded from the byte rows of the bvecs file)" << std::endl;
+        } else {  // (padded rows, D > N, are floats)
+          RowMatrixF dataset = readOri(a["dataset"], N, dsize, D - N);
+          t0 = std::chrono::steady_clock::now();
+          vaq.encode(dataset, false);
+        }
       }
       vaq.mMethods = methods;
       std::cout << "== Encoding time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s ("

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 117
+#define VAQHIP_VERSION 118
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -273,6 +273,16 @@ int vaqhip_encode(vaqhip_index *ix, const float *X_rowmajor, int64_t n, int proj
                   uint16_t *codes_out);
 int vaqhip_encode_device(vaqhip_index *ix, const float *d_X, int64_t n, int projected,
                          uint16_t *d_codes_out, void *stream);
+/* Byte rows: the same calls over uint8 rows, n x D row-major, as a bvecs file stores them.  (float)uint8 is exact and
+ * a byte is widened where the projection loads it, so the codes are those of the float call on the widened matrix,
+ * code for code: the same refusals, codes and chunks; the host form uploads a quarter of the bytes.  Where no
+ * projection runs (projected != 0, or no eigvec on an index that is not VAQHIP_SUM_SEQUENTIAL) a chunk is widened on the
+ * device first.  The _device forms take ANY byte address (a view that starts at an odd offset): packed 4-byte loads
+ * are used only where d_X is 4-byte aligned, and the result is that of an aligned copy.  This holds for every *_u8
+ * call that builds an index below (vaqhip_encode_lut_u8*, vaqhip_lut_fit_quantiles_u8*, vaqhip_multi_*_u8). */
+int vaqhip_encode_u8(vaqhip_index *ix, const uint8_t *X_rowmajor, int64_t n, int projected, uint16_t *codes_out);
+int vaqhip_encode_u8_device(vaqhip_index *ix, const uint8_t *d_X, int64_t n, int projected,
+                            uint16_t *d_codes_out, void *stream);
 
 /* ---------------------------------------------------------------------------
  * Building a queryLUT index: BitVecEngine::binaryEncodingLUT (BitVecEngine.hpp:594-935) from the bit allocation
@@ -306,6 +316,13 @@ int vaqhip_lut_fit_quantiles(int device_id, const float *X_rowmajor, int64_t n, 
 int vaqhip_lut_fit_quantiles_device(int device_id, const float *d_X, int64_t n, int D, const int *bits,
                                     const float *d_eigvec, float *d_centroids_out, float *d_quantiles_out,
                                     void *stream);
+/* the same over uint8 rows (see vaqhip_encode_u8): the float call's result on the widened matrix, bit for bit; with
+ * eigvec the projection widens the bytes, without it the column extract does, and no float copy of the rows is made */
+int vaqhip_lut_fit_quantiles_u8(int device_id, const uint8_t *X_rowmajor, int64_t n, int D, const int *bits,
+                                const float *eigvec_real_rowmajor, float *centroids_out, float *quantiles_out);
+int vaqhip_lut_fit_quantiles_u8_device(int device_id, const uint8_t *d_X, int64_t n, int D, const int *bits,
+                                       const float *d_eigvec, float *d_centroids_out, float *d_quantiles_out,
+                                       void *stream);
 typedef struct {
   float total_ms;                                    /* host time of the last fit on this thread, copies excluded */
   float project_ms;                                  /* only with vaqhip_lut_fit_set_timing(1), else 0: */
@@ -330,6 +347,10 @@ int vaqhip_index_set_lut_quantiles(vaqhip_index *ix, const float *quantiles);
 int vaqhip_encode_lut(vaqhip_index *ix, const float *X_rowmajor, int64_t n, int projected, uint16_t *codes_out);
 int vaqhip_encode_lut_device(vaqhip_index *ix, const float *d_X, int64_t n, int projected, uint16_t *d_codes_out,
                              void *stream);
+/* the same over uint8 rows (see vaqhip_encode_u8) */
+int vaqhip_encode_lut_u8(vaqhip_index *ix, const uint8_t *X_rowmajor, int64_t n, int projected, uint16_t *codes_out);
+int vaqhip_encode_lut_u8_device(vaqhip_index *ix, const uint8_t *d_X, int64_t n, int projected, uint16_t *d_codes_out,
+                                void *stream);
 
 /* VAQ::refine (VAQ.cpp:849-876): exact squared L2 in the ORIGINAL space between each
  * query and its R candidate rows of the raw dataset, k best by the same k-min rule.  The sum is
@@ -594,6 +615,10 @@ int vaqhip_multi_learn_quantization(vaqhip_multi *mx, const float *X_rowmajor, i
  *               shards take their codes: a failure there is vaqhip_multi_set_codes_u16's.
  *   option      "encode_chunk_rows" (vaqhip_multi_set_option): rows per upload / project chunk, 0 = 1 << 20, negative
  *               VAQHIP_EINVAL.  Results do not depend on it.
+ *   byte rows   the *_u8 forms take uint8 rows (vaqhip_encode_u8's contract): every shard uploads ITS slice as bytes,
+ *               chunks of D bytes per row, and encodes it with vaqhip_encode_u8_device; the index ends in the state the
+ *               float form leaves from the widened matrix.  The refiner form over a byte refiner reads the bytes in
+ *               place the same way: no widened chunk is written where a projection runs.
  * Synchronous; the caller's current device is left as it was; serialised with the other calls on the index. */
 int vaqhip_multi_encode_set_codes(vaqhip_multi *mx, const float *X_rowmajor, int64_t N, int projected,
                                   int64_t id_base, uint16_t *codes_out /* N x M, may be NULL */);
@@ -601,6 +626,10 @@ int vaqhip_multi_encode_add_codes(vaqhip_multi *mx, const float *X_rowmajor, int
                                   uint16_t *codes_out /* n_new x M, may be NULL */);
 int vaqhip_multi_encode_from_refiner(vaqhip_multi *mx, vaqhip_multi_refiner *r,
                                      uint16_t *codes_out /* N x M, may be NULL */);
+int vaqhip_multi_encode_set_codes_u8(vaqhip_multi *mx, const uint8_t *X_rowmajor, int64_t N, int projected,
+                                     int64_t id_base, uint16_t *codes_out /* N x M, may be NULL */);
+int vaqhip_multi_encode_add_codes_u8(vaqhip_multi *mx, const uint8_t *X_rowmajor, int64_t n_new, int projected,
+                                     uint16_t *codes_out /* n_new x M, may be NULL */);
 typedef struct {
   float total_ms;      /* wall time of the call                                                   */
   float encode_ms;     /* the slowest shard, device events: upload (host form), project, encode   */
@@ -630,6 +659,10 @@ int vaqhip_multi_encode_lut_add_codes(vaqhip_multi *mx, const float *X_rowmajor,
                                       uint16_t *codes_out /* n_new x M, may be NULL */);
 int vaqhip_multi_encode_lut_from_refiner(vaqhip_multi *mx, vaqhip_multi_refiner *r,
                                          uint16_t *codes_out /* N x M, may be NULL */);
+int vaqhip_multi_encode_lut_set_codes_u8(vaqhip_multi *mx, const uint8_t *X_rowmajor, int64_t N, int projected,
+                                         int64_t id_base, uint16_t *codes_out /* N x M, may be NULL */);
+int vaqhip_multi_encode_lut_add_codes_u8(vaqhip_multi *mx, const uint8_t *X_rowmajor, int64_t n_new, int projected,
+                                         uint16_t *codes_out /* n_new x M, may be NULL */);
 /* The sharded quantile fit: vaqhip_lut_fit_quantiles's result, bit for bit, for ANY device list, with no device ever
  * holding the n x D rows (nor a projected copy of its own slice).
  *   scheme      dimension d is owned by device d % G.  In rounds of G consecutive dimensions every shard turns its
@@ -649,12 +682,18 @@ int vaqhip_multi_encode_lut_from_refiner(vaqhip_multi *mx, vaqhip_multi_refiner 
  *               D < 1 (VAQHIP_EINVAL), D > 4096 (VAQHIP_EUNSUPPORTED), bits outside 1..8; n_devices outside
  *               1..VAQHIP_MAX_DEVICES, a null refiner (VAQHIP_EINVAL), a refiner without rows (VAQHIP_ESTATE).  A NaN or
  *               infinite (projected) value on ANY shard: VAQHIP_EINVAL, both outputs untouched.
- *   byte rows   a refiner that holds uint8 rows (vaqhip_multi_refiner_set_rows_u8) is refused for now,
- *               VAQHIP_EUNSUPPORTED: the column kernel re-reads the rows every round and has no byte form yet.
+ *   byte rows   vaqhip_multi_lut_fit_quantiles_u8 uploads every shard's slice as n_g x D bytes, and a refiner that holds
+ *               uint8 rows (vaqhip_multi_refiner_set_rows_u8) is read in place like one that holds floats: the column
+ *               kernel widens a byte where it loads it, every round, and no n_g x D float copy exists at any time.
+ *               Per shard the call owns what it owns over float rows: G x n_g key words, eigvec and the flag.  The
+ *               result is vaqhip_lut_fit_quantiles's on the widened rows, bit for bit.
  * Synchronous; a failing shard ends the call; the caller's current device is left as it was. */
 int vaqhip_multi_lut_fit_quantiles(int n_devices, const int *device_ids, const float *X_rowmajor, int64_t n, int D,
                                    const int *bits, const float *eigvec_real_rowmajor /* D x D or NULL */,
                                    float *centroids_out /* [D][256] */, float *quantiles_out /* [D][257] */);
+int vaqhip_multi_lut_fit_quantiles_u8(int n_devices, const int *device_ids, const uint8_t *X_rowmajor, int64_t n, int D,
+                                      const int *bits, const float *eigvec_real_rowmajor /* D x D or NULL */,
+                                      float *centroids_out /* [D][256] */, float *quantiles_out /* [D][257] */);
 int vaqhip_multi_refiner_lut_fit_quantiles(vaqhip_multi_refiner *r, const int *bits,
                                            const float *eigvec_real_rowmajor /* D x D or NULL */,
                                            float *centroids_out /* [D][256] */, float *quantiles_out /* [D][257] */);
@@ -721,8 +760,9 @@ const char *vaqhip_multi_last_error(void);
  *   byte rows   vaqhip_multi_refiner_set_rows_u8 / _add_rows_u8 / _elem_size: the single refiner's byte rows with its
  *               rules (one element type for all shards; VAQHIP_ESTATE for an append of the other type), cut as set_rows
  *               cuts, add_rows_u8 extending the last shard.  Refine, the fused call, the exhaustive form and
- *               vaqhip_multi_encode[_lut]_from_refiner (chunks of "encode_chunk_rows" rows widened on the shard, codes
- *               equal to those from the widened host matrix) read them; the sharded quantile fit does not yet.
+ *               vaqhip_multi_encode[_lut]_from_refiner (chunks of "encode_chunk_rows" rows, a byte widened where the
+ *               projection loads it, codes equal to those from the widened host matrix) and
+ *               vaqhip_multi_refiner_lut_fit_quantiles read them in place.
  * ------------------------------------------------------------------------- */
 #define VAQHIP_MULTI_REFINER_SET 16384
 int vaqhip_multi_refiner_create(vaqhip_multi_refiner **out, int D, int n_devices, const int *device_ids);

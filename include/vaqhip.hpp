@@ -321,22 +321,45 @@ public:
   // space (as the reference expects after train()); projected = false applies
   // mEigenVectors first.
   template <class Mat> void encode(const Mat &XTrain, bool projected = true) {
+    encodeRows(XTrain.data(), (int64_t)XTrain.rows(), projected);
+  }
+  // The same from byte rows (a bvecs dataset as its file holds it, vaqhip_io.hpp readBVecsU8): the codes of the float
+  // overload on the widened rows, code for code, from a quarter of the upload (vaqhip_encode_u8,
+  // vaqhip_multi_encode_set_codes_u8 after setDevices()).
+  void encode(const RowMatrix<uint8_t> &XTrain, bool projected = true) {
+    encodeRows(XTrain.data(), (int64_t)XTrain.rows(), projected);
+  }
+
+private:
+  static int encodeCall(vaqhip_index *h, const float *X, int64_t n, int projected, uint16_t *codes) {
+    return vaqhip_encode(h, X, n, projected, codes);
+  }
+  static int encodeCall(vaqhip_index *h, const uint8_t *X, int64_t n, int projected, uint16_t *codes) {
+    return vaqhip_encode_u8(h, X, n, projected, codes);
+  }
+  static int encodeCall(vaqhip_multi *h, const float *X, int64_t n, int projected, int64_t id_base, uint16_t *codes) {
+    return vaqhip_multi_encode_set_codes(h, X, n, projected, id_base, codes);
+  }
+  static int encodeCall(vaqhip_multi *h, const uint8_t *X, int64_t n, int projected, int64_t id_base, uint16_t *codes) {
+    return vaqhip_multi_encode_set_codes_u8(h, X, n, projected, id_base, codes);
+  }
+  template <class T> void encodeRows(const T *X, int64_t n, bool projected) {
     const bool had = codes_set_;
     codes_set_ = true;  // sync() must not try to upload the (empty) codebook first
     try { sync(); } catch (...) { codes_set_ = had; throw; }
     codes_set_ = false;
-    mCodebook = CodebookType((size_t)XTrain.rows(), (size_t)mHighestSubs());
+    mCodebook = CodebookType((size_t)n, (size_t)mHighestSubs());
     if (mh_) {
       // every shard encodes the rows it will hold and keeps their codes (vaqhip.h, "Encode across the shards");
       // mCodebook is filled all the same (saveCodebook and callers read it), but search() need not upload it again
-      checkMulti(vaqhip_multi_encode_set_codes(mh_, XTrain.data(), (int64_t)XTrain.rows(), projected ? 1 : 0, mIdBase,
-                                               mCodebook.data()));
+      checkMulti(encodeCall(mh_, X, n, projected ? 1 : 0, mIdBase, mCodebook.data()));
       codes_set_ = true;
       return;
     }
-    check(vaqhip_encode(h_, XTrain.data(), (int64_t)XTrain.rows(), projected ? 1 : 0, mCodebook.data()));
+    check(encodeCall(h_, X, n, projected ? 1 : 0, mCodebook.data()));
   }
 
+public:
   // encode() from the rows setRefineDataset() left on the devices (after setDevices(); the RAW rows, so mEigenVectors
   // are applied): nothing is uploaded, every shard encodes its resident rows in place, and mCodebook is filled as
   // encode(XTrain, false) fills it.  On one device the rows of a refiner are not encoded in place: VAQHIP_EUNSUPPORTED.
@@ -697,32 +720,60 @@ public:
   std::vector<float> quantiles;  // nonZeroAllocCount x 257: row d = Q[d][0 .. 1 << solutionX[d]], the rest 0
   template <class Mat>
   void binaryEncodingLUT(const Mat &XTrain, CodebookType &codebookOut) {
+    buildFromRows(XTrain.data(), (int64_t)XTrain.rows(), (int)XTrain.cols(), codebookOut);
+  }
+  // The same from byte rows (a bvecs dataset as its file holds it): the members and codebookOut of the float overload
+  // on the widened rows, bit for bit (the *_u8 forms of the same calls).
+  void binaryEncodingLUT(const RowMatrix<uint8_t> &XTrain, CodebookType &codebookOut) {
+    buildFromRows(XTrain.data(), (int64_t)XTrain.rows(), (int)XTrain.cols(), codebookOut);
+  }
+
+private:
+  // the float calls and their byte twins under one name each
+  static int fitCall(int dev, const float *X, int64_t n, int D, const int *bits, const float *eig, float *c, float *q) {
+    return vaqhip_lut_fit_quantiles(dev, X, n, D, bits, eig, c, q);
+  }
+  static int fitCall(int dev, const uint8_t *X, int64_t n, int D, const int *bits, const float *eig, float *c, float *q) {
+    return vaqhip_lut_fit_quantiles_u8(dev, X, n, D, bits, eig, c, q);
+  }
+  static int fitCall(const std::vector<int> &devs, const float *X, int64_t n, int D, const int *bits, const float *eig,
+                     float *c, float *q) {
+    return vaqhip_multi_lut_fit_quantiles((int)devs.size(), devs.data(), X, n, D, bits, eig, c, q);
+  }
+  static int fitCall(const std::vector<int> &devs, const uint8_t *X, int64_t n, int D, const int *bits, const float *eig,
+                     float *c, float *q) {
+    return vaqhip_multi_lut_fit_quantiles_u8((int)devs.size(), devs.data(), X, n, D, bits, eig, c, q);
+  }
+  static int encodeCall(vaqhip_index *h, const float *X, int64_t n, uint16_t *codes) { return vaqhip_encode_lut(h, X, n, 0, codes); }
+  static int encodeCall(vaqhip_index *h, const uint8_t *X, int64_t n, uint16_t *codes) { return vaqhip_encode_lut_u8(h, X, n, 0, codes); }
+  static int encodeCall(vaqhip_multi *h, const float *X, int64_t n, uint16_t *codes) {
+    return vaqhip_multi_encode_lut_set_codes(h, X, n, 0, 0, codes);
+  }
+  static int encodeCall(vaqhip_multi *h, const uint8_t *X, int64_t n, uint16_t *codes) {
+    return vaqhip_multi_encode_lut_set_codes_u8(h, X, n, 0, 0, codes);
+  }
+  template <class T> void buildFromRows(const T *X, int64_t n, int cols, CodebookType &codebookOut) {
     const int nd = (int)solutionX.size();
-    if ((int)XTrain.cols() != nd) throw Error(VAQHIP_EINVAL, "vaqhip: XTrain must have one column per entry of solutionX");
+    if (cols != nd) throw Error(VAQHIP_EINVAL, "vaqhip: XTrain must have one column per entry of solutionX");
     centroidRows = 256;
     std::vector<float> cent((size_t)centroidRows * nd), q((size_t)257 * nd);
     const float *eig = eigenVectors.rows() ? eigenVectors.data() : nullptr;
-    if (mDevices.empty())
-      check(vaqhip_lut_fit_quantiles(mDevice, XTrain.data(), (int64_t)XTrain.rows(), nd, solutionX.data(), eig,
-                                     cent.data(), q.data()));
-    else
-      checkMulti(vaqhip_multi_lut_fit_quantiles((int)mDevices.size(), mDevices.data(), XTrain.data(),
-                                                (int64_t)XTrain.rows(), nd, solutionX.data(), eig, cent.data(), q.data()));
+    if (mDevices.empty()) check(fitCall(mDevice, X, n, nd, solutionX.data(), eig, cent.data(), q.data()));
+    else checkMulti(fitCall(mDevices, X, n, nd, solutionX.data(), eig, cent.data(), q.data()));
     centroidsMat.swap(cent);
     quantiles.swap(q);
     invalidate();
     ensureIndex();
-    codebookOut = CodebookType((size_t)XTrain.rows(), (size_t)nd);
+    codebookOut = CodebookType((size_t)n, (size_t)nd);
     if (mh_) {
       checkMulti(vaqhip_multi_set_lut_quantiles(mh_, quantiles.data()));
-      checkMulti(vaqhip_multi_encode_lut_set_codes(mh_, XTrain.data(), (int64_t)XTrain.rows(), 0, 0, codebookOut.data()));
+      checkMulti(encodeCall(mh_, X, n, codebookOut.data()));
       return;
     }
     check(vaqhip_index_set_lut_quantiles(h_, quantiles.data()));
-    check(vaqhip_encode_lut(h_, XTrain.data(), (int64_t)XTrain.rows(), 0, codebookOut.data()));
+    check(encodeCall(h_, X, n, codebookOut.data()));
   }
 
-private:
   static void checkMulti(int rc) {
     if (rc < 0) throw Error(rc, std::string("vaqhip: ") + vaqhip_multi_last_error());
   }

@@ -49,6 +49,11 @@ SYMBOLS = [
     "vaqhip_multi_refiner_refine_device", "vaqhip_multi_search_refine", "vaqhip_multi_search_refine_device",
     "vaqhip_multi_refiner_get_info",
     "vaqhip_multi_refiner_search", "vaqhip_multi_refiner_search_device", "vaqhip_multi_refiner_last_search_timing",
+    "vaqhip_encode_u8", "vaqhip_encode_u8_device", "vaqhip_encode_lut_u8", "vaqhip_encode_lut_u8_device",
+    "vaqhip_lut_fit_quantiles_u8", "vaqhip_lut_fit_quantiles_u8_device",
+    "vaqhip_multi_encode_set_codes_u8", "vaqhip_multi_encode_add_codes_u8",
+    "vaqhip_multi_encode_lut_set_codes_u8", "vaqhip_multi_encode_lut_add_codes_u8",
+    "vaqhip_multi_lut_fit_quantiles_u8",
 ]
 MAX_DEVICES = 16
 
@@ -265,6 +270,13 @@ def load():
     L.vaqhip_multi_refiner_search.argtypes = [vp, vp, i32, i32, vp, vp]
     L.vaqhip_multi_refiner_search_device.argtypes = [vp, vp, i32, i32, vp, vp, vp]
     L.vaqhip_multi_refiner_last_search_timing.argtypes = [vp, C.POINTER(MultiRefinerSearchTiming)]
+    for name in ("vaqhip_encode", "vaqhip_encode_device", "vaqhip_encode_lut", "vaqhip_encode_lut_device",
+                 "vaqhip_lut_fit_quantiles", "vaqhip_lut_fit_quantiles_device", "vaqhip_multi_encode_set_codes",
+                 "vaqhip_multi_encode_add_codes", "vaqhip_multi_encode_lut_set_codes",
+                 "vaqhip_multi_encode_lut_add_codes", "vaqhip_multi_lut_fit_quantiles"):
+        # the byte-row twins: the float call's argument list, the rows a void pointer either way
+        u8 = name[:-len("_device")] + "_u8_device" if name.endswith("_device") else name + "_u8"
+        getattr(L, u8).argtypes = getattr(L, name).argtypes
     for name in SYMBOLS:
         fn = getattr(L, name)
         if fn.restype is C.c_int:

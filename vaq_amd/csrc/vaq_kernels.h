@@ -163,7 +163,18 @@ struct RowsRef {
   const void *p;
   int elem;
 };
+// the rows from element `elems` on
+inline RowsRef rows_at(RowsRef r, size_t elems) {
+  return RowsRef{static_cast<const char *>(r.p) + elems * (size_t)r.elem, r.elem};
+}
 size_t refine_rows_max_dim();
+// lut_fit_columns over rows of either type: a byte is widened where the extract loads it
+hipError_t lut_fit_columns(RowsRef d_Xp, int64_t n, int D, const int *bits, float *d_cent_out, float *d_q_out,
+                           int *d_bad, float *phase_ms, hipStream_t st);
+// launch_project over rows of either type: byte rows are widened where they are loaded, every output is the float
+// form's fmaf chain on the float form's operands (any byte address: the tile kernel's packed loads are taken only
+// where X is 4-byte aligned)
+hipError_t launch_project(RowsRef X, int64_t n, int D, const float *E, float *out, hipStream_t st, int checked = 0);
 hipError_t launch_refine_rows(const float *Q, int nq, int D, RowsRef rows, int64_t N, int64_t id_base,
                               const int32_t *labels_in, int R, int k, int exact, int32_t *labels, float *dist,
                               hipStream_t st);
@@ -176,8 +187,8 @@ hipError_t launch_refine_dist(const float *Q, int nq, int D, RowsRef rows, int64
 hipError_t launch_refine_select(const int32_t *labels_in, int nq, const float *planes, size_t plane_stride,
                                 const RefineBounds &bounds, int R, int k, int exact, int32_t *labels, float *dist,
                                 hipStream_t st);
-// n x D byte rows widened to float (dst[i] = (float)src[i]): the encoders read float rows, a byte refiner's chunk
-// goes through here first
+// n x D byte rows widened to float (dst[i] = (float)src[i]): the encoders read float rows, so a chunk of byte rows
+// that no projection turns into floats goes through here first
 hipError_t launch_widen_rows_u8(const uint8_t *src, int64_t elems, float *dst, hipStream_t st);
 // ---- the exhaustive form of VAQ::refine (vaq_exhaust.hip): every resident row a candidate, in row order ----
 constexpr int XS_TILE = 256;      // rows a workgroup takes at a time

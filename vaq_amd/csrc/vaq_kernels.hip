@@ -32,13 +32,16 @@ namespace vaq {
 // by queryLUT at :1226): a coordinate that comes out NaN or infinite is replaced by 0.  E == nullptr
 // stands for the identity matrix: the product z * I is then NaN in EVERY column as soon as one
 // component of z is not finite (NaN * 0 and inf * 0 are NaN), i.e. the whole row becomes 0.
-__global__ void project_kernel(const float *__restrict__ X, int D,
+// T: the rows' element, float or uint8_t (RowsRef).  A byte is widened where it is loaded ((float)uint8 is exact) and
+// sits in LDS as the float the float form would have loaded: nothing after the load differs.
+template <typename T>
+__global__ void project_kernel(const T *__restrict__ X, int D,
                                const float *__restrict__ E, float *__restrict__ out, int checked) {
   extern __shared__ float xs[];
   __shared__ int bad;
   const int64_t r = blockIdx.x;
   if (threadIdx.x == 0) bad = 0;
-  for (int j = threadIdx.x; j < D; j += blockDim.x) xs[j] = X[r * D + j];
+  for (int j = threadIdx.x; j < D; j += blockDim.x) xs[j] = (float)X[r * D + j];
   __syncthreads();
   if (!E) {
     for (int j = threadIdx.x; j < D; j += blockDim.x)
@@ -62,8 +65,25 @@ __global__ void project_kernel(const float *__restrict__ X, int D,
 // wave: a broadcast).  Every output is still ONE fmaf chain over the inner index ascending from 0,
 // so the result is bit for bit the one-row-per-workgroup kernel's; per four inner steps a thread
 // issues 4 loads of E, RPT LDS reads and 4 RPT FMAs.
-template <int D_, int RPT>
-__global__ __launch_bounds__(256) void project_tile_kernel(const float *__restrict__ X, int64_t n,
+// Byte rows (T = uint8_t) are widened on the way INTO LDS, so the FMA loop below reads the floats it always read.  Four
+// consecutive bytes come in as one dword where the source is 4-byte aligned (PACKED; a tile starts at a multiple of D_
+// bytes, so that is the alignment of X itself) and as four byte loads where it is not: a quarter of the float form's
+// bytes either way, and no misaligned dword load.
+template <bool PACKED>
+__device__ __forceinline__ float4 project_load4(const float *p) {
+  return *reinterpret_cast<const float4 *>(p);
+}
+template <bool PACKED>
+__device__ __forceinline__ float4 project_load4(const uint8_t *p) {
+  if (PACKED) {
+    const uint32_t w = *reinterpret_cast<const uint32_t *>(p);
+    return make_float4((float)(w & 0xffu), (float)((w >> 8) & 0xffu), (float)((w >> 16) & 0xffu), (float)(w >> 24));
+  }
+  return make_float4((float)p[0], (float)p[1], (float)p[2], (float)p[3]);
+}
+
+template <int D_, int RPT, typename T, bool PACKED>
+__global__ __launch_bounds__(256) void project_tile_kernel(const T *__restrict__ X, int64_t n,
                                                            const float *__restrict__ E, float *__restrict__ out,
                                                            int checked) {
   constexpr int G = 256 / D_, R = G * RPT;
@@ -73,7 +93,7 @@ __global__ __launch_bounds__(256) void project_tile_kernel(const float *__restri
   for (int i = tid; i < R * D_ / 4; i += 256) {
     const int64_t row = row0 + (i * 4) / D_;
     float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (row < n) v = reinterpret_cast<const float4 *>(X + row0 * D_)[i];
+    if (row < n) v = project_load4<PACKED>(X + row0 * D_ + (int64_t)i * 4);
     reinterpret_cast<float4 *>(xs)[i] = v;
   }
   __syncthreads();
@@ -113,18 +133,29 @@ __global__ __launch_bounds__(256) void project_tile_kernel(const float *__restri
 constexpr int64_t PROJECT_TILE_MIN_ROWS = VAQ_PROJECT_TILE_MIN;
 constexpr int64_t PROJECT_TILE_BIG_ROWS = 65536;
 
-template <int RPT>
-static hipError_t launch_project_tile(const float *X, int64_t n, int D, const float *E, float *out, hipStream_t st, int checked) {
+template <int RPT, typename T, bool PACKED>
+static hipError_t launch_project_tile_as(const T *X, int64_t n, int D, const float *E, float *out, hipStream_t st, int checked) {
   const int R = (256 / D) * RPT;
   const dim3 grid((unsigned)((n + R - 1) / R));
-  if (D == 64) hipLaunchKernelGGL((project_tile_kernel<64, RPT>), grid, dim3(256), 0, st, X, n, E, out, checked);
-  else if (D == 128) hipLaunchKernelGGL((project_tile_kernel<128, RPT>), grid, dim3(256), 0, st, X, n, E, out, checked);
-  else hipLaunchKernelGGL((project_tile_kernel<256, RPT>), grid, dim3(256), 0, st, X, n, E, out, checked);
+  if (D == 64) hipLaunchKernelGGL((project_tile_kernel<64, RPT, T, PACKED>), grid, dim3(256), 0, st, X, n, E, out, checked);
+  else if (D == 128) hipLaunchKernelGGL((project_tile_kernel<128, RPT, T, PACKED>), grid, dim3(256), 0, st, X, n, E, out, checked);
+  else hipLaunchKernelGGL((project_tile_kernel<256, RPT, T, PACKED>), grid, dim3(256), 0, st, X, n, E, out, checked);
   return hipGetLastError();
 }
 
-hipError_t launch_project(const float *X, int64_t n, int D, const float *E, float *out,
-                          hipStream_t st, int checked) {
+template <int RPT>
+static hipError_t launch_project_tile(const float *X, int64_t n, int D, const float *E, float *out, hipStream_t st, int checked) {
+  return launch_project_tile_as<RPT, float, true>(X, n, D, E, out, st, checked);
+}
+// byte rows: a device caller may hand over any address (a view that starts at an odd byte)
+template <int RPT>
+static hipError_t launch_project_tile(const uint8_t *X, int64_t n, int D, const float *E, float *out, hipStream_t st, int checked) {
+  if ((reinterpret_cast<uintptr_t>(X) & 3u) == 0) return launch_project_tile_as<RPT, uint8_t, true>(X, n, D, E, out, st, checked);
+  return launch_project_tile_as<RPT, uint8_t, false>(X, n, D, E, out, st, checked);
+}
+
+template <typename T>
+static hipError_t launch_project_rows(const T *X, int64_t n, int D, const float *E, float *out, hipStream_t st, int checked) {
   if (n == 0) return hipSuccess;
   if (E && n >= PROJECT_TILE_MIN_ROWS && (D == 64 || D == 128 || D == 256)) {
     if (n >= PROJECT_TILE_BIG_ROWS) return launch_project_tile<16>(X, n, D, E, out, st, checked);
@@ -133,9 +164,20 @@ hipError_t launch_project(const float *X, int64_t n, int D, const float *E, floa
   // (one workgroup per row: batching 8 rows per workgroup, as the LUT build does with queries,
   //  was measured slower here -- 0.044 vs 0.030 ms for 10 k rows: too few workgroups to fill the chip)
   int threads = D < 256 ? ((D + 63) / 64) * 64 : 256;
-  hipLaunchKernelGGL(project_kernel, dim3((unsigned)n), dim3(threads), D * sizeof(float), st, X, D,
+  hipLaunchKernelGGL(project_kernel<T>, dim3((unsigned)n), dim3(threads), D * sizeof(float), st, X, D,
                      E, out, checked);
   return hipGetLastError();
+}
+
+hipError_t launch_project(const float *X, int64_t n, int D, const float *E, float *out,
+                          hipStream_t st, int checked) {
+  return launch_project_rows(X, n, D, E, out, st, checked);
+}
+
+hipError_t launch_project(RowsRef X, int64_t n, int D, const float *E, float *out, hipStream_t st, int checked) {
+  if (X.elem == 1) return launch_project_rows(static_cast<const uint8_t *>(X.p), n, D, E, out, st, checked);
+  if (X.elem != 4) return hipErrorInvalidValue;
+  return launch_project_rows(static_cast<const float *>(X.p), n, D, E, out, st, checked);
 }
 
 // ---------------------------------------------------------------------------

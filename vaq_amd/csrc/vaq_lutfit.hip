@@ -28,12 +28,14 @@ namespace {
 
 using namespace lutfit;
 
-__global__ __launch_bounds__(256) void lutfit_extract_kernel(const float *__restrict__ Xp, int64_t n, int D, int d,
+// T: the rows' element, float or uint8_t (RowsRef).  A byte is widened where it is loaded, (float)uint8 is exact.
+template <typename T>
+__global__ __launch_bounds__(256) void lutfit_extract_kernel(const T *__restrict__ Xp, int64_t n, int D, int d,
                                                              uint32_t *__restrict__ keys, int *__restrict__ bad) {
   const int64_t stride = (int64_t)gridDim.x * 256;
   bool any_bad = false;
   for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += stride) {
-    const float x = Xp[r * D + d];
+    const float x = (float)Xp[r * D + d];
     any_bad = any_bad || !is_finite(x);
     keys[r] = float_to_key(x);
   }
@@ -50,10 +52,14 @@ __global__ __launch_bounds__(256) void lutfit_extract_kernel(const float *__rest
 // 16 accumulators, the tile value and the addresses stay far below the 128 VGPRs at which a SIMD still holds four
 // waves; LDS (33 KB) allows four workgroups per CU.  Rows and offsets are 64-bit: a shard of 125M x 128 has 1.6e10
 // elements.
+// Byte rows (T = uint8_t): the tile load and the transposing extract widen each byte as they load it, the tile holds
+// floats and everything behind the load is unchanged.  The loads stay one element per lane -- a half-wave reads 32
+// consecutive bytes of a row -- so they need no alignment (D = 5 or 33 puts a row at any byte) and the LDS pattern,
+// stride 33, is the float form's: the same instructions on a quarter of the bytes.
 constexpr int PC_ROWS = 256, PC_JT = 32, PC_STRIDE = PC_JT + 1, PC_MAX_W = 16;
 
-template <int W>
-__global__ __launch_bounds__(PC_ROWS) void lutfit_project_columns_kernel(const float *__restrict__ X, int64_t n, int D,
+template <int W, typename T>
+__global__ __launch_bounds__(PC_ROWS) void lutfit_project_columns_kernel(const T *__restrict__ X, int64_t n, int D,
                                                                          const float *__restrict__ E, int d0,
                                                                          uint32_t *__restrict__ keys,
                                                                          int *__restrict__ bad) {
@@ -69,7 +75,7 @@ __global__ __launch_bounds__(PC_ROWS) void lutfit_project_columns_kernel(const f
     if (!E) {  // a transposing extract: the row's own values
       if (row < n) {
 #pragma unroll
-        for (int w = 0; w < W; w++) acc[w] = X[row * D + d0 + w];
+        for (int w = 0; w < W; w++) acc[w] = (float)X[row * D + d0 + w];
       }
     } else {
       for (int j0 = 0; j0 < D; j0 += PC_JT) {
@@ -78,7 +84,7 @@ __global__ __launch_bounds__(PC_ROWS) void lutfit_project_columns_kernel(const f
         for (int i = 0; i < PC_JT; i++) {  // (PC_ROWS x PC_JT values by PC_ROWS threads)
           const int r = i * (PC_ROWS / PC_JT) + r8;
           const int64_t src = row0 + r;
-          tile[r * PC_STRIDE + c] = (src < n && j0 + c < D) ? X[src * D + j0 + c] : 0.0f;
+          tile[r * PC_STRIDE + c] = (src < n && j0 + c < D) ? (float)X[src * D + j0 + c] : 0.0f;
         }
         __syncthreads();
         const int jn = D - j0 < PC_JT ? D - j0 : PC_JT;
@@ -226,21 +232,31 @@ hipError_t launch_lut_encode(const float *Xp, int64_t n, int D, const SubDesc *h
   return hipSuccess;
 }
 
-hipError_t launch_lutfit_project_columns(const float *X, int64_t n, int D, const float *E, int d0, int W, uint32_t *keys,
-                                         int *d_bad, hipStream_t st) {
+namespace {
+template <typename T>
+hipError_t project_columns_as(const T *X, int64_t n, int D, const float *E, int d0, int W, uint32_t *keys, int *d_bad,
+                              hipStream_t st) {
   if (n == 0 || W == 0) return hipSuccess;
   if (W < 0 || W > PC_MAX_W || d0 < 0 || d0 + W > D) return hipErrorInvalidValue;
   const dim3 grid((unsigned)std::min<int64_t>((n + PC_ROWS - 1) / PC_ROWS, 4096));
   switch (W) {
 #define PC_CASE(w)                                                                                                   \
   case w:                                                                                                            \
-    hipLaunchKernelGGL((lutfit_project_columns_kernel<w>), grid, dim3(PC_ROWS), 0, st, X, n, D, E, d0, keys, d_bad); \
+    hipLaunchKernelGGL((lutfit_project_columns_kernel<w, T>), grid, dim3(PC_ROWS), 0, st, X, n, D, E, d0, keys, d_bad); \
     break;
     PC_CASE(1) PC_CASE(2) PC_CASE(3) PC_CASE(4) PC_CASE(5) PC_CASE(6) PC_CASE(7) PC_CASE(8)
     PC_CASE(9) PC_CASE(10) PC_CASE(11) PC_CASE(12) PC_CASE(13) PC_CASE(14) PC_CASE(15) PC_CASE(16)
 #undef PC_CASE
   }
   return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_lutfit_project_columns(RowsRef X, int64_t n, int D, const float *E, int d0, int W, uint32_t *keys,
+                                         int *d_bad, hipStream_t st) {
+  if (X.elem == 1) return project_columns_as(static_cast<const uint8_t *>(X.p), n, D, E, d0, W, keys, d_bad, st);
+  if (X.elem != 4) return hipErrorInvalidValue;
+  return project_columns_as(static_cast<const float *>(X.p), n, D, E, d0, W, keys, d_bad, st);
 }
 
 hipError_t LutFitColumnWork::ensure(int64_t n, hipStream_t st) {
@@ -277,6 +293,12 @@ hipError_t lut_fit_column_from_keys(LutFitColumnWork &w, int64_t n, int bits, fl
 // phase_ms (optional) [4]: extract, sort, quantiles, means, summed over the columns (device events).
 hipError_t lut_fit_columns(const float *d_Xp, int64_t n, int D, const int *bits, float *d_cent_out, float *d_q_out,
                            int *d_bad, float *phase_ms, hipStream_t st) {
+  return lut_fit_columns(RowsRef{d_Xp, 4}, n, D, bits, d_cent_out, d_q_out, d_bad, phase_ms, st);
+}
+
+hipError_t lut_fit_columns(RowsRef d_Xp, int64_t n, int D, const int *bits, float *d_cent_out, float *d_q_out,
+                           int *d_bad, float *phase_ms, hipStream_t st) {
+  if (d_Xp.elem != 4 && d_Xp.elem != 1) return hipErrorInvalidValue;
   LutFitColumnWork w;
   LF_TRY(w.ensure(n, st));
   LF_TRY(hipMemsetAsync(d_bad, 0, sizeof(int), st));
@@ -295,8 +317,12 @@ hipError_t lut_fit_columns(const float *d_Xp, int64_t n, int D, const int *bits,
   for (int d = 0; d < D; d++) {
     hipEvent_t *e = phase_ms ? ev.data() + (size_t)d * 5 : nullptr;
     if (e) LF_TRY(hipEventRecord(e[0], st));
-    hipLaunchKernelGGL(lutfit_extract_kernel, dim3(ex_grid), dim3(256), 0, st, d_Xp, n, D, d, w.keys.as<uint32_t>(),
-                       d_bad);
+    if (d_Xp.elem == 1)
+      hipLaunchKernelGGL(lutfit_extract_kernel<uint8_t>, dim3(ex_grid), dim3(256), 0, st,
+                         static_cast<const uint8_t *>(d_Xp.p), n, D, d, w.keys.as<uint32_t>(), d_bad);
+    else
+      hipLaunchKernelGGL(lutfit_extract_kernel<float>, dim3(ex_grid), dim3(256), 0, st,
+                         static_cast<const float *>(d_Xp.p), n, D, d, w.keys.as<uint32_t>(), d_bad);
     LF_TRY(hipGetLastError());
     // (e[1], the end of the extract, is the column fit's first event)
     LF_TRY(lut_fit_column_from_keys(w, n, bits[d], d_q_out + (size_t)d * MAX_Q, d_cent_out + (size_t)d * MAX_CENT,

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "vaq_kernels.h"
 #include "vaqhip_dev.h"
 
 namespace vaq {
@@ -26,8 +27,9 @@ hipError_t lut_fit_column_from_keys(LutFitColumnWork &w, int64_t n, int bits, fl
 
 // Columns [d0, d0 + W), W <= 16, of the n x D rows X as sortable keys: keys[w * n + r] = float_to_key(y), y = the
 // row's own value (E null) or ONE fmaf chain over the inner index ascending from acc = 0.0f (launch_project's value,
-// bit for bit); *d_bad is ORed with 1 when a y is not finite.  Enqueues only.
-hipError_t launch_lutfit_project_columns(const float *X, int64_t n, int D, const float *E, int d0, int W, uint32_t *keys,
+// bit for bit); *d_bad is ORed with 1 when a y is not finite.  X: float or byte rows at any byte address, a byte
+// widened where it is loaded.  Enqueues only.
+hipError_t launch_lutfit_project_columns(RowsRef X, int64_t n, int D, const float *E, int d0, int W, uint32_t *keys,
                                          int *d_bad, hipStream_t st);
 
 }  // namespace vaq

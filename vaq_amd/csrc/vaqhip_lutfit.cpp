@@ -27,16 +27,16 @@ int check_fit_args(int64_t n, int D, const int *bits, const void *X, const void 
 }
 
 // device pointers throughout, the device current; the outputs are written only when the fit succeeds
-int fit_core(const float *d_X, int64_t n, int D, const int *bits, const float *d_eig, float *d_cent_out, float *d_q_out,
+int fit_core(vaq::RowsRef d_X, int64_t n, int D, const int *bits, const float *d_eig, float *d_cent_out, float *d_q_out,
              hipStream_t st) {
   const auto t0 = std::chrono::steady_clock::now();
   DevBuf b_proj, b_cent, b_q, b_bad;
   float project_ms = 0.0f;
-  const float *xp = d_X;
+  vaq::RowsRef xp = d_X;  // (byte rows without a rotation: the extract widens them, no float copy)
   if (d_eig) {  // unchecked, as :620 projects the training rows
     HIP_TRY(b_proj.ensure((size_t)n * D * sizeof(float)));
     HIP_TRY(vaq::launch_project(d_X, n, D, d_eig, b_proj.as<float>(), st, 0));
-    xp = b_proj.as<float>();
+    xp = vaq::RowsRef{b_proj.p, 4};
     if (g_fit_timing) {
       HIP_TRY(hipStreamSynchronize(st));
       project_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -74,17 +74,23 @@ int check_encode_args(const vaqhip_index *ix, const void *X, int64_t n, const vo
   return VAQHIP_OK;
 }
 
-// core of vaqhip_encode_lut*: caller holds ix->mu and has the device current
-int encode_lut_locked(vaqhip_index *ix, const float *d_X, int64_t n, int projected, uint16_t *d_codes, hipStream_t st) {
+// core of vaqhip_encode_lut*: caller holds ix->mu and has the device current.  d_X: float or byte rows; byte rows are
+// widened by the projection's own load, or without a projection by launch_widen_rows_u8 into the projection's buffer
+int encode_lut_locked(vaqhip_index *ix, vaq::RowsRef d_X, int64_t n, int projected, uint16_t *d_codes, hipStream_t st) {
   const bool do_project = !projected && ix->has_eig;  // unchecked (:620); without a rotation the rows are their own image
+  const bool widen = !do_project && d_X.elem == 1;
   const int64_t chunk = std::min<int64_t>(n, 1 << 20);
-  if (do_project) HIP_TRY(ix->w_qproj.ensure((size_t)chunk * ix->D * sizeof(float)));
+  if (do_project || widen) HIP_TRY(ix->w_qproj.ensure((size_t)chunk * ix->D * sizeof(float)));
   WS_SCOPE(ws, ix, st);
   for (int64_t r = 0; r < n; r += chunk) {
     const int64_t m = std::min(chunk, n - r);
-    const float *xp = d_X + r * ix->D;
+    const vaq::RowsRef x = vaq::rows_at(d_X, (size_t)r * ix->D);
+    const float *xp = static_cast<const float *>(x.p);
     if (do_project) {
-      HIP_TRY(vaq::launch_project(xp, m, ix->D, ix->d_eig.as<float>(), ix->w_qproj.as<float>(), st, 0));
+      HIP_TRY(vaq::launch_project(x, m, ix->D, ix->d_eig.as<float>(), ix->w_qproj.as<float>(), st, 0));
+      xp = ix->w_qproj.as<float>();
+    } else if (widen) {
+      HIP_TRY(vaq::launch_widen_rows_u8(static_cast<const uint8_t *>(x.p), m * ix->D, ix->w_qproj.as<float>(), st));
       xp = ix->w_qproj.as<float>();
     }
     HIP_TRY(vaq::launch_lut_encode(xp, m, ix->D, ix->sub.data(), ix->d_sub.as<vaq::SubDesc>(), ix->d_lut_pm.as<float>(),
@@ -92,29 +98,28 @@ int encode_lut_locked(vaqhip_index *ix, const float *d_X, int64_t n, int project
   }
   return ws.finish();
 }
-}  // namespace
 
-extern "C" {
-
-int vaqhip_lut_fit_quantiles_device(int device_id, const float *d_X, int64_t n, int D, const int *bits,
-                                    const float *d_eigvec, float *d_centroids_out, float *d_quantiles_out, void *stream) {
-  if (int rc = check_fit_args(n, D, bits, d_X, d_centroids_out, d_quantiles_out)) return rc;
+int fit_device_entry(int device_id, vaq::RowsRef d_X, int64_t n, int D, const int *bits, const float *d_eigvec,
+                     float *d_centroids_out, float *d_quantiles_out, void *stream) {
+  if (int rc = check_fit_args(n, D, bits, d_X.p, d_centroids_out, d_quantiles_out)) return rc;
   DeviceGuard g(device_id);
   if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed (no CPU path)", device_id);
   return fit_core(d_X, n, D, bits, d_eigvec, d_centroids_out, d_quantiles_out, static_cast<hipStream_t>(stream));
 }
 
-int vaqhip_lut_fit_quantiles(int device_id, const float *X, int64_t n, int D, const int *bits, const float *eigvec,
-                             float *centroids_out, float *quantiles_out) {
-  if (int rc = check_fit_args(n, D, bits, X, centroids_out, quantiles_out)) return rc;
+// X: host rows of X.elem bytes per element, uploaded as they are
+int fit_host_entry(int device_id, vaq::RowsRef X, int64_t n, int D, const int *bits, const float *eigvec,
+                   float *centroids_out, float *quantiles_out) {
+  if (int rc = check_fit_args(n, D, bits, X.p, centroids_out, quantiles_out)) return rc;
   DeviceGuard g(device_id);
   if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed (no CPU path)", device_id);
   DevBuf d_x, d_eig, d_cent, d_q;
   const size_t cent_bytes = (size_t)D * lf::MAX_CENT * sizeof(float), q_bytes = (size_t)D * lf::MAX_Q * sizeof(float);
-  HIP_TRY(d_x.ensure((size_t)n * D * sizeof(float)));
+  const size_t x_bytes = (size_t)n * D * (size_t)X.elem;
+  HIP_TRY(d_x.ensure(x_bytes));
   HIP_TRY(d_cent.ensure(cent_bytes));
   HIP_TRY(d_q.ensure(q_bytes));
-  HIP_TRY(hipMemcpy(d_x.p, X, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(d_x.p, X.p, x_bytes, hipMemcpyHostToDevice));
   if (eigvec) {
     HIP_TRY(d_eig.ensure((size_t)D * D * sizeof(float)));
     HIP_TRY(hipMemcpy(d_eig.p, eigvec, (size_t)D * D * sizeof(float), hipMemcpyHostToDevice));
@@ -125,12 +130,60 @@ int vaqhip_lut_fit_quantiles(int device_id, const float *X, int64_t n, int D, co
     hipStream_t s;
     ~StreamFree() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
   } stream_free{st};
-  if (int rc = fit_core(d_x.as<float>(), n, D, bits, eigvec ? d_eig.as<float>() : nullptr, d_cent.as<float>(),
+  if (int rc = fit_core(vaq::RowsRef{d_x.p, X.elem}, n, D, bits, eigvec ? d_eig.as<float>() : nullptr, d_cent.as<float>(),
                         d_q.as<float>(), st))
     return rc;
   HIP_TRY(hipMemcpy(centroids_out, d_cent.p, cent_bytes, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(quantiles_out, d_q.p, q_bytes, hipMemcpyDeviceToHost));
   return VAQHIP_OK;
+}
+
+int encode_lut_device_entry(vaqhip_index *ix, vaq::RowsRef d_X, int64_t n, int projected, uint16_t *d_codes, void *stream) {
+  if (int rc = check_encode_args(ix, d_X.p, n, d_codes)) return rc;
+  if (n == 0) return VAQHIP_OK;
+  ENTRY(ix);
+  return encode_lut_locked(ix, d_X, n, projected, d_codes, static_cast<hipStream_t>(stream));
+}
+
+int encode_lut_host_entry(vaqhip_index *ix, vaq::RowsRef X, int64_t n, int projected, uint16_t *codes) {
+  if (int rc = check_encode_args(ix, X.p, n, codes)) return rc;
+  if (n == 0) return VAQHIP_OK;
+  const int64_t chunk = std::min<int64_t>(n, 1 << 20);
+  ENTRY(ix);
+  HIP_TRY(ix->w_q.ensure((size_t)chunk * ix->D * (size_t)X.elem));
+  HIP_TRY(ix->w_stage.ensure((size_t)chunk * ix->M * sizeof(uint16_t)));
+  WS_SCOPE(ws, ix, ix->stream);
+  for (int64_t r = 0; r < n; r += chunk) {
+    const int64_t m = std::min(chunk, n - r);
+    HIP_TRY(hipMemcpyAsync(ix->w_q.p, vaq::rows_at(X, (size_t)r * ix->D).p, (size_t)m * ix->D * (size_t)X.elem,
+                           hipMemcpyHostToDevice, ix->stream));
+    if (int rc = encode_lut_locked(ix, vaq::RowsRef{ix->w_q.p, X.elem}, m, projected, ix->w_stage.as<uint16_t>(), ix->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(codes + r * ix->M, ix->w_stage.p, (size_t)m * ix->M * sizeof(uint16_t),
+                           hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+  }
+  return ws.finish();
+}
+}  // namespace
+
+extern "C" {
+
+int vaqhip_lut_fit_quantiles_device(int device_id, const float *d_X, int64_t n, int D, const int *bits,
+                                    const float *d_eigvec, float *d_centroids_out, float *d_quantiles_out, void *stream) {
+  return fit_device_entry(device_id, vaq::RowsRef{d_X, 4}, n, D, bits, d_eigvec, d_centroids_out, d_quantiles_out, stream);
+}
+int vaqhip_lut_fit_quantiles_u8_device(int device_id, const uint8_t *d_X, int64_t n, int D, const int *bits,
+                                       const float *d_eigvec, float *d_centroids_out, float *d_quantiles_out,
+                                       void *stream) {
+  return fit_device_entry(device_id, vaq::RowsRef{d_X, 1}, n, D, bits, d_eigvec, d_centroids_out, d_quantiles_out, stream);
+}
+int vaqhip_lut_fit_quantiles(int device_id, const float *X, int64_t n, int D, const int *bits, const float *eigvec,
+                             float *centroids_out, float *quantiles_out) {
+  return fit_host_entry(device_id, vaq::RowsRef{X, 4}, n, D, bits, eigvec, centroids_out, quantiles_out);
+}
+int vaqhip_lut_fit_quantiles_u8(int device_id, const uint8_t *X, int64_t n, int D, const int *bits, const float *eigvec,
+                                float *centroids_out, float *quantiles_out) {
+  return fit_host_entry(device_id, vaq::RowsRef{X, 1}, n, D, bits, eigvec, centroids_out, quantiles_out);
 }
 
 int vaqhip_lut_fit_set_timing(int on) {
@@ -169,30 +222,17 @@ int vaqhip_index_set_lut_quantiles(vaqhip_index *ix, const float *quantiles) {
 
 int vaqhip_encode_lut_device(vaqhip_index *ix, const float *d_X, int64_t n, int projected, uint16_t *d_codes,
                              void *stream) {
-  if (int rc = check_encode_args(ix, d_X, n, d_codes)) return rc;
-  if (n == 0) return VAQHIP_OK;
-  ENTRY(ix);
-  return encode_lut_locked(ix, d_X, n, projected, d_codes, static_cast<hipStream_t>(stream));
+  return encode_lut_device_entry(ix, vaq::RowsRef{d_X, 4}, n, projected, d_codes, stream);
 }
-
+int vaqhip_encode_lut_u8_device(vaqhip_index *ix, const uint8_t *d_X, int64_t n, int projected, uint16_t *d_codes,
+                                void *stream) {
+  return encode_lut_device_entry(ix, vaq::RowsRef{d_X, 1}, n, projected, d_codes, stream);
+}
 int vaqhip_encode_lut(vaqhip_index *ix, const float *X, int64_t n, int projected, uint16_t *codes) {
-  if (int rc = check_encode_args(ix, X, n, codes)) return rc;
-  if (n == 0) return VAQHIP_OK;
-  const int64_t chunk = std::min<int64_t>(n, 1 << 20);
-  ENTRY(ix);
-  HIP_TRY(ix->w_q.ensure((size_t)chunk * ix->D * sizeof(float)));
-  HIP_TRY(ix->w_stage.ensure((size_t)chunk * ix->M * sizeof(uint16_t)));
-  WS_SCOPE(ws, ix, ix->stream);
-  for (int64_t r = 0; r < n; r += chunk) {
-    const int64_t m = std::min(chunk, n - r);
-    HIP_TRY(hipMemcpyAsync(ix->w_q.p, X + r * ix->D, (size_t)m * ix->D * sizeof(float), hipMemcpyHostToDevice,
-                           ix->stream));
-    if (int rc = encode_lut_locked(ix, ix->w_q.as<float>(), m, projected, ix->w_stage.as<uint16_t>(), ix->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(codes + r * ix->M, ix->w_stage.p, (size_t)m * ix->M * sizeof(uint16_t),
-                           hipMemcpyDeviceToHost, ix->stream));
-    HIP_TRY(hipStreamSynchronize(ix->stream));
-  }
-  return ws.finish();
+  return encode_lut_host_entry(ix, vaq::RowsRef{X, 4}, n, projected, codes);
+}
+int vaqhip_encode_lut_u8(vaqhip_index *ix, const uint8_t *X, int64_t n, int projected, uint16_t *codes) {
+  return encode_lut_host_entry(ix, vaq::RowsRef{X, 1}, n, projected, codes);
 }
 
 }  // extern "C"

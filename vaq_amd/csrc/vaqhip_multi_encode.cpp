@@ -10,10 +10,11 @@
 // encodeToLUTCode) in the place of VAQ::encode's: one flag on the call, everything else shared.
 //
 // Two phases, each on every shard's worker at once (on_shards):
-//   1 encode  the rows -- uploaded slice by slice in chunks (host form), or read where a multi refiner holds them
-//             (refiner form; byte rows are widened chunk by chunk into the host form's chunk buffer:
-//             launch_widen_rows_u8, (float)uint8 is exact) -- into a scratch buffer of n_g x M uint16 on the shard's device; the stream is
-//             synchronised, so whatever fails has failed before any shard's rows change
+//   1 encode  the rows -- uploaded slice by slice in chunks (host form; byte rows as the bytes they are), or read where
+//             a multi refiner holds them (refiner form) -- into a scratch buffer of n_g x M uint16 on the shard's
+//             device.  Byte rows go to the shard's vaqhip_encode[_lut]_u8_device, whose projection widens a byte where
+//             it loads it ((float)uint8 is exact).  The stream is synchronised, so whatever fails has failed before any
+//             shard's rows change
 //   2 set     the index takes the buffer (set: every shard, an empty one is emptied; append: the last shard), the
 //             codes go to the host only when the caller asked for them
 // The scratch is released by the calling thread once both phases are over, whichever way they ended.  It is the
@@ -35,13 +36,13 @@ constexpr int64_t ENCODE_CHUNK_ROWS = (int64_t)1 << 20;  // rows per upload / pr
 struct EncodePart {
   int64_t lo = 0, n = 0;           // rows [lo, lo + n) of the call's matrix
   vaq::RowsRef d_rows = {nullptr, 4};  // refiner form: the shard's resident rows, float or byte
-  DevBuf chunk, codes;             // float [chunk rows][D] (host form, byte rows widened), uint16 [n][M]
+  DevBuf chunk, codes;             // host form: [chunk rows][D] of the call's element; uint16 [n][M]
   hipEvent_t t[4] = {nullptr, nullptr, nullptr, nullptr};  // phase 1: start, encoded; phase 2: start, set
   float encode_ms = 0, set_ms = 0;
 };
 
 struct EncodeCall {
-  const float *X = nullptr;  // host form: the call's matrix
+  vaq::RowsRef X = {nullptr, 4};  // host form: the call's matrix, float or byte
   int projected = 0;
   bool lut = false;          // the engine's encoder (vaqhip_encode_lut_device) in the place of vaqhip_encode_device
   int64_t id_base = 0;       // set: the label of the matrix's first row
@@ -65,20 +66,25 @@ int encode_part(vaqhip_multi *mx, const EncodeCall &c, EncodePart &p, Shard &s) 
   MHIP(hipSetDevice(s.device));
   MHIP(ensure_events(p.t));
   MHIP(p.codes.ensure((size_t)p.n * M * sizeof(uint16_t)));
-  const bool widen = !c.X && p.d_rows.elem == 1;
-  if (c.X || widen) MHIP(p.chunk.ensure((size_t)std::min(c.chunk, p.n) * D * sizeof(float)));
+  const size_t elem = (size_t)(c.X.p ? c.X.elem : p.d_rows.elem);
+  if (c.X.p) MHIP(p.chunk.ensure((size_t)std::min(c.chunk, p.n) * D * elem));  // (sized in bytes)
   MHIP(hipEventRecord(p.t[0], s.stream));
   for (int64_t r = 0; r < p.n; r += c.chunk) {
     const int64_t m = std::min(c.chunk, p.n - r);
-    const float *d_x = p.chunk.as<float>();
-    if (c.X)  // (one chunk buffer: the stream orders this copy behind the encode of the chunk before)
-      MHIP(hipMemcpyAsync(p.chunk.p, c.X + (size_t)(p.lo + r) * D, (size_t)m * D * sizeof(float), hipMemcpyHostToDevice, s.stream));
-    else if (widen)  // (the same one buffer, the same order)
-      MHIP(vaq::launch_widen_rows_u8(static_cast<const uint8_t *>(p.d_rows.p) + (size_t)r * D, m * (int64_t)D, p.chunk.as<float>(), s.stream));
-    else d_x = static_cast<const float *>(p.d_rows.p) + (size_t)r * D;
+    const void *d_x = p.chunk.p;
+    if (c.X.p)  // (one chunk buffer: the stream orders this copy behind the encode of the chunk before)
+      MHIP(hipMemcpyAsync(p.chunk.p, vaq::rows_at(c.X, (size_t)(p.lo + r) * D).p, (size_t)m * D * elem, hipMemcpyHostToDevice, s.stream));
+    else d_x = vaq::rows_at(p.d_rows, (size_t)r * D).p;
     uint16_t *d_codes = p.codes.as<uint16_t>() + (size_t)r * M;
-    if (c.lut) MIX(vaqhip_encode_lut_device(s.ix, d_x, m, c.projected, d_codes, s.stream));
-    else MIX(vaqhip_encode_device(s.ix, d_x, m, c.projected, d_codes, s.stream));
+    if (elem == 1) {
+      const uint8_t *x = static_cast<const uint8_t *>(d_x);
+      if (c.lut) MIX(vaqhip_encode_lut_u8_device(s.ix, x, m, c.projected, d_codes, s.stream));
+      else MIX(vaqhip_encode_u8_device(s.ix, x, m, c.projected, d_codes, s.stream));
+    } else {
+      const float *x = static_cast<const float *>(d_x);
+      if (c.lut) MIX(vaqhip_encode_lut_device(s.ix, x, m, c.projected, d_codes, s.stream));
+      else MIX(vaqhip_encode_device(s.ix, x, m, c.projected, d_codes, s.stream));
+    }
   }
   MHIP(hipEventRecord(p.t[1], s.stream));
   MHIP(hipStreamSynchronize(s.stream));
@@ -159,10 +165,10 @@ int check_lut(const vaqhip_multi *mx, bool lut) {
   return VAQHIP_OK;
 }
 
-int encode_set_codes(vaqhip_multi *mx, const float *X, int64_t N, int projected, int64_t id_base, uint16_t *codes_out,
+int encode_set_codes(vaqhip_multi *mx, vaq::RowsRef X, int64_t N, int projected, int64_t id_base, uint16_t *codes_out,
                      bool lut) {
   if (!mx) return mfail(VAQHIP_EINVAL, "multi index is null");
-  if (N < 0 || (N > 0 && !X) || id_base < 0) return mfail(VAQHIP_EINVAL, "bad rows/N/id_base");
+  if (N < 0 || (N > 0 && !X.p) || id_base < 0) return mfail(VAQHIP_EINVAL, "bad rows/N/id_base");
   std::lock_guard<std::mutex> lk(mx->mu);
   if (const int rc = check_lut(mx, lut)) return rc;
   EncodeCall c;
@@ -182,9 +188,9 @@ int encode_set_codes(vaqhip_multi *mx, const float *X, int64_t N, int projected,
   return VAQHIP_OK;
 }
 
-int encode_add_codes(vaqhip_multi *mx, const float *X, int64_t n_new, int projected, uint16_t *codes_out, bool lut) {
+int encode_add_codes(vaqhip_multi *mx, vaq::RowsRef X, int64_t n_new, int projected, uint16_t *codes_out, bool lut) {
   if (!mx) return mfail(VAQHIP_EINVAL, "multi index is null");
-  if (n_new < 0 || (n_new > 0 && !X)) return mfail(VAQHIP_EINVAL, "bad rows/N");
+  if (n_new < 0 || (n_new > 0 && !X.p)) return mfail(VAQHIP_EINVAL, "bad rows/N");
   std::lock_guard<std::mutex> lk(mx->mu);
   if (const int rc = check_lut(mx, lut)) return rc;
   if (!mx->has_codes) return mfail(VAQHIP_ESTATE, "no codes yet: vaqhip_multi_encode_set_codes (or set_codes_u16) first");
@@ -240,21 +246,33 @@ extern "C" {
 
 int vaqhip_multi_encode_set_codes(vaqhip_multi *mx, const float *X, int64_t N, int projected, int64_t id_base,
                                   uint16_t *codes_out) {
-  return encode_set_codes(mx, X, N, projected, id_base, codes_out, false);
+  return encode_set_codes(mx, vaq::RowsRef{X, 4}, N, projected, id_base, codes_out, false);
+}
+int vaqhip_multi_encode_set_codes_u8(vaqhip_multi *mx, const uint8_t *X, int64_t N, int projected, int64_t id_base, uint16_t *codes_out) {
+  return encode_set_codes(mx, vaq::RowsRef{X, 1}, N, projected, id_base, codes_out, false);
 }
 int vaqhip_multi_encode_add_codes(vaqhip_multi *mx, const float *X, int64_t n_new, int projected, uint16_t *codes_out) {
-  return encode_add_codes(mx, X, n_new, projected, codes_out, false);
+  return encode_add_codes(mx, vaq::RowsRef{X, 4}, n_new, projected, codes_out, false);
+}
+int vaqhip_multi_encode_add_codes_u8(vaqhip_multi *mx, const uint8_t *X, int64_t n_new, int projected, uint16_t *codes_out) {
+  return encode_add_codes(mx, vaq::RowsRef{X, 1}, n_new, projected, codes_out, false);
 }
 int vaqhip_multi_encode_from_refiner(vaqhip_multi *mx, vaqhip_multi_refiner *r, uint16_t *codes_out) {
   return encode_from_refiner(mx, r, codes_out, false);
 }
 int vaqhip_multi_encode_lut_set_codes(vaqhip_multi *mx, const float *X, int64_t N, int projected, int64_t id_base,
                                       uint16_t *codes_out) {
-  return encode_set_codes(mx, X, N, projected, id_base, codes_out, true);
+  return encode_set_codes(mx, vaq::RowsRef{X, 4}, N, projected, id_base, codes_out, true);
+}
+int vaqhip_multi_encode_lut_set_codes_u8(vaqhip_multi *mx, const uint8_t *X, int64_t N, int projected, int64_t id_base, uint16_t *codes_out) {
+  return encode_set_codes(mx, vaq::RowsRef{X, 1}, N, projected, id_base, codes_out, true);
 }
 int vaqhip_multi_encode_lut_add_codes(vaqhip_multi *mx, const float *X, int64_t n_new, int projected,
                                       uint16_t *codes_out) {
-  return encode_add_codes(mx, X, n_new, projected, codes_out, true);
+  return encode_add_codes(mx, vaq::RowsRef{X, 4}, n_new, projected, codes_out, true);
+}
+int vaqhip_multi_encode_lut_add_codes_u8(vaqhip_multi *mx, const uint8_t *X, int64_t n_new, int projected, uint16_t *codes_out) {
+  return encode_add_codes(mx, vaq::RowsRef{X, 1}, n_new, projected, codes_out, true);
 }
 int vaqhip_multi_encode_lut_from_refiner(vaqhip_multi *mx, vaqhip_multi_refiner *r, uint16_t *codes_out) {
   return encode_from_refiner(mx, r, codes_out, true);

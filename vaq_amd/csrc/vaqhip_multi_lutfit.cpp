@@ -40,8 +40,8 @@ struct FitShard {
   int device = 0;
   std::string err;
   hipStream_t stream = nullptr;
-  const float *d_rows = nullptr;  // the shard's n_g x D rows on its device
-  DevBuf slice, eig, cols, bad;   // host form: the uploaded rows; eigvec; [W][n_g] keys; the non-finite flag
+  vaq::RowsRef d_rows = {nullptr, 4};  // the shard's n_g x D rows on its device, float or byte, read in place every round
+  DevBuf slice, eig, cols, bad;   // host form: the uploaded rows (n_g x D of the call's element); eigvec; [W][n_g] keys; the non-finite flag
   vaq::LutFitColumnWork work;     // as an owner: the column in flight
   DevBuf cent, q;                 //   and its slots, [slots][256] and [slots][257]
   std::vector<float> h_cent, h_q;
@@ -57,7 +57,7 @@ struct FitRun {
   vaq::JobPool pool;
   lp::Plan plan;
   const int *bits = nullptr;
-  const float *X = nullptr;    // host form: the call's matrix
+  vaq::RowsRef X = {nullptr, 4};  // host form: the call's matrix, float or byte
   const float *eig = nullptr;  // host pointer or null
   // by the calling thread, whichever way the call ended: the workers first, then every device's streams and buffers
   ~FitRun() {
@@ -98,10 +98,11 @@ int setup_shard(FitRun &f, int g, FitShard &s) {
   MHIP(ensure_events(s.t));
   const int64_t n_g = p.cnt[g];
   if (n_g > 0) {
-    if (f.X) {
-      MHIP(s.slice.ensure((size_t)n_g * D * sizeof(float)));
-      MHIP(hipMemcpyAsync(s.slice.p, f.X + (size_t)p.lo[g] * D, (size_t)n_g * D * sizeof(float), hipMemcpyHostToDevice, s.stream));
-      s.d_rows = s.slice.as<float>();
+    if (f.X.p) {
+      const size_t bytes = (size_t)n_g * D * (size_t)f.X.elem;
+      MHIP(s.slice.ensure(bytes));
+      MHIP(hipMemcpyAsync(s.slice.p, vaq::rows_at(f.X, (size_t)p.lo[g] * D).p, bytes, hipMemcpyHostToDevice, s.stream));
+      s.d_rows = vaq::RowsRef{s.slice.p, f.X.elem};
     }
     if (f.eig) {
       MHIP(s.eig.ensure(D * D * sizeof(float)));
@@ -222,13 +223,10 @@ int run_fit(FitRun &f, float *centroids_out, float *quantiles_out) {
   return VAQHIP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int vaqhip_multi_lut_fit_quantiles(int n_devices, const int *device_ids, const float *X, int64_t n, int D, const int *bits,
-                                   const float *eigvec, float *centroids_out, float *quantiles_out) {
-  if (!X || !device_ids) return mfail(VAQHIP_EINVAL, "null pointer");
+// the host form over float or byte rows: every shard uploads its slice as the elements the caller holds
+int fit_host(int n_devices, const int *device_ids, vaq::RowsRef X, int64_t n, int D, const int *bits, const float *eigvec,
+             float *centroids_out, float *quantiles_out) {
+  if (!X.p || !device_ids) return mfail(VAQHIP_EINVAL, "null pointer");
   if (const int rc = check_fit_args(n, D, bits, centroids_out, quantiles_out)) return rc;
   if (n_devices < 1 || n_devices > VAQHIP_MAX_DEVICES)
     return mfail(VAQHIP_EINVAL, "n_devices=%d outside 1..%d", n_devices, VAQHIP_MAX_DEVICES);
@@ -244,14 +242,25 @@ int vaqhip_multi_lut_fit_quantiles(int n_devices, const int *device_ids, const f
   return run_fit(f, centroids_out, quantiles_out);
 }
 
+}  // namespace
+
+extern "C" {
+
+int vaqhip_multi_lut_fit_quantiles(int n_devices, const int *device_ids, const float *X, int64_t n, int D, const int *bits,
+                                   const float *eigvec, float *centroids_out, float *quantiles_out) {
+  return fit_host(n_devices, device_ids, vaq::RowsRef{X, 4}, n, D, bits, eigvec, centroids_out, quantiles_out);
+}
+int vaqhip_multi_lut_fit_quantiles_u8(int n_devices, const int *device_ids, const uint8_t *X, int64_t n, int D,
+                                      const int *bits, const float *eigvec, float *centroids_out, float *quantiles_out) {
+  return fit_host(n_devices, device_ids, vaq::RowsRef{X, 1}, n, D, bits, eigvec, centroids_out, quantiles_out);
+}
+
 int vaqhip_multi_refiner_lut_fit_quantiles(vaqhip_multi_refiner *r, const int *bits, const float *eigvec,
                                            float *centroids_out, float *quantiles_out) {
   if (!r) return mfail(VAQHIP_EINVAL, "multi refiner is null");
   if (!bits || !centroids_out || !quantiles_out) return mfail(VAQHIP_EINVAL, "null pointer");
   std::lock_guard<std::mutex> lk(r->mu);
   if (r->N == 0) return mfail(VAQHIP_ESTATE, "the refiner holds no rows: vaqhip_multi_refiner_set_rows first");
-  if (rows_elem(r) != 4)  // (the column kernel re-reads the rows every round: its byte form is not written yet)
-    return mfail(VAQHIP_EUNSUPPORTED, "the refiner holds uint8 rows: the sharded quantile fit reads float32 rows only");
   if (const int rc = check_fit_args(r->N, r->D, bits, centroids_out, quantiles_out)) return rc;
   DeviceGuard keep(DeviceGuard::restore_only);  // (declared first: it puts the device back after f has released)
   FitRun f;
@@ -261,7 +270,7 @@ int vaqhip_multi_refiner_lut_fit_quantiles(vaqhip_multi_refiner *r, const int *b
   for (int g = 0; g < r->G; g++) {
     const ResidentRows rows = resident_rows(r, g);
     f.sh[(size_t)g].device = r->sh[g].device;
-    f.sh[(size_t)g].d_rows = static_cast<const float *>(rows.rows.p);
+    f.sh[(size_t)g].d_rows = rows.rows;  // (float or byte: the column kernel reads either in place)
     cnt[g] = rows.n;
   }
   if (!lp::plan_from_counts(r->G, r->D, cnt, &f.plan)) return mfail(VAQHIP_EINVAL, "bad shard counts");

@@ -42,6 +42,23 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def _u8_rows(X, D: int) -> np.ndarray:
+    """Byte rows as the *_u8 calls take them: a contiguous uint8 n x D array; anything else is EINVAL, nothing is
+    converted."""
+    X = np.asarray(X)
+    if X.dtype != np.uint8 or X.ndim != 2 or X.shape[1] != D or not X.flags.c_contiguous:
+        raise _lib.VaqHipError(-1, f"byte rows must be a contiguous uint8 n x {D} array (nothing is converted)")
+    return X
+
+
+def _u8_rows_device(d_X, D: int):
+    """The same for a torch CUDA tensor; a view that starts at any byte of its allocation is taken as it is."""
+    import torch
+    if not (d_X.is_cuda and d_X.dtype == torch.uint8 and d_X.dim() == 2 and d_X.shape[1] == D and d_X.is_contiguous()):
+        raise _lib.VaqHipError(-1, f"byte rows must be a contiguous uint8 n x {D} CUDA tensor (nothing is converted)")
+    return d_X
+
+
 def _wref(obj):
     """Identity token of a member that was uploaded: a weak reference (an id() can be recycled
     by a new array once the old one is freed; a dead weak reference never compares alive)."""
@@ -405,10 +422,20 @@ class VaqHip:
         dataset in place); projected=False applies mEigenVectors first."""
         self._ensure_index()
         X = np.ascontiguousarray(XTrain, dtype=np.float32)
+        self._encode_host(_lib.load().vaqhip_encode, X, projected)
+
+    def _encode_host(self, fn, X: np.ndarray, projected: bool) -> None:
         codes = np.empty((X.shape[0], len(self.mBitsAlloc)), np.uint16)
-        _lib.check(_lib.load().vaqhip_encode(self._h, _ptr(X), X.shape[0], 1 if projected else 0,
-                                             _ptr(codes)))
+        _lib.check(fn(self._h, _ptr(X), X.shape[0], 1 if projected else 0, _ptr(codes)))
         self.mCodebook = codes
+
+    def encode_u8(self, XTrain: np.ndarray, projected: bool = True) -> None:
+        """encode() from byte rows (a bvecs dataset as its file holds it; vaqhip_encode_u8): the codes encode() gives
+        on XTrain.astype(float32), code for code, from a quarter of the upload.  Anything but a contiguous uint8
+        n x D array is EINVAL: nothing is converted."""
+        X = _u8_rows(XTrain, self.mTotalDim)
+        self._ensure_index()
+        self._encode_host(_lib.load().vaqhip_encode_u8, X, projected)
 
     def encode_device(self, d_X, projected: bool = True):
         """torch CUDA tensor in, N x M int16 CUDA tensor (uint16 codes) out, on
@@ -417,12 +444,21 @@ class VaqHip:
         self._ensure_index()
         x = d_X.contiguous()
         assert x.is_cuda and x.dtype == torch.float32 and x.shape[1] == self.mTotalDim
+        return self._encode_on_device(_lib.load().vaqhip_encode_device, x, projected)
+
+    def _encode_on_device(self, fn, x, projected: bool):
+        import torch
         codes = torch.empty((x.shape[0], len(self.mBitsAlloc)), dtype=torch.int16, device=x.device)
         st = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(_lib.load().vaqhip_encode_device(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
-                                                    1 if projected else 0, C.c_void_p(codes.data_ptr()),
-                                                    C.c_void_p(st)))
+        _lib.check(fn(self._h, C.c_void_p(x.data_ptr()), x.shape[0], 1 if projected else 0,
+                      C.c_void_p(codes.data_ptr()), C.c_void_p(st)))
         return codes
+
+    def encode_u8_device(self, d_X, projected: bool = True):
+        """encode_device() from a torch uint8 CUDA tensor (vaqhip_encode_u8_device); it may start at any byte."""
+        x = _u8_rows_device(d_X, self.mTotalDim)
+        self._ensure_index()
+        return self._encode_on_device(_lib.load().vaqhip_encode_u8_device, x, projected)
 
     # ------------------------------------------- building a queryLUT index --
     def _need_sequential(self, what: str) -> None:
@@ -442,18 +478,31 @@ class VaqHip:
         D = len(self.mBitsAlloc)
         if X.ndim != 2 or X.shape[1] != D or D == 0:
             raise _lib.VaqHipError(-1, f"XTrain {X.shape} is not n x {D} (one quantiser per dimension)")
+        self._fit_quantiles(X, projected, devices, False)
+
+    def fitQuantiles_u8(self, XTrain: np.ndarray, projected: bool = True, devices: Optional[Sequence[int]] = None) -> None:
+        """fitQuantiles() from byte rows (vaqhip_lut_fit_quantiles_u8, or lut_fit_quantiles_multi_u8 with devices):
+        the members fitQuantiles() fills from XTrain.astype(float32), bit for bit.  Anything but a contiguous uint8
+        n x D array is EINVAL."""
+        self._need_sequential("fitQuantiles_u8")
+        self._fit_quantiles(_u8_rows(XTrain, len(self.mBitsAlloc)), projected, devices, True)
+
+    def _fit_quantiles(self, X: np.ndarray, projected: bool, devices, u8: bool) -> None:
+        D = len(self.mBitsAlloc)
+        L = _lib.load()
         eig = None
         if not projected and self.mEigenVectors is not None:
             eig = np.ascontiguousarray(np.real(self.mEigenVectors), dtype=np.float32)
             if eig.shape != (D, D):
                 raise _lib.VaqHipError(-1, f"mEigenVectors {eig.shape} is not {D}x{D}")
         if devices is not None:
-            cent, q = lut_fit_quantiles_multi(devices, X, self.mBitsAlloc, eig)
+            cent, q = (lut_fit_quantiles_multi_u8 if u8 else lut_fit_quantiles_multi)(devices, X, self.mBitsAlloc, eig)
         else:
             cent = np.empty((D, 256), np.float32)
             q = np.empty((D, 257), np.float32)
-            _lib.check(_lib.load().vaqhip_lut_fit_quantiles(self.device, _ptr(X), X.shape[0], D, (C.c_int * D)(*self.mBitsAlloc),
-                                                            _ptr(eig) if eig is not None else None, _ptr(cent), _ptr(q)))
+            fit = L.vaqhip_lut_fit_quantiles_u8 if u8 else L.vaqhip_lut_fit_quantiles
+            _lib.check(fit(self.device, _ptr(X), X.shape[0], D, (C.c_int * max(D, 1))(*self.mBitsAlloc),
+                           _ptr(eig) if eig is not None else None, _ptr(cent), _ptr(q)))
         self.centroidsMat = np.ascontiguousarray(cent.T)
         self.mCentroidsPerSubs = [np.ascontiguousarray(cent[d, :1 << b].reshape(-1, 1)) for d, b in enumerate(self.mBitsAlloc)]
         self.mQuantiles = q
@@ -480,9 +529,13 @@ class VaqHip:
         X = np.ascontiguousarray(XTrain, dtype=np.float32)
         if X.ndim != 2 or X.shape[1] != len(self.mBitsAlloc):
             raise _lib.VaqHipError(-1, f"XTrain {X.shape} is not n x {len(self.mBitsAlloc)}")
-        codes = np.empty((X.shape[0], len(self.mBitsAlloc)), np.uint16)
-        _lib.check(_lib.load().vaqhip_encode_lut(self._h, _ptr(X), X.shape[0], 1 if projected else 0, _ptr(codes)))
-        self.mCodebook = codes
+        self._encode_host(_lib.load().vaqhip_encode_lut, X, projected)
+
+    def encodeLUT_u8(self, XTrain: np.ndarray, projected: bool = True) -> None:
+        """encodeLUT() from byte rows (vaqhip_encode_lut_u8): the codes of encodeLUT() on XTrain.astype(float32)."""
+        X = _u8_rows(XTrain, len(self.mBitsAlloc))
+        self._ensure_quantiles()
+        self._encode_host(_lib.load().vaqhip_encode_lut_u8, X, projected)
 
     def encodeLUT_device(self, d_X, projected: bool = True):
         """torch CUDA tensor in, N x D int16 CUDA tensor (uint16 codes) out, on torch's current stream: the layout
@@ -491,12 +544,13 @@ class VaqHip:
         self._ensure_quantiles()
         x = d_X.contiguous()
         assert x.is_cuda and x.dtype == torch.float32 and x.shape[1] == len(self.mBitsAlloc)
-        codes = torch.empty((x.shape[0], len(self.mBitsAlloc)), dtype=torch.int16, device=x.device)
-        st = torch.cuda.current_stream(x.device).cuda_stream
-        _lib.check(_lib.load().vaqhip_encode_lut_device(self._h, C.c_void_p(x.data_ptr()), x.shape[0],
-                                                        1 if projected else 0, C.c_void_p(codes.data_ptr()),
-                                                        C.c_void_p(st)))
-        return codes
+        return self._encode_on_device(_lib.load().vaqhip_encode_lut_device, x, projected)
+
+    def encodeLUT_u8_device(self, d_X, projected: bool = True):
+        """encodeLUT_device() from a torch uint8 CUDA tensor (vaqhip_encode_lut_u8_device); it may start at any byte."""
+        x = _u8_rows_device(d_X, len(self.mBitsAlloc))
+        self._ensure_quantiles()
+        return self._encode_on_device(_lib.load().vaqhip_encode_lut_u8_device, x, projected)
 
     def refine(self, XTest: np.ndarray, answersIn: LabelDistVec, XTrain: np.ndarray, k: int) -> LabelDistVec:
         """VAQ::refine (VAQ.cpp:849-876): exact re-rank of the candidates in
@@ -915,7 +969,8 @@ class VaqMultiRefiner:
     def fit_quantiles(self, bits: Sequence[int], eigvec: Optional[np.ndarray] = None):
         """vaqhip_multi_refiner_lut_fit_quantiles: binaryEncodingLUT's quantile codebooks over the RAW rows resident on
         the shards, read in place (eigvec: D x D, applied first; None: the rows are their own image).  Returns
-        (cent[D, 256], q[D, 257]), bit for bit the single fit's over all rows."""
+        (cent[D, 256], q[D, 257]), bit for bit the single fit's over all rows.  Byte rows (set_rows_u8) are read as
+        they lie, a byte widened where it is loaded: the fit's result over the widened rows."""
         return _fit_quantiles_call(self.D, bits, eigvec, lambda L, b, e, c, q: L.vaqhip_multi_refiner_lut_fit_quantiles(
             self._h, b, e, c, q))
 
@@ -973,6 +1028,18 @@ def lut_fit_quantiles_multi(devices: Sequence[int], X, bits: Sequence[int], eigv
     devs = [int(d) for d in devices]
     arr = (C.c_int * max(len(devs), 1))(*devs)
     return _fit_quantiles_call(X.shape[1], bits, eigvec, lambda L, b, e, c, q: L.vaqhip_multi_lut_fit_quantiles(
+        len(devs), arr, _ptr(X), X.shape[0], X.shape[1], b, e, c, q))
+
+
+def lut_fit_quantiles_multi_u8(devices: Sequence[int], X, bits: Sequence[int], eigvec: Optional[np.ndarray] = None):
+    """lut_fit_quantiles_multi from byte rows (vaqhip_multi_lut_fit_quantiles_u8): every shard uploads its slice as
+    n_g x D bytes; the result is lut_fit_quantiles_multi's on X.astype(float32), bit for bit.  Anything but a
+    contiguous uint8 n x D array is EINVAL."""
+    X = np.asarray(X)
+    X = _u8_rows(X, X.shape[1] if X.ndim == 2 else 0)
+    devs = [int(d) for d in devices]
+    arr = (C.c_int * max(len(devs), 1))(*devs)
+    return _fit_quantiles_call(X.shape[1], bits, eigvec, lambda L, b, e, c, q: L.vaqhip_multi_lut_fit_quantiles_u8(
         len(devs), arr, _ptr(X), X.shape[0], X.shape[1], b, e, c, q))
 
 
@@ -1093,20 +1160,40 @@ class VaqHipMulti:
         device -- the state VaqHip.encode on one index followed by set_codes(codes, id_base) leaves, bit for bit,
         without the codes crossing to the host and back.  projected = False applies the eigenvectors first.
         return_codes: the N x M uint16 matrix VaqHip.encode would have filled (else None)."""
-        X = self._train_rows(X)
+        return self._encode_set(_lib.load().vaqhip_multi_encode_set_codes, self._train_rows(X), projected, id_base, return_codes)
+
+    def _encode_set(self, fn, X: np.ndarray, projected: bool, id_base: int, return_codes: bool):
         codes = np.empty((X.shape[0], self.M), np.uint16) if return_codes else None
-        _lib.check_multi(_lib.load().vaqhip_multi_encode_set_codes(
-            self._h, _ptr(X), X.shape[0], 1 if projected else 0, int(id_base), _ptr(codes) if return_codes else None))
+        _lib.check_multi(fn(self._h, _ptr(X), X.shape[0], 1 if projected else 0, int(id_base),
+                            _ptr(codes) if return_codes else None))
         return codes
+
+    def _encode_add(self, fn, X: np.ndarray, projected: bool, return_codes: bool):
+        codes = np.empty((X.shape[0], self.M), np.uint16) if return_codes else None
+        _lib.check_multi(fn(self._h, _ptr(X), X.shape[0], 1 if projected else 0, _ptr(codes) if return_codes else None))
+        return codes
+
+    def encode_u8(self, X, projected: bool = True, id_base: int = 0, return_codes: bool = False):
+        """encode() from byte rows (vaqhip_multi_encode_set_codes_u8): every shard uploads its slice as bytes; the
+        state encode() leaves from X.astype(float32).  Anything but a contiguous uint8 n x D array is EINVAL."""
+        return self._encode_set(_lib.load().vaqhip_multi_encode_set_codes_u8, _u8_rows(X, self.D), projected, id_base, return_codes)
+
+    def encode_add_u8(self, X, projected: bool = True, return_codes: bool = False):
+        """encode_add() from byte rows (vaqhip_multi_encode_add_codes_u8)."""
+        return self._encode_add(_lib.load().vaqhip_multi_encode_add_codes_u8, _u8_rows(X, self.D), projected, return_codes)
+
+    def encode_lut_u8(self, X, projected: bool = True, id_base: int = 0, return_codes: bool = False):
+        """encode_lut() from byte rows (vaqhip_multi_encode_lut_set_codes_u8)."""
+        return self._encode_set(_lib.load().vaqhip_multi_encode_lut_set_codes_u8, _u8_rows(X, self.D), projected, id_base, return_codes)
+
+    def encode_lut_add_u8(self, X, projected: bool = True, return_codes: bool = False):
+        """encode_lut_add() from byte rows (vaqhip_multi_encode_lut_add_codes_u8)."""
+        return self._encode_add(_lib.load().vaqhip_multi_encode_lut_add_codes_u8, _u8_rows(X, self.D), projected, return_codes)
 
     def encode_add(self, X, projected: bool = True, return_codes: bool = False):
         """vaqhip_multi_encode_add_codes: encode + add_codes; the rows extend the last shard and are encoded on its
         device.  ESTATE on an index that never received codes."""
-        X = self._train_rows(X)
-        codes = np.empty((X.shape[0], self.M), np.uint16) if return_codes else None
-        _lib.check_multi(_lib.load().vaqhip_multi_encode_add_codes(
-            self._h, _ptr(X), X.shape[0], 1 if projected else 0, _ptr(codes) if return_codes else None))
-        return codes
+        return self._encode_add(_lib.load().vaqhip_multi_encode_add_codes, self._train_rows(X), projected, return_codes)
 
     def encode_from_refiner(self, refiner: "VaqMultiRefiner", return_codes: bool = False):
         """vaqhip_multi_encode_from_refiner: encode the RAW rows resident in a multi refiner on the same devices where
@@ -1129,19 +1216,11 @@ class VaqHipMulti:
     def encode_lut(self, X, projected: bool = True, id_base: int = 0, return_codes: bool = False):
         """encode() with the engine's rule (encodeToLUTCode, VaqHip.encodeLUT) in the place of VAQ::encode's: the state
         VaqHip.encodeLUT on one index followed by set_codes(codes, id_base) leaves, bit for bit."""
-        X = self._train_rows(X)
-        codes = np.empty((X.shape[0], self.M), np.uint16) if return_codes else None
-        _lib.check_multi(_lib.load().vaqhip_multi_encode_lut_set_codes(
-            self._h, _ptr(X), X.shape[0], 1 if projected else 0, int(id_base), _ptr(codes) if return_codes else None))
-        return codes
+        return self._encode_set(_lib.load().vaqhip_multi_encode_lut_set_codes, self._train_rows(X), projected, id_base, return_codes)
 
     def encode_lut_add(self, X, projected: bool = True, return_codes: bool = False):
         """encode_add() with the engine's rule: the rows extend the last shard and are encoded on its device."""
-        X = self._train_rows(X)
-        codes = np.empty((X.shape[0], self.M), np.uint16) if return_codes else None
-        _lib.check_multi(_lib.load().vaqhip_multi_encode_lut_add_codes(
-            self._h, _ptr(X), X.shape[0], 1 if projected else 0, _ptr(codes) if return_codes else None))
-        return codes
+        return self._encode_add(_lib.load().vaqhip_multi_encode_lut_add_codes, self._train_rows(X), projected, return_codes)
 
     def encode_lut_from_refiner(self, refiner: "VaqMultiRefiner", return_codes: bool = False):
         """encode_from_refiner() with the engine's rule over the RAW rows resident in a multi refiner."""
