@@ -130,9 +130,16 @@ hipError_t launch_project(const float *X, int64_t n, int D, const float *E, floa
                           hipStream_t st, int checked = 0);
 // cent_t: the codebooks dimension-major (entry j * ncent + c of subspace s at cent_off)
 // min_ncent: the smallest codebook (subspaces of < 8 centroids take the reference's scalar branch)
+// ck: also make the cost keys of launch_cost_order, where table 0 is computed; launch_cost_scatter then ranks.
+//     Only for nq >= 16 and a first codebook of >= 8 centroids (n0; shift = bucket_shift) within
+//     launch_cost_order's limits: anything else is refused
+struct CostKeys {
+  unsigned long long *keys;  // [nq]
+  int n0, shift;
+};
 hipError_t launch_lut_build(const float *qproj, int nq, int D, int M, int L,
                             const SubDesc *sub, const float *cent_t, int lut_floats, int max_ncent,
-                            float *lut, hipStream_t st, int min_ncent = 1);
+                            float *lut, hipStream_t st, int min_ncent = 1, const CostKeys *ck = nullptr);
 hipError_t launch_lut_expand(const float *lut_packed, int nq, int M, const SubDesc *sub,
                              int lut_floats, int ksub, float *lut_ref, hipStream_t st);
 // VAQ::encodeImpl: Xp is n x D already in PCA space; codes is n x M uint16 row-major
@@ -258,9 +265,12 @@ hipError_t launch_slice_order(const float *lut, int lut_floats, int nq, int qb, 
                               int64_t n_rows, int *order, hipStream_t st);
 // order[i] = the query the i-th pass slot takes: by (nearest first code, nearest second code); nq <= 16384
 // best-first form, one workgroup per query: order[b] = the query block b serves, expensive queries
-// first (keys: nq 64-bit scratch words; n0 = entries of table 0, shift = bucket_shift)
+// first (keys: nq 64-bit scratch words; n0 = entries of table 0, shift = bucket_shift).  launch_cost_order makes
+// the keys from tables that are there; launch_cost_scatter is its second half alone, after a launch_lut_build
+// that made the keys (CostKeys) on the same stream
 hipError_t launch_cost_order(const float *lut, int lut_floats, int nq, int n0, int shift, unsigned long long *keys,
                              int *order, hipStream_t st);
+hipError_t launch_cost_scatter(const unsigned long long *keys, int nq, int *order, hipStream_t st);
 hipError_t launch_query_order(const float *lut, int lut_floats, int nq, int n0, int off1, int n1, int *order,
                               hipStream_t st);
 // LDS geometry of a scan workgroup for top-k = k

@@ -255,12 +255,22 @@ __global__ void lut_build_kernel(const float *__restrict__ qproj, int D, int L,
 // thread owns one centroid and reads each of its coordinates ONCE for the whole batch of queries
 // (the per-query kernel above spends its time launching 80 000 workgroups of 16 FMAs a thread
 // at C2).  Per (query, centroid) the chain is unchanged: acc = fma(diff, diff, acc), j ascending.
+// With `keys` (the ranking of the queries by cost, further down) the workgroups of subspace 0 also make each of
+// their queries' cost key, from the entries they have just computed: a table 0 of up to
+// COST_KEY_LDS_ENTRIES entries goes to the key through LDS, a larger one (whose key samples a part of it) is read
+// back by the workgroup that wrote it.  One wave per query, the key of query_cost_kernel bit for bit.
 constexpr int LUT_QT = 8;
+constexpr int COST_KEY_LDS_ENTRIES = 256;
+template <int NREG>
+__device__ __forceinline__ unsigned cost_key_bits(const float *l, int n0, int shift, int lane);
+__device__ __forceinline__ void cost_key_emit(unsigned kb, int q, unsigned long long *__restrict__ keys);
+
 __global__ __launch_bounds__(256) void lut_build_batch_kernel(const float *__restrict__ qproj, int nq, int D, int L,
                                                               const SubDesc *__restrict__ sub,
                                                               const float *__restrict__ cent_t, int lut_floats,
-                                                              float *__restrict__ lut) {
-  extern __shared__ float qs[];  // [LUT_QT][L]
+                                                              float *__restrict__ lut,
+                                                              unsigned long long *__restrict__ keys, int shift) {
+  extern __shared__ float qs[];  // [LUT_QT][L]; with keys, for a small table 0: then [LUT_QT][K]
   const int q0 = blockIdx.x * LUT_QT, s = blockIdx.y;
   const SubDesc sd = sub[s];
   const int K = sd.ncent;
@@ -270,6 +280,9 @@ __global__ __launch_bounds__(256) void lut_build_batch_kernel(const float *__res
     qs[i] = q0 + qt < nq ? qproj[(size_t)(q0 + qt) * D + (size_t)s * L + j] : 0.0f;
   }
   __syncthreads();
+  const bool rank = keys != nullptr && s == 0;
+  const bool rank_lds = rank && K <= COST_KEY_LDS_ENTRIES;
+  float *t0 = qs + LUT_QT * L;
   const float *cs = cent_t + sd.cent_off;
   for (int c = threadIdx.x; c < K; c += blockDim.x) {
     float acc[LUT_QT];
@@ -284,19 +297,37 @@ __global__ __launch_bounds__(256) void lut_build_batch_kernel(const float *__res
       }
     }
 #pragma unroll
-    for (int qt = 0; qt < LUT_QT; qt++)
+    for (int qt = 0; qt < LUT_QT; qt++) {
       if (q0 + qt < nq) lut[(size_t)(q0 + qt) * lut_floats + sd.lut_off + c] = acc[qt];
+      if (rank_lds) t0[qt * K + c] = acc[qt];
+    }
+  }
+  if (!rank) return;
+  __threadfence_block();  // (the read-back form: this workgroup's stores before its own loads)
+  __syncthreads();
+  const int lane = threadIdx.x & 63;
+  for (int qt = threadIdx.x >> 6; qt < LUT_QT && q0 + qt < nq; qt += blockDim.x >> 6) {
+    const int q = q0 + qt;
+    const unsigned kb = rank_lds ? cost_key_bits<4>(t0 + qt * K, K, shift, lane)
+                                 : cost_key_bits<4>(lut + (size_t)q * lut_floats + sd.lut_off, K, shift, lane);
+    if (lane == 0) cost_key_emit(kb, q, keys);
   }
 }
 
+static bool cost_order_shape_ok(int nq, int n0, int shift);  // (with the ranking, further down)
+
 hipError_t launch_lut_build(const float *qproj, int nq, int D, int M, int L, const SubDesc *sub,
                             const float *cent_t, int lut_floats, int max_ncent, float *lut,
-                            hipStream_t st, int min_ncent) {
+                            hipStream_t st, int min_ncent, const CostKeys *ck) {
   if (nq == 0) return hipSuccess;
   (void)max_ncent;
+  // (keys come from the batched kernel's subspace-0 workgroups alone: the caller asks only where those run)
+  if (ck && !(nq >= 2 * LUT_QT && ck->n0 >= 8 && cost_order_shape_ok(nq, ck->n0, ck->shift))) return hipErrorInvalidValue;
   if (nq >= 2 * LUT_QT && max_ncent >= 8) {
-    hipLaunchKernelGGL(lut_build_batch_kernel, dim3((nq + LUT_QT - 1) / LUT_QT, M), dim3(256),
-                       LUT_QT * L * sizeof(float), st, qproj, nq, D, L, sub, cent_t, lut_floats, lut);
+    size_t lds = LUT_QT * L * sizeof(float);
+    if (ck && ck->n0 <= COST_KEY_LDS_ENTRIES) lds += (size_t)LUT_QT * ck->n0 * sizeof(float);
+    hipLaunchKernelGGL(lut_build_batch_kernel, dim3((nq + LUT_QT - 1) / LUT_QT, M), dim3(256), lds, st, qproj, nq, D, L,
+                       sub, cent_t, lut_floats, lut, ck ? ck->keys : nullptr, ck ? ck->shift : 0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || min_ncent >= 8) return e;
     // codebooks of fewer than 8 centroids (the reference's scalar branch) go through the per-query kernel
@@ -766,18 +797,16 @@ hipError_t launch_query_order(const float *lut, int lut_floats, int nq, int n0, 
 // near the minimum: cost key = (sum of the 16 smallest - 16 x the smallest) of the per-bucket minima of
 // table 0 (of 256 of them, sampled, when there are more),
 // ascending (Spearman 0.72 with a workgroup's lifetime, 0.83 with its steps).
-//   query_cost_kernel   one wave per query -> key bits << 32 | query
-//   cost_sort_kernel    one workgroup: counting sort by the key's top bits -> order[b] = query of block b
+//   cost_key_bits        one wave per query -> key bits; cost_key_emit: keys[q] = key bits << 32 | query.  Run where
+//                        table 0 is made (lut_build_batch_kernel) or, over tables that are there already, by
+//                        query_cost_kernel
+//   cost_scatter_kernel  counting sort by the key's top bits -> order[b] = query of block b
 // Block b serves order[b]: blocks are dealt round-robin over the XCDs and dispatched in order, so
 // every XCD gets every 8th query of the ranking.  Speed only: any order is correct.
 // ---------------------------------------------------------------------------
+// `l`: the query's table 0 (n0 entries), in LDS or in global memory; all 64 lanes of the wave call it
 template <int NREG>  // per-bucket minima a lane holds: buckets at the level of the first code <= 64 NREG
-__global__ __launch_bounds__(256) void query_cost_kernel(const float *__restrict__ lut, int lut_floats, int nq, int n0,
-                                                         int shift, unsigned long long *__restrict__ keys) {
-  const int lane = threadIdx.x & 63;
-  const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (q >= nq) return;
-  const float *l = lut + (size_t)q * lut_floats;
+__device__ __forceinline__ unsigned cost_key_bits(const float *l, int n0, int shift, int lane) {
   // (more than 256 buckets at the level of the first code: every stride-th one is sampled -- the
   //  statistic is a ranking aid, and reading a 4096-entry table per query costs more than it saves)
   const int nb_all = n0 >> shift;
@@ -836,30 +865,56 @@ __global__ __launch_bounds__(256) void query_cost_kernel(const float *__restrict
   for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o);
   const float v0 = bits_to_float(vmin < 0x7f800000u ? vmin : 0x7f800000u);
   const float spread = (part + (float)(J - below) * bits_to_float(lo)) - (float)J * v0;
-  const unsigned kb = (spread == spread && spread >= 0.0f) ? float_to_bits(spread) : (spread < 0.0f ? 0u : 0x7f800000u);  // (inf - inf: last)
-  if (lane == 0) keys[q] = ((unsigned long long)kb << 32) | (unsigned)q;
+  return (spread == spread && spread >= 0.0f) ? float_to_bits(spread) : (spread < 0.0f ? 0u : 0x7f800000u);  // (inf - inf: last)
 }
 
-// One workgroup: counting sort of the queries by the top 12 value bits of their cost key (sign 0,
-// exponent, 4 mantissa bits: 6 % steps -- the ranking only has to put expensive queries ahead of cheap
-// ones; a full bitonic sort of 16 k keys in one workgroup takes longer than the launch it speeds up).
+// The queries are sorted by the top 12 value bits of their cost key (sign 0, exponent, 4 mantissa bits: 6 % steps
+// -- the ranking only has to put expensive queries ahead of cheap ones), a counting sort over COST_CLASSES classes.
 constexpr int COST_CLASSES = 4096;
-__global__ __launch_bounds__(QORDER_THREADS) void cost_sort_kernel(const unsigned long long *__restrict__ keys, int nq,
-                                                                   int *__restrict__ order) {
-  __shared__ unsigned hist[COST_CLASSES];
+
+__device__ __forceinline__ unsigned cost_class(unsigned long long key) { return (unsigned)(key >> 51) & (COST_CLASSES - 1); }
+
+__device__ __forceinline__ void cost_key_emit(unsigned kb, int q, unsigned long long *__restrict__ keys) {
+  keys[q] = ((unsigned long long)kb << 32) | (unsigned)q;
+}
+
+// over tables that are already there (no table build in front, or a table 0 the batched build does not make)
+template <int NREG>
+__global__ __launch_bounds__(256) void query_cost_kernel(const float *__restrict__ lut, int lut_floats, int nq, int n0,
+                                                         int shift, unsigned long long *__restrict__ keys) {
+  const int lane = threadIdx.x & 63;
+  const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (q >= nq) return;
+  const unsigned kb = cost_key_bits<NREG>(lut + (size_t)q * lut_floats, n0, shift, lane);
+  if (lane == 0) cost_key_emit(kb, q, keys);
+}
+
+// QORDER_THREADS queries per workgroup, and no word shared between the workgroups: each counts ALL the keys for
+// itself in LDS (nq x 8 bytes out of L2) -- per class the queries there are (low half of the word) and those of
+// them that belong to earlier workgroups (high half; nq <= QORDER_MAX keeps both inside 16 bits) --, takes the
+// exclusive prefix over the classes, and places its own queries from where the earlier workgroups' end.  Inside a
+// class the queries stand in the order of their workgroups, inside a workgroup in the order of its LDS atomics.
+// (Counting the classes in global memory while the keys are made, and handing places out with returning global
+//  atomics, was measured: the 10 k same-word atomics of a C2 batch add 69 us to the kernel that makes the keys and
+//  take 23 us in the scatter.)
+static_assert(QORDER_MAX < (1 << 16), "a class's two counts share one word");
+__global__ __launch_bounds__(QORDER_THREADS) void cost_scatter_kernel(const unsigned long long *__restrict__ keys, int nq,
+                                                                      int *__restrict__ order) {
+  __shared__ unsigned cnt[COST_CLASSES];
   __shared__ unsigned wave_tot[QORDER_THREADS / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int i = tid; i < COST_CLASSES; i += QORDER_THREADS) hist[i] = 0u;
+  const int mine0 = blockIdx.x * QORDER_THREADS;  // this workgroup's first query
+  for (int i = tid; i < COST_CLASSES; i += QORDER_THREADS) cnt[i] = 0u;
   __syncthreads();
-  for (int i = tid; i < nq; i += QORDER_THREADS) atomicAdd(&hist[(unsigned)(keys[i] >> 51) & (COST_CLASSES - 1)], 1u);
+  for (int i = tid; i < nq; i += QORDER_THREADS) atomicAdd(&cnt[cost_class(keys[i])], i < mine0 ? 0x10001u : 1u);
   __syncthreads();
   // exclusive prefix over the classes: 4 per thread, then a wave scan, then the waves' totals
   constexpr int PER = COST_CLASSES / QORDER_THREADS;
   unsigned c[PER], sum = 0u;
 #pragma unroll
   for (int j = 0; j < PER; j++) {
-    c[j] = hist[tid * PER + j];
-    sum += c[j];
+    c[j] = cnt[tid * PER + j];
+    sum += c[j] & 0xffffu;
   }
   unsigned inc = sum;
 #pragma unroll
@@ -873,25 +928,35 @@ __global__ __launch_bounds__(QORDER_THREADS) void cost_sort_kernel(const unsigne
   for (int w = 0; w < wave; w++) base += wave_tot[w];
 #pragma unroll
   for (int j = 0; j < PER; j++) {
-    hist[tid * PER + j] = base;
-    base += c[j];
+    cnt[tid * PER + j] = base + (c[j] >> 16);  // the class's first place, then the earlier workgroups' queries
+    base += c[j] & 0xffffu;
   }
   __syncthreads();
-  for (int i = tid; i < nq; i += QORDER_THREADS) {
-    const unsigned long long kq = keys[i];
-    const unsigned pos = atomicAdd(&hist[(unsigned)(kq >> 51) & (COST_CLASSES - 1)], 1u);
-    order[pos] = (int)(kq & 0xffffffffu);
-  }
+  const int i = mine0 + tid;
+  if (i >= nq) return;
+  const unsigned long long kq = keys[i];
+  const unsigned pos = atomicAdd(&cnt[cost_class(kq)], 1u);
+  if (pos < (unsigned)nq) order[pos] = (int)(kq & 0xffffffffu);  // (always: the counts are these keys')
+}
+
+static bool cost_order_shape_ok(int nq, int n0, int shift) {
+  return nq > 0 && nq <= QORDER_MAX && (n0 >> shift) <= 1024 && (n0 >> shift) >= 1;
+}
+
+hipError_t launch_cost_scatter(const unsigned long long *keys, int nq, int *order, hipStream_t st) {
+  if (nq <= 0 || nq > QORDER_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(cost_scatter_kernel, dim3((nq + QORDER_THREADS - 1) / QORDER_THREADS), dim3(QORDER_THREADS), 0, st,
+                     keys, nq, order);
+  return hipGetLastError();
 }
 
 hipError_t launch_cost_order(const float *lut, int lut_floats, int nq, int n0, int shift, unsigned long long *keys,
                              int *order, hipStream_t st) {
-  if (nq <= 0 || nq > QORDER_MAX || (n0 >> shift) > 1024 || (n0 >> shift) < 1) return hipErrorInvalidValue;
+  if (!cost_order_shape_ok(nq, n0, shift)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(query_cost_kernel<4>, dim3((nq + 3) / 4), dim3(256), 0, st, lut, lut_floats, nq, n0, shift, keys);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(cost_sort_kernel, dim3(1), dim3(QORDER_THREADS), 0, st, keys, nq, order);
-  return hipGetLastError();
+  return launch_cost_scatter(keys, nq, order, st);
 }
 
 // __global__ entry points: the SGPR-capped one for EA_NONE / EA_QUEUE, a plain one for EA_INPLACE

@@ -292,6 +292,15 @@ int scan_chunk_ti(vaqhip_index *ix, const Plan &pl, const float *qp, int n, int 
   return VAQHIP_OK;
 }
 
+// whether this chunk's queries are ranked by cost, and whether the table build makes the keys of that ranking (it
+// does wherever its batched kernel computes table 0: from 8 centroids on; n >= COST_ORDER_MIN_QUERIES is batched)
+bool ranks_queries(const vaqhip_index *ix, const Plan &pl, int n) {
+  return pl.bf && pl.cost_order && pl.n_slices == 1 && ix->N > 0 && n >= COST_ORDER_MIN_QUERIES;
+}
+bool keys_from_table_build(const vaqhip_index *ix, const Plan &pl, int n) {
+  return ranks_queries(ix, pl, n) && ix->sub[0].ncent >= 8;
+}
+
 // what runs before the scan proper: the sampling pre-pass with its threshold merge, the ranking of the queries
 int seed_prepass(vaqhip_index *ix, const Plan &pl, int n, int k, vaq::ScanParams &sp, hipStream_t st) {
   if (ix->N > 0 && pl.seed_slices > 0) {
@@ -308,9 +317,12 @@ int seed_prepass(vaqhip_index *ix, const Plan &pl, int n, int k, vaq::ScanParams
                               ix->w_ms_d.as<float>(), ix->w_ms_id.as<int>(), st));
   }
   // (the ranking of the queries counts as a pre-pass in the timing: "seed_ms")
-  if (pl.bf && pl.cost_order && pl.n_slices == 1 && ix->N > 0 && n >= COST_ORDER_MIN_QUERIES) {
-    HIP_TRY(vaq::launch_cost_order(ix->w_lut.as<float>(), ix->lut_floats, n, ix->sub[0].ncent, ix->bucket_shift,
-                                   ix->w_cost.as<unsigned long long>(), ix->w_qorder.as<int>(), st));
+  if (ranks_queries(ix, pl, n)) {
+    if (keys_from_table_build(ix, pl, n))  // (the keys are there: search_core asked the table build for them)
+      HIP_TRY(vaq::launch_cost_scatter(ix->w_cost.as<unsigned long long>(), n, ix->w_qorder.as<int>(), st));
+    else
+      HIP_TRY(vaq::launch_cost_order(ix->w_lut.as<float>(), ix->lut_floats, n, ix->sub[0].ncent, ix->bucket_shift,
+                                     ix->w_cost.as<unsigned long long>(), ix->w_qorder.as<int>(), st));
     sp.qorder = ix->w_qorder.as<int>();
   }
   return VAQHIP_OK;
@@ -523,9 +535,11 @@ int search_core(vaqhip_index *ix, const float *d_queries, int nq, int k, int pro
       qp = ix->w_qproj.as<float>();
     }
     if (timing) HIP_TRY(hipEventRecord(ev[1], st));
+    // (a ranking of the queries takes its keys from the table build: seed_prepass only places the queries)
+    const vaq::CostKeys ck = {ix->w_cost.as<unsigned long long>(), ix->sub[0].ncent, ix->bucket_shift};
     HIP_TRY(vaq::launch_lut_build(qp, n, ix->D, ix->M, ix->L, ix->d_sub.as<vaq::SubDesc>(),
                                   ix->d_cent_t.as<float>(), ix->lut_floats, 1 << ix->max_bits, ix->w_lut.as<float>(), st,
-                                  1 << ix->min_bits));
+                                  1 << ix->min_bits, !ti && keys_from_table_build(ix, pl, n) ? &ck : nullptr));
     if (timing) HIP_TRY(hipEventRecord(ev[2], st));
     vaq::ScanParams sp = base_scan_params(ix, pl, n, k);
 #if defined(VAQ_STATS) || defined(VAQ_PHASES)
