@@ -37,7 +37,8 @@
 //                                           codes; with --devices and --refine-resident the rows are uploaded once, cut
 //                                           over the GPUs, and encoded where they lie -- the same codes either way)
 //               with a ...,FAST method (codes of at most 4 bits): --dataset base.fvecs [--dataset-size N]
-//               [--learn-ratio 0.05]       (demo_vaq.cpp:42, :120-124: VAQ::learnQuantization on the raw dataset)
+//               [--learn-ratio 0.05]       (demo_vaq.cpp:42, :120-124: VAQ::learnQuantization on the raw dataset; from the
+//                                           bytes with --file-format-ori bvecs, from the resident rows with --refine-resident)
 //
 //   demo_vaqhip --lut-bits 8,6,5,...  --dataset base.fvecs [--dataset-size N] [--eigen e.f32] \
 //               --queries q.fvecs --timeseries-size 128 [--queries-size N] --k 100 [--exact-ties 1] \
@@ -313,12 +314,28 @@ int main(int argc, char **argv) {
     }
     if (vaq.searchMethod() & VaqHip::NNMethod::Fast) {  // demo_vaq.cpp:120-124
       if (!a.count("dataset")) throw Error(VAQHIP_EINVAL, "a FAST method learns its quantisation from --dataset <.fvecs>");
-      RowMatrixF dataset = readOri(a["dataset"], N, a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1, D - N);
+      const int lsize = a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1;
       const float ratio = (float)std::atof(a.count("learn-ratio") ? a["learn-ratio"].c_str() : "0.05");
+      // the same mOffsets / mScale three ways: from the rows --refine-resident left on the device(s) when they are
+      // --dataset's, from the bytes of a bvecs file, or from the host float matrix as the reference does
+      const bool same_rows = !a.count("dataset-refine") || a["dataset-refine"] == a["dataset"];
+      const char *from = "";
       auto t0 = std::chrono::steady_clock::now();
-      vaq.learnQuantization(dataset, ratio);
+      if (a.count("refine-resident") && same_rows && N == D && (vaq.refinerHandle() || vaq.multiRefinerHandle())) {
+        vaq.learnQuantizationRefineDataset(ratio);
+        from = " (from the resident rows)";
+      } else if (g_bvecs && N == D) {
+        RowMatrix<uint8_t> dataset8 = readBVecsU8(a["dataset"], N, lsize);
+        t0 = std::chrono::steady_clock::now();
+        vaq.learnQuantization(dataset8, ratio);
+        from = " (from the byte rows of the bvecs file)";
+      } else {
+        RowMatrixF dataset = readOri(a["dataset"], N, lsize, D - N);
+        t0 = std::chrono::steady_clock::now();
+        vaq.learnQuantization(dataset, ratio);
+      }
       std::cout << "== Learn Quantization time: "
-                << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << std::endl;
+                << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() << " s" << from << std::endl;
     }
     vaq.sync();
     for (const int refine : refines) {

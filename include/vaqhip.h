@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 118
+#define VAQHIP_VERSION 119
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -211,6 +211,45 @@ int vaqhip_index_set_lut_quantization(vaqhip_index *ix, const float *offsets, co
  * not NULL, written to offsets_out[M] / scale_out[M]. */
 int vaqhip_learn_quantization(vaqhip_index *ix, const float *X_rowmajor, int64_t n, int projected,
                               float sample_ratio, float *offsets_out, float *scale_out);
+
+/* Learning on the device: vaqhip_learn_quantization over rows where they live and in the type they have -- host
+ * bytes (_u8), device floats (_device), device bytes (_u8_device), or the rows resident in a refiner, float or
+ * byte, read in place as raw rows (projected = 0).  offsets, scale and the chosen alpha are those of
+ * vaqhip_learn_quantization on the same rows (a byte widened, (float)uint8 is exact), bit for bit.
+ *   how         only the sampled rows are gathered (the first sampleSize entries of randomPermutation, found
+ *               without building the permutation), their tables are built by the launches the host form makes
+ *               and stay on the device; per column a radix sort, the few order statistics the fourteen
+ *               percentiles read are fetched, floors and scales are computed on the host by the host form's
+ *               code, and the loss is summed on the device in the host form's order: per (alpha, column) one
+ *               chain of double additions over the table in sample-major, centroid-minor order.
+ *   memory      the tables of at most Mc subspaces are held at a time ([sampleSize][Mc][16] floats) beside one
+ *               column's sort buffers; Mc is the largest that fits the workspace of vaqhip_learn_set_workspace.
+ *               The results do not depend on Mc.
+ *   refusals    as the host form's, all before a device is touched: null index or rows, n <= 0 VAQHIP_EINVAL;
+ *               n > INT_MAX VAQHIP_ERANGE; int(ratio * float(n)) < 1 VAQHIP_EINVAL; no FAST form
+ *               VAQHIP_EUNSUPPORTED; a refiner without rows VAQHIP_ESTATE, of another D or device VAQHIP_EINVAL.
+ *               Also sampleSize > n (a ratio above 1): VAQHIP_EINVAL -- the host form reads past its
+ *               permutation there.  A table value that is NaN or infinite (a NaN in a sampled row), or no alpha
+ *               of finite loss: VAQHIP_EINVAL, the outputs and the index's quantisation untouched.
+ *   streams     the device forms run on the index's own stream and return when the result is set: the rows
+ *               must be complete when the call is made. */
+int vaqhip_learn_quantization_u8(vaqhip_index *ix, const uint8_t *X_rowmajor, int64_t n, int projected,
+                                 float sample_ratio, float *offsets_out, float *scale_out);
+int vaqhip_learn_quantization_device(vaqhip_index *ix, const float *d_X, int64_t n, int projected,
+                                     float sample_ratio, float *offsets_out, float *scale_out);
+int vaqhip_learn_quantization_u8_device(vaqhip_index *ix, const uint8_t *d_X, int64_t n, int projected,
+                                        float sample_ratio, float *offsets_out, float *scale_out);
+/* (vaqhip_learn_quantization_from_refiner is declared with the refiner, below) */
+/* bytes the device forms called from this thread may hold for tables and sort buffers; 0 = the default (1 GiB).
+ * A group of one subspace is taken even where it does not fit.  Negative: VAQHIP_EINVAL. */
+int vaqhip_learn_set_workspace(int64_t bytes);
+typedef struct vaqhip_learn_timing {
+  int sample_rows, column_groups, chosen_alpha; /* chosen_alpha: index into the seven alphas, -1 = none was finite */
+  float gather_ms, tables_ms, sort_ms, order_stats_ms, loss_ms, total_ms; /* host clock around each phase */
+  double loss[7]; /* per alpha, the columns' losses added for s = 0 .. M - 1 */
+} vaqhip_learn_timing;
+/* the last device-form learn on this index (a multi index: on vaqhip_multi_shard(mx, 0)) */
+int vaqhip_last_learn_timing(vaqhip_index *ix, vaqhip_learn_timing *out);
 
 /* Test hook for FAST's smallQuantize(CreateLUT(query)): out[q*M*16 + s*16 + c], uint8; entries
  * c >= 1 << max(bits) (the reference's table has no such rows) are 0.  Needs max bits <= 4 and a
@@ -421,6 +460,9 @@ int vaqhip_search_refine(vaqhip_index *ix, vaqhip_refiner *r, const float *queri
                          int32_t *labels_out, float *distances_out);
 int vaqhip_search_refine_device(vaqhip_index *ix, vaqhip_refiner *r, const float *d_queries_raw, int nq, int R, int k,
                                 int32_t *d_labels_out, float *d_distances_out, void *stream);
+/* "Learning on the device" above, over the refiner's resident rows (raw rows: projected = 0) */
+int vaqhip_learn_quantization_from_refiner(vaqhip_index *ix, vaqhip_refiner *r, float sample_ratio,
+                                           float *offsets_out, float *scale_out);
 
 /* Exhaustive form of the resident refiner: the true k nearest rows of every query, i.e. what vaqhip_refiner_refine
  * would return for the candidate list id_base, id_base + 1, ..., id_base + N - 1 in that order if R were allowed to be
@@ -590,6 +632,15 @@ int vaqhip_multi_set_option(vaqhip_multi *mx, const char *key, int64_t value);
 int vaqhip_multi_set_lut_quantization(vaqhip_multi *mx, const float *offsets, const float *scale);
 int vaqhip_multi_learn_quantization(vaqhip_multi *mx, const float *X_rowmajor, int64_t n, int projected,
                                     float sample_ratio, float *offsets_out, float *scale_out);
+/* The device forms on a multi index.  _u8: vaqhip_learn_quantization_u8 on shard 0, replicated.  _from_refiner: the
+ * sample is cut by the shard that holds each row; every shard gathers its rows on its own device (a byte widened)
+ * and they are copied to the first device at their sample positions; the first device learns and every shard is
+ * given the result.  The index and the refiner must name the same device list and D (VAQHIP_EINVAL); a refiner
+ * without rows is VAQHIP_ESTATE. */
+int vaqhip_multi_learn_quantization_u8(vaqhip_multi *mx, const uint8_t *X_rowmajor, int64_t n, int projected,
+                                       float sample_ratio, float *offsets_out, float *scale_out);
+int vaqhip_multi_learn_quantization_from_refiner(vaqhip_multi *mx, vaqhip_multi_refiner *r, float sample_ratio,
+                                                 float *offsets_out, float *scale_out);
 /* Encode across the shards: VAQ::encode (vaqhip_encode's rule: strict `<`, first minimum, the checked projection on
  * VAQHIP_SUM_SEQUENTIAL shards) with every shard encoding the rows it will hold, on its own device.
  *   contract    vaqhip_multi_encode_set_codes leaves the index in exactly the state of vaqhip_encode on one index with

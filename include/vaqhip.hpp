@@ -606,6 +606,28 @@ public:
     pushedOffsets_ = mOffsets;
     pushedScale_ = mScale;
   }
+  // ... from byte rows (a bvecs dataset as its file holds it): only the sampled rows are uploaded, as bytes, and
+  // mOffsets / mScale are those of the float form over the widened rows, bit for bit (vaqhip_learn_quantization_u8,
+  // vaqhip_multi_learn_quantization_u8 after setDevices())
+  void learnQuantization(const RowMatrix<uint8_t> &XTrain, float sampleRatio) {
+    if ((int)XTrain.cols() != mTotalDim()) throw Error(VAQHIP_EINVAL, "vaqhip: XTrain has the wrong width");
+    learnWith([&](float *off, float *sc) {
+      return multiHandle() ? vaqhip_multi_learn_quantization_u8(multiHandle(), XTrain.data(), (int64_t)XTrain.rows(), 0,
+                                                                sampleRatio, off, sc)
+                           : vaqhip_learn_quantization_u8(handle(), XTrain.data(), (int64_t)XTrain.rows(), 0, sampleRatio,
+                                                          off, sc);
+    });
+  }
+  // ... from the rows setRefineDataset() left on the device, float or byte, read in place (the resident refiner on
+  // one device, the multi refiner after setDevices(): vaqhip_[multi_]learn_quantization_from_refiner)
+  void learnQuantizationRefineDataset(float sampleRatio) {
+    if (!refinerHandle() && !multiRefinerHandle())
+      throw Error(VAQHIP_ESTATE, "vaqhip: learnQuantizationRefineDataset needs setRefineDataset() first");
+    learnWith([&](float *off, float *sc) {
+      return multiHandle() ? vaqhip_multi_learn_quantization_from_refiner(multiHandle(), multiRefinerHandle(), sampleRatio, off, sc)
+                           : vaqhip_learn_quantization_from_refiner(handle(), refinerHandle(), sampleRatio, off, sc);
+    });
+  }
 
   // VAQ::search: pushes mOffsets / mScale when they changed, then runs the method in force
   template <class Mat> LabelDistVecF search(const Mat &XTest, const int k, bool verbose = false) {
@@ -619,6 +641,19 @@ public:
   }
 
 private:
+  // one of the device forms: call(offsets, scale) -> code; mOffsets / mScale change on success only
+  template <class Call> void learnWith(Call &&call) {
+    sync();
+    std::vector<float> off((size_t)mHighestSubs(), 0.0f), sc((size_t)mHighestSubs(), 0.0f);
+    const bool multi = multiHandle() != nullptr;
+    checkFast(call(off.data(), sc.data()), multi);
+    if (multi) fastQuantPushed_ = true;
+    mOffsets = off;
+    mScale = sc;
+    pushedFor_ = current();
+    pushedOffsets_ = mOffsets;
+    pushedScale_ = mScale;
+  }
   void pushQuantization() {
     sync();
     if (mOffsets.size() == (size_t)mHighestSubs() && mScale.size() == mOffsets.size() &&

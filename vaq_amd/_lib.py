@@ -54,6 +54,9 @@ SYMBOLS = [
     "vaqhip_multi_encode_set_codes_u8", "vaqhip_multi_encode_add_codes_u8",
     "vaqhip_multi_encode_lut_set_codes_u8", "vaqhip_multi_encode_lut_add_codes_u8",
     "vaqhip_multi_lut_fit_quantiles_u8",
+    "vaqhip_learn_quantization_u8", "vaqhip_learn_quantization_device", "vaqhip_learn_quantization_u8_device",
+    "vaqhip_learn_quantization_from_refiner", "vaqhip_learn_set_workspace", "vaqhip_last_learn_timing",
+    "vaqhip_multi_learn_quantization_u8", "vaqhip_multi_learn_quantization_from_refiner",
 ]
 MAX_DEVICES = 16
 
@@ -97,6 +100,13 @@ class LutFitTiming(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("project_ms", C.c_float), ("extract_ms", C.c_float),
                 ("sort_ms", C.c_float), ("quantile_ms", C.c_float), ("means_ms", C.c_float),
                 ("rows", C.c_int64), ("dims", C.c_int)]
+
+
+class LearnTiming(C.Structure):
+    _fields_ = [("sample_rows", C.c_int), ("column_groups", C.c_int), ("chosen_alpha", C.c_int),
+                ("gather_ms", C.c_float), ("tables_ms", C.c_float), ("sort_ms", C.c_float),
+                ("order_stats_ms", C.c_float), ("loss_ms", C.c_float), ("total_ms", C.c_float),
+                ("loss", C.c_double * 7)]
 
 
 class RefinerSearchTiming(C.Structure):
@@ -179,6 +189,13 @@ def load():
     L.vaqhip_index_set_lut_quantization.argtypes = [vp, vp, vp]
     L.vaqhip_learn_quantization.argtypes = [vp, vp, i64, i32, C.c_float, vp, vp]
     L.vaqhip_build_small_lut.argtypes = [vp, vp, i32, i32, vp]
+    for name in ("vaqhip_learn_quantization_u8", "vaqhip_learn_quantization_device",
+                 "vaqhip_learn_quantization_u8_device", "vaqhip_multi_learn_quantization_u8"):
+        getattr(L, name).argtypes = [vp, vp, i64, i32, C.c_float, vp, vp]
+    L.vaqhip_learn_quantization_from_refiner.argtypes = [vp, vp, C.c_float, vp, vp]
+    L.vaqhip_multi_learn_quantization_from_refiner.argtypes = [vp, vp, C.c_float, vp, vp]
+    L.vaqhip_learn_set_workspace.argtypes = [i64]
+    L.vaqhip_last_learn_timing.argtypes = [vp, C.POINTER(LearnTiming)]
     L.vaqhip_search.argtypes = [vp, vp, i32, i32, vp, vp]
     L.vaqhip_search_projected.argtypes = [vp, vp, i32, i32, vp, vp]
     L.vaqhip_search_device.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]

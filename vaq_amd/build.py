@@ -13,12 +13,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vaq_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "vaq_amd", "lib")
 LIB = os.path.join(LIBDIR, "libvaqhip.so")
-SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_fast.hip", "vaq_lutfit.hip", "vaq_refine.hip", "vaq_exhaust.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp", "vaqhip_lutfit.cpp", "vaqhip_refiner.cpp",
-           "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp", "vaqhip_multi_encode.cpp", "vaqhip_multi_lutfit.cpp", "vaqhip_rccl.cpp"]
+SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_fast.hip", "vaq_lutfit.hip", "vaq_learn.hip", "vaq_refine.hip", "vaq_exhaust.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp", "vaqhip_learn.cpp", "vaqhip_lutfit.cpp", "vaqhip_refiner.cpp",
+           "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp", "vaqhip_multi_encode.cpp", "vaqhip_multi_lutfit.cpp", "vaqhip_multi_learn.cpp", "vaqhip_rccl.cpp"]
 MULTI_REFINER_SOURCES = ("vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp")
 MULTI_ENCODE_SOURCE = "vaqhip_multi_encode.cpp"  # reads the multi refiner's resident rows: its headers too
 MULTI_LUTFIT_SOURCE = "vaqhip_multi_lutfit.cpp"  # the sharded quantile fit: reads the multi refiner's resident rows too
-MULTI_SOURCES = ("vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE) + MULTI_REFINER_SOURCES
+MULTI_LEARN_SOURCE = "vaqhip_multi_learn.cpp"  # learnQuantization over the multi refiner's resident rows
+MULTI_SOURCES = ("vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE, MULTI_LEARN_SOURCE) + MULTI_REFINER_SOURCES
 KERNEL_HEADER = os.path.join(CSRC, "vaq_kernels.h")
 OWNER_HEADER = os.path.join(CSRC, "refine_owner.h")  # the refiner's cut and label -> shard: vaq_kernels.h brings it
 API_HEADER = os.path.join(ROOT, "include", "vaqhip.h")
@@ -43,6 +44,8 @@ KMEANS_SAMPLE_HEADER = os.path.join(CSRC, "kmeans_sample.h")  # the k-means' sam
 LUTFIT_HEADER = os.path.join(CSRC, "vaq_lutfit.h")  # binaryEncodingLUT's two lambdas: kernels and host
 LUTFIT_DEV_HEADER = os.path.join(CSRC, "vaq_lutfit_dev.h")  # the column fit's two halves: kernels and the sharded fit
 LUTFIT_PLAN_HEADER = os.path.join(CSRC, "lutfit_multi_plan.h")  # owners, rounds, offsets of the sharded fit (no HIP)
+LEARN_PLAN_HEADER = os.path.join(CSRC, "learn_plan.h")  # learnQuantization's host arithmetic: both forms, the loss kernel (no HIP)
+LEARN_HEADER = os.path.join(CSRC, "vaq_learn.h")  # the kernels of learnQuantization's device forms
 
 
 def _deps(src: str):
@@ -55,13 +58,17 @@ def _deps(src: str):
         deps += [MULTI_HEADER, JOB_POOL_HEADER, RCCL_HEADER] if src in MULTI_SOURCES else [INDEX_HEADER]
     if src in ("vaq_kernels.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_lutfit.hip"):
         deps.append(DEV_HEADER)
-    if src in ("vaq_lutfit.hip", "vaqhip_lutfit.cpp", MULTI_LUTFIT_SOURCE):
+    if src in ("vaq_lutfit.hip", "vaqhip_lutfit.cpp", MULTI_LUTFIT_SOURCE, "vaq_learn.hip"):
         deps.append(LUTFIT_HEADER)
+    if src in ("vaq_learn.hip", "vaqhip_learn.cpp", "vaqhip_fast.cpp"):
+        deps.append(LEARN_PLAN_HEADER)
+    if src in ("vaq_learn.hip", "vaqhip_learn.cpp", MULTI_LEARN_SOURCE):
+        deps.append(LEARN_HEADER)
     if src in ("vaq_lutfit.hip", MULTI_LUTFIT_SOURCE):
         deps.append(LUTFIT_DEV_HEADER)
     if src == MULTI_LUTFIT_SOURCE:
         deps.append(LUTFIT_PLAN_HEADER)
-    if src in ("vaq_kmeans.hip", "vaqhip_codes.cpp", "vaqhip_multi_kmeans.cpp"):
+    if src in ("vaq_kmeans.hip", "vaqhip_codes.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_learn.cpp", MULTI_LEARN_SOURCE):
         deps.append(KMEANS_SAMPLE_HEADER)
     if src in ("vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_refine.hip", "vaq_exhaust.hip"):
         deps.append(SCAN_HEADER)
@@ -75,9 +82,9 @@ def _deps(src: str):
         deps.append(REFINE_GROUP_HEADER)
     if src == "vaq_exhaust.hip":
         deps.append(EXHAUST_HEADER)
-    if src == "vaqhip_refiner.cpp" or src in MULTI_REFINER_SOURCES or src in (MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE):
+    if src == "vaqhip_refiner.cpp" or src in MULTI_REFINER_SOURCES or src in (MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE, MULTI_LEARN_SOURCE):
         deps += [EXHAUST_PLAN_HEADER, REFINE_COMMON_HEADER]
-    if src in MULTI_REFINER_SOURCES or src in (MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE):
+    if src in MULTI_REFINER_SOURCES or src in (MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE, MULTI_LEARN_SOURCE):
         deps.append(MULTI_REFINER_HEADER)
     return deps
 OBJDIR = os.path.join(LIBDIR, "obj")

@@ -7,6 +7,7 @@
 #include <random>
 #include <thread>
 
+#include "learn_plan.h"
 #include "vaq_fast.h"
 
 using namespace vaqhost;
@@ -55,6 +56,22 @@ int fast_codes_update(vaqhip_index *ix, const uint16_t *d_u16, int64_t row_begin
   ix->fast_rows = row_end;
   return VAQHIP_OK;
 }
+// vaqhip_index_set_lut_quantization with the index locked and its device current (the learnt forms end with it)
+int set_quantization_locked(vaqhip_index *ix, const float *off, const float *scale) {
+  for (int s = 0; s < ix->M; s++)
+    if (!std::isfinite(off[s]) || !std::isfinite(scale[s]) || !(scale[s] > 0.0f))
+      return fail(VAQHIP_EINVAL, "subspace %d: offset %g, scale %g (finite, scale > 0)", s, off[s], scale[s]);
+  HIP_TRY(ix->d_fast_off.ensure((size_t)ix->M * sizeof(float)));
+  HIP_TRY(ix->d_fast_scale.ensure((size_t)ix->M * sizeof(float)));
+  WS_SCOPE(ws, ix, ix->stream);  // (a search on another stream may still read them)
+  HIP_TRY(hipMemcpyAsync(ix->d_fast_off.p, off, (size_t)ix->M * sizeof(float), hipMemcpyHostToDevice, ix->stream));
+  HIP_TRY(hipMemcpyAsync(ix->d_fast_scale.p, scale, (size_t)ix->M * sizeof(float), hipMemcpyHostToDevice, ix->stream));
+  HIP_TRY(hipStreamSynchronize(ix->stream));
+  ix->fast_off.assign(off, off + ix->M);
+  ix->fast_scale.assign(scale, scale + ix->M);
+  ix->fast_q = true;
+  return ws.finish();
+}
 } // namespace vaqhost
 
 namespace {
@@ -82,30 +99,9 @@ int fast_codes_ensure(vaqhip_index *ix, hipStream_t st) {
   return fast_codes_update(ix, rows.as<uint16_t>(), 0, ix->N, st);  // synchronises: `rows` is freed on return
 }
 
-int set_quantization_locked(vaqhip_index *ix, const float *off, const float *scale) {
-  for (int s = 0; s < ix->M; s++)
-    if (!std::isfinite(off[s]) || !std::isfinite(scale[s]) || !(scale[s] > 0.0f))
-      return fail(VAQHIP_EINVAL, "subspace %d: offset %g, scale %g (finite, scale > 0)", s, off[s], scale[s]);
-  HIP_TRY(ix->d_fast_off.ensure((size_t)ix->M * sizeof(float)));
-  HIP_TRY(ix->d_fast_scale.ensure((size_t)ix->M * sizeof(float)));
-  WS_SCOPE(ws, ix, ix->stream);  // (a search on another stream may still read them)
-  HIP_TRY(hipMemcpyAsync(ix->d_fast_off.p, off, (size_t)ix->M * sizeof(float), hipMemcpyHostToDevice, ix->stream));
-  HIP_TRY(hipMemcpyAsync(ix->d_fast_scale.p, scale, (size_t)ix->M * sizeof(float), hipMemcpyHostToDevice, ix->stream));
-  HIP_TRY(hipStreamSynchronize(ix->stream));
-  ix->fast_off.assign(off, off + ix->M);
-  ix->fast_scale.assign(scale, scale + ix->M);
-  ix->fast_q = true;
-  return ws.finish();
-}
-
-// utils/Math.hpp:190-213 on an ascending column: the value at rank percent * (rows - 1), as written
-// (its `fraction` is taken against round(), not floor(), and may be negative)
+// utils/Math.hpp:190-213 on an ascending column (learn_plan.h has the body, shared with the device forms)
 float percentile_sorted(const float *v, int64_t rows, float percent) {
-  const float nthF = percent * static_cast<float>(rows - 1);
-  if (std::fabs(std::round(nthF) - nthF) <= 0.00001f) return v[static_cast<int64_t>(nthF)];
-  const float f = v[static_cast<int64_t>(std::floor(nthF))], c = v[static_cast<int64_t>(std::ceil(nthF))];
-  const float fraction = nthF - std::round(nthF);
-  return f + (c - f) * fraction;
+  return vaq::learn::percentile_at([v](int64_t i) { return v[i]; }, rows, percent);
 }
 } // namespace
 

@@ -129,6 +129,7 @@ struct vaqhip_index {
   int ev_used = 0;              // searches recorded since the last vaqhip_last_timing
   vaqhip_timing last = {};
   vaqhip_kmeans_timing km_last = {};  // the last vaqhip_index_cluster_ti_kmeans
+  vaqhip_learn_timing learn_last = {};  // the last device-form learnQuantization (vaqhip_learn.cpp)
   std::mutex mu;
 };
 
@@ -168,6 +169,12 @@ int search_fast(vaqhip_index *ix, const float *d_queries, int nq, int k, int pro
                 float *d_dist, hipStream_t st, const FastShardPart *part = nullptr);
 void fast_release(vaqhip_index *ix);
 int fast_codes_update(vaqhip_index *ix, const uint16_t *d_u16, int64_t row_begin, int64_t row_end, hipStream_t st);
+// vaqhip_index_set_lut_quantization with the index locked and its device current
+int set_quantization_locked(vaqhip_index *ix, const float *off, const float *scale);
+// vaqhip_learn.cpp: vaqhip_learn_quantization[_u8]_device's body, which vaqhip_refiner.cpp calls over its resident
+// rows (n x D on the index's device, complete); takes the index's lock itself
+int learn_rows_device(vaqhip_index *ix, vaq::RowsRef d_X, int64_t n, int projected, float ratio, float *offsets_out,
+                      float *scale_out);
 
 // The preamble of an entry point: the index's lock, then its device current (put back when the scope ends).
 // rc: VAQHIP_OK, or what the entry returns at once -- ENTRY(ix) declares it and does so, as HIP_TRY would.

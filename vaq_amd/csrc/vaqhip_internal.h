@@ -75,6 +75,14 @@ int vaqhip_internal_kmeans_gather(vaqhip_index *ix, const int *sample_rows, int 
 /* the index's subspace table (vaq::SubDesc [M]) and centroids on its device, and D / M */
 int vaqhip_internal_kmeans_tables(vaqhip_index *ix, const void **d_sub, const float **d_cent, int *L);
 
+
+/* learnQuantization's device forms on a multi index (vaqhip_learn.cpp).  1 when the index can hold FAST codes. */
+int vaqhip_internal_fast_ok(vaqhip_index *ix);
+/* vaqhip_learn_quantization_device without the sampling: d_rows [sample][D] floats on the index's device, complete,
+ * ARE the sample in sample order.  gather_ms: what the caller spent bringing them there, for the timing. */
+int vaqhip_internal_learn_sample_device(vaqhip_index *ix, const float *d_rows, int sample, int projected,
+                                        float gather_ms, float *offsets_out, float *scale_out);
+
 #ifdef __cplusplus
 }
 #endif

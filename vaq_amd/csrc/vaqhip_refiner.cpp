@@ -291,4 +291,21 @@ int vaqhip_search_refine(vaqhip_index *ix, vaqhip_refiner *r, const float *queri
   });
 }
 
+// learnQuantization over the resident rows, read in place as raw rows (vaqhip_learn.cpp does the rest, under the
+// index's lock; the refiner's lock keeps the rows where they are meanwhile)
+int vaqhip_learn_quantization_from_refiner(vaqhip_index *ix, vaqhip_refiner *r, float sample_ratio, float *offsets_out,
+                                           float *scale_out) {
+  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
+  if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
+  std::lock_guard<std::mutex> lk(r->mu);
+  if (r->N == 0) return fail(VAQHIP_ESTATE, "the refiner holds no rows: vaqhip_refiner_set_rows first");
+  vaqhip_info inf;
+  if (int rc = vaqhip_index_info(ix, &inf)) return rc;
+  if (inf.D != r->D) return fail(VAQHIP_EINVAL, "the index has D=%d, the refiner D=%d", inf.D, r->D);
+  if (inf.device_id != r->device)
+    return fail(VAQHIP_EINVAL, "the index is on device %d, the refiner on device %d", inf.device_id, r->device);
+  // (set_rows and add_rows copy synchronously: the rows are complete)
+  return learn_rows_device(ix, r->rows.rows(), r->N, 0, sample_ratio, offsets_out, scale_out);
+}
+
 }  // extern "C"

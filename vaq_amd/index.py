@@ -631,6 +631,15 @@ class VaqHip:
         _lib.check(_lib.load().vaqhip_last_timing(self._h, C.byref(t)))
         return {f: getattr(t, f) for f, _ in _lib.Timing._fields_}
 
+    def last_learn_timing(self) -> dict:
+        """Figures of the last device-form learnQuantization on this index (vaqhip_last_learn_timing): the sample,
+        the column groups, the chosen alpha, the phases' host-clock times and the seven alphas' losses."""
+        t = _lib.LearnTiming()
+        _lib.check(_lib.load().vaqhip_last_learn_timing(self._h, C.byref(t)))
+        d = {f: getattr(t, f) for f, _ in _lib.LearnTiming._fields_ if f != "loss"}
+        d["loss"] = np.array(list(t.loss), np.float64)
+        return d
+
     def last_kmeans_timing(self) -> dict:
         """Figures of the last clusterTI(True) on this index (vaqhip_last_kmeans_timing)."""
         t = _lib.KmeansTiming()
@@ -1276,6 +1285,25 @@ class VaqHipMulti:
             self._h, _ptr(X), X.shape[0], 1 if projected else 0, C.c_float(sampleRatio), _ptr(off), _ptr(sc)))
         return off, sc
 
+    def learn_quantization_u8(self, XTrain: np.ndarray, sampleRatio: float, projected: bool = False):
+        """learn_quantization() from byte rows (vaqhip_multi_learn_quantization_u8); anything but a contiguous uint8
+        n x D array is EINVAL.  Returns (offsets, scale)."""
+        X = _u8_rows(XTrain, self.D)
+        off = np.empty(self.M, np.float32)
+        sc = np.empty(self.M, np.float32)
+        _lib.check_multi(_lib.load().vaqhip_multi_learn_quantization_u8(
+            self._h, _ptr(X), X.shape[0], 1 if projected else 0, C.c_float(sampleRatio), _ptr(off), _ptr(sc)))
+        return off, sc
+
+    def learn_quantization_from_refiner(self, refiner: "VaqMultiRefiner", sampleRatio: float):
+        """learn_quantization() over the raw rows a VaqMultiRefiner on the same devices holds, read where they are
+        (vaqhip_multi_learn_quantization_from_refiner).  Returns (offsets, scale)."""
+        off = np.empty(self.M, np.float32)
+        sc = np.empty(self.M, np.float32)
+        _lib.check_multi(_lib.load().vaqhip_multi_learn_quantization_from_refiner(
+            self._h, refiner._h, C.c_float(sampleRatio), _ptr(off), _ptr(sc)))
+        return off, sc
+
     def set_ti_clusters(self, clusters: Optional[np.ndarray], seg: int = 0) -> None:
         if clusters is None:
             _lib.check_multi(_lib.load().vaqhip_multi_set_ti_clusters(self._h, None, 0, 0))
@@ -1447,6 +1475,53 @@ class VaqHipFast(VaqHip):
                                                          C.c_float(sampleRatio), _ptr(off), _ptr(sc)))
         self.mOffsets, self.mScale = off, sc
         self._q_sig = (self._h.value, _wref(off), _wref(sc))
+
+    def _learn_with(self, call) -> None:
+        """One of the device forms: call(off, sc) -> code; mOffsets / mScale on success, as learnQuantization."""
+        M = len(self.mBitsAlloc)
+        off = np.empty(M, np.float32)
+        sc = np.empty(M, np.float32)
+        _lib.check(call(_ptr(off), _ptr(sc)))
+        self.mOffsets, self.mScale = off, sc
+        self._q_sig = (self._h.value, _wref(off), _wref(sc))
+
+    def learnQuantization_u8(self, XTrain: np.ndarray, sampleRatio: float, projected: bool = False) -> None:
+        """learnQuantization() from byte rows (vaqhip_learn_quantization_u8): only the sampled rows are uploaded, as
+        bytes; mOffsets / mScale are those of learnQuantization(XTrain.astype(float32)), bit for bit.  Anything but
+        a contiguous uint8 n x D array is EINVAL: nothing is converted."""
+        X = _u8_rows(XTrain, self.mTotalDim)
+        self._ensure_index()
+        self._learn_with(lambda off, sc: _lib.load().vaqhip_learn_quantization_u8(
+            self._h, _ptr(X), X.shape[0], 1 if projected else 0, C.c_float(sampleRatio), off, sc))
+
+    def learnQuantization_device(self, d_X, sampleRatio: float, projected: bool = False) -> None:
+        """learnQuantization() from a float32 torch CUDA tensor on the index's device
+        (vaqhip_learn_quantization_device).  The call runs on the index's own stream: torch's current stream is
+        synchronised first, so that the rows are complete."""
+        import torch
+        x = d_X.contiguous()
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.shape[1] == self.mTotalDim):
+            raise _lib.VaqHipError(-1, f"rows must be a float32 n x {self.mTotalDim} CUDA tensor")
+        self._ensure_index()
+        torch.cuda.current_stream(x.device).synchronize()
+        self._learn_with(lambda off, sc: _lib.load().vaqhip_learn_quantization_device(
+            self._h, C.c_void_p(x.data_ptr()), x.shape[0], 1 if projected else 0, C.c_float(sampleRatio), off, sc))
+
+    def learnQuantization_u8_device(self, d_X, sampleRatio: float, projected: bool = False) -> None:
+        """The same from a uint8 torch CUDA tensor (vaqhip_learn_quantization_u8_device); it may start at any byte."""
+        import torch
+        x = _u8_rows_device(d_X, self.mTotalDim)
+        self._ensure_index()
+        torch.cuda.current_stream(x.device).synchronize()
+        self._learn_with(lambda off, sc: _lib.load().vaqhip_learn_quantization_u8_device(
+            self._h, C.c_void_p(x.data_ptr()), x.shape[0], 1 if projected else 0, C.c_float(sampleRatio), off, sc))
+
+    def learnQuantizationFromRefiner(self, refiner: "VaqRefiner", sampleRatio: float) -> None:
+        """learnQuantization() over the raw rows resident in a VaqRefiner on the same device, float or byte, read in
+        place (vaqhip_learn_quantization_from_refiner)."""
+        self._ensure_index()
+        self._learn_with(lambda off, sc: _lib.load().vaqhip_learn_quantization_from_refiner(
+            self._h, refiner._h, C.c_float(sampleRatio), off, sc))
 
     def _ensure_quant(self):
         if self.mOffsets is None or self.mScale is None:
