@@ -1,9 +1,11 @@
 // demo_vaqhip.cpp -- the query half of the reference's examples/demo_vaq.cpp
-// (:58-92 load, :336-363 search + recall) on the MI355X path.  Training is out
-// of scope (it needs glpk / armadillo in the reference), so the index is read
-// from the files `demo_vaq --save <centroids> --save-enc <codebook>` writes,
-// plus the rotation (which the reference never persists) as a raw D x D
-// float32 file.
+// (:58-92 load, :336-363 search + recall) on the MI355X path.  The PCA and the
+// bit allocation of VAQ::train are out of scope (they need glpk / armadillo in
+// the reference), so the index is read from the files `demo_vaq --save
+// <centroids> --save-enc <codebook>` writes, plus the rotation (which the
+// reference never persists) as a raw D x D float32 file -- or, with
+// --fit-codebooks and --encode, built here from the raw vectors, the rotation
+// and the bits.
 //
 //   demo_vaqhip --centroids c.bin --codebook cb.bin [--eigen e.f32] \
 //               --queries q.fvecs --timeseries-size 128 [--queries-size N] \
@@ -36,6 +38,13 @@
 //                                           With --devices every shard encodes the rows it will hold and keeps their
 //                                           codes; with --devices and --refine-resident the rows are uploaded once, cut
 //                                           over the GPUs, and encoded where they lie -- the same codes either way)
+//               [--fit-codebooks --bits 8,8,... --dataset base.fvecs [--save c.bin] [--max-iter 25]]
+//                                          (instead of --centroids: the subspace codebooks are fitted on the GPU from
+//                                           the raw vectors by KMeans::staticFitSampling, the call of VAQ.cpp:644-649 --
+//                                           not the arma::kmeans call VAQ::train runs today; --eigen is applied first,
+//                                           the bits are the caller's.  --file-format-ori bvecs fits from the bytes,
+//                                           --refine-resident from the rows on the device.  --save writes them as
+//                                           demo_vaq --save does; composes with --encode; without --queries it ends there)
 //               with a ...,FAST method (codes of at most 4 bits): --dataset base.fvecs [--dataset-size N]
 //               [--learn-ratio 0.05]       (demo_vaq.cpp:42, :120-124: VAQ::learnQuantization on the raw dataset; from the
 //                                           bytes with --file-format-ori bvecs, from the resident rows with --refine-resident)
@@ -136,7 +145,7 @@ int main(int argc, char **argv) {
                                           {"timeseries-size", "128"}, {"queries-size", "-1"}};
   for (int i = 1; i < argc; i += 2) {
     if (std::strcmp(argv[i], "--refine-resident") == 0 || std::strcmp(argv[i], "--exact-groundtruth") == 0 ||
-        std::strcmp(argv[i], "--encode") == 0) {
+        std::strcmp(argv[i], "--encode") == 0 || std::strcmp(argv[i], "--fit-codebooks") == 0) {
       a[argv[i] + 2] = "1";  // the switches without a value
       i--;
       continue;
@@ -158,15 +167,20 @@ int main(int argc, char **argv) {
       return 1;
     }
   }
-  const bool encode = a.count("encode") != 0;
-  for (const char *req : {"centroids", encode ? "dataset" : "codebook", "queries"})
+  const bool encode = a.count("encode") != 0, fit = a.count("fit-codebooks") != 0;
+  const bool fit_only = fit && !encode && !a.count("codebook") && !a.count("queries");  // fit, --save, done
+  std::vector<std::string> required = {fit ? "bits" : "centroids"};
+  if (fit || encode) required.push_back("dataset");
+  if (!encode && !fit_only) required.push_back("codebook");
+  if (!fit_only) required.push_back("queries");
+  for (const std::string &req : required)
     if (!a.count(req)) { std::cerr << "missing --" << req << "\n"; return 2; }
   try {
     VaqHipFast vaq;  // VaqHip plus the FAST method
     vaq.parseMethodString(a["method"]);
-    vaq.mCentroidsPerSubs = loadCentroids(a["centroids"]);
-    if (!encode) vaq.mCodebook = loadCodebook(a["codebook"]);
-    const int M = (int)vaq.mCentroidsPerSubs.size();
+    if (!fit) vaq.mCentroidsPerSubs = loadCentroids(a["centroids"]);
+    if (!encode && !fit_only) vaq.mCodebook = loadCodebook(a["codebook"]);
+    const int M = fit ? (int)intList(a["bits"]).size() : (int)vaq.mCentroidsPerSubs.size();
     if (a.count("bits")) {  // --hc-bitalloc style list (demo_vaq.cpp:94-97)
       std::stringstream ss(a["bits"]);
       std::string t;
@@ -174,8 +188,8 @@ int main(int argc, char **argv) {
     } else {
       for (int s = 0; s < M; s++) vaq.mBitsAlloc.push_back((int)std::lround(std::log2((double)vaq.mCentroidsPerSubs[s].rows())));
     }
-    const int D = vaq.mTotalDim();
     const int N = std::atoi(a["timeseries-size"].c_str());
+    const int D = fit ? N : vaq.mTotalDim();  // (a fit works on the raw vectors as they are: no padding)
     if (a.count("eigen")) {
       vaq.mEigenVectors = RowMatrixF(D, D);
       detail::File f(a["eigen"], "rb");
@@ -204,6 +218,36 @@ int main(int argc, char **argv) {
     };
     size_t resident_rows = 0;
     bool uploaded = false;  // the raw vectors are resident already (--encode with --refine-resident)
+    if (fit) {  // VAQ.cpp:628-660 by the call of :644-649
+      const int dsize = a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1;
+      const int max_iter = a.count("max-iter") ? std::atoi(a["max-iter"].c_str()) : 25;
+      const char *from = "";
+      auto t0 = std::chrono::steady_clock::now();
+      if (a.count("refine-resident") && !a.count("devices")) {
+        resident_rows = uploadRefine(a.count("dataset-refine") ? a["dataset-refine"] : a["dataset"], dsize);
+        uploaded = true;
+        t0 = std::chrono::steady_clock::now();
+        vaq.fitCodebooksRefineDataset(max_iter);
+        from = " (from the resident rows)";
+      } else if (g_bvecs) {
+        RowMatrix<uint8_t> dataset8 = readBVecsU8(a["dataset"], N, dsize);
+        t0 = std::chrono::steady_clock::now();
+        vaq.fitCodebooks(dataset8, max_iter);
+        from = " (from the byte rows of the bvecs file)";
+      } else {
+        RowMatrixF dataset = readFVecs(a["dataset"], N, dsize, 0);
+        t0 = std::chrono::steady_clock::now();
+        vaq.fitCodebooks(dataset, max_iter);
+      }
+      std::cout << "== Codebook fit time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+                << " s" << from << "; iterations";
+      for (int it : vaq.mCodebookIters) std::cout << " " << it;
+      std::cout << "; NaN centres";
+      for (int nn : vaq.mCodebookNanRows) std::cout << " " << nn;
+      std::cout << std::endl;
+      if (a.count("save")) saveCentroids(vaq.mCentroidsPerSubs, a["save"]);
+      if (fit_only) return 0;
+    }
     if (encode) {  // demo_vaq.cpp:126-135, from the raw vectors
       const int dsize = a.count("dataset-size") ? std::atoi(a["dataset-size"].c_str()) : -1;
       auto t0 = std::chrono::steady_clock::now();

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 119
+#define VAQHIP_VERSION 120
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -391,6 +391,64 @@ int vaqhip_encode_lut_u8(vaqhip_index *ix, const uint8_t *X_rowmajor, int64_t n,
 int vaqhip_encode_lut_u8_device(vaqhip_index *ix, const uint8_t *d_X, int64_t n, int projected, uint16_t *d_codes_out,
                                 void *stream);
 
+/* ---------------------------------------------------------------------------
+ * Fitting the subspace codebooks mCentroidsPerSubs: KMeans::staticFitSampling (KMeans.hpp:487-616), the call of
+ * VAQ.cpp:644-649 -- KMeans::staticFitSampling(XTrain.block(0, s * L, n, L), 1 << bits[s], 25) for every subspace s.
+ * It is NOT the arma::kmeans call VAQ::train runs today beside it (armadillo: not reproduced).  The PCA and the bit
+ * allocation stay the caller's: eigvec and bits come in.  With this an index is built on the device from raw rows:
+ * fit, vaqhip_index_create with the centres, vaqhip_encode.
+ *   X              n x D row-major; in PCA space when eigvec is NULL, else X * eigvec by vaqhip_project's chain, unchecked
+ *   M, bits[M]     M subspaces of L = D / M columns, k_s = 1 << bits[s] centres, 1 <= bits[s] <= VAQHIP_MAX_BITS
+ *   sample         a fit of k centres works on rows_s = min(n, max(256 * k, 65536)) rows: all rows in order, or the
+ *                  first rows_s of randomPermutation(n) (mt19937(13517106)).  The head of the permutation for a smaller
+ *                  sample is a prefix of the head for a larger one, so ONE sample (the largest) is gathered and
+ *                  projected and every subspace works on its prefix; rows outside it are never read.
+ *   seeds          means[i] = sample row randomPermutation(rows_s)[i]
+ *   Lloyd          until no centre of the subspace changes or max_iter (the reference passes 25): assign by
+ *                  sqrt((x - mean).squaredNorm()) in Eigen's summation order over the L floats (plain sequential for
+ *                  L < 8), centres ascending, strict <; sums in the order of the reference's two OpenMP threads (rows
+ *                  [0, ceil(rows_s / 2)) and the rest, each ascending from +0); new = ((0 + p0) + p1) / float(count).
+ *                  An empty cluster becomes NaN and stays NaN, and that subspace runs to max_iter, as the reference's.
+ *   centroids_out  the M matrices back to back in subspace order, k_s x L row-major each (sum of k_s * L floats): what
+ *                  vaqhip_index_create takes
+ *   iters_out[M]   the reference's iter_count per subspace (the iteration that changes nothing is counted); may be NULL
+ *   nan_rows_out[M]  centres of the subspace that hold a NaN; may be NULL.  Both are host arrays in every form.
+ * Every centre equals the reference's bit for bit (a NaN by position), pinned by tests/golden/codebooks.  All
+ * subspaces are fitted together, one launch per phase and iteration; no value of a subspace depends on another.
+ * Refused before any device work, the outputs left untouched: VAQHIP_EINVAL for a null X, bits or centroids_out,
+ * n < 1, n >= 2^31, M < 1, D % M != 0, max_iter < 1, bits outside 1..VAQHIP_MAX_BITS, and 1 << bits[s] above that
+ * subspace's rows_s (the reference seeds from rows out of bounds); VAQHIP_EUNSUPPORTED for M > VAQHIP_MAX_SUBSPACES
+ * and D > 4096.  Known only after the run: VAQHIP_EINVAL when a row is
+ * at a distance >= FLT_MAX or NaN from every centre (the reference indexes row -1); VAQHIP_ENOMEM from a failed
+ * allocation (nothing is kept).  Workspace: the projected sample (sample x D floats, twice with a gathered sample and
+ * eigvec) and 16 bytes per (subspace, sampled row).  The host forms upload only the sample; the _device forms take
+ * device pointers for X, eigvec and centroids_out (bits and the two small outputs stay host arrays), work on
+ * `stream` and synchronise it before they return.  The _u8 forms: the float call's result on the widened matrix, bit
+ * for bit (see vaqhip_encode_u8; any byte address in the _device form). */
+int vaqhip_fit_codebooks(int device_id, const float *X_rowmajor, int64_t n, int D, int M, const int *bits,
+                         const float *eigvec_real_rowmajor, int max_iter, float *centroids_out, int *iters_out,
+                         int *nan_rows_out);
+int vaqhip_fit_codebooks_device(int device_id, const float *d_X, int64_t n, int D, int M, const int *bits,
+                                const float *d_eigvec, int max_iter, float *d_centroids_out, int *iters_out,
+                                int *nan_rows_out, void *stream);
+int vaqhip_fit_codebooks_u8(int device_id, const uint8_t *X_rowmajor, int64_t n, int D, int M, const int *bits,
+                            const float *eigvec_real_rowmajor, int max_iter, float *centroids_out, int *iters_out,
+                            int *nan_rows_out);
+int vaqhip_fit_codebooks_u8_device(int device_id, const uint8_t *d_X, int64_t n, int D, int M, const int *bits,
+                                   const float *d_eigvec, int max_iter, float *d_centroids_out, int *iters_out,
+                                   int *nan_rows_out, void *stream);
+typedef struct {
+  float total_ms;                          /* host time of the last fit on this thread, the copies of the host forms excluded */
+  float gather_ms;                         /* only with vaqhip_fit_codebooks_set_timing(1), else 0: gather, project, seeds */
+  float assign_ms, accumulate_ms, update_ms;  /*   summed over the iterations; accumulate = sort + run bounds + sums */
+  int iterations;                          /* the largest iteration count of a subspace */
+  int subspaces, dims;
+  int64_t sample_rows;                     /* rows gathered and projected */
+  int64_t rows;
+} vaqhip_fit_codebooks_timing;
+int vaqhip_fit_codebooks_set_timing(int on);                             /* per calling thread */
+int vaqhip_last_fit_codebooks_timing(vaqhip_fit_codebooks_timing *out);  /* the calling thread's last fit */
+
 /* VAQ::refine (VAQ.cpp:849-876): exact squared L2 in the ORIGINAL space between each
  * query and its R candidate rows of the raw dataset, k best by the same k-min rule.  The sum is
  * sequential (dist += t * t), ties go to the smaller label: see the resident refiner below for the
@@ -463,6 +521,10 @@ int vaqhip_search_refine_device(vaqhip_index *ix, vaqhip_refiner *r, const float
 /* "Learning on the device" above, over the refiner's resident rows (raw rows: projected = 0) */
 int vaqhip_learn_quantization_from_refiner(vaqhip_index *ix, vaqhip_refiner *r, float sample_ratio,
                                            float *offsets_out, float *scale_out);
+/* vaqhip_fit_codebooks above over the refiner's resident rows, float or byte, read in place (eigvec and the outputs are
+ * host arrays); VAQHIP_ESTATE on a refiner without rows */
+int vaqhip_refiner_fit_codebooks(vaqhip_refiner *r, int M, const int *bits, const float *eigvec_real_rowmajor,
+                                 int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out);
 
 /* Exhaustive form of the resident refiner: the true k nearest rows of every query, i.e. what vaqhip_refiner_refine
  * would return for the candidate list id_base, id_base + 1, ..., id_base + N - 1 in that order if R were allowed to be

@@ -377,6 +377,64 @@ public:
     codes_set_ = true;
   }
 
+  // The codebook step of VAQ::train (VAQ.cpp:628-660) by the call of :644-649, KMeans::staticFitSampling per subspace
+  // (NOT the arma::kmeans call that runs beside it today): fills mCentroidsPerSubs from mBitsAlloc and mEigenVectors
+  // (empty: XTrain is in PCA space already), every centre the reference's bit for bit (vaqhip_fit_codebooks; one
+  // device, mDevice).  XTrain: raw rows, as wide as the index.  mCodebookIters / mCodebookNanRows: per subspace the
+  // reference's iter_count and the centres an empty cluster left NaN.  PCA and bit allocation stay the caller's.
+  std::vector<int> mCodebookIters, mCodebookNanRows;
+  void fitCodebooks(const RowMatrixF &XTrain, int maxIter = 25) { fitCodebooksRows(XTrain.data(), (int64_t)XTrain.rows(), (int)XTrain.cols(), maxIter); }
+  // from byte rows (readBVecsU8): the float overload's centres on the widened rows, bit for bit
+  void fitCodebooks(const RowMatrix<uint8_t> &XTrain, int maxIter = 25) { fitCodebooksRows(XTrain.data(), (int64_t)XTrain.rows(), (int)XTrain.cols(), maxIter); }
+  // from the rows setRefineDataset() left on the device (one device), float or byte, read in place
+  void fitCodebooksRefineDataset(int maxIter = 25) {
+    if (!rf_) throw Error(mDevices.empty() ? VAQHIP_ESTATE : VAQHIP_EUNSUPPORTED,
+                          "vaqhip: fitCodebooksRefineDataset needs setRefineDataset() on one device first");
+    fitCodebooksWith(rf_dim_, [&](const float *eig, float *cent) {
+      return vaqhip_refiner_fit_codebooks(rf_, mHighestSubs(), mBitsAlloc.data(), eig, maxIter, cent, mCodebookIters.data(),
+                                          mCodebookNanRows.data());
+    });
+  }
+
+private:
+  static int fitCodebooksCall(int dev, const float *X, int64_t n, int D, int M, const int *bits, const float *eig, int it,
+                              float *cent, int *iters, int *nan) {
+    return vaqhip_fit_codebooks(dev, X, n, D, M, bits, eig, it, cent, iters, nan);
+  }
+  static int fitCodebooksCall(int dev, const uint8_t *X, int64_t n, int D, int M, const int *bits, const float *eig, int it,
+                              float *cent, int *iters, int *nan) {
+    return vaqhip_fit_codebooks_u8(dev, X, n, D, M, bits, eig, it, cent, iters, nan);
+  }
+  template <class T> void fitCodebooksRows(const T *X, int64_t n, int D, int maxIter) {
+    fitCodebooksWith(D, [&](const float *eig, float *cent) {
+      return fitCodebooksCall(mDevice, X, n, D, mHighestSubs(), mBitsAlloc.data(), eig, maxIter, cent, mCodebookIters.data(),
+                              mCodebookNanRows.data());
+    });
+  }
+  template <class Call> void fitCodebooksWith(int D, Call call) {
+    const int M = mHighestSubs();
+    if (M < 1 || D < 1 || D % M != 0) throw Error(VAQHIP_EINVAL, "vaqhip: fitCodebooks needs mBitsAlloc, and rows of M subspaces");
+    if (mEigenVectors.rows() && ((int)mEigenVectors.rows() != D || (int)mEigenVectors.cols() != D))
+      throw Error(VAQHIP_EINVAL, "vaqhip: mEigenVectors is not D x D");
+    const int L = D / M;
+    size_t total = 0;
+    for (int b : mBitsAlloc) total += (b > 0 && b < 31) ? ((size_t)1 << b) * L : 0;  // (bits out of range: the call refuses them)
+    std::vector<float> cent(total ? total : 1);
+    mCodebookIters.assign((size_t)M, 0);
+    mCodebookNanRows.assign((size_t)M, 0);
+    check(call(mEigenVectors.rows() ? mEigenVectors.data() : nullptr, cent.data()));
+    invalidate();  // (an index made from other centres)
+    mCentroidsPerSubs.clear();
+    size_t off = 0;
+    for (int s = 0; s < M; s++) {
+      RowMatrixF c((size_t)1 << mBitsAlloc[s], (size_t)L);
+      std::copy(cent.begin() + off, cent.begin() + off + c.rows() * c.cols(), c.data());
+      off += c.rows() * c.cols();
+      mCentroidsPerSubs.push_back(std::move(c));
+    }
+  }
+
+public:
   // VAQ::refine, VAQ.hpp:104 / VAQ.cpp:849-876
   template <class MatQ, class MatT>
   LabelDistVecF refine(const MatQ &XTest, const LabelDistVecF &answersIn, const MatT &XTrain, const int k) {

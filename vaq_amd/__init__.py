@@ -9,12 +9,16 @@ Product surface:
   vaq_amd.VaqMultiRefiner     the same over raw rows sharded across several GPUs
   vaq_amd.lut_fit_quantiles_multi  binaryEncodingLUT's quantile codebooks with the rows cut over several GPUs
   vaq_amd.lut_fit_quantiles_multi_u8  the same from byte rows (a bvecs dataset as its file holds it)
+  vaq_amd.fit_codebooks       the subspace codebooks (KMeans::staticFitSampling per subspace) from raw rows
+  vaq_amd.fit_codebooks_u8    the same from byte rows; VaqRefiner.fit_codebooks over resident rows
 There is no CPU path: importing works anywhere, but every compute call needs
 the HIP library and a GPU and raises otherwise.
 """
 from ._lib import VaqHipError, lib_path, load  # noqa: F401
 from .index import LabelDistVec, NNMethod, VaqHip, VaqHipFast, VaqHipMulti, VaqMultiRefiner, VaqRefiner  # noqa: F401
 from .index import last_lut_fit_multi_timing, lut_fit_quantiles_multi, lut_fit_quantiles_multi_u8  # noqa: F401
+from .index import fit_codebooks, fit_codebooks_timing, fit_codebooks_u8, last_fit_codebooks_timing  # noqa: F401
 
 __all__ = ["VaqHip", "VaqHipFast", "VaqHipMulti", "VaqRefiner", "VaqMultiRefiner", "NNMethod", "LabelDistVec", "VaqHipError", "load", "lib_path",
-           "lut_fit_quantiles_multi", "lut_fit_quantiles_multi_u8", "last_lut_fit_multi_timing"]
+           "lut_fit_quantiles_multi", "lut_fit_quantiles_multi_u8", "last_lut_fit_multi_timing",
+           "fit_codebooks", "fit_codebooks_u8", "fit_codebooks_timing", "last_fit_codebooks_timing"]

@@ -57,6 +57,8 @@ SYMBOLS = [
     "vaqhip_learn_quantization_u8", "vaqhip_learn_quantization_device", "vaqhip_learn_quantization_u8_device",
     "vaqhip_learn_quantization_from_refiner", "vaqhip_learn_set_workspace", "vaqhip_last_learn_timing",
     "vaqhip_multi_learn_quantization_u8", "vaqhip_multi_learn_quantization_from_refiner",
+    "vaqhip_fit_codebooks", "vaqhip_fit_codebooks_device", "vaqhip_fit_codebooks_u8", "vaqhip_fit_codebooks_u8_device",
+    "vaqhip_refiner_fit_codebooks", "vaqhip_fit_codebooks_set_timing", "vaqhip_last_fit_codebooks_timing",
 ]
 MAX_DEVICES = 16
 
@@ -100,6 +102,12 @@ class LutFitTiming(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("project_ms", C.c_float), ("extract_ms", C.c_float),
                 ("sort_ms", C.c_float), ("quantile_ms", C.c_float), ("means_ms", C.c_float),
                 ("rows", C.c_int64), ("dims", C.c_int)]
+
+
+class FitCodebooksTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("gather_ms", C.c_float), ("assign_ms", C.c_float),
+                ("accumulate_ms", C.c_float), ("update_ms", C.c_float), ("iterations", C.c_int),
+                ("subspaces", C.c_int), ("dims", C.c_int), ("sample_rows", C.c_int64), ("rows", C.c_int64)]
 
 
 class LearnTiming(C.Structure):
@@ -212,6 +220,13 @@ def load():
     L.vaqhip_lut_fit_set_timing.argtypes = [i32]
     L.vaqhip_last_lut_fit_timing.argtypes = [C.POINTER(LutFitTiming)]
     L.vaqhip_index_set_lut_quantiles.argtypes = [vp, vp]
+    for name in ("vaqhip_fit_codebooks", "vaqhip_fit_codebooks_u8"):
+        getattr(L, name).argtypes = [i32, vp, i64, i32, i32, C.POINTER(i32), vp, i32, vp, vp, vp]
+    for name in ("vaqhip_fit_codebooks_device", "vaqhip_fit_codebooks_u8_device"):
+        getattr(L, name).argtypes = [i32, vp, i64, i32, i32, C.POINTER(i32), vp, i32, vp, vp, vp, vp]
+    L.vaqhip_refiner_fit_codebooks.argtypes = [vp, i32, C.POINTER(i32), vp, i32, vp, vp, vp]
+    L.vaqhip_fit_codebooks_set_timing.argtypes = [i32]
+    L.vaqhip_last_fit_codebooks_timing.argtypes = [C.POINTER(FitCodebooksTiming)]
     L.vaqhip_encode_lut.argtypes = [vp, vp, i64, i32, vp]
     L.vaqhip_encode_lut_device.argtypes = [vp, vp, i64, i32, vp, vp]
     L.vaqhip_refine.argtypes = [i32, vp, i32, i32, vp, i64, vp, i32, i32, vp, vp]

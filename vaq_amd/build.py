@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vaq_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "vaq_amd", "lib")
 LIB = os.path.join(LIBDIR, "libvaqhip.so")
-SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_fast.hip", "vaq_lutfit.hip", "vaq_learn.hip", "vaq_refine.hip", "vaq_exhaust.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp", "vaqhip_learn.cpp", "vaqhip_lutfit.cpp", "vaqhip_refiner.cpp",
+SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_codebooks.hip", "vaq_fast.hip", "vaq_lutfit.hip", "vaq_learn.hip", "vaq_refine.hip", "vaq_exhaust.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp", "vaqhip_learn.cpp", "vaqhip_lutfit.cpp", "vaqhip_codebooks.cpp", "vaqhip_refiner.cpp",
            "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp", "vaqhip_multi_encode.cpp", "vaqhip_multi_lutfit.cpp", "vaqhip_multi_learn.cpp", "vaqhip_rccl.cpp"]
 MULTI_REFINER_SOURCES = ("vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp")
 MULTI_ENCODE_SOURCE = "vaqhip_multi_encode.cpp"  # reads the multi refiner's resident rows: its headers too
@@ -46,6 +46,7 @@ LUTFIT_DEV_HEADER = os.path.join(CSRC, "vaq_lutfit_dev.h")  # the column fit's t
 LUTFIT_PLAN_HEADER = os.path.join(CSRC, "lutfit_multi_plan.h")  # owners, rounds, offsets of the sharded fit (no HIP)
 LEARN_PLAN_HEADER = os.path.join(CSRC, "learn_plan.h")  # learnQuantization's host arithmetic: both forms, the loss kernel (no HIP)
 LEARN_HEADER = os.path.join(CSRC, "vaq_learn.h")  # the kernels of learnQuantization's device forms
+CODEBOOKS_PLAN_HEADER = os.path.join(CSRC, "fit_codebooks_plan.h")  # samples, offsets, key width of the codebook fit (no HIP)
 
 
 def _deps(src: str):
@@ -56,8 +57,10 @@ def _deps(src: str):
     if src.endswith(".cpp"):
         deps += [API_HEADER, INTERNAL_HEADER, DEV_HEADER]
         deps += [MULTI_HEADER, JOB_POOL_HEADER, RCCL_HEADER] if src in MULTI_SOURCES else [INDEX_HEADER]
-    if src in ("vaq_kernels.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_lutfit.hip"):
+    if src in ("vaq_kernels.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_lutfit.hip", "vaq_codebooks.hip"):
         deps.append(DEV_HEADER)
+    if src in ("vaq_codebooks.hip", "vaqhip_codebooks.cpp"):
+        deps += [CODEBOOKS_PLAN_HEADER, KMEANS_SAMPLE_HEADER]
     if src in ("vaq_lutfit.hip", "vaqhip_lutfit.cpp", MULTI_LUTFIT_SOURCE, "vaq_learn.hip"):
         deps.append(LUTFIT_HEADER)
     if src in ("vaq_learn.hip", "vaqhip_learn.cpp", "vaqhip_fast.cpp"):
@@ -76,7 +79,7 @@ def _deps(src: str):
         deps.append(SCAN_BF_HEADER)
     if src in ("vaq_fast.hip", "vaqhip_fast.cpp"):
         deps.append(FAST_HEADER)
-    if src in ("vaq_fast.hip", "vaqhip_fast.cpp", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_refine.hip", "vaq_exhaust.hip"):
+    if src in ("vaq_fast.hip", "vaqhip_fast.cpp", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_codebooks.hip", "vaq_refine.hip", "vaq_exhaust.hip"):
         deps.append(RESTATED_HEADER)
     if src in ("vaq_refine.hip", "vaq_exhaust.hip"):
         deps.append(REFINE_GROUP_HEADER)

@@ -1,0 +1,315 @@
+// vaq_codebooks.hip -- the subspace codebooks mCentroidsPerSubs on gfx950: KMeans::staticFitSampling (KMeans.hpp:487-616)
+// as VAQ.cpp:644-649 calls it, once per subspace on XTrain.block(0, s * L, n, L), for ALL subspaces in one launch per
+// phase and iteration.  The arithmetic is vaq_kmeans.hip's (the same reference function), statement for statement:
+//   assign      sqrt((x - mean).squaredNorm()) in Eigen's summation order over the L floats of the slice
+//               (sq_norm_eigen, vaq_restated.h), centres ascending, strict `<`
+//   accumulate  per (half, centre, column) a float sum from +0 in ascending row order: a stable sort of the rows by
+//               run_off[s] + half * k_s + centre and one thread per (run, column) walking its run
+//   update      new = ((0 + p0) + p1) / float(count); a centre whose new row is not elementwise == the old one is
+//               replaced (an empty cluster: 0 / 0 = NaN, unequal for ever)
+// Batching cannot change a bit: no value of subspace s is computed from another subspace's -- the slices are
+// disjoint columns of the projected sample, the keys of s lie in its own range [run_off, run_off + 2 k_s), its pairs
+// enter the sort in ascending row order and the sort is stable, so every run is the run the single fit would walk.
+// A subspace whose centres stopped changing is a fixed point: its assign step is skipped (its pairs are still there
+// from the iteration before), the rest recomputes the same centres.
+// No float atomics, no MFMA, no reassociation; compiled with -ffp-contract=off like every file of the library.
+#include "fit_codebooks_plan.h"
+#include "kmeans_sample.h"
+#include "vaq_kernels.h"
+#include "vaq_restated.h"
+#include "vaqhip_dev.h"
+
+#include <chrono>
+#include <vector>
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include <float.h>
+#include <math.h>
+
+namespace vaq {
+
+namespace {
+// floats of centres a workgroup of the assign kernel stages in LDS at a time
+constexpr int CB_STAGE_FLOATS = 4096;
+// bytes of LDS its tile of slices may take; wider slices are read from global memory
+constexpr int CB_TILE_BYTES = 40 * 1024;
+}  // namespace
+
+// out[i][j] = (float)X[rows[i]][j]: the sample in the reference's order, a byte widened where it is loaded
+template <typename T>
+__global__ void cb_gather_kernel(const T *__restrict__ X, int D, const int *__restrict__ rows, int64_t S,
+                                 float *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= S * D) return;
+  const int64_t r = i / D;
+  out[i] = (float)X[(int64_t)rows[r] * D + (i - r * D)];
+}
+
+// means[c] = slice s of sample row seed_rows[c] (KMeans.hpp:516-520); grid.y = subspace
+__global__ void cb_seed_kernel(const float *__restrict__ P, int D, int L, const cbfit::Sub *__restrict__ subs,
+                               const int *__restrict__ seed_rows, float *__restrict__ means) {
+  const int s = blockIdx.y;
+  const cbfit::Sub sd = subs[s];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= sd.k * L) return;
+  const int c = i / L, j = i % L;
+  means[(size_t)(sd.cent_off + c) * L + j] = P[(size_t)seed_rows[sd.cent_off + c] * D + (size_t)s * L + j];
+}
+
+// One row per thread, grid = (row tile, subspace).  X_LDS: the workgroup's slices sit in LDS as [column][row] (each
+// thread reads its own column, conflict-free); else every thread reads its slice from global memory.  The
+// subspace's centres pass through LDS `stage` at a time and are read with wave-uniform addresses (broadcast).
+// Row r of subspace s: keys[pair_off + r] = run_off + half * k + centre, vals[pair_off + r] = r.
+template <bool X_LDS>
+__global__ void cb_assign_kernel(const float *__restrict__ P, int D, int L, const cbfit::Sub *__restrict__ subs,
+                                 const float *__restrict__ means, int stage, const int *__restrict__ active,
+                                 unsigned *__restrict__ keys, unsigned *__restrict__ vals, int *__restrict__ no_centre) {
+  extern __shared__ float cb_lds[];
+  const int s = blockIdx.y;
+  const cbfit::Sub sd = subs[s];
+  const int R = blockDim.x, tid = threadIdx.x;
+  const int64_t r0 = (int64_t)blockIdx.x * R;
+  if (r0 >= sd.rows || !active[s]) return;  // (the whole workgroup)
+  float *cs = cb_lds;                        // [stage][L]
+  float *xt = cb_lds + (size_t)stage * L;    // [L][R]
+  const int64_t r = r0 + tid;
+  const int64_t rr = r < sd.rows ? r : sd.rows - 1;  // (rows past the end work on the last row and store nothing)
+  const float *slice0 = P + (size_t)s * L;
+  if (X_LDS) {
+    for (int i = tid; i < R * L; i += R) {
+      const int row = i / L, col = i % L;
+      xt[(size_t)col * R + row] = r0 + row < sd.rows ? slice0[(size_t)(r0 + row) * D + col] : 0.0f;
+    }
+  }
+  const float *m = means + (size_t)sd.cent_off * L;
+  float best = FLT_MAX;
+  int idx = -1;
+  for (int c0 = 0; c0 < sd.k; c0 += stage) {
+    const int cn = min(stage, sd.k - c0);
+    __syncthreads();  // the last stage is read, the tile is written
+    for (int i = tid; i < cn * L; i += R) cs[i] = m[(size_t)c0 * L + i];
+    __syncthreads();
+    for (int c = 0; c < cn; c++) {
+      const float d2 = X_LDS ? sq_norm_eigen<false>(xt + tid, R, cs + (size_t)c * L, L)
+                             : sq_norm_eigen<true>(slice0 + (size_t)rr * D, 1, cs + (size_t)c * L, L);
+      const float dist = sqrtf(d2);
+      if (dist < best) {
+        best = dist;
+        idx = c0 + c;
+      }
+    }
+  }
+  if (r < sd.rows) {
+    if (idx < 0) no_centre[s] = 1;  // the reference indexes row -1 here
+    keys[sd.pair_off + r] = (unsigned)(sd.run_off + (r >= sd.half ? sd.k : 0) + max(idx, 0));
+    vals[sd.pair_off + r] = (unsigned)r;
+  }
+}
+
+// run [start, end) of every key in the sorted keys (both preset to 0: keys that do not occur are empty)
+__global__ void cb_bounds_kernel(const unsigned *__restrict__ keys, int n, int *__restrict__ start,
+                                 int *__restrict__ end) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const unsigned k = keys[i];
+  if (i == 0 || keys[i - 1] != k) start[k] = i;
+  if (i == n - 1 || keys[i + 1] != k) end[k] = i + 1;
+}
+
+// part[run * L + col] = the rows of that run added from +0 in ascending row order; grid.y = subspace, neighbouring
+// threads take neighbouring columns of the same run
+__global__ void cb_accumulate_kernel(const float *__restrict__ P, int D, int L, const cbfit::Sub *__restrict__ subs,
+                                     const unsigned *__restrict__ rows_sorted, const int *__restrict__ start,
+                                     const int *__restrict__ end, float *__restrict__ part) {
+  const int s = blockIdx.y;
+  const cbfit::Sub sd = subs[s];
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 2 * sd.k * L) return;
+  const int g = sd.run_off + t / L, col = t % L;
+  const float *x = P + (size_t)s * L + col;
+  float sum = 0.0f;
+  for (int i = start[g], e = end[g]; i < e; i++) sum += x[(size_t)rows_sorted[i] * D];
+  part[(size_t)g * L + col] = sum;
+}
+
+// one wavefront per (centre, subspace) (KMeans.hpp:586-604); changed[s] is set when a centre of s was replaced
+__global__ __launch_bounds__(64) void cb_update_kernel(const float *__restrict__ part, const int *__restrict__ start,
+                                                      const int *__restrict__ end, int L,
+                                                      const cbfit::Sub *__restrict__ subs, float *__restrict__ means,
+                                                      int *__restrict__ changed) {
+  const int s = blockIdx.y;
+  const cbfit::Sub sd = subs[s];
+  const int c = blockIdx.x, lane = threadIdx.x;
+  if (c >= sd.k) return;
+  const int g0 = sd.run_off + c, g1 = g0 + sd.k;
+  const int count = (end[g0] - start[g0]) + (end[g1] - start[g1]);
+  const float *p0 = part + (size_t)g0 * L, *p1 = part + (size_t)g1 * L;
+  float *m = means + (size_t)(sd.cent_off + c) * L;
+  bool differs = false;
+  for (int j = lane; j < L; j += 64) {
+    const float v = ((0.0f + p0[j]) + p1[j]) / (float)count;
+    if (!(v == m[j])) differs = true;
+  }
+  if (!__any(differs)) return;
+  for (int j = lane; j < L; j += 64) m[j] = ((0.0f + p0[j]) + p1[j]) / (float)count;
+  if (lane == 0) changed[s] = 1;
+}
+
+namespace {
+double cb_ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+}  // namespace
+
+hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan &plan, const float *d_eig,
+                         int max_iter, float *d_means, int *iters_out, int *no_centre_out, CodebookPhases *phases,
+                         hipStream_t st) {
+  const int M = (int)plan.sub.size();
+  const int64_t S = plan.sample;
+  if (M < 1 || S < 1 || plan.n_pairs > 0x7fffffff) return hipErrorInvalidValue;
+  const int n_pairs = (int)plan.n_pairs, n_runs = plan.n_runs;
+  hipError_t e;
+#define CB_TRY(expr)                          \
+  do {                                        \
+    if ((e = (expr)) != hipSuccess) return e; \
+  } while (0)
+  // (freed on return, after the stream is synchronised)
+  struct Sync {
+    hipStream_t st;
+    ~Sync() { (void)hipStreamSynchronize(st); }
+  };
+  vaqhost::DevBuf b_rows, b_gather, b_proj, b_sub, b_seed, b_keys_in, b_keys_out, b_vals_in, b_vals_out, b_bounds, b_part,
+      b_flags, b_temp;
+  Sync sync_on_return{st};
+  if (phases) *phases = CodebookPhases{};
+  auto t0 = std::chrono::steady_clock::now();
+
+  // ---- the sample, gathered and projected once: every subspace works on a prefix of it ----
+  RowsRef src = d_X;
+  if (plan.sampled) {
+    const std::vector<int> rows = permutation_head(n, S);
+    CB_TRY(b_rows.ensure((size_t)S * sizeof(int)));
+    CB_TRY(b_gather.ensure((size_t)S * D * sizeof(float)));
+    CB_TRY(hipMemcpyAsync(b_rows.p, rows.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, st));
+    const unsigned grid = (unsigned)((S * D + 255) / 256);
+    if (d_X.elem == 1)
+      hipLaunchKernelGGL(cb_gather_kernel<uint8_t>, dim3(grid), dim3(256), 0, st, static_cast<const uint8_t *>(d_X.p), D,
+                         b_rows.as<int>(), S, b_gather.as<float>());
+    else
+      hipLaunchKernelGGL(cb_gather_kernel<float>, dim3(grid), dim3(256), 0, st, static_cast<const float *>(d_X.p), D,
+                         b_rows.as<int>(), S, b_gather.as<float>());
+    CB_TRY(hipGetLastError());
+    CB_TRY(hipStreamSynchronize(st));  // (rows is the host's)
+    src = RowsRef{b_gather.p, 4};
+  }
+  const float *P = static_cast<const float *>(src.p);
+  if (d_eig) {  // unchecked, as VAQ::train projects the training rows
+    CB_TRY(b_proj.ensure((size_t)S * D * sizeof(float)));
+    CB_TRY(launch_project(src, S, D, d_eig, b_proj.as<float>(), st, 0));
+    P = b_proj.as<float>();
+  } else if (src.elem == 1) {
+    CB_TRY(b_proj.ensure((size_t)S * D * sizeof(float)));
+    CB_TRY(launch_widen_rows_u8(static_cast<const uint8_t *>(src.p), S * D, b_proj.as<float>(), st));
+    P = b_proj.as<float>();
+  }
+
+  // ---- the batch's tables and the seeds ----
+  std::vector<int> seeds((size_t)plan.n_cent);
+  for (int s = 0; s < M; s++) {
+    const cbfit::Sub &sd = plan.sub[(size_t)s];
+    const std::vector<int> head = permutation_head(sd.rows, sd.k);
+    std::copy(head.begin(), head.end(), seeds.begin() + sd.cent_off);
+  }
+  CB_TRY(b_sub.ensure((size_t)M * sizeof(cbfit::Sub)));
+  CB_TRY(b_seed.ensure(seeds.size() * sizeof(int)));
+  CB_TRY(b_keys_in.ensure((size_t)n_pairs * 4));
+  CB_TRY(b_keys_out.ensure((size_t)n_pairs * 4));
+  CB_TRY(b_vals_in.ensure((size_t)n_pairs * 4));
+  CB_TRY(b_vals_out.ensure((size_t)n_pairs * 4));
+  CB_TRY(b_bounds.ensure((size_t)2 * n_runs * sizeof(int)));
+  CB_TRY(b_part.ensure((size_t)n_runs * L * sizeof(float)));
+  CB_TRY(b_flags.ensure((size_t)3 * M * sizeof(int)));
+  const cbfit::Sub *subs = b_sub.as<cbfit::Sub>();
+  unsigned *keys_in = b_keys_in.as<unsigned>(), *keys_out = b_keys_out.as<unsigned>();
+  unsigned *vals_in = b_vals_in.as<unsigned>(), *vals_out = b_vals_out.as<unsigned>();
+  int *start = b_bounds.as<int>(), *end = start + n_runs;
+  int *flags = b_flags.as<int>();  // changed[2][M] (this iteration's and the one before), then no_centre[M]
+  size_t temp_bytes = 0;
+  CB_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n_pairs, 0u,
+                                   plan.key_bits, st));
+  CB_TRY(b_temp.ensure(temp_bytes ? temp_bytes : 16));
+  std::vector<int> host_flags((size_t)3 * M, 0);
+  for (int s = 0; s < M; s++) host_flags[(size_t)s] = 1;  // every subspace starts active
+  CB_TRY(hipMemcpyAsync(b_sub.p, plan.sub.data(), (size_t)M * sizeof(cbfit::Sub), hipMemcpyHostToDevice, st));
+  CB_TRY(hipMemcpyAsync(b_seed.p, seeds.data(), seeds.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  CB_TRY(hipMemcpyAsync(flags, host_flags.data(), host_flags.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(cb_seed_kernel, dim3((unsigned)((plan.k_max * L + 255) / 256), (unsigned)M), dim3(256), 0, st, P, D,
+                     L, subs, b_seed.as<int>(), d_means);
+  CB_TRY(hipGetLastError());
+  CB_TRY(hipStreamSynchronize(st));  // (the tables are the host's)
+  if (phases) phases->gather_ms = cb_ms_since(t0);
+
+  // launch shape of the assign kernel: the widest workgroup whose tile of slices fits
+  int R = 256;
+  while (R > 64 && (size_t)R * L * sizeof(float) > CB_TILE_BYTES) R >>= 1;
+  const bool x_lds = (size_t)R * L * sizeof(float) <= CB_TILE_BYTES;
+  const int stage = std::max(1, std::min(plan.k_max, CB_STAGE_FLOATS / L));
+  const size_t lds = ((size_t)stage * L + (x_lds ? (size_t)R * L : 0)) * sizeof(float);
+  const dim3 assign_grid((unsigned)((S + R - 1) / R), (unsigned)M);
+  const dim3 acc_grid((unsigned)((2 * (int64_t)plan.k_max * L + 255) / 256), (unsigned)M);
+
+  auto phase_end = [&](double *acc) -> hipError_t {
+    if (!phases) return hipSuccess;
+    const hipError_t pe = hipStreamSynchronize(st);
+    *acc += cb_ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    return pe;
+  };
+  std::vector<char> done((size_t)M, 0);
+  for (int s = 0; s < M; s++) iters_out[s] = 0;
+  int no_centre = 0, n_done = 0;
+  t0 = std::chrono::steady_clock::now();
+  for (int it = 0; it < max_iter && n_done < M && !no_centre; it++) {
+    int *prev = flags + (size_t)(it & 1) * M, *now = flags + (size_t)((it + 1) & 1) * M;
+    CB_TRY(hipMemsetAsync(now, 0, (size_t)M * sizeof(int), st));
+    CB_TRY(hipMemsetAsync(start, 0, (size_t)2 * n_runs * sizeof(int), st));
+    if (x_lds)
+      hipLaunchKernelGGL(cb_assign_kernel<true>, assign_grid, dim3(R), lds, st, P, D, L, subs, d_means, stage, prev,
+                         keys_in, vals_in, flags + 2 * M);
+    else
+      hipLaunchKernelGGL(cb_assign_kernel<false>, assign_grid, dim3(R), lds, st, P, D, L, subs, d_means, stage, prev,
+                         keys_in, vals_in, flags + 2 * M);
+    CB_TRY(hipGetLastError());
+    CB_TRY(phase_end(phases ? &phases->assign_ms : nullptr));
+    // stable: rows of equal (subspace, half, centre) stay in ascending order
+    CB_TRY(rocprim::radix_sort_pairs(b_temp.p, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n_pairs, 0u,
+                                     plan.key_bits, st));
+    hipLaunchKernelGGL(cb_bounds_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, keys_out, n_pairs,
+                       start, end);
+    CB_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cb_accumulate_kernel, acc_grid, dim3(256), 0, st, P, D, L, subs, vals_out, start, end,
+                       b_part.as<float>());
+    CB_TRY(hipGetLastError());
+    CB_TRY(phase_end(phases ? &phases->accumulate_ms : nullptr));
+    hipLaunchKernelGGL(cb_update_kernel, dim3((unsigned)plan.k_max, (unsigned)M), dim3(64), 0, st, b_part.as<float>(),
+                       start, end, L, subs, d_means, now);
+    CB_TRY(hipGetLastError());
+    CB_TRY(hipMemcpyAsync(host_flags.data(), flags, host_flags.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    CB_TRY(hipStreamSynchronize(st));
+    CB_TRY(phase_end(phases ? &phases->update_ms : nullptr));
+    for (int s = 0; s < M; s++) {
+      no_centre |= host_flags[(size_t)2 * M + s];
+      if (done[(size_t)s]) continue;
+      iters_out[s] = it + 1;  // the reference's iter_count: the iteration that changes nothing is counted
+      if (!host_flags[(size_t)((it + 1) & 1) * M + s]) {
+        done[(size_t)s] = 1;
+        n_done++;
+      }
+    }
+  }
+#undef CB_TRY
+  *no_centre_out = no_centre;
+  return hipStreamSynchronize(st);
+}
+
+}  // namespace vaq

@@ -510,5 +510,26 @@ hipError_t kmeans_fit(const KmeansDev *devs, int G, const uint16_t *d_scodes, in
                       const int *seed_rows, int T, int max_iter, float *d_means, int *iters_out, int *no_centre_out,
                       KmeansPhases *phases, int *failed_dev);
 
+// ---- the subspace codebooks (vaq_codebooks.hip): staticFitSampling per subspace, all subspaces per launch ----
+namespace cbfit {
+struct Plan;  // fit_codebooks_plan.h
+}
+// host time per phase over all iterations, each phase ended by a stream synchronisation
+struct CodebookPhases {
+  double gather_ms = 0, assign_ms = 0, accumulate_ms = 0, update_ms = 0;
+};
+// d_X: n x D device rows of either type (any byte address for byte rows), the device current.  The rows of the
+// largest sample are gathered (n > plan.sample: permutation_head(n, plan.sample), else all in order), widened and
+// projected by launch_project's chain (d_eig null: taken as they are); subspace s = columns [s * L, (s + 1) * L)
+// of the first plan.sub[s].rows of them, seeded from permutation_head(rows, k), then Lloyd iterations until its
+// centres stop changing or max_iter.  d_means: the M matrices back to back (plan.n_cent x L floats, device).
+// iters_out[M] (host): the reference's iter_count per subspace.  *no_centre_out != 0: some row had no centre at a
+// distance below FLT_MAX (the reference indexes row -1 there); the centres are then not to be used.  phases
+// (optional) adds one synchronisation per phase.  Synchronises the stream; plan.n_pairs must be below 2^31 (it is
+// for every M and bits the library accepts).
+hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan &plan, const float *d_eig,
+                         int max_iter, float *d_means, int *iters_out, int *no_centre_out, CodebookPhases *phases,
+                         hipStream_t st);
+
 } // namespace vaq
 #endif

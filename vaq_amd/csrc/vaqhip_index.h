@@ -175,6 +175,10 @@ int set_quantization_locked(vaqhip_index *ix, const float *off, const float *sca
 // rows (n x D on the index's device, complete); takes the index's lock itself
 int learn_rows_device(vaqhip_index *ix, vaq::RowsRef d_X, int64_t n, int projected, float ratio, float *offsets_out,
                       float *scale_out);
+// vaqhip_codebooks.cpp: vaqhip_fit_codebooks[_u8]'s body from the upload on, which vaqhip_refiner.cpp calls over its
+// resident rows (n x D on `device`, complete); eigvec and the outputs are the host's
+int fit_codebooks_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits, const float *eigvec,
+                              int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out);
 
 // The preamble of an entry point: the index's lock, then its device current (put back when the scope ends).
 // rc: VAQHIP_OK, or what the entry returns at once -- ENTRY(ix) declares it and does so, as HIP_TRY would.

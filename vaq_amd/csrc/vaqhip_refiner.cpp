@@ -308,4 +308,16 @@ int vaqhip_learn_quantization_from_refiner(vaqhip_index *ix, vaqhip_refiner *r, 
   return learn_rows_device(ix, r->rows.rows(), r->N, 0, sample_ratio, offsets_out, scale_out);
 }
 
+// the subspace codebooks over the resident rows, read in place (vaqhip_codebooks.cpp does the rest; the refiner's lock
+// keeps the rows where they are meanwhile)
+int vaqhip_refiner_fit_codebooks(vaqhip_refiner *r, int M, const int *bits, const float *eigvec, int max_iter,
+                                 float *centroids_out, int *iters_out, int *nan_rows_out) {
+  if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
+  std::lock_guard<std::mutex> lk(r->mu);
+  if (r->N == 0) return fail(VAQHIP_ESTATE, "the refiner holds no rows: vaqhip_refiner_set_rows first");
+  // (set_rows and add_rows copy synchronously: the rows are complete)
+  return fit_codebooks_rows_device(r->device, r->rows.rows(), r->N, r->D, M, bits, eigvec, max_iter, centroids_out,
+                                   iters_out, nan_rows_out);
+}
+
 }  // extern "C"

@@ -741,6 +741,11 @@ class VaqRefiner:
         """Bytes per element of the rows held: 4 (float32) or 1 (uint8)."""
         return _lib.check(_lib.load().vaqhip_refiner_elem_size(self._h))
 
+    def fit_codebooks(self, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25):
+        """fit_codebooks() over the rows held, float or byte, read where they are (vaqhip_refiner_fit_codebooks)."""
+        return _fit_codebooks_call(self.D, M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn: L.vaqhip_refiner_fit_codebooks(
+            self._h, int(M), b, e, it, c, i, nn))
+
     @property
     def exact_ties(self) -> bool:
         return self._exact
@@ -1009,6 +1014,61 @@ class VaqMultiRefiner:
             self.close()
         except Exception:
             pass
+
+
+def _fit_codebooks_call(D: int, M: int, bits, eigvec, max_iter: int, call):
+    """The arrays around a vaqhip_*fit_codebooks call: ([M centre matrices k_s x L], iterations[M], nan_rows[M])."""
+    bits = [int(b) for b in bits]
+    M = int(M)
+    if M < 1 or len(bits) != M or D % M != 0:
+        raise _lib.VaqHipError(-1, f"{len(bits)} bits for M = {M} subspaces of D = {D}")
+    eig = None
+    if eigvec is not None:
+        eig = np.ascontiguousarray(np.real(eigvec), dtype=np.float32)
+        if eig.shape != (D, D):
+            raise _lib.VaqHipError(-1, f"eigvec {eig.shape} is not {D}x{D}")
+    L_ = D // M
+    ks = [1 << b if 0 < b < 31 else 0 for b in bits]  # (bits out of range: the call refuses them, nothing is written)
+    cent = np.empty(max(sum(ks) * L_, 1), np.float32)
+    iters = np.zeros(M, np.int32)
+    nan_rows = np.zeros(M, np.int32)
+    _lib.check(call(_lib.load(), (C.c_int * M)(*bits), _ptr(eig) if eig is not None else None, int(max_iter), _ptr(cent),
+                    _ptr(iters), _ptr(nan_rows)))
+    offs = np.concatenate([[0], np.cumsum(ks)]) * L_
+    return [cent[offs[s]:offs[s + 1]].reshape(ks[s], L_).copy() for s in range(M)], iters, nan_rows
+
+
+def fit_codebooks(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25, device: int = 0):
+    """vaqhip_fit_codebooks: the subspace codebooks mCentroidsPerSubs by KMeans::staticFitSampling (the call of
+    VAQ.cpp:644-649; not the arma::kmeans call VAQ::train runs today), every subspace fitted on the device, bit for
+    bit the reference's.  X: n x D rows (unprojected when eigvec is given, else in PCA space); bits[M].  Returns
+    ([M arrays (1 << bits[s]) x L], iterations[M], nan_rows[M])."""
+    X = np.ascontiguousarray(X, dtype=np.float32)
+    if X.ndim != 2:
+        raise _lib.VaqHipError(-1, f"X {X.shape} is not n x D")
+    return _fit_codebooks_call(X.shape[1], M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn: L.vaqhip_fit_codebooks(
+        int(device), _ptr(X), X.shape[0], X.shape[1], int(M), b, e, it, c, i, nn))
+
+
+def fit_codebooks_u8(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25, device: int = 0):
+    """fit_codebooks from byte rows (vaqhip_fit_codebooks_u8): the result is fit_codebooks's on X.astype(float32), bit
+    for bit.  Anything but a contiguous uint8 n x D array is EINVAL."""
+    X = np.asarray(X)
+    X = _u8_rows(X, X.shape[1] if X.ndim == 2 else 0)
+    return _fit_codebooks_call(X.shape[1], M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn: L.vaqhip_fit_codebooks_u8(
+        int(device), _ptr(X), X.shape[0], X.shape[1], int(M), b, e, it, c, i, nn))
+
+
+def fit_codebooks_timing(on: bool) -> None:
+    """Phase times for the calling thread's fits (vaqhip_fit_codebooks_set_timing): one synchronisation per phase."""
+    _lib.check(_lib.load().vaqhip_fit_codebooks_set_timing(1 if on else 0))
+
+
+def last_fit_codebooks_timing() -> dict:
+    """Figures of the calling thread's last codebook fit (vaqhip_last_fit_codebooks_timing)."""
+    t = _lib.FitCodebooksTiming()
+    _lib.check(_lib.load().vaqhip_last_fit_codebooks_timing(C.byref(t)))
+    return {f: getattr(t, f) for f, _ in _lib.FitCodebooksTiming._fields_}
 
 
 def _fit_quantiles_call(D: int, bits, eigvec, call):
