@@ -399,11 +399,16 @@ int vaqhip_encode_lut_u8_device(vaqhip_index *ix, const uint8_t *d_X, int64_t n,
  * fit, vaqhip_index_create with the centres, vaqhip_encode.
  *   X              n x D row-major; in PCA space when eigvec is NULL, else X * eigvec by vaqhip_project's chain, unchecked
  *   M, bits[M]     M subspaces of L = D / M columns, k_s = 1 << bits[s] centres, 1 <= bits[s] <= VAQHIP_MAX_BITS
- *   sample         a fit of k centres works on rows_s = min(n, max(256 * k, 65536)) rows: all rows in order, or the
- *                  first rows_s of randomPermutation(n) (mt19937(13517106)).  The head of the permutation for a smaller
- *                  sample is a prefix of the head for a larger one, so ONE sample (the largest) is gathered and
- *                  projected and every subspace works on its prefix; rows outside it are never read.
- *   seeds          means[i] = sample row randomPermutation(rows_s)[i]
+ *   sample         decided PER SUBSPACE, as every call of the reference decides for itself (KMeans.hpp:489-503): with
+ *                  size_s = max(256 * k_s, 65536), subspace s works on all n rows in their own order when n <= size_s,
+ *                  else on rows randomPermutation(n)[0 .. size_s) (mt19937(13517106)) in that order; rows_s =
+ *                  min(n, size_s).  One batch may hold both kinds (65536 < n <= 256 * k_max with a smaller k_s beside
+ *                  it): a subspace that samples never works on rows 0 .. rows_s-1 in order.  The head of the permutation
+ *                  for a smaller sample is a prefix of the head for a larger one, so one sample -- the largest among the
+ *                  subspaces that sample -- is gathered and each of them works on its prefix; the subspaces that do
+ *                  not sample read the full matrix, projected or widened whole where eigvec or byte rows require it
+ *                  (the sample is then gathered from the projected matrix: a row's projection is its own).
+ *   seeds          means[i] = row randomPermutation(rows_s)[i] of the subspace's rows_s rows
  *   Lloyd          until no centre of the subspace changes or max_iter (the reference passes 25): assign by
  *                  sqrt((x - mean).squaredNorm()) in Eigen's summation order over the L floats (plain sequential for
  *                  L < 8), centres ascending, strict <; sums in the order of the reference's two OpenMP threads (rows
@@ -421,7 +426,9 @@ int vaqhip_encode_lut_u8_device(vaqhip_index *ix, const uint8_t *d_X, int64_t n,
  * and D > 4096.  Known only after the run: VAQHIP_EINVAL when a row is
  * at a distance >= FLT_MAX or NaN from every centre (the reference indexes row -1); VAQHIP_ENOMEM from a failed
  * allocation (nothing is kept).  Workspace: the projected sample (sample x D floats, twice with a gathered sample and
- * eigvec) and 16 bytes per (subspace, sampled row).  The host forms upload only the sample; the _device forms take
+ * eigvec), n x D floats more when a subspace reads all rows and they are bytes or rotated, and 16 bytes per
+ * (subspace, row it works on).  The host forms upload only the sample when every subspace samples, else all rows; the
+ * _device forms take
  * device pointers for X, eigvec and centroids_out (bits and the two small outputs stay host arrays), work on
  * `stream` and synchronise it before they return.  The _u8 forms: the float call's result on the widened matrix, bit
  * for bit (see vaqhip_encode_u8; any byte address in the _device form). */
@@ -443,7 +450,7 @@ typedef struct {
   float assign_ms, accumulate_ms, update_ms;  /*   summed over the iterations; accumulate = sort + run bounds + sums */
   int iterations;                          /* the largest iteration count of a subspace */
   int subspaces, dims;
-  int64_t sample_rows;                     /* rows gathered and projected */
+  int64_t sample_rows;                     /* the most rows a subspace worked on: max rows_s (n when one read all rows) */
   int64_t rows;
 } vaqhip_fit_codebooks_timing;
 int vaqhip_fit_codebooks_set_timing(int on);                             /* per calling thread */

@@ -1,6 +1,6 @@
 """The subspace codebook fit on the CPU: tests/codebooks_ref.py (per subspace tests/kmeans_ref.py's restatement of
-KMeans::staticFitSampling on the sample prefix) against the fixtures recorded from the reference itself
-(tests/golden/codebooks/README.md); the symbols; every refusal made before a device is touched; and the host arithmetic
+KMeans::staticFitSampling on the rows that call takes: all of them in order, or its prefix of the sample) against
+the fixtures recorded from the reference itself (tests/golden/codebooks/README.md); the symbols; every refusal made before a device is touched; and the host arithmetic
 of vaq_amd/csrc/fit_codebooks_plan.h through its stand-alone program (tests/cpp/fit_codebooks_plan_test.cpp, once more
 under AddressSanitizer + UBSan: host code only, its own main)."""
 import ctypes as C
@@ -30,7 +30,7 @@ def test_inputs_are_the_recorded_ones(name):
     n, D, M, bits, kind, salt = cr.CASES[name]
     X, eig = cr.make_inputs(name)
     fx = cr.load_fixture(name)
-    assert X.shape == (n, D) and X.dtype == (np.uint8 if kind == "bytes" else np.float32)
+    assert X.shape == (n, D) and X.dtype == (np.uint8 if kind in ("bytes", "bits01") else np.float32)
     assert (eig is not None) == (kind == "rotated")
     assert tuple(int(v) for v in fx["shape"]) == (n, D, M) and tuple(int(b) for b in fx["bits"]) == bits
     assert int(fx["max_iter"]) == cr.MAX_ITER
@@ -62,7 +62,8 @@ def test_restatement_equals_the_reference(fits, name):
 
 def test_every_case_shows_what_it_names():
     """The table of the README: no run under three iterations; NaN centres run to the cap; the sampled cases show a
-    NaN subspace beside one without, `prefix` and `bytes` also a subspace that converges early beside one at the cap."""
+    NaN subspace beside one without, `prefix` and `bytes` also a subspace that converges early beside one at the cap;
+    `mixed` and the launch-shape cases the conditions their rows name."""
     fx = {n: cr.load_fixture(n) for n in CASES}
     its = {n: [int(fx[n]["iterations_%d" % s]) for s in range(cr.CASES[n][2])] for n in CASES}
     nan = {n: [int(fx[n]["nan_rows_%d" % s].sum()) for s in range(cr.CASES[n][2])] for n in CASES}
@@ -81,6 +82,67 @@ def test_every_case_shows_what_it_names():
     assert len(np.unique(cr.make_inputs("bytes")[0][:, :2], axis=0)) <= 16 < 32
     assert sum(nan["rotated"]) == 0 and cr.CASES["rotated"][2] % 4 == 0
     assert cr.CASES["wide"][1] * 4 * 64 > 40 * 1024  # a 64-row tile of such slices does not fit the LDS tile
+    # mixed: the sampling decision is each subspace's own, a sampling one before and after the one that does not
+    n, D, M, bits, kind, salt = cr.CASES["mixed"]
+    assert [cr.sampled(n, 1 << b) for b in bits] == [True, False, True]
+    assert [cr.sample_count(n, 1 << b) for b in bits] == [65536, 66000, 65536]
+    _launch_shape_cases()
+
+
+def _slices(name):
+    """(L, [per subspace the dense rows the reference's call works on]) of an unsampled case"""
+    n, D, M, bits, kind, salt = cr.CASES[name]
+    assert not any(cr.sampled(n, 1 << b) for b in bits)
+    P = cr.projected_rows(*cr.make_inputs(name))
+    return D // M, [cr.subspace_rows(P, n, D, M, bits, s) for s in range(M)]
+
+
+def _launch_shape_cases():
+    """The launch-shape rows of the README's table, from the rules of codebooks_fit restated in cr.assign_launch."""
+    # staged: two turns of the centre staging loop, the second clipped; rows on both sides of the boundary
+    n, D, M, bits, kind, salt = cr.CASES["staged"]
+    L, rows = _slices("staged")
+    k = 1 << bits[0]
+    R, x_lds, stage = cr.assign_launch(L, max(1 << b for b in bits))
+    assert (L, R, x_lds, stage) == (12, 256, True, 341) and cr.STAGE_FLOATS // L < k and k % (cr.STAGE_FLOATS // L) != 0
+    assert [min(stage, k - c0) for c0 in range(0, k, stage)] == [341, 171]
+    assert (1 << bits[1]) < stage  # the second subspace's only turn is clipped by its k
+    last = cr.assign(rows[0], cr.load_fixture("staged")["centres_0"])
+    assert (last < stage).any() and (last >= stage).any() and (last >= 0).all()
+    # dupes: an identical seed on either side of the stage boundary, a row at distance 0 from both
+    n, D, M, bits, kind, salt = cr.CASES["dupes"]
+    L, rows = _slices("dupes")
+    k = 1 << bits[0]
+    R, x_lds, stage = cr.assign_launch(L, k)
+    assert (stage, k) == (512, 1024) and len(np.unique(rows[0], axis=0)) <= 256
+    heads = cr.permutation_head(n, k)
+    seeds = rows[0][heads]
+    first = {}
+    for i in range(stage):
+        first.setdefault(seeds[i].tobytes(), i)
+    pairs = [(first[seeds[j].tobytes()], j) for j in range(stage, k) if seeds[j].tobytes() in first]
+    assert pairs
+    i, j = pairs[0]
+    assert i < stage <= j and np.array_equal(seeds[i], seeds[j]) and np.array_equal(rows[0][heads[i]], seeds[j])
+    fx = cr.load_fixture("dupes")
+    assert int(fx["iterations_0"]) == cr.MAX_ITER and int(fx["nan_rows_0"].sum()) == 773
+    # the tiers of the row tile, both sides of every boundary; a row stride that is not the slice length
+    got = []
+    for name, L in cr.TIERS.items():
+        n, D, M, bits, kind, salt = cr.CASES[name]
+        assert D // M == L and M == 2 and D != L
+        R, x_lds, stage = cr.assign_launch(L, max(1 << b for b in bits))
+        assert n % R != 0 and n > R  # ragged, more than one workgroup
+        got.append(R if x_lds else "global")
+    assert got == [256, 128, 128, 64, 64, "global"]
+    # wide_staged: the global path in two turns
+    n, D, M, bits, kind, salt = cr.CASES["wide_staged"]
+    R, x_lds, stage = cr.assign_launch(D // M, 1 << bits[0])
+    assert (R, x_lds, stage) == (64, False, 25) and (1 << bits[0]) * D > cr.STAGE_FLOATS and (1 << bits[0]) % stage == 7
+    # the odd lengths: one column; three packets (the third joins after the accumulators) and a tail of 3
+    assert cr.CASES["len1"][1] // cr.CASES["len1"][2] == 1
+    L = cr.CASES["len27"][1] // cr.CASES["len27"][2]
+    assert (L // 8, L % 8, (L // 16) * 16) == (3, 3, 16)
 
 
 def test_lloyd_lowers_the_cost_on_rotated(fits):
@@ -230,6 +292,19 @@ def test_plan_of_every_case(plan_exe, name):
         k, r, half, run_off, cent_off, pair_off = map(int, out[1 + s].split())
         assert (k, r, half) == (ks[s], rows[s], (rows[s] + 1) // 2)
         assert (run_off, cent_off, pair_off) == (2 * sum(ks[:s]), sum(ks[:s]), sum(rows[:s]))
+
+
+@pytest.mark.parametrize("name", CASES)
+def test_plan_sources_of_every_case(plan_exe, name):
+    """which source every subspace reads, and how long the gathered sample is, as the restatement has them"""
+    n, D, M, bits, kind, salt = cr.CASES[name]
+    out = _run(plan_exe, "plan", n, ",".join(map(str, bits)))
+    sample, n_full, gather = map(int, out[1 + M].split())
+    full = [int(v) for v in out[2 + M].split()]
+    want = [int(not cr.sampled(n, 1 << b)) for b in bits]
+    assert full == want and n_full == sum(want)
+    assert sample == max([cr.sample_count(n, 1 << b) for b in bits if cr.sampled(n, 1 << b)], default=0)
+    assert gather == int(sample > 0)
 
 
 def test_permutation_head_of_the_program_is_the_restatement(plan_exe):

@@ -97,28 +97,35 @@ def test_fixtures_through_the_host_form(vaqlib, name):
 
 
 def test_forms_agree_on_float_rows(vaqlib):
-    """`sampled` (the host form gathers its sample on the host, the others on the device): the _device form and the
-    refiner over float rows equal the host form."""
+    """`sampled` (the host form gathers its sample on the host, the others on the device) and `mixed` (one subspace
+    reads all rows in place, the device gathers the others' sample in every form): the _device form and the refiner
+    over float rows equal the host form."""
     import torch
     import vaq_amd
-    n, D, M, bits, kind, salt = cr.CASES["sampled"]
-    X, _ = inputs("sampled")
-    want = fitted("sampled")
-    same_fit(device_fit(vaqlib, torch.from_numpy(X).cuda(), n, D, M, bits), want, "_device")
-    r = vaq_amd.VaqRefiner(D)
-    r.set_rows(X)
-    cents, iters, nan = r.fit_codebooks(M, bits)
-    same_fit((0, cents, iters, nan), want, "refiner, float rows")
-    r.close()
+    for name in ("sampled", "mixed"):
+        n, D, M, bits, kind, salt = cr.CASES[name]
+        X, _ = inputs(name)
+        want = fitted(name)
+        same_fit(device_fit(vaqlib, torch.from_numpy(X).cuda(), n, D, M, bits), want, name + " _device")
+        r = vaq_amd.VaqRefiner(D)
+        r.set_rows(X)
+        cents, iters, nan = r.fit_codebooks(M, bits)
+        same_fit((0, cents, iters, nan), want, name + " refiner, float rows")
+        r.close()
 
 
 def test_forms_agree_on_byte_rows(vaqlib):
-    """`bytes`, and a byte matrix large enough to be sampled: _u8 and _u8_device equal the float form on the widened
-    matrix; a byte pointer at an odd offset gives the aligned result; so does the refiner over byte rows."""
+    """`bytes`, a byte matrix large enough to be sampled, one of `mixed`'s shape (values 0..255: all rows widened
+    for the subspace that does not sample, the sample gathered from them) and `dupes` (two turns of the centre staging
+    loop): _u8 and _u8_device equal the float form on the widened matrix; a byte pointer at an odd offset gives the
+    aligned result; so does the refiner over byte rows."""
     import torch
     import vaq_amd
     big = np.random.default_rng(77).integers(0, 256, size=(66001, 8), dtype=np.int64).astype(np.uint8)
-    for what, X8, M, bits in (("bytes", inputs("bytes")[0], 4, cr.CASES["bytes"][3]), ("sampled bytes", big, 2, (3, 2))):
+    n, D, M, bits, kind, salt = cr.CASES["mixed"]
+    mixed = np.random.default_rng(78).integers(0, 256, size=(n, D), dtype=np.int64).astype(np.uint8)
+    for what, X8, M, bits in (("bytes", inputs("bytes")[0], 4, cr.CASES["bytes"][3]), ("sampled bytes", big, 2, (3, 2)),
+                              ("mixed bytes", mixed, M, bits), ("dupes", inputs("dupes")[0], 1, cr.CASES["dupes"][3])):
         n, D = X8.shape
         want = host_fit(vaqlib, X8.astype(np.float32), M, bits)
         assert want[0] == 0
@@ -160,9 +167,31 @@ def test_rotation_in_front_is_the_projection(vaqlib):
     same_fit(host_fit(vaqlib, P, M, bits, None), want, "fit of the projected matrix")
 
 
-@pytest.mark.parametrize("name", ["tiny", "prefix"])
+def test_rotation_in_front_of_a_mixed_batch(vaqlib):
+    """`mixed` behind a random orthogonal eigvec (all rows are projected once and the sample is gathered from the
+    projected matrix): the fit equals the fit, with eigvec = NULL, of the matrix vaqhip_project returns."""
+    import vaq_amd
+    n, D, M, bits, kind, salt = cr.CASES["mixed"]
+    X, _ = inputs("mixed")
+    q, _ = np.linalg.qr(np.random.default_rng(79).normal(size=(D, D)))
+    eig = np.ascontiguousarray(q, np.float32)
+    v = vaq_amd.VaqHip(sequential_sum=True)  # any index of D columns projects: one 1-bit quantiser per column
+    v.mBitsAlloc = [1] * D
+    v.mCentroidsPerSubs = [np.array([[0.0], [1.0]], np.float32) for _ in range(D)]
+    v.mEigenVectors = eig
+    P = v.project(X)
+    v.close()
+    assert not np.array_equal(P, X)
+    want = host_fit(vaqlib, P, M, bits, None)
+    assert want[0] == 0, vaqlib.vaqhip_last_error()
+    same_fit(host_fit(vaqlib, X, M, bits, eig), want, "mixed, eigvec in front")
+    assert not np.array_equal(want[1][0], fitted("mixed")[1][0])
+
+
+@pytest.mark.parametrize("name", ["tiny", "prefix", "mixed"])
 def test_batching_changes_nothing(vaqlib, name):
-    """Subspace s alone (M = 1 on its column block, copied dense) equals subspace s of the batched call."""
+    """Subspace s alone (M = 1 on its column block, copied dense) equals subspace s of the batched call: the
+    reference's own calling pattern, every call sampling for itself."""
     n, D, M, bits, kind, salt = cr.CASES[name]
     X, _ = inputs(name)
     L = D // M
@@ -185,6 +214,12 @@ def test_repeatable_and_undisturbed(vaqlib):
     same_fit((0, cents, iters, nan), fitted("odd"), "vaq_amd.fit_codebooks")
     t = vaq_amd.last_fit_codebooks_timing()
     assert t["sample_rows"] == 4001 and t["iterations"] == max(fitted("odd")[2]) and t["subspaces"] == 2
+    # sample_rows: the most rows a subspace works on -- all of them as soon as one subspace does not sample
+    for name, rows in (("sampled", 65536), ("mixed", 66000)):
+        n, D, M, bits, kind, salt = cr.CASES[name]
+        same_fit(host_fit(vaqlib, inputs(name)[0], M, bits), fitted(name), name + " again")
+        t = vaq_amd.last_fit_codebooks_timing()
+        assert t["sample_rows"] == rows and t["rows"] == n and t["subspaces"] == M
 
 
 def test_max_iter_and_late_refusal_leave_outputs(vaqlib):

@@ -227,3 +227,60 @@ def test_again_and_after_add_codes():
     assert (iters, nan_rows) == (int(fx["iterations"]), int(fx["nan_rows"].sum()))
     assert not np.array_equal(out.view(np.uint32), first.view(np.uint32))
     v.close()
+
+
+# ---- the launch shapes of km_assign_kernel no fixture reaches ------------------------------------------------------
+# Its row tile halves while R * d * 4 > 40960 bytes (d <= 40: 256 rows, 41..80: 128, 81..160: 64, wider: rows read
+# from global memory) and its centres pass through LDS 4096 / d at a time.  The fixtures have d in {6, 12, 16, 20, 32,
+# 40, 64, 512}: no case in 41..63 or 81..160, none at a boundary from above, and none on the global path with more
+# than one turn of the staging loop.  name: (N, seg, L, T, centroids per subspace, subspaces of the index), as
+# kmeans_ref.CASES; the expected centres are kmeans_ref.fit_codebook's, the restatement the fixtures pin.
+TIER_CASES = {
+    "d41": (321, 1, 41, 7, 64, 4),
+    "d81": (321, 1, 81, 7, 64, 4),
+    "d160": (321, 1, 160, 7, 64, 4),
+    "d161": (321, 1, 161, 7, 64, 4),
+    "d161_t30": (333, 1, 161, 30, 64, 4),
+}
+
+
+def _launch(d, T):
+    """(rows per workgroup or "global", centres per stage) by the rules of kmeans_fit"""
+    R = 256
+    while R > 64 and R * d * 4 > 40 * 1024:
+        R >>= 1
+    return (R if R * d * 4 <= 40 * 1024 else "global"), max(1, min(T, 4096 // d))
+
+
+def test_tier_cases_land_where_they_are_meant_to():
+    got = {n: _launch(c[1] * c[2], c[3]) for n, c in TIER_CASES.items()}
+    assert got == {"d41": (128, 7), "d81": (64, 7), "d160": (64, 7), "d161": ("global", 7), "d161_t30": ("global", 25)}
+    for n, (N, seg, L, T, ncent, M) in TIER_CASES.items():
+        R = got[n][0] if got[n][0] != "global" else 64
+        assert N > R and N % R != 0 and N <= kr.ROWS_PER_CENTRE * T  # more than one workgroup, ragged, unsampled
+    assert 30 * 161 > 4096 and 30 % 25 == 5  # two turns, the second clipped
+
+
+@pytest.mark.parametrize("name", list(TIER_CASES))
+def test_tile_tiers_equal_the_restatement(name):
+    """Centres, iteration count and NaN rows bit for bit with kmeans_ref.fit on the decoded rows."""
+    import hashlib
+    from vaq_amd.index import VaqHip
+    N, seg, L, T, ncent, M = TIER_CASES[name]
+    rng = np.random.default_rng(int(hashlib.sha256(("tiers:" + name).encode()).hexdigest()[:8], 16))
+    cents = [rng.normal(size=(ncent, L)).astype(np.float32) for _ in range(M)]
+    codes = rng.integers(0, ncent, size=(N, M), dtype=np.int64).astype(np.uint16)
+    want, want_iters, want_nan = kr.fit_codebook(codes, cents, seg, T)
+    v = VaqHip()
+    v.mBitsAlloc = [_bits(ncent)] * M
+    v.mCentroidsPerSubs = cents
+    v.mCodebook = codes
+    v._ensure_codes()
+    rc, out, iters, nan_rows = _kmeans(v, T, seg)
+    v.close()
+    assert rc == 0
+    print(f"{name}: iterations {iters} (restatement {want_iters}), NaN centres {nan_rows} (restatement {int(want_nan.sum())})")
+    kr.assert_centres_equal(out, want, name)
+    assert iters == want_iters and iters >= 2
+    assert nan_rows == int(want_nan.sum())
+    assert np.array_equal(np.isnan(out).any(axis=1), want_nan)

@@ -7,8 +7,14 @@
 //               run_off[s] + half * k_s + centre and one thread per (run, column) walking its run
 //   update      new = ((0 + p0) + p1) / float(count); a centre whose new row is not elementwise == the old one is
 //               replaced (an empty cluster: 0 / 0 = NaN, unequal for ever)
+// Every call of the reference samples for itself (KMeans.hpp:489-503): subspace s works on all n rows in their own
+// order when n <= max(256 k_s, 65536), else on the first max(256 k_s, 65536) rows of randomPermutation(n).  So a batch
+// has up to two sources, and cbfit::Sub::full says which one a subspace reads: the full matrix (all rows projected, or
+// widened, whole), or the gathered sample (the head of the permutation as long as the largest sampling subspace needs;
+// a smaller one takes a prefix).  A row's projection does not depend on other rows, so where both are needed the
+// sample is gathered from the projected full matrix.
 // Batching cannot change a bit: no value of subspace s is computed from another subspace's -- the slices are
-// disjoint columns of the projected sample, the keys of s lie in its own range [run_off, run_off + 2 k_s), its pairs
+// disjoint columns of the subspace's source, the keys of s lie in its own range [run_off, run_off + 2 k_s), its pairs
 // enter the sort in ascending row order and the sort is stable, so every run is the run the single fit would walk.
 // A subspace whose centres stopped changing is a fixed point: its assign step is skipped (its pairs are still there
 // from the iteration before), the rest recomputes the same centres.
@@ -45,24 +51,27 @@ __global__ void cb_gather_kernel(const T *__restrict__ X, int D, const int *__re
   out[i] = (float)X[(int64_t)rows[r] * D + (i - r * D)];
 }
 
-// means[c] = slice s of sample row seed_rows[c] (KMeans.hpp:516-520); grid.y = subspace
-__global__ void cb_seed_kernel(const float *__restrict__ P, int D, int L, const cbfit::Sub *__restrict__ subs,
-                               const int *__restrict__ seed_rows, float *__restrict__ means) {
+// means[c] = slice s of row seed_rows[c] of the subspace's source (KMeans.hpp:516-520); grid.y = subspace
+__global__ void cb_seed_kernel(const float *__restrict__ Ps, const float *__restrict__ Pf, int D, int L,
+                               const cbfit::Sub *__restrict__ subs, const int *__restrict__ seed_rows,
+                               float *__restrict__ means) {
   const int s = blockIdx.y;
   const cbfit::Sub sd = subs[s];
+  const float *P = sd.full ? Pf : Ps;
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= sd.k * L) return;
   const int c = i / L, j = i % L;
   means[(size_t)(sd.cent_off + c) * L + j] = P[(size_t)seed_rows[sd.cent_off + c] * D + (size_t)s * L + j];
 }
 
-// One row per thread, grid = (row tile, subspace).  X_LDS: the workgroup's slices sit in LDS as [column][row] (each
+// One row per thread, grid = (row tile, subspace); Ps: the gathered sample, Pf: the full matrix, the subspace reads
+// the one its Sub names (either may be null when no subspace reads it).  X_LDS: the workgroup's slices sit in LDS as [column][row] (each
 // thread reads its own column, conflict-free); else every thread reads its slice from global memory.  The
 // subspace's centres pass through LDS `stage` at a time and are read with wave-uniform addresses (broadcast).
 // Row r of subspace s: keys[pair_off + r] = run_off + half * k + centre, vals[pair_off + r] = r.
 template <bool X_LDS>
-__global__ void cb_assign_kernel(const float *__restrict__ P, int D, int L, const cbfit::Sub *__restrict__ subs,
-                                 const float *__restrict__ means, int stage, const int *__restrict__ active,
+__global__ void cb_assign_kernel(const float *__restrict__ Ps, const float *__restrict__ Pf, int D, int L,
+                                 const cbfit::Sub *__restrict__ subs, const float *__restrict__ means, int stage, const int *__restrict__ active,
                                  unsigned *__restrict__ keys, unsigned *__restrict__ vals, int *__restrict__ no_centre) {
   extern __shared__ float cb_lds[];
   const int s = blockIdx.y;
@@ -74,7 +83,7 @@ __global__ void cb_assign_kernel(const float *__restrict__ P, int D, int L, cons
   float *xt = cb_lds + (size_t)stage * L;    // [L][R]
   const int64_t r = r0 + tid;
   const int64_t rr = r < sd.rows ? r : sd.rows - 1;  // (rows past the end work on the last row and store nothing)
-  const float *slice0 = P + (size_t)s * L;
+  const float *slice0 = (sd.full ? Pf : Ps) + (size_t)s * L;
   if (X_LDS) {
     for (int i = tid; i < R * L; i += R) {
       const int row = i / L, col = i % L;
@@ -118,15 +127,15 @@ __global__ void cb_bounds_kernel(const unsigned *__restrict__ keys, int n, int *
 
 // part[run * L + col] = the rows of that run added from +0 in ascending row order; grid.y = subspace, neighbouring
 // threads take neighbouring columns of the same run
-__global__ void cb_accumulate_kernel(const float *__restrict__ P, int D, int L, const cbfit::Sub *__restrict__ subs,
-                                     const unsigned *__restrict__ rows_sorted, const int *__restrict__ start,
+__global__ void cb_accumulate_kernel(const float *__restrict__ Ps, const float *__restrict__ Pf, int D, int L,
+                                     const cbfit::Sub *__restrict__ subs, const unsigned *__restrict__ rows_sorted, const int *__restrict__ start,
                                      const int *__restrict__ end, float *__restrict__ part) {
   const int s = blockIdx.y;
   const cbfit::Sub sd = subs[s];
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= 2 * sd.k * L) return;
   const int g = sd.run_off + t / L, col = t % L;
-  const float *x = P + (size_t)s * L + col;
+  const float *x = (sd.full ? Pf : Ps) + (size_t)s * L + col;
   float sum = 0.0f;
   for (int i = start[g], e = end[g]; i < e; i++) sum += x[(size_t)rows_sorted[i] * D];
   part[(size_t)g * L + col] = sum;
@@ -165,8 +174,9 @@ hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan
                          int max_iter, float *d_means, int *iters_out, int *no_centre_out, CodebookPhases *phases,
                          hipStream_t st) {
   const int M = (int)plan.sub.size();
-  const int64_t S = plan.sample;
-  if (M < 1 || S < 1 || plan.n_pairs > 0x7fffffff) return hipErrorInvalidValue;
+  const int64_t S = plan.gathered;
+  if (M < 1 || plan.sample < 1 || plan.n_pairs > 0x7fffffff) return hipErrorInvalidValue;
+  if (plan.n_full ? (S > 0 && !plan.gather) : S < 1) return hipErrorInvalidValue;
   const int n_pairs = (int)plan.n_pairs, n_runs = plan.n_runs;
   hipError_t e;
 #define CB_TRY(expr)                          \
@@ -178,39 +188,45 @@ hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan
     hipStream_t st;
     ~Sync() { (void)hipStreamSynchronize(st); }
   };
-  vaqhost::DevBuf b_rows, b_gather, b_proj, b_sub, b_seed, b_keys_in, b_keys_out, b_vals_in, b_vals_out, b_bounds, b_part,
-      b_flags, b_temp;
+  vaqhost::DevBuf b_rows, b_gather, b_proj, b_full, b_sub, b_seed, b_keys_in, b_keys_out, b_vals_in, b_vals_out, b_bounds,
+      b_part, b_flags, b_temp;
   Sync sync_on_return{st};
   if (phases) *phases = CodebookPhases{};
   auto t0 = std::chrono::steady_clock::now();
 
-  // ---- the sample, gathered and projected once: every subspace works on a prefix of it ----
-  RowsRef src = d_X;
-  if (plan.sampled) {
+  // rows x D of src as floats, projected where there is a rotation: in place when nothing is to be done, else in buf
+  auto projected = [&](RowsRef src, int64_t rows, vaqhost::DevBuf &buf, const float **out) -> hipError_t {
+    *out = static_cast<const float *>(src.p);
+    if (!d_eig && src.elem != 1) return hipSuccess;
+    hipError_t pe = buf.ensure((size_t)rows * D * sizeof(float));
+    if (pe != hipSuccess) return pe;
+    *out = buf.as<float>();
+    if (d_eig) return launch_project(src, rows, D, d_eig, buf.as<float>(), st, 0);  // unchecked, as VAQ::train projects
+    return launch_widen_rows_u8(static_cast<const uint8_t *>(src.p), rows * D, buf.as<float>(), st);
+  };
+
+  // ---- the full matrix, for the subspaces that do not sample: all n rows projected (or widened) once ----
+  const float *Pf = nullptr, *Ps = nullptr;
+  if (plan.n_full) CB_TRY(projected(d_X, n, b_full, &Pf));
+  // ---- the sample, for those that do: gathered once, every one of them works on a prefix of it ----
+  if (S > 0 && !plan.gather) {
+    CB_TRY(projected(d_X, S, b_proj, &Ps));  // (the caller's rows are the sample)
+  } else if (S > 0) {
     const std::vector<int> rows = permutation_head(n, S);
     CB_TRY(b_rows.ensure((size_t)S * sizeof(int)));
     CB_TRY(b_gather.ensure((size_t)S * D * sizeof(float)));
     CB_TRY(hipMemcpyAsync(b_rows.p, rows.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, st));
     const unsigned grid = (unsigned)((S * D + 255) / 256);
-    if (d_X.elem == 1)
-      hipLaunchKernelGGL(cb_gather_kernel<uint8_t>, dim3(grid), dim3(256), 0, st, static_cast<const uint8_t *>(d_X.p), D,
-                         b_rows.as<int>(), S, b_gather.as<float>());
+    if (Pf || d_X.elem != 1)  // from the projected full matrix where there is one: a row's projection is its own
+      hipLaunchKernelGGL(cb_gather_kernel<float>, dim3(grid), dim3(256), 0, st,
+                         Pf ? Pf : static_cast<const float *>(d_X.p), D, b_rows.as<int>(), S, b_gather.as<float>());
     else
-      hipLaunchKernelGGL(cb_gather_kernel<float>, dim3(grid), dim3(256), 0, st, static_cast<const float *>(d_X.p), D,
+      hipLaunchKernelGGL(cb_gather_kernel<uint8_t>, dim3(grid), dim3(256), 0, st, static_cast<const uint8_t *>(d_X.p), D,
                          b_rows.as<int>(), S, b_gather.as<float>());
     CB_TRY(hipGetLastError());
     CB_TRY(hipStreamSynchronize(st));  // (rows is the host's)
-    src = RowsRef{b_gather.p, 4};
-  }
-  const float *P = static_cast<const float *>(src.p);
-  if (d_eig) {  // unchecked, as VAQ::train projects the training rows
-    CB_TRY(b_proj.ensure((size_t)S * D * sizeof(float)));
-    CB_TRY(launch_project(src, S, D, d_eig, b_proj.as<float>(), st, 0));
-    P = b_proj.as<float>();
-  } else if (src.elem == 1) {
-    CB_TRY(b_proj.ensure((size_t)S * D * sizeof(float)));
-    CB_TRY(launch_widen_rows_u8(static_cast<const uint8_t *>(src.p), S * D, b_proj.as<float>(), st));
-    P = b_proj.as<float>();
+    Ps = b_gather.as<float>();
+    if (!Pf && d_eig) CB_TRY(projected(RowsRef{b_gather.p, 4}, S, b_proj, &Ps));
   }
 
   // ---- the batch's tables and the seeds ----
@@ -243,8 +259,8 @@ hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan
   CB_TRY(hipMemcpyAsync(b_sub.p, plan.sub.data(), (size_t)M * sizeof(cbfit::Sub), hipMemcpyHostToDevice, st));
   CB_TRY(hipMemcpyAsync(b_seed.p, seeds.data(), seeds.size() * sizeof(int), hipMemcpyHostToDevice, st));
   CB_TRY(hipMemcpyAsync(flags, host_flags.data(), host_flags.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(cb_seed_kernel, dim3((unsigned)((plan.k_max * L + 255) / 256), (unsigned)M), dim3(256), 0, st, P, D,
-                     L, subs, b_seed.as<int>(), d_means);
+  hipLaunchKernelGGL(cb_seed_kernel, dim3((unsigned)((plan.k_max * L + 255) / 256), (unsigned)M), dim3(256), 0, st, Ps, Pf,
+                     D, L, subs, b_seed.as<int>(), d_means);
   CB_TRY(hipGetLastError());
   CB_TRY(hipStreamSynchronize(st));  // (the tables are the host's)
   if (phases) phases->gather_ms = cb_ms_since(t0);
@@ -255,7 +271,7 @@ hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan
   const bool x_lds = (size_t)R * L * sizeof(float) <= CB_TILE_BYTES;
   const int stage = std::max(1, std::min(plan.k_max, CB_STAGE_FLOATS / L));
   const size_t lds = ((size_t)stage * L + (x_lds ? (size_t)R * L : 0)) * sizeof(float);
-  const dim3 assign_grid((unsigned)((S + R - 1) / R), (unsigned)M);
+  const dim3 assign_grid((unsigned)((plan.sample + R - 1) / R), (unsigned)M);
   const dim3 acc_grid((unsigned)((2 * (int64_t)plan.k_max * L + 255) / 256), (unsigned)M);
 
   auto phase_end = [&](double *acc) -> hipError_t {
@@ -274,10 +290,10 @@ hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan
     CB_TRY(hipMemsetAsync(now, 0, (size_t)M * sizeof(int), st));
     CB_TRY(hipMemsetAsync(start, 0, (size_t)2 * n_runs * sizeof(int), st));
     if (x_lds)
-      hipLaunchKernelGGL(cb_assign_kernel<true>, assign_grid, dim3(R), lds, st, P, D, L, subs, d_means, stage, prev,
+      hipLaunchKernelGGL(cb_assign_kernel<true>, assign_grid, dim3(R), lds, st, Ps, Pf, D, L, subs, d_means, stage, prev,
                          keys_in, vals_in, flags + 2 * M);
     else
-      hipLaunchKernelGGL(cb_assign_kernel<false>, assign_grid, dim3(R), lds, st, P, D, L, subs, d_means, stage, prev,
+      hipLaunchKernelGGL(cb_assign_kernel<false>, assign_grid, dim3(R), lds, st, Ps, Pf, D, L, subs, d_means, stage, prev,
                          keys_in, vals_in, flags + 2 * M);
     CB_TRY(hipGetLastError());
     CB_TRY(phase_end(phases ? &phases->assign_ms : nullptr));
@@ -287,7 +303,7 @@ hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan
     hipLaunchKernelGGL(cb_bounds_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, keys_out, n_pairs,
                        start, end);
     CB_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cb_accumulate_kernel, acc_grid, dim3(256), 0, st, P, D, L, subs, vals_out, start, end,
+    hipLaunchKernelGGL(cb_accumulate_kernel, acc_grid, dim3(256), 0, st, Ps, Pf, D, L, subs, vals_out, start, end,
                        b_part.as<float>());
     CB_TRY(hipGetLastError());
     CB_TRY(phase_end(phases ? &phases->accumulate_ms : nullptr));

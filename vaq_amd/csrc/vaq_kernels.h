@@ -518,11 +518,14 @@ struct Plan;  // fit_codebooks_plan.h
 struct CodebookPhases {
   double gather_ms = 0, assign_ms = 0, accumulate_ms = 0, update_ms = 0;
 };
-// d_X: n x D device rows of either type (any byte address for byte rows), the device current.  The rows of the
-// largest sample are gathered (n > plan.sample: permutation_head(n, plan.sample), else all in order), widened and
-// projected by launch_project's chain (d_eig null: taken as they are); subspace s = columns [s * L, (s + 1) * L)
-// of the first plan.sub[s].rows of them, seeded from permutation_head(rows, k), then Lloyd iterations until its
-// centres stop changing or max_iter.  d_means: the M matrices back to back (plan.n_cent x L floats, device).
+// d_X: n x D device rows of either type (any byte address for byte rows), the device current (plan.gather cleared:
+// the plan.gathered rows of the sample, in its order).  The source is chosen per subspace, as every call of the
+// reference samples for itself: a subspace with plan.sub[s].full reads all n rows in their own order, widened and
+// projected whole by launch_project's chain (d_eig null and float rows: read in place); the others read the first
+// plan.sub[s].rows rows of permutation_head(n, plan.gathered), gathered once (from the projected matrix where there
+// is one, else gathered first and projected then).  Subspace s = columns [s * L, (s + 1) * L) of its rows, seeded
+// from permutation_head(rows, k), then Lloyd iterations until its centres stop changing or max_iter.  d_means: the M
+// matrices back to back (plan.n_cent x L floats, device).
 // iters_out[M] (host): the reference's iter_count per subspace.  *no_centre_out != 0: some row had no centre at a
 // distance below FLT_MAX (the reference indexes row -1 there); the centres are then not to be used.  phases
 // (optional) adds one synchronisation per phase.  Synchronises the stream; plan.n_pairs must be below 2^31 (it is

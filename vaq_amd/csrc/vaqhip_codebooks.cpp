@@ -119,8 +119,9 @@ int fit_to_host(vaq::RowsRef d_X, int64_t n, int D, const cb::Plan &plan, const 
   return VAQHIP_OK;
 }
 
-// X: host rows of X.elem bytes per element, uploaded as they are.  Where the fit samples, only the sample goes up:
-// its rows are copied out in the sample's order here, and the device is handed a matrix it takes whole.
+// X: host rows of X.elem bytes per element, uploaded as they are.  Where every subspace samples, only the sample goes
+// up: its rows are copied out in the sample's order here, and the device is handed the sample itself.  Where one
+// subspace reads all rows, all rows go up, and the device gathers the sample of the others.
 int fit_host_entry(int device_id, vaq::RowsRef X, int64_t n, int D, int M, const int *bits, const float *eigvec,
                    int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out) {
   cb::Plan plan;
@@ -128,7 +129,7 @@ int fit_host_entry(int device_id, vaq::RowsRef X, int64_t n, int D, int M, const
   DeviceGuard g(device_id);
   if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed (no CPU path)", device_id);
   DevBuf d_x;
-  const size_t row_bytes = (size_t)D * (size_t)X.elem, x_bytes = (size_t)plan.sample * row_bytes;
+  const size_t row_bytes = (size_t)D * (size_t)X.elem, x_bytes = (size_t)(plan.sampled ? plan.sample : n) * row_bytes;
   HIP_TRY(d_x.ensure(x_bytes));
   if (plan.sampled) {
     const std::vector<int> rows = vaq::permutation_head(n, plan.sample);
@@ -136,7 +137,7 @@ int fit_host_entry(int device_id, vaq::RowsRef X, int64_t n, int D, int M, const
     for (int64_t i = 0; i < plan.sample; i++)
       std::memcpy(picked.data() + (size_t)i * row_bytes, static_cast<const char *>(X.p) + (size_t)rows[(size_t)i] * row_bytes, row_bytes);
     HIP_TRY(hipMemcpy(d_x.p, picked.data(), x_bytes, hipMemcpyHostToDevice));
-    plan.sampled = false;
+    plan.gather = false;
   } else {
     HIP_TRY(hipMemcpy(d_x.p, X.p, x_bytes, hipMemcpyHostToDevice));
   }
