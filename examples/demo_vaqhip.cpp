@@ -43,7 +43,9 @@
 //                                           the raw vectors by KMeans::staticFitSampling, the call of VAQ.cpp:644-649 --
 //                                           not the arma::kmeans call VAQ::train runs today; --eigen is applied first,
 //                                           the bits are the caller's.  --file-format-ori bvecs fits from the bytes,
-//                                           --refine-resident from the rows on the device.  --save writes them as
+//                                           --refine-resident from the rows on the device.  With --devices the fit is
+//                                           sharded: the rows are cut over the GPUs, subspace s is fitted on device
+//                                           s % G, the same centres bit for bit.  --save writes them as
 //                                           demo_vaq --save does; composes with --encode; without --queries it ends there)
 //               with a ...,FAST method (codes of at most 4 bits): --dataset base.fvecs [--dataset-size N]
 //               [--learn-ratio 0.05]       (demo_vaq.cpp:42, :120-124: VAQ::learnQuantization on the raw dataset; from the
@@ -223,7 +225,7 @@ int main(int argc, char **argv) {
       const int max_iter = a.count("max-iter") ? std::atoi(a["max-iter"].c_str()) : 25;
       const char *from = "";
       auto t0 = std::chrono::steady_clock::now();
-      if (a.count("refine-resident") && !a.count("devices")) {
+      if (a.count("refine-resident")) {  // (with --devices: the rows cut over them, fitted where they lie)
         resident_rows = uploadRefine(a.count("dataset-refine") ? a["dataset-refine"] : a["dataset"], dsize);
         uploaded = true;
         t0 = std::chrono::steady_clock::now();
@@ -245,6 +247,15 @@ int main(int argc, char **argv) {
       std::cout << "; NaN centres";
       for (int nn : vaq.mCodebookNanRows) std::cout << " " << nn;
       std::cout << std::endl;
+      if (a.count("devices")) {
+        vaqhip_multi_fit_codebooks_timing ft;
+        if (vaqhip_multi_last_fit_codebooks_timing(&ft) == VAQHIP_OK && ft.n_devices > 0) {
+          std::cout << "   across " << ft.n_devices << " shards: fit " << ft.total_ms << " ms (columns " << ft.columns_ms
+                    << ", copy " << ft.copy_ms << ", place " << ft.place_ms << "); subspaces per owner";
+          for (int g = 0; g < ft.n_devices; g++) std::cout << " " << ft.owner_subspaces[g];
+          std::cout << std::endl;
+        }
+      }
       if (a.count("save")) saveCentroids(vaq.mCentroidsPerSubs, a["save"]);
       if (fit_only) return 0;
     }
@@ -256,11 +267,13 @@ int main(int argc, char **argv) {
       vaq.mMethods = plain ? plain : (uint32_t)VaqHip::NNMethod::Heap;
       if (a.count("devices") && a.count("refine-resident")) {
         if (N != D) throw Error(VAQHIP_EINVAL, "--encode with --refine-resident encodes the resident raw rows: --timeseries-size must be D");
-        t0 = std::chrono::steady_clock::now();
-        resident_rows = uploadRefine(a.count("dataset-refine") ? a["dataset-refine"] : a["dataset"], dsize);
-        uploaded = true;
-        std::cout << "== Refine dataset read + upload: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
-                  << " s (" << resident_rows << " rows resident" << (g_bvecs ? ", as bytes" : "") << ")" << std::endl;
+        if (!uploaded) {  // (--fit-codebooks with --refine-resident has left them there)
+          t0 = std::chrono::steady_clock::now();
+          resident_rows = uploadRefine(a.count("dataset-refine") ? a["dataset-refine"] : a["dataset"], dsize);
+          uploaded = true;
+          std::cout << "== Refine dataset read + upload: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
+                    << " s (" << resident_rows << " rows resident" << (g_bvecs ? ", as bytes" : "") << ")" << std::endl;
+        }
         t0 = std::chrono::steady_clock::now();
         vaq.encodeRefineDataset();
       } else {

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 120
+#define VAQHIP_VERSION 121
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -829,6 +829,65 @@ typedef struct {
   int n_devices;
 } vaqhip_multi_lut_fit_timing;
 int vaqhip_multi_last_lut_fit_timing(vaqhip_multi_lut_fit_timing *out);  /* the calling thread's last sharded fit */
+/* The sharded codebook fit: vaqhip_fit_codebooks's result, bit for bit -- centres (a NaN by position), iterations and
+ * NaN counts --, for ANY device list, with the training rows cut over the devices and no device ever holding the
+ * n x D rows, nor a projected copy of them.  Outputs and semantics are vaqhip_fit_codebooks's: sampling decided per
+ * subspace, all subspaces drawing from one permutation head, its seeds, Lloyd loop and NaN centres.
+ *   scheme      subspace s is owned by device s % G (M < G leaves owners idle; the result does not depend on the rule:
+ *               no value of a subspace is computed from another's).  Every shard writes, per owner, the packed block
+ *               [rows it contributes][D_w] of that owner's columns, D_w = subspaces owned x L (one kernel: a byte is
+ *               widened where it is loaded and, with eigvec, every value is one fmaf chain over the row's D inputs in
+ *               vaqhip_project's order; only the columns an owner needs are computed for it, so across owners the
+ *               contributed rows are projected once).  The rows contributed are the shard's rows of the sample
+ *               permutation_head(n, sample), or ALL of its rows for an owner of a subspace that does not sample.
+ *               Copies only carry the blocks to the owners (peer copies; device-to-device where two shards name one
+ *               GPU): a block of all rows lands at row lo_g of the owner's n x D_w matrix, a sample block in a staging
+ *               area from where a placement kernel writes each row to its position in the owner's sample x D_w matrix.
+ *               Every owner then runs the single fit's phases unchanged over its two matrices with D = D_w and no
+ *               eigvec: seeds, assign, one stable radix sort, run bounds, ordered sums, update.
+ *   G == 1      is the single fit itself (vaqhip_fit_codebooks / vaqhip_refiner_fit_codebooks): no exchange.
+ *   host form   X is cut over the devices as vaqhip_multi_set_codes_u16 cuts rows.  Where every subspace samples, each
+ *               shard uploads only the sample rows that fall in its slice, picked on the host; otherwise its slice,
+ *               once.  Float or byte rows go up as they are.
+ *   refiner     the RAW rows a multi refiner holds, float or byte, are read in place; n, D and the cut are the
+ *               refiner's (a last shard grown by add_rows and empty shards included); nothing is uploaded but eigvec
+ *               and the row lists.  The refiner's lock is held; its rows are only read.
+ *   memory      per owner sample x D_w floats (twice while the staging area lives); per owner of a subspace that does
+ *               not sample n x D_w floats more (there n <= 256 k_max); per owner 16 bytes per (owned subspace, row it
+ *               works on); per shard its packed blocks (rows contributed x D floats at most per kind) and, in the host
+ *               form, its uploaded rows.
+ *   refusals    decided before any device is touched, the three outputs untouched: vaqhip_fit_codebooks's, with its
+ *               codes; n_devices outside 1..VAQHIP_MAX_DEVICES and a null device list or refiner (VAQHIP_EINVAL); a
+ *               refiner without rows (VAQHIP_ESTATE); D % M != 0 against the refiner's D (VAQHIP_EINVAL).  Known only
+ *               after the run: VAQHIP_EINVAL when a row has no centre on ANY owner, the outputs untouched as on every
+ *               failure.
+ * iters_out and nan_rows_out may be NULL.  Synchronous; a failing shard ends the call; the caller's current device is
+ * left as it was; errors are read through vaqhip_multi_last_error(). */
+int vaqhip_multi_fit_codebooks(int n_devices, const int *device_ids, const float *X_rowmajor, int64_t n, int D, int M,
+                               const int *bits, const float *eigvec_real_rowmajor /* D x D or NULL */, int max_iter,
+                               float *centroids_out, int *iters_out, int *nan_rows_out);
+int vaqhip_multi_fit_codebooks_u8(int n_devices, const int *device_ids, const uint8_t *X_rowmajor, int64_t n, int D, int M,
+                                  const int *bits, const float *eigvec_real_rowmajor /* D x D or NULL */, int max_iter,
+                                  float *centroids_out, int *iters_out, int *nan_rows_out);
+int vaqhip_multi_refiner_fit_codebooks(vaqhip_multi_refiner *r, int M, const int *bits,
+                                       const float *eigvec_real_rowmajor /* D x D or NULL */, int max_iter,
+                                       float *centroids_out, int *iters_out, int *nan_rows_out);
+typedef struct {
+  float total_ms;       /* wall time of the call, its planning and the release of its workers, streams and
+                           buffers included (G == 1: the single fit's total_ms)                               */
+  float columns_ms;     /* per phase the slowest device, device events: rows -> the owners' packed blocks;     */
+  float copy_ms;        /*   the blocks to their owners;                                                       */
+  float place_ms;       /*   staging -> sample matrix (or the owner's own gather from its full matrix)         */
+  float assign_ms, accumulate_ms, update_ms;  /* the slowest owner's, as vaqhip_fit_codebooks_timing has them: only
+                                                 with vaqhip_fit_codebooks_set_timing(1) on the calling thread, else 0 */
+  int iterations;       /* the largest iteration count of a subspace */
+  int subspaces, dims;
+  int64_t rows;
+  int64_t sample_rows;  /* the most rows a subspace worked on */
+  int n_devices;
+  int owner_subspaces[VAQHIP_MAX_DEVICES];  /* subspaces fitted per device of the list; they sum to M */
+} vaqhip_multi_fit_codebooks_timing;
+int vaqhip_multi_last_fit_codebooks_timing(vaqhip_multi_fit_codebooks_timing *out);  /* calling thread's last sharded fit */
 typedef struct {
   int n_devices;
   int exchange;              /* what the last search used: 0 none (one shard), 1 RCCL all-gather, 2 copies */

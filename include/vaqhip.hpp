@@ -379,17 +379,26 @@ public:
 
   // The codebook step of VAQ::train (VAQ.cpp:628-660) by the call of :644-649, KMeans::staticFitSampling per subspace
   // (NOT the arma::kmeans call that runs beside it today): fills mCentroidsPerSubs from mBitsAlloc and mEigenVectors
-  // (empty: XTrain is in PCA space already), every centre the reference's bit for bit (vaqhip_fit_codebooks; one
-  // device, mDevice).  XTrain: raw rows, as wide as the index.  mCodebookIters / mCodebookNanRows: per subspace the
+  // (empty: XTrain is in PCA space already), every centre the reference's bit for bit (vaqhip_fit_codebooks on
+  // mDevice; after setDevices() vaqhip_multi_fit_codebooks: the rows cut over mDevices, subspace s fitted on device
+  // s % G, the same centres bit for bit).  XTrain: raw rows, as wide as the index.  mCodebookIters / mCodebookNanRows: per subspace the
   // reference's iter_count and the centres an empty cluster left NaN.  PCA and bit allocation stay the caller's.
   std::vector<int> mCodebookIters, mCodebookNanRows;
   void fitCodebooks(const RowMatrixF &XTrain, int maxIter = 25) { fitCodebooksRows(XTrain.data(), (int64_t)XTrain.rows(), (int)XTrain.cols(), maxIter); }
   // from byte rows (readBVecsU8): the float overload's centres on the widened rows, bit for bit
   void fitCodebooks(const RowMatrix<uint8_t> &XTrain, int maxIter = 25) { fitCodebooksRows(XTrain.data(), (int64_t)XTrain.rows(), (int)XTrain.cols(), maxIter); }
-  // from the rows setRefineDataset() left on the device (one device), float or byte, read in place
+  // from the rows setRefineDataset() left on the device, float or byte, read in place; after setDevices() over the
+  // multi refiner's shards (vaqhip_multi_refiner_fit_codebooks)
   void fitCodebooksRefineDataset(int maxIter = 25) {
-    if (!rf_) throw Error(mDevices.empty() ? VAQHIP_ESTATE : VAQHIP_EUNSUPPORTED,
-                          "vaqhip: fitCodebooksRefineDataset needs setRefineDataset() on one device first");
+    if (!(mDevices.empty() ? (bool)rf_ : (bool)mrf_))
+      throw Error(VAQHIP_ESTATE, "vaqhip: fitCodebooksRefineDataset needs setRefineDataset() first");
+    if (mrf_) {
+      fitCodebooksWith(rf_dim_, [&](const float *eig, float *cent) {
+        return vaqhip_multi_refiner_fit_codebooks(mrf_, mHighestSubs(), mBitsAlloc.data(), eig, maxIter, cent,
+                                                  mCodebookIters.data(), mCodebookNanRows.data());
+      }, true);
+      return;
+    }
     fitCodebooksWith(rf_dim_, [&](const float *eig, float *cent) {
       return vaqhip_refiner_fit_codebooks(rf_, mHighestSubs(), mBitsAlloc.data(), eig, maxIter, cent, mCodebookIters.data(),
                                           mCodebookNanRows.data());
@@ -405,13 +414,28 @@ private:
                               float *cent, int *iters, int *nan) {
     return vaqhip_fit_codebooks_u8(dev, X, n, D, M, bits, eig, it, cent, iters, nan);
   }
+  static int fitCodebooksCall(const std::vector<int> &devs, const float *X, int64_t n, int D, int M, const int *bits,
+                              const float *eig, int it, float *cent, int *iters, int *nan) {
+    return vaqhip_multi_fit_codebooks((int)devs.size(), devs.data(), X, n, D, M, bits, eig, it, cent, iters, nan);
+  }
+  static int fitCodebooksCall(const std::vector<int> &devs, const uint8_t *X, int64_t n, int D, int M, const int *bits,
+                              const float *eig, int it, float *cent, int *iters, int *nan) {
+    return vaqhip_multi_fit_codebooks_u8((int)devs.size(), devs.data(), X, n, D, M, bits, eig, it, cent, iters, nan);
+  }
   template <class T> void fitCodebooksRows(const T *X, int64_t n, int D, int maxIter) {
+    if (!mDevices.empty()) {
+      fitCodebooksWith(D, [&](const float *eig, float *cent) {
+        return fitCodebooksCall(mDevices, X, n, D, mHighestSubs(), mBitsAlloc.data(), eig, maxIter, cent, mCodebookIters.data(),
+                                mCodebookNanRows.data());
+      }, true);
+      return;
+    }
     fitCodebooksWith(D, [&](const float *eig, float *cent) {
       return fitCodebooksCall(mDevice, X, n, D, mHighestSubs(), mBitsAlloc.data(), eig, maxIter, cent, mCodebookIters.data(),
                               mCodebookNanRows.data());
     });
   }
-  template <class Call> void fitCodebooksWith(int D, Call call) {
+  template <class Call> void fitCodebooksWith(int D, Call call, bool multi = false) {
     const int M = mHighestSubs();
     if (M < 1 || D < 1 || D % M != 0) throw Error(VAQHIP_EINVAL, "vaqhip: fitCodebooks needs mBitsAlloc, and rows of M subspaces");
     if (mEigenVectors.rows() && ((int)mEigenVectors.rows() != D || (int)mEigenVectors.cols() != D))
@@ -422,7 +446,9 @@ private:
     std::vector<float> cent(total ? total : 1);
     mCodebookIters.assign((size_t)M, 0);
     mCodebookNanRows.assign((size_t)M, 0);
-    check(call(mEigenVectors.rows() ? mEigenVectors.data() : nullptr, cent.data()));
+    const int rc = call(mEigenVectors.rows() ? mEigenVectors.data() : nullptr, cent.data());
+    if (multi) checkMulti(rc);  // (a sharded call's text is vaqhip_multi_last_error's)
+    else check(rc);
     invalidate();  // (an index made from other centres)
     mCentroidsPerSubs.clear();
     size_t off = 0;

@@ -59,6 +59,8 @@ SYMBOLS = [
     "vaqhip_multi_learn_quantization_u8", "vaqhip_multi_learn_quantization_from_refiner",
     "vaqhip_fit_codebooks", "vaqhip_fit_codebooks_device", "vaqhip_fit_codebooks_u8", "vaqhip_fit_codebooks_u8_device",
     "vaqhip_refiner_fit_codebooks", "vaqhip_fit_codebooks_set_timing", "vaqhip_last_fit_codebooks_timing",
+    "vaqhip_multi_fit_codebooks", "vaqhip_multi_fit_codebooks_u8", "vaqhip_multi_refiner_fit_codebooks",
+    "vaqhip_multi_last_fit_codebooks_timing",
 ]
 MAX_DEVICES = 16
 
@@ -137,6 +139,13 @@ class MultiLutFitTiming(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("columns_ms", C.c_float), ("copy_ms", C.c_float), ("sort_ms", C.c_float),
                 ("quantile_ms", C.c_float), ("means_ms", C.c_float), ("rows", C.c_int64), ("dims", C.c_int),
                 ("n_devices", C.c_int)]
+
+
+class MultiFitCodebooksTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("columns_ms", C.c_float), ("copy_ms", C.c_float), ("place_ms", C.c_float),
+                ("assign_ms", C.c_float), ("accumulate_ms", C.c_float), ("update_ms", C.c_float),
+                ("iterations", C.c_int), ("subspaces", C.c_int), ("dims", C.c_int), ("rows", C.c_int64),
+                ("sample_rows", C.c_int64), ("n_devices", C.c_int), ("owner_subspaces", C.c_int * 16)]
 
 
 class MultiInfo(C.Structure):
@@ -285,6 +294,10 @@ def load():
     L.vaqhip_multi_lut_fit_quantiles.argtypes = [i32, C.POINTER(i32), vp, i64, i32, C.POINTER(i32), vp, vp, vp]
     L.vaqhip_multi_refiner_lut_fit_quantiles.argtypes = [vp, C.POINTER(i32), vp, vp, vp]
     L.vaqhip_multi_last_lut_fit_timing.argtypes = [C.POINTER(MultiLutFitTiming)]
+    for name in ("vaqhip_multi_fit_codebooks", "vaqhip_multi_fit_codebooks_u8"):
+        getattr(L, name).argtypes = [i32, C.POINTER(i32), vp, i64, i32, i32, C.POINTER(i32), vp, i32, vp, vp, vp]
+    L.vaqhip_multi_refiner_fit_codebooks.argtypes = [vp, i32, C.POINTER(i32), vp, i32, vp, vp, vp]
+    L.vaqhip_multi_last_fit_codebooks_timing.argtypes = [C.POINTER(MultiFitCodebooksTiming)]
     L.vaqhip_multi_refiner_create.argtypes = [C.POINTER(vp), i32, i32, C.POINTER(i32)]
     L.vaqhip_multi_refiner_destroy.argtypes = [vp]
     L.vaqhip_multi_refiner_destroy.restype = None

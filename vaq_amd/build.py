@@ -14,12 +14,13 @@ CSRC = os.path.join(ROOT, "vaq_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "vaq_amd", "lib")
 LIB = os.path.join(LIBDIR, "libvaqhip.so")
 SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_codebooks.hip", "vaq_fast.hip", "vaq_lutfit.hip", "vaq_learn.hip", "vaq_refine.hip", "vaq_exhaust.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp", "vaqhip_learn.cpp", "vaqhip_lutfit.cpp", "vaqhip_codebooks.cpp", "vaqhip_refiner.cpp",
-           "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp", "vaqhip_multi_encode.cpp", "vaqhip_multi_lutfit.cpp", "vaqhip_multi_learn.cpp", "vaqhip_rccl.cpp"]
+           "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp", "vaqhip_multi_encode.cpp", "vaqhip_multi_lutfit.cpp", "vaqhip_multi_learn.cpp", "vaqhip_multi_codebooks.cpp", "vaqhip_rccl.cpp"]
 MULTI_REFINER_SOURCES = ("vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp")
 MULTI_ENCODE_SOURCE = "vaqhip_multi_encode.cpp"  # reads the multi refiner's resident rows: its headers too
 MULTI_LUTFIT_SOURCE = "vaqhip_multi_lutfit.cpp"  # the sharded quantile fit: reads the multi refiner's resident rows too
 MULTI_LEARN_SOURCE = "vaqhip_multi_learn.cpp"  # learnQuantization over the multi refiner's resident rows
-MULTI_SOURCES = ("vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE, MULTI_LEARN_SOURCE) + MULTI_REFINER_SOURCES
+MULTI_CODEBOOKS_SOURCE = "vaqhip_multi_codebooks.cpp"  # the sharded codebook fit: reads the multi refiner's resident rows too
+MULTI_SOURCES = ("vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE, MULTI_LEARN_SOURCE, MULTI_CODEBOOKS_SOURCE) + MULTI_REFINER_SOURCES
 KERNEL_HEADER = os.path.join(CSRC, "vaq_kernels.h")
 OWNER_HEADER = os.path.join(CSRC, "refine_owner.h")  # the refiner's cut and label -> shard: vaq_kernels.h brings it
 API_HEADER = os.path.join(ROOT, "include", "vaqhip.h")
@@ -47,6 +48,7 @@ LUTFIT_PLAN_HEADER = os.path.join(CSRC, "lutfit_multi_plan.h")  # owners, rounds
 LEARN_PLAN_HEADER = os.path.join(CSRC, "learn_plan.h")  # learnQuantization's host arithmetic: both forms, the loss kernel (no HIP)
 LEARN_HEADER = os.path.join(CSRC, "vaq_learn.h")  # the kernels of learnQuantization's device forms
 CODEBOOKS_PLAN_HEADER = os.path.join(CSRC, "fit_codebooks_plan.h")  # samples, offsets, key width of the codebook fit (no HIP)
+CODEBOOKS_MULTI_PLAN_HEADER = os.path.join(CSRC, "fit_codebooks_multi_plan.h")  # owners, sub-plans, sample split of the sharded fit (no HIP)
 
 
 def _deps(src: str):
@@ -59,8 +61,10 @@ def _deps(src: str):
         deps += [MULTI_HEADER, JOB_POOL_HEADER, RCCL_HEADER] if src in MULTI_SOURCES else [INDEX_HEADER]
     if src in ("vaq_kernels.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_lutfit.hip", "vaq_codebooks.hip"):
         deps.append(DEV_HEADER)
-    if src in ("vaq_codebooks.hip", "vaqhip_codebooks.cpp"):
+    if src in ("vaq_codebooks.hip", "vaqhip_codebooks.cpp", MULTI_CODEBOOKS_SOURCE):
         deps += [CODEBOOKS_PLAN_HEADER, KMEANS_SAMPLE_HEADER]
+    if src == MULTI_CODEBOOKS_SOURCE:
+        deps.append(CODEBOOKS_MULTI_PLAN_HEADER)
     if src in ("vaq_lutfit.hip", "vaqhip_lutfit.cpp", MULTI_LUTFIT_SOURCE, "vaq_learn.hip"):
         deps.append(LUTFIT_HEADER)
     if src in ("vaq_learn.hip", "vaqhip_learn.cpp", "vaqhip_fast.cpp"):
@@ -85,9 +89,9 @@ def _deps(src: str):
         deps.append(REFINE_GROUP_HEADER)
     if src == "vaq_exhaust.hip":
         deps.append(EXHAUST_HEADER)
-    if src == "vaqhip_refiner.cpp" or src in MULTI_REFINER_SOURCES or src in (MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE, MULTI_LEARN_SOURCE):
+    if src == "vaqhip_refiner.cpp" or src in MULTI_REFINER_SOURCES or src in (MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE, MULTI_LEARN_SOURCE, MULTI_CODEBOOKS_SOURCE):
         deps += [EXHAUST_PLAN_HEADER, REFINE_COMMON_HEADER]
-    if src in MULTI_REFINER_SOURCES or src in (MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE, MULTI_LEARN_SOURCE):
+    if src in MULTI_REFINER_SOURCES or src in (MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE, MULTI_LEARN_SOURCE, MULTI_CODEBOOKS_SOURCE):
         deps.append(MULTI_REFINER_HEADER)
     return deps
 OBJDIR = os.path.join(LIBDIR, "obj")

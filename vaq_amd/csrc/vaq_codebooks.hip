@@ -164,6 +164,116 @@ __global__ __launch_bounds__(64) void cb_update_kernel(const float *__restrict__
   if (lane == 0) changed[s] = 1;
 }
 
+// ---- the sharded fit's shard step (vaqhip_multi_codebooks.cpp, DESIGN.md section 4f "Across shards") ----
+// out[i][c], i < cnt, c < D_w: compact column c of ONE owner (column subs[c / L] * L + c % L of the rows) for the i-th
+// row a shard contributes -- local row rows[i], or first + i where rows is null.  Without E the value is the row's
+// own, a byte widened where it is loaded.  With E it is ONE fmaf chain over the row's D inputs ascending from
+// acc = 0.0f: project_kernel's value bit for bit (vaq_kernels.hip), computed for the owner's columns only.
+// A workgroup is tc column threads by tr = 256 / tc row groups (tc: the power of two from 16 to 256 that covers D_w,
+// blockIdx.y the column block where D_w > 256) and takes CC_RPT * tr rows at a time, CC_RPT accumulators per thread.
+// The rows pass through LDS in tiles of CC_JT inner indices, each element loaded once per workgroup: a half-wave loads
+// 32 consecutive elements of a row, and the row stride CC_STRIDE = 33 words is odd, so the loader's 32 lanes and the
+// row groups of a half-wave (at most 16, rows rg apart) hit different banks; lanes of one row group read one address
+// (a broadcast).  E[j][column] is read by neighbouring lanes at neighbouring addresses inside a subspace's L columns.
+// 8.4 KB of LDS and a handful of VGPRs: occupancy is bounded by waves, not by either.  Rows and offsets are 64-bit.
+constexpr int CC_THREADS = 256, CC_JT = 32, CC_STRIDE = CC_JT + 1, CC_RPT = 4, CC_MIN_TC_LOG2 = 4;
+constexpr int CC_TILE_ROWS = CC_RPT * (CC_THREADS >> CC_MIN_TC_LOG2);
+
+template <typename T>
+__global__ __launch_bounds__(CC_THREADS) void cb_columns_kernel(const T *__restrict__ X, int D, const float *__restrict__ E,
+                                                                const int *__restrict__ rows, int64_t first, int64_t cnt,
+                                                                const int *__restrict__ subs, int L, int D_w, int tc_log2,
+                                                                float *__restrict__ out) {
+  __shared__ float tile[CC_TILE_ROWS * CC_STRIDE];
+  const int tid = threadIdx.x;
+  const int tc = 1 << tc_log2, tr = CC_THREADS >> tc_log2;
+  const int rg = tid >> tc_log2;
+  const int c = blockIdx.y * tc + (tid & (tc - 1));
+  const bool col_ok = c < D_w;
+  const int gc = col_ok ? subs[c / L] * L + c % L : 0;
+  const int tile_rows = tr * CC_RPT;
+  const int lc = tid & (CC_JT - 1), lr = tid / CC_JT;
+  for (int64_t row0 = (int64_t)blockIdx.x * tile_rows; row0 < cnt; row0 += (int64_t)gridDim.x * tile_rows) {
+    float acc[CC_RPT];
+#pragma unroll
+    for (int i = 0; i < CC_RPT; i++) acc[i] = 0.0f;
+    if (!E) {
+#pragma unroll
+      for (int i = 0; i < CC_RPT; i++) {
+        const int64_t r = row0 + rg + i * tr;
+        if (col_ok && r < cnt) acc[i] = (float)X[(rows ? (int64_t)rows[r] : first + r) * D + gc];
+      }
+    } else {
+      for (int j0 = 0; j0 < D; j0 += CC_JT) {
+        __syncthreads();  // (the tile before has been read)
+        for (int r = lr; r < tile_rows; r += CC_THREADS / CC_JT) {
+          const int64_t i = row0 + r;
+          float v = 0.0f;
+          if (i < cnt && j0 + lc < D) v = (float)X[(rows ? (int64_t)rows[i] : first + i) * D + j0 + lc];
+          tile[r * CC_STRIDE + lc] = v;
+        }
+        __syncthreads();
+        if (col_ok) {
+          const int jn = D - j0 < CC_JT ? D - j0 : CC_JT;
+          const float *e = E + (size_t)j0 * D + gc;
+          for (int jj = 0; jj < jn; jj++, e += D) {
+            const float ev = *e;
+#pragma unroll
+            for (int i = 0; i < CC_RPT; i++) acc[i] = __builtin_fmaf(tile[(rg + i * tr) * CC_STRIDE + jj], ev, acc[i]);
+          }
+        }
+      }
+    }
+    if (col_ok) {
+#pragma unroll
+      for (int i = 0; i < CC_RPT; i++) {
+        const int64_t r = row0 + rg + i * tr;
+        if (r < cnt) out[r * D_w + c] = acc[i];
+      }
+    }
+  }
+}
+
+// the owner's side of the exchange: staging row i goes to row pos[i] of the sample matrix (the sample is in
+// permutation order, so a shard's rows are scattered in it)
+__global__ void cb_place_kernel(const float *__restrict__ stage, const int *__restrict__ pos, int64_t rows, int D_w,
+                                float *__restrict__ Ps) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * D_w) return;
+  const int64_t r = i / D_w;
+  Ps[(int64_t)pos[r] * D_w + (i - r * D_w)] = stage[i];
+}
+
+hipError_t launch_codebook_columns(RowsRef X, int D, const float *d_eig, const int *d_rows, int64_t first, int64_t cnt,
+                                   const int *d_subs, int L, int D_w, float *out, hipStream_t st) {
+  if (cnt < 1 || D_w < 1) return hipSuccess;
+  int tc_log2 = CC_MIN_TC_LOG2;
+  while (tc_log2 < 8 && (1 << tc_log2) < D_w) tc_log2++;
+  const int tc = 1 << tc_log2, tile_rows = CC_RPT * (CC_THREADS >> tc_log2);
+  const dim3 grid((unsigned)std::min<int64_t>((cnt + tile_rows - 1) / tile_rows, 1 << 16), (unsigned)((D_w + tc - 1) / tc));
+  if (X.elem == 1)
+    hipLaunchKernelGGL(cb_columns_kernel<uint8_t>, grid, dim3(CC_THREADS), 0, st, static_cast<const uint8_t *>(X.p), D, d_eig,
+                       d_rows, first, cnt, d_subs, L, D_w, tc_log2, out);
+  else
+    hipLaunchKernelGGL(cb_columns_kernel<float>, grid, dim3(CC_THREADS), 0, st, static_cast<const float *>(X.p), D, d_eig,
+                       d_rows, first, cnt, d_subs, L, D_w, tc_log2, out);
+  return hipGetLastError();
+}
+
+hipError_t launch_codebook_place(const float *d_stage, const int *d_pos, int64_t rows, int D_w, float *d_Ps, hipStream_t st) {
+  if (rows < 1) return hipSuccess;
+  hipLaunchKernelGGL(cb_place_kernel, dim3((unsigned)((rows * D_w + 255) / 256)), dim3(256), 0, st, d_stage, d_pos, rows,
+                     D_w, d_Ps);
+  return hipGetLastError();
+}
+
+hipError_t launch_codebook_gather(const float *d_Pf, int D_w, const int *d_rows, int64_t S, float *d_Ps, hipStream_t st) {
+  if (S < 1) return hipSuccess;
+  hipLaunchKernelGGL(cb_gather_kernel<float>, dim3((unsigned)((S * D_w + 255) / 256)), dim3(256), 0, st, d_Pf, D_w, d_rows, S,
+                     d_Ps);
+  return hipGetLastError();
+}
+
 namespace {
 double cb_ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -177,7 +287,6 @@ hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan
   const int64_t S = plan.gathered;
   if (M < 1 || plan.sample < 1 || plan.n_pairs > 0x7fffffff) return hipErrorInvalidValue;
   if (plan.n_full ? (S > 0 && !plan.gather) : S < 1) return hipErrorInvalidValue;
-  const int n_pairs = (int)plan.n_pairs, n_runs = plan.n_runs;
   hipError_t e;
 #define CB_TRY(expr)                          \
   do {                                        \
@@ -186,11 +295,13 @@ hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan
   // (freed on return, after the stream is synchronised)
   struct Sync {
     hipStream_t st;
-    ~Sync() { (void)hipStreamSynchronize(st); }
+    bool armed;
+    ~Sync() {
+      if (armed) (void)hipStreamSynchronize(st);
+    }
   };
-  vaqhost::DevBuf b_rows, b_gather, b_proj, b_full, b_sub, b_seed, b_keys_in, b_keys_out, b_vals_in, b_vals_out, b_bounds,
-      b_part, b_flags, b_temp;
-  Sync sync_on_return{st};
+  vaqhost::DevBuf b_rows, b_gather, b_proj, b_full;
+  Sync sync_on_return{st, true};
   if (phases) *phases = CodebookPhases{};
   auto t0 = std::chrono::steady_clock::now();
 
@@ -228,6 +339,35 @@ hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan
     Ps = b_gather.as<float>();
     if (!Pf && d_eig) CB_TRY(projected(RowsRef{b_gather.p, 4}, S, b_proj, &Ps));
   }
+
+#undef CB_TRY
+  sync_on_return.armed = false;  // (codebooks_lloyd synchronises before it returns, and the sources are freed behind it)
+  return codebooks_lloyd(Ps, Pf, D, L, plan, max_iter, d_means, iters_out, no_centre_out, phases, t0, st);
+}
+
+// The fit from its two sources on: Ps the sample (plan.gathered x D, the subspaces with full == 0 read prefixes of
+// it), Pf the full matrix (n x D, those with full == 1), either null when no subspace reads it; both complete on `st`.
+// codebooks_fit above ends in it; the owners of the sharded fit (vaqhip_multi_codebooks.cpp) call it over their
+// compact matrices.  began: when the caller started preparing the sources, for phases->gather_ms.
+hipError_t codebooks_lloyd(const float *Ps, const float *Pf, int D, int L, const cbfit::Plan &plan, int max_iter,
+                           float *d_means, int *iters_out, int *no_centre_out, CodebookPhases *phases,
+                           std::chrono::steady_clock::time_point began, hipStream_t st) {
+  const int M = (int)plan.sub.size();
+  if (M < 1 || plan.sample < 1 || plan.n_pairs > 0x7fffffff) return hipErrorInvalidValue;
+  const int n_pairs = (int)plan.n_pairs, n_runs = plan.n_runs;
+  hipError_t e;
+#define CB_TRY(expr)                          \
+  do {                                        \
+    if ((e = (expr)) != hipSuccess) return e; \
+  } while (0)
+  // (freed on return, after the stream is synchronised)
+  struct Sync {
+    hipStream_t st;
+    ~Sync() { (void)hipStreamSynchronize(st); }
+  };
+  vaqhost::DevBuf b_sub, b_seed, b_keys_in, b_keys_out, b_vals_in, b_vals_out, b_bounds, b_part, b_flags, b_temp;
+  Sync sync_on_return{st};
+  auto t0 = began;
 
   // ---- the batch's tables and the seeds ----
   std::vector<int> seeds((size_t)plan.n_cent);

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <chrono>
+
 #include "refine_owner.h"
 
 namespace vaq {
@@ -533,6 +535,23 @@ struct CodebookPhases {
 hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan &plan, const float *d_eig,
                          int max_iter, float *d_means, int *iters_out, int *no_centre_out, CodebookPhases *phases,
                          hipStream_t st);
+// codebooks_fit from its two sources on (it ends in this): Ps the sample (plan.gathered x D), Pf the full matrix
+// (n x D), floats on the current device and complete on `st`, either null when no subspace reads it; no eigvec, no
+// gather.  The owners of the sharded fit call it over their compact matrices with D = D_w and their sub-plan.
+// began: when the caller started preparing the sources (phases->gather_ms counts from it).
+hipError_t codebooks_lloyd(const float *Ps, const float *Pf, int D, int L, const cbfit::Plan &plan, int max_iter,
+                           float *d_means, int *iters_out, int *no_centre_out, CodebookPhases *phases,
+                           std::chrono::steady_clock::time_point began, hipStream_t st);
+// The sharded fit's shard step: out [cnt][D_w] = the compact columns of one owner (d_subs: its subspaces, D_w / L of
+// them, device) for the rows a shard contributes -- X's local rows d_rows[0 .. cnt) (device), or first + i where
+// d_rows is null.  X: the shard's rows, float or byte, D wide; d_eig null: the rows' own values, else
+// launch_project's fmaf chain per value.  cnt == 0 launches nothing.
+hipError_t launch_codebook_columns(RowsRef X, int D, const float *d_eig, const int *d_rows, int64_t first, int64_t cnt,
+                                   const int *d_subs, int L, int D_w, float *out, hipStream_t st);
+// the owner's placement: d_Ps[d_pos[i]][.] = d_stage[i][.] for i < rows, D_w floats per row
+hipError_t launch_codebook_place(const float *d_stage, const int *d_pos, int64_t rows, int D_w, float *d_Ps, hipStream_t st);
+// an owner that holds all rows gathers the sample of its other subspaces: d_Ps[i][.] = d_Pf[d_rows[i]][.], i < S
+hipError_t launch_codebook_gather(const float *d_Pf, int D_w, const int *d_rows, int64_t S, float *d_Ps, hipStream_t st);
 
 } // namespace vaq
 #endif

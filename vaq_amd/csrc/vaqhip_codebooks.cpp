@@ -179,6 +179,20 @@ int vaqhip_fit_codebooks_u8_device(int device_id, const uint8_t *d_X, int64_t n,
                           nan_rows_out, stream);
 }
 
+// ---- vaqhip_internal.h: what the sharded fit takes from here ----
+int vaqhip_internal_fit_codebooks_check(const void *X, int64_t n, int D, int M, const int *bits, int max_iter,
+                                        const void *centroids_out) {
+  cb::Plan plan;
+  return check_args(X, n, D, M, bits, max_iter, centroids_out, &plan);
+}
+int vaqhip_internal_fit_codebooks_rows_device(int device, const void *d_X, int elem, int64_t n, int D, int M,
+                                              const int *bits, const float *eigvec, int max_iter, float *centroids_out,
+                                              int *iters_out, int *nan_rows_out) {
+  return fit_codebooks_rows_device(device, vaq::RowsRef{d_X, elem}, n, D, M, bits, eigvec, max_iter, centroids_out,
+                                   iters_out, nan_rows_out);
+}
+int vaqhip_internal_fit_codebooks_timing_on(void) { return g_cb_timing; }
+
 int vaqhip_fit_codebooks_set_timing(int on) {
   g_cb_timing = on != 0;
   return VAQHIP_OK;

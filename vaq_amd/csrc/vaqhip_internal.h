@@ -83,6 +83,19 @@ int vaqhip_internal_fast_ok(vaqhip_index *ix);
 int vaqhip_internal_learn_sample_device(vaqhip_index *ix, const float *d_rows, int sample, int projected,
                                         float gather_ms, float *offsets_out, float *scale_out);
 
+
+/* The sharded codebook fit (vaqhip_multi_codebooks.cpp) over the single fit's host side (vaqhip_codebooks.cpp).
+ * Every refusal of vaqhip_fit_codebooks that needs no device, with its code and text (vaqhip_last_error). */
+int vaqhip_internal_fit_codebooks_check(const void *X, int64_t n, int D, int M, const int *bits, int max_iter,
+                                        const void *centroids_out);
+/* vaqhip_fit_codebooks[_u8] from the upload on, over n x D rows resident on `device` (elem: 4 float, 1 byte); eigvec
+ * and the outputs are the host's.  What vaqhip_refiner_fit_codebooks runs: a multi refiner of one shard is that. */
+int vaqhip_internal_fit_codebooks_rows_device(int device, const void *d_X, int elem, int64_t n, int D, int M,
+                                              const int *bits, const float *eigvec, int max_iter, float *centroids_out,
+                                              int *iters_out, int *nan_rows_out);
+/* 1 when vaqhip_fit_codebooks_set_timing(1) holds for the calling thread */
+int vaqhip_internal_fit_codebooks_timing_on(void);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,7 +2,8 @@
 // geometry of the search in flight, the error hand-over, the grow path of a phase's buffers and the two loops over
 // shards.  Private to vaqhip_multi.cpp (life cycle, codes, setters), vaqhip_multi_search.cpp (the search),
 // vaqhip_multi_kmeans.cpp (the k-means of clusterTI), vaqhip_multi_encode.cpp (the encode across the shards),
-// vaqhip_multi_lutfit.cpp (the sharded quantile fit: the error hand-over and on_shards over a call of its own) and,
+// vaqhip_multi_lutfit.cpp and vaqhip_multi_codebooks.cpp (the sharded quantile and codebook fits: the error hand-over
+// and on_shards over a call of their own) and,
 // through vaqhip_multi_refiner.h, the refiner over sharded raw rows (vaqhip_multi_refiner.cpp,
 // vaqhip_multi_refiner_search.cpp), which takes the error hand-over, the grow path and on_shards from here; they see a
 // shard's index through include/vaqhip.h and vaqhip_internal.h only.

@@ -988,6 +988,13 @@ class VaqMultiRefiner:
         return _fit_quantiles_call(self.D, bits, eigvec, lambda L, b, e, c, q: L.vaqhip_multi_refiner_lut_fit_quantiles(
             self._h, b, e, c, q))
 
+    def fit_codebooks(self, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25):
+        """vaqhip_multi_refiner_fit_codebooks: fit_codebooks() over the RAW rows resident on the shards, float or byte,
+        read in place; subspace s is fitted on shard s % G from the columns the shards send it.  Returns what
+        fit_codebooks returns, bit for bit the single fit's over all rows."""
+        return _fit_codebooks_call(self.D, M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn:
+                                   L.vaqhip_multi_refiner_fit_codebooks(self._h, int(M), b, e, it, c, i, nn), multi=True)
+
     def last_search_timing(self) -> dict:
         """Figures of the last search (times only under set_option("timing", 1)): the slowest shard's select, merge and
         link, the gather, the cross-shard merge, the flag step and the chain on the first device."""
@@ -1016,8 +1023,9 @@ class VaqMultiRefiner:
             pass
 
 
-def _fit_codebooks_call(D: int, M: int, bits, eigvec, max_iter: int, call):
-    """The arrays around a vaqhip_*fit_codebooks call: ([M centre matrices k_s x L], iterations[M], nan_rows[M])."""
+def _fit_codebooks_call(D: int, M: int, bits, eigvec, max_iter: int, call, multi: bool = False):
+    """The arrays around a vaqhip_*fit_codebooks call: ([M centre matrices k_s x L], iterations[M], nan_rows[M]).
+    multi: a sharded call, whose error text is vaqhip_multi_last_error's."""
     bits = [int(b) for b in bits]
     M = int(M)
     if M < 1 or len(bits) != M or D % M != 0:
@@ -1032,29 +1040,44 @@ def _fit_codebooks_call(D: int, M: int, bits, eigvec, max_iter: int, call):
     cent = np.empty(max(sum(ks) * L_, 1), np.float32)
     iters = np.zeros(M, np.int32)
     nan_rows = np.zeros(M, np.int32)
-    _lib.check(call(_lib.load(), (C.c_int * M)(*bits), _ptr(eig) if eig is not None else None, int(max_iter), _ptr(cent),
-                    _ptr(iters), _ptr(nan_rows)))
+    (_lib.check_multi if multi else _lib.check)(call(_lib.load(), (C.c_int * M)(*bits), _ptr(eig) if eig is not None else None,
+                                                     int(max_iter), _ptr(cent), _ptr(iters), _ptr(nan_rows)))
     offs = np.concatenate([[0], np.cumsum(ks)]) * L_
     return [cent[offs[s]:offs[s + 1]].reshape(ks[s], L_).copy() for s in range(M)], iters, nan_rows
 
 
-def fit_codebooks(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25, device: int = 0):
+def _fit_codebooks_sharded(fn_name: str, devices, X, M, bits, eigvec, max_iter):
+    devs = [int(d) for d in devices]
+    arr = (C.c_int * max(len(devs), 1))(*devs)
+    return _fit_codebooks_call(X.shape[1], M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn: getattr(L, fn_name)(
+        len(devs), arr, _ptr(X), X.shape[0], X.shape[1], int(M), b, e, it, c, i, nn), multi=True)
+
+
+def fit_codebooks(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25, device: int = 0,
+                  devices: Optional[Sequence[int]] = None):
     """vaqhip_fit_codebooks: the subspace codebooks mCentroidsPerSubs by KMeans::staticFitSampling (the call of
     VAQ.cpp:644-649; not the arma::kmeans call VAQ::train runs today), every subspace fitted on the device, bit for
     bit the reference's.  X: n x D rows (unprojected when eigvec is given, else in PCA space); bits[M].  Returns
-    ([M arrays (1 << bits[s]) x L], iterations[M], nan_rows[M])."""
+    ([M arrays (1 << bits[s]) x L], iterations[M], nan_rows[M]).  devices=[...]: the same result from the sharded fit
+    (vaqhip_multi_fit_codebooks): the rows are cut over the devices, subspace s is fitted on devices[s % G] and no
+    device holds all rows; a device named several times gives logical shards on that GPU."""
     X = np.ascontiguousarray(X, dtype=np.float32)
     if X.ndim != 2:
         raise _lib.VaqHipError(-1, f"X {X.shape} is not n x D")
+    if devices is not None:
+        return _fit_codebooks_sharded("vaqhip_multi_fit_codebooks", devices, X, M, bits, eigvec, max_iter)
     return _fit_codebooks_call(X.shape[1], M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn: L.vaqhip_fit_codebooks(
         int(device), _ptr(X), X.shape[0], X.shape[1], int(M), b, e, it, c, i, nn))
 
 
-def fit_codebooks_u8(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25, device: int = 0):
-    """fit_codebooks from byte rows (vaqhip_fit_codebooks_u8): the result is fit_codebooks's on X.astype(float32), bit
-    for bit.  Anything but a contiguous uint8 n x D array is EINVAL."""
+def fit_codebooks_u8(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25, device: int = 0,
+                     devices: Optional[Sequence[int]] = None):
+    """fit_codebooks from byte rows (vaqhip_fit_codebooks_u8, or vaqhip_multi_fit_codebooks_u8 with devices): the result
+    is fit_codebooks's on X.astype(float32), bit for bit.  Anything but a contiguous uint8 n x D array is EINVAL."""
     X = np.asarray(X)
     X = _u8_rows(X, X.shape[1] if X.ndim == 2 else 0)
+    if devices is not None:
+        return _fit_codebooks_sharded("vaqhip_multi_fit_codebooks_u8", devices, X, M, bits, eigvec, max_iter)
     return _fit_codebooks_call(X.shape[1], M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn: L.vaqhip_fit_codebooks_u8(
         int(device), _ptr(X), X.shape[0], X.shape[1], int(M), b, e, it, c, i, nn))
 
@@ -1069,6 +1092,16 @@ def last_fit_codebooks_timing() -> dict:
     t = _lib.FitCodebooksTiming()
     _lib.check(_lib.load().vaqhip_last_fit_codebooks_timing(C.byref(t)))
     return {f: getattr(t, f) for f, _ in _lib.FitCodebooksTiming._fields_}
+
+
+def last_multi_fit_codebooks_timing() -> dict:
+    """Figures of the calling thread's last sharded codebook fit (vaqhip_multi_last_fit_codebooks_timing); the owners'
+    assign / accumulate / update times only under fit_codebooks_timing(True)."""
+    t = _lib.MultiFitCodebooksTiming()
+    _lib.check_multi(_lib.load().vaqhip_multi_last_fit_codebooks_timing(C.byref(t)))
+    d = {f: getattr(t, f) for f, _ in _lib.MultiFitCodebooksTiming._fields_ if f != "owner_subspaces"}
+    d["owner_subspaces"] = list(t.owner_subspaces)[:t.n_devices]
+    return d
 
 
 def _fit_quantiles_call(D: int, bits, eigvec, call):
