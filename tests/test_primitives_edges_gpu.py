@@ -217,7 +217,7 @@ def test_encode_row_tile_edges(vaqlib, oracle, n):
 
 
 def test_encode_chunk_loop_past_2_pow_20_rows(vaqlib, oracle):
-    """encode_device_locked cuts the rows in chunks of 2^20 and offsets the output by r * M codes:
+    """encode_rows_locked cuts the rows in chunks of 2^20 and offsets the output by r * M codes:
     2^20 + 3 rows through the device form (the host form cuts its staging in the same chunks).  M = 2
     is no multiple of 4, which only the sequential-sum index admits; the encoder is the same kernel."""
     n = (1 << 20) + 3
@@ -234,6 +234,44 @@ def test_encode_chunk_loop_past_2_pow_20_rows(vaqlib, oracle):
         assert bad.size == 0, f"{name} form: {bad.size} rows differ, first {bad[:5]}; rows 2^20-1, 2^20, 2^20+2: {edge}"
     sub = np.r_[0:2048, (1 << 20) - 1024:n]
     assert_encoder_guard(Xp[sub], cents, dev[sub], L)
+
+
+def test_encode_u8_and_lut_chunk_loop_past_2_pow_20_rows(vaqlib):
+    """The same chunk loop (one driver, encode_rows_locked, for both rules) under byte rows and under
+    encodeToLUTCode's rule: 2^20 + 3 byte rows through vaqhip_encode_lut_u8[_device] and vaqhip_encode_u8[_device]
+    on a sequential-sum index with D = M = 2, bits [4, 4] and the quantiles of the first 4096 rows.  Expected: the
+    float calls on X.astype(float32) in two calls cut at row 600 000, so that neither reaches a chunk boundary
+    (other tests tie those to the reference at small n)."""
+    import torch
+    n, cut = (1 << 20) + 3, 600_000
+    X = np.random.default_rng(21).integers(0, 256, size=(n, 2), dtype=np.uint8)
+    Xf = X.astype(np.float32)
+    v = plain_index([4, 4], [], seq=True)
+    v.fitQuantiles(Xf[:4096])
+    d_X = torch.from_numpy(X).cuda()
+
+    def two_calls(encode):
+        parts = []
+        for part in (Xf[:cut], Xf[cut:]):
+            encode(part)
+            parts.append(np.array(v.mCodebook))
+        return np.concatenate(parts)
+
+    def host_form(encode_u8):
+        encode_u8(X)
+        return np.array(v.mCodebook)
+
+    cases = [("encode_lut_u8", two_calls(v.encodeLUT), host_form(v.encodeLUT_u8),
+              v.encodeLUT_u8_device(d_X).cpu().numpy().view(np.uint16)),
+             ("encode_u8", two_calls(v.encode), host_form(v.encode_u8),
+              v.encode_u8_device(d_X).cpu().numpy().view(np.uint16))]
+    for what, want, host, dev in cases:
+        assert want.shape == (n, 2) and want.max() <= 15 and np.unique(want).size == 16
+        for name, got in (("host", host), ("device", dev)):
+            bad = np.nonzero((got != want).any(axis=1))[0]
+            edge = {r: (got[r].tolist(), want[r].tolist()) for r in ((1 << 20) - 1, 1 << 20, (1 << 20) + 2)}
+            assert bad.size == 0, (f"{what}, {name} form: {bad.size} rows differ, first {bad[:5]}; "
+                                   f"rows 2^20-1, 2^20, 2^20+2: {edge}")
 
 
 def test_encode_codebooks_up_to_32768_entries(vaqlib, oracle):

@@ -24,6 +24,89 @@ int vaqhost::fail(int code, const char *fmt, ...) {
   return code;
 }
 
+// ---- rows of either element type to codes: one driver, two rules (vaqhip_index.h) ----
+namespace vaqhost {
+// VAQ::encode.  (BitVecEngine::queryLUT projects with checking, BitVecEngine.hpp:1226: non-finite coordinates -> 0,
+//  which needs a pass over the queries even without a rotation)
+static bool vaq_projects(const vaqhip_index *ix) { return ix->has_eig || ix->seq; }
+static hipError_t vaq_launch(const vaqhip_index *ix, const float *xp, int64_t m, uint16_t *d_codes, hipStream_t st) {
+  return vaq::launch_encode(xp, m, ix->D, ix->M, ix->L, ix->d_sub.as<vaq::SubDesc>(), ix->d_cent.as<float>(), d_codes, st);
+}
+// encodeToLUTCode.  The projection is unchecked (:620); without a rotation the rows are their own image
+static bool lut_projects(const vaqhip_index *ix) { return ix->has_eig; }
+static hipError_t lut_launch(const vaqhip_index *ix, const float *xp, int64_t m, uint16_t *d_codes, hipStream_t st) {
+  return vaq::launch_lut_encode(xp, m, ix->D, ix->sub.data(), ix->d_sub.as<vaq::SubDesc>(), ix->d_lut_pm.as<float>(),
+                                ix->d_cent.as<float>(), d_codes, ix->n_cu, st);
+}
+// (functions, not constants: this file is compiled as HIP, where a constant object is emitted for the device too)
+EncodeRule encode_rule_vaq() { return {false, vaq_projects, vaq_launch}; }
+EncodeRule encode_rule_lut() { return {true, lut_projects, lut_launch}; }
+
+int check_encode_args(const vaqhip_index *ix, const EncodeRule &rule, const void *X, int64_t n, const void *codes) {
+  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
+  if (n < 0 || (n > 0 && (!X || !codes))) return fail(VAQHIP_EINVAL, "bad arguments");
+  if (rule.lut && ix->lut_q.empty()) return fail(VAQHIP_ESTATE, "vaqhip_encode_lut needs vaqhip_index_set_lut_quantiles first");
+  return VAQHIP_OK;
+}
+
+// core of vaqhip_encode*: caller holds ix->mu and has the device current.  d_X: float or byte rows.  Byte rows are
+// widened by the projection's own load; where no projection runs, by launch_widen_rows_u8 into the buffer the
+// projection would have written
+int encode_rows_locked(vaqhip_index *ix, const EncodeRule &rule, vaq::RowsRef d_X, int64_t n, int projected,
+                       uint16_t *d_codes, hipStream_t st) {
+  const bool do_project = !projected && rule.project(ix);
+  const bool widen = !do_project && d_X.elem == 1;
+  const int64_t chunk = std::min<int64_t>(n, 1 << 20);
+  if (do_project || widen) HIP_TRY(ix->w_qproj.ensure((size_t)chunk * ix->D * sizeof(float)));
+  WS_SCOPE(ws, ix, st);
+  for (int64_t r = 0; r < n; r += chunk) {
+    const int64_t m = std::min(chunk, n - r);
+    const vaq::RowsRef x = vaq::rows_at(d_X, (size_t)r * ix->D);
+    const float *xp = static_cast<const float *>(x.p);
+    if (do_project) {
+      HIP_TRY(vaq::launch_project(x, m, ix->D, ix->d_eig.as<float>(), ix->w_qproj.as<float>(), st, 0));
+      xp = ix->w_qproj.as<float>();
+    } else if (widen) {
+      HIP_TRY(vaq::launch_widen_rows_u8(static_cast<const uint8_t *>(x.p), m * ix->D, ix->w_qproj.as<float>(), st));
+      xp = ix->w_qproj.as<float>();
+    }
+    HIP_TRY(rule.launch(ix, xp, m, d_codes + r * ix->M, st));
+  }
+  return ws.finish();
+}
+
+int encode_device_entry(vaqhip_index *ix, const EncodeRule &rule, vaq::RowsRef d_X, int64_t n, int projected,
+                        uint16_t *d_codes, void *stream) {
+  if (int rc = check_encode_args(ix, rule, d_X.p, n, d_codes)) return rc;
+  if (n == 0) return VAQHIP_OK;
+  ENTRY(ix);
+  return encode_rows_locked(ix, rule, d_X, n, projected, d_codes, static_cast<hipStream_t>(stream));
+}
+
+// X: host rows of X.elem bytes per element; the staging buffer is sized in bytes
+int encode_host_entry(vaqhip_index *ix, const EncodeRule &rule, vaq::RowsRef X, int64_t n, int projected, uint16_t *codes) {
+  if (int rc = check_encode_args(ix, rule, X.p, n, codes)) return rc;
+  if (n == 0) return VAQHIP_OK;
+  const int64_t chunk = std::min<int64_t>(n, 1 << 20);
+  // the staging buffers (w_q, w_stage) are the index's: hold its lock across upload, encode and
+  // download, as search_host does
+  ENTRY(ix);
+  HIP_TRY(ix->w_q.ensure((size_t)chunk * ix->D * (size_t)X.elem));
+  HIP_TRY(ix->w_stage.ensure((size_t)chunk * ix->M * sizeof(uint16_t)));
+  WS_SCOPE(ws, ix, ix->stream);  // (w_q may still be read by a search on another stream)
+  for (int64_t r = 0; r < n; r += chunk) {
+    const int64_t m = std::min(chunk, n - r);
+    HIP_TRY(hipMemcpyAsync(ix->w_q.p, vaq::rows_at(X, (size_t)r * ix->D).p, (size_t)m * ix->D * (size_t)X.elem,
+                           hipMemcpyHostToDevice, ix->stream));
+    if (int rc = encode_rows_locked(ix, rule, vaq::RowsRef{ix->w_q.p, X.elem}, m, projected, ix->w_stage.as<uint16_t>(), ix->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(codes + r * ix->M, ix->w_stage.p, (size_t)m * ix->M * sizeof(uint16_t),
+                           hipMemcpyDeviceToHost, ix->stream));
+    HIP_TRY(hipStreamSynchronize(ix->stream));
+  }
+  return ws.finish();
+}
+}  // namespace vaqhost
+
 extern "C" {
 const char *vaqhip_last_error(void) { return g_err.c_str(); }
 int vaqhip_version(void) { return VAQHIP_VERSION; }
@@ -245,81 +328,19 @@ int vaqhip_merge_topk_strided_device(int device_id, const float *d_dist_lists,
   return VAQHIP_OK;
 }
 
-// core of vaqhip_encode*: caller holds ix->mu and has the device current.  d_X: float or byte rows.  Byte rows are
-// widened by the projection's own load; where no projection runs, by launch_widen_rows_u8 into the buffer the
-// projection would have written
-static int encode_device_locked(vaqhip_index *ix, vaq::RowsRef d_X, int64_t n, int projected, uint16_t *d_codes,
-                                hipStream_t st) {
-  // (BitVecEngine::queryLUT projects with checking, BitVecEngine.hpp:1226: non-finite coordinates -> 0,
-  //  which needs a pass over the queries even without a rotation)
-  const bool do_project = !projected && (ix->has_eig || ix->seq);
-  const bool widen = !do_project && d_X.elem == 1;
-  const int64_t chunk = std::min<int64_t>(n, 1 << 20);
-  if (do_project || widen) HIP_TRY(ix->w_qproj.ensure((size_t)chunk * ix->D * sizeof(float)));
-  WS_SCOPE(ws, ix, st);
-  for (int64_t r = 0; r < n; r += chunk) {
-    const int64_t m = std::min(chunk, n - r);
-    const vaq::RowsRef x = vaq::rows_at(d_X, (size_t)r * ix->D);
-    const float *xp = static_cast<const float *>(x.p);
-    if (do_project) {
-      HIP_TRY(vaq::launch_project(x, m, ix->D, ix->d_eig.as<float>(), ix->w_qproj.as<float>(), st));
-      xp = ix->w_qproj.as<float>();
-    } else if (widen) {
-      HIP_TRY(vaq::launch_widen_rows_u8(static_cast<const uint8_t *>(x.p), m * ix->D, ix->w_qproj.as<float>(), st));
-      xp = ix->w_qproj.as<float>();
-    }
-    HIP_TRY(vaq::launch_encode(xp, m, ix->D, ix->M, ix->L, ix->d_sub.as<vaq::SubDesc>(),
-                               ix->d_cent.as<float>(), d_codes + r * ix->M, st));
-  }
-  return ws.finish();
-}
-
-static int encode_device_entry(vaqhip_index *ix, vaq::RowsRef d_X, int64_t n, int projected, uint16_t *d_codes,
-                               void *stream) {
-  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
-  if (n < 0 || (n > 0 && (!d_X.p || !d_codes))) return fail(VAQHIP_EINVAL, "bad arguments");
-  if (n == 0) return VAQHIP_OK;
-  ENTRY(ix);
-  return encode_device_locked(ix, d_X, n, projected, d_codes, static_cast<hipStream_t>(stream));
-}
-
-// X: host rows of X.elem bytes per element; the staging buffer is sized in bytes
-static int encode_host_entry(vaqhip_index *ix, vaq::RowsRef X, int64_t n, int projected, uint16_t *codes) {
-  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
-  if (n < 0 || (n > 0 && (!X.p || !codes))) return fail(VAQHIP_EINVAL, "bad arguments");
-  if (n == 0) return VAQHIP_OK;
-  const int64_t chunk = std::min<int64_t>(n, 1 << 20);
-  // the staging buffers (w_q, w_stage) are the index's: hold its lock across upload, encode and
-  // download, as search_host does
-  ENTRY(ix);
-  HIP_TRY(ix->w_q.ensure((size_t)chunk * ix->D * (size_t)X.elem));
-  HIP_TRY(ix->w_stage.ensure((size_t)chunk * ix->M * sizeof(uint16_t)));
-  WS_SCOPE(ws, ix, ix->stream);  // (w_q may still be read by a search on another stream)
-  for (int64_t r = 0; r < n; r += chunk) {
-    const int64_t m = std::min(chunk, n - r);
-    HIP_TRY(hipMemcpyAsync(ix->w_q.p, vaq::rows_at(X, (size_t)r * ix->D).p, (size_t)m * ix->D * (size_t)X.elem,
-                           hipMemcpyHostToDevice, ix->stream));
-    if (int rc = encode_device_locked(ix, vaq::RowsRef{ix->w_q.p, X.elem}, m, projected, ix->w_stage.as<uint16_t>(), ix->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(codes + r * ix->M, ix->w_stage.p, (size_t)m * ix->M * sizeof(uint16_t),
-                           hipMemcpyDeviceToHost, ix->stream));
-    HIP_TRY(hipStreamSynchronize(ix->stream));
-  }
-  return ws.finish();
-}
-
 int vaqhip_encode_device(vaqhip_index *ix, const float *d_X, int64_t n, int projected,
                          uint16_t *d_codes, void *stream) {
-  return encode_device_entry(ix, vaq::RowsRef{d_X, 4}, n, projected, d_codes, stream);
+  return encode_device_entry(ix, encode_rule_vaq(), vaq::RowsRef{d_X, 4}, n, projected, d_codes, stream);
 }
 int vaqhip_encode_u8_device(vaqhip_index *ix, const uint8_t *d_X, int64_t n, int projected,
                             uint16_t *d_codes, void *stream) {
-  return encode_device_entry(ix, vaq::RowsRef{d_X, 1}, n, projected, d_codes, stream);
+  return encode_device_entry(ix, encode_rule_vaq(), vaq::RowsRef{d_X, 1}, n, projected, d_codes, stream);
 }
 int vaqhip_encode(vaqhip_index *ix, const float *X, int64_t n, int projected, uint16_t *codes) {
-  return encode_host_entry(ix, vaq::RowsRef{X, 4}, n, projected, codes);
+  return encode_host_entry(ix, encode_rule_vaq(), vaq::RowsRef{X, 4}, n, projected, codes);
 }
 int vaqhip_encode_u8(vaqhip_index *ix, const uint8_t *X, int64_t n, int projected, uint16_t *codes) {
-  return encode_host_entry(ix, vaq::RowsRef{X, 1}, n, projected, codes);
+  return encode_host_entry(ix, encode_rule_vaq(), vaq::RowsRef{X, 1}, n, projected, codes);
 }
 
 int vaqhip_refine_device(int device_id, const float *d_queries, int nq, int D, const float *d_dataset,

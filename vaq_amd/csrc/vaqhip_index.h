@@ -1,7 +1,8 @@
 // vaqhip_index.h -- what the host files of the single-device index share: the index itself, its device
 // buffers (vaqhip_dev.h), the entry preamble, the workspace scope, the launch plan and the few functions
-// that cross files.  Private to vaqhip_api.cpp,
-// vaqhip_plan.cpp, vaqhip_search.cpp, vaqhip_codes.cpp, vaqhip_fast.cpp and vaqhip_lutfit.cpp (vaqhip_refiner.cpp takes
+// that cross files -- among them the one encode driver (EncodeRule, encode_rows_locked and its two entries: defined in
+// vaqhip_api.cpp, called there for vaqhip_encode* and from vaqhip_lutfit.cpp for vaqhip_encode_lut*).  Private to
+// vaqhip_api.cpp, vaqhip_plan.cpp, vaqhip_search.cpp, vaqhip_codes.cpp, vaqhip_fast.cpp and vaqhip_lutfit.cpp (vaqhip_refiner.cpp takes
 // fail(), HIP_TRY and the device types from here and reaches the index through include/vaqhip.h): the multi-device host
 // (vaqhip_multi*.cpp) sees the index through include/vaqhip.h and vaqhip_internal.h only.
 #ifndef VAQHIP_INDEX_H
@@ -171,6 +172,23 @@ void fast_release(vaqhip_index *ix);
 int fast_codes_update(vaqhip_index *ix, const uint16_t *d_u16, int64_t row_begin, int64_t row_end, hipStream_t st);
 // vaqhip_index_set_lut_quantization with the index locked and its device current
 int set_quantization_locked(vaqhip_index *ix, const float *off, const float *scale);
+// vaqhip_api.cpp: rows of either element type to codes -- the one driver behind vaqhip_encode* (encode_rule_vaq) and
+// vaqhip_encode_lut* (encode_rule_lut, entries in vaqhip_lutfit.cpp).  A rule says what differs between the two
+struct EncodeRule {
+  bool lut;                                  // encodeToLUTCode: ESTATE without quantiles (before the n == 0 return)
+  bool (*project)(const vaqhip_index *ix);   // do unprojected rows need launch_project?
+  hipError_t (*launch)(const vaqhip_index *ix, const float *xp, int64_t m, uint16_t *d_codes, hipStream_t st);
+};
+EncodeRule encode_rule_vaq();
+EncodeRule encode_rule_lut();
+// the refusals both entries start with: null index, bad arguments, the rule's own; n == 0 passes
+int check_encode_args(const vaqhip_index *ix, const EncodeRule &rule, const void *X, int64_t n, const void *codes);
+// the chunk loop, on `st`: caller holds ix->mu and has the device current
+int encode_rows_locked(vaqhip_index *ix, const EncodeRule &rule, vaq::RowsRef d_X, int64_t n, int projected,
+                       uint16_t *d_codes, hipStream_t st);
+int encode_device_entry(vaqhip_index *ix, const EncodeRule &rule, vaq::RowsRef d_X, int64_t n, int projected,
+                        uint16_t *d_codes, void *stream);
+int encode_host_entry(vaqhip_index *ix, const EncodeRule &rule, vaq::RowsRef X, int64_t n, int projected, uint16_t *codes);
 // vaqhip_learn.cpp: vaqhip_learn_quantization[_u8]_device's body, which vaqhip_refiner.cpp calls over its resident
 // rows (n x D on the index's device, complete); takes the index's lock itself
 int learn_rows_device(vaqhip_index *ix, vaq::RowsRef d_X, int64_t n, int projected, float ratio, float *offsets_out,

@@ -1,6 +1,6 @@
 // vaqhip_lutfit.cpp -- host side of building a queryLUT index (BitVecEngine::binaryEncodingLUT from the bit
-// allocation on): vaqhip_lut_fit_quantiles*, vaqhip_index_set_lut_quantiles, vaqhip_encode_lut*.  Kernels in
-// vaq_lutfit.hip, arithmetic in vaq_lutfit.h.
+// allocation on): vaqhip_lut_fit_quantiles*, vaqhip_index_set_lut_quantiles, and the vaqhip_encode_lut* entries, which
+// run vaqhip_api.cpp's encode driver under encode_rule_lut().  Kernels in vaq_lutfit.hip, arithmetic in vaq_lutfit.h.
 #include "vaqhip_index.h"
 
 #include <chrono>
@@ -67,38 +67,6 @@ int fit_core(vaq::RowsRef d_X, int64_t n, int D, const int *bits, const float *d
   return VAQHIP_OK;
 }
 
-int check_encode_args(const vaqhip_index *ix, const void *X, int64_t n, const void *codes) {
-  if (!ix) return fail(VAQHIP_EINVAL, "index is null");
-  if (n < 0 || (n > 0 && (!X || !codes))) return fail(VAQHIP_EINVAL, "bad arguments");
-  if (ix->lut_q.empty()) return fail(VAQHIP_ESTATE, "vaqhip_encode_lut needs vaqhip_index_set_lut_quantiles first");
-  return VAQHIP_OK;
-}
-
-// core of vaqhip_encode_lut*: caller holds ix->mu and has the device current.  d_X: float or byte rows; byte rows are
-// widened by the projection's own load, or without a projection by launch_widen_rows_u8 into the projection's buffer
-int encode_lut_locked(vaqhip_index *ix, vaq::RowsRef d_X, int64_t n, int projected, uint16_t *d_codes, hipStream_t st) {
-  const bool do_project = !projected && ix->has_eig;  // unchecked (:620); without a rotation the rows are their own image
-  const bool widen = !do_project && d_X.elem == 1;
-  const int64_t chunk = std::min<int64_t>(n, 1 << 20);
-  if (do_project || widen) HIP_TRY(ix->w_qproj.ensure((size_t)chunk * ix->D * sizeof(float)));
-  WS_SCOPE(ws, ix, st);
-  for (int64_t r = 0; r < n; r += chunk) {
-    const int64_t m = std::min(chunk, n - r);
-    const vaq::RowsRef x = vaq::rows_at(d_X, (size_t)r * ix->D);
-    const float *xp = static_cast<const float *>(x.p);
-    if (do_project) {
-      HIP_TRY(vaq::launch_project(x, m, ix->D, ix->d_eig.as<float>(), ix->w_qproj.as<float>(), st, 0));
-      xp = ix->w_qproj.as<float>();
-    } else if (widen) {
-      HIP_TRY(vaq::launch_widen_rows_u8(static_cast<const uint8_t *>(x.p), m * ix->D, ix->w_qproj.as<float>(), st));
-      xp = ix->w_qproj.as<float>();
-    }
-    HIP_TRY(vaq::launch_lut_encode(xp, m, ix->D, ix->sub.data(), ix->d_sub.as<vaq::SubDesc>(), ix->d_lut_pm.as<float>(),
-                                   ix->d_cent.as<float>(), d_codes + r * ix->M, ix->n_cu, st));
-  }
-  return ws.finish();
-}
-
 int fit_device_entry(int device_id, vaq::RowsRef d_X, int64_t n, int D, const int *bits, const float *d_eigvec,
                      float *d_centroids_out, float *d_quantiles_out, void *stream) {
   if (int rc = check_fit_args(n, D, bits, d_X.p, d_centroids_out, d_quantiles_out)) return rc;
@@ -136,33 +104,6 @@ int fit_host_entry(int device_id, vaq::RowsRef X, int64_t n, int D, const int *b
   HIP_TRY(hipMemcpy(centroids_out, d_cent.p, cent_bytes, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(quantiles_out, d_q.p, q_bytes, hipMemcpyDeviceToHost));
   return VAQHIP_OK;
-}
-
-int encode_lut_device_entry(vaqhip_index *ix, vaq::RowsRef d_X, int64_t n, int projected, uint16_t *d_codes, void *stream) {
-  if (int rc = check_encode_args(ix, d_X.p, n, d_codes)) return rc;
-  if (n == 0) return VAQHIP_OK;
-  ENTRY(ix);
-  return encode_lut_locked(ix, d_X, n, projected, d_codes, static_cast<hipStream_t>(stream));
-}
-
-int encode_lut_host_entry(vaqhip_index *ix, vaq::RowsRef X, int64_t n, int projected, uint16_t *codes) {
-  if (int rc = check_encode_args(ix, X.p, n, codes)) return rc;
-  if (n == 0) return VAQHIP_OK;
-  const int64_t chunk = std::min<int64_t>(n, 1 << 20);
-  ENTRY(ix);
-  HIP_TRY(ix->w_q.ensure((size_t)chunk * ix->D * (size_t)X.elem));
-  HIP_TRY(ix->w_stage.ensure((size_t)chunk * ix->M * sizeof(uint16_t)));
-  WS_SCOPE(ws, ix, ix->stream);
-  for (int64_t r = 0; r < n; r += chunk) {
-    const int64_t m = std::min(chunk, n - r);
-    HIP_TRY(hipMemcpyAsync(ix->w_q.p, vaq::rows_at(X, (size_t)r * ix->D).p, (size_t)m * ix->D * (size_t)X.elem,
-                           hipMemcpyHostToDevice, ix->stream));
-    if (int rc = encode_lut_locked(ix, vaq::RowsRef{ix->w_q.p, X.elem}, m, projected, ix->w_stage.as<uint16_t>(), ix->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(codes + r * ix->M, ix->w_stage.p, (size_t)m * ix->M * sizeof(uint16_t),
-                           hipMemcpyDeviceToHost, ix->stream));
-    HIP_TRY(hipStreamSynchronize(ix->stream));
-  }
-  return ws.finish();
 }
 }  // namespace
 
@@ -222,17 +163,17 @@ int vaqhip_index_set_lut_quantiles(vaqhip_index *ix, const float *quantiles) {
 
 int vaqhip_encode_lut_device(vaqhip_index *ix, const float *d_X, int64_t n, int projected, uint16_t *d_codes,
                              void *stream) {
-  return encode_lut_device_entry(ix, vaq::RowsRef{d_X, 4}, n, projected, d_codes, stream);
+  return encode_device_entry(ix, encode_rule_lut(), vaq::RowsRef{d_X, 4}, n, projected, d_codes, stream);
 }
 int vaqhip_encode_lut_u8_device(vaqhip_index *ix, const uint8_t *d_X, int64_t n, int projected, uint16_t *d_codes,
                                 void *stream) {
-  return encode_lut_device_entry(ix, vaq::RowsRef{d_X, 1}, n, projected, d_codes, stream);
+  return encode_device_entry(ix, encode_rule_lut(), vaq::RowsRef{d_X, 1}, n, projected, d_codes, stream);
 }
 int vaqhip_encode_lut(vaqhip_index *ix, const float *X, int64_t n, int projected, uint16_t *codes) {
-  return encode_lut_host_entry(ix, vaq::RowsRef{X, 4}, n, projected, codes);
+  return encode_host_entry(ix, encode_rule_lut(), vaq::RowsRef{X, 4}, n, projected, codes);
 }
 int vaqhip_encode_lut_u8(vaqhip_index *ix, const uint8_t *X, int64_t n, int projected, uint16_t *codes) {
-  return encode_lut_host_entry(ix, vaq::RowsRef{X, 1}, n, projected, codes);
+  return encode_host_entry(ix, encode_rule_lut(), vaq::RowsRef{X, 1}, n, projected, codes);
 }
 
 }  // extern "C"
