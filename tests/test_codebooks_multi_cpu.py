@@ -71,6 +71,23 @@ def test_refusals_touch_no_device(vaqlib):
     assert np.all(cent == SENTINEL) and np.all(iters == -9) and np.all(nan == -9)
 
 
+def test_setup_and_teardown_on_devices_that_do_not_exist(vaqlib):
+    """Valid arguments, so the call-owned run (vaq_amd/csrc/vaqhip_shard_run.h) starts its workers, fails in the first
+    step of every shard's setup and is taken down with no shard opened; twice, so that a teardown which leaves the pool
+    or the thread's state broken shows.  The same on a machine with GPUs: ordinal 977 exists on none."""
+    X = np.zeros((8, 4), np.float32)
+    bits = (C.c_int * 4)(3, 3, 3, 3)
+    devs = (C.c_int * 2)(977, 978)
+    for _ in range(2):
+        cent = np.full(4 * 8, SENTINEL, np.float32)
+        iters = np.full(4, -9, np.int32)
+        nan = np.full(4, -9, np.int32)
+        rc = vaqlib.vaqhip_multi_fit_codebooks(2, devs, _p(X), 8, 4, 4, bits, None, 5, _p(cent), _p(iters), _p(nan))
+        assert rc == -3  # ENODEVICE
+        assert vaqlib.vaqhip_multi_last_error() == b"shard 0 (device 977): hipSetDevice failed (no CPU path)"
+        assert np.all(cent == SENTINEL) and np.all(iters == -9) and np.all(nan == -9)
+
+
 def test_refiner_form_refuses_null(vaqlib):
     cent = np.full(64, SENTINEL, np.float32)
     bits = (C.c_int * 2)(2, 2)

@@ -238,6 +238,27 @@ def test_refusals_leave_the_outputs(vaqlib):
     r.close()
 
 
+def test_a_shard_that_fails_in_setup_takes_the_run_down_cleanly(vaqlib):
+    """[0, 977]: shard 0 opens its stream, uploads its rows and succeeds in setup; shard 1 is refused by hipSetDevice (an
+    error return: ordinal 977 does not exist).  The run's teardown (vaq_amd/csrc/vaqhip_shard_run.h) then has one
+    opened and one unopened shard: ENODEVICE naming shard 1, the outputs untouched, the caller's device as it was, and
+    the next fit of the same rows is the single fit's."""
+    import torch
+    rng = np.random.default_rng(977)
+    X = (rng.normal(size=(64, 4)) * 5).astype(np.float32)
+    M, bits = 4, (1, 2, 3, 4)
+    torch.cuda.set_device(torch.cuda.device_count() - 1)
+    dev = torch.cuda.current_device()
+    got = sharded_fit(vaqlib, [0, 977], X, M, bits)
+    assert got[0] == -3 and vaqlib.vaqhip_multi_last_error().startswith(b"shard 1 (device 977): ")
+    assert all(np.all(c == PATTERN) for c in got[1]) and np.all(got[2] == -9) and np.all(got[3] == -9)
+    assert torch.cuda.current_device() == dev
+    torch.cuda.set_device(0)
+    want = single_fit(vaqlib, X, M, bits)
+    assert want[0] == 0
+    same_fit(sharded_fit(vaqlib, [0, 0], X, M, bits), want, "after the failed setup")
+
+
 def test_python_adapters_and_timing(vaqlib):
     import vaq_amd
     n, D, M, bits, kind, salt = cr.CASES["rotated"]

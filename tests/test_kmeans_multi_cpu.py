@@ -36,6 +36,18 @@ def split_exe(tmp_path_factory):
     return exe
 
 
+def test_nan_rows_header(tmp_path):
+    """vaq::nan_rows (kmeans_sample.h), what every k-means here reports of its centres: tests/cpp/nan_rows_test.cpp,
+    plain and once more under AddressSanitizer + UBSan (host code only, its own main)."""
+    for extra, name in ((["-O2"], "nan_rows_test"),
+                        (["-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "nan_rows_asan")):
+        exe = str(tmp_path / name)
+        subprocess.check_call(["g++", "-std=c++17", "-g", "-Wall", "-I" + os.path.join(ROOT, "vaq_amd", "csrc")] + extra +
+                              [os.path.join(ROOT, "tests", "cpp", "nan_rows_test.cpp"), "-o", exe])
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+        assert r.returncode == 0 and "nan_rows_test: ok" in r.stdout, (r.stdout + r.stderr)[-2000:]
+
+
 # N = 9 over 4 shards (one empty); N = 4001 over 3 after an append of 1001 rows; a sampled case (2560 of 20000)
 @pytest.mark.parametrize("N,T,G,appended", [(9, 4, 4, 0), (4001, 24, 3, 1001), (20000, 10, 5, 0), (20000, 10, 3, 7000)])
 def test_sample_split_over_the_shards(split_exe, N, T, G, appended):

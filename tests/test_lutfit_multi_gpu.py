@@ -163,6 +163,25 @@ def test_fit_refuses_non_finite_values(vaqlib):
     same_bits(cent, lr.fit_ref("n4099_d5")[0], "the fit after the refusals")
 
 
+def test_a_shard_that_fails_in_setup_takes_the_run_down_cleanly(vaqlib):
+    """[0, 977]: shard 0 opens its stream, uploads its rows and succeeds in setup; shard 1 is refused by hipSetDevice (an
+    error return: ordinal 977 does not exist).  The run's teardown (vaq_amd/csrc/vaqhip_shard_run.h) then has one
+    opened and one unopened shard: ENODEVICE naming shard 1, the outputs untouched, the caller's device as it was, and
+    the next fit of the same rows is the single fit's."""
+    import torch
+    rng = np.random.default_rng(977)
+    X = (rng.normal(size=(64, 4)) * 5).astype(np.float32)
+    bits = [3, 8, 1, 5]
+    torch.cuda.set_device(torch.cuda.device_count() - 1)
+    dev = torch.cuda.current_device()
+    rc, cent, Qs = multi_fit(vaqlib, [0, 977], X, bits)
+    assert rc == -3 and vaqlib.vaqhip_multi_last_error().startswith(b"shard 1 (device 977): ")
+    assert np.all(cent == SENTINEL) and np.all(Qs == SENTINEL)
+    assert torch.cuda.current_device() == dev
+    torch.cuda.set_device(0)
+    check_against_single(vaqlib, X, bits, ([0, 0],), what="after the failed setup")
+
+
 def test_fit_refiner_form(vaqlib):
     """set_rows over [0, 0, 0], then add_rows growing the last shard: the cut is the refiner's, the result the single
     fit's over the concatenated rows; with and without eigvec.  A refiner without rows: ESTATE."""

@@ -34,6 +34,7 @@ EXHAUST_HEADER = os.path.join(CSRC, "vaq_exhaust.h")  # the same by one thread, 
 EXHAUST_PLAN_HEADER = os.path.join(CSRC, "vaqhip_exhaust_plan.h")  # the exhaustive form's plan and launches: both refiners
 REFINE_COMMON_HEADER = os.path.join(CSRC, "vaqhip_refine_common.h")  # checks, options, the row store: both refiners
 MULTI_REFINER_HEADER = os.path.join(CSRC, "vaqhip_multi_refiner.h")  # private to the multi refiner's two host files
+SHARD_RUN_HEADER = os.path.join(CSRC, "vaqhip_shard_run.h")  # the call-owned run and its teardown: the sharded builds
 RESTATED_HEADER = os.path.join(CSRC, "vaq_restated.h")  # stdsort, stdheap, refheap, sq_norm_eigen: FAST, TI planning, the replay, k-means, refine
 INTERNAL_HEADER = os.path.join(CSRC, "vaqhip_internal.h")
 INDEX_HEADER = os.path.join(CSRC, "vaqhip_index.h")  # private to the single-index host files
@@ -93,6 +94,8 @@ def _deps(src: str):
         deps += [EXHAUST_PLAN_HEADER, REFINE_COMMON_HEADER]
     if src in MULTI_REFINER_SOURCES or src in (MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE, MULTI_LEARN_SOURCE, MULTI_CODEBOOKS_SOURCE):
         deps.append(MULTI_REFINER_HEADER)
+    if src in (MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE, MULTI_LEARN_SOURCE, MULTI_CODEBOOKS_SOURCE):
+        deps.append(SHARD_RUN_HEADER)
     return deps
 OBJDIR = os.path.join(LIBDIR, "obj")
 # Experiment builds: VAQ_VARIANT=name compiles (with VAQ_EXTRA_FLAGS) into vaq_amd/lib/variants/name/

@@ -1,11 +1,12 @@
 // kmeans_sample.h -- the host arithmetic of the k-means of clusterTI (vaq_kmeans.hip) that both hosts share:
 // which rows KMeans::staticFitCodebook samples, which shard of a multi-device index holds each of them, and
-// which slice of the sample every device assigns.
-// No HIP in here: tests/cpp/kmeans_split_test.cpp runs it on the CPU.
+// which slice of the sample every device assigns; and what every k-means here reports of its centres (nan_rows).
+// No HIP in here: tests/cpp/kmeans_split_test.cpp and tests/cpp/nan_rows_test.cpp run it on the CPU.
 #ifndef VAQ_KMEANS_SAMPLE_H_
 #define VAQ_KMEANS_SAMPLE_H_
 
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <random>
 #include <unordered_map>
@@ -73,6 +74,17 @@ inline void kmeans_assign_slice(int rows, int G, int g, int *begin, int *end) {
   const int64_t per = ((int64_t)rows + G - 1) / G;
   *begin = (int)std::min<int64_t>(rows, (int64_t)g * per);
   *end = (int)std::min<int64_t>(rows, (int64_t)(g + 1) * per);
+}
+
+// rows of the centre matrix m [rows][width] that hold a NaN (a centre no row was assigned to: 0 / 0), each counted once
+inline int nan_rows(const float *m, int rows, int width) {
+  int n = 0;
+  for (int c = 0; c < rows; c++) {
+    bool nan = false;
+    for (int j = 0; j < width; j++) nan |= std::isnan(m[(size_t)c * width + j]);
+    n += nan;
+  }
+  return n;
 }
 
 } // namespace vaq

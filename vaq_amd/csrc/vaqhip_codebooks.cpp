@@ -4,7 +4,6 @@
 #include "vaqhip_index.h"
 
 #include <chrono>
-#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -62,14 +61,8 @@ int fit_core(vaq::RowsRef d_X, int64_t n, int D, const cb::Plan &plan, const flo
   int max_iters = 0;
   for (int s = 0; s < M; s++) {
     const cb::Sub &sd = plan.sub[(size_t)s];
-    int nan_rows = 0;
-    for (int c = 0; c < sd.k; c++) {
-      bool nan = false;
-      for (int j = 0; j < L; j++) nan |= std::isnan(means[(size_t)(sd.cent_off + c) * L + j]);
-      nan_rows += nan;
-    }
     if (iters_out) iters_out[s] = iters[(size_t)s];
-    if (nan_rows_out) nan_rows_out[s] = nan_rows;
+    if (nan_rows_out) nan_rows_out[s] = vaq::nan_rows(means.data() + (size_t)sd.cent_off * L, sd.k, L);
     max_iters = std::max(max_iters, iters[(size_t)s]);
   }
   g_cb_last = vaqhip_fit_codebooks_timing{};
@@ -106,14 +99,10 @@ int fit_to_host(vaq::RowsRef d_X, int64_t n, int D, const cb::Plan &plan, const 
     HIP_TRY(d_eig.ensure((size_t)D * D * sizeof(float)));
     HIP_TRY(hipMemcpy(d_eig.p, eigvec, (size_t)D * D * sizeof(float), hipMemcpyHostToDevice));
   }
-  hipStream_t st = nullptr;
-  HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  struct StreamFree {
-    hipStream_t s;
-    ~StreamFree() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-  } stream_free{st};
+  CallStream st;
+  HIP_TRY(st.open());
   if (int rc = fit_core(d_X, n, D, plan, eigvec ? d_eig.as<float>() : nullptr, max_iter, d_cent.as<float>(), iters_out,
-                        nan_rows_out, st))
+                        nan_rows_out, st.s))
     return rc;
   HIP_TRY(hipMemcpy(centroids_out, d_cent.p, cent_bytes, hipMemcpyDeviceToHost));
   return VAQHIP_OK;

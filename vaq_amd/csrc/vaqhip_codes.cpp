@@ -377,15 +377,9 @@ int vaqhip_index_cluster_ti_kmeans(vaqhip_index *ix, int T, int seg_num, int max
   }
   if (no_centre)
     return fail(VAQHIP_EINVAL, "a row is at a distance >= FLT_MAX (or NaN) from every centre: the reference indexes row -1");
-  int nan_rows = 0;
-  for (int c = 0; c < T; c++) {
-    bool nan = false;
-    for (int j = 0; j < dd; j++) nan |= std::isnan(means[(size_t)c * dd + j]);
-    nan_rows += nan;
-  }
   if (clusters_out) std::memcpy(clusters_out, means.data(), means.size() * sizeof(float));
   if (iters_out) *iters_out = iters;
-  if (nan_rows_out) *nan_rows_out = nan_rows;
+  if (nan_rows_out) *nan_rows_out = vaq::nan_rows(means.data(), T, dd);
   return set_ti_clusters_locked(ix, means.data(), T, seg_num);
 }
 

@@ -71,6 +71,21 @@ struct EventList {
   void release() { destroy_events(e.data(), e.size()); }
 };
 
+// A stream of one call's own: non-blocking, made by open() with the device current, synchronised and destroyed when it
+// leaves scope.  Declared behind what the stream's work reads and writes.
+struct CallStream {
+  hipStream_t s = nullptr;
+  CallStream() = default;
+  CallStream(const CallStream &) = delete;
+  CallStream &operator=(const CallStream &) = delete;
+  hipError_t open() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
+  ~CallStream() {
+    if (!s) return;
+    (void)hipStreamSynchronize(s);
+    (void)hipStreamDestroy(s);
+  }
+};
+
 inline void release_all(std::initializer_list<DevBuf *> bufs) {
   for (DevBuf *b : bufs) b->release();
 }

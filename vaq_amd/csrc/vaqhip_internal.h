@@ -84,6 +84,12 @@ int vaqhip_internal_learn_sample_device(vaqhip_index *ix, const float *d_rows, i
                                         float gather_ms, float *offsets_out, float *scale_out);
 
 
+/* The sharded quantile fit (vaqhip_multi_lutfit.cpp): every refusal of vaqhip_lut_fit_quantiles that needs no device,
+ * with its code and text (vaqhip_last_error).  X: the rows, or any non-null pointer that stands for resident ones. */
+int vaqhip_internal_lut_fit_check(const void *X, int64_t n, int D, const int *bits, const void *centroids_out,
+                                  const void *quantiles_out);
+
+
 /* The sharded codebook fit (vaqhip_multi_codebooks.cpp) over the single fit's host side (vaqhip_codebooks.cpp).
  * Every refusal of vaqhip_fit_codebooks that needs no device, with its code and text (vaqhip_last_error). */
 int vaqhip_internal_fit_codebooks_check(const void *X, int64_t n, int D, int M, const int *bits, int max_iter,

@@ -92,14 +92,10 @@ int fit_host_entry(int device_id, vaq::RowsRef X, int64_t n, int D, const int *b
     HIP_TRY(d_eig.ensure((size_t)D * D * sizeof(float)));
     HIP_TRY(hipMemcpy(d_eig.p, eigvec, (size_t)D * D * sizeof(float), hipMemcpyHostToDevice));
   }
-  hipStream_t st = nullptr;
-  HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-  struct StreamFree {
-    hipStream_t s;
-    ~StreamFree() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-  } stream_free{st};
+  CallStream st;
+  HIP_TRY(st.open());
   if (int rc = fit_core(vaq::RowsRef{d_x.p, X.elem}, n, D, bits, eigvec ? d_eig.as<float>() : nullptr, d_cent.as<float>(),
-                        d_q.as<float>(), st))
+                        d_q.as<float>(), st.s))
     return rc;
   HIP_TRY(hipMemcpy(centroids_out, d_cent.p, cent_bytes, hipMemcpyDeviceToHost));
   HIP_TRY(hipMemcpy(quantiles_out, d_q.p, q_bytes, hipMemcpyDeviceToHost));
@@ -125,6 +121,12 @@ int vaqhip_lut_fit_quantiles(int device_id, const float *X, int64_t n, int D, co
 int vaqhip_lut_fit_quantiles_u8(int device_id, const uint8_t *X, int64_t n, int D, const int *bits, const float *eigvec,
                                 float *centroids_out, float *quantiles_out) {
   return fit_host_entry(device_id, vaq::RowsRef{X, 1}, n, D, bits, eigvec, centroids_out, quantiles_out);
+}
+
+// ---- vaqhip_internal.h: what the sharded fit takes from here ----
+int vaqhip_internal_lut_fit_check(const void *X, int64_t n, int D, const int *bits, const void *centroids_out,
+                                  const void *quantiles_out) {
+  return check_fit_args(n, D, bits, X, centroids_out, quantiles_out);
 }
 
 int vaqhip_lut_fit_set_timing(int on) {

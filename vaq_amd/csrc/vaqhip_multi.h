@@ -1,9 +1,9 @@
 // vaqhip_multi.h -- what the host files of the multi-device index share: the shard, the index with the
-// geometry of the search in flight, the error hand-over, the grow path of a phase's buffers and the two loops over
-// shards.  Private to vaqhip_multi.cpp (life cycle, codes, setters), vaqhip_multi_search.cpp (the search),
-// vaqhip_multi_kmeans.cpp (the k-means of clusterTI), vaqhip_multi_encode.cpp (the encode across the shards),
-// vaqhip_multi_lutfit.cpp and vaqhip_multi_codebooks.cpp (the sharded quantile and codebook fits: the error hand-over
-// and on_shards over a call of their own) and,
+// geometry of the search in flight, the error hand-over, the grow path of a phase's buffers, the two loops over
+// shards and the copy between two shards' devices.  Private to vaqhip_multi.cpp (life cycle, codes, setters),
+// vaqhip_multi_search.cpp (the search), vaqhip_multi_kmeans.cpp (the k-means of clusterTI), the builds across the
+// shards -- vaqhip_multi_encode.cpp, vaqhip_multi_learn.cpp, and vaqhip_multi_lutfit.cpp and vaqhip_multi_codebooks.cpp,
+// whose call-owned run (vaqhip_shard_run.h) is what on_shards works on there -- and,
 // through vaqhip_multi_refiner.h, the refiner over sharded raw rows (vaqhip_multi_refiner.cpp,
 // vaqhip_multi_refiner_search.cpp), which takes the error hand-over, the grow path and on_shards from here; they see a
 // shard's index through include/vaqhip.h and vaqhip_internal.h only.
@@ -181,7 +181,8 @@ struct FitList {
 
 // job(g, shard) on every shard's worker at once.  A job that fails and leaves the shard's text empty says that a
 // single-index call failed: the text is then that call's, taken on the worker's thread.  The first failing shard
-// is reported.  (Owner: vaqhip_multi, or the multi-device refiner -- G, pool and sh[] with device and err.)
+// is reported.  (Owner: vaqhip_multi, the multi-device refiner or a call's ShardRun -- G, pool and sh[] with device and
+// err.)
 template <class Owner, class Job> int on_shards(Owner *mx, Job &&job) {
   const int rc = mx->pool.run([&](int g) -> int {
     auto &s = mx->sh[g];
@@ -193,6 +194,14 @@ template <class Owner, class Job> int on_shards(Owner *mx, Job &&job) {
   for (int g = 0; rc && g < mx->G; g++)
     if (mx->pool.rc(g)) return mfail(mx->pool.rc(g), "shard %d (device %d): %s", g, mx->sh[g].device, mx->sh[g].err.c_str());
   return VAQHIP_OK;
+}
+
+// `bytes` from src on src_device to dst on dst_device, behind `stream`: a plain device-to-device copy where both shards
+// name one GPU, a peer copy otherwise.  (The search and the refiner copy between shards 1.. and the first device with
+// hipMemcpyPeerAsync throughout; that is their own decision.)
+inline hipError_t copy_between(void *dst, int dst_device, const void *src, int src_device, size_t bytes, hipStream_t stream) {
+  if (dst_device == src_device) return hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, stream);
+  return hipMemcpyPeerAsync(dst, dst_device, src, src_device, bytes, stream);
 }
 
 // the code of a single-index call made on the calling thread, with its text when it failed

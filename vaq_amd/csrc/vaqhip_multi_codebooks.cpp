@@ -7,9 +7,9 @@
 //   1 columns  every shard writes, per owner, the packed [rows it contributes][D_w] block of that owner's columns
 //              (launch_codebook_columns: a byte widened where it is loaded, the projection fused as one fmaf chain per
 //              value) -- its rows of the sample, or all of its rows for an owner of a subspace that does not sample
-//   2 copy     every shard sends each block to its owner (hipMemcpyPeerAsync; device-to-device where both shards name
-//              one GPU): a block of all rows to row lo_g of the owner's n x D_w matrix, a sample block to the owner's
-//              staging area behind the blocks of the shards before it
+//   2 copy     every shard sends each block to its owner (copy_between, vaqhip_multi.h): a block of all rows to row
+//              lo_g of the owner's n x D_w matrix, a sample block to the owner's staging area behind the blocks of the
+//              shards before it
 //   3 fit      every owner places the staged rows at their positions in its sample matrix (an owner that holds all rows
 //              gathers the sample of its other subspaces from them instead, as the single fit does) and runs the single
 //              fit from there on, unchanged: vaq::codebooks_lloyd with D = D_w, its sub-plan and no eigvec
@@ -17,13 +17,14 @@
 // stream before it reports, and the caller starts a phase only when every shard has succeeded in the one before, so a
 // failing shard ends the call and an owner never reads a matrix that is still being written.  The outputs are written
 // only when every owner has succeeded and no row was left without a centre.
-// The workers, streams, events and buffers are the call's own: the host form has no handle to keep them in, and the
-// refiner form only reads the refiner's rows (r->mu held; set_rows and add_rows copy synchronously).
+// The workers, streams, events and buffers are the call's own (vaqhip_shard_run.h: the run, the start of a shard's
+// setup and the teardown): the host form has no handle to keep them in, and the refiner form only reads the refiner's
+// rows (r->mu held; set_rows and add_rows copy synchronously).  What is here is the plan, the sample a host form picks,
+// the phases and the outputs.
 // One device (G == 1) is the single fit itself; there is no exchange.
-#include "vaqhip_multi_refiner.h"
+#include "vaqhip_shard_run.h"
 
 #include <chrono>
-#include <cmath>
 #include <cstring>
 
 #include "fit_codebooks_multi_plan.h"
@@ -38,13 +39,9 @@ thread_local vaqhip_multi_fit_codebooks_timing g_cbm_last = {};
 
 enum { PH_COLUMNS, PH_COPY, PH_PLACE, PH_COUNT };
 
-struct CbShard {
-  int device = 0;
-  std::string err;
-  hipStream_t stream = nullptr;
-  vaq::RowsRef d_rows = {nullptr, 4};  // the shard's rows on its device, float or byte: resident, or uploaded (slice)
-  bool picked = false;                 // host form, every subspace samples: d_rows are its sample rows, in sample order
-  DevBuf slice, eig, subs, local, blocks;  // uploaded rows; eigvec; the owners' subspaces [M]; local rows; packed blocks
+struct CbShard : RunShard {
+  bool picked = false;         // host form, every subspace samples: d_rows are its sample rows, in sample order
+  DevBuf subs, local, blocks;  // the owners' subspaces [M]; local rows; packed blocks
   // as an owner: the sample and full matrices, the staging area with its positions, the permutation head an owner of all
   // rows gathers by, the centres
   DevBuf Ps, Pf, stage, pos, perm, means;
@@ -54,34 +51,15 @@ struct CbShard {
   vaq::CodebookPhases ph;
   hipEvent_t t[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // columns start, end, copied; place start, end
   float ms[PH_COUNT] = {0, 0, 0};
+  void release() { release_all({&subs, &local, &blocks, &Ps, &Pf, &stage, &pos, &perm, &means}), destroy_events(t); }
 };
 
-// what on_shards runs over: G, pool, sh[] with device and err
-struct CbRun {
-  int G = 0;
-  std::vector<CbShard> sh;
-  vaq::JobPool pool;
+// the call's run (vaqhip_shard_run.h) with what this fit adds
+struct CbRun : ShardRun<CbShard> {
   cm::Plan plan;
   int D = 0, max_iter = 0;
   int sub_at[VAQHIP_MAX_DEVICES + 1] = {};  // where owner w's subspaces start in the list every shard holds
-  vaq::RowsRef X = {nullptr, 4};            // host form: the call's matrix, float or byte
-  const float *eig = nullptr;               // host pointer or null
   bool timing = false;
-  // by the calling thread, whichever way the call ended: the workers first, then every device's streams and buffers
-  ~CbRun() {
-    pool.stop();
-    // every stream idle before anything is freed: after a failure part-way a later shard's stream may still hold a
-    // copy into an earlier owner's matrices
-    for (CbShard &s : sh)
-      if (s.stream && hipSetDevice(s.device) == hipSuccess) (void)hipStreamSynchronize(s.stream);
-    for (CbShard &s : sh) {
-      if (!s.stream && !s.t[0]) continue;  // (setup_shard makes these two first)
-      if (hipSetDevice(s.device) != hipSuccess) continue;
-      release_all({&s.slice, &s.eig, &s.subs, &s.local, &s.blocks, &s.Ps, &s.Pf, &s.stage, &s.pos, &s.perm, &s.means});
-      destroy_events(s.t);
-      if (s.stream) (void)hipStreamDestroy(s.stream);
-    }
-  }
 };
 
 // (declared behind the host memory a stream copies from: the stream is idle before that memory goes, on every return)
@@ -96,22 +74,17 @@ struct SyncOnLeave {
 // its matrices
 int setup_shard(CbRun &f, int g, CbShard &s) {
   const cm::Plan &p = f.plan;
-  const size_t D = (size_t)f.D;
-  if (hipSetDevice(s.device) != hipSuccess) {
-    s.err = "hipSetDevice failed (no CPU path)";
-    return VAQHIP_ENODEVICE;
-  }
+  const cm::ShardPart &sp = p.shard[(size_t)g];
   std::vector<char> picked_rows;  // the sample rows a host form picks, and
   std::vector<int> list;          //   an owner's positions: the host's until the stream is synchronised
   SyncOnLeave idle_on_return{s.stream};
-  MHIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
+  // every subspace samples: only this slice's rows of the sample go up, in the sample's order
+  s.picked = f.X.p && p.whole.sampled && sp.cnt > 0;
+  if (const int rc = f.open(s, sp.lo, sp.cnt, f.D, !s.picked)) return rc;
   MHIP(ensure_events(s.t));
-  const cm::ShardPart &sp = p.shard[(size_t)g];
   if (sp.cnt > 0) {
-    const size_t row_bytes = D * (size_t)f.X.elem;
-    if (f.X.p && p.whole.sampled) {
-      // every subspace samples: only this slice's rows of the sample go up, in the sample's order
-      s.picked = true;
+    if (s.picked) {
+      const size_t row_bytes = (size_t)f.D * (size_t)f.X.elem;
       picked_rows.resize(std::max<size_t>(sp.local.size() * row_bytes, 1));
       const char *base = static_cast<const char *>(f.X.p) + (size_t)sp.lo * row_bytes;
       for (size_t i = 0; i < sp.local.size(); i++)
@@ -120,15 +93,6 @@ int setup_shard(CbRun &f, int g, CbShard &s) {
       if (!sp.local.empty())
         MHIP(hipMemcpyAsync(s.slice.p, picked_rows.data(), sp.local.size() * row_bytes, hipMemcpyHostToDevice, s.stream));
       s.d_rows = vaq::RowsRef{s.slice.p, f.X.elem};
-    } else if (f.X.p) {
-      const size_t bytes = (size_t)sp.cnt * row_bytes;
-      MHIP(s.slice.ensure(bytes));
-      MHIP(hipMemcpyAsync(s.slice.p, vaq::rows_at(f.X, (size_t)sp.lo * D).p, bytes, hipMemcpyHostToDevice, s.stream));
-      s.d_rows = vaq::RowsRef{s.slice.p, f.X.elem};
-    }
-    if (f.eig) {
-      MHIP(s.eig.ensure(D * D * sizeof(float)));
-      MHIP(hipMemcpyAsync(s.eig.p, f.eig, D * D * sizeof(float), hipMemcpyHostToDevice, s.stream));
     }
     std::vector<int> subs;
     for (const cm::Owner &o : p.owner) subs.insert(subs.end(), o.subs.begin(), o.subs.end());
@@ -191,9 +155,7 @@ int columns_and_copy(CbRun &f, int g, CbShard &s) {
     CbShard &os = f.sh[(size_t)w];
     const float *src = s.blocks.as<float>() + cm::block_at(p, g, w);
     float *dst = o.full() ? os.Pf.as<float>() + (size_t)sp.lo * o.D_w : os.stage.as<float>() + (size_t)cm::stage_row(p, g, w) * o.D_w;
-    const size_t bytes = (size_t)rows * o.D_w * sizeof(float);
-    if (os.device == s.device) MHIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s.stream));
-    else MHIP(hipMemcpyPeerAsync(dst, os.device, src, s.device, bytes, s.stream));
+    MHIP(copy_between(dst, os.device, src, s.device, (size_t)rows * o.D_w * sizeof(float), s.stream));
   }
   MHIP(hipEventRecord(s.t[2], s.stream));
   MHIP(hipStreamSynchronize(s.stream));
@@ -247,23 +209,17 @@ int run_fit(CbRun &f, float *centroids_out, int *iters_out, int *nan_rows_out) {
       const cb::Sub &mine = o.plan.sub[i], &sd = p.whole.sub[(size_t)o.subs[i]];
       const float *m = s.h_means.data() + (size_t)mine.cent_off * p.L;
       std::memcpy(centroids_out + (size_t)sd.cent_off * p.L, m, (size_t)sd.k * p.L * sizeof(float));
-      int nan_rows = 0;
-      for (int c = 0; c < sd.k; c++) {
-        bool nan = false;
-        for (int j = 0; j < p.L; j++) nan |= std::isnan(m[(size_t)c * p.L + j]);
-        nan_rows += nan;
-      }
       if (iters_out) iters_out[o.subs[i]] = s.iters[i];
-      if (nan_rows_out) nan_rows_out[o.subs[i]] = nan_rows;
+      if (nan_rows_out) nan_rows_out[o.subs[i]] = vaq::nan_rows(m, sd.k, p.L);
       tm.iterations = std::max(tm.iterations, s.iters[i]);
     }
-    tm.columns_ms = std::max(tm.columns_ms, s.ms[PH_COLUMNS]);
-    tm.copy_ms = std::max(tm.copy_ms, s.ms[PH_COPY]);
-    tm.place_ms = std::max(tm.place_ms, s.ms[PH_PLACE]);
     tm.assign_ms = std::max(tm.assign_ms, (float)s.ph.assign_ms);
     tm.accumulate_ms = std::max(tm.accumulate_ms, (float)s.ph.accumulate_ms);
     tm.update_ms = std::max(tm.update_ms, (float)s.ph.update_ms);
   }
+  tm.columns_ms = f.max_ms(PH_COLUMNS);
+  tm.copy_ms = f.max_ms(PH_COPY);
+  tm.place_ms = f.max_ms(PH_PLACE);
   tm.subspaces = p.M;
   tm.dims = f.D;
   tm.rows = p.n;
@@ -307,8 +263,9 @@ int fit_host(int n_devices, const int *device_ids, vaq::RowsRef X, int64_t n, in
              const float *eigvec, int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out) {
   if (!device_ids) return mfail(VAQHIP_EINVAL, "null pointer");
   if (const int rc = forward(vaqhip_internal_fit_codebooks_check(X.p, n, D, M, bits, max_iter, centroids_out))) return rc;
-  if (n_devices < 1 || n_devices > VAQHIP_MAX_DEVICES)
-    return mfail(VAQHIP_EINVAL, "n_devices=%d outside 1..%d", n_devices, VAQHIP_MAX_DEVICES);
+  WallClock wall;
+  CbRun f;
+  if (const int rc = f.from_devices(n_devices, device_ids)) return rc;
   if (n_devices == 1) {  // the single fit itself
     const int rc = forward(X.elem == 1 ? vaqhip_fit_codebooks_u8(device_ids[0], static_cast<const uint8_t *>(X.p), n, D, M, bits,
                                                                  eigvec, max_iter, centroids_out, iters_out, nan_rows_out)
@@ -317,12 +274,6 @@ int fit_host(int n_devices, const int *device_ids, vaq::RowsRef X, int64_t n, in
     if (!rc) timing_from_single();
     return rc;
   }
-  DeviceGuard keep(DeviceGuard::restore_only);  // (declared first: it puts the device back after f has released)
-  WallClock wall;
-  CbRun f;
-  f.G = n_devices;
-  f.sh.resize((size_t)n_devices);
-  for (int g = 0; g < n_devices; g++) f.sh[(size_t)g].device = device_ids[g];
   if (!cm::plan_host(n_devices, n, D, M, bits, &f.plan)) return mfail(VAQHIP_EINVAL, "bad n_devices/n/D/M");
   f.D = D;
   f.max_iter = max_iter;
@@ -364,18 +315,10 @@ int vaqhip_multi_refiner_fit_codebooks(vaqhip_multi_refiner *r, int M, const int
     if (!rc) timing_from_single();
     return rc;
   }
-  DeviceGuard keep(DeviceGuard::restore_only);  // (declared first: it puts the device back after f has released)
   WallClock wall;
   CbRun f;
-  f.G = r->G;
-  f.sh.resize((size_t)r->G);
   int64_t cnt[VAQHIP_MAX_DEVICES];
-  for (int g = 0; g < r->G; g++) {
-    const ResidentRows rows = resident_rows(r, g);
-    f.sh[(size_t)g].device = r->sh[g].device;
-    f.sh[(size_t)g].d_rows = rows.rows;  // (float or byte: the column kernel reads either in place)
-    cnt[g] = rows.n;
-  }
+  f.from_refiner(r, cnt);  // (float or byte rows: the column kernel reads either in place)
   if (!cm::plan_from_counts(r->G, cnt, r->D, M, bits, &f.plan) || f.plan.n != r->N) return mfail(VAQHIP_EINVAL, "bad shard counts");
   f.D = r->D;
   f.max_iter = max_iter;

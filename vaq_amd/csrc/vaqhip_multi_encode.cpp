@@ -21,7 +21,7 @@
 // call's, not the handle's, on purpose: n_g x M x 2 bytes per shard (4 GB at 125M x 16) that nothing needs between two
 // builds; the price is two hipMalloc / hipFree and four events per shard and call.
 // All row and element offsets are int64_t / size_t: a shard of 125M x 16 codes has 2e9 elements.
-#include "vaqhip_multi_refiner.h"
+#include "vaqhip_shard_run.h"
 
 #include <chrono>
 #include <cstring>
@@ -39,6 +39,8 @@ struct EncodePart {
   DevBuf chunk, codes;             // host form: [chunk rows][D] of the call's element; uint16 [n][M]
   hipEvent_t t[4] = {nullptr, nullptr, nullptr, nullptr};  // phase 1: start, encoded; phase 2: start, set
   float encode_ms = 0, set_ms = 0;
+  bool held() const { return codes.p || chunk.p || t[0]; }
+  void release() { release_all({&chunk, &codes}), destroy_events(t); }
 };
 
 struct EncodeCall {
@@ -111,15 +113,9 @@ int set_part(vaqhip_multi *mx, const EncodeCall &c, EncodePart &p, Shard &s, boo
   return 0;
 }
 
-// the scratch of every shard, by the calling thread; the streams are idle first (a phase may have failed part-way)
+// the scratch of every shard, by the calling thread; the handle's streams are idle first (a phase may have failed part-way)
 void release_parts(vaqhip_multi *mx, EncodeCall &c) {
-  for (int g = 0; g < mx->G; g++) {
-    EncodePart &p = c.part[g];
-    if (!p.codes.p && !p.chunk.p && !p.t[0]) continue;
-    if (hipSetDevice(mx->sh[g].device) == hipSuccess) (void)hipStreamSynchronize(mx->sh[g].stream);
-    release_all({&p.chunk, &p.codes});
-    destroy_events(p.t);
-  }
+  idle_then_release(c.part, [&](int g) { return ShardAt{mx->sh[g].device, mx->sh[g].stream}; });
 }
 
 // Both phases over the parts in c.part; mx->mu held, everything refused that can be.  A set gives the shards the parts'
@@ -217,11 +213,7 @@ int encode_from_refiner(vaqhip_multi *mx, vaqhip_multi_refiner *r, uint16_t *cod
   std::lock_guard<std::mutex> lr(r->mu);  // (the order of vaqhip_multi_search_refine: the refiner, then the index)
   std::lock_guard<std::mutex> lk(mx->mu);
   if (const int rc = check_lut(mx, lut)) return rc;
-  if (mx->D != r->D) return mfail(VAQHIP_EINVAL, "the index has D=%d, the refiner D=%d", mx->D, r->D);
-  bool same = mx->G == r->G;
-  for (int g = 0; same && g < r->G; g++) same = mx->sh[g].device == r->sh[g].device;
-  if (!same) return mfail(VAQHIP_EINVAL, "the index and the refiner name different device lists");
-  if (r->N == 0) return mfail(VAQHIP_ESTATE, "the refiner holds no rows: vaqhip_multi_refiner_set_rows first");
+  if (const int rc = check_refiner_pair(mx, r)) return rc;
   EncodeCall c;
   c.lut = lut;
   c.id_base = r->id_base;

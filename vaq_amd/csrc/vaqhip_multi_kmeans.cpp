@@ -3,7 +3,6 @@
 #include "vaqhip_multi.h"
 
 #include <chrono>
-#include <cmath>
 #include <cstring>
 
 #include "kmeans_sample.h"
@@ -107,15 +106,9 @@ int vaqhip_multi_cluster_ti_kmeans(vaqhip_multi *mx, int T, int seg_num, int max
   mx->km_last.clusters = T;
   if (no_centre)
     return mfail(VAQHIP_EINVAL, "a row is at a distance >= FLT_MAX (or NaN) from every centre: the reference indexes row -1");
-  int nan_rows = 0;
-  for (int c = 0; c < T; c++) {
-    bool nan = false;
-    for (int j = 0; j < dd; j++) nan |= std::isnan(means[(size_t)c * dd + j]);
-    nan_rows += nan;
-  }
   if (clusters_out) std::memcpy(clusters_out, means.data(), means.size() * sizeof(float));
   if (iters_out) *iters_out = iters;
-  if (nan_rows_out) *nan_rows_out = nan_rows;
+  if (nan_rows_out) *nan_rows_out = vaq::nan_rows(means.data(), T, dd);
   return set_ti_clusters_on_shards(mx, means.data(), T, seg_num);
 }
 

@@ -8,8 +8,9 @@
 //             (the same gather kernel over the staged blocks); the host waits for that stream alone
 //   3 learn   vaqhip_internal_learn_sample_device on shard 0, the result to every other shard through
 //             vaqhip_index_set_lut_quantization
-// The scratch is the call's: two sample x D float buffers on the first device, one block per shard.
-#include "vaqhip_multi_refiner.h"
+// The scratch is the call's: two sample x D float buffers on the first device, one block per shard (released by
+// idle_then_release, vaqhip_shard_run.h).
+#include "vaqhip_shard_run.h"
 
 #include <chrono>
 #include <cstring>
@@ -25,6 +26,8 @@ struct GatherPart {
   DevBuf idx, block;  // the shard's sampled rows (local), gathered as floats [cnt][D]
   int64_t at = 0;     // the block's first row among the staged blocks
   hipEvent_t copied = nullptr;  // the block is on the first device
+  bool held() const { return idx.p || block.p || copied; }
+  void release() { release_all({&idx, &block}), destroy_events(&copied, 1); }
 };
 
 // every shard gets shard 0's result (mx->mu held)
@@ -58,11 +61,7 @@ int vaqhip_multi_learn_quantization_from_refiner(vaqhip_multi *mx, vaqhip_multi_
   if (!r) return mfail(VAQHIP_EINVAL, "multi refiner is null");
   std::lock_guard<std::mutex> lr(r->mu);  // (the order of vaqhip_multi_search_refine: the refiner, then the index)
   std::lock_guard<std::mutex> lk(mx->mu);
-  if (mx->D != r->D) return mfail(VAQHIP_EINVAL, "the index has D=%d, the refiner D=%d", mx->D, r->D);
-  bool same = mx->G == r->G;
-  for (int g = 0; same && g < r->G; g++) same = mx->sh[g].device == r->sh[g].device;
-  if (!same) return mfail(VAQHIP_EINVAL, "the index and the refiner name different device lists");
-  if (r->N == 0) return mfail(VAQHIP_ESTATE, "the refiner holds no rows: vaqhip_multi_refiner_set_rows first");
+  if (const int rc = check_refiner_pair(mx, r)) return rc;
   if (!vaqhip_internal_fast_ok(mx->sh[0].ix))
     return mfail(VAQHIP_EUNSUPPORTED, "FAST needs max bits per subspace <= 4 and the grouped row sum");
   const int64_t n = r->N;
@@ -91,20 +90,13 @@ int vaqhip_multi_learn_quantization_from_refiner(vaqhip_multi *mx, vaqhip_multi_
   DeviceGuard keep(DeviceGuard::restore_only);  // (declared before the buffers: it puts the device back after they went)
   const int dev0 = r->sh[0].device;
   DevBuf d_stage, d_rows, d_place;
-  // the blocks are the shards': freed with their device current and their stream idle, however the call ends
+  // the blocks are the shards': freed with their device current and every shard's stream idle, however the call ends
   struct PartsFree {
     vaqhip_multi_refiner *r;
     std::vector<GatherPart> &part;
     int dev0;
     ~PartsFree() {
-      for (int g = 0; g < r->G; g++) {
-        GatherPart &p = part[(size_t)g];
-        if (!p.idx.p && !p.block.p && !p.copied) continue;
-        if (hipSetDevice(r->sh[g].device) == hipSuccess) (void)hipStreamSynchronize(r->sh[g].stream);
-        release_all({&p.idx, &p.block});
-        if (p.copied) (void)hipEventDestroy(p.copied);
-        p.copied = nullptr;
-      }
+      idle_then_release(part, [&](int g) { return ShardAt{r->sh[g].device, r->sh[g].stream}; });
       (void)hipSetDevice(dev0);  // (for the first device's buffers, which go next)
     }
   } parts_free{r, part, dev0};
@@ -129,9 +121,7 @@ int vaqhip_multi_learn_quantization_from_refiner(vaqhip_multi *mx, vaqhip_multi_
         MHIP(hipMemcpyAsync(p.idx.p, local.data(), (size_t)m * sizeof(int), hipMemcpyHostToDevice, s.stream));
         MHIP(vaq::launch_learn_gather(s.rows.rows(), p.idx.as<int>(), m, D, p.block.as<float>(), s.stream));
         float *dst = stage + (size_t)p.at * D;
-        const size_t bytes = (size_t)m * D * sizeof(float);
-        if (s.device == dev0) MHIP(hipMemcpyAsync(dst, p.block.p, bytes, hipMemcpyDeviceToDevice, s.stream));
-        else MHIP(hipMemcpyPeerAsync(dst, dev0, p.block.p, s.device, bytes, s.stream));
+        MHIP(copy_between(dst, dev0, p.block.p, s.device, (size_t)m * D * sizeof(float), s.stream));
         MHIP(hipEventRecord(p.copied, s.stream));
         return 0;
       }))

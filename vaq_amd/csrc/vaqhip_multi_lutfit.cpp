@@ -6,8 +6,7 @@
 // arrived in.  So dimension d is owned by device d % G (lutfit_multi_plan.h), and per round of G consecutive dimensions:
 //   1 columns  every shard turns its resident rows into the round's column slices of sortable keys, the projection
 //              fused (lutfit_project_columns_kernel), into a scratch of G x n_g words
-//   2 copy     every shard sends slice w to owner w's key buffer at word lo_g (hipMemcpyPeerAsync; device-to-device
-//              where both shards name one GPU)
+//   2 copy     every shard sends slice w to owner w's key buffer at word lo_g (copy_between, vaqhip_multi.h)
 //   3 fit      every owner runs the single fit's column pipeline on its n keys (lut_fit_column_from_keys: the body
 //              lut_fit_columns runs too) into its own slot for that dimension
 // Steps 1-2 and step 3 are two phases on the shards' workers (job_pool.h, on_shards): every worker synchronises its
@@ -15,9 +14,10 @@
 // failing shard ends the call and an owner never sorts a buffer that is still being written.  (Round t + 1's columns
 // could overlap round t's fit with a second key buffer per owner; not done.)  After the last round the owners' slots
 // and every shard's non-finite flag go to the host; the outputs are written only when no flag is set.
-// The workers, streams, events and buffers are the call's own: the host form has no handle to keep them in, and the
-// refiner form only reads the refiner's rows (r->mu held; set_rows and add_rows copy synchronously).
-#include "vaqhip_multi_refiner.h"
+// The workers, streams, events and buffers are the call's own (vaqhip_shard_run.h: the run, the start of a shard's
+// setup and the teardown): the host form has no handle to keep them in, and the refiner form only reads the refiner's
+// rows (r->mu held; set_rows and add_rows copy synchronously).  What is here is the plan, the phases and the gather.
+#include "vaqhip_shard_run.h"
 
 #include <chrono>
 #include <cstring>
@@ -36,78 +36,30 @@ thread_local vaqhip_multi_lut_fit_timing g_fit_last = {};
 
 enum { PH_COLUMNS, PH_COPY, PH_SORT, PH_QUANTILE, PH_MEANS, PH_COUNT };
 
-struct FitShard {
-  int device = 0;
-  std::string err;
-  hipStream_t stream = nullptr;
-  vaq::RowsRef d_rows = {nullptr, 4};  // the shard's n_g x D rows on its device, float or byte, read in place every round
-  DevBuf slice, eig, cols, bad;   // host form: the uploaded rows (n_g x D of the call's element); eigvec; [W][n_g] keys; the non-finite flag
+struct FitShard : RunShard {
+  DevBuf cols, bad;               // [W][n_g] keys; the non-finite flag
   vaq::LutFitColumnWork work;     // as an owner: the column in flight
   DevBuf cent, q;                 //   and its slots, [slots][256] and [slots][257]
   std::vector<float> h_cent, h_q;
   int h_bad = 0;
   hipEvent_t t[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // columns start, end, copied; the fit's 4
   float ms[PH_COUNT] = {0, 0, 0, 0, 0};  // summed over the rounds
+  void release() { release_all({&cols, &bad, &cent, &q}), work.release(), destroy_events(t); }
 };
 
-// what on_shards runs over: G, pool, sh[] with device and err
-struct FitRun {
-  int G = 0;
-  std::vector<FitShard> sh;
-  vaq::JobPool pool;
+// the call's run (vaqhip_shard_run.h) with what this fit adds
+struct FitRun : ShardRun<FitShard> {
   lp::Plan plan;
   const int *bits = nullptr;
-  vaq::RowsRef X = {nullptr, 4};  // host form: the call's matrix, float or byte
-  const float *eig = nullptr;  // host pointer or null
-  // by the calling thread, whichever way the call ended: the workers first, then every device's streams and buffers
-  ~FitRun() {
-    pool.stop();
-    for (FitShard &s : sh) {
-      if (!s.stream && !s.t[0] && !s.slice.p && !s.eig.p && !s.cols.p && !s.bad.p && !s.work.keys.p && !s.cent.p) continue;
-      if (hipSetDevice(s.device) != hipSuccess) continue;
-      if (s.stream) (void)hipStreamSynchronize(s.stream);
-      release_all({&s.slice, &s.eig, &s.cols, &s.bad, &s.cent, &s.q});
-      s.work.release();
-      destroy_events(s.t);
-      if (s.stream) (void)hipStreamDestroy(s.stream);
-    }
-  }
 };
-
-// the single fit's refusals (vaqhip_lutfit.cpp, check_fit_args) with its codes
-int check_fit_args(int64_t n, int D, const int *bits, const void *cent, const void *q) {
-  if (!bits || !cent || !q) return mfail(VAQHIP_EINVAL, "null pointer");
-  if (n < 1) return mfail(VAQHIP_EINVAL, "n=%lld: centroidsQuantile reads Z.front() of an empty column", (long long)n);
-  if (n >= ((int64_t)1 << 31)) return mfail(VAQHIP_EINVAL, "n=%lld: the reference counts a bucket in an int", (long long)n);
-  if (D < 1) return mfail(VAQHIP_EINVAL, "D=%d", D);
-  if (D > 4096) return mfail(VAQHIP_EUNSUPPORTED, "D=%d > 4096", D);
-  for (int d = 0; d < D; d++)
-    if (bits[d] < 1 || bits[d] > 8) return mfail(VAQHIP_EINVAL, "bits[%d]=%d outside 1..8 (centroidsMat has 256 rows)", d, bits[d]);
-  return VAQHIP_OK;
-}
 
 // every shard: its stream and events, its rows (host form: uploaded once), eigvec, its scratch; every owner: its buffers
 int setup_shard(FitRun &f, int g, FitShard &s) {
   const lp::Plan &p = f.plan;
-  const size_t D = (size_t)p.D;
-  if (hipSetDevice(s.device) != hipSuccess) {
-    s.err = "hipSetDevice failed (no CPU path)";
-    return VAQHIP_ENODEVICE;
-  }
-  MHIP(hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking));
-  MHIP(ensure_events(s.t));
   const int64_t n_g = p.cnt[g];
+  if (const int rc = f.open(s, p.lo[g], n_g, p.D)) return rc;
+  MHIP(ensure_events(s.t));
   if (n_g > 0) {
-    if (f.X.p) {
-      const size_t bytes = (size_t)n_g * D * (size_t)f.X.elem;
-      MHIP(s.slice.ensure(bytes));
-      MHIP(hipMemcpyAsync(s.slice.p, vaq::rows_at(f.X, (size_t)p.lo[g] * D).p, bytes, hipMemcpyHostToDevice, s.stream));
-      s.d_rows = vaq::RowsRef{s.slice.p, f.X.elem};
-    }
-    if (f.eig) {
-      MHIP(s.eig.ensure(D * D * sizeof(float)));
-      MHIP(hipMemcpyAsync(s.eig.p, f.eig, D * D * sizeof(float), hipMemcpyHostToDevice, s.stream));
-    }
     MHIP(s.cols.ensure((size_t)lp::shard_scratch_words(p, g) * sizeof(uint32_t)));
     MHIP(s.bad.ensure(sizeof(int)));
     MHIP(hipMemsetAsync(s.bad.p, 0, sizeof(int), s.stream));
@@ -138,9 +90,7 @@ int columns_and_copy(FitRun &f, int t, int g, FitShard &s) {
     FitShard &o = f.sh[(size_t)lp::owner_of(d0 + w, p.G)];
     const uint32_t *src = s.cols.as<uint32_t>() + lp::slice_src_word(p, g, w);
     uint32_t *dst = o.work.keys.as<uint32_t>() + lp::slice_dst_word(p, g);
-    const size_t bytes = (size_t)n_g * sizeof(uint32_t);
-    if (o.device == s.device) MHIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s.stream));
-    else MHIP(hipMemcpyPeerAsync(dst, o.device, src, s.device, bytes, s.stream));
+    MHIP(copy_between(dst, o.device, src, s.device, (size_t)n_g * sizeof(uint32_t), s.stream));
   }
   MHIP(hipEventRecord(s.t[2], s.stream));
   MHIP(hipStreamSynchronize(s.stream));
@@ -208,13 +158,11 @@ int run_fit(FitRun &f, float *centroids_out, float *quantiles_out) {
     std::memcpy(quantiles_out + (size_t)d * lf::MAX_Q, o.h_q.data() + slot * lf::MAX_Q, lf::MAX_Q * sizeof(float));
   }
   vaqhip_multi_lut_fit_timing tm = {};
-  for (const FitShard &s : f.sh) {
-    tm.columns_ms = std::max(tm.columns_ms, s.ms[PH_COLUMNS]);
-    tm.copy_ms = std::max(tm.copy_ms, s.ms[PH_COPY]);
-    tm.sort_ms = std::max(tm.sort_ms, s.ms[PH_SORT]);
-    tm.quantile_ms = std::max(tm.quantile_ms, s.ms[PH_QUANTILE]);
-    tm.means_ms = std::max(tm.means_ms, s.ms[PH_MEANS]);
-  }
+  tm.columns_ms = f.max_ms(PH_COLUMNS);
+  tm.copy_ms = f.max_ms(PH_COPY);
+  tm.sort_ms = f.max_ms(PH_SORT);
+  tm.quantile_ms = f.max_ms(PH_QUANTILE);
+  tm.means_ms = f.max_ms(PH_MEANS);
   tm.rows = p.n;
   tm.dims = p.D;
   tm.n_devices = p.G;
@@ -227,14 +175,9 @@ int run_fit(FitRun &f, float *centroids_out, float *quantiles_out) {
 int fit_host(int n_devices, const int *device_ids, vaq::RowsRef X, int64_t n, int D, const int *bits, const float *eigvec,
              float *centroids_out, float *quantiles_out) {
   if (!X.p || !device_ids) return mfail(VAQHIP_EINVAL, "null pointer");
-  if (const int rc = check_fit_args(n, D, bits, centroids_out, quantiles_out)) return rc;
-  if (n_devices < 1 || n_devices > VAQHIP_MAX_DEVICES)
-    return mfail(VAQHIP_EINVAL, "n_devices=%d outside 1..%d", n_devices, VAQHIP_MAX_DEVICES);
-  DeviceGuard keep(DeviceGuard::restore_only);  // (declared first: it puts the device back after f has released)
+  if (const int rc = forward(vaqhip_internal_lut_fit_check(X.p, n, D, bits, centroids_out, quantiles_out))) return rc;
   FitRun f;
-  f.G = n_devices;
-  f.sh.resize((size_t)n_devices);
-  for (int g = 0; g < n_devices; g++) f.sh[(size_t)g].device = device_ids[g];
+  if (const int rc = f.from_devices(n_devices, device_ids)) return rc;
   if (!lp::plan_host(n_devices, D, n, &f.plan)) return mfail(VAQHIP_EINVAL, "bad n_devices/D/n");
   f.bits = bits;
   f.X = X;
@@ -261,18 +204,11 @@ int vaqhip_multi_refiner_lut_fit_quantiles(vaqhip_multi_refiner *r, const int *b
   if (!bits || !centroids_out || !quantiles_out) return mfail(VAQHIP_EINVAL, "null pointer");
   std::lock_guard<std::mutex> lk(r->mu);
   if (r->N == 0) return mfail(VAQHIP_ESTATE, "the refiner holds no rows: vaqhip_multi_refiner_set_rows first");
-  if (const int rc = check_fit_args(r->N, r->D, bits, centroids_out, quantiles_out)) return rc;
-  DeviceGuard keep(DeviceGuard::restore_only);  // (declared first: it puts the device back after f has released)
+  // (the rows are the refiner's: any non-null pointer stands for them in the single fit's checks)
+  if (const int rc = forward(vaqhip_internal_lut_fit_check(r, r->N, r->D, bits, centroids_out, quantiles_out))) return rc;
   FitRun f;
-  f.G = r->G;
-  f.sh.resize((size_t)r->G);
   int64_t cnt[VAQHIP_MAX_DEVICES];
-  for (int g = 0; g < r->G; g++) {
-    const ResidentRows rows = resident_rows(r, g);
-    f.sh[(size_t)g].device = r->sh[g].device;
-    f.sh[(size_t)g].d_rows = rows.rows;  // (float or byte: the column kernel reads either in place)
-    cnt[g] = rows.n;
-  }
+  f.from_refiner(r, cnt);  // (float or byte rows: the column kernel reads either in place)
   if (!lp::plan_from_counts(r->G, r->D, cnt, &f.plan)) return mfail(VAQHIP_EINVAL, "bad shard counts");
   f.bits = bits;
   f.eig = eigvec;

@@ -151,10 +151,7 @@ int check_pair(vaqhip_multi *mx, const vaqhip_multi_refiner *r, int R) {
   if (R > VAQHIP_MAX_K) return mfail(VAQHIP_EUNSUPPORTED, "R=%d > %d (the search returns the candidates)", R, VAQHIP_MAX_K);
   vaqhip_multi_info inf;
   if (const int rc = vaqhip_multi_get_info(mx, &inf)) return rc;
-  if (mx->D != r->D) return mfail(VAQHIP_EINVAL, "the index has D=%d, the refiner D=%d", mx->D, r->D);
-  bool same = inf.n_devices == r->G;
-  for (int g = 0; same && g < r->G; g++) same = inf.device_ids[g] == r->sh[g].device;
-  if (!same) return mfail(VAQHIP_EINVAL, "the index and the refiner name different device lists");
+  if (const int rc = check_same_devices(mx, r)) return rc;
   if (inf.N != r->N || inf.id_base != r->id_base)
     return mfail(VAQHIP_ESTATE, "the index holds %lld rows from label %lld, the refiner %lld from %lld", (long long)inf.N,
                  (long long)inf.id_base, (long long)r->N, (long long)r->id_base);

@@ -1,7 +1,8 @@
 // vaqhip_multi_refiner.h -- what the two host files of the multi-device refiner share: the shard, the handle, the set
 // of each form in flight (every buffer of a set is sized by it) and the two steps both forms take.  Buffers are
 // grouped by form and device.  Private to vaqhip_multi_refiner.cpp (life cycle, rows, options, the refine form, the
-// fused call) and vaqhip_multi_refiner_search.cpp (the exhaustive form); vaqhip_multi_encode.cpp takes resident_rows().
+// fused call) and vaqhip_multi_refiner_search.cpp (the exhaustive form); the builds from a refiner's rows (vaqhip_multi_encode.cpp,
+// vaqhip_multi_learn.cpp, the sharded fits through vaqhip_shard_run.h) take resident_rows() and the pair checks.
 #ifndef VAQHIP_MULTI_REFINER_H
 #define VAQHIP_MULTI_REFINER_H
 #include "vaqhip_multi.h"
@@ -124,8 +125,25 @@ inline int rows_elem(const vaqhip_multi_refiner *r) { return r->sh[0].rows.elem;
 // every stream idle: after a call that failed part-way, before anything it may still read is freed or reused
 void drain(vaqhip_multi_refiner *r);
 
-// Shard g's resident rows for the encode across the shards (vaqhip_multi_encode.cpp), which reads them in place on the
-// shard's device: n rows of D floats or bytes (rows.elem), the first with label first_label.  r->mu held; set_rows and
+// An index and a refiner that stand for the same rows: one D, one device list (neither changes after create).
+inline int check_same_devices(const vaqhip_multi *mx, const vaqhip_multi_refiner *r) {
+  if (mx->D != r->D) return mfail(VAQHIP_EINVAL, "the index has D=%d, the refiner D=%d", mx->D, r->D);
+  bool same = mx->G == r->G;
+  for (int g = 0; same && g < r->G; g++) same = mx->sh[g].device == r->sh[g].device;
+  if (!same) return mfail(VAQHIP_EINVAL, "the index and the refiner name different device lists");
+  return VAQHIP_OK;
+}
+
+// what a build of the index from the refiner's rows refuses (vaqhip_multi_encode*_from_refiner,
+// vaqhip_multi_learn_quantization_from_refiner): the above, and a refiner without rows.  r->mu held.
+inline int check_refiner_pair(const vaqhip_multi *mx, const vaqhip_multi_refiner *r) {
+  if (const int rc = check_same_devices(mx, r)) return rc;
+  if (r->N == 0) return mfail(VAQHIP_ESTATE, "the refiner holds no rows: vaqhip_multi_refiner_set_rows first");
+  return VAQHIP_OK;
+}
+
+// Shard g's resident rows for the builds across the shards (vaqhip_multi_encode.cpp, vaqhip_shard_run.h), which read
+// them in place on the shard's device: n rows of D floats or bytes (rows.elem), the first with label first_label.  r->mu held; set_rows and
 // add_rows copy synchronously, so the rows are complete.
 struct ResidentRows { vaq::RowsRef rows; int64_t n, first_label; };
 inline ResidentRows resident_rows(const vaqhip_multi_refiner *r, int g) {
