@@ -4,6 +4,8 @@ VAQ::searchTriangleInequality.
 CPU part: properties of the oracle's restatement (oracle/vaq_oracle.c,
 vo_cluster_ti / vo_search_ti; PARITY UNPINNED, see its header).
 GPU part: libvaqhip.so's TI form against that restatement, through the C ABI.
+Launch-shape edges of the regroup and the plan (summation orders, LDS tiers, T up to 4096):
+tests/test_ti_shapes_gpu.py.
 """
 import numpy as np
 import pytest
