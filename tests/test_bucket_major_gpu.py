@@ -90,7 +90,8 @@ def test_bucket_major_matches_oracle(vaqlib, oracle, seed, bits, N, nq, k, bb, k
 
 def test_bucket_major_overflow_and_small_k(vaqlib, oracle):
     """Fewer than k rows within reach of pass A (k close to the rows of a bucket), candidate
-    buffers of 1 slot (every query overflows and is finished by the best-first form), N < k."""
+    buffers of 1 slot (every query overflows and is finished by the best-first form).  N < k is
+    tests/test_bucket_major_edges_gpu.py's (test_fewer_rows_than_k)."""
     bits = [8] * 8
     c = make_case(9201, 64, bits, 280_000, 40, dup_frac=0.3, integer=True)  # small integers: massive ties
     Xp = oracle.project(c["X"], c["eig"])
