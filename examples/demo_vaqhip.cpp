@@ -47,6 +47,14 @@
 //                                           sharded: the rows are cut over the GPUs, subspace s is fitted on device
 //                                           s % G, the same centres bit for bit.  --save writes them as
 //                                           demo_vaq --save does; composes with --encode; without --queries it ends there)
+//               [--train --bit-budget 128 --subspaces 16 [--min-bits 1 --max-bits 12 --var 1] --dataset base.fvecs]
+//                                          (instead of --centroids, --eigen and --bits: VAQ::train from the raw vectors
+//                                           alone -- the second moment of the sampled rows, its eigenvectors, the
+//                                           partial balance, the exact bit allocation, then the codebook fit above.
+//                                           min / max / var default to the method string's.  bvecs and
+//                                           --refine-resident as with --fit-codebooks; no --devices.  Goes in front of
+//                                           --encode: demo_vaqhip --train ... --encode --queries q.fvecs builds and
+//                                           searches an index with no foreign input)
 //               with a ...,FAST method (codes of at most 4 bits): --dataset base.fvecs [--dataset-size N]
 //               [--learn-ratio 0.05]       (demo_vaq.cpp:42, :120-124: VAQ::learnQuantization on the raw dataset; from the
 //                                           bytes with --file-format-ori bvecs, from the resident rows with --refine-resident)
@@ -147,7 +155,8 @@ int main(int argc, char **argv) {
                                           {"timeseries-size", "128"}, {"queries-size", "-1"}};
   for (int i = 1; i < argc; i += 2) {
     if (std::strcmp(argv[i], "--refine-resident") == 0 || std::strcmp(argv[i], "--exact-groundtruth") == 0 ||
-        std::strcmp(argv[i], "--encode") == 0 || std::strcmp(argv[i], "--fit-codebooks") == 0) {
+        std::strcmp(argv[i], "--encode") == 0 || std::strcmp(argv[i], "--fit-codebooks") == 0 ||
+        std::strcmp(argv[i], "--train") == 0) {
       a[argv[i] + 2] = "1";  // the switches without a value
       i--;
       continue;
@@ -169,9 +178,11 @@ int main(int argc, char **argv) {
       return 1;
     }
   }
-  const bool encode = a.count("encode") != 0, fit = a.count("fit-codebooks") != 0;
+  const bool train = a.count("train") != 0;  // PCA, bit allocation and codebooks from the raw vectors alone
+  const bool encode = a.count("encode") != 0, fit = a.count("fit-codebooks") != 0 || train;
   const bool fit_only = fit && !encode && !a.count("codebook") && !a.count("queries");  // fit, --save, done
-  std::vector<std::string> required = {fit ? "bits" : "centroids"};
+  std::vector<std::string> required = {train ? "bit-budget" : fit ? "bits" : "centroids"};
+  if (train) required.push_back("subspaces");
   if (fit || encode) required.push_back("dataset");
   if (!encode && !fit_only) required.push_back("codebook");
   if (!fit_only) required.push_back("queries");
@@ -182,8 +193,18 @@ int main(int argc, char **argv) {
     vaq.parseMethodString(a["method"]);
     if (!fit) vaq.mCentroidsPerSubs = loadCentroids(a["centroids"]);
     if (!encode && !fit_only) vaq.mCodebook = loadCodebook(a["codebook"]);
-    const int M = fit ? (int)intList(a["bits"]).size() : (int)vaq.mCentroidsPerSubs.size();
-    if (a.count("bits")) {  // --hc-bitalloc style list (demo_vaq.cpp:94-97)
+    if (train) {  // the method string's min / max / var hold unless the flags name others
+      if (a.count("devices")) throw Error(VAQHIP_EUNSUPPORTED, "--train has no multi-device form");
+      if (a.count("eigen") || a.count("bits")) throw Error(VAQHIP_EINVAL, "--train computes the rotation and the bits: no --eigen, no --bits");
+      vaq.mBitBudget = std::atoi(a["bit-budget"].c_str());
+      vaq.mSubspaceNum = std::atoi(a["subspaces"].c_str());
+      if (a.count("min-bits")) vaq.mMinBitsPerSubs = std::atoi(a["min-bits"].c_str());
+      if (a.count("max-bits")) vaq.mMaxBitsPerSubs = std::atoi(a["max-bits"].c_str());
+      if (a.count("var")) vaq.mPercentVarExplained = (float)std::atof(a["var"].c_str());
+    }
+    const int M = train ? vaq.mSubspaceNum : fit ? (int)intList(a["bits"]).size() : (int)vaq.mCentroidsPerSubs.size();
+    if (train) {
+    } else if (a.count("bits")) {  // --hc-bitalloc style list (demo_vaq.cpp:94-97)
       std::stringstream ss(a["bits"]);
       std::string t;
       while (std::getline(ss, t, ',')) vaq.mBitsAlloc.push_back(std::atoi(t.c_str()));
@@ -229,17 +250,29 @@ int main(int argc, char **argv) {
         resident_rows = uploadRefine(a.count("dataset-refine") ? a["dataset-refine"] : a["dataset"], dsize);
         uploaded = true;
         t0 = std::chrono::steady_clock::now();
-        vaq.fitCodebooksRefineDataset(max_iter);
+        if (train) vaq.trainRefineDataset(max_iter);
+        else vaq.fitCodebooksRefineDataset(max_iter);
         from = " (from the resident rows)";
       } else if (g_bvecs) {
         RowMatrix<uint8_t> dataset8 = readBVecsU8(a["dataset"], N, dsize);
         t0 = std::chrono::steady_clock::now();
-        vaq.fitCodebooks(dataset8, max_iter);
+        if (train) vaq.train(dataset8, max_iter);
+        else vaq.fitCodebooks(dataset8, max_iter);
         from = " (from the byte rows of the bvecs file)";
       } else {
         RowMatrixF dataset = readFVecs(a["dataset"], N, dsize, 0);
         t0 = std::chrono::steady_clock::now();
-        vaq.fitCodebooks(dataset, max_iter);
+        if (train) vaq.train(dataset, max_iter);
+        else vaq.fitCodebooks(dataset, max_iter);
+      }
+      if (train) {  // VAQ.cpp:11-524: what the reference prints of its allocation
+        vaqhip_train_timing tt;
+        check(vaqhip_last_train_timing(&tt));
+        std::cout << "== PCA computation time: " << (tt.moment_ms + tt.eigen_ms) / 1000.0 << " s (second moment of "
+                  << tt.sample_rows << " rows " << tt.moment_ms << " ms, " << tt.sweeps << " Jacobi sweeps " << tt.eigen_ms
+                  << " ms, plan and allocation " << tt.plan_ms << " ms)" << std::endl << "bit allocation: ";
+        for (int b : vaq.mBitsAlloc) std::cout << b << ", ";
+        std::cout << std::endl;
       }
       std::cout << "== Codebook fit time: " << std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count()
                 << " s" << from << "; iterations";

@@ -48,6 +48,7 @@ extern "C" {
 #define VAQHIP_EHIP         -5   /* HIP runtime error during a call                             */
 #define VAQHIP_ERANGE       -6   /* label would not fit the reference's 32-bit int labels       */
 #define VAQHIP_ESTATE       -7   /* call order (e.g. search before codes were added)            */
+#define VAQHIP_ENOCONV      -8   /* an iteration reached its limit (vaqhip_sym_eigen_*: 60 sweeps) */
 
 /* search method bits, numerically equal to VAQ::NNMethod (VAQ.hpp:38-49).
  * HEAP and EA run the same kernels because the reference's early abandon
@@ -394,8 +395,8 @@ int vaqhip_encode_lut_u8_device(vaqhip_index *ix, const uint8_t *d_X, int64_t n,
 /* ---------------------------------------------------------------------------
  * Fitting the subspace codebooks mCentroidsPerSubs: KMeans::staticFitSampling (KMeans.hpp:487-616), the call of
  * VAQ.cpp:644-649 -- KMeans::staticFitSampling(XTrain.block(0, s * L, n, L), 1 << bits[s], 25) for every subspace s.
- * It is NOT the arma::kmeans call VAQ::train runs today beside it (armadillo: not reproduced).  The PCA and the bit
- * allocation stay the caller's: eigvec and bits come in.  With this an index is built on the device from raw rows:
+ * It is NOT the arma::kmeans call VAQ::train runs today beside it (armadillo: not reproduced).  eigvec and bits come
+ * in: the caller's, or vaqhip_train_rotation's below.  With this an index is built on the device from raw rows:
  * fit, vaqhip_index_create with the centres, vaqhip_encode.
  *   X              n x D row-major; in PCA space when eigvec is NULL, else X * eigvec by vaqhip_project's chain, unchecked
  *   M, bits[M]     M subspaces of L = D / M columns, k_s = 1 << bits[s] centres, 1 <= bits[s] <= VAQHIP_MAX_BITS
@@ -455,6 +456,106 @@ typedef struct {
 } vaqhip_fit_codebooks_timing;
 int vaqhip_fit_codebooks_set_timing(int on);                             /* per calling thread */
 int vaqhip_last_fit_codebooks_timing(vaqhip_fit_codebooks_timing *out);  /* the calling thread's last fit */
+
+/* ---------------------------------------------------------------------------
+ * Training from raw rows: the front half of VAQ::train (VAQ.cpp:11-524) -- the second moment of the sampled rows, its
+ * eigen-decomposition, the partial balance of the leading dimensions and the ILP that hands each subspace its bits.
+ * With vaqhip_fit_codebooks above an index is built from raw rows and a bit budget alone.  The parity contract:
+ *   covmat       The reference builds XtX in float through Eigen's blocked GEMM (no mean is subtracted: a second moment);
+ *                its summation order is NOT reproduced.  Here the sum is taken in double -- the product of two floats is
+ *                exact, only the additions round -- in a fixed order: the rows are those of VAQ.cpp:17-24 (with
+ *                s = 1000 * D < n the rows randomPermutation(n)[0 .. s) in that order, mt19937(13517106); else all rows
+ *                in order), gathered where they are loaded; sample positions are cut into tiles of 1024; within a tile
+ *                the products are added in ascending position from +0; the tile partials are added in ascending tile
+ *                order from +0; no floating-point atomics, no MFMA.  Every entry (i, j) follows the same order: the
+ *                matrix is exactly symmetric.  It lies within gamma_n * sum_r |x_ri x_rj| of the reference's entry by
+ *                entry (gamma_n = n u / (1 - n u), u = 2^-24, n the rows summed); integer-valued rows (bvecs) with
+ *                n * 255^2 < 2^53 give the exact integer in any order.  A non-finite input propagates; nothing is
+ *                filtered.  cov_f_out (may be NULL): the same matrix rounded to float.
+ *   eigen        Eigen::EigenSolver (real Schur in float, signs arbitrary) cannot be matched bit for bit.  Here: a cyclic
+ *                two-sided Jacobi in double with round-robin ordering, two ordinary launches per step (no cooperative
+ *                launch, no grid barrier, no spinning), one read-back per sweep.  A pair is rotated when
+ *                |a_pq| > 2^-52 sqrt(|a_pp a_qq|) (zero product: a_pq != 0) by theta = (a_qq - a_pp) / (2 a_pq),
+ *                t = sign(theta) / (|theta| + sqrt(theta^2 + 1)), c = 1 / sqrt(t^2 + 1), s = t c; a_pq = a_qp = 0 after it.
+ *                Stops after the first sweep that rotates nothing (sweeps_out counts the sweeps that rotated: 0 for a
+ *                diagonal matrix or D = 1) or with VAQHIP_ENOCONV when sweep 60 still rotated.  A NaN or Inf in A:
+ *                VAQHIP_EINVAL before the first sweep.  A (D x D double, row-major) is destroyed.  After the sweeps
+ *                every vector is divided by its norm (a product of hundreds of rotations drifts from length 1) and its
+ *                eigenvalue is its Rayleigh quotient v^T (A v) on the matrix as it came, all sums in ascending index
+ *                from +0, on the host in both forms (2 D^3 host operations).  Eigenvalues
+ *                descending, equal ones by ascending original column; each vector (a COLUMN of the row-major D x D
+ *                matrix, like eigvec everywhere) has its component of largest magnitude positive, the first such on
+ *                ties.  vaqhip_sym_eigen_host is the same algorithm on the host from the same header
+ *                (vaq_train_rot.h).  What is pinned: the invariants (residual, orthogonality, eigenvalues against
+ *                LAPACK) and the DECISIONS the reference takes from its eigenvalues, not the solver's bits.
+ *   plan         VAQ.cpp:80-96, 243-280, 301-336, 374-412 restated in float BIT FOR BIT from a vector of eigenvalues (in
+ *                the solver's order): sorted_out[D] the columns by descending value (may be NULL), order_out[D] the same
+ *                after the partial balance (with its break at the first swap that leaves the per-subspace sums
+ *                unsorted; swaps_kept_out, may be NULL), var_out[M] varExplainedPerSubs in Eigen's sum() /
+ *                segment().sum() order after the division by the sum and the clamp to 1e-12, cum_out[M] the sequential
+ *                cumSum, highest_subs, lb_out[highest_subs] (min_bits where cum <= percent_var, else 0),
+ *                k_out[highest_subs - 1] = nextPow2 of the float ratio widened to double, clamped to [0, 2^30] (the
+ *                reference's (int) cast of a larger power is undefined; any k >= max_bits constrains nothing).
+ *                lb_out and k_out have room for M and M - 1 entries.  VAQHIP_EINVAL: D % M != 0 (the reference rounds
+ *                the subspace length up and reads past the end), min_bits > max_bits, max_bits > VAQHIP_MAX_BITS,
+ *                M > VAQHIP_MAX_SUBSPACES, a non-finite eigenvalue, a non-positive eigenvalue sum.
+ *   allocation   maximise sum c_i x_i subject to sum x_i = budget, lb_i <= x_i <= max_bits, x_i - x_(i+1) <= k_i, solved
+ *                EXACTLY by dynamic programming over (subspace, its bits, bits spent); c_i the float coefficients widened
+ *                to double as glpk receives them, objective sums in double in ascending i.  Where several allocations
+ *                reach the optimum the lexicographically greatest is taken (most bits to subspace 0, then 1, ...):
+ *                glpk's choice among ties is unknown and not reproduced.  The reference's repair loop for totalBit <
+ *                mBitBudget (VAQ.cpp:473-498) cannot trigger under the equality constraint and is not restated.
+ *                VAQHIP_EINVAL when no allocation satisfies the constraints (the reference asserts).
+ *   composite    vaqhip_train_rotation*: moment -> eigen -> plan -> allocation.  eigvec_out: float D x D, columns in
+ *                balanced order -- what vaqhip_project, vaqhip_fit_codebooks and vaqhip_index_create take;
+ *                eigenvalues_out[D] in that order (may be NULL); bits_out[M] (entries from highest_subs on are 0);
+ *                highest_subs_out.  LIMIT: when percent_var < 1 leaves a subspace with 0 bits or highest_subs < M the
+ *                outputs are returned as they are, and the caller must not pass them to vaqhip_fit_codebooks, which
+ *                takes 1..VAQHIP_MAX_BITS over all M subspaces (the chained forms of the adapters return
+ *                VAQHIP_EUNSUPPORTED there rather than guessing).
+ * Refused before any device work: null pointers, n < 1, n >= 2^31, D < 1, D > 4096 (VAQHIP_EINVAL), and the plan's
+ * refusals.  The host forms upload only the sample; the _device forms take device pointers for the rows and the
+ * matrices (eigenvalues, bits and highest_subs stay host values), work on `stream` and synchronise it.  The _u8 forms
+ * widen a byte where it is loaded: the float call's result on the widened rows, bit for bit.  The refiner forms read a
+ * single-device refiner's resident rows of either type in place; VAQHIP_ESTATE without rows.  Not provided: the
+ * multi-device forms.
+ * ------------------------------------------------------------------------- */
+int vaqhip_train_moment(int device_id, const float *X_rowmajor, int64_t n, int D, double *cov_out, float *cov_f_out);
+int vaqhip_train_moment_device(int device_id, const float *d_X, int64_t n, int D, double *d_cov_out, float *d_cov_f_out,
+                               void *stream);
+int vaqhip_train_moment_u8(int device_id, const uint8_t *X_rowmajor, int64_t n, int D, double *cov_out, float *cov_f_out);
+int vaqhip_train_moment_u8_device(int device_id, const uint8_t *d_X, int64_t n, int D, double *d_cov_out,
+                                  float *d_cov_f_out, void *stream);
+int vaqhip_sym_eigen_device(int device_id, double *d_A, int D, double *d_values, double *d_vectors, int *sweeps_out,
+                            void *stream);
+int vaqhip_sym_eigen_host(double *A, int D, double *values, double *vectors, int *sweeps_out);
+int vaqhip_train_plan(const float *eigenvalues, int D, int M, float percent_var, int min_bits, int max_bits,
+                      int *sorted_out, int *order_out, float *var_out, float *cum_out, int *highest_subs_out, int *lb_out,
+                      int *k_out, int *swaps_kept_out);
+int vaqhip_allocate_bits(const float *c, int H, const int *lb, int max_bits, const int *k, int budget, int *bits_out,
+                         double *objective_out);
+int vaqhip_train_rotation(int device_id, const float *X_rowmajor, int64_t n, int D, int M, int bit_budget, int min_bits,
+                          int max_bits, float percent_var, float *eigvec_out, float *eigenvalues_out, int *bits_out,
+                          int *highest_subs_out);
+int vaqhip_train_rotation_device(int device_id, const float *d_X, int64_t n, int D, int M, int bit_budget, int min_bits,
+                                 int max_bits, float percent_var, float *d_eigvec_out, float *eigenvalues_out,
+                                 int *bits_out, int *highest_subs_out, void *stream);
+int vaqhip_train_rotation_u8(int device_id, const uint8_t *X_rowmajor, int64_t n, int D, int M, int bit_budget,
+                             int min_bits, int max_bits, float percent_var, float *eigvec_out, float *eigenvalues_out,
+                             int *bits_out, int *highest_subs_out);
+int vaqhip_train_rotation_u8_device(int device_id, const uint8_t *d_X, int64_t n, int D, int M, int bit_budget,
+                                    int min_bits, int max_bits, float percent_var, float *d_eigvec_out,
+                                    float *eigenvalues_out, int *bits_out, int *highest_subs_out, void *stream);
+typedef struct {
+  float total_ms;               /* host time of the last vaqhip_*train_rotation* on this thread, uploads excluded */
+  float moment_ms, eigen_ms;    /* the second moment; the solver: sweeps, read-backs and the host finish */
+  float finish_ms;              /*   of eigen_ms: the host finish (norms, Rayleigh quotients, order, signs) */
+  float plan_ms;                /* the plan, the allocation and the outputs */
+  int sweeps;                   /* Jacobi sweeps that rotated */
+  int subspaces, dims;
+  int64_t sample_rows, rows;    /* rows summed; rows given */
+} vaqhip_train_timing;
+int vaqhip_last_train_timing(vaqhip_train_timing *out);  /* the calling thread's last composite */
 
 /* VAQ::refine (VAQ.cpp:849-876): exact squared L2 in the ORIGINAL space between each
  * query and its R candidate rows of the raw dataset, k best by the same k-min rule.  The sum is
@@ -532,6 +633,10 @@ int vaqhip_learn_quantization_from_refiner(vaqhip_index *ix, vaqhip_refiner *r, 
  * host arrays); VAQHIP_ESTATE on a refiner without rows */
 int vaqhip_refiner_fit_codebooks(vaqhip_refiner *r, int M, const int *bits, const float *eigvec_real_rowmajor,
                                  int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out);
+/* "Training from raw rows" above over the refiner's resident rows, float or byte, read in place (outputs: host arrays) */
+int vaqhip_refiner_train_moment(vaqhip_refiner *r, double *cov_out, float *cov_f_out);
+int vaqhip_refiner_train_rotation(vaqhip_refiner *r, int M, int bit_budget, int min_bits, int max_bits, float percent_var,
+                                  float *eigvec_out, float *eigenvalues_out, int *bits_out, int *highest_subs_out);
 
 /* Exhaustive form of the resident refiner: the true k nearest rows of every query, i.e. what vaqhip_refiner_refine
  * would return for the candidate list id_base, id_base + 1, ..., id_base + N - 1 in that order if R were allowed to be

@@ -382,7 +382,7 @@ public:
   // (empty: XTrain is in PCA space already), every centre the reference's bit for bit (vaqhip_fit_codebooks on
   // mDevice; after setDevices() vaqhip_multi_fit_codebooks: the rows cut over mDevices, subspace s fitted on device
   // s % G, the same centres bit for bit).  XTrain: raw rows, as wide as the index.  mCodebookIters / mCodebookNanRows: per subspace the
-  // reference's iter_count and the centres an empty cluster left NaN.  PCA and bit allocation stay the caller's.
+  // reference's iter_count and the centres an empty cluster left NaN.  PCA and bit allocation are the caller's, or train()'s below.
   std::vector<int> mCodebookIters, mCodebookNanRows;
   void fitCodebooks(const RowMatrixF &XTrain, int maxIter = 25) { fitCodebooksRows(XTrain.data(), (int64_t)XTrain.rows(), (int)XTrain.cols(), maxIter); }
   // from byte rows (readBVecsU8): the float overload's centres on the widened rows, bit for bit
@@ -405,7 +405,66 @@ public:
     });
   }
 
+  // VAQ::train (VAQ.cpp:11-524, and the codebook step above) from raw rows: driven by mBitBudget, mSubspaceNum,
+  // mPercentVarExplained, mMinBitsPerSubs, mMaxBitsPerSubs (parseMethodString sets them), it fills mEigenVectors (the
+  // columns in balanced order), mEigenValues (in that order), mBitsAlloc and mCentroidsPerSubs -- vaqhip_train_rotation
+  // on mDevice, then fitCodebooks.  What is the reference's and what is not (the solver's bits, glpk's choice among
+  // tied optima): include/vaqhip.h.  VAQHIP_EUNSUPPORTED when mPercentVarExplained < 1 leaves fewer than mSubspaceNum
+  // subspaces or one without bits (the codebook fit takes at least 1 bit everywhere), and after setDevices(): the
+  // training front half has no multi-device form.  mTrainSweeps: the Jacobi sweeps that rotated.
+  std::vector<float> mEigenValues;
+  int mTrainSweeps = 0;
+  void train(const RowMatrixF &XTrain, int maxIter = 25) { trainRows(XTrain.data(), (int64_t)XTrain.rows(), (int)XTrain.cols(), maxIter); }
+  // from byte rows (readBVecsU8): the float overload's result on the widened rows, bit for bit
+  void train(const RowMatrix<uint8_t> &XTrain, int maxIter = 25) { trainRows(XTrain.data(), (int64_t)XTrain.rows(), (int)XTrain.cols(), maxIter); }
+  // from the rows setRefineDataset() left on the device, float or byte, read in place
+  void trainRefineDataset(int maxIter = 25) {
+    if (!mDevices.empty()) throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: train has no multi-device form");
+    if (!rf_) throw Error(VAQHIP_ESTATE, "vaqhip: trainRefineDataset needs setRefineDataset() first");
+    trainWith(rf_dim_, [&](float *eig, float *ev, int *bits, int *highest) {
+      return vaqhip_refiner_train_rotation(rf_, mSubspaceNum, mBitBudget, mMinBitsPerSubs, mMaxBitsPerSubs,
+                                           mPercentVarExplained, eig, ev, bits, highest);
+    });
+    fitCodebooksRefineDataset(maxIter);
+  }
+
 private:
+  static int trainCall(int dev, const float *X, int64_t n, int D, int M, int B, int lo, int hi, float pv, float *eig,
+                       float *ev, int *bits, int *highest) {
+    return vaqhip_train_rotation(dev, X, n, D, M, B, lo, hi, pv, eig, ev, bits, highest);
+  }
+  static int trainCall(int dev, const uint8_t *X, int64_t n, int D, int M, int B, int lo, int hi, float pv, float *eig,
+                       float *ev, int *bits, int *highest) {
+    return vaqhip_train_rotation_u8(dev, X, n, D, M, B, lo, hi, pv, eig, ev, bits, highest);
+  }
+  template <class T> void trainRows(const T *X, int64_t n, int D, int maxIter) {
+    if (!mDevices.empty()) throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: train has no multi-device form");
+    trainWith(D, [&](float *eig, float *ev, int *bits, int *highest) {
+      return trainCall(mDevice, X, n, D, mSubspaceNum, mBitBudget, mMinBitsPerSubs, mMaxBitsPerSubs, mPercentVarExplained,
+                       eig, ev, bits, highest);
+    });
+    fitCodebooksRows(X, n, D, maxIter);
+  }
+  // the rotation and the bits into the members; the outputs are kept only when the allocation can be fitted
+  template <class Call> void trainWith(int D, Call call) {
+    const int M = mSubspaceNum;
+    if (M < 1 || D < 1) throw Error(VAQHIP_EINVAL, "vaqhip: train needs mSubspaceNum and rows");
+    RowMatrixF eig((size_t)D, (size_t)D);
+    std::vector<float> ev((size_t)D);
+    std::vector<int> bits((size_t)M, 0);
+    int highest = 0;
+    check(call(eig.data(), ev.data(), bits.data(), &highest));
+    bool fits = highest == M;
+    for (int s = 0; s < highest; s++) fits = fits && bits[(size_t)s] >= 1;
+    if (!fits)
+      throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: train: the allocation leaves a subspace without bits (mPercentVarExplained < 1): "
+                                       "the codebook fit takes at least 1 bit in every subspace");
+    vaqhip_train_timing tt;
+    if (vaqhip_last_train_timing(&tt) == VAQHIP_OK) mTrainSweeps = tt.sweeps;
+    mEigenVectors = eig;
+    mEigenValues = ev;
+    mBitsAlloc = bits;
+  }
   static int fitCodebooksCall(int dev, const float *X, int64_t n, int D, int M, const int *bits, const float *eig, int it,
                               float *cent, int *iters, int *nan) {
     return vaqhip_fit_codebooks(dev, X, n, D, M, bits, eig, it, cent, iters, nan);

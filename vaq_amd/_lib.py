@@ -61,12 +61,16 @@ SYMBOLS = [
     "vaqhip_refiner_fit_codebooks", "vaqhip_fit_codebooks_set_timing", "vaqhip_last_fit_codebooks_timing",
     "vaqhip_multi_fit_codebooks", "vaqhip_multi_fit_codebooks_u8", "vaqhip_multi_refiner_fit_codebooks",
     "vaqhip_multi_last_fit_codebooks_timing",
+    "vaqhip_train_moment", "vaqhip_train_moment_device", "vaqhip_train_moment_u8", "vaqhip_train_moment_u8_device",
+    "vaqhip_refiner_train_moment", "vaqhip_sym_eigen_device", "vaqhip_sym_eigen_host", "vaqhip_train_plan",
+    "vaqhip_allocate_bits", "vaqhip_train_rotation", "vaqhip_train_rotation_device", "vaqhip_train_rotation_u8",
+    "vaqhip_train_rotation_u8_device", "vaqhip_refiner_train_rotation", "vaqhip_last_train_timing",
 ]
 MAX_DEVICES = 16
 
 ERROR_NAMES = {
     -1: "EINVAL", -2: "EUNSUPPORTED", -3: "ENODEVICE", -4: "ENOMEM", -5: "EHIP",
-    -6: "ERANGE", -7: "ESTATE",
+    -6: "ERANGE", -7: "ESTATE", -8: "ENOCONV",
 }
 
 
@@ -110,6 +114,13 @@ class FitCodebooksTiming(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("gather_ms", C.c_float), ("assign_ms", C.c_float),
                 ("accumulate_ms", C.c_float), ("update_ms", C.c_float), ("iterations", C.c_int),
                 ("subspaces", C.c_int), ("dims", C.c_int), ("sample_rows", C.c_int64), ("rows", C.c_int64)]
+
+
+class TrainTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("moment_ms", C.c_float), ("eigen_ms", C.c_float), ("finish_ms", C.c_float),
+                ("plan_ms", C.c_float),
+                ("sweeps", C.c_int), ("subspaces", C.c_int), ("dims", C.c_int), ("sample_rows", C.c_int64),
+                ("rows", C.c_int64)]
 
 
 class LearnTiming(C.Structure):
@@ -236,6 +247,22 @@ def load():
     L.vaqhip_refiner_fit_codebooks.argtypes = [vp, i32, C.POINTER(i32), vp, i32, vp, vp, vp]
     L.vaqhip_fit_codebooks_set_timing.argtypes = [i32]
     L.vaqhip_last_fit_codebooks_timing.argtypes = [C.POINTER(FitCodebooksTiming)]
+    for name in ("vaqhip_train_moment", "vaqhip_train_moment_u8"):
+        getattr(L, name).argtypes = [i32, vp, i64, i32, vp, vp]
+    for name in ("vaqhip_train_moment_device", "vaqhip_train_moment_u8_device"):
+        getattr(L, name).argtypes = [i32, vp, i64, i32, vp, vp, vp]
+    L.vaqhip_refiner_train_moment.argtypes = [vp, vp, vp]
+    L.vaqhip_sym_eigen_device.argtypes = [i32, vp, i32, vp, vp, C.POINTER(i32), vp]
+    L.vaqhip_sym_eigen_host.argtypes = [vp, i32, vp, vp, C.POINTER(i32)]
+    L.vaqhip_train_plan.argtypes = [vp, i32, i32, C.c_float, i32, i32, vp, vp, vp, vp, C.POINTER(i32), vp, vp,
+                                    C.POINTER(i32)]
+    L.vaqhip_allocate_bits.argtypes = [vp, i32, vp, i32, vp, i32, vp, C.POINTER(C.c_double)]
+    for name in ("vaqhip_train_rotation", "vaqhip_train_rotation_u8"):
+        getattr(L, name).argtypes = [i32, vp, i64, i32, i32, i32, i32, i32, C.c_float, vp, vp, vp, C.POINTER(i32)]
+    for name in ("vaqhip_train_rotation_device", "vaqhip_train_rotation_u8_device"):
+        getattr(L, name).argtypes = [i32, vp, i64, i32, i32, i32, i32, i32, C.c_float, vp, vp, vp, C.POINTER(i32), vp]
+    L.vaqhip_refiner_train_rotation.argtypes = [vp, i32, i32, i32, i32, C.c_float, vp, vp, vp, C.POINTER(i32)]
+    L.vaqhip_last_train_timing.argtypes = [C.POINTER(TrainTiming)]
     L.vaqhip_encode_lut.argtypes = [vp, vp, i64, i32, vp]
     L.vaqhip_encode_lut_device.argtypes = [vp, vp, i64, i32, vp, vp]
     L.vaqhip_refine.argtypes = [i32, vp, i32, i32, vp, i64, vp, i32, i32, vp, vp]

@@ -13,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vaq_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "vaq_amd", "lib")
 LIB = os.path.join(LIBDIR, "libvaqhip.so")
-SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_codebooks.hip", "vaq_fast.hip", "vaq_lutfit.hip", "vaq_learn.hip", "vaq_refine.hip", "vaq_exhaust.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp", "vaqhip_learn.cpp", "vaqhip_lutfit.cpp", "vaqhip_codebooks.cpp", "vaqhip_refiner.cpp",
+SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_codebooks.hip", "vaq_fast.hip", "vaq_lutfit.hip", "vaq_learn.hip", "vaq_refine.hip", "vaq_exhaust.hip", "vaq_train.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp", "vaqhip_learn.cpp", "vaqhip_lutfit.cpp", "vaqhip_codebooks.cpp", "vaqhip_train.cpp", "vaqhip_refiner.cpp",
            "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp", "vaqhip_multi_encode.cpp", "vaqhip_multi_lutfit.cpp", "vaqhip_multi_learn.cpp", "vaqhip_multi_codebooks.cpp", "vaqhip_rccl.cpp"]
 MULTI_REFINER_SOURCES = ("vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp")
 MULTI_ENCODE_SOURCE = "vaqhip_multi_encode.cpp"  # reads the multi refiner's resident rows: its headers too
@@ -49,6 +49,9 @@ LUTFIT_PLAN_HEADER = os.path.join(CSRC, "lutfit_multi_plan.h")  # owners, rounds
 LEARN_PLAN_HEADER = os.path.join(CSRC, "learn_plan.h")  # learnQuantization's host arithmetic: both forms, the loss kernel (no HIP)
 LEARN_HEADER = os.path.join(CSRC, "vaq_learn.h")  # the kernels of learnQuantization's device forms
 CODEBOOKS_PLAN_HEADER = os.path.join(CSRC, "fit_codebooks_plan.h")  # samples, offsets, key width of the codebook fit (no HIP)
+TRAIN_PLAN_HEADER = os.path.join(CSRC, "train_plan.h")  # sample, plan and exact bit allocation of the training front half (no HIP)
+TRAIN_ROT_HEADER = os.path.join(CSRC, "vaq_train_rot.h")  # the Jacobi rotation, ordering and host solver: kernels and host
+TRAIN_HEADER = os.path.join(CSRC, "vaq_train.h")  # the kernels of the training front half
 CODEBOOKS_MULTI_PLAN_HEADER = os.path.join(CSRC, "fit_codebooks_multi_plan.h")  # owners, sub-plans, sample split of the sharded fit (no HIP)
 
 
@@ -66,6 +69,8 @@ def _deps(src: str):
         deps += [CODEBOOKS_PLAN_HEADER, KMEANS_SAMPLE_HEADER]
     if src == MULTI_CODEBOOKS_SOURCE:
         deps.append(CODEBOOKS_MULTI_PLAN_HEADER)
+    if src in ("vaq_train.hip", "vaqhip_train.cpp"):
+        deps += [TRAIN_PLAN_HEADER, TRAIN_ROT_HEADER, TRAIN_HEADER, KMEANS_SAMPLE_HEADER]
     if src in ("vaq_lutfit.hip", "vaqhip_lutfit.cpp", MULTI_LUTFIT_SOURCE, "vaq_learn.hip"):
         deps.append(LUTFIT_HEADER)
     if src in ("vaq_learn.hip", "vaqhip_learn.cpp", "vaqhip_fast.cpp"):

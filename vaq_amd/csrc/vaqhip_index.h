@@ -197,6 +197,12 @@ int learn_rows_device(vaqhip_index *ix, vaq::RowsRef d_X, int64_t n, int project
 // resident rows (n x D on `device`, complete); eigvec and the outputs are the host's
 int fit_codebooks_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits, const float *eigvec,
                               int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out);
+// vaqhip_train.cpp: vaqhip_train_moment's and vaqhip_train_rotation's bodies over rows resident on `device`, which
+// vaqhip_refiner.cpp calls over its resident rows (complete); the outputs are the host's
+int train_moment_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, double *cov_out, float *cov_f_out);
+int train_rotation_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, int M, int bit_budget, int min_bits,
+                               int max_bits, float percent_var, float *eigvec_out, float *eigenvalues_out, int *bits_out,
+                               int *highest_subs_out);
 
 // The preamble of an entry point: the index's lock, then its device current (put back when the scope ends).
 // rc: VAQHIP_OK, or what the entry returns at once -- ENTRY(ix) declares it and does so, as HIP_TRY would.

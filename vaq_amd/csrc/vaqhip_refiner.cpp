@@ -320,4 +320,21 @@ int vaqhip_refiner_fit_codebooks(vaqhip_refiner *r, int M, const int *bits, cons
                                    iters_out, nan_rows_out);
 }
 
+// the training front half over the resident rows, read in place (vaqhip_train.cpp does the rest)
+int vaqhip_refiner_train_moment(vaqhip_refiner *r, double *cov_out, float *cov_f_out) {
+  if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
+  std::lock_guard<std::mutex> lk(r->mu);
+  if (r->N == 0) return fail(VAQHIP_ESTATE, "the refiner holds no rows: vaqhip_refiner_set_rows first");
+  return train_moment_rows_device(r->device, r->rows.rows(), r->N, r->D, cov_out, cov_f_out);
+}
+
+int vaqhip_refiner_train_rotation(vaqhip_refiner *r, int M, int bit_budget, int min_bits, int max_bits, float percent_var,
+                                  float *eigvec_out, float *eigenvalues_out, int *bits_out, int *highest_subs_out) {
+  if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
+  std::lock_guard<std::mutex> lk(r->mu);
+  if (r->N == 0) return fail(VAQHIP_ESTATE, "the refiner holds no rows: vaqhip_refiner_set_rows first");
+  return train_rotation_rows_device(r->device, r->rows.rows(), r->N, r->D, M, bit_budget, min_bits, max_bits, percent_var,
+                                    eigvec_out, eigenvalues_out, bits_out, highest_subs_out);
+}
+
 }  // extern "C"

@@ -9,7 +9,7 @@ from typing import Optional, Sequence
 import numpy as np
 
 from . import _lib
-from ._adapt import _eig_f32, _ptr, _struct_dict, _u8_rows
+from ._adapt import _dptr, _eig_f32, _ptr, _stream, _struct_dict, _u8_rows
 
 
 def _fit_rows(X, u8: bool) -> np.ndarray:
@@ -95,6 +95,73 @@ def last_multi_fit_codebooks_timing() -> dict:
     t = _lib.MultiFitCodebooksTiming()
     _lib.check_multi(_lib.load().vaqhip_multi_last_fit_codebooks_timing(C.byref(t)))
     return _struct_dict(t, cut=("owner_subspaces",))
+
+
+def _train_rotation_call(D: int, M: int, call):
+    """The arrays around a vaqhip_*train_rotation call: (eigvec D x D float32, eigenvalues[D], bits[highest_subs],
+    highest_subs).  call(L, eigvec, eigenvalues, bits, highest) with eigvec None: the caller passes its own."""
+    M = int(M)
+    eig = np.empty((max(D, 1), max(D, 1)), np.float32)
+    ev = np.empty(max(D, 1), np.float32)
+    bits = np.zeros(max(M, 1), np.int32)
+    hi = C.c_int(0)
+    _lib.check(call(_lib.load(), _ptr(eig), _ptr(ev), _ptr(bits), C.byref(hi)))
+    return eig, ev, [int(b) for b in bits[:hi.value]], hi.value
+
+
+def train_rotation(X, M: int, bit_budget: int, min_bits: int, max_bits: int, percent_var: float = 1.0, device: int = 0):
+    """vaqhip_train_rotation*: the front half of VAQ::train from raw rows -- the second moment of the sampled rows
+    (in double, in a fixed order), its eigen-decomposition (Jacobi, on the device), the partial balance and the exact
+    bit allocation.  X: n x D rows, a host array (uint8 stays bytes, anything else becomes float32) or a contiguous
+    float32 / uint8 torch tensor on the device.  Returns (eigvec float32 D x D with its columns in balanced order,
+    eigenvalues[D] in that order, bits[highest_subs], highest_subs): eigvec and bits are what fit_codebooks and
+    VaqHip take.  With percent_var < 1 highest_subs may be below M or a subspace may get 0 bits: see train()."""
+    if hasattr(X, "data_ptr"):
+        import torch
+        if not (X.is_cuda and X.dim() == 2 and X.is_contiguous() and X.dtype in (torch.float32, torch.uint8)):
+            raise _lib.VaqHipError(-1, "device rows must be a contiguous float32 or uint8 n x D CUDA tensor")
+        n, D = (int(v) for v in X.shape)
+        fn = "vaqhip_train_rotation_u8_device" if X.dtype == torch.uint8 else "vaqhip_train_rotation_device"
+        d_eig = torch.empty((D, D), dtype=torch.float32, device=X.device)
+        _, ev, bits, hi = _train_rotation_call(D, M, lambda L, e, v, b, h: getattr(L, fn)(
+            X.device.index, _dptr(X), n, D, int(M), int(bit_budget), int(min_bits), int(max_bits), float(percent_var),
+            _dptr(d_eig), v, b, h, _stream(X)))
+        return d_eig.cpu().numpy(), ev, bits, hi
+    u8 = isinstance(X, np.ndarray) and X.dtype == np.uint8
+    X = _fit_rows(X, u8)
+    fn = "vaqhip_train_rotation" + ("_u8" if u8 else "")
+    return _train_rotation_call(X.shape[1], M, lambda L, e, v, b, h: getattr(L, fn)(
+        int(device), _ptr(X), X.shape[0], X.shape[1], int(M), int(bit_budget), int(min_bits), int(max_bits),
+        float(percent_var), e, v, b, h))
+
+
+def _check_fittable(M: int, bits, highest: int) -> None:
+    """What the chained forms refuse: fit_codebooks takes 1..15 bits over all M subspaces."""
+    if highest < int(M) or any(b < 1 for b in bits):
+        raise _lib.VaqHipError(-2, f"the allocation {list(bits)} over {highest} of {M} subspaces cannot be fitted: "
+                                   "fit_codebooks takes at least 1 bit in every subspace (percent_var < 1)")
+
+
+def train(X, M: int, bit_budget: int, min_bits: int, max_bits: int, percent_var: float = 1.0, device: int = 0,
+          max_iter: int = 25):
+    """train_rotation() followed by fit_codebooks() with its eigvec and bits, from host rows: (eigvec, bits,
+    centroids [M arrays (1 << bits[s]) x L]) -- an index from raw rows and a bit budget alone.  EUNSUPPORTED (-2)
+    where percent_var < 1 leaves highest_subs < M or a subspace without bits."""
+    if hasattr(X, "data_ptr"):
+        raise _lib.VaqHipError(-2, "train() chains fit_codebooks, which takes host rows: pass a host array, keep the rows "
+                                   "in a VaqRefiner and call its train(), or call train_rotation() on the tensor")
+    eig, _, bits, hi = train_rotation(X, M, bit_budget, min_bits, max_bits, percent_var, device)
+    _check_fittable(M, bits, hi)
+    u8 = isinstance(X, np.ndarray) and X.dtype == np.uint8
+    cents, _, _ = _fit_codebooks(X, M, bits, eig, max_iter, device, None, u8)
+    return eig, bits, cents
+
+
+def last_train_timing() -> dict:
+    """Figures of the calling thread's last train_rotation (vaqhip_last_train_timing)."""
+    t = _lib.TrainTiming()
+    _lib.check(_lib.load().vaqhip_last_train_timing(C.byref(t)))
+    return _struct_dict(t)
 
 
 def _fit_quantiles_call(D: int, bits, eigvec, call):

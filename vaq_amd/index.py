@@ -3,7 +3,7 @@ include/vaqhip.h.  This module only gathers the names; the code is one module pe
 
   single.py   NNMethod, LabelDistVec, VaqHip          fast.py    VaqHipFast
   refiner.py  VaqRefiner, VaqMultiRefiner             multi.py   VaqHipMulti
-  fits.py     fit_codebooks*, lut_fit_quantiles_multi*, their timing calls
+  fits.py     fit_codebooks*, lut_fit_quantiles_multi*, train_rotation, train, their timing calls
   merge.py    merge_topk_device, merge_topk_packed_device, merge_fast_device
   _adapt.py   what they share (pointers, row checks, the output pair and stream of a device call, handle lifetime)
 
@@ -14,7 +14,8 @@ from ._adapt import _ptr, _same, _u8_rows, _u8_rows_device, _wref  # noqa: F401
 from .fast import VaqHipFast  # noqa: F401
 from .fits import (_fit_codebooks_call, _fit_quantiles_call, fit_codebooks, fit_codebooks_timing,  # noqa: F401
                    fit_codebooks_u8, last_fit_codebooks_timing, last_lut_fit_multi_timing,
-                   last_multi_fit_codebooks_timing, lut_fit_quantiles_multi, lut_fit_quantiles_multi_u8)
+                   last_multi_fit_codebooks_timing, last_train_timing, lut_fit_quantiles_multi,
+                   lut_fit_quantiles_multi_u8, train, train_rotation)
 from .merge import merge_fast_device, merge_topk_device, merge_topk_packed_device  # noqa: F401
 from .multi import VaqHipMulti  # noqa: F401
 from .refiner import VaqMultiRefiner, VaqRefiner  # noqa: F401

@@ -11,7 +11,7 @@ import numpy as np
 
 from . import _lib
 from ._adapt import _Handle, _dptr, _f32_rows, _out_pair, _ptr, _stream, _struct_dict, _u8_rows
-from .fits import _fit_codebooks_call, _fit_quantiles_call
+from .fits import _check_fittable, _fit_codebooks_call, _fit_quantiles_call, _train_rotation_call
 from .single import LabelDistVec, _new_answer
 
 
@@ -190,6 +190,26 @@ class VaqRefiner(_RefinerBase):
         if hasattr(XTrain, "data_ptr"):
             return self._set_rows_device("set_rows_u8_device", XTrain, "uint8", id_base)
         super().set_rows_u8(XTrain, id_base)
+
+    def train_moment(self):
+        """The second moment of the sampled resident rows (vaqhip_refiner_train_moment): (float64 D x D, its float32
+        rounding)."""
+        cov, cov_f = np.empty((self.D, self.D), np.float64), np.empty((self.D, self.D), np.float32)
+        self._call("train_moment", _ptr(cov), _ptr(cov_f))
+        return cov, cov_f
+
+    def train_rotation(self, M: int, bit_budget: int, min_bits: int, max_bits: int, percent_var: float = 1.0):
+        """train_rotation() over the RAW rows held, float or byte, read where they are (vaqhip_refiner_train_rotation):
+        what train_rotation returns on the same rows, bit for bit."""
+        return _train_rotation_call(self.D, M, lambda L, e, v, b, h: L.vaqhip_refiner_train_rotation(
+            self._h, int(M), int(bit_budget), int(min_bits), int(max_bits), float(percent_var), e, v, b, h))
+
+    def train(self, M: int, bit_budget: int, min_bits: int, max_bits: int, percent_var: float = 1.0, max_iter: int = 25):
+        """train_rotation() then fit_codebooks() over the rows held: (eigvec, bits, centroids), as vaq_amd.train."""
+        eig, _, bits, hi = self.train_rotation(M, bit_budget, min_bits, max_bits, percent_var)
+        _check_fittable(M, bits, hi)
+        cents, _, _ = self.fit_codebooks(M, bits, eig, max_iter)
+        return eig, bits, cents
 
 
 class VaqMultiRefiner(_RefinerBase):
