@@ -39,6 +39,8 @@
 //                                           codes; with --devices and --refine-resident the rows are uploaded once, cut
 //                                           over the GPUs, and encoded where they lie -- the same codes either way)
 //               [--fit-codebooks --bits 8,8,... --dataset base.fvecs [--save c.bin] [--max-iter 25]]
+//               [--kmeans-ver 1]                 with --fit-codebooks or --train: subspaces above 8 bits are fitted
+//                                           hierarchically, 128 x 2^(bits-7) centres (demo_vaq's switch; 2 is refused)
 //                                          (instead of --centroids: the subspace codebooks are fitted on the GPU from
 //                                           the raw vectors by KMeans::staticFitSampling, the call of VAQ.cpp:644-649 --
 //                                           not the arma::kmeans call VAQ::train runs today; --eigen is applied first,
@@ -192,6 +194,12 @@ int main(int argc, char **argv) {
     VaqHipFast vaq;  // VaqHip plus the FAST method
     vaq.parseMethodString(a["method"]);
     if (!fit) vaq.mCentroidsPerSubs = loadCentroids(a["centroids"]);
+    if (a.count("kmeans-ver")) {  // demo_vaq's switch: 0 flat, 1 hierarchical (subspaces above 8 bits), 2 binary
+      const int ver = std::atoi(a["kmeans-ver"].c_str());
+      if (ver == 2) throw Error(VAQHIP_EUNSUPPORTED, "--kmeans-ver 2: binary k-means is not built");
+      if (ver != 0 && ver != 1) throw Error(VAQHIP_EINVAL, "--kmeans-ver takes 0 or 1");
+      vaq.mHierarchicalKmeans = ver == 1;
+    }
     if (!encode && !fit_only) vaq.mCodebook = loadCodebook(a["codebook"]);
     if (train) {  // the method string's min / max / var hold unless the flags name others
       if (a.count("devices")) throw Error(VAQHIP_EUNSUPPORTED, "--train has no multi-device form");

@@ -458,6 +458,73 @@ int vaqhip_fit_codebooks_set_timing(int on);                             /* per 
 int vaqhip_last_fit_codebooks_timing(vaqhip_fit_codebooks_timing *out);  /* the calling thread's last fit */
 
 /* ---------------------------------------------------------------------------
+ * The hierarchical form of the fit above: VAQ::train with mHierarchicalKmeans (demo_vaq --kmeans-ver 1; VAQ.cpp:535-594).
+ * Inputs and outputs are vaqhip_fit_codebooks's.  B = sum(bits), L = D / M, k_s = 1 << bits[s].
+ *   flat subspaces   bits[s] <= 8: fitted exactly as vaqhip_fit_codebooks fits them -- the same rows, seeds, Lloyd loop
+ *                    and NaN centres.  A call in which no subspace exceeds 8 bits IS vaqhip_fit_codebooks, bit for bit.
+ *   hierarchical     bits[s] > 8: two stages, K1 = 128 and K2 = 1 << (bits[s] - 7) centres.
+ *   rows R_s         rows_s = min(n, max(256 * k_s, 256 << (B / M))) (VAQ.cpp:535-536, integer division).  Row i of R_s
+ *                    is row randomPermutation(n)[i] of the projected matrix, for every rows_s, also when rows_s == n
+ *                    (VAQ.cpp:539-543).  The reference leaves the slice unfilled when rows_s < n: a defect, not a rule;
+ *                    here it is always filled.  Heads of one permutation are prefixes of each other: one gather of the
+ *                    largest serves every hierarchical subspace (and every flat one that samples).
+ *   stage 1          C1 = KMeans::staticFitSampling(R_s[:, s*L .. (s+1)*L), 128, max_iter) as that function behaves
+ *                    when handed those rows: with rows_s > 65536 it works on rows randomPermutation(rows_s)[0 .. 65536)
+ *                    of R_s; its seeds are the head of randomPermutation(rows it works on); its two OpenMP halves are
+ *                    the flat fit's.  This stands for the reference's arma::kmeans call there (armadillo: not
+ *                    reproduced) -- the substitution this library makes everywhere (see vaqhip_fit_codebooks).
+ *   membership       of ALL rows_s rows of R_s (getBelongsToCluster, VAQ.cpp:1272-1292): the nearest of the 128 centres
+ *                    by (x - c).squaredNorm() in Eigen's summation order (plain sequential for L < 8), centres
+ *                    ascending, strict <.  NO sqrt, unlike the Lloyd assign: two distinct squares whose roots round to
+ *                    one float choose different centres under the two rules.  Group i keeps its rows in ascending
+ *                    position within R_s.
+ *   stage 2          for i = 0..127: staticFitSampling(rows of group i, K2, max_iter) with its own seeds (the head of
+ *                    randomPermutation(m_i), m_i the group's rows), its own halves [0, ceil(m_i / 2)) and the rest, its
+ *                    own stopping and its own NaN centres.  Its centres are rows i * K2 .. (i + 1) * K2 - 1 of the
+ *                    subspace's block of centroids_out (VAQ.cpp:593).
+ *   iters_out[s]     the largest iteration count among the subspace's 129 fits; nan_rows_out[s] the NaN centres among
+ *                    its final k_s.
+ * The flat subspaces and every 128-centre fit run as ONE batch of the flat fit's phases; stage 2 of all groups of all
+ * hierarchical subspaces as one more, over a compact matrix regrouped by a stable sort.  A row meets 128 + K2 centres
+ * per iteration in place of k_s.
+ * Parity: VAQ.cpp does not compile, so the composition is not pinned against the compiled reference; each component is
+ * (staticFitSampling: tests/golden/codebooks; randomPermutation; Eigen's squaredNorm), and the oracle is the
+ * composition of their numpy restatements (tests/codebooks_hier_ref.py).
+ * Refused before any device work, the outputs untouched: everything vaqhip_fit_codebooks refuses, and rows_s < k_s for
+ * a hierarchical subspace.  Refused after stage 1, outputs untouched, the message naming subspace and group:
+ * VAQHIP_EINVAL when a stage-1 centre is NaN or a group is empty (the reference asserts "hierarchical kmeans failed"),
+ * when m_i < K2 (the reference seeds from rows out of bounds), when a row has no centre (squared distance NaN or
+ * >= FLT_MAX from all 128); VAQHIP_EUNSUPPORTED when m_i > max(256 * K2, 65536): there the reference's stage 2 would
+ * sample the group.  That happens under extreme skew, and regularly at 15 bits, where the average group already holds
+ * 256 * K2 = 65536 rows; it is left out on purpose.  Not built either: a multi-device form, mBinaryKmeans.
+ * The host forms upload all rows when a subspace is hierarchical.  _device and _u8 forms: as vaqhip_fit_codebooks's. */
+int vaqhip_fit_codebooks_hier(int device_id, const float *X_rowmajor, int64_t n, int D, int M, const int *bits,
+                              const float *eigvec_real_rowmajor, int max_iter, float *centroids_out, int *iters_out,
+                              int *nan_rows_out);
+int vaqhip_fit_codebooks_hier_device(int device_id, const float *d_X, int64_t n, int D, int M, const int *bits,
+                                     const float *d_eigvec, int max_iter, float *d_centroids_out, int *iters_out,
+                                     int *nan_rows_out, void *stream);
+int vaqhip_fit_codebooks_hier_u8(int device_id, const uint8_t *X_rowmajor, int64_t n, int D, int M, const int *bits,
+                                 const float *eigvec_real_rowmajor, int max_iter, float *centroids_out, int *iters_out,
+                                 int *nan_rows_out);
+int vaqhip_fit_codebooks_hier_u8_device(int device_id, const uint8_t *d_X, int64_t n, int D, int M, const int *bits,
+                                        const float *d_eigvec, int max_iter, float *d_centroids_out, int *iters_out,
+                                        int *nan_rows_out, void *stream);
+typedef struct {
+  float total_ms;                       /* host time of the last hierarchical fit on this thread, host copies excluded */
+  float stage1_ms;                      /* sources, seeds and the batch of flat subspaces and 128-centre fits */
+  float regroup_ms;                     /* membership, stable sort, group bounds, gather into the compact matrices */
+  float stage2_ms;                      /* the batch of all groups' K2-centre fits */
+  int groups;                           /* 128 per hierarchical subspace */
+  int min_group_rows, max_group_rows;   /* the smallest and the largest group */
+  int stage1_iterations, stage2_iterations;  /* the largest iteration count of a fit of the stage */
+  int hier_subspaces;                   /* 0: the call was the flat fit (stage1_ms = total_ms) */
+  int subspaces, dims;
+  int64_t rows;
+} vaqhip_fit_codebooks_hier_timing;
+int vaqhip_last_fit_codebooks_hier_timing(vaqhip_fit_codebooks_hier_timing *out);  /* the calling thread's last one */
+
+/* ---------------------------------------------------------------------------
  * Training from raw rows: the front half of VAQ::train (VAQ.cpp:11-524) -- the second moment of the sampled rows, its
  * eigen-decomposition, the partial balance of the leading dimensions and the ILP that hands each subspace its bits.
  * With vaqhip_fit_codebooks above an index is built from raw rows and a bit budget alone.  The parity contract:
@@ -633,6 +700,9 @@ int vaqhip_learn_quantization_from_refiner(vaqhip_index *ix, vaqhip_refiner *r, 
  * host arrays); VAQHIP_ESTATE on a refiner without rows */
 int vaqhip_refiner_fit_codebooks(vaqhip_refiner *r, int M, const int *bits, const float *eigvec_real_rowmajor,
                                  int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out);
+/* vaqhip_fit_codebooks_hier above over the refiner's resident rows, float or byte, read in place */
+int vaqhip_refiner_fit_codebooks_hier(vaqhip_refiner *r, int M, const int *bits, const float *eigvec_real_rowmajor,
+                                      int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out);
 /* "Training from raw rows" above over the refiner's resident rows, float or byte, read in place (outputs: host arrays) */
 int vaqhip_refiner_train_moment(vaqhip_refiner *r, double *cov_out, float *cov_f_out);
 int vaqhip_refiner_train_rotation(vaqhip_refiner *r, int M, int bit_budget, int min_bits, int max_bits, float percent_var,

@@ -383,6 +383,11 @@ public:
   // mDevice; after setDevices() vaqhip_multi_fit_codebooks: the rows cut over mDevices, subspace s fitted on device
   // s % G, the same centres bit for bit).  XTrain: raw rows, as wide as the index.  mCodebookIters / mCodebookNanRows: per subspace the
   // reference's iter_count and the centres an empty cluster left NaN.  PCA and bit allocation are the caller's, or train()'s below.
+  // mHierarchicalKmeans (demo_vaq --kmeans-ver 1, VAQ.cpp:546-594): every subspace above 8 bits is fitted as 128 centres
+  // and 1 << (bits - 7) centres inside each of their groups (vaqhip_fit_codebooks_hier; include/vaqhip.h has the
+  // contract).  fitCodebooks, fitCodebooksRefineDataset and train honour it; after setDevices() it is
+  // VAQHIP_EUNSUPPORTED: the hierarchical fit has no multi-device form.  mBinaryKmeans is not built.
+  bool mHierarchicalKmeans = false;
   std::vector<int> mCodebookIters, mCodebookNanRows;
   void fitCodebooks(const RowMatrixF &XTrain, int maxIter = 25) { fitCodebooksRows(XTrain.data(), (int64_t)XTrain.rows(), (int)XTrain.cols(), maxIter); }
   // from byte rows (readBVecsU8): the float overload's centres on the widened rows, bit for bit
@@ -392,6 +397,7 @@ public:
   void fitCodebooksRefineDataset(int maxIter = 25) {
     if (!(mDevices.empty() ? (bool)rf_ : (bool)mrf_))
       throw Error(VAQHIP_ESTATE, "vaqhip: fitCodebooksRefineDataset needs setRefineDataset() first");
+    refuseHierarchicalMulti();
     if (mrf_) {
       fitCodebooksWith(rf_dim_, [&](const float *eig, float *cent) {
         return vaqhip_multi_refiner_fit_codebooks(mrf_, mHighestSubs(), mBitsAlloc.data(), eig, maxIter, cent,
@@ -400,8 +406,8 @@ public:
       return;
     }
     fitCodebooksWith(rf_dim_, [&](const float *eig, float *cent) {
-      return vaqhip_refiner_fit_codebooks(rf_, mHighestSubs(), mBitsAlloc.data(), eig, maxIter, cent, mCodebookIters.data(),
-                                          mCodebookNanRows.data());
+      return (mHierarchicalKmeans ? vaqhip_refiner_fit_codebooks_hier : vaqhip_refiner_fit_codebooks)(
+          rf_, mHighestSubs(), mBitsAlloc.data(), eig, maxIter, cent, mCodebookIters.data(), mCodebookNanRows.data());
     });
   }
 
@@ -465,13 +471,17 @@ private:
     mEigenValues = ev;
     mBitsAlloc = bits;
   }
-  static int fitCodebooksCall(int dev, const float *X, int64_t n, int D, int M, const int *bits, const float *eig, int it,
-                              float *cent, int *iters, int *nan) {
-    return vaqhip_fit_codebooks(dev, X, n, D, M, bits, eig, it, cent, iters, nan);
+  void refuseHierarchicalMulti() const {
+    if (mHierarchicalKmeans && !mDevices.empty())
+      throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: mHierarchicalKmeans has no multi-device form");
   }
-  static int fitCodebooksCall(int dev, const uint8_t *X, int64_t n, int D, int M, const int *bits, const float *eig, int it,
-                              float *cent, int *iters, int *nan) {
-    return vaqhip_fit_codebooks_u8(dev, X, n, D, M, bits, eig, it, cent, iters, nan);
+  int fitCodebooksCall(int dev, const float *X, int64_t n, int D, int M, const int *bits, const float *eig, int it,
+                       float *cent, int *iters, int *nan) const {
+    return (mHierarchicalKmeans ? vaqhip_fit_codebooks_hier : vaqhip_fit_codebooks)(dev, X, n, D, M, bits, eig, it, cent, iters, nan);
+  }
+  int fitCodebooksCall(int dev, const uint8_t *X, int64_t n, int D, int M, const int *bits, const float *eig, int it,
+                       float *cent, int *iters, int *nan) const {
+    return (mHierarchicalKmeans ? vaqhip_fit_codebooks_hier_u8 : vaqhip_fit_codebooks_u8)(dev, X, n, D, M, bits, eig, it, cent, iters, nan);
   }
   static int fitCodebooksCall(const std::vector<int> &devs, const float *X, int64_t n, int D, int M, const int *bits,
                               const float *eig, int it, float *cent, int *iters, int *nan) {
@@ -482,6 +492,7 @@ private:
     return vaqhip_multi_fit_codebooks_u8((int)devs.size(), devs.data(), X, n, D, M, bits, eig, it, cent, iters, nan);
   }
   template <class T> void fitCodebooksRows(const T *X, int64_t n, int D, int maxIter) {
+    refuseHierarchicalMulti();
     if (!mDevices.empty()) {
       fitCodebooksWith(D, [&](const float *eig, float *cent) {
         return fitCodebooksCall(mDevices, X, n, D, mHighestSubs(), mBitsAlloc.data(), eig, maxIter, cent, mCodebookIters.data(),

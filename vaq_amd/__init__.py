@@ -14,6 +14,8 @@ Product surface:
   fit_codebooks(devices=[...])  the same fit with the rows cut over several GPUs, one owner per subspace, bit for bit;
                               VaqMultiRefiner.fit_codebooks over sharded resident rows; last_multi_fit_codebooks_timing
   vaq_amd.train_rotation      VAQ::train's front half from raw rows: second-moment PCA and variance-aware bits
+  vaq_amd.fit_codebooks_hier  the hierarchical form (--kmeans-ver 1): subspaces above 8 bits as 128 x 2^(bits-7) centres;
+                              fit_codebooks_hier_u8, VaqRefiner.fit_codebooks_hier, last_fit_codebooks_hier_timing
   vaq_amd.train               the same chained into fit_codebooks; VaqRefiner.train_rotation / .train over resident rows
 There is no CPU path: importing works anywhere, but every compute call needs
 the HIP library and a GPU and raises otherwise.
@@ -23,9 +25,11 @@ from .index import LabelDistVec, NNMethod, VaqHip, VaqHipFast, VaqHipMulti, VaqM
 from .index import last_lut_fit_multi_timing, lut_fit_quantiles_multi, lut_fit_quantiles_multi_u8  # noqa: F401
 from .index import fit_codebooks, fit_codebooks_timing, fit_codebooks_u8, last_fit_codebooks_timing  # noqa: F401
 from .index import last_multi_fit_codebooks_timing  # noqa: F401
+from .index import fit_codebooks_hier, fit_codebooks_hier_u8, last_fit_codebooks_hier_timing  # noqa: F401
 from .index import last_train_timing, train, train_rotation  # noqa: F401
 
 __all__ = ["VaqHip", "VaqHipFast", "VaqHipMulti", "VaqRefiner", "VaqMultiRefiner", "NNMethod", "LabelDistVec", "VaqHipError", "load", "lib_path",
            "lut_fit_quantiles_multi", "lut_fit_quantiles_multi_u8", "last_lut_fit_multi_timing",
            "fit_codebooks", "fit_codebooks_u8", "fit_codebooks_timing", "last_fit_codebooks_timing",
-           "last_multi_fit_codebooks_timing", "train_rotation", "train", "last_train_timing"]
+           "last_multi_fit_codebooks_timing", "fit_codebooks_hier", "fit_codebooks_hier_u8",
+           "last_fit_codebooks_hier_timing", "train_rotation", "train", "last_train_timing"]

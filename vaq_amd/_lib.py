@@ -61,6 +61,8 @@ SYMBOLS = [
     "vaqhip_refiner_fit_codebooks", "vaqhip_fit_codebooks_set_timing", "vaqhip_last_fit_codebooks_timing",
     "vaqhip_multi_fit_codebooks", "vaqhip_multi_fit_codebooks_u8", "vaqhip_multi_refiner_fit_codebooks",
     "vaqhip_multi_last_fit_codebooks_timing",
+    "vaqhip_fit_codebooks_hier", "vaqhip_fit_codebooks_hier_device", "vaqhip_fit_codebooks_hier_u8",
+    "vaqhip_fit_codebooks_hier_u8_device", "vaqhip_refiner_fit_codebooks_hier", "vaqhip_last_fit_codebooks_hier_timing",
     "vaqhip_train_moment", "vaqhip_train_moment_device", "vaqhip_train_moment_u8", "vaqhip_train_moment_u8_device",
     "vaqhip_refiner_train_moment", "vaqhip_sym_eigen_device", "vaqhip_sym_eigen_host", "vaqhip_train_plan",
     "vaqhip_allocate_bits", "vaqhip_train_rotation", "vaqhip_train_rotation_device", "vaqhip_train_rotation_u8",
@@ -114,6 +116,13 @@ class FitCodebooksTiming(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("gather_ms", C.c_float), ("assign_ms", C.c_float),
                 ("accumulate_ms", C.c_float), ("update_ms", C.c_float), ("iterations", C.c_int),
                 ("subspaces", C.c_int), ("dims", C.c_int), ("sample_rows", C.c_int64), ("rows", C.c_int64)]
+
+
+class FitCodebooksHierTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("stage1_ms", C.c_float), ("regroup_ms", C.c_float), ("stage2_ms", C.c_float),
+                ("groups", C.c_int), ("min_group_rows", C.c_int), ("max_group_rows", C.c_int),
+                ("stage1_iterations", C.c_int), ("stage2_iterations", C.c_int), ("hier_subspaces", C.c_int),
+                ("subspaces", C.c_int), ("dims", C.c_int), ("rows", C.c_int64)]
 
 
 class TrainTiming(C.Structure):
@@ -240,11 +249,14 @@ def load():
     L.vaqhip_lut_fit_set_timing.argtypes = [i32]
     L.vaqhip_last_lut_fit_timing.argtypes = [C.POINTER(LutFitTiming)]
     L.vaqhip_index_set_lut_quantiles.argtypes = [vp, vp]
-    for name in ("vaqhip_fit_codebooks", "vaqhip_fit_codebooks_u8"):
+    for name in ("vaqhip_fit_codebooks", "vaqhip_fit_codebooks_u8", "vaqhip_fit_codebooks_hier", "vaqhip_fit_codebooks_hier_u8"):
         getattr(L, name).argtypes = [i32, vp, i64, i32, i32, C.POINTER(i32), vp, i32, vp, vp, vp]
-    for name in ("vaqhip_fit_codebooks_device", "vaqhip_fit_codebooks_u8_device"):
+    for name in ("vaqhip_fit_codebooks_device", "vaqhip_fit_codebooks_u8_device", "vaqhip_fit_codebooks_hier_device",
+                 "vaqhip_fit_codebooks_hier_u8_device"):
         getattr(L, name).argtypes = [i32, vp, i64, i32, i32, C.POINTER(i32), vp, i32, vp, vp, vp, vp]
     L.vaqhip_refiner_fit_codebooks.argtypes = [vp, i32, C.POINTER(i32), vp, i32, vp, vp, vp]
+    L.vaqhip_refiner_fit_codebooks_hier.argtypes = [vp, i32, C.POINTER(i32), vp, i32, vp, vp, vp]
+    L.vaqhip_last_fit_codebooks_hier_timing.argtypes = [C.POINTER(FitCodebooksHierTiming)]
     L.vaqhip_fit_codebooks_set_timing.argtypes = [i32]
     L.vaqhip_last_fit_codebooks_timing.argtypes = [C.POINTER(FitCodebooksTiming)]
     for name in ("vaqhip_train_moment", "vaqhip_train_moment_u8"):

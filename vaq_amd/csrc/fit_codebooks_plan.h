@@ -80,6 +80,82 @@ inline Plan make_plan(int64_t n, int M, const int *bits) {
   return p;
 }
 
+// ---- the batch as the kernels address it ----
+// One fit of a batch: a subspace of the flat fit, or one of the 129 fits of a hierarchical subspace
+// (fit_codebooks_hier_plan.h).  Its rows are rows [row0, row0 + rows) of source matrix `src`, `stride` floats apart,
+// its slice the L floats from column `col` on.  Centre c of half h owns run run_off + h * k + c; its row r emits pair
+// pair_off + r with value r.
+struct Fit {
+  int k;             // centres
+  int rows;          // rows it works on
+  int half;          // half_rows(rows)
+  int run_off;       // first of its 2 * k runs (= sort keys)
+  int cent_off;      // its centres in the centre table, in centres
+  int src;           // which of the batch's source matrices it reads
+  int stride;        // floats between two rows of that matrix
+  int col;           // first column of its slice
+  int64_t row0;      // its first row in that matrix
+  int64_t pair_off;  // first of its (key, row) pairs
+};
+// rows [row0, row0 + tile rows) of fit `fit`: what one workgroup of the assign kernel takes where the fits differ
+// widely in size (a grid of (largest fit's tiles, fits) would be mostly empty)
+struct Tile {
+  int fit;
+  int row0;
+};
+constexpr int SRC_SAMPLE = 0, SRC_FULL = 1, SRC_EXTRA = 2, N_SOURCES = 3;
+
+struct Batch {
+  std::vector<Fit> fit;
+  std::vector<Tile> tile;  // empty: the assign grid is (tiles of the largest fit, fits)
+  int64_t n_pairs = 0;     // sum of rows
+  int64_t rows_max = 0;
+  int n_runs = 0;          // sum of 2 * k
+  int n_cent = 0;          // centres the centre table spans: the largest cent_off + k
+  int k_max = 0;
+  unsigned key_bits = 1;   // the smallest with 1 << key_bits >= n_runs
+};
+
+// bytes of LDS the assign kernel's tile of slices may take; wider slices are read from global memory
+constexpr int TILE_BYTES = 40 * 1024;
+// rows a workgroup of the assign kernel takes: the widest workgroup whose tile of slices fits, at least a wavefront
+inline int assign_tile_rows(int L) {
+  int R = 256;
+  while (R > 64 && (size_t)R * L * sizeof(float) > (size_t)TILE_BYTES) R >>= 1;
+  return R;
+}
+
+inline void batch_add(Batch &b, int k, int rows, int cent_off, int src, int stride, int col, int64_t row0) {
+  Fit f;
+  f.k = k;
+  f.rows = rows;
+  f.half = half_rows(rows);
+  f.run_off = b.n_runs;
+  f.cent_off = cent_off;
+  f.src = src;
+  f.stride = stride;
+  f.col = col;
+  f.row0 = row0;
+  f.pair_off = b.n_pairs;
+  b.fit.push_back(f);
+  b.n_runs += 2 * k;
+  b.n_pairs += rows;
+  b.n_cent = std::max(b.n_cent, cent_off + k);
+  b.k_max = std::max(b.k_max, k);
+  b.rows_max = std::max<int64_t>(b.rows_max, rows);
+  while (b.key_bits < 32 && ((uint64_t)1 << b.key_bits) < (uint64_t)b.n_runs) b.key_bits++;
+}
+
+// the flat fit's batch: subspace s reads columns [s * L, (s + 1) * L) of the full matrix or of the sample, D wide
+inline Batch make_batch(const Plan &p, int D, int L) {
+  Batch b;
+  for (size_t s = 0; s < p.sub.size(); s++) {
+    const Sub &d = p.sub[s];
+    batch_add(b, d.k, d.rows, d.cent_off, d.full ? SRC_FULL : SRC_SAMPLE, D, (int)s * L, 0);
+  }
+  return b;
+}
+
 }  // namespace cbfit
 }  // namespace vaq
 #endif

@@ -18,8 +18,11 @@
 // enter the sort in ascending row order and the sort is stable, so every run is the run the single fit would walk.
 // A subspace whose centres stopped changing is a fixed point: its assign step is skipped (its pairs are still there
 // from the iteration before), the rest recomputes the same centres.
+// The kernels address a fit through cbfit::Fit (source matrix, row stride, column, first row), so the same phases run
+// the hierarchical form's batches (codebooks_fit_hier below): 128-centre fits beside the flat subspaces, then the
+// K2-centre fits of all groups over a compact regrouped matrix, the assign kernel walking a table of row tiles.
 // No float atomics, no MFMA, no reassociation; compiled with -ffp-contract=off like every file of the library.
-#include "fit_codebooks_plan.h"
+#include "fit_codebooks_hier_plan.h"
 #include "kmeans_sample.h"
 #include "vaq_kernels.h"
 #include "vaq_restated.h"
@@ -37,8 +40,7 @@ namespace vaq {
 namespace {
 // floats of centres a workgroup of the assign kernel stages in LDS at a time
 constexpr int CB_STAGE_FLOATS = 4096;
-// bytes of LDS its tile of slices may take; wider slices are read from global memory
-constexpr int CB_TILE_BYTES = 40 * 1024;
+// (the LDS its tile of slices may take, and with it the rows per workgroup: cbfit::assign_tile_rows)
 }  // namespace
 
 // out[i][j] = (float)X[rows[i]][j]: the sample in the reference's order, a byte widened where it is loaded
@@ -51,67 +53,88 @@ __global__ void cb_gather_kernel(const T *__restrict__ X, int D, const int *__re
   out[i] = (float)X[(int64_t)rows[r] * D + (i - r * D)];
 }
 
-// means[c] = slice s of row seed_rows[c] of the subspace's source (KMeans.hpp:516-520); grid.y = subspace
-__global__ void cb_seed_kernel(const float *__restrict__ Ps, const float *__restrict__ Pf, int D, int L,
-                               const cbfit::Sub *__restrict__ subs, const int *__restrict__ seed_rows,
-                               float *__restrict__ means) {
-  const int s = blockIdx.y;
-  const cbfit::Sub sd = subs[s];
-  const float *P = sd.full ? Pf : Ps;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= sd.k * L) return;
-  const int c = i / L, j = i % L;
-  means[(size_t)(sd.cent_off + c) * L + j] = P[(size_t)seed_rows[sd.cent_off + c] * D + (size_t)s * L + j];
+// the source matrices of a batch (cbfit::Fit::src indexes them; unused ones are null)
+struct CbSources {
+  const float *p[cbfit::N_SOURCES];
+};
+// the first float of a fit's slice of its row 0
+__device__ __forceinline__ const float *cb_fit_base(const CbSources &src, const cbfit::Fit &f) {
+  return src.p[f.src] + (size_t)f.row0 * f.stride + f.col;
 }
 
-// One row per thread, grid = (row tile, subspace); Ps: the gathered sample, Pf: the full matrix, the subspace reads
-// the one its Sub names (either may be null when no subspace reads it).  X_LDS: the workgroup's slices sit in LDS as [column][row] (each
-// thread reads its own column, conflict-free); else every thread reads its slice from global memory.  The
-// subspace's centres pass through LDS `stage` at a time and are read with wave-uniform addresses (broadcast).
-// Row r of subspace s: keys[pair_off + r] = run_off + half * k + centre, vals[pair_off + r] = r.
-template <bool X_LDS>
-__global__ void cb_assign_kernel(const float *__restrict__ Ps, const float *__restrict__ Pf, int D, int L,
-                                 const cbfit::Sub *__restrict__ subs, const float *__restrict__ means, int stage, const int *__restrict__ active,
+// out[i][j] = src[rows[i] (or i, rows null)][col + j], i < cnt, j < L: a column slice, gathered compactly
+__global__ void cb_slice_kernel(const float *__restrict__ src, int stride, int col, const int *__restrict__ rows, int64_t cnt,
+                                int L, float *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= cnt * L) return;
+  const int64_t r = i / L;
+  out[i] = src[(size_t)(rows ? rows[r] : r) * stride + col + (i - r * L)];
+}
+
+// means[c] = the slice of row seed_rows[c] of the fit's rows (KMeans.hpp:516-520); grid.y = fit
+__global__ void cb_seed_kernel(CbSources src, int L, const cbfit::Fit *__restrict__ fits, const int *__restrict__ seed_rows,
+                               float *__restrict__ means) {
+  const cbfit::Fit fd = fits[blockIdx.y];
+  const float *P = cb_fit_base(src, fd);
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= fd.k * L) return;
+  const int c = i / L, j = i % L;
+  means[(size_t)(fd.cent_off + c) * L + j] = P[(size_t)seed_rows[fd.cent_off + c] * fd.stride + j];
+}
+
+// One row per thread.  Which rows a workgroup takes: with `tiles`, rows [row0, row0 + blockDim.x) of fit tiles[blockIdx.x]
+// (fits of very different sizes: no workgroup is launched to find itself past its fit's end); without, grid = (row
+// tile, fit).  X_LDS: the workgroup's slices sit in LDS as [column][row] (each thread reads its own column,
+// conflict-free); else every thread reads its slice from global memory.  The fit's centres pass through LDS `stage` at
+// a time and are read with wave-uniform addresses (broadcast).
+// Lloyd (MEMBER false): the distance is sqrt(squaredNorm), row r of fit f: keys[pair_off + r] = run_off + half * k +
+// centre, vals[pair_off + r] = r.  MEMBER: the hierarchical fit's split of R_s by nearest stage-1 centre
+// (getBelongsToCluster, VAQ.cpp:1272-1292): the squaredNorm itself is compared, NO sqrt -- two distinct squares whose
+// roots round to one float choose differently --, and the key is run_off + centre.
+template <bool X_LDS, bool MEMBER>
+__global__ void cb_assign_kernel(CbSources src, int L, const cbfit::Fit *__restrict__ fits, const cbfit::Tile *__restrict__ tiles,
+                                 const float *__restrict__ means, int stage, const int *__restrict__ active,
                                  unsigned *__restrict__ keys, unsigned *__restrict__ vals, int *__restrict__ no_centre) {
   extern __shared__ float cb_lds[];
-  const int s = blockIdx.y;
-  const cbfit::Sub sd = subs[s];
   const int R = blockDim.x, tid = threadIdx.x;
-  const int64_t r0 = (int64_t)blockIdx.x * R;
-  if (r0 >= sd.rows || !active[s]) return;  // (the whole workgroup)
+  const int f = tiles ? tiles[blockIdx.x].fit : (int)blockIdx.y;
+  const int64_t r0 = tiles ? (int64_t)tiles[blockIdx.x].row0 : (int64_t)blockIdx.x * R;
+  const cbfit::Fit fd = fits[f];
+  if (r0 >= fd.rows || (active && !active[f])) return;  // (the whole workgroup)
   float *cs = cb_lds;                        // [stage][L]
   float *xt = cb_lds + (size_t)stage * L;    // [L][R]
   const int64_t r = r0 + tid;
-  const int64_t rr = r < sd.rows ? r : sd.rows - 1;  // (rows past the end work on the last row and store nothing)
-  const float *slice0 = (sd.full ? Pf : Ps) + (size_t)s * L;
+  const int64_t rr = r < fd.rows ? r : fd.rows - 1;  // (rows past the end work on the last row and store nothing)
+  const float *slice0 = cb_fit_base(src, fd);
+  const int D = fd.stride;
   if (X_LDS) {
     for (int i = tid; i < R * L; i += R) {
       const int row = i / L, col = i % L;
-      xt[(size_t)col * R + row] = r0 + row < sd.rows ? slice0[(size_t)(r0 + row) * D + col] : 0.0f;
+      xt[(size_t)col * R + row] = r0 + row < fd.rows ? slice0[(size_t)(r0 + row) * D + col] : 0.0f;
     }
   }
-  const float *m = means + (size_t)sd.cent_off * L;
+  const float *m = means + (size_t)fd.cent_off * L;
   float best = FLT_MAX;
   int idx = -1;
-  for (int c0 = 0; c0 < sd.k; c0 += stage) {
-    const int cn = min(stage, sd.k - c0);
+  for (int c0 = 0; c0 < fd.k; c0 += stage) {
+    const int cn = min(stage, fd.k - c0);
     __syncthreads();  // the last stage is read, the tile is written
     for (int i = tid; i < cn * L; i += R) cs[i] = m[(size_t)c0 * L + i];
     __syncthreads();
     for (int c = 0; c < cn; c++) {
       const float d2 = X_LDS ? sq_norm_eigen<false>(xt + tid, R, cs + (size_t)c * L, L)
                              : sq_norm_eigen<true>(slice0 + (size_t)rr * D, 1, cs + (size_t)c * L, L);
-      const float dist = sqrtf(d2);
+      const float dist = MEMBER ? d2 : sqrtf(d2);
       if (dist < best) {
         best = dist;
         idx = c0 + c;
       }
     }
   }
-  if (r < sd.rows) {
-    if (idx < 0) no_centre[s] = 1;  // the reference indexes row -1 here
-    keys[sd.pair_off + r] = (unsigned)(sd.run_off + (r >= sd.half ? sd.k : 0) + max(idx, 0));
-    vals[sd.pair_off + r] = (unsigned)r;
+  if (r < fd.rows) {
+    if (idx < 0) no_centre[f] = 1;  // the reference indexes row -1 here
+    keys[fd.pair_off + r] = (unsigned)(fd.run_off + (!MEMBER && r >= fd.half ? fd.k : 0) + max(idx, 0));
+    vals[fd.pair_off + r] = (unsigned)r;
   }
 }
 
@@ -125,35 +148,34 @@ __global__ void cb_bounds_kernel(const unsigned *__restrict__ keys, int n, int *
   if (i == n - 1 || keys[i + 1] != k) end[k] = i + 1;
 }
 
-// part[run * L + col] = the rows of that run added from +0 in ascending row order; grid.y = subspace, neighbouring
+// part[run * L + col] = the rows of that run added from +0 in ascending row order; grid.y = fit, neighbouring
 // threads take neighbouring columns of the same run
-__global__ void cb_accumulate_kernel(const float *__restrict__ Ps, const float *__restrict__ Pf, int D, int L,
-                                     const cbfit::Sub *__restrict__ subs, const unsigned *__restrict__ rows_sorted, const int *__restrict__ start,
+__global__ void cb_accumulate_kernel(CbSources src, int L, const cbfit::Fit *__restrict__ fits,
+                                     const unsigned *__restrict__ rows_sorted, const int *__restrict__ start,
                                      const int *__restrict__ end, float *__restrict__ part) {
-  const int s = blockIdx.y;
-  const cbfit::Sub sd = subs[s];
+  const cbfit::Fit fd = fits[blockIdx.y];
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= 2 * sd.k * L) return;
-  const int g = sd.run_off + t / L, col = t % L;
-  const float *x = (sd.full ? Pf : Ps) + (size_t)s * L + col;
+  if (t >= 2 * fd.k * L) return;
+  const int g = fd.run_off + t / L, col = t % L;
+  const float *x = cb_fit_base(src, fd) + col;
   float sum = 0.0f;
-  for (int i = start[g], e = end[g]; i < e; i++) sum += x[(size_t)rows_sorted[i] * D];
+  for (int i = start[g], e = end[g]; i < e; i++) sum += x[(size_t)rows_sorted[i] * fd.stride];
   part[(size_t)g * L + col] = sum;
 }
 
-// one wavefront per (centre, subspace) (KMeans.hpp:586-604); changed[s] is set when a centre of s was replaced
+// one wavefront per (centre, fit) (KMeans.hpp:586-604); changed[f] is set when a centre of fit f was replaced
 __global__ __launch_bounds__(64) void cb_update_kernel(const float *__restrict__ part, const int *__restrict__ start,
                                                       const int *__restrict__ end, int L,
-                                                      const cbfit::Sub *__restrict__ subs, float *__restrict__ means,
+                                                      const cbfit::Fit *__restrict__ fits, float *__restrict__ means,
                                                       int *__restrict__ changed) {
-  const int s = blockIdx.y;
-  const cbfit::Sub sd = subs[s];
+  const int f = blockIdx.y;
+  const cbfit::Fit fd = fits[f];
   const int c = blockIdx.x, lane = threadIdx.x;
-  if (c >= sd.k) return;
-  const int g0 = sd.run_off + c, g1 = g0 + sd.k;
+  if (c >= fd.k) return;
+  const int g0 = fd.run_off + c, g1 = g0 + fd.k;
   const int count = (end[g0] - start[g0]) + (end[g1] - start[g1]);
   const float *p0 = part + (size_t)g0 * L, *p1 = part + (size_t)g1 * L;
-  float *m = means + (size_t)(sd.cent_off + c) * L;
+  float *m = means + (size_t)(fd.cent_off + c) * L;
   bool differs = false;
   for (int j = lane; j < L; j += 64) {
     const float v = ((0.0f + p0[j]) + p1[j]) / (float)count;
@@ -161,7 +183,7 @@ __global__ __launch_bounds__(64) void cb_update_kernel(const float *__restrict__
   }
   if (!__any(differs)) return;
   for (int j = lane; j < L; j += 64) m[j] = ((0.0f + p0[j]) + p1[j]) / (float)count;
-  if (lane == 0) changed[s] = 1;
+  if (lane == 0) changed[f] = 1;
 }
 
 // ---- the sharded fit's shard step (vaqhip_multi_codebooks.cpp, DESIGN.md section 4f "Across shards") ----
@@ -278,6 +300,204 @@ namespace {
 double cb_ms_since(std::chrono::steady_clock::time_point t0) {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
+
+#define CB_TRY(expr)                          \
+  do {                                        \
+    if ((e = (expr)) != hipSuccess) return e; \
+  } while (0)
+
+// (buffers are freed on return, after the stream is synchronised)
+struct CbSync {
+  hipStream_t st;
+  bool armed;
+  ~CbSync() {
+    if (armed) (void)hipStreamSynchronize(st);
+  }
+};
+
+// The two sources of a fit and the buffers that hold them.  full: all n rows projected (or widened) once, for the
+// readers of all rows in their own order.  sample: the first S rows of randomPermutation(n), projected, every reader
+// of it working on a prefix -- gathered here (`gather`), or the caller's rows are the sample already.
+struct CbPrepared {
+  vaqhost::DevBuf rows, gathered, proj, all;
+  const float *full = nullptr, *sample = nullptr;
+};
+
+hipError_t cb_prepare(RowsRef d_X, int64_t n, int D, const float *d_eig, bool need_full, int64_t S, bool gather,
+                      CbPrepared &out, hipStream_t st) {
+  hipError_t e;
+  // rows x D of src as floats, projected where there is a rotation: in place when nothing is to be done, else in buf
+  auto projected = [&](RowsRef src, int64_t rows, vaqhost::DevBuf &buf, const float **res) -> hipError_t {
+    *res = static_cast<const float *>(src.p);
+    if (!d_eig && src.elem != 1) return hipSuccess;
+    hipError_t pe = buf.ensure((size_t)rows * D * sizeof(float));
+    if (pe != hipSuccess) return pe;
+    *res = buf.as<float>();
+    if (d_eig) return launch_project(src, rows, D, d_eig, buf.as<float>(), st, 0);  // unchecked, as VAQ::train projects
+    return launch_widen_rows_u8(static_cast<const uint8_t *>(src.p), rows * D, buf.as<float>(), st);
+  };
+  // ---- the full matrix, for the subspaces that do not sample: all n rows projected (or widened) once ----
+  if (need_full) CB_TRY(projected(d_X, n, out.all, &out.full));
+  // ---- the sample, for those that do: gathered once, every one of them works on a prefix of it ----
+  if (S > 0 && !gather) {
+    CB_TRY(projected(d_X, S, out.proj, &out.sample));  // (the caller's rows are the sample)
+  } else if (S > 0) {
+    const std::vector<int> rows = permutation_head(n, S);
+    CB_TRY(out.rows.ensure((size_t)S * sizeof(int)));
+    CB_TRY(out.gathered.ensure((size_t)S * D * sizeof(float)));
+    CB_TRY(hipMemcpyAsync(out.rows.p, rows.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, st));
+    const unsigned grid = (unsigned)((S * D + 255) / 256);
+    if (out.full || d_X.elem != 1)  // from the projected full matrix where there is one: a row's projection is its own
+      hipLaunchKernelGGL(cb_gather_kernel<float>, dim3(grid), dim3(256), 0, st,
+                         out.full ? out.full : static_cast<const float *>(d_X.p), D, out.rows.as<int>(), S,
+                         out.gathered.as<float>());
+    else
+      hipLaunchKernelGGL(cb_gather_kernel<uint8_t>, dim3(grid), dim3(256), 0, st, static_cast<const uint8_t *>(d_X.p), D,
+                         out.rows.as<int>(), S, out.gathered.as<float>());
+    CB_TRY(hipGetLastError());
+    CB_TRY(hipStreamSynchronize(st));  // (rows is the host's)
+    out.sample = out.gathered.as<float>();
+    if (!out.full && d_eig) CB_TRY(projected(RowsRef{out.gathered.p, 4}, S, out.proj, &out.sample));
+  }
+  return hipSuccess;
+}
+
+// launch shape of the assign kernel for slices of L floats and at most k_max centres per fit
+struct CbAssignShape {
+  int R, stage;
+  bool x_lds;
+  size_t lds;
+};
+CbAssignShape cb_assign_shape(int L, int k_max) {
+  CbAssignShape a;
+  a.R = cbfit::assign_tile_rows(L);
+  a.x_lds = (size_t)a.R * L * sizeof(float) <= (size_t)cbfit::TILE_BYTES;
+  a.stage = std::max(1, std::min(k_max, CB_STAGE_FLOATS / L));
+  a.lds = ((size_t)a.stage * L + (a.x_lds ? (size_t)a.R * L : 0)) * sizeof(float);
+  return a;
+}
+
+// the assign kernel over a batch: by its tile table (d_tiles, n_tiles) or, without one, over (row tile, fit)
+template <bool MEMBER>
+hipError_t cb_launch_assign(const CbSources &src, int L, const cbfit::Batch &b, const cbfit::Fit *d_fits,
+                            const cbfit::Tile *d_tiles, const float *d_means, const int *d_active, unsigned *keys,
+                            unsigned *vals, int *d_no_centre, hipStream_t st) {
+  const CbAssignShape a = cb_assign_shape(L, b.k_max);
+  const dim3 grid = d_tiles ? dim3((unsigned)b.tile.size()) : dim3((unsigned)((b.rows_max + a.R - 1) / a.R), (unsigned)b.fit.size());
+  if (a.x_lds)
+    hipLaunchKernelGGL((cb_assign_kernel<true, MEMBER>), grid, dim3(a.R), a.lds, st, src, L, d_fits, d_tiles, d_means, a.stage,
+                       d_active, keys, vals, d_no_centre);
+  else
+    hipLaunchKernelGGL((cb_assign_kernel<false, MEMBER>), grid, dim3(a.R), a.lds, st, src, L, d_fits, d_tiles, d_means, a.stage,
+                       d_active, keys, vals, d_no_centre);
+  return hipGetLastError();
+}
+
+// The Lloyd loop over a batch of fits: seeds from permutation_head(rows, k) of every fit's own rows, then one launch per
+// phase and iteration for ALL fits until every fit's centres stopped changing or max_iter.  The sources are complete on
+// `st`; d_means spans b.n_cent centres.  iters_out[fits] (host).  began: when the caller started preparing the
+// sources, for phases->gather_ms (null phases: no per-phase synchronisation).  Synchronises the stream.
+hipError_t cb_lloyd_batch(const CbSources &src, int L, const cbfit::Batch &b, int max_iter, float *d_means, int *iters_out,
+                          int *no_centre_out, CodebookPhases *phases, std::chrono::steady_clock::time_point began,
+                          hipStream_t st) {
+  const int F = (int)b.fit.size();
+  if (F < 1 || b.rows_max < 1 || b.n_pairs > 0x7fffffff || F > 65535) return hipErrorInvalidValue;
+  const int n_pairs = (int)b.n_pairs, n_runs = b.n_runs;
+  hipError_t e;
+  vaqhost::DevBuf b_fit, b_tile, b_seed, b_keys_in, b_keys_out, b_vals_in, b_vals_out, b_bounds, b_part, b_flags, b_temp;
+  CbSync sync_on_return{st, true};
+  auto t0 = began;
+
+  // ---- the batch's tables and the seeds ----
+  std::vector<int> seeds((size_t)b.n_cent, 0);
+  for (const cbfit::Fit &fd : b.fit) {
+    const std::vector<int> head = permutation_head(fd.rows, fd.k);
+    std::copy(head.begin(), head.end(), seeds.begin() + fd.cent_off);
+  }
+  CB_TRY(b_fit.ensure((size_t)F * sizeof(cbfit::Fit)));
+  CB_TRY(b_seed.ensure(seeds.size() * sizeof(int)));
+  CB_TRY(b_keys_in.ensure((size_t)n_pairs * 4));
+  CB_TRY(b_keys_out.ensure((size_t)n_pairs * 4));
+  CB_TRY(b_vals_in.ensure((size_t)n_pairs * 4));
+  CB_TRY(b_vals_out.ensure((size_t)n_pairs * 4));
+  CB_TRY(b_bounds.ensure((size_t)2 * n_runs * sizeof(int)));
+  CB_TRY(b_part.ensure((size_t)n_runs * L * sizeof(float)));
+  CB_TRY(b_flags.ensure((size_t)3 * F * sizeof(int)));
+  const cbfit::Fit *fits = b_fit.as<cbfit::Fit>();
+  const cbfit::Tile *tiles = nullptr;
+  if (!b.tile.empty()) {
+    CB_TRY(b_tile.ensure(b.tile.size() * sizeof(cbfit::Tile)));
+    CB_TRY(hipMemcpyAsync(b_tile.p, b.tile.data(), b.tile.size() * sizeof(cbfit::Tile), hipMemcpyHostToDevice, st));
+    tiles = b_tile.as<cbfit::Tile>();
+  }
+  unsigned *keys_in = b_keys_in.as<unsigned>(), *keys_out = b_keys_out.as<unsigned>();
+  unsigned *vals_in = b_vals_in.as<unsigned>(), *vals_out = b_vals_out.as<unsigned>();
+  int *start = b_bounds.as<int>(), *end = start + n_runs;
+  int *flags = b_flags.as<int>();  // changed[2][F] (this iteration's and the one before), then no_centre[F]
+  size_t temp_bytes = 0;
+  CB_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n_pairs, 0u,
+                                   b.key_bits, st));
+  CB_TRY(b_temp.ensure(temp_bytes ? temp_bytes : 16));
+  std::vector<int> host_flags((size_t)3 * F, 0);
+  for (int f = 0; f < F; f++) host_flags[(size_t)f] = 1;  // every fit starts active
+  CB_TRY(hipMemcpyAsync(b_fit.p, b.fit.data(), (size_t)F * sizeof(cbfit::Fit), hipMemcpyHostToDevice, st));
+  CB_TRY(hipMemcpyAsync(b_seed.p, seeds.data(), seeds.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  CB_TRY(hipMemcpyAsync(flags, host_flags.data(), host_flags.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  hipLaunchKernelGGL(cb_seed_kernel, dim3((unsigned)((b.k_max * L + 255) / 256), (unsigned)F), dim3(256), 0, st, src, L,
+                     fits, b_seed.as<int>(), d_means);
+  CB_TRY(hipGetLastError());
+  CB_TRY(hipStreamSynchronize(st));  // (the tables are the host's)
+  if (phases) phases->gather_ms += cb_ms_since(t0);
+
+  const dim3 acc_grid((unsigned)((2 * (int64_t)b.k_max * L + 255) / 256), (unsigned)F);
+
+  auto phase_end = [&](double *acc) -> hipError_t {
+    if (!phases) return hipSuccess;
+    const hipError_t pe = hipStreamSynchronize(st);
+    *acc += cb_ms_since(t0);
+    t0 = std::chrono::steady_clock::now();
+    return pe;
+  };
+  std::vector<char> done((size_t)F, 0);
+  for (int f = 0; f < F; f++) iters_out[f] = 0;
+  int no_centre = 0, n_done = 0;
+  t0 = std::chrono::steady_clock::now();
+  for (int it = 0; it < max_iter && n_done < F && !no_centre; it++) {
+    int *prev = flags + (size_t)(it & 1) * F, *now = flags + (size_t)((it + 1) & 1) * F;
+    CB_TRY(hipMemsetAsync(now, 0, (size_t)F * sizeof(int), st));
+    CB_TRY(hipMemsetAsync(start, 0, (size_t)2 * n_runs * sizeof(int), st));
+    CB_TRY(cb_launch_assign<false>(src, L, b, fits, tiles, d_means, prev, keys_in, vals_in, flags + 2 * F, st));
+    CB_TRY(phase_end(phases ? &phases->assign_ms : nullptr));
+    // stable: rows of equal (fit, half, centre) stay in ascending order
+    CB_TRY(rocprim::radix_sort_pairs(b_temp.p, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n_pairs, 0u,
+                                     b.key_bits, st));
+    hipLaunchKernelGGL(cb_bounds_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, keys_out, n_pairs,
+                       start, end);
+    CB_TRY(hipGetLastError());
+    hipLaunchKernelGGL(cb_accumulate_kernel, acc_grid, dim3(256), 0, st, src, L, fits, vals_out, start, end,
+                       b_part.as<float>());
+    CB_TRY(hipGetLastError());
+    CB_TRY(phase_end(phases ? &phases->accumulate_ms : nullptr));
+    hipLaunchKernelGGL(cb_update_kernel, dim3((unsigned)b.k_max, (unsigned)F), dim3(64), 0, st, b_part.as<float>(), start,
+                       end, L, fits, d_means, now);
+    CB_TRY(hipGetLastError());
+    CB_TRY(hipMemcpyAsync(host_flags.data(), flags, host_flags.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    CB_TRY(hipStreamSynchronize(st));
+    CB_TRY(phase_end(phases ? &phases->update_ms : nullptr));
+    for (int f = 0; f < F; f++) {
+      no_centre |= host_flags[(size_t)2 * F + f];
+      if (done[(size_t)f]) continue;
+      iters_out[f] = it + 1;  // the reference's iter_count: the iteration that changes nothing is counted
+      if (!host_flags[(size_t)((it + 1) & 1) * F + f]) {
+        done[(size_t)f] = 1;
+        n_done++;
+      }
+    }
+  }
+  *no_centre_out = no_centre;
+  sync_on_return.armed = false;
+  return hipStreamSynchronize(st);
+}
 }  // namespace
 
 hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan &plan, const float *d_eig,
@@ -288,61 +508,13 @@ hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan
   if (M < 1 || plan.sample < 1 || plan.n_pairs > 0x7fffffff) return hipErrorInvalidValue;
   if (plan.n_full ? (S > 0 && !plan.gather) : S < 1) return hipErrorInvalidValue;
   hipError_t e;
-#define CB_TRY(expr)                          \
-  do {                                        \
-    if ((e = (expr)) != hipSuccess) return e; \
-  } while (0)
-  // (freed on return, after the stream is synchronised)
-  struct Sync {
-    hipStream_t st;
-    bool armed;
-    ~Sync() {
-      if (armed) (void)hipStreamSynchronize(st);
-    }
-  };
-  vaqhost::DevBuf b_rows, b_gather, b_proj, b_full;
-  Sync sync_on_return{st, true};
+  CbPrepared src;
+  CbSync sync_on_return{st, true};
   if (phases) *phases = CodebookPhases{};
   auto t0 = std::chrono::steady_clock::now();
-
-  // rows x D of src as floats, projected where there is a rotation: in place when nothing is to be done, else in buf
-  auto projected = [&](RowsRef src, int64_t rows, vaqhost::DevBuf &buf, const float **out) -> hipError_t {
-    *out = static_cast<const float *>(src.p);
-    if (!d_eig && src.elem != 1) return hipSuccess;
-    hipError_t pe = buf.ensure((size_t)rows * D * sizeof(float));
-    if (pe != hipSuccess) return pe;
-    *out = buf.as<float>();
-    if (d_eig) return launch_project(src, rows, D, d_eig, buf.as<float>(), st, 0);  // unchecked, as VAQ::train projects
-    return launch_widen_rows_u8(static_cast<const uint8_t *>(src.p), rows * D, buf.as<float>(), st);
-  };
-
-  // ---- the full matrix, for the subspaces that do not sample: all n rows projected (or widened) once ----
-  const float *Pf = nullptr, *Ps = nullptr;
-  if (plan.n_full) CB_TRY(projected(d_X, n, b_full, &Pf));
-  // ---- the sample, for those that do: gathered once, every one of them works on a prefix of it ----
-  if (S > 0 && !plan.gather) {
-    CB_TRY(projected(d_X, S, b_proj, &Ps));  // (the caller's rows are the sample)
-  } else if (S > 0) {
-    const std::vector<int> rows = permutation_head(n, S);
-    CB_TRY(b_rows.ensure((size_t)S * sizeof(int)));
-    CB_TRY(b_gather.ensure((size_t)S * D * sizeof(float)));
-    CB_TRY(hipMemcpyAsync(b_rows.p, rows.data(), (size_t)S * sizeof(int), hipMemcpyHostToDevice, st));
-    const unsigned grid = (unsigned)((S * D + 255) / 256);
-    if (Pf || d_X.elem != 1)  // from the projected full matrix where there is one: a row's projection is its own
-      hipLaunchKernelGGL(cb_gather_kernel<float>, dim3(grid), dim3(256), 0, st,
-                         Pf ? Pf : static_cast<const float *>(d_X.p), D, b_rows.as<int>(), S, b_gather.as<float>());
-    else
-      hipLaunchKernelGGL(cb_gather_kernel<uint8_t>, dim3(grid), dim3(256), 0, st, static_cast<const uint8_t *>(d_X.p), D,
-                         b_rows.as<int>(), S, b_gather.as<float>());
-    CB_TRY(hipGetLastError());
-    CB_TRY(hipStreamSynchronize(st));  // (rows is the host's)
-    Ps = b_gather.as<float>();
-    if (!Pf && d_eig) CB_TRY(projected(RowsRef{b_gather.p, 4}, S, b_proj, &Ps));
-  }
-
-#undef CB_TRY
+  CB_TRY(cb_prepare(d_X, n, D, d_eig, plan.n_full > 0, S, plan.gather, src, st));
   sync_on_return.armed = false;  // (codebooks_lloyd synchronises before it returns, and the sources are freed behind it)
-  return codebooks_lloyd(Ps, Pf, D, L, plan, max_iter, d_means, iters_out, no_centre_out, phases, t0, st);
+  return codebooks_lloyd(src.sample, src.full, D, L, plan, max_iter, d_means, iters_out, no_centre_out, phases, t0, st);
 }
 
 // The fit from its two sources on: Ps the sample (plan.gathered x D, the subspaces with full == 0 read prefixes of
@@ -352,120 +524,146 @@ hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan
 hipError_t codebooks_lloyd(const float *Ps, const float *Pf, int D, int L, const cbfit::Plan &plan, int max_iter,
                            float *d_means, int *iters_out, int *no_centre_out, CodebookPhases *phases,
                            std::chrono::steady_clock::time_point began, hipStream_t st) {
-  const int M = (int)plan.sub.size();
-  if (M < 1 || plan.sample < 1 || plan.n_pairs > 0x7fffffff) return hipErrorInvalidValue;
-  const int n_pairs = (int)plan.n_pairs, n_runs = plan.n_runs;
-  hipError_t e;
-#define CB_TRY(expr)                          \
-  do {                                        \
-    if ((e = (expr)) != hipSuccess) return e; \
-  } while (0)
-  // (freed on return, after the stream is synchronised)
-  struct Sync {
-    hipStream_t st;
-    ~Sync() { (void)hipStreamSynchronize(st); }
-  };
-  vaqhost::DevBuf b_sub, b_seed, b_keys_in, b_keys_out, b_vals_in, b_vals_out, b_bounds, b_part, b_flags, b_temp;
-  Sync sync_on_return{st};
-  auto t0 = began;
+  if (plan.sub.empty() || plan.sample < 1) return hipErrorInvalidValue;
+  return cb_lloyd_batch(CbSources{{Ps, Pf, nullptr}}, L, cbfit::make_batch(plan, D, L), max_iter, d_means, iters_out,
+                        no_centre_out, phases, began, st);
+}
 
-  // ---- the batch's tables and the seeds ----
-  std::vector<int> seeds((size_t)plan.n_cent);
-  for (int s = 0; s < M; s++) {
-    const cbfit::Sub &sd = plan.sub[(size_t)s];
-    const std::vector<int> head = permutation_head(sd.rows, sd.k);
-    std::copy(head.begin(), head.end(), seeds.begin() + sd.cent_off);
+// ---- the hierarchical fit (DESIGN.md section 4f "Hierarchical"; fit_codebooks_hier_plan.h) ----
+// Stage 1: the flat subspaces and the 128-centre fits of the hierarchical ones in ONE run of the Lloyd phases.  Then the
+// membership of every row of R_s (nearest stage-1 centre by squaredNorm, no sqrt), a stable sort of the rows by
+// (subspace, group) and a gather into one compact [rows_s][L] matrix per subspace whose groups are contiguous and in
+// R_s order -- the stable order is what makes the stage-2 sums the reference's.  Stage 2: the K2-centre fits of ALL
+// groups of ALL hierarchical subspaces as one more run of the same phases over the compact matrices, the assign kernel
+// walking the plan's tile table.  d_means: plan.n_cent + 128 per hierarchical subspace centres (the stage-1 centres
+// behind the final ones).  On a refusal (*refusal, or *no_centre_out) the centres are not to be used.
+hipError_t codebooks_fit_hier(RowsRef d_X, int64_t n, int D, int L, const cbhier::Plan &plan, const float *d_eig,
+                              int max_iter, float *d_means, int *iters_out, int *no_centre_out, cbhier::Refusal *refusal,
+                              CodebookHierStats *stats, CodebookPhases *phases, hipStream_t st) {
+  const int M = (int)plan.flat.sub.size(), H = (int)plan.hsub.size();
+  if (M < 1 || H < 1 || plan.gathered < 1 || plan.n_pairs > 0x7fffffff) return hipErrorInvalidValue;
+  hipError_t e;
+  CbPrepared src;
+  vaqhost::DevBuf b_perm, b_resample, b_fit, b_keys_in, b_keys_out, b_vals_in, b_vals_out, b_bounds, b_flag, b_temp, b_compact;
+  CbSync sync_on_return{st, true};
+  *refusal = cbhier::Refusal{};
+  *no_centre_out = 0;
+  *stats = CodebookHierStats{};
+  CodebookPhases ph;
+  auto t0 = std::chrono::steady_clock::now();
+  const auto began = t0;
+
+  // ---- the sources: all rows for the flat subspaces that read them, and ONE head of randomPermutation(n) ----
+  CB_TRY(cb_prepare(d_X, n, D, d_eig, plan.n_full > 0, plan.gathered, true, src, st));
+  // stage 1 of a subspace with more than 65536 rows samples for itself: rows randomPermutation(rows_s)[0 .. 65536) of R_s
+  if (plan.resample_rows > 0) {
+    CB_TRY(b_resample.ensure((size_t)plan.resample_rows * L * sizeof(float)));
+    for (const cbhier::HSub &h : plan.hsub) {
+      if (!h.resampled) continue;
+      const std::vector<int> rows = permutation_head(h.rows, h.stage1_rows);
+      CB_TRY(b_perm.ensure(rows.size() * sizeof(int)));
+      CB_TRY(hipMemcpyAsync(b_perm.p, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(cb_slice_kernel, dim3((unsigned)(((int64_t)h.stage1_rows * L + 255) / 256)), dim3(256), 0, st,
+                         src.sample, D, h.s * L, b_perm.as<int>(), (int64_t)h.stage1_rows, L,
+                         b_resample.as<float>() + (size_t)h.resample_off * L);
+      CB_TRY(hipGetLastError());
+      CB_TRY(hipStreamSynchronize(st));  // (rows is the host's, b_perm is reused)
+    }
   }
-  CB_TRY(b_sub.ensure((size_t)M * sizeof(cbfit::Sub)));
-  CB_TRY(b_seed.ensure(seeds.size() * sizeof(int)));
+
+  // ---- stage 1 ----
+  std::vector<int> it1((size_t)M, 0);
+  CB_TRY(cb_lloyd_batch(CbSources{{src.sample, src.full, b_resample.as<float>()}}, L, plan.stage1, max_iter, d_means, it1.data(),
+                        no_centre_out, phases ? &ph : nullptr, began, st));
+  for (int s = 0; s < M; s++) iters_out[s] = it1[(size_t)s];
+  stats->stage1_ms = cb_ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  if (*no_centre_out) return hipSuccess;
+  std::vector<float> c1((size_t)H * cbhier::K1 * L);
+  CB_TRY(hipMemcpyAsync(c1.data(), d_means + (size_t)plan.n_cent * L, c1.size() * sizeof(float), hipMemcpyDeviceToHost, st));
+  CB_TRY(hipStreamSynchronize(st));
+  for (int h = 0; h < H; h++)
+    for (int g = 0; g < cbhier::K1; g++)
+      if (nan_rows(c1.data() + ((size_t)h * cbhier::K1 + g) * L, 1, L)) {
+        refusal->kind = cbhier::NAN_CENTRE;
+        refusal->s = plan.hsub[(size_t)h].s;
+        refusal->group = g;
+        return hipSuccess;
+      }
+
+  // ---- membership and regroup ----
+  const int n_pairs = (int)plan.n_pairs, n_groups = H * cbhier::K1;
+  CB_TRY(b_fit.ensure((size_t)H * sizeof(cbfit::Fit)));
   CB_TRY(b_keys_in.ensure((size_t)n_pairs * 4));
   CB_TRY(b_keys_out.ensure((size_t)n_pairs * 4));
   CB_TRY(b_vals_in.ensure((size_t)n_pairs * 4));
   CB_TRY(b_vals_out.ensure((size_t)n_pairs * 4));
-  CB_TRY(b_bounds.ensure((size_t)2 * n_runs * sizeof(int)));
-  CB_TRY(b_part.ensure((size_t)n_runs * L * sizeof(float)));
-  CB_TRY(b_flags.ensure((size_t)3 * M * sizeof(int)));
-  const cbfit::Sub *subs = b_sub.as<cbfit::Sub>();
+  CB_TRY(b_bounds.ensure((size_t)2 * n_groups * sizeof(int)));
+  CB_TRY(b_flag.ensure((size_t)H * sizeof(int)));
+  CB_TRY(b_compact.ensure((size_t)n_pairs * L * sizeof(float)));
   unsigned *keys_in = b_keys_in.as<unsigned>(), *keys_out = b_keys_out.as<unsigned>();
   unsigned *vals_in = b_vals_in.as<unsigned>(), *vals_out = b_vals_out.as<unsigned>();
-  int *start = b_bounds.as<int>(), *end = start + n_runs;
-  int *flags = b_flags.as<int>();  // changed[2][M] (this iteration's and the one before), then no_centre[M]
+  int *start = b_bounds.as<int>(), *end = start + n_groups;
   size_t temp_bytes = 0;
   CB_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n_pairs, 0u,
-                                   plan.key_bits, st));
+                                   plan.member.key_bits, st));
   CB_TRY(b_temp.ensure(temp_bytes ? temp_bytes : 16));
-  std::vector<int> host_flags((size_t)3 * M, 0);
-  for (int s = 0; s < M; s++) host_flags[(size_t)s] = 1;  // every subspace starts active
-  CB_TRY(hipMemcpyAsync(b_sub.p, plan.sub.data(), (size_t)M * sizeof(cbfit::Sub), hipMemcpyHostToDevice, st));
-  CB_TRY(hipMemcpyAsync(b_seed.p, seeds.data(), seeds.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  CB_TRY(hipMemcpyAsync(flags, host_flags.data(), host_flags.size() * sizeof(int), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(cb_seed_kernel, dim3((unsigned)((plan.k_max * L + 255) / 256), (unsigned)M), dim3(256), 0, st, Ps, Pf,
-                     D, L, subs, b_seed.as<int>(), d_means);
+  CB_TRY(hipMemcpyAsync(b_fit.p, plan.member.fit.data(), (size_t)H * sizeof(cbfit::Fit), hipMemcpyHostToDevice, st));
+  CB_TRY(hipMemsetAsync(b_flag.p, 0, (size_t)H * sizeof(int), st));
+  CB_TRY(hipMemsetAsync(start, 0, (size_t)2 * n_groups * sizeof(int), st));
+  const CbSources member_src{{src.sample, nullptr, nullptr}};
+  CB_TRY(cb_launch_assign<true>(member_src, L, plan.member, b_fit.as<cbfit::Fit>(), nullptr, d_means, nullptr, keys_in, vals_in,
+                                b_flag.as<int>(), st));
+  // stable: the rows of a group stay in ascending position within R_s
+  CB_TRY(rocprim::radix_sort_pairs(b_temp.p, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n_pairs, 0u,
+                                   plan.member.key_bits, st));
+  hipLaunchKernelGGL(cb_bounds_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, keys_out, n_pairs, start, end);
   CB_TRY(hipGetLastError());
-  CB_TRY(hipStreamSynchronize(st));  // (the tables are the host's)
-  if (phases) phases->gather_ms = cb_ms_since(t0);
-
-  // launch shape of the assign kernel: the widest workgroup whose tile of slices fits
-  int R = 256;
-  while (R > 64 && (size_t)R * L * sizeof(float) > CB_TILE_BYTES) R >>= 1;
-  const bool x_lds = (size_t)R * L * sizeof(float) <= CB_TILE_BYTES;
-  const int stage = std::max(1, std::min(plan.k_max, CB_STAGE_FLOATS / L));
-  const size_t lds = ((size_t)stage * L + (x_lds ? (size_t)R * L : 0)) * sizeof(float);
-  const dim3 assign_grid((unsigned)((plan.sample + R - 1) / R), (unsigned)M);
-  const dim3 acc_grid((unsigned)((2 * (int64_t)plan.k_max * L + 255) / 256), (unsigned)M);
-
-  auto phase_end = [&](double *acc) -> hipError_t {
-    if (!phases) return hipSuccess;
-    const hipError_t pe = hipStreamSynchronize(st);
-    *acc += cb_ms_since(t0);
-    t0 = std::chrono::steady_clock::now();
-    return pe;
-  };
-  std::vector<char> done((size_t)M, 0);
-  for (int s = 0; s < M; s++) iters_out[s] = 0;
-  int no_centre = 0, n_done = 0;
-  t0 = std::chrono::steady_clock::now();
-  for (int it = 0; it < max_iter && n_done < M && !no_centre; it++) {
-    int *prev = flags + (size_t)(it & 1) * M, *now = flags + (size_t)((it + 1) & 1) * M;
-    CB_TRY(hipMemsetAsync(now, 0, (size_t)M * sizeof(int), st));
-    CB_TRY(hipMemsetAsync(start, 0, (size_t)2 * n_runs * sizeof(int), st));
-    if (x_lds)
-      hipLaunchKernelGGL(cb_assign_kernel<true>, assign_grid, dim3(R), lds, st, Ps, Pf, D, L, subs, d_means, stage, prev,
-                         keys_in, vals_in, flags + 2 * M);
-    else
-      hipLaunchKernelGGL(cb_assign_kernel<false>, assign_grid, dim3(R), lds, st, Ps, Pf, D, L, subs, d_means, stage, prev,
-                         keys_in, vals_in, flags + 2 * M);
+  for (const cbhier::HSub &h : plan.hsub) {  // the sorted rows of subspace h are pairs [pair_off, pair_off + rows)
+    hipLaunchKernelGGL(cb_slice_kernel, dim3((unsigned)(((int64_t)h.rows * L + 255) / 256)), dim3(256), 0, st, src.sample, D,
+                       h.s * L, reinterpret_cast<const int *>(vals_out) + h.pair_off, (int64_t)h.rows, L,
+                       b_compact.as<float>() + (size_t)h.pair_off * L);
     CB_TRY(hipGetLastError());
-    CB_TRY(phase_end(phases ? &phases->assign_ms : nullptr));
-    // stable: rows of equal (subspace, half, centre) stay in ascending order
-    CB_TRY(rocprim::radix_sort_pairs(b_temp.p, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n_pairs, 0u,
-                                     plan.key_bits, st));
-    hipLaunchKernelGGL(cb_bounds_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, keys_out, n_pairs,
-                       start, end);
-    CB_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cb_accumulate_kernel, acc_grid, dim3(256), 0, st, Ps, Pf, D, L, subs, vals_out, start, end,
-                       b_part.as<float>());
-    CB_TRY(hipGetLastError());
-    CB_TRY(phase_end(phases ? &phases->accumulate_ms : nullptr));
-    hipLaunchKernelGGL(cb_update_kernel, dim3((unsigned)plan.k_max, (unsigned)M), dim3(64), 0, st, b_part.as<float>(),
-                       start, end, L, subs, d_means, now);
-    CB_TRY(hipGetLastError());
-    CB_TRY(hipMemcpyAsync(host_flags.data(), flags, host_flags.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-    CB_TRY(hipStreamSynchronize(st));
-    CB_TRY(phase_end(phases ? &phases->update_ms : nullptr));
-    for (int s = 0; s < M; s++) {
-      no_centre |= host_flags[(size_t)2 * M + s];
-      if (done[(size_t)s]) continue;
-      iters_out[s] = it + 1;  // the reference's iter_count: the iteration that changes nothing is counted
-      if (!host_flags[(size_t)((it + 1) & 1) * M + s]) {
-        done[(size_t)s] = 1;
-        n_done++;
-      }
-    }
   }
-#undef CB_TRY
-  *no_centre_out = no_centre;
+  std::vector<int> bounds((size_t)2 * n_groups), counts((size_t)n_groups), unreached((size_t)H);
+  CB_TRY(hipMemcpyAsync(bounds.data(), start, bounds.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  CB_TRY(hipMemcpyAsync(unreached.data(), b_flag.p, (size_t)H * sizeof(int), hipMemcpyDeviceToHost, st));
+  CB_TRY(hipStreamSynchronize(st));
+  stats->groups = n_groups;
+  stats->min_group = 0x7fffffff;
+  for (int g = 0; g < n_groups; g++) {
+    counts[(size_t)g] = bounds[(size_t)n_groups + g] - bounds[(size_t)g];
+    stats->min_group = std::min(stats->min_group, counts[(size_t)g]);
+    stats->max_group = std::max(stats->max_group, counts[(size_t)g]);
+  }
+  stats->regroup_ms = cb_ms_since(t0);
+  t0 = std::chrono::steady_clock::now();
+  for (int h = 0; h < H; h++)
+    if (unreached[(size_t)h]) {
+      refusal->kind = cbhier::NO_CENTRE;
+      refusal->s = plan.hsub[(size_t)h].s;
+      return hipSuccess;
+    }
+  *refusal = cbhier::check_groups(plan, counts.data());
+  if (refusal->kind != cbhier::OK) return hipSuccess;
+
+  // ---- stage 2: every group of every hierarchical subspace, one batch ----
+  const cbfit::Batch stage2 = cbhier::make_stage2(plan, counts.data(), L, cbfit::assign_tile_rows(L));
+  std::vector<int> it2(stage2.fit.size(), 0);
+  CB_TRY(cb_lloyd_batch(CbSources{{b_compact.as<float>(), nullptr, nullptr}}, L, stage2, max_iter, d_means, it2.data(),
+                        no_centre_out, phases ? &ph : nullptr, t0, st));
+  for (int h = 0; h < H; h++)
+    for (int g = 0; g < cbhier::K1; g++) {
+      int &out = iters_out[plan.hsub[(size_t)h].s];
+      out = std::max(out, it2[(size_t)h * cbhier::K1 + g]);
+      stats->stage2_iters = std::max(stats->stage2_iters, it2[(size_t)h * cbhier::K1 + g]);
+    }
+  for (int s = 0; s < M; s++) stats->stage1_iters = std::max(stats->stage1_iters, it1[(size_t)s]);
+  stats->stage2_ms = cb_ms_since(t0);
+  if (phases) *phases = ph;
+  sync_on_return.armed = false;
   return hipStreamSynchronize(st);
 }
+#undef CB_TRY
 
 }  // namespace vaq

@@ -542,6 +542,25 @@ hipError_t codebooks_fit(RowsRef d_X, int64_t n, int D, int L, const cbfit::Plan
 hipError_t codebooks_lloyd(const float *Ps, const float *Pf, int D, int L, const cbfit::Plan &plan, int max_iter,
                            float *d_means, int *iters_out, int *no_centre_out, CodebookPhases *phases,
                            std::chrono::steady_clock::time_point began, hipStream_t st);
+// ---- the hierarchical form (fit_codebooks_hier_plan.h): subspaces above 8 bits in two stages ----
+namespace cbhier {
+struct Plan;
+struct Refusal;
+}
+struct CodebookHierStats {
+  double stage1_ms = 0, regroup_ms = 0, stage2_ms = 0;  // host time, each ended by a stream synchronisation
+  int groups = 0, min_group = 0, max_group = 0;          // 128 per hierarchical subspace; rows of the smallest and largest
+  int stage1_iters = 0, stage2_iters = 0;                // the largest iteration count of a fit of the stage
+};
+// d_X, d_eig, max_iter, iters_out[M], phases, st: as codebooks_fit.  The flat subspaces and the 128-centre fits of the
+// hierarchical ones run as one batch; then the membership of all rows of R_s by squaredNorm (no sqrt), the stable
+// regroup, and the K2-centre fits of all groups as one batch.  d_means: plan.n_cent final centres followed by 128
+// stage-1 centres per hierarchical subspace (device).  A refusal known only on the device is reported in *refusal
+// (kind != OK) or *no_centre_out, with hipSuccess: the centres are then not to be used.  The plan must hold a
+// hierarchical subspace.  Synchronises the stream.
+hipError_t codebooks_fit_hier(RowsRef d_X, int64_t n, int D, int L, const cbhier::Plan &plan, const float *d_eig,
+                              int max_iter, float *d_means, int *iters_out, int *no_centre_out, cbhier::Refusal *refusal,
+                              CodebookHierStats *stats, CodebookPhases *phases, hipStream_t st);
 // The sharded fit's shard step: out [cnt][D_w] = the compact columns of one owner (d_subs: its subspaces, D_w / L of
 // them, device) for the rows a shard contributes -- X's local rows d_rows[0 .. cnt) (device), or first + i where
 // d_rows is null.  X: the shard's rows, float or byte, D wide; d_eig null: the rows' own values, else

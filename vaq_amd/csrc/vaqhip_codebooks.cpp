@@ -7,15 +7,17 @@
 #include <cstring>
 #include <vector>
 
-#include "fit_codebooks_plan.h"
+#include "fit_codebooks_hier_plan.h"
 #include "kmeans_sample.h"
 
 using namespace vaqhost;
 namespace cb = vaq::cbfit;
+namespace ch = vaq::cbhier;
 
 namespace {
 thread_local int g_cb_timing = 0;
 thread_local vaqhip_fit_codebooks_timing g_cb_last = {};
+thread_local vaqhip_fit_codebooks_hier_timing g_cbh_last = {};
 
 // every refusal that needs no device, in the order the header lists them; fills the plan when there is none
 int check_args(const void *X, int64_t n, int D, int M, const int *bits, int max_iter, const void *cent, cb::Plan *plan) {
@@ -79,18 +81,134 @@ int fit_core(vaq::RowsRef d_X, int64_t n, int D, const cb::Plan &plan, const flo
   return VAQHIP_OK;
 }
 
+// ---- the hierarchical form: subspaces above 8 bits in two stages (fit_codebooks_hier_plan.h) ----
+// what the hierarchical form refuses beyond check_args, and its plan; hp->hsub stays empty when no subspace is above
+// 8 bits: the call is then the flat fit, bit for bit
+int plan_hier(int64_t n, int D, int M, const int *bits, ch::Plan *hp) {
+  const int s = ch::first_short_subspace(n, M, bits);
+  if (s >= 0)
+    return fail(VAQHIP_EINVAL, "bits[%d]=%d: %d centres from %lld rows (the reference seeds from rows out of bounds)", s,
+                bits[s], 1 << bits[s], (long long)n);
+  bool any = false;
+  for (int i = 0; i < M; i++) any |= ch::hierarchical(bits[i]);
+  if (any) *hp = ch::make_plan(n, D, M, bits);
+  return VAQHIP_OK;
+}
+
+// the last hierarchical call's figures when it was the flat fit (no subspace above 8 bits)
+void note_flat_as_hier() {
+  g_cbh_last = vaqhip_fit_codebooks_hier_timing{};
+  g_cbh_last.total_ms = g_cbh_last.stage1_ms = g_cb_last.total_ms;
+  g_cbh_last.stage1_iterations = g_cb_last.iterations;
+  g_cbh_last.subspaces = g_cb_last.subspaces;
+  g_cbh_last.dims = g_cb_last.dims;
+  g_cbh_last.rows = g_cb_last.rows;
+}
+
+int refuse_hier(const ch::Refusal &r) {
+  switch (r.kind) {
+  case ch::NAN_CENTRE:
+    return fail(VAQHIP_EINVAL, "subspace %d, group %d: the stage-1 centre is NaN (the reference asserts \"hierarchical kmeans failed\")",
+                r.s, r.group);
+  case ch::EMPTY_GROUP:
+    return fail(VAQHIP_EINVAL, "subspace %d, group %d: no row is nearest to this stage-1 centre (the reference asserts "
+                               "\"hierarchical kmeans failed\")", r.s, r.group);
+  case ch::SHORT_GROUP:
+    return fail(VAQHIP_EINVAL, "subspace %d, group %d: %d centres from %lld rows (the reference seeds from rows out of bounds)",
+                r.s, r.group, r.K2, (long long)r.rows);
+  case ch::NO_CENTRE:
+    return fail(VAQHIP_EINVAL, "subspace %d: a row is at a squared distance >= FLT_MAX (or NaN) from all 128 stage-1 centres", r.s);
+  case ch::SAMPLED_GROUP:
+    return fail(VAQHIP_EUNSUPPORTED, "subspace %d, group %d: %lld rows > %lld: the reference's stage 2 would sample the group "
+                                     "(not built)", r.s, r.group, (long long)r.rows, (long long)ch::group_limit(r.K2));
+  default:
+    return VAQHIP_OK;
+  }
+}
+
+// fit_core's twin over a plan with a hierarchical subspace
+int fit_core_hier(vaq::RowsRef d_X, int64_t n, int D, const ch::Plan &hp, const float *d_eig, int max_iter, float *d_cent_out,
+                  int *iters_out, int *nan_rows_out, hipStream_t st) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const int M = (int)hp.flat.sub.size(), L = D / M, H = (int)hp.hsub.size();
+  const size_t cent_floats = (size_t)hp.n_cent * L;
+  DevBuf b_means;  // the final centres, the stage-1 centres behind them
+  HIP_TRY(b_means.ensure((cent_floats + (size_t)H * ch::K1 * L) * sizeof(float)));
+  std::vector<int> iters((size_t)M, 0);
+  int no_centre = 0;
+  ch::Refusal refusal;
+  vaq::CodebookHierStats hs;
+  vaq::CodebookPhases ph;
+  HIP_TRY(vaq::codebooks_fit_hier(d_X, n, D, L, hp, d_eig, max_iter, b_means.as<float>(), iters.data(), &no_centre, &refusal,
+                                  &hs, g_cb_timing ? &ph : nullptr, st));  // synchronises
+  if (refusal.kind != ch::OK) return refuse_hier(refusal);
+  if (no_centre)
+    return fail(VAQHIP_EINVAL, "a row is at a distance >= FLT_MAX (or NaN) from every centre: the reference indexes row -1");
+  std::vector<float> means(cent_floats);
+  HIP_TRY(hipMemcpyAsync(means.data(), b_means.p, cent_floats * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(d_cent_out, b_means.p, cent_floats * sizeof(float), hipMemcpyDeviceToDevice, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  int max_iters = 0;
+  for (int s = 0; s < M; s++) {
+    const cb::Sub &sd = hp.flat.sub[(size_t)s];
+    if (iters_out) iters_out[s] = iters[(size_t)s];
+    if (nan_rows_out) nan_rows_out[s] = vaq::nan_rows(means.data() + (size_t)sd.cent_off * L, sd.k, L);
+    max_iters = std::max(max_iters, iters[(size_t)s]);
+  }
+  const float total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  g_cb_last = vaqhip_fit_codebooks_timing{};
+  g_cb_last.total_ms = total;
+  g_cb_last.gather_ms = (float)ph.gather_ms;
+  g_cb_last.assign_ms = (float)ph.assign_ms;
+  g_cb_last.accumulate_ms = (float)ph.accumulate_ms;
+  g_cb_last.update_ms = (float)ph.update_ms;
+  g_cb_last.iterations = max_iters;
+  g_cb_last.sample_rows = std::max(hp.gathered, hp.n_full ? n : (int64_t)0);
+  g_cb_last.rows = n;
+  g_cb_last.dims = D;
+  g_cb_last.subspaces = M;
+  g_cbh_last = vaqhip_fit_codebooks_hier_timing{};
+  g_cbh_last.total_ms = total;
+  g_cbh_last.stage1_ms = (float)hs.stage1_ms;
+  g_cbh_last.regroup_ms = (float)hs.regroup_ms;
+  g_cbh_last.stage2_ms = (float)hs.stage2_ms;
+  g_cbh_last.groups = hs.groups;
+  g_cbh_last.min_group_rows = hs.min_group;
+  g_cbh_last.max_group_rows = hs.max_group;
+  g_cbh_last.stage1_iterations = hs.stage1_iters;
+  g_cbh_last.stage2_iterations = hs.stage2_iters;
+  g_cbh_last.hier_subspaces = H;
+  g_cbh_last.subspaces = M;
+  g_cbh_last.dims = D;
+  g_cbh_last.rows = n;
+  return VAQHIP_OK;
+}
+
+// hp with a hierarchical subspace: the two-stage fit; else the flat one over `plan`
+int fit_either(vaq::RowsRef d_X, int64_t n, int D, const cb::Plan &plan, const ch::Plan *hp, const float *d_eig, int max_iter,
+               float *d_cent_out, int *iters_out, int *nan_rows_out, hipStream_t st) {
+  if (hp && !hp->hsub.empty()) return fit_core_hier(d_X, n, D, *hp, d_eig, max_iter, d_cent_out, iters_out, nan_rows_out, st);
+  const int rc = fit_core(d_X, n, D, plan, d_eig, max_iter, d_cent_out, iters_out, nan_rows_out, st);
+  if (hp && rc == VAQHIP_OK) note_flat_as_hier();
+  return rc;
+}
+
+// hier: the hierarchical form's refusals and plan on top (vaqhip_fit_codebooks_hier*)
 int fit_device_entry(int device_id, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits, const float *d_eigvec,
-                     int max_iter, float *d_centroids_out, int *iters_out, int *nan_rows_out, void *stream) {
+                     int max_iter, float *d_centroids_out, int *iters_out, int *nan_rows_out, void *stream, bool hier = false) {
   cb::Plan plan;
+  ch::Plan hp;
   if (int rc = check_args(d_X.p, n, D, M, bits, max_iter, d_centroids_out, &plan)) return rc;
+  if (hier)
+    if (int rc = plan_hier(n, D, M, bits, &hp)) return rc;
   DeviceGuard g(device_id);
   if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed (no CPU path)", device_id);
-  return fit_core(d_X, n, D, plan, d_eigvec, max_iter, d_centroids_out, iters_out, nan_rows_out,
-                  static_cast<hipStream_t>(stream));
+  return fit_either(d_X, n, D, plan, hier ? &hp : nullptr, d_eigvec, max_iter, d_centroids_out, iters_out, nan_rows_out,
+                    static_cast<hipStream_t>(stream));
 }
 
 // the rest of a host-output call once the rows are on the device (current): eigvec up, fit, centres down
-int fit_to_host(vaq::RowsRef d_X, int64_t n, int D, const cb::Plan &plan, const float *eigvec, int max_iter,
+int fit_to_host(vaq::RowsRef d_X, int64_t n, int D, const cb::Plan &plan, const ch::Plan *hp, const float *eigvec, int max_iter,
                 float *centroids_out, int *iters_out, int *nan_rows_out) {
   DevBuf d_eig, d_cent;
   const size_t cent_bytes = (size_t)plan.n_cent * (D / (int)plan.sub.size()) * sizeof(float);
@@ -101,8 +219,8 @@ int fit_to_host(vaq::RowsRef d_X, int64_t n, int D, const cb::Plan &plan, const 
   }
   CallStream st;
   HIP_TRY(st.open());
-  if (int rc = fit_core(d_X, n, D, plan, eigvec ? d_eig.as<float>() : nullptr, max_iter, d_cent.as<float>(), iters_out,
-                        nan_rows_out, st.s))
+  if (int rc = fit_either(d_X, n, D, plan, hp, eigvec ? d_eig.as<float>() : nullptr, max_iter, d_cent.as<float>(), iters_out,
+                          nan_rows_out, st.s))
     return rc;
   HIP_TRY(hipMemcpy(centroids_out, d_cent.p, cent_bytes, hipMemcpyDeviceToHost));
   return VAQHIP_OK;
@@ -111,16 +229,21 @@ int fit_to_host(vaq::RowsRef d_X, int64_t n, int D, const cb::Plan &plan, const 
 // X: host rows of X.elem bytes per element, uploaded as they are.  Where every subspace samples, only the sample goes
 // up: its rows are copied out in the sample's order here, and the device is handed the sample itself.  Where one
 // subspace reads all rows, all rows go up, and the device gathers the sample of the others.
+// The hierarchical form with a hierarchical subspace uploads all rows: its one gather serves both kinds of subspace.
 int fit_host_entry(int device_id, vaq::RowsRef X, int64_t n, int D, int M, const int *bits, const float *eigvec,
-                   int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out) {
+                   int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out, bool hier = false) {
   cb::Plan plan;
+  ch::Plan hp;
   if (int rc = check_args(X.p, n, D, M, bits, max_iter, centroids_out, &plan)) return rc;
+  if (hier)
+    if (int rc = plan_hier(n, D, M, bits, &hp)) return rc;
   DeviceGuard g(device_id);
   if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed (no CPU path)", device_id);
   DevBuf d_x;
-  const size_t row_bytes = (size_t)D * (size_t)X.elem, x_bytes = (size_t)(plan.sampled ? plan.sample : n) * row_bytes;
+  const bool sample_only = plan.sampled && hp.hsub.empty();
+  const size_t row_bytes = (size_t)D * (size_t)X.elem, x_bytes = (size_t)(sample_only ? plan.sample : n) * row_bytes;
   HIP_TRY(d_x.ensure(x_bytes));
-  if (plan.sampled) {
+  if (sample_only) {
     const std::vector<int> rows = vaq::permutation_head(n, plan.sample);
     std::vector<char> picked(x_bytes);
     for (int64_t i = 0; i < plan.sample; i++)
@@ -130,7 +253,8 @@ int fit_host_entry(int device_id, vaq::RowsRef X, int64_t n, int D, int M, const
   } else {
     HIP_TRY(hipMemcpy(d_x.p, X.p, x_bytes, hipMemcpyHostToDevice));
   }
-  return fit_to_host(vaq::RowsRef{d_x.p, X.elem}, n, D, plan, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
+  return fit_to_host(vaq::RowsRef{d_x.p, X.elem}, n, D, plan, hier ? &hp : nullptr, eigvec, max_iter, centroids_out, iters_out,
+                     nan_rows_out);
 }
 }  // namespace
 
@@ -142,10 +266,49 @@ int vaqhost::fit_codebooks_rows_device(int device, vaq::RowsRef d_X, int64_t n, 
   if (int rc = check_args(d_X.p, n, D, M, bits, max_iter, centroids_out, &plan)) return rc;
   DeviceGuard g(device);
   if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed (no CPU path)", device);
-  return fit_to_host(d_X, n, D, plan, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
+  return fit_to_host(d_X, n, D, plan, nullptr, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
+}
+
+// the hierarchical twin (vaqhip_refiner_fit_codebooks_hier)
+int vaqhost::fit_codebooks_hier_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits,
+                                            const float *eigvec, int max_iter, float *centroids_out, int *iters_out,
+                                            int *nan_rows_out) {
+  cb::Plan plan;
+  ch::Plan hp;
+  if (int rc = check_args(d_X.p, n, D, M, bits, max_iter, centroids_out, &plan)) return rc;
+  if (int rc = plan_hier(n, D, M, bits, &hp)) return rc;
+  DeviceGuard g(device);
+  if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed (no CPU path)", device);
+  return fit_to_host(d_X, n, D, plan, &hp, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
 }
 
 extern "C" {
+
+int vaqhip_fit_codebooks_hier(int device_id, const float *X, int64_t n, int D, int M, const int *bits, const float *eigvec,
+                              int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out) {
+  return fit_host_entry(device_id, vaq::RowsRef{X, 4}, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out, true);
+}
+int vaqhip_fit_codebooks_hier_u8(int device_id, const uint8_t *X, int64_t n, int D, int M, const int *bits, const float *eigvec,
+                                 int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out) {
+  return fit_host_entry(device_id, vaq::RowsRef{X, 1}, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out, true);
+}
+int vaqhip_fit_codebooks_hier_device(int device_id, const float *d_X, int64_t n, int D, int M, const int *bits,
+                                     const float *d_eigvec, int max_iter, float *d_centroids_out, int *iters_out,
+                                     int *nan_rows_out, void *stream) {
+  return fit_device_entry(device_id, vaq::RowsRef{d_X, 4}, n, D, M, bits, d_eigvec, max_iter, d_centroids_out, iters_out,
+                          nan_rows_out, stream, true);
+}
+int vaqhip_fit_codebooks_hier_u8_device(int device_id, const uint8_t *d_X, int64_t n, int D, int M, const int *bits,
+                                        const float *d_eigvec, int max_iter, float *d_centroids_out, int *iters_out,
+                                        int *nan_rows_out, void *stream) {
+  return fit_device_entry(device_id, vaq::RowsRef{d_X, 1}, n, D, M, bits, d_eigvec, max_iter, d_centroids_out, iters_out,
+                          nan_rows_out, stream, true);
+}
+int vaqhip_last_fit_codebooks_hier_timing(vaqhip_fit_codebooks_hier_timing *out) {
+  if (!out) return fail(VAQHIP_EINVAL, "null pointer");
+  *out = g_cbh_last;
+  return VAQHIP_OK;
+}
 
 int vaqhip_fit_codebooks(int device_id, const float *X, int64_t n, int D, int M, const int *bits, const float *eigvec,
                          int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out) {

@@ -77,6 +77,37 @@ def fit_codebooks_u8(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray
     return _fit_codebooks(X, M, bits, eigvec, max_iter, device, devices, True)
 
 
+def _fit_codebooks_hier(X, M, bits, eigvec, max_iter, device, u8: bool):
+    X = _fit_rows(X, u8)
+    fn = "vaqhip_fit_codebooks_hier" + ("_u8" if u8 else "")
+    return _fit_codebooks_call(X.shape[1], M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn: getattr(L, fn)(
+        int(device), _ptr(X), X.shape[0], X.shape[1], int(M), b, e, it, c, i, nn))
+
+
+def fit_codebooks_hier(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25,
+                       device: int = 0):
+    """vaqhip_fit_codebooks_hier: fit_codebooks with every subspace above 8 bits fitted in two stages, as VAQ::train
+    does under mHierarchicalKmeans (demo_vaq --kmeans-ver 1): 128 centres over the head of randomPermutation(n), the
+    rows split by nearest centre (squaredNorm, no sqrt), then 1 << (bits - 7) centres inside each group.  Subspaces of
+    at most 8 bits, and a call without any wider one, are fit_codebooks's bit for bit.  Returns what fit_codebooks
+    returns; iterations[s] is the largest count among a hierarchical subspace's 129 fits.  Single device only."""
+    return _fit_codebooks_hier(X, M, bits, eigvec, max_iter, device, False)
+
+
+def fit_codebooks_hier_u8(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25,
+                          device: int = 0):
+    """fit_codebooks_hier from byte rows (vaqhip_fit_codebooks_hier_u8): its result on X.astype(float32), bit for bit."""
+    return _fit_codebooks_hier(X, M, bits, eigvec, max_iter, device, True)
+
+
+def last_fit_codebooks_hier_timing() -> dict:
+    """Figures of the calling thread's last hierarchical fit (vaqhip_last_fit_codebooks_hier_timing): stage1_ms,
+    regroup_ms, stage2_ms, the groups and the smallest and largest of them, the iterations per stage."""
+    t = _lib.FitCodebooksHierTiming()
+    _lib.check(_lib.load().vaqhip_last_fit_codebooks_hier_timing(C.byref(t)))
+    return _struct_dict(t)
+
+
 def fit_codebooks_timing(on: bool) -> None:
     """Phase times for the calling thread's fits (vaqhip_fit_codebooks_set_timing): one synchronisation per phase."""
     _lib.check(_lib.load().vaqhip_fit_codebooks_set_timing(1 if on else 0))
