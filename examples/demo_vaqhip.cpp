@@ -41,6 +41,9 @@
 //               [--fit-codebooks --bits 8,8,... --dataset base.fvecs [--save c.bin] [--max-iter 25]]
 //               [--kmeans-ver 1]                 with --fit-codebooks or --train: subspaces above 8 bits are fitted
 //                                           hierarchically, 128 x 2^(bits-7) centres (demo_vaq's switch; 2 is refused)
+//               [--kmeans-binary]                with --fit-codebooks or --train: the way to the binary fit -- subspaces
+//                                           above 8 bits as a tree of 2-centre fits (the rule of demo_vaq's --kmeans-ver 2);
+//                                           not together with --kmeans-ver 1
 //                                          (instead of --centroids: the subspace codebooks are fitted on the GPU from
 //                                           the raw vectors by KMeans::staticFitSampling, the call of VAQ.cpp:644-649 --
 //                                           not the arma::kmeans call VAQ::train runs today; --eigen is applied first,
@@ -158,7 +161,7 @@ int main(int argc, char **argv) {
   for (int i = 1; i < argc; i += 2) {
     if (std::strcmp(argv[i], "--refine-resident") == 0 || std::strcmp(argv[i], "--exact-groundtruth") == 0 ||
         std::strcmp(argv[i], "--encode") == 0 || std::strcmp(argv[i], "--fit-codebooks") == 0 ||
-        std::strcmp(argv[i], "--train") == 0) {
+        std::strcmp(argv[i], "--train") == 0 || std::strcmp(argv[i], "--kmeans-binary") == 0) {
       a[argv[i] + 2] = "1";  // the switches without a value
       i--;
       continue;
@@ -199,6 +202,10 @@ int main(int argc, char **argv) {
       if (ver == 2) throw Error(VAQHIP_EUNSUPPORTED, "--kmeans-ver 2: binary k-means is not built");
       if (ver != 0 && ver != 1) throw Error(VAQHIP_EINVAL, "--kmeans-ver takes 0 or 1");
       vaq.mHierarchicalKmeans = ver == 1;
+    }
+    if (a.count("kmeans-binary")) {  // the binary-tree fit (the rule of demo_vaq's --kmeans-ver 2)
+      if (vaq.mHierarchicalKmeans) throw Error(VAQHIP_EINVAL, "--kmeans-binary and --kmeans-ver 1 name two different fits");
+      vaq.mBinaryKmeans = true;
     }
     if (!encode && !fit_only) vaq.mCodebook = loadCodebook(a["codebook"]);
     if (train) {  // the method string's min / max / var hold unless the flags name others

@@ -496,7 +496,8 @@ int vaqhip_last_fit_codebooks_timing(vaqhip_fit_codebooks_timing *out);  /* the 
  * when m_i < K2 (the reference seeds from rows out of bounds), when a row has no centre (squared distance NaN or
  * >= FLT_MAX from all 128); VAQHIP_EUNSUPPORTED when m_i > max(256 * K2, 65536): there the reference's stage 2 would
  * sample the group.  That happens under extreme skew, and regularly at 15 bits, where the average group already holds
- * 256 * K2 = 65536 rows; it is left out on purpose.  Not built either: a multi-device form, mBinaryKmeans.
+ * 256 * K2 = 65536 rows; it is left out on purpose (vaqhip_fit_codebooks_bin below never refuses on group sizes).
+ * Not built either: a multi-device form.
  * The host forms upload all rows when a subspace is hierarchical.  _device and _u8 forms: as vaqhip_fit_codebooks's. */
 int vaqhip_fit_codebooks_hier(int device_id, const float *X_rowmajor, int64_t n, int D, int M, const int *bits,
                               const float *eigvec_real_rowmajor, int max_iter, float *centroids_out, int *iters_out,
@@ -523,6 +524,77 @@ typedef struct {
   int64_t rows;
 } vaqhip_fit_codebooks_hier_timing;
 int vaqhip_last_fit_codebooks_hier_timing(vaqhip_fit_codebooks_hier_timing *out);  /* the calling thread's last one */
+
+/* ---------------------------------------------------------------------------
+ * The binary-tree form of the fit: VAQ::train with mBinaryKmeans (hierarchicalBinKmeans, VAQ.cpp:1293-1371; demo_vaq
+ * --kmeans-ver 2).  Inputs and outputs are vaqhip_fit_codebooks's.  B = sum(bits), L = D / M, k_s = 1 << bits[s].
+ *   flat subspaces   bits[s] <= 8: the flat fit's, exactly, as in the hierarchical form.  A call in which no subspace
+ *                    exceeds 8 bits IS vaqhip_fit_codebooks, bit for bit.
+ *   rows R_s         of a subspace with bits[s] > 8: exactly the hierarchical form's -- rows_s = min(n, max(256 * k_s,
+ *                    256 << (B / M))), row i = row randomPermutation(n)[i] of the projected matrix, always filled; one
+ *                    gathered head serves every reader.
+ *   node (d, j)      depth d = 1 .. maxdepth = bits[s], tempK = 1 << (maxdepth - d + 1).  The root (1, 0) holds R_s.
+ *                    Node (d, j) owns rows [j * tempK, (j + 1) * tempK) of the subspace's block of centroids_out
+ *                    (VAQ.cpp:1361-1367: the left block first).
+ *   2-centre fit     C = KMeans::staticFitSampling(node rows, 2, max_iter) as that function behaves on those rows: above
+ *                    65536 rows it works on rows randomPermutation(m)[0 .. 65536) of the node; its seeds are the head of
+ *                    randomPermutation(rows it works on); its halves [0, ceil(m / 2)) and the rest; its NaN centres and
+ *                    its stopping are its own.  It stands for the reference's arma::kmeans, as everywhere in this library.
+ *   leaf             d == maxdepth: the two centres are the node's output.
+ *   split            getBelongsToBinaryCluster (VAQ.cpp:1293-1310) over ALL m rows of the node: left = (x - C0)
+ *                    .squaredNorm(), right = (x - C1).squaredNorm(), each in Eigen's summation order (sequential for
+ *                    L < 8), NO sqrt; the row goes left iff left < right (strict).  A tie and a NaN on either side go
+ *                    right; there is no "row without a centre": a NaN centre 0 sends every row right.
+ *   cut              sizeleft < tempK / 2 or sizeright < tempK / 2: the node's output is staticFitSampling(node rows,
+ *                    tempK, max_iter) -- sampling for itself above max(256 * tempK, 65536) rows, with its own seeds --
+ *                    and the recursion stops there.  Every node holds at least tempK rows once rows_s >= k_s.
+ *   children         else (d + 1, 2j) takes the left rows and (d + 1, 2j + 1) the right ones, each in ascending
+ *                    position within the node (VAQ.cpp:1345-1351): that order makes the children's sums the reference's.
+ *   iters_out[s]     the largest iteration count among the subspace's fits; nan_rows_out[s] the NaN centres among its
+ *                    final k_s.
+ * The tree is walked level by level: the 2-centre fits of all live nodes of all binary subspaces are ONE batch of the
+ * flat fit's phases (the first level's carries the flat subspaces), then one split pass, a stable sort, the sizes back
+ * to the host, the cut fits as one more batch, and a gather into the next level's compact matrix.  The batches' ordered
+ * sums run through a kernel in which a wavefront owns a run and stages its rows through LDS: the additions per (run,
+ * column) are the flat fit's, from +0 in ascending row order.
+ * Parity: as for the hierarchical form -- VAQ.cpp does not compile, every component is pinned, the oracle is the
+ * composition of the numpy restatements (tests/codebooks_bin_ref.py).
+ * Refused before any device work, the outputs untouched: everything vaqhip_fit_codebooks refuses, and rows_s < k_s for
+ * a binary subspace.  After the run: VAQHIP_EINVAL when a Lloyd assign meets a row at NaN or >= FLT_MAX from every
+ * centre (the flat rule).  Group sizes never refuse: this is the form for inputs the hierarchical one refuses.
+ * Not built: a multi-device form.  The host forms upload all rows when a subspace is binary. */
+int vaqhip_fit_codebooks_bin(int device_id, const float *X_rowmajor, int64_t n, int D, int M, const int *bits,
+                             const float *eigvec_real_rowmajor, int max_iter, float *centroids_out, int *iters_out,
+                             int *nan_rows_out);
+int vaqhip_fit_codebooks_bin_device(int device_id, const float *d_X, int64_t n, int D, int M, const int *bits,
+                                    const float *d_eigvec, int max_iter, float *d_centroids_out, int *iters_out,
+                                    int *nan_rows_out, void *stream);
+int vaqhip_fit_codebooks_bin_u8(int device_id, const uint8_t *X_rowmajor, int64_t n, int D, int M, const int *bits,
+                                const float *eigvec_real_rowmajor, int max_iter, float *centroids_out, int *iters_out,
+                                int *nan_rows_out);
+int vaqhip_fit_codebooks_bin_u8_device(int device_id, const uint8_t *d_X, int64_t n, int D, int M, const int *bits,
+                                       const float *d_eigvec, int max_iter, float *d_centroids_out, int *iters_out,
+                                       int *nan_rows_out, void *stream);
+typedef struct {
+  float total_ms;                       /* host time of the last binary fit on this thread, host copies excluded */
+  float fit_ms;                         /* sources, seeds and the levels' batches of 2-centre fits (and the flat subspaces) */
+  float split_ms;                       /* split pass, stable sort, bounds, counts to the host, regroup */
+  float cut_ms;                         /* the batches of the cut nodes' flat fits */
+  int levels;                           /* levels walked: the deepest node's depth */
+  int nodes;                            /* 2-centre fits run */
+  int cut_nodes;                        /* nodes that ended in a flat fit of tempK centres */
+  int resampled_fits;                   /* fits, 2-centre or cut, that sampled their node's rows */
+  int leaf_nodes;                       /* nodes at depth bits[s] */
+  int min_leaf_rows, max_leaf_rows;     /* the smallest and the largest of them (0: no path reached leaf depth) */
+  int max_iterations;                   /* the largest iteration count of a fit */
+  int bin_subspaces;                    /* 0: the call was the flat fit (fit_ms = total_ms) */
+  int subspaces, dims;
+  int64_t rows;
+} vaqhip_fit_codebooks_bin_timing;
+int vaqhip_last_fit_codebooks_bin_timing(vaqhip_fit_codebooks_bin_timing *out);  /* the calling thread's last one */
+/* per calling thread, for tests and measurements: 0 (default) the staged ordered sums, 1 the flat fit's one-thread-per-run
+ * kernel; the centres are the same bit for bit.  VAQHIP_EINVAL for another value. */
+int vaqhip_fit_codebooks_bin_set_sums(int mode);
 
 /* ---------------------------------------------------------------------------
  * Training from raw rows: the front half of VAQ::train (VAQ.cpp:11-524) -- the second moment of the sampled rows, its
@@ -703,6 +775,9 @@ int vaqhip_refiner_fit_codebooks(vaqhip_refiner *r, int M, const int *bits, cons
 /* vaqhip_fit_codebooks_hier above over the refiner's resident rows, float or byte, read in place */
 int vaqhip_refiner_fit_codebooks_hier(vaqhip_refiner *r, int M, const int *bits, const float *eigvec_real_rowmajor,
                                       int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out);
+/* vaqhip_fit_codebooks_bin above over the refiner's resident rows, float or byte, read in place */
+int vaqhip_refiner_fit_codebooks_bin(vaqhip_refiner *r, int M, const int *bits, const float *eigvec_real_rowmajor,
+                                     int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out);
 /* "Training from raw rows" above over the refiner's resident rows, float or byte, read in place (outputs: host arrays) */
 int vaqhip_refiner_train_moment(vaqhip_refiner *r, double *cov_out, float *cov_f_out);
 int vaqhip_refiner_train_rotation(vaqhip_refiner *r, int M, int bit_budget, int min_bits, int max_bits, float percent_var,

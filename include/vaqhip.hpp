@@ -386,8 +386,12 @@ public:
   // mHierarchicalKmeans (demo_vaq --kmeans-ver 1, VAQ.cpp:546-594): every subspace above 8 bits is fitted as 128 centres
   // and 1 << (bits - 7) centres inside each of their groups (vaqhip_fit_codebooks_hier; include/vaqhip.h has the
   // contract).  fitCodebooks, fitCodebooksRefineDataset and train honour it; after setDevices() it is
-  // VAQHIP_EUNSUPPORTED: the hierarchical fit has no multi-device form.  mBinaryKmeans is not built.
+  // VAQHIP_EUNSUPPORTED: the hierarchical fit has no multi-device form.
+  // mBinaryKmeans (demo_vaq --kmeans-ver 2, hierarchicalBinKmeans, VAQ.cpp:1293-1371): every subspace above 8 bits is
+  // fitted as a binary tree of 2-centre fits (vaqhip_fit_codebooks_bin); honoured by the same calls, refused after
+  // setDevices() in the same way.  As in the reference's if / else if, mHierarchicalKmeans wins when both are set.
   bool mHierarchicalKmeans = false;
+  bool mBinaryKmeans = false;
   std::vector<int> mCodebookIters, mCodebookNanRows;
   void fitCodebooks(const RowMatrixF &XTrain, int maxIter = 25) { fitCodebooksRows(XTrain.data(), (int64_t)XTrain.rows(), (int)XTrain.cols(), maxIter); }
   // from byte rows (readBVecsU8): the float overload's centres on the widened rows, bit for bit
@@ -406,7 +410,7 @@ public:
       return;
     }
     fitCodebooksWith(rf_dim_, [&](const float *eig, float *cent) {
-      return (mHierarchicalKmeans ? vaqhip_refiner_fit_codebooks_hier : vaqhip_refiner_fit_codebooks)(
+      return (mHierarchicalKmeans ? vaqhip_refiner_fit_codebooks_hier : mBinaryKmeans ? vaqhip_refiner_fit_codebooks_bin : vaqhip_refiner_fit_codebooks)(
           rf_, mHighestSubs(), mBitsAlloc.data(), eig, maxIter, cent, mCodebookIters.data(), mCodebookNanRows.data());
     });
   }
@@ -474,14 +478,16 @@ private:
   void refuseHierarchicalMulti() const {
     if (mHierarchicalKmeans && !mDevices.empty())
       throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: mHierarchicalKmeans has no multi-device form");
+    if (mBinaryKmeans && !mDevices.empty())
+      throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: mBinaryKmeans has no multi-device form");
   }
   int fitCodebooksCall(int dev, const float *X, int64_t n, int D, int M, const int *bits, const float *eig, int it,
                        float *cent, int *iters, int *nan) const {
-    return (mHierarchicalKmeans ? vaqhip_fit_codebooks_hier : vaqhip_fit_codebooks)(dev, X, n, D, M, bits, eig, it, cent, iters, nan);
+    return (mHierarchicalKmeans ? vaqhip_fit_codebooks_hier : mBinaryKmeans ? vaqhip_fit_codebooks_bin : vaqhip_fit_codebooks)(dev, X, n, D, M, bits, eig, it, cent, iters, nan);
   }
   int fitCodebooksCall(int dev, const uint8_t *X, int64_t n, int D, int M, const int *bits, const float *eig, int it,
                        float *cent, int *iters, int *nan) const {
-    return (mHierarchicalKmeans ? vaqhip_fit_codebooks_hier_u8 : vaqhip_fit_codebooks_u8)(dev, X, n, D, M, bits, eig, it, cent, iters, nan);
+    return (mHierarchicalKmeans ? vaqhip_fit_codebooks_hier_u8 : mBinaryKmeans ? vaqhip_fit_codebooks_bin_u8 : vaqhip_fit_codebooks_u8)(dev, X, n, D, M, bits, eig, it, cent, iters, nan);
   }
   static int fitCodebooksCall(const std::vector<int> &devs, const float *X, int64_t n, int D, int M, const int *bits,
                               const float *eig, int it, float *cent, int *iters, int *nan) {

@@ -63,6 +63,9 @@ SYMBOLS = [
     "vaqhip_multi_last_fit_codebooks_timing",
     "vaqhip_fit_codebooks_hier", "vaqhip_fit_codebooks_hier_device", "vaqhip_fit_codebooks_hier_u8",
     "vaqhip_fit_codebooks_hier_u8_device", "vaqhip_refiner_fit_codebooks_hier", "vaqhip_last_fit_codebooks_hier_timing",
+    "vaqhip_fit_codebooks_bin", "vaqhip_fit_codebooks_bin_device", "vaqhip_fit_codebooks_bin_u8",
+    "vaqhip_fit_codebooks_bin_u8_device", "vaqhip_refiner_fit_codebooks_bin", "vaqhip_last_fit_codebooks_bin_timing",
+    "vaqhip_fit_codebooks_bin_set_sums",
     "vaqhip_train_moment", "vaqhip_train_moment_device", "vaqhip_train_moment_u8", "vaqhip_train_moment_u8_device",
     "vaqhip_refiner_train_moment", "vaqhip_sym_eigen_device", "vaqhip_sym_eigen_host", "vaqhip_train_plan",
     "vaqhip_allocate_bits", "vaqhip_train_rotation", "vaqhip_train_rotation_device", "vaqhip_train_rotation_u8",
@@ -123,6 +126,14 @@ class FitCodebooksHierTiming(C.Structure):
                 ("groups", C.c_int), ("min_group_rows", C.c_int), ("max_group_rows", C.c_int),
                 ("stage1_iterations", C.c_int), ("stage2_iterations", C.c_int), ("hier_subspaces", C.c_int),
                 ("subspaces", C.c_int), ("dims", C.c_int), ("rows", C.c_int64)]
+
+
+class FitCodebooksBinTiming(C.Structure):
+    _fields_ = [("total_ms", C.c_float), ("fit_ms", C.c_float), ("split_ms", C.c_float), ("cut_ms", C.c_float),
+                ("levels", C.c_int), ("nodes", C.c_int), ("cut_nodes", C.c_int), ("resampled_fits", C.c_int),
+                ("leaf_nodes", C.c_int), ("min_leaf_rows", C.c_int), ("max_leaf_rows", C.c_int),
+                ("max_iterations", C.c_int), ("bin_subspaces", C.c_int), ("subspaces", C.c_int), ("dims", C.c_int),
+                ("rows", C.c_int64)]
 
 
 class TrainTiming(C.Structure):
@@ -249,14 +260,18 @@ def load():
     L.vaqhip_lut_fit_set_timing.argtypes = [i32]
     L.vaqhip_last_lut_fit_timing.argtypes = [C.POINTER(LutFitTiming)]
     L.vaqhip_index_set_lut_quantiles.argtypes = [vp, vp]
-    for name in ("vaqhip_fit_codebooks", "vaqhip_fit_codebooks_u8", "vaqhip_fit_codebooks_hier", "vaqhip_fit_codebooks_hier_u8"):
+    for name in ("vaqhip_fit_codebooks", "vaqhip_fit_codebooks_u8", "vaqhip_fit_codebooks_hier", "vaqhip_fit_codebooks_hier_u8",
+                 "vaqhip_fit_codebooks_bin", "vaqhip_fit_codebooks_bin_u8"):
         getattr(L, name).argtypes = [i32, vp, i64, i32, i32, C.POINTER(i32), vp, i32, vp, vp, vp]
     for name in ("vaqhip_fit_codebooks_device", "vaqhip_fit_codebooks_u8_device", "vaqhip_fit_codebooks_hier_device",
-                 "vaqhip_fit_codebooks_hier_u8_device"):
+                 "vaqhip_fit_codebooks_hier_u8_device", "vaqhip_fit_codebooks_bin_device", "vaqhip_fit_codebooks_bin_u8_device"):
         getattr(L, name).argtypes = [i32, vp, i64, i32, i32, C.POINTER(i32), vp, i32, vp, vp, vp, vp]
     L.vaqhip_refiner_fit_codebooks.argtypes = [vp, i32, C.POINTER(i32), vp, i32, vp, vp, vp]
     L.vaqhip_refiner_fit_codebooks_hier.argtypes = [vp, i32, C.POINTER(i32), vp, i32, vp, vp, vp]
     L.vaqhip_last_fit_codebooks_hier_timing.argtypes = [C.POINTER(FitCodebooksHierTiming)]
+    L.vaqhip_refiner_fit_codebooks_bin.argtypes = [vp, i32, C.POINTER(i32), vp, i32, vp, vp, vp]
+    L.vaqhip_last_fit_codebooks_bin_timing.argtypes = [C.POINTER(FitCodebooksBinTiming)]
+    L.vaqhip_fit_codebooks_bin_set_sums.argtypes = [i32]
     L.vaqhip_fit_codebooks_set_timing.argtypes = [i32]
     L.vaqhip_last_fit_codebooks_timing.argtypes = [C.POINTER(FitCodebooksTiming)]
     for name in ("vaqhip_train_moment", "vaqhip_train_moment_u8"):

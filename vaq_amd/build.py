@@ -54,6 +54,7 @@ TRAIN_ROT_HEADER = os.path.join(CSRC, "vaq_train_rot.h")  # the Jacobi rotation,
 TRAIN_HEADER = os.path.join(CSRC, "vaq_train.h")  # the kernels of the training front half
 CODEBOOKS_MULTI_PLAN_HEADER = os.path.join(CSRC, "fit_codebooks_multi_plan.h")  # owners, sub-plans, sample split of the sharded fit (no HIP)
 CODEBOOKS_HIER_PLAN_HEADER = os.path.join(CSRC, "fit_codebooks_hier_plan.h")  # rows, batches, refusals, tiles of the hierarchical fit (no HIP)
+CODEBOOKS_BIN_PLAN_HEADER = os.path.join(CSRC, "fit_codebooks_bin_plan.h")  # nodes, level batches, chunks, tiles of the binary-tree fit (no HIP)
 
 
 def _deps(src: str):
@@ -70,6 +71,7 @@ def _deps(src: str):
         deps += [CODEBOOKS_PLAN_HEADER, KMEANS_SAMPLE_HEADER]
     if src in ("vaq_codebooks.hip", "vaqhip_codebooks.cpp"):
         deps.append(CODEBOOKS_HIER_PLAN_HEADER)
+        deps.append(CODEBOOKS_BIN_PLAN_HEADER)
     if src == MULTI_CODEBOOKS_SOURCE:
         deps.append(CODEBOOKS_MULTI_PLAN_HEADER)
     if src in ("vaq_train.hip", "vaqhip_train.cpp"):

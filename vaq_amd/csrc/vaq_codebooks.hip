@@ -22,6 +22,7 @@
 // the hierarchical form's batches (codebooks_fit_hier below): 128-centre fits beside the flat subspaces, then the
 // K2-centre fits of all groups over a compact regrouped matrix, the assign kernel walking a table of row tiles.
 // No float atomics, no MFMA, no reassociation; compiled with -ffp-contract=off like every file of the library.
+#include "fit_codebooks_bin_plan.h"
 #include "fit_codebooks_hier_plan.h"
 #include "kmeans_sample.h"
 #include "vaq_kernels.h"
@@ -161,6 +162,83 @@ __global__ void cb_accumulate_kernel(CbSources src, int L, const cbfit::Fit *__r
   float sum = 0.0f;
   for (int i = start[g], e = end[g]; i < e; i++) sum += x[(size_t)rows_sorted[i] * fd.stride];
   part[(size_t)g * L + col] = sum;
+}
+
+// cb_accumulate_kernel's sums for long runs (the binary fit's batches: two centres make a run a quarter of a node): one
+// wavefront per run, grid = (run of the fit, fit).  The wavefront stages a tile of the run's rows through LDS -- first the
+// row numbers, then the slices, 64 loads in flight per instruction and none of them on the add chain -- and lane c
+// adds column c of the staged rows in ascending order, the sum carried in a register from tile to tile.  Per (run,
+// column) that is cb_accumulate_kernel's chain exactly: from +0.0f, one row after the other, nothing reassociated.
+// The tile is [row][column] for CB_SUMS_COLS columns at a time: the adding lanes read neighbouring words (no bank
+// conflict), the staging lanes write neighbouring words.  An empty run writes +0.
+constexpr int CB_SUMS_COLS = 64, CB_SUMS_TILE_FLOATS = 4096, CB_SUMS_MAX_ROWS = 256;
+
+__global__ __launch_bounds__(64) void cb_sums_staged_kernel(CbSources src, int L, const cbfit::Fit *__restrict__ fits,
+                                                           const unsigned *__restrict__ rows_sorted,
+                                                           const int *__restrict__ start, const int *__restrict__ end,
+                                                           float *__restrict__ part) {
+  __shared__ float tile[CB_SUMS_TILE_FLOATS];
+  __shared__ unsigned tile_row[CB_SUMS_MAX_ROWS];
+  const cbfit::Fit fd = fits[blockIdx.y];
+  if ((int)blockIdx.x >= 2 * fd.k) return;  // (the whole wavefront)
+  const int g = fd.run_off + (int)blockIdx.x, lane = threadIdx.x;
+  const int s = start[g], e = end[g];
+  const float *x = cb_fit_base(src, fd);
+  for (int c0 = 0; c0 < L; c0 += CB_SUMS_COLS) {
+    const int cw = min(CB_SUMS_COLS, L - c0);
+    const int T = min(CB_SUMS_MAX_ROWS, CB_SUMS_TILE_FLOATS / cw);
+    float sum = 0.0f;
+    for (int t0 = s; t0 < e; t0 += T) {
+      const int tn = min(T, e - t0);
+      __syncthreads();  // (the tile before has been added)
+      for (int i = lane; i < tn; i += 64) tile_row[i] = rows_sorted[t0 + i];
+      __syncthreads();
+      for (int i = lane; i < tn * cw; i += 64) {
+        const int r = i / cw;
+        tile[i] = x[(size_t)tile_row[r] * fd.stride + c0 + (i - r * cw)];
+      }
+      __syncthreads();
+      if (lane < cw)
+        for (int r = 0; r < tn; r++) sum += tile[r * cw + lane];
+    }
+    if (lane < cw) part[(size_t)g * L + c0 + lane] = sum;
+  }
+}
+
+// The binary fit's split of a node's rows between its two centres (getBelongsToBinaryCluster, VAQ.cpp:1293-1310): one
+// row per thread, rows [row0, row0 + blockDim.x) of fit tiles[blockIdx.x].fit, the two centres in LDS (every lane reads
+// the same word: a broadcast).  left = (x - C0).squaredNorm(), right = (x - C1).squaredNorm() in Eigen's order, no
+// sqrt; the row goes left iff left < right -- a tie and a NaN on either side go right, and there is no row without a
+// centre.  keys[pair_off + r] = run_off + side, vals[pair_off + r] = r.
+__global__ void cb_split_kernel(CbSources src, int L, const cbfit::Fit *__restrict__ fits, const cbfit::Tile *__restrict__ tiles,
+                                const float *__restrict__ means, unsigned *__restrict__ keys, unsigned *__restrict__ vals) {
+  extern __shared__ float cb_lds[];  // [2][L]
+  const cbfit::Tile t = tiles[blockIdx.x];
+  const cbfit::Fit fd = fits[t.fit];
+  for (int i = threadIdx.x; i < 2 * L; i += blockDim.x) cb_lds[i] = means[(size_t)fd.cent_off * L + i];
+  __syncthreads();
+  const int64_t r = (int64_t)t.row0 + threadIdx.x;
+  if (r >= fd.rows) return;
+  const float *x = cb_fit_base(src, fd) + (size_t)r * fd.stride;
+  const float left = sq_norm_eigen<true>(x, 1, cb_lds, L);
+  const float right = sq_norm_eigen<true>(x, 1, cb_lds + L, L);
+  keys[fd.pair_off + r] = (unsigned)(fd.run_off + (left < right ? 0 : 1));
+  vals[fd.pair_off + r] = (unsigned)r;
+}
+
+// The regroup behind the split: sorted pair p belongs to fit keys_sorted[p] / 2 and is row rows_sorted[p] of it; where
+// that node has children (dest >= 0) its slice becomes row dest + (p - pair_off) of the next level's compact matrix.
+__global__ void cb_regroup_kernel(CbSources src, int L, const cbfit::Fit *__restrict__ fits, const int64_t *__restrict__ dest,
+                                  const unsigned *__restrict__ keys_sorted, const unsigned *__restrict__ rows_sorted,
+                                  int64_t n_pairs, float *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_pairs * L) return;
+  const int64_t p = i / L;
+  const int f = (int)(keys_sorted[p] >> 1);
+  const int64_t d = dest[f];
+  if (d < 0) return;
+  const cbfit::Fit fd = fits[f];
+  out[(size_t)(d + (p - fd.pair_off)) * L + (i - p * L)] = cb_fit_base(src, fd)[(size_t)rows_sorted[p] * fd.stride + (i - p * L)];
 }
 
 // one wavefront per (centre, fit) (KMeans.hpp:586-604); changed[f] is set when a centre of fit f was replaced
@@ -397,9 +475,10 @@ hipError_t cb_launch_assign(const CbSources &src, int L, const cbfit::Batch &b, 
 // phase and iteration for ALL fits until every fit's centres stopped changing or max_iter.  The sources are complete on
 // `st`; d_means spans b.n_cent centres.  iters_out[fits] (host).  began: when the caller started preparing the
 // sources, for phases->gather_ms (null phases: no per-phase synchronisation).  Synchronises the stream.
+// staged_sums (the binary fit's batches): the sums by cb_sums_staged_kernel, the same bits.
 hipError_t cb_lloyd_batch(const CbSources &src, int L, const cbfit::Batch &b, int max_iter, float *d_means, int *iters_out,
                           int *no_centre_out, CodebookPhases *phases, std::chrono::steady_clock::time_point began,
-                          hipStream_t st) {
+                          hipStream_t st, bool staged_sums = false) {
   const int F = (int)b.fit.size();
   if (F < 1 || b.rows_max < 1 || b.n_pairs > 0x7fffffff || F > 65535) return hipErrorInvalidValue;
   const int n_pairs = (int)b.n_pairs, n_runs = b.n_runs;
@@ -474,8 +553,12 @@ hipError_t cb_lloyd_batch(const CbSources &src, int L, const cbfit::Batch &b, in
     hipLaunchKernelGGL(cb_bounds_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, keys_out, n_pairs,
                        start, end);
     CB_TRY(hipGetLastError());
-    hipLaunchKernelGGL(cb_accumulate_kernel, acc_grid, dim3(256), 0, st, src, L, fits, vals_out, start, end,
-                       b_part.as<float>());
+    if (staged_sums)
+      hipLaunchKernelGGL(cb_sums_staged_kernel, dim3((unsigned)(2 * b.k_max), (unsigned)F), dim3(64), 0, st, src, L, fits, vals_out,
+                         start, end, b_part.as<float>());
+    else
+      hipLaunchKernelGGL(cb_accumulate_kernel, acc_grid, dim3(256), 0, st, src, L, fits, vals_out, start, end,
+                         b_part.as<float>());
     CB_TRY(hipGetLastError());
     CB_TRY(phase_end(phases ? &phases->accumulate_ms : nullptr));
     hipLaunchKernelGGL(cb_update_kernel, dim3((unsigned)b.k_max, (unsigned)F), dim3(64), 0, st, b_part.as<float>(), start,
@@ -660,6 +743,172 @@ hipError_t codebooks_fit_hier(RowsRef d_X, int64_t n, int D, int L, const cbhier
     }
   for (int s = 0; s < M; s++) stats->stage1_iters = std::max(stats->stage1_iters, it1[(size_t)s]);
   stats->stage2_ms = cb_ms_since(t0);
+  if (phases) *phases = ph;
+  sync_on_return.armed = false;
+  return hipStreamSynchronize(st);
+}
+
+// ---- the binary-tree fit (DESIGN.md section 4f "Binary form"; fit_codebooks_bin_plan.h) ----
+// Level by level over the trees of ALL binary subspaces.  Per level: the 2-centre fits of every live node as one run
+// of the Lloyd phases (the first level's carries the call's flat subspaces); unless the level is a subspace's last,
+// the split of all rows of its nodes, a stable sort by 2 * node + side and the run bounds, which come back to the
+// host; the flat fits of the nodes the sizes cut, as one more run over the same matrix; then the rows of the nodes
+// that go on are gathered, in sorted order, into the other compact [rows][L] matrix -- left child, right child, node
+// after node, every child's rows in ascending position within its parent.  A fit over more rows than
+// staticFitSampling takes works on rows randomPermutation(m)[0 .. sample) of its node, gathered into `extra`.  Every
+// fit writes its centres where the node's block of the output begins: a split node's two centres are overwritten by
+// its descendants, which tile the block.  On *no_centre_out the centres are not to be used.
+hipError_t codebooks_fit_bin(RowsRef d_X, int64_t n, int D, int L, const cbbin::Plan &plan, const float *d_eig, int max_iter,
+                             bool staged_sums, float *d_means, int *iters_out, int *no_centre_out, CodebookBinStats *stats,
+                             CodebookPhases *phases, hipStream_t st) {
+  const int M = (int)plan.flat.sub.size();
+  if (M < 1 || plan.bsub.empty() || plan.gathered < 1 || plan.n_pairs > 0x7fffffff) return hipErrorInvalidValue;
+  hipError_t e;
+  CbPrepared src;
+  vaqhost::DevBuf b_perm, b_extra, b_fit, b_tile, b_dest, b_keys_in, b_keys_out, b_vals_in, b_vals_out, b_bounds, b_temp, b_level[2];
+  CbSync sync_on_return{st, true};
+  *no_centre_out = 0;
+  *stats = CodebookBinStats{};
+  stats->min_leaf_rows = 0x7fffffff;
+  CodebookPhases ph;
+  const auto began = std::chrono::steady_clock::now();
+  for (int s = 0; s < M; s++) iters_out[s] = 0;
+
+  CB_TRY(cb_prepare(d_X, n, D, d_eig, plan.n_full > 0, plan.gathered, true, src, st));
+  const int n_pairs = (int)plan.n_pairs, tile_rows = cbfit::assign_tile_rows(L);
+  CB_TRY(b_keys_in.ensure((size_t)n_pairs * 4));
+  CB_TRY(b_keys_out.ensure((size_t)n_pairs * 4));
+  CB_TRY(b_vals_in.ensure((size_t)n_pairs * 4));
+  CB_TRY(b_vals_out.ensure((size_t)n_pairs * 4));
+  unsigned *keys_in = b_keys_in.as<unsigned>(), *keys_out = b_keys_out.as<unsigned>();
+  unsigned *vals_in = b_vals_in.as<unsigned>(), *vals_out = b_vals_out.as<unsigned>();
+
+  CbSources cur{{src.sample, src.full, nullptr}};
+  // one kind of fits of a level: the samples of those that sample, then chunk after chunk of the Lloyd phases
+  auto run_fits = [&](const std::vector<cbbin::Node> &level, const cbbin::Fits &f, std::chrono::steady_clock::time_point t0) -> hipError_t {
+    if (!f.resample.empty()) {
+      std::vector<int> perm;
+      std::vector<size_t> at;
+      for (const cbbin::Resample &r : f.resample) {
+        const std::vector<int> rows = permutation_head(level[(size_t)r.node].rows, r.rows);
+        at.push_back(perm.size());
+        perm.insert(perm.end(), rows.begin(), rows.end());
+      }
+      CB_TRY(b_perm.ensure(perm.size() * sizeof(int)));
+      CB_TRY(b_extra.ensure((size_t)f.extra_rows * L * sizeof(float)));
+      CB_TRY(hipMemcpyAsync(b_perm.p, perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice, st));
+      for (size_t i = 0; i < f.resample.size(); i++) {
+        const cbbin::Resample &r = f.resample[i];
+        const cbbin::Node &nd = level[(size_t)r.node];
+        hipLaunchKernelGGL(cb_slice_kernel, dim3((unsigned)(((int64_t)r.rows * L + 255) / 256)), dim3(256), 0, st,
+                           cur.p[nd.src] + (size_t)nd.row0 * nd.stride, nd.stride, nd.col, b_perm.as<int>() + at[i],
+                           (int64_t)r.rows, L, b_extra.as<float>() + (size_t)r.off * L);
+        CB_TRY(hipGetLastError());
+      }
+      CB_TRY(hipStreamSynchronize(st));  // (perm is the host's)
+      stats->resampled_fits += (int)f.resample.size();
+    }
+    const CbSources fit_src{{cur.p[0], cur.p[1], b_extra.as<float>()}};
+    for (size_t c = 0; c < f.chunk.size(); c++) {
+      std::vector<int> its(f.chunk[c].fit.size(), 0);
+      int nc = 0;
+      CB_TRY(cb_lloyd_batch(fit_src, L, f.chunk[c], max_iter, d_means, its.data(), &nc, phases ? &ph : nullptr, t0, st, staged_sums));
+      *no_centre_out |= nc;
+      for (size_t i = 0; i < its.size(); i++) {
+        const int o = f.owner[c][i];
+        int &out = iters_out[o < 0 ? -1 - o : plan.bsub[(size_t)level[(size_t)o].b].s];
+        out = std::max(out, its[i]);
+        stats->max_iters = std::max(stats->max_iters, its[i]);
+      }
+      t0 = std::chrono::steady_clock::now();
+    }
+    return hipSuccess;
+  };
+
+  std::vector<cbbin::Node> level = cbbin::root_level(plan, D, L);
+  for (int depth = 1; !level.empty(); depth++) {
+    // ---- the 2-centre fits of every live node ----
+    auto t0 = std::chrono::steady_clock::now();
+    std::vector<int> all(level.size()), inner;
+    for (size_t i = 0; i < level.size(); i++) {
+      all[i] = (int)i;
+      const cbbin::Node &nd = level[i];
+      if (nd.depth < plan.bsub[(size_t)nd.b].bits) {
+        inner.push_back((int)i);
+        continue;
+      }
+      stats->leaf_nodes++;
+      stats->min_leaf_rows = std::min(stats->min_leaf_rows, nd.rows);
+      stats->max_leaf_rows = std::max(stats->max_leaf_rows, nd.rows);
+    }
+    stats->levels = depth;
+    stats->nodes += (int)level.size();
+    CB_TRY(run_fits(level, cbbin::make_fits(plan, level, all, false, depth == 1, D, L, tile_rows), depth == 1 ? began : t0));
+    stats->fit_ms += cb_ms_since(t0);
+    if (*no_centre_out || inner.empty()) break;
+
+    // ---- the split of the nodes that are no leaves ----
+    t0 = std::chrono::steady_clock::now();
+    const cbfit::Batch split = cbbin::make_split(plan, level, inner, tile_rows);
+    const int F = (int)split.fit.size(), sp = (int)split.n_pairs;
+    CB_TRY(b_fit.ensure((size_t)F * sizeof(cbfit::Fit)));
+    CB_TRY(b_tile.ensure(split.tile.size() * sizeof(cbfit::Tile)));
+    CB_TRY(b_bounds.ensure((size_t)4 * F * sizeof(int)));
+    CB_TRY(b_dest.ensure((size_t)F * sizeof(int64_t)));
+    int *start = b_bounds.as<int>(), *end = start + 2 * F;
+    size_t temp_bytes = 0;
+    CB_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)sp, 0u, split.key_bits, st));
+    CB_TRY(b_temp.ensure(temp_bytes ? temp_bytes : 16));
+    CB_TRY(hipMemcpyAsync(b_fit.p, split.fit.data(), (size_t)F * sizeof(cbfit::Fit), hipMemcpyHostToDevice, st));
+    CB_TRY(hipMemcpyAsync(b_tile.p, split.tile.data(), split.tile.size() * sizeof(cbfit::Tile), hipMemcpyHostToDevice, st));
+    CB_TRY(hipMemsetAsync(start, 0, (size_t)4 * F * sizeof(int), st));
+    hipLaunchKernelGGL(cb_split_kernel, dim3((unsigned)split.tile.size()), dim3(tile_rows), (size_t)2 * L * sizeof(float), st, cur, L,
+                       b_fit.as<cbfit::Fit>(), b_tile.as<cbfit::Tile>(), d_means, keys_in, vals_in);
+    CB_TRY(hipGetLastError());
+    // stable: each side of a node keeps its rows in ascending position within the node
+    CB_TRY(rocprim::radix_sort_pairs(b_temp.p, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)sp, 0u, split.key_bits, st));
+    hipLaunchKernelGGL(cb_bounds_kernel, dim3((unsigned)((sp + 255) / 256)), dim3(256), 0, st, keys_out, sp, start, end);
+    CB_TRY(hipGetLastError());
+    std::vector<int> bounds((size_t)4 * F), left((size_t)F), right((size_t)F), cut;
+    CB_TRY(hipMemcpyAsync(bounds.data(), start, bounds.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    CB_TRY(hipStreamSynchronize(st));
+    std::vector<cbbin::Kind> kind((size_t)F);
+    for (int i = 0; i < F; i++) {
+      left[(size_t)i] = bounds[(size_t)2 * F + 2 * i] - bounds[(size_t)2 * i];
+      right[(size_t)i] = bounds[(size_t)2 * F + 2 * i + 1] - bounds[(size_t)2 * i + 1];
+      const cbbin::Node &nd = level[(size_t)inner[(size_t)i]];
+      kind[(size_t)i] = cbbin::decide(plan.bsub[(size_t)nd.b], nd, left[(size_t)i], right[(size_t)i]);
+      if (kind[(size_t)i] == cbbin::CUT) cut.push_back(inner[(size_t)i]);
+    }
+    std::vector<int64_t> dest;
+    int64_t next_rows = 0;
+    std::vector<cbbin::Node> next = cbbin::next_level(level, inner, kind, left.data(), right.data(), L, &dest, &next_rows);
+    float *out = nullptr;
+    if (next_rows > 0) {  // (before the cut fits: they read `cur` as well, nothing writes it)
+      vaqhost::DevBuf &nb = b_level[depth & 1];
+      CB_TRY(nb.ensure((size_t)next_rows * L * sizeof(float)));
+      out = nb.as<float>();
+      CB_TRY(hipMemcpyAsync(b_dest.p, dest.data(), (size_t)F * sizeof(int64_t), hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(cb_regroup_kernel, dim3((unsigned)(((int64_t)sp * L + 255) / 256)), dim3(256), 0, st, cur, L,
+                         b_fit.as<cbfit::Fit>(), b_dest.as<int64_t>(), keys_out, vals_out, (int64_t)sp, out);
+      CB_TRY(hipGetLastError());
+      CB_TRY(hipStreamSynchronize(st));  // (dest is the host's)
+    }
+    stats->split_ms += cb_ms_since(t0);
+
+    // ---- the nodes the sizes cut: a flat fit of tempK centres each, over the matrix the level was fitted on ----
+    if (!cut.empty()) {
+      t0 = std::chrono::steady_clock::now();
+      stats->cut_nodes += (int)cut.size();
+      CB_TRY(run_fits(level, cbbin::make_fits(plan, level, cut, true, false, D, L, tile_rows), t0));
+      stats->cut_ms += cb_ms_since(t0);
+      if (*no_centre_out) break;
+    }
+    level.swap(next);
+    cur = CbSources{{out, nullptr, nullptr}};
+  }
+  if (!stats->leaf_nodes) stats->min_leaf_rows = 0;
+  stats->total_ms = cb_ms_since(began);
   if (phases) *phases = ph;
   sync_on_return.armed = false;
   return hipStreamSynchronize(st);

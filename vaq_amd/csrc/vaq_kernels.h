@@ -561,6 +561,26 @@ struct CodebookHierStats {
 hipError_t codebooks_fit_hier(RowsRef d_X, int64_t n, int D, int L, const cbhier::Plan &plan, const float *d_eig,
                               int max_iter, float *d_means, int *iters_out, int *no_centre_out, cbhier::Refusal *refusal,
                               CodebookHierStats *stats, CodebookPhases *phases, hipStream_t st);
+// ---- the binary-tree form (fit_codebooks_bin_plan.h): subspaces above 8 bits as a tree of 2-centre fits ----
+namespace cbbin {
+struct Plan;
+}
+struct CodebookBinStats {
+  double total_ms = 0, fit_ms = 0, split_ms = 0, cut_ms = 0;  // host time, each ended by a stream synchronisation
+  int levels = 0, nodes = 0, cut_nodes = 0, leaf_nodes = 0;   // nodes: 2-centre fits run; leaves: nodes at depth bits[s]
+  int resampled_fits = 0;                                    // fits (2-centre or cut) that sampled their node's rows
+  int min_leaf_rows = 0, max_leaf_rows = 0;                  // 0 where no path reached leaf depth
+  int max_iters = 0;
+};
+// d_X, d_eig, max_iter, iters_out[M], phases, st: as codebooks_fit.  Level by level: the 2-centre fits of all live nodes
+// of all binary subspaces as one batch (the first one carries the flat subspaces), the split of their rows by
+// squaredNorm (left iff left < right), the counts back to the host, the flat fits of the cut nodes as one more batch,
+// the stable regroup into the next level's compact matrix.  staged_sums: the batches' ordered sums by the staged
+// kernel (the same bits as cb_accumulate_kernel's).  d_means: plan.n_cent centres (device).  *no_centre_out: as
+// codebooks_fit.  The plan must hold a binary subspace.  Synchronises the stream.
+hipError_t codebooks_fit_bin(RowsRef d_X, int64_t n, int D, int L, const cbbin::Plan &plan, const float *d_eig, int max_iter,
+                             bool staged_sums, float *d_means, int *iters_out, int *no_centre_out, CodebookBinStats *stats,
+                             CodebookPhases *phases, hipStream_t st);
 // The sharded fit's shard step: out [cnt][D_w] = the compact columns of one owner (d_subs: its subspaces, D_w / L of
 // them, device) for the rows a shard contributes -- X's local rows d_rows[0 .. cnt) (device), or first + i where
 // d_rows is null.  X: the shard's rows, float or byte, D wide; d_eig null: the rows' own values, else

@@ -200,6 +200,9 @@ int fit_codebooks_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, in
 // the same for vaqhip_fit_codebooks_hier[_u8] (subspaces above 8 bits in two stages)
 int fit_codebooks_hier_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits, const float *eigvec,
                                    int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out);
+// and for vaqhip_fit_codebooks_bin[_u8] (subspaces above 8 bits as a tree of 2-centre fits)
+int fit_codebooks_bin_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits, const float *eigvec,
+                                  int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out);
 // vaqhip_train.cpp: vaqhip_train_moment's and vaqhip_train_rotation's bodies over rows resident on `device`, which
 // vaqhip_refiner.cpp calls over its resident rows (complete); the outputs are the host's
 int train_moment_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, double *cov_out, float *cov_f_out);

@@ -330,6 +330,16 @@ int vaqhip_refiner_fit_codebooks_hier(vaqhip_refiner *r, int M, const int *bits,
                                         iters_out, nan_rows_out);
 }
 
+// the binary-tree form of the same (subspaces above 8 bits as a tree of 2-centre fits)
+int vaqhip_refiner_fit_codebooks_bin(vaqhip_refiner *r, int M, const int *bits, const float *eigvec, int max_iter,
+                                     float *centroids_out, int *iters_out, int *nan_rows_out) {
+  if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
+  std::lock_guard<std::mutex> lk(r->mu);
+  if (r->N == 0) return fail(VAQHIP_ESTATE, "the refiner holds no rows: vaqhip_refiner_set_rows first");
+  return fit_codebooks_bin_rows_device(r->device, r->rows.rows(), r->N, r->D, M, bits, eigvec, max_iter, centroids_out,
+                                       iters_out, nan_rows_out);
+}
+
 // the training front half over the resident rows, read in place (vaqhip_train.cpp does the rest)
 int vaqhip_refiner_train_moment(vaqhip_refiner *r, double *cov_out, float *cov_f_out) {
   if (!r) return fail(VAQHIP_EINVAL, "refiner is null");

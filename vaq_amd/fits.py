@@ -108,6 +108,44 @@ def last_fit_codebooks_hier_timing() -> dict:
     return _struct_dict(t)
 
 
+def _fit_codebooks_bin(X, M, bits, eigvec, max_iter, device, u8: bool):
+    X = _fit_rows(X, u8)
+    fn = "vaqhip_fit_codebooks_bin" + ("_u8" if u8 else "")
+    return _fit_codebooks_call(X.shape[1], M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn: getattr(L, fn)(
+        int(device), _ptr(X), X.shape[0], X.shape[1], int(M), b, e, it, c, i, nn))
+
+
+def fit_codebooks_bin(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25,
+                      device: int = 0):
+    """vaqhip_fit_codebooks_bin: fit_codebooks with every subspace above 8 bits fitted as a binary tree, as VAQ::train
+    does under mBinaryKmeans (demo_vaq --kmeans-ver 2): a 2-centre fit per node, the node's rows split by the nearer
+    centre (squaredNorm, no sqrt, ties right), down to depth bits[s]; a node whose split leaves a side with fewer rows
+    than it needs centres is fitted flat and ends its branch.  No group size is refused: the form for skewed data.
+    Subspaces of at most 8 bits, and a call without any wider one, are fit_codebooks's bit for bit.  Returns what
+    fit_codebooks returns; iterations[s] is the largest count among a binary subspace's fits.  Single device only."""
+    return _fit_codebooks_bin(X, M, bits, eigvec, max_iter, device, False)
+
+
+def fit_codebooks_bin_u8(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25,
+                         device: int = 0):
+    """fit_codebooks_bin from byte rows (vaqhip_fit_codebooks_bin_u8): its result on X.astype(float32), bit for bit."""
+    return _fit_codebooks_bin(X, M, bits, eigvec, max_iter, device, True)
+
+
+def last_fit_codebooks_bin_timing() -> dict:
+    """Figures of the calling thread's last binary fit (vaqhip_last_fit_codebooks_bin_timing): fit_ms, split_ms, cut_ms,
+    the levels walked, the 2-centre fits run, the cut and leaf nodes, the fits that sampled."""
+    t = _lib.FitCodebooksBinTiming()
+    _lib.check(_lib.load().vaqhip_last_fit_codebooks_bin_timing(C.byref(t)))
+    return _struct_dict(t)
+
+
+def fit_codebooks_bin_sums(mode: int) -> None:
+    """Which kernel adds the binary fit's ordered sums for the calling thread (vaqhip_fit_codebooks_bin_set_sums): 0 the
+    staged one (default), 1 the flat fit's; the centres are the same bit for bit."""
+    _lib.check(_lib.load().vaqhip_fit_codebooks_bin_set_sums(int(mode)))
+
+
 def fit_codebooks_timing(on: bool) -> None:
     """Phase times for the calling thread's fits (vaqhip_fit_codebooks_set_timing): one synchronisation per phase."""
     _lib.check(_lib.load().vaqhip_fit_codebooks_set_timing(1 if on else 0))

@@ -13,6 +13,7 @@ from . import _lib  # noqa: F401
 from ._adapt import _ptr, _same, _u8_rows, _u8_rows_device, _wref  # noqa: F401
 from .fast import VaqHipFast  # noqa: F401
 from .fits import fit_codebooks_hier, fit_codebooks_hier_u8, last_fit_codebooks_hier_timing  # noqa: F401
+from .fits import fit_codebooks_bin, fit_codebooks_bin_u8, last_fit_codebooks_bin_timing, fit_codebooks_bin_sums  # noqa: F401
 from .fits import (_fit_codebooks_call, _fit_quantiles_call, fit_codebooks, fit_codebooks_timing,  # noqa: F401
                    fit_codebooks_u8, last_fit_codebooks_timing, last_lut_fit_multi_timing,
                    last_multi_fit_codebooks_timing, last_train_timing, lut_fit_quantiles_multi,

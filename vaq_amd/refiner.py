@@ -210,6 +210,12 @@ class VaqRefiner(_RefinerBase):
         return _fit_codebooks_call(self.D, M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn:
                                    L.vaqhip_refiner_fit_codebooks_hier(self._h, int(M), b, e, it, c, i, nn))
 
+    def fit_codebooks_bin(self, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25):
+        """fit_codebooks_bin() over the RAW rows held, float or byte, read where they are
+        (vaqhip_refiner_fit_codebooks_bin): subspaces above 8 bits as a tree of 2-centre fits.  Single device only."""
+        return _fit_codebooks_call(self.D, M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn:
+                                   L.vaqhip_refiner_fit_codebooks_bin(self._h, int(M), b, e, it, c, i, nn))
+
     def train(self, M: int, bit_budget: int, min_bits: int, max_bits: int, percent_var: float = 1.0, max_iter: int = 25):
         """train_rotation() then fit_codebooks() over the rows held: (eigvec, bits, centroids), as vaq_amd.train."""
         eig, _, bits, hi = self.train_rotation(M, bit_budget, min_bits, max_bits, percent_var)
