@@ -41,6 +41,97 @@ __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
+// ---------------------------------------------------------------------------
+// Wave-wide primitives in registers: cross-lane moves are DPP modifiers and the gfx950 row /
+// half swaps -- no LDS instruction (__shfl_* is ds_bpermute_b32) and no loop over the lanes.
+// Every lane of the wave must be active.
+// ---------------------------------------------------------------------------
+// DPP controls (the encodings of the ISA's dpp_ctrl field)
+constexpr int DPP_QUAD_XOR1 = 0xB1;     // quad_perm:[1,0,3,2]
+constexpr int DPP_QUAD_XOR2 = 0x4E;     // quad_perm:[2,3,0,1]
+constexpr int DPP_QUAD_MIRROR = 0x1B;   // quad_perm:[3,2,1,0]
+constexpr int DPP_ROW_SHL = 0x100;      // + n: lane i reads lane i + n of its row of 16
+constexpr int DPP_ROW_SHR = 0x110;      // + n: lane i reads lane i - n
+constexpr int DPP_ROW_ROR = 0x120;      // + n: rotation within the row
+constexpr int DPP_ROW_MIRROR = 0x140;   // lane i reads lane 15 - i of its row
+constexpr int DPP_ROW_HALF_MIRROR = 0x141;  // lane i reads lane 7 - i of its half row
+constexpr int DPP_ROW_BCAST15 = 0x142;  // lane 15 of a row to the next row
+constexpr int DPP_ROW_BCAST31 = 0x143;  // lane 31 to rows 2 and 3
+
+template <int CTRL> __device__ __forceinline__ unsigned wave_dpp_perm(const unsigned x) {
+  return (unsigned)__builtin_amdgcn_update_dpp((int)x, (int)x, CTRL, 0xf, 0xf, false);
+}
+// one compare-exchange of a sorting network: the lane keeps the smaller or the larger of its value and its
+// partner's (unsigned order)
+__device__ __forceinline__ unsigned wave_cx(const unsigned x, const unsigned p, const bool keep_min) {
+  const unsigned lo = x < p ? x : p, hi = x < p ? p : x;
+  return keep_min ? lo : hi;
+}
+// lane ^ 16 / lane ^ 32 as partner: after the swap one result holds the lower row's (half's) value and the
+// other the upper one's in BOTH of them, so their min and max are the exchange itself
+__device__ __forceinline__ unsigned wave_cx_row_swap(const unsigned x, const bool keep_min) {
+  const auto r = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+  return wave_cx(r[0], r[1], keep_min);
+}
+__device__ __forceinline__ unsigned wave_cx_half_swap(const unsigned x, const bool keep_min) {
+  const auto r = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+  return wave_cx(r[0], r[1], keep_min);
+}
+
+// The wave's 64 values x (one per lane) in ascending UNSIGNED order: lane r of the result holds the
+// (r + 1)-th smallest.  For floats that are >= +0 (or +inf) bit order is value order.  A bitonic network
+// of 21 compare-exchange stages.  Within a row of 16 a merge is the "mirror" form (first partner
+// 2^m - 1 - i, then lane ^ 2^j: every sub-block sorted the same way, no direction per block); the
+// merges of 32 and of 64 use lane ^ 16 and lane ^ 32 first, so the rows of a pair (then the halves) are
+// sorted in opposite directions beforehand: a lane-constant flip of which side keeps the minimum.
+__device__ __forceinline__ unsigned wave_sort64(unsigned x, const int lane) {
+  // bit b of `a` clear: the lane keeps the minimum in a stage that pairs lanes differing in bit b.
+  // Rows 1 and 3 sort descending up to the merge of 16, the upper half up to the merge of 32.
+  const unsigned a16 = (lane & 16) ? ~(unsigned)lane : (unsigned)lane;
+  const unsigned a32 = (lane & 32) ? ~(unsigned)lane : (unsigned)lane;
+  const unsigned a64 = (unsigned)lane;
+#define VAQ_WAVE_LOW_STAGES(a, from)                                                                       \
+  if (from >= 3) {                                                                                         \
+    x = wave_cx(x, wave_dpp_perm<DPP_ROW_ROR + 8>(x), ((a) & 8u) == 0u);                                   \
+  }                                                                                                        \
+  if (from >= 2) {                                                                                         \
+    unsigned p = (unsigned)__builtin_amdgcn_update_dpp((int)x, (int)x, DPP_ROW_SHL + 4, 0xf, 0x5, false);  \
+    p = (unsigned)__builtin_amdgcn_update_dpp((int)p, (int)x, DPP_ROW_SHR + 4, 0xf, 0xa, false);           \
+    x = wave_cx(x, p, ((a) & 4u) == 0u);                                                                   \
+  }                                                                                                        \
+  if (from >= 1) x = wave_cx(x, wave_dpp_perm<DPP_QUAD_XOR2>(x), ((a) & 2u) == 0u);                        \
+  x = wave_cx(x, wave_dpp_perm<DPP_QUAD_XOR1>(x), ((a) & 1u) == 0u);
+  // merges of 2, 4, 8, 16
+  VAQ_WAVE_LOW_STAGES(a16, 0)
+  x = wave_cx(x, wave_dpp_perm<DPP_QUAD_MIRROR>(x), (a16 & 2u) == 0u);
+  VAQ_WAVE_LOW_STAGES(a16, 0)
+  x = wave_cx(x, wave_dpp_perm<DPP_ROW_HALF_MIRROR>(x), (a16 & 4u) == 0u);
+  VAQ_WAVE_LOW_STAGES(a16, 1)
+  x = wave_cx(x, wave_dpp_perm<DPP_ROW_MIRROR>(x), (a16 & 8u) == 0u);
+  VAQ_WAVE_LOW_STAGES(a16, 2)
+  // merge of 32: rows 0 | 1 (2 | 3) are ascending | descending
+  x = wave_cx_row_swap(x, (a32 & 16u) == 0u);
+  VAQ_WAVE_LOW_STAGES(a32, 3)
+  // merge of 64: the halves are ascending | descending
+  x = wave_cx_half_swap(x, (a64 & 32u) == 0u);
+  x = wave_cx_row_swap(x, (a64 & 16u) == 0u);
+  VAQ_WAVE_LOW_STAGES(a64, 3)
+#undef VAQ_WAVE_LOW_STAGES
+  return x;
+}
+
+// inclusive prefix sum over the wave's lanes: the six DPP steps of the standard wave scan (four shifts
+// within a row, lane 15 to the next row, lane 31 to the upper half)
+__device__ __forceinline__ int wave_prefix_incl(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_SHR + 1, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_SHR + 2, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_SHR + 4, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_SHR + 8, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_BCAST15, 0xa, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, DPP_ROW_BCAST31, 0xc, 0xf, false);
+  return v;
+}
+
 // strict total order on (distance, id): the contract for ties
 __device__ __forceinline__ bool pair_less(float da, int ia, float db, int ib) {
   return (da < db) || (da == db && ia < ib);

@@ -757,12 +757,7 @@ __device__ __forceinline__ void scan_bf_body(const ScanParams &p) {
             atomicAdd(&hist[b < BF_HIST_BINS - 1 ? b : BF_HIST_BINS - 1], 1u);
           }
           wave_lds_sync();
-          int inc = (int)hist[lane];
-#pragma unroll
-          for (int o = 1; o < 64; o <<= 1) {
-            const int x = __shfl_up(inc, o);
-            if (lane >= o) inc += x;
-          }
+          const int inc = wave_prefix_incl((int)hist[lane]);  // (DPP: no LDS round trips while the lock is held)
           const unsigned long long reach = __ballot(inc >= k);
           if (reach != 0ull) {
             const int jb = __builtin_ctzll(reach);
@@ -868,19 +863,18 @@ __device__ __forceinline__ void scan_bf_body(const ScanParams &p) {
           if (row >= pos && row < be && acc < best) best = acc;
         }
       }
-      int rank = 0;  // position of the lane's value among the wave's 64 (ties by lane)
-      for (int o = 0; o < 64; o++) {
-        const float dj = bits_to_float((unsigned)__builtin_amdgcn_readlane((int)float_to_bits(best), o));
-        rank += (dj < best || (dj == best && o < lane)) ? 1 : 0;
-      }
+      // the wave's 64 lane minima in ascending order, in registers (wave_sort64: 21 compare-exchange stages,
+      // no LDS, no loop over the lanes); only the VALUE of the qw-th smallest is used, so which of several
+      // equal lanes held it does not matter.  Lanes that saw no row hold +inf and sort last.
+      // (distances are >= 0: bit order == value order)
+      const unsigned sorted = wave_sort64(float_to_bits(best), lane);
       const int have = __popcll(__ballot(best < INFINITY));
       const int qw = q < have ? q : have;
       if (qw > 0) {
-        const unsigned long long at = __ballot(rank == qw - 1);
-        const float tw = bits_to_float((unsigned)__builtin_amdgcn_readlane((int)float_to_bits(best), __builtin_ctzll(at)));
+        const unsigned tw = (unsigned)__builtin_amdgcn_readlane((int)sorted, qw - 1);
         if (lane == 0) {
           atomicAdd(boot_cnt, (unsigned)qw);
-          atomicMax(boot_thr, float_to_bits(tw));  // distances are >= 0: bit order == value order
+          atomicMax(boot_thr, tw);
         }
       }
     }
@@ -1020,12 +1014,38 @@ __device__ __forceinline__ void scan_bf_body(const ScanParams &p) {
       __syncthreads();
       n = (int)*sh_cnt;  // >= 1: keys are unique, so the smallest eligible key alone always fits
     }
-    // rank sort (n <= BF_ROUND_BUCKETS): position = number of smaller keys
+    // rank sort (n <= BF_ROUND_BUCKETS): position = number of smaller keys.  The other keys are broadcast
+    // reads of LDS, four to a 16-byte read and eight to a trip of the loop; the one to seven keys past the
+    // last whole eight come from one more pair of reads and count only where they exist (kuns[n ..] is whatever
+    // the buffers held, still inside kuns[0, BF_ROUND_BUCKETS)).
+    const uint4 *kuns4 = reinterpret_cast<const uint4 *>(kuns);
+    const int n8 = n >> 3, ntail = n & 7;
     for (int i = tid; i < n; i += nthreads) {
       const unsigned key = kuns[i];
       const int units = units_of(key);  // (two reads of bucket_start: in flight while the rank is counted)
       int rank = 0;
-      for (int j = 0; j < n; j++) rank += kuns[j] < key ? 1 : 0;
+#pragma unroll 1
+      for (int j = 0; j < n8; j++) {
+        const uint4 ka = kuns4[2 * j], kb = kuns4[2 * j + 1];
+        rank += ka.x < key ? 1 : 0;
+        rank += ka.y < key ? 1 : 0;
+        rank += ka.z < key ? 1 : 0;
+        rank += ka.w < key ? 1 : 0;
+        rank += kb.x < key ? 1 : 0;
+        rank += kb.y < key ? 1 : 0;
+        rank += kb.z < key ? 1 : 0;
+        rank += kb.w < key ? 1 : 0;
+      }
+      if (ntail != 0) {
+        const uint4 ka = kuns4[2 * n8], kb = kuns4[2 * n8 + 1];
+        rank += ka.x < key ? 1 : 0;
+        rank += (ntail > 1 && ka.y < key) ? 1 : 0;
+        rank += (ntail > 2 && ka.z < key) ? 1 : 0;
+        rank += (ntail > 3 && ka.w < key) ? 1 : 0;
+        rank += (ntail > 4 && kb.x < key) ? 1 : 0;
+        rank += (ntail > 5 && kb.y < key) ? 1 : 0;
+        rank += (ntail > 6 && kb.z < key) ? 1 : 0;
+      }
       keys[rank] = key;
       cum[rank + 1] = units;
     }
@@ -1036,12 +1056,7 @@ __device__ __forceinline__ void scan_bf_body(const ScanParams &p) {
       for (int base = 0; base < n; base += 64) {
         const int i = base + lane;
         const int u = i < n ? cum[i + 1] : 0;
-        int inc = u;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-          const int x = __shfl_up(inc, o);
-          if (lane >= o) inc += x;
-        }
+        const int inc = wave_prefix_incl(u);
         if (i < n) cum[i + 1] = carry + inc;
         carry += __builtin_amdgcn_readlane(inc, 63);
       }
@@ -1275,12 +1290,7 @@ __device__ __forceinline__ void scan_bf_body(const ScanParams &p) {
     // others wait, that made the final cut 8 % of a C2 workgroup's life.
     const float hscale = bits_to_float(sel.hdr[BF_HDR_SCALE]);
     if (n0 > k && hscale != 0.0f) {
-      int inc = (int)hist[lane];
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const int x = __shfl_up(inc, o);
-        if (lane >= o) inc += x;
-      }
+      const int inc = wave_prefix_incl((int)hist[lane]);
       const unsigned long long reach = __ballot(inc >= k);
       const int jb = reach != 0ull ? __builtin_ctzll(reach) : BF_HIST_BINS - 1;
       if (jb < BF_HIST_BINS - 1) {  // (the last bin also holds everything beyond H: nothing to drop)
