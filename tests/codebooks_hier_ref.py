@@ -30,6 +30,7 @@ CASES = {
     "l12": (4001, 12, 1, (10,), "planted", 0),
     "two": (6000, 16, 4, (10, 9, 8, 5), "rotated", 33),
     "resampled": (70000, 2, 1, (9,), "float", 2),
+    "resampled2": (70000, 2, 2, (9, 9), "float", 0),  # two subspaces whose stage 1 samples for itself, in one call
     "budget": (20000, 4, 2, (9, 11), "paired", 2),
 }
 BLOBS = 128     # blobs of a hierarchical subspace, far apart; the noise is uniform (no stray row to hold a centre alone)

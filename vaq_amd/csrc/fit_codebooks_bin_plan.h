@@ -8,18 +8,18 @@
 #ifndef VAQ_FIT_CODEBOOKS_BIN_PLAN_H_
 #define VAQ_FIT_CODEBOOKS_BIN_PLAN_H_
 
-#include "fit_codebooks_hier_plan.h"
+#include "fit_codebooks_plan.h"
 
 namespace vaq {
 namespace cbbin {
 
 constexpr int MAX_BATCH_FITS = 65535;  // fits one run of the Lloyd phases takes (a grid dimension)
 
-inline bool binary(int bits) { return cbhier::hierarchical(bits); }  // the same subspaces: more than 8 bits
+// (which subspaces: cbfit::wide, the hierarchical form's)
 // centres node (depth d of maxdepth, any index) stands for: 1 << (maxdepth - d + 1) (VAQ.cpp:1318)
 inline int temp_k(int maxdepth, int d) { return 1 << (maxdepth - d + 1); }
 
-// One binary subspace.  R_s = rows randomPermutation(n)[0 .. rows) of the projected matrix (cbhier::rows_for).
+// One binary subspace.  R_s = rows randomPermutation(n)[0 .. rows) of the projected matrix (cbfit::rows_for).
 struct BSub {
   int s;         // the subspace
   int bits;      // = maxdepth
@@ -28,45 +28,20 @@ struct BSub {
   int cent_off;  // its block of the output, in centres
 };
 
-struct Plan {
-  cbfit::Plan flat;        // make_plan over ALL subspaces: cent_off of every subspace, rows / full of the flat ones
+struct Plan : cbfit::WideHead {  // (n_pairs: rows of a level's compact matrix at most)
   std::vector<BSub> bsub;  // the binary subspaces, ascending
-  int64_t rows_max = 0;    // the largest R_s
-  int64_t gathered = 0;    // rows of the ONE gathered head of randomPermutation(n): every reader takes a prefix
-  int64_t n_pairs = 0;     // sum of rows over the binary subspaces: rows of a level's compact matrix at most
-  int n_full = 0;          // flat subspaces that read all n rows in their own order
-  int n_cent = 0;          // sum of k_s
   int max_bits = 0;        // the deepest tree
 };
 
-// bits[s] in 1..15, n in 1..2^31-1, D % M == 0; rows_s >= k_s has been checked (cbhier::first_short_subspace)
+// bits[s] in 1..15, n in 1..2^31-1, D % M == 0; rows_s >= k_s has been checked (cbfit::first_short_subspace)
 inline Plan make_plan(int64_t n, int M, const int *bits) {
   Plan p;
-  p.flat = cbfit::make_plan(n, M, bits);
-  p.n_cent = p.flat.n_cent;
-  int B = 0;
-  for (int s = 0; s < M; s++) B += bits[s];
+  static_cast<cbfit::WideHead &>(p) = cbfit::wide_head(n, M, bits);
   for (int s = 0; s < M; s++) {
-    const cbfit::Sub &d = p.flat.sub[(size_t)s];
-    if (!binary(bits[s])) {
-      if (d.full)
-        p.n_full++;
-      else
-        p.gathered = std::max<int64_t>(p.gathered, d.rows);
-      continue;
-    }
-    BSub b;
-    b.s = s;
-    b.bits = bits[s];
-    b.k = 1 << bits[s];
-    b.rows = (int)cbhier::rows_for(n, bits[s], B, M);
-    b.cent_off = d.cent_off;
-    p.n_pairs += b.rows;
-    p.rows_max = std::max<int64_t>(p.rows_max, b.rows);
-    p.max_bits = std::max(p.max_bits, b.bits);
-    p.bsub.push_back(b);
+    if (!cbfit::wide(bits[s])) continue;
+    p.bsub.push_back(BSub{s, bits[s], 1 << bits[s], p.rows[(size_t)s], p.flat.sub[(size_t)s].cent_off});
+    p.max_bits = std::max(p.max_bits, bits[s]);
   }
-  p.gathered = std::max(p.gathered, p.rows_max);
   return p;
 }
 
@@ -120,7 +95,7 @@ inline void add_fit(Fits &f, int owner, int k, int rows, int cent_off, int src, 
   }
   cbfit::Batch &b = f.chunk.back();
   cbfit::batch_add(b, k, rows, cent_off, src, stride, col, row0);
-  for (int r = 0; r < rows; r += tile_rows) b.tile.push_back(cbfit::Tile{(int)b.fit.size() - 1, r});  // none across a fit
+  cbfit::batch_add_tiles(b, (int)b.fit.size() - 1, rows, tile_rows);
   f.owner.back().push_back(owner);
 }
 
@@ -165,11 +140,10 @@ inline cbfit::Batch make_split(const Plan &p, const std::vector<Node> &level, co
     const Node &nd = level[(size_t)which[i]];
     cbfit::batch_add(b, 2, nd.rows, node_cent_off(p.bsub[(size_t)nd.b], nd), nd.src, nd.stride, nd.col, nd.row0);
     b.fit.back().run_off = 2 * (int)i;
-    for (int r = 0; r < nd.rows; r += tile_rows) b.tile.push_back(cbfit::Tile{(int)i, r});
+    cbfit::batch_add_tiles(b, (int)i, nd.rows, tile_rows);
   }
   b.n_runs = 2 * (int)which.size();
-  b.key_bits = 1;
-  while (((uint64_t)1 << b.key_bits) < (uint64_t)b.n_runs) b.key_bits++;
+  b.key_bits = cbfit::key_bits_for(b.n_runs);
   return b;
 }
 

@@ -14,13 +14,7 @@ namespace cbhier {
 
 constexpr int K1 = 128;           // centres of stage 1 (VAQ.cpp:548)
 constexpr int K1_BITS = 7;
-constexpr int FLAT_MAX_BITS = 8;  // a subspace with more bits is hierarchical (VAQ.cpp:546)
-
-inline bool hierarchical(int bits) { return bits > FLAT_MAX_BITS; }
-// VAQ.cpp:535-536: min(n, max(256 * k_s, 256 << (B / M))), B the bit budget, integer division
-inline int64_t rows_for(int64_t n, int bits_s, int B, int M) {
-  return std::min<int64_t>(n, std::max<int64_t>(cbfit::ROWS_PER_CENTRE << bits_s, (int64_t)256 << (B / M)));
-}
+// (which subspaces: cbfit::wide; the rows R_s of one: cbfit::rows_for)
 // the most rows a stage-2 fit takes without sampling (KMeans.hpp:489 with k = K2); larger groups are not built
 inline int64_t group_limit(int K2) { return std::max<int64_t>(cbfit::ROWS_PER_CENTRE * K2, cbfit::MIN_SAMPLE); }
 
@@ -37,81 +31,47 @@ struct HSub {
   int64_t pair_off;    // first of its membership pairs = first row of its compact regrouped matrix
 };
 
-struct Plan {
-  cbfit::Plan flat;        // make_plan over ALL subspaces: cent_off of every subspace, rows / full of the flat ones
-  std::vector<HSub> hsub;  // the hierarchical subspaces, ascending
-  int64_t rows_max = 0;    // the largest R_s
-  int64_t gathered = 0;    // rows of the ONE gathered head of randomPermutation(n): the largest R_s or sampling flat
-                           // subspace's prefix; every such reader takes a prefix of it
-  int64_t n_pairs = 0;     // sum of rows over the hierarchical subspaces
+struct Plan : cbfit::WideHead {
+  std::vector<HSub> hsub;     // the hierarchical subspaces, ascending
   int64_t resample_rows = 0;  // rows of the compact stage-1 matrices
-  int n_full = 0;          // flat subspaces that read all n rows in their own order
-  int n_cent = 0;          // final centres: sum of k_s
-  cbfit::Batch stage1;     // flat subspaces, then the 128-centre fits, in subspace order (fit index = subspace)
-  cbfit::Batch member;     // fit h: 128 centres over all rows of R_s, keys h * 128 + group
+  cbfit::Batch stage1;        // flat subspaces, then the 128-centre fits, in subspace order (fit index = subspace)
+  cbfit::Batch member;        // fit h: 128 centres over all rows of R_s, keys h * 128 + group
 };
 
-// -1 when the shape can be planned, else the first hierarchical subspace with rows_s < k_s (refused: seeds out of bounds)
-inline int first_short_subspace(int64_t n, int M, const int *bits) {
-  int B = 0;
-  for (int s = 0; s < M; s++) B += bits[s];
-  for (int s = 0; s < M; s++)
-    if (hierarchical(bits[s]) && rows_for(n, bits[s], B, M) < ((int64_t)1 << bits[s])) return s;
-  return -1;
-}
-
-// bits[s] in 1..15, n in 1..2^31-1, D % M == 0
+// bits[s] in 1..15, n in 1..2^31-1, D % M == 0; rows_s >= k_s has been checked (cbfit::first_short_subspace)
 inline Plan make_plan(int64_t n, int D, int M, const int *bits) {
   Plan p;
+  static_cast<cbfit::WideHead &>(p) = cbfit::wide_head(n, M, bits);
   const int L = D / M;
-  p.flat = cbfit::make_plan(n, M, bits);
-  p.n_cent = p.flat.n_cent;
-  int B = 0;
-  for (int s = 0; s < M; s++) B += bits[s];
   for (int s = 0; s < M; s++) {
-    if (!hierarchical(bits[s])) {
-      const cbfit::Sub &d = p.flat.sub[(size_t)s];
-      if (d.full)
-        p.n_full++;
-      else
-        p.gathered = std::max<int64_t>(p.gathered, d.rows);
+    const cbfit::Sub &d = p.flat.sub[(size_t)s];
+    if (!cbfit::wide(bits[s])) {
+      cbfit::batch_add(p.stage1, d.k, d.rows, d.cent_off, d.full ? cbfit::SRC_FULL : cbfit::SRC_SAMPLE, D, s * L, 0);
       continue;
     }
     HSub h;
     h.s = s;
     h.k = 1 << bits[s];
     h.K2 = h.k / K1;
-    h.rows = (int)rows_for(n, bits[s], B, M);
+    h.rows = p.rows[(size_t)s];
     h.stage1_rows = (int)cbfit::sample_rows(h.rows, K1);
     h.resampled = h.stage1_rows < h.rows;
     h.c1_off = p.n_cent + (int)p.hsub.size() * K1;
     h.resample_off = p.resample_rows;
-    h.pair_off = p.n_pairs;
-    if (h.resampled) p.resample_rows += h.stage1_rows;
-    p.n_pairs += h.rows;
-    p.rows_max = std::max<int64_t>(p.rows_max, h.rows);
-    p.hsub.push_back(h);
-  }
-  p.gathered = std::max(p.gathered, p.rows_max);
-  size_t hi = 0;
-  for (int s = 0; s < M; s++) {
-    const cbfit::Sub &d = p.flat.sub[(size_t)s];
-    if (!hierarchical(bits[s])) {
-      cbfit::batch_add(p.stage1, d.k, d.rows, d.cent_off, d.full ? cbfit::SRC_FULL : cbfit::SRC_SAMPLE, D, s * L, 0);
-      continue;
-    }
-    const HSub &h = p.hsub[hi++];
-    if (h.resampled)
+    h.pair_off = p.member.n_pairs;
+    if (h.resampled) {
+      p.resample_rows += h.stage1_rows;
       cbfit::batch_add(p.stage1, K1, h.stage1_rows, h.c1_off, cbfit::SRC_EXTRA, L, 0, h.resample_off);
-    else
+    } else {
       cbfit::batch_add(p.stage1, K1, h.stage1_rows, h.c1_off, cbfit::SRC_SAMPLE, D, s * L, 0);
+    }
     cbfit::batch_add(p.member, K1, h.rows, h.c1_off, cbfit::SRC_SAMPLE, D, s * L, 0);
     // (the membership keys carry no half: group g of subspace h is key h * 128 + g)
-    p.member.fit.back().run_off = (int)(hi - 1) * K1;
+    p.member.fit.back().run_off = (int)p.hsub.size() * K1;
+    p.hsub.push_back(h);
   }
   p.member.n_runs = (int)p.hsub.size() * K1;
-  p.member.key_bits = 1;
-  while (((uint64_t)1 << p.member.key_bits) < (uint64_t)p.member.n_runs) p.member.key_bits++;
+  p.member.key_bits = cbfit::key_bits_for(p.member.n_runs);
   return p;
 }
 
@@ -157,7 +117,7 @@ inline cbfit::Batch make_stage2(const Plan &p, const int *counts, int L, int til
     for (int g = 0; g < K1; g++) {
       const int m = counts[h * K1 + g];
       cbfit::batch_add(b, hs.K2, m, p.flat.sub[(size_t)hs.s].cent_off + g * hs.K2, cbfit::SRC_SAMPLE, L, 0, row0);
-      for (int r = 0; r < m; r += tile_rows) b.tile.push_back(cbfit::Tile{(int)b.fit.size() - 1, r});
+      cbfit::batch_add_tiles(b, (int)b.fit.size() - 1, m, tile_rows);
       row0 += m;
     }
   }

@@ -2,7 +2,8 @@
 // how many rows KMeans::staticFitSampling (KMeans.hpp:487-503) works on per subspace and which -- every call of the
 // reference decides for itself: all n rows in their own order when n <= max(256 k_s, 65536), else the head of
 // randomPermutation(n) --, where each subspace's (key, row) pairs, runs and centres lie in the batched buffers, how
-// wide the sort key is, and where the reference's two OpenMP threads cut the rows.
+// wide the sort key is, where the reference's two OpenMP threads cut the rows, and the head that the plans of the two
+// forms for subspaces above 8 bits share.
 // No HIP in here: tests/cpp/fit_codebooks_plan_test.cpp runs it on the CPU.
 #ifndef VAQ_FIT_CODEBOOKS_PLAN_H_
 #define VAQ_FIT_CODEBOOKS_PLAN_H_
@@ -22,6 +23,12 @@ constexpr int64_t MIN_SAMPLE = 256 * 256;
 inline int64_t sample_rows(int64_t n, int k) { return std::min<int64_t>(n, std::max<int64_t>(ROWS_PER_CENTRE * k, MIN_SAMPLE)); }
 // rows [0, half_rows) are the first OpenMP thread's (schedule(static), two threads), the rest the second's
 inline int half_rows(int rows) { return (int)(((int64_t)rows + 1) / 2); }
+// radix-sort key width: the smallest with 1 << key_bits >= n_runs, at least 1
+inline unsigned key_bits_for(int n_runs) {
+  unsigned b = 1;
+  while (b < 32 && ((uint64_t)1 << b) < (uint64_t)n_runs) b++;
+  return b;
+}
 
 // One subspace of the batch (the kernels read it as it is).  Centre c of half h owns run run_off + h * k + c; row r
 // of the subspace's rows emits pair pair_off + r.
@@ -45,7 +52,7 @@ struct Plan {
   int n_cent = 0;        // sum of k
   int n_full = 0;        // subspaces that read all n rows
   int k_max = 0;
-  unsigned key_bits = 1;  // radix-sort key width: the smallest with 1 << key_bits >= n_runs
+  unsigned key_bits = 1;  // key_bits_for(n_runs)
   bool sampled = false;   // n > sample: every subspace samples (n_full == 0, gathered == sample)
   bool gather = false;    // gathered > 0 and the fit is handed all n rows: it gathers the sample itself.  A caller that
                           // hands over just the sample's rows, in the sample's order, clears it (only when n_full == 0)
@@ -74,7 +81,7 @@ inline Plan make_plan(int64_t n, int M, const int *bits) {
     else
       p.gathered = std::max<int64_t>(p.gathered, d.rows);
   }
-  while (p.key_bits < 32 && ((uint64_t)1 << p.key_bits) < (uint64_t)p.n_runs) p.key_bits++;
+  p.key_bits = key_bits_for(p.n_runs);
   p.sampled = n > p.sample;
   p.gather = p.gathered > 0;
   return p;
@@ -113,7 +120,7 @@ struct Batch {
   int n_runs = 0;          // sum of 2 * k
   int n_cent = 0;          // centres the centre table spans: the largest cent_off + k
   int k_max = 0;
-  unsigned key_bits = 1;   // the smallest with 1 << key_bits >= n_runs
+  unsigned key_bits = 1;   // key_bits_for(n_runs)
 };
 
 // bytes of LDS the assign kernel's tile of slices may take; wider slices are read from global memory
@@ -143,7 +150,11 @@ inline void batch_add(Batch &b, int k, int rows, int cent_off, int src, int stri
   b.n_cent = std::max(b.n_cent, cent_off + k);
   b.k_max = std::max(b.k_max, k);
   b.rows_max = std::max<int64_t>(b.rows_max, rows);
-  while (b.key_bits < 32 && ((uint64_t)1 << b.key_bits) < (uint64_t)b.n_runs) b.key_bits++;
+  b.key_bits = key_bits_for(b.n_runs);
+}
+// the tile table's entries of fit `fit`: its rows in pieces of tile_rows, none across a fit
+inline void batch_add_tiles(Batch &b, int fit, int rows, int tile_rows) {
+  for (int r = 0; r < rows; r += tile_rows) b.tile.push_back(Tile{fit, r});
 }
 
 // the flat fit's batch: subspace s reads columns [s * L, (s + 1) * L) of the full matrix or of the sample, D wide
@@ -156,6 +167,69 @@ inline Batch make_batch(const Plan &p, int D, int L) {
   return b;
 }
 
+// ---- what the two forms for wide subspaces share (fit_codebooks_hier_plan.h, fit_codebooks_bin_plan.h) ----
+constexpr int FLAT_MAX_BITS = 8;  // a subspace with more bits is wide: hierarchical or binary (VAQ.cpp:546)
+inline bool wide(int bits) { return bits > FLAT_MAX_BITS; }
+// rows R_s of a wide subspace, VAQ.cpp:535-536: min(n, max(256 * k_s, 256 << (B / M))), B the bit budget, integer division
+inline int64_t rows_for(int64_t n, int bits_s, int B, int M) {
+  return std::min<int64_t>(n, std::max<int64_t>(ROWS_PER_CENTRE << bits_s, (int64_t)256 << (B / M)));
+}
+inline int bit_budget(int M, const int *bits) {
+  int B = 0;
+  for (int s = 0; s < M; s++) B += bits[s];
+  return B;
+}
+// -1 when the shape can be planned, else the first wide subspace with rows_s < k_s (refused: seeds out of bounds)
+inline int first_short_subspace(int64_t n, int M, const int *bits) {
+  const int B = bit_budget(M, bits);
+  for (int s = 0; s < M; s++)
+    if (wide(bits[s]) && rows_for(n, bits[s], B, M) < ((int64_t)1 << bits[s])) return s;
+  return -1;
+}
+
+// The head of a wide form's plan.  R_s = rows randomPermutation(n)[0 .. rows[s]) of the projected matrix.
+// (hidden, as the host's own types are: the library exports nothing for it)
+struct __attribute__((visibility("hidden"))) WideHead {
+  Plan flat;              // make_plan over ALL subspaces: cent_off of every subspace, rows / full of the flat ones
+  std::vector<int> rows;  // rows of R_s per subspace; 0 for a flat one
+  int64_t rows_max = 0;   // the largest R_s
+  int64_t gathered = 0;   // rows of the ONE gathered head of randomPermutation(n): the largest R_s or sampling flat
+                          // subspace's prefix; every such reader takes a prefix of it
+  int64_t n_pairs = 0;    // sum of rows over the wide subspaces
+  int n_full = 0;         // flat subspaces that read all n rows in their own order
+  int n_cent = 0;         // final centres: sum of k_s
+};
+
+// bits[s] in 1..15, n in 1..2^31-1
+__attribute__((visibility("hidden"))) inline WideHead wide_head(int64_t n, int M, const int *bits) {
+  WideHead p;
+  p.flat = make_plan(n, M, bits);
+  p.n_cent = p.flat.n_cent;
+  p.rows.assign((size_t)M, 0);
+  const int B = bit_budget(M, bits);
+  for (int s = 0; s < M; s++) {
+    const Sub &d = p.flat.sub[(size_t)s];
+    if (wide(bits[s])) {
+      p.rows[(size_t)s] = (int)rows_for(n, bits[s], B, M);
+      p.n_pairs += p.rows[(size_t)s];
+      p.rows_max = std::max<int64_t>(p.rows_max, p.rows[(size_t)s]);
+    } else if (d.full) {
+      p.n_full++;
+    } else {
+      p.gathered = std::max<int64_t>(p.gathered, d.rows);
+    }
+  }
+  p.gathered = std::max(p.gathered, p.rows_max);
+  return p;
+}
+
 }  // namespace cbfit
+
+// the names these had while the hierarchical form alone owned them (the plan tests of both wide forms spell them so)
+namespace cbhier {
+using cbfit::first_short_subspace;
+using cbfit::rows_for;
+inline bool hierarchical(int bits) { return cbfit::wide(bits); }
+}  // namespace cbhier
 }  // namespace vaq
 #endif

@@ -471,20 +471,110 @@ hipError_t cb_launch_assign(const CbSources &src, int L, const cbfit::Batch &b, 
   return hipGetLastError();
 }
 
+// One fit that samples for itself (KMeans.hpp:489-503 over the rows it is handed): rows
+// randomPermutation(node_rows)[0 .. rows) of the matrix at src (rows `stride` floats apart, the slice from column `col`
+// on) become rows [off, off + rows) of a compact [.][L] matrix.
+struct CbResample {
+  const float *src;
+  int stride, col, node_rows, rows;
+  int64_t off;
+};
+
+// The buffers the passes of ONE call share.  The call's entry point (codebooks_lloyd, codebooks_fit_hier,
+// codebooks_fit_bin; codebooks_fit through codebooks_lloyd) owns it and hands it to every pass: a run of the Lloyd
+// phases (cb_lloyd_batch), the hierarchical fit's membership pass, the binary fit's split pass.  The buffers only grow,
+// so a level of the binary fit allocates what no pass before it needed and nothing else.
+// The one rule: DevBuf::ensure drops the contents when it grows, and a pass ensures what it needs as it begins.  So
+// NOTHING a pass left in here -- tables, pairs sorted or not, bounds -- may be read once the next pass has begun.  Who
+// needs it longer launches the readers and synchronises first.  There are two such readers: the hierarchical fit's
+// cb_slice_kernel over vals_out (the bounds' copy to the host synchronises behind it, before stage 2), and the binary
+// fit's cb_regroup_kernel over keys_out, vals_out and the split's fit table (launched and synchronised before the cut
+// fits).  A source matrix a later pass reads (the resamples, the compact matrices) is not kept in here.
+struct CbWork {
+  hipStream_t st;
+  vaqhost::DevBuf b_keys_in, b_keys_out, b_vals_in, b_vals_out, b_bounds, b_temp, b_fit, b_tile, b_part, b_flags, b_seed, b_perm;
+  unsigned *keys_in = nullptr, *keys_out = nullptr, *vals_in = nullptr, *vals_out = nullptr;  // of the last pairs()
+  int *start = nullptr, *end = nullptr;  // run [start[k], end[k]) of key k, of the last sort_and_bound()
+  size_t temp_bytes = 0, sized_pairs = 0;  // rocprim's temporary storage for (sized_pairs, sized_bits)
+  unsigned sized_bits = 0;
+
+  struct Tables {
+    const cbfit::Fit *fits = nullptr;
+    const cbfit::Tile *tiles = nullptr;  // null: the batch has no tile table
+  };
+  // the batch's fit table and, where there is one, its tile table, on the stream (the batch is the host's until it is
+  // synchronised)
+  hipError_t upload(const cbfit::Batch &b, Tables *t) {
+    hipError_t e;
+    CB_TRY(b_fit.ensure(b.fit.size() * sizeof(cbfit::Fit)));
+    CB_TRY(hipMemcpyAsync(b_fit.p, b.fit.data(), b.fit.size() * sizeof(cbfit::Fit), hipMemcpyHostToDevice, st));
+    *t = Tables{b_fit.as<cbfit::Fit>(), nullptr};
+    if (b.tile.empty()) return hipSuccess;
+    CB_TRY(b_tile.ensure(b.tile.size() * sizeof(cbfit::Tile)));
+    CB_TRY(hipMemcpyAsync(b_tile.p, b.tile.data(), b.tile.size() * sizeof(cbfit::Tile), hipMemcpyHostToDevice, st));
+    t->tiles = b_tile.as<cbfit::Tile>();
+    return hipSuccess;
+  }
+  // room for n_pairs (key, row) pairs, unsorted (keys_in, vals_in) and sorted
+  hipError_t pairs(int n_pairs) {
+    hipError_t e;
+    for (vaqhost::DevBuf *b : {&b_keys_in, &b_keys_out, &b_vals_in, &b_vals_out}) CB_TRY(b->ensure((size_t)n_pairs * 4));
+    keys_in = b_keys_in.as<unsigned>(), keys_out = b_keys_out.as<unsigned>();
+    vals_in = b_vals_in.as<unsigned>(), vals_out = b_vals_out.as<unsigned>();
+    return hipSuccess;
+  }
+  // (keys_in, vals_in) sorted by the low key_bits of the key into (keys_out, vals_out) -- stable: pairs of equal key stay
+  // in the order they were emitted in -- and the run of every key below n_runs (a key that does not occur: empty)
+  hipError_t sort_and_bound(int n_pairs, unsigned key_bits, int n_runs) {
+    hipError_t e;
+    if ((size_t)n_pairs != sized_pairs || key_bits != sized_bits) {
+      CB_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n_pairs, 0u, key_bits, st));
+      CB_TRY(b_temp.ensure(temp_bytes ? temp_bytes : 16));
+      sized_pairs = (size_t)n_pairs, sized_bits = key_bits;
+    }
+    CB_TRY(b_bounds.ensure((size_t)2 * n_runs * sizeof(int)));
+    start = b_bounds.as<int>(), end = start + n_runs;
+    CB_TRY(hipMemsetAsync(start, 0, (size_t)2 * n_runs * sizeof(int), st));
+    CB_TRY(rocprim::radix_sort_pairs(b_temp.p, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n_pairs, 0u, key_bits, st));
+    hipLaunchKernelGGL(cb_bounds_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, keys_out, n_pairs, start, end);
+    return hipGetLastError();
+  }
+  // the compact matrix of the fits that sample for themselves: ONE upload of their permutation heads back to back, one
+  // cb_slice_kernel each, one synchronisation (the heads are the host's)
+  hipError_t gather_resamples(const std::vector<CbResample> &rs, int L, float *out) {
+    hipError_t e;
+    std::vector<int> perm;
+    std::vector<size_t> at;
+    for (const CbResample &r : rs) {
+      const std::vector<int> rows = permutation_head(r.node_rows, r.rows);
+      at.push_back(perm.size());
+      perm.insert(perm.end(), rows.begin(), rows.end());
+    }
+    CB_TRY(b_perm.ensure(perm.size() * sizeof(int)));
+    CB_TRY(hipMemcpyAsync(b_perm.p, perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    for (size_t i = 0; i < rs.size(); i++) {
+      const CbResample &r = rs[i];
+      hipLaunchKernelGGL(cb_slice_kernel, dim3((unsigned)(((int64_t)r.rows * L + 255) / 256)), dim3(256), 0, st, r.src, r.stride,
+                         r.col, b_perm.as<int>() + at[i], (int64_t)r.rows, L, out + (size_t)r.off * L);
+      CB_TRY(hipGetLastError());
+    }
+    return hipStreamSynchronize(st);
+  }
+};
+
 // The Lloyd loop over a batch of fits: seeds from permutation_head(rows, k) of every fit's own rows, then one launch per
 // phase and iteration for ALL fits until every fit's centres stopped changing or max_iter.  The sources are complete on
-// `st`; d_means spans b.n_cent centres.  iters_out[fits] (host).  began: when the caller started preparing the
+// w.st; d_means spans b.n_cent centres.  iters_out[fits] (host).  began: when the caller started preparing the
 // sources, for phases->gather_ms (null phases: no per-phase synchronisation).  Synchronises the stream.
 // staged_sums (the binary fit's batches): the sums by cb_sums_staged_kernel, the same bits.
-hipError_t cb_lloyd_batch(const CbSources &src, int L, const cbfit::Batch &b, int max_iter, float *d_means, int *iters_out,
-                          int *no_centre_out, CodebookPhases *phases, std::chrono::steady_clock::time_point began,
-                          hipStream_t st, bool staged_sums = false) {
+hipError_t cb_lloyd_batch(CbWork &w, const CbSources &src, int L, const cbfit::Batch &b, int max_iter, float *d_means,
+                          int *iters_out, int *no_centre_out, CodebookPhases *phases,
+                          std::chrono::steady_clock::time_point began, bool staged_sums = false) {
   const int F = (int)b.fit.size();
   if (F < 1 || b.rows_max < 1 || b.n_pairs > 0x7fffffff || F > 65535) return hipErrorInvalidValue;
   const int n_pairs = (int)b.n_pairs, n_runs = b.n_runs;
+  const hipStream_t st = w.st;
   hipError_t e;
-  vaqhost::DevBuf b_fit, b_tile, b_seed, b_keys_in, b_keys_out, b_vals_in, b_vals_out, b_bounds, b_part, b_flags, b_temp;
-  CbSync sync_on_return{st, true};
   auto t0 = began;
 
   // ---- the batch's tables and the seeds ----
@@ -493,37 +583,20 @@ hipError_t cb_lloyd_batch(const CbSources &src, int L, const cbfit::Batch &b, in
     const std::vector<int> head = permutation_head(fd.rows, fd.k);
     std::copy(head.begin(), head.end(), seeds.begin() + fd.cent_off);
   }
-  CB_TRY(b_fit.ensure((size_t)F * sizeof(cbfit::Fit)));
-  CB_TRY(b_seed.ensure(seeds.size() * sizeof(int)));
-  CB_TRY(b_keys_in.ensure((size_t)n_pairs * 4));
-  CB_TRY(b_keys_out.ensure((size_t)n_pairs * 4));
-  CB_TRY(b_vals_in.ensure((size_t)n_pairs * 4));
-  CB_TRY(b_vals_out.ensure((size_t)n_pairs * 4));
-  CB_TRY(b_bounds.ensure((size_t)2 * n_runs * sizeof(int)));
-  CB_TRY(b_part.ensure((size_t)n_runs * L * sizeof(float)));
-  CB_TRY(b_flags.ensure((size_t)3 * F * sizeof(int)));
-  const cbfit::Fit *fits = b_fit.as<cbfit::Fit>();
-  const cbfit::Tile *tiles = nullptr;
-  if (!b.tile.empty()) {
-    CB_TRY(b_tile.ensure(b.tile.size() * sizeof(cbfit::Tile)));
-    CB_TRY(hipMemcpyAsync(b_tile.p, b.tile.data(), b.tile.size() * sizeof(cbfit::Tile), hipMemcpyHostToDevice, st));
-    tiles = b_tile.as<cbfit::Tile>();
-  }
-  unsigned *keys_in = b_keys_in.as<unsigned>(), *keys_out = b_keys_out.as<unsigned>();
-  unsigned *vals_in = b_vals_in.as<unsigned>(), *vals_out = b_vals_out.as<unsigned>();
-  int *start = b_bounds.as<int>(), *end = start + n_runs;
-  int *flags = b_flags.as<int>();  // changed[2][F] (this iteration's and the one before), then no_centre[F]
-  size_t temp_bytes = 0;
-  CB_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n_pairs, 0u,
-                                   b.key_bits, st));
-  CB_TRY(b_temp.ensure(temp_bytes ? temp_bytes : 16));
+  CbWork::Tables t;
+  CB_TRY(w.upload(b, &t));
+  CB_TRY(w.pairs(n_pairs));
+  CB_TRY(w.b_seed.ensure(seeds.size() * sizeof(int)));
+  CB_TRY(w.b_part.ensure((size_t)n_runs * L * sizeof(float)));
+  CB_TRY(w.b_flags.ensure((size_t)3 * F * sizeof(int)));
+  int *flags = w.b_flags.as<int>();  // changed[2][F] (this iteration's and the one before), then no_centre[F]
+  float *part = w.b_part.as<float>();
   std::vector<int> host_flags((size_t)3 * F, 0);
   for (int f = 0; f < F; f++) host_flags[(size_t)f] = 1;  // every fit starts active
-  CB_TRY(hipMemcpyAsync(b_fit.p, b.fit.data(), (size_t)F * sizeof(cbfit::Fit), hipMemcpyHostToDevice, st));
-  CB_TRY(hipMemcpyAsync(b_seed.p, seeds.data(), seeds.size() * sizeof(int), hipMemcpyHostToDevice, st));
+  CB_TRY(hipMemcpyAsync(w.b_seed.p, seeds.data(), seeds.size() * sizeof(int), hipMemcpyHostToDevice, st));
   CB_TRY(hipMemcpyAsync(flags, host_flags.data(), host_flags.size() * sizeof(int), hipMemcpyHostToDevice, st));
   hipLaunchKernelGGL(cb_seed_kernel, dim3((unsigned)((b.k_max * L + 255) / 256), (unsigned)F), dim3(256), 0, st, src, L,
-                     fits, b_seed.as<int>(), d_means);
+                     t.fits, w.b_seed.as<int>(), d_means);
   CB_TRY(hipGetLastError());
   CB_TRY(hipStreamSynchronize(st));  // (the tables are the host's)
   if (phases) phases->gather_ms += cb_ms_since(t0);
@@ -544,25 +617,19 @@ hipError_t cb_lloyd_batch(const CbSources &src, int L, const cbfit::Batch &b, in
   for (int it = 0; it < max_iter && n_done < F && !no_centre; it++) {
     int *prev = flags + (size_t)(it & 1) * F, *now = flags + (size_t)((it + 1) & 1) * F;
     CB_TRY(hipMemsetAsync(now, 0, (size_t)F * sizeof(int), st));
-    CB_TRY(hipMemsetAsync(start, 0, (size_t)2 * n_runs * sizeof(int), st));
-    CB_TRY(cb_launch_assign<false>(src, L, b, fits, tiles, d_means, prev, keys_in, vals_in, flags + 2 * F, st));
+    CB_TRY(cb_launch_assign<false>(src, L, b, t.fits, t.tiles, d_means, prev, w.keys_in, w.vals_in, flags + 2 * F, st));
     CB_TRY(phase_end(phases ? &phases->assign_ms : nullptr));
     // stable: rows of equal (fit, half, centre) stay in ascending order
-    CB_TRY(rocprim::radix_sort_pairs(b_temp.p, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n_pairs, 0u,
-                                     b.key_bits, st));
-    hipLaunchKernelGGL(cb_bounds_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, keys_out, n_pairs,
-                       start, end);
-    CB_TRY(hipGetLastError());
+    CB_TRY(w.sort_and_bound(n_pairs, b.key_bits, n_runs));
     if (staged_sums)
-      hipLaunchKernelGGL(cb_sums_staged_kernel, dim3((unsigned)(2 * b.k_max), (unsigned)F), dim3(64), 0, st, src, L, fits, vals_out,
-                         start, end, b_part.as<float>());
+      hipLaunchKernelGGL(cb_sums_staged_kernel, dim3((unsigned)(2 * b.k_max), (unsigned)F), dim3(64), 0, st, src, L, t.fits,
+                         w.vals_out, w.start, w.end, part);
     else
-      hipLaunchKernelGGL(cb_accumulate_kernel, acc_grid, dim3(256), 0, st, src, L, fits, vals_out, start, end,
-                         b_part.as<float>());
+      hipLaunchKernelGGL(cb_accumulate_kernel, acc_grid, dim3(256), 0, st, src, L, t.fits, w.vals_out, w.start, w.end, part);
     CB_TRY(hipGetLastError());
     CB_TRY(phase_end(phases ? &phases->accumulate_ms : nullptr));
-    hipLaunchKernelGGL(cb_update_kernel, dim3((unsigned)b.k_max, (unsigned)F), dim3(64), 0, st, b_part.as<float>(), start,
-                       end, L, fits, d_means, now);
+    hipLaunchKernelGGL(cb_update_kernel, dim3((unsigned)b.k_max, (unsigned)F), dim3(64), 0, st, part, w.start, w.end, L, t.fits,
+                       d_means, now);
     CB_TRY(hipGetLastError());
     CB_TRY(hipMemcpyAsync(host_flags.data(), flags, host_flags.size() * sizeof(int), hipMemcpyDeviceToHost, st));
     CB_TRY(hipStreamSynchronize(st));
@@ -578,7 +645,6 @@ hipError_t cb_lloyd_batch(const CbSources &src, int L, const cbfit::Batch &b, in
     }
   }
   *no_centre_out = no_centre;
-  sync_on_return.armed = false;
   return hipStreamSynchronize(st);
 }
 }  // namespace
@@ -608,8 +674,10 @@ hipError_t codebooks_lloyd(const float *Ps, const float *Pf, int D, int L, const
                            float *d_means, int *iters_out, int *no_centre_out, CodebookPhases *phases,
                            std::chrono::steady_clock::time_point began, hipStream_t st) {
   if (plan.sub.empty() || plan.sample < 1) return hipErrorInvalidValue;
-  return cb_lloyd_batch(CbSources{{Ps, Pf, nullptr}}, L, cbfit::make_batch(plan, D, L), max_iter, d_means, iters_out,
-                        no_centre_out, phases, began, st);
+  CbWork work{st};
+  CbSync sync_on_return{st, true};  // (a failed launch: the workspace is freed behind what still runs)
+  return cb_lloyd_batch(work, CbSources{{Ps, Pf, nullptr}}, L, cbfit::make_batch(plan, D, L), max_iter, d_means, iters_out,
+                        no_centre_out, phases, began);
 }
 
 // ---- the hierarchical fit (DESIGN.md section 4f "Hierarchical"; fit_codebooks_hier_plan.h) ----
@@ -627,7 +695,8 @@ hipError_t codebooks_fit_hier(RowsRef d_X, int64_t n, int D, int L, const cbhier
   if (M < 1 || H < 1 || plan.gathered < 1 || plan.n_pairs > 0x7fffffff) return hipErrorInvalidValue;
   hipError_t e;
   CbPrepared src;
-  vaqhost::DevBuf b_perm, b_resample, b_fit, b_keys_in, b_keys_out, b_vals_in, b_vals_out, b_bounds, b_flag, b_temp, b_compact;
+  CbWork work{st};
+  vaqhost::DevBuf b_resample, b_compact;
   CbSync sync_on_return{st, true};
   *refusal = cbhier::Refusal{};
   *no_centre_out = 0;
@@ -640,24 +709,17 @@ hipError_t codebooks_fit_hier(RowsRef d_X, int64_t n, int D, int L, const cbhier
   CB_TRY(cb_prepare(d_X, n, D, d_eig, plan.n_full > 0, plan.gathered, true, src, st));
   // stage 1 of a subspace with more than 65536 rows samples for itself: rows randomPermutation(rows_s)[0 .. 65536) of R_s
   if (plan.resample_rows > 0) {
+    std::vector<CbResample> rs;
+    for (const cbhier::HSub &h : plan.hsub)
+      if (h.resampled) rs.push_back(CbResample{src.sample, D, h.s * L, h.rows, h.stage1_rows, h.resample_off});
     CB_TRY(b_resample.ensure((size_t)plan.resample_rows * L * sizeof(float)));
-    for (const cbhier::HSub &h : plan.hsub) {
-      if (!h.resampled) continue;
-      const std::vector<int> rows = permutation_head(h.rows, h.stage1_rows);
-      CB_TRY(b_perm.ensure(rows.size() * sizeof(int)));
-      CB_TRY(hipMemcpyAsync(b_perm.p, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(cb_slice_kernel, dim3((unsigned)(((int64_t)h.stage1_rows * L + 255) / 256)), dim3(256), 0, st,
-                         src.sample, D, h.s * L, b_perm.as<int>(), (int64_t)h.stage1_rows, L,
-                         b_resample.as<float>() + (size_t)h.resample_off * L);
-      CB_TRY(hipGetLastError());
-      CB_TRY(hipStreamSynchronize(st));  // (rows is the host's, b_perm is reused)
-    }
+    CB_TRY(work.gather_resamples(rs, L, b_resample.as<float>()));
   }
 
   // ---- stage 1 ----
   std::vector<int> it1((size_t)M, 0);
-  CB_TRY(cb_lloyd_batch(CbSources{{src.sample, src.full, b_resample.as<float>()}}, L, plan.stage1, max_iter, d_means, it1.data(),
-                        no_centre_out, phases ? &ph : nullptr, began, st));
+  CB_TRY(cb_lloyd_batch(work, CbSources{{src.sample, src.full, b_resample.as<float>()}}, L, plan.stage1, max_iter, d_means,
+                        it1.data(), no_centre_out, phases ? &ph : nullptr, began));
   for (int s = 0; s < M; s++) iters_out[s] = it1[(size_t)s];
   stats->stage1_ms = cb_ms_since(t0);
   t0 = std::chrono::steady_clock::now();
@@ -676,42 +738,27 @@ hipError_t codebooks_fit_hier(RowsRef d_X, int64_t n, int D, int L, const cbhier
 
   // ---- membership and regroup ----
   const int n_pairs = (int)plan.n_pairs, n_groups = H * cbhier::K1;
-  CB_TRY(b_fit.ensure((size_t)H * sizeof(cbfit::Fit)));
-  CB_TRY(b_keys_in.ensure((size_t)n_pairs * 4));
-  CB_TRY(b_keys_out.ensure((size_t)n_pairs * 4));
-  CB_TRY(b_vals_in.ensure((size_t)n_pairs * 4));
-  CB_TRY(b_vals_out.ensure((size_t)n_pairs * 4));
-  CB_TRY(b_bounds.ensure((size_t)2 * n_groups * sizeof(int)));
-  CB_TRY(b_flag.ensure((size_t)H * sizeof(int)));
+  CbWork::Tables member;
+  CB_TRY(work.upload(plan.member, &member));
+  CB_TRY(work.pairs(n_pairs));
+  CB_TRY(work.b_flags.ensure((size_t)H * sizeof(int)));
   CB_TRY(b_compact.ensure((size_t)n_pairs * L * sizeof(float)));
-  unsigned *keys_in = b_keys_in.as<unsigned>(), *keys_out = b_keys_out.as<unsigned>();
-  unsigned *vals_in = b_vals_in.as<unsigned>(), *vals_out = b_vals_out.as<unsigned>();
-  int *start = b_bounds.as<int>(), *end = start + n_groups;
-  size_t temp_bytes = 0;
-  CB_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n_pairs, 0u,
-                                   plan.member.key_bits, st));
-  CB_TRY(b_temp.ensure(temp_bytes ? temp_bytes : 16));
-  CB_TRY(hipMemcpyAsync(b_fit.p, plan.member.fit.data(), (size_t)H * sizeof(cbfit::Fit), hipMemcpyHostToDevice, st));
-  CB_TRY(hipMemsetAsync(b_flag.p, 0, (size_t)H * sizeof(int), st));
-  CB_TRY(hipMemsetAsync(start, 0, (size_t)2 * n_groups * sizeof(int), st));
+  CB_TRY(hipMemsetAsync(work.b_flags.p, 0, (size_t)H * sizeof(int), st));
   const CbSources member_src{{src.sample, nullptr, nullptr}};
-  CB_TRY(cb_launch_assign<true>(member_src, L, plan.member, b_fit.as<cbfit::Fit>(), nullptr, d_means, nullptr, keys_in, vals_in,
-                                b_flag.as<int>(), st));
+  CB_TRY(cb_launch_assign<true>(member_src, L, plan.member, member.fits, nullptr, d_means, nullptr, work.keys_in, work.vals_in,
+                                work.b_flags.as<int>(), st));
   // stable: the rows of a group stay in ascending position within R_s
-  CB_TRY(rocprim::radix_sort_pairs(b_temp.p, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)n_pairs, 0u,
-                                   plan.member.key_bits, st));
-  hipLaunchKernelGGL(cb_bounds_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st, keys_out, n_pairs, start, end);
-  CB_TRY(hipGetLastError());
+  CB_TRY(work.sort_and_bound(n_pairs, plan.member.key_bits, n_groups));
   for (const cbhier::HSub &h : plan.hsub) {  // the sorted rows of subspace h are pairs [pair_off, pair_off + rows)
     hipLaunchKernelGGL(cb_slice_kernel, dim3((unsigned)(((int64_t)h.rows * L + 255) / 256)), dim3(256), 0, st, src.sample, D,
-                       h.s * L, reinterpret_cast<const int *>(vals_out) + h.pair_off, (int64_t)h.rows, L,
+                       h.s * L, reinterpret_cast<const int *>(work.vals_out) + h.pair_off, (int64_t)h.rows, L,
                        b_compact.as<float>() + (size_t)h.pair_off * L);
     CB_TRY(hipGetLastError());
   }
   std::vector<int> bounds((size_t)2 * n_groups), counts((size_t)n_groups), unreached((size_t)H);
-  CB_TRY(hipMemcpyAsync(bounds.data(), start, bounds.size() * sizeof(int), hipMemcpyDeviceToHost, st));
-  CB_TRY(hipMemcpyAsync(unreached.data(), b_flag.p, (size_t)H * sizeof(int), hipMemcpyDeviceToHost, st));
-  CB_TRY(hipStreamSynchronize(st));
+  CB_TRY(hipMemcpyAsync(bounds.data(), work.start, bounds.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+  CB_TRY(hipMemcpyAsync(unreached.data(), work.b_flags.p, (size_t)H * sizeof(int), hipMemcpyDeviceToHost, st));
+  CB_TRY(hipStreamSynchronize(st));  // (and the slices have read vals_out: stage 2 may take the workspace)
   stats->groups = n_groups;
   stats->min_group = 0x7fffffff;
   for (int g = 0; g < n_groups; g++) {
@@ -733,8 +780,8 @@ hipError_t codebooks_fit_hier(RowsRef d_X, int64_t n, int D, int L, const cbhier
   // ---- stage 2: every group of every hierarchical subspace, one batch ----
   const cbfit::Batch stage2 = cbhier::make_stage2(plan, counts.data(), L, cbfit::assign_tile_rows(L));
   std::vector<int> it2(stage2.fit.size(), 0);
-  CB_TRY(cb_lloyd_batch(CbSources{{b_compact.as<float>(), nullptr, nullptr}}, L, stage2, max_iter, d_means, it2.data(),
-                        no_centre_out, phases ? &ph : nullptr, t0, st));
+  CB_TRY(cb_lloyd_batch(work, CbSources{{b_compact.as<float>(), nullptr, nullptr}}, L, stage2, max_iter, d_means, it2.data(),
+                        no_centre_out, phases ? &ph : nullptr, t0));
   for (int h = 0; h < H; h++)
     for (int g = 0; g < cbhier::K1; g++) {
       int &out = iters_out[plan.hsub[(size_t)h].s];
@@ -765,7 +812,8 @@ hipError_t codebooks_fit_bin(RowsRef d_X, int64_t n, int D, int L, const cbbin::
   if (M < 1 || plan.bsub.empty() || plan.gathered < 1 || plan.n_pairs > 0x7fffffff) return hipErrorInvalidValue;
   hipError_t e;
   CbPrepared src;
-  vaqhost::DevBuf b_perm, b_extra, b_fit, b_tile, b_dest, b_keys_in, b_keys_out, b_vals_in, b_vals_out, b_bounds, b_temp, b_level[2];
+  CbWork work{st};
+  vaqhost::DevBuf b_extra, b_dest, b_level[2];
   CbSync sync_on_return{st, true};
   *no_centre_out = 0;
   *stats = CodebookBinStats{};
@@ -775,44 +823,26 @@ hipError_t codebooks_fit_bin(RowsRef d_X, int64_t n, int D, int L, const cbbin::
   for (int s = 0; s < M; s++) iters_out[s] = 0;
 
   CB_TRY(cb_prepare(d_X, n, D, d_eig, plan.n_full > 0, plan.gathered, true, src, st));
-  const int n_pairs = (int)plan.n_pairs, tile_rows = cbfit::assign_tile_rows(L);
-  CB_TRY(b_keys_in.ensure((size_t)n_pairs * 4));
-  CB_TRY(b_keys_out.ensure((size_t)n_pairs * 4));
-  CB_TRY(b_vals_in.ensure((size_t)n_pairs * 4));
-  CB_TRY(b_vals_out.ensure((size_t)n_pairs * 4));
-  unsigned *keys_in = b_keys_in.as<unsigned>(), *keys_out = b_keys_out.as<unsigned>();
-  unsigned *vals_in = b_vals_in.as<unsigned>(), *vals_out = b_vals_out.as<unsigned>();
+  const int tile_rows = cbfit::assign_tile_rows(L);
 
   CbSources cur{{src.sample, src.full, nullptr}};
   // one kind of fits of a level: the samples of those that sample, then chunk after chunk of the Lloyd phases
   auto run_fits = [&](const std::vector<cbbin::Node> &level, const cbbin::Fits &f, std::chrono::steady_clock::time_point t0) -> hipError_t {
     if (!f.resample.empty()) {
-      std::vector<int> perm;
-      std::vector<size_t> at;
+      std::vector<CbResample> rs;
       for (const cbbin::Resample &r : f.resample) {
-        const std::vector<int> rows = permutation_head(level[(size_t)r.node].rows, r.rows);
-        at.push_back(perm.size());
-        perm.insert(perm.end(), rows.begin(), rows.end());
-      }
-      CB_TRY(b_perm.ensure(perm.size() * sizeof(int)));
-      CB_TRY(b_extra.ensure((size_t)f.extra_rows * L * sizeof(float)));
-      CB_TRY(hipMemcpyAsync(b_perm.p, perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice, st));
-      for (size_t i = 0; i < f.resample.size(); i++) {
-        const cbbin::Resample &r = f.resample[i];
         const cbbin::Node &nd = level[(size_t)r.node];
-        hipLaunchKernelGGL(cb_slice_kernel, dim3((unsigned)(((int64_t)r.rows * L + 255) / 256)), dim3(256), 0, st,
-                           cur.p[nd.src] + (size_t)nd.row0 * nd.stride, nd.stride, nd.col, b_perm.as<int>() + at[i],
-                           (int64_t)r.rows, L, b_extra.as<float>() + (size_t)r.off * L);
-        CB_TRY(hipGetLastError());
+        rs.push_back(CbResample{cur.p[nd.src] + (size_t)nd.row0 * nd.stride, nd.stride, nd.col, nd.rows, r.rows, r.off});
       }
-      CB_TRY(hipStreamSynchronize(st));  // (perm is the host's)
+      CB_TRY(b_extra.ensure((size_t)f.extra_rows * L * sizeof(float)));
+      CB_TRY(work.gather_resamples(rs, L, b_extra.as<float>()));
       stats->resampled_fits += (int)f.resample.size();
     }
     const CbSources fit_src{{cur.p[0], cur.p[1], b_extra.as<float>()}};
     for (size_t c = 0; c < f.chunk.size(); c++) {
       std::vector<int> its(f.chunk[c].fit.size(), 0);
       int nc = 0;
-      CB_TRY(cb_lloyd_batch(fit_src, L, f.chunk[c], max_iter, d_means, its.data(), &nc, phases ? &ph : nullptr, t0, st, staged_sums));
+      CB_TRY(cb_lloyd_batch(work, fit_src, L, f.chunk[c], max_iter, d_means, its.data(), &nc, phases ? &ph : nullptr, t0, staged_sums));
       *no_centre_out |= nc;
       for (size_t i = 0; i < its.size(); i++) {
         const int o = f.owner[c][i];
@@ -851,26 +881,17 @@ hipError_t codebooks_fit_bin(RowsRef d_X, int64_t n, int D, int L, const cbbin::
     t0 = std::chrono::steady_clock::now();
     const cbfit::Batch split = cbbin::make_split(plan, level, inner, tile_rows);
     const int F = (int)split.fit.size(), sp = (int)split.n_pairs;
-    CB_TRY(b_fit.ensure((size_t)F * sizeof(cbfit::Fit)));
-    CB_TRY(b_tile.ensure(split.tile.size() * sizeof(cbfit::Tile)));
-    CB_TRY(b_bounds.ensure((size_t)4 * F * sizeof(int)));
+    CbWork::Tables tabs;
+    CB_TRY(work.upload(split, &tabs));
+    CB_TRY(work.pairs(sp));
     CB_TRY(b_dest.ensure((size_t)F * sizeof(int64_t)));
-    int *start = b_bounds.as<int>(), *end = start + 2 * F;
-    size_t temp_bytes = 0;
-    CB_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)sp, 0u, split.key_bits, st));
-    CB_TRY(b_temp.ensure(temp_bytes ? temp_bytes : 16));
-    CB_TRY(hipMemcpyAsync(b_fit.p, split.fit.data(), (size_t)F * sizeof(cbfit::Fit), hipMemcpyHostToDevice, st));
-    CB_TRY(hipMemcpyAsync(b_tile.p, split.tile.data(), split.tile.size() * sizeof(cbfit::Tile), hipMemcpyHostToDevice, st));
-    CB_TRY(hipMemsetAsync(start, 0, (size_t)4 * F * sizeof(int), st));
     hipLaunchKernelGGL(cb_split_kernel, dim3((unsigned)split.tile.size()), dim3(tile_rows), (size_t)2 * L * sizeof(float), st, cur, L,
-                       b_fit.as<cbfit::Fit>(), b_tile.as<cbfit::Tile>(), d_means, keys_in, vals_in);
+                       tabs.fits, tabs.tiles, d_means, work.keys_in, work.vals_in);
     CB_TRY(hipGetLastError());
     // stable: each side of a node keeps its rows in ascending position within the node
-    CB_TRY(rocprim::radix_sort_pairs(b_temp.p, temp_bytes, keys_in, keys_out, vals_in, vals_out, (size_t)sp, 0u, split.key_bits, st));
-    hipLaunchKernelGGL(cb_bounds_kernel, dim3((unsigned)((sp + 255) / 256)), dim3(256), 0, st, keys_out, sp, start, end);
-    CB_TRY(hipGetLastError());
+    CB_TRY(work.sort_and_bound(sp, split.key_bits, 2 * F));
     std::vector<int> bounds((size_t)4 * F), left((size_t)F), right((size_t)F), cut;
-    CB_TRY(hipMemcpyAsync(bounds.data(), start, bounds.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    CB_TRY(hipMemcpyAsync(bounds.data(), work.start, bounds.size() * sizeof(int), hipMemcpyDeviceToHost, st));
     CB_TRY(hipStreamSynchronize(st));
     std::vector<cbbin::Kind> kind((size_t)F);
     for (int i = 0; i < F; i++) {
@@ -884,15 +905,15 @@ hipError_t codebooks_fit_bin(RowsRef d_X, int64_t n, int D, int L, const cbbin::
     int64_t next_rows = 0;
     std::vector<cbbin::Node> next = cbbin::next_level(level, inner, kind, left.data(), right.data(), L, &dest, &next_rows);
     float *out = nullptr;
-    if (next_rows > 0) {  // (before the cut fits: they read `cur` as well, nothing writes it)
+    if (next_rows > 0) {  // (before the cut fits: they read `cur` as well, nothing writes it -- and they take the workspace)
       vaqhost::DevBuf &nb = b_level[depth & 1];
       CB_TRY(nb.ensure((size_t)next_rows * L * sizeof(float)));
       out = nb.as<float>();
       CB_TRY(hipMemcpyAsync(b_dest.p, dest.data(), (size_t)F * sizeof(int64_t), hipMemcpyHostToDevice, st));
       hipLaunchKernelGGL(cb_regroup_kernel, dim3((unsigned)(((int64_t)sp * L + 255) / 256)), dim3(256), 0, st, cur, L,
-                         b_fit.as<cbfit::Fit>(), b_dest.as<int64_t>(), keys_out, vals_out, (int64_t)sp, out);
+                         tabs.fits, b_dest.as<int64_t>(), work.keys_out, work.vals_out, (int64_t)sp, out);
       CB_TRY(hipGetLastError());
-      CB_TRY(hipStreamSynchronize(st));  // (dest is the host's)
+      CB_TRY(hipStreamSynchronize(st));  // (dest is the host's; the sorted pairs and the fit table have been read)
     }
     stats->split_ms += cb_ms_since(t0);
 

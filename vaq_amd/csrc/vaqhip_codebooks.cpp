@@ -23,8 +23,7 @@ thread_local vaqhip_fit_codebooks_hier_timing g_cbh_last = {};
 thread_local vaqhip_fit_codebooks_bin_timing g_cbn_last = {};
 thread_local int g_cbn_sums = 0;  // vaqhip_fit_codebooks_bin_set_sums
 
-// which of the three forms an entry point is
-enum Form { FLAT = 0, HIER, BIN };
+using Form = vaqhost::CodebookForm;  // which of the three forms an entry point is
 
 // every refusal that needs no device, in the order the header lists them; fills the plan when there is none
 int check_args(const void *X, int64_t n, int D, int M, const int *bits, int max_iter, const void *cent, cb::Plan *plan) {
@@ -47,69 +46,31 @@ int check_args(const void *X, int64_t n, int D, int M, const int *bits, int max_
   return VAQHIP_OK;
 }
 
-// device pointers throughout (bits, iters_out, nan_rows_out: host), the device current; the outputs are written only
-// when the fit succeeds
-int fit_core(vaq::RowsRef d_X, int64_t n, int D, const cb::Plan &plan, const float *d_eig, int max_iter,
-             float *d_cent_out, int *iters_out, int *nan_rows_out, hipStream_t st) {
-  const auto t0 = std::chrono::steady_clock::now();
-  const int M = (int)plan.sub.size(), L = D / M;
-  const size_t cent_floats = (size_t)plan.n_cent * L;
-  DevBuf b_means;
-  HIP_TRY(b_means.ensure(cent_floats * sizeof(float)));
-  std::vector<int> iters((size_t)M, 0);
-  int no_centre = 0;
-  vaq::CodebookPhases ph;
-  HIP_TRY(vaq::codebooks_fit(d_X, n, D, L, plan, d_eig, max_iter, b_means.as<float>(), iters.data(), &no_centre,
-                             g_cb_timing ? &ph : nullptr, st));  // synchronises
-  if (no_centre)
-    return fail(VAQHIP_EINVAL, "a row is at a distance >= FLT_MAX (or NaN) from every centre: the reference indexes row -1");
-  std::vector<float> means(cent_floats);
-  HIP_TRY(hipMemcpyAsync(means.data(), b_means.p, cent_floats * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(d_cent_out, b_means.p, cent_floats * sizeof(float), hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  int max_iters = 0;
-  for (int s = 0; s < M; s++) {
-    const cb::Sub &sd = plan.sub[(size_t)s];
-    if (iters_out) iters_out[s] = iters[(size_t)s];
-    if (nan_rows_out) nan_rows_out[s] = vaq::nan_rows(means.data() + (size_t)sd.cent_off * L, sd.k, L);
-    max_iters = std::max(max_iters, iters[(size_t)s]);
-  }
-  g_cb_last = vaqhip_fit_codebooks_timing{};
-  g_cb_last.total_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  g_cb_last.gather_ms = (float)ph.gather_ms;
-  g_cb_last.assign_ms = (float)ph.assign_ms;
-  g_cb_last.accumulate_ms = (float)ph.accumulate_ms;
-  g_cb_last.update_ms = (float)ph.update_ms;
-  g_cb_last.iterations = max_iters;
-  g_cb_last.sample_rows = plan.sample;
-  g_cb_last.rows = n;
-  g_cb_last.dims = D;
-  g_cb_last.subspaces = M;
-  return VAQHIP_OK;
-}
+// the plans of a call: the flat one always, and the form's own (fit_codebooks_hier_plan.h, fit_codebooks_bin_plan.h)
+// where a subspace is above 8 bits -- else the call is the flat fit, bit for bit
+struct Plans {
+  Form form = Form::FLAT;
+  cb::Plan flat;
+  ch::Plan hier;
+  cn::Plan bin;
+  // the wide form's plan head; null when the call is the flat fit
+  const cb::WideHead *wide() const { return !hier.hsub.empty() ? &hier : !bin.bsub.empty() ? &bin : (const cb::WideHead *)nullptr; }
+};
 
-// ---- the hierarchical form: subspaces above 8 bits in two stages (fit_codebooks_hier_plan.h) ----
-// what the hierarchical form refuses beyond check_args, and its plan; hp->hsub stays empty when no subspace is above
-// 8 bits: the call is then the flat fit, bit for bit
-int plan_hier(int64_t n, int D, int M, const int *bits, ch::Plan *hp) {
-  const int s = ch::first_short_subspace(n, M, bits);
+// every refusal that needs no device, for any form; fills the plans
+int plan_call(Form form, const void *X, int64_t n, int D, int M, const int *bits, int max_iter, const void *cent, Plans *p) {
+  p->form = form;
+  if (int rc = check_args(X, n, D, M, bits, max_iter, cent, &p->flat)) return rc;
+  if (form == Form::FLAT) return VAQHIP_OK;
+  const int s = cb::first_short_subspace(n, M, bits);  // (both wide forms: the same subspaces, the same rows)
   if (s >= 0)
     return fail(VAQHIP_EINVAL, "bits[%d]=%d: %d centres from %lld rows (the reference seeds from rows out of bounds)", s,
                 bits[s], 1 << bits[s], (long long)n);
   bool any = false;
-  for (int i = 0; i < M; i++) any |= ch::hierarchical(bits[i]);
-  if (any) *hp = ch::make_plan(n, D, M, bits);
+  for (int i = 0; i < M; i++) any |= cb::wide(bits[i]);
+  if (any && form == Form::HIER) p->hier = ch::make_plan(n, D, M, bits);
+  if (any && form == Form::BIN) p->bin = cn::make_plan(n, M, bits);
   return VAQHIP_OK;
-}
-
-// the last hierarchical call's figures when it was the flat fit (no subspace above 8 bits)
-void note_flat_as_hier() {
-  g_cbh_last = vaqhip_fit_codebooks_hier_timing{};
-  g_cbh_last.total_ms = g_cbh_last.stage1_ms = g_cb_last.total_ms;
-  g_cbh_last.stage1_iterations = g_cb_last.iterations;
-  g_cbh_last.subspaces = g_cb_last.subspaces;
-  g_cbh_last.dims = g_cb_last.dims;
-  g_cbh_last.rows = g_cb_last.rows;
 }
 
 int refuse_hier(const ch::Refusal &r) {
@@ -133,21 +94,65 @@ int refuse_hier(const ch::Refusal &r) {
   }
 }
 
-// fit_core's twin over a plan with a hierarchical subspace
-int fit_core_hier(vaq::RowsRef d_X, int64_t n, int D, const ch::Plan &hp, const float *d_eig, int max_iter, float *d_cent_out,
-                  int *iters_out, int *nan_rows_out, hipStream_t st) {
+// what every form reports of its last call
+void note_last(float total_ms, const vaq::CodebookPhases &ph, int iterations, int64_t sample_rows, int64_t n, int D, int M) {
+  g_cb_last = vaqhip_fit_codebooks_timing{};
+  g_cb_last.total_ms = total_ms;
+  g_cb_last.gather_ms = (float)ph.gather_ms;
+  g_cb_last.assign_ms = (float)ph.assign_ms;
+  g_cb_last.accumulate_ms = (float)ph.accumulate_ms;
+  g_cb_last.update_ms = (float)ph.update_ms;
+  g_cb_last.iterations = iterations;
+  g_cb_last.sample_rows = sample_rows;
+  g_cb_last.rows = n;
+  g_cb_last.dims = D;
+  g_cb_last.subspaces = M;
+}
+
+// a wide form's figures emptied but for what they share with g_cb_last; a call that was the flat fit (no subspace above
+// 8 bits) is one stage `ms` of `iterations`
+template <typename T>
+void note_wide(T &last, float T::*ms = nullptr, int T::*iterations = nullptr) {
+  last = T{};
+  last.total_ms = g_cb_last.total_ms;
+  if (ms) last.*ms = g_cb_last.total_ms;
+  if (iterations) last.*iterations = g_cb_last.iterations;
+  last.subspaces = g_cb_last.subspaces;
+  last.dims = g_cb_last.dims;
+  last.rows = g_cb_last.rows;
+}
+void note_flat_as(Form form) {
+  if (form == Form::HIER)
+    note_wide(g_cbh_last, &vaqhip_fit_codebooks_hier_timing::stage1_ms, &vaqhip_fit_codebooks_hier_timing::stage1_iterations);
+  if (form == Form::BIN)
+    note_wide(g_cbn_last, &vaqhip_fit_codebooks_bin_timing::fit_ms, &vaqhip_fit_codebooks_bin_timing::max_iterations);
+}
+
+// The fit of any form: the form's own device fit where a subspace is above 8 bits, else the flat one.  Device pointers
+// throughout (bits, iters_out, nan_rows_out: host), the device current; the outputs are written only when the fit
+// succeeds.
+int fit_core(vaq::RowsRef d_X, int64_t n, int D, const Plans &p, const float *d_eig, int max_iter, float *d_cent_out,
+             int *iters_out, int *nan_rows_out, hipStream_t st) {
   const auto t0 = std::chrono::steady_clock::now();
-  const int M = (int)hp.flat.sub.size(), L = D / M, H = (int)hp.hsub.size();
-  const size_t cent_floats = (size_t)hp.n_cent * L;
-  DevBuf b_means;  // the final centres, the stage-1 centres behind them
+  const int M = (int)p.flat.sub.size(), L = D / M, H = (int)p.hier.hsub.size();
+  const bool bin = !p.bin.bsub.empty();
+  const size_t cent_floats = (size_t)p.flat.n_cent * L;
+  DevBuf b_means;  // the final centres, the hierarchical form's stage-1 centres behind them
   HIP_TRY(b_means.ensure((cent_floats + (size_t)H * ch::K1 * L) * sizeof(float)));
   std::vector<int> iters((size_t)M, 0);
   int no_centre = 0;
   ch::Refusal refusal;
   vaq::CodebookHierStats hs;
-  vaq::CodebookPhases ph;
-  HIP_TRY(vaq::codebooks_fit_hier(d_X, n, D, L, hp, d_eig, max_iter, b_means.as<float>(), iters.data(), &no_centre, &refusal,
-                                  &hs, g_cb_timing ? &ph : nullptr, st));  // synchronises
+  vaq::CodebookBinStats bs;
+  vaq::CodebookPhases ph, *php = g_cb_timing ? &ph : nullptr;
+  if (H)  // (all three synchronise)
+    HIP_TRY(vaq::codebooks_fit_hier(d_X, n, D, L, p.hier, d_eig, max_iter, b_means.as<float>(), iters.data(), &no_centre, &refusal,
+                                    &hs, php, st));
+  else if (bin)
+    HIP_TRY(vaq::codebooks_fit_bin(d_X, n, D, L, p.bin, d_eig, max_iter, g_cbn_sums == 0, b_means.as<float>(), iters.data(),
+                                   &no_centre, &bs, php, st));
+  else
+    HIP_TRY(vaq::codebooks_fit(d_X, n, D, L, p.flat, d_eig, max_iter, b_means.as<float>(), iters.data(), &no_centre, php, st));
   if (refusal.kind != ch::OK) return refuse_hier(refusal);
   if (no_centre)
     return fail(VAQHIP_EINVAL, "a row is at a distance >= FLT_MAX (or NaN) from every centre: the reference indexes row -1");
@@ -157,151 +162,52 @@ int fit_core_hier(vaq::RowsRef d_X, int64_t n, int D, const ch::Plan &hp, const 
   HIP_TRY(hipStreamSynchronize(st));
   int max_iters = 0;
   for (int s = 0; s < M; s++) {
-    const cb::Sub &sd = hp.flat.sub[(size_t)s];
+    const cb::Sub &sd = p.flat.sub[(size_t)s];
     if (iters_out) iters_out[s] = iters[(size_t)s];
     if (nan_rows_out) nan_rows_out[s] = vaq::nan_rows(means.data() + (size_t)sd.cent_off * L, sd.k, L);
     max_iters = std::max(max_iters, iters[(size_t)s]);
   }
-  const float total = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  g_cb_last = vaqhip_fit_codebooks_timing{};
-  g_cb_last.total_ms = total;
-  g_cb_last.gather_ms = (float)ph.gather_ms;
-  g_cb_last.assign_ms = (float)ph.assign_ms;
-  g_cb_last.accumulate_ms = (float)ph.accumulate_ms;
-  g_cb_last.update_ms = (float)ph.update_ms;
-  g_cb_last.iterations = max_iters;
-  g_cb_last.sample_rows = std::max(hp.gathered, hp.n_full ? n : (int64_t)0);
-  g_cb_last.rows = n;
-  g_cb_last.dims = D;
-  g_cb_last.subspaces = M;
-  g_cbh_last = vaqhip_fit_codebooks_hier_timing{};
-  g_cbh_last.total_ms = total;
-  g_cbh_last.stage1_ms = (float)hs.stage1_ms;
-  g_cbh_last.regroup_ms = (float)hs.regroup_ms;
-  g_cbh_last.stage2_ms = (float)hs.stage2_ms;
-  g_cbh_last.groups = hs.groups;
-  g_cbh_last.min_group_rows = hs.min_group;
-  g_cbh_last.max_group_rows = hs.max_group;
-  g_cbh_last.stage1_iterations = hs.stage1_iters;
-  g_cbh_last.stage2_iterations = hs.stage2_iters;
-  g_cbh_last.hier_subspaces = H;
-  g_cbh_last.subspaces = M;
-  g_cbh_last.dims = D;
-  g_cbh_last.rows = n;
-  return VAQHIP_OK;
-}
-
-// ---- the binary-tree form: subspaces above 8 bits as a tree of 2-centre fits (fit_codebooks_bin_plan.h) ----
-// the plans of a call: the flat one always, and the form's own where a subspace is above 8 bits (else the call is the
-// flat fit, bit for bit)
-struct Plans {
-  Form form = FLAT;
-  cb::Plan flat;
-  ch::Plan hier;
-  cn::Plan bin;
-  bool wide() const { return !hier.hsub.empty() || !bin.bsub.empty(); }
-};
-
-// every refusal that needs no device, for any form; fills the plans
-int plan_call(Form form, const void *X, int64_t n, int D, int M, const int *bits, int max_iter, const void *cent, Plans *p) {
-  p->form = form;
-  if (int rc = check_args(X, n, D, M, bits, max_iter, cent, &p->flat)) return rc;
-  if (form == HIER) return plan_hier(n, D, M, bits, &p->hier);
-  if (form != BIN) return VAQHIP_OK;
-  const int s = ch::first_short_subspace(n, M, bits);  // (the same subspaces, the same rows)
-  if (s >= 0)
-    return fail(VAQHIP_EINVAL, "bits[%d]=%d: %d centres from %lld rows (the reference seeds from rows out of bounds)", s,
-                bits[s], 1 << bits[s], (long long)n);
-  bool any = false;
-  for (int i = 0; i < M; i++) any |= cn::binary(bits[i]);
-  if (any) p->bin = cn::make_plan(n, M, bits);
-  return VAQHIP_OK;
-}
-
-// the last binary call's figures when it was the flat fit (no subspace above 8 bits)
-void note_flat_as_bin() {
-  g_cbn_last = vaqhip_fit_codebooks_bin_timing{};
-  g_cbn_last.total_ms = g_cbn_last.fit_ms = g_cb_last.total_ms;
-  g_cbn_last.max_iterations = g_cb_last.iterations;
-  g_cbn_last.subspaces = g_cb_last.subspaces;
-  g_cbn_last.dims = g_cb_last.dims;
-  g_cbn_last.rows = g_cb_last.rows;
-}
-
-// fit_core's twin over a plan with a binary subspace
-int fit_core_bin(vaq::RowsRef d_X, int64_t n, int D, const cn::Plan &bp, const float *d_eig, int max_iter, float *d_cent_out,
-                 int *iters_out, int *nan_rows_out, hipStream_t st) {
-  const int M = (int)bp.flat.sub.size(), L = D / M;
-  const size_t cent_floats = (size_t)bp.n_cent * L;
-  DevBuf b_means;
-  HIP_TRY(b_means.ensure(cent_floats * sizeof(float)));
-  std::vector<int> iters((size_t)M, 0);
-  int no_centre = 0;
-  vaq::CodebookBinStats bs;
-  vaq::CodebookPhases ph;
-  HIP_TRY(vaq::codebooks_fit_bin(d_X, n, D, L, bp, d_eig, max_iter, g_cbn_sums == 0, b_means.as<float>(), iters.data(), &no_centre,
-                                 &bs, g_cb_timing ? &ph : nullptr, st));  // synchronises
-  if (no_centre)
-    return fail(VAQHIP_EINVAL, "a row is at a distance >= FLT_MAX (or NaN) from every centre: the reference indexes row -1");
-  std::vector<float> means(cent_floats);
-  HIP_TRY(hipMemcpyAsync(means.data(), b_means.p, cent_floats * sizeof(float), hipMemcpyDeviceToHost, st));
-  HIP_TRY(hipMemcpyAsync(d_cent_out, b_means.p, cent_floats * sizeof(float), hipMemcpyDeviceToDevice, st));
-  HIP_TRY(hipStreamSynchronize(st));
-  for (int s = 0; s < M; s++) {
-    const cb::Sub &sd = bp.flat.sub[(size_t)s];
-    if (iters_out) iters_out[s] = iters[(size_t)s];
-    if (nan_rows_out) nan_rows_out[s] = vaq::nan_rows(means.data() + (size_t)sd.cent_off * L, sd.k, L);
+  const cb::WideHead *w = p.wide();
+  note_last(bin ? (float)bs.total_ms : std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count(), ph,
+            bin ? bs.max_iters : max_iters, w ? std::max(w->gathered, w->n_full ? n : (int64_t)0) : p.flat.sample, n, D, M);
+  if (H) {
+    note_wide(g_cbh_last);
+    g_cbh_last.stage1_ms = (float)hs.stage1_ms;
+    g_cbh_last.regroup_ms = (float)hs.regroup_ms;
+    g_cbh_last.stage2_ms = (float)hs.stage2_ms;
+    g_cbh_last.groups = hs.groups;
+    g_cbh_last.min_group_rows = hs.min_group;
+    g_cbh_last.max_group_rows = hs.max_group;
+    g_cbh_last.stage1_iterations = hs.stage1_iters;
+    g_cbh_last.stage2_iterations = hs.stage2_iters;
+    g_cbh_last.hier_subspaces = H;
+  } else if (bin) {
+    note_wide(g_cbn_last);
+    g_cbn_last.fit_ms = (float)bs.fit_ms;
+    g_cbn_last.split_ms = (float)bs.split_ms;
+    g_cbn_last.cut_ms = (float)bs.cut_ms;
+    g_cbn_last.levels = bs.levels;
+    g_cbn_last.nodes = bs.nodes;
+    g_cbn_last.cut_nodes = bs.cut_nodes;
+    g_cbn_last.resampled_fits = bs.resampled_fits;
+    g_cbn_last.leaf_nodes = bs.leaf_nodes;
+    g_cbn_last.min_leaf_rows = bs.min_leaf_rows;
+    g_cbn_last.max_leaf_rows = bs.max_leaf_rows;
+    g_cbn_last.max_iterations = bs.max_iters;
+    g_cbn_last.bin_subspaces = (int)p.bin.bsub.size();
+  } else {
+    note_flat_as(p.form);
   }
-  g_cb_last = vaqhip_fit_codebooks_timing{};
-  g_cb_last.total_ms = (float)bs.total_ms;
-  g_cb_last.gather_ms = (float)ph.gather_ms;
-  g_cb_last.assign_ms = (float)ph.assign_ms;
-  g_cb_last.accumulate_ms = (float)ph.accumulate_ms;
-  g_cb_last.update_ms = (float)ph.update_ms;
-  g_cb_last.iterations = bs.max_iters;
-  g_cb_last.sample_rows = std::max(bp.gathered, bp.n_full ? n : (int64_t)0);
-  g_cb_last.rows = n;
-  g_cb_last.dims = D;
-  g_cb_last.subspaces = M;
-  g_cbn_last = vaqhip_fit_codebooks_bin_timing{};
-  g_cbn_last.total_ms = (float)bs.total_ms;
-  g_cbn_last.fit_ms = (float)bs.fit_ms;
-  g_cbn_last.split_ms = (float)bs.split_ms;
-  g_cbn_last.cut_ms = (float)bs.cut_ms;
-  g_cbn_last.levels = bs.levels;
-  g_cbn_last.nodes = bs.nodes;
-  g_cbn_last.cut_nodes = bs.cut_nodes;
-  g_cbn_last.resampled_fits = bs.resampled_fits;
-  g_cbn_last.leaf_nodes = bs.leaf_nodes;
-  g_cbn_last.min_leaf_rows = bs.min_leaf_rows;
-  g_cbn_last.max_leaf_rows = bs.max_leaf_rows;
-  g_cbn_last.max_iterations = bs.max_iters;
-  g_cbn_last.bin_subspaces = (int)bp.bsub.size();
-  g_cbn_last.subspaces = M;
-  g_cbn_last.dims = D;
-  g_cbn_last.rows = n;
   return VAQHIP_OK;
 }
 
-// the form's own fit where a subspace is above 8 bits; else the flat one
-int fit_either(vaq::RowsRef d_X, int64_t n, int D, const Plans &p, const float *d_eig, int max_iter, float *d_cent_out,
-               int *iters_out, int *nan_rows_out, hipStream_t st) {
-  if (!p.hier.hsub.empty()) return fit_core_hier(d_X, n, D, p.hier, d_eig, max_iter, d_cent_out, iters_out, nan_rows_out, st);
-  if (!p.bin.bsub.empty()) return fit_core_bin(d_X, n, D, p.bin, d_eig, max_iter, d_cent_out, iters_out, nan_rows_out, st);
-  const int rc = fit_core(d_X, n, D, p.flat, d_eig, max_iter, d_cent_out, iters_out, nan_rows_out, st);
-  if (p.form == HIER && rc == VAQHIP_OK) note_flat_as_hier();
-  if (p.form == BIN && rc == VAQHIP_OK) note_flat_as_bin();
-  return rc;
-}
-
-// form: the hierarchical or the binary form's refusals and plan on top (vaqhip_fit_codebooks_hier*, _bin*)
-int fit_device_entry(int device_id, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits, const float *d_eigvec,
-                     int max_iter, float *d_centroids_out, int *iters_out, int *nan_rows_out, void *stream, Form form = FLAT) {
+int fit_device_entry(Form form, int device_id, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits, const float *d_eigvec,
+                     int max_iter, float *d_centroids_out, int *iters_out, int *nan_rows_out, void *stream) {
   Plans p;
   if (int rc = plan_call(form, d_X.p, n, D, M, bits, max_iter, d_centroids_out, &p)) return rc;
   DeviceGuard g(device_id);
   if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed (no CPU path)", device_id);
-  return fit_either(d_X, n, D, p, d_eigvec, max_iter, d_centroids_out, iters_out, nan_rows_out, static_cast<hipStream_t>(stream));
+  return fit_core(d_X, n, D, p, d_eigvec, max_iter, d_centroids_out, iters_out, nan_rows_out, static_cast<hipStream_t>(stream));
 }
 
 // the rest of a host-output call once the rows are on the device (current): eigvec up, fit, centres down
@@ -317,8 +223,8 @@ int fit_to_host(vaq::RowsRef d_X, int64_t n, int D, const Plans &p, const float 
   }
   CallStream st;
   HIP_TRY(st.open());
-  if (int rc = fit_either(d_X, n, D, p, eigvec ? d_eig.as<float>() : nullptr, max_iter, d_cent.as<float>(), iters_out,
-                          nan_rows_out, st.s))
+  if (int rc = fit_core(d_X, n, D, p, eigvec ? d_eig.as<float>() : nullptr, max_iter, d_cent.as<float>(), iters_out,
+                        nan_rows_out, st.s))
     return rc;
   HIP_TRY(hipMemcpy(centroids_out, d_cent.p, cent_bytes, hipMemcpyDeviceToHost));
   return VAQHIP_OK;
@@ -329,8 +235,8 @@ int fit_to_host(vaq::RowsRef d_X, int64_t n, int D, const Plans &p, const float 
 // subspace reads all rows, all rows go up, and the device gathers the sample of the others.
 // The hierarchical and the binary form with a subspace above 8 bits upload all rows: their one gather serves both kinds
 // of subspace.
-int fit_host_entry(int device_id, vaq::RowsRef X, int64_t n, int D, int M, const int *bits, const float *eigvec,
-                   int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out, Form form = FLAT) {
+int fit_host_entry(Form form, int device_id, vaq::RowsRef X, int64_t n, int D, int M, const int *bits, const float *eigvec,
+                   int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out) {
   Plans p;
   if (int rc = plan_call(form, X.p, n, D, M, bits, max_iter, centroids_out, &p)) return rc;
   cb::Plan &plan = p.flat;
@@ -352,60 +258,41 @@ int fit_host_entry(int device_id, vaq::RowsRef X, int64_t n, int D, int M, const
   }
   return fit_to_host(vaq::RowsRef{d_x.p, X.elem}, n, D, p, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
 }
+}  // namespace
 
-// a form over rows resident on `device` (n x D, complete), the outputs the host's
-int rows_device_entry(Form form, int device, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits, const float *eigvec,
-                      int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out) {
+// vaqhip_refiner.cpp calls this over its resident rows (n x D on `device`, complete), its lock held: a form over rows
+// resident on `device`, the outputs the host's
+int vaqhost::fit_codebooks_rows_device(CodebookForm form, int device, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits,
+                                       const float *eigvec, int max_iter, float *centroids_out, int *iters_out,
+                                       int *nan_rows_out) {
   Plans p;
   if (int rc = plan_call(form, d_X.p, n, D, M, bits, max_iter, centroids_out, &p)) return rc;
   DeviceGuard g(device);
   if (!g.ok) return fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed (no CPU path)", device);
   return fit_to_host(d_X, n, D, p, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
 }
-}  // namespace
-
-// vaqhip_refiner.cpp calls this over its resident rows (n x D on `device`, complete), its lock held
-int vaqhost::fit_codebooks_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits,
-                                       const float *eigvec, int max_iter, float *centroids_out, int *iters_out,
-                                       int *nan_rows_out) {
-  return rows_device_entry(FLAT, device, d_X, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
-}
-
-// the hierarchical twin (vaqhip_refiner_fit_codebooks_hier)
-int vaqhost::fit_codebooks_hier_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits,
-                                            const float *eigvec, int max_iter, float *centroids_out, int *iters_out,
-                                            int *nan_rows_out) {
-  return rows_device_entry(HIER, device, d_X, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
-}
-
-// the binary twin (vaqhip_refiner_fit_codebooks_bin)
-int vaqhost::fit_codebooks_bin_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits,
-                                           const float *eigvec, int max_iter, float *centroids_out, int *iters_out,
-                                           int *nan_rows_out) {
-  return rows_device_entry(BIN, device, d_X, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
-}
 
 extern "C" {
 
 int vaqhip_fit_codebooks_hier(int device_id, const float *X, int64_t n, int D, int M, const int *bits, const float *eigvec,
                               int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out) {
-  return fit_host_entry(device_id, vaq::RowsRef{X, 4}, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out, HIER);
+  return fit_host_entry(Form::HIER, device_id, vaq::RowsRef{X, 4}, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
 }
 int vaqhip_fit_codebooks_hier_u8(int device_id, const uint8_t *X, int64_t n, int D, int M, const int *bits, const float *eigvec,
                                  int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out) {
-  return fit_host_entry(device_id, vaq::RowsRef{X, 1}, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out, HIER);
+  return fit_host_entry(Form::HIER, device_id, vaq::RowsRef{X, 1}, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
 }
 int vaqhip_fit_codebooks_hier_device(int device_id, const float *d_X, int64_t n, int D, int M, const int *bits,
                                      const float *d_eigvec, int max_iter, float *d_centroids_out, int *iters_out,
                                      int *nan_rows_out, void *stream) {
-  return fit_device_entry(device_id, vaq::RowsRef{d_X, 4}, n, D, M, bits, d_eigvec, max_iter, d_centroids_out, iters_out,
-                          nan_rows_out, stream, HIER);
+  return fit_device_entry(Form::HIER, device_id, vaq::RowsRef{d_X, 4}, n, D, M, bits, d_eigvec, max_iter, d_centroids_out, iters_out,
+                          nan_rows_out, stream);
 }
 int vaqhip_fit_codebooks_hier_u8_device(int device_id, const uint8_t *d_X, int64_t n, int D, int M, const int *bits,
                                         const float *d_eigvec, int max_iter, float *d_centroids_out, int *iters_out,
                                         int *nan_rows_out, void *stream) {
-  return fit_device_entry(device_id, vaq::RowsRef{d_X, 1}, n, D, M, bits, d_eigvec, max_iter, d_centroids_out, iters_out,
-                          nan_rows_out, stream, HIER);
+  return fit_device_entry(Form::HIER, device_id, vaq::RowsRef{d_X, 1}, n, D, M, bits, d_eigvec, max_iter, d_centroids_out, iters_out,
+                          nan_rows_out, stream);
 }
 int vaqhip_last_fit_codebooks_hier_timing(vaqhip_fit_codebooks_hier_timing *out) {
   if (!out) return fail(VAQHIP_EINVAL, "null pointer");
@@ -415,23 +302,23 @@ int vaqhip_last_fit_codebooks_hier_timing(vaqhip_fit_codebooks_hier_timing *out)
 
 int vaqhip_fit_codebooks_bin(int device_id, const float *X, int64_t n, int D, int M, const int *bits, const float *eigvec,
                              int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out) {
-  return fit_host_entry(device_id, vaq::RowsRef{X, 4}, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out, BIN);
+  return fit_host_entry(Form::BIN, device_id, vaq::RowsRef{X, 4}, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
 }
 int vaqhip_fit_codebooks_bin_u8(int device_id, const uint8_t *X, int64_t n, int D, int M, const int *bits, const float *eigvec,
                                 int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out) {
-  return fit_host_entry(device_id, vaq::RowsRef{X, 1}, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out, BIN);
+  return fit_host_entry(Form::BIN, device_id, vaq::RowsRef{X, 1}, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
 }
 int vaqhip_fit_codebooks_bin_device(int device_id, const float *d_X, int64_t n, int D, int M, const int *bits,
                                     const float *d_eigvec, int max_iter, float *d_centroids_out, int *iters_out,
                                     int *nan_rows_out, void *stream) {
-  return fit_device_entry(device_id, vaq::RowsRef{d_X, 4}, n, D, M, bits, d_eigvec, max_iter, d_centroids_out, iters_out,
-                          nan_rows_out, stream, BIN);
+  return fit_device_entry(Form::BIN, device_id, vaq::RowsRef{d_X, 4}, n, D, M, bits, d_eigvec, max_iter, d_centroids_out, iters_out,
+                          nan_rows_out, stream);
 }
 int vaqhip_fit_codebooks_bin_u8_device(int device_id, const uint8_t *d_X, int64_t n, int D, int M, const int *bits,
                                        const float *d_eigvec, int max_iter, float *d_centroids_out, int *iters_out,
                                        int *nan_rows_out, void *stream) {
-  return fit_device_entry(device_id, vaq::RowsRef{d_X, 1}, n, D, M, bits, d_eigvec, max_iter, d_centroids_out, iters_out,
-                          nan_rows_out, stream, BIN);
+  return fit_device_entry(Form::BIN, device_id, vaq::RowsRef{d_X, 1}, n, D, M, bits, d_eigvec, max_iter, d_centroids_out, iters_out,
+                          nan_rows_out, stream);
 }
 int vaqhip_last_fit_codebooks_bin_timing(vaqhip_fit_codebooks_bin_timing *out) {
   if (!out) return fail(VAQHIP_EINVAL, "null pointer");
@@ -446,22 +333,22 @@ int vaqhip_fit_codebooks_bin_set_sums(int mode) {
 
 int vaqhip_fit_codebooks(int device_id, const float *X, int64_t n, int D, int M, const int *bits, const float *eigvec,
                          int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out) {
-  return fit_host_entry(device_id, vaq::RowsRef{X, 4}, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
+  return fit_host_entry(Form::FLAT, device_id, vaq::RowsRef{X, 4}, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
 }
 int vaqhip_fit_codebooks_u8(int device_id, const uint8_t *X, int64_t n, int D, int M, const int *bits, const float *eigvec,
                             int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out) {
-  return fit_host_entry(device_id, vaq::RowsRef{X, 1}, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
+  return fit_host_entry(Form::FLAT, device_id, vaq::RowsRef{X, 1}, n, D, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
 }
 int vaqhip_fit_codebooks_device(int device_id, const float *d_X, int64_t n, int D, int M, const int *bits,
                                 const float *d_eigvec, int max_iter, float *d_centroids_out, int *iters_out,
                                 int *nan_rows_out, void *stream) {
-  return fit_device_entry(device_id, vaq::RowsRef{d_X, 4}, n, D, M, bits, d_eigvec, max_iter, d_centroids_out, iters_out,
+  return fit_device_entry(Form::FLAT, device_id, vaq::RowsRef{d_X, 4}, n, D, M, bits, d_eigvec, max_iter, d_centroids_out, iters_out,
                           nan_rows_out, stream);
 }
 int vaqhip_fit_codebooks_u8_device(int device_id, const uint8_t *d_X, int64_t n, int D, int M, const int *bits,
                                    const float *d_eigvec, int max_iter, float *d_centroids_out, int *iters_out,
                                    int *nan_rows_out, void *stream) {
-  return fit_device_entry(device_id, vaq::RowsRef{d_X, 1}, n, D, M, bits, d_eigvec, max_iter, d_centroids_out, iters_out,
+  return fit_device_entry(Form::FLAT, device_id, vaq::RowsRef{d_X, 1}, n, D, M, bits, d_eigvec, max_iter, d_centroids_out, iters_out,
                           nan_rows_out, stream);
 }
 
@@ -474,7 +361,7 @@ int vaqhip_internal_fit_codebooks_check(const void *X, int64_t n, int D, int M, 
 int vaqhip_internal_fit_codebooks_rows_device(int device, const void *d_X, int elem, int64_t n, int D, int M,
                                               const int *bits, const float *eigvec, int max_iter, float *centroids_out,
                                               int *iters_out, int *nan_rows_out) {
-  return fit_codebooks_rows_device(device, vaq::RowsRef{d_X, elem}, n, D, M, bits, eigvec, max_iter, centroids_out,
+  return fit_codebooks_rows_device(Form::FLAT, device, vaq::RowsRef{d_X, elem}, n, D, M, bits, eigvec, max_iter, centroids_out,
                                    iters_out, nan_rows_out);
 }
 int vaqhip_internal_fit_codebooks_timing_on(void) { return g_cb_timing; }

@@ -193,16 +193,12 @@ int encode_host_entry(vaqhip_index *ix, const EncodeRule &rule, vaq::RowsRef X, 
 // rows (n x D on the index's device, complete); takes the index's lock itself
 int learn_rows_device(vaqhip_index *ix, vaq::RowsRef d_X, int64_t n, int projected, float ratio, float *offsets_out,
                       float *scale_out);
-// vaqhip_codebooks.cpp: vaqhip_fit_codebooks[_u8]'s body from the upload on, which vaqhip_refiner.cpp calls over its
-// resident rows (n x D on `device`, complete); eigvec and the outputs are the host's
-int fit_codebooks_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits, const float *eigvec,
-                              int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out);
-// the same for vaqhip_fit_codebooks_hier[_u8] (subspaces above 8 bits in two stages)
-int fit_codebooks_hier_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits, const float *eigvec,
-                                   int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out);
-// and for vaqhip_fit_codebooks_bin[_u8] (subspaces above 8 bits as a tree of 2-centre fits)
-int fit_codebooks_bin_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits, const float *eigvec,
-                                  int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out);
+// vaqhip_codebooks.cpp: vaqhip_fit_codebooks[_u8]'s body from the upload on -- or, by `form`, that of the hierarchical
+// (subspaces above 8 bits in two stages) or the binary form (as a tree of 2-centre fits) --, which vaqhip_refiner.cpp
+// calls over its resident rows (n x D on `device`, complete); eigvec and the outputs are the host's
+enum class CodebookForm { FLAT = 0, HIER, BIN };
+int fit_codebooks_rows_device(CodebookForm form, int device, vaq::RowsRef d_X, int64_t n, int D, int M, const int *bits,
+                              const float *eigvec, int max_iter, float *centroids_out, int *iters_out, int *nan_rows_out);
 // vaqhip_train.cpp: vaqhip_train_moment's and vaqhip_train_rotation's bodies over rows resident on `device`, which
 // vaqhip_refiner.cpp calls over its resident rows (complete); the outputs are the host's
 int train_moment_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, double *cov_out, float *cov_f_out);

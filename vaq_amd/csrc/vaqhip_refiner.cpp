@@ -308,36 +308,30 @@ int vaqhip_learn_quantization_from_refiner(vaqhip_index *ix, vaqhip_refiner *r, 
   return learn_rows_device(ix, r->rows.rows(), r->N, 0, sample_ratio, offsets_out, scale_out);
 }
 
-// the subspace codebooks over the resident rows, read in place (vaqhip_codebooks.cpp does the rest; the refiner's lock
-// keeps the rows where they are meanwhile)
-int vaqhip_refiner_fit_codebooks(vaqhip_refiner *r, int M, const int *bits, const float *eigvec, int max_iter,
+// the subspace codebooks over the resident rows, read in place, by any form of the fit (vaqhip_codebooks.cpp does the
+// rest; the refiner's lock keeps the rows where they are meanwhile)
+static int refiner_fit_codebooks(CodebookForm form, vaqhip_refiner *r, int M, const int *bits, const float *eigvec, int max_iter,
                                  float *centroids_out, int *iters_out, int *nan_rows_out) {
   if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
   std::lock_guard<std::mutex> lk(r->mu);
   if (r->N == 0) return fail(VAQHIP_ESTATE, "the refiner holds no rows: vaqhip_refiner_set_rows first");
   // (set_rows and add_rows copy synchronously: the rows are complete)
-  return fit_codebooks_rows_device(r->device, r->rows.rows(), r->N, r->D, M, bits, eigvec, max_iter, centroids_out,
+  return fit_codebooks_rows_device(form, r->device, r->rows.rows(), r->N, r->D, M, bits, eigvec, max_iter, centroids_out,
                                    iters_out, nan_rows_out);
 }
-
+int vaqhip_refiner_fit_codebooks(vaqhip_refiner *r, int M, const int *bits, const float *eigvec, int max_iter,
+                                 float *centroids_out, int *iters_out, int *nan_rows_out) {
+  return refiner_fit_codebooks(CodebookForm::FLAT, r, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
+}
 // the hierarchical form of the same (subspaces above 8 bits in two stages)
 int vaqhip_refiner_fit_codebooks_hier(vaqhip_refiner *r, int M, const int *bits, const float *eigvec, int max_iter,
                                       float *centroids_out, int *iters_out, int *nan_rows_out) {
-  if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
-  std::lock_guard<std::mutex> lk(r->mu);
-  if (r->N == 0) return fail(VAQHIP_ESTATE, "the refiner holds no rows: vaqhip_refiner_set_rows first");
-  return fit_codebooks_hier_rows_device(r->device, r->rows.rows(), r->N, r->D, M, bits, eigvec, max_iter, centroids_out,
-                                        iters_out, nan_rows_out);
+  return refiner_fit_codebooks(CodebookForm::HIER, r, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
 }
-
 // the binary-tree form of the same (subspaces above 8 bits as a tree of 2-centre fits)
 int vaqhip_refiner_fit_codebooks_bin(vaqhip_refiner *r, int M, const int *bits, const float *eigvec, int max_iter,
                                      float *centroids_out, int *iters_out, int *nan_rows_out) {
-  if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
-  std::lock_guard<std::mutex> lk(r->mu);
-  if (r->N == 0) return fail(VAQHIP_ESTATE, "the refiner holds no rows: vaqhip_refiner_set_rows first");
-  return fit_codebooks_bin_rows_device(r->device, r->rows.rows(), r->N, r->D, M, bits, eigvec, max_iter, centroids_out,
-                                       iters_out, nan_rows_out);
+  return refiner_fit_codebooks(CodebookForm::BIN, r, M, bits, eigvec, max_iter, centroids_out, iters_out, nan_rows_out);
 }
 
 // the training front half over the resident rows, read in place (vaqhip_train.cpp does the rest)

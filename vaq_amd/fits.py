@@ -77,9 +77,10 @@ def fit_codebooks_u8(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray
     return _fit_codebooks(X, M, bits, eigvec, max_iter, device, devices, True)
 
 
-def _fit_codebooks_hier(X, M, bits, eigvec, max_iter, device, u8: bool):
+def _fit_codebooks_form(form: str, X, M, bits, eigvec, max_iter, device, u8: bool):
+    """A wide form of the fit ("hier" or "bin"): vaqhip_fit_codebooks_<form>[_u8]."""
     X = _fit_rows(X, u8)
-    fn = "vaqhip_fit_codebooks_hier" + ("_u8" if u8 else "")
+    fn = "vaqhip_fit_codebooks_" + form + ("_u8" if u8 else "")
     return _fit_codebooks_call(X.shape[1], M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn: getattr(L, fn)(
         int(device), _ptr(X), X.shape[0], X.shape[1], int(M), b, e, it, c, i, nn))
 
@@ -91,13 +92,13 @@ def fit_codebooks_hier(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarr
     rows split by nearest centre (squaredNorm, no sqrt), then 1 << (bits - 7) centres inside each group.  Subspaces of
     at most 8 bits, and a call without any wider one, are fit_codebooks's bit for bit.  Returns what fit_codebooks
     returns; iterations[s] is the largest count among a hierarchical subspace's 129 fits.  Single device only."""
-    return _fit_codebooks_hier(X, M, bits, eigvec, max_iter, device, False)
+    return _fit_codebooks_form("hier", X, M, bits, eigvec, max_iter, device, False)
 
 
 def fit_codebooks_hier_u8(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25,
                           device: int = 0):
     """fit_codebooks_hier from byte rows (vaqhip_fit_codebooks_hier_u8): its result on X.astype(float32), bit for bit."""
-    return _fit_codebooks_hier(X, M, bits, eigvec, max_iter, device, True)
+    return _fit_codebooks_form("hier", X, M, bits, eigvec, max_iter, device, True)
 
 
 def last_fit_codebooks_hier_timing() -> dict:
@@ -108,13 +109,6 @@ def last_fit_codebooks_hier_timing() -> dict:
     return _struct_dict(t)
 
 
-def _fit_codebooks_bin(X, M, bits, eigvec, max_iter, device, u8: bool):
-    X = _fit_rows(X, u8)
-    fn = "vaqhip_fit_codebooks_bin" + ("_u8" if u8 else "")
-    return _fit_codebooks_call(X.shape[1], M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn: getattr(L, fn)(
-        int(device), _ptr(X), X.shape[0], X.shape[1], int(M), b, e, it, c, i, nn))
-
-
 def fit_codebooks_bin(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25,
                       device: int = 0):
     """vaqhip_fit_codebooks_bin: fit_codebooks with every subspace above 8 bits fitted as a binary tree, as VAQ::train
@@ -123,13 +117,13 @@ def fit_codebooks_bin(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarra
     than it needs centres is fitted flat and ends its branch.  No group size is refused: the form for skewed data.
     Subspaces of at most 8 bits, and a call without any wider one, are fit_codebooks's bit for bit.  Returns what
     fit_codebooks returns; iterations[s] is the largest count among a binary subspace's fits.  Single device only."""
-    return _fit_codebooks_bin(X, M, bits, eigvec, max_iter, device, False)
+    return _fit_codebooks_form("bin", X, M, bits, eigvec, max_iter, device, False)
 
 
 def fit_codebooks_bin_u8(X, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25,
                          device: int = 0):
     """fit_codebooks_bin from byte rows (vaqhip_fit_codebooks_bin_u8): its result on X.astype(float32), bit for bit."""
-    return _fit_codebooks_bin(X, M, bits, eigvec, max_iter, device, True)
+    return _fit_codebooks_form("bin", X, M, bits, eigvec, max_iter, device, True)
 
 
 def last_fit_codebooks_bin_timing() -> dict:

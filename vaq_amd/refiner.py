@@ -204,17 +204,21 @@ class VaqRefiner(_RefinerBase):
         return _train_rotation_call(self.D, M, lambda L, e, v, b, h: L.vaqhip_refiner_train_rotation(
             self._h, int(M), int(bit_budget), int(min_bits), int(max_bits), float(percent_var), e, v, b, h))
 
+    def _fit_codebooks_form(self, form: str, M, bits, eigvec, max_iter):
+        """A wide form of the fit ("hier" or "bin") over the rows held: vaqhip_refiner_fit_codebooks_<form>."""
+        fn = "vaqhip_refiner_fit_codebooks_" + form
+        return _fit_codebooks_call(self.D, M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn: getattr(L, fn)(
+            self._h, int(M), b, e, it, c, i, nn))
+
     def fit_codebooks_hier(self, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25):
         """fit_codebooks_hier() over the RAW rows held, float or byte, read where they are
         (vaqhip_refiner_fit_codebooks_hier): subspaces above 8 bits in two stages.  Single device only."""
-        return _fit_codebooks_call(self.D, M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn:
-                                   L.vaqhip_refiner_fit_codebooks_hier(self._h, int(M), b, e, it, c, i, nn))
+        return self._fit_codebooks_form("hier", M, bits, eigvec, max_iter)
 
     def fit_codebooks_bin(self, M: int, bits: Sequence[int], eigvec: Optional[np.ndarray] = None, max_iter: int = 25):
         """fit_codebooks_bin() over the RAW rows held, float or byte, read where they are
         (vaqhip_refiner_fit_codebooks_bin): subspaces above 8 bits as a tree of 2-centre fits.  Single device only."""
-        return _fit_codebooks_call(self.D, M, bits, eigvec, max_iter, lambda L, b, e, it, c, i, nn:
-                                   L.vaqhip_refiner_fit_codebooks_bin(self._h, int(M), b, e, it, c, i, nn))
+        return self._fit_codebooks_form("bin", M, bits, eigvec, max_iter)
 
     def train(self, M: int, bit_budget: int, min_bits: int, max_bits: int, percent_var: float = 1.0, max_iter: int = 25):
         """train_rotation() then fit_codebooks() over the rows held: (eigvec, bits, centroids), as vaq_amd.train."""
