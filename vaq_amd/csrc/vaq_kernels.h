@@ -289,6 +289,9 @@ bool scan_bf_supported(int layout, int M, int qb, int ea, int n_buckets, int seq
 // `pool`: slots of the k-min pool (ScanParams::bf_pool), a multiple of 64 within scan_bf_pool_range(k)
 size_t scan_bf_lds_bytes(int layout, int M, int lut_entries, int pool, int nwaves, int n_buckets, int bf_carry);
 void scan_bf_pool_range(int k, int *lo, int *hi);
+// dwords the code buffer must hold beyond its padded rows: the best-first form starts a unit on a 128-byte
+// line, and the unit's last wave step may reach that far past the end (vaq_scan_bf.h, ALIGN_ROWS)
+int64_t scan_bf_slack_words(int layout, int M);
 // in_final != 0: inputs use the API's -1 / FLT_MAX convention for empty slots
 // candidate i of list l of query q sits at l*list_stride + q*query_stride + i
 // labels == nullptr: no result is written (only thr_out is wanted).

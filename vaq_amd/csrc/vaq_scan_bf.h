@@ -270,6 +270,15 @@ template <int M> struct BfBytes {
   static constexpr int WPR = Item::WPR;
   static constexpr int QCW = (M <= 16) ? WPR - 1 : 0;
   static constexpr bool HAS_TAIL = WPR > 1;
+  // A unit's first item starts on a 128-byte line, not on a whole wave step: the lanes' 16-byte loads
+  // coalesce line by line, and a bucket that starts inside a step then rarely spills into one step more.
+  // The last step of a unit may read up to 64 ROWS - ALIGN_ROWS rows past the padded end of the rows:
+  // the code buffer carries that slack (scan_bf_slack_words).
+  static constexpr int ALIGN_ROWS = 128 / M;
+  static_assert(ALIGN_ROWS % ROWS == 0 && (64 * ROWS) % ALIGN_ROWS == 0, "items stay 16-byte aligned, steps whole lines");
+  // The overflow bisection of a round (rare) derives what it needs from the thread number in place, so that
+  // nothing of it stays live across the scan: at the 64-VGPR cap the 8-byte kernel spilled it to scratch.
+  static constexpr bool BISECT_IN_PLACE = true;
   // No test after the first two terms: a byte costs one instruction to take out of its dword, and on the
   // cache-resident databases this form serves 41 % of the rows of a visited bucket pass that test (C2) --
   // some lane of nearly every wave step does, so the wave looks the other two terms up anyway and the
@@ -344,6 +353,8 @@ template <int W, bool CARRY> struct BfBits {
     uint32_t w[W];
   };
   static constexpr int ROWS = 1;
+  static constexpr int ALIGN_ROWS = TILE_ROWS;  // a wave step IS a tile
+  static constexpr bool BISECT_IN_PLACE = false;  // (its kernels spill inside the scan whatever that path does; in place measured C3 about 1 % slower)
   static constexpr int QCW = CARRY ? 1 : 0;
   static constexpr bool HAS_TAIL = true;
   static constexpr bool TEST_A = true;  // (taking a field out of a packed row costs several instructions: C3 0.92 ms with the test, 1.04 without)
@@ -446,6 +457,7 @@ __device__ __forceinline__ void scan_bf_body(const ScanParams &p) {
   constexpr int QCW = Pol::QCW;
   constexpr int WSTEP = 64 * ROWS;  // rows per wave step
   constexpr int SEG_ROWS = BF_SEG_STEPS * WSTEP;
+  constexpr int ALIGN = Pol::ALIGN_ROWS;  // units start on a multiple of it (units_of, geometry)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x, nthreads = blockDim.x;
 #ifdef VAQ_BF_VECTOR_WAVE
@@ -630,7 +642,7 @@ __device__ __forceinline__ void scan_bf_body(const ScanParams &p) {
     const int b = (int)(key & idx_mask);
     const int s0 = bstart[b] > r0 ? bstart[b] : r0;
     const int e0 = bstart[b + 1] < r1 ? bstart[b + 1] : r1;
-    return (e0 - (s0 & ~(WSTEP - 1)) + SEG_ROWS - 1) / SEG_ROWS;
+    return (e0 - (s0 & ~(ALIGN - 1)) + SEG_ROWS - 1) / SEG_ROWS;
   };
   // every bucket's key, kept in LDS (the waves' buffers, not yet in use) until the first round has
   // picked its buckets; a thread only ever reads back the entries it wrote
@@ -977,21 +989,32 @@ __device__ __forceinline__ void scan_bf_body(const ScanParams &p) {
       // (any bound that lets between half a round and a whole round in will do; three counters
       //  in rotation: one barrier per step)
       unsigned lo = 0u, hi = thr_bits | idx_mask;  // count(key <= lo) <= cap is maintained
+      // (Pol::BISECT_IN_PLACE: this rarely taken path computes what it derives from the thread number HERE.
+      //  Hoisted out of the round loop, its loop-invariant addresses and a 64-bit pair of zeros for the
+      //  counters' reset cost registers the scan has none to spare of -- they were spilled to scratch, and a
+      //  kernel with scratch pays its set-up at every wave launch.  The empty asm hides from the compiler that
+      //  tb is tid; DESIGN.md section 4 says how to re-check the resource report.)
+      int tb = tid;
+      if (Pol::BISECT_IN_PLACE) asm volatile("" : "+v"(tb));
       __syncthreads();
-      if (tid == 0) { sh_rot[0] = 0u; sh_rot[1] = 0u; sh_rot[2] = 0u; }
+      if (Pol::BISECT_IN_PLACE) {
+        if (tb < 3) sh_rot[tb] = 0u;  // (one dword each)
+      } else if (tid == 0) {
+        sh_rot[0] = 0u; sh_rot[1] = 0u; sh_rot[2] = 0u;
+      }
       __syncthreads();
       int it = 0;
       while (lo < hi) {
         const unsigned mid = lo + ((hi - lo) >> 1) + 1u;  // upper middle: lo < mid <= hi
         int c = 0;
 #pragma unroll 1
-        for (int b = tid; b < K0; b += nthreads) {
+        for (int b = tb; b < K0; b += nthreads) {
           const unsigned key = kall[b];
           c += (eligible(key) && key <= mid) ? 1 : 0;
         }
         unsigned *cur = sh_rot + (it % 3);
         if (c) atomicAdd(cur, (unsigned)c);
-        if (tid == 0) sh_rot[(it + 1) % 3] = 0u;  // (last read two steps ago)
+        if (tb == 0) sh_rot[(it + 1) % 3] = 0u;  // (last read two steps ago)
         __syncthreads();
         const int tot = (int)*cur;
         it++;
@@ -1004,10 +1027,10 @@ __device__ __forceinline__ void scan_bf_body(const ScanParams &p) {
       }
       hi_key = lo;
       __syncthreads();
-      if (tid == 0) *sh_cnt = 0u;
+      if (tb == 0) *sh_cnt = 0u;
       __syncthreads();
 #pragma unroll 1
-      for (int b = tid; b < K0; b += nthreads) {
+      for (int b = tb; b < K0; b += nthreads) {
         const unsigned key = kall[b];
         if (eligible(key) && key <= hi_key) kuns[atomicAdd(sh_cnt, 1u)] = key;
       }
@@ -1108,12 +1131,12 @@ __device__ __forceinline__ void scan_bf_body(const ScanParams &p) {
       const int bs = __builtin_amdgcn_readfirstlane(bsr > r0 ? bsr : r0);
       const int bend = __builtin_amdgcn_readfirstlane(ber < r1 ? ber : r1);
       const int j = tt - __builtin_amdgcn_readfirstlane(cum[ii]);
-      const int al = bs & ~(WSTEP - 1);
+      const int al = bs & ~(ALIGN - 1);
       pos = al + j * SEG_ROWS;
       if (pos < bs) pos = bs;
       be = al + (j + 1) * SEG_ROWS;
       if (be > bend) be = bend;
-      base0 = pos & ~(WSTEP - 1);
+      base0 = pos & ~(ALIGN - 1);
       nst = (be - base0 + WSTEP - 1) / WSTEP;
     };
     // BF_RING code items in flight per wave, ACROSS units: while the last steps of a unit are
@@ -1407,6 +1430,9 @@ __device__ __forceinline__ void scan_bf_body(const ScanParams &p) {
   }
 #endif
 }
+
+// rows the last step of a unit may read past the wave-step-rounded end of the rows
+template <typename Pol> constexpr int bf_overread_rows() { return 64 * Pol::ROWS - Pol::ALIGN_ROWS; }
 
 // bytes of LDS of the byte-code best-first kernel and its launch (vaq_scan_bf.hip)
 hipError_t launch_scan_bf(const ScanParams &p, int grid, hipStream_t st);

@@ -42,8 +42,25 @@ size_t scan_bf_lds_bytes(int layout, int M, int lut_entries, int pool, int nwave
                       scan_bf_queue_words(layout, M, bf_carry), layout == LAYOUT_BYTES ? 0 : VAQ_BF_MAX_SUBS);
 }
 
+// the byte-row widths that have a kernel: ONE list for scan_bf_supported, the code buffer's slack and the launch
+#define VAQ_BF_BYTE_WIDTHS(X) X(8) X(16) X(32)
+
+int64_t scan_bf_slack_words(int layout, int M) {
+  if (layout != LAYOUT_BYTES) return 0;  // (bit-packed rows: units start on whole tiles)
+#define VAQ_BF_SLACK(A) if (M == A) return (int64_t)bf_overread_rows<BfBytes<A>>() * (A / 4);
+  VAQ_BF_BYTE_WIDTHS(VAQ_BF_SLACK)
+#undef VAQ_BF_SLACK
+  return 0;  // (no best-first kernel for this width: nothing reads past the end)
+}
+
 bool scan_bf_supported(int layout, int M, int qb, int ea, int n_buckets, int seq) {
-  if (layout == LAYOUT_BYTES && M != 8 && M != 16 && M != 32) return false;
+  if (layout == LAYOUT_BYTES) {
+    bool has_kernel = false;
+#define VAQ_BF_HAS(A) has_kernel = has_kernel || M == A;
+    VAQ_BF_BYTE_WIDTHS(VAQ_BF_HAS)
+#undef VAQ_BF_HAS
+    if (!has_kernel) return false;
+  }
   if (layout == LAYOUT_BITS && (M < 4 || M % 4 != 0)) return false;
   return qb == 1 && ea == EA_QUEUE && !seq && n_buckets >= 16 && n_buckets <= BF_MAX_BUCKETS &&
          (n_buckets & (n_buckets - 1)) == 0;
@@ -70,9 +87,9 @@ hipError_t launch_scan_bf(const ScanParams &p, int grid, hipStream_t st) {
   const size_t lds = scan_bf_lds_bytes(p.layout, p.M, p.lut_lds_entries, p.bf_pool, p.nwaves, p.n_buckets, p.bf_carry);
   if (p.layout == LAYOUT_BYTES) {
     switch (p.M) {
-    case 8:  VAQ_BF_M(8)
-    case 16: VAQ_BF_M(16)
-    case 32: VAQ_BF_M(32)
+#define VAQ_BF_CASE(A) case A: VAQ_BF_M(A)
+    VAQ_BF_BYTE_WIDTHS(VAQ_BF_CASE)
+#undef VAQ_BF_CASE
     default: return hipErrorInvalidValue;
     }
   }

@@ -20,7 +20,8 @@ int build_rows(vaqhip_index *ix, const uint16_t *d_u16, int64_t N, hipStream_t s
   const int step = vaq::scan_wg_step_rows(ix->layout, ix->M);
   const int64_t padded = std::max<int64_t>(step, ((N + step - 1) / step) * step);
   const int64_t words = vaq::packed_words(padded, ix->M, ix->layout, ix->W);
-  HIP_TRY(ix->d_codes.ensure((size_t)words * sizeof(uint32_t)));
+  // (behind the padded rows: what the best-first form's last wave step may read, never use -- not written)
+  HIP_TRY(ix->d_codes.ensure((size_t)(words + vaq::scan_bf_slack_words(ix->layout, ix->M)) * sizeof(uint32_t)));
   const vaq::SubDesc *dsub = ix->d_sub.as<vaq::SubDesc>();
   int shift = 0, bt = 0, K0 = 1, fine = 0;
   if (ix->ti_T > 0) {
@@ -164,7 +165,7 @@ int append_rows_bucketed(vaqhip_index *ix, const uint16_t *d_new, int64_t n_new,
   // the merged buffers
   const int64_t padded = std::max<int64_t>(step, ((N + step - 1) / step) * step);
   const int64_t words = vaq::packed_words(padded, ix->M, ix->layout, ix->W);
-  HIP_TRY(out_codes.ensure((size_t)words * sizeof(uint32_t)));
+  HIP_TRY(out_codes.ensure((size_t)(words + vaq::scan_bf_slack_words(ix->layout, ix->M)) * sizeof(uint32_t)));
   HIP_TRY(out_perm.ensure((size_t)N * sizeof(uint32_t)));
   HIP_TRY(hipMemsetAsync(out_codes.p, 0, (size_t)words * sizeof(uint32_t), st));  // (the padding rows must be zero)
   HIP_TRY(vaq::launch_merge_rows(ix->d_codes.as<uint32_t>(), ix->d_perm.as<uint32_t>(), d_old_start,
