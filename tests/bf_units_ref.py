@@ -7,14 +7,14 @@ slack the library allocates behind them (Policy.slack_rows).  tests/test_bf_unit
 that these tile every bucket and that the over-read never exceeds the slack; the same functions say what each case
 of tests/test_bf_unit_widths.py plants.  Every function takes Python ints or numpy integer arrays.
 
-The key rule (bucket_keys) is vaqhip_codes.cpp's build_rows and vaq_kernels.hip's first_code_keys_kernel."""
+The key rule (bucket_keys) is vaqhip_codes.cpp's build_rows and vaq_codes.hip's first_code_keys_kernel."""
 import numpy as np
 
 BF_SEG_STEPS = 64        # vaq_scan_bf.h:35, :62  (VAQ_BF_SEG: wave steps per work unit)
 BF_MAX_BUCKETS = 1024    # vaq_scan_bf.h:67
 BF_ROUND_BUCKETS = 128   # vaq_scan_bf.h:70, :72  (VAQ_BF_ROUND: buckets one round orders and scans)
-TILE_ROWS = 64           # vaq_kernels.h:38
-SCAN_MAX_THREADS = 1024  # vaq_scan.h:329  (SCAN_MAX_WAVES = 16, vaq_kernels.h:40, times 64)
+TILE_ROWS = 64           # vaq_common.h
+SCAN_MAX_THREADS = 1024  # vaq_scan.h  (SCAN_MAX_WAVES = 16, vaq_scan_params.h, times 64)
 
 
 class Policy:
@@ -26,7 +26,7 @@ class Policy:
         self.WSTEP = 64 * rows                 # vaq_scan_bf.h:458  rows per wave step
         self.ALIGN_ROWS = align_rows           # Pol::ALIGN_ROWS: units start on a multiple of it (:460)
         self.SEG_ROWS = BF_SEG_STEPS * self.WSTEP  # vaq_scan_bf.h:459
-        self.step_rows = step_rows             # scan_wg_step_rows(), vaq_kernels.hip:963-966
+        self.step_rows = step_rows             # scan_wg_step_rows(), vaq_scan_launch.hip
         self.slack_rows = slack_rows           # scan_bf_slack_words() / dwords per row, vaq_scan_bf.hip:48-54
         assert align_rows % rows == 0 and self.WSTEP % align_rows == 0  # vaq_scan_bf.h:278
         assert step_rows % self.WSTEP == 0
@@ -49,7 +49,7 @@ def bytes_policy(M):
     item_bytes = 16 if M < 16 else M           # :268  (VAQ_BF_M8_ITEM_BYTES = 16, :247)
     rows = item_bytes // M                     # :251  BfBytesItem::ROWS
     align = 128 // M                           # :277  a 128-byte line
-    step = SCAN_MAX_THREADS * (16 // M if M < 16 else 1)  # vaq_kernels.hip:963, :966
+    step = SCAN_MAX_THREADS * (16 // M if M < 16 else 1)  # rows_per_item(), scan_wg_step_rows(), vaq_scan_launch.hip
     # vaq_scan_bf.hip:50: bf_overread_rows<BfBytes<M>>() * (M / 4) dwords, i.e. that many rows of M / 4 dwords
     return Policy(f"bytes{M}", rows, align, step, 64 * rows - align)
 
@@ -120,7 +120,7 @@ def key_shape(bucket_bits, bits0=8, bits1=8):
 
 
 def bucket_keys(codes, bucket_bits, bits0=8, bits1=8):
-    """first_code_keys_kernel, vaq_kernels.hip:495-496 (without the fine bits, which order rows inside a bucket)."""
+    """first_code_keys_kernel, vaq_codes.hip (without the fine bits, which order rows inside a bucket)."""
     shift, bt = key_shape(bucket_bits, bits0, bits1)
     key = codes[:, 0].astype(np.int64) >> shift
     if bt > 0:

@@ -9,7 +9,7 @@
 #include <cstring>
 #include <vector>
 
-#include "vaq_kernels.h"
+#include "vaq_front.h"
 
 #define HIP_OK(x)                                                                      \
   do {                                                                                 \

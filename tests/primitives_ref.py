@@ -1,5 +1,5 @@
-"""Plain numpy references for the first-round primitives of vaq_kernels.hip (projection, encoder, the
-old refine, the k-min merge) and the input generators the edge tests share.
+"""Plain numpy references for the first-round primitives of vaq_front.hip, vaq_codes.hip and vaq_merge.hip
+(projection, encoder, the old refine, the k-min merge) and the input generators the edge tests share.
 
 Every operation has two references:
 

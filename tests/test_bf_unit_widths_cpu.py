@@ -29,7 +29,7 @@ def test_restated_constants_match_the_sources():
     csrc = os.path.join(ROOT, "vaq_amd", "csrc")
     h = open(os.path.join(csrc, "vaq_scan_bf.h")).read()
     hip = open(os.path.join(csrc, "vaq_scan_bf.hip")).read()
-    k = open(os.path.join(csrc, "vaq_kernels.hip")).read()
+    k = open(os.path.join(csrc, "vaq_scan_launch.hip")).read()
     for text, pat in ((h, r"#define VAQ_BF_SEG %d\b" % U.BF_SEG_STEPS), (h, r"#define VAQ_BF_ROUND %d\b" % U.BF_ROUND_BUCKETS),
                       (h, r"constexpr int BF_MAX_BUCKETS = %d;" % U.BF_MAX_BUCKETS),
                       (h, r"#define VAQ_BF_M8_ITEM_BYTES 16\b"),

@@ -14,9 +14,9 @@ from helpers import assert_topk_matches, make_case
 
 pytestmark = pytest.mark.gpu
 
-LUT_QT = 8                       # queries per workgroup of the batched table kernel (vaq_kernels.hip)
+LUT_QT = 8                       # queries per workgroup of the batched table kernel (vaq_front.hip)
 COST_ORDER_MIN_QUERIES = 1024    # vaqhip_index.h
-QORDER_MAX = 16384               # vaq_kernels.hip: most queries of one ranking
+QORDER_MAX = 16384               # vaq_front.hip: most queries of one ranking
 N_ROWS = 20000
 NONUNIFORM = [12, 10, 9, 8, 8, 7, 6, 4]   # a first table of 4096 entries: the key samples its buckets
 SHAPES = {"m8": [8] * 8, "nonuniform": NONUNIFORM}

@@ -1,4 +1,4 @@
-"""The first-round primitives of vaq_kernels.hip at their launch-shape edges: the projection's three
+"""The first-round primitives (vaq_front.hip, vaq_codes.hip, vaq_merge.hip) at their launch-shape edges: the projection's three
 kernels on both sides of their row thresholds, CreateLUT's small-codebook branch in every reduction
 order, the encoder's row tiles, chunk loops and non-finite rows, the old refine on continuous data, and
 the k-min merge at every fold count, fill level and stride.

@@ -1,8 +1,8 @@
 """The row packing the scan kernels assume, restated in numpy for the case table of
 tests/test_scan_widths_gpu.py (no GPU needed).
 
-LAYOUT_BITS (vaq_kernels.hip, pack_codes_kernel): field s of a row occupies bits [bit_off, bit_off + bits)
-of a W-dword little-endian row, LSB first; rows lie in planar tiles of 64 (vaq_kernels.h TILE_ROWS): word w
+LAYOUT_BITS (vaq_codes.hip, pack_codes_kernel): field s of a row occupies bits [bit_off, bit_off + bits)
+of a W-dword little-endian row, LSB first; rows lie in planar tiles of 64 (vaq_common.h TILE_ROWS): word w
 of row r at (r / 64) * 64 * W + w * 64 + r % 64.  The kernels take a field out of (lo, hi) = words
 (word, word + 1) with a funnel shift by bit_off % 32 and a mask, and read hi as 0 when word is the row's
 last (vaq_scan.h drain / tail_inplace, vaq_scan_bf.h BfBits::chain).  The best-first form keeps one packed

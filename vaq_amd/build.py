@@ -1,11 +1,12 @@
 """Build the gfx950 shared library (vaq_amd/lib/libvaqhip.so) with hipcc.
 
 hipcc cross-compiles for gfx950 without a GPU.  -ffp-contract=off is part of
-the numerics contract (vaq_kernels.hip header): only explicit fmaf() fuses.
+the numerics contract (vaq_common.h): only explicit fmaf() fuses.
 """
 from __future__ import annotations
 
 import os
+import re
 import subprocess
 import sys
 
@@ -13,100 +14,49 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "vaq_amd", "csrc")
 LIBDIR = os.path.join(ROOT, "vaq_amd", "lib")
 LIB = os.path.join(LIBDIR, "libvaqhip.so")
-SOURCES = ["vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_codebooks.hip", "vaq_fast.hip", "vaq_lutfit.hip", "vaq_learn.hip", "vaq_refine.hip", "vaq_exhaust.hip", "vaq_train.hip", "vaqhip_api.cpp", "vaqhip_plan.cpp", "vaqhip_search.cpp", "vaqhip_codes.cpp", "vaqhip_fast.cpp", "vaqhip_learn.cpp", "vaqhip_lutfit.cpp", "vaqhip_codebooks.cpp", "vaqhip_train.cpp", "vaqhip_refiner.cpp",
-           "vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp", "vaqhip_multi_encode.cpp", "vaqhip_multi_lutfit.cpp", "vaqhip_multi_learn.cpp", "vaqhip_multi_codebooks.cpp", "vaqhip_rccl.cpp"]
-MULTI_REFINER_SOURCES = ("vaqhip_multi_refiner.cpp", "vaqhip_multi_refiner_search.cpp")
-MULTI_ENCODE_SOURCE = "vaqhip_multi_encode.cpp"  # reads the multi refiner's resident rows: its headers too
-MULTI_LUTFIT_SOURCE = "vaqhip_multi_lutfit.cpp"  # the sharded quantile fit: reads the multi refiner's resident rows too
-MULTI_LEARN_SOURCE = "vaqhip_multi_learn.cpp"  # learnQuantization over the multi refiner's resident rows
-MULTI_CODEBOOKS_SOURCE = "vaqhip_multi_codebooks.cpp"  # the sharded codebook fit: reads the multi refiner's resident rows too
-MULTI_SOURCES = ("vaqhip_multi.cpp", "vaqhip_multi_search.cpp", "vaqhip_multi_kmeans.cpp", MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE, MULTI_LEARN_SOURCE, MULTI_CODEBOOKS_SOURCE) + MULTI_REFINER_SOURCES
-KERNEL_HEADER = os.path.join(CSRC, "vaq_kernels.h")
-OWNER_HEADER = os.path.join(CSRC, "refine_owner.h")  # the refiner's cut and label -> shard: vaq_kernels.h brings it
-API_HEADER = os.path.join(ROOT, "include", "vaqhip.h")
-
-
-SCAN_HEADER = os.path.join(CSRC, "vaq_scan.h")
-SCAN_BF_HEADER = os.path.join(CSRC, "vaq_scan_bf.h")
-FAST_HEADER = os.path.join(CSRC, "vaq_fast.h")
-REFINE_GROUP_HEADER = os.path.join(CSRC, "vaq_refine_group.h")  # Eigen's squaredNorm over 16 lanes: refine, exhaustive form
-EXHAUST_HEADER = os.path.join(CSRC, "vaq_exhaust.h")  # the same by one thread, host and device: exhaustive form
-EXHAUST_PLAN_HEADER = os.path.join(CSRC, "vaqhip_exhaust_plan.h")  # the exhaustive form's plan and launches: both refiners
-REFINE_COMMON_HEADER = os.path.join(CSRC, "vaqhip_refine_common.h")  # checks, options, the row store: both refiners
-MULTI_REFINER_HEADER = os.path.join(CSRC, "vaqhip_multi_refiner.h")  # private to the multi refiner's two host files
-SHARD_RUN_HEADER = os.path.join(CSRC, "vaqhip_shard_run.h")  # the call-owned run and its teardown: the sharded builds
-RESTATED_HEADER = os.path.join(CSRC, "vaq_restated.h")  # stdsort, stdheap, refheap, sq_norm_eigen: FAST, TI planning, the replay, k-means, refine
-INTERNAL_HEADER = os.path.join(CSRC, "vaqhip_internal.h")
-INDEX_HEADER = os.path.join(CSRC, "vaqhip_index.h")  # private to the single-index host files
-DEV_HEADER = os.path.join(CSRC, "vaqhip_dev.h")      # DevBuf, DeviceGuard: both hosts and the scratch allocators
-MULTI_HEADER = os.path.join(CSRC, "vaqhip_multi.h")  # private to the multi-device host files; brings the next two
-JOB_POOL_HEADER = os.path.join(CSRC, "job_pool.h")
-RCCL_HEADER = os.path.join(CSRC, "vaqhip_rccl.h")
-KMEANS_SAMPLE_HEADER = os.path.join(CSRC, "kmeans_sample.h")  # the k-means' sample and its split: both hosts
-LUTFIT_HEADER = os.path.join(CSRC, "vaq_lutfit.h")  # binaryEncodingLUT's two lambdas: kernels and host
-LUTFIT_DEV_HEADER = os.path.join(CSRC, "vaq_lutfit_dev.h")  # the column fit's two halves: kernels and the sharded fit
-LUTFIT_PLAN_HEADER = os.path.join(CSRC, "lutfit_multi_plan.h")  # owners, rounds, offsets of the sharded fit (no HIP)
-LEARN_PLAN_HEADER = os.path.join(CSRC, "learn_plan.h")  # learnQuantization's host arithmetic: both forms, the loss kernel (no HIP)
-LEARN_HEADER = os.path.join(CSRC, "vaq_learn.h")  # the kernels of learnQuantization's device forms
-CODEBOOKS_PLAN_HEADER = os.path.join(CSRC, "fit_codebooks_plan.h")  # samples, offsets, key width of the codebook fit (no HIP)
-TRAIN_PLAN_HEADER = os.path.join(CSRC, "train_plan.h")  # sample, plan and exact bit allocation of the training front half (no HIP)
-TRAIN_ROT_HEADER = os.path.join(CSRC, "vaq_train_rot.h")  # the Jacobi rotation, ordering and host solver: kernels and host
-TRAIN_HEADER = os.path.join(CSRC, "vaq_train.h")  # the kernels of the training front half
-CODEBOOKS_MULTI_PLAN_HEADER = os.path.join(CSRC, "fit_codebooks_multi_plan.h")  # owners, sub-plans, sample split of the sharded fit (no HIP)
-CODEBOOKS_HIER_PLAN_HEADER = os.path.join(CSRC, "fit_codebooks_hier_plan.h")  # rows, batches, refusals, tiles of the hierarchical fit (no HIP)
-CODEBOOKS_BIN_PLAN_HEADER = os.path.join(CSRC, "fit_codebooks_bin_plan.h")  # nodes, level batches, chunks, tiles of the binary-tree fit (no HIP)
-
-
-def _deps(src: str):
-    # only the host files see the public C header; the scan bodies live in vaq_scan.h
-    deps = [os.path.join(CSRC, src), KERNEL_HEADER, OWNER_HEADER]
-    if src == "vaqhip_rccl.cpp":  # nothing of the index
-        return [os.path.join(CSRC, src), RCCL_HEADER]
-    if src.endswith(".cpp"):
-        deps += [API_HEADER, INTERNAL_HEADER, DEV_HEADER]
-        deps += [MULTI_HEADER, JOB_POOL_HEADER, RCCL_HEADER] if src in MULTI_SOURCES else [INDEX_HEADER]
-    if src in ("vaq_kernels.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_lutfit.hip", "vaq_codebooks.hip"):
-        deps.append(DEV_HEADER)
-    if src in ("vaq_codebooks.hip", "vaqhip_codebooks.cpp", MULTI_CODEBOOKS_SOURCE):
-        deps += [CODEBOOKS_PLAN_HEADER, KMEANS_SAMPLE_HEADER]
-    if src in ("vaq_codebooks.hip", "vaqhip_codebooks.cpp"):
-        deps.append(CODEBOOKS_HIER_PLAN_HEADER)
-        deps.append(CODEBOOKS_BIN_PLAN_HEADER)
-    if src == MULTI_CODEBOOKS_SOURCE:
-        deps.append(CODEBOOKS_MULTI_PLAN_HEADER)
-    if src in ("vaq_train.hip", "vaqhip_train.cpp"):
-        deps += [TRAIN_PLAN_HEADER, TRAIN_ROT_HEADER, TRAIN_HEADER, KMEANS_SAMPLE_HEADER]
-    if src in ("vaq_lutfit.hip", "vaqhip_lutfit.cpp", MULTI_LUTFIT_SOURCE, "vaq_learn.hip"):
-        deps.append(LUTFIT_HEADER)
-    if src in ("vaq_learn.hip", "vaqhip_learn.cpp", "vaqhip_fast.cpp"):
-        deps.append(LEARN_PLAN_HEADER)
-    if src in ("vaq_learn.hip", "vaqhip_learn.cpp", MULTI_LEARN_SOURCE):
-        deps.append(LEARN_HEADER)
-    if src in ("vaq_lutfit.hip", MULTI_LUTFIT_SOURCE):
-        deps.append(LUTFIT_DEV_HEADER)
-    if src == MULTI_LUTFIT_SOURCE:
-        deps.append(LUTFIT_PLAN_HEADER)
-    if src in ("vaq_kmeans.hip", "vaqhip_codes.cpp", "vaqhip_multi_kmeans.cpp", "vaqhip_learn.cpp", MULTI_LEARN_SOURCE):
-        deps.append(KMEANS_SAMPLE_HEADER)
-    if src in ("vaq_kernels.hip", "vaq_scan_bytes.hip", "vaq_scan_bits.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip", "vaq_exact.hip", "vaq_refine.hip", "vaq_exhaust.hip"):
-        deps.append(SCAN_HEADER)
-    if src in ("vaq_kernels.hip", "vaq_scan_bf.hip", "vaq_scan_bm.hip"):
-        deps.append(SCAN_BF_HEADER)
-    if src in ("vaq_fast.hip", "vaqhip_fast.cpp"):
-        deps.append(FAST_HEADER)
-    if src in ("vaq_fast.hip", "vaqhip_fast.cpp", "vaq_exact.hip", "vaq_ti.hip", "vaq_kmeans.hip", "vaq_codebooks.hip", "vaq_refine.hip", "vaq_exhaust.hip"):
-        deps.append(RESTATED_HEADER)
-    if src in ("vaq_refine.hip", "vaq_exhaust.hip"):
-        deps.append(REFINE_GROUP_HEADER)
-    if src == "vaq_exhaust.hip":
-        deps.append(EXHAUST_HEADER)
-    if src == "vaqhip_refiner.cpp" or src in MULTI_REFINER_SOURCES or src in (MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE, MULTI_LEARN_SOURCE, MULTI_CODEBOOKS_SOURCE):
-        deps += [EXHAUST_PLAN_HEADER, REFINE_COMMON_HEADER]
-    if src in MULTI_REFINER_SOURCES or src in (MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE, MULTI_LEARN_SOURCE, MULTI_CODEBOOKS_SOURCE):
-        deps.append(MULTI_REFINER_HEADER)
-    if src in (MULTI_ENCODE_SOURCE, MULTI_LUTFIT_SOURCE, MULTI_LEARN_SOURCE, MULTI_CODEBOOKS_SOURCE):
-        deps.append(SHARD_RUN_HEADER)
-    return deps
+SOURCES = [
+    # device units
+    "vaq_front.hip",
+    "vaq_codes.hip",
+    "vaq_scan_launch.hip",
+    "vaq_scan_bytes.hip",
+    "vaq_scan_bits.hip",
+    "vaq_scan_bf.hip",
+    "vaq_scan_bm.hip",
+    "vaq_merge.hip",
+    "vaq_exact.hip",
+    "vaq_ti.hip",
+    "vaq_kmeans.hip",
+    "vaq_codebooks.hip",
+    "vaq_fast.hip",
+    "vaq_lutfit.hip",
+    "vaq_learn.hip",
+    "vaq_refine.hip",
+    "vaq_exhaust.hip",
+    "vaq_train.hip",
+    # the single-index host
+    "vaqhip_api.cpp",
+    "vaqhip_plan.cpp",
+    "vaqhip_search.cpp",
+    "vaqhip_codes.cpp",
+    "vaqhip_fast.cpp",
+    "vaqhip_learn.cpp",
+    "vaqhip_lutfit.cpp",
+    "vaqhip_codebooks.cpp",
+    "vaqhip_train.cpp",
+    "vaqhip_refiner.cpp",
+    # the multi-device host
+    "vaqhip_multi.cpp",
+    "vaqhip_multi_search.cpp",
+    "vaqhip_multi_kmeans.cpp",
+    "vaqhip_multi_refiner.cpp",
+    "vaqhip_multi_refiner_search.cpp",
+    "vaqhip_multi_encode.cpp",
+    "vaqhip_multi_lutfit.cpp",
+    "vaqhip_multi_learn.cpp",
+    "vaqhip_multi_codebooks.cpp",
+    "vaqhip_rccl.cpp",
+]
 OBJDIR = os.path.join(LIBDIR, "obj")
 # Experiment builds: VAQ_VARIANT=name compiles (with VAQ_EXTRA_FLAGS) into vaq_amd/lib/variants/name/
 # and VAQHIP_LIB=<path> makes the package load that library instead (tools/ sweeps).
@@ -132,7 +82,15 @@ def _obj(src: str) -> str:
     return os.path.join(d, os.path.splitext(src)[0] + ".o")
 
 
+def parse_depfile(text: str) -> list:
+    """The files a compiler's -MD output names after its `target:` words; lines continue with a backslash, and a
+    space inside a name is written `\\ `."""
+    words = re.findall(r"(?:\\.|[^\s\\])+", text.replace("\\\n", " "))
+    return [re.sub(r"\\(.)", r"\1", w).replace("$$", "$") for w in words if not w.endswith(":")]
+
+
 def _obj_stale(src: str) -> bool:
+    """Every unit is compiled with -MD: what it read is what the compiler wrote down, not a table kept here."""
     o = _obj(src)
     if not os.path.exists(o):
         return True
@@ -140,7 +98,9 @@ def _obj_stale(src: str) -> bool:
     tag = o + ".flags"
     if not os.path.exists(tag) or open(tag).read() != _flags_tag():
         return True
-    return any(os.path.getmtime(d) > t for d in _deps(src))
+    if not os.path.exists(o + ".d"):
+        return True
+    return any(not os.path.exists(d) or os.path.getmtime(d) > t for d in parse_depfile(open(o + ".d").read()))
 
 
 def build_lib(force: bool = False, verbose: bool = False) -> str:
@@ -164,7 +124,7 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
             not (_VARIANT and _VARIANT_ONLY and s not in _VARIANT_ONLY)]
     procs = []
     for s in todo:
-        cmd = common + extra + ["-c", os.path.join(CSRC, s), "-o", _obj(s)]
+        cmd = common + extra + ["-MD", "-MF", _obj(s) + ".d", "-c", os.path.join(CSRC, s), "-o", _obj(s)]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         procs.append((s, cmd, subprocess.Popen(cmd)))

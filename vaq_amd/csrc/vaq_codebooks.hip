@@ -25,7 +25,9 @@
 #include "fit_codebooks_bin_plan.h"
 #include "fit_codebooks_hier_plan.h"
 #include "kmeans_sample.h"
-#include "vaq_kernels.h"
+#include "vaq_codebooks.h"
+#include "vaq_front.h"
+#include "vaq_refine.h"
 #include "vaq_restated.h"
 #include "vaqhip_dev.h"
 
@@ -268,7 +270,7 @@ __global__ __launch_bounds__(64) void cb_update_kernel(const float *__restrict__
 // out[i][c], i < cnt, c < D_w: compact column c of ONE owner (column subs[c / L] * L + c % L of the rows) for the i-th
 // row a shard contributes -- local row rows[i], or first + i where rows is null.  Without E the value is the row's
 // own, a byte widened where it is loaded.  With E it is ONE fmaf chain over the row's D inputs ascending from
-// acc = 0.0f: project_kernel's value bit for bit (vaq_kernels.hip), computed for the owner's columns only.
+// acc = 0.0f: project_kernel's value bit for bit (vaq_front.hip), computed for the owner's columns only.
 // A workgroup is tc column threads by tr = 256 / tc row groups (tc: the power of two from 16 to 256 that covers D_w,
 // blockIdx.y the column block where D_w > 256) and takes CC_RPT * tr rows at a time, CC_RPT accumulators per thread.
 // The rows pass through LDS in tiles of CC_JT inner indices, each element loaded once per workgroup: a half-wave loads

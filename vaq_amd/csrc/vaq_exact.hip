@@ -41,6 +41,7 @@
 // chain link is the raw heap, its length and bsfK, and the links count i from ExactParams::row0.  The
 // loop's partial-sum abandon only drops rows the test dist < bsfK drops (table entries are >= 0), so the
 // evaluating waves abandon and skip buckets against bsfK exactly as they do against the heap top.
+#include "vaq_exact.h"
 #include "vaq_restated.h"
 #include "vaq_scan.h"
 

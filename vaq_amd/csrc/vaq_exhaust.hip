@@ -26,7 +26,8 @@
 // loop -- and nothing after the load differs.
 // Compiled with -ffp-contract=off like the rest: no FMA, no MFMA, no float atomics; plain vector stores.
 #include "vaq_exhaust.h"
-#include "vaq_kernels.h"
+#include "vaq_exhaust_launch.h"
+#include "vaq_refine.h"
 #include "vaq_refine_group.h"
 #include "vaq_scan.h"
 

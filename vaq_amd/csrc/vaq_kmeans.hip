@@ -15,7 +15,7 @@
 //               max_iter, as the reference's does)
 // No float atomics, no MFMA, no reassociation.
 #include "kmeans_sample.h"
-#include "vaq_kernels.h"
+#include "vaq_kmeans.h"
 #include "vaq_restated.h"
 #include "vaqhip_dev.h"
 

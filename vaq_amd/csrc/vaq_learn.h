@@ -5,7 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "vaq_kernels.h"
+#include "vaq_common.h"
 
 namespace vaq {
 

@@ -13,7 +13,6 @@
 //                             contract (centroids[i] += Z[lastidx], :829), no tree may replace it
 // Encode: lut_encode_kernel streams the rows; PM (prefix maxima of Q) and the centres of a tile of
 // dimensions sit in LDS, packed (2N + 1 floats per dimension).
-#include "vaq_kernels.h"
 #include "vaq_lutfit.h"
 #include "vaq_lutfit_dev.h"
 #include "vaqhip_dev.h"
@@ -48,7 +47,7 @@ __global__ __launch_bounds__(256) void lutfit_extract_kernel(const T *__restrict
 // row per half-wave) and read back one row per lane; the row stride PC_STRIDE = 33 words is odd, so the 32 lanes of
 // a half-wave hit 32 different banks both ways (a stride of D = 128 would put them all on one).  A thread keeps W
 // accumulators; E[j][d0 + w] is the same for the whole wave and comes in as scalar loads.  Each y is ONE fmaf chain
-// over j ascending from acc = 0.0f: project_kernel's / project_tile_kernel's value bit for bit (vaq_kernels.hip).
+// over j ascending from acc = 0.0f: project_kernel's / project_tile_kernel's value bit for bit (vaq_front.hip).
 // 16 accumulators, the tile value and the addresses stay far below the 128 VGPRs at which a SIMD still holds four
 // waves; LDS (33 KB) allows four workgroups per CU.  Rows and offsets are 64-bit: a shard of 125M x 128 has 1.6e10
 // elements.

@@ -23,7 +23,7 @@
 // order only, so the answer is refine_rows_kernel's slot for slot.
 #include "refine_owner.h"
 #include "vaq_refine_group.h"
-#include "vaq_kernels.h"
+#include "vaq_refine.h"
 #include "vaq_restated.h"
 #include "vaq_scan.h"
 

@@ -1,12 +1,12 @@
 // vaq_scan.h -- device code shared by the scan translation units: the k-min selection state,
 // the workgroup scaffolding (ScanCtx) and the two scan bodies (byte codes, bit-packed codes).
 // vaq_scan_bytes.hip and vaq_scan_bits.hip instantiate the kernels (split so that the two
-// halves compile in parallel); vaq_kernels.hip holds everything else and launch_scan().
+// halves compile in parallel); vaq_scan_launch.hip holds the LDS geometry and launch_scan().
 // Everything here is a template or an inline device function.
 #ifndef VAQ_SCAN_H_
 #define VAQ_SCAN_H_
 
-#include "vaq_kernels.h"
+#include "vaq_scan_params.h"
 
 #include <float.h>
 #include <limits.h>

@@ -35,6 +35,7 @@
 // Arithmetic per row: dism = l0; dism += l1; dism += l2; dism += l3; dist (+)= dism, group by group
 // (VAQ.cpp:1737-1748).
 #include "vaq_scan_bf.h"
+#include "vaq_scan_bm.h"
 
 namespace vaq {
 

@@ -2,12 +2,12 @@
 // pruning of the reference: the index-side regrouping of VAQ::clusterTI
 // (VAQ.cpp:878-999) and the per-query cluster order of the TI branch of
 // VAQ::search (VAQ.cpp:799-826).  The pruned scan itself is the TI form of the
-// scan kernels in vaq_kernels.hip.
+// scan kernels (vaq_scan.h, launch_scan in vaq_scan_launch.hip).
 //
 // Compiled with -ffp-contract=off like every file of the library: distances
 // are the reference's  res += tmp * tmp  (utils/Math.hpp:8-19), multiply and
 // add unfused, or its SSE orders for d in {1,2,4,8,12} (:38-128).
-#include "vaq_kernels.h"
+#include "vaq_ti.h"
 #include "vaq_restated.h"
 #include "vaqhip_dev.h"
 

@@ -4,6 +4,11 @@
 // vaqhip_fast.cpp.  There is no CPU path here: every entry point needs a HIP
 // device and fails with VAQHIP_ENODEVICE / VAQHIP_EHIP otherwise.
 #include "vaqhip_index.h"
+#include "vaq_codes.h"
+#include "vaq_front.h"
+#include "vaq_lutfit_dev.h"
+#include "vaq_merge.h"
+#include "vaq_refine.h"
 
 #include <cstdarg>
 #include <string>

@@ -10,6 +10,7 @@
 #include "fit_codebooks_bin_plan.h"
 #include "fit_codebooks_hier_plan.h"
 #include "kmeans_sample.h"
+#include "vaq_codebooks.h"
 
 using namespace vaqhost;
 namespace cb = vaq::cbfit;

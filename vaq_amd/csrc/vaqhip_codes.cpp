@@ -3,6 +3,9 @@
 #include "vaqhip_index.h"
 
 #include "kmeans_sample.h"
+#include "vaq_codes.h"
+#include "vaq_kmeans.h"
+#include "vaq_ti.h"
 
 #include <chrono>
 #include <cmath>

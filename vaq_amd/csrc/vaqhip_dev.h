@@ -1,7 +1,7 @@
 // vaqhip_dev.h -- what every host of the library owns device state with: a grow-only device buffer, the
 // events of an option "timing" and the guard of the current device.  Shared by the single-index host files
 // (through vaqhip_index.h), the multi-device host files (through vaqhip_multi.h) and the two kernel files that
-// allocate scratch (vaq_kernels.hip, vaq_ti.hip).  It holds nothing of vaqhip_index.
+// allocate scratch (vaq_codes.hip, vaq_ti.hip).  It holds nothing of vaqhip_index.
 #ifndef VAQHIP_DEV_H
 #define VAQHIP_DEV_H
 #include <hip/hip_runtime.h>

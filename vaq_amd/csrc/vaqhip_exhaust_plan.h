@@ -12,7 +12,9 @@
 
 #include <algorithm>
 
-#include "vaq_kernels.h"
+#include "vaq_exact.h"
+#include "vaq_exhaust_launch.h"
+#include "vaq_merge.h"
 #include "vaqhip_dev.h"
 
 // (hidden: none of this joins the library's exported symbols)

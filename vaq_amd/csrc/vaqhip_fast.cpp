@@ -9,6 +9,8 @@
 
 #include "learn_plan.h"
 #include "vaq_fast.h"
+#include "vaq_front.h"
+#include "vaq_ti.h"
 
 using namespace vaqhost;
 

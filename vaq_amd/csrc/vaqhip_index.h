@@ -17,7 +17,9 @@
 #include <mutex>
 #include <vector>
 
-#include "vaq_kernels.h"
+#include "vaq_common.h"
+#include "vaq_scan_bm.h"
+#include "vaq_scan_params.h"
 #include "vaqhip_dev.h"
 #include "vaqhip_internal.h"
 

@@ -21,7 +21,9 @@
 
 #include "kmeans_sample.h"
 #include "learn_plan.h"
+#include "vaq_front.h"
 #include "vaq_learn.h"
+#include "vaq_refine.h"
 
 using namespace vaqhost;
 namespace ln = vaq::learn;

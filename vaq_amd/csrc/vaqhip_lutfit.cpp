@@ -6,7 +6,9 @@
 #include <chrono>
 #include <cmath>
 
+#include "vaq_front.h"
 #include "vaq_lutfit.h"
+#include "vaq_lutfit_dev.h"
 
 using namespace vaqhost;
 namespace lf = vaq::lutfit;

@@ -28,6 +28,7 @@
 #include <cstring>
 
 #include "fit_codebooks_multi_plan.h"
+#include "vaq_codebooks.h"
 
 using namespace vaqhost;
 namespace cm = vaq::cbfit_multi;

@@ -6,7 +6,7 @@
 #include <cstring>
 
 #include "kmeans_sample.h"
-#include "vaq_kernels.h"
+#include "vaq_kmeans.h"
 
 using namespace vaqhost;
 

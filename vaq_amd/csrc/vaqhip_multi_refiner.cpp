@@ -19,6 +19,7 @@
 // Every wait is a stream wait on an event.  With one shard the call is launch_refine_rows on the caller's stream.
 // The exhaustive form (every resident row a candidate) is vaqhip_multi_refiner_search.cpp.
 #include "vaqhip_multi_refiner.h"
+#include "vaq_refine.h"
 
 #include <cstring>
 

@@ -7,7 +7,8 @@
 #define VAQHIP_MULTI_REFINER_H
 #include "vaqhip_multi.h"
 
-#include "vaq_kernels.h"
+#include "refine_owner.h"
+#include "vaq_merge.h"
 #include "vaqhip_refine_common.h"
 
 namespace vaqhost __attribute__((visibility("hidden"))) {

@@ -11,6 +11,9 @@
 // B to D are enqueued by the calling thread in chain order, so an event is always recorded before its wait is enqueued.
 // With one shard the call is the single refiner's launches (xs_search_set) on the caller's stream.
 #include "vaqhip_multi_refiner.h"
+#include "vaq_exact.h"
+#include "vaq_exhaust_launch.h"
+#include "vaq_merge.h"
 
 using namespace vaqhost;
 

@@ -26,8 +26,6 @@
 // by distance of "head, then the shards' lists in shard order".
 #include "vaqhip_multi.h"
 
-#include "vaq_kernels.h"
-
 using namespace vaqhost;
 using Call = vaqhip_multi::Call;
 

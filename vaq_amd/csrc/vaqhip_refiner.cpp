@@ -7,6 +7,8 @@
 #include "vaqhip_index.h"
 
 #include "vaqhip_refine_common.h"
+#include "vaq_exhaust_launch.h"
+#include "vaq_refine.h"
 
 using namespace vaqhost;
 

@@ -1,6 +1,10 @@
 // vaqhip_search.cpp -- the scan driver of the single-device index: search_core and its stages, the
 // bucket-major rounds, the staged begin / finish, option "exact_ties", and the search entry points.
 #include "vaqhip_index.h"
+#include "vaq_exact.h"
+#include "vaq_front.h"
+#include "vaq_merge.h"
+#include "vaq_ti.h"
 
 using namespace vaqhost;
 
