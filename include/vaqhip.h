@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define VAQHIP_VERSION 121
+#define VAQHIP_VERSION 122
 
 /* error codes */
 #define VAQHIP_OK            0
@@ -1435,6 +1435,66 @@ typedef struct {
   int bucket_major;                            /* 1: the bucket-major second pass ran ("bucket_major") */
 } vaqhip_timing;
 int vaqhip_last_timing(vaqhip_index *ix, vaqhip_timing *out);
+
+/* ---- Hamming engine: BitVecEngine::query and BitVecEngine::queryRerank over packed bit rows -------------------------
+ * The rows of BitVecEngine's `data` (bitvectors: W = (n_bits + 63) / 64 uint64 words a row, actBitVLen) resident on the
+ * device.  hammingDist (utils/DistanceFunctions.hpp:164-172) counts every bit of every word: nothing is masked, and
+ * whatever bits the caller left in the tail of the last word count, in rows and in queries alike.
+ *   create      1 <= n_bits, W <= 16 (more: VAQHIP_EUNSUPPORTED -- a distance must fit 16 bits); both are checked
+ *               before a device is looked for.
+ *   rows        set_rows replaces them (row i has label id_base + i), add_rows appends (labels continue); both copy
+ *               synchronously.  set_rows_device takes a pointer on the engine's GPU and copies on `stream`, waiting for
+ *               it.  Labels are 32-bit ints: VAQHIP_ERANGE past 2^31 - 1.
+ *   query       BitVecEngine::query(queries, k, QueryMethod::Sort) (BitVecEngine.cpp:60-76): every row's distance, then
+ *               KNNFromDists (utils/Experiment.hpp:40-56) -- std::sort (libstdc++) of rows 0..k-1 by distance alone,
+ *               every later row inserted behind its equals: the reference's labels slot for slot, ties included.
+ *               labels_out int32 [nq][k] = id_base + row, distances_out float [nq][k] = the exact integers; slots past
+ *               min(k, n) are -1 / FLT_MAX (the reference reads past its array there).
+ *   method      the reference's QueryMethod values.  Only VAQHIP_BITVEC_SORT is provided: Heap, HeapEarlyAbandon and
+ *               SortEarlyAbandon return the same distances but keep OTHER rows among equal ones (their answer follows
+ *               from a sequential walk of all rows per query, and with integer distances every query has ties):
+ *               VAQHIP_EUNSUPPORTED.  Any other value VAQHIP_EINVAL.
+ *   rerank      BitVecEngine::queryRerank(queries, oriQueries, k, factor, Sort, earlyAbandonRank = false)
+ *               (BitVecEngine.cpp:454-466, :521-535): kTemp = min(factor * k, n); the Hamming kTemp best as above, kept
+ *               on the device; euclideanDistNoSQRT of each against ori_queries [nq][D] over the refiner's resident rows,
+ *               float or byte (distance += (a - b) * (a - b) in dimension order, nothing fused: squared distances, as
+ *               the reference returns them); then KNNFromDistsIndicesSupplied (BitVecEngine.hpp:171-187): std::sort of
+ *               the first k (dist, idx) pairs by distance alone, every later candidate behind its equals.  Slots past
+ *               min(k, kTemp) are -1 / FLT_MAX.  factor >= 1 (VAQHIP_EINVAL); factor * k <= VAQHIP_MAX_K before the
+ *               clamp to n (VAQHIP_EUNSUPPORTED).  The refiner must be on the engine's device (VAQHIP_EINVAL) and hold
+ *               the engine's number of rows from the engine's id_base (VAQHIP_ESTATE).  Rows or queries that are not
+ *               finite are outside the contract: the reference's comparator is no strict weak order on them and its
+ *               std::sort is undefined (here the call stays inside its arrays and returns some order).
+ *   option      "dist_chunk_bytes" (default 2^30): the queries are cut into chunks whose [chunk][n padded to 32] uint16
+ *               distance matrix stays within it (one query at least).  The answer does not depend on it.
+ *   limits      1 <= k <= VAQHIP_MAX_K (larger: VAQHIP_EUNSUPPORTED); nq == 0 succeeds and writes nothing; null pointers,
+ *               nq < 0 or k < 1 VAQHIP_EINVAL.  Every refusal is made before any device work.
+ * The host forms are synchronous; the _device forms take pointers on the engine's GPU, enqueue on `stream` and do not
+ * synchronise once the workspaces have their size.  Calls on one engine are serialised.  Errors leave their text in
+ * vaqhip_last_error(), as the index's and the refiner's do.  Not provided: the other three methods, earlyAbandonRank,
+ * the cluster-info, filtering and naive variants, the encoders (binaryEncoding*), a multi-device form. */
+typedef struct vaqhip_bitvec vaqhip_bitvec;
+#define VAQHIP_BITVEC_HEAP                0  /* BitVecEngine::QueryMethod (BitVecEngine.hpp:82-84) */
+#define VAQHIP_BITVEC_SORT                1
+#define VAQHIP_BITVEC_HEAP_EARLY_ABANDON  2
+#define VAQHIP_BITVEC_SORT_EARLY_ABANDON  3
+int vaqhip_bitvec_create(vaqhip_bitvec **out, int device_id, int n_bits);
+void vaqhip_bitvec_destroy(vaqhip_bitvec *bv);
+int vaqhip_bitvec_set_rows(vaqhip_bitvec *bv, const uint64_t *rows, int64_t n, int64_t id_base);
+int vaqhip_bitvec_set_rows_device(vaqhip_bitvec *bv, const uint64_t *d_rows, int64_t n, int64_t id_base, void *stream);
+int vaqhip_bitvec_add_rows(vaqhip_bitvec *bv, const uint64_t *rows, int64_t n_new);
+/* rows held, or a negative error code */
+int64_t vaqhip_bitvec_size(vaqhip_bitvec *bv);
+int vaqhip_bitvec_set_option(vaqhip_bitvec *bv, const char *key, int64_t value);
+int vaqhip_bitvec_query(vaqhip_bitvec *bv, const uint64_t *queries, int nq, int k, int method, int32_t *labels_out,
+                        float *distances_out);
+int vaqhip_bitvec_query_device(vaqhip_bitvec *bv, const uint64_t *d_queries, int nq, int k, int method,
+                               int32_t *d_labels_out, float *d_distances_out, void *stream);
+int vaqhip_bitvec_query_rerank(vaqhip_bitvec *bv, vaqhip_refiner *r, const uint64_t *bit_queries, const float *ori_queries,
+                               int nq, int k, int factor, int32_t *labels_out, float *distances_out);
+int vaqhip_bitvec_query_rerank_device(vaqhip_bitvec *bv, vaqhip_refiner *r, const uint64_t *d_bit_queries,
+                                      const float *d_ori_queries, int nq, int k, int factor, int32_t *d_labels_out,
+                                      float *d_distances_out, void *stream);
 
 const char *vaqhip_last_error(void);
 int vaqhip_version(void);

@@ -850,6 +850,12 @@ struct IdxDistPairFloat {  // utils/Types.hpp:41-57
   int idx;
   float dist;
 };
+struct IdxDistPair {  // utils/Types.hpp:51 (IdxDistPairBase<uint32_t>)
+  int idx;
+  uint32_t dist;
+};
+using bitv = std::vector<uint64_t>;  // BitVector.hpp: actBitVLen words a vector
+using bitvectors = std::vector<bitv>;
 
 class BitVecEngineHip {
 public:
@@ -864,13 +870,82 @@ public:
   BitVecEngineHip() = default;
   BitVecEngineHip(const BitVecEngineHip &) = delete;
   BitVecEngineHip &operator=(const BitVecEngineHip &) = delete;
-  ~BitVecEngineHip() { invalidate(); }
+  ~BitVecEngineHip() {
+    invalidate();
+    vaqhip_bitvec_destroy(bv_);
+    vaqhip_refiner_destroy(ori_);
+  }
   void invalidate() {
     vaqhip_index_destroy(h_);
     h_ = nullptr;
     vaqhip_multi_destroy(mh_);
     mh_ = nullptr;
   }
+
+  // ---- the Hamming queries (vaqhip_bitvec_* of vaqhip.h), on mDevice ----
+  struct QueryMethod {  // BitVecEngine.hpp:82-84
+    enum { Heap, Sort, HeapEarlyAbandon, SortEarlyAbandon };
+  };
+  // BitVecEngine::loadBitV: the bit vectors, all of one length (at most 16 words), copied to the device
+  void loadBitV(const bitvectors &bitVectors) {
+    const size_t W = bitVectors.empty() ? 1 : bitVectors[0].size();
+    std::vector<uint64_t> flat;
+    flat.reserve(bitVectors.size() * W);
+    for (const bitv &v : bitVectors) {
+      if (v.size() != W) throw Error(VAQHIP_EINVAL, "vaqhip: loadBitV: bit vectors of different lengths");
+      flat.insert(flat.end(), v.begin(), v.end());
+    }
+    vaqhip_bitvec_destroy(bv_);
+    bv_ = nullptr;
+    bitWords_ = (int)W;
+    check(vaqhip_bitvec_create(&bv_, mDevice, (int)(64 * W)));
+    check(vaqhip_bitvec_set_rows(bv_, flat.data(), (int64_t)bitVectors.size(), 0));
+  }
+  // BitVecEngine::loadOriginal: the raw rows queryRerank measures, kept on the device as floats or as bytes
+  void loadOriginal(const RowMatrix<float> &oriDataset) {
+    newOriginal((int)oriDataset.cols());
+    check(vaqhip_refiner_set_rows(ori_, oriDataset.data(), (int64_t)oriDataset.rows(), 0));
+  }
+  void loadOriginal(const RowMatrix<uint8_t> &oriDataset) {
+    newOriginal((int)oriDataset.cols());
+    check(vaqhip_refiner_set_rows_u8(ori_, oriDataset.data(), (int64_t)oriDataset.rows(), 0));
+  }
+  // BitVecEngine::query: min(k, rows) pairs per query.  Only QueryMethod::Sort is provided: the other three keep
+  // other rows among equal distances (vaqhip.h), and throw as parseMethodString does for a token it does not serve
+  std::vector<std::vector<IdxDistPair>> query(const bitvectors &queries, const int k, int method = QueryMethod::Sort) {
+    if (!bv_) throw Error(VAQHIP_ESTATE, "vaqhip: query before loadBitV");
+    const std::vector<uint64_t> q = flatQueries(queries);
+    const int nq = (int)queries.size();
+    std::vector<int> lab((size_t)nq * k);
+    std::vector<float> dis((size_t)nq * k);
+    check(vaqhip_bitvec_query(bv_, q.data(), nq, k, method, lab.data(), dis.data()));
+    std::vector<std::vector<IdxDistPair>> answers(nq);
+    for (int i = 0; i < nq; i++)
+      for (int j = 0; j < k && lab[(size_t)i * k + j] >= 0; j++)
+        answers[i].push_back({lab[(size_t)i * k + j], (uint32_t)dis[(size_t)i * k + j]});
+    return answers;
+  }
+  // BitVecEngine::queryRerank with earlyAbandonRank = false: squared Euclidean distances, as the reference's
+  template <class Mat>
+  std::vector<std::vector<IdxDistPairFloat>> queryRerank(const bitvectors &queries, const Mat &oriQueries, const int k,
+                                                         const int factor = 2, int method = QueryMethod::Sort) {
+    if (!bv_ || !ori_) throw Error(VAQHIP_ESTATE, "vaqhip: queryRerank before loadBitV and loadOriginal");
+    if (method != QueryMethod::Sort)
+      throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: queryRerank: only QueryMethod::Sort is provided");
+    const std::vector<uint64_t> q = flatQueries(queries);
+    const int nq = (int)queries.size();
+    if ((int)oriQueries.rows() != nq || (int)oriQueries.cols() != oriDim_)
+      throw Error(VAQHIP_EINVAL, "vaqhip: queryRerank: oriQueries must have one row of the original dimension per query");
+    std::vector<int> lab((size_t)nq * k);
+    std::vector<float> dis((size_t)nq * k);
+    check(vaqhip_bitvec_query_rerank(bv_, ori_, q.data(), oriQueries.data(), nq, k, factor, lab.data(), dis.data()));
+    std::vector<std::vector<IdxDistPairFloat>> answers(nq);
+    for (int i = 0; i < nq; i++)
+      for (int j = 0; j < k && lab[(size_t)i * k + j] >= 0; j++)
+        answers[i].push_back({lab[(size_t)i * k + j], dis[(size_t)i * k + j]});
+    return answers;
+  }
+  vaqhip_bitvec *bitvecHandle() const { return bv_; }
   // Several devices (a device named several times: logical shards on that GPU): binaryEncodingLUT then fits over
   // them (vaqhip_multi_lut_fit_quantiles), builds a VAQHIP_SUM_SEQUENTIAL multi index, gives it Q and encodes across
   // the shards (vaqhip_multi_encode_lut_set_codes), and queryLUT answers from that multi index -- the same members
@@ -990,9 +1065,27 @@ private:
     }
     check(vaqhip_index_create_ex(&h_, nd, nd, solutionX.data(), cp.data(), eig, mDevice, VAQHIP_SUM_SEQUENTIAL));
   }
+  std::vector<uint64_t> flatQueries(const bitvectors &queries) const {
+    std::vector<uint64_t> flat;
+    flat.reserve(queries.size() * (size_t)bitWords_);
+    for (const bitv &v : queries) {
+      if ((int)v.size() != bitWords_) throw Error(VAQHIP_EINVAL, "vaqhip: a query's length differs from the bit vectors'");
+      flat.insert(flat.end(), v.begin(), v.end());
+    }
+    return flat;
+  }
+  void newOriginal(int D) {
+    vaqhip_refiner_destroy(ori_);
+    ori_ = nullptr;
+    oriDim_ = D;
+    check(vaqhip_refiner_create(&ori_, mDevice, D));
+  }
   vaqhip_index *h_ = nullptr;
   vaqhip_multi *mh_ = nullptr;
   std::vector<int> mDevices;
+  vaqhip_bitvec *bv_ = nullptr;   // loadBitV
+  vaqhip_refiner *ori_ = nullptr;  // loadOriginal
+  int bitWords_ = 0, oriDim_ = 0;
 };
 
 } // namespace vaqhip

@@ -7,6 +7,7 @@ Product surface:
   vaq_amd.VaqHipFast          the same with the FAST search method (uint8 tables, 4-bit codes)
   vaq_amd.VaqRefiner          VAQ::refine over raw rows resident on the device, reference-exact
   vaq_amd.VaqMultiRefiner     the same over raw rows sharded across several GPUs
+  vaq_amd.VaqBitVec           BitVecEngine::query / ::queryRerank (QueryMethod::Sort) over packed bit rows on the device
   vaq_amd.lut_fit_quantiles_multi  binaryEncodingLUT's quantile codebooks with the rows cut over several GPUs
   vaq_amd.lut_fit_quantiles_multi_u8  the same from byte rows (a bvecs dataset as its file holds it)
   vaq_amd.fit_codebooks       the subspace codebooks (KMeans::staticFitSampling per subspace) from raw rows
@@ -31,10 +32,11 @@ from .index import last_multi_fit_codebooks_timing  # noqa: F401
 from .index import fit_codebooks_hier, fit_codebooks_hier_u8, last_fit_codebooks_hier_timing  # noqa: F401
 from .index import fit_codebooks_bin, fit_codebooks_bin_u8, last_fit_codebooks_bin_timing  # noqa: F401
 from .index import last_train_timing, train, train_rotation  # noqa: F401
+from .index import QueryMethod, VaqBitVec  # noqa: F401
 
 __all__ = ["VaqHip", "VaqHipFast", "VaqHipMulti", "VaqRefiner", "VaqMultiRefiner", "NNMethod", "LabelDistVec", "VaqHipError", "load", "lib_path",
            "lut_fit_quantiles_multi", "lut_fit_quantiles_multi_u8", "last_lut_fit_multi_timing",
            "fit_codebooks", "fit_codebooks_u8", "fit_codebooks_timing", "last_fit_codebooks_timing",
            "last_multi_fit_codebooks_timing", "fit_codebooks_hier", "fit_codebooks_hier_u8",
            "last_fit_codebooks_hier_timing", "fit_codebooks_bin", "fit_codebooks_bin_u8", "last_fit_codebooks_bin_timing",
-           "train_rotation", "train", "last_train_timing"]
+           "train_rotation", "train", "last_train_timing", "VaqBitVec", "QueryMethod"]

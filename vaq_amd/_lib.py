@@ -70,6 +70,9 @@ SYMBOLS = [
     "vaqhip_refiner_train_moment", "vaqhip_sym_eigen_device", "vaqhip_sym_eigen_host", "vaqhip_train_plan",
     "vaqhip_allocate_bits", "vaqhip_train_rotation", "vaqhip_train_rotation_device", "vaqhip_train_rotation_u8",
     "vaqhip_train_rotation_u8_device", "vaqhip_refiner_train_rotation", "vaqhip_last_train_timing",
+    "vaqhip_bitvec_create", "vaqhip_bitvec_destroy", "vaqhip_bitvec_set_rows", "vaqhip_bitvec_set_rows_device",
+    "vaqhip_bitvec_add_rows", "vaqhip_bitvec_size", "vaqhip_bitvec_set_option", "vaqhip_bitvec_query",
+    "vaqhip_bitvec_query_device", "vaqhip_bitvec_query_rerank", "vaqhip_bitvec_query_rerank_device",
 ]
 MAX_DEVICES = 16
 
@@ -314,6 +317,19 @@ def load():
     L.vaqhip_search_refine_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.vaqhip_merge_topk_strided_device.argtypes = [i32, vp, vp, i32, i64, i64, i32, i32, vp, vp, vp]
     L.vaqhip_merge_fast_device.argtypes = [i32, vp, i64, i32, i64, vp, vp, i32, i64, i64, i32, i32, vp, vp, vp]
+    L.vaqhip_bitvec_create.argtypes = [C.POINTER(vp), i32, i32]
+    L.vaqhip_bitvec_destroy.argtypes = [vp]
+    L.vaqhip_bitvec_destroy.restype = None
+    L.vaqhip_bitvec_set_rows.argtypes = [vp, vp, i64, i64]
+    L.vaqhip_bitvec_set_rows_device.argtypes = [vp, vp, i64, i64, vp]
+    L.vaqhip_bitvec_add_rows.argtypes = [vp, vp, i64]
+    L.vaqhip_bitvec_size.argtypes = [vp]
+    L.vaqhip_bitvec_size.restype = i64
+    L.vaqhip_bitvec_set_option.argtypes = [vp, C.c_char_p, i64]
+    L.vaqhip_bitvec_query.argtypes = [vp, vp, i32, i32, i32, vp, vp]
+    L.vaqhip_bitvec_query_device.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
+    L.vaqhip_bitvec_query_rerank.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
+    L.vaqhip_bitvec_query_rerank_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.vaqhip_index_info.argtypes = [vp, C.POINTER(Info)]
     L.vaqhip_set_option.argtypes = [vp, C.c_char_p, i64]
     L.vaqhip_last_timing.argtypes = [vp, C.POINTER(Timing)]

@@ -34,6 +34,7 @@ SOURCES = [
     "vaq_refine.hip",
     "vaq_exhaust.hip",
     "vaq_train.hip",
+    "vaq_bitvec.hip",
     # the single-index host
     "vaqhip_api.cpp",
     "vaqhip_plan.cpp",
@@ -45,6 +46,7 @@ SOURCES = [
     "vaqhip_codebooks.cpp",
     "vaqhip_train.cpp",
     "vaqhip_refiner.cpp",
+    "vaqhip_bitvec.cpp",
     # the multi-device host
     "vaqhip_multi.cpp",
     "vaqhip_multi_search.cpp",

@@ -225,13 +225,15 @@ struct Entry {
 // and is the success path.  A return before finish() is a failure with work possibly enqueued already: the
 // destructor leaves the event all the same, without touching the failure's code and text.
 // WS_SCOPE(ws, ix, st) declares the scope and returns its code at once when the construction failed.
+// Owner: the index, or another handle that keeps the same three members (ws_event, ws_stream, ws_used) for workspaces
+// of its own (vaqhip_bitvec.cpp); the macro's argument names it.
 #define WS_SCOPE(name, ix, st) WsScope name(ix, st); if (name.rc) return name.rc
-struct WsScope {
-  vaqhip_index *ix;
+template <class Owner> struct WsScope {
+  Owner *ix;
   hipStream_t st;
   bool open = false;
   int rc;
-  WsScope(vaqhip_index *ix, hipStream_t st) : ix(ix), st(st), rc(acquire()) { open = rc == VAQHIP_OK; }
+  WsScope(Owner *ix, hipStream_t st) : ix(ix), st(st), rc(acquire()) { open = rc == VAQHIP_OK; }
   WsScope(const WsScope &) = delete;
   ~WsScope() {
     if (open && hipEventRecord(ix->ws_event, st) == hipSuccess) mark();

@@ -117,4 +117,18 @@ template <class Call> hipError_t through_staging(StagingBufs &w, hipStream_t st,
 }
 
 }  // namespace vaqhost
+
+// What another handle's call reads of a single-device refiner (vaqhip_bitvec.cpp: the rerank over its resident rows).
+// Defined in vaqhip_refiner.cpp.  The caller holds refiner_mutex(r) from refiner_view(r) until the work that reads the
+// rows is enqueued: a set or an append waits for the device before it moves them.
+struct vaqhip_refiner;
+namespace vaqhost __attribute__((visibility("hidden"))) {
+struct RefinerView {
+  vaq::RowsRef rows;
+  int64_t N, id_base;
+  int device, D;
+};
+std::mutex &refiner_mutex(vaqhip_refiner *r);
+RefinerView refiner_view(const vaqhip_refiner *r);
+}  // namespace vaqhost
 #endif

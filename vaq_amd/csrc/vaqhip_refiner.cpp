@@ -29,6 +29,11 @@ struct vaqhip_refiner {
   std::mutex mu;
 };
 
+namespace vaqhost {
+std::mutex &refiner_mutex(vaqhip_refiner *r) { return r->mu; }
+RefinerView refiner_view(const vaqhip_refiner *r) { return RefinerView{r->rows.rows(), r->N, r->id_base, r->device, r->D}; }
+}  // namespace vaqhost
+
 namespace {
 
 constexpr RefineHost REFINER = {fail, "refiner"};

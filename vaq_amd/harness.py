@@ -182,3 +182,17 @@ def recall_at_r(labels: np.ndarray, topnn: np.ndarray) -> float:
     labels = np.asarray(labels)
     topnn = np.asarray(topnn)
     return float(np.mean([topnn[q, 0] in set(labels[q].tolist()) for q in range(labels.shape[0])]))
+
+
+def sign_bits(Xproj) -> np.ndarray:
+    """The bit vectors of projected rows as BitVecEngine::binaryEncodingSimple packs them (cols % 64 != 63): uint64
+    [n][W], W = (D + 63) // 64, dimension d is bit 63 - d % 64 of word d // 64 (MSB first), set where the value is
+    positive; the unused tail bits are 0.  NumPy, for tests and benches only -- not a device encoder."""
+    X = Xproj.detach().cpu().numpy() if hasattr(Xproj, "detach") else np.asarray(Xproj)
+    n, D = X.shape
+    W = (D + 63) // 64
+    bits = np.zeros((n, W * 64), np.uint8)
+    bits[:, :D] = X > 0
+    # np.packbits is MSB first within a byte; the eight bytes of a word, most significant first, are its big-endian image
+    return np.ascontiguousarray(np.packbits(bits, axis=1).reshape(n, W, 8)).view(">u8").reshape(n, W).astype(np.uint64)
+

@@ -5,12 +5,14 @@ include/vaqhip.h.  This module only gathers the names; the code is one module pe
   refiner.py  VaqRefiner, VaqMultiRefiner             multi.py   VaqHipMulti
   fits.py     fit_codebooks*, lut_fit_quantiles_multi*, train_rotation, train, their timing calls
   merge.py    merge_topk_device, merge_topk_packed_device, merge_fast_device
+  bitvec.py   VaqBitVec, QueryMethod (the Hamming queries of BitVecEngine)
   _adapt.py   what they share (pointers, row checks, the output pair and stream of a device call, handle lifetime)
 
 All compute goes through libvaqhip.so; nothing here has a NumPy fallback.
 """
 from . import _lib  # noqa: F401
 from ._adapt import _ptr, _same, _u8_rows, _u8_rows_device, _wref  # noqa: F401
+from .bitvec import QueryMethod, VaqBitVec  # noqa: F401
 from .fast import VaqHipFast  # noqa: F401
 from .fits import fit_codebooks_hier, fit_codebooks_hier_u8, last_fit_codebooks_hier_timing  # noqa: F401
 from .fits import fit_codebooks_bin, fit_codebooks_bin_u8, last_fit_codebooks_bin_timing, fit_codebooks_bin_sums  # noqa: F401
