@@ -15,6 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(HERE)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import bitvec_cases as bc  # noqa: E402
 import bitvec_ref as br  # noqa: E402
 from oracle import pyoracle as po  # noqa: E402
 
@@ -23,6 +24,12 @@ HAMMING = {
     "hamming_w1_k10": (11, 64, 200, 4, 10, 6),
     "hamming_w3_k40_tail": (12, 150, 300, 3, 40, 10),   # 150 bits in 3 words: the 42 tail bits hold noise
     "hamming_w2_k100": (13, 128, 700, 2, 100, 8),
+}
+# name: (seed, W, n, k): tests/bitvec_cases.py's far crowd -- rows are the complement of query 0 with 0..3 bits turned
+# back (full words), query 1 is random; the k-th best distance of query 0 is 64 W, the largest there is
+FAR = {
+    "hamming_w4_k260_far": (1, 4, 300, 260),
+    "hamming_w16_k105_far": (1, 16, 120, 105),
 }
 # name: (seed, n_bits, n, nq, k, factor, D, top): raw rows are integers in [0, top)
 RERANK = {
@@ -55,10 +62,16 @@ def crosses(d, k):
 
 
 def make_hamming(name):
-    seed, n_bits, n, nq, k, flip = HAMMING[name]
-    rs = np.random.RandomState(seed)
-    rows, centres = bit_rows(rs, n_bits, n, flip)
-    queries, _ = bit_rows(rs, n_bits, nq, flip, centres)
+    if name in FAR:
+        seed, W, n, k = FAR[name]
+        n_bits, nq = 64 * W, 2
+        rows, queries = bc.far_crowd(W, n=n, seed=seed)
+        bc.check_far(rows, queries, k, 0)
+    else:
+        seed, n_bits, n, nq, k, flip = HAMMING[name]
+        rs = np.random.RandomState(seed)
+        rows, centres = bit_rows(rs, n_bits, n, flip)
+        queries, _ = bit_rows(rs, n_bits, nq, flip, centres)
     d = br.hamming_dists(rows, queries)
     labels = np.empty((nq, k), np.int32)
     dists = np.empty((nq, k), np.uint32)
@@ -108,7 +121,7 @@ def make_rerank(name):
 
 def main():
     assert po.have_ref(), "oracle/_ref is not built"
-    big_head = [make_hamming(name) for name in HAMMING]
+    big_head = [make_hamming(name) for name in list(HAMMING) + list(FAR)]
     assert any(big_head), "no Hamming fixture with k > 16 and equal distances among rows 0..k-1"
     big_head = [make_rerank(name) for name in RERANK]
     assert any(big_head), "no rerank fixture with k > 16 and equal distances inside the head"

@@ -12,27 +12,13 @@ import numpy as np
 import pytest
 
 import bitvec_ref as br
+from bitvec_cases import near, words
 from vaq_amd import QueryMethod, VaqBitVec, VaqHipError, VaqRefiner
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 GOLD = os.path.join(HERE, "golden", "hamming")
-
-
-def words(rs, n, W):
-    """n random rows of W full 64-bit words"""
-    return rs.randint(0, 1 << 32, (n, W), dtype=np.uint64) | (rs.randint(0, 1 << 32, (n, W), dtype=np.uint64) << np.uint64(32))
-
-
-def near(rs, centre, n, flip):
-    """n rows around one centre row with `flip` random bits turned: small distances with many ties"""
-    W = centre.shape[0]
-    rows = np.repeat(centre[None, :], n, axis=0).copy()
-    for r in range(n):
-        for b in rs.randint(0, 64 * W, flip):
-            rows[r, b // 64] ^= np.uint64(1) << np.uint64(b % 64)
-    return rows
 
 
 def fixtures(prefix):

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import bitvec_cases as bc
 import bitvec_ref as br
 from oracle import pyoracle as po
 
@@ -43,15 +44,19 @@ def test_query_rerank_matches_fixture(path):
 
 def test_fixtures_are_not_vacuous():
     """what make_hamming_golden.py asserts when it records, checked again on what is committed"""
-    big_head = False
+    big_head, far = False, 0
     for p in glob.glob(os.path.join(GOLD, "hamming_*.npz")):
         g = np.load(p)
         k = int(g["k"])
         d = br.hamming_dists(g["rows"], g["queries"])
         s = np.sort(d, axis=1)
         assert (s[:, k - 1] == s[:, k]).any(), p
+        if p.endswith("_far.npz"):  # the k-th best distance of query 0 is 64 W, in the selection's last bin
+            far += 1
+            assert g["rows"].shape[1] in (4, 16) and int(g["n_bits"]) == 64 * g["rows"].shape[1]
+            bc.check_far(g["rows"], g["queries"], k, 0)
         big_head |= k > 16 and any(len(np.unique(d[q, :k])) < k for q in range(d.shape[0]))
-    assert big_head
+    assert big_head and far == 2
     for p in glob.glob(os.path.join(GOLD, "rerank_*.npz")):
         g = np.load(p)
         k = int(g["k"])
@@ -63,6 +68,63 @@ def test_fixtures_are_not_vacuous():
             s = np.sort(e)
             across |= bool(s[k - 1] == s[k])
         assert inside and across, p
+
+
+def test_edge_inputs_every_width():
+    """tests/bitvec_cases.py, the inputs of tests/test_bitvec_edges_gpu.py: each builder asserts what makes its input
+    worth running, and the properties the GPU tests lean on are checked again here"""
+    for W in range(1, 17):
+        n_bits, rows, queries = bc.every_width(W)
+        assert (n_bits + 63) // 64 == W and (n_bits % 64 != 0) == (W % 2 == 1)
+        assert rows.shape == (1025, W) and queries.shape == (65, W)
+        d0 = br.hamming_dists(rows, queries[:1])[0]
+        assert bc.crosses(d0, 17)
+        if W % 2:  # the noise counts: some distance of the whole rows is not the distance of the first n_bits bits
+            keep = ~np.uint64((1 << (64 - n_bits % 64)) - 1)
+            masked_r, masked_q = rows.copy(), queries.copy()
+            masked_r[:, -1] &= keep
+            masked_q[:, -1] &= keep
+            assert not np.array_equal(br.hamming_dists(masked_r, masked_q[:2]), br.hamming_dists(rows, queries[:2]))
+
+
+def test_edge_inputs_far_crowd():
+    for W in range(1, 17):  # bitvec_select_m: every distance up to 64 W has a bin, and no M below it would do
+        M = bc.select_m(W)
+        assert 255 * M >= 64 * W > 255 * (M - 1)
+    # the widths at which M steps up: there an M one less ends below 64 W and merges 64 W and 64 W - 1 in its last bin
+    steps = [W for W in range(2, 17) if bc.select_m(W) > bc.select_m(W - 1)]
+    assert steps == [4, 8, 12, 16] and all(255 * (bc.select_m(W) - 1) <= 64 * W - 1 for W in steps)
+    assert set(bc.FAR_WIDTHS) >= {4, 8, 12, 16} and 1 in bc.FAR_WIDTHS and 3 in bc.FAR_WIDTHS
+    for W in bc.FAR_WIDTHS:
+        rows, queries = bc.far_crowd(W)
+        s = np.sort(br.hamming_dists(rows, queries[:1])[0])
+        assert s[0] == 64 * W - 3 and s[-1] == 64 * W
+        ks = [bc.far_k(rows, queries, off) for off in (0, 1)]
+        for k, off in zip(ks, (0, 1)):
+            assert s[k - 1] == 64 * W - off == s[k]
+    rows, queries = bc.far_crowd(8, n=1100)
+    bc.check_far(rows, queries, 1024, 0)
+
+
+def test_edge_inputs_seams_rerank_and_infinities():
+    rows, base, want = bc.seam_query()
+    assert rows.shape == (64, 1) and bc.distinct_answers(*want)
+    nq = bc.QUERY_CHUNK + 5
+    q = bc.periodic(base, nq)
+    assert np.array_equal(q[bc.QUERY_CHUNK], base[bc.QUERY_CHUNK % bc.PERIOD]) and bc.QUERY_CHUNK % bc.PERIOD != 0
+    at = bc.seam_window(nq)
+    assert bc.QUERY_CHUNK - 1 in at and bc.QUERY_CHUNK in at and nq - 1 in at
+    assert bc.distinct_answers(*bc.seam_rerank()[4])
+    bc.small_chunks()
+    assert bc.REFINER_MAX_DIM == 8176 and bc.RERANK_MAX_DIM == 14272 and bc.RERANK_DIMS[-1] == bc.REFINER_MAX_DIM
+    assert [D % 4 for D in bc.RERANK_DIMS[:3]] == [1, 2, 0] and all(D > bc.RR_THREADS for D in bc.RERANK_DIMS)
+    for D in bc.RERANK_DIMS[:4]:
+        bc.rerank_edge(D)
+    rows, queries, X, XQ, k, factor = bc.infinite_case()
+    with np.errstate(over="ignore"):
+        lab, dis = br.query_rerank(rows, queries, X, XQ, k, factor)
+    assert (lab >= 0).all() and np.isinf(dis[:, k - 1]).all() and np.isfinite(dis[:, 0]).all()
+    assert float(np.float32(3e19)) ** 2 > float(br.FLT_MAX)
 
 
 def test_indices_supplied_is_dist_seq_order():

@@ -81,6 +81,31 @@ def test_obj_stale_without_depfile_and_with_a_missing_dependency(built, tmp_path
     assert build._obj_stale(src)
 
 
+def test_obj_stale_when_the_depfile_names_another_tree(built, tmp_path, monkeypatch):
+    """a build copied to another place with its objects: the depfiles still name the files of the tree they were
+    written in, which exist and are older than the objects, and none of them is a file of this tree"""
+    src = "vaq_merge.hip"
+    real = build._obj(src)
+    monkeypatch.setattr(build, "OBJDIR", str(tmp_path))
+    o = build._obj(src)
+    for ext in ("", ".flags", ".d"):
+        shutil.copy2(real + ext, o + ext)
+    assert not build._obj_stale(src)
+    other = tmp_path / "other_tree"
+    shutil.copytree(CSRC, other / "vaq_amd" / "csrc", copy_function=shutil.copy2)
+    shutil.copytree(INCLUDE, other / "include", copy_function=shutil.copy2)
+    here = build.ROOT + os.sep
+    moved = [str(other) + os.sep + d[len(here):] if d.startswith(here) else d
+             for d in build.parse_depfile(open(o + ".d").read())]
+    with open(o + ".d", "w") as f:
+        f.write("x.o: " + " \\\n  ".join(d.replace(" ", "\\ ") for d in moved) + "\n")
+    deps = build.parse_depfile(open(o + ".d").read())
+    assert deps == moved
+    assert str(other / "vaq_amd" / "csrc" / src) in deps and all(os.path.exists(d) for d in deps)
+    assert all(os.path.getmtime(d) <= os.path.getmtime(o) for d in deps)
+    assert build._obj_stale(src)
+
+
 def test_sources_are_the_units_in_csrc():
     units = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".cpp")))
     assert sorted(build.SOURCES) == units

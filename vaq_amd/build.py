@@ -102,7 +102,12 @@ def _obj_stale(src: str) -> bool:
         return True
     if not os.path.exists(o + ".d"):
         return True
-    return any(not os.path.exists(d) or os.path.getmtime(d) > t for d in parse_depfile(open(o + ".d").read()))
+    deps = parse_depfile(open(o + ".d").read())
+    # a depfile that does not name this tree's own unit was written in another tree (a build copied or moved with
+    # its objects): what it names are that tree's files, which say nothing about the ones here
+    if os.path.realpath(os.path.join(CSRC, src)) not in {os.path.realpath(d) for d in deps}:
+        return True
+    return any(not os.path.exists(d) or os.path.getmtime(d) > t for d in deps)
 
 
 def build_lib(force: bool = False, verbose: bool = False) -> str:

@@ -56,6 +56,8 @@ struct RerankLt {
 };
 // std::sort of n <= 1024 pairs.  Guarded: with finite distances (the contract) the walk is std::sort's own; with a
 // NaN the real function may leave the array, this one stops at its ends.
+// +inf is inside the contract: finite rows whose squared distance overflows compare equal at +inf, keep their
+// labels and rank by position behind every finite candidate, as in the reference; their distance is inf, not FLT_MAX.
 __host__ __device__ inline void rerank_sort(RerankPair *f, int n) { stdsort::sort_by<10, true>(f, n, RerankLt{}); }
 
 }  // namespace vaq
