@@ -217,6 +217,63 @@ def test_fused_refuses_other_rows(vaqlib):
     v.close()
 
 
+@pytest.mark.parametrize("exact", [False, True])
+def test_two_streams_share_one_refiner(vaqlib, exact):
+    """A refiner's workspaces -- the exhaustive form's lists, the fused call's candidates -- are shared by its callers'
+    streams.  Two streams, A with (nq, k) = (9, 20) and B with (70, 7), calls interleaved A B A B and nothing
+    synchronised until all are enqueued: the exhaustive search_device over 600 integer rows of 8 dims, then the fused
+    vaqhip_search_refine_device (R = 40) over 3000 integer rows of 32 dims behind an index with the d32_m8_b8 golden's
+    codebooks (a refiner has one D: one per form, each used from both streams).  Every answer is the restatement's,
+    slot for slot.  The fused call's candidates are the index's own search(R) made beforehand, with exact_ties on the
+    index in both cases so that rows of equal code distance leave one candidate list."""
+    import ctypes as C
+    import torch
+    import vaq_amd
+    from test_exhaustive_gpu import want
+    rng = np.random.default_rng(83)
+    shapes, R = ((9, 20), (70, 7)), 40
+    Xs = rng.integers(0, 6, size=(600, 8)).astype(np.float32)
+    Qs = [rng.integers(0, 6, size=(nq, 8)).astype(np.float32) for nq, _ in shapes]
+    Xf = rng.integers(-40, 41, size=(3000, 32)).astype(np.float32)
+    Qf = [rng.integers(-40, 41, size=(nq, 32)).astype(np.float32) for nq, _ in shapes]
+    v, _ = golden_index("d32_m8_b8", True)
+    v.encode(Xf, projected=False)
+    cand = [v.search(q, R).labels.reshape(len(q), R) for q in Qf]
+    rs, rf = vaq_amd.VaqRefiner(8), vaq_amd.VaqRefiner(32)
+    rs.set_rows(Xs)
+    rf.set_rows(Xf)
+    rs.exact_ties = rf.exact_ties = exact
+    d_Qs, d_Qf = [torch.from_numpy(q).cuda() for q in Qs], [torch.from_numpy(q).cuda() for q in Qf]
+    fused = [(torch.empty((nq, k), dtype=torch.int32, device="cuda"), torch.empty((nq, k), dtype=torch.float32, device="cuda"))
+             for nq, k in shapes]
+    p = lambda t: C.c_void_p(t.data_ptr())
+    torch.cuda.synchronize()
+    streams = [torch.cuda.Stream(), torch.cuda.Stream()]
+    found = [None, None]
+    try:
+        for i, s in enumerate(streams):
+            with torch.cuda.stream(s):
+                found[i] = rs.search_device(d_Qs[i], shapes[i][1])
+        for i, s in enumerate(streams):
+            nq, k = shapes[i]
+            assert vaqlib.vaqhip_search_refine_device(v._h, rf._h, p(d_Qf[i]), nq, R, k, p(fused[i][0]), p(fused[i][1]),
+                                                      C.c_void_p(s.cuda_stream)) == 0
+        for s in streams:
+            s.synchronize()
+        for i, (nq, k) in enumerate(shapes):
+            want_l, want_d = want(Qs[i], Xs, k, exact)
+            assert np.array_equal(found[i][0].cpu().numpy(), want_l), (i, "exhaustive")
+            assert bits_equal(found[i][1].cpu().numpy(), want_d), (i, "exhaustive")
+            want_l, want_d = rr.refine(Qf[i], Xf, cand[i], k, exact=exact)
+            assert np.array_equal(fused[i][0].cpu().numpy(), want_l), (i, "fused")
+            assert bits_equal(fused[i][1].cpu().numpy(), want_d), (i, "fused")
+    finally:
+        torch.cuda.synchronize()
+        rs.close()
+        rf.close()
+        v.close()
+
+
 def test_cpp_demo_refine_resident(vaqlib, oracle, tmp_path):
     """demo_vaqhip --refine 100,200 --refine-resident on a 20 000 x 128 float, non-integer base: the answer files
     are what the restatement predicts from the oracle's search result, label for label"""

@@ -13,6 +13,8 @@ namespace vaq {
 
 // rows of the FAST code image are padded to this (the reference pads mCodebookCMajor to 32, VAQ.cpp:666-670)
 constexpr int FAST_ROW_PAD = 32;
+// rows an image of n rows holds with its padding: one pad at least
+inline int64_t fast_pad_rows(int64_t n) { return (n > 0 ? (n + FAST_ROW_PAD - 1) / FAST_ROW_PAD : 1) * FAST_ROW_PAD; }
 // dwords per (row, lane group) of the FAST code image: code s = 4t + h sits in group h, nibble t
 __host__ __device__ inline int fast_code_words(int M) { return (M / 4 + 7) / 8; }
 

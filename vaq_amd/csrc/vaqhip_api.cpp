@@ -140,10 +140,7 @@ int vaqhip_index_create_ex(vaqhip_index **out, int D, int M, const int *bits,
   if (M % 4 != 0 && !seq)
     return fail(VAQHIP_EINVAL, "M=%d: the reference scan reads 4 codes per step (VAQ.cpp:1741-1746)", M);
   if (D % M != 0) return fail(VAQHIP_EINVAL, "D=%d is not a multiple of M=%d", D, M);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(VAQHIP_ENODEVICE, "no HIP device available (this library has no CPU path)");
-  if (device_id < 0 || device_id >= ndev) return fail(VAQHIP_EINVAL, "device_id=%d of %d", device_id, ndev);
+  if (int rc = check_device_id(device_id)) return rc;
 
   vaqhip_index *ix = new (std::nothrow) vaqhip_index();
   if (!ix) return fail(VAQHIP_ENOMEM, "host allocation");
@@ -238,12 +235,9 @@ int vaqhip_index_create_ex(vaqhip_index **out, int D, int M, const int *bits,
 void vaqhip_index_destroy(vaqhip_index *ix) {
   if (!ix) return;
   DeviceGuard g(ix->device);
-  if (ix->stream) {
-    (void)hipStreamSynchronize(ix->stream);
-    (void)hipStreamDestroy(ix->stream);
-  }
+  if (ix->stream) (void)hipStreamSynchronize(ix->stream);
+  close_handle(ix);
   for (auto &e : ix->ev) (void)hipEventDestroy(e);
-  if (ix->ws_event) (void)hipEventDestroy(ix->ws_event);
   delete ix;  // every DevBuf goes here: the index's device is current, its stream idle and gone
 }
 

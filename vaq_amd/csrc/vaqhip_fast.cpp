@@ -39,7 +39,7 @@ int fast_codes_update(vaqhip_index *ix, const uint16_t *d_u16, int64_t row_begin
     return VAQHIP_OK;
   }
   const size_t row_bytes = (size_t)16 * vaq::fast_code_words(ix->M);
-  const int64_t n_pad = std::max<int64_t>(1, (row_end + vaq::FAST_ROW_PAD - 1) / vaq::FAST_ROW_PAD) * vaq::FAST_ROW_PAD;
+  const int64_t n_pad = vaq::fast_pad_rows(row_end);
   if (n_pad > ix->fast_cap || row_begin == 0) {
     const int64_t cap = row_begin == 0 ? n_pad
                                        : std::max<int64_t>(n_pad, (2 * ix->fast_cap) / vaq::FAST_ROW_PAD * vaq::FAST_ROW_PAD);
@@ -126,8 +126,7 @@ int vaqhost::search_fast(vaqhip_index *ix, const float *d_queries, int nq, int k
   if (nq == 0) return VAQHIP_OK;
   WS_SCOPE(ws, ix, st);
   if (int rc = fast_codes_ensure(ix, st)) return rc;
-  const int64_t N = ix->N;
-  const int64_t n_pad = std::max<int64_t>(1, (N + vaq::FAST_ROW_PAD - 1) / vaq::FAST_ROW_PAD) * vaq::FAST_ROW_PAD;
+  const int64_t N = ix->N, n_pad = vaq::fast_pad_rows(N);
   const int kk = (int)std::min<int64_t>(k, N);
   // the distance matrix of a chunk stays within 1 GiB
   const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)nq, (int64_t)QUERY_CHUNK, ((int64_t)1 << 29) / n_pad}));

@@ -1,10 +1,13 @@
-// vaqhip_index.h -- what the host files of the single-device index share: the index itself, its device
-// buffers (vaqhip_dev.h), the entry preamble, the workspace scope, the launch plan and the few functions
-// that cross files -- among them the one encode driver (EncodeRule, encode_rows_locked and its two entries: defined in
-// vaqhip_api.cpp, called there for vaqhip_encode* and from vaqhip_lutfit.cpp for vaqhip_encode_lut*).  Private to
-// vaqhip_api.cpp, vaqhip_plan.cpp, vaqhip_search.cpp, vaqhip_codes.cpp, vaqhip_fast.cpp and vaqhip_lutfit.cpp (vaqhip_refiner.cpp takes
-// fail(), HIP_TRY and the device types from here and reaches the index through include/vaqhip.h): the multi-device host
-// (vaqhip_multi*.cpp) sees the index through include/vaqhip.h and vaqhip_internal.h only.
+// vaqhip_index.h -- what the host files of the single-device index share: the index itself (a handle of
+// vaqhip_handle.h, which has fail(), HIP_TRY, the entry preamble and the workspace scope), its device buffers
+// (vaqhip_dev.h), the launch plan and the few functions that cross files -- among them the one encode driver
+// (EncodeRule, encode_rows_locked and its two entries: defined in vaqhip_api.cpp, called there for vaqhip_encode* and
+// from vaqhip_lutfit.cpp for vaqhip_encode_lut*).  Private to vaqhip_api.cpp, vaqhip_plan.cpp, vaqhip_search.cpp,
+// vaqhip_codes.cpp, vaqhip_fast.cpp, vaqhip_learn.cpp, vaqhip_lutfit.cpp, vaqhip_codebooks.cpp and vaqhip_train.cpp;
+// vaqhip_refiner.cpp takes the bodies it runs over its resident rows from here (learn_rows_device,
+// fit_codebooks_rows_device, train_*_rows_device) and reaches the index itself through include/vaqhip.h;
+// vaqhip_bitvec.cpp takes QUERY_CHUNK.  The multi-device host (vaqhip_multi*.cpp) sees the index through
+// include/vaqhip.h and vaqhip_internal.h only.
 #ifndef VAQHIP_INDEX_H
 #define VAQHIP_INDEX_H
 #include "vaqhip.h"
@@ -21,21 +24,11 @@
 #include "vaq_scan_bm.h"
 #include "vaq_scan_params.h"
 #include "vaqhip_dev.h"
+#include "vaqhip_handle.h"
 #include "vaqhip_internal.h"
 
 // (hidden: none of this joins the library's exported symbols)
 namespace vaqhost __attribute__((visibility("hidden"))) {
-
-// sets vaqhip_last_error()'s text for this thread (vaqhip_api.cpp) and returns `code`
-int fail(int code, const char *fmt, ...);
-
-#define HIP_TRY(expr)                                                                     \
-  do {                                                                                    \
-    hipError_t e_ = (expr);                                                               \
-    if (e_ != hipSuccess)                                                                 \
-      return fail(e_ == hipErrorOutOfMemory ? VAQHIP_ENOMEM : VAQHIP_EHIP, "%s: %s", #expr, \
-                  hipGetErrorString(e_));                                                 \
-  } while (0)
 
 constexpr int QUERY_CHUNK = 16384;             // queries per internal launch set
 // (launch_cost_order pays from about one residency of workgroups on: 7 per CU)
@@ -61,11 +54,11 @@ struct StagedState {
 
 } // namespace vaqhost
 
-struct vaqhip_index {
+struct vaqhip_index : vaqhost::HandleCore {
   using DevBuf = vaqhost::DevBuf;
   int D = 0, M = 0, L = 0;
   int max_bits = 0, min_bits = 0, total_bits = 0, W = 0, layout = 0, lut_floats = 0;
-  int device = 0, n_cu = 256;
+  int n_cu = 256;
   std::vector<int> bits;
   std::vector<vaq::SubDesc> sub;
   DevBuf d_cent, d_cent_t, d_eig, d_sub, d_first_sub, d_codes, d_perm, d_bstart;
@@ -116,14 +109,6 @@ struct vaqhip_index {
   // BitVecEngine::binaryEncodingLUT on the host, its prefix maxima packed on the device (vaq_lutfit.h)
   std::vector<float> lut_q;
   DevBuf d_lut_pm;
-  hipStream_t stream = nullptr;
-  // The workspaces above are shared by every call on this index.  Host-side enqueues are
-  // serialised by `mu`, but `_device` entry points run on the caller's stream: the last enqueue
-  // that used the workspaces leaves an event, and a call on a DIFFERENT stream makes its stream
-  // wait for it first (same stream: in order anyway).
-  hipEvent_t ws_event = nullptr;
-  hipStream_t ws_stream = nullptr;
-  bool ws_used = false;
   // options
   int opt_qb = 0, opt_slices = 0, opt_timing = 0, opt_ea = 3, opt_nwaves = 0, opt_seed = 1, opt_hot = 16, opt_seed_frac = 64, opt_order = 0, opt_bucket_bits = 0, opt_no_skip = 0, opt_bf = 1, opt_group = 1, opt_defer = 0, opt_cost_order = 1, opt_bm = 1, opt_bm_cap = 0, opt_bm_units = 0, opt_bm_qb = 0, opt_bm_nwaves = 0, opt_sub_order = 1, opt_bm_sub = 1, opt_bm_boot = 1, opt_bm_round = 6, opt_exact = 0;
   // timing: a ring of 5-event sets, one per search since the last read
@@ -133,7 +118,6 @@ struct vaqhip_index {
   vaqhip_timing last = {};
   vaqhip_kmeans_timing km_last = {};  // the last vaqhip_index_cluster_ti_kmeans
   vaqhip_learn_timing learn_last = {};  // the last device-form learnQuantization (vaqhip_learn.cpp)
-  std::mutex mu;
 };
 
 namespace vaqhost __attribute__((visibility("hidden"))) {
@@ -207,55 +191,6 @@ int train_moment_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, dou
 int train_rotation_rows_device(int device, vaq::RowsRef d_X, int64_t n, int D, int M, int bit_budget, int min_bits,
                                int max_bits, float percent_var, float *eigvec_out, float *eigenvalues_out, int *bits_out,
                                int *highest_subs_out);
-
-// The preamble of an entry point: the index's lock, then its device current (put back when the scope ends).
-// rc: VAQHIP_OK, or what the entry returns at once -- ENTRY(ix) declares it and does so, as HIP_TRY would.
-#define ENTRY(ix) Entry entry_(ix); if (entry_.rc) return entry_.rc
-struct Entry {
-  std::lock_guard<std::mutex> lk;
-  DeviceGuard g;
-  int rc;
-  explicit Entry(vaqhip_index *ix)
-      : lk(ix->mu), g(ix->device),
-        rc(g.ok ? VAQHIP_OK : fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", ix->device)) {}
-};
-
-// Around the enqueueing of work that touches the index's shared workspaces on stream `st`: construction makes
-// `st` wait for the last such work on another stream (rc: its code), finish() leaves the event for the next call
-// and is the success path.  A return before finish() is a failure with work possibly enqueued already: the
-// destructor leaves the event all the same, without touching the failure's code and text.
-// WS_SCOPE(ws, ix, st) declares the scope and returns its code at once when the construction failed.
-// Owner: the index, or another handle that keeps the same three members (ws_event, ws_stream, ws_used) for workspaces
-// of its own (vaqhip_bitvec.cpp); the macro's argument names it.
-#define WS_SCOPE(name, ix, st) WsScope name(ix, st); if (name.rc) return name.rc
-template <class Owner> struct WsScope {
-  Owner *ix;
-  hipStream_t st;
-  bool open = false;
-  int rc;
-  WsScope(Owner *ix, hipStream_t st) : ix(ix), st(st), rc(acquire()) { open = rc == VAQHIP_OK; }
-  WsScope(const WsScope &) = delete;
-  ~WsScope() {
-    if (open && hipEventRecord(ix->ws_event, st) == hipSuccess) mark();
-  }
-  int finish() {
-    open = false;
-    HIP_TRY(hipEventRecord(ix->ws_event, st));
-    mark();
-    return VAQHIP_OK;
-  }
-
- private:
-  int acquire() {
-    if (!ix->ws_event) HIP_TRY(hipEventCreateWithFlags(&ix->ws_event, hipEventDisableTiming));
-    if (ix->ws_used && st != ix->ws_stream) HIP_TRY(hipStreamWaitEvent(st, ix->ws_event, 0));
-    return VAQHIP_OK;
-  }
-  void mark() {
-    ix->ws_stream = st;
-    ix->ws_used = true;
-  }
-};
 
 inline int ensure_events(vaqhip_index *ix) {
   if (!ix->ev.empty()) return VAQHIP_OK;

@@ -162,8 +162,8 @@ template <class Call> int through_staging(vaqhip_multi_refiner *r, const float *
   int rc = 0;
   hipError_t e = hipEventSynchronize(r->finished);  // (the staging may grow: nothing reads it any more)
   if (e == hipSuccess)  // (a call that succeeds leaves the first device current: its last step runs there)
-    e = through_staging(r->w, s.stream, r->D, std::min(nq, SET_QUERIES), queries, nq, labels_in, R, k, labels_out, distances_out,
-                        rc, [&](int n) { return call(n, s.stream); });
+    e = through_staging(r->w, s.stream, {{&r->w.q, queries, r->D * sizeof(float)}, {&r->w.lin, labels_in, R * sizeof(int32_t)}},
+                        std::min(nq, SET_QUERIES), nq, k, labels_out, distances_out, rc, [&](int n) { return call(n, s.stream); });
   if (e != hipSuccess) return mfail(hip_code(e), "device %d: %s", s.device, hipGetErrorString(e));
   if (rc && !s.err.empty()) return mfail(rc, "device %d: %s", s.device, s.err.c_str());
   return rc;

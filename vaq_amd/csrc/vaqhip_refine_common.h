@@ -85,29 +85,48 @@ struct RowStore {
     cap_rows = want;
     return hipSuccess;
   }
+  // rows [at, at + n) of row_bytes each from X, the device's (enqueued on st and waited for) or the host's (a
+  // synchronous copy); the caller has made room, and for a set has waited for the device (a refine enqueued on any
+  // stream may still read the old rows)
+  hipError_t write(const void *X, int64_t at, int64_t n, size_t row_bytes, bool on_device, hipStream_t st) {
+    char *dst = buf.as<char>() + (size_t)at * row_bytes;
+    if (n > 0 && on_device) XS_TRY(hipMemcpyAsync(dst, X, (size_t)n * row_bytes, hipMemcpyDeviceToDevice, st));
+    if (on_device) XS_TRY(hipStreamSynchronize(st));
+    if (n > 0 && !on_device) XS_TRY(hipMemcpy(dst, X, (size_t)n * row_bytes, hipMemcpyHostToDevice));
+    return hipSuccess;
+  }
 };
 
-// the workspaces of the host forms (queries, candidate labels, the answer) and the fused call's candidates
+// the workspaces of the host forms (queries, the refiners' candidate labels, the Hamming engine's raw queries, the
+// answer) and the candidates of a fused call
 struct StagingBufs {
-  DevBuf q, lin, lout, dout, cand_l, cand_d;
-  void release() { release_all({&q, &lin, &lout, &dout, &cand_l, &cand_d}); }
+  DevBuf q, lin, oq, lout, dout, cand_l, cand_d;
+  void release() { release_all({&q, &lin, &oq, &lout, &dout, &cand_l, &cand_d}); }
 };
 
-// The host form of a device call: chunks of `chunk` queries through `w` on stream st; labels_in may be null.  call(n)
-// runs one staged chunk from w.q (w.lin) into w.lout, w.dout and returns the host's code; a code other than 0 ends
+// one input of a host form: `bytes` per query from `host` into `buf`; a null `host` leaves the input out
+struct StagedInput {
+  DevBuf *buf;
+  const void *host;
+  size_t bytes;
+};
+
+// The host form of a device call: chunks of `chunk` queries through `w` on stream st.  call(n) runs one staged chunk
+// from the inputs' buffers into w.lout, w.dout (k per query) and returns the host's code; a code other than 0 ends
 // the loop and is left in rc.  Returns the first HIP error.
-template <class Call> hipError_t through_staging(StagingBufs &w, hipStream_t st, int D, int chunk, const float *queries, int nq,
-                                                 const int32_t *labels_in, int R, int k, int32_t *labels_out,
-                                                 float *distances_out, int &rc, Call &&call) {
-  XS_TRY(w.q.ensure((size_t)chunk * D * sizeof(float)));
-  if (labels_in) XS_TRY(w.lin.ensure((size_t)chunk * R * sizeof(int32_t)));
+template <class Call> hipError_t through_staging(StagingBufs &w, hipStream_t st, std::initializer_list<StagedInput> inputs,
+                                                 int chunk, int nq, int k, int32_t *labels_out, float *distances_out,
+                                                 int &rc, Call &&call) {
+  for (const StagedInput &in : inputs)
+    if (in.host) XS_TRY(in.buf->ensure((size_t)chunk * in.bytes));
   XS_TRY(w.lout.ensure((size_t)chunk * k * sizeof(int32_t)));
   XS_TRY(w.dout.ensure((size_t)chunk * k * sizeof(float)));
   for (int q0 = 0; q0 < nq; q0 += chunk) {
     const int n = std::min(chunk, nq - q0);
-    XS_TRY(hipMemcpyAsync(w.q.p, queries + (size_t)q0 * D, (size_t)n * D * sizeof(float), hipMemcpyHostToDevice, st));
-    if (labels_in)
-      XS_TRY(hipMemcpyAsync(w.lin.p, labels_in + (size_t)q0 * R, (size_t)n * R * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    for (const StagedInput &in : inputs)
+      if (in.host)
+        XS_TRY(hipMemcpyAsync(in.buf->p, static_cast<const char *>(in.host) + (size_t)q0 * in.bytes, (size_t)n * in.bytes,
+                              hipMemcpyHostToDevice, st));
     if ((rc = call(n)) != 0) return hipSuccess;
     XS_TRY(hipMemcpyAsync(labels_out + (size_t)q0 * k, w.lout.p, (size_t)n * k * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     XS_TRY(hipMemcpyAsync(distances_out + (size_t)q0 * k, w.dout.p, (size_t)n * k * sizeof(float), hipMemcpyDeviceToHost, st));

@@ -12,21 +12,17 @@
 
 using namespace vaqhost;
 
-struct vaqhip_refiner {
-  int device = 0, D = 0;
+struct vaqhip_refiner : HandleCore {
+  int D = 0;
   int64_t N = 0, id_base = 0;
   RefineOptions opt;  // ("timing": around the phases of the exhaustive form)
   RowStore rows;
-  StagingBufs w;  // of the host forms and of the fused call (grow-only)
+  // of the host forms and of the fused call (grow-only); the candidate buffers of the fused _device call and the
+  // exhaustive form's workspace are shared by the callers' streams (WS_SCOPE)
+  StagingBufs w;
   XsWork xs;  // the exhaustive form's
   vaqhip_refiner_search_timing x_timing = {};
-  hipStream_t stream = nullptr;
-  // the candidate buffers of the fused _device call are shared by its callers' streams: as on the index, the last
-  // enqueue leaves an event and a call on another stream waits for it first
-  hipEvent_t ws_event = nullptr;
-  hipStream_t ws_stream = nullptr;
-  bool ws_used = false;
-  std::mutex mu;
+  __attribute__((noinline)) ~vaqhip_refiner() = default;  // (one copy for create and destroy, as the library has exported it so far)
 };
 
 namespace vaqhost {
@@ -38,15 +34,6 @@ namespace {
 
 constexpr RefineHost REFINER = {fail, "refiner"};
 constexpr int HOST_CHUNK = 65536;  // queries per launch of the host forms
-
-struct REntry {
-  std::lock_guard<std::mutex> lk;
-  DeviceGuard g;
-  int rc;
-  explicit REntry(vaqhip_refiner *r)
-      : lk(r->mu), g(r->device), rc(g.ok ? VAQHIP_OK : fail(VAQHIP_ENODEVICE, "hipSetDevice(%d) failed", r->device)) {}
-};
-#define RENTRY(r) REntry entry_(r); if (entry_.rc) return entry_.rc
 
 int refine_locked(vaqhip_refiner *r, const float *d_q, int nq, const int32_t *d_lin, int R, int k, int32_t *d_lout,
                   float *d_dout, hipStream_t st) {
@@ -74,15 +61,10 @@ int search_refine_locked(vaqhip_index *ix, vaqhip_refiner *r, const float *d_q, 
                          float *d_dout, hipStream_t st) {
   HIP_TRY(r->w.cand_l.ensure((size_t)nq * R * sizeof(int32_t)));
   HIP_TRY(r->w.cand_d.ensure((size_t)nq * R * sizeof(float)));
-  if (!r->ws_event) HIP_TRY(hipEventCreateWithFlags(&r->ws_event, hipEventDisableTiming));
-  if (r->ws_used && st != r->ws_stream) HIP_TRY(hipStreamWaitEvent(st, r->ws_event, 0));
-  int rc = vaqhip_search_device(ix, d_q, nq, R, 0, r->w.cand_l.as<int32_t>(), r->w.cand_d.as<float>(), st);
-  if (!rc) rc = refine_locked(r, d_q, nq, r->w.cand_l.as<int32_t>(), R, k, d_lout, d_dout, st);
-  if (hipEventRecord(r->ws_event, st) == hipSuccess) {  // (also after a failure: work may be enqueued already)
-    r->ws_stream = st;
-    r->ws_used = true;
-  }
-  return rc;
+  WS_SCOPE(ws, r, st);
+  if (int rc = vaqhip_search_device(ix, d_q, nq, R, 0, r->w.cand_l.as<int32_t>(), r->w.cand_d.as<float>(), st)) return rc;
+  if (int rc = refine_locked(r, d_q, nq, r->w.cand_l.as<int32_t>(), R, k, d_lout, d_dout, st)) return rc;
+  return ws.finish();
 }
 
 // ---- the exhaustive form ----
@@ -94,8 +76,7 @@ int search_locked(vaqhip_refiner *r, const float *d_q, int nq, int k, int32_t *d
   const int k1 = exact ? k + 1 : k;
   const XsPlan pl = xs_plan(r->xs, r->N, r->opt.splits, nq, k1);
   HIP_TRY(r->xs.fit(pl, k1, exact, r->opt.timing != 0));
-  if (!r->ws_event) HIP_TRY(hipEventCreateWithFlags(&r->ws_event, hipEventDisableTiming));
-  if (r->ws_used && st != r->ws_stream) HIP_TRY(hipStreamWaitEvent(st, r->ws_event, 0));
+  WS_SCOPE(ws, r, st);
   r->x_timing = {};
   r->x_timing.splits = pl.S;
   r->x_timing.register_form = r->D <= (int)vaq::exhaust_register_max_dim();
@@ -104,21 +85,17 @@ int search_locked(vaqhip_refiner *r, const float *d_q, int nq, int k, int32_t *d
   for (int q0 = 0; q0 < nq && e == hipSuccess; q0 += pl.chunk)
     e = xs_search_set(r->xs, pl, rows, d_q + (size_t)q0 * r->D, std::min(pl.chunk, nq - q0), k, exact,
                       d_lout + (size_t)q0 * k, d_dout + (size_t)q0 * k, st, r->opt.timing ? &r->x_timing : nullptr);
-  const int rc = e == hipSuccess ? VAQHIP_OK
-                                 : fail(e == hipErrorOutOfMemory ? VAQHIP_ENOMEM : VAQHIP_EHIP, "exhaustive search: %s",
-                                        hipGetErrorString(e));
-  if (hipEventRecord(r->ws_event, st) == hipSuccess) {  // (also after a failure: work may be enqueued already)
-    r->ws_stream = st;
-    r->ws_used = true;
-  }
-  return rc;
+  if (e != hipSuccess)
+    return fail(e == hipErrorOutOfMemory ? VAQHIP_ENOMEM : VAQHIP_EHIP, "exhaustive search: %s", hipGetErrorString(e));
+  return ws.finish();
 }
 
 // the host form of a device call on the refiner's stream (vaqhip_refine_common.h); caller holds r->mu
 template <class Call> int through_staging(vaqhip_refiner *r, int chunk, const float *queries, int nq, const int32_t *labels_in,
                                           int R, int k, int32_t *labels_out, float *distances_out, Call &&call) {
   int rc = 0;
-  HIP_TRY(through_staging(r->w, r->stream, r->D, chunk, queries, nq, labels_in, R, k, labels_out, distances_out, rc, call));
+  HIP_TRY(through_staging(r->w, r->stream, {{&r->w.q, queries, r->D * sizeof(float)}, {&r->w.lin, labels_in, R * sizeof(int32_t)}},
+                          chunk, nq, k, labels_out, distances_out, rc, call));
   return rc;
 }
 
@@ -128,18 +105,14 @@ int set_rows_any(vaqhip_refiner *r, const void *X, int elem, bool on_device, int
   if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
   if (N < 0 || (N > 0 && !X)) return fail(VAQHIP_EINVAL, "bad rows");
   if (int rc = check_labels_fit(REFINER, N, id_base)) return rc;
-  RENTRY(r);
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  ENTRY(r);
   if (r->rows.elem != elem) {  // (the rows there are go either way: a failure below leaves none, not rows misread)
     r->N = 0;
     r->rows.retype(elem, r->D);
   }
   HIP_TRY(r->rows.reserve(N, RowStore::DROP, r->D));
   HIP_TRY(hipDeviceSynchronize());
-  const size_t bytes = (size_t)N * r->rows.row_bytes(r->D);
-  if (N > 0 && on_device) HIP_TRY(hipMemcpyAsync(r->rows.buf.p, X, bytes, hipMemcpyDeviceToDevice, st));
-  if (on_device) HIP_TRY(hipStreamSynchronize(st));
-  if (N > 0 && !on_device) HIP_TRY(hipMemcpy(r->rows.buf.p, X, bytes, hipMemcpyHostToDevice));
+  HIP_TRY(r->rows.write(X, 0, N, r->rows.row_bytes(r->D), on_device, static_cast<hipStream_t>(stream)));
   r->N = N;
   r->id_base = id_base;
   return VAQHIP_OK;
@@ -149,7 +122,7 @@ int add_rows_any(vaqhip_refiner *r, const void *X, int elem, int64_t n_new) {
   if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
   if (n_new < 0 || (n_new > 0 && !X)) return fail(VAQHIP_EINVAL, "bad rows");
   if (n_new == 0) return VAQHIP_OK;
-  RENTRY(r);
+  ENTRY(r);
   if (r->N > 0 && r->rows.elem != elem)
     return fail(VAQHIP_ESTATE, "the refiner holds %s rows: append rows of that type (nothing is converted)",
                 r->rows.elem == 1 ? "uint8" : "float32");
@@ -157,8 +130,7 @@ int add_rows_any(vaqhip_refiner *r, const void *X, int elem, int64_t n_new) {
   r->rows.retype(elem, r->D);
   HIP_TRY(r->rows.reserve(r->N + n_new, r->N, r->D));
   // (rows past N are read by no launch in flight: no wait is needed before they are written)
-  const size_t rb = r->rows.row_bytes(r->D);
-  HIP_TRY(hipMemcpy(r->rows.buf.as<char>() + (size_t)r->N * rb, X, (size_t)n_new * rb, hipMemcpyHostToDevice));
+  HIP_TRY(r->rows.write(X, r->N, n_new, r->rows.row_bytes(r->D), false, nullptr));
   r->N += n_new;
   return VAQHIP_OK;
 }
@@ -174,19 +146,13 @@ int vaqhip_refiner_create(vaqhip_refiner **out, int device_id, int D) {
   if ((size_t)D > vaq::refine_rows_max_dim())
     return fail(VAQHIP_EUNSUPPORTED, "D=%d: the query row must fit the workgroup's LDS (%zu floats)", D,
                 vaq::refine_rows_max_dim());
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    return fail(VAQHIP_ENODEVICE, "no HIP device available (this library has no CPU path)");
-  if (device_id < 0 || device_id >= ndev) return fail(VAQHIP_EINVAL, "device_id=%d of %d", device_id, ndev);
+  if (int rc = check_device_id(device_id)) return rc;
   vaqhip_refiner *r = new (std::nothrow) vaqhip_refiner();
   if (!r) return fail(VAQHIP_ENOMEM, "host allocation");
-  r->device = device_id;
   r->D = D;
-  DeviceGuard g(device_id);
-  hipError_t e = g.ok ? hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking) : hipErrorInvalidDevice;
-  if (e != hipSuccess) {
+  if (int rc = open_handle(r, device_id)) {
     delete r;
-    return fail(VAQHIP_ENODEVICE, "device %d: %s", device_id, hipGetErrorString(e));
+    return rc;
   }
   *out = r;
   return VAQHIP_OK;
@@ -196,8 +162,7 @@ void vaqhip_refiner_destroy(vaqhip_refiner *r) {
   if (!r) return;
   DeviceGuard g(r->device);
   (void)hipDeviceSynchronize();  // (refines enqueued on the callers' streams read the rows)
-  if (r->stream) (void)hipStreamDestroy(r->stream);
-  if (r->ws_event) (void)hipEventDestroy(r->ws_event);
+  close_handle(r);
   r->xs.release();
   delete r;  // every DevBuf goes here, with the refiner's device current
 }
@@ -232,7 +197,7 @@ int vaqhip_refiner_search_device(vaqhip_refiner *r, const float *d_queries, int 
                                  float *d_distances_out, void *stream) {
   if (int rc = check_search(REFINER, r, nq, k, d_queries, d_labels_out, d_distances_out)) return rc;
   if (nq == 0) return VAQHIP_OK;
-  RENTRY(r);
+  ENTRY(r);
   return search_locked(r, d_queries, nq, k, d_labels_out, d_distances_out, static_cast<hipStream_t>(stream));
 }
 
@@ -240,7 +205,7 @@ int vaqhip_refiner_search(vaqhip_refiner *r, const float *queries, int nq, int k
                           float *distances_out) {
   if (int rc = check_search(REFINER, r, nq, k, queries, labels_out, distances_out)) return rc;
   if (nq == 0) return VAQHIP_OK;
-  RENTRY(r);
+  ENTRY(r);
   return through_staging(r, nq, queries, nq, nullptr, 0, k, labels_out, distances_out, [&](int n) {
     return search_locked(r, r->w.q.as<float>(), n, k, r->w.lout.as<int32_t>(), r->w.dout.as<float>(), r->stream);
   });
@@ -258,7 +223,7 @@ int vaqhip_refiner_refine_device(vaqhip_refiner *r, const float *d_queries, int 
   if (int rc = check_sizes(REFINER, r, nq, R, k)) return rc;
   if (nq == 0) return VAQHIP_OK;
   if (!d_queries || !d_labels_in || !d_labels_out || !d_distances_out) return fail(VAQHIP_EINVAL, "null pointer");
-  RENTRY(r);
+  ENTRY(r);
   return refine_locked(r, d_queries, nq, d_labels_in, R, k, d_labels_out, d_distances_out,
                        static_cast<hipStream_t>(stream));
 }
@@ -268,7 +233,7 @@ int vaqhip_refiner_refine(vaqhip_refiner *r, const float *queries, int nq, const
   if (int rc = check_sizes(REFINER, r, nq, R, k)) return rc;
   if (nq == 0) return VAQHIP_OK;
   if (!queries || !labels_in || !labels_out || !distances_out) return fail(VAQHIP_EINVAL, "null pointer");
-  RENTRY(r);
+  ENTRY(r);
   return through_staging(r, std::min(nq, HOST_CHUNK), queries, nq, labels_in, R, k, labels_out, distances_out, [&](int n) {
     return refine_locked(r, r->w.q.as<float>(), n, r->w.lin.as<int32_t>(), R, k, r->w.lout.as<int32_t>(), r->w.dout.as<float>(),
                          r->stream);
@@ -278,7 +243,7 @@ int vaqhip_refiner_refine(vaqhip_refiner *r, const float *queries, int nq, const
 int vaqhip_search_refine_device(vaqhip_index *ix, vaqhip_refiner *r, const float *d_queries_raw, int nq, int R, int k,
                                 int32_t *d_labels_out, float *d_distances_out, void *stream) {
   if (int rc = check_sizes(REFINER, r, nq, R, k)) return rc;
-  RENTRY(r);
+  ENTRY(r);
   if (int rc = check_pair(ix, r, R)) return rc;
   if (nq == 0) return VAQHIP_OK;
   if (!d_queries_raw || !d_labels_out || !d_distances_out) return fail(VAQHIP_EINVAL, "null pointer");
@@ -289,7 +254,7 @@ int vaqhip_search_refine_device(vaqhip_index *ix, vaqhip_refiner *r, const float
 int vaqhip_search_refine(vaqhip_index *ix, vaqhip_refiner *r, const float *queries_raw, int nq, int R, int k,
                          int32_t *labels_out, float *distances_out) {
   if (int rc = check_sizes(REFINER, r, nq, R, k)) return rc;
-  RENTRY(r);
+  ENTRY(r);
   if (int rc = check_pair(ix, r, R)) return rc;
   if (nq == 0) return VAQHIP_OK;
   if (!queries_raw || !labels_out || !distances_out) return fail(VAQHIP_EINVAL, "null pointer");
