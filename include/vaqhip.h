@@ -1472,7 +1472,7 @@ int vaqhip_last_timing(vaqhip_index *ix, vaqhip_timing *out);
  * The host forms are synchronous; the _device forms take pointers on the engine's GPU, enqueue on `stream` and do not
  * synchronise once the workspaces have their size.  Calls on one engine are serialised.  Errors leave their text in
  * vaqhip_last_error(), as the index's and the refiner's do.  Not provided: the other three methods, earlyAbandonRank,
- * the cluster-info, filtering and naive variants, the encoders (binaryEncoding*), a multi-device form. */
+ * the cluster-info, filtering and naive variants, a multi-device form.  The encoders follow the queries below. */
 typedef struct vaqhip_bitvec vaqhip_bitvec;
 #define VAQHIP_BITVEC_HEAP                0  /* BitVecEngine::QueryMethod (BitVecEngine.hpp:82-84) */
 #define VAQHIP_BITVEC_SORT                1
@@ -1495,6 +1495,55 @@ int vaqhip_bitvec_query_rerank(vaqhip_bitvec *bv, vaqhip_refiner *r, const uint6
 int vaqhip_bitvec_query_rerank_device(vaqhip_bitvec *bv, vaqhip_refiner *r, const uint64_t *d_bit_queries,
                                       const float *d_ori_queries, int nq, int k, int factor, int32_t *d_labels_out,
                                       float *d_distances_out, void *stream);
+
+/* ---- Hamming engine: the encoders (BitVecEngine::binaryEncodingSimple and ::binaryEncoding) on the device ------------
+ * Raw rows (float or byte; host, device or resident in a refiner) -> bit rows, with no projected matrix written.  Both
+ * forms start where the eigenvectors, and for the quantile form the bits per dimension, are given: the PCA and the
+ * glpk allocation stay the caller's (vaqhip_train_rotation / vaqhip_sym_eigen_* exist for the first).  Parity-unpinned,
+ * as vaqhip_lut_fit_quantiles is (BitVecEngine.hpp needs glpk.h): the device equals the host build of
+ * vaq_bitvec_encode.h and a NumPy restatement, bit for bit.
+ *   value       x[i][c] is vaqhip_project's, unchecked: one fmaf chain over the inner index ascending from 0.0f, a byte
+ *               widened where it is loaded; with eigvec == NULL the row's own value.  eigvec is D x D row-major.
+ *   sign form   (BitVecEngine.hpp:239-255) n_bits = D, W = (D + 63) / 64; dimension d is bit 63 - d % 64 of word d / 64,
+ *               set where x > 0 (NaN, -0, +0: 0; a positive denormal, +inf: 1); the tail bits are 0.  D % 64 == 63 is
+ *               VAQHIP_EUNSUPPORTED: the reference shifts by 64 there and writes word (D + 1) / 64, past the row's end.
+ *   quantile    (:509-590) bits[D], each 0..8 (0: the dimension is skipped), n_bits = sum(bits).  Thresholds of a
+ *               dimension with b bits, over its column sorted ascending: T[q], q = 0 .. 2^b - 2, is the quantile at
+ *               p = (float)(q + 1) / 2^b with the poi / left / right interpolation of :516-519 -- Q[1 .. 2^b - 1] of
+ *               vaqhip_lut_fit_quantiles with b bits -- and T[2^b - 1] = FLT_MAX.  The code is the FIRST q with
+ *               x <= T[q] (T need not be monotone after rounding; NaN and +inf match none: code 0), its b bits go most
+ *               significant first to bit position sum(bits[0 .. j-1]) of the row's stream (bit 0 = the top bit of
+ *               word 0); a code may straddle two words.
+ *   fit_thresholds   thresholds_out [D][256]: row d gets its 2^bits[d] entries; rows of unallocated dimensions and the
+ *               entries behind 2^bits[d] are left untouched.  The refusals of vaqhip_lut_fit_quantiles (n < 1,
+ *               n >= 2^31, a NaN or infinite value in an allocated column: VAQHIP_EINVAL, nothing written), bits outside
+ *               0..8 VAQHIP_EINVAL, D > 2048 VAQHIP_EUNSUPPORTED.  The _device forms synchronise `stream`.
+ *   set_encoder bits == NULL selects the sign form.  The engine's n_bits must equal D (sign) or sum(bits) (quantile):
+ *               VAQHIP_EINVAL; so are bits outside 0..8 and a NaN among the thresholds in use.  Host pointers; copied.
+ *   encode      X [n][D] -> rows_out uint64 [n][W]; also how a query batch gets its bits before query_device.  The
+ *               _device forms enqueue on `stream` and do not synchronise.  VAQHIP_ESTATE before set_encoder.
+ *   encode_set_rows / encode_add_rows   as set_rows / add_rows from raw host rows: encoded straight into the engine's
+ *               store, zero padding included; the bits never visit the host.
+ *   encode_from_refiner   the same from the float or byte rows a refiner on the engine's device holds (D must be the
+ *               encoder's: VAQHIP_EINVAL), read in place; row i gets label id_base + i. */
+int vaqhip_bitvec_fit_thresholds(int device_id, const float *X, int64_t n, int D, const int *bits, const float *eigvec,
+                                 float *thresholds_out);
+int vaqhip_bitvec_fit_thresholds_u8(int device_id, const uint8_t *X, int64_t n, int D, const int *bits, const float *eigvec,
+                                    float *thresholds_out);
+int vaqhip_bitvec_fit_thresholds_device(int device_id, const float *d_X, int64_t n, int D, const int *bits,
+                                        const float *d_eigvec, float *d_thresholds_out, void *stream);
+int vaqhip_bitvec_fit_thresholds_u8_device(int device_id, const uint8_t *d_X, int64_t n, int D, const int *bits,
+                                           const float *d_eigvec, float *d_thresholds_out, void *stream);
+int vaqhip_bitvec_set_encoder(vaqhip_bitvec *bv, int D, const float *eigvec, const int *bits, const float *thresholds);
+int vaqhip_bitvec_encode(vaqhip_bitvec *bv, const float *X, int64_t n, uint64_t *rows_out);
+int vaqhip_bitvec_encode_u8(vaqhip_bitvec *bv, const uint8_t *X, int64_t n, uint64_t *rows_out);
+int vaqhip_bitvec_encode_device(vaqhip_bitvec *bv, const float *d_X, int64_t n, uint64_t *d_rows_out, void *stream);
+int vaqhip_bitvec_encode_u8_device(vaqhip_bitvec *bv, const uint8_t *d_X, int64_t n, uint64_t *d_rows_out, void *stream);
+int vaqhip_bitvec_encode_set_rows(vaqhip_bitvec *bv, const float *X, int64_t n, int64_t id_base);
+int vaqhip_bitvec_encode_set_rows_u8(vaqhip_bitvec *bv, const uint8_t *X, int64_t n, int64_t id_base);
+int vaqhip_bitvec_encode_add_rows(vaqhip_bitvec *bv, const float *X, int64_t n_new);
+int vaqhip_bitvec_encode_add_rows_u8(vaqhip_bitvec *bv, const uint8_t *X, int64_t n_new);
+int vaqhip_bitvec_encode_from_refiner(vaqhip_bitvec *bv, vaqhip_refiner *r, int64_t id_base);
 
 const char *vaqhip_last_error(void);
 int vaqhip_version(void);

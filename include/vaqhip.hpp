@@ -14,6 +14,7 @@
 #ifndef VAQHIP_HPP_
 #define VAQHIP_HPP_
 
+#include <algorithm>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -945,6 +946,34 @@ public:
         answers[i].push_back({lab[(size_t)i * k + j], dis[(size_t)i * k + j]});
     return answers;
   }
+  // ---- the encoders (vaqhip_bitvec_encode* of vaqhip.h): the eigenvectors are supplied in `eigenVectors` (empty: the
+  // rows are in PCA space already); the glpk allocation of binaryEncoding is supplied as solutionX.  Rows are float
+  // or uint8_t row-major matrices with data()/rows()/cols().  Each leaves a new engine that holds the encoder and no
+  // rows: loadBitVEncoded(X) then encodes X into it on the device, loadBitV replaces it. ----
+  template <class Mat>
+  void binaryEncodingSimple(const Mat &XTrain, const Mat &XTest, bitvectors &XTrainBinary, bitvectors &XTestBinary) {
+    newEncoder((int)XTrain.cols(), (int)XTrain.cols(), nullptr, nullptr);
+    encodeTo(XTrain, XTrainBinary);
+    encodeTo(XTest, XTestBinary);
+  }
+  template <class Mat>
+  void binaryEncoding(const Mat &XTrain, const Mat &XTest, bitvectors &XTrainBinary, bitvectors &XTestBinary,
+                      const std::vector<int> &solutionXIn) {
+    const int D = (int)XTrain.cols();
+    if ((int)solutionXIn.size() != D) throw Error(VAQHIP_EINVAL, "vaqhip: binaryEncoding: one bit count per dimension");
+    int total = 0;
+    for (int b : solutionXIn) total += b;
+    std::vector<float> thr((size_t)D * 256, 0.0f);
+    check(fitThresholds(XTrain.data(), (int64_t)XTrain.rows(), D, solutionXIn.data(), thr.data()));
+    newEncoder(D, total, solutionXIn.data(), thr.data());
+    encodeTo(XTrain, XTrainBinary);
+    encodeTo(XTest, XTestBinary);
+  }
+  // loadBitV of the encoded X, the bits made and kept on the device (labels from 0)
+  template <class Mat> void loadBitVEncoded(const Mat &X) {
+    if (!bv_ || (int)X.cols() != encDim_) throw Error(VAQHIP_ESTATE, "vaqhip: loadBitVEncoded before binaryEncoding*");
+    check(encodeSetRows(X.data(), (int64_t)X.rows()));
+  }
   vaqhip_bitvec *bitvecHandle() const { return bv_; }
   // Several devices (a device named several times: logical shards on that GPU): binaryEncodingLUT then fits over
   // them (vaqhip_multi_lut_fit_quantiles), builds a VAQHIP_SUM_SEQUENTIAL multi index, gives it Q and encodes across
@@ -1074,6 +1103,30 @@ private:
     }
     return flat;
   }
+  void newEncoder(int D, int nBits, const int *bits, const float *thr) {
+    vaqhip_bitvec_destroy(bv_);
+    bv_ = nullptr;
+    encDim_ = D;
+    bitWords_ = (nBits + 63) / 64;
+    check(vaqhip_bitvec_create(&bv_, mDevice, nBits));
+    check(vaqhip_bitvec_set_encoder(bv_, D, eigenVectors.rows() ? eigenVectors.data() : nullptr, bits, thr));
+  }
+  template <class Mat> void encodeTo(const Mat &X, bitvectors &out) {
+    std::vector<uint64_t> flat((size_t)X.rows() * bitWords_);
+    check(encodeRows(X.data(), (int64_t)X.rows(), flat.data()));
+    out.assign((size_t)X.rows(), bitv((size_t)bitWords_));
+    for (size_t i = 0; i < out.size(); i++) std::copy_n(flat.begin() + i * bitWords_, bitWords_, out[i].begin());
+  }
+  int fitThresholds(const float *X, int64_t n, int D, const int *bits, float *thr) {
+    return vaqhip_bitvec_fit_thresholds(mDevice, X, n, D, bits, eigenVectors.rows() ? eigenVectors.data() : nullptr, thr);
+  }
+  int fitThresholds(const uint8_t *X, int64_t n, int D, const int *bits, float *thr) {
+    return vaqhip_bitvec_fit_thresholds_u8(mDevice, X, n, D, bits, eigenVectors.rows() ? eigenVectors.data() : nullptr, thr);
+  }
+  int encodeRows(const float *X, int64_t n, uint64_t *out) { return vaqhip_bitvec_encode(bv_, X, n, out); }
+  int encodeRows(const uint8_t *X, int64_t n, uint64_t *out) { return vaqhip_bitvec_encode_u8(bv_, X, n, out); }
+  int encodeSetRows(const float *X, int64_t n) { return vaqhip_bitvec_encode_set_rows(bv_, X, n, 0); }
+  int encodeSetRows(const uint8_t *X, int64_t n) { return vaqhip_bitvec_encode_set_rows_u8(bv_, X, n, 0); }
   void newOriginal(int D) {
     vaqhip_refiner_destroy(ori_);
     ori_ = nullptr;
@@ -1085,7 +1138,7 @@ private:
   std::vector<int> mDevices;
   vaqhip_bitvec *bv_ = nullptr;   // loadBitV
   vaqhip_refiner *ori_ = nullptr;  // loadOriginal
-  int bitWords_ = 0, oriDim_ = 0;
+  int bitWords_ = 0, oriDim_ = 0, encDim_ = 0;
 };
 
 } // namespace vaqhip

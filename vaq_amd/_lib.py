@@ -73,6 +73,11 @@ SYMBOLS = [
     "vaqhip_bitvec_create", "vaqhip_bitvec_destroy", "vaqhip_bitvec_set_rows", "vaqhip_bitvec_set_rows_device",
     "vaqhip_bitvec_add_rows", "vaqhip_bitvec_size", "vaqhip_bitvec_set_option", "vaqhip_bitvec_query",
     "vaqhip_bitvec_query_device", "vaqhip_bitvec_query_rerank", "vaqhip_bitvec_query_rerank_device",
+    "vaqhip_bitvec_fit_thresholds", "vaqhip_bitvec_fit_thresholds_u8", "vaqhip_bitvec_fit_thresholds_device",
+    "vaqhip_bitvec_fit_thresholds_u8_device", "vaqhip_bitvec_set_encoder", "vaqhip_bitvec_encode",
+    "vaqhip_bitvec_encode_u8", "vaqhip_bitvec_encode_device", "vaqhip_bitvec_encode_u8_device",
+    "vaqhip_bitvec_encode_set_rows", "vaqhip_bitvec_encode_set_rows_u8", "vaqhip_bitvec_encode_add_rows",
+    "vaqhip_bitvec_encode_add_rows_u8", "vaqhip_bitvec_encode_from_refiner",
 ]
 MAX_DEVICES = 16
 
@@ -330,6 +335,15 @@ def load():
     L.vaqhip_bitvec_query_device.argtypes = [vp, vp, i32, i32, i32, vp, vp, vp]
     L.vaqhip_bitvec_query_rerank.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp]
     L.vaqhip_bitvec_query_rerank_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    for u8 in ("", "_u8"):
+        getattr(L, "vaqhip_bitvec_fit_thresholds" + u8).argtypes = [i32, vp, i64, i32, C.POINTER(i32), vp, vp]
+        getattr(L, "vaqhip_bitvec_fit_thresholds" + u8 + "_device").argtypes = [i32, vp, i64, i32, C.POINTER(i32), vp, vp, vp]
+        getattr(L, "vaqhip_bitvec_encode" + u8).argtypes = [vp, vp, i64, vp]
+        getattr(L, "vaqhip_bitvec_encode" + u8 + "_device").argtypes = [vp, vp, i64, vp, vp]
+        getattr(L, "vaqhip_bitvec_encode_set_rows" + u8).argtypes = [vp, vp, i64, i64]
+        getattr(L, "vaqhip_bitvec_encode_add_rows" + u8).argtypes = [vp, vp, i64]
+    L.vaqhip_bitvec_set_encoder.argtypes = [vp, i32, vp, C.POINTER(i32), vp]
+    L.vaqhip_bitvec_encode_from_refiner.argtypes = [vp, vp, i64]
     L.vaqhip_index_info.argtypes = [vp, C.POINTER(Info)]
     L.vaqhip_set_option.argtypes = [vp, C.c_char_p, i64]
     L.vaqhip_last_timing.argtypes = [vp, C.POINTER(Timing)]

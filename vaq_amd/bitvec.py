@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._adapt import _Handle, _dptr, _f32_rows, _out_pair, _ptr, _stream
+from ._adapt import _Handle, _dptr, _eig_f32, _f32_rows, _out_pair, _ptr, _stream, _u8_rows, _u8_rows_device
 
 
 class QueryMethod:
@@ -28,6 +28,12 @@ class VaqBitVec(_Handle):
         labels, dist = bv.query(harness.sign_bits(XTestPCA), 100)
         r = VaqRefiner(D); r.set_rows_u8(XTrain)              # originalData
         ans = bv.query_rerank(Qbits, XTest, 100, 10, r)       # queryRerank(..., k, factor)
+
+    The engine can make the bits itself, from raw rows on the host, on the device or in a refiner:
+
+        bv.set_encoder(D, eigvec)                             # binaryEncodingSimple; with bits and thresholds
+        bv.encode_from_refiner(r)                             # (bitvec_fit_thresholds): binaryEncoding
+        labels, dist = bv.query_device(bv.encode(d_XTest), 100)
     """
     _destroy = "vaqhip_bitvec_destroy"
 
@@ -72,6 +78,66 @@ class VaqBitVec(_Handle):
         """Append rows; their labels continue behind the rows already held."""
         X = self._words(rows, "rows")
         self._call("add_rows", _ptr(X), X.shape[0])
+
+    # ---- the encoders: raw rows -> bit rows on the device ----
+    def set_encoder(self, D: int, eigvec=None, bits=None, thresholds=None) -> None:
+        """The encoder of the rows and queries to come: BitVecEngine::binaryEncodingSimple (bits None: one sign bit per
+        dimension, n_bits == D) or ::binaryEncoding (bits[D] in 0..8, thresholds float32 [D][256] as
+        bitvec_fit_thresholds leaves them, n_bits == sum(bits)).  eigvec: D x D, or None for rows already projected."""
+        self.enc_D = int(D)
+        eig = _eig_f32(eigvec, self.enc_D, "eigvec")
+        b = thr = None
+        if bits is not None:
+            b = (C.c_int * self.enc_D)(*_bits_list(bits, self.enc_D))
+            thr = _thresholds(thresholds, self.enc_D)
+        self._call("set_encoder", self.enc_D, _ptr(eig) if eig is not None else None, b,
+                   _ptr(thr) if thr is not None else None)
+
+    def _raw(self, X):
+        """(rows, "_u8" or ""): uint8 rows stay bytes, anything else is taken as float32; n x D of the encoder."""
+        D = getattr(self, "enc_D", 0)
+        if not D:
+            raise _lib.VaqHipError(-7, "no encoder: call set_encoder first")
+        if hasattr(X, "data_ptr"):
+            import torch
+            if X.dtype == torch.uint8:
+                return _u8_rows_device(X, D), "_u8"
+            if not (X.is_cuda and X.dtype == torch.float32 and X.dim() == 2 and X.shape[1] == D and X.is_contiguous()):
+                raise _lib.VaqHipError(-1, f"device rows must be a contiguous float32 or uint8 n x {D} CUDA tensor")
+            return X, ""
+        if getattr(X, "dtype", None) == np.uint8:
+            return _u8_rows(X, D), "_u8"
+        return _f32_rows(X, D, "rows {shape} are not n x {D}"), ""
+
+    def encode(self, X, out=None):
+        """The bit rows of raw rows (or of a query batch): a host array gives uint64 [n][W]; a torch CUDA tensor (float32
+        or uint8) gives an int64 [n][W] tensor, enqueued on torch's current stream with no synchronisation."""
+        X, u8 = self._raw(X)
+        if hasattr(X, "data_ptr"):
+            import torch
+            if X.device.index != self.device:
+                raise _lib.VaqHipError(-1, f"device rows must be on cuda:{self.device}")
+            if out is None:
+                out = torch.empty((X.shape[0], self.W), dtype=torch.int64, device=X.device)
+            self._call("encode" + u8 + "_device", _dptr(X), X.shape[0], _dptr(self._words_device(out, "out")), _stream(X))
+            return out
+        rows = np.empty((X.shape[0], self.W), np.uint64)
+        self._call("encode" + u8, _ptr(X), X.shape[0], _ptr(rows))
+        return rows
+
+    def set_rows_encoded(self, X, id_base: int = 0) -> None:
+        """set_rows(encode(X)) from raw host rows, the bits written straight into the engine's store."""
+        X, u8 = self._raw(np.asarray(X))
+        self._call("encode_set_rows" + u8, _ptr(X), X.shape[0], int(id_base))
+
+    def add_rows_encoded(self, X) -> None:
+        """add_rows(encode(X)) from raw host rows."""
+        X, u8 = self._raw(np.asarray(X))
+        self._call("encode_add_rows" + u8, _ptr(X), X.shape[0])
+
+    def encode_from_refiner(self, refiner, id_base: int = 0) -> None:
+        """Replace the rows by the encoded rows a VaqRefiner on the same device holds (float or byte), read in place."""
+        self._call("encode_from_refiner", refiner._h, int(id_base))
 
     def __len__(self) -> int:
         return int(self._call("size"))
@@ -127,3 +193,56 @@ class VaqBitVec(_Handle):
         self._call("query_rerank_device", refiner._h, _dptr(q), _dptr(oq), nq, int(k), int(factor), _dptr(labels),
                    _dptr(dists), _stream(q))
         return labels, dists
+
+
+def _bits_list(bits, D: int):
+    b = [int(x) for x in bits]
+    if len(b) != D:
+        raise _lib.VaqHipError(-1, f"{len(b)} bit counts for D={D}")
+    return b
+
+
+def _thresholds(thr, D: int) -> np.ndarray:
+    thr = np.ascontiguousarray(thr, dtype=np.float32)
+    if thr.shape != (D, 256):
+        raise _lib.VaqHipError(-1, f"thresholds {thr.shape} are not {D} x 256")
+    return thr
+
+
+def _fit_thresholds(X, bits, eigvec, device: int, u8: bool, out):
+    if hasattr(X, "data_ptr"):
+        import torch
+        X = _u8_rows_device(X, X.shape[-1]) if u8 else X
+        if not (X.is_cuda and X.dim() == 2 and X.is_contiguous() and X.dtype == (torch.uint8 if u8 else torch.float32)):
+            raise _lib.VaqHipError(-1, "device rows must be a contiguous n x D CUDA tensor of the call's element type")
+        n, D = X.shape
+        if eigvec is not None and not (eigvec.is_cuda and eigvec.dtype == torch.float32 and tuple(eigvec.shape) == (D, D)
+                                       and eigvec.is_contiguous()):
+            raise _lib.VaqHipError(-1, f"device eigvec must be a contiguous float32 {D} x {D} CUDA tensor")
+        if out is None:
+            out = torch.zeros((D, 256), dtype=torch.float32, device=X.device)
+        b = (C.c_int * D)(*_bits_list(bits, D))
+        fn = getattr(_lib.load(), "vaqhip_bitvec_fit_thresholds" + ("_u8" if u8 else "") + "_device")
+        _lib.check(fn(X.device.index, _dptr(X), n, D, b, _dptr(eigvec) if eigvec is not None else None, _dptr(out), _stream(X)))
+        return out
+    X = np.asarray(X)
+    X = _u8_rows(X, X.shape[-1]) if u8 else _f32_rows(X, X.shape[-1], "rows {shape} are not n x {D}")
+    n, D = X.shape
+    eig = _eig_f32(eigvec, D, "eigvec")
+    out = np.zeros((D, 256), np.float32) if out is None else _thresholds(out, D)
+    b = (C.c_int * D)(*_bits_list(bits, D))
+    fn = getattr(_lib.load(), "vaqhip_bitvec_fit_thresholds" + ("_u8" if u8 else ""))
+    _lib.check(fn(device, _ptr(X), n, D, b, _ptr(eig) if eig is not None else None, _ptr(out)))
+    return out
+
+
+def bitvec_fit_thresholds(X, bits, eigvec=None, device: int = 0, out=None):
+    """The quantile thresholds of BitVecEngine::binaryEncoding from raw float rows: float32 [D][256], row d holding its
+    2^bits[d] entries (the last is FLT_MAX); the rest of `out` (zeros when it is not given) is left as it is.  Host
+    arrays, or torch CUDA tensors (X, eigvec, out), on whose device and current stream the fit then runs."""
+    return _fit_thresholds(X, bits, eigvec, device, False, out)
+
+
+def bitvec_fit_thresholds_u8(X, bits, eigvec=None, device: int = 0, out=None):
+    """bitvec_fit_thresholds from byte rows (a bvecs dataset as its file holds it)."""
+    return _fit_thresholds(X, bits, eigvec, device, True, out)

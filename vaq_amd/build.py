@@ -35,6 +35,7 @@ SOURCES = [
     "vaq_exhaust.hip",
     "vaq_train.hip",
     "vaq_bitvec.hip",
+    "vaq_bitvec_encode.hip",
     # the single-index host
     "vaqhip_api.cpp",
     "vaqhip_plan.cpp",
@@ -47,6 +48,7 @@ SOURCES = [
     "vaqhip_train.cpp",
     "vaqhip_refiner.cpp",
     "vaqhip_bitvec.cpp",
+    "vaqhip_bitvec_encode.cpp",
     # the multi-device host
     "vaqhip_multi.cpp",
     "vaqhip_multi_search.cpp",
@@ -59,6 +61,8 @@ SOURCES = [
     "vaqhip_multi_codebooks.cpp",
     "vaqhip_rccl.cpp",
 ]
+# flags of single units: packed fp32 arithmetic is kept out of the encoder's FMA chains
+UNIT_FLAGS = {"vaq_bitvec_encode.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 OBJDIR = os.path.join(LIBDIR, "obj")
 # Experiment builds: VAQ_VARIANT=name compiles (with VAQ_EXTRA_FLAGS) into vaq_amd/lib/variants/name/
 # and VAQHIP_LIB=<path> makes the package load that library instead (tools/ sweeps).
@@ -131,7 +135,7 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
             not (_VARIANT and _VARIANT_ONLY and s not in _VARIANT_ONLY)]
     procs = []
     for s in todo:
-        cmd = common + extra + ["-MD", "-MF", _obj(s) + ".d", "-c", os.path.join(CSRC, s), "-o", _obj(s)]
+        cmd = common + UNIT_FLAGS.get(s, []) + extra + ["-MD", "-MF", _obj(s) + ".d", "-c", os.path.join(CSRC, s), "-o", _obj(s)]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         procs.append((s, cmd, subprocess.Popen(cmd)))

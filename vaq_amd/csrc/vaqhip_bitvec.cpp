@@ -5,20 +5,9 @@
 
 #include "vaq_bitvec.h"
 #include "vaq_fast.h"
-#include "vaqhip_refine_common.h"
+#include "vaqhip_bitvec.h"
 
 using namespace vaqhost;
-
-struct vaqhip_bitvec : HandleCore {
-  int n_bits = 0, W = 0;
-  int64_t N = 0, id_base = 0;
-  int64_t dist_chunk_bytes = (int64_t)1 << 30;  // option "dist_chunk_bytes": the distance matrix of a chunk of queries
-  RowStore rows;  // uint64 words (elem 8, W a row), room for the rows padded to FAST_ROW_PAD
-  // workspaces (grow-only), shared by the callers' streams (WS_SCOPE): the distance matrix, FAST's head order and its
-  // scratch; the rerank's candidates and the staging of the host forms
-  DevBuf w_dist, w_order, w_scratch;
-  StagingBufs w;
-};
 
 namespace {
 

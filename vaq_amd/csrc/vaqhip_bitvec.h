@@ -1,0 +1,35 @@
+// vaqhip_bitvec.h -- the Hamming engine's handle, shared by its two hosts: vaqhip_bitvec.cpp (rows and queries) and
+// vaqhip_bitvec_encode.cpp (the encoders that make the rows on the device).
+#ifndef VAQHIP_BITVEC_H
+#define VAQHIP_BITVEC_H
+#include "vaqhip_index.h"
+
+#include "vaq_bitvec_encode.h"
+#include "vaqhip_refine_common.h"
+
+// What vaqhip_bitvec_set_encoder leaves on the device: the rotation, and for the quantile form the allocated
+// dimensions and their running-maximum thresholds, ragged.  Read by encodes enqueued on any stream: a set waits for the
+// device before it replaces them.
+struct BitvecEncoder {
+  bool set = false;
+  int D = 0, n_live = 0, pm_floats = 0;
+  bool quantile = false, has_eig = false;
+  vaqhost::DevBuf eig, live, pm;
+  vaq::BitvecEncodePlan plan(int W) const {
+    return vaq::BitvecEncodePlan{D, W, has_eig ? eig.as<float>() : nullptr, n_live,
+                                 quantile ? live.as<vaq::BitvecLive>() : nullptr, pm.as<float>(), pm_floats};
+  }
+};
+
+struct vaqhip_bitvec : vaqhost::HandleCore {
+  int n_bits = 0, W = 0;
+  int64_t N = 0, id_base = 0;
+  int64_t dist_chunk_bytes = (int64_t)1 << 30;  // option "dist_chunk_bytes": the distance matrix of a chunk of queries
+  vaqhost::RowStore rows;  // uint64 words (elem 8, W a row), room for the rows padded to FAST_ROW_PAD
+  // workspaces (grow-only), shared by the callers' streams (WS_SCOPE): the distance matrix, FAST's head order and its
+  // scratch; the rerank's candidates and the staging of the host forms
+  vaqhost::DevBuf w_dist, w_order, w_scratch;
+  vaqhost::StagingBufs w;
+  BitvecEncoder enc;
+};
+#endif
