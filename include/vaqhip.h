@@ -1472,7 +1472,7 @@ int vaqhip_last_timing(vaqhip_index *ix, vaqhip_timing *out);
  * The host forms are synchronous; the _device forms take pointers on the engine's GPU, enqueue on `stream` and do not
  * synchronise once the workspaces have their size.  Calls on one engine are serialised.  Errors leave their text in
  * vaqhip_last_error(), as the index's and the refiner's do.  Not provided: the other three methods, earlyAbandonRank,
- * the cluster-info, filtering and naive variants, a multi-device form.  The encoders follow the queries below. */
+ * the filtering and naive variants, a multi-device form.  The cluster forms and the encoders follow the queries below. */
 typedef struct vaqhip_bitvec vaqhip_bitvec;
 #define VAQHIP_BITVEC_HEAP                0  /* BitVecEngine::QueryMethod (BitVecEngine.hpp:82-84) */
 #define VAQHIP_BITVEC_SORT                1
@@ -1495,6 +1495,41 @@ int vaqhip_bitvec_query_rerank(vaqhip_bitvec *bv, vaqhip_refiner *r, const uint6
 int vaqhip_bitvec_query_rerank_device(vaqhip_bitvec *bv, vaqhip_refiner *r, const uint64_t *d_bit_queries,
                                       const float *d_ori_queries, int nq, int k, int factor, int32_t *d_labels_out,
                                       float *d_distances_out, void *stream);
+
+/* ---- Hamming engine: the cluster forms (BitVecEngine::queryWithClusterInfo, ::queryRerankWithClusterInfo) -------------
+ * The sub-linear queries of the reference (BitVecEngine.cpp:259-304, :537-568; loadCentroids, loadClusterInfo :37-52)
+ * with QueryMethod::Sort.  Per query: dist[c] = euclideanDistNoSQRT(ori_query, centre c) for the T centres (one float
+ * accumulator from 0.0f in dimension order, nothing fused); the centres in std::sort's order under dist alone (equal
+ * distances as libstdc++ leaves them); the sorted centres are walked until their members number k at least (an empty
+ * cluster counts as walked), then on until atleast_cluster centres are walked; the candidates are the members of those
+ * clusters, cluster after cluster, each in ascending row order; their Hamming distances go through
+ * KNNFromDistsIndicesSupplied as the rerank's do: std::sort of the first k by distance alone, every later candidate
+ * behind its equals.  The rerank form does this with kTemp = min(factor * k, n) and then reranks as query_rerank does.
+ * Parity-unpinned: BitVecEngine.cpp cannot be compiled here (glpk.h); the walk is restated from its text, the pieces it
+ * composes (std::sort, KNNFromDists*) are pinned.  No [nq][n] array is made: the selection is fused into the scan.
+ *   set_clusters  centroids float [T][D] and clust_idx int32 [n] (the cluster of each row held), host arrays.
+ *                 1 <= T <= 4096, 1 <= D <= 8176, every clust_idx[i] in [0, T): otherwise VAQHIP_EINVAL and the state
+ *                 stays as it was.  The call keeps the centres, the member lists and a second, cluster-major copy of
+ *                 the bit rows on the device (the rows' bytes once more) and waits for the device before it replaces
+ *                 them.  Whatever replaces or appends rows (set_rows*, add_rows, encode_set_rows*, encode_add_rows*,
+ *                 encode_from_refiner) drops the state: a cluster query is then VAQHIP_ESTATE until the next set_clusters.
+ *   queries       ori_queries float [nq][D].  atleast_cluster outside 1..T is VAQHIP_EINVAL (the reference reads past
+ *                 its centres there).  Where the candidates number fewer than k (only with n < k) the slots behind them
+ *                 are -1 / FLT_MAX, as query answers.  Methods, k, nq and the refiner: as query and query_rerank
+ *                 refuse them; the refiner's D must be the centres' (VAQHIP_EINVAL).
+ * "dist_chunk_bytes" bounds the visit lists of a chunk of queries (4 T + 16 bytes a query). */
+int vaqhip_bitvec_set_clusters(vaqhip_bitvec *bv, const float *centroids, int T, int D, const int32_t *clust_idx);
+int vaqhip_bitvec_query_clusters(vaqhip_bitvec *bv, const uint64_t *bit_queries, const float *ori_queries, int nq, int k,
+                                 int method, int atleast_cluster, int32_t *labels_out, float *distances_out);
+int vaqhip_bitvec_query_clusters_device(vaqhip_bitvec *bv, const uint64_t *d_bit_queries, const float *d_ori_queries, int nq,
+                                        int k, int method, int atleast_cluster, int32_t *d_labels_out, float *d_distances_out,
+                                        void *stream);
+int vaqhip_bitvec_query_rerank_clusters(vaqhip_bitvec *bv, vaqhip_refiner *r, const uint64_t *bit_queries,
+                                        const float *ori_queries, int nq, int k, int factor, int atleast_cluster,
+                                        int32_t *labels_out, float *distances_out);
+int vaqhip_bitvec_query_rerank_clusters_device(vaqhip_bitvec *bv, vaqhip_refiner *r, const uint64_t *d_bit_queries,
+                                               const float *d_ori_queries, int nq, int k, int factor, int atleast_cluster,
+                                               int32_t *d_labels_out, float *d_distances_out, void *stream);
 
 /* ---- Hamming engine: the encoders (BitVecEngine::binaryEncodingSimple and ::binaryEncoding) on the device ------------
  * Raw rows (float or byte; host, device or resident in a refiner) -> bit rows, with no projected matrix written.  Both

@@ -857,6 +857,7 @@ struct IdxDistPair {  // utils/Types.hpp:51 (IdxDistPairBase<uint32_t>)
 };
 using bitv = std::vector<uint64_t>;  // BitVector.hpp: actBitVLen words a vector
 using bitvectors = std::vector<bitv>;
+using Matrixf = std::vector<std::vector<float>>;  // utils/Types.hpp:28
 
 class BitVecEngineHip {
 public:
@@ -898,6 +899,7 @@ public:
     }
     vaqhip_bitvec_destroy(bv_);
     bv_ = nullptr;
+    clustersPushed_ = false;
     bitWords_ = (int)W;
     check(vaqhip_bitvec_create(&bv_, mDevice, (int)(64 * W)));
     check(vaqhip_bitvec_set_rows(bv_, flat.data(), (int64_t)bitVectors.size(), 0));
@@ -973,6 +975,71 @@ public:
   template <class Mat> void loadBitVEncoded(const Mat &X) {
     if (!bv_ || (int)X.cols() != encDim_) throw Error(VAQHIP_ESTATE, "vaqhip: loadBitVEncoded before binaryEncoding*");
     check(encodeSetRows(X.data(), (int64_t)X.rows()));
+    clustersPushed_ = false;
+  }
+  // ---- the cluster forms (vaqhip_bitvec_*_clusters of vaqhip.h) ----
+  // BitVecEngine::loadCentroids and ::loadClusterInfo (BitVecEngine.cpp:37-52): the centres in original space and the
+  // cluster of every bit vector.  The device state is built by the first cluster query behind both loads and the bit
+  // vectors; loading bit vectors again drops it.
+  void loadCentroids(Matrixf _centroids) {
+    centroids_ = std::move(_centroids);
+    clustersPushed_ = false;
+  }
+  void loadClusterInfo(std::vector<int> clustIdx, int _centroids_size) {
+    clustIdx_ = std::move(clustIdx);
+    centroidsSize_ = _centroids_size;
+    clustersPushed_ = false;
+  }
+  // BitVecEngine::queryWithClusterInfo: min(k, candidates) pairs per query; only QueryMethod::Sort, as query
+  template <class Mat>
+  std::vector<std::vector<IdxDistPair>> queryWithClusterInfo(const bitvectors &queries, const Mat &oriQueries, const int k,
+                                                             int method = QueryMethod::Sort, int atleastCluster = 1) {
+    ensureClusters();
+    const std::vector<uint64_t> q = flatQueries(queries);
+    const int nq = (int)queries.size();
+    checkOriQueries(oriQueries, nq, clusterDim_);
+    std::vector<int> lab((size_t)nq * k);
+    std::vector<float> dis((size_t)nq * k);
+    check(vaqhip_bitvec_query_clusters(bv_, q.data(), oriQueries.data(), nq, k, method, atleastCluster, lab.data(), dis.data()));
+    std::vector<std::vector<IdxDistPair>> answers(nq);
+    for (int i = 0; i < nq; i++)
+      for (int j = 0; j < k && lab[(size_t)i * k + j] >= 0; j++)
+        answers[i].push_back({lab[(size_t)i * k + j], (uint32_t)dis[(size_t)i * k + j]});
+    return answers;
+  }
+  std::vector<std::vector<IdxDistPair>> queryWithClusterInfo(const bitvectors &queries, const Matrixf &oriQueries, const int k,
+                                                             int method = QueryMethod::Sort, int atleastCluster = 1) {
+    return queryWithClusterInfo(queries, FlatRows(oriQueries), k, method, atleastCluster);
+  }
+  // BitVecEngine::queryRerankWithClusterInfo with earlyAbandonRank = false
+  template <class Mat>
+  std::vector<std::vector<IdxDistPairFloat>> queryRerankWithClusterInfo(const bitvectors &queries, const Mat &oriQueries,
+                                                                        const int k, const int factor,
+                                                                        int method = QueryMethod::Sort, int atleastCluster = 1,
+                                                                        bool earlyAbandonRank = false) {
+    if (!ori_) throw Error(VAQHIP_ESTATE, "vaqhip: queryRerankWithClusterInfo before loadOriginal");
+    if (method != QueryMethod::Sort || earlyAbandonRank)
+      throw Error(VAQHIP_EUNSUPPORTED, "vaqhip: queryRerankWithClusterInfo: only QueryMethod::Sort without earlyAbandonRank "
+                                       "is provided");
+    ensureClusters();
+    const std::vector<uint64_t> q = flatQueries(queries);
+    const int nq = (int)queries.size();
+    checkOriQueries(oriQueries, nq, oriDim_);
+    std::vector<int> lab((size_t)nq * k);
+    std::vector<float> dis((size_t)nq * k);
+    check(vaqhip_bitvec_query_rerank_clusters(bv_, ori_, q.data(), oriQueries.data(), nq, k, factor, atleastCluster,
+                                              lab.data(), dis.data()));
+    std::vector<std::vector<IdxDistPairFloat>> answers(nq);
+    for (int i = 0; i < nq; i++)
+      for (int j = 0; j < k && lab[(size_t)i * k + j] >= 0; j++)
+        answers[i].push_back({lab[(size_t)i * k + j], dis[(size_t)i * k + j]});
+    return answers;
+  }
+  std::vector<std::vector<IdxDistPairFloat>> queryRerankWithClusterInfo(const bitvectors &queries, const Matrixf &oriQueries,
+                                                                        const int k, const int factor,
+                                                                        int method = QueryMethod::Sort, int atleastCluster = 1,
+                                                                        bool earlyAbandonRank = false) {
+    return queryRerankWithClusterInfo(queries, FlatRows(oriQueries), k, factor, method, atleastCluster, earlyAbandonRank);
   }
   vaqhip_bitvec *bitvecHandle() const { return bv_; }
   // Several devices (a device named several times: logical shards on that GPU): binaryEncodingLUT then fits over
@@ -1103,9 +1170,43 @@ private:
     }
     return flat;
   }
+  // a Matrixf as the row-major matrix the calls take; rows of different lengths are refused
+  struct FlatRows {
+    std::vector<float> flat;
+    size_t n = 0, d = 0;
+    explicit FlatRows(const Matrixf &m) : n(m.size()), d(m.empty() ? 0 : m[0].size()) {
+      flat.reserve(n * d);
+      for (const std::vector<float> &r : m) {
+        if (r.size() != d) throw Error(VAQHIP_EINVAL, "vaqhip: rows of different lengths");
+        flat.insert(flat.end(), r.begin(), r.end());
+      }
+    }
+    const float *data() const { return flat.data(); }
+    size_t rows() const { return n; }
+    size_t cols() const { return d; }
+  };
+  template <class Mat> static void checkOriQueries(const Mat &oriQueries, int nq, int D) {
+    if ((int)oriQueries.rows() != nq || (nq > 0 && (int)oriQueries.cols() != D))
+      throw Error(VAQHIP_EINVAL, "vaqhip: oriQueries must have one row of the centres' dimension per query");
+  }
+  // vaqhip_bitvec_set_clusters once the bit vectors, the centres and the cluster indices are all there
+  void ensureClusters() {
+    if (!bv_ || centroids_.empty() || centroidsSize_ < 0)
+      throw Error(VAQHIP_ESTATE, "vaqhip: a cluster query before loadBitV, loadCentroids and loadClusterInfo");
+    if (clustersPushed_) return;
+    if ((int)centroids_.size() != centroidsSize_)
+      throw Error(VAQHIP_EINVAL, "vaqhip: loadClusterInfo's centroids_size differs from the centres loaded");
+    if ((int64_t)clustIdx_.size() != vaqhip_bitvec_size(bv_))
+      throw Error(VAQHIP_EINVAL, "vaqhip: loadClusterInfo needs one cluster index per bit vector");
+    const FlatRows c(centroids_);
+    check(vaqhip_bitvec_set_clusters(bv_, c.data(), (int)c.rows(), (int)c.cols(), clustIdx_.data()));
+    clusterDim_ = (int)c.cols();
+    clustersPushed_ = true;
+  }
   void newEncoder(int D, int nBits, const int *bits, const float *thr) {
     vaqhip_bitvec_destroy(bv_);
     bv_ = nullptr;
+    clustersPushed_ = false;
     encDim_ = D;
     bitWords_ = (nBits + 63) / 64;
     check(vaqhip_bitvec_create(&bv_, mDevice, nBits));
@@ -1139,6 +1240,10 @@ private:
   vaqhip_bitvec *bv_ = nullptr;   // loadBitV
   vaqhip_refiner *ori_ = nullptr;  // loadOriginal
   int bitWords_ = 0, oriDim_ = 0, encDim_ = 0;
+  Matrixf centroids_;            // loadCentroids
+  std::vector<int> clustIdx_;    // loadClusterInfo
+  int centroidsSize_ = -1, clusterDim_ = 0;
+  bool clustersPushed_ = false;  // the engine bv_ holds them
 };
 
 } // namespace vaqhip

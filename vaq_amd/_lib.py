@@ -78,6 +78,8 @@ SYMBOLS = [
     "vaqhip_bitvec_encode_u8", "vaqhip_bitvec_encode_device", "vaqhip_bitvec_encode_u8_device",
     "vaqhip_bitvec_encode_set_rows", "vaqhip_bitvec_encode_set_rows_u8", "vaqhip_bitvec_encode_add_rows",
     "vaqhip_bitvec_encode_add_rows_u8", "vaqhip_bitvec_encode_from_refiner",
+    "vaqhip_bitvec_set_clusters", "vaqhip_bitvec_query_clusters", "vaqhip_bitvec_query_clusters_device",
+    "vaqhip_bitvec_query_rerank_clusters", "vaqhip_bitvec_query_rerank_clusters_device",
 ]
 MAX_DEVICES = 16
 
@@ -344,6 +346,11 @@ def load():
         getattr(L, "vaqhip_bitvec_encode_add_rows" + u8).argtypes = [vp, vp, i64]
     L.vaqhip_bitvec_set_encoder.argtypes = [vp, i32, vp, C.POINTER(i32), vp]
     L.vaqhip_bitvec_encode_from_refiner.argtypes = [vp, vp, i64]
+    L.vaqhip_bitvec_set_clusters.argtypes = [vp, vp, i32, i32, vp]
+    L.vaqhip_bitvec_query_clusters.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp]
+    L.vaqhip_bitvec_query_clusters_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.vaqhip_bitvec_query_rerank_clusters.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
+    L.vaqhip_bitvec_query_rerank_clusters_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.vaqhip_index_info.argtypes = [vp, C.POINTER(Info)]
     L.vaqhip_set_option.argtypes = [vp, C.c_char_p, i64]
     L.vaqhip_last_timing.argtypes = [vp, C.POINTER(Timing)]

@@ -34,6 +34,12 @@ class VaqBitVec(_Handle):
         bv.set_encoder(D, eigvec)                             # binaryEncodingSimple; with bits and thresholds
         bv.encode_from_refiner(r)                             # (bitvec_fit_thresholds): binaryEncoding
         labels, dist = bv.query_device(bv.encode(d_XTest), 100)
+
+    The sub-linear forms visit only the members of the clusters nearest to each query (queryWithClusterInfo):
+
+        bv.set_clusters(centroids, clust_idx)                 # loadCentroids, loadClusterInfo
+        labels, dist = bv.query_clusters(Qbits, XTest, 100, atleast_cluster=8)
+        ans = bv.query_rerank_clusters(Qbits, XTest, 100, 10, r, atleast_cluster=8)
     """
     _destroy = "vaqhip_bitvec_destroy"
 
@@ -192,6 +198,93 @@ class VaqBitVec(_Handle):
         labels, dists = _out_pair(out, nq, k, q.device)
         self._call("query_rerank_device", refiner._h, _dptr(q), _dptr(oq), nq, int(k), int(factor), _dptr(labels),
                    _dptr(dists), _stream(q))
+        return labels, dists
+
+    # ---- the cluster forms: BitVecEngine::queryWithClusterInfo and ::queryRerankWithClusterInfo ----
+    def set_clusters(self, centroids, clust_idx) -> None:
+        """loadCentroids and loadClusterInfo: centroids float32 [T][D], clust_idx int32 [n] = the cluster of each row
+        held.  Keeps a second, cluster-major copy of the bit rows on the device.  Whatever replaces or appends rows
+        drops the state: call this again behind it."""
+        cen = np.ascontiguousarray(centroids, dtype=np.float32)
+        if cen.ndim != 2 or cen.shape[0] < 1 or cen.shape[1] < 1:
+            raise _lib.VaqHipError(-1, f"centroids {cen.shape} are not T x D")
+        idx = np.asarray(clust_idx)
+        if idx.ndim != 1 or idx.dtype.kind not in "iu":
+            raise _lib.VaqHipError(-1, "clust_idx must be a one-dimensional integer array")
+        if idx.size and (int(idx.min()) < 0 or int(idx.max()) >= cen.shape[0]):
+            raise _lib.VaqHipError(-1, f"clust_idx outside 0..{cen.shape[0] - 1}")
+        idx = np.ascontiguousarray(idx, dtype=np.int32)
+        if idx.shape[0] != len(self):
+            raise _lib.VaqHipError(-1, f"{idx.shape[0]} cluster indices for {len(self)} rows")
+        self._call("set_clusters", _ptr(cen), cen.shape[0], cen.shape[1], _ptr(idx))
+        self.cluster_D = cen.shape[1]
+
+    def _ori(self, Q, ori_queries) -> np.ndarray:
+        D = getattr(self, "cluster_D", 0)
+        if not D:
+            raise _lib.VaqHipError(-7, "no cluster state: call set_clusters first")
+        XQ = _f32_rows(ori_queries, D, "oriQueries {shape} are not nq x {D}")
+        if XQ.shape[0] != Q.shape[0]:
+            raise _lib.VaqHipError(-1, f"{Q.shape[0]} bit queries but {XQ.shape[0]} original queries")
+        return XQ
+
+    def _ori_device(self, q, d_ori_queries):
+        import torch
+        D = getattr(self, "cluster_D", 0)
+        if not D:
+            raise _lib.VaqHipError(-7, "no cluster state: call set_clusters first")
+        oq = d_ori_queries.contiguous()
+        if not (oq.is_cuda and oq.device == q.device and oq.dtype == torch.float32 and tuple(oq.shape) == (q.shape[0], D)):
+            raise _lib.VaqHipError(-1, f"device oriQueries must be float32 {q.shape[0]} x {D} on the queries' device")
+        return oq
+
+    def query_clusters(self, queries, ori_queries, k: int, method: int = QueryMethod.Sort, atleast_cluster: int = 1):
+        """BitVecEngine::queryWithClusterInfo: the k best among the members of the clusters nearest to each original
+        query (as many as hold k rows, and atleast_cluster at least): (labels int32 [nq][k], distances uint32
+        [nq][k]), slots past the candidates -1 / 0xffffffff."""
+        Q = self._words(queries, "queries")
+        XQ = self._ori(Q, ori_queries)
+        nq = Q.shape[0]
+        lab = np.empty((nq, k), np.int32)
+        dis = np.empty((nq, k), np.float32)
+        self._call("query_clusters", _ptr(Q), _ptr(XQ), nq, int(k), int(method), int(atleast_cluster), _ptr(lab), _ptr(dis))
+        out = np.full((nq, k), 0xffffffff, np.uint32)
+        np.copyto(out, dis, where=lab >= 0, casting="unsafe")
+        return lab, out
+
+    def query_clusters_device(self, d_queries, d_ori_queries, k: int, method: int = QueryMethod.Sort,
+                              atleast_cluster: int = 1, out=None):
+        """query_clusters() on torch CUDA tensors, enqueued on torch's current stream, no synchronisation: distances
+        float32, the exact integers; empty slots -1 / FLT_MAX."""
+        q = self._words_device(d_queries, "device queries")
+        oq = self._ori_device(q, d_ori_queries)
+        nq = q.shape[0]
+        labels, dists = _out_pair(out, nq, k, q.device)
+        self._call("query_clusters_device", _dptr(q), _dptr(oq), nq, int(k), int(method), int(atleast_cluster),
+                   _dptr(labels), _dptr(dists), _stream(q))
+        return labels, dists
+
+    def query_rerank_clusters(self, queries, ori_queries, k: int, factor: int, refiner, atleast_cluster: int = 1):
+        """BitVecEngine::queryRerankWithClusterInfo: query_clusters with min(factor * k, n) candidates, reranked as
+        query_rerank does: (labels int32 [nq][k], squared Euclidean distances float32 [nq][k])."""
+        Q = self._words(queries, "queries")
+        XQ = self._ori(Q, ori_queries)
+        nq = Q.shape[0]
+        lab = np.empty((nq, k), np.int32)
+        dis = np.empty((nq, k), np.float32)
+        self._call("query_rerank_clusters", refiner._h, _ptr(Q), _ptr(XQ), nq, int(k), int(factor), int(atleast_cluster),
+                   _ptr(lab), _ptr(dis))
+        return lab, dis
+
+    def query_rerank_clusters_device(self, d_queries, d_ori_queries, k: int, factor: int, refiner,
+                                     atleast_cluster: int = 1, out=None):
+        """query_rerank_clusters() on torch CUDA tensors, enqueued on torch's current stream, no synchronisation."""
+        q = self._words_device(d_queries, "device queries")
+        oq = self._ori_device(q, d_ori_queries)
+        nq = q.shape[0]
+        labels, dists = _out_pair(out, nq, k, q.device)
+        self._call("query_rerank_clusters_device", refiner._h, _dptr(q), _dptr(oq), nq, int(k), int(factor),
+                   int(atleast_cluster), _dptr(labels), _dptr(dists), _stream(q))
         return labels, dists
 
 

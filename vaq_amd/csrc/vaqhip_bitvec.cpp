@@ -1,6 +1,7 @@
 // vaqhip_bitvec.cpp -- the Hamming engine of include/vaqhip.h: packed bit rows resident on the device,
 // BitVecEngine::query with QueryMethod::Sort over them (vaq_bitvec.hip's scan, then FAST's selection: vaq_fast.hip)
-// and BitVecEngine::queryRerank over a resident refiner's raw rows (the Hamming candidates stay on the device).
+// and BitVecEngine::queryRerank over a resident refiner's raw rows (the Hamming candidates stay on the device); the
+// cluster forms of both (queryWithClusterInfo: vaq_bitvec_clusters.hip's plan and fused scan-and-select).
 #include "vaqhip_index.h"
 
 #include "vaq_bitvec.h"
@@ -49,6 +50,7 @@ int set_rows_any(vaqhip_bitvec *bv, const uint64_t *X, bool on_device, int64_t n
     return fail(VAQHIP_ERANGE, "labels are 32-bit ints: id_base+n = %lld", (long long)(id_base + n));
   ENTRY(bv);
   bv->N = 0;  // (a failure below leaves no rows, not rows half replaced)
+  bv->cl.set = false;
   HIP_TRY(bv->rows.reserve(vaq::fast_pad_rows(n), RowStore::DROP, bv->W));
   HIP_TRY(hipDeviceSynchronize());  // (a query enqueued on any stream may still read the old rows)
   if (int rc = write_rows(bv, X, 0, n, on_device, static_cast<hipStream_t>(stream))) return rc;
@@ -152,6 +154,93 @@ int rerank_entry(vaqhip_bitvec *bv, vaqhip_refiner *r, const uint64_t *bit_queri
   });
 }
 
+// what a cluster query must hold beside check_query's; under the engine's lock
+int check_clusters(const vaqhip_bitvec *bv, int atleast) {
+  if (!bv->cl.set)
+    return fail(VAQHIP_ESTATE, "no cluster state: call vaqhip_bitvec_set_clusters once the rows are in place (a set or an "
+                "append of rows drops it)");
+  if (atleast < 1 || atleast > bv->cl.T)
+    return fail(VAQHIP_EINVAL, "atleast_cluster=%d outside 1..%d (past the centres the reference reads outside its array)",
+                atleast, bv->cl.T);
+  return VAQHIP_OK;
+}
+
+// BitVecEngine::queryWithClusterInfo(queries, oriQueries, k, Sort, atleast) for nq queries on the device, enqueued on
+// st inside the caller's workspace scope: per chunk of queries the visiting plan, then the scan and the selection in one
+int clusters_enqueue(vaqhip_bitvec *bv, const uint64_t *d_bq, const float *d_oq, int nq, int k, int atleast, int32_t *d_labels,
+                     float *d_dist, hipStream_t st) {
+  const BitvecClusters &cl = bv->cl;
+  const int64_t per_query = (int64_t)cl.T * sizeof(int32_t) + sizeof(vaq::BitvecClusterPlan);
+  const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)nq, (int64_t)QUERY_CHUNK, bv->dist_chunk_bytes / per_query}));
+  HIP_TRY(bv->w_visit.ensure((size_t)chunk * cl.T * sizeof(int32_t)));
+  HIP_TRY(bv->w_plan.ensure((size_t)chunk * sizeof(vaq::BitvecClusterPlan)));
+  for (int q0 = 0; q0 < nq; q0 += chunk) {
+    const int n = std::min(chunk, nq - q0);
+    HIP_TRY(vaq::launch_bitvec_cluster_plan(d_oq + (size_t)q0 * cl.D, n, cl.D, cl.centres_t.as<float>(), cl.T,
+                                            cl.start.as<int32_t>(), k, atleast, bv->w_visit.as<int32_t>(),
+                                            bv->w_plan.as<vaq::BitvecClusterPlan>(), st));
+    HIP_TRY(vaq::launch_bitvec_cluster_select(cl.image.as<uint64_t>(), bv->W, cl.start.as<int32_t>(), cl.member.as<int32_t>(),
+                                              cl.T, d_bq + (size_t)q0 * bv->W, n, bv->w_visit.as<int32_t>(),
+                                              bv->w_plan.as<vaq::BitvecClusterPlan>(), k, bv->id_base,
+                                              d_labels + (size_t)q0 * k, d_dist + (size_t)q0 * k, st));
+  }
+  return VAQHIP_OK;
+}
+
+// the plain form (rv null) or queryRerankWithClusterInfo(..., Sort, atleast, earlyAbandonRank = false) on the device
+int clusters_locked(vaqhip_bitvec *bv, const RefinerView *rv, const uint64_t *d_bq, const float *d_oq, int nq, int k, int factor,
+                    int atleast, int32_t *d_labels, float *d_dist, hipStream_t st) {
+  const int k_temp = rv ? (int)std::min<int64_t>((int64_t)factor * k, bv->N) : 0;
+  if (k_temp == 0) {  // the plain form, or no rows: every slot -1 / FLT_MAX
+    WS_SCOPE(ws, bv, st);
+    if (int rc = clusters_enqueue(bv, d_bq, d_oq, nq, k, atleast, d_labels, d_dist, st)) return rc;
+    return ws.finish();
+  }
+  const int chunk = std::min(nq, QUERY_CHUNK);
+  HIP_TRY(bv->w.cand_l.ensure((size_t)chunk * k_temp * sizeof(int32_t)));
+  HIP_TRY(bv->w.cand_d.ensure((size_t)chunk * k_temp * sizeof(float)));
+  WS_SCOPE(ws, bv, st);
+  for (int q0 = 0; q0 < nq; q0 += chunk) {
+    const int n = std::min(chunk, nq - q0);
+    if (int rc = clusters_enqueue(bv, d_bq + (size_t)q0 * bv->W, d_oq + (size_t)q0 * rv->D, n, k_temp, atleast,
+                                  bv->w.cand_l.as<int32_t>(), bv->w.cand_d.as<float>(), st))
+      return rc;
+    HIP_TRY(vaq::launch_bitvec_rerank(d_oq + (size_t)q0 * rv->D, n, rv->D, rv->rows, rv->N, rv->id_base, bv->w.cand_l.as<int32_t>(),
+                                      k_temp, k_temp, k, d_labels + (size_t)q0 * k, d_dist + (size_t)q0 * k, st));
+  }
+  return ws.finish();
+}
+
+// all four cluster entries: r null is the plain form; the queries and the answer are the device's, or the host's
+int clusters_entry(vaqhip_bitvec *bv, vaqhip_refiner *r, bool rerank, const uint64_t *bit_queries, const float *ori_queries,
+                   int nq, int k, int factor, int method, int atleast, int32_t *labels_out, float *distances_out,
+                   bool on_device, hipStream_t st) {
+  if (int rc = check_query(bv, nq, k, method, bit_queries, labels_out, distances_out)) return rc;
+  if (rerank && !r) return fail(VAQHIP_EINVAL, "refiner is null");
+  if (nq > 0 && !ori_queries) return fail(VAQHIP_EINVAL, "null pointer");
+  ENTRY(bv);
+  std::unique_lock<std::mutex> rlk;
+  RefinerView rv{};
+  if (rerank) {
+    rlk = std::unique_lock<std::mutex>(refiner_mutex(r));
+    rv = refiner_view(r);
+    if (int rc = check_rerank(bv, rv, k, factor)) return rc;
+  }
+  if (int rc = check_clusters(bv, atleast)) return rc;
+  if (rerank && rv.D != bv->cl.D)
+    return fail(VAQHIP_EINVAL, "the refiner's rows have D=%d, the centres D=%d", rv.D, bv->cl.D);
+  if (nq == 0) return VAQHIP_OK;
+  const RefinerView *rvp = rerank ? &rv : nullptr;
+  if (on_device)
+    return clusters_locked(bv, rvp, bit_queries, ori_queries, nq, k, factor, atleast, labels_out, distances_out, st);
+  StagingBufs &w = bv->w;
+  return through_staging(bv, {{&w.q, bit_queries, bv->W * sizeof(uint64_t)}, {&w.oq, ori_queries, bv->cl.D * sizeof(float)}}, nq,
+                         k, labels_out, distances_out, [&] {
+    return clusters_locked(bv, rvp, w.q.as<uint64_t>(), w.oq.as<float>(), nq, k, factor, atleast, w.lout.as<int32_t>(),
+                           w.dout.as<float>(), bv->stream);
+  });
+}
+
 }  // namespace
 
 extern "C" {
@@ -200,10 +289,54 @@ int vaqhip_bitvec_add_rows(vaqhip_bitvec *bv, const uint64_t *rows, int64_t n_ne
   ENTRY(bv);
   if (bv->N + n_new > 0x7fffffffLL - 1 || bv->id_base + bv->N + n_new > 0x7fffffffLL)
     return fail(VAQHIP_ERANGE, "labels are 32-bit ints: id_base+n = %lld", (long long)(bv->id_base + bv->N + n_new));
+  bv->cl.set = false;  // (the cluster state describes the rows as they were)
   HIP_TRY(bv->rows.reserve(vaq::fast_pad_rows(bv->N + n_new), bv->N, bv->W));
   // (rows past N are the padding: a query in flight may read them, but no answer depends on what they hold)
   if (int rc = write_rows(bv, rows, bv->N, n_new, false, nullptr)) return rc;
   bv->N += n_new;
+  return VAQHIP_OK;
+}
+
+int vaqhip_bitvec_set_clusters(vaqhip_bitvec *bv, const float *centroids, int T, int D, const int32_t *clust_idx) {
+  if (!bv) return fail(VAQHIP_EINVAL, "bitvec engine is null");
+  if (!centroids) return fail(VAQHIP_EINVAL, "null pointer");
+  if (T < 1 || T > vaq::BITVEC_CLUSTERS_MAX) return fail(VAQHIP_EINVAL, "T=%d centres outside 1..%d", T, vaq::BITVEC_CLUSTERS_MAX);
+  if (D < 1 || D > vaq::BITVEC_CLUSTERS_MAX_DIM)
+    return fail(VAQHIP_EINVAL, "D=%d outside 1..%d (the refiner's row limit)", D, vaq::BITVEC_CLUSTERS_MAX_DIM);
+  ENTRY(bv);
+  const int64_t N = bv->N, n_pad = vaq::fast_pad_rows(N);
+  if (N > 0 && !clust_idx) return fail(VAQHIP_EINVAL, "null pointer");
+  // a stable counting sort of the rows by cluster: start[c] is the first image row of cluster c, member[g] the row
+  std::vector<int32_t> start((size_t)T + 1, 0), member((size_t)std::max<int64_t>(N, 1));
+  for (int64_t i = 0; i < N; i++) {
+    if (clust_idx[i] < 0 || clust_idx[i] >= T)
+      return fail(VAQHIP_EINVAL, "clust_idx[%lld]=%d outside 0..%d", (long long)i, clust_idx[i], T - 1);
+    start[(size_t)clust_idx[i] + 1]++;
+  }
+  for (int c = 0; c < T; c++) start[(size_t)c + 1] += start[c];
+  {
+    std::vector<int32_t> next(start.begin(), start.end() - 1);
+    for (int64_t i = 0; i < N; i++) member[(size_t)next[clust_idx[i]]++] = (int32_t)i;
+  }
+  std::vector<float> centres_t((size_t)D * T);  // dimension-major: lane = centre reads adjacent floats
+  for (int c = 0; c < T; c++)
+    for (int d = 0; d < D; d++) centres_t[(size_t)d * T + c] = centroids[(size_t)c * D + d];
+  BitvecClusters &cl = bv->cl;
+  HIP_TRY(hipDeviceSynchronize());  // (a query enqueued on any stream may still read the old state)
+  cl.set = false;
+  HIP_TRY(cl.centres_t.ensure(centres_t.size() * sizeof(float)));
+  HIP_TRY(cl.start.ensure(start.size() * sizeof(int32_t)));
+  HIP_TRY(cl.member.ensure(member.size() * sizeof(int32_t)));
+  HIP_TRY(cl.image.ensure((size_t)n_pad * bv->rows.row_bytes(bv->W)));
+  HIP_TRY(hipMemcpy(cl.centres_t.p, centres_t.data(), centres_t.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(cl.start.p, start.data(), start.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(cl.member.p, member.data(), member.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIP_TRY(vaq::launch_bitvec_cluster_gather(bv->rows.buf.as<uint64_t>(), cl.member.as<int32_t>(), N, n_pad, bv->W,
+                                            cl.image.as<uint64_t>(), bv->stream));
+  HIP_TRY(hipStreamSynchronize(bv->stream));
+  cl.T = T;
+  cl.D = D;
+  cl.set = true;
   return VAQHIP_OK;
 }
 
@@ -251,6 +384,30 @@ int vaqhip_bitvec_query_rerank_device(vaqhip_bitvec *bv, vaqhip_refiner *r, cons
 int vaqhip_bitvec_query_rerank(vaqhip_bitvec *bv, vaqhip_refiner *r, const uint64_t *bit_queries, const float *ori_queries,
                                int nq, int k, int factor, int32_t *labels_out, float *distances_out) {
   return rerank_entry(bv, r, bit_queries, ori_queries, nq, k, factor, labels_out, distances_out, false, nullptr);
+}
+
+int vaqhip_bitvec_query_clusters(vaqhip_bitvec *bv, const uint64_t *bit_queries, const float *ori_queries, int nq, int k,
+                                 int method, int atleast_cluster, int32_t *labels_out, float *distances_out) {
+  return clusters_entry(bv, nullptr, false, bit_queries, ori_queries, nq, k, 1, method, atleast_cluster, labels_out,
+                        distances_out, false, nullptr);
+}
+int vaqhip_bitvec_query_clusters_device(vaqhip_bitvec *bv, const uint64_t *d_bit_queries, const float *d_ori_queries, int nq,
+                                        int k, int method, int atleast_cluster, int32_t *d_labels_out, float *d_distances_out,
+                                        void *stream) {
+  return clusters_entry(bv, nullptr, false, d_bit_queries, d_ori_queries, nq, k, 1, method, atleast_cluster, d_labels_out,
+                        d_distances_out, true, static_cast<hipStream_t>(stream));
+}
+int vaqhip_bitvec_query_rerank_clusters(vaqhip_bitvec *bv, vaqhip_refiner *r, const uint64_t *bit_queries,
+                                        const float *ori_queries, int nq, int k, int factor, int atleast_cluster,
+                                        int32_t *labels_out, float *distances_out) {
+  return clusters_entry(bv, r, true, bit_queries, ori_queries, nq, k, factor, VAQHIP_BITVEC_SORT, atleast_cluster, labels_out,
+                        distances_out, false, nullptr);
+}
+int vaqhip_bitvec_query_rerank_clusters_device(vaqhip_bitvec *bv, vaqhip_refiner *r, const uint64_t *d_bit_queries,
+                                               const float *d_ori_queries, int nq, int k, int factor, int atleast_cluster,
+                                               int32_t *d_labels_out, float *d_distances_out, void *stream) {
+  return clusters_entry(bv, r, true, d_bit_queries, d_ori_queries, nq, k, factor, VAQHIP_BITVEC_SORT, atleast_cluster,
+                        d_labels_out, d_distances_out, true, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 #define VAQHIP_BITVEC_H
 #include "vaqhip_index.h"
 
+#include "vaq_bitvec_clusters.h"
 #include "vaq_bitvec_encode.h"
 #include "vaqhip_refine_common.h"
 
@@ -21,15 +22,25 @@ struct BitvecEncoder {
   }
 };
 
+// What vaqhip_bitvec_set_clusters leaves on the device: the centres dimension-major, the clusters' first image rows
+// (start[T + 1]), the original row of every image row, and the bit rows once more, cluster after cluster.  Whatever
+// replaces or appends rows drops it (`set`); a set waits for the device before it replaces the buffers.
+struct BitvecClusters {
+  bool set = false;
+  int T = 0, D = 0;
+  vaqhost::DevBuf centres_t, start, member, image;
+};
+
 struct vaqhip_bitvec : vaqhost::HandleCore {
   int n_bits = 0, W = 0;
   int64_t N = 0, id_base = 0;
   int64_t dist_chunk_bytes = (int64_t)1 << 30;  // option "dist_chunk_bytes": the distance matrix of a chunk of queries
   vaqhost::RowStore rows;  // uint64 words (elem 8, W a row), room for the rows padded to FAST_ROW_PAD
   // workspaces (grow-only), shared by the callers' streams (WS_SCOPE): the distance matrix, FAST's head order and its
-  // scratch; the rerank's candidates and the staging of the host forms
-  vaqhost::DevBuf w_dist, w_order, w_scratch;
-  vaqhost::StagingBufs w;
+  // scratch; the cluster form's visit lists and plans
+  vaqhost::DevBuf w_dist, w_order, w_scratch, w_visit, w_plan;
+  vaqhost::StagingBufs w;  // the rerank's candidates and the staging of the host forms
   BitvecEncoder enc;
+  BitvecClusters cl;
 };
 #endif
