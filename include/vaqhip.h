@@ -1513,9 +1513,13 @@ int vaqhip_bitvec_query_rerank_device(vaqhip_bitvec *bv, vaqhip_refiner *r, cons
  *                 the bit rows on the device (the rows' bytes once more) and waits for the device before it replaces
  *                 them.  Whatever replaces or appends rows (set_rows*, add_rows, encode_set_rows*, encode_add_rows*,
  *                 encode_from_refiner) drops the state: a cluster query is then VAQHIP_ESTATE until the next set_clusters.
+ *                 An engine with no rows takes set_clusters too (clust_idx is not read and may be null): every cluster is
+ *                 empty, and a cluster query on it answers -1 / FLT_MAX in every slot, the rerank form as well.
  *   queries       ori_queries float [nq][D].  atleast_cluster outside 1..T is VAQHIP_EINVAL (the reference reads past
  *                 its centres there).  Where the candidates number fewer than k (only with n < k) the slots behind them
- *                 are -1 / FLT_MAX, as query answers.  Methods, k, nq and the refiner: as query and query_rerank
+ *                 are -1 / FLT_MAX, as query answers.  A centre distance that is NaN (a NaN coordinate in a query or a
+ *                 centre) leaves std::sort undefined in C++: the order is then the restated sort's, not one the reference
+ *                 defines.  Methods, k, nq and the refiner: as query and query_rerank
  *                 refuse them; the refiner's D must be the centres' (VAQHIP_EINVAL).
  * "dist_chunk_bytes" bounds the visit lists of a chunk of queries (4 T + 16 bytes a query). */
 int vaqhip_bitvec_set_clusters(vaqhip_bitvec *bv, const float *centroids, int T, int D, const int32_t *clust_idx);

@@ -36,6 +36,14 @@ RERANK = {
     "rerank_d16_k20_f3": (21, 128, 300, 4, 20, 3, 16, 3),
     "rerank_d7_k5_f10": (22, 64, 90, 3, 5, 10, 7, 3),
 }
+# name: (seed, n_bits, n, nq, k, factor, atleast, T, D): the cluster form.  Raw rows, raw queries and centres are small
+# integers; factor 0: no rerank.  Every query's centre distances are distinct integers, so the visiting order is plain
+# ascending order and needs no sort from anyone
+CLUSTERS = {
+    "clusters_w2_k20": (31, 128, 400, 3, 20, 0, 1, 6, 6),
+    "clusters_w1_k30_atleast4": (32, 64, 500, 3, 30, 0, 4, 7, 6),     # atleast beyond where the walk stops by itself
+    "clusters_rerank_d6_k8_f4": (33, 128, 300, 4, 8, 4, 2, 6, 6),
+}
 
 
 def bit_rows(rs, n_bits, n, flip, centres=None):
@@ -119,8 +127,72 @@ def make_rerank(name):
     return k > 16 and inside
 
 
+def make_clusters(name):
+    seed, n_bits, n, nq, k, factor, atleast, T, D = CLUSTERS[name]
+    rs = np.random.RandomState(seed)
+    rows, centres = bit_rows(rs, n_bits, n, 7)
+    queries, _ = bit_rows(rs, n_bits, nq, 7, centres)
+    top = 3
+    X = rs.randint(0, top, (n, D)).astype(np.uint8)
+    XQ = rs.randint(0, top, (nq, D)).astype(np.float32)
+    assert D * (top - 1) ** 2 <= 32767  # float and int16 comparisons agree
+    clust_idx = rs.randint(0, T, n).astype(np.int32)
+    k_walk = min(factor * k, n) if factor else k
+    while True:  # integer centres whose squared distances to every query are distinct
+        cen = rs.randint(-2 * top, 3 * top, (T, D)).astype(np.float32)
+        cd = ((XQ[:, None, :].astype(np.int64) - cen[None, :, :].astype(np.int64)) ** 2).sum(axis=2)
+        if all(len(np.unique(cd[q])) == T for q in range(nq)):
+            break
+    assert np.abs(np.diff(np.sort(cd, axis=1), axis=1)).min() >= 1 and cd.max() < 2 ** 24  # exact in float, well apart
+    sizes = np.bincount(clust_idx, minlength=T)
+    cands, n_cand = np.full((nq, n), -1, np.int32), np.zeros(nq, np.int32)
+    labels = np.empty((nq, k), np.int32)
+    dists = np.empty((nq, k), np.float32 if factor else np.uint32)
+    ham_labels = np.empty((nq, k_walk), np.int32)
+    tie = head = beyond = inside = across = False
+    for q in range(nq):
+        order = np.argsort(cd[q])  # (distinct: no sort's tie order is involved)
+        visit = cum = 0
+        for c in order:  # BitVecEngine.cpp:259-304: the centres are walked until their members number k ...
+            visit += 1
+            cum += sizes[c]
+            if cum >= k_walk:
+                break
+        beyond |= visit < atleast
+        visit = max(visit, atleast)  # ... and atleastCluster at least
+        cand = np.concatenate([np.flatnonzero(clust_idx == c) for c in order[:visit]]).astype(np.int32)
+        assert len(cand) >= k_walk
+        cands[q, :len(cand)], n_cand[q] = cand, len(cand)
+        h = br.hamming_dists(rows[cand], queries[q:q + 1])[0]
+        idx, dh = ref_topk(h, k_walk)
+        ham_labels[q] = cand[idx]
+        tie |= crosses(h, k_walk)
+        head |= len(np.unique(h[:k_walk])) < k_walk
+        if factor:
+            e = ((XQ[q][None, :].astype(np.int64) - X[ham_labels[q]].astype(np.int64)) ** 2).sum(axis=1)
+            idx, de = ref_topk(e, k)
+            labels[q] = ham_labels[q][idx]
+            dists[q] = de.astype(np.float32)
+            inside |= len(np.unique(e[:k])) < k
+            across |= crosses(e, k)
+        else:
+            labels[q], dists[q] = ham_labels[q], dh
+    assert tie, name + ": no Hamming tie across slot k"
+    assert k_walk > 16 and head, name + ": no equal distances among candidates 0..k-1 with k > 16"
+    assert beyond or atleast <= 2, name + ": atleast is not beyond the walk's own stopping point"
+    extra = {}
+    if factor:
+        assert inside and across, name + ": no equal Euclidean distances inside the head and across slot k"
+        extra = dict(factor=factor, X=X, hamming_labels=ham_labels)
+    np.savez_compressed(os.path.join(HERE, name + ".npz"), n_bits=n_bits, k=k, k_walk=k_walk, atleast=atleast, rows=rows,
+                        queries=queries, centroids=cen, clust_idx=clust_idx, XQ=XQ, candidates=cands[:, :n_cand.max()],
+                        n_cand=n_cand, labels=labels, dists=dists, **extra)
+    return beyond
+
+
 def main():
     assert po.have_ref(), "oracle/_ref is not built"
+    assert any([make_clusters(name) for name in CLUSTERS]), "no cluster fixture with atleast beyond the walk's stop"
     big_head = [make_hamming(name) for name in list(HAMMING) + list(FAR)]
     assert any(big_head), "no Hamming fixture with k > 16 and equal distances among rows 0..k-1"
     big_head = [make_rerank(name) for name in RERANK]
