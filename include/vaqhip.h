@@ -1472,7 +1472,8 @@ int vaqhip_last_timing(vaqhip_index *ix, vaqhip_timing *out);
  * The host forms are synchronous; the _device forms take pointers on the engine's GPU, enqueue on `stream` and do not
  * synchronise once the workspaces have their size.  Calls on one engine are serialised.  Errors leave their text in
  * vaqhip_last_error(), as the index's and the refiner's do.  Not provided: the other three methods, earlyAbandonRank,
- * the filtering and naive variants, a multi-device form.  The cluster forms and the encoders follow the queries below. */
+ * the filtering variants, the naive variants other than queryNaiveWithClusterInfo (the exact cluster form below), a
+ * multi-device form.  The cluster forms and the encoders follow the queries below. */
 typedef struct vaqhip_bitvec vaqhip_bitvec;
 #define VAQHIP_BITVEC_HEAP                0  /* BitVecEngine::QueryMethod (BitVecEngine.hpp:82-84) */
 #define VAQHIP_BITVEC_SORT                1
@@ -1534,6 +1535,31 @@ int vaqhip_bitvec_query_rerank_clusters(vaqhip_bitvec *bv, vaqhip_refiner *r, co
 int vaqhip_bitvec_query_rerank_clusters_device(vaqhip_bitvec *bv, vaqhip_refiner *r, const uint64_t *d_bit_queries,
                                                const float *d_ori_queries, int nq, int k, int factor, int atleast_cluster,
                                                int32_t *d_labels_out, float *d_distances_out, void *stream);
+
+/* ---- Hamming engine: the exact cluster form (BitVecEngine::queryNaiveWithClusterInfo) ----------------------------------
+ * BitVecEngine::queryNaiveWithClusterInfo(oriQueries, k, QueryMethod::Sort, atleastCluster) (BitVecEngine.cpp:875-918):
+ * IVF-flat over the cluster state.  The centre ranking and the walk are the cluster form's, unchanged; the candidates
+ * are the members of the visited clusters, cluster after cluster, each in ascending row order; EVERY candidate's
+ * distance is euclideanDistNoSQRT(ori_query, raw row) over the refiner's resident rows, float or byte (one float
+ * accumulator from 0.0f in dimension order, distance += (a - b) * (a - b), nothing fused); then
+ * KNNFromDistsIndicesSupplied: std::sort of the first k (dist, idx) pairs by distance alone, every later candidate
+ * behind its equals.  No bit queries are taken and no bit row is read: the recall is bounded by the clusters visited
+ * alone.  labels_out int32 [nq][k] = id_base + row, distances_out float [nq][k] the squared distances; slots past the
+ * candidates (only with n < k) are -1 / FLT_MAX.  A distance that overflows to +inf keeps its label and ranks by
+ * position behind every finite one; NaN (rows or queries that are not finite) is outside the contract, as for the rerank.
+ * Parity-unpinned like the cluster form.  One pass over the candidates' rows: no [nq][n] array and no per-query distance
+ * workspace is made.
+ *   refusals    as query_rerank_clusters makes them, before any device work: the refiner on the engine's device
+ *               (VAQHIP_EINVAL), holding the engine's n rows from its id_base (VAQHIP_ESTATE), its D the centres'
+ *               (VAQHIP_EINVAL); atleast_cluster in 1..T (VAQHIP_EINVAL); VAQHIP_ESTATE without set_clusters; k, nq and
+ *               the method as query refuses them (only VAQHIP_BITVEC_SORT; the other three VAQHIP_EUNSUPPORTED).
+ * "dist_chunk_bytes" bounds the visit lists of a chunk of queries, as for the cluster forms.  Not provided: queryNaive,
+ * queryNaiveTriangleInequality, the disk-resident and parallel variants. */
+int vaqhip_bitvec_query_naive_clusters(vaqhip_bitvec *bv, vaqhip_refiner *r, const float *ori_queries, int nq, int k,
+                                       int method, int atleast_cluster, int32_t *labels_out, float *distances_out);
+int vaqhip_bitvec_query_naive_clusters_device(vaqhip_bitvec *bv, vaqhip_refiner *r, const float *d_ori_queries, int nq, int k,
+                                              int method, int atleast_cluster, int32_t *d_labels_out, float *d_distances_out,
+                                              void *stream);
 
 /* ---- Hamming engine: the encoders (BitVecEngine::binaryEncodingSimple and ::binaryEncoding) on the device ------------
  * Raw rows (float or byte; host, device or resident in a refiner) -> bit rows, with no projected matrix written.  Both

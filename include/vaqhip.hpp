@@ -1041,6 +1041,28 @@ public:
                                                                         bool earlyAbandonRank = false) {
     return queryRerankWithClusterInfo(queries, FlatRows(oriQueries), k, factor, method, atleastCluster, earlyAbandonRank);
   }
+  // BitVecEngine::queryNaiveWithClusterInfo: exact squared distances to every member of the visited clusters over
+  // loadOriginal's rows; min(k, candidates) pairs per query; only QueryMethod::Sort
+  template <class Mat>
+  std::vector<std::vector<IdxDistPairFloat>> queryNaiveWithClusterInfo(const Mat &oriQueries, const int k,
+                                                                       int method = QueryMethod::Sort, int atleastCluster = 1) {
+    if (!ori_) throw Error(VAQHIP_ESTATE, "vaqhip: queryNaiveWithClusterInfo before loadOriginal");
+    ensureClusters();
+    const int nq = (int)oriQueries.rows();
+    checkOriQueries(oriQueries, nq, oriDim_);
+    std::vector<int> lab((size_t)nq * k);
+    std::vector<float> dis((size_t)nq * k);
+    check(vaqhip_bitvec_query_naive_clusters(bv_, ori_, oriQueries.data(), nq, k, method, atleastCluster, lab.data(), dis.data()));
+    std::vector<std::vector<IdxDistPairFloat>> answers(nq);
+    for (int i = 0; i < nq; i++)
+      for (int j = 0; j < k && lab[(size_t)i * k + j] >= 0; j++)
+        answers[i].push_back({lab[(size_t)i * k + j], dis[(size_t)i * k + j]});
+    return answers;
+  }
+  std::vector<std::vector<IdxDistPairFloat>> queryNaiveWithClusterInfo(const Matrixf &oriQueries, const int k,
+                                                                       int method = QueryMethod::Sort, int atleastCluster = 1) {
+    return queryNaiveWithClusterInfo(FlatRows(oriQueries), k, method, atleastCluster);
+  }
   vaqhip_bitvec *bitvecHandle() const { return bv_; }
   // Several devices (a device named several times: logical shards on that GPU): binaryEncodingLUT then fits over
   // them (vaqhip_multi_lut_fit_quantiles), builds a VAQHIP_SUM_SEQUENTIAL multi index, gives it Q and encodes across

@@ -80,6 +80,7 @@ SYMBOLS = [
     "vaqhip_bitvec_encode_add_rows_u8", "vaqhip_bitvec_encode_from_refiner",
     "vaqhip_bitvec_set_clusters", "vaqhip_bitvec_query_clusters", "vaqhip_bitvec_query_clusters_device",
     "vaqhip_bitvec_query_rerank_clusters", "vaqhip_bitvec_query_rerank_clusters_device",
+    "vaqhip_bitvec_query_naive_clusters", "vaqhip_bitvec_query_naive_clusters_device",
 ]
 MAX_DEVICES = 16
 
@@ -351,6 +352,8 @@ def load():
     L.vaqhip_bitvec_query_clusters_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.vaqhip_bitvec_query_rerank_clusters.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.vaqhip_bitvec_query_rerank_clusters_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.vaqhip_bitvec_query_naive_clusters.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp]
+    L.vaqhip_bitvec_query_naive_clusters_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.vaqhip_index_info.argtypes = [vp, C.POINTER(Info)]
     L.vaqhip_set_option.argtypes = [vp, C.c_char_p, i64]
     L.vaqhip_last_timing.argtypes = [vp, C.POINTER(Timing)]

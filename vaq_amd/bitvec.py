@@ -40,6 +40,7 @@ class VaqBitVec(_Handle):
         bv.set_clusters(centroids, clust_idx)                 # loadCentroids, loadClusterInfo
         labels, dist = bv.query_clusters(Qbits, XTest, 100, atleast_cluster=8)
         ans = bv.query_rerank_clusters(Qbits, XTest, 100, 10, r, atleast_cluster=8)
+        ans = bv.query_naive_clusters(XTest, 100, r, atleast_cluster=8)   # exact distances to every member visited
     """
     _destroy = "vaqhip_bitvec_destroy"
 
@@ -285,6 +286,39 @@ class VaqBitVec(_Handle):
         labels, dists = _out_pair(out, nq, k, q.device)
         self._call("query_rerank_clusters_device", refiner._h, _dptr(q), _dptr(oq), nq, int(k), int(factor),
                    int(atleast_cluster), _dptr(labels), _dptr(dists), _stream(q))
+        return labels, dists
+
+    # ---- the exact cluster form: BitVecEngine::queryNaiveWithClusterInfo ----
+    def query_naive_clusters(self, ori_queries, k: int, refiner, method: int = QueryMethod.Sort, atleast_cluster: int = 1):
+        """BitVecEngine::queryNaiveWithClusterInfo: the k best by exact squared Euclidean distance among ALL members of
+        the clusters query_clusters would visit, over the rows of a VaqRefiner on the same device (float or byte); no
+        bits are read.  (labels int32 [nq][k], distances float32 [nq][k]); slots past the candidates -1 / FLT_MAX."""
+        D = getattr(self, "cluster_D", 0)
+        if not D:
+            raise _lib.VaqHipError(-7, "no cluster state: call set_clusters first")
+        XQ = _f32_rows(ori_queries, D, "oriQueries {shape} are not nq x {D}")
+        nq = XQ.shape[0]
+        lab = np.empty((nq, k), np.int32)
+        dis = np.empty((nq, k), np.float32)
+        self._call("query_naive_clusters", refiner._h, _ptr(XQ), nq, int(k), int(method), int(atleast_cluster), _ptr(lab),
+                   _ptr(dis))
+        return lab, dis
+
+    def query_naive_clusters_device(self, d_ori_queries, k: int, refiner, method: int = QueryMethod.Sort,
+                                    atleast_cluster: int = 1, out=None):
+        """query_naive_clusters() on a float32 [nq][D] torch CUDA tensor, enqueued on torch's current stream, no
+        synchronisation."""
+        import torch
+        D = getattr(self, "cluster_D", 0)
+        if not D:
+            raise _lib.VaqHipError(-7, "no cluster state: call set_clusters first")
+        oq = d_ori_queries.contiguous()
+        if not (oq.is_cuda and oq.device.index == self.device and oq.dtype == torch.float32 and oq.dim() == 2 and oq.shape[1] == D):
+            raise _lib.VaqHipError(-1, f"device oriQueries must be float32 nq x {D} on cuda:{self.device}")
+        nq = oq.shape[0]
+        labels, dists = _out_pair(out, nq, k, oq.device)
+        self._call("query_naive_clusters_device", refiner._h, _dptr(oq), nq, int(k), int(method), int(atleast_cluster),
+                   _dptr(labels), _dptr(dists), _stream(oq))
         return labels, dists
 
 

@@ -36,6 +36,7 @@ SOURCES = [
     "vaq_train.hip",
     "vaq_bitvec.hip",
     "vaq_bitvec_clusters.hip",
+    "vaq_bitvec_naive.hip",
     "vaq_bitvec_encode.hip",
     # the single-index host
     "vaqhip_api.cpp",
@@ -62,9 +63,11 @@ SOURCES = [
     "vaqhip_multi_codebooks.cpp",
     "vaqhip_rccl.cpp",
 ]
-# flags of single units: packed fp32 arithmetic is kept out of the encoder's FMA chains and of the centre distances
+# flags of single units: packed fp32 arithmetic is kept out of the encoder's FMA chains, of the centre distances and of
+# the exact cluster form's row distances
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
-UNIT_FLAGS = {"vaq_bitvec_encode.hip": _NO_PACKED_FP32, "vaq_bitvec_clusters.hip": _NO_PACKED_FP32}
+UNIT_FLAGS = {"vaq_bitvec_encode.hip": _NO_PACKED_FP32, "vaq_bitvec_clusters.hip": _NO_PACKED_FP32,
+              "vaq_bitvec_naive.hip": _NO_PACKED_FP32}
 OBJDIR = os.path.join(LIBDIR, "obj")
 # Experiment builds: VAQ_VARIANT=name compiles (with VAQ_EXTRA_FLAGS) into vaq_amd/lib/variants/name/
 # and VAQHIP_LIB=<path> makes the package load that library instead (tools/ sweeps).

@@ -126,14 +126,16 @@ constexpr int THRESHOLD = 16;
 // comparator (NaN keys) the real function may run past an end of the sequence and read whatever lies
 // there.  With GUARDED the scans stop at the ends of the range instead -- the same walk wherever the
 // real function stays inside, and defined where it does not.
-template <int LG_MAX, bool GUARDED, class T, class Lt>
-__host__ __device__ inline void sort_by(T *f, int n, Lt lt) {
+// sort_by_on: the same over a stack the caller supplies, frames(LG_MAX) frames of it (a kernel whose one sorting
+// thread would otherwise be the only user of scratch memory keeps the stack in LDS).
+struct Frame { int lo, hi, depth; };
+constexpr int frames(int lg_max) { return 2 * (lg_max + 1) + 2; }
+template <bool GUARDED, class T, class Lt>
+__host__ __device__ inline void sort_by_on(T *f, int n, Lt lt, Frame *stack) {
   if (n <= 1) return;
   const Impl<T, Lt> s{lt};
   int lg = 0;
   while ((2 << lg) <= n) lg++;  // std::__lg(n)
-  struct Frame { int lo, hi, depth; };
-  Frame stack[2 * (LG_MAX + 1) + 2];
   int sp = 0;
   stack[sp++] = {0, n, 2 * lg};
   while (sp > 0) {
@@ -160,6 +162,11 @@ __host__ __device__ inline void sort_by(T *f, int n, Lt lt) {
   } else {
     s.template insertion_sort<GUARDED>(f, 0, n);
   }
+}
+template <int LG_MAX, bool GUARDED, class T, class Lt>
+__host__ __device__ inline void sort_by(T *f, int n, Lt lt) {
+  Frame stack[frames(LG_MAX)];
+  sort_by_on<GUARDED>(f, n, lt, stack);
 }
 }  // namespace stdsort
 

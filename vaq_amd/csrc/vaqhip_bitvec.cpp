@@ -1,10 +1,12 @@
 // vaqhip_bitvec.cpp -- the Hamming engine of include/vaqhip.h: packed bit rows resident on the device,
 // BitVecEngine::query with QueryMethod::Sort over them (vaq_bitvec.hip's scan, then FAST's selection: vaq_fast.hip)
 // and BitVecEngine::queryRerank over a resident refiner's raw rows (the Hamming candidates stay on the device); the
-// cluster forms of both (queryWithClusterInfo: vaq_bitvec_clusters.hip's plan and fused scan-and-select).
+// cluster forms of both (queryWithClusterInfo: vaq_bitvec_clusters.hip's plan and fused scan-and-select); the exact
+// cluster form (queryNaiveWithClusterInfo: the same plan, then vaq_bitvec_naive.hip over the refiner's raw rows).
 #include "vaqhip_index.h"
 
 #include "vaq_bitvec.h"
+#include "vaq_bitvec_naive.h"
 #include "vaq_fast.h"
 #include "vaqhip_bitvec.h"
 
@@ -90,16 +92,22 @@ int query_locked(vaqhip_bitvec *bv, const uint64_t *d_q, int nq, int k, int32_t 
   return ws.finish();
 }
 
-// what a rerank call must hold before any device work; rv is read under the refiner's lock
-int check_rerank(const vaqhip_bitvec *bv, const RefinerView &rv, int k, int factor) {
-  if (factor < 1) return fail(VAQHIP_EINVAL, "factor=%d < 1", factor);
-  if ((int64_t)factor * k > VAQHIP_MAX_K)
-    return fail(VAQHIP_EUNSUPPORTED, "factor * k = %lld > %d candidates per query", (long long)factor * k, VAQHIP_MAX_K);
+// the refiner describes the engine's rows, on the engine's device; rv is read under the refiner's lock
+int check_refiner_rows(const vaqhip_bitvec *bv, const RefinerView &rv) {
   if (rv.device != bv->device)
     return fail(VAQHIP_EINVAL, "the bitvec engine is on device %d, the refiner on device %d", bv->device, rv.device);
   if (rv.N != bv->N || rv.id_base != bv->id_base)
     return fail(VAQHIP_ESTATE, "the bitvec engine holds %lld rows from label %lld, the refiner %lld from %lld",
                 (long long)bv->N, (long long)bv->id_base, (long long)rv.N, (long long)rv.id_base);
+  return VAQHIP_OK;
+}
+
+// what a rerank call must hold before any device work
+int check_rerank(const vaqhip_bitvec *bv, const RefinerView &rv, int k, int factor) {
+  if (factor < 1) return fail(VAQHIP_EINVAL, "factor=%d < 1", factor);
+  if ((int64_t)factor * k > VAQHIP_MAX_K)
+    return fail(VAQHIP_EUNSUPPORTED, "factor * k = %lld > %d candidates per query", (long long)factor * k, VAQHIP_MAX_K);
+  if (int rc = check_refiner_rows(bv, rv)) return rc;
   if ((size_t)rv.D > vaq::bitvec_rerank_max_dim())
     return fail(VAQHIP_EUNSUPPORTED, "D=%d: the query row must fit the workgroup's LDS (%zu floats)", rv.D,
                 vaq::bitvec_rerank_max_dim());
@@ -238,6 +246,47 @@ int clusters_entry(vaqhip_bitvec *bv, vaqhip_refiner *r, bool rerank, const uint
                          k, labels_out, distances_out, [&] {
     return clusters_locked(bv, rvp, w.q.as<uint64_t>(), w.oq.as<float>(), nq, k, factor, atleast, w.lout.as<int32_t>(),
                            w.dout.as<float>(), bv->stream);
+  });
+}
+
+// BitVecEngine::queryNaiveWithClusterInfo(oriQueries, k, Sort, atleast) for nq queries on the device, enqueued on st:
+// per chunk of queries the visiting plan, then the exact distances to every member visited and the selection in one
+int naive_locked(vaqhip_bitvec *bv, const RefinerView &rv, const float *d_oq, int nq, int k, int atleast, int32_t *d_labels,
+                 float *d_dist, hipStream_t st) {
+  const BitvecClusters &cl = bv->cl;
+  const int64_t per_query = (int64_t)cl.T * sizeof(int32_t) + sizeof(vaq::BitvecClusterPlan);
+  const int chunk = (int)std::max<int64_t>(1, std::min<int64_t>({(int64_t)nq, (int64_t)QUERY_CHUNK, bv->dist_chunk_bytes / per_query}));
+  WS_SCOPE(ws, bv, st);
+  HIP_TRY(bv->w_visit.ensure((size_t)chunk * cl.T * sizeof(int32_t)));
+  HIP_TRY(bv->w_plan.ensure((size_t)chunk * sizeof(vaq::BitvecClusterPlan)));
+  for (int q0 = 0; q0 < nq; q0 += chunk) {
+    const int n = std::min(chunk, nq - q0);
+    const float *oq = d_oq + (size_t)q0 * cl.D;
+    HIP_TRY(vaq::launch_bitvec_cluster_plan(oq, n, cl.D, cl.centres_t.as<float>(), cl.T, cl.start.as<int32_t>(), k, atleast,
+                                            bv->w_visit.as<int32_t>(), bv->w_plan.as<vaq::BitvecClusterPlan>(), st));
+    HIP_TRY(vaq::launch_bitvec_cluster_exact_select(oq, n, cl.D, rv.rows, rv.N, cl.start.as<int32_t>(), cl.member.as<int32_t>(),
+                                                    cl.T, bv->w_visit.as<int32_t>(), bv->w_plan.as<vaq::BitvecClusterPlan>(), k,
+                                                    bv->id_base, d_labels + (size_t)q0 * k, d_dist + (size_t)q0 * k, st));
+  }
+  return ws.finish();
+}
+
+// both exact cluster entries: the queries and the answer are the device's and the work goes on st, or the host's
+int naive_entry(vaqhip_bitvec *bv, vaqhip_refiner *r, const float *ori_queries, int nq, int k, int method, int atleast,
+                int32_t *labels_out, float *distances_out, bool on_device, hipStream_t st) {
+  if (int rc = check_query(bv, nq, k, method, ori_queries, labels_out, distances_out)) return rc;
+  if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
+  ENTRY(bv);
+  std::lock_guard<std::mutex> rlk(refiner_mutex(r));
+  const RefinerView rv = refiner_view(r);
+  if (int rc = check_refiner_rows(bv, rv)) return rc;
+  if (int rc = check_clusters(bv, atleast)) return rc;
+  if (rv.D != bv->cl.D) return fail(VAQHIP_EINVAL, "the refiner's rows have D=%d, the centres D=%d", rv.D, bv->cl.D);
+  if (nq == 0) return VAQHIP_OK;
+  if (on_device) return naive_locked(bv, rv, ori_queries, nq, k, atleast, labels_out, distances_out, st);
+  StagingBufs &w = bv->w;
+  return through_staging(bv, {{&w.oq, ori_queries, rv.D * sizeof(float)}}, nq, k, labels_out, distances_out, [&] {
+    return naive_locked(bv, rv, w.oq.as<float>(), nq, k, atleast, w.lout.as<int32_t>(), w.dout.as<float>(), bv->stream);
   });
 }
 
@@ -408,6 +457,17 @@ int vaqhip_bitvec_query_rerank_clusters_device(vaqhip_bitvec *bv, vaqhip_refiner
                                                int32_t *d_labels_out, float *d_distances_out, void *stream) {
   return clusters_entry(bv, r, true, d_bit_queries, d_ori_queries, nq, k, factor, VAQHIP_BITVEC_SORT, atleast_cluster,
                         d_labels_out, d_distances_out, true, static_cast<hipStream_t>(stream));
+}
+
+int vaqhip_bitvec_query_naive_clusters(vaqhip_bitvec *bv, vaqhip_refiner *r, const float *ori_queries, int nq, int k,
+                                       int method, int atleast_cluster, int32_t *labels_out, float *distances_out) {
+  return naive_entry(bv, r, ori_queries, nq, k, method, atleast_cluster, labels_out, distances_out, false, nullptr);
+}
+int vaqhip_bitvec_query_naive_clusters_device(vaqhip_bitvec *bv, vaqhip_refiner *r, const float *d_ori_queries, int nq, int k,
+                                              int method, int atleast_cluster, int32_t *d_labels_out, float *d_distances_out,
+                                              void *stream) {
+  return naive_entry(bv, r, d_ori_queries, nq, k, method, atleast_cluster, d_labels_out, d_distances_out, true,
+                     static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"
