@@ -1561,6 +1561,46 @@ int vaqhip_bitvec_query_naive_clusters_device(vaqhip_bitvec *bv, vaqhip_refiner 
                                               int method, int atleast_cluster, int32_t *d_labels_out, float *d_distances_out,
                                               void *stream);
 
+/* ---- Cluster index: the cluster of every raw row (computeClusterIndex, utils/Experiment.hpp:372-392) ------------------
+ * What set_clusters takes as clust_idx, made on the device.  For every row, in row order: nearestIdx = -1, nearestDist =
+ * FLT_MAX; for the centres c = 0 .. T - 1 in order dist = 0.0f, for i = 0 .. D - 1 dist += (row[i] - centre[i]) *
+ * (row[i] - centre[i]) (one float accumulator, every step rounded, nothing fused); if (dist < nearestDist) take c.  So
+ * the first of several equally near centres wins; a distance that is NaN, +inf or >= FLT_MAX never wins; a row with no
+ * other distance gets -1.  A byte row is widened where it is loaded: the byte forms equal the float forms over the
+ * widened rows bit for bit.  Parity-unpinned like the cluster forms: the checker is a float32 restatement of these lines.
+ *   outputs     clust_idx_out int32 [n]; dist_out float [n], the chosen centre's squared distance (FLT_MAX beside -1), may
+ *               be NULL.  centroids float [T][D] row-major.
+ *   refiner     vaqhip_refiner_cluster_index[_device]: over the refiner's resident rows, float or byte, read in place;
+ *               row i of the output is row i of the refiner, D is the refiner's.
+ *   raw rows    vaqhip_cluster_index[_u8][_device]: rows that are in no refiner, n x D on the host or on device_id.  The
+ *               host forms stage the rows in pieces of 2^20, so a dataset larger than the device is assigned in one
+ *               call or in batches of the caller's.
+ *   set_clusters_from_refiner  assigns the refiner's rows on the device, fetches the n indices and then does exactly what
+ *               vaqhip_bitvec_set_clusters(bv, centroids, T, D, those indices) does.  The refiner as the rerank forms
+ *               require it: on the engine's device (VAQHIP_EINVAL), holding the engine's n rows from its id_base
+ *               (VAQHIP_ESTATE), its D the centres' (VAQHIP_EINVAL).  If any row's index is -1 the call is VAQHIP_EINVAL,
+ *               names the first such row and leaves the cluster state as it was (the reference would index
+ *               clusterMembers[-1]).
+ *   limits      1 <= T <= 4096, 1 <= D <= 8176, 0 <= n < 2^31, null pointers: VAQHIP_EINVAL, before any device work.
+ *               n == 0 succeeds and writes nothing.
+ * The host forms are synchronous.  The _device forms take pointers on the rows' GPU, enqueue one kernel on `stream` and
+ * neither allocate nor synchronise.  Not provided: the centres themselves (k-means), computeTriangleInequalityClusters,
+ * a multi-device form. */
+/* rows held (what clust_idx_out must have room for), or a negative error code */
+int64_t vaqhip_refiner_size(vaqhip_refiner *r);
+int vaqhip_refiner_cluster_index(vaqhip_refiner *r, const float *centroids, int T, int32_t *clust_idx_out, float *dist_out);
+int vaqhip_refiner_cluster_index_device(vaqhip_refiner *r, const float *d_centroids, int T, int32_t *d_clust_idx_out,
+                                        float *d_dist_out, void *stream);
+int vaqhip_cluster_index(int device_id, const float *X, int64_t n, int D, const float *centroids, int T, int32_t *clust_idx_out,
+                         float *dist_out);
+int vaqhip_cluster_index_u8(int device_id, const uint8_t *X, int64_t n, int D, const float *centroids, int T,
+                            int32_t *clust_idx_out, float *dist_out);
+int vaqhip_cluster_index_device(int device_id, const float *d_X, int64_t n, int D, const float *d_centroids, int T,
+                                int32_t *d_clust_idx_out, float *d_dist_out, void *stream);
+int vaqhip_cluster_index_u8_device(int device_id, const uint8_t *d_X, int64_t n, int D, const float *d_centroids, int T,
+                                   int32_t *d_clust_idx_out, float *d_dist_out, void *stream);
+int vaqhip_bitvec_set_clusters_from_refiner(vaqhip_bitvec *bv, vaqhip_refiner *r, const float *centroids, int T, int D);
+
 /* ---- Hamming engine: the encoders (BitVecEngine::binaryEncodingSimple and ::binaryEncoding) on the device ------------
  * Raw rows (float or byte; host, device or resident in a refiner) -> bit rows, with no projected matrix written.  Both
  * forms start where the eigenvectors, and for the quantile form the bits per dimension, are given: the PCA and the

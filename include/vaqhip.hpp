@@ -908,10 +908,12 @@ public:
   void loadOriginal(const RowMatrix<float> &oriDataset) {
     newOriginal((int)oriDataset.cols());
     check(vaqhip_refiner_set_rows(ori_, oriDataset.data(), (int64_t)oriDataset.rows(), 0));
+    oriRows_ = (int64_t)oriDataset.rows();
   }
   void loadOriginal(const RowMatrix<uint8_t> &oriDataset) {
     newOriginal((int)oriDataset.cols());
     check(vaqhip_refiner_set_rows_u8(ori_, oriDataset.data(), (int64_t)oriDataset.rows(), 0));
+    oriRows_ = (int64_t)oriDataset.rows();
   }
   // BitVecEngine::query: min(k, rows) pairs per query.  Only QueryMethod::Sort is provided: the other three keep
   // other rows among equal distances (vaqhip.h), and throw as parseMethodString does for a token it does not serve
@@ -989,6 +991,24 @@ public:
     clustIdx_ = std::move(clustIdx);
     centroidsSize_ = _centroids_size;
     clustersPushed_ = false;
+  }
+  // computeClusterIndex (utils/Experiment.hpp:372-392) on the device: the nearest of loadCentroids' centres for every
+  // row of loadOriginal, the first of equally near ones; -1 where no distance is below FLT_MAX
+  void computeClusterIndex(std::vector<int> &clusterIdx) {
+    const FlatRows c(centresForOriginal());
+    if ((int)c.cols() != oriDim_) throw Error(VAQHIP_EINVAL, "vaqhip: the centres' dimension differs from loadOriginal's rows");
+    clusterIdx.assign((size_t)oriRows_, -1);
+    check(vaqhip_refiner_cluster_index(ori_, c.data(), (int)c.rows(), clusterIdx.data(), nullptr));
+  }
+  // computeClusterIndex and loadClusterInfo in one: the cluster state of the bit vectors from loadOriginal's rows and
+  // loadCentroids' centres, the indices never visiting the caller (vaqhip_bitvec_set_clusters_from_refiner)
+  void loadClusterInfoFromOriginal() {
+    const FlatRows c(centresForOriginal());
+    if (!bv_) throw Error(VAQHIP_ESTATE, "vaqhip: loadClusterInfoFromOriginal before loadBitV");
+    check(vaqhip_bitvec_set_clusters_from_refiner(bv_, ori_, c.data(), (int)c.rows(), (int)c.cols()));
+    centroidsSize_ = (int)c.rows();
+    clusterDim_ = (int)c.cols();
+    clustersPushed_ = true;
   }
   // BitVecEngine::queryWithClusterInfo: min(k, candidates) pairs per query; only QueryMethod::Sort, as query
   template <class Mat>
@@ -1211,6 +1231,10 @@ private:
     if ((int)oriQueries.rows() != nq || (nq > 0 && (int)oriQueries.cols() != D))
       throw Error(VAQHIP_EINVAL, "vaqhip: oriQueries must have one row of the centres' dimension per query");
   }
+  const Matrixf &centresForOriginal() const {
+    if (!ori_ || centroids_.empty()) throw Error(VAQHIP_ESTATE, "vaqhip: a cluster index before loadOriginal and loadCentroids");
+    return centroids_;
+  }
   // vaqhip_bitvec_set_clusters once the bit vectors, the centres and the cluster indices are all there
   void ensureClusters() {
     if (!bv_ || centroids_.empty() || centroidsSize_ < 0)
@@ -1262,6 +1286,7 @@ private:
   vaqhip_bitvec *bv_ = nullptr;   // loadBitV
   vaqhip_refiner *ori_ = nullptr;  // loadOriginal
   int bitWords_ = 0, oriDim_ = 0, encDim_ = 0;
+  int64_t oriRows_ = 0;
   Matrixf centroids_;            // loadCentroids
   std::vector<int> clustIdx_;    // loadClusterInfo
   int centroidsSize_ = -1, clusterDim_ = 0;

@@ -10,6 +10,8 @@ Product surface:
   vaq_amd.VaqBitVec           BitVecEngine::query / ::queryRerank (QueryMethod::Sort) over packed bit rows on the device
   VaqBitVec.set_encoder / .encode / .set_rows_encoded / .encode_from_refiner  the engine's bits made on the device from
                               raw rows (binaryEncodingSimple, binaryEncoding); vaq_amd.bitvec_fit_thresholds[_u8]
+  vaq_amd.cluster_index       computeClusterIndex on the device: the cluster of every raw row (cluster_index_u8 from bytes;
+                              VaqRefiner.cluster_index over resident rows; VaqBitVec.set_clusters_from_refiner)
   vaq_amd.lut_fit_quantiles_multi  binaryEncodingLUT's quantile codebooks with the rows cut over several GPUs
   vaq_amd.lut_fit_quantiles_multi_u8  the same from byte rows (a bvecs dataset as its file holds it)
   vaq_amd.fit_codebooks       the subspace codebooks (KMeans::staticFitSampling per subspace) from raw rows
@@ -35,6 +37,7 @@ from .index import fit_codebooks_hier, fit_codebooks_hier_u8, last_fit_codebooks
 from .index import fit_codebooks_bin, fit_codebooks_bin_u8, last_fit_codebooks_bin_timing  # noqa: F401
 from .index import last_train_timing, train, train_rotation  # noqa: F401
 from .index import QueryMethod, VaqBitVec, bitvec_fit_thresholds, bitvec_fit_thresholds_u8  # noqa: F401
+from .index import cluster_index, cluster_index_u8  # noqa: F401
 
 __all__ = ["VaqHip", "VaqHipFast", "VaqHipMulti", "VaqRefiner", "VaqMultiRefiner", "NNMethod", "LabelDistVec", "VaqHipError", "load", "lib_path",
            "lut_fit_quantiles_multi", "lut_fit_quantiles_multi_u8", "last_lut_fit_multi_timing",
@@ -42,4 +45,4 @@ __all__ = ["VaqHip", "VaqHipFast", "VaqHipMulti", "VaqRefiner", "VaqMultiRefiner
            "last_multi_fit_codebooks_timing", "fit_codebooks_hier", "fit_codebooks_hier_u8",
            "last_fit_codebooks_hier_timing", "fit_codebooks_bin", "fit_codebooks_bin_u8", "last_fit_codebooks_bin_timing",
            "train_rotation", "train", "last_train_timing", "VaqBitVec", "QueryMethod",
-           "bitvec_fit_thresholds", "bitvec_fit_thresholds_u8"]
+           "bitvec_fit_thresholds", "bitvec_fit_thresholds_u8", "cluster_index", "cluster_index_u8"]

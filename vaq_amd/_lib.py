@@ -81,6 +81,8 @@ SYMBOLS = [
     "vaqhip_bitvec_set_clusters", "vaqhip_bitvec_query_clusters", "vaqhip_bitvec_query_clusters_device",
     "vaqhip_bitvec_query_rerank_clusters", "vaqhip_bitvec_query_rerank_clusters_device",
     "vaqhip_bitvec_query_naive_clusters", "vaqhip_bitvec_query_naive_clusters_device",
+    "vaqhip_refiner_size", "vaqhip_refiner_cluster_index", "vaqhip_refiner_cluster_index_device", "vaqhip_cluster_index", "vaqhip_cluster_index_u8",
+    "vaqhip_cluster_index_device", "vaqhip_cluster_index_u8_device", "vaqhip_bitvec_set_clusters_from_refiner",
 ]
 MAX_DEVICES = 16
 
@@ -354,6 +356,14 @@ def load():
     L.vaqhip_bitvec_query_rerank_clusters_device.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
     L.vaqhip_bitvec_query_naive_clusters.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp]
     L.vaqhip_bitvec_query_naive_clusters_device.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp]
+    L.vaqhip_refiner_size.argtypes = [vp]
+    L.vaqhip_refiner_size.restype = i64
+    L.vaqhip_refiner_cluster_index.argtypes = [vp, vp, i32, vp, vp]
+    L.vaqhip_refiner_cluster_index_device.argtypes = [vp, vp, i32, vp, vp, vp]
+    for u8 in ("", "_u8"):
+        getattr(L, "vaqhip_cluster_index" + u8).argtypes = [i32, vp, i64, i32, vp, i32, vp, vp]
+        getattr(L, "vaqhip_cluster_index" + u8 + "_device").argtypes = [i32, vp, i64, i32, vp, i32, vp, vp, vp]
+    L.vaqhip_bitvec_set_clusters_from_refiner.argtypes = [vp, vp, vp, i32, i32]
     L.vaqhip_index_info.argtypes = [vp, C.POINTER(Info)]
     L.vaqhip_set_option.argtypes = [vp, C.c_char_p, i64]
     L.vaqhip_last_timing.argtypes = [vp, C.POINTER(Timing)]

@@ -38,6 +38,7 @@ class VaqBitVec(_Handle):
     The sub-linear forms visit only the members of the clusters nearest to each query (queryWithClusterInfo):
 
         bv.set_clusters(centroids, clust_idx)                 # loadCentroids, loadClusterInfo
+        bv.set_clusters_from_refiner(centroids, r)            # or with clust_idx made on the device (computeClusterIndex)
         labels, dist = bv.query_clusters(Qbits, XTest, 100, atleast_cluster=8)
         ans = bv.query_rerank_clusters(Qbits, XTest, 100, 10, r, atleast_cluster=8)
         ans = bv.query_naive_clusters(XTest, 100, r, atleast_cluster=8)   # exact distances to every member visited
@@ -218,6 +219,16 @@ class VaqBitVec(_Handle):
         if idx.shape[0] != len(self):
             raise _lib.VaqHipError(-1, f"{idx.shape[0]} cluster indices for {len(self)} rows")
         self._call("set_clusters", _ptr(cen), cen.shape[0], cen.shape[1], _ptr(idx))
+        self.cluster_D = cen.shape[1]
+
+    def set_clusters_from_refiner(self, centroids, refiner) -> None:
+        """set_clusters(centroids, refiner.cluster_index(centroids)) with the assignment made on the device
+        (computeClusterIndex over the refiner's rows, float or byte): the refiner holds the raw rows of the bit rows
+        held.  A row with no centre below FLT_MAX (index -1) is EINVAL and the state stays as it was."""
+        cen = np.ascontiguousarray(centroids, dtype=np.float32)
+        if cen.ndim != 2 or cen.shape[0] < 1 or cen.shape[1] < 1:
+            raise _lib.VaqHipError(-1, f"centroids {cen.shape} are not T x D")
+        self._call("set_clusters_from_refiner", refiner._h, _ptr(cen), cen.shape[0], cen.shape[1])
         self.cluster_D = cen.shape[1]
 
     def _ori(self, Q, ori_queries) -> np.ndarray:

@@ -92,8 +92,10 @@ int query_locked(vaqhip_bitvec *bv, const uint64_t *d_q, int nq, int k, int32_t 
   return ws.finish();
 }
 
+}  // namespace
+
 // the refiner describes the engine's rows, on the engine's device; rv is read under the refiner's lock
-int check_refiner_rows(const vaqhip_bitvec *bv, const RefinerView &rv) {
+int vaqhost::check_refiner_rows(const vaqhip_bitvec *bv, const RefinerView &rv) {
   if (rv.device != bv->device)
     return fail(VAQHIP_EINVAL, "the bitvec engine is on device %d, the refiner on device %d", bv->device, rv.device);
   if (rv.N != bv->N || rv.id_base != bv->id_base)
@@ -101,6 +103,8 @@ int check_refiner_rows(const vaqhip_bitvec *bv, const RefinerView &rv) {
                 (long long)bv->N, (long long)bv->id_base, (long long)rv.N, (long long)rv.id_base);
   return VAQHIP_OK;
 }
+
+namespace {
 
 // what a rerank call must hold before any device work
 int check_rerank(const vaqhip_bitvec *bv, const RefinerView &rv, int k, int factor) {
@@ -353,6 +357,13 @@ int vaqhip_bitvec_set_clusters(vaqhip_bitvec *bv, const float *centroids, int T,
   if (D < 1 || D > vaq::BITVEC_CLUSTERS_MAX_DIM)
     return fail(VAQHIP_EINVAL, "D=%d outside 1..%d (the refiner's row limit)", D, vaq::BITVEC_CLUSTERS_MAX_DIM);
   ENTRY(bv);
+  return bitvec_set_clusters_locked(bv, centroids, T, D, clust_idx);
+}
+
+}  // extern "C"
+
+// the body of vaqhip_bitvec_set_clusters behind its refusals of T and D (vaqhip_bitvec.h)
+int vaqhost::bitvec_set_clusters_locked(vaqhip_bitvec *bv, const float *centroids, int T, int D, const int32_t *clust_idx) {
   const int64_t N = bv->N, n_pad = vaq::fast_pad_rows(N);
   if (N > 0 && !clust_idx) return fail(VAQHIP_EINVAL, "null pointer");
   // a stable counting sort of the rows by cluster: start[c] is the first image row of cluster c, member[g] the row
@@ -388,6 +399,8 @@ int vaqhip_bitvec_set_clusters(vaqhip_bitvec *bv, const float *centroids, int T,
   cl.set = true;
   return VAQHIP_OK;
 }
+
+extern "C" {
 
 int64_t vaqhip_bitvec_size(vaqhip_bitvec *bv) {
   if (!bv) return fail(VAQHIP_EINVAL, "bitvec engine is null");

@@ -43,4 +43,13 @@ struct vaqhip_bitvec : vaqhost::HandleCore {
   BitvecEncoder enc;
   BitvecClusters cl;
 };
+
+// What vaqhip_cluster_index.cpp shares with vaqhip_bitvec.cpp, which defines both.  The caller holds bv->mu with the
+// engine's device current (ENTRY).
+namespace vaqhost __attribute__((visibility("hidden"))) {
+// the refiner describes the engine's rows, on the engine's device; rv is read under the refiner's lock
+int check_refiner_rows(const vaqhip_bitvec *bv, const RefinerView &rv);
+// vaqhip_bitvec_set_clusters behind its refusals of T and D: the counting sort, the centres, the cluster-major image
+int bitvec_set_clusters_locked(vaqhip_bitvec *bv, const float *centroids, int T, int D, const int32_t *clust_idx);
+}  // namespace vaqhost
 #endif

@@ -149,5 +149,10 @@ struct RefinerView {
 };
 std::mutex &refiner_mutex(vaqhip_refiner *r);
 RefinerView refiner_view(const vaqhip_refiner *r);
+// What a call made ON the refiner from another host file takes (vaqhip_cluster_index.cpp): the handle core for ENTRY
+// and WS_SCOPE, and the staging of its host forms.
+struct HandleCore;
+HandleCore *refiner_core(vaqhip_refiner *r);
+StagingBufs &refiner_staging(vaqhip_refiner *r);
 }  // namespace vaqhost
 #endif

@@ -28,6 +28,8 @@ struct vaqhip_refiner : HandleCore {
 namespace vaqhost {
 std::mutex &refiner_mutex(vaqhip_refiner *r) { return r->mu; }
 RefinerView refiner_view(const vaqhip_refiner *r) { return RefinerView{r->rows.rows(), r->N, r->id_base, r->device, r->D}; }
+HandleCore *refiner_core(vaqhip_refiner *r) { return r; }
+StagingBufs &refiner_staging(vaqhip_refiner *r) { return r->w; }
 }  // namespace vaqhost
 
 namespace {

@@ -6,6 +6,7 @@ include/vaqhip.h.  This module only gathers the names; the code is one module pe
   fits.py     fit_codebooks*, lut_fit_quantiles_multi*, train_rotation, train, their timing calls
   merge.py    merge_topk_device, merge_topk_packed_device, merge_fast_device
   bitvec.py   VaqBitVec, QueryMethod (the Hamming queries of BitVecEngine and its encoders), bitvec_fit_thresholds*
+  clusters.py cluster_index, cluster_index_u8 (the cluster of every raw row, for VaqBitVec.set_clusters)
   _adapt.py   what they share (pointers, row checks, the output pair and stream of a device call, handle lifetime)
 
 All compute goes through libvaqhip.so; nothing here has a NumPy fallback.
@@ -13,6 +14,7 @@ All compute goes through libvaqhip.so; nothing here has a NumPy fallback.
 from . import _lib  # noqa: F401
 from ._adapt import _ptr, _same, _u8_rows, _u8_rows_device, _wref  # noqa: F401
 from .bitvec import QueryMethod, VaqBitVec, bitvec_fit_thresholds, bitvec_fit_thresholds_u8  # noqa: F401
+from .clusters import cluster_index, cluster_index_u8  # noqa: F401
 from .fast import VaqHipFast  # noqa: F401
 from .fits import fit_codebooks_hier, fit_codebooks_hier_u8, last_fit_codebooks_hier_timing  # noqa: F401
 from .fits import fit_codebooks_bin, fit_codebooks_bin_u8, last_fit_codebooks_bin_timing, fit_codebooks_bin_sums  # noqa: F401

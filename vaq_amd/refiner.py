@@ -191,6 +191,32 @@ class VaqRefiner(_RefinerBase):
             return self._set_rows_device("set_rows_u8_device", XTrain, "uint8", id_base)
         super().set_rows_u8(XTrain, id_base)
 
+    def size(self) -> int:
+        """Rows held."""
+        return int(self._call("size"))
+
+    def cluster_index(self, centroids, return_dist: bool = False):
+        """cluster_index() over the rows held, float or byte, read where they are (vaqhip_refiner_cluster_index): int32
+        [n], entry i the cluster of row i; with return_dist also the squared distances float32 [n]."""
+        from .clusters import _centres, _outputs
+        cen = _centres(centroids)
+        if cen.shape[1] != self.D:
+            raise _lib.VaqHipError(-1, f"centroids {cen.shape} are not T x {self.D}")
+        idx, dist = _outputs(self.size(), return_dist)
+        self._call("cluster_index", _ptr(cen), cen.shape[0], _ptr(idx), _ptr(dist) if return_dist else None)
+        return (idx, dist) if return_dist else idx
+
+    def cluster_index_device(self, d_centroids, return_dist: bool = False):
+        """cluster_index() with the centres and the answer torch CUDA tensors on the refiner's device, enqueued on torch's
+        current stream, no synchronisation."""
+        import torch
+        from .clusters import _centres_device, _outputs_device
+        cen = _centres_device(d_centroids, torch.device("cuda", self.device), self.D)
+        idx, dist = _outputs_device(self.size(), return_dist, cen.device)
+        self._call("cluster_index_device", _dptr(cen), cen.shape[0], _dptr(idx), _dptr(dist) if return_dist else None,
+                   _stream(cen))
+        return (idx, dist) if return_dist else idx
+
     def train_moment(self):
         """The second moment of the sampled resident rows (vaqhip_refiner_train_moment): (float64 D x D, its float32
         rounding)."""
