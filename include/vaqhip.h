@@ -1472,8 +1472,8 @@ int vaqhip_last_timing(vaqhip_index *ix, vaqhip_timing *out);
  * The host forms are synchronous; the _device forms take pointers on the engine's GPU, enqueue on `stream` and do not
  * synchronise once the workspaces have their size.  Calls on one engine are serialised.  Errors leave their text in
  * vaqhip_last_error(), as the index's and the refiner's do.  Not provided: the other three methods, earlyAbandonRank,
- * the filtering variants, the naive variants other than queryNaiveWithClusterInfo (the exact cluster form below), a
- * multi-device form.  The cluster forms and the encoders follow the queries below. */
+ * the filtering variants, the naive variants other than queryNaiveWithClusterInfo and queryNaiveTriangleInequality (the
+ * exact cluster form and the triangle-inequality form below), a multi-device form.  The cluster forms and the encoders follow the queries below. */
 typedef struct vaqhip_bitvec vaqhip_bitvec;
 #define VAQHIP_BITVEC_HEAP                0  /* BitVecEngine::QueryMethod (BitVecEngine.hpp:82-84) */
 #define VAQHIP_BITVEC_SORT                1
@@ -1553,8 +1553,9 @@ int vaqhip_bitvec_query_rerank_clusters_device(vaqhip_bitvec *bv, vaqhip_refiner
  *               (VAQHIP_EINVAL), holding the engine's n rows from its id_base (VAQHIP_ESTATE), its D the centres'
  *               (VAQHIP_EINVAL); atleast_cluster in 1..T (VAQHIP_EINVAL); VAQHIP_ESTATE without set_clusters; k, nq and
  *               the method as query refuses them (only VAQHIP_BITVEC_SORT; the other three VAQHIP_EUNSUPPORTED).
- * "dist_chunk_bytes" bounds the visit lists of a chunk of queries, as for the cluster forms.  Not provided: queryNaive,
- * queryNaiveTriangleInequality, the disk-resident and parallel variants. */
+ * "dist_chunk_bytes" bounds the visit lists of a chunk of queries, as for the cluster forms.  Not provided: queryNaive
+ * (VaqRefiner's exhaustive search and the triangle-inequality form below have its answer), the disk-resident and parallel
+ * variants. */
 int vaqhip_bitvec_query_naive_clusters(vaqhip_bitvec *bv, vaqhip_refiner *r, const float *ori_queries, int nq, int k,
                                        int method, int atleast_cluster, int32_t *labels_out, float *distances_out);
 int vaqhip_bitvec_query_naive_clusters_device(vaqhip_bitvec *bv, vaqhip_refiner *r, const float *d_ori_queries, int nq, int k,
@@ -1584,8 +1585,8 @@ int vaqhip_bitvec_query_naive_clusters_device(vaqhip_bitvec *bv, vaqhip_refiner 
  *   limits      1 <= T <= 4096, 1 <= D <= 8176, 0 <= n < 2^31, null pointers: VAQHIP_EINVAL, before any device work.
  *               n == 0 succeeds and writes nothing.
  * The host forms are synchronous.  The _device forms take pointers on the rows' GPU, enqueue one kernel on `stream` and
- * neither allocate nor synchronise.  Not provided: the centres themselves (k-means), computeTriangleInequalityClusters,
- * a multi-device form. */
+ * neither allocate nor synchronise.  Not provided: the centres themselves (k-means), a multi-device form.
+ * computeTriangleInequalityClusters is vaqhip_bitvec_set_ti_clusters_from_refiner below. */
 /* rows held (what clust_idx_out must have room for), or a negative error code */
 int64_t vaqhip_refiner_size(vaqhip_refiner *r);
 int vaqhip_refiner_cluster_index(vaqhip_refiner *r, const float *centroids, int T, int32_t *clust_idx_out, float *dist_out);
@@ -1600,6 +1601,59 @@ int vaqhip_cluster_index_device(int device_id, const float *d_X, int64_t n, int 
 int vaqhip_cluster_index_u8_device(int device_id, const uint8_t *d_X, int64_t n, int D, const float *d_centroids, int T,
                                    int32_t *d_clust_idx_out, float *d_dist_out, void *stream);
 int vaqhip_bitvec_set_clusters_from_refiner(vaqhip_bitvec *bv, vaqhip_refiner *r, const float *centroids, int T, int D);
+
+/* ---- Hamming engine: the triangle-inequality form (BitVecEngine::queryNaiveTriangleInequality) -------------------------
+ * An exact nearest-neighbour search over the refiner's raw rows that never loads the rows a centre distance proves out of
+ * reach (BitVecEngine::computeTriangleInequalityClusters, BitVecEngine.hpp:1036-1088; ::queryNaiveTriangleInequality,
+ * BitVecEngine.cpp:722-873, QueryMethod::Heap).  No bit row is read.
+ *   build       set_ti_clusters_from_refiner: every row of the refiner gets its centre and the squared distance by the
+ *               cluster index's rule above, unchanged; xcc[row] = sqrtf(that distance).  The rows are grouped cluster
+ *               after cluster, inside a cluster the farthest from its centre first (xcc descending, equal xcc by
+ *               ascending row), by a stable radix sort on the device.  The engine keeps the group starts, the members,
+ *               their xcc and the centres; the raw rows are NOT copied or regrouped, the query reads them in place.
+ *               Two deviations, neither of which can change an answer (any assignment with a true xcc gives a valid
+ *               bound): the reference compares square roots when it assigns; and it gives a row with no finite distance
+ *               to centre 0 -- here such a row (index -1) is VAQHIP_EINVAL, the first such row named, the state untouched.
+ *               Limits and refusals are set_clusters_from_refiner's (1 <= T <= 4096, 1 <= D <= 8176, the refiner's
+ *               device, rows, id_base and D), all before any device work.  The state is separate from set_clusters'
+ *               (whose members ascend by row): both may exist at once.  Whatever drops the cluster state (a set or an
+ *               append of rows) drops this one too.
+ *   query       the distance of row i is sqrtf(euclideanDistNoSQRT(query, row i)): one float accumulator from 0.0f in
+ *               dimension order, distance += (a - b) * (a - b), nothing fused, a byte widened where it is loaded.  The
+ *               answer is the k smallest of ALL n rows by (distance, row): equal distances go to the smaller label.
+ *               labels_out int32 [nq][k] = id_base + row, distances_out float [nq][k] the square roots, as the reference
+ *               returns them; slots past min(k, n) are -1 / FLT_MAX.  The answer does not depend on the centres, the
+ *               assignment, the visiting order or the launch shape: pruning only skips rows that cannot enter.  A row is
+ *               skipped when |qcc - xcc| - (D + 8) 2^-23 (qcc + xcc) exceeds the present k-th best distance (qcc: the
+ *               query's distance to the row's centre); the slack covers the rounding of the three float distances
+ *               (DESIGN.md 4h).  Against the reference's Heap form: the same distances, except where its unslacked
+ *               `bsfK <= qToCC - dToCC` decides a 1-ulp case against a true neighbour, or where equal distances meet its
+ *               heap order.
+ *   method      VAQHIP_BITVEC_HEAP.  VAQHIP_BITVEC_SORT is VAQHIP_EUNSUPPORTED: the reference's insertionSort
+ *               (BitVecEngine.cpp:810-822) never compares against the last element while it fills, so its list is not
+ *               sorted and its bsfK is not the k-th best; that is not reproduced.  HEAP_EARLY_ABANDON (an empty branch in
+ *               the reference) and SORT_EARLY_ABANDON (not handled there) are VAQHIP_EUNSUPPORTED.  Any other value
+ *               VAQHIP_EINVAL.
+ *   evaluated   evaluated_out int64 [nq], may be NULL: the rows of the walk that were dealt to a lane (loaded and
+ *               summed); n minus it is what the reference prints as "total pruned".  Deterministic: one workgroup walks
+ *               one query in a fixed order.
+ *   refusals    before any device work: null engine, refiner or arrays, nq < 0, k < 1 (VAQHIP_EINVAL); k > VAQHIP_MAX_K
+ *               (VAQHIP_EUNSUPPORTED); VAQHIP_ESTATE before set_ti_clusters_from_refiner; the refiner as
+ *               query_naive_clusters requires it.  nq == 0 succeeds and writes nothing.
+ *   options     "dist_chunk_bytes" bounds the plan of a chunk of queries (8 T bytes a query).  "ti_refresh" (default 1,
+ *               1 .. 2048): the admissions since the last compaction of the candidate pool that make the walk compact
+ *               it again, which tightens the threshold.  It exists for tools/bench_bitvec_naive_ti.py, which times the
+ *               policies against each other; the answer does not depend on it and the default is the fastest measured.
+ * Values that are not finite, and values whose squares overflow or underflow, are outside the guarantee; the call stays
+ * inside its arrays.  The host form is synchronous; the _device form takes pointers on the engine's GPU, enqueues on
+ * `stream` and does not synchronise once the workspaces have their size.  Not provided: early abandon inside a row,
+ * several workgroups per query, a regrouped copy of the raw rows, a multi-device form. */
+int vaqhip_bitvec_set_ti_clusters_from_refiner(vaqhip_bitvec *bv, vaqhip_refiner *r, const float *centroids, int T, int D);
+int vaqhip_bitvec_query_naive_ti(vaqhip_bitvec *bv, vaqhip_refiner *r, const float *ori_queries, int nq, int k, int method,
+                                 int32_t *labels_out, float *distances_out, int64_t *evaluated_out);
+int vaqhip_bitvec_query_naive_ti_device(vaqhip_bitvec *bv, vaqhip_refiner *r, const float *d_ori_queries, int nq, int k,
+                                        int method, int32_t *d_labels_out, float *d_distances_out, int64_t *d_evaluated_out,
+                                        void *stream);
 
 /* ---- Hamming engine: the encoders (BitVecEngine::binaryEncodingSimple and ::binaryEncoding) on the device ------------
  * Raw rows (float or byte; host, device or resident in a refiner) -> bit rows, with no projected matrix written.  Both

@@ -1083,6 +1083,40 @@ public:
                                                                        int method = QueryMethod::Sort, int atleastCluster = 1) {
     return queryNaiveWithClusterInfo(FlatRows(oriQueries), k, method, atleastCluster);
   }
+  // BitVecEngine::computeTriangleInequalityClusters on the device: loadOriginal's rows assigned to loadCentroids' centres
+  // and grouped cluster after cluster, the farthest from its centre first (vaqhip_bitvec_set_ti_clusters_from_refiner).
+  // The reference's arguments (the cluster indices and the dataset) are not taken: the device makes and keeps them.
+  void computeTriangleInequalityClusters() {
+    const FlatRows c(centresForOriginal());
+    if (!bv_) throw Error(VAQHIP_ESTATE, "vaqhip: computeTriangleInequalityClusters before loadBitV");
+    check(vaqhip_bitvec_set_ti_clusters_from_refiner(bv_, ori_, c.data(), (int)c.rows(), (int)c.cols()));
+  }
+  // BitVecEngine::queryNaiveTriangleInequality: the k nearest of all rows by (Euclidean distance, row), exact;
+  // min(k, rows) pairs per query, the distances the square roots; only QueryMethod::Heap.  evaluated (may be null) gets
+  // the rows each query loaded: the rows minus it is the reference's "total pruned".
+  template <class Mat>
+  std::vector<std::vector<IdxDistPairFloat>> queryNaiveTriangleInequality(const Mat &oriQueries, const int k,
+                                                                          int method = QueryMethod::Heap,
+                                                                          std::vector<int64_t> *evaluated = nullptr) {
+    if (!ori_ || !bv_) throw Error(VAQHIP_ESTATE, "vaqhip: queryNaiveTriangleInequality before loadOriginal and loadBitV");
+    const int nq = (int)oriQueries.rows();
+    checkOriQueries(oriQueries, nq, oriDim_);  // (whether the TI state is there and current is the engine's to say)
+    std::vector<int> lab((size_t)nq * k);
+    std::vector<float> dis((size_t)nq * k);
+    if (evaluated) evaluated->assign((size_t)nq, 0);
+    check(vaqhip_bitvec_query_naive_ti(bv_, ori_, oriQueries.data(), nq, k, method, lab.data(), dis.data(),
+                                       evaluated ? evaluated->data() : nullptr));
+    std::vector<std::vector<IdxDistPairFloat>> answers(nq);
+    for (int i = 0; i < nq; i++)
+      for (int j = 0; j < k && lab[(size_t)i * k + j] >= 0; j++)
+        answers[i].push_back({lab[(size_t)i * k + j], dis[(size_t)i * k + j]});
+    return answers;
+  }
+  std::vector<std::vector<IdxDistPairFloat>> queryNaiveTriangleInequality(const Matrixf &oriQueries, const int k,
+                                                                          int method = QueryMethod::Heap,
+                                                                          std::vector<int64_t> *evaluated = nullptr) {
+    return queryNaiveTriangleInequality(FlatRows(oriQueries), k, method, evaluated);
+  }
   vaqhip_bitvec *bitvecHandle() const { return bv_; }
   // Several devices (a device named several times: logical shards on that GPU): binaryEncodingLUT then fits over
   // them (vaqhip_multi_lut_fit_quantiles), builds a VAQHIP_SUM_SEQUENTIAL multi index, gives it Q and encodes across

@@ -83,6 +83,7 @@ SYMBOLS = [
     "vaqhip_bitvec_query_naive_clusters", "vaqhip_bitvec_query_naive_clusters_device",
     "vaqhip_refiner_size", "vaqhip_refiner_cluster_index", "vaqhip_refiner_cluster_index_device", "vaqhip_cluster_index", "vaqhip_cluster_index_u8",
     "vaqhip_cluster_index_device", "vaqhip_cluster_index_u8_device", "vaqhip_bitvec_set_clusters_from_refiner",
+    "vaqhip_bitvec_set_ti_clusters_from_refiner", "vaqhip_bitvec_query_naive_ti", "vaqhip_bitvec_query_naive_ti_device",
 ]
 MAX_DEVICES = 16
 
@@ -364,6 +365,9 @@ def load():
         getattr(L, "vaqhip_cluster_index" + u8).argtypes = [i32, vp, i64, i32, vp, i32, vp, vp]
         getattr(L, "vaqhip_cluster_index" + u8 + "_device").argtypes = [i32, vp, i64, i32, vp, i32, vp, vp, vp]
     L.vaqhip_bitvec_set_clusters_from_refiner.argtypes = [vp, vp, vp, i32, i32]
+    L.vaqhip_bitvec_set_ti_clusters_from_refiner.argtypes = [vp, vp, vp, i32, i32]
+    L.vaqhip_bitvec_query_naive_ti.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
+    L.vaqhip_bitvec_query_naive_ti_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
     L.vaqhip_index_info.argtypes = [vp, C.POINTER(Info)]
     L.vaqhip_set_option.argtypes = [vp, C.c_char_p, i64]
     L.vaqhip_last_timing.argtypes = [vp, C.POINTER(Timing)]

@@ -11,7 +11,8 @@ from ._adapt import _Handle, _dptr, _eig_f32, _f32_rows, _out_pair, _ptr, _strea
 
 
 class QueryMethod:
-    """BitVecEngine::QueryMethod (BitVecEngine.hpp:82-84).  Only Sort is provided (include/vaqhip.h says why)."""
+    """BitVecEngine::QueryMethod (BitVecEngine.hpp:82-84).  Only Sort is provided, and for query_naive_ti only Heap
+    (include/vaqhip.h says why)."""
     Heap = 0
     Sort = 1
     HeapEarlyAbandon = 2
@@ -42,6 +43,11 @@ class VaqBitVec(_Handle):
         labels, dist = bv.query_clusters(Qbits, XTest, 100, atleast_cluster=8)
         ans = bv.query_rerank_clusters(Qbits, XTest, 100, 10, r, atleast_cluster=8)
         ans = bv.query_naive_clusters(XTest, 100, r, atleast_cluster=8)   # exact distances to every member visited
+
+    The exact search with triangle-inequality pruning (queryNaiveTriangleInequality) has the exhaustive answer:
+
+        bv.set_ti_clusters_from_refiner(centroids, r)         # computeTriangleInequalityClusters
+        labels, dist, evaluated = bv.query_naive_ti(XTest, 100, r, evaluated=True)
     """
     _destroy = "vaqhip_bitvec_destroy"
 
@@ -330,6 +336,49 @@ class VaqBitVec(_Handle):
         labels, dists = _out_pair(out, nq, k, oq.device)
         self._call("query_naive_clusters_device", refiner._h, _dptr(oq), nq, int(k), int(method), int(atleast_cluster),
                    _dptr(labels), _dptr(dists), _stream(oq))
+        return labels, dists
+
+    # ---- the triangle-inequality form: BitVecEngine::queryNaiveTriangleInequality ----
+    def set_ti_clusters_from_refiner(self, centroids, refiner) -> None:
+        """computeTriangleInequalityClusters on the device: every row of the refiner (float or byte) gets its nearest
+        centre as set_clusters_from_refiner gives it, and the rows are grouped cluster after cluster, the farthest from its
+        centre first.  The raw rows stay in the refiner.  Separate from set_clusters' state; dropped with it."""
+        cen = np.ascontiguousarray(centroids, dtype=np.float32)
+        if cen.ndim != 2 or cen.shape[0] < 1 or cen.shape[1] < 1:
+            raise _lib.VaqHipError(-1, f"centroids {cen.shape} are not T x D")
+        self._call("set_ti_clusters_from_refiner", refiner._h, _ptr(cen), cen.shape[0], cen.shape[1])
+
+    def query_naive_ti(self, ori_queries, k: int, refiner, method: int = QueryMethod.Heap, evaluated: bool = False):
+        """BitVecEngine::queryNaiveTriangleInequality: the k nearest of ALL rows by (Euclidean distance, label), exact; the
+        rows a centre distance proves out of reach are never loaded.  (labels int32 [nq][k], distances float32 [nq][k], the
+        square roots); slots past min(k, n) are -1 / FLT_MAX.  evaluated=True adds int64 [nq], the rows each query loaded.
+        Before set_ti_clusters_from_refiner, or once the rows have changed, the call is VAQHIP_ESTATE."""
+        XQ = _f32_rows(ori_queries, refiner.D, "oriQueries {shape} are not nq x {D}")
+        nq = XQ.shape[0]
+        lab = np.empty((nq, k), np.int32)
+        dis = np.empty((nq, k), np.float32)
+        ev = np.zeros(nq, np.int64) if evaluated else None
+        self._call("query_naive_ti", refiner._h, _ptr(XQ), nq, int(k), int(method), _ptr(lab), _ptr(dis),
+                   _ptr(ev) if evaluated else None)
+        return (lab, dis, ev) if evaluated else (lab, dis)
+
+    def query_naive_ti_device(self, d_ori_queries, k: int, refiner, method: int = QueryMethod.Heap, out=None,
+                              evaluated_out=None):
+        """query_naive_ti() on a float32 [nq][D] torch CUDA tensor, enqueued on torch's current stream, no
+        synchronisation.  evaluated_out: an int64 [nq] tensor on the same device, or None."""
+        import torch
+        D = refiner.D
+        oq = d_ori_queries.contiguous()
+        if not (oq.is_cuda and oq.device.index == self.device and oq.dtype == torch.float32 and oq.dim() == 2 and oq.shape[1] == D):
+            raise _lib.VaqHipError(-1, f"device oriQueries must be float32 nq x {D} on cuda:{self.device}")
+        nq = oq.shape[0]
+        ev = evaluated_out
+        if ev is not None and not (ev.is_cuda and ev.device == oq.device and ev.dtype == torch.int64 and ev.is_contiguous()
+                                   and tuple(ev.shape) == (nq,)):
+            raise _lib.VaqHipError(-1, f"evaluated_out must be a contiguous int64 [{nq}] tensor on the queries' device")
+        labels, dists = _out_pair(out, nq, k, oq.device)
+        self._call("query_naive_ti_device", refiner._h, _dptr(oq), nq, int(k), int(method), _dptr(labels), _dptr(dists),
+                   _dptr(ev) if ev is not None else None, _stream(oq))
         return labels, dists
 
 

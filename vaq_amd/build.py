@@ -37,6 +37,7 @@ SOURCES = [
     "vaq_bitvec.hip",
     "vaq_bitvec_clusters.hip",
     "vaq_bitvec_naive.hip",
+    "vaq_bitvec_ti.hip",
     "vaq_bitvec_encode.hip",
     "vaq_cluster_index.hip",
     # the single-index host
@@ -51,6 +52,7 @@ SOURCES = [
     "vaqhip_train.cpp",
     "vaqhip_refiner.cpp",
     "vaqhip_bitvec.cpp",
+    "vaqhip_bitvec_ti.cpp",
     "vaqhip_bitvec_encode.cpp",
     "vaqhip_cluster_index.cpp",
     # the multi-device host
@@ -66,10 +68,11 @@ SOURCES = [
     "vaqhip_rccl.cpp",
 ]
 # flags of single units: packed fp32 arithmetic is kept out of the encoder's FMA chains, of the centre distances and of
-# the exact cluster form's row distances, and of the cluster index's
+# the exact cluster form's and the triangle-inequality form's row distances, and of the cluster index's
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"vaq_bitvec_encode.hip": _NO_PACKED_FP32, "vaq_bitvec_clusters.hip": _NO_PACKED_FP32,
-              "vaq_bitvec_naive.hip": _NO_PACKED_FP32, "vaq_cluster_index.hip": _NO_PACKED_FP32}
+              "vaq_bitvec_naive.hip": _NO_PACKED_FP32, "vaq_bitvec_ti.hip": _NO_PACKED_FP32,
+              "vaq_cluster_index.hip": _NO_PACKED_FP32}
 OBJDIR = os.path.join(LIBDIR, "obj")
 # Experiment builds: VAQ_VARIANT=name compiles (with VAQ_EXTRA_FLAGS) into vaq_amd/lib/variants/name/
 # and VAQHIP_LIB=<path> makes the package load that library instead (tools/ sweeps).

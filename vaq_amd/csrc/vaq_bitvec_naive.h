@@ -13,7 +13,7 @@
 
 namespace vaq {
 
-constexpr int BITVEC_EXACT_DC = 32;      // dimensions of a chunk: a tile of 256 rows is staged in LDS DC floats at a time
+// (the chunk of a tile, BITVEC_EXACT_DC dimensions, is vaq_bitvec_tile.h's)
 constexpr int BITVEC_EXACT_POOL = 2048;  // (key, row) slots of the selection pool: VAQHIP_MAX_K + a tile, a power of two
 
 // Per query the candidates are the members of the first plan.visit clusters of its visit list, cluster after cluster,

@@ -52,7 +52,7 @@ int set_rows_any(vaqhip_bitvec *bv, const uint64_t *X, bool on_device, int64_t n
     return fail(VAQHIP_ERANGE, "labels are 32-bit ints: id_base+n = %lld", (long long)(id_base + n));
   ENTRY(bv);
   bv->N = 0;  // (a failure below leaves no rows, not rows half replaced)
-  bv->cl.set = false;
+  bv->drop_clusters();
   HIP_TRY(bv->rows.reserve(vaq::fast_pad_rows(n), RowStore::DROP, bv->W));
   HIP_TRY(hipDeviceSynchronize());  // (a query enqueued on any stream may still read the old rows)
   if (int rc = write_rows(bv, X, 0, n, on_device, static_cast<hipStream_t>(stream))) return rc;
@@ -342,7 +342,7 @@ int vaqhip_bitvec_add_rows(vaqhip_bitvec *bv, const uint64_t *rows, int64_t n_ne
   ENTRY(bv);
   if (bv->N + n_new > 0x7fffffffLL - 1 || bv->id_base + bv->N + n_new > 0x7fffffffLL)
     return fail(VAQHIP_ERANGE, "labels are 32-bit ints: id_base+n = %lld", (long long)(bv->id_base + bv->N + n_new));
-  bv->cl.set = false;  // (the cluster state describes the rows as they were)
+  bv->drop_clusters();  // (the cluster state describes the rows as they were)
   HIP_TRY(bv->rows.reserve(vaq::fast_pad_rows(bv->N + n_new), bv->N, bv->W));
   // (rows past N are the padding: a query in flight may read them, but no answer depends on what they hold)
   if (int rc = write_rows(bv, rows, bv->N, n_new, false, nullptr)) return rc;
@@ -410,10 +410,14 @@ int64_t vaqhip_bitvec_size(vaqhip_bitvec *bv) {
 
 int vaqhip_bitvec_set_option(vaqhip_bitvec *bv, const char *key, int64_t value) {
   if (!bv || !key) return fail(VAQHIP_EINVAL, "null pointer");
-  if (std::strcmp(key, "dist_chunk_bytes") != 0) return fail(VAQHIP_EINVAL, "unknown option '%s'", key);
+  const bool refresh = std::strcmp(key, "ti_refresh") == 0;
+  if (!refresh && std::strcmp(key, "dist_chunk_bytes") != 0) return fail(VAQHIP_EINVAL, "unknown option '%s'", key);
+  if (refresh && (value < 1 || value > vaq::BITVEC_TI_POOL))
+    return fail(VAQHIP_EINVAL, "ti_refresh=%lld: 1 .. %d", (long long)value, vaq::BITVEC_TI_POOL);
   if (value < 1 || value > ((int64_t)1 << 40)) return fail(VAQHIP_EINVAL, "dist_chunk_bytes=%lld: 1 .. 2^40", (long long)value);
   std::lock_guard<std::mutex> lk(bv->mu);
-  bv->dist_chunk_bytes = value;
+  if (refresh) bv->ti_refresh = (int)value;
+  else bv->dist_chunk_bytes = value;
   return VAQHIP_OK;
 }
 

@@ -136,7 +136,7 @@ int finish_store(vaqhip_bitvec *bv, int64_t end) {
 // replaces the engine's rows by the encoded X (host rows, or the rows of a device on the engine's GPU)
 int set_encoded(vaqhip_bitvec *bv, vaq::RowsRef X, bool on_device, int64_t n, int64_t id_base) {
   bv->N = 0;  // (a failure below leaves no rows, not rows half replaced)
-  bv->cl.set = false;
+  bv->drop_clusters();
   HIP_TRY(bv->rows.reserve(vaq::fast_pad_rows(n), RowStore::DROP, bv->W));
   HIP_TRY(hipDeviceSynchronize());  // (a query enqueued on any stream may still read the old rows)
   if (n > 0 && on_device)
@@ -163,7 +163,7 @@ int add_rows_entry(vaqhip_bitvec *bv, vaq::RowsRef X, int64_t n_new) {
   if (int rc = check_encoder(bv)) return rc;
   if (n_new == 0) return VAQHIP_OK;
   if (int rc = check_labels(bv->N + n_new, bv->id_base)) return rc;
-  bv->cl.set = false;  // (the cluster state describes the rows as they were)
+  bv->drop_clusters();  // (the cluster state describes the rows as they were)
   HIP_TRY(bv->rows.reserve(vaq::fast_pad_rows(bv->N + n_new), bv->N, bv->W));
   // (rows past N are the padding: a query in flight may read them, but no answer depends on what they hold)
   if (int rc = encode_host_rows(bv, X, n_new, bv->rows.buf.as<uint64_t>() + (size_t)bv->N * bv->W, nullptr)) return rc;

@@ -12,15 +12,6 @@ namespace {
 
 constexpr int64_t HOST_CHUNK_ROWS = (int64_t)1 << 20;  // rows per staged piece of the raw host forms
 
-// set_clusters' own limits, before any device work
-int check_centres(const float *centroids, int T, int D) {
-  if (!centroids) return fail(VAQHIP_EINVAL, "null pointer");
-  if (T < 1 || T > vaq::BITVEC_CLUSTERS_MAX) return fail(VAQHIP_EINVAL, "T=%d centres outside 1..%d", T, vaq::BITVEC_CLUSTERS_MAX);
-  if (D < 1 || D > vaq::BITVEC_CLUSTERS_MAX_DIM)
-    return fail(VAQHIP_EINVAL, "D=%d outside 1..%d (the refiner's row limit)", D, vaq::BITVEC_CLUSTERS_MAX_DIM);
-  return VAQHIP_OK;
-}
-
 int check_rows(const void *X, int64_t n, const void *idx_out) {
   if (n < 0 || n > 0x7fffffffLL) return fail(VAQHIP_EINVAL, "n=%lld outside 0..2^31 - 1 (a cluster index is one int32 a row)", (long long)n);
   if (n > 0 && (!X || !idx_out)) return fail(VAQHIP_EINVAL, "null pointer");
@@ -52,7 +43,7 @@ int refiner_entry(vaqhip_refiner *r, const float *centroids, int T, int32_t *idx
   HandleCore *h = refiner_core(r);
   ENTRY(h);
   const RefinerView rv = refiner_view(r);
-  if (int rc = check_centres(centroids, T, rv.D)) return rc;
+  if (int rc = bitvec_check_centres(centroids, T, rv.D)) return rc;
   if (rv.N > 0 && !idx_out) return fail(VAQHIP_EINVAL, "null pointer");
   if (rv.N == 0) return VAQHIP_OK;
   if (!on_device) return assign_to_host(h, refiner_staging(r), rv.rows, rv.N, rv.D, centroids, T, idx_out, dist_out);
@@ -63,7 +54,7 @@ int refiner_entry(vaqhip_refiner *r, const float *centroids, int T, int32_t *idx
 // the four entries over rows that are in no refiner
 int raw_entry(int device_id, vaq::RowsRef X, int64_t n, int D, const float *centroids, int T, int32_t *idx_out, float *dist_out,
               bool on_device, hipStream_t st) {
-  if (int rc = check_centres(centroids, T, D)) return rc;
+  if (int rc = bitvec_check_centres(centroids, T, D)) return rc;
   if (int rc = check_rows(X.p, n, idx_out)) return rc;
   if (n == 0) return VAQHIP_OK;
   DeviceGuard g(device_id);
@@ -136,7 +127,7 @@ int vaqhip_cluster_index_u8_device(int device_id, const uint8_t *d_X, int64_t n,
 int vaqhip_bitvec_set_clusters_from_refiner(vaqhip_bitvec *bv, vaqhip_refiner *r, const float *centroids, int T, int D) {
   if (!bv) return fail(VAQHIP_EINVAL, "bitvec engine is null");
   if (!r) return fail(VAQHIP_EINVAL, "refiner is null");
-  if (int rc = check_centres(centroids, T, D)) return rc;
+  if (int rc = bitvec_check_centres(centroids, T, D)) return rc;
   ENTRY(bv);
   std::lock_guard<std::mutex> rlk(refiner_mutex(r));
   const RefinerView rv = refiner_view(r);
