@@ -1585,7 +1585,8 @@ int vaqhip_bitvec_query_naive_clusters_device(vaqhip_bitvec *bv, vaqhip_refiner 
  *   limits      1 <= T <= 4096, 1 <= D <= 8176, 0 <= n < 2^31, null pointers: VAQHIP_EINVAL, before any device work.
  *               n == 0 succeeds and writes nothing.
  * The host forms are synchronous.  The _device forms take pointers on the rows' GPU, enqueue one kernel on `stream` and
- * neither allocate nor synchronise.  Not provided: the centres themselves (k-means), a multi-device form.
+ * neither allocate nor synchronise.  The centres themselves: vaqhip_refiner_fit_centres below.  Not provided: a
+ * multi-device form.
  * computeTriangleInequalityClusters is vaqhip_bitvec_set_ti_clusters_from_refiner below. */
 /* rows held (what clust_idx_out must have room for), or a negative error code */
 int64_t vaqhip_refiner_size(vaqhip_refiner *r);
@@ -1601,6 +1602,44 @@ int vaqhip_cluster_index_device(int device_id, const float *d_X, int64_t n, int 
 int vaqhip_cluster_index_u8_device(int device_id, const uint8_t *d_X, int64_t n, int D, const float *d_centroids, int T,
                                    int32_t *d_clust_idx_out, float *d_dist_out, void *stream);
 int vaqhip_bitvec_set_clusters_from_refiner(vaqhip_bitvec *bv, vaqhip_refiner *r, const float *centroids, int T, int D);
+
+/* ---- Fitting the centres: KMeans::fit (KMeans.hpp:42-107) over the refiner's resident rows --------------------------
+ * The centres that set_clusters, set_clusters_from_refiner and set_ti_clusters_from_refiner take, made on the device from
+ * all n rows, float or byte, read in place.  Parity-unpinned like the cluster index: the checker is a float32 restatement
+ * of the reference's loops (tests/kmeans_fit_ref.py); the device equals it bit for bit.
+ *   seeds       seed_rows int32 [T], the caller's: means[c] = row seed_rows[c], a byte widened (the reference draws
+ *               X[rand() % nrows] behind srand(time(NULL))).  Duplicates are allowed.  A value outside [0, n) is VAQHIP_EINVAL.
+ *   iteration   every row, in row order, joins the FIRST centre j (ascending, from (FLT_MAX, -1)) with dist < dist_min, where
+ *               dist = sqrtf(sum) and sum is the cluster index's: one float accumulator from 0.0f in dimension order,
+ *               nothing fused.  The root is kept: of two centres whose sums differ but whose roots are one float the first
+ *               wins.  new[c][d] = (the values of c's rows added in ascending row order into one accumulator from +0.0f) /
+ *               (float)count.  A centre with no rows becomes 0 / 0 = NaN, never compares equal again, and the fit then runs
+ *               to max_iter: the reference's behaviour, kept.  means[c] is replaced, whole, where new[c] == means[c] fails.
+ *               The fit ends when no centre was replaced or after max_iter iterations (the reference's default: 25).
+ *   outputs     centres_out float [T][D]; belongs_to_out int32 [n], the assignment of the last iteration executed -- as in
+ *               the reference, against the centres BEFORE that iteration's update; *iterations_out.
+ *   refusals    before any device work: T < 1, max_iter < 1, null pointers (VAQHIP_EINVAL); T > 4096 (VAQHIP_EUNSUPPORTED,
+ *               the cluster state's limit); a refiner without rows (VAQHIP_ESTATE).  A row that no centre wins (a NaN or an
+ *               overflowed distance to every centre; the reference indexes new_centroids[-1]) is VAQHIP_EINVAL naming the
+ *               first such row, as set_clusters_from_refiner refuses it.  No refusal writes an output.
+ *   limits      the seeds are the caller's (no RANDOM, no k-means++); a cluster that holds most of the rows is one serial
+ *               chain per dimension, which is the reference's order and is not split; KMeans::fitParallel, ::fastFit and a
+ *               multi-device form are not provided.
+ * Both forms are synchronous: the host reads two flags once per iteration (did a centre change, did a row fail) and
+ * nothing else until the end.  The _device form takes seed_rows, centres_out and belongs_to_out on the refiner's GPU
+ * (iterations_out on the host), enqueues on `stream`, synchronises it once per iteration and once at the end, and
+ * allocates its workspace per call. */
+int vaqhip_refiner_fit_centres(vaqhip_refiner *r, int T, const int32_t *seed_rows, int max_iter, float *centres_out,
+                               int32_t *belongs_to_out, int *iterations_out);
+int vaqhip_refiner_fit_centres_device(vaqhip_refiner *r, int T, const int32_t *d_seed_rows, int max_iter, float *d_centres_out,
+                                      int32_t *d_belongs_to_out, int *iterations_out, void *stream);
+typedef struct {
+  float assign_ms, group_ms, update_ms; /* device time of the three phases, summed over the iterations */
+  int iterations;
+  int64_t rows;
+  int centres, dims;
+} vaqhip_fit_centres_timing;
+int vaqhip_last_fit_centres_timing(vaqhip_fit_centres_timing *out); /* the calling thread's last fit */
 
 /* ---- Hamming engine: the triangle-inequality form (BitVecEngine::queryNaiveTriangleInequality) -------------------------
  * An exact nearest-neighbour search over the refiner's raw rows that never loads the rows a centre distance proves out of

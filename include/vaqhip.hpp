@@ -1000,6 +1000,22 @@ public:
     clusterIdx.assign((size_t)oriRows_, -1);
     check(vaqhip_refiner_cluster_index(ori_, c.data(), (int)c.rows(), clusterIdx.data(), nullptr));
   }
+  // KMeans(k, maxIter).fit(loadOriginal's rows) on the device, the centres starting as the rows seedRows (the reference
+  // draws them with rand(); vaqhip_refiner_fit_centres).  Returns the assignment of the last iteration and leaves the
+  // centres loaded as loadCentroids does: loadClusterInfoFromOriginal() or computeTriangleInequalityClusters() follow.
+  std::vector<int> fitCentroids(int k, const std::vector<int> &seedRows, int maxIter = 25, int *iterations = nullptr) {
+    if (!ori_) throw Error(VAQHIP_ESTATE, "vaqhip: fitCentroids before loadOriginal");
+    if ((int)seedRows.size() != k) throw Error(VAQHIP_EINVAL, "vaqhip: fitCentroids needs one seed row per centre");
+    std::vector<float> flat((size_t)std::max(k, 0) * oriDim_);
+    std::vector<int> belongsTo((size_t)oriRows_);
+    int iters = 0;
+    check(vaqhip_refiner_fit_centres(ori_, k, seedRows.data(), maxIter, flat.data(), belongsTo.data(), &iters));
+    Matrixf centres((size_t)k);
+    for (int c = 0; c < k; c++) centres[c].assign(flat.begin() + (size_t)c * oriDim_, flat.begin() + (size_t)(c + 1) * oriDim_);
+    loadCentroids(std::move(centres));
+    if (iterations) *iterations = iters;
+    return belongsTo;
+  }
   // computeClusterIndex and loadClusterInfo in one: the cluster state of the bit vectors from loadOriginal's rows and
   // loadCentroids' centres, the indices never visiting the caller (vaqhip_bitvec_set_clusters_from_refiner)
   void loadClusterInfoFromOriginal() {

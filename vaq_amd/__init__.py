@@ -12,6 +12,7 @@ Product surface:
                               raw rows (binaryEncodingSimple, binaryEncoding); vaq_amd.bitvec_fit_thresholds[_u8]
   vaq_amd.cluster_index       computeClusterIndex on the device: the cluster of every raw row (cluster_index_u8 from bytes;
                               VaqRefiner.cluster_index over resident rows; VaqBitVec.set_clusters_from_refiner)
+  VaqRefiner.fit_centres      KMeans::fit on the device over the resident rows: the centres the cluster forms start from
   vaq_amd.lut_fit_quantiles_multi  binaryEncodingLUT's quantile codebooks with the rows cut over several GPUs
   vaq_amd.lut_fit_quantiles_multi_u8  the same from byte rows (a bvecs dataset as its file holds it)
   vaq_amd.fit_codebooks       the subspace codebooks (KMeans::staticFitSampling per subspace) from raw rows

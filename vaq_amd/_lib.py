@@ -84,6 +84,7 @@ SYMBOLS = [
     "vaqhip_refiner_size", "vaqhip_refiner_cluster_index", "vaqhip_refiner_cluster_index_device", "vaqhip_cluster_index", "vaqhip_cluster_index_u8",
     "vaqhip_cluster_index_device", "vaqhip_cluster_index_u8_device", "vaqhip_bitvec_set_clusters_from_refiner",
     "vaqhip_bitvec_set_ti_clusters_from_refiner", "vaqhip_bitvec_query_naive_ti", "vaqhip_bitvec_query_naive_ti_device",
+    "vaqhip_refiner_fit_centres", "vaqhip_refiner_fit_centres_device", "vaqhip_last_fit_centres_timing",
 ]
 MAX_DEVICES = 16
 
@@ -133,6 +134,11 @@ class FitCodebooksTiming(C.Structure):
     _fields_ = [("total_ms", C.c_float), ("gather_ms", C.c_float), ("assign_ms", C.c_float),
                 ("accumulate_ms", C.c_float), ("update_ms", C.c_float), ("iterations", C.c_int),
                 ("subspaces", C.c_int), ("dims", C.c_int), ("sample_rows", C.c_int64), ("rows", C.c_int64)]
+
+
+class FitCentresTiming(C.Structure):
+    _fields_ = [("assign_ms", C.c_float), ("group_ms", C.c_float), ("update_ms", C.c_float), ("iterations", C.c_int),
+                ("rows", C.c_int64), ("centres", C.c_int), ("dims", C.c_int)]
 
 
 class FitCodebooksHierTiming(C.Structure):
@@ -368,6 +374,9 @@ def load():
     L.vaqhip_bitvec_set_ti_clusters_from_refiner.argtypes = [vp, vp, vp, i32, i32]
     L.vaqhip_bitvec_query_naive_ti.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp]
     L.vaqhip_bitvec_query_naive_ti_device.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp]
+    L.vaqhip_refiner_fit_centres.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    L.vaqhip_refiner_fit_centres_device.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp]
+    L.vaqhip_last_fit_centres_timing.argtypes = [C.POINTER(FitCentresTiming)]
     L.vaqhip_index_info.argtypes = [vp, C.POINTER(Info)]
     L.vaqhip_set_option.argtypes = [vp, C.c_char_p, i64]
     L.vaqhip_last_timing.argtypes = [vp, C.POINTER(Timing)]

@@ -40,6 +40,7 @@ SOURCES = [
     "vaq_bitvec_ti.hip",
     "vaq_bitvec_encode.hip",
     "vaq_cluster_index.hip",
+    "vaq_kmeans_fit.hip",
     # the single-index host
     "vaqhip_api.cpp",
     "vaqhip_plan.cpp",
@@ -55,6 +56,7 @@ SOURCES = [
     "vaqhip_bitvec_ti.cpp",
     "vaqhip_bitvec_encode.cpp",
     "vaqhip_cluster_index.cpp",
+    "vaqhip_kmeans_fit.cpp",
     # the multi-device host
     "vaqhip_multi.cpp",
     "vaqhip_multi_search.cpp",
@@ -68,11 +70,12 @@ SOURCES = [
     "vaqhip_rccl.cpp",
 ]
 # flags of single units: packed fp32 arithmetic is kept out of the encoder's FMA chains, of the centre distances and of
-# the exact cluster form's and the triangle-inequality form's row distances, and of the cluster index's
+# the exact cluster form's and the triangle-inequality form's row distances, of the cluster index's and of the centre
+# fit's sums
 _NO_PACKED_FP32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNIT_FLAGS = {"vaq_bitvec_encode.hip": _NO_PACKED_FP32, "vaq_bitvec_clusters.hip": _NO_PACKED_FP32,
               "vaq_bitvec_naive.hip": _NO_PACKED_FP32, "vaq_bitvec_ti.hip": _NO_PACKED_FP32,
-              "vaq_cluster_index.hip": _NO_PACKED_FP32}
+              "vaq_cluster_index.hip": _NO_PACKED_FP32, "vaq_kmeans_fit.hip": _NO_PACKED_FP32}
 OBJDIR = os.path.join(LIBDIR, "obj")
 # Experiment builds: VAQ_VARIANT=name compiles (with VAQ_EXTRA_FLAGS) into vaq_amd/lib/variants/name/
 # and VAQHIP_LIB=<path> makes the package load that library instead (tools/ sweeps).

@@ -26,5 +26,11 @@ constexpr int CLUSTER_INDEX_TC = 64;  // centres of a block: a lane keeps their 
 hipError_t launch_cluster_index(RowsRef rows, int64_t n, int D, const float *centroids, int T, int32_t *idx_out,
                                 float *dist_out, hipStream_t st);
 
+// The assign step of KMeans::fit (KMeans.hpp:67-77, vaq_kmeans_fit.h): the same kernel with dist = sqrtf(that sum)
+// before the `<`, so the first of two centres whose roots are one float wins although its sum is the larger.  dist_out
+// gets the root.
+hipError_t launch_cluster_index_root(RowsRef rows, int64_t n, int D, const float *centroids, int T, int32_t *idx_out,
+                                     float *dist_out, hipStream_t st);
+
 }  // namespace vaq
 #endif  // VAQ_CLUSTER_INDEX_H_

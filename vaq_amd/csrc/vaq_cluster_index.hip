@@ -113,7 +113,9 @@ __device__ __forceinline__ void ci_dimension(float x, const float *cen, float (&
   }
 }
 
-template <typename T, bool VEC>
+// ROOT (the k-means fit's assign, vaq_kmeans_fit.h): a finished sum becomes its square root before it meets the fold,
+// so two sums whose roots round to one float keep the earlier centre.  Nothing else differs.
+template <typename T, bool VEC, bool ROOT>
 __global__ void __launch_bounds__(CI_THREADS)
 cluster_index_kernel(const T *__restrict__ rows, int64_t n, int D, const float *__restrict__ centroids, int nT,
                      int32_t *__restrict__ idx_out, float *__restrict__ dist_out) {
@@ -154,6 +156,7 @@ cluster_index_kernel(const T *__restrict__ rows, int64_t n, int D, const float *
     // the fold, in centre order; a centre past T - 1 holds the sum against zeros and is left out
 #pragma unroll
     for (int i = 0; i < CI_TC; i++) {
+      if constexpr (ROOT) acc[i] = sqrtf(acc[i]);
       if (c0 + i < nT && acc[i] < nearest) {
         nearest = acc[i];
         nearest_c = c0 + i;
@@ -166,31 +169,42 @@ cluster_index_kernel(const T *__restrict__ rows, int64_t n, int D, const float *
   }
 }
 
-template <typename T>
+template <typename T, bool ROOT>
 hipError_t cluster_index_t(const void *rows, bool vec, int64_t n, int D, const float *centroids, int T_, int32_t *idx_out,
                            float *dist_out, hipStream_t st) {
   const dim3 grid((unsigned)((n + CI_THREADS - 1) / CI_THREADS));
   if (vec)
-    hipLaunchKernelGGL((cluster_index_kernel<T, true>), grid, dim3(CI_THREADS), 0, st, static_cast<const T *>(rows), n, D,
+    hipLaunchKernelGGL((cluster_index_kernel<T, true, ROOT>), grid, dim3(CI_THREADS), 0, st, static_cast<const T *>(rows), n, D,
                        centroids, T_, idx_out, dist_out);
   else
-    hipLaunchKernelGGL((cluster_index_kernel<T, false>), grid, dim3(CI_THREADS), 0, st, static_cast<const T *>(rows), n, D,
+    hipLaunchKernelGGL((cluster_index_kernel<T, false, ROOT>), grid, dim3(CI_THREADS), 0, st, static_cast<const T *>(rows), n, D,
                        centroids, T_, idx_out, dist_out);
   return hipGetLastError();
 }
 
-}  // namespace
-
-hipError_t launch_cluster_index(RowsRef rows, int64_t n, int D, const float *centroids, int T, int32_t *idx_out,
-                                float *dist_out, hipStream_t st) {
+template <bool ROOT>
+hipError_t cluster_index_any(RowsRef rows, int64_t n, int D, const float *centroids, int T, int32_t *idx_out, float *dist_out,
+                             hipStream_t st) {
   if (n == 0) return hipSuccess;
   if (D < 1 || D > BITVEC_CLUSTERS_MAX_DIM || T < 1 || T > BITVEC_CLUSTERS_MAX || n < 0 || n > 0x7fffffffLL ||
       (rows.elem != 4 && rows.elem != 1) || !rows.p || !centroids || !idx_out)
     return hipErrorInvalidValue;
   // whole aligned pieces of four elements: 16 bytes of floats, 4 of bytes
   const bool vec = D % 4 == 0 && reinterpret_cast<uintptr_t>(rows.p) % (size_t)(4 * rows.elem) == 0;
-  if (rows.elem == 1) return cluster_index_t<uint8_t>(rows.p, vec, n, D, centroids, T, idx_out, dist_out, st);
-  return cluster_index_t<float>(rows.p, vec, n, D, centroids, T, idx_out, dist_out, st);
+  if (rows.elem == 1) return cluster_index_t<uint8_t, ROOT>(rows.p, vec, n, D, centroids, T, idx_out, dist_out, st);
+  return cluster_index_t<float, ROOT>(rows.p, vec, n, D, centroids, T, idx_out, dist_out, st);
+}
+
+}  // namespace
+
+hipError_t launch_cluster_index(RowsRef rows, int64_t n, int D, const float *centroids, int T, int32_t *idx_out,
+                                float *dist_out, hipStream_t st) {
+  return cluster_index_any<false>(rows, n, D, centroids, T, idx_out, dist_out, st);
+}
+
+hipError_t launch_cluster_index_root(RowsRef rows, int64_t n, int D, const float *centroids, int T, int32_t *idx_out,
+                                     float *dist_out, hipStream_t st) {
+  return cluster_index_any<true>(rows, n, D, centroids, T, idx_out, dist_out, st);
 }
 
 }  // namespace vaq

@@ -217,6 +217,38 @@ class VaqRefiner(_RefinerBase):
                    _stream(cen))
         return (idx, dist) if return_dist else idx
 
+    def fit_centres(self, T: int, seed_rows, max_iter: int = 25):
+        """KMeans::fit over the rows held, float or byte, read where they are (vaqhip_refiner_fit_centres): the centres
+        start as the rows seed_rows (T row numbers, the caller's choice).  Returns (centres float32 [T][D], belongs_to
+        int32 [n] of the last iteration's assign step, iterations)."""
+        seeds = np.ascontiguousarray(seed_rows, dtype=np.int32)
+        if seeds.shape != (int(T),):
+            raise _lib.VaqHipError(-1, f"seed_rows {seeds.shape} are not {T} row numbers")
+        cen, idx, it = np.empty((int(T), self.D), np.float32), np.empty(self.size(), np.int32), C.c_int(0)
+        self._call("fit_centres", int(T), _ptr(seeds), int(max_iter), _ptr(cen), _ptr(idx), C.byref(it))
+        return cen, idx, it.value
+
+    def fit_centres_device(self, T: int, d_seed_rows, max_iter: int = 25):
+        """fit_centres() with the seeds (int32 [T]) and the answers torch CUDA tensors on the refiner's device, enqueued on
+        torch's current stream, which is synchronised once per iteration; iterations is a host int."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        seeds = d_seed_rows.contiguous()
+        if not (seeds.is_cuda and seeds.device == dev and seeds.dtype == torch.int32 and tuple(seeds.shape) == (int(T),)):
+            raise _lib.VaqHipError(-1, f"device seed_rows must be int32 [{T}] on {dev}")
+        cen = torch.empty((int(T), self.D), dtype=torch.float32, device=dev)
+        idx, it = torch.empty(self.size(), dtype=torch.int32, device=dev), C.c_int(0)
+        self._call("fit_centres_device", int(T), _dptr(seeds), int(max_iter), _dptr(cen), _dptr(idx), C.byref(it), _stream(cen))
+        return cen, idx, it.value
+
+    @staticmethod
+    def last_fit_centres_timing() -> dict:
+        """Figures of the calling thread's last fit_centres (vaqhip_last_fit_centres_timing): the device time of the assign,
+        group and update phases summed over its iterations."""
+        t = _lib.FitCentresTiming()
+        _lib.check(_lib.load().vaqhip_last_fit_centres_timing(C.byref(t)))
+        return _struct_dict(t)
+
     def train_moment(self):
         """The second moment of the sampled resident rows (vaqhip_refiner_train_moment): (float64 D x D, its float32
         rounding)."""
